@@ -19,10 +19,18 @@ result rows, on the library's streams (csrc/comm.hip; no torch collective on the
 torch.distributed/gloo carries only the rendezvous, the barriers and the max over ranks).  Every
 step searches the same `--batch` queries on all ranks; partitions_to_search is fixed, so the work of
 a step is fixed and split over the ranks ("strong").  `--multi-gpu replica` times N query-parallel
-copies of the N = 1 workload instead (reported as `secondary` by the default N > 1 run).
+copies of the N = 1 workload instead (reported as `secondary` by the default N > 1 run with `--full`).
 
 The CPU oracle is used here ONLY as (a) the checker of a few result rows and (b) the cpu_baseline
 leg; the timed path is libscann_hip.so through its C ABI.
+
+A plain run does only what the headline figure needs: build the index, warm up, time exactly `--steps`
+steps, print the JSON line (`ms_per_step` = milliseconds of one timed step).  `--full` adds everything
+else the line can carry: the roofline of the dominant kernel (from the HIP events of the timed region and
+a single-stream pass after it), the batch-size sweep, recall10@10, the oracle check of the last timed
+step's rows, the CPU baseline and, at N > 1, the replica secondary; fields it did not measure are null.
+`--dump-outputs DIR` writes the rows of the last timed step (see dump_outputs); the inputs are seeded, so
+the same arguments give the same inputs on every run.
 """
 import argparse
 import ctypes
@@ -95,7 +103,14 @@ def parse():
     p.add_argument("--kmeans-iters", type=int, default=8)
     p.add_argument("--bf-exact", action="store_true",
                    help="bf_dot: exact f32-MFMA kernels only (no bf16 shortlist)")
+    p.add_argument("--full", action="store_true",
+                   help="also measure and check everything beyond the headline figure: roofline, batch sweep, "
+                        "recall, oracle check, CPU baseline, replica secondary (the --no-* options trim it)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the result rows of the last timed step to DIR/*.npy")
     a = p.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        p.error("--steps must be >= 1 and --warmup >= 0")
     a.raw = {key: getattr(a, key) for key in ("workload", "n", "dim", "subspaces", "leaves", "partitions_to_search",
                                               "pre_reorder_k")}
     return resolve_defaults(a)
@@ -129,6 +144,31 @@ def resolve_defaults(a):
 
 def dev_ptr(t):
     return ctypes.c_void_p(t.data_ptr())
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, idx, dist, cnt, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: what a caller of the timed path receives for the last timed step, as
+    out_dir/indices.npy [Q, k] float64 (the uint32 datapoint indices, exact), distances.npy [Q, k] float32 and
+    counts.npy [Q] float64.  Slots past a query's count hold what the library writes there (index 0xFFFFFFFF,
+    distance +inf).  Should the rows exceed `limit` bytes, a fixed seeded sample of the queries is written
+    instead, with its ascending row numbers in rows.npy."""
+    arrays = {"indices": np.asarray(idx).view(np.uint32).astype(np.float64),
+              "distances": np.asarray(dist, np.float32),
+              "counts": np.asarray(cnt).view(np.uint32).astype(np.float64)}
+    nq = arrays["counts"].shape[0]
+    row_bytes = sum(a[:1].nbytes for a in arrays.values()) + 8
+    keep = min(nq, limit // max(row_bytes, 1))
+    if keep < nq:
+        rows = np.sort(np.random.default_rng(0).choice(nq, keep, replace=False))
+        arrays = {name: a[rows] for name, a in arrays.items()}
+        arrays["rows"] = rows.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(arrays)
 
 
 def lib_sha256(hip):
@@ -574,6 +614,8 @@ def main():
                 args.m_local = 0
                 continue
             raise
+        # The kernel-timing events stay on in a plain run too, so the timed region is the same with and without --full
+        # (two-stream runs without them were not faster on the MI355X, and up to 0.75 % slower).
         index.enable_timing(True)
         barrier()
         torch.cuda.synchronize()
@@ -587,14 +629,14 @@ def main():
         kernel_ms_timed, kernel_name = index.last_kernel_ms()
         index.enable_timing(False)
         device_status()
-        # rows of the LAST TIMED step, for the oracle check (the passes below reuse the buffers)
+        # rows of the LAST TIMED step, for --dump-outputs and the oracle check (the passes below reuse the buffers)
         last_out = tuple(t.clone() for t in outs[(args.steps - 1) % n_bufs])
         # The dominant kernel ALONE on the machine, for the roofline: with two caller streams the timed region runs
         # kernels of consecutive batches side by side, so an event pair around one of them also measures its neighbours
         # (C3: 0.52 ms inside the region, 0.35 ms alone; rocprofv3 --kernel-trace agrees with each in its own run).  A
         # short single-stream pass after the timed region, same index, same batches, HIP events on the launch stream.
         kernel_ms = kernel_ms_timed
-        if two_streams and not sharded:
+        if args.full and two_streams and not sharded:
             index.enable_timing(True)
             two_streams = False
             for i in range(min(args.steps, 40)):
@@ -612,10 +654,13 @@ def main():
         log("WARNING: the timed region is only %.3f s (%d steps); raise --steps for a stable number" % (elapsed, args.steps))
     qps = Q * args.steps * (nproc if replica else 1) / elapsed
     last_q = queries_all[((args.steps - 1) % nbatches) * Q:][:Q]
+    if args.dump_outputs and rank == 0:
+        names = dump_outputs(args.dump_outputs, *(t.cpu().numpy() for t in last_out))
+        log("outputs of the last timed step written to %s: %s" % (args.dump_outputs, ", ".join(names)))
 
-    # ---------------- batch-size sweep (batches {1, 100, 1024}, >= 10 reps, median) -----------
+    # ---------------- --full from here on: batch-size sweep (batches {1, 100, 1024}, >= 10 reps, median)
     sweep = None
-    if not args.no_batch_sweep and not replica:
+    if args.full and not args.no_batch_sweep and not replica:
         sweep = {}
         for bsz in (1, 100, Q):
             ts = []
@@ -640,7 +685,7 @@ def main():
     recall = checked = None
     ne = min(args.eval_queries, queries_all.shape[0])
     qe = np.ascontiguousarray(queries_all[:ne])
-    if not args.no_recall and args.workload != "bf_dot" and not replica:
+    if args.full and not args.no_recall and args.workload != "bf_dot" and not replica:
         if sharded:
             # ground truth = exact brute force over every rank's shard (library kernels), merged on rank 0
             qt = torch.from_numpy(qe).to(device)
@@ -689,7 +734,7 @@ def main():
             ti, td, tc = bf.search_batched(qe, k)
             recall = sum(len(set(gi[i].tolist()) & set(ti[i].tolist())) for i in range(ne)) / float(ne * k)
             bf.close()
-    if rank == 0 and nproc == 1 and not sharded:
+    if args.full and rank == 0 and nproc == 1 and not sharded:
         # result rows of the LAST TIMED step checked against the oracle (checker only)
         from oracle import pyoracle as orc
         gi = last_out[0].cpu().numpy().view(np.uint32)
@@ -708,7 +753,7 @@ def main():
 
     # ---------------- CPU baseline: the oracle on this box's host cores (rank 0, N = 1) -----------------
     cpu = None
-    if rank == 0 and nproc == 1 and not sharded and not args.no_cpu_baseline:
+    if args.full and rank == 0 and nproc == 1 and not sharded and not args.no_cpu_baseline:
         from oracle import pyoracle as orc
         threads = orc.max_threads()
 
@@ -743,12 +788,14 @@ def main():
 
     # ---------------- the replica layout as a secondary number of the sharded run ---------------------
     secondary = None
-    if sharded and nproc > 1 and not args.no_secondary:
+    if args.full and sharded and nproc > 1 and not args.no_secondary:
         secondary = replica_secondary(args, torch, dist, hip, synth, trainer, device, local_rank, rank, nproc)
 
     if rank == 0:
-        algo = None
-        if args.workload == "bf_dot" and kernel_name == "bf_stream_kernel":
+        algo = roof = None      # the roofline of the dominant kernel: --full only
+        if not args.full:
+            pass
+        elif args.workload == "bf_dot" and kernel_name == "bf_stream_kernel":
             passes = (Q + 7) // 8
             by = n * dim * 4
             achieved = by * passes / (kernel_ms * 1e-3) / 1e9 if kernel_ms else 0.0
@@ -772,7 +819,7 @@ def main():
             pairs = 1 if args.workload == "ah" else args.partitions_to_search
             roof, algo = scan_roofline(hip, "txh_sharded" if sharded else args.workload, kernel_name, kernel_ms,
                                        scanned, S, K, Q, k, pairs)
-        if roof["frac"] > 1.0:
+        if roof is not None and roof["frac"] > 1.0:
             roof["warning"] = "fraction above 1: the assumed bound is not the binding one"
         if roof is not None:
             roof["kernel_ms_in_timed_region"] = kernel_ms_timed
@@ -804,7 +851,7 @@ def main():
                                       ("1 process/GPU, %d query-parallel replicas of the index (no data-path "
                                        "collective)" % nproc) if replica else "single GPU"},
             "roofline": roof, "algorithmic_hbm": algo, "cpu_baseline": cpu, "batch_sweep": sweep,
-            "secondary": secondary, "lib_sha256": lib_sha256(hip), "src_sha256": src_sha256(),
+            "secondary": secondary, "full": args.full, "lib_sha256": lib_sha256(hip), "src_sha256": src_sha256(),
         }
         if shard_fallback:
             line["config"]["note"] = ("the leaf-sharded layout could not start (%s): replica layout measured "

@@ -4,7 +4,7 @@
 run() {
   v=$1; P=$2; m=$3
   if [ $v = unset ]; then unset SCANN_HIP_MFMA; else export SCANN_HIP_MFMA=$v; fi
-  timeout -k 10 400 python3 bench.py --workload txh --dist clustered --num-points 10000000 --leaves 1000 --partitions-to-search $P \
+  timeout -k 10 400 python3 bench.py --full --workload txh --dist clustered --num-points 10000000 --leaves 1000 --partitions-to-search $P \
       --pre-reorder-k $m --no-cpu-baseline --no-batch-sweep --no-recall 2>/dev/null | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])

@@ -4,7 +4,7 @@ out=${1:-gpurun_out/r01_f_batch_sweep.jsonl}
 : > "$out"
 for w in ah bf_dot "txh --dist clustered --partitions-to-search 10 --pre-reorder-k 1000"; do
   for b in 1 100 1024; do
-    timeout -k 10 280 python3 bench.py --workload $w --batch $b --steps 50 --warmup 5 --no-cpu-baseline >> "$out" 2>> gpurun_out/batch_sweep.err || exit 1
+    timeout -k 10 280 python3 bench.py --full --workload $w --batch $b --steps 50 --warmup 5 --no-cpu-baseline >> "$out" 2>> "$(dirname "$out")/batch_sweep.err" || exit 1
   done
 done
 python3 - "$out" <<'PY'

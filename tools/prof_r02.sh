@@ -20,7 +20,7 @@ cp profiles/traffic.json $O/traffic.json &&
 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_LDS_IDX_ACTIVE SQ_LDS_BANK_CONFLICT SQ_ACTIVE_INST_VALU SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAVE_CYCLES SQ_WAIT_INST_ANY --output-format csv -d $O/pmc_sq -- python3 bench.py --steps 3 --warmup 1 $B > $O/pmc_sq.log 2>&1 &&
 grep -E "Counter_Name|$KERNEL" $(find $O/pmc_sq -name "*counter_collection.csv" | head -1) > $O/${TAG}_pmc_ah_sq.csv &&
 python3 tools/pmc_summary.py $O/${TAG}_pmc_ah_sq.csv $KERNEL > $O/${TAG}_pmc_ah_sq_summary.txt
-python3 bench.py > $O/${TAG}_bench_ah.json 2> $O/bench_ah.err
+python3 bench.py --full > $O/${TAG}_bench_ah.json 2> $O/bench_ah.err
 rm -rf $O/ks $O/pmc_FETCH_SIZE $O/pmc_WRITE_SIZE $O/pmc_sq
 ls -la $O
 cat $O/${TAG}_pmc_ah_sq_summary.txt

@@ -6,8 +6,8 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 TAG=${1:-r02_c}
 O=gpurun_out/${TAG}_rest
 mkdir -p $O
-python3 bench.py --workload bf_dot > $O/${TAG}_bench_bf_dot.json 2> $O/bench_bf.err &&
-python3 bench.py --workload txh --dist clustered --partitions-to-search 10 --pre-reorder-k 1000 > $O/${TAG}_bench_txh_1m.json 2> $O/bench_txh.err &&
+python3 bench.py --full --workload bf_dot > $O/${TAG}_bench_bf_dot.json 2> $O/bench_bf.err &&
+python3 bench.py --full --workload txh --dist clustered --partitions-to-search 10 --pre-reorder-k 1000 > $O/${TAG}_bench_txh_1m.json 2> $O/bench_txh.err &&
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/ks_txh -- python3 bench.py --workload txh --dist clustered --partitions-to-search 10 --pre-reorder-k 1000 --steps 50 --no-cpu-baseline --no-recall --no-batch-sweep > $O/ks_txh.log 2>&1 &&
 cp $(find $O/ks_txh -name "*kernel_stats.csv" | head -1) $O/${TAG}_txh_1m_kernel_stats.csv
 rm -rf $O/ks_txh

@@ -29,9 +29,9 @@ for set in "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY
   f=$(find $O/pmc_sq$i -name "*counter_collection.csv" | head -1)
   [ -n "$f" ] && grep -E "Counter_Name|$KERNEL" $f > $O/${TAG}_pmc_ah_sq$i.csv && python3 tools/pmc_summary.py $O/${TAG}_pmc_ah_sq$i.csv $KERNEL >> $O/${TAG}_pmc_ah_sq_summary.txt
 done
-python3 bench.py > $O/${TAG}_bench_ah_1stream.json 2> $O/bench_ah_1s.err
+python3 bench.py --full > $O/${TAG}_bench_ah_1stream.json 2> $O/bench_ah_1s.err
 unset SCANN_BENCH_STREAMS
-python3 bench.py > $O/${TAG}_bench_ah.json 2> $O/bench_ah.err
+python3 bench.py --full > $O/${TAG}_bench_ah.json 2> $O/bench_ah.err
 rm -rf $O/ks $O/ks1 $O/pmc_FETCH_SIZE $O/pmc_WRITE_SIZE $O/pmc_sq1 $O/pmc_sq2
 ls -la $O
 cat $O/${TAG}_pmc_ah_sq_summary.txt

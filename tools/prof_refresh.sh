@@ -13,9 +13,9 @@ for w in ah bf_dot; do
 done
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/ks_txh -- python3 bench.py --workload txh --dist clustered --partitions-to-search 10 --pre-reorder-k 1000 --steps 20 --no-cpu-baseline --no-recall > $O/ks_txh.log 2>&1
 cp $(find $O/ks_txh -name "*kernel_stats.csv" | head -1) $O/r01_f_txh_1m_kernel_stats.csv
-python3 bench.py > $O/r01_f_bench_ah.json 2> $O/bench_ah.err
-python3 bench.py --workload bf_dot > $O/r01_f_bench_bf_dot.json 2> $O/bench_bf.err
-python3 bench.py --workload txh --dist clustered --partitions-to-search 10 --pre-reorder-k 1000 > $O/r01_f_bench_txh_1m.json 2> $O/bench_txh.err
+python3 bench.py --full > $O/r01_f_bench_ah.json 2> $O/bench_ah.err
+python3 bench.py --full --workload bf_dot > $O/r01_f_bench_bf_dot.json 2> $O/bench_bf.err
+python3 bench.py --full --workload txh --dist clustered --partitions-to-search 10 --pre-reorder-k 1000 > $O/r01_f_bench_txh_1m.json 2> $O/bench_txh.err
 rm -rf $O/ks_* $O/pmc_*
 ls -la $O
 tail -c 600 $O/r01_f_bench_ah.json
