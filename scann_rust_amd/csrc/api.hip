@@ -17,6 +17,7 @@
 #include "bf.h"
 #include "comm.h"
 #include "common.h"
+#include "knobs.h"
 #include "txh.h"
 
 namespace scann {
@@ -584,11 +585,11 @@ int scann::txh_create_checked(scann_hip_ctx *ctx, const scann_hip_txh_desc *d, s
     t.leaf_ids = ah ? nullptr : ix->d_leaf_ids.as<uint32_t>();
     t.codes = exact ? nullptr : ix->d_codes.as<uint32_t>();
     t.codes_sp = nullptr;
+    const Knobs kn = read_knobs();
     // operand planes of the sparse-MFMA prefilter (txh.hip K6e): a second copy of the 4-bit codes, S/2 .. 2 S bytes
     // per point.  SCANN_HIP_SMFMAC=0: not built, the dense integer-MFMA prefilter is used instead.
     {
-        const char *e = std::getenv("SCANN_HIP_SMFMAC");
-        if (!exact && bits == 4 && !(e && std::atoi(e) == 0)) {
+        if (!exact && bits == 4 && kn.smfmac) {
             if ((s = ix->d_codes_sp.ensure((size_t)n * sp_words(S) * 4)) != SCANN_HIP_OK) return bail(s);
             if ((s = launch_codes_sp_build(ix->d_codes.as<uint32_t>(), n, S, ix->d_codes_sp.as<uint32_t>(), ix->stream)) != SCANN_HIP_OK)
                 return bail(s);
@@ -609,10 +610,8 @@ int scann::txh_create_checked(scann_hip_ctx *ctx, const scann_hip_txh_desc *d, s
     t.rows8_uniform = 0;
     t.rows8_scale = t.rows8_emax = 0.0f;
     {
-        int mode = 1;
-        if (const char *e = std::getenv("SCANN_HIP_RERANK_I8")) mode = std::atoi(e);
-        const char *store = std::getenv("SCANN_HIP_RERANK_STORE");
-        const bool fp8 = store && std::strcmp(store, "fp8") == 0;
+        const int mode = kn.rerank_i8;
+        const bool fp8 = kn.rerank_fp8;
         const bool want = d->data && !exact && d->distance_measure == SCANN_HIP_SQUARED_L2 && (d->dim & 15u) == 0 &&
                           (mode == 2 || (mode == 1 && d->n_rows >= 65536));
         if (want) {
@@ -644,9 +643,8 @@ int scann::txh_create_checked(scann_hip_ctx *ctx, const scann_hip_txh_desc *d, s
                 // bound is strict because a coarser common scale widens every bracket: on the clustered 10M x 128 set
                 // (per-row maxima 25 % apart, candidates nearly equidistant) the shortlists outgrew the fast path and
                 // the step went from 1.43 to 1.86 ms.  SCANN_HIP_RERANK_UNIFORM=0: always per-row, 2: always one scale.
-                const char *ue = std::getenv("SCANN_HIP_RERANK_UNIFORM");
-                const double spread = (ue && std::atoi(ue) == 2) ? 1e30 : 1.02;
-                if (!(ue && std::atoi(ue) == 0)) {
+                const double spread = kn.rerank_uniform == 2 ? 1e30 : 1.02;
+                if (kn.rerank_uniform != 0) {
                     std::vector<float> meta((size_t)d->n_rows * 2);
                     if (hipMemcpy(meta.data(), ix->d_rows8_meta.p, meta.size() * 4, hipMemcpyDeviceToHost) != hipSuccess)
                         return bail(fail(SCANN_HIP_INTERNAL, "int8 row meta copy failed"));
@@ -697,39 +695,56 @@ int scann_hip_txh_create(scann_hip_ctx *ctx, const scann_hip_txh_desc *d, scann_
     return scann::txh_create_checked(ctx, d, out, SCANN_HIP_INVALID_ARGUMENT);
 }
 
-// SCANN_HIP_SMALL=0 turns the small-batch pipeline off (read per call: tests flip it)
-static bool small_batch_enabled() {
-    const char *e = std::getenv("SCANN_HIP_SMALL");
-    return !(e && std::atoi(e) == 0);
-}
-
-// ---- per-call parameter resolution --------------------------------------------------
-struct TxhCallParams {
-    uint32_t P, m, k, cap, st, scap;
-    int exact_reorder;
-    int no_threshold;
-    int small;   // small-batch pipeline (txh.hip "Small batches"); 2 = the wide one ("Few queries, long streams")
-    uint32_t wide_cap2;
-};
-
+// ---- per-call planning --------------------------------------------------------------
 static uint64_t max_stream(const scann_hip_index *ix, uint32_t P) {
     uint64_t s = 0;
     for (uint32_t i = 0; i < P && i < ix->local_sizes_desc.size(); ++i) s += ix->local_sizes_desc[i];
     return s;
 }
 
-static int resolve_params(const scann_hip_index *ix, uint32_t k, const scann_hip_search_opts *o,
-                          bool full_cap, TxhCallParams *out, uint32_t nq = 0xFFFFFFFFu, bool allow_wide = true) {
+// One-launch forms of the small and wide pipelines: stream positions per workgroup and workgroups per query.
+static void plan_small_launch(const TxhIndexDev &t, const Knobs &kn, TxhPlan *p) {
+    if (p->pipeline == TxhPipeline::Wide) {
+        // 1024 x rep stream positions per workgroup, rep <= kWideRep chosen so that one wave of workgroups (256 CUs)
+        // covers the stream.  (ADC scans only: an exact scan wants a row per thread and ~128 rows per workgroup --
+        // hundreds of workgroups per query that would each repeat the leaf selection; Partitioned mode keeps the small
+        // pipeline.)
+        p->chunk = kFusedChunk * std::min<uint32_t>(kWideRep, std::max(1u, ceil_div_u32(p->cap, 256u * kFusedChunk)));
+        p->grid = std::max(1u, ceil_div_u32(p->cap, p->chunk));
+        p->fused = false;
+        return;
+    }
+    // One launch when the grid stays small (SCANN_HIP_FUSED=0: always three).  Exact scans read a whole row per
+    // thread, 64 cache lines per wave instruction: they are bound by the L1's line-request rate of ONE compute unit,
+    // so their workgroups take only 128 positions each (more compute units share the rows); ADC scans read 16
+    // coalesced code bytes per point and take 1024 -- but rebuild the tables per leaf one after the other, so tree
+    // indexes with several leaves per query keep the three-launch form, whose scan builds every leaf's table in its
+    // own workgroup.
+    p->chunk = kFusedChunk;
+    if (t.exact_scan) p->chunk = std::min(kFusedChunk, std::max(128u, (ceil_div_u32(p->cap, 256u) + 127u) & ~127u));
+    p->grid = std::max(1u, ceil_div_u32(p->cap, p->chunk));
+    p->fused = kn.fused && p->P <= kDecodeStage && (uint64_t)p->nq * p->grid <= kFusedMaxWgs &&
+               (t.exact_scan || p->P == 1);
+}
+
+// Every path decision of a tree / AH search of nq queries.  retry: the host entry's second attempt after a
+// threshold or buffer miss -- a candidate slot for every scanned point, and not the wide pipeline.  widest: the
+// widest pipeline the caller takes (Staged for callers that only size buffers or run the local stage).
+static int plan_txh_search(const scann_hip_index *ix, uint32_t k, const scann_hip_search_opts *o, uint32_t nq,
+                           bool retry, TxhPipeline widest, const Knobs &kn, TxhPlan *out) {
     scann_hip_search_opts def;
     scann_hip_search_opts_default(&def);
     if (!o) o = &def;
+    const TxhIndexDev &t = ix->tx;
+    bool full_cap = retry;
+    if (retry && widest == TxhPipeline::Wide) widest = TxhPipeline::Small;
     uint32_t P = o->partitions_to_search ? o->partitions_to_search : ix->default_P;
-    P = std::min(P, ix->tx.L);  // tree_partitioner.rs:214
-    if (ix->tx.ah_mode) P = 1;
+    P = std::min(P, t.L);  // tree_partitioner.rs:214
+    if (t.ah_mode) P = 1;
     if (P > kMaxPartitionsToSearch)
         return fail(SCANN_HIP_UNIMPLEMENTED, "partitions_to_search > 4096");
-    const bool exact_reorder = o->exact_reorder && !ix->tx.exact_scan;   // the scan's distances ARE exact
-    if (ix->tx.exact_scan) {
+    const bool exact_reorder = o->exact_reorder && !t.exact_scan;   // the scan's distances ARE exact
+    if (t.exact_scan) {
         full_cap = true;   // dense key lists: one slot per scanned row, no threshold
         if (o->allow_bitmap) return fail(SCANN_HIP_UNIMPLEMENTED, "the exact leaf scan takes no filter");
     }
@@ -746,53 +761,151 @@ static int resolve_params(const scann_hip_index *ix, uint32_t k, const scann_hip
         return fail(SCANN_HIP_UNIMPLEMENTED,
                     "pre-reorder candidate count " + std::to_string(m) + " exceeds " +
                         std::to_string(kMaxPreReorderK));
-    if (exact_reorder && !ix->tx.rows)  // hasher.rs:194-197
+    if (exact_reorder && !t.rows)  // hasher.rs:194-197
         return fail(SCANN_HIP_FAILED_PRECONDITION, "Dataset not stored");
-    const uint64_t ms = std::min<uint64_t>(std::max<uint64_t>(1, max_stream(ix, P)), 0xFFFFFFFFull);
-    uint32_t st, scap;
-    sample_plan(ms, P, &st, &scap);
+    const uint64_t stream = std::max<uint64_t>(1, max_stream(ix, P));
+    const uint64_t ms = std::min<uint64_t>(stream, 0xFFFFFFFFull);
+    TxhPlan p{};
+    p.nq = nq;
+    p.P = P;
+    p.m = m;
+    p.k = k;
+    p.exact_reorder = exact_reorder;
+    sample_plan(ms, P, &p.st, &p.scap);
     // A handful of queries over a short stream: three launches with dense candidate lists instead of
     // the batched pipeline (SCANN_HIP_SMALL=0 disables).  Unsharded indexes only: stream positions are
     // list slots, and a shard's local leaves leave holes in them.
-    const bool small_on = small_batch_enabled();
-    out->small = (small_on && nq <= kSmallBatch && !ix->sharded && m <= kSmallMaxCandidates &&
-                  k <= 64 && ms <= kSmallMaxStream && ix->tx.L <= 4096) ? 1 : 0;
+    p.pipeline = TxhPipeline::Staged;
+    if (widest != TxhPipeline::Staged && kn.small && nq <= kSmallBatch && !ix->sharded && m <= kSmallMaxCandidates &&
+        k <= 64 && ms <= kSmallMaxStream && t.L <= 4096)
+        p.pipeline = TxhPipeline::Small;
     // Fewer queries still, over a long stream: the wide pipeline (three launches, every stage spread over the chip).
     // Its scan rebuilds the tables per leaf inside a workgroup of 1024 stream positions: leaves of >= 512 points
     // (or one leaf); ADC scans only (Partitioned mode, 4 queries over 20 leaves of 1M x 128: 0.097 ms on the small-batch
     // pipeline, 0.147 through this one).  Streams of >= 8 m points: below that most of the stream is candidates anyway.
     // SCANN_HIP_WIDE: 0 = never, 2 = whenever the limits allow (tests), else from kWideMinStream points.
-    out->wide_cap2 = 0;
     {
-        int mode = 1;
-        if (const char *e = std::getenv("SCANN_HIP_WIDE")) mode = std::atoi(e);
-        const bool limits = small_on && allow_wide && mode != 0 && nq <= kWideBatch && !ix->sharded && m >= 1 &&
-                            m <= kWideMaxCandidates && k <= 64 && ms <= kWideMaxStream && ix->tx.L <= 4096 && P <= 512 &&
-                            !ix->tx.exact_scan;
-        const bool long_leaves = P == 1 || ix->tx.n_local / std::max(1u, ix->tx.L) >= 512;
+        const bool limits = widest == TxhPipeline::Wide && kn.small && kn.wide != 0 && nq <= kWideBatch &&
+                            !ix->sharded && m >= 1 && m <= kWideMaxCandidates && k <= 64 && ms <= kWideMaxStream &&
+                            t.L <= 4096 && P <= 512 && !t.exact_scan;
+        const bool long_leaves = P == 1 || t.n_local / std::max(1u, t.L) >= 512;
         const bool pays = ms >= kWideMinStream && ms >= 8ull * m && long_leaves;
-        if (limits && (mode == 2 || pays)) {
-            out->small = 2;
-            out->wide_cap2 = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(ms, 3ull * m + 1024), 16384);
+        if (limits && (kn.wide == 2 || pays)) {
+            p.pipeline = TxhPipeline::Wide;
+            p.wide_cap2 = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(ms, 3ull * m + 1024), 16384);
         }
     }
-    if (out->small) full_cap = true;
+    if (p.pipeline != TxhPipeline::Staged) full_cap = true;
     uint64_t cap = ms;
     if (!full_cap) {
         // upper bound of the survivors of the sampled threshold (rank j of a stride-st sample)
-        const uint32_t j = sample_rank(m, st);
-        cap = (uint64_t)((double)j + 8.0 * std::sqrt((double)j) + 16.0) * st + 256;
+        const uint32_t j = sample_rank(m, p.st);
+        cap = (uint64_t)((double)j + 8.0 * std::sqrt((double)j) + 16.0) * p.st + 256;
         cap = std::min(std::max<uint64_t>(cap, m), ms);
     }
-    out->st = st;
-    out->scap = scap;
-    out->P = P;
-    out->m = m;
-    out->k = k;
-    out->cap = (uint32_t)std::min<uint64_t>(cap, 0xFFFFFFFFull);
-    out->exact_reorder = exact_reorder ? 1 : 0;
-    out->no_threshold = full_cap ? 1 : 0;
+    p.cap = (uint32_t)std::min<uint64_t>(cap, 0xFFFFFFFFull);
+    p.no_threshold = full_cap;
+    p.small_max_leaf = ix->local_sizes_desc.empty() ? 0u : ix->local_sizes_desc[0];
+    if (p.pipeline != TxhPipeline::Staged) plan_small_launch(t, kn, &p);
+
+    const uint32_t L = t.L;
+    // sample tiles: enough of them to fill the chip (the sample pass is 1/st of the scan)
+    const uint64_t quads = ((uint64_t)nq * P + 3) / 4;
+    const uint32_t tp = scan_tile_points(t);
+    const uint64_t chunks = std::max<uint64_t>(1, ((uint64_t)p.scap + tp - 1) / tp);
+    p.sqpt = kScanQuadsPerTile;
+    while (p.sqpt > 2 && chunks * ((quads + p.sqpt - 1) / p.sqpt) < 4096) p.sqpt >>= 1;
+    // scan tiles: the largest quad group that still yields ~4 tiles per resident workgroup
+    // (small shards and small batches would otherwise leave most of the chip idle)
+    const uint64_t all_chunks = t.n_local / tp + L;
+    const uint64_t quads_per_leaf = std::max<uint64_t>(1, quads / std::max(1u, L));
+    p.qpt = kScanQuadsPerTile;
+    while (p.qpt > 8 && all_chunks * ((quads_per_leaf + p.qpt - 1) / p.qpt) < 6144) p.qpt >>= 1;
+    // long leaves scanned by many queries (AsymmetricHasher mode, few big partitions): tables
+    // resident in LDS over a range of chunks (adc_scan_res_kernel); needs 4-bit codes with
+    // S <= 32.  With few quads per leaf (typical Tree-X-Hybrid batches: measured at 10M / 1000
+    // leaves) the per-chunk kernel is as fast or faster.
+    const uint64_t rtp = (uint64_t)kResThreads * kScanPPT;
+    const uint64_t res_chunks_per_leaf = std::max<uint64_t>(1, (t.n_local / std::max(1u, L)) / rtp);
+    const uint64_t qgroups = std::max<uint64_t>(1, (quads_per_leaf + kResQuads - 1) / kResQuads);
+    const uint64_t units = (t.n_local / rtp + L) * qgroups;       // (chunk, quad group) pairs
+    // a tile must cover >= 8 chunks to amortise its table load, and there must be >= 2 tiles
+    // per resident workgroup (small shards: measured at 125k-500k rows)
+    p.res_cl = (uint32_t)std::min<uint64_t>(64, std::max<uint64_t>(8, units / 4096));
+    const bool res_layout = t.code_bits == 4 && t.S <= 32;
+    bool resident = res_layout && res_chunks_per_leaf >= 8 && quads_per_leaf >= 32 && units / p.res_cl >= 1536;
+    // SCANN_HIP_RESIDENT: 0 = never, 2 = whenever the code layout allows (tests), else the heuristic
+    if (kn.resident == 0) resident = false;
+    if (kn.resident == 2) resident = res_layout;
+    if (kn.res_cl) p.res_cl = kn.res_cl;
+    // Integer-MFMA prefilter + exact refine (txh.hip K6d): 4-bit codes, a filter bound to prove
+    // against, and enough pairs per leaf to fill 32-column MFMA tiles (a leaf scanned by few
+    // queries would leave most columns empty; the LDS-gather kernels take those).
+    // Leaves scanned by 8-24 queries (2-5 quads: typical Tree-X-Hybrid batches) take the 16-column form
+    // (adc_mfma16_kernel); fewer than that and the LDS-gather kernel wins.
+    const bool mfma_ok = t.code_bits == 4 && !p.no_threshold && !t.exact_scan;
+    // The prefilter pays while the wanted candidates are a small share of the scanned stream: every
+    // survivor (~1.5-2.4 m) is staged, flushed and recomputed by the refine.  Measured: 1M x 128 flat,
+    // m = 5000 (0.5 %): 2.7x faster than the gather scan; 10M x 128 / 1000 leaves, m / stream 0.1-0.6 %:
+    // steps 1.1-1.4x faster; 1-3 % (P = 10 or 25 with m = 8192): 1.1-1.2x slower.
+    const bool sparse = (uint64_t)m * 128 <= stream;
+    TxhScan mfma = TxhScan::Gather;   // (Gather: no prefilter)
+    if (mfma_ok && sparse) mfma = quads_per_leaf >= 6 ? TxhScan::Mfma32 : quads_per_leaf >= 2 ? TxhScan::Mfma16 : TxhScan::Gather;
+    // SCANN_HIP_MFMA: 0 = never, 2 / 3 = the 32- / 16-column form whenever the code layout allows (tests),
+    // else the heuristic
+    if (kn.mfma == 0) mfma = TxhScan::Gather;
+    if (kn.mfma == 2) mfma = mfma_ok ? TxhScan::Mfma32 : TxhScan::Gather;
+    if (kn.mfma == 3) mfma = mfma_ok ? TxhScan::Mfma16 : TxhScan::Gather;
+    // With the operand planes in the index the 32-pair form runs on the 2:4-sparse MFMA (SCANN_HIP_SMFMAC=0 at this
+    // call keeps the dense instruction: tests compare the two) -- and takes over from 8 pairs per leaf, whatever
+    // m / stream is: at 10M x 128, 1000 leaves, 1024 queries, P = 10 (10 pairs per leaf: tiles a third full)
+    // m = 1000 / 4000 / 8192 run 0.68 / 0.95 / 1.29 ms per step on it against 0.88 / 1.09 / 1.61 ms on the 16-pair
+    // dense form / the f32 gather scan the rules above pick (P = 25 / 50 / 100 at m = 1000: 0.94 / 1.11 / 1.44 ms
+    // against round 2's 1.12 / 1.41 / 1.91).
+    // (long leaves only -- an item is up to 2048 points of a leaf, and its fixed costs, the table fragments and the
+    // flush, want most of that: at 1M x 128 / 1000 leaves of 1000 points the gather scan's 0.08 ms beats 0.13 ms)
+    if (mfma_ok && t.codes_sp && quads_per_leaf >= 2 && t.n_local / std::max(1u, L) >= 4096 && kn.smfmac &&
+        kn.mfma != 0 && kn.mfma != 3)
+        mfma = TxhScan::Smfmac;
+    if (mfma == TxhScan::Mfma32 && t.codes_sp && kn.smfmac) mfma = TxhScan::Smfmac;   // (forced 32-pair form, fewer pairs per leaf)
+    p.scan = t.exact_scan ? TxhScan::Exact : mfma != TxhScan::Gather ? mfma : resident ? TxhScan::Resident : TxhScan::Gather;
+    if (txh_scan_is_mfma(p.scan)) {
+        // survivors of the integer bound: the f32 filter's (<= cap) plus the quantisation margin
+        // (the margin's share is independent of m -- the points within 17 table steps above the bound -- and in
+        // the dense nearest leaves of a tree index it can be several thousand: a generous floor)
+        p.cap32 = (uint32_t)std::min<uint64_t>(ms, (uint64_t)p.cap * 4 + 16384);
+    }
+    // the sparse kernel's flush: lanes walk their own words on flat hashers, word-parallel on tree indexes
+    p.sp_words = kn.sp_words < 0 ? !t.ah_mode : kn.sp_words != 0;
+    // The survivors' codes travel with their positions for flat hashers: their ~12 k survivors per query
+    // are spread over the whole code array (random 16-byte gathers from 16 MB: refine 145 -> 65 us at
+    // C3).  In a tree index the survivors sit densely in the query's nearest leaves, the gathers hit
+    // L2, and writing the codes only costs the scan (10M x 128, P = 25 / 50: step +3.5 %).
+    p.codes_in_list = t.ah_mode != 0;
+    p.thr_ties = kn.thr_ties;
+    // a bound in the low tail of a long sample: threshold_tail_kernel
+    p.thr_tail = kn.thr_tail && !p.no_threshold && sample_rank(m, p.st) <= kThrTailMaxRank && p.scap > 4096;
+    p.select_direct = kn.select_direct;
+    // int8 re-rank filter: lists of a few hundred candidates and more
+    p.use_i8 = t.rows8 && exact_reorder && m >= kn.rerank_i8_min && m > 4 * k;
+    p.local_prune = kn.local_prune;
+    *out = p;
     return SCANN_HIP_OK;
+}
+
+// The kernel scann_hip_index_last_kernel_ms names for a search run on `p`.  pinned: the host entry's small / wide
+// pipeline with queries and results in pinned memory; every other call is named by its batched-pipeline scan (also
+// when a device entry point or staged outputs run it on a small pipeline).
+static const char *txh_kernel_name(const TxhPlan &p, bool pinned) {
+    if (pinned) return p.pipeline == TxhPipeline::Wide ? "wide_scan_kernel" : "small_scan_kernel";
+    switch (p.scan) {
+        case TxhScan::Exact: return "leaf_exact_scan_kernel";
+        case TxhScan::Mfma16: return "adc_mfma16_kernel";
+        case TxhScan::Smfmac: return "adc_smfmac_kernel";
+        case TxhScan::Mfma32: return "adc_mfma_kernel";
+        case TxhScan::Resident: return "adc_scan_res_kernel";
+        default: return "adc_scan_kernel";
+    }
 }
 
 }  // extern "C"
@@ -802,28 +915,27 @@ int scann::txh_resolve_m(scann_hip_index *ix, uint32_t k, const scann_hip_search
     scann_hip_search_opts o;
     if (opts) o = *opts; else scann_hip_search_opts_default(&o);
     o.exact_reorder = 1;
-    TxhCallParams p;
-    SCANN_TRY(resolve_params(ix, k, &o, false, &p));
+    TxhPlan p;
+    SCANN_TRY(plan_txh_search(ix, k, &o, 0, false, TxhPipeline::Staged, read_knobs(), &p));
     *out_m = p.m;
     return SCANN_HIP_OK;
 }
 
 extern "C" {
 
+// Buffers of the plan p (the arena re-places everything when one grows), bound into *w.
 // allow_bytes: size of an allow-bitmap the caller will copy into s.allow (0 = none)
-static int ensure_txh_workspace(scann_hip_index *ix, TxhWorkspace &s, uint32_t nq, const TxhCallParams &p,
-                                bool own_queries, uint32_t q_stride, bool own_outputs,
-                                TxhWork *w, size_t allow_bytes = 0) {
+static int ensure_txh_workspace(scann_hip_index *ix, TxhWorkspace &s, const TxhPlan &p, bool own_queries,
+                                uint32_t q_stride, bool own_outputs, TxhWork *w, size_t allow_bytes = 0) {
     const TxhIndexDev &t = ix->tx;
-    const uint32_t L = t.L, P = p.P, m = std::max(1u, p.m), k = std::max(1u, p.k);
+    const uint32_t nq = p.nq, L = t.L, P = p.P, m = std::max(1u, p.m), k = std::max(1u, p.k);
     const uint64_t max_slots64 = (uint64_t)nq * P + 3ull * L + 4;
     if (max_slots64 > 0xFFFFFFF0ull)
         return fail(SCANN_HIP_RESOURCE_EXHAUSTED, "batch x partitions_to_search exceeds the pair table (2^32 slots)");
     const uint32_t max_slots = (uint32_t)max_slots64;
     const uint32_t max_quads = max_slots / 4 + 1;
-    // (per-candidate arrays sized for THIS call's pre_reorder_k; the arena re-places everything when one grows)
-    const uint32_t m_al = m;
-    const uint64_t cap_al = p.cap;
+    const bool mfma = txh_scan_is_mfma(p.scan), small = p.pipeline != TxhPipeline::Staged,
+               wide = p.pipeline == TxhPipeline::Wide;
     if (allow_bytes) s.want(s.allow, allow_bytes);
     if (own_queries) s.want(s.queries, (size_t)nq * q_stride * 4);
     if (!t.ah_mode) s.want(s.cdist, (size_t)nq * L * 4);
@@ -847,148 +959,34 @@ static int ensure_txh_workspace(scann_hip_index *ix, TxhWorkspace &s, uint32_t n
     s.want(s.lutq, (size_t)max_quads * t.S * t.kp * 4 * 4);
     s.want(s.thr, (size_t)nq * 8);
     s.want(s.cand_cnt, (size_t)nq * 4);
-    s.want(s.cand, (size_t)nq * cap_al * 8);
-    s.want(s.cand_key, (size_t)nq * m_al * 8);
-    s.want(s.cand_idx, (size_t)nq * m_al * 4);
-    s.want(s.cand_dist, (size_t)nq * m_al * 4);
-    s.want(s.cand_exact, (size_t)nq * m_al * 4);
-    s.want(s.cand_row, (size_t)nq * m_al * 4);
+    s.want(s.cand, (size_t)nq * p.cap * 8);
+    s.want(s.cand_key, (size_t)nq * m * 8);
+    s.want(s.cand_idx, (size_t)nq * m * 4);
+    s.want(s.cand_dist, (size_t)nq * m * 4);
+    s.want(s.cand_exact, (size_t)nq * m * 4);
+    s.want(s.cand_row, (size_t)nq * m * 4);
     s.want(s.cand_count, (size_t)nq * 4);
     if (own_outputs) {
         s.want(s.out_idx, (size_t)nq * k * 4);
         s.want(s.out_dist, (size_t)nq * k * 4);
         s.want(s.out_count, (size_t)nq * 4);
     }
-    w->nq = nq;
-    w->q_stride = q_stride;
-    w->P = P;
-    w->m = p.m;
-    w->k = p.k;
-    w->cap = p.cap;
-    w->exact_reorder = p.exact_reorder;
-    w->no_threshold = p.no_threshold;
-    w->small = (uint32_t)p.small;
-    w->small_done = nullptr;
-    w->small_seq = 0;
-    w->small_tickets = nullptr;
-    w->small_max_leaf = ix->local_sizes_desc.empty() ? 0u : ix->local_sizes_desc[0];
-    w->need_sorted_cands = 0;
-    w->allow = nullptr;
-    w->allow_bits = 0;
-    w->st = p.st;
-    w->scap = p.scap;
-    {   // sample tiles: enough of them to fill the chip (the sample pass is 1/st of the scan)
-        const uint64_t quads = ((uint64_t)nq * P + 3) / 4;
-        const uint32_t tp = scan_tile_points(t);
-        const uint64_t chunks = std::max<uint64_t>(1, ((uint64_t)p.scap + tp - 1) / tp);
-        uint32_t qpt = kScanQuadsPerTile;
-        while (qpt > 2 && chunks * ((quads + qpt - 1) / qpt) < 4096) qpt >>= 1;
-        if (const char *e = std::getenv("SCANN_HIP_SQPT")) qpt = (uint32_t)std::max(1, std::atoi(e));
-        w->sqpt = qpt;
-        // scan tiles: the largest quad group that still yields ~4 tiles per resident workgroup
-        // (small shards and small batches would otherwise leave most of the chip idle)
-        const uint64_t all_chunks = t.n_local / tp + L;
-        const uint64_t quads_per_leaf = std::max<uint64_t>(1, quads / std::max(1u, L));
-        uint32_t sq = kScanQuadsPerTile;
-        while (sq > 8 && all_chunks * ((quads_per_leaf + sq - 1) / sq) < 6144) sq >>= 1;
-        w->qpt = sq;
-        if (const char *e = std::getenv("SCANN_HIP_QPT")) w->qpt = (uint32_t)std::max(1, std::atoi(e));
-        // long leaves scanned by many queries (AsymmetricHasher mode, few big partitions): tables
-        // resident in LDS over a range of chunks (adc_scan_res_kernel); needs 4-bit codes with
-        // S <= 32.  With few quads per leaf (typical Tree-X-Hybrid batches: measured at 10M / 1000
-        // leaves) the per-chunk kernel is as fast or faster.
-        const uint64_t rtp = (uint64_t)kResThreads * kScanPPT;
-        const uint64_t res_chunks_per_leaf = std::max<uint64_t>(1, (t.n_local / std::max(1u, L)) / rtp);
-        const uint64_t qgroups = std::max<uint64_t>(1, (quads_per_leaf + kResQuads - 1) / kResQuads);
-        const uint64_t units = (t.n_local / rtp + L) * qgroups;       // (chunk, quad group) pairs
-        // a tile must cover >= 8 chunks to amortise its table load, and there must be >= 2 tiles
-        // per resident workgroup (small shards: measured at 125k-500k rows)
-        w->res_cl = (uint32_t)std::min<uint64_t>(64, std::max<uint64_t>(8, units / 4096));
-        w->resident = (t.code_bits == 4 && t.S <= 32 && res_chunks_per_leaf >= 8 && quads_per_leaf >= 32 &&
-                       units / w->res_cl >= 1536) ? 1u : 0u;
-        // SCANN_HIP_RESIDENT: 0 = never, 2 = whenever the code layout allows (tests), else the heuristic
-        if (const char *e = std::getenv("SCANN_HIP_RESIDENT")) {
-            const int v = std::atoi(e);
-            if (v == 0) w->resident = 0u;
-            if (v == 2) w->resident = (t.code_bits == 4 && t.S <= 32) ? 1u : 0u;
-        }
-        if (const char *e = std::getenv("SCANN_HIP_RES_CL")) w->res_cl = (uint32_t)std::max(1, std::atoi(e));
-        // Integer-MFMA prefilter + exact refine (txh.hip K6d): 4-bit codes, a filter bound to prove
-        // against, and enough pairs per leaf to fill 32-column MFMA tiles (a leaf scanned by few
-        // queries would leave most columns empty; the LDS-gather kernels take those).
-        // Leaves scanned by 8-24 queries (2-5 quads: typical Tree-X-Hybrid batches) take the 16-column form
-        // (adc_mfma16_kernel); fewer than that and the LDS-gather kernel wins.
-        const bool mfma_ok = t.code_bits == 4 && !p.no_threshold && !t.exact_scan;
-        // The prefilter pays while the wanted candidates are a small share of the scanned stream: every
-        // survivor (~1.5-2.4 m) is staged, flushed and recomputed by the refine.  Measured: 1M x 128 flat,
-        // m = 5000 (0.5 %): 2.7x faster than the gather scan; 10M x 128 / 1000 leaves, m / stream 0.1-0.6 %:
-        // steps 1.1-1.4x faster; 1-3 % (P = 10 or 25 with m = 8192): 1.1-1.2x slower.
-        const uint64_t stream = std::max<uint64_t>(1, max_stream(ix, P));
-        const bool sparse = (uint64_t)p.m * 128 <= stream;
-        w->mfma = !(mfma_ok && sparse) ? 0u : quads_per_leaf >= 6 ? 1u : quads_per_leaf >= 2 ? 2u : 0u;
-        // SCANN_HIP_MFMA: 0 = never, 2 / 3 = the 32- / 16-column form whenever the code layout allows (tests),
-        // else the heuristic
-        if (const char *e = std::getenv("SCANN_HIP_MFMA")) {
-            const int v = std::atoi(e);
-            if (v == 0) w->mfma = 0u;
-            if (v == 2) w->mfma = mfma_ok ? 1u : 0u;
-            if (v == 3) w->mfma = mfma_ok ? 2u : 0u;
-        }
-        // With the operand planes in the index the 32-pair form runs on the 2:4-sparse MFMA (SCANN_HIP_SMFMAC=0 at this
-        // call keeps the dense instruction: tests compare the two) -- and takes over from 8 pairs per leaf, whatever
-        // m / stream is: at 10M x 128, 1000 leaves, 1024 queries, P = 10 (10 pairs per leaf: tiles a third full)
-        // m = 1000 / 4000 / 8192 run 0.68 / 0.95 / 1.29 ms per step on it against 0.88 / 1.09 / 1.61 ms on the 16-pair
-        // dense form / the f32 gather scan the rules above pick (P = 25 / 50 / 100 at m = 1000: 0.94 / 1.11 / 1.44 ms
-        // against round 2's 1.12 / 1.41 / 1.91).
-        // (long leaves only -- an item is up to 2048 points of a leaf, and its fixed costs, the table fragments and the
-        // flush, want most of that: at 1M x 128 / 1000 leaves of 1000 points the gather scan's 0.08 ms beats 0.13 ms)
-        if (mfma_ok && t.codes_sp && quads_per_leaf >= 2 && t.n_local / std::max(1u, L) >= 4096) {
-            const char *e = std::getenv("SCANN_HIP_SMFMAC");
-            const char *f = std::getenv("SCANN_HIP_MFMA");
-            if (!(e && std::atoi(e) == 0) && !(f && (std::atoi(f) == 0 || std::atoi(f) == 3))) w->mfma = 3u;
-        }
-        if (w->mfma == 1 && t.codes_sp) {   // (forced 32-pair form, fewer pairs per leaf)
-            const char *e = std::getenv("SCANN_HIP_SMFMAC");
-            if (!(e && std::atoi(e) == 0)) w->mfma = 3u;
-        }
-        if (w->mfma) w->resident = 0u;
+    if (p.use_i8) {
+        s.want(s.rr_lb, (size_t)nq * m * 4);
+        s.want(s.rr_ub, (size_t)nq * m * 4);
     }
-    // int8 re-rank filter: lists of a few hundred candidates and more (SCANN_HIP_RERANK_I8_MIN overrides)
-    {
-        uint32_t min_m = 512;
-        if (const char *e = std::getenv("SCANN_HIP_RERANK_I8_MIN")) min_m = (uint32_t)std::max(1, std::atoi(e));
-        w->use_i8 = (t.rows8 && p.exact_reorder && p.m >= min_m && p.m > 4 * p.k) ? 1u : 0u;
-        w->rr_lb = w->rr_ub = nullptr;
-        if (w->use_i8) {
-            s.want(s.rr_lb, (size_t)nq * m_al * 4);
-            s.want(s.rr_ub, (size_t)nq * m_al * 4);
-        }
-    }
-    w->lut8 = nullptr;
-    w->lut8_meta = nullptr;
-    w->mfma_thr1 = nullptr;
-    w->cand32 = nullptr;
-    w->cand32_codes = nullptr;
-    w->cand32_cnt = nullptr;
-    w->cap32 = 0;
-    if (w->mfma) {
-        // survivors of the integer bound: the f32 filter's (<= cap) plus the quantisation margin
-        const uint64_t ms2 = std::min<uint64_t>(std::max<uint64_t>(1, max_stream(ix, P)), 0xFFFFFFFFull);
-        // (the margin's share is independent of m -- the points within 17 table steps above the bound -- and in
-        // the dense nearest leaves of a tree index it can be several thousand: a generous floor)
-        const uint64_t cap32 = std::min<uint64_t>(ms2, (uint64_t)p.cap * 4 + 16384);
+    if (mfma) {
         s.want(s.lut8, (size_t)max_slots * t.S * 16 + 64);
         s.want(s.lut8_meta, (size_t)(max_slots + 4) * 16);
         s.want(s.mfma_thr1, (size_t)(max_slots + 4) * 4);
-        const uint64_t cap32_al = std::min<uint64_t>(ms2, cap_al * 4 + 16384);   // (allocation; the stride stays cap32)
-        s.want(s.cand32, (size_t)nq * cap32_al * 4);
+        s.want(s.cand32, (size_t)nq * p.cap32 * 4);
         // flat hashers: the survivors' packed codes (dense prefilter) or plane rows (sparse prefilter) travel with them
-        if (t.ah_mode) s.want(s.cand32_codes, (size_t)nq * cap32_al * std::max(t.S / 8, w->mfma == 3 ? sp_words(t.S) : 0u) * 4);
+        if (t.ah_mode)
+            s.want(s.cand32_codes, (size_t)nq * p.cap32 * std::max(t.S / 8, p.scan == TxhScan::Smfmac ? sp_words(t.S) : 0u) * 4);
         s.want(s.cand32_cnt, (size_t)nq * 4);
-        w->cap32 = (uint32_t)cap32;
     }
-    if (p.small) s.want(s.small_tickets, 64 * 4);
-    if (p.small == 2) {
+    if (small) s.want(s.small_tickets, 64 * 4);
+    if (wide) {
         s.want(s.wide_min, (size_t)nq * p.cap * 4);
         s.want(s.wide_ckey, (size_t)nq * p.wide_cap2 * 8);
         s.want(s.wide_ceb, (size_t)nq * p.wide_cap2 * 4);
@@ -996,16 +994,19 @@ static int ensure_txh_workspace(scann_hip_index *ix, TxhWorkspace &s, uint32_t n
         s.want(s.wide_cnt, 64 * 4);
     }
     SCANN_TRY(s.commit());
+    *w = TxhWork{};
+    static_cast<TxhPlan &>(*w) = p;
+    w->q_stride = q_stride;
     w->queries = s.queries.as<float>();
     w->cdist = s.cdist.as<float>();
     w->tokens = s.tokens.as<uint32_t>();
     w->token_dists = s.token_dists.as<float>();
     w->vbase = s.vbase.as<uint32_t>();
-    if (w->use_i8) {
+    if (p.use_i8) {
         w->rr_lb = s.rr_lb.as<uint32_t>();
         w->rr_ub = s.rr_ub.as<uint32_t>();
     }
-    if (w->mfma) {
+    if (mfma) {
         w->lut8 = s.lut8.as<int8_t>();
         w->lut8_meta = s.lut8_meta.p;
         w->mfma_thr1 = s.mfma_thr1.as<int>();
@@ -1013,11 +1014,8 @@ static int ensure_txh_workspace(scann_hip_index *ix, TxhWorkspace &s, uint32_t n
         w->cand32_codes = t.ah_mode ? s.cand32_codes.as<uint32_t>() : nullptr;
         w->cand32_cnt = s.cand32_cnt.as<uint32_t>();
     }
-    if (p.small) w->small_tickets = s.small_tickets.as<uint32_t>();
-    w->wide_cap2 = p.wide_cap2;
-    w->wide_min = w->wide_ceb = w->wide_cidx = w->wide_cnt = nullptr;
-    w->wide_ckey = nullptr;
-    if (p.small == 2) {
+    if (small) w->small_tickets = s.small_tickets.as<uint32_t>();
+    if (wide) {
         w->wide_min = s.wide_min.as<uint32_t>();
         w->wide_ckey = s.wide_ckey.as<uint64_t>();
         w->wide_ceb = s.wide_ceb.as<uint32_t>();
@@ -1068,10 +1066,7 @@ static void fill_empty(uint32_t nq, uint32_t k, uint32_t *out_idx, float *out_di
 
 // ---- workspaces of the device entry points: one per caller stream (ix->mu held) ---------------------------------
 static int device_slot_count() {
-    static const int v = [] {
-        const char *e = std::getenv("SCANN_HIP_DEVICE_SLOTS");
-        return std::max(1, std::min((int)scann_hip_index::kMaxDeviceSlots, e ? std::atoi(e) : 2));
-    }();
+    static const int v = std::max(1, std::min((int)scann_hip_index::kMaxDeviceSlots, read_knobs().device_slots));
     return v;
 }
 
@@ -1141,10 +1136,7 @@ struct SlotLock {
 };
 
 static uint32_t max_slots() {
-    static const uint32_t v = [] {
-        const char *e = std::getenv("SCANN_HIP_SEARCH_SLOTS");
-        return (uint32_t)std::max(1, std::min(64, e ? std::atoi(e) : 4));
-    }();
+    static const uint32_t v = read_knobs().search_slots;
     return v;
 }
 
@@ -1225,9 +1217,10 @@ static int txh_search_host(scann_hip_index *ix, const float *queries, uint32_t n
     TxhWorkspace &ws = *sl.ws;
     const hipStream_t stream = sl.stream;
     SCANN_TRY(set_device(ix->ctx));
+    const Knobs kn = read_knobs();
     for (int attempt = 0; attempt < 2; ++attempt) {
-        TxhCallParams p;
-        SCANN_TRY(resolve_params(ix, k, opts, /*full_cap=*/attempt == 1, &p, nq, /*allow_wide=*/attempt == 0));
+        TxhPlan p;
+        SCANN_TRY(plan_txh_search(ix, k, opts, nq, /*retry=*/attempt == 1, TxhPipeline::Wide, kn, &p));
         if (p.m == 0) {  // nothing can be kept (reference panics on FastTopNeighbors::new(0))
             fill_empty(nq, k, out_idx, out_dist, out_count);
             if (opts && opts->cand_count) std::memset(opts->cand_count, 0, (size_t)nq * 4);
@@ -1235,12 +1228,12 @@ static int txh_search_host(scann_hip_index *ix, const float *queries, uint32_t n
         }
         TxhWork w;
         const size_t allow_words = (opts && opts->allow_bitmap) ? (size_t)((opts->allow_bitmap_bits + 63) / 64) : 0;
-        SCANN_TRY(ensure_txh_workspace(ix, ws, nq, p, true, q_stride, true, &w, allow_words * 8));
+        SCANN_TRY(ensure_txh_workspace(ix, ws, p, true, q_stride, true, &w, allow_words * 8));
         // (cand_count alone also takes the staged pipeline: the small-batch one keeps no candidate counts)
         w.need_sorted_cands = (opts && (opts->cand_idx || opts->cand_dist || opts->cand_count)) ? 1 : 0;
         const bool stage_outputs = opts && (opts->tokens || opts->token_dists || opts->cand_idx || opts->cand_dist ||
                                             opts->cand_count);
-        if (w.small && !stage_outputs && !(opts && opts->allow_bitmap)) {
+        if (p.pipeline != TxhPipeline::Staged && !stage_outputs && !(opts && opts->allow_bitmap)) {
             // small batch: queries and result rows live in pinned host memory the kernels access in place
             const size_t qb = (size_t)nq * q_stride * 4, ob = (size_t)nq * k * 4;
             const size_t off_idx = (qb + 255) & ~(size_t)255, off_dist = off_idx + ((ob + 255) & ~(size_t)255),
@@ -1264,10 +1257,10 @@ static int txh_search_host(scann_hip_index *ix, const float *queries, uint32_t n
                                         sl.primary ? ix->ev1 : nullptr));
             if (sl.primary) {
                 ix->timing_valid = ix->timing;
-                ix->timed_kernel = w.small == 2 ? "wide_scan_kernel" : "small_scan_kernel";
+                ix->timed_kernel = txh_kernel_name(p, /*pinned=*/true);
             }
             SCANN_TRY(wait_small_done(stream, reinterpret_cast<const volatile uint32_t *>(hp + off_flag), nq, seq));
-            if (w.small == 2) {   // the wide pipeline's compact arrays can overflow: count row 0xFFFFFFFF -> the batched pipeline
+            if (p.pipeline == TxhPipeline::Wide) {   // the wide pipeline's compact arrays can overflow: count row 0xFFFFFFFF -> the batched pipeline
                 bool overflow = false;
                 for (uint32_t i = 0; i < nq; ++i) overflow = overflow || reinterpret_cast<const uint32_t *>(hp + off_cnt)[i] == 0xFFFFFFFFu;
                 if (overflow) continue;
@@ -1289,7 +1282,7 @@ static int txh_search_host(scann_hip_index *ix, const float *queries, uint32_t n
         SCANN_TRY(txh_launch_search(ix->tx, w, false, stream, sl.primary ? ix->ev0 : nullptr,
                                     sl.primary ? ix->ev1 : nullptr));
         if (sl.primary) ix->timing_valid = ix->timing;
-        if (sl.primary) ix->timed_kernel = ix->tx.exact_scan ? "leaf_exact_scan_kernel" : w.mfma == 2 ? "adc_mfma16_kernel" : w.mfma == 3 ? "adc_smfmac_kernel" : w.mfma ? "adc_mfma_kernel" : w.resident ? "adc_scan_res_kernel" : "adc_scan_kernel";
+        if (sl.primary) ix->timed_kernel = txh_kernel_name(p, /*pinned=*/false);
         uint32_t counters[CNT_N];
         SCANN_HIP_CHECK(hipMemcpyAsync(counters, w.counters, sizeof(counters), hipMemcpyDeviceToHost,
                                        stream));
@@ -1334,7 +1327,7 @@ static int txh_search_host(scann_hip_index *ix, const float *queries, uint32_t n
 // one-to-many kernels' arithmetic, the k smallest (distance, index) keys = TopK -- with queries and result
 // rows in pinned host memory (no copy commands).
 static int bf_small_search_host(scann_hip_index *ix, SlotLock &sl, const float *queries, uint32_t nq,
-                                uint32_t q_stride, uint32_t k, uint32_t *out_idx, float *out_dist,
+                                uint32_t q_stride, uint32_t k, const Knobs &kn, uint32_t *out_idx, float *out_dist,
                                 uint32_t *out_count) {
     TxhWorkspace &ws = *sl.ws;
     const uint32_t n = (uint32_t)ix->bf.n, kk = std::min(k, n);
@@ -1356,8 +1349,8 @@ static int bf_small_search_host(scann_hip_index *ix, SlotLock &sl, const float *
     const uint32_t seq = ++sl.pin->seq ? sl.pin->seq : ++sl.pin->seq;
     std::memset(hp + off_flag, 0, (size_t)nq * 4);   // (stale words of an earlier call's layout: see txh_search_host)
     TxhWork w{};
-    w.nq = nq; w.q_stride = q_stride; w.P = 1; w.m = kk; w.k = k; w.cap = n; w.exact_reorder = 0;
-    w.no_threshold = 1; w.need_sorted_cands = 0; w.allow = nullptr; w.allow_bits = 0;
+    w.nq = nq; w.q_stride = q_stride; w.P = 1; w.m = kk; w.k = k; w.cap = n; w.exact_reorder = false;
+    w.no_threshold = true; w.need_sorted_cands = 0; w.allow = nullptr; w.allow_bits = 0;
     w.queries = reinterpret_cast<const float *>(dp);
     w.tokens = ws.tokens.as<uint32_t>(); w.token_dists = ws.token_dists.as<float>();
     w.vbase = ws.vbase.as<uint32_t>(); w.sbase = ws.sbase.as<uint32_t>(); w.st = 1;
@@ -1365,7 +1358,8 @@ static int bf_small_search_host(scann_hip_index *ix, SlotLock &sl, const float *
     w.out_idx = reinterpret_cast<uint32_t *>(dp + off_idx);
     w.out_dist = reinterpret_cast<float *>(dp + off_dist);
     w.out_count = reinterpret_cast<uint32_t *>(dp + off_cnt);
-    w.small = 1; w.small_max_leaf = n;
+    w.pipeline = TxhPipeline::Small; w.scan = TxhScan::Exact; w.small_max_leaf = n;
+    plan_small_launch(ix->bfx, kn, &w);
     w.small_tickets = ws.small_tickets.as<uint32_t>();
     w.small_done = reinterpret_cast<uint32_t *>(dp + off_flag);
     w.small_seq = seq;
@@ -1404,17 +1398,17 @@ int scann_hip_search_batched(scann_hip_index *ix, const float *queries, uint32_t
         SlotLock sl;
         SCANN_TRY(acquire_slot(ix, &sl));
         SCANN_TRY(set_device(ix->ctx));
-        const bool small_on = small_batch_enabled();
-        if (small_on && ix->bfx.rows && nq <= kSmallBatch && k <= 64)
-            return bf_small_search_host(ix, sl, queries, nq, q_stride, k, out_idx, out_dist, out_count);
+        const Knobs kn = read_knobs();
+        if (kn.small && ix->bfx.rows && nq <= kSmallBatch && k <= 64)
+            return bf_small_search_host(ix, sl, queries, nq, q_stride, k, kn, out_idx, out_dist, out_count);
         if (sl.primary) ix->next_events();
-        int s = bf_search_host(ix->bf, *sl.bfw, queries, nq, q_stride, k, opts && opts->bf_exact, out_idx,
+        const bool shortlist = !(opts && opts->bf_exact) && bf_shortlist_eligible(ix->bf, nq, k, kn);
+        int s = bf_search_host(ix->bf, *sl.bfw, queries, nq, q_stride, k, shortlist, kn.bf_shortlist_tail, out_idx,
                                out_dist, out_count, sl.stream, sl.primary ? ix->ev0 : nullptr,
                                sl.primary ? ix->ev1 : nullptr);
         if (sl.primary) {
             ix->timing_valid = ix->timing && s == SCANN_HIP_OK;
-            ix->timed_kernel = (!(opts && opts->bf_exact) && bf_shortlist_eligible(ix->bf, nq, k))
-                                   ? "bf_bf16_kernel" : bf_pass_kernel_name(ix->bf, nq);
+            ix->timed_kernel = shortlist ? "bf_bf16_kernel" : bf_pass_kernel_name(ix->bf, nq);
         }
         return s;
     }
@@ -1481,10 +1475,10 @@ int scann_hip_index_reserve(scann_hip_index *ix, uint32_t max_nq, uint32_t max_k
     std::lock_guard<std::mutex> lock(ix->mu);
     SCANN_TRY(set_device(ix->ctx));
     if (ix->kind == KIND_BF) return bf_reserve(ix->bf, ix->bfw, max_nq, max_k);
-    TxhCallParams p;
-    SCANN_TRY(resolve_params(ix, max_k, opts, false, &p));
+    TxhPlan p;
+    SCANN_TRY(plan_txh_search(ix, max_k, opts, max_nq, false, TxhPipeline::Staged, read_knobs(), &p));
     TxhWork w;
-    return ensure_txh_workspace(ix, ix->ws, max_nq, p, false, 0, false, &w);
+    return ensure_txh_workspace(ix, ix->ws, p, false, 0, false, &w);
 }
 
 int scann_hip_search_batched_device(scann_hip_index *ix, const float *d_queries, uint32_t nq,
@@ -1499,22 +1493,22 @@ int scann_hip_search_batched_device(scann_hip_index *ix, const float *d_queries,
     SCANN_TRY(set_device(ix->ctx));
     scann_hip_index::DeviceSlot *dsl = nullptr;
     SCANN_TRY(device_slot(ix, st, &dsl));
+    const Knobs kn = read_knobs();
     if (ix->kind == KIND_BF) {
         ix->next_events();
-        const bool exact_only = opts && opts->bf_exact;
-        int s = bf_search_device(ix->bf, *dsl->bfw, d_queries, nq, q_stride, k, exact_only, d_out_idx,
-                                 d_out_dist, d_out_count, st, ix->ev0, ix->ev1);
+        const bool shortlist = !(opts && opts->bf_exact) && bf_shortlist_eligible(ix->bf, nq, k, kn);
+        int s = bf_search_device(ix->bf, *dsl->bfw, d_queries, nq, q_stride, k, shortlist, kn.bf_shortlist_tail,
+                                 d_out_idx, d_out_dist, d_out_count, st, ix->ev0, ix->ev1);
         if (s == SCANN_HIP_OK) s = device_slot_done(dsl, st);
         ix->timing_valid = ix->timing && s == SCANN_HIP_OK;
-        ix->timed_kernel = (!exact_only && bf_shortlist_eligible(ix->bf, nq, k)) ? "bf_bf16_kernel"
-                                                                                : bf_pass_kernel_name(ix->bf, nq);
+        ix->timed_kernel = shortlist ? "bf_bf16_kernel" : bf_pass_kernel_name(ix->bf, nq);
         return s;
     }
-    TxhCallParams p;
-    SCANN_TRY(resolve_params(ix, k, opts, false, &p, nq));
+    TxhPlan p;
+    SCANN_TRY(plan_txh_search(ix, k, opts, nq, false, TxhPipeline::Wide, kn, &p));
     if (p.m == 0) return fail(SCANN_HIP_INVALID_ARGUMENT, "pre-reorder candidate count is 0");
     TxhWork w;
-    SCANN_TRY(ensure_txh_workspace(ix, *dsl->ws, nq, p, false, q_stride, false, &w));
+    SCANN_TRY(ensure_txh_workspace(ix, *dsl->ws, p, false, q_stride, false, &w));
     w.queries = d_queries;
     w.out_idx = d_out_idx;
     w.out_dist = d_out_dist;
@@ -1529,7 +1523,7 @@ int scann_hip_search_batched_device(scann_hip_index *ix, const float *d_queries,
                                 ix->ev1));
     SCANN_TRY(device_slot_done(dsl, st));
     ix->timing_valid = ix->timing;
-    ix->timed_kernel = ix->tx.exact_scan ? "leaf_exact_scan_kernel" : w.mfma == 2 ? "adc_mfma16_kernel" : w.mfma == 3 ? "adc_smfmac_kernel" : w.mfma ? "adc_mfma_kernel" : w.resident ? "adc_scan_res_kernel" : "adc_scan_kernel";
+    ix->timed_kernel = txh_kernel_name(p, /*pinned=*/false);
     return SCANN_HIP_OK;
 }
 
@@ -1570,14 +1564,14 @@ int scann_hip_txh_search_local_device(scann_hip_index *ix, const float *d_querie
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     std::lock_guard<std::mutex> lock(ix->mu);
     SCANN_TRY(set_device(ix->ctx));
-    TxhCallParams p;
-    SCANN_TRY(resolve_params(ix, k, opts, false, &p));
+    TxhPlan p;
+    SCANN_TRY(plan_txh_search(ix, k, opts, nq, false, TxhPipeline::Staged, read_knobs(), &p));
     if (!p.exact_reorder) return fail(SCANN_HIP_INVALID_ARGUMENT, "local stage needs exact_reorder");
     if (p.m == 0) return fail(SCANN_HIP_INVALID_ARGUMENT, "pre-reorder candidate count is 0");
     scann_hip_index::DeviceSlot *dsl = nullptr;
     SCANN_TRY(device_slot(ix, st, &dsl));
     TxhWork w;
-    SCANN_TRY(ensure_txh_workspace(ix, *dsl->ws, nq, p, false, q_stride, false, &w));
+    SCANN_TRY(ensure_txh_workspace(ix, *dsl->ws, p, false, q_stride, false, &w));
     w.queries = d_queries;
     w.cand_key = d_keys;
     w.cand_idx = d_idx;
@@ -1593,7 +1587,7 @@ int scann_hip_txh_search_local_device(scann_hip_index *ix, const float *d_querie
                                 ix->ev1));
     SCANN_TRY(device_slot_done(dsl, st));
     ix->timing_valid = ix->timing;
-    ix->timed_kernel = ix->tx.exact_scan ? "leaf_exact_scan_kernel" : w.mfma == 2 ? "adc_mfma16_kernel" : w.mfma == 3 ? "adc_smfmac_kernel" : w.mfma ? "adc_mfma_kernel" : w.resident ? "adc_scan_res_kernel" : "adc_scan_kernel";
+    ix->timed_kernel = txh_kernel_name(p, /*pinned=*/false);
     return SCANN_HIP_OK;
 }
 
@@ -1654,11 +1648,11 @@ int scann_hip_txh_partition(scann_hip_index *ix, const float *queries, uint32_t 
     scann_hip_search_opts_default(&o);
     o.partitions_to_search = std::max(1u, num_partitions);
     o.exact_reorder = 0;
-    TxhCallParams p;
-    SCANN_TRY(resolve_params(ix, 1, &o, false, &p));
+    TxhPlan p;
+    SCANN_TRY(plan_txh_search(ix, 1, &o, nq, false, TxhPipeline::Staged, read_knobs(), &p));
     TxhWork w;
     SCANN_TRY(claim_primary_workspace(ix));
-    SCANN_TRY(ensure_txh_workspace(ix, ix->ws, nq, p, true, q_stride, true, &w));
+    SCANN_TRY(ensure_txh_workspace(ix, ix->ws, p, true, q_stride, true, &w));
     SCANN_HIP_CHECK(hipMemcpyAsync(ix->ws.queries.p, queries, (size_t)nq * q_stride * 4,
                                    hipMemcpyHostToDevice, ix->stream));
     SCANN_TRY(txh_launch_partition_only(ix->tx, w, ix->stream));

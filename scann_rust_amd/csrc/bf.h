@@ -1,6 +1,7 @@
 // bf.h -- brute-force path (BruteForceSearcher, brute_force/searcher.rs:77-208).
 #pragma once
 #include "common.h"
+#include "knobs.h"
 
 namespace scann {
 
@@ -25,7 +26,7 @@ struct BfWorkspace {
 int bf_build_shortlist_data(const BfIndexDev &ix, DevBuf &rows_b, DevBuf &rows_bl, DevBuf &norm2,
                             float *max_norm, hipStream_t stream);
 // true if searches on this index may take the bf16-shortlist path for (nq, k)
-bool bf_shortlist_eligible(const BfIndexDev &ix, uint32_t nq, uint32_t k);
+bool bf_shortlist_eligible(const BfIndexDev &ix, uint32_t nq, uint32_t k, const Knobs &kn);
 
 constexpr uint32_t kBfSampleRows = 8192;   // rows of the threshold sample (== LDS sort size)
 
@@ -33,16 +34,17 @@ int bf_reserve(const BfIndexDev &ix, BfWorkspace &w, uint32_t max_nq, uint32_t m
 
 const char *bf_pass_kernel_name(const BfIndexDev &ix, uint32_t nq);
 
-// Host-pointer entry (copies in/out, synchronises).
+// Host-pointer entry (copies in/out, synchronises).  shortlist: take the bf16-shortlist path first
+// (bf_shortlist_eligible), whose bound misses with probability `tail`; queries it cannot verify are repeated exactly.
 int bf_search_host(const BfIndexDev &ix, BfWorkspace &w, const float *queries, uint32_t nq,
-                   uint32_t q_stride, uint32_t k, bool exact_only, uint32_t *out_idx, float *out_dist,
+                   uint32_t q_stride, uint32_t k, bool shortlist, double tail, uint32_t *out_idx, float *out_dist,
                    uint32_t *out_count, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1);
 
 // Device-pointer entry (enqueue only).
-// exact_only = false: searches that qualify take the bf16-shortlist path (status Aborted in the
-// counters if a query's result could not be verified: repeat with exact_only = true).
+// shortlist: the bf16-shortlist path (status Aborted in the counters if a query's result could not be verified:
+// repeat without it).
 int bf_search_device(const BfIndexDev &ix, BfWorkspace &w, const float *d_queries, uint32_t nq,
-                     uint32_t q_stride, uint32_t k, bool exact_only, uint32_t *d_out_idx,
+                     uint32_t q_stride, uint32_t k, bool shortlist, double tail, uint32_t *d_out_idx,
                      float *d_out_dist, uint32_t *d_out_count, hipStream_t stream, hipEvent_t ev0,
                      hipEvent_t ev1);
 // OK, or the status the last enqueued search left in the workspace counters (synchronises).

@@ -1362,15 +1362,11 @@ static bool vq_eligible(const BfIndexDev &ix, const BfPass &p) {
     return p.nq >= 128;
 }
 
-// streaming kernel: a few queries (one database pass per 8), 16-byte-loadable rows
+// streaming kernel: a few queries (at most 16, one database pass per 8), 16-byte-loadable rows
 static bool stream_eligible(const BfIndexDev &ix, const BfPass &p) {
     if (ix.measure > SCANN_HIP_DOT_PRODUCT) return false;   // L1 / Cosine: the pair-at-a-time kernel
     if ((ix.stride & 3u) || (reinterpret_cast<uintptr_t>(ix.rows) & 15u) || ix.dim < 8) return false;
-    static const uint32_t max_q = [] {
-        const char *e = std::getenv("SCANN_HIP_BF_STREAM_MAX_QUERIES");
-        return e ? (uint32_t)std::max(0, std::atoi(e)) : 16u;
-    }();
-    return p.nq <= max_q;
+    return p.nq <= 16;
 }
 
 // name of the kernel launch_pass picks for a batch of nq queries (timing reports)
@@ -1561,11 +1557,6 @@ static int enqueue_search(const BfIndexDev &ix, BfWorkspace &w, const BfPlan &pl
 }
 
 // ---- bf16 shortlist path --------------------------------------------------------------------
-static uint32_t env_u32(const char *name, uint32_t dflt) {
-    const char *e = std::getenv(name);
-    return e ? (uint32_t)std::strtoul(e, nullptr, 10) : dflt;
-}
-
 static bool shortlist_dims_ok(uint32_t dim) {
     switch (dim) {
         case 32: case 64: case 96: case 128: case 192: case 256: return true;
@@ -1578,7 +1569,7 @@ int bf_build_shortlist_data(const BfIndexDev &ix, DevBuf &rows_b, DevBuf &rows_b
     *max_norm = 0.0f;
     if (ix.n == 0 || !shortlist_dims_ok(ix.dim)) return SCANN_HIP_OK;
     // SCANN_HIP_BF_SHORTLIST_MIN_ROWS: below this the exact kernels are fast enough (tests set 1)
-    if (ix.n < env_u32("SCANN_HIP_BF_SHORTLIST_MIN_ROWS", 65536)) return SCANN_HIP_OK;
+    if (ix.n < read_knobs().bf_shortlist_min_rows) return SCANN_HIP_OK;
     if (ix.measure > SCANN_HIP_DOT_PRODUCT) return SCANN_HIP_OK;   // L1 / Cosine: no bf16 bound is derived for them
     SCANN_TRY(rows_b.ensure((size_t)ix.n * ix.dim * 2));
     SCANN_TRY(rows_bl.ensure((size_t)ix.n * ix.dim * 2));
@@ -1604,12 +1595,12 @@ int bf_build_shortlist_data(const BfIndexDev &ix, DevBuf &rows_b, DevBuf &rows_b
 // shortlist size: 4k, at least 32, at most kShortMax
 static uint32_t shortlist_size(uint32_t k) { return std::min(kShortMax, std::max(32u, 4u * k)); }
 
-bool bf_shortlist_eligible(const BfIndexDev &ix, uint32_t nq, uint32_t k) {
+bool bf_shortlist_eligible(const BfIndexDev &ix, uint32_t nq, uint32_t k, const Knobs &kn) {
     if (!ix.rows_b || !ix.rows_bl || !ix.norm2) return false;
     if (!(ix.max_norm == ix.max_norm) || std::isinf(ix.max_norm)) return false;
     if (k == 0 || 4u * k > kShortMax) return false;
     if ((uint64_t)shortlist_size(k) * 8 > ix.n) return false;   // a shortlist that is most of the data
-    return nq >= env_u32("SCANN_HIP_BF_SHORTLIST_MIN_QUERIES", 32);
+    return nq >= kn.bf_shortlist_min_queries;
 }
 
 template <int TS>
@@ -1648,7 +1639,7 @@ static int launch_bf16_pass(const BfIndexDev &ix, const BfPass &p, const uint16_
 }
 
 // bf16 scores -> shortlist of kp rows -> exact re-score -> first k + verification
-static int enqueue_shortlist_search(const BfIndexDev &ix, BfWorkspace &w, uint32_t k, const float *d_queries,
+static int enqueue_shortlist_search(const BfIndexDev &ix, BfWorkspace &w, uint32_t k, double tail, const float *d_queries,
                                     uint32_t nq, uint32_t q_stride, uint32_t *d_out_idx, float *d_out_dist,
                                     uint32_t *d_out_count, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1) {
     const uint32_t n = (uint32_t)ix.n, kp = shortlist_size(k);
@@ -1692,12 +1683,7 @@ static int enqueue_shortlist_search(const BfIndexDev &ix, BfWorkspace &w, uint32
     // 1-in-rs sample -- lets ~j * rs through.  Should it cut deeper, the shortlist is merely shorter
     // than kp and the final kernel proves the result against the bound itself (or flags the query).
     uint32_t jthr = kp;
-    {
-        double tail = 1e-6;   // read per call: tests force the short-shortlist paths through it
-        if (const char *e = std::getenv("SCANN_HIP_BF_SHORTLIST_TAIL")) {
-            const double v = std::atof(e);
-            if (v > 0.0 && v < 1.0) tail = v;
-        }
+    {   // (tail: SCANN_HIP_BF_SHORTLIST_TAIL, read per call: tests force the short-shortlist paths through it)
         const double lam = (double)kp / (double)rs;
         double term = std::exp(-lam), cdf = term;   // P(X <= 0)
         for (uint32_t j = 1; j < kp; ++j) {         // smallest j with P(X >= j) = 1 - P(X <= j-1) <= 1e-6
@@ -1778,15 +1764,15 @@ int bf_last_status(const BfWorkspace &w, hipStream_t st) {
 }
 
 int bf_search_device(const BfIndexDev &ix, BfWorkspace &w, const float *d_queries, uint32_t nq,
-                     uint32_t q_stride, uint32_t k, bool exact_only, uint32_t *d_out_idx, float *d_out_dist,
+                     uint32_t q_stride, uint32_t k, bool shortlist, double tail, uint32_t *d_out_idx, float *d_out_dist,
                      uint32_t *d_out_count, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1) {
     if (ix.n == 0) return fail(SCANN_HIP_INVALID_ARGUMENT, "empty dataset on the device path");
     BfPlan pl;
     SCANN_TRY(make_plan(ix, k, false, &pl));
     if (pl.k != k)
         return fail(SCANN_HIP_INVALID_ARGUMENT, "k > dataset size on the device path (row pitch)");
-    if (!exact_only && bf_shortlist_eligible(ix, nq, k))
-        return enqueue_shortlist_search(ix, w, k, d_queries, nq, q_stride, d_out_idx, d_out_dist, d_out_count, st,
+    if (shortlist)
+        return enqueue_shortlist_search(ix, w, k, tail, d_queries, nq, q_stride, d_out_idx, d_out_dist, d_out_count, st,
                                         ev0, ev1);
     SCANN_TRY(ensure_ws(ix, w, nq, pl, false, q_stride, false));
     return enqueue_search(ix, w, pl, d_queries, nq, q_stride, d_out_idx, d_out_dist, d_out_count, st,
@@ -1794,19 +1780,17 @@ int bf_search_device(const BfIndexDev &ix, BfWorkspace &w, const float *d_querie
 }
 
 int bf_search_host(const BfIndexDev &ix, BfWorkspace &w, const float *queries, uint32_t nq,
-                   uint32_t q_stride, uint32_t k, bool exact_only, uint32_t *out_idx, float *out_dist,
+                   uint32_t q_stride, uint32_t k, bool shortlist, double tail, uint32_t *out_idx, float *out_dist,
                    uint32_t *out_count, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1) {
     // attempt 0: bf16 shortlist (if the search qualifies); 1: exact kernels; 2: exact, full buffers
-    const uint32_t kk = (uint32_t)std::min<uint64_t>(k, ix.n);
-    for (int attempt = (!exact_only && bf_shortlist_eligible(ix, nq, kk) && kk == k) ? 0 : 1; attempt < 3;
-         ++attempt) {
+    for (int attempt = shortlist ? 0 : 1; attempt < 3; ++attempt) {
         BfPlan pl;
         SCANN_TRY(make_plan(ix, k, attempt == 2, &pl));
         SCANN_TRY(ensure_ws(ix, w, nq, pl, true, q_stride, true));
         SCANN_HIP_CHECK(hipMemcpyAsync(w.queries.p, queries, (size_t)nq * q_stride * 4,
                                        hipMemcpyHostToDevice, st));
         if (attempt == 0)
-            SCANN_TRY(enqueue_shortlist_search(ix, w, k, w.queries.as<float>(), nq, q_stride,
+            SCANN_TRY(enqueue_shortlist_search(ix, w, k, tail, w.queries.as<float>(), nq, q_stride,
                                                w.out_idx.as<uint32_t>(), w.out_dist.as<float>(),
                                                w.out_count.as<uint32_t>(), st, ev0, ev1));
         else
@@ -1851,7 +1835,7 @@ int bf_search_host(const BfIndexDev &ix, BfWorkspace &w, const float *queries, u
                 std::memcpy(&sub[(size_t)r * q_stride], queries + (size_t)redo[r] * q_stride, (size_t)q_stride * 4);
             std::vector<uint32_t> ri((size_t)nr * k), rc(nr);
             std::vector<float> rd((size_t)nr * k);
-            SCANN_TRY(bf_search_host(ix, w, sub.data(), nr, q_stride, k, true, ri.data(), rd.data(), rc.data(), st,
+            SCANN_TRY(bf_search_host(ix, w, sub.data(), nr, q_stride, k, false, tail, ri.data(), rd.data(), rc.data(), st,
                                      nullptr, nullptr));
             for (uint32_t r = 0; r < nr; ++r) {
                 std::memcpy(out_idx + (size_t)redo[r] * k, &ri[(size_t)r * k], (size_t)k * 4);

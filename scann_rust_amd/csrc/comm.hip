@@ -22,6 +22,7 @@
 
 #include "comm.h"
 #include "common.h"
+#include "knobs.h"
 #include "txh.h"
 
 namespace scann {
@@ -46,7 +47,7 @@ Rccl *rccl() {
     static Rccl r;
     static std::once_flag once;
     std::call_once(once, [] {
-        const char *names[] = {std::getenv("SCANN_HIP_RCCL_LIB"), "librccl.so.1", "/opt/rocm/lib/librccl.so.1",
+        const char *names[] = {read_knobs().rccl_lib, "librccl.so.1", "/opt/rocm/lib/librccl.so.1",
                                "librccl.so"};
         for (const char *nm : names) {
             if (!nm || !*nm) continue;
@@ -99,12 +100,6 @@ int rccl_ready(Rccl **out) {
 // therefore COMPACT (a count per query, the entries of the queries one behind the other) with room for fill / world of
 // the worst case; a block that overflows is flagged, the merge reports Aborted on every rank, and the caller repeats the
 // batch with m_local = 0 (worst-case blocks).
-static double comm_fill() {   // (read per call: every rank must run with the same value)
-    const char *e = std::getenv("SCANN_HIP_COMM_FILL");
-    const double f = e ? std::atof(e) : 2.5;
-    return f < 0.0 ? 0.0 : f;
-}
-
 // Layout of the exchange for nq queries over `world` ranks with m_local candidates per (rank, query).
 CommLayout comm_layout(uint32_t nq, uint32_t world, uint32_t m_local, uint32_t k, bool worst_case) {
     CommLayout l;
@@ -112,7 +107,7 @@ CommLayout comm_layout(uint32_t nq, uint32_t world, uint32_t m_local, uint32_t k
     l.nq_pad = l.qr * world;
     const uint64_t full = (uint64_t)l.qr * m_local;
     uint64_t cap = full;
-    const double f = comm_fill();
+    const double f = read_knobs().comm_fill;   // (read per call: every rank must run with the same value)
     if (!worst_case && f > 0.0) {
         const uint64_t want = (uint64_t)std::ceil(f * (double)full / (double)world);
         cap = std::min<uint64_t>(full, std::max<uint64_t>(m_local, want));

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "common.h"
+#include "knobs.h"
 
 namespace {
 
@@ -272,8 +273,7 @@ int scann_hip_index_load_file(scann_hip_ctx *ctx, const char *path, scann_hip_in
     const FileHeader &h = m.header();
     // Pin the mapping so the uploads DMA straight from the page cache.  Best effort: a driver
     // that cannot pin a read-only file mapping leaves the (staged) pageable copy path.
-    const char *pin = std::getenv("SCANN_HIP_LOAD_PIN");
-    if (!(pin && std::atoi(pin) == 0)) {
+    if (scann::read_knobs().load_pin) {
         if (hipHostRegister(m.base, m.bytes, hipHostRegisterReadOnly) == hipSuccess) m.pinned = true;
         else (void)hipGetLastError();
     }

@@ -1,0 +1,126 @@
+// knobs.h -- the SCANN_HIP_* process-environment knobs, read in ONE pass over environ.
+//
+// None of them changes a result.  Every knob is optional; unset means the default below.
+//
+// knob                              values                                                        read
+// --------------------------------  ------------------------------------------------------------  ---------------------
+// SCANN_HIP_DEVICE_SLOTS            workspaces of the device entry points, 1..4 (default 2)        once per process
+// SCANN_HIP_SEARCH_SLOTS            search slots of the host entry points, 1..64 (default 4)       once per process
+// SCANN_HIP_RCCL_LIB                path of librccl tried before the default names                 once per process
+// SCANN_HIP_SMFMAC                  0: no operand planes (creation) / dense 32-pair MFMA (search)  creation, every call
+// SCANN_HIP_RERANK_I8               8-bit row copy of the re-rank filter: 0 never, 2 always        creation / load
+// SCANN_HIP_RERANK_STORE            fp8: that copy in the reference's E4M3 codec (default int8)    creation / load
+// SCANN_HIP_RERANK_UNIFORM          int8 copy: 0 a scale per row, 2 one scale (default: rows'      creation / load
+//                                   magnitudes within 2 %)
+// SCANN_HIP_BF_SHORTLIST_MIN_ROWS   rows from which the bf16 shortlist copy is built (65536)       creation / load
+// SCANN_HIP_LOAD_PIN                0: index files skip hipHostRegister                            load
+// SCANN_HIP_SMALL                   0: no small-batch / wide pipelines                             every call
+// SCANN_HIP_WIDE                    0: never the wide pipeline, 2: wherever its limits allow       every call
+// SCANN_HIP_RESIDENT                0: never the resident-table scan, 2: whenever codes allow      every call
+// SCANN_HIP_RES_CL                  chunks per tile of the resident-table scan (>= 1)              every call
+// SCANN_HIP_MFMA                    0: f32 LUT scan only, 2 / 3: 32- / 16-pair integer-MFMA        every call
+//                                   prefilter whenever it applies
+// SCANN_HIP_RERANK_I8_MIN           shortest candidate list the int8 filter takes (512)            every call
+// SCANN_HIP_SP_WORDS                0 / 1: lane-walk / word-parallel survivor flush of the sparse  every call
+//                                   prefilter (default: word-parallel on tree indexes)
+// SCANN_HIP_THR_TIES                0: filter bound on the distance alone (diagnostics)            every call
+// SCANN_HIP_THR_TAIL                0: filter bound by the full histogram select                   every call
+// SCANN_HIP_FUSED                   0: small batches always as three launches                      every call
+// SCANN_HIP_SELECT_DIRECT           0: stage long candidate lists in LDS for the unsorted select   every call
+// SCANN_HIP_LOCAL_PRUNE             0: multi-GPU local stage re-ranks every candidate exactly      every call
+// SCANN_HIP_COMM_FILL               multi-GPU: room in a destination block, multiple of the even   every call
+//                                   share (2.5; 0 = worst case)
+// SCANN_HIP_BF_SHORTLIST_TAIL       miss probability of the bf16 shortlist's bound, (0, 1) (1e-6)  every call
+// SCANN_HIP_BF_SHORTLIST_MIN_QUERIES  batch size from which the bf16 shortlist is used (32)        every call
+//
+// "every call": one read_knobs() snapshot at the entry point, passed down.
+#pragma once
+
+#include <stdint.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <algorithm>
+
+extern char **environ;
+
+namespace scann {
+
+struct Knobs {
+    int device_slots = 2;                 // (clamped to the slot array by its user)
+    uint32_t search_slots = 4;
+    const char *rccl_lib = nullptr;
+    bool smfmac = true;
+    int rerank_i8 = 1;
+    bool rerank_fp8 = false;
+    int rerank_uniform = 1;
+    uint32_t bf_shortlist_min_rows = 65536;
+    bool load_pin = true;
+    bool small = true;
+    int wide = 1;
+    int resident = 1;
+    uint32_t res_cl = 0;                  // 0 = from the work size
+    int mfma = 1;
+    uint32_t rerank_i8_min = 512;
+    int sp_words = -1;                    // -1 = by index kind
+    bool thr_ties = true;
+    bool thr_tail = true;
+    bool fused = true;
+    bool select_direct = true;
+    bool local_prune = true;
+    double comm_fill = 2.5;
+    double bf_shortlist_tail = 1e-6;
+    uint32_t bf_shortlist_min_queries = 32;
+};
+
+// The first occurrence of a name wins, as with getenv.
+inline Knobs read_knobs() {
+    Knobs k;
+    uint32_t seen = 0;
+    for (char **ep = environ; ep && *ep; ++ep) {
+        const char *e = *ep;
+        if (strncmp(e, "SCANN_HIP_", 10) != 0) continue;
+        const char *eq = strchr(e, '=');
+        if (!eq) continue;
+        const size_t n = (size_t)(eq - e);
+        const char *v = eq + 1;
+        int bit = 0;
+        auto is = [&](const char *s) {
+            const int b = bit++;
+            if (strlen(s) != n || memcmp(s, e, n) != 0 || ((seen >> b) & 1u)) return false;
+            seen |= 1u << b;
+            return true;
+        };
+        if (is("SCANN_HIP_DEVICE_SLOTS")) k.device_slots = atoi(v);
+        else if (is("SCANN_HIP_SEARCH_SLOTS")) k.search_slots = (uint32_t)std::max(1, std::min(64, atoi(v)));
+        else if (is("SCANN_HIP_RCCL_LIB")) k.rccl_lib = v;
+        else if (is("SCANN_HIP_SMFMAC")) k.smfmac = atoi(v) != 0;
+        else if (is("SCANN_HIP_RERANK_I8")) k.rerank_i8 = atoi(v);
+        else if (is("SCANN_HIP_RERANK_STORE")) k.rerank_fp8 = strcmp(v, "fp8") == 0;
+        else if (is("SCANN_HIP_RERANK_UNIFORM")) k.rerank_uniform = atoi(v);
+        else if (is("SCANN_HIP_BF_SHORTLIST_MIN_ROWS")) k.bf_shortlist_min_rows = (uint32_t)strtoul(v, nullptr, 10);
+        else if (is("SCANN_HIP_LOAD_PIN")) k.load_pin = atoi(v) != 0;
+        else if (is("SCANN_HIP_SMALL")) k.small = atoi(v) != 0;
+        else if (is("SCANN_HIP_WIDE")) k.wide = atoi(v);
+        else if (is("SCANN_HIP_RESIDENT")) k.resident = atoi(v);
+        else if (is("SCANN_HIP_RES_CL")) k.res_cl = (uint32_t)std::max(1, atoi(v));
+        else if (is("SCANN_HIP_MFMA")) k.mfma = atoi(v);
+        else if (is("SCANN_HIP_RERANK_I8_MIN")) k.rerank_i8_min = (uint32_t)std::max(1, atoi(v));
+        else if (is("SCANN_HIP_SP_WORDS")) k.sp_words = atoi(v) != 0 ? 1 : 0;
+        else if (is("SCANN_HIP_THR_TIES")) k.thr_ties = atoi(v) != 0;
+        else if (is("SCANN_HIP_THR_TAIL")) k.thr_tail = atoi(v) != 0;
+        else if (is("SCANN_HIP_FUSED")) k.fused = atoi(v) != 0;
+        else if (is("SCANN_HIP_SELECT_DIRECT")) k.select_direct = atoi(v) != 0;
+        else if (is("SCANN_HIP_LOCAL_PRUNE")) k.local_prune = atoi(v) != 0;
+        else if (is("SCANN_HIP_COMM_FILL")) {
+            const double f = atof(v);
+            k.comm_fill = f < 0.0 ? 0.0 : f;
+        } else if (is("SCANN_HIP_BF_SHORTLIST_TAIL")) {
+            const double t = atof(v);
+            if (t > 0.0 && t < 1.0) k.bf_shortlist_tail = t;
+        } else if (is("SCANN_HIP_BF_SHORTLIST_MIN_QUERIES")) k.bf_shortlist_min_queries = (uint32_t)strtoul(v, nullptr, 10);
+    }
+    return k;
+}
+
+}  // namespace scann

@@ -44,6 +44,11 @@ constexpr uint32_t kWideBatch = 4;                        // queries per call it
 constexpr uint32_t kWideMaxStream = 4u << 20;             // ... longest candidate stream (points)
 constexpr uint32_t kWideMaxCandidates = 8192;             // ... largest pre_reorder_k
 constexpr uint32_t kWideMinStream = 16384;                // ... and the stream from which it replaces the pipeline above
+constexpr int kWideRep = 4;                               // ... ADC stream positions per thread of its scan
+constexpr uint32_t kFusedChunk = kSelectThreads;          // one-launch small pipeline: stream positions per workgroup
+constexpr uint32_t kFusedMaxWgs = 512;                    // ... nq x workgroups per query above which three launches are used
+constexpr uint32_t kDecodeStage = 512;                    // selected leaves whose decode tables are staged in LDS
+constexpr uint32_t kThrTailMaxRank = 384;                 // J above this takes threshold_select_kernel
 
 // ---- threshold sampling plan (shared by host buffer sizing and the device kernels) ----
 // Every st-th point of each selected leaf is scored ahead of the scan (adc_sample_kernel,
@@ -130,10 +135,42 @@ enum {
     CNT_WORDS = CNT_XS + 8 * CNT_XQ_STRIDE
 };
 
-struct TxhWork {
-    uint32_t nq, q_stride, P, m, k, cap;
-    int exact_reorder;
-    int no_threshold;          // retry mode: keep every scanned point as a candidate
+// Pipeline of a search call: the batched one (sample, threshold, scan, select, re-rank), the small-batch one
+// ("Small batches": three launches or one, dense candidate lists), the wide few-query one ("Few queries, long streams").
+enum class TxhPipeline : uint8_t { Staged, Small, Wide };
+// Scan kernel of the batched pipeline: the f32 LDS-gather scan, its resident-table form (long leaves), the
+// integer-MFMA prefilter + exact refine on 32- or 16-pair dense tiles or 32-pair tiles of the 2:4-sparse MFMA, or the
+// exact leaf scan (SearchMode::Partitioned).
+enum class TxhScan : uint8_t { Gather, Resident, Mfma32, Mfma16, Smfmac, Exact };
+
+// Every path decision of one search call and the sizes they were derived from (api.hip plan_txh_search).
+struct TxhPlan {
+    uint32_t nq, P, m, k;
+    uint32_t cap;              // candidate slots per query
+    bool exact_reorder;
+    bool no_threshold;         // retry mode / dense lists: keep every scanned point as a candidate
+    TxhPipeline pipeline;
+    TxhScan scan;
+    uint32_t st, scap, sqpt;   // sample stride, per-query sample capacity, quads per sample tile
+    uint32_t qpt;              // quads per scan tile (gather scan)
+    uint32_t res_cl;           // chunks per tile of the resident-table scan
+    uint32_t cap32;            // survivors per query of the MFMA prefilter
+    bool sp_words;             // sparse prefilter's survivor flush: word-parallel (else lanes walk their own words)
+    bool codes_in_list;        // prefilter survivors carry their packed codes / plane rows
+    bool thr_ties;             // filter bound on (distance, stream position); false: on the distance alone
+    bool thr_tail;             // filter bound by threshold_tail_kernel (else threshold_select_kernel)
+    bool fused;                // small pipeline in one launch (small_fused_kernel)
+    uint32_t chunk, grid;      // one-launch small / wide pipeline: stream positions per workgroup, workgroups per query
+    uint32_t small_max_leaf;   // longest local leaf (grid of the three-launch small scan)
+    uint32_t wide_cap2;        // wide pipeline: entries per query of the compact candidate arrays
+    bool select_direct;        // the unsorted select of a long list may read it straight from global memory
+    bool use_i8;               // int8 row filter in front of the exact re-rank (needs ix.rows8)
+    bool local_prune;          // local stage of a sharded search: the filter's prefix form (+inf for hopeless candidates)
+};
+
+// A plan bound to its buffers.
+struct TxhWork : TxhPlan {
+    uint32_t q_stride;
     int need_sorted_cands;     // the caller reads cand_* (parity outputs): keep them sorted
     const uint64_t *allow;     // device allow-bitmap (bit = datapoint index) or nullptr
     uint64_t allow_bits;       // bitmap capacity in bits; indices >= capacity are not allowed
@@ -142,15 +179,7 @@ struct TxhWork {
     uint32_t *tokens;          // [nq][P]
     float *token_dists;        // [nq][P]
     uint32_t *vbase;           // [nq][P+1] prefix of global leaf sizes in token order
-    uint32_t st, scap, sqpt;   // sample stride, per-query sample capacity, quads per sample tile
-    uint32_t qpt;              // quads per scan tile
-    uint32_t resident, res_cl; // resident-table scan kernel (long leaves) and its chunks per tile
-    uint32_t small;            // small-batch pipeline (three launches; dense candidate lists: cap = the stream)
-    uint32_t small_max_leaf;   // longest local leaf (grid of the small scan)
-    uint32_t use_i8;           // int8 row filter in front of the exact re-rank (needs ix.rows8)
     uint32_t *rr_lb, *rr_ub;   // [nq][m] ordered lower / upper bounds of the candidates' exact distances
-    uint32_t mfma;             // integer-MFMA prefilter + exact refine instead of the f32 LDS-gather scan:
-                               // 1 = 32-pair dense tiles, 2 = 16-pair dense tiles, 3 = 32-pair tiles on the sparse MFMA
     int8_t *lut8;              // [max_slots][S][16] quantised tables (value - 128)
     void *lut8_meta;           // [max_slots] {f64 bias_sum, f64 scale}
     int *mfma_thr1;            // [max_slots] integer pass bound + 1 of every pair slot
@@ -160,14 +189,12 @@ struct TxhWork {
     uint32_t *small_done;      // small-batch host calls: [nq] pinned completion flags (or nullptr) ...
     uint32_t small_seq;        // ... and the value the finish kernel stores there after the result rows
     uint32_t *small_tickets;   // [kSmallBatch] ticket counters of the one-launch pipeline (zero between launches)
-    // small == 2: the wide few-query pipeline
-    uint32_t wide_cap2;        // entries per query of the compact candidate arrays
+    // the wide few-query pipeline
     uint32_t *wide_min;        // [nq][cap] ordered approximate distance: minimum of each group of stream positions
     uint64_t *wide_ckey;       // [nq][wide_cap2] merge keys of the candidates under the pivot ...
     uint32_t *wide_ceb;        // ... their ordered exact distances (approximate ones without re-ordering) ...
     uint32_t *wide_cidx;       // ... and datapoint indices
     uint32_t *wide_cnt;        // [nq] entries appended
-    uint32_t cap32;
     uint32_t *sbase;           // [nq][P+2] prefix of per-leaf sample counts; [P]=samples, [P+1]=local points
     uint32_t *pair_sbase;      // [max_slots]
     uint32_t *stile_off;       // [L+1] tile table of the sample pass
@@ -197,6 +224,8 @@ struct TxhWork {
     float *out_dist;           // [nq][k]
     uint32_t *out_count;       // [nq]
 };
+
+static inline bool txh_scan_is_mfma(TxhScan s) { return s == TxhScan::Mfma32 || s == TxhScan::Mfma16 || s == TxhScan::Smfmac; }
 
 // Enqueue the whole search pipeline on `stream`.  local_only: stop after the local
 // top-m + exact distances (multi-GPU local stage).

@@ -1158,7 +1158,6 @@ __global__ __launch_bounds__(kResThreads, 6) void adc_scan_res_kernel(TxhIndexDe
 // Survivors are staged per (wave, pair) in LDS and written at the end of the item as one
 // contiguous segment per pair behind ONE returning atomic per pair.
 // =====================================================================================
-constexpr uint32_t kDecodeStage = 512;    // selected leaves whose decode tables are staged in LDS
 #ifndef SCANN_MFMA_RANGE
 #define SCANN_MFMA_RANGE 2048
 #endif
@@ -2059,7 +2058,7 @@ __device__ __forceinline__ void adc_smfmac_body(const TxhIndexDev &ix, const Mfm
 
 // S <= 32: three waves per SIMD (the pair tile's table fragments alone are 64 registers); S = 48, 64: two.  (Capping the
 // registers at 144 to leave room for a wave of another stream's kernel was tried: amdgpu_num_vgpr is ignored by this
-// compiler, and two waves per SIMD -- SCANN_HIP_MFMA_WGS=2 -- cost the scan 10 % and gained the two-stream step nothing.)
+// compiler, and two waves per SIMD (two workgroups per CU) cost the scan 10 % and gained the two-stream step nothing.)
 #ifndef SCANN_SP_VGPRS
 #define SCANN_SP_VGPRS 144
 #endif
@@ -2731,7 +2730,6 @@ __global__ __launch_bounds__(kSelectThreads) void threshold_select_kernel(
 // smallest), merely looser.
 constexpr uint32_t kThrTailThreads = 256;
 constexpr uint32_t kThrTailList = 2048;
-constexpr uint32_t kThrTailMaxRank = 384;   // J above this takes threshold_select_kernel
 
 __global__ __launch_bounds__(kThrTailThreads) void threshold_tail_kernel(
     uint32_t P, uint32_t m, uint32_t st, const uint32_t *__restrict__ sbase, const uint32_t *__restrict__ samp,
@@ -4858,55 +4856,36 @@ static int launch_scan_stages(const TxhIndexDev &ix, const TxhWork &w, hipStream
         const SelCfg tcfg = sel_cfg(w.scap);
         const size_t lds_thr = ((size_t)((w.scap + 3u) & ~3u) + tcfg.bins + tcfg.list) * 4 + 48 * 8;
         const uint32_t nt = w.scap > 8192 ? kSelectThreads : 256u;
-        // SCANN_HIP_THR_TIES=0 (diagnostics / tests): bound on the distance alone, whole tie groups pass
-        bool thr_ties = true;
-        if (const char *e = std::getenv("SCANN_HIP_THR_TIES")) thr_ties = std::atoi(e) != 0;
-        // a bound in the low tail of a long sample: threshold_tail_kernel (SCANN_HIP_THR_TAIL=0: the full select)
-        static const bool tail_ok = [] {
-            const char *e = std::getenv("SCANN_HIP_THR_TAIL");
-            return !e || std::atoi(e) != 0;
-        }();
-        const uint32_t J = sample_rank(w.m, w.st);
-        if (tail_ok && !w.no_threshold && J <= kThrTailMaxRank && w.scap > 4096) {
+        // (without thr_ties the bound is on the distance alone: whole tie groups pass)
+        if (w.thr_tail) {
             hipLaunchKernelGGL(threshold_tail_kernel, dim3(w.nq), dim3(kThrTailThreads), 0, st, w.P, w.m, w.st, w.sbase,
-                               w.samp, w.scap, w.slot_of, w.thr, w.pair_thr, thr_ties ? w.vbase : nullptr);
+                               w.samp, w.scap, w.slot_of, w.thr, w.pair_thr, w.thr_ties ? w.vbase : nullptr);
         } else {
             SCANN_TRY(set_dyn_lds(threshold_select_kernel, lds_thr));
             hipLaunchKernelGGL(threshold_select_kernel, dim3(w.nq), dim3(nt), lds_thr, st, w.P, w.m, w.st,
-                               w.no_threshold, w.sbase, w.samp, w.scap, w.slot_of, w.thr, w.pair_thr,
-                               thr_ties ? w.vbase : nullptr);
+                               (int)w.no_threshold, w.sbase, w.samp, w.scap, w.slot_of, w.thr, w.pair_thr,
+                               w.thr_ties ? w.vbase : nullptr);
         }
         LAUNCH_CHECK();
     }
     if constexpr (C::BITS == 4) {
-        if (w.mfma) {
+        if (txh_scan_is_mfma(w.scan)) {
             hipLaunchKernelGGL(lut8_build_kernel, dim3(w.max_quads), dim3(256), 0, st, (uint32_t)C::S, w.lutq,
                                w.counters, w.lut8, reinterpret_cast<Lut8Meta *>(w.lut8_meta), w.pair_q, w.pair_thr,
-                               w.mfma_thr1, w.mfma == 3 ? 1 : 0);
+                               w.mfma_thr1, w.scan == TxhScan::Smfmac ? 1 : 0);
             LAUNCH_CHECK();
-            // The survivors' codes travel with their positions for flat hashers: their ~12 k survivors per query
-            // are spread over the whole code array (random 16-byte gathers from 16 MB: refine 145 -> 65 us at
-            // C3).  In a tree index the survivors sit densely in the query's nearest leaves, the gathers hit
-            // L2, and writing the codes only costs the scan (10M x 128, P = 25 / 50: step +3.5 %).
-            // SCANN_HIP_MFMA_CODES: 0 never, 1 always.
-            bool codes_in_list = ix.ah_mode != 0;
-            if (const char *e = std::getenv("SCANN_HIP_MFMA_CODES")) codes_in_list = std::atoi(e) != 0;
+            const bool codes_in_list = w.codes_in_list;
             MfmaArgs ma;
             ma.thr1 = w.mfma_thr1;
             ma.pair_off = w.pair_off; ma.tile_off = w.tile_off; ma.pair_q = w.pair_q; ma.pair_vbase = w.pair_vbase;
             ma.counters = w.counters; ma.lut8 = w.lut8; ma.meta = reinterpret_cast<const Lut8Meta *>(w.lut8_meta);
             ma.pair_thr = w.pair_thr; ma.cand32_cnt = w.cand32_cnt; ma.cand32 = w.cand32; ma.cand32_codes = codes_in_list ? w.cand32_codes : nullptr; ma.cap32 = w.cap32;
             if (ev0) SCANN_HIP_CHECK(hipEventRecord(ev0, st));
-            uint32_t mwgs = 4;   // workgroups per CU (4 waves each)
-            if (const char *e = std::getenv("SCANN_HIP_MFMA_WGS")) mwgs = (uint32_t)std::max(1, std::atoi(e));
-            // the sparse kernel's flush: lanes walk their own words on flat hashers, word-parallel on tree indexes
-            // (SCANN_HIP_SP_WORDS = 0 / 1 forces a form)
-            bool words = !ix.ah_mode;
-            if (const char *e = std::getenv("SCANN_HIP_SP_WORDS")) words = std::atoi(e) != 0;
-            const dim3 mgrid((uint32_t)cus * mwgs), mblock(kMfmaWaves * 64);
-            if (w.mfma == 2)
+            const bool words = w.sp_words;
+            const dim3 mgrid((uint32_t)cus * 4u), mblock(kMfmaWaves * 64);   // 4 workgroups per CU (4 waves each)
+            if (w.scan == TxhScan::Mfma16)
                 hipLaunchKernelGGL(adc_mfma16_kernel<C::S>, mgrid, mblock, 0, st, ix, ma);
-            else if (w.mfma != 3)
+            else if (w.scan == TxhScan::Mfma32)
                 hipLaunchKernelGGL(adc_mfma_kernel<C::S>, mgrid, mblock, 0, st, ix, ma);
             else if (C::S <= 32 && !words)
                 hipLaunchKernelGGL((adc_smfmac_kernel<C::S, false>), mgrid, mblock, 0, st, ix, ma);
@@ -4923,7 +4902,7 @@ static int launch_scan_stages(const TxhIndexDev &ix, const TxhWork &w, hipStream
             ra.slot_of = w.slot_of; ra.lutq = w.lutq; ra.thr = w.thr; ra.cand32_cnt = w.cand32_cnt;
             ra.cand32 = w.cand32; ra.cand32_codes = codes_in_list ? w.cand32_codes : nullptr; ra.cand_cnt = w.cand_cnt; ra.cand = w.cand; ra.counters = w.counters;
             ra.allow = w.allow; ra.allow_bits = w.allow_bits;
-            ra.planes = (w.mfma == 3 && ra.cand32_codes) ? 1 : 0;
+            ra.planes = (w.scan == TxhScan::Smfmac && ra.cand32_codes) ? 1 : 0;
             const size_t lds_rf = w.P <= kRefineTablesMax ? (size_t)w.P * C::S * 16 * sizeof(float) : 16;
             SCANN_TRY(set_dyn_lds(adc_refine_kernel<C>, lds_rf));
             hipLaunchKernelGGL(adc_refine_kernel<C>, dim3(w.nq), dim3(kRefineThreads), lds_rf, st, ix, ra);
@@ -4936,11 +4915,10 @@ static int launch_scan_stages(const TxhIndexDev &ix, const TxhWork &w, hipStream
     a.pair_vbase = w.pair_vbase; a.counters = w.counters; a.lutq = w.lutq; a.pair_thr = w.pair_thr;
     a.cand_cnt = w.cand_cnt; a.cand = w.cand; a.cap = w.cap; a.qpt = w.qpt; a.allow = w.allow; a.allow_bits = w.allow_bits;
     if (ev0) SCANN_HIP_CHECK(hipEventRecord(ev0, st));
-    uint32_t wgs = (uint32_t)cus * 8u;
-    if (const char *e = std::getenv("SCANN_HIP_WGS")) wgs = (uint32_t)cus * (uint32_t)std::max(1, std::atoi(e));
+    const uint32_t wgs = (uint32_t)cus * 8u;
     a.res_cl = w.res_cl;
     if constexpr (C::BITS == 4 && C::S <= 32) {
-        if (w.resident) {
+        if (w.scan == TxhScan::Resident) {
             SCANN_TRY(set_dyn_lds(adc_scan_res_kernel<C>, res_lds_bytes<C>()));
             hipLaunchKernelGGL(adc_scan_res_kernel<C>, dim3((uint32_t)cus * 4u), dim3(kResThreads),
                                res_lds_bytes<C>(), st, ix, a);
@@ -5013,8 +4991,6 @@ static int launch_exact_scan(const TxhIndexDev &ix, const TxhWork &w, hipStream_
 // query's leaf selection (select_leaves_body: the tables come from L2, the repetition costs no time), then
 // scores its positions into the dense key list, and the LAST workgroup of the query to finish (a ticket
 // counter behind a __threadfence) runs the finish stage.  No workgroup ever waits for another.
-constexpr uint32_t kFusedChunk = kSelectThreads;   // stream positions per workgroup
-constexpr uint32_t kFusedMaxWgs = 512;              // nq x workgroups per query above which three launches are used
 
 // Wide pipeline: stream positions per group minimum for a stream of cnt keys and m wanted candidates: the smallest
 // power of two that leaves at most kWideGroups groups (wide_filter_kernel holds them in registers, 16 per thread) --
@@ -5218,7 +5194,6 @@ struct WideArgs {
 // [v0, v0 + chunk) stream positions per workgroup -- for ADC scans up to kWideRep positions per thread, so that a
 // workgroup's table build (and its four dependent round trips) is shared by 4096 points and one wave of workgroups
 // covers a 1M stream -- plus the group minima.
-constexpr int kWideRep = 4;
 
 __global__ __launch_bounds__(kSelectThreads) void wide_scan_kernel(TxhIndexDev ix, SmallArgs a, FusedArgs f, WideArgs wa) {
     extern __shared__ __attribute__((aligned(16))) unsigned char s_dyn[];   // selection | scan tables | query
@@ -5834,35 +5809,31 @@ __global__ __launch_bounds__(kSelectThreads) void wide_final_kernel(SmallArgs a,
 // the three-launch pipeline for small batches (see "Small batches" above)
 static int launch_search_small(const TxhIndexDev &ix, const TxhWork &w, hipStream_t st, hipEvent_t ev0,
                                hipEvent_t ev1) {
-    if (w.small == 2) {   // the wide few-query pipeline ("Few queries, long streams")
-        // 1024 x rep stream positions per workgroup, rep <= kWideRep chosen so that one wave of workgroups (256 CUs) covers
-        // the stream.  (ADC scans only: an exact scan wants a row per thread and ~128 rows per workgroup -- hundreds of
-        // workgroups per query that would each repeat the leaf selection; Partitioned mode keeps the pipelines above.)
-        const uint32_t chunk = kFusedChunk * std::min<uint32_t>(kWideRep, std::max(1u, ceil_div_u32(w.cap, 256u * kFusedChunk)));
-        const uint32_t G = std::max(1u, ceil_div_u32(w.cap, chunk));
-        SmallArgs a;
-        a.nq = w.nq; a.P = w.P; a.m = w.m; a.k = w.k; a.cap = w.cap; a.q_stride = w.q_stride;
-        a.exact_reorder = w.exact_reorder; a.queries = w.queries; a.tokens = w.tokens; a.vbase = w.vbase;
-        a.cand = w.cand; a.counters = w.counters; a.allow = w.allow; a.allow_bits = w.allow_bits;
-        a.out_idx = w.out_idx; a.out_dist = w.out_dist; a.out_count = w.out_count;
-        a.done = w.small_done; a.seq = w.small_seq; a.chunk = chunk;
-        FusedArgs f;
-        f.L = ix.L; f.n_pow2 = next_pow2_u32(ix.L);
-        f.p_pow2 = (w.P * 4u <= f.n_pow2) ? next_pow2_u32(std::max(1u, w.P)) : 0u;
-        f.st = w.st; f.cdist = w.cdist; f.token_dists = w.token_dists; f.tokens = w.tokens; f.vbase = w.vbase;
-        f.sbase = w.sbase; f.tickets = nullptr;
+    SmallArgs a;
+    a.nq = w.nq; a.P = w.P; a.m = w.m; a.k = w.k; a.cap = w.cap; a.q_stride = w.q_stride;
+    a.exact_reorder = w.exact_reorder; a.queries = w.queries; a.tokens = w.tokens; a.vbase = w.vbase;
+    a.cand = w.cand; a.counters = w.counters; a.allow = w.allow; a.allow_bits = w.allow_bits;
+    a.out_idx = w.out_idx; a.out_dist = w.out_dist; a.out_count = w.out_count;
+    a.done = w.small_done; a.seq = w.small_seq; a.chunk = w.chunk;
+    // the one-launch forms: every workgroup repeats the leaf selection
+    FusedArgs f;
+    f.L = ix.L; f.n_pow2 = next_pow2_u32(ix.L);
+    f.p_pow2 = (w.P * 4u <= f.n_pow2) ? next_pow2_u32(std::max(1u, w.P)) : 0u;
+    f.st = w.st; f.cdist = w.cdist; f.token_dists = w.token_dists; f.tokens = w.tokens; f.vbase = w.vbase;
+    f.sbase = w.sbase; f.tickets = w.pipeline == TxhPipeline::Wide ? nullptr : w.small_tickets;
+    const SelCfg lcfg = sel_cfg(ix.L);
+    const size_t lds_sel = ix.ah_mode ? 0 : (size_t)(f.n_pow2 + f.p_pow2) * sizeof(uint64_t) + (size_t)lcfg.bins * 4 +
+                                            (size_t)lcfg.list * 8 + 48 * 8 + 64 * 4 + (size_t)ix.L * 8 +
+                                            (size_t)((ix.dim + 3u) & ~3u) * 4 + 16;
+    if (w.pipeline == TxhPipeline::Wide) {   // the wide few-query pipeline ("Few queries, long streams")
         WideArgs wa;
         wa.ng_stride = w.cap; wa.cap2 = w.wide_cap2;
         wa.wgs = std::min(256u, std::max(8u, ceil_div_u32(w.cap, 1024u)));
         wa.mins = w.wide_min; wa.ckey = w.wide_ckey; wa.ceb = w.wide_ceb; wa.cidx = w.wide_cidx; wa.ccnt = w.wide_cnt;
-        const SelCfg lcfg = sel_cfg(ix.L);
-        const size_t lds_sel = ix.ah_mode ? 0 : (size_t)(f.n_pow2 + f.p_pow2) * sizeof(uint64_t) + (size_t)lcfg.bins * 4 +
-                                                (size_t)lcfg.list * 8 + 48 * 8 + 64 * 4 + (size_t)ix.L * 8 +
-                                                (size_t)((ix.dim + 3u) & ~3u) * 4 + 16;
         const size_t lds_scan = ((size_t)ix.S * ix.kp + ix.dim) * sizeof(float);
         SCANN_TRY(set_dyn_lds_with_static(wide_scan_kernel, std::max(lds_sel, lds_scan), 8 * 1024));   // (6160 B of static arrays)
         if (ev0) SCANN_HIP_CHECK(hipEventRecord(ev0, st));
-        hipLaunchKernelGGL(wide_scan_kernel, dim3(G, w.nq), dim3(kSelectThreads), std::max(lds_sel, lds_scan), st, ix, a, f, wa);
+        hipLaunchKernelGGL(wide_scan_kernel, dim3(w.grid, w.nq), dim3(kSelectThreads), std::max(lds_sel, lds_scan), st, ix, a, f, wa);
         LAUNCH_CHECK();
         if (ev1) SCANN_HIP_CHECK(hipEventRecord(ev1, st));
         const size_t lds_f = (size_t)((ix.dim + 3u) & ~3u) * 4;
@@ -5875,68 +5846,28 @@ static int launch_search_small(const TxhIndexDev &ix, const TxhWork &w, hipStrea
         LAUNCH_CHECK();
         return SCANN_HIP_OK;
     }
-    {   // one launch when the grid stays small (SCANN_HIP_FUSED=0: always three)
-        // Exact scans read a whole row per thread, 64 cache lines per wave instruction: they are bound by the
-        // L1's line-request rate of ONE compute unit, so their workgroups take only 128 positions each (more
-        // compute units share the rows); ADC scans read 16 coalesced code bytes per point and take 1024 --
-        // but rebuild the tables per leaf one after the other, so tree indexes with several leaves per
-        // query keep the three-launch form, whose scan builds every leaf's table in its own workgroup.
-        uint32_t chunk = kFusedChunk;
-        if (ix.exact_scan) chunk = std::min(kFusedChunk, std::max(128u, (ceil_div_u32(w.cap, 256u) + 127u) & ~127u));
-        const uint32_t G = std::max(1u, ceil_div_u32(w.cap, chunk));
-        bool fused = w.small_tickets && w.P <= kDecodeStage && (uint64_t)w.nq * G <= kFusedMaxWgs &&
-                     (ix.exact_scan || w.P == 1);
-        if (const char *e = std::getenv("SCANN_HIP_FUSED")) fused = fused && std::atoi(e) != 0;
-        if (fused) {
-            SmallArgs a;
-            a.nq = w.nq; a.P = w.P; a.m = w.m; a.k = w.k; a.cap = w.cap; a.q_stride = w.q_stride;
-            a.exact_reorder = w.exact_reorder; a.queries = w.queries; a.tokens = w.tokens; a.vbase = w.vbase;
-            a.cand = w.cand; a.counters = w.counters; a.allow = w.allow; a.allow_bits = w.allow_bits;
-            a.out_idx = w.out_idx; a.out_dist = w.out_dist; a.out_count = w.out_count;
-            a.done = w.small_done; a.seq = w.small_seq; a.chunk = chunk;
-            FusedArgs f;
-            f.L = ix.L; f.n_pow2 = next_pow2_u32(ix.L);
-            f.p_pow2 = (w.P * 4u <= f.n_pow2) ? next_pow2_u32(std::max(1u, w.P)) : 0u;
-            f.st = w.st; f.cdist = w.cdist; f.token_dists = w.token_dists; f.tokens = w.tokens; f.vbase = w.vbase;
-            f.sbase = w.sbase; f.tickets = w.small_tickets;
-            const SelCfg lcfg = sel_cfg(ix.L);
-            const size_t lds_sel = ix.ah_mode ? 0 : (size_t)(f.n_pow2 + f.p_pow2) * sizeof(uint64_t) + (size_t)lcfg.bins * 4 +
-                                                    (size_t)lcfg.list * 8 + 48 * 8 + 64 * 4 + (size_t)ix.L * 8 +
-                                                    (size_t)((ix.dim + 3u) & ~3u) * 4 + 16;
-            const size_t lds_scan = ((size_t)(ix.exact_scan ? 0u : ix.S * ix.kp) + ix.dim) * sizeof(float);
-            const size_t lds = std::max(lds_sel, lds_scan);
-            // (80272 B of static arrays -- the finish stage's: from ~2200 leaves the selection's dynamic part passes 64 KB, and
-            // the attribute must leave room for both)
-            SCANN_TRY(set_dyn_lds_with_static(small_fused_kernel, lds, 79 * 1024));
-            if (ev0) SCANN_HIP_CHECK(hipEventRecord(ev0, st));
-            hipLaunchKernelGGL(small_fused_kernel, dim3(G, w.nq), dim3(kSelectThreads), lds, st, ix, a, f);
-            LAUNCH_CHECK();
-            if (ev1) SCANN_HIP_CHECK(hipEventRecord(ev1, st));
-            return SCANN_HIP_OK;
-        }
+    if (w.fused) {   // one launch when the grid stays small
+        const size_t lds_scan = ((size_t)(ix.exact_scan ? 0u : ix.S * ix.kp) + ix.dim) * sizeof(float);
+        const size_t lds = std::max(lds_sel, lds_scan);
+        // (80272 B of static arrays -- the finish stage's: from ~2200 leaves the selection's dynamic part passes 64 KB, and
+        // the attribute must leave room for both)
+        SCANN_TRY(set_dyn_lds_with_static(small_fused_kernel, lds, 79 * 1024));
+        if (ev0) SCANN_HIP_CHECK(hipEventRecord(ev0, st));
+        hipLaunchKernelGGL(small_fused_kernel, dim3(w.grid, w.nq), dim3(kSelectThreads), lds, st, ix, a, f);
+        LAUNCH_CHECK();
+        if (ev1) SCANN_HIP_CHECK(hipEventRecord(ev1, st));
+        return SCANN_HIP_OK;
     }
     if (ix.ah_mode) {
         hipLaunchKernelGGL(ah_tokens_kernel, dim3(ceil_div_u32(w.nq, 256)), dim3(256), 0, st, w.nq,
                            ix.leaf_gsize, ix.leaf_off, w.st, w.tokens, w.token_dists, w.vbase, w.sbase);
-    } else {
-        const uint32_t n2 = next_pow2_u32(ix.L);
-        const uint32_t p2 = (w.P * 4u <= n2) ? next_pow2_u32(std::max(1u, w.P)) : 0u;
-        const SelCfg lcfg = sel_cfg(ix.L);
-        // (+ the leaf size tables and the query: the kernel's inline mode)
-        const size_t lds2 = (size_t)(n2 + p2) * sizeof(uint64_t) + (size_t)lcfg.bins * 4 + (size_t)lcfg.list * 8 +
-                            48 * 8 + 64 * 4 + (size_t)ix.L * 8 + (size_t)((ix.dim + 3u) & ~3u) * 4 + 16;
-        SCANN_TRY(set_dyn_lds(select_leaves_kernel, lds2));
-        hipLaunchKernelGGL(select_leaves_kernel, dim3(w.nq), dim3(kSelectThreads), lds2, st, w.cdist, ix.L, n2, w.P, p2,
-                           ix.leaf_gsize, ix.leaf_off, w.st, w.tokens, w.token_dists, w.vbase, w.sbase, ix.centers_t,
+    } else {   // (lds_sel: + the leaf size tables and the query, the kernel's inline mode)
+        SCANN_TRY(set_dyn_lds(select_leaves_kernel, lds_sel));
+        hipLaunchKernelGGL(select_leaves_kernel, dim3(w.nq), dim3(kSelectThreads), lds_sel, st, w.cdist, ix.L, f.n_pow2, w.P,
+                           f.p_pow2, ix.leaf_gsize, ix.leaf_off, w.st, w.tokens, w.token_dists, w.vbase, w.sbase, ix.centers_t,
                            w.queries, w.q_stride, ix.dim, ix.centers_pitch);
     }
     LAUNCH_CHECK();
-    SmallArgs a;
-    a.nq = w.nq; a.P = w.P; a.m = w.m; a.k = w.k; a.cap = w.cap; a.q_stride = w.q_stride;
-    a.exact_reorder = w.exact_reorder; a.queries = w.queries; a.tokens = w.tokens; a.vbase = w.vbase;
-    a.cand = w.cand; a.counters = w.counters; a.allow = w.allow; a.allow_bits = w.allow_bits;
-    a.out_idx = w.out_idx; a.out_dist = w.out_dist; a.out_count = w.out_count;
-    a.done = w.small_done; a.seq = w.small_seq;
     // exact scans read a whole row per point (one row per thread keeps every load in flight at once); the
     // ADC scan amortises the table build of its workgroup over four points per thread
     a.chunk = ix.exact_scan ? 256u : kSmallChunk;
@@ -5957,16 +5888,17 @@ static int launch_search_small(const TxhIndexDev &ix, const TxhWork &w, hipStrea
 int txh_launch_search(const TxhIndexDev &ix, const TxhWork &w, bool local_only, hipStream_t st,
                       hipEvent_t ev0, hipEvent_t ev1) {
     if (w.nq == 0) return SCANN_HIP_OK;
-    if (w.small && !local_only && !w.need_sorted_cands) return launch_search_small(ix, w, st, ev0, ev1);
-    const uint32_t wl_tp = ix.exact_scan ? kExactRows : w.mfma ? kMfmaRange : w.resident ? kResThreads * kScanPPT : scan_tile_points(ix);
-    const uint32_t wl_qpt = ix.exact_scan ? exact_quads_per_tile(ix.dim) : w.mfma == 2 ? 4u : w.mfma ? 8u : w.resident ? kResQuads : w.qpt;
-    const uint32_t wl_cpt = (w.resident && !ix.exact_scan && !w.mfma) ? w.res_cl : 1u;
+    if (w.pipeline != TxhPipeline::Staged && !local_only && !w.need_sorted_cands) return launch_search_small(ix, w, st, ev0, ev1);
+    const bool mfma = txh_scan_is_mfma(w.scan);
+    const uint32_t wl_tp = w.scan == TxhScan::Exact ? kExactRows : mfma ? kMfmaRange : w.scan == TxhScan::Resident ? kResThreads * kScanPPT : scan_tile_points(ix);
+    const uint32_t wl_qpt = w.scan == TxhScan::Exact ? exact_quads_per_tile(ix.dim) : w.scan == TxhScan::Mfma16 ? 4u : mfma ? 8u : w.scan == TxhScan::Resident ? kResQuads : w.qpt;
+    const uint32_t wl_cpt = w.scan == TxhScan::Resident ? w.res_cl : 1u;
     if (ix.ah_mode && ix.L == 1 && w.P == 1) {
         AhSetupArgs h;
         h.nq = w.nq; h.max_slots = w.max_slots; h.st = w.st; h.tp = wl_tp; h.quads_per_tile = wl_qpt;
         h.chunks_per_tile = wl_cpt; h.stp = scan_tile_points(ix); h.squads_per_tile = w.sqpt;
         h.leaf_gsize = ix.leaf_gsize; h.leaf_off = ix.leaf_off; h.leaf_cnt = w.leaf_cnt; h.leaf_cursor = w.leaf_cursor;
-        h.counters = w.counters; h.cand_cnt = w.cand_cnt; h.cand32_cnt = w.mfma ? w.cand32_cnt : nullptr;
+        h.counters = w.counters; h.cand_cnt = w.cand_cnt; h.cand32_cnt = mfma ? w.cand32_cnt : nullptr;
         h.pair_q = w.pair_q; h.pair_leaf = w.pair_leaf; h.pair_vbase = w.pair_vbase; h.pair_sbase = w.pair_sbase;
         h.slot_of = w.slot_of; h.tokens = w.tokens; h.vbase = w.vbase; h.sbase = w.sbase; h.pair_off = w.pair_off;
         h.tile_off = w.tile_off; h.stile_off = w.stile_off; h.token_dists = w.token_dists;
@@ -5977,7 +5909,7 @@ int txh_launch_search(const TxhIndexDev &ix, const TxhWork &w, bool local_only, 
         const uint32_t work = std::max(std::max(ix.L, w.nq), w.max_slots);
         hipLaunchKernelGGL(txh_init_kernel, dim3(std::min(1024u, ceil_div_u32(work, 256))), dim3(256), 0, st,
                            ix.L, w.nq, w.max_slots, w.leaf_cnt, w.leaf_cursor, w.counters, w.cand_cnt,
-                           w.mfma ? w.cand32_cnt : nullptr, w.pair_q);
+                           mfma ? w.cand32_cnt : nullptr, w.pair_q);
         LAUNCH_CHECK();
     }
     SCANN_TRY(launch_partition_stage(ix, w, st));
@@ -5996,7 +5928,7 @@ int txh_launch_search(const TxhIndexDev &ix, const TxhWork &w, bool local_only, 
                        w.pair_leaf, w.pair_vbase, w.pair_sbase, w.slot_of);
     LAUNCH_CHECK();
     }
-    if (ix.exact_scan) {
+    if (w.scan == TxhScan::Exact) {
         SCANN_TRY(launch_exact_scan(ix, w, st, ev0, ev1));
     } else {
     const size_t lds_lut = (size_t)4 * ix.dim * sizeof(float);
@@ -6039,12 +5971,8 @@ int txh_launch_search(const TxhIndexDev &ix, const TxhWork &w, bool local_only, 
     // capacity ~1.4 m)
     uint32_t lds_keys = std::min(kSortCap, next_pow2_u32(std::max(unsorted ? w.cap : std::min(w.cap, w.m), 64u)));
     // unsorted selection of a long list: straight from the global list, 512-thread workgroups with ~30 KB of
-    // LDS (SCANN_HIP_SELECT_DIRECT=0: stage the keys as before)
-    static const bool direct_ok = [] {
-        const char *e = std::getenv("SCANN_HIP_SELECT_DIRECT");
-        return !e || std::atoi(e) != 0;
-    }();
-    const bool direct = unsorted && direct_ok && lds_keys > 4096u;
+    // LDS (without select_direct: stage the keys as before)
+    const bool direct = unsorted && w.select_direct && lds_keys > 4096u;
     s.direct = direct ? 1u : 0u;
     s.sel_n = w.cap;
     if (direct) lds_keys = 64;
@@ -6061,11 +5989,8 @@ int txh_launch_search(const TxhIndexDev &ix, const TxhWork &w, bool local_only, 
     // int8 row filter in front of the exact re-rank (K8b): single-GPU final stage, squared L2, lists long
     // enough for the two extra kernels to pay
     // (the local stage of a leaf-sharded search takes the same two kernels in their prefix form: ShortArgs::local_head;
-    // SCANN_HIP_LOCAL_PRUNE=0: every local candidate re-ranked exactly, as before)
-    bool local_prune_ok = true;   // (read per call: the tests flip it)
-    if (local_only)
-        if (const char *e = std::getenv("SCANN_HIP_LOCAL_PRUNE")) local_prune_ok = std::atoi(e) != 0;
-    const bool i8_local = local_only && local_prune_ok && w.exact_reorder && !w.need_sorted_cands && w.k <= kTopkMaxK &&
+    // without local_prune: every local candidate re-ranked exactly, as before)
+    const bool i8_local = local_only && w.local_prune && w.exact_reorder && !w.need_sorted_cands && w.k <= kTopkMaxK &&
                           w.m > 2 * kLocalHead;
     const bool i8 = (unsorted || i8_local) && w.use_i8 && ix.rows8 && ix.measure == SCANN_HIP_SQUARED_L2 && (ix.dim & 15u) == 0;
     if (i8) {
