@@ -105,6 +105,53 @@ uint32_t scann_hip_compute_stride(uint32_t dim);
 int scann_hip_bf_create(scann_hip_ctx *ctx, const float *data, uint64_t n, uint32_t dim,
                         uint32_t stride, int measure, scann_hip_index **out_index);
 
+/* Brute force over rows the caller already stores quantized: ScalarQuantizedBruteForceSearcher
+ * (brute_force/scalar_quantized.rs:168-296) and its siblings over bf16 / FP8 rows.  rows: n rows of
+ * `stride` ELEMENTS of row_format:
+ *   SCANN_HIP_ROWS_BF16      half::bf16 bits (u16); distances = one_to_many_bf16_float_{dot_product,squared_l2}
+ *                            (distance_measures/one_to_many_asymmetric.rs:267-314): to_f32 (exact), then ONE
+ *                            sequential f32 sum per row, no FMA (dot: sum += q*x; SquaredL2: d = q - x, sum += d*d).
+ *                            BFloat16Dataset::{dot_product, squared_l2_distance} use other SIMD code and are not
+ *                            what this reproduces.
+ *   SCANN_HIP_ROWS_FP8_E4M3  the reference's Fp8Value E4M3 codes (quantization/fp8.rs, u8); distances =
+ *                            one_to_many_fp8_float_* (:327-377), the same sequential loops over to_f32_e4m3 as
+ *                            scann_hip_fp8_distances.  Not OCP e4m3fn: exponent field 0 with mantissa m != 0
+ *                            decodes to 2^-8 * (1 + m/8), 0x7F / 0xFF to +-480.
+ *   SCANN_HIP_ROWS_INT8      i8, value = (float)i8 * inv_multiplier (rounded); distances = one_to_many_int8_float_*
+ *                            in the AVX2 form the reference runs on x86 hosts (:78-142, :208-257): 8 lane chains
+ *                            of fma over full 8-element chunks, horizontal sum (lo + hi, then (t0+t1)+(t2+t3)), an
+ *                            unfused scalar tail -- the f32 brute-force arithmetic on the dequantized rows.
+ *                            inv_multiplier is ScalarQuantizedBruteForceSearcher's quantizer.scale()
+ *                            (scalar_quantized.rs:198-225), which reads the quantizer's offset-binary bytes
+ *                            (scalar.rs:162-172) as SIGNED and ignores min_value: such bytes passed here give
+ *                            exactly that reading.  inv_multiplier is ignored for the other formats.
+ * Dot products are negated; L2 = sqrtf(SquaredL2), applied before selection (scalar_quantized.rs:217-224), so
+ * ties it creates are broken by TopK's (distance, index) rule.  L1 / Cosine -> Unimplemented.
+ * Searches: k = min(k, n), TopK over all rows in index order, drained sorted; n == 0 gives empty rows; radius
+ * search = every d <= radius, stable-sorted by distance.  The handle works with scann_hip_search_batched(_params),
+ * scann_hip_index_reserve, scann_hip_search_batched_device / scann_hip_index_last_device_status,
+ * scann_hip_bf_search_radius, scann_hip_bf_distances, the introspection and timing calls, from concurrent
+ * threads as any brute-force handle.  Entry points that read rows as f32 (scann_hip_kmeans_*,
+ * scann_hip_bf_assign_nearest, Tree-X-Hybrid calls) return InvalidArgument.  opts.allow_bitmap is not applied
+ * (as for f32 brute force).  opts.bf_exact has the f32 contract: large batches on large indexes (the dims and
+ * sizes of the f32 shortlist, stride % 8 == 0) take the bf16-shortlist path, whose row operand is the stored
+ * value itself (exact in bf16 for all three formats: only the query is split); a query it cannot prove sets
+ * status Aborted, which the host entry point repeats by itself and *_device callers repeat with bf_exact = 1.
+ * The device holds the rows as given (2 or 1 byte per element), no f32 or bf16 copy, plus one f32 squared
+ * norm per row when the index qualifies for the shortlist.
+ * Errors: stride < dim, dim == 0 with n > 0, unknown row_format, rows == NULL with n > 0, non-finite
+ * inv_multiplier for INT8 -> InvalidArgument; n >= 2^32 - 1 -> OutOfRange; measure L1 / Cosine -> Unimplemented. */
+#define SCANN_HIP_ROWS_BF16 1
+#define SCANN_HIP_ROWS_FP8_E4M3 2
+#define SCANN_HIP_ROWS_INT8 3
+int scann_hip_bf_create_quantized(scann_hip_ctx *ctx, const void *rows, uint64_t n, uint32_t dim,
+                                  uint32_t stride, int row_format, float inv_multiplier, int measure,
+                                  scann_hip_index **out_index);
+/* f32_slice_to_bf16 / half::bf16::from_f32 (quantization/bfloat16.rs:13-30) on the device: round to nearest
+ * even, +-inf stay +-inf, finite values past the largest bf16 round to inf, a NaN stays a NaN
+ * ((bits >> 16) | 0x40). */
+int scann_hip_bf16_quantize(scann_hip_ctx *ctx, const float *values, uint64_t n, uint16_t *out_bits);
+
 /* ---- Tree-X-Hybrid / AsymmetricHasher ------------------------------------ */
 /* The trained index TreeXHybridSearcher::build (tree_x_hybrid/mod.rs:131-209)
  * or AsymmetricHasher::build (hashes/hasher.rs:109-134) produced, flattened:

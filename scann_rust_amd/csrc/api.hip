@@ -407,6 +407,59 @@ int scann_hip_bf_create(scann_hip_ctx *ctx, const float *data, uint64_t n, uint3
     return SCANN_HIP_OK;
 }
 
+// Rows the caller stores quantized (scann_hip.h): uploaded as given, no f32 copy and no small-batch view (bfx stays
+// empty); the bf16 shortlist reads the rows themselves and needs only their squared norms.
+int scann_hip_bf_create_quantized(scann_hip_ctx *ctx, const void *rows, uint64_t n, uint32_t dim, uint32_t stride,
+                                  int row_format, float inv_multiplier, int measure, scann_hip_index **out) {
+    if (!ctx || !out) return fail(SCANN_HIP_INVALID_ARGUMENT, "null ctx/out_index");
+    if (row_format != SCANN_HIP_ROWS_BF16 && row_format != SCANN_HIP_ROWS_FP8_E4M3 && row_format != SCANN_HIP_ROWS_INT8)
+        return fail(SCANN_HIP_INVALID_ARGUMENT, "unknown row format " + std::to_string(row_format));
+    if (n > 0 && !rows) return fail(SCANN_HIP_INVALID_ARGUMENT, "rows is null");
+    if (n > 0 && (dim == 0 || stride < dim)) return fail(SCANN_HIP_INVALID_ARGUMENT, "bad dim/stride");
+    if (row_format == SCANN_HIP_ROWS_INT8 && !std::isfinite(inv_multiplier))
+        return fail(SCANN_HIP_INVALID_ARGUMENT, "inv_multiplier is not finite");
+    if (measure == SCANN_HIP_L1 || measure == SCANN_HIP_COSINE)
+        return fail(SCANN_HIP_UNIMPLEMENTED, "quantized rows: SquaredL2, L2 and DotProduct only");
+    if (measure < SCANN_HIP_SQUARED_L2 || measure > SCANN_HIP_DOT_PRODUCT)
+        return fail(SCANN_HIP_UNIMPLEMENTED, "unknown distance measure");
+    if (n >= 0xFFFFFFFFull) return fail(SCANN_HIP_OUT_OF_RANGE, "DatapointIndex is u32");
+    SCANN_TRY(set_device(ctx));
+    auto *ix = new scann_hip_index();
+    ix->ctx = ctx;
+    ix->kind = KIND_BF;
+    const size_t bytes = (size_t)n * stride * (row_format == SCANN_HIP_ROWS_BF16 ? 2 : 1);
+    int s = index_common_init(ix);
+    if (s == SCANN_HIP_OK) s = upload(ix->bf_rows, rows, bytes);
+    if (s != SCANN_HIP_OK) {
+        scann_hip_index_destroy(ix);
+        return s;
+    }
+    ix->bf.rows = nullptr;
+    ix->bf.n = n;
+    ix->bf.dim = dim;
+    ix->bf.stride = stride;
+    ix->bf.measure = measure;
+    ix->bf.fmt = row_format;
+    ix->bf.qrows = ix->bf_rows.p;
+    ix->bf.inv_mult = row_format == SCANN_HIP_ROWS_INT8 ? inv_multiplier : 1.0f;
+    s = bf_build_shortlist_data(ix->bf, ix->bf_rows_b, ix->bf_rows_bl, ix->bf_norm2, &ix->bf.max_norm, ix->stream);
+    if (s != SCANN_HIP_OK) {
+        scann_hip_index_destroy(ix);
+        return s;
+    }
+    if (ix->bf_norm2.p) ix->bf.norm2 = ix->bf_norm2.as<float>();
+    *out = ix;
+    return SCANN_HIP_OK;
+}
+
+int scann_hip_bf16_quantize(scann_hip_ctx *ctx, const float *values, uint64_t n, uint16_t *out_bits) {
+    if (!ctx) return fail(SCANN_HIP_INVALID_ARGUMENT, "ctx is null");
+    if (n == 0) return SCANN_HIP_OK;
+    if (!values || !out_bits) return fail(SCANN_HIP_INVALID_ARGUMENT, "null values/output");
+    SCANN_TRY(set_device(ctx));
+    return bf16_quantize_host(values, n, out_bits, nullptr);
+}
+
 // =====================================================================================
 // Tree-X-Hybrid / AsymmetricHasher index
 // =====================================================================================
@@ -1858,6 +1911,7 @@ int scann_hip_bf_search_radius(scann_hip_index *ix, const float *query, uint32_t
 int scann_hip_bf_assign_nearest(scann_hip_index *ix, const float *centers, uint32_t num_centers,
                                 uint32_t *out_assign, float *out_dist) {
     if (!ix || ix->kind != KIND_BF) return fail(SCANN_HIP_INVALID_ARGUMENT, "not a brute-force index");
+    if (ix->bf.fmt) return fail(SCANN_HIP_INVALID_ARGUMENT, "the index holds quantized rows, not f32 rows");
     if (!centers || num_centers == 0 || !out_assign)
         return fail(SCANN_HIP_INVALID_ARGUMENT, "null/empty centres or output");
     std::lock_guard<std::mutex> lock(ix->mu);
@@ -1867,6 +1921,7 @@ int scann_hip_bf_assign_nearest(scann_hip_index *ix, const float *centers, uint3
 
 static int kmeans_args(scann_hip_index *ix, uint32_t col_offset, uint32_t sub_dim, uint32_t k, const void *c) {
     if (!ix || ix->kind != KIND_BF) return fail(SCANN_HIP_INVALID_ARGUMENT, "not a brute-force index");
+    if (ix->bf.fmt) return fail(SCANN_HIP_INVALID_ARGUMENT, "the index holds quantized rows, not f32 rows");
     if (ix->bf.n == 0) return fail(SCANN_HIP_INVALID_ARGUMENT, "Cannot cluster empty dataset");   // kmeans.rs:167-169
     if (!c || k == 0) return fail(SCANN_HIP_INVALID_ARGUMENT, "null centres / zero clusters");
     if (sub_dim == 0 || (uint64_t)col_offset + sub_dim > ix->bf.dim)

@@ -6,10 +6,15 @@
 namespace scann {
 
 struct BfIndexDev {
-    const float *rows;   // [n][stride]
+    const float *rows;   // [n][stride]; nullptr when the rows are quantized (fmt != 0)
     uint64_t n;
     uint32_t dim, stride;
     int measure;         // scann_hip_measure
+    // quantized rows (scann_hip_bf_create_quantized): fmt = SCANN_HIP_ROWS_BF16 / _FP8_E4M3 / _INT8, qrows =
+    // [n][stride] elements of that format; every pass takes bf_quant_kernel.  fmt 0 = f32 rows above.
+    int fmt;
+    const void *qrows;
+    float inv_mult;      // INT8: value = (float)i8 * inv_mult
     // bf16 shortlist (bf_shortlist_*): a bf16 copy of the rows [n][dim], f32 squared norms and the
     // largest row norm; nullptr when the index does not qualify (dim % 16, size)
     const uint16_t *rows_b, *rows_bl;   // hi and lo halves of the split bf16 copy
@@ -49,6 +54,9 @@ int bf_search_device(const BfIndexDev &ix, BfWorkspace &w, const float *d_querie
                      hipEvent_t ev1);
 // OK, or the status the last enqueued search left in the workspace counters (synchronises).
 int bf_last_status(const BfWorkspace &w, hipStream_t stream);
+
+// half::bf16::from_f32 over n values (scann_hip_bf16_quantize), host in / host out.
+int bf16_quantize_host(const float *values, uint64_t n, uint16_t *out_bits, hipStream_t stream);
 
 // Dense [nq][n] distance matrix to host memory.
 int bf_distances_host(const BfIndexDev &ix, BfWorkspace &w, const float *queries, uint32_t nq,

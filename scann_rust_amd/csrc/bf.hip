@@ -748,9 +748,65 @@ __global__ __launch_bounds__(256) void assign_nearest_avx_kernel(BfIndexDev ix, 
 static inline float shortlist_dot_err(uint32_t dim) {
     return 1.01f * (3.1f / 65536.0f + (3.0f * (float)dim + 64.0f) / 8388608.0f);
 }
+// Quantized rows (fmt != 0): the row operand is exact in bf16 (bf16 itself; |i8| <= 128 fits 8 significant
+// bits; every E4M3 value has <= 4 significant bits and an exponent in [-8, 8]), so only the query is split and
+// the dropped terms shrink to eq.x <= 1.1 u^2 |q||x|; the accumulation term above is kept (2 dim MFMA products
+// + the exact path's sequential sum of dim products stay under 3 dim + 64 roundings).  INT8: the MFMA scores
+// q.i8 and the pass multiplies by s once (<= 2^-24 |q||x|), while the reference sums fl(i8 s), off by
+// <= 2^-24 |i8 s| per element (<= 2^-24 |q||x| in total): + 2^-23.
+static inline float shortlist_quant_err(uint32_t dim, int fmt) {
+    return 1.01f * (1.1f / 65536.0f + (3.0f * (float)dim + 64.0f) / 8388608.0f +
+                    (fmt == SCANN_HIP_ROWS_INT8 ? 1.0f / 8388608.0f : 0.0f));
+}
 constexpr float kF32SqErr = 6.0e-5f;       // f32 rounding of the norms, of |q|^2 + |x|^2 - 2 q.x and of the
                                            // exact (q - x)^2 sum, relative to |q|^2 + |x|^2 (dim <= 256)
 constexpr uint32_t kShortMax = 256;        // largest shortlist per query
+
+// ---- element decoders of quantized rows (bf_quant_kernel, the quantized shortlist pass) ----
+typedef float f32x2q __attribute__((ext_vector_type(2)));
+
+template <int FMT>
+__host__ __device__ constexpr uint32_t quant_bytes() { return FMT == SCANN_HIP_ROWS_BF16 ? 2u : 1u; }
+
+// fp8_to_f32(b, 0) of txh.hip without branches: exponent field e and mantissa m as one 7-bit field em shifted
+// into place, biased by 120 = 127 - 7, one binade lower when e == 0 (2^-8 * (1 + m/8)), zero when em == 0.
+// The branchy form makes the compiler decode a whole 64-element block into registers before using it.
+__device__ __forceinline__ float fp8_e4m3_to_f32(uint32_t b) {
+    const uint32_t em = b & 0x7Fu;
+    const uint32_t mag = em ? (em << 20) + (em < 8u ? 119u << 23 : 120u << 23) : 0u;
+    return __uint_as_float(((b & 0x80u) << 24) | mag);
+}
+
+// element `sub` of a 32-bit word of packed row elements
+template <int FMT>
+__device__ __forceinline__ float quant_decode(uint32_t w, int sub, float inv) {
+    if (FMT == SCANN_HIP_ROWS_BF16) return __uint_as_float(sub ? (w & 0xFFFF0000u) : (w << 16));
+    const uint32_t b = (w >> (8 * sub)) & 0xFFu;
+    if (FMT == SCANN_HIP_ROWS_FP8_E4M3) return fp8_e4m3_to_f32(b);
+    return (float)(int)(int8_t)b * inv;
+}
+
+template <int FMT>
+__device__ __forceinline__ float quant_load1(const uint8_t *row, uint32_t e, float inv) {
+    if (FMT == SCANN_HIP_ROWS_BF16)
+        return __uint_as_float((uint32_t)reinterpret_cast<const uint16_t *>(row)[e] << 16);
+    if (FMT == SCANN_HIP_ROWS_FP8_E4M3) return fp8_e4m3_to_f32(row[e]);
+    return (float)(int)(int8_t)row[e] * inv;
+}
+
+// one element into an accumulator: INT8 chains fuse (_mm256_fmadd_ps), everything else is add(mul)
+template <int MEASURE, bool FUSED>
+__device__ __forceinline__ void quant_step(f32x2q &acc, f32x2q q, float x) {
+    const f32x2q xv = f32x2q{x, x};
+    if (MEASURE == SCANN_HIP_DOT_PRODUCT) {
+        if (FUSED) acc = __builtin_elementwise_fma(q, xv, acc);
+        else acc = acc + q * xv;
+    } else {
+        const f32x2q d = q - xv;
+        if (FUSED) acc = __builtin_elementwise_fma(d, d, acc);
+        else acc = acc + d * d;
+    }
+}
 
 __device__ __forceinline__ uint16_t f32_to_bf16_rne(float f) {
     const uint32_t u = __float_as_uint(f);
@@ -852,7 +908,10 @@ __device__ __forceinline__ void wait_all_but_pairs(uint32_t pairs) {
     }
 }
 
-template <int TS, int MEASURE>
+// FMT != 0 (quantized rows): the row operand is the stored value as bf16 (exact, see shortlist_quant_err; INT8:
+// the code i8, the score scaled by inv_mult), decoded by plain loads + LDS writes in the DMA's layout, and only
+// two MFMAs per k-step (x.qh + x.ql); the lo half of the stage stays unused.
+template <int TS, int MEASURE, int FMT>
 __global__ __launch_bounds__(kB16Waves * 64, (TS <= 8 ? kB16Occ : 2)) void bf_bf16_kernel(BfIndexDev ix, BfPass p,
                                                                     const uint16_t *__restrict__ qb,
                                                                     const uint16_t *__restrict__ qbl,
@@ -927,6 +986,34 @@ __global__ __launch_bounds__(kB16Waves * 64, (TS <= 8 ? kB16Occ : 2)) void bf_bf
 #pragma unroll
         for (int i = 0; i < MYI; ++i) {
             const uint32_t gi = wave + (uint32_t)kB16Waves * i;
+            if constexpr (FMT != 0) {
+                if (gi < (uint32_t)NI) {
+                    uint32_t vr = tile * RT + lane_row[i];
+                    if (last) vr = min(vr, p.nrows - 1u);
+                    const size_t e0 = (size_t)vr * p.row_mult * ix.stride + lane_col[i];
+                    const unsigned char *src = static_cast<const unsigned char *>(ix.qrows) + e0 * quant_bytes<FMT>();
+                    uint32_t w[4];
+                    if constexpr (FMT == SCANN_HIP_ROWS_BF16) {
+                        const uint4 v = *reinterpret_cast<const uint4 *>(src);
+                        w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+                    } else {
+                        const uint2 v = *reinterpret_cast<const uint2 *>(src);
+                        const uint32_t b[2] = {v.x, v.y};
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) {
+                            const uint32_t wb = b[j >> 1] >> (16 * (j & 1));
+                            // INT8: the code itself (exact in bf16); FP8: the decoded value (exact in bf16)
+                            const float lo = FMT == SCANN_HIP_ROWS_INT8 ? (float)(int)(int8_t)(wb & 0xFFu)
+                                                                        : fp8_e4m3_to_f32(wb & 0xFFu);
+                            const float hi = FMT == SCANN_HIP_ROWS_INT8 ? (float)(int)(int8_t)((wb >> 8) & 0xFFu)
+                                                                        : fp8_e4m3_to_f32((wb >> 8) & 0xFFu);
+                            w[j] = (__float_as_uint(lo) >> 16) | (__float_as_uint(hi) & 0xFFFF0000u);
+                        }
+                    }
+                    *reinterpret_cast<uint4 *>(stage + gi * 1024u + lane * 16u) = make_uint4(w[0], w[1], w[2], w[3]);
+                }
+                continue;
+            }
             if (gi < (uint32_t)NI) {
                 uint32_t vr = tile * RT + lane_row[i];
                 if (last) vr = min(vr, p.nrows - 1u);
@@ -997,11 +1084,13 @@ __global__ __launch_bounds__(kB16Waves * 64, (TS <= 8 ? kB16Occ : 2)) void bf_bf
             for (int t = 0; t < TS; ++t) {
                 const uint32_t c0 = 2u * t + h;
                 const bf16x8 a = *reinterpret_cast<const bf16x8 *>(xrow + 16u * (c0 ^ sw));
-                const bf16x8 al = *reinterpret_cast<const bf16x8 *>(xrow + TILE_B + 16u * (c0 ^ sw));
+                bf16x8 al;
+                if constexpr (FMT == 0) al = *reinterpret_cast<const bf16x8 *>(xrow + TILE_B + 16u * (c0 ^ sw));
                 acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, qf[t], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, qf[t], acc, 0, 0, 0);
+                if constexpr (FMT == 0) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, qf[t], acc, 0, 0, 0);
                 acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, ql[t], acc, 0, 0, 0);
             }
+            if constexpr (FMT == SCANN_HIP_ROWS_INT8) acc = acc * ix.inv_mult;   // q.i8 -> q.(i8 s)
             float sc[16];
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
@@ -1111,6 +1200,62 @@ __global__ __launch_bounds__(256) void bf_rerank_kernel(BfIndexDev ix, const flo
         }
         sl_exact[(size_t)q * kp + c] = MEASURE == SCANN_HIP_DOT_PRODUCT ? -r : r;   // L2: squared here
     }
+}
+
+// Quantized rows: exact score of the shortlisted rows with bf_quant_kernel's arithmetic (one_to_many_asymmetric.rs:
+// bf16 / FP8 one sequential sum; INT8 8 FMA chains + horizontal_sum_avx + unfused tail), one candidate per thread.
+template <int FMT, int MEASURE>
+__global__ __launch_bounds__(256) void bf_quant_rerank_kernel(BfIndexDev ix, const float *__restrict__ queries,
+                                                              uint32_t q_stride, uint32_t kp,
+                                                              const uint32_t *__restrict__ sl_idx,
+                                                              const uint32_t *__restrict__ sl_cnt,
+                                                              float *__restrict__ sl_exact) {
+    extern __shared__ __attribute__((aligned(16))) float s_q[];   // [dim]
+    const uint32_t q = blockIdx.y, tid = threadIdx.x, dim = ix.dim;
+    const uint32_t nsel = min(sl_cnt[q], kp);
+    if (blockIdx.x * 256u >= nsel) return;   // uniform
+    for (uint32_t j = tid; j < dim; j += blockDim.x) s_q[j] = queries[(size_t)q * q_stride + j];
+    __syncthreads();
+    const uint32_t c = blockIdx.x * 256u + tid;
+    if (c >= nsel) return;
+    constexpr bool FUSED = FMT == SCANN_HIP_ROWS_INT8;
+    const float inv = ix.inv_mult;
+    const uint8_t *row = static_cast<const uint8_t *>(ix.qrows) +
+                         (size_t)sl_idx[(size_t)q * kp + c] * ix.stride * quant_bytes<FMT>();
+    f32x2q acc[8];
+#pragma unroll
+    for (int t = 0; t < 8; ++t) acc[t] = f32x2q{0.0f, 0.0f};
+    uint32_t e = 0;
+    for (; e + 8 <= dim; e += 8)
+#pragma unroll
+        for (int t = 0; t < 8; ++t)
+            quant_step<MEASURE, FUSED>(acc[FUSED ? t : 0], f32x2q{s_q[e + t], 0.0f}, quant_load1<FMT>(row, e + t, inv));
+    float r = acc[0].x;
+    if (FUSED) {   // horizontal_sum_avx
+        const float s0 = acc[0].x + acc[4].x, s1 = acc[1].x + acc[5].x, s2 = acc[2].x + acc[6].x,
+                    s3 = acc[3].x + acc[7].x;
+        r = (s0 + s1) + (s2 + s3);
+    }
+    for (; e < dim; ++e) {
+        f32x2q rv = f32x2q{r, 0.0f};
+        quant_step<MEASURE, false>(rv, f32x2q{s_q[e], 0.0f}, quant_load1<FMT>(row, e, inv));
+        r = rv.x;
+    }
+    sl_exact[(size_t)q * kp + c] = MEASURE == SCANN_HIP_DOT_PRODUCT ? -r : r;   // L2: squared here
+}
+
+// Quantized rows: squared norms of the decoded values (sequential f32, as bf_to_bf16_kernel) for the shortlist bound.
+template <int FMT>
+__global__ void bf_quant_norms_kernel(BfIndexDev ix, float *__restrict__ norm2) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= ix.n) return;
+    const uint8_t *row = static_cast<const uint8_t *>(ix.qrows) + i * ix.stride * quant_bytes<FMT>();
+    float s2 = 0.0f;
+    for (uint32_t j = 0; j < ix.dim; ++j) {
+        const float v = quant_load1<FMT>(row, j, ix.inv_mult);
+        s2 = s2 + v * v;
+    }
+    norm2[i] = s2;
 }
 
 // per query (one wave): sort the shortlist by (exact, index), emit the first k, verify.
@@ -1298,6 +1443,128 @@ __global__ __launch_bounds__(kBfSelectThreads) void bf_select_kernel(
 }
 
 // =====================================================================================
+// Quantized rows (scann_hip_bf_create_quantized): f32 queries against bf16 / E4M3 / int8 rows,
+// one_to_many_{bf16,fp8,int8}_float_{dot_product,squared_l2} (distance_measures/one_to_many_asymmetric.rs).
+//  * BF16, FP8_E4M3 (:267-377): one sequential f32 sum per (query, row), no FMA.
+//  * INT8, the AVX2 form (:78-142, :208-257): x = (float)i8 * inv_multiplier (rounded), 8 FMA lane chains
+//    over full 8-element chunks, horizontal_sum_avx = ((c0+c4)+(c1+c5)) + ((c2+c6)+(c3+c7)), unfused tail.
+// Dot products are negated; L2 = sqrtf(SquaredL2) (brute_force/scalar_quantized.rs:217-224).
+// One row per lane, QT queries from LDS ([dim][QT], a query pair = one 8-byte broadcast read) computed in
+// pairs on the packed-f32 pipe (v_pk_*: two IEEE operations, the results of the scalar ones).  A lane reads
+// its row 64 elements at a time (8 x 16-byte loads in flight for bf16, 4 for the byte formats, so a cache line
+// of the row is consumed in one or two consecutive visits) and decodes in registers.  (128 byte-format elements
+// at a time spill: the compiler decodes them all before the first use.)
+// =====================================================================================
+template <int FMT, int MEASURE, int QT>
+__global__ __launch_bounds__(256) void bf_quant_kernel(BfIndexDev ix, BfPass p) {
+    static_assert(QT % 2 == 0, "queries travel in pairs");
+    constexpr int NCH = FMT == SCANN_HIP_ROWS_INT8 ? 8 : 1;   // accumulator chains per query
+    constexpr bool FUSED = FMT == SCANN_HIP_ROWS_INT8;
+    constexpr uint32_t B = quant_bytes<FMT>(), EPW = 4 / B, EPV = 16 / B;   // elements per word / per 16 B
+    constexpr int NV = 64 / EPV;                                             // 16-byte loads per 64 elements
+    extern __shared__ __attribute__((aligned(16))) float qs[];   // [dim][QT]
+    const uint32_t dim = ix.dim;
+    const uint32_t q0 = blockIdx.y * QT;
+    for (uint32_t i = threadIdx.x; i < QT * dim; i += blockDim.x) {
+        const uint32_t j = i / QT, qi = i - j * QT;
+        qs[i] = q0 + qi < p.nq ? p.queries[(size_t)(q0 + qi) * p.q_stride + j] : 0.0f;
+    }
+    __syncthreads();
+    const uint32_t vrow = blockIdx.x * blockDim.x + threadIdx.x;
+    if (vrow >= p.nrows) return;
+    const float inv = ix.inv_mult;
+    const uint8_t *row = static_cast<const uint8_t *>(ix.qrows) + (size_t)vrow * p.row_mult * ix.stride * B;
+    const bool vec = (((size_t)ix.stride * B) & 15u) == 0 && (reinterpret_cast<uintptr_t>(ix.qrows) & 15u) == 0;
+    f32x2q acc[QT / 2][NCH];
+#pragma unroll
+    for (int h = 0; h < QT / 2; ++h)
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) acc[h][c] = f32x2q{0.0f, 0.0f};
+    // element e0 + t of the row, t a compile-time offset with e0 % 8 == 0: chain t & 7
+    auto consume = [&](uint32_t e0, int t, float x) {
+#pragma unroll
+        for (int h = 0; h < QT / 2; ++h) {
+            const float2 qv = *reinterpret_cast<const float2 *>(qs + (size_t)(e0 + t) * QT + 2 * h);
+            quant_step<MEASURE, FUSED>(acc[h][NCH == 8 ? (t & 7) : 0], f32x2q{qv.x, qv.y}, x);
+        }
+    };
+    uint32_t e = 0;
+    if (vec) {
+        for (; e + 64 <= dim; e += 64) {
+            uint4 r[NV];
+#pragma unroll
+            for (int i = 0; i < NV; ++i) r[i] = *reinterpret_cast<const uint4 *>(row + (size_t)e * B + 16 * i);
+#pragma unroll
+            for (int i = 0; i < NV; ++i) {
+                const uint32_t w[4] = {r[i].x, r[i].y, r[i].z, r[i].w};
+#pragma unroll
+                for (int wi = 0; wi < 4; ++wi)
+#pragma unroll
+                    for (int s = 0; s < (int)EPW; ++s)
+                        consume(e, i * EPV + wi * EPW + s, quant_decode<FMT>(w[wi], s, inv));
+            }
+        }
+        for (; e + EPV <= dim; e += EPV) {
+            const uint4 r = *reinterpret_cast<const uint4 *>(row + (size_t)e * B);
+            const uint32_t w[4] = {r.x, r.y, r.z, r.w};
+#pragma unroll
+            for (int wi = 0; wi < 4; ++wi)
+#pragma unroll
+                for (int s = 0; s < (int)EPW; ++s) consume(e, wi * EPW + s, quant_decode<FMT>(w[wi], s, inv));
+        }
+    }
+    for (; e + 8 <= dim; e += 8)   // full 8-element chunks (int8: the FMA chains)
+#pragma unroll
+        for (int t = 0; t < 8; ++t) consume(e, t, quant_load1<FMT>(row, e + t, inv));
+    f32x2q r[QT / 2];
+#pragma unroll
+    for (int h = 0; h < QT / 2; ++h) {
+        if constexpr (NCH == 8) {   // horizontal_sum_avx (one_to_many_asymmetric.rs:386-399)
+            const f32x2q s0 = acc[h][0] + acc[h][4], s1 = acc[h][1] + acc[h][5];
+            const f32x2q s2 = acc[h][2] + acc[h][6], s3 = acc[h][3] + acc[h][7];
+            r[h] = (s0 + s1) + (s2 + s3);
+        } else {
+            r[h] = acc[h][0];
+        }
+    }
+    for (; e < dim; ++e) {   // bf16 / FP8: the rest of the sequential sum; int8: the unfused scalar tail
+        const float x = quant_load1<FMT>(row, e, inv);
+#pragma unroll
+        for (int h = 0; h < QT / 2; ++h) {
+            const float2 qv = *reinterpret_cast<const float2 *>(qs + (size_t)e * QT + 2 * h);
+            quant_step<MEASURE, false>(r[h], f32x2q{qv.x, qv.y}, x);
+        }
+    }
+#pragma unroll
+    for (int qi = 0; qi < QT; ++qi) {
+        if (q0 + qi >= p.nq) continue;
+        float dist = (qi & 1) ? r[qi / 2].y : r[qi / 2].x;
+        if (MEASURE == SCANN_HIP_DOT_PRODUCT) dist = -dist;
+        if (MEASURE == SCANN_HIP_L2) dist = sqrtf(dist);
+        uint64_t T = 0;
+        float Tf = 0.0f;
+        if (p.filter) {
+            T = p.thr[q0 + qi];
+            Tf = bf_thr_float(T);
+        }
+        bf_emit(p, q0 + qi, vrow, dist, Tf, T);
+    }
+}
+
+// half::bf16::from_f32 (quantization/bfloat16.rs:13-30): NaN keeps its top bits with the quiet bit set;
+// otherwise round to nearest even on bit 15 (inf stays inf, the largest finite values round up to inf).
+__global__ __launch_bounds__(256) void bf16_quantize_kernel(const float *__restrict__ values, uint64_t n,
+                                                            uint16_t *__restrict__ out) {
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) {
+        const uint32_t x = __float_as_uint(values[i]);
+        uint32_t b;
+        if ((x & 0x7FFFFFFFu) > 0x7F800000u) b = (x >> 16) | 0x40u;
+        else b = (x >> 16) + (((x & 0x8000u) && (x & 0x17FFFu)) ? 1u : 0u);
+        out[i] = (uint16_t)b;
+    }
+}
+
+// =====================================================================================
 // host side
 // =====================================================================================
 #define LAUNCH_CHECK()                                                                \
@@ -1369,8 +1636,50 @@ static bool stream_eligible(const BfIndexDev &ix, const BfPass &p) {
     return p.nq <= 16;
 }
 
+template <int FMT, int QT>
+static int launch_quant(const BfIndexDev &ix, const BfPass &p, hipStream_t st) {
+    const size_t lds = (size_t)ix.dim * QT * sizeof(float);
+    const dim3 grid(ceil_div_u32(p.nrows, 256), ceil_div_u32(p.nq, QT));
+    switch (ix.measure) {
+        case SCANN_HIP_SQUARED_L2:
+            SCANN_TRY(set_dyn_lds(bf_quant_kernel<FMT, SCANN_HIP_SQUARED_L2, QT>, lds));
+            hipLaunchKernelGGL((bf_quant_kernel<FMT, SCANN_HIP_SQUARED_L2, QT>), grid, dim3(256), lds, st, ix, p);
+            break;
+        case SCANN_HIP_L2:
+            SCANN_TRY(set_dyn_lds(bf_quant_kernel<FMT, SCANN_HIP_L2, QT>, lds));
+            hipLaunchKernelGGL((bf_quant_kernel<FMT, SCANN_HIP_L2, QT>), grid, dim3(256), lds, st, ix, p);
+            break;
+        case SCANN_HIP_DOT_PRODUCT:
+            SCANN_TRY(set_dyn_lds(bf_quant_kernel<FMT, SCANN_HIP_DOT_PRODUCT, QT>, lds));
+            hipLaunchKernelGGL((bf_quant_kernel<FMT, SCANN_HIP_DOT_PRODUCT, QT>), grid, dim3(256), lds, st, ix, p);
+            break;
+        default:
+            return fail(SCANN_HIP_UNIMPLEMENTED, "quantized rows: SquaredL2, L2 and DotProduct only");
+    }
+    LAUNCH_CHECK();
+    return SCANN_HIP_OK;
+}
+
+// quantized rows: every pass (sample, filter, dense matrix, radius) on bf_quant_kernel; one query pair per
+// workgroup row for the one- and two-query searches, four pairs otherwise
+static int launch_quant_pass(const BfIndexDev &ix, const BfPass &p, hipStream_t st) {
+    const bool few = p.nq <= 2;
+    switch (ix.fmt) {
+        case SCANN_HIP_ROWS_BF16:
+            return few ? launch_quant<SCANN_HIP_ROWS_BF16, 2>(ix, p, st) : launch_quant<SCANN_HIP_ROWS_BF16, 8>(ix, p, st);
+        case SCANN_HIP_ROWS_FP8_E4M3:
+            return few ? launch_quant<SCANN_HIP_ROWS_FP8_E4M3, 2>(ix, p, st)
+                       : launch_quant<SCANN_HIP_ROWS_FP8_E4M3, 8>(ix, p, st);
+        case SCANN_HIP_ROWS_INT8:
+            return few ? launch_quant<SCANN_HIP_ROWS_INT8, 2>(ix, p, st) : launch_quant<SCANN_HIP_ROWS_INT8, 8>(ix, p, st);
+        default:
+            return fail(SCANN_HIP_INVALID_ARGUMENT, "unknown row format");
+    }
+}
+
 // name of the kernel launch_pass picks for a batch of nq queries (timing reports)
 const char *bf_pass_kernel_name(const BfIndexDev &ix, uint32_t nq) {
+    if (ix.fmt) return "bf_quant_kernel";
     BfPass p{};
     p.nq = nq;
     if (stream_eligible(ix, p)) return "bf_stream_kernel";
@@ -1381,6 +1690,7 @@ const char *bf_pass_kernel_name(const BfIndexDev &ix, uint32_t nq) {
 
 static int launch_pass(const BfIndexDev &ix, const BfPass &p, hipStream_t st) {
     if (p.nq == 0 || p.nrows == 0) return SCANN_HIP_OK;
+    if (ix.fmt) return launch_quant_pass(ix, p, st);
     if (stream_eligible(ix, p)) {
         const uint32_t dimp = (ix.dim + 3u) & ~3u;
         const size_t lds = ((size_t)kStQT * dimp + 4u * 64u * kStLd) * sizeof(float);
@@ -1571,14 +1881,33 @@ int bf_build_shortlist_data(const BfIndexDev &ix, DevBuf &rows_b, DevBuf &rows_b
     // SCANN_HIP_BF_SHORTLIST_MIN_ROWS: below this the exact kernels are fast enough (tests set 1)
     if (ix.n < read_knobs().bf_shortlist_min_rows) return SCANN_HIP_OK;
     if (ix.measure > SCANN_HIP_DOT_PRODUCT) return SCANN_HIP_OK;   // L1 / Cosine: no bf16 bound is derived for them
-    SCANN_TRY(rows_b.ensure((size_t)ix.n * ix.dim * 2));
-    SCANN_TRY(rows_bl.ensure((size_t)ix.n * ix.dim * 2));
+    // quantized rows: the pass reads 8 elements per load (stride % 8) and needs only the norms, no row copy
+    if (ix.fmt && ((ix.stride & 7u) || (reinterpret_cast<uintptr_t>(ix.qrows) & 15u))) return SCANN_HIP_OK;
+    if (!ix.fmt) {
+        SCANN_TRY(rows_b.ensure((size_t)ix.n * ix.dim * 2));
+        SCANN_TRY(rows_bl.ensure((size_t)ix.n * ix.dim * 2));
+    }
     SCANN_TRY(norm2.ensure((size_t)ix.n * 4));
     DevBuf mx;
     SCANN_TRY(mx.ensure(4));
     SCANN_HIP_CHECK(hipMemsetAsync(mx.p, 0, 4, st));
-    hipLaunchKernelGGL(bf_to_bf16_kernel, dim3((uint32_t)ceil_div_u64(ix.n, 256)), dim3(256), 0, st, ix.rows,
-                       ix.n, ix.dim, ix.stride, rows_b.as<uint16_t>(), rows_bl.as<uint16_t>(), norm2.as<float>());
+    const dim3 grid_n((uint32_t)ceil_div_u64(ix.n, 256));
+    switch (ix.fmt) {
+        case SCANN_HIP_ROWS_BF16:
+            hipLaunchKernelGGL(bf_quant_norms_kernel<SCANN_HIP_ROWS_BF16>, grid_n, dim3(256), 0, st, ix, norm2.as<float>());
+            break;
+        case SCANN_HIP_ROWS_FP8_E4M3:
+            hipLaunchKernelGGL(bf_quant_norms_kernel<SCANN_HIP_ROWS_FP8_E4M3>, grid_n, dim3(256), 0, st, ix,
+                               norm2.as<float>());
+            break;
+        case SCANN_HIP_ROWS_INT8:
+            hipLaunchKernelGGL(bf_quant_norms_kernel<SCANN_HIP_ROWS_INT8>, grid_n, dim3(256), 0, st, ix, norm2.as<float>());
+            break;
+        default:
+            hipLaunchKernelGGL(bf_to_bf16_kernel, grid_n, dim3(256), 0, st, ix.rows, ix.n, ix.dim, ix.stride,
+                               rows_b.as<uint16_t>(), rows_bl.as<uint16_t>(), norm2.as<float>());
+            break;
+    }
     LAUNCH_CHECK();
     hipLaunchKernelGGL(bf_max_norm_kernel, dim3(256), dim3(256), 0, st, norm2.as<float>(), ix.n,
                        mx.as<uint32_t>());
@@ -1596,14 +1925,14 @@ int bf_build_shortlist_data(const BfIndexDev &ix, DevBuf &rows_b, DevBuf &rows_b
 static uint32_t shortlist_size(uint32_t k) { return std::min(kShortMax, std::max(32u, 4u * k)); }
 
 bool bf_shortlist_eligible(const BfIndexDev &ix, uint32_t nq, uint32_t k, const Knobs &kn) {
-    if (!ix.rows_b || !ix.rows_bl || !ix.norm2) return false;
+    if (!ix.norm2 || (!ix.fmt && (!ix.rows_b || !ix.rows_bl))) return false;   // quantized rows: norms only
     if (!(ix.max_norm == ix.max_norm) || std::isinf(ix.max_norm)) return false;
     if (k == 0 || 4u * k > kShortMax) return false;
     if ((uint64_t)shortlist_size(k) * 8 > ix.n) return false;   // a shortlist that is most of the data
     return nq >= kn.bf_shortlist_min_queries;
 }
 
-template <int TS>
+template <int TS, int FMT>
 static int launch_bf16(const BfIndexDev &ix, const BfPass &p, const uint16_t *qb, const uint16_t *qbl,
                        const float *qn2, hipStream_t st) {
     const uint32_t ny = ceil_div_u32(p.nq, kB16Waves * 32);
@@ -1614,28 +1943,67 @@ static int launch_bf16(const BfIndexDev &ix, const BfPass &p, const uint16_t *qb
     const size_t lds = (size_t)kB16Ring * (2 * 32 * kB16Sub * (TS * 16) * 2 + 256) +   // (hi | lo | norms) stages
                        16;
     if (ix.measure == SCANN_HIP_DOT_PRODUCT) {
-        SCANN_TRY(set_dyn_lds((bf_bf16_kernel<TS, SCANN_HIP_DOT_PRODUCT>), lds));
-        hipLaunchKernelGGL((bf_bf16_kernel<TS, SCANN_HIP_DOT_PRODUCT>), dim3(nx * ny), dim3(kB16Waves * 64), lds, st,
-                           ix, p, qb, qbl, qn2, nx, ny);
+        SCANN_TRY(set_dyn_lds((bf_bf16_kernel<TS, SCANN_HIP_DOT_PRODUCT, FMT>), lds));
+        hipLaunchKernelGGL((bf_bf16_kernel<TS, SCANN_HIP_DOT_PRODUCT, FMT>), dim3(nx * ny), dim3(kB16Waves * 64), lds,
+                           st, ix, p, qb, qbl, qn2, nx, ny);
     } else {
-        SCANN_TRY(set_dyn_lds((bf_bf16_kernel<TS, SCANN_HIP_SQUARED_L2>), lds));
-        hipLaunchKernelGGL((bf_bf16_kernel<TS, SCANN_HIP_SQUARED_L2>), dim3(nx * ny), dim3(kB16Waves * 64), lds, st,
-                           ix, p, qb, qbl, qn2, nx, ny);
+        SCANN_TRY(set_dyn_lds((bf_bf16_kernel<TS, SCANN_HIP_SQUARED_L2, FMT>), lds));
+        hipLaunchKernelGGL((bf_bf16_kernel<TS, SCANN_HIP_SQUARED_L2, FMT>), dim3(nx * ny), dim3(kB16Waves * 64), lds,
+                           st, ix, p, qb, qbl, qn2, nx, ny);
     }
     LAUNCH_CHECK();
     return SCANN_HIP_OK;
 }
 
-static int launch_bf16_pass(const BfIndexDev &ix, const BfPass &p, const uint16_t *qb, const uint16_t *qbl,
+template <int FMT>
+static int launch_bf16_dims(const BfIndexDev &ix, const BfPass &p, const uint16_t *qb, const uint16_t *qbl,
                             const float *qn2, hipStream_t st) {
     switch (ix.dim / 16) {
-        case 2: return launch_bf16<2>(ix, p, qb, qbl, qn2, st);
-        case 4: return launch_bf16<4>(ix, p, qb, qbl, qn2, st);
-        case 6: return launch_bf16<6>(ix, p, qb, qbl, qn2, st);
-        case 8: return launch_bf16<8>(ix, p, qb, qbl, qn2, st);
-        case 12: return launch_bf16<12>(ix, p, qb, qbl, qn2, st);
-        default: return launch_bf16<16>(ix, p, qb, qbl, qn2, st);
+        case 2: return launch_bf16<2, FMT>(ix, p, qb, qbl, qn2, st);
+        case 4: return launch_bf16<4, FMT>(ix, p, qb, qbl, qn2, st);
+        case 6: return launch_bf16<6, FMT>(ix, p, qb, qbl, qn2, st);
+        case 8: return launch_bf16<8, FMT>(ix, p, qb, qbl, qn2, st);
+        case 12: return launch_bf16<12, FMT>(ix, p, qb, qbl, qn2, st);
+        default: return launch_bf16<16, FMT>(ix, p, qb, qbl, qn2, st);
     }
+}
+
+static int launch_bf16_pass(const BfIndexDev &ix, const BfPass &p, const uint16_t *qb, const uint16_t *qbl,
+                            const float *qn2, hipStream_t st) {
+    switch (ix.fmt) {
+        case SCANN_HIP_ROWS_BF16: return launch_bf16_dims<SCANN_HIP_ROWS_BF16>(ix, p, qb, qbl, qn2, st);
+        case SCANN_HIP_ROWS_FP8_E4M3: return launch_bf16_dims<SCANN_HIP_ROWS_FP8_E4M3>(ix, p, qb, qbl, qn2, st);
+        case SCANN_HIP_ROWS_INT8: return launch_bf16_dims<SCANN_HIP_ROWS_INT8>(ix, p, qb, qbl, qn2, st);
+        default: return launch_bf16_dims<0>(ix, p, qb, qbl, qn2, st);
+    }
+}
+
+template <int FMT, int MEASURE>
+static void launch_quant_rerank(const BfIndexDev &ix, const float *d_queries, uint32_t q_stride, uint32_t kp,
+                                BfWorkspace &w, uint32_t nq, hipStream_t st) {
+    hipLaunchKernelGGL((bf_quant_rerank_kernel<FMT, MEASURE>), dim3(ceil_div_u32(kp, 256), nq), dim3(256),
+                       (size_t)ix.dim * 4, st, ix, d_queries, q_stride, kp, w.sl_idx.as<uint32_t>(),
+                       w.sl_cnt.as<uint32_t>(), w.sl_exact.as<float>());
+}
+
+// exact re-score of the shortlist of quantized rows (SquaredL2 serves L2: the final kernel takes the root)
+template <int MEASURE>
+static int launch_rerank(const BfIndexDev &ix, const float *d_queries, uint32_t q_stride, uint32_t kp, BfWorkspace &w,
+                         uint32_t nq, hipStream_t st) {
+    switch (ix.fmt) {
+        case SCANN_HIP_ROWS_BF16: launch_quant_rerank<SCANN_HIP_ROWS_BF16, MEASURE>(ix, d_queries, q_stride, kp, w, nq, st); break;
+        case SCANN_HIP_ROWS_FP8_E4M3:
+            launch_quant_rerank<SCANN_HIP_ROWS_FP8_E4M3, MEASURE>(ix, d_queries, q_stride, kp, w, nq, st);
+            break;
+        case SCANN_HIP_ROWS_INT8: launch_quant_rerank<SCANN_HIP_ROWS_INT8, MEASURE>(ix, d_queries, q_stride, kp, w, nq, st); break;
+        default:
+            hipLaunchKernelGGL(bf_rerank_kernel<MEASURE>, dim3(ceil_div_u32(kp, 32), nq), dim3(256), (size_t)ix.dim * 4, st,
+                               ix, d_queries, q_stride, kp, w.sl_idx.as<uint32_t>(), w.sl_cnt.as<uint32_t>(),
+                               w.sl_exact.as<float>());
+            break;
+    }
+    LAUNCH_CHECK();
+    return SCANN_HIP_OK;
 }
 
 // bf16 scores -> shortlist of kp rows -> exact re-score -> first k + verification
@@ -1720,28 +2088,23 @@ static int enqueue_shortlist_search(const BfIndexDev &ix, BfWorkspace &w, uint32
                        w.sl_idx.as<uint32_t>(), w.sl_approx.as<float>(), w.sl_cnt.as<uint32_t>());
     LAUNCH_CHECK();
     // 4. exact f32 score of the shortlist, 5. first k + verification
-    const size_t lds_rr = (size_t)ix.dim * 4;
-    dim3 grid(ceil_div_u32(kp, 32), nq);
+    const float err = ix.fmt ? shortlist_quant_err(ix.dim, ix.fmt) : shortlist_dot_err(ix.dim);
     if (ix.measure == SCANN_HIP_DOT_PRODUCT) {
-        hipLaunchKernelGGL(bf_rerank_kernel<SCANN_HIP_DOT_PRODUCT>, grid, dim3(256), lds_rr, st, ix, d_queries,
-                           q_stride, kp, w.sl_idx.as<uint32_t>(), w.sl_cnt.as<uint32_t>(), w.sl_exact.as<float>());
-        LAUNCH_CHECK();
+        SCANN_TRY(launch_rerank<SCANN_HIP_DOT_PRODUCT>(ix, d_queries, q_stride, kp, w, nq, st));
         hipLaunchKernelGGL(bf_shortlist_final_kernel<SCANN_HIP_DOT_PRODUCT>, dim3(nq), dim3(64), 0, st, n, k, kp,
-                           ix.max_norm, shortlist_dot_err(ix.dim), w.q_n2.as<float>(), w.thr.as<uint64_t>(), w.sl_idx.as<uint32_t>(), w.sl_approx.as<float>(),
+                           ix.max_norm, err, w.q_n2.as<float>(), w.thr.as<uint64_t>(), w.sl_idx.as<uint32_t>(), w.sl_approx.as<float>(),
                            w.sl_cnt.as<uint32_t>(), w.sl_exact.as<float>(), w.counters.as<uint32_t>(),
                            w.sl_fail.as<uint32_t>(), d_out_idx, d_out_dist, d_out_count);
     } else {
-        hipLaunchKernelGGL(bf_rerank_kernel<SCANN_HIP_SQUARED_L2>, grid, dim3(256), lds_rr, st, ix, d_queries,
-                           q_stride, kp, w.sl_idx.as<uint32_t>(), w.sl_cnt.as<uint32_t>(), w.sl_exact.as<float>());
-        LAUNCH_CHECK();
+        SCANN_TRY(launch_rerank<SCANN_HIP_SQUARED_L2>(ix, d_queries, q_stride, kp, w, nq, st));
         if (ix.measure == SCANN_HIP_L2)
             hipLaunchKernelGGL(bf_shortlist_final_kernel<SCANN_HIP_L2>, dim3(nq), dim3(64), 0, st, n, k, kp,
-                               ix.max_norm, shortlist_dot_err(ix.dim), w.q_n2.as<float>(), w.thr.as<uint64_t>(), w.sl_idx.as<uint32_t>(), w.sl_approx.as<float>(),
+                               ix.max_norm, err, w.q_n2.as<float>(), w.thr.as<uint64_t>(), w.sl_idx.as<uint32_t>(), w.sl_approx.as<float>(),
                                w.sl_cnt.as<uint32_t>(), w.sl_exact.as<float>(), w.counters.as<uint32_t>(),
                                w.sl_fail.as<uint32_t>(), d_out_idx, d_out_dist, d_out_count);
         else
             hipLaunchKernelGGL(bf_shortlist_final_kernel<SCANN_HIP_SQUARED_L2>, dim3(nq), dim3(64), 0, st, n, k, kp,
-                               ix.max_norm, shortlist_dot_err(ix.dim), w.q_n2.as<float>(), w.thr.as<uint64_t>(), w.sl_idx.as<uint32_t>(), w.sl_approx.as<float>(),
+                               ix.max_norm, err, w.q_n2.as<float>(), w.thr.as<uint64_t>(), w.sl_idx.as<uint32_t>(), w.sl_approx.as<float>(),
                                w.sl_cnt.as<uint32_t>(), w.sl_exact.as<float>(), w.counters.as<uint32_t>(),
                                w.sl_fail.as<uint32_t>(), d_out_idx, d_out_dist, d_out_count);
     }
@@ -1848,6 +2211,19 @@ int bf_search_host(const BfIndexDev &ix, BfWorkspace &w, const float *queries, u
         if (!retry) return fail((int)counters[BF_CNT_STATUS], "device reported a search failure");
     }
     return fail(SCANN_HIP_INTERNAL, "unreachable");
+}
+
+int bf16_quantize_host(const float *values, uint64_t n, uint16_t *out_bits, hipStream_t st) {
+    if (n == 0) return SCANN_HIP_OK;
+    DevBuf dv, dout;
+    SCANN_TRY(upload(dv, values, (size_t)n * 4));
+    SCANN_TRY(dout.ensure((size_t)n * 2));
+    const uint32_t blocks = (uint32_t)std::min<uint64_t>(ceil_div_u64(n, 256), 65535);
+    hipLaunchKernelGGL(bf16_quantize_kernel, dim3(blocks), dim3(256), 0, st, dv.as<float>(), n, dout.as<uint16_t>());
+    LAUNCH_CHECK();
+    SCANN_HIP_CHECK(hipMemcpyAsync(out_bits, dout.p, (size_t)n * 2, hipMemcpyDeviceToHost, st));
+    SCANN_HIP_CHECK(hipStreamSynchronize(st));
+    return SCANN_HIP_OK;
 }
 
 int bf_distances_host(const BfIndexDev &ix, BfWorkspace &w, const float *queries, uint32_t nq,

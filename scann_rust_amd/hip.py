@@ -25,7 +25,8 @@ _CODE_NAMES = {
 
 EXPORTS = [
     "scann_hip_init", "scann_hip_shutdown", "scann_hip_last_error", "scann_hip_version",
-    "scann_hip_compute_stride", "scann_hip_bf_create", "scann_hip_txh_create",
+    "scann_hip_compute_stride", "scann_hip_bf_create", "scann_hip_bf_create_quantized", "scann_hip_bf16_quantize",
+    "scann_hip_txh_create",
     "scann_hip_search_opts_default", "scann_hip_search_batched", "scann_hip_search_batched_params", "scann_hip_index_reserve",
     "scann_hip_search_batched_device", "scann_hip_index_last_device_status",
     "scann_hip_txh_search_local_device", "scann_hip_txh_merge_device",
@@ -56,6 +57,7 @@ class ScannError(RuntimeError):
 f32p = C.POINTER(C.c_float)
 u32p = C.POINTER(C.c_uint32)
 u64p = C.POINTER(C.c_uint64)
+u16p = C.POINTER(C.c_uint16)
 u8p = C.POINTER(C.c_uint8)
 vp = C.c_void_p
 
@@ -119,6 +121,9 @@ def load():
     L.scann_hip_compute_stride.argtypes = [C.c_uint32]
     L.scann_hip_bf_create.argtypes = [vp, f32p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int,
                                       C.POINTER(vp)]
+    L.scann_hip_bf_create_quantized.argtypes = [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.c_float,
+                                                C.c_int, C.POINTER(vp)]
+    L.scann_hip_bf16_quantize.argtypes = [vp, f32p, C.c_uint64, u16p]
     L.scann_hip_txh_create.argtypes = [vp, C.POINTER(TxhDesc), C.POINTER(vp)]
     L.scann_hip_txh_write_file.argtypes = [C.c_char_p, C.POINTER(TxhDesc)]
     L.scann_hip_bf_write_file.argtypes = [C.c_char_p, f32p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int]
@@ -321,6 +326,44 @@ def bf_create(data, n, dim, stride, measure, device=0):
     check(load().scann_hip_bf_create(context(device), ptr(d, f32p) if n else None, n, dim,
                                      stride, measure, C.byref(h)))
     return Index(h)
+
+
+ROWS_BF16, ROWS_FP8_E4M3, ROWS_INT8 = 1, 2, 3
+_ROWS_DTYPE = {ROWS_BF16: np.uint16, ROWS_FP8_E4M3: np.uint8, ROWS_INT8: np.int8}
+
+
+def bf_create_quantized(rows, n, dim, stride, fmt, measure, inv_multiplier=1.0, device=0):
+    """Brute force over rows stored as bf16 bits (uint16), the reference's E4M3 codes (uint8) or int8
+    (value = i8 * inv_multiplier): scann_hip_bf_create_quantized.  The returned Index's search methods,
+    bf_distances and bf_search_radius work as for bf_create."""
+    dt = _ROWS_DTYPE.get(fmt, np.uint8)
+    r = np.ascontiguousarray(rows).view(dt) if n else None
+    if r is not None and r.size < n * stride:
+        raise ValueError("rows holds %d elements, n * stride = %d" % (r.size, n * stride))
+    h = vp()
+    check(load().scann_hip_bf_create_quantized(context(device), r.ctypes.data if n else None, n, dim, stride, fmt,
+                                               float(np.float32(inv_multiplier)), measure, C.byref(h)))
+    return Index(h)
+
+
+def bf16_quantize(values, device=0):
+    """half::bf16::from_f32 (quantization/bfloat16.rs:13-30) on the device: uint16 bits."""
+    v = f32(values)
+    out = np.zeros(v.shape, np.uint16)
+    check(load().scann_hip_bf16_quantize(context(device), ptr(v, f32p), v.size, ptr(out, u16p)))
+    return out
+
+
+def symmetric_int8(rows):
+    """Host helper: symmetric per-dataset int8 codes, s = max|x| / 127, i8 = round(x / s) (half to even), and
+    inv_multiplier = s.  NOT the reference's ScalarQuantizer, which writes offset-binary bytes
+    (quantization/scalar.rs:162-172); bf_create_quantized reads any bytes as signed, exactly as
+    ScalarQuantizedBruteForceSearcher does (brute_force/scalar_quantized.rs:198-225)."""
+    x = np.asarray(rows, np.float32)
+    m = float(np.max(np.abs(x))) if x.size else 0.0
+    s = np.float32(m / 127.0) if m > 0 else np.float32(1.0)
+    codes = np.clip(np.rint(x / s), -127, 127).astype(np.int8)
+    return codes, float(s)
 
 
 def txh_create(*, data, n_rows, dim, stride, centers, leaf_offsets, leaf_ids, codebook, codes,
