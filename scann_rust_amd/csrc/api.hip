@@ -336,8 +336,13 @@ float scann_hip_index_last_kernel_ms(scann_hip_index *ix, const char **name) {
     uint32_t ok = 0;
     for (uint32_t i = 0; i < cnt; ++i) {   // mean over the recorded launches
         float ms = 0.0f;
-        if (hipEventSynchronize(ix->evs[i][1]) != hipSuccess) continue;
-        if (hipEventElapsedTime(&ms, ix->evs[i][0], ix->evs[i][1]) != hipSuccess) continue;
+        // a pair handed to a call that failed before recording it (k > kBfMaxK, say) has no time: skip it and
+        // clear the error the query leaves behind, or the next search's launch check reports it as its own
+        if (hipEventSynchronize(ix->evs[i][1]) != hipSuccess ||
+            hipEventElapsedTime(&ms, ix->evs[i][0], ix->evs[i][1]) != hipSuccess) {
+            (void)hipGetLastError();
+            continue;
+        }
         sum += ms;
         ++ok;
     }

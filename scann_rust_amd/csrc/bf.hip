@@ -1271,8 +1271,13 @@ __global__ __launch_bounds__(64) void bf_shortlist_final_kernel(
     const uint32_t nsel = min(sl_cnt[q], kp);
     uint32_t n2 = 1;
     while (n2 < nsel) n2 <<= 1;
-    for (uint32_t i = tid; i < n2; i += nt)
-        skeys[i] = i < nsel ? make_key(sl_exact[(size_t)q * kp + i], sl_idx[(size_t)q * kp + i]) : SCANN_KEY_MAX;
+    // L2: key on the root, as the exact kernels do -- two squared distances can round to one L2 distance, and
+    // those rows tie and go by index
+    for (uint32_t i = tid; i < n2; i += nt) {
+        float e = i < nsel ? sl_exact[(size_t)q * kp + i] : 0.0f;
+        if (MEASURE == SCANN_HIP_L2) e = sqrtf(e);
+        skeys[i] = i < nsel ? make_key(e, sl_idx[(size_t)q * kp + i]) : SCANN_KEY_MAX;
+    }
     __syncthreads();
     bitonic_sort_lds(skeys, n2);
     const uint32_t nout = min(k, nsel);
@@ -1282,7 +1287,6 @@ __global__ __launch_bounds__(64) void bf_shortlist_final_kernel(
         if (i < nout) {
             id = (uint32_t)skeys[i];
             d = ordered_to_f32((uint32_t)(skeys[i] >> 32));
-            if (MEASURE == SCANN_HIP_L2) d = sqrtf(d);
         }
         out_idx[(size_t)q * k + i] = id;
         out_dist[(size_t)q * k + i] = d;
@@ -1295,12 +1299,15 @@ __global__ __launch_bounds__(64) void bf_shortlist_final_kernel(
             // shortlist shorter than kp holds EVERY row that passed the filter, so the rest score
             // >= the filter's bound
             const float floor_b = nsel == kp ? sl_approx[(size_t)q * kp + kp - 1] : bf_thr_float(thr[q]);
-            const float dk = ordered_to_f32((uint32_t)(skeys[k - 1] >> 32));   // k-th exact (squared for L2)
+            const float dk = ordered_to_f32((uint32_t)(skeys[k - 1] >> 32));   // k-th exact (the root for L2)
             const float qn = sqrtf(qn2[q]);
             float E;
             if (MEASURE == SCANN_HIP_DOT_PRODUCT) E = dot_err * qn * max_norm;
             else E = 2.0f * dot_err * qn * max_norm + kF32SqErr * (qn * qn + max_norm * max_norm);
-            ok = dk < floor_b - E * 1.0001f;         // NaNs compare false -> exact path
+            // L2: every row outside scores >= floor_b - E squared, so its root is >= the root of that (sqrtf is
+            // monotone); strictly above dk, no root ties it
+            const float lb = floor_b - E * 1.0001f;
+            ok = MEASURE == SCANN_HIP_L2 ? dk < sqrtf(lb) : dk < lb;   // NaNs compare false -> exact path
         }
         fail_flag[q] = ok ? 0u : 1u;
         if (!ok) atomicMax(&counters[BF_CNT_STATUS], (uint32_t)SCANN_HIP_ABORTED);
