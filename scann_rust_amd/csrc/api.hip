@@ -951,15 +951,15 @@ static int plan_txh_search(const scann_hip_index *ix, uint32_t k, const scann_hi
     return SCANN_HIP_OK;
 }
 
-// The kernel scann_hip_index_last_kernel_ms names for a search run on `p`.  pinned: the host entry's small / wide
-// pipeline with queries and results in pinned memory; every other call is named by its batched-pipeline scan (also
-// when a device entry point or staged outputs run it on a small pipeline).
-static const char *txh_kernel_name(const TxhPlan &p, bool pinned) {
+// The kernel scann_hip_index_last_kernel_ms names for a search run on `p` over `t`.  pinned: the host entry's small /
+// wide pipeline with queries and results in pinned memory; every other call is named by its batched-pipeline scan
+// (also when a device entry point or staged outputs run it on a small pipeline).
+static const char *txh_kernel_name(const TxhIndexDev &t, const TxhPlan &p, bool pinned) {
     if (pinned) return p.pipeline == TxhPipeline::Wide ? "wide_scan_kernel" : "small_scan_kernel";
     switch (p.scan) {
         case TxhScan::Exact: return "leaf_exact_scan_kernel";
         case TxhScan::Mfma16: return "adc_mfma16_kernel";
-        case TxhScan::Smfmac: return "adc_smfmac_kernel";
+        case TxhScan::Smfmac: return t.S > 32 ? "adc_smfmac_wide_kernel" : "adc_smfmac_kernel";
         case TxhScan::Mfma32: return "adc_mfma_kernel";
         case TxhScan::Resident: return "adc_scan_res_kernel";
         default: return "adc_scan_kernel";
@@ -1315,7 +1315,7 @@ static int txh_search_host(scann_hip_index *ix, const float *queries, uint32_t n
                                         sl.primary ? ix->ev1 : nullptr));
             if (sl.primary) {
                 ix->timing_valid = ix->timing;
-                ix->timed_kernel = txh_kernel_name(p, /*pinned=*/true);
+                ix->timed_kernel = txh_kernel_name(ix->tx, p, /*pinned=*/true);
             }
             SCANN_TRY(wait_small_done(stream, reinterpret_cast<const volatile uint32_t *>(hp + off_flag), nq, seq));
             if (p.pipeline == TxhPipeline::Wide) {   // the wide pipeline's compact arrays can overflow: count row 0xFFFFFFFF -> the batched pipeline
@@ -1340,7 +1340,7 @@ static int txh_search_host(scann_hip_index *ix, const float *queries, uint32_t n
         SCANN_TRY(txh_launch_search(ix->tx, w, false, stream, sl.primary ? ix->ev0 : nullptr,
                                     sl.primary ? ix->ev1 : nullptr));
         if (sl.primary) ix->timing_valid = ix->timing;
-        if (sl.primary) ix->timed_kernel = txh_kernel_name(p, /*pinned=*/false);
+        if (sl.primary) ix->timed_kernel = txh_kernel_name(ix->tx, p, /*pinned=*/false);
         uint32_t counters[CNT_N];
         SCANN_HIP_CHECK(hipMemcpyAsync(counters, w.counters, sizeof(counters), hipMemcpyDeviceToHost,
                                        stream));
@@ -1581,7 +1581,7 @@ int scann_hip_search_batched_device(scann_hip_index *ix, const float *d_queries,
                                 ix->ev1));
     SCANN_TRY(device_slot_done(dsl, st));
     ix->timing_valid = ix->timing;
-    ix->timed_kernel = txh_kernel_name(p, /*pinned=*/false);
+    ix->timed_kernel = txh_kernel_name(ix->tx, p, /*pinned=*/false);
     return SCANN_HIP_OK;
 }
 
@@ -1645,7 +1645,7 @@ int scann_hip_txh_search_local_device(scann_hip_index *ix, const float *d_querie
                                 ix->ev1));
     SCANN_TRY(device_slot_done(dsl, st));
     ix->timing_valid = ix->timing;
-    ix->timed_kernel = txh_kernel_name(p, /*pinned=*/false);
+    ix->timed_kernel = txh_kernel_name(ix->tx, p, /*pinned=*/false);
     return SCANN_HIP_OK;
 }
 

@@ -241,3 +241,148 @@ def bf16_split_ties(n, dim, seed):
         x[r, lo_dims] = np.float32(1.0 + 2.0 ** -8)
     q = np.full((4, dim), 1.0 + 2.0 ** -9, np.float32) * np.array([1, 2, 4, 0.5], np.float32)[:, None]
     return x, q
+
+
+# ---- explicit-codebook indexes for the tree / flat hasher scans (tests/test_gpu_txh_subspaces.py) -------------------
+# Codebooks and codes are written down, not trained: numpy k-means never sees the pathological tables, and the codes
+# need not be anyone's nearest codeword (the reference's ADC scan only reads them).
+PQ_FAMILIES = ("one-code", "flat", "flat-one", "dominant", "loose", "integers", "tiny", "huge", "nonfinite")
+PQ_HUGE_EXP = 62
+
+
+def pq_tables(codebook, q):
+    """[S, K] f32 LUT of query q, with the reference's arithmetic (oracle lut_from_query)"""
+    return orc.lut_from_query(codebook, q).reshape(codebook.shape[0], codebook.shape[1])
+
+
+def adversarial_pq(family, n, dim, S, nq, seed):
+    """(codebook [S, 16, dim / S] f32, codes [n, S] u8, rows [n, dim] f32, queries [nq, dim] f32) of one family.
+
+    one-code  every row has code row A, every 1000th row code row B: all approximate distances tie in two groups,
+              and the survivors of any bound overflow the candidate lists of a stream of >= ~30k points
+    flat      every subspace's 16 codewords are equal: tables without a range (scale 0, every point passes)
+    flat-one  subspace 1 alone is flat
+    dominant  subspace 0's codewords (and the data / queries there) spread 2^20 wider than the rest: the int8 step is
+              set by one subspace, every other one quantises to a few steps (a coarse, loose filter)
+    loose     codeword 0 of every subspace lies far from every query and most rows use it in all but two subspaces: the
+              bound sits beyond half of the int8 sum range (the sparse prefilter's coarser-scale branch)
+    integers  codewords, rows and queries in {-2, ..., 2}: exact tables, massive exact ties at the bound
+    tiny      everything x 2^-70: table entries are subnormal or zero
+    huge      everything x 2^62: every table entry is finite, sums of S entries overflow to +inf (asserted)
+    nonfinite codeword 5 of subspace 2 is +-1e20: that table entry is +inf (the pair is not quantised: all pass)
+    """
+    assert dim % S == 0
+    dsub = dim // S
+    rng = np.random.default_rng([seed, 7, S])
+    cb = rng.uniform(-1.0, 1.0, (S, 16, dsub)).astype(np.float32)
+    codes = rng.integers(0, 16, (n, S)).astype(np.uint8)
+    q = rng.uniform(-1.0, 1.0, (nq, dim)).astype(np.float32)
+    noise = 0.1
+    if family == "one-code":
+        rows_ab = rng.integers(0, 16, (2, S)).astype(np.uint8)
+        codes[:] = rows_ab[0]
+        codes[::1000] = rows_ab[1]
+    elif family == "flat":
+        cb[:] = cb[:, :1]
+    elif family == "flat-one":
+        cb[1] = cb[1, :1]
+    elif family == "dominant":
+        cb[0] *= np.float32(2.0 ** 20)
+        q[:, :dsub] *= np.float32(2.0 ** 20)
+    elif family == "loose":
+        cb[:, 0] = 5.0
+        far = rng.random((n, S)) < 0.999
+        far[np.arange(n), rng.integers(0, S, n)] = False
+        far[np.arange(n), rng.integers(0, S, n)] = False
+        codes[far] = 0
+        codes[~far] = rng.integers(1, 16, int((~far).sum())).astype(np.uint8)
+    elif family == "integers":
+        cb = rng.integers(-2, 3, (S, 16, dsub)).astype(np.float32)
+        q = rng.integers(-2, 3, (nq, dim)).astype(np.float32)
+    elif family == "nonfinite":
+        cb[2, 5] = np.where(rng.random(dsub) < 0.5, -1e20, 1e20).astype(np.float32)
+    elif family not in ("tiny", "huge"):
+        raise ValueError(family)
+    rows = cb[np.arange(S)[None, :], codes].reshape(n, dim)
+    if family == "integers":
+        rows = np.clip(rows + rng.integers(-1, 2, (n, dim)), -2, 2).astype(np.float32)
+    elif family == "nonfinite":
+        rows = np.clip(rows, -1.0, 1.0) + np.float32(noise) * rng.uniform(-1.0, 1.0, (n, dim)).astype(np.float32)
+    else:
+        rows = rows + np.float32(noise) * rng.uniform(-1.0, 1.0, (n, dim)).astype(np.float32)
+    if family in ("tiny", "huge"):
+        f = np.float32(2.0 ** (-70 if family == "tiny" else PQ_HUGE_EXP))
+        cb, rows, q = cb * f, rows * f, q * f
+    rows = np.ascontiguousarray(rows, np.float32)
+    if family == "huge":
+        for qi in q:
+            t = pq_tables(cb, qi)
+            assert np.all(np.isfinite(t)), "huge: a single table entry overflowed"
+            with np.errstate(over="ignore"):
+                assert np.isinf(t.max(1).sum(dtype=np.float32)), "huge: a sum of S entries stays finite"
+    if family == "nonfinite":
+        assert all(np.isinf(pq_tables(cb, qi)[2, 5]) for qi in q)
+    return cb, codes, rows, np.ascontiguousarray(q, np.float32)
+
+
+def pq_loose_bound_reached(codebook, codes, q, m):
+    """True when the m-th smallest approximate distance of q puts the sparse prefilter's bound past half of the int8
+    sum range (txh.hip lut8_build_kernel: qmax > 128 S - 1 takes the coarser scale; the sampled bound is >= it)."""
+    t = pq_tables(codebook, q).astype(np.float64)
+    S = t.shape[0]
+    _, od = orc.ah_search(codebook, codes, q, m)
+    T = float(od[-1])
+    sc = float((t.max(1) - t.min(1)).max()) / 255.0
+    tq = T * (1.0 + S * 2.0 ** -23) - float(t.min(1).sum())
+    return sc > 0 and np.floor(tq / sc + 0.5 * S + 1.0) > 128.0 * S - 1.0
+
+
+def ah_kwargs_from_codes(rows, codebook, codes):
+    """hip.txh_create kwargs of a flat hasher over explicit codes (the AsymmetricHasher view)."""
+    n, dim = rows.shape
+    data, stride = orc.to_strided(rows)
+    return dict(data=data, n_rows=n, dim=dim, stride=stride, centers=None, leaf_offsets=None, leaf_ids=None,
+                codebook=codebook, codes=np.ascontiguousarray(codes, np.uint8), codes_packed4=False,
+                use_residuals=False, partitions_to_search=1, pre_reorder_multiplier=1.0)
+
+
+def txh_from_codes(rows, codebook, codes, L, P, mult, seed, use_residuals=True):
+    """(oracle TxhIndex, hip.txh_create kwargs) of a tree index over explicit codes: L centres picked among the rows,
+    every row in its nearest centre's leaf (f64 distances, the lowest centre on ties), leaves in ascending row order,
+    the codes in that CSR order (read against the residual to the leaf centre when use_residuals)."""
+    n, dim = rows.shape
+    rng = np.random.default_rng([seed, 9])
+    centers = np.ascontiguousarray(rows[np.sort(rng.choice(n, L, replace=False))], np.float32)
+    c64 = centers.astype(np.float64)
+    assign = np.empty(n, np.int64)
+    for r0 in range(0, n, 8192):
+        x = rows[r0:r0 + 8192].astype(np.float64)
+        assign[r0:r0 + 8192] = ((x[:, None, :] - c64[None]) ** 2).sum(2).argmin(1)
+    order = np.argsort(assign, kind="stable").astype(np.uint32)
+    leaf_off = np.zeros(L + 1, np.uint32)
+    leaf_off[1:] = np.cumsum(np.bincount(assign, minlength=L))
+    csr_codes = np.ascontiguousarray(codes[order], np.uint8)
+    data, stride = orc.to_strided(rows)
+    oix = orc.TxhIndex(data, stride, dim, centers, leaf_off, order, codebook, csr_codes, use_residuals=use_residuals,
+                       partitions_to_search=P, pre_reorder_multiplier=mult)
+    kw = dict(data=data, n_rows=n, dim=dim, stride=stride, centers=centers, leaf_offsets=leaf_off, leaf_ids=order,
+              codebook=codebook, codes=csr_codes, codes_packed4=False, use_residuals=use_residuals,
+              partitions_to_search=P, pre_reorder_multiplier=mult)
+    return oix, kw
+
+
+def check_ah_query(codebook, codes, data, stride, dim, query, k, m, got_idx, got_dist, got_ci, got_cd, what=""):
+    """Stage-aware parity check of one AsymmetricHasher::search_with_reordering query (as check_txh_query): the sorted
+    approximate candidate distances bitwise equal to the oracle's, memberships equal up to their ties; final rows
+    equal to the oracle's if the candidate sets agree, else to the oracle's re-rank of the GPU's candidate list."""
+    oci, ocd = orc.ah_search(codebook, codes, query, m)
+    assert got_ci.size == oci.size, "%s candidate count %d vs %d" % (what, got_ci.size, oci.size)
+    assert np.array_equal(np.asarray(got_cd, np.float32).view(np.uint32), ocd.view(np.uint32)), \
+        "%s approximate distances differ" % what
+    assert_topk_equal_up_to_ties(got_ci, got_cd, oci, ocd, what=what + " cand")
+    if sorted(got_ci.tolist()) == sorted(oci.tolist()):
+        oi, od = orc.ah_search_with_reordering(codebook, codes, data, stride, query, k, m)
+    else:
+        oi, od = orc.reorder(data, stride, dim, query, got_ci, k)
+    assert got_idx.size == oi.size, "%s final count %d vs %d" % (what, got_idx.size, oi.size)
+    assert_topk_equal_up_to_ties(got_idx, got_dist, oi, od, what=what + " final")

@@ -1,0 +1,360 @@
+"""Flat hasher (AH) and tree (Tree-X-Hybrid) searches at every subspace count the scan kernels are compiled for, and on
+explicit codebooks built to hit the int8 prefilter's special cases, each compared with the ORACLE.
+
+txh.hip launch_scan_stages takes 4-bit codes at S = 8, 16, 24, 32, 48 and 64.  Every scan it can launch there is forced
+through its knobs and asserted by the name scann_hip_index_last_kernel_ms reports:
+
+    gather      SCANN_HIP_MFMA=0 SCANN_HIP_RESIDENT=0                adc_scan_kernel
+    resident    SCANN_HIP_MFMA=0 SCANN_HIP_RESIDENT=2                adc_scan_res_kernel (S <= 32), else adc_scan_kernel
+    dense32     SCANN_HIP_SMFMAC=0 at index creation, SCANN_HIP_MFMA=2   adc_mfma_kernel
+    mfma16      SCANN_HIP_MFMA=3                                     adc_mfma16_kernel
+    sp-lanes    SCANN_HIP_SMFMAC=1 SCANN_HIP_MFMA=2 SCANN_HIP_SP_WORDS=0   adc_smfmac_kernel (S <= 32) /
+    sp-words    ... SCANN_HIP_SP_WORDS=1                             adc_smfmac_wide_kernel (S = 48, 64)
+    default     no knobs, a batch and leaves large enough for the sparse prefilter
+
+Distances must match the oracle bitwise; indices may differ only inside ties.  The adversarial families of
+tests/helpers.py adversarial_pq (explicit codebooks and codes) cross the forced scans at S = 16 and 48 on both index
+kinds, on the host entry (with its retry after a candidate-list overflow) and on the device entry (no retry: Ok with the
+host's rows, or a failure status with count 0 for the failed queries)."""
+import ctypes
+
+import numpy as np
+import pytest
+
+from oracle import pyoracle as orc
+from scann_rust_amd import hip, synth, trainer
+from tests import helpers as H
+
+pytestmark = pytest.mark.gpu
+
+ABORTED = 10   # scann_hip.h SCANN_HIP_ABORTED: a statistical bound that kept fewer than m points
+
+KNOBS = ("SCANN_HIP_MFMA", "SCANN_HIP_SMFMAC", "SCANN_HIP_RESIDENT", "SCANN_HIP_SP_WORDS", "SCANN_HIP_SMALL",
+         "SCANN_HIP_WIDE", "SCANN_HIP_FUSED", "SCANN_HIP_RERANK_I8", "SCANN_HIP_RERANK_I8_MIN", "SCANN_HIP_RERANK_STORE",
+         "SCANN_HIP_RERANK_UNIFORM", "SCANN_HIP_THR_TIES", "SCANN_HIP_THR_TAIL", "SCANN_HIP_SELECT_DIRECT")
+SCANS = {
+    "gather": {"SCANN_HIP_MFMA": "0", "SCANN_HIP_RESIDENT": "0"},
+    "resident": {"SCANN_HIP_MFMA": "0", "SCANN_HIP_RESIDENT": "2"},
+    "dense32": {"SCANN_HIP_SMFMAC": "0", "SCANN_HIP_MFMA": "2"},
+    "mfma16": {"SCANN_HIP_MFMA": "3"},
+    "sp-lanes": {"SCANN_HIP_SMFMAC": "1", "SCANN_HIP_MFMA": "2", "SCANN_HIP_SP_WORDS": "0"},
+    "sp-words": {"SCANN_HIP_SMFMAC": "1", "SCANN_HIP_MFMA": "2", "SCANN_HIP_SP_WORDS": "1"},
+    "default": {},
+}
+SUBSPACES = (8, 16, 24, 32, 48, 64)
+# dims per subspace 1, 2 and odd across each index kind
+AH_DIM = {8: 40, 16: 16, 24: 72, 32: 32, 48: 48, 64: 128}
+TXH_DIM = {8: 16, 16: 48, 24: 48, 32: 96, 48: 144, 64: 64}
+
+
+def _env(monkeypatch, scan):
+    """Set the knobs of `scan` (before the index is created: SMFMAC=0 then builds no operand planes)."""
+    for name in KNOBS:
+        monkeypatch.delenv(name, raising=False)
+    for name, val in SCANS[scan].items():
+        monkeypatch.setenv(name, val)
+
+
+def _sparse_name(S):
+    return "adc_smfmac_kernel" if S <= 32 else "adc_smfmac_wide_kernel"
+
+
+def _expected(scan, S):
+    if scan == "gather" or (scan == "resident" and S > 32):
+        return "adc_scan_kernel"     # (the resident layout holds S <= 32)
+    return {"resident": "adc_scan_res_kernel", "dense32": "adc_mfma_kernel", "mfma16": "adc_mfma16_kernel"}.get(
+        scan, _sparse_name(S))
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def _device_search(index, q, k, o):
+    """scann_hip_search_batched_device on torch's current stream: (status, idx, dist, count) after the call."""
+    import torch
+    dev = torch.device("cuda:0")
+    L = hip.load()
+    p = lambda t: ctypes.c_void_p(t.data_ptr())
+    nq, dim = q.shape
+    qd = torch.from_numpy(np.ascontiguousarray(q, np.float32)).to(dev)
+    oi = torch.full((nq, k), -1, dtype=torch.int32, device=dev)
+    od = torch.zeros((nq, k), dtype=torch.float32, device=dev)
+    oc = torch.full((nq,), 7, dtype=torch.int32, device=dev)
+    st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    torch.cuda.synchronize()
+    hip.check(L.scann_hip_search_batched_device(index.h, p(qd), nq, dim, k, ctypes.byref(o), p(oi), p(od), p(oc), st))
+    status = L.scann_hip_index_last_device_status(index.h, st)
+    torch.cuda.synchronize()
+    return status, oi.cpu().numpy().view(np.uint32), od.cpu().numpy(), oc.cpu().numpy().view(np.uint32)
+
+
+def _fast_equals_staged(fast, staged, what):
+    """the unsorted fast path's rows = the staged path's: counts and distances bitwise, indices up to ties"""
+    idx2, dist2, cnt2 = fast
+    idx, dist, cnt = staged[:3]
+    assert np.array_equal(cnt2, cnt), what + ": counts"
+    assert np.array_equal(_bits(dist2), _bits(dist)), what + ": distances"
+    for i in range(idx.shape[0]):
+        H.assert_topk_equal_up_to_ties(idx2[i, :cnt[i]], dist2[i, :cnt[i]], idx[i, :cnt[i]], dist[i, :cnt[i]],
+                                       what="%s fast q%d" % (what, i))
+
+
+# ---- A. every subspace count x every scan -------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def trained():
+    """trained cases, built once per (kind, S) and module"""
+    cache = {}
+
+    def get(kind, S):
+        if (kind, S) not in cache:
+            if kind == "ah":
+                dim = AH_DIM[S]
+                rows, data, stride, ix, kw = H.make_ah_case(60000, dim, S, seed=100 + S, pq_iters=3)
+                q = synth.uniform_f32(64, dim, 200 + S)
+                cache[kind, S] = dict(kw=kw, ix=ix, data=data, stride=stride, q=q, oix=None)
+            else:
+                dim = TXH_DIM[S]
+                rows, data, stride, ix, oix, kw = H.make_txh_case(80000, dim, 16, S, seed=300 + S, P=6, mult=25.0,
+                                                                  kmeans_iters=3, pq_iters=3, clustered=True)
+                assert int(np.diff(ix["leaf_off"]).mean()) >= 4096
+                q = synth.clustered_f32(96, dim, 400 + S, n_clusters=16)[0]
+                cache[kind, S] = dict(kw=kw, ix=ix, data=data, stride=stride, q=q, oix=oix)
+        return cache[kind, S]
+
+    yield get
+    cache.clear()
+
+
+def _opts(kind):
+    o = hip.default_opts()
+    if kind == "ah":
+        o.pre_reorder_k = 300
+    else:
+        o.partitions_to_search, o.pre_reorder_k = 6, 250
+    return o
+
+
+def _check_rows(kind, c, o, q, k, staged, qs, what):
+    """staged outputs of queries qs against the oracle, stage by stage"""
+    idx, dist, cnt, (tok, tokd, ci, cd, cc) = staged
+    for i in qs:
+        w = "%s q%d" % (what, i)
+        if kind == "ah":
+            H.check_ah_query(c["ix"]["codebook"], c["ix"]["codes"], c["data"], c["stride"], q.shape[1], q[i], k,
+                             o.pre_reorder_k, idx[i, :cnt[i]], dist[i, :cnt[i]], ci[i, :cc[i]], cd[i, :cc[i]], what=w)
+        else:
+            H.check_txh_query(c["oix"], q[i], k, idx[i, :cnt[i]], dist[i, :cnt[i]], tok[i], tokd[i], ci[i, :cc[i]],
+                              cd[i, :cc[i]], what=w)
+
+
+@pytest.mark.parametrize("scan", list(SCANS))
+@pytest.mark.parametrize("S", SUBSPACES)
+@pytest.mark.parametrize("kind", ["ah", "txh"])
+def test_every_scan_at_every_subspace_count(trained, kind, S, scan, monkeypatch):
+    """AsymmetricHasher::search_with_reordering on a flat 60k-row hasher (pre_reorder_k 300) and
+    TreeXHybridSearcher::search on a clustered 80k-row tree of 16 leaves (P 6, m 250), both with a filter bound in
+    force, under each forced scan (and the default heuristics, which take the sparse prefilter here): the named
+    kernel ran, the staged outputs match the oracle, the fast path's rows equal the staged path's."""
+    c = trained(kind, S)
+    _env(monkeypatch, scan)
+    index = hip.txh_create(**c["kw"])
+    index.enable_timing(True)
+    o, q, k = _opts(kind), c["q"], 10
+    staged = index.search_batched(q, k, o, stages=True)
+    assert index.last_kernel_ms()[1] == _expected(scan, S)
+    _check_rows(kind, c, o, q, k, staged, range(0, q.shape[0], 6), "%s S%d %s" % (kind, S, scan))
+    fast = index.search_batched(q, k, o)
+    assert index.last_kernel_ms()[1] == _expected(scan, S)
+    _fast_equals_staged(fast, staged, "%s S%d %s" % (kind, S, scan))
+
+
+@pytest.mark.parametrize("S", [48, 64])
+@pytest.mark.parametrize("kind", ["ah", "txh"])
+def test_few_query_pipelines_at_wide_subspace_counts(trained, kind, S, monkeypatch):
+    """At S = 48 and 64: the small three-launch pipeline (SCANN_HIP_FUSED=0), its one-launch form (flat hashers), the
+    wide pipeline (SCANN_HIP_WIDE=2, 1-4 queries) and scann_hip_search_batched_device (wide, small and batched calls)
+    return rows bitwise equal to the batched pipeline's (SCANN_HIP_SMALL=0) for the same queries, and the oracle's."""
+    c = trained(kind, S)
+    _env(monkeypatch, "default")
+    index = hip.txh_create(**c["kw"])
+    index.enable_timing(True)
+    o, k = _opts(kind), 10
+    q = c["q"][:32]
+    monkeypatch.setenv("SCANN_HIP_SMALL", "0")
+    ref = index.search_batched(q, k, o)
+    assert index.last_kernel_ms()[1] == _sparse_name(S)
+
+    def same(got, lo, what):
+        nq = got[0].shape[0]
+        assert np.array_equal(got[2], ref[2][lo:lo + nq]), what + ": counts"
+        assert np.array_equal(_bits(got[1]), _bits(ref[1][lo:lo + nq])), what + ": distances"
+        assert np.array_equal(got[0], ref[0][lo:lo + nq]), what + ": indices"
+
+    monkeypatch.delenv("SCANN_HIP_SMALL")
+    monkeypatch.setenv("SCANN_HIP_WIDE", "0")
+    for fused in ("0", "1"):
+        monkeypatch.setenv("SCANN_HIP_FUSED", fused)
+        for lo, nq in ((0, 1), (3, 7), (16, 16)):
+            same(index.search_batched(q[lo:lo + nq], k, o), lo, "small fused=%s q%d+%d" % (fused, lo, nq))
+            assert index.last_kernel_ms()[1] == "small_scan_kernel"
+    monkeypatch.delenv("SCANN_HIP_FUSED")
+    monkeypatch.setenv("SCANN_HIP_WIDE", "2")
+    for lo, nq in ((0, 1), (5, 2), (28, 4)):
+        same(index.search_batched(q[lo:lo + nq], k, o), lo, "wide q%d+%d" % (lo, nq))
+        assert index.last_kernel_ms()[1] == "wide_scan_kernel"
+    for lo, nq in ((0, 4), (8, 12), (0, 32)):
+        status, di, dd, dc = _device_search(index, q[lo:lo + nq], k, o)
+        assert status == hip.OK, (lo, nq, status)
+        same((di, dd, dc), lo, "device q%d+%d" % (lo, nq))
+    monkeypatch.delenv("SCANN_HIP_WIDE")
+    for i in (0, 5, 31):
+        cnt = ref[2][i]
+        if kind == "ah":
+            oi, od = orc.ah_search_with_reordering(c["ix"]["codebook"], c["ix"]["codes"], c["data"], c["stride"], q[i],
+                                                   k, o.pre_reorder_k)
+        else:
+            oi, od = orc.txh_search(c["oix"], q[i], k)
+        assert cnt == oi.size
+        H.assert_topk_equal_up_to_ties(ref[0][i, :cnt], ref[1][i, :cnt], oi, od, what="oracle q%d" % i)
+
+
+@pytest.mark.parametrize("S", [4, 8, 16])
+def test_byte_codes_ignore_the_forced_prefilter(S, monkeypatch):
+    """8-bit codes (K = 256) have no int8 prefilter: SCANN_HIP_MFMA=2 falls back to the gather kernel, exact."""
+    n, dim, k, pre_k = 20000, 32, 10, 200
+    rows = synth.uniform_f32(n, dim, 500 + S)
+    rng = np.random.default_rng(S)
+    dsub = dim // S
+    pick = rng.choice(n, 256, replace=False)
+    cb = np.ascontiguousarray(rows[pick].reshape(256, S, dsub).transpose(1, 0, 2), np.float32)   # [S, 256, dsub]
+    codes = trainer.encode(cb, rows, chunk=2048)
+    kw = H.ah_kwargs_from_codes(rows, cb, codes)
+    _env(monkeypatch, "dense32")
+    index = hip.txh_create(**kw)
+    index.enable_timing(True)
+    q = synth.uniform_f32(32, dim, 600 + S)
+    o = hip.default_opts()
+    o.pre_reorder_k = pre_k
+    idx, dist, cnt = index.search_batched(q, k, o)
+    assert index.last_kernel_ms()[1] == "adc_scan_kernel"
+    for i in range(0, 32, 3):
+        oi, od = orc.ah_search_with_reordering(cb, codes, kw["data"], kw["stride"], q[i], k, pre_k)
+        assert cnt[i] == oi.size
+        H.assert_topk_equal_up_to_ties(idx[i, :cnt[i]], dist[i, :cnt[i]], oi, od, what="S%d q%d" % (S, i))
+
+
+# ---- B. adversarial tables for the prefilter ----------------------------------------------------------------------
+ADV_N, ADV_NQ, ADV_L, ADV_P, ADV_M = 60000, 32, 8, 5, 250
+ADV_DIM = {16: 32, 48: 48}
+ADV_SCANS = ("gather", "dense32", "mfma16", "sp-words")
+
+
+@pytest.fixture(scope="module")
+def adversarial():
+    """explicit-codebook cases, built once per (family, kind, S) and module"""
+    cache = {}
+
+    def get(family, kind, S):
+        if (family, kind, S) not in cache:
+            cb, codes, rows, q = H.adversarial_pq(family, ADV_N, ADV_DIM[S], S, ADV_NQ, seed=S)
+            if kind == "ah":
+                kw, oix = H.ah_kwargs_from_codes(rows, cb, codes), None
+            else:
+                # (one-code: tables of the raw query, so that the ties span every leaf)
+                oix, kw = H.txh_from_codes(rows, cb, codes, ADV_L, ADV_P, ADV_M / 10.0, seed=S,
+                                           use_residuals=family != "one-code")
+            cache[family, kind, S] = dict(kw=kw, oix=oix, ix=dict(codebook=cb, codes=kw["codes"]), data=kw["data"],
+                                          stride=kw["stride"], q=q)
+        return cache[family, kind, S]
+
+    yield get
+    cache.clear()
+
+
+def _adv_opts(kind):
+    o = hip.default_opts()
+    o.pre_reorder_k = ADV_M
+    if kind == "txh":
+        o.partitions_to_search = ADV_P
+    return o
+
+
+@pytest.mark.parametrize("scan", ADV_SCANS)
+@pytest.mark.parametrize("S", [16, 48])
+@pytest.mark.parametrize("kind", ["ah", "txh"])
+@pytest.mark.parametrize("family", H.PQ_FAMILIES)
+def test_adversarial_tables_every_prefilter(adversarial, family, kind, S, scan, monkeypatch):
+    """Each adversarial family under each forced scan: the device entry (no retry) runs the forced kernel and returns
+    Ok with the host's rows, or a failure status with count 0 for the failed queries -- never a wrong row; the host
+    entry's staged outputs match the oracle stage by stage, and its fast path's rows equal them."""
+    c = adversarial(family, kind, S)
+    _env(monkeypatch, scan)
+    index = hip.txh_create(**c["kw"])
+    index.enable_timing(True)
+    o, q, k = _adv_opts(kind), c["q"], 10
+    want = _expected(scan, S)
+    what = "%s %s S%d %s" % (family, kind, S, scan)
+    status, di, dd, dc = _device_search(index, q, k, o)
+    assert index.last_kernel_ms()[1] == want
+    assert status in (hip.OK, hip.RESOURCE_EXHAUSTED, ABORTED), status
+    staged = index.search_batched(q, k, o, stages=True)
+    # after a failed first attempt the host entry's second one scans without a bound (the gather kernel)
+    assert index.last_kernel_ms()[1] == want or (status != hip.OK and index.last_kernel_ms()[1] == "adc_scan_kernel")
+    _check_rows(kind, c, o, q, k, staged, range(0, ADV_NQ, 8), what)
+    fast = index.search_batched(q, k, o)
+    _fast_equals_staged(fast, staged, what)
+    idx, dist, cnt = fast
+    failed = dc == 0
+    if status == hip.OK:
+        assert not failed.any(), what + ": count 0 under status Ok"
+    else:
+        assert failed.any(), what + ": a failure status without a failed query"
+    ok = ~failed
+    assert np.array_equal(dc[ok], cnt[ok]), what + ": device counts"
+    assert np.array_equal(_bits(dd[ok]), _bits(dist[ok])), what + ": device distances"
+    for i in np.flatnonzero(ok):
+        H.assert_topk_equal_up_to_ties(di[i, :cnt[i]], dd[i, :cnt[i]], idx[i, :cnt[i]], dist[i, :cnt[i]],
+                                       what="%s device q%d" % (what, i))
+
+
+@pytest.mark.parametrize("scan", ["gather", "dense32", "sp-lanes", "sp-words"])
+@pytest.mark.parametrize("S", [16, 48])
+@pytest.mark.parametrize("kind", ["ah", "txh"])
+def test_one_code_overflows_the_candidate_lists(adversarial, kind, S, scan, monkeypatch):
+    """All rows on one code row (every 1000th on a second): the points tie at the bound, and the survivors outnumber
+    the prefilter's list (cap32 = min(stream, 4 cap + 16384)) or the gather scan's (cap).  The device entry reports
+    ResourceExhausted with count 0 for every query; the host entry retries once without a bound and returns the
+    oracle's rows."""
+    c = adversarial("one-code", kind, S)
+    _env(monkeypatch, scan)
+    index = hip.txh_create(**c["kw"])
+    index.enable_timing(True)
+    o, q, k = _adv_opts(kind), c["q"], 10     # (> 16 queries: the batched pipeline, which has a bound)
+    what = "one-code %s S%d %s" % (kind, S, scan)
+    if kind == "txh":
+        o.partitions_to_search = ADV_L     # every leaf: a stream of all rows
+    status, di, dd, dc = _device_search(index, q, k, o)
+    assert index.last_kernel_ms()[1] == _expected(scan, S)
+    assert status == hip.RESOURCE_EXHAUSTED, status
+    assert np.all(dc == 0)
+    staged = index.search_batched(q, k, o, stages=True)
+    assert index.last_kernel_ms()[1] == "adc_scan_kernel"      # the retry: no bound, every point a candidate
+    oix = c["oix"]
+    if oix is not None:
+        oix.partitions_to_search = ADV_L
+    try:
+        _check_rows(kind, c, o, q, k, staged, range(q.shape[0]), what)
+    finally:
+        if oix is not None:
+            oix.partitions_to_search = ADV_P
+    _fast_equals_staged(index.search_batched(q, k, o), staged, what)
+
+
+def test_loose_bound_takes_the_coarser_scale(adversarial):
+    """The `loose` family really puts the sparse prefilter's bound past half of the int8 sum range (on the flat
+    hasher's tables; the sampled bound the kernel folds is only larger than the m-th distance checked here)."""
+    for S in (16, 48):
+        c = adversarial("loose", "ah", S)
+        reached = [H.pq_loose_bound_reached(c["ix"]["codebook"], c["ix"]["codes"], qi, ADV_M) for qi in c["q"][:8]]
+        assert all(reached), (S, reached)
