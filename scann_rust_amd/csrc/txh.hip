@@ -3802,7 +3802,9 @@ __global__ __launch_bounds__(256) void rerank_i8_kernel(uint32_t dim, I8RerankAr
             // of the two dim-term sums (each <= (dim + 4) 2^-24 relative) + slack on the bound itself
             const float slack = (2.0f * sqrtf(acc) * E + E * E) * 1.0001f + acc * ((float)(dim + 8) * 1.2e-7f) + 1e-30f;
             float L = acc - slack, U = acc + slack;
-            if (!(slack == slack) || !(acc == acc)) {   // NaN anywhere: never filtered out, never a bound for others
+            // NaN or overflow anywhere (an infinite d~ would make L = inf - inf = NaN, which orders above +inf and
+            // drops the candidate): never filtered out, never a bound for others
+            if (!(slack < __builtin_inff()) || !(acc < __builtin_inff())) {
                 L = -__builtin_inff();
                 U = __builtin_inff();
             }
@@ -3883,7 +3885,10 @@ __global__ __launch_bounds__(256) void rerank_short_kernel(TxhIndexDev ix, Short
     }
     __syncthreads();
     const uint32_t ns = s_ns;
-    const bool fast = ns <= kShortMaxFast;
+    // (a shortlist under nout rows means a bracket did not hold: the query is re-ranked without the filter, and the
+    // fast path's nout arg-min rounds never run past s_pos[ns - 1])
+    const bool unfiltered = ns < nout;
+    const bool fast = ns <= kShortMaxFast && !unfiltered;
     // exact distances of the shortlist: rerank_kernel's arithmetic (8 FMA lane chains, fixed hsum tree,
     // unfused tail: simd/x86.rs:139-165, 31-44)
     const uint32_t chunks = ix.dim >> 3, lane8 = tid & 7u;
@@ -3903,7 +3908,7 @@ __global__ __launch_bounds__(256) void rerank_short_kernel(TxhIndexDev ix, Short
             listed[u] = false;
             if (act[u]) {
                 ci[u] = fast ? s_pos[jx[u]] : jx[u];
-                listed[u] = fast || ci[u] < head || a.lb[(size_t)q * m + ci[u]] <= tau;
+                listed[u] = fast || unfiltered || ci[u] < head || a.lb[(size_t)q * m + ci[u]] <= tau;
             }
             rowp[u] = ix.rows + (size_t)(listed[u] ? a.cand_row[(size_t)q * m + ci[u]] : 0u) * ix.stride;
         }

@@ -346,17 +346,19 @@ def ah_kwargs_from_codes(rows, codebook, codes):
                 use_residuals=False, partitions_to_search=1, pre_reorder_multiplier=1.0)
 
 
-def txh_from_codes(rows, codebook, codes, L, P, mult, seed, use_residuals=True):
+def txh_from_codes(rows, codebook, codes, L, P, mult, seed, use_residuals=True, tree_rows=None):
     """(oracle TxhIndex, hip.txh_create kwargs) of a tree index over explicit codes: L centres picked among the rows,
     every row in its nearest centre's leaf (f64 distances, the lowest centre on ties), leaves in ascending row order,
-    the codes in that CSR order (read against the residual to the leaf centre when use_residuals)."""
+    the codes in that CSR order (read against the residual to the leaf centre when use_residuals).  `tree_rows`: the
+    rows the centres and the assignment are taken from, when they are not the indexed rows."""
     n, dim = rows.shape
+    tr = rows if tree_rows is None else tree_rows
     rng = np.random.default_rng([seed, 9])
-    centers = np.ascontiguousarray(rows[np.sort(rng.choice(n, L, replace=False))], np.float32)
+    centers = np.ascontiguousarray(tr[np.sort(rng.choice(n, L, replace=False))], np.float32)
     c64 = centers.astype(np.float64)
     assign = np.empty(n, np.int64)
     for r0 in range(0, n, 8192):
-        x = rows[r0:r0 + 8192].astype(np.float64)
+        x = tr[r0:r0 + 8192].astype(np.float64)
         assign[r0:r0 + 8192] = ((x[:, None, :] - c64[None]) ** 2).sum(2).argmin(1)
     order = np.argsort(assign, kind="stable").astype(np.uint32)
     leaf_off = np.zeros(L + 1, np.uint32)
@@ -386,3 +388,174 @@ def check_ah_query(codebook, codes, data, stride, dim, query, k, m, got_idx, got
         oi, od = orc.reorder(data, stride, dim, query, got_ci, k)
     assert got_idx.size == oi.size, "%s final count %d vs %d" % (what, got_idx.size, oi.size)
     assert_topk_equal_up_to_ties(got_idx, got_dist, oi, od, what=what + " final")
+
+
+# ---- rows for the re-rank row filter (tests/test_gpu_rerank_rows.py, tests/rerank_filter_model.py) -------------------
+# The codebook and codes only choose the candidates: they are written down (codes = the nearest codeword of each row's
+# unit-scale `base`), and the rows the re-rank reads are the family's.  The overflow families keep the codebook and the
+# queries at unit scale, so that the scan's approximate distances stay finite while the exact ones overflow.
+RERANK_FAMILIES = ("offset", "overflow-all", "overflow-most", "near-overflow", "tiny", "magnitudes", "spike", "permuted",
+                   "duplicates", "nonfinite")
+RERANK_OVERFLOW_EXP = 62
+RERANK_FINITE_STRIDE = 1000   # overflow-most: rows i % 1000 == 7 stay finite (at most 9 of them below 10 000 rows)
+FLT_MAX = float(np.finfo(np.float32).max)
+
+
+def rerank_subspaces(dim):
+    return 16 if dim % 16 == 0 else 8
+
+
+def encode_codes(codebook, base):
+    """[n, S] u8: the nearest codeword of every subspace of the unit-scale rows (float64)"""
+    S, K, dsub = codebook.shape
+    x = np.asarray(base, np.float64).reshape(base.shape[0], S, dsub)
+    cb = codebook.astype(np.float64)
+    codes = np.empty((base.shape[0], S), np.uint8)
+    for s in range(S):
+        codes[:, s] = ((x[:, s, None, :] - cb[None, s]) ** 2).sum(2).argmin(1)
+    return codes
+
+
+def overflow_finite_rows(n):
+    return np.arange(7, n, RERANK_FINITE_STRIDE)
+
+
+def _exact_all(rows, q):
+    """[nq, n] oracle f32 SquaredL2 distances of every row"""
+    data, stride = orc.to_strided(rows)
+    return np.stack([orc.one_to_many(qi, data, stride, rows.shape[0], 0) for qi in q])
+
+
+def rerank_rows(family, n, dim, nq, seed):
+    """dict(codebook [S, 16, dim / S], codes [n, S] u8, rows [n, dim] f32, base [n, dim] f32 (unit scale: the tree's
+    centres and assignment), queries [nq, dim] f32) of one family; each family asserts its premise.
+
+    offset        rows and queries + 1000 (the codebook too): brackets wider than the candidates' spread
+    overflow-all  rows x 2^62 (elements 0.6-1 in magnitude): every exact distance is +inf
+    overflow-most overflow-all, except rows i % 1000 == 7, small and near every query: fewer than 10 finite distances
+    near-overflow rows of squared norm 2^128 (1 +- 2^-9): distances straddle FLT_MAX
+    tiny          everything x 2^-70: e^2 and d~ underflow, the 1e-30 floor carries the bracket
+    magnitudes    rows x 2^+-20, half of the queries x 2^-20: under one scale the small rows quantise to 0
+    spike         one coordinate per row (and query) 1000 x the rest: every other coordinate quantises to 0
+    permuted      coordinate permutations of one int8-grid vector (scale 2^-4: x~ = x, E = 0); queries c (1, ..., 1):
+                  the distances tie in real arithmetic and differ only by f32 summation order
+    duplicates    rows 4i + 1 copy rows 4i, rows 4i + 2 differ from them by one ulp in one coordinate; every 3rd query
+                  is a row
+    nonfinite     rows with a NaN, +inf or -inf element, a zero row; query 0 holds a NaN, query 1 is a row, query 2 is
+                  zero (the zero row: d~ = 0)
+    """
+    from tests import rerank_filter_model as RM
+    assert dim % 16 == 0 or family in ("duplicates", "offset", "spike")
+    S = rerank_subspaces(dim)
+    rng = np.random.default_rng([seed, 11, dim])
+    cb = rng.uniform(-1.0, 1.0, (S, 16, dim // S)).astype(np.float32)
+    base = rng.uniform(-1.0, 1.0, (n, dim)).astype(np.float32)
+    q = rng.uniform(-1.0, 1.0, (nq, dim)).astype(np.float32)
+    f32 = np.float32
+    if family == "offset":
+        rows, q, cbr = base + f32(1000.0), q + f32(1000.0), cb + f32(1000.0)
+    elif family in ("overflow-all", "overflow-most"):
+        base = (np.sign(base) * rng.uniform(0.6, 1.0, (n, dim))).astype(np.float32)
+        rows, cbr = base * f32(2.0 ** RERANK_OVERFLOW_EXP), cb
+        if family == "overflow-most":
+            fin = overflow_finite_rows(n)
+            base[fin] = rng.uniform(-0.05, 0.05, (fin.size, dim)).astype(np.float32)
+            rows[fin] = base[fin]
+    elif family == "near-overflow":
+        b64 = base.astype(np.float64)
+        b64 /= np.linalg.norm(b64, axis=1, keepdims=True)
+        rows = (b64 * 2.0 ** 64 * np.sqrt(1.0 + rng.uniform(-2.0 ** -9, 2.0 ** -9, (n, 1)))).astype(np.float32)
+        cbr = cb
+    elif family == "tiny":
+        f = f32(2.0 ** -70)
+        rows, q, cbr = base * f, q * f, cb * f
+    elif family == "magnitudes":
+        rows = base * np.where(rng.random((n, 1)) < 0.5, f32(2.0 ** -20), f32(2.0 ** 20))
+        q = q * np.where(np.arange(nq)[:, None] % 2 == 0, f32(2.0 ** -20), f32(1.0))   # (2^20 queries: scan ties)
+        cbr = cb
+    elif family == "spike":
+        for a in (base, q):
+            j = rng.integers(0, dim, a.shape[0])
+            a[np.arange(a.shape[0]), j] = np.where(rng.random(a.shape[0]) < 0.5, -1.0, 1.0) * \
+                rng.uniform(500.0, 1000.0, a.shape[0])
+        rows, cbr = base, cb
+        base = np.clip(base, -1.0, 1.0)
+    elif family == "permuted":
+        v = rng.integers(-127, 128, dim).astype(np.float32)
+        v[0] = 127.0
+        rows = np.stack([v[rng.permutation(dim)] for _ in range(n)]) * f32(2.0 ** -4)
+        base, cbr = rows / f32(8.0), cb
+        q = np.repeat((f32(0.3) + f32(0.0137) * np.arange(nq, dtype=np.float32))[:, None], dim, axis=1)
+    elif family == "duplicates":
+        rows, cbr = base.copy(), cb
+        m4 = (n // 4) * 4
+        rows[1:m4:4] = rows[0:m4:4]
+        rows[2:m4:4] = rows[0:m4:4]
+        rows[2:m4:4, 5] = np.nextafter(rows[2:m4:4, 5], np.float32(np.inf))
+        q[::3] = rows[rng.integers(0, n // 4, q[::3].shape[0]) * 4]
+        base = rows
+    elif family == "nonfinite":
+        rows, cbr = base.copy(), cb
+        bad = rng.choice(n, 60, replace=False)
+        vals = np.array([np.nan, np.inf, -np.inf], np.float32)
+        rows[bad, rng.integers(0, dim, bad.size)] = vals[np.arange(bad.size) % 3]
+        rows[nonfinite_zero_row(n)] = 0.0
+        base = np.where(np.isfinite(rows), rows, 0.0).astype(np.float32)
+        q[0, 3] = np.nan
+        q[1] = rows[np.setdiff1d(np.arange(n), bad)[17]]
+        q[2] = 0.0
+    else:
+        raise ValueError(family)
+    rows = np.ascontiguousarray(rows, np.float32)
+    q = np.ascontiguousarray(q, np.float32)
+    codes = encode_codes(cb, base if family != "offset" else rows - f32(1000.0))
+    out = dict(codebook=np.ascontiguousarray(cbr, np.float32), codes=codes, rows=rows, base=base, queries=q)
+    # ---- premises
+    if family in ("overflow-all", "overflow-most", "near-overflow"):
+        ex = _exact_all(rows, q)
+        fin = np.isfinite(ex)
+        if family == "overflow-all":
+            assert not fin.any(), "overflow-all: an exact distance is finite"
+        elif family == "overflow-most":
+            assert (fin.sum(1) < 10).all() and (fin.sum(1) > 0).all(), fin.sum(1)
+            d8 = RM.approx_distances(RM.i8_store(rows), q[0])
+            assert (np.isinf(d8).sum() > n // 2), "overflow-most: d~ does not overflow"
+        else:
+            near = fin & (ex >= FLT_MAX * (1.0 - 2.0 ** -10))
+            assert near.sum() > nq and (~fin).sum() > nq, (int(near.sum()), int((~fin).sum()))
+    if family == "tiny":
+        st = RM.i8_store(rows)
+        assert np.mean(st.E == np.float32(1e-30)) > 0.9, "tiny: e^2 does not underflow"
+        assert RM.approx_distances(st, q[0]).max() < np.finfo(np.float32).tiny
+    if family == "magnitudes":
+        st = RM.i8_store(rows, uni_scale=RM.i8_store(rows).deq.max())
+        small = np.abs(rows).max(1) < 2.0 ** -19
+        assert small.sum() > n // 4 and not st.codes[small].any(), "magnitudes: small rows keep a code under one scale"
+    if family == "spike":
+        st = RM.i8_store(rows)
+        assert ((st.codes != 0).sum(1) == 1).all(), "spike: a coordinate besides the spike keeps a code"
+    if family == "permuted":
+        st = RM.i8_store(rows)
+        assert (st.E == np.float32(1e-30)).all(), "permuted: x~ != x"
+        ex = _exact_all(rows[:2000], q[:1])[0]
+        assert np.unique(ex).size >= 3, "permuted: the f32 distances do not differ"
+    if family == "duplicates":
+        st = RM.i8_store(rows)
+        m4 = (n // 4) * 4
+        assert np.mean((st.codes[2:m4:4] == st.codes[0:m4:4]).all(1)) > 0.9, "duplicates: near-pairs differ in int8"
+        ex = _exact_all(rows[:m4], q[:4])
+        assert (ex[:, 2::4] != ex[:, 0::4]).any() and (ex[:, 1::4] == ex[:, 0::4]).all()
+    if family == "nonfinite":
+        st = RM.i8_store(rows)
+        assert np.isinf(st.E[~np.isfinite(rows).all(1)]).all()
+        assert RM.approx_distances(st, q[2], [nonfinite_zero_row(n)])[0] == 0.0
+    if family == "offset":
+        st = RM.i8_store(rows)
+        for qi in q[:4]:
+            Lb, Ub = RM.bracket(RM.approx_distances(st, qi), st.E, dim)
+            assert Lb.max() < Ub.min(), "offset: a bracket is narrower than the rows' spread"
+    return out
+
+
+def nonfinite_zero_row(n):
+    return n // 2 + 1
