@@ -244,8 +244,9 @@ typedef struct {
      * (tree_x_hybrid/mod.rs:245-250, 327-332; restricts/allowlist.rs): bit i set = datapoint i
      * may be returned; disallowed points are skipped before scoring.  NULL = no filter.  Host
      * pointer in the host entry points, DEVICE pointer in the *_device entry points.
-     * allow_bitmap_bits = the bitmap's capacity (a multiple-of-64-bit allocation is read);
-     * datapoint indices >= capacity are not allowed (allowlist.rs:97-100).  Any other
+     * allow_bitmap_bits = the bitmap's capacity: ceil(bits / 64) words are read, bits at or past
+     * the capacity in the last word are ignored, and datapoint indices >= capacity are not allowed
+     * (allowlist.rs:97-100) -- capacity 0 allows nothing (empty rows).  Any other
      * `dyn RestrictFilter` is served by materialising is_allowed(0..n) into such a bitmap
      * (what scann.hpp's search_with_filter does). */
     const uint64_t *allow_bitmap;
@@ -296,8 +297,17 @@ int scann_hip_search_batched_device(scann_hip_index *index, const float *d_queri
                                     float *d_out_dist, uint32_t *d_out_count,
                                     void *hip_stream);
 /* Device status word of the last *_device call on this index (0 = ok, else a
- * scann_hip_status: candidate-buffer overflow -> ResourceExhausted).  Synchronises
- * the stream. */
+ * scann_hip_status), synchronising the stream.  The device entry point does not retry; the
+ * queries it could not finish have out_count 0:
+ *   ResourceExhausted  a candidate buffer overflowed (more points tied at or passed the sampled
+ *                      bound than the buffer sized from it holds) -- e.g. an allow-bitmap that
+ *                      allows none of the points the bound's sample reads: no bound, and every
+ *                      allowed point of a long stream is a candidate;
+ *   Aborted            the sampled bound kept fewer than pre_reorder_k points for some query --
+ *                      e.g. an allow-bitmap that allows the points the bound's sample reads but
+ *                      few of the others.
+ * Remedy for both: search those queries again through scann_hip_search_batched (the host entry
+ * point repeats such a batch once without a bound and with a buffer for the whole stream). */
 int scann_hip_index_last_device_status(scann_hip_index *index, void *hip_stream);
 
 /* ---- multi-GPU: leaf-sharded Tree-X-Hybrid ------------------- */

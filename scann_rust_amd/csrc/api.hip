@@ -1285,13 +1285,16 @@ static int txh_search_host(scann_hip_index *ix, const float *queries, uint32_t n
             return SCANN_HIP_OK;
         }
         TxhWork w;
-        const size_t allow_words = (opts && opts->allow_bitmap) ? (size_t)((opts->allow_bitmap_bits + 63) / 64) : 0;
-        SCANN_TRY(ensure_txh_workspace(ix, ws, p, true, q_stride, true, &w, allow_words * 8));
+        // (a filter of capacity 0 still binds a workspace bitmap -- of one word, read by no row -- so that it allows
+        // nothing whatever an earlier call left in the workspace: a null bitmap would allow every row)
+        const bool filtered = opts && opts->allow_bitmap;
+        const size_t allow_words = filtered ? (size_t)((opts->allow_bitmap_bits + 63) / 64) : 0;
+        SCANN_TRY(ensure_txh_workspace(ix, ws, p, true, q_stride, true, &w, filtered ? std::max<size_t>(allow_words, 1) * 8 : 0));
         // (cand_count alone also takes the staged pipeline: the small-batch one keeps no candidate counts)
         w.need_sorted_cands = (opts && (opts->cand_idx || opts->cand_dist || opts->cand_count)) ? 1 : 0;
         const bool stage_outputs = opts && (opts->tokens || opts->token_dists || opts->cand_idx || opts->cand_dist ||
                                             opts->cand_count);
-        if (p.pipeline != TxhPipeline::Staged && !stage_outputs && !(opts && opts->allow_bitmap)) {
+        if (p.pipeline != TxhPipeline::Staged && !stage_outputs && !filtered) {
             // small batch: queries and result rows live in pinned host memory the kernels access in place
             const size_t qb = (size_t)nq * q_stride * 4, ob = (size_t)nq * k * 4;
             const size_t off_idx = (qb + 255) & ~(size_t)255, off_dist = off_idx + ((ob + 255) & ~(size_t)255),
@@ -1328,9 +1331,10 @@ static int txh_search_host(scann_hip_index *ix, const float *queries, uint32_t n
             std::memcpy(out_count, hp + off_cnt, (size_t)nq * 4);
             return SCANN_HIP_OK;   // (dense candidate lists: the three-launch / one-launch forms have no overflow / retry case)
         }
-        if (opts && opts->allow_bitmap) {   // search_with_filter(Some(allow-list))
-            SCANN_HIP_CHECK(hipMemcpyAsync(ws.allow.p, opts->allow_bitmap, allow_words * 8,
-                                           hipMemcpyHostToDevice, stream));
+        if (filtered) {   // search_with_filter(Some(allow-list))
+            if (allow_words)
+                SCANN_HIP_CHECK(hipMemcpyAsync(ws.allow.p, opts->allow_bitmap, allow_words * 8,
+                                               hipMemcpyHostToDevice, stream));
             w.allow = ws.allow.as<uint64_t>();
             w.allow_bits = opts->allow_bitmap_bits;
         }

@@ -1324,7 +1324,24 @@ struct MfmaArgs {
     uint32_t *cand32;         // [nq][cap32] stream positions of the prefilter's survivors
     uint32_t *cand32_codes;   // [nq][cap32][S/8] their packed codes: the refine reads them in list order
     uint32_t cap32;
+    const uint64_t *allow;    // the search's allow-bitmap (or nullptr): disallowed survivors never enter the lists,
+    uint64_t allow_bits;      // so that the filter bounds them as it bounds the gather scan's (cap32 assumes it)
 };
+
+// The survivor mask `m` of a prefilter tile without its disallowed points: bit b of m stands for the point at leaf
+// position pos_of(b) (CSR row lb + pos_of(b)).  Walks the set bits only (a few per tile); callers take this branch
+// only when a bitmap is present, so an unfiltered scan runs none of it.
+template <typename F>
+__device__ __forceinline__ uint32_t mask_allowed(const TxhIndexDev &ix, const uint64_t *allow, uint64_t allow_bits,
+                                                 uint32_t lb, uint32_t m, F pos_of) {
+    uint32_t keep = 0;
+    while (m) {
+        const uint32_t b = (uint32_t)__ffs((int)m) - 1u;
+        m &= m - 1u;
+        if (row_allowed(ix, allow, allow_bits, lb + pos_of(b))) keep |= 1u << b;
+    }
+    return keep;
+}
 
 template <int S_>
 __global__ __launch_bounds__(kMfmaWaves * 64, (S_ <= 32 ? SCANN_MFMA_MINW : 2)) void adc_mfma_kernel(TxhIndexDev ix, MfmaArgs a) {
@@ -1491,6 +1508,11 @@ __global__ __launch_bounds__(kMfmaWaves * 64, (S_ <= 32 ? SCANN_MFMA_MINW : 2)) 
                     okm |= (base + (uint32_t)((r & 3) + 8 * (r >> 2)) < size ? 1u : 0u) << (15 - r);
                 m16 &= okm;
             }
+            if (a.allow && m16)                // search_with_filter: disallowed points are not survivors
+                m16 = mask_allowed(ix, a.allow, a.allow_bits, lb, m16, [&](uint32_t b) {
+                    const uint32_t r = 15u - b;
+                    return base + (r & 3u) + ((r >> 2) << 3);
+                });
             bool risk = false;                 // this lane's pair could overflow its stage in the next tile
             if (m16) {
                 uint32_t sl = atomicAdd(&s_cnt[wave][col], (uint32_t)__popc(m16));   // one LDS atomic per lane
@@ -1614,6 +1636,23 @@ __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
     return v;
 }
 
+// search_with_filter in the sparse prefilter: lane (col, h) drops the disallowed points from its own words of the item's
+// survivor bitmap (words[tt * 64], tt < ntt; see adc_smfmac_body: word [tt][h][col] = the masks of tiles 2 tt (low half)
+// and 2 tt + 1, result r of a tile -- point row (r & 3) + 8 (r >> 2) + 4 h -- at bit 15 - r), before the flush counts
+// them.  Called at the top of the flushes, where the tile loop's registers are dead, and only when a bitmap is present.
+__device__ __forceinline__ void sp_filter_words(const TxhIndexDev &ix, const uint64_t *allow, uint64_t allow_bits,
+                                                uint32_t *words, uint32_t ntt, uint32_t c0, uint32_t lb, uint32_t h) {
+    for (uint32_t tt = 0; tt < ntt; ++tt) {
+        const uint32_t wd = words[tt * 64u];
+        if (wd)
+            words[tt * 64u] = mask_allowed(ix, allow, allow_bits, lb, wd, [&](uint32_t b) {
+                const uint32_t r = 15u - (b & 15u);
+                return c0 + (2u * tt + (b >> 4)) * 32u + 4u * h + (r & 3u) + ((r >> 2) << 3);
+            });
+    }
+    __builtin_amdgcn_wave_barrier();   // (the word-parallel flush reads the other lanes' words)
+}
+
 #ifndef SCANN_SP_FLUSH_INLINE
 #define SCANN_SP_FLUSH_INLINE __forceinline__
 #endif
@@ -1623,15 +1662,17 @@ __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
 // 0.44 ms for the word-parallel form -- which wins wherever pairs are dense (tree indexes: 10M x 128, P = 25, m = 1000:
 // scan 0.27 ms against 0.71 ms), because a lane walking its own survivors takes them one by one.
 template <int S>
-__device__ SCANN_SP_FLUSH_INLINE void sp_flush_item_lanes(const uint32_t *__restrict__ codes_sp, uint32_t *__restrict__ cand32_cnt,
+__device__ SCANN_SP_FLUSH_INLINE void sp_flush_item_lanes(const uint32_t *__restrict__ codes_sp, const TxhIndexDev &ix,
+                                                        const uint64_t *allow, uint64_t allow_bits, uint32_t *__restrict__ cand32_cnt,
                                                         uint32_t *__restrict__ cand32, uint32_t *__restrict__ cand32_codes,
-                                                        uint32_t cap32, const uint32_t *bits, uint2 *stage, uint32_t *s_fq,
+                                                        uint32_t cap32, uint32_t *bits, uint2 *stage, uint32_t *s_fq,
                                                         uint32_t *s_fvb, uint32_t *s_fgb, uint32_t ntile, uint32_t c0,
                                                         uint32_t lb, uint32_t pq, uint32_t vb) {
     constexpr int SPW = SpLayout<S>::SPW;
     constexpr int TTM = (int)(kMfmaRange / 64);
     const uint32_t lane = threadIdx.x & 63u, col = lane & 31u, h = lane >> 5;
     const uint32_t ntt = (ntile + 1u) >> 1;
+    if (allow) sp_filter_words(ix, allow, allow_bits, bits, ntt, c0, lb, h);
     uint32_t w[TTM];
     uint32_t cnt = 0;
 #pragma unroll
@@ -1728,9 +1769,10 @@ __device__ SCANN_SP_FLUSH_INLINE void sp_flush_item_lanes(const uint32_t *__rest
 //      the point's PLANE row (codes_sp: the lines the tile loop has just read, still in L2 -- the packed codes were
 //      last touched at index creation); adc_refine_kernel decodes it (RefineArgs::planes).
 template <int S>
-__device__ SCANN_SP_FLUSH_INLINE void sp_flush_item_words(const uint32_t *__restrict__ codes_sp, uint32_t *__restrict__ cand32_cnt,
+__device__ SCANN_SP_FLUSH_INLINE void sp_flush_item_words(const uint32_t *__restrict__ codes_sp, const TxhIndexDev &ix,
+                                                        const uint64_t *allow, uint64_t allow_bits, uint32_t *__restrict__ cand32_cnt,
                                                         uint32_t *__restrict__ cand32, uint32_t *__restrict__ cand32_codes,
-                                                        uint32_t cap32, const uint32_t *bits_w, uint2 *stage, uint32_t *s_fq,
+                                                        uint32_t cap32, uint32_t *bits_w, uint2 *stage, uint32_t *s_fq,
                                                         uint32_t *s_fvb, uint32_t *s_fgb, uint32_t ntile, uint32_t c0,
                                                         uint32_t lb, uint32_t pq, uint32_t vb) {
     constexpr int SPW = SpLayout<S>::SPW;
@@ -1738,6 +1780,7 @@ __device__ SCANN_SP_FLUSH_INLINE void sp_flush_item_words(const uint32_t *__rest
     static_assert(TTM == 32, "the flush maps the 64 words of a pair onto the 64 lanes");
     const uint32_t lane = threadIdx.x & 63u, h = lane >> 5;
     const uint32_t ntt = (ntile + 1u) >> 1;
+    if (allow) sp_filter_words(ix, allow, allow_bits, bits_w + lane, ntt, c0, lb, h);
     uint32_t cnt = 0;
 #pragma unroll
     for (int tt = 0; tt < TTM; ++tt) cnt += (uint32_t)tt < ntt ? (uint32_t)__popc(bits_w[tt * 64 + lane]) : 0u;
@@ -2043,15 +2086,14 @@ __device__ __forceinline__ void adc_smfmac_body(const TxhIndexDev &ix, const Mfm
             if (tl + 1 <= ntile) step(accA, accB, tl + 1, std::true_type());  // mask of tile tl (odd): high half, write
         }
         if (ntile & 1u) bits[(ntile >> 1) * 64u] = mlo;   // the last tile had an even number: its word has no high half
-
         // ---- flush: the item's bitmap -> the queries' lists (sp_flush_item: its own function, so that its registers
         // are allocated apart from the tile loop's -- inlined, the loop spilled its table fragments)
         if constexpr (WORDS)
-            sp_flush_item_words<S>(ix.codes_sp, a.cand32_cnt, a.cand32, a.cand32_codes, a.cap32, &s_bits[wave][0][0], s_stage[wave],
-                                   s_fq[wave], s_fvb[wave], s_fgb[wave], ntile, c0, lb, pq, vb);
+            sp_flush_item_words<S>(ix.codes_sp, ix, a.allow, a.allow_bits, a.cand32_cnt, a.cand32, a.cand32_codes, a.cap32, &s_bits[wave][0][0],
+                                   s_stage[wave], s_fq[wave], s_fvb[wave], s_fgb[wave], ntile, c0, lb, pq, vb);
         else
-            sp_flush_item_lanes<S>(ix.codes_sp, a.cand32_cnt, a.cand32, a.cand32_codes, a.cap32, bits, s_stage[wave], s_fq[wave],
-                                   s_fvb[wave], s_fgb[wave], ntile, c0, lb, pq, vb);
+            sp_flush_item_lanes<S>(ix.codes_sp, ix, a.allow, a.allow_bits, a.cand32_cnt, a.cand32, a.cand32_codes, a.cap32, bits, s_stage[wave],
+                                   s_fq[wave], s_fvb[wave], s_fgb[wave], ntile, c0, lb, pq, vb);
         tile = __builtin_amdgcn_readfirstlane(next_tile);
     }
 }
@@ -2241,6 +2283,11 @@ __global__ __launch_bounds__(kMfmaWaves * 64, (S_ <= 32 ? 4 : 2)) void adc_mfma1
             }
             bool risk = false;
             m8 &= 0xFFu;
+            if (a.allow && m8)                 // search_with_filter: disallowed points are not survivors
+                m8 = mask_allowed(ix, a.allow, a.allow_bits, lb, m8, [&](uint32_t b) {
+                    const uint32_t qi = 7u - b;
+                    return base + 16u * (qi >> 2) + (qi & 3u);
+                });
             if (m8) {
                 uint32_t sl = atomicAdd(&s_cnt[wave][c16], (uint32_t)__popc(m8));
                 do {
@@ -4885,6 +4932,7 @@ static int launch_scan_stages(const TxhIndexDev &ix, const TxhWork &w, hipStream
             ma.pair_off = w.pair_off; ma.tile_off = w.tile_off; ma.pair_q = w.pair_q; ma.pair_vbase = w.pair_vbase;
             ma.counters = w.counters; ma.lut8 = w.lut8; ma.meta = reinterpret_cast<const Lut8Meta *>(w.lut8_meta);
             ma.pair_thr = w.pair_thr; ma.cand32_cnt = w.cand32_cnt; ma.cand32 = w.cand32; ma.cand32_codes = codes_in_list ? w.cand32_codes : nullptr; ma.cap32 = w.cap32;
+            ma.allow = w.allow; ma.allow_bits = w.allow_bits;
             if (ev0) SCANN_HIP_CHECK(hipEventRecord(ev0, st));
             const bool words = w.sp_words;
             const dim3 mgrid((uint32_t)cus * 4u), mblock(kMfmaWaves * 64);   // 4 workgroups per CU (4 waves each)

@@ -250,8 +250,9 @@ class Index:
     def dimensionality(self):
         return int(load().scann_hip_index_dimensionality(self.h))
 
-    def search_batched(self, queries, k, opts=None, q_dim=None, stages=False, allow=None):
-        """`allow`: optional uint64 allow-bitmap (see allow_bitmap()) = search_with_filter."""
+    def search_batched(self, queries, k, opts=None, q_dim=None, stages=False, allow=None, allow_bits=None):
+        """`allow`: optional uint64 allow-bitmap (see allow_bitmap()) = search_with_filter.  `allow_bits`: its
+        capacity in bits (default: every word, allow.size * 64); indices at or past it are not allowed."""
         q = f32(queries)
         if q.ndim == 1:
             q = q[None]
@@ -264,7 +265,7 @@ class Index:
         extra = None
         if allow is not None:
             allow = np.ascontiguousarray(allow, np.uint64)
-            o.allow_bitmap, o.allow_bitmap_bits = ptr(allow, u64p), allow.size * 64
+            o.allow_bitmap, o.allow_bitmap_bits = ptr(allow, u64p), _allow_capacity(allow, allow_bits)
         if stages:
             P = o.partitions_to_search or 4096
             m = o.pre_reorder_k or 4096
@@ -289,17 +290,27 @@ class Index:
             return out_idx[:, :k], out_dist[:, :k], out_cnt, extra
         return out_idx[:, :k], out_dist[:, :k], out_cnt
 
-    def search_batched_with_params(self, queries, ks, opts=None):
-        """Searcher::search_batched_with_params: one num_neighbors per query; rows at pitch max(ks)."""
+    def search_batched_with_params(self, queries, ks, opts=None, allow=None, allow_bits=None):
+        """Searcher::search_batched_with_params: one num_neighbors per query; rows at pitch max(ks).  `allow`,
+        `allow_bits`: an allow-bitmap and its capacity, as in search_batched."""
         q = f32(queries)
         nq, qs = q.shape
         ks = np.ascontiguousarray(ks, np.uint32)
         pitch = max(int(ks.max()), 1)
         out_idx = np.zeros((nq, pitch), np.uint32); out_dist = np.zeros((nq, pitch), np.float32)
         out_cnt = np.zeros(nq, np.uint32)
-        check(load().scann_hip_search_batched_params(self.h, ptr(q, f32p), nq, qs, qs, ptr(ks, u32p),
-                                                     C.byref(opts) if opts is not None else None, pitch,
-                                                     ptr(out_idx, u32p), ptr(out_dist, f32p), ptr(out_cnt, u32p)))
+        if allow is not None:
+            if opts is None:
+                opts = default_opts()
+            allow = np.ascontiguousarray(allow, np.uint64)
+            opts.allow_bitmap, opts.allow_bitmap_bits = ptr(allow, u64p), _allow_capacity(allow, allow_bits)
+        try:
+            check(load().scann_hip_search_batched_params(self.h, ptr(q, f32p), nq, qs, qs, ptr(ks, u32p),
+                                                         C.byref(opts) if opts is not None else None, pitch,
+                                                         ptr(out_idx, u32p), ptr(out_dist, f32p), ptr(out_cnt, u32p)))
+        finally:
+            if allow is not None:   # (see search_batched)
+                opts.allow_bitmap, opts.allow_bitmap_bits = None, 0
         return out_idx, out_dist, out_cnt
 
     def enable_timing(self, on=True):
@@ -309,6 +320,15 @@ class Index:
         name = C.c_char_p()
         ms = load().scann_hip_index_last_kernel_ms(self.h, C.byref(name))
         return float(ms), (name.value or b"").decode()
+
+
+def _allow_capacity(allow, allow_bits):
+    """allow_bitmap_bits of a bitmap of allow.size words: every word, or the caller's capacity (at most that)"""
+    if allow_bits is None:
+        return allow.size * 64
+    if not 0 <= int(allow_bits) <= allow.size * 64:
+        raise ValueError("allow_bits %d exceeds the bitmap's %d words" % (allow_bits, allow.size))
+    return int(allow_bits)
 
 
 def allow_bitmap(n, allowed):

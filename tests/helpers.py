@@ -559,3 +559,218 @@ def rerank_rows(family, n, dim, nq, seed):
 
 def nonfinite_zero_row(n):
     return n // 2 + 1
+
+
+# ---- allow-list filters (tests/test_gpu_filters.py) -----------------------------------------------------------------
+# Python mirror of the sample plan of csrc/txh.h (sample_stride / sample_plan / sample_rank) and of the candidate
+# capacities plan_txh_search derives from it (api.hip), so that a test can name the points the threshold sample reads
+# and the sizes at which a bound is statistical.
+SAMPLE_TARGET, SAMPLE_MIN = 32768, 4096
+WIDE_GROUPS = 16384
+
+
+def sample_stride(total):
+    ns = min(max(total // 16, SAMPLE_MIN), SAMPLE_TARGET)
+    return max(1, -(-total // ns))
+
+
+def sample_plan(max_stream, P):
+    """(st, scap): stride and per-query sample capacity for a batch whose longest stream is max_stream points"""
+    ms = min(int(max_stream), 0xFFFFFFFF)
+    st = sample_stride(ms)
+    while True:
+        scap = ((-(-ms // st) + P) + 3) & ~3
+        if scap <= SAMPLE_TARGET or P >= SAMPLE_TARGET - 4:
+            return st, max(scap, 4)
+        st += 1 + st // 8
+
+
+def sample_rank(m, st):
+    """J: the rank of the sampled bound (f32 arithmetic as in txh.h); 0 = no bound"""
+    if m == 0:
+        return 0
+    r = np.float32(m) / np.float32(st)
+    s = np.float32(0.5) * (np.float32(6.0) + np.sqrt(np.float32(36.0) + np.float32(4.0) * r, dtype=np.float32))
+    jp = s * s + np.float32(2.0)
+    j = m if jp >= np.float32(m) else int(jp)
+    return max(1, min(j, m))
+
+
+def plan_caps(max_stream, P, m):
+    """(st, J, cap, cap32) of the batched pipeline's first attempt: cap = the candidate list of the f32 bound, cap32 =
+    the integer prefilter's survivor list (plan_txh_search)"""
+    ms = min(int(max_stream), 0xFFFFFFFF)
+    st, _ = sample_plan(ms, P)
+    j = sample_rank(m, st)
+    cap = int(j + 8.0 * np.sqrt(j) + 16.0) * st + 256
+    cap = min(max(cap, m), ms)
+    return st, j, cap, min(ms, 4 * cap + 16384)
+
+
+def wide_group(cnt, m):
+    """stream positions per group minimum of the wide pipeline (txh.hip wide_group)"""
+    g = 1
+    while g < 64 and -(-cnt // g) > WIDE_GROUPS:
+        g <<= 1
+    while g > 1 and cnt // g < (m * 3) // 2:
+        g >>= 1
+    return g
+
+
+def max_stream(leaf_off, P):
+    """the longest stream of P leaves: the sum of the P largest"""
+    return int(np.sort(np.diff(np.asarray(leaf_off, np.int64)))[::-1][:P].sum())
+
+
+def words_of(ids, cap):
+    """(words, cap): the bitmap of datapoint indices `ids` (all < cap) over ceil(cap / 64) words, at least one"""
+    words = np.zeros(max(1, -(-cap // 64)), np.uint64)
+    ids = np.asarray(ids, np.uint64)
+    np.bitwise_or.at(words, (ids >> np.uint64(6)).astype(np.int64), np.uint64(1) << (ids & np.uint64(63)))
+    return words, int(cap)
+
+
+def allowed_ids(words, cap, n):
+    """datapoint indices below n the bitmap (words, capacity cap) allows: bit i set and i < cap"""
+    i = np.arange(min(n, cap, words.size * 64), dtype=np.uint64)
+    return i[((words[(i >> np.uint64(6)).astype(np.int64)] >> (i & np.uint64(63))) & np.uint64(1)) == 1] \
+        .astype(np.int64)
+
+
+def masked_words(words, cap, n):
+    """the bitmap as the reference reads it, over ceil(n / 64) words: bits at or past the capacity cleared"""
+    return words_of(allowed_ids(words, cap, n), n)[0]
+
+
+def sampled_rows(leaf_off, st):
+    """CSR rows the threshold sample reads: positions j * st of every leaf (adc_sample_kernel)"""
+    leaf_off = np.asarray(leaf_off, np.int64)
+    return np.concatenate([np.arange(a, b, st) for a, b in zip(leaf_off[:-1], leaf_off[1:])])
+
+
+FILTER_FAMILIES = ("empty", "one", "k-1", "m-1", "m", "m+1", "one-leaf", "unprobed", "f50", "f10", "f3", "f1", "f0.1",
+                   "not-topk", "not-topm", "sampled", "unsampled", "wide-one-per-group", "wide-one-group",
+                   "cap0", "cap1", "cap63", "cap64", "cap65", "cap-n-1", "cap-n", "cap-over", "prefix")
+
+
+def allow_family(family, leaf_off, leaf_ids, tokens, k, m, st, seed, topk=None, topm=None):
+    """(words, capacity) of the allow-set `family` over an index of CSR offsets leaf_off and row ids leaf_ids (None =
+    identity).  tokens: [nq][P] the queries' probed leaves (query 0's decide the m-sized families); st: the sample
+    stride of the batch; topk / topm: per query, the oracle's exact top-k / approximate top-m indices (the not-top
+    families).  Deterministic for a given seed."""
+    leaf_off = np.asarray(leaf_off, np.int64)
+    n = int(leaf_off[-1])
+    ids = np.arange(n, dtype=np.int64) if leaf_ids is None else np.asarray(leaf_ids, np.int64)
+    rng = np.random.default_rng([seed, FILTER_FAMILIES.index(family)])
+    tokens = np.asarray(tokens, np.int64)
+
+    def rows_of(leaves):
+        return np.concatenate([np.arange(leaf_off[l], leaf_off[l + 1]) for l in leaves] + [np.zeros(0, np.int64)])
+
+    probed0 = ids[rows_of(tokens[0])]
+
+    def spread(cnt):   # cnt of query 0's probed points, evenly spaced over its stream
+        cnt = min(cnt, probed0.size)
+        return probed0[np.linspace(0, probed0.size - 1, cnt).astype(np.int64)] if cnt else probed0[:0]
+
+    if family == "empty":
+        return words_of([], n)
+    if family in ("one", "k-1", "m-1", "m", "m+1"):
+        cnt = {"one": 1, "k-1": k - 1, "m-1": m - 1, "m": m, "m+1": m + 1}[family]
+        return words_of(spread(cnt), n)
+    if family == "one-leaf":
+        return words_of(ids[rows_of([tokens[0][0]])], n)
+    if family == "unprobed":
+        return words_of(ids[rows_of(np.setdiff1d(np.arange(leaf_off.size - 1), tokens.ravel()))], n)
+    if family[0] == "f":
+        return words_of(np.flatnonzero(rng.random(n) < float(family[1:]) / 100.0), n)
+    if family in ("not-topk", "not-topm"):
+        drop = np.unique(np.concatenate([np.asarray(x, np.int64) for x in (topk if family == "not-topk" else topm)]))
+        return words_of(np.setdiff1d(np.arange(n), drop), n)
+    if family in ("sampled", "unsampled"):
+        s = np.zeros(n, bool)
+        s[ids[sampled_rows(leaf_off, st)]] = True
+        return words_of(np.flatnonzero(s if family == "sampled" else ~s), n)
+    if family in ("wide-one-per-group", "wide-one-group"):
+        # stream positions of query 0 = its probed leaves in token order; groups of g positions
+        g = wide_group(probed0.size, m)
+        if family == "wide-one-per-group":
+            return words_of(probed0[g // 2::g], n)
+        grp = int(rng.integers(0, max(1, probed0.size // g)))
+        return words_of(probed0[grp * g:(grp + 1) * g], n)
+    # word and capacity edges: every bit of every word set, the stray bits past the capacity included
+    cap = {"cap0": 0, "cap1": 1, "cap63": 63, "cap64": 64, "cap65": 65, "cap-n-1": n - 1, "cap-n": n,
+           "cap-over": n + 100, "prefix": n // 2 + 7}[family]
+    words = np.full(max(1, -(-cap // 64)), np.uint64(0xFFFFFFFFFFFFFFFF))
+    if family == "prefix":   # a bitmap of a prefix of the index (ceil(cap / 64) words), every other row allowed
+        words[:] = np.uint64(0x5555555555555555)
+    return words, cap
+
+
+# ---- forced scans and the device entry (tests/test_gpu_txh_subspaces.py, tests/test_gpu_filters.py) -----------------
+SCAN_KNOBS = ("SCANN_HIP_MFMA", "SCANN_HIP_SMFMAC", "SCANN_HIP_RESIDENT", "SCANN_HIP_SP_WORDS", "SCANN_HIP_SMALL",
+              "SCANN_HIP_WIDE", "SCANN_HIP_FUSED", "SCANN_HIP_RERANK_I8", "SCANN_HIP_RERANK_I8_MIN",
+              "SCANN_HIP_RERANK_STORE", "SCANN_HIP_RERANK_UNIFORM", "SCANN_HIP_THR_TIES", "SCANN_HIP_THR_TAIL",
+              "SCANN_HIP_SELECT_DIRECT", "SCANN_HIP_LOCAL_PRUNE")
+SCANS = {
+    "gather": {"SCANN_HIP_MFMA": "0", "SCANN_HIP_RESIDENT": "0"},
+    "resident": {"SCANN_HIP_MFMA": "0", "SCANN_HIP_RESIDENT": "2"},
+    "dense32": {"SCANN_HIP_SMFMAC": "0", "SCANN_HIP_MFMA": "2"},
+    "mfma16": {"SCANN_HIP_MFMA": "3"},
+    "sp-lanes": {"SCANN_HIP_SMFMAC": "1", "SCANN_HIP_MFMA": "2", "SCANN_HIP_SP_WORDS": "0"},
+    "sp-words": {"SCANN_HIP_SMFMAC": "1", "SCANN_HIP_MFMA": "2", "SCANN_HIP_SP_WORDS": "1"},
+    "default": {},
+}
+
+
+def scan_env(monkeypatch, scan):
+    """Set the knobs of `scan` (before the index is created: SMFMAC=0 then builds no operand planes)."""
+    for name in SCAN_KNOBS:
+        monkeypatch.delenv(name, raising=False)
+    for name, val in SCANS[scan].items():
+        monkeypatch.setenv(name, val)
+
+
+def sparse_kernel_name(S):
+    return "adc_smfmac_kernel" if S <= 32 else "adc_smfmac_wide_kernel"
+
+
+def scan_kernel_name(scan, S):
+    """the kernel scann_hip_index_last_kernel_ms names for a batched search under `scan` (4-bit codes)"""
+    if scan == "gather" or (scan == "resident" and S > 32):
+        return "adc_scan_kernel"     # (the resident layout holds S <= 32)
+    return {"resident": "adc_scan_res_kernel", "dense32": "adc_mfma_kernel", "mfma16": "adc_mfma16_kernel"}.get(
+        scan, sparse_kernel_name(S))
+
+
+def device_search(index, q, k, o, allow=None, allow_bits=None):
+    """scann_hip_search_batched_device on torch's current stream: (status, idx, dist, count) after the call.  `allow`:
+    a host bitmap, copied to the device for the call (capacity allow_bits, default every word)."""
+    import ctypes
+    import torch
+    from scann_rust_amd import hip
+    dev = torch.device("cuda:0")
+    L = hip.load()
+    p = lambda t: ctypes.c_void_p(t.data_ptr())
+    nq, dim = q.shape
+    qd = torch.from_numpy(np.ascontiguousarray(q, np.float32)).to(dev)
+    oi = torch.full((nq, k), -1, dtype=torch.int32, device=dev)
+    od = torch.zeros((nq, k), dtype=torch.float32, device=dev)
+    oc = torch.full((nq,), 7, dtype=torch.int32, device=dev)
+    st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    da = None
+    if allow is not None:
+        words = np.ascontiguousarray(allow, np.uint64)
+        da = torch.from_numpy(words.view(np.int64).copy()).to(dev)
+        o.allow_bitmap = ctypes.cast(ctypes.c_void_p(da.data_ptr()), ctypes.POINTER(ctypes.c_uint64))
+        o.allow_bitmap_bits = words.size * 64 if allow_bits is None else int(allow_bits)
+    torch.cuda.synchronize()
+    try:
+        hip.check(L.scann_hip_search_batched_device(index.h, p(qd), nq, dim, k, ctypes.byref(o), p(oi), p(od), p(oc),
+                                                    st))
+        status = L.scann_hip_index_last_device_status(index.h, st)
+        torch.cuda.synchronize()
+    finally:
+        if da is not None:
+            o.allow_bitmap, o.allow_bitmap_bits = None, 0
+    return status, oi.cpu().numpy().view(np.uint32), od.cpu().numpy(), oc.cpu().numpy().view(np.uint32)

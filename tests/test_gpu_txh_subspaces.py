@@ -16,8 +16,6 @@ Distances must match the oracle bitwise; indices may differ only inside ties.  T
 tests/helpers.py adversarial_pq (explicit codebooks and codes) cross the forced scans at S = 16 and 48 on both index
 kinds, on the host entry (with its retry after a candidate-list overflow) and on the device entry (no retry: Ok with the
 host's rows, or a failure status with count 0 for the failed queries)."""
-import ctypes
-
 import numpy as np
 import pytest
 
@@ -29,64 +27,21 @@ pytestmark = pytest.mark.gpu
 
 ABORTED = 10   # scann_hip.h SCANN_HIP_ABORTED: a statistical bound that kept fewer than m points
 
-KNOBS = ("SCANN_HIP_MFMA", "SCANN_HIP_SMFMAC", "SCANN_HIP_RESIDENT", "SCANN_HIP_SP_WORDS", "SCANN_HIP_SMALL",
-         "SCANN_HIP_WIDE", "SCANN_HIP_FUSED", "SCANN_HIP_RERANK_I8", "SCANN_HIP_RERANK_I8_MIN", "SCANN_HIP_RERANK_STORE",
-         "SCANN_HIP_RERANK_UNIFORM", "SCANN_HIP_THR_TIES", "SCANN_HIP_THR_TAIL", "SCANN_HIP_SELECT_DIRECT")
-SCANS = {
-    "gather": {"SCANN_HIP_MFMA": "0", "SCANN_HIP_RESIDENT": "0"},
-    "resident": {"SCANN_HIP_MFMA": "0", "SCANN_HIP_RESIDENT": "2"},
-    "dense32": {"SCANN_HIP_SMFMAC": "0", "SCANN_HIP_MFMA": "2"},
-    "mfma16": {"SCANN_HIP_MFMA": "3"},
-    "sp-lanes": {"SCANN_HIP_SMFMAC": "1", "SCANN_HIP_MFMA": "2", "SCANN_HIP_SP_WORDS": "0"},
-    "sp-words": {"SCANN_HIP_SMFMAC": "1", "SCANN_HIP_MFMA": "2", "SCANN_HIP_SP_WORDS": "1"},
-    "default": {},
-}
+KNOBS, SCANS = H.SCAN_KNOBS, H.SCANS
 SUBSPACES = (8, 16, 24, 32, 48, 64)
 # dims per subspace 1, 2 and odd across each index kind
 AH_DIM = {8: 40, 16: 16, 24: 72, 32: 32, 48: 48, 64: 128}
 TXH_DIM = {8: 16, 16: 48, 24: 48, 32: 96, 48: 144, 64: 64}
 
 
-def _env(monkeypatch, scan):
-    """Set the knobs of `scan` (before the index is created: SMFMAC=0 then builds no operand planes)."""
-    for name in KNOBS:
-        monkeypatch.delenv(name, raising=False)
-    for name, val in SCANS[scan].items():
-        monkeypatch.setenv(name, val)
-
-
-def _sparse_name(S):
-    return "adc_smfmac_kernel" if S <= 32 else "adc_smfmac_wide_kernel"
-
-
-def _expected(scan, S):
-    if scan == "gather" or (scan == "resident" and S > 32):
-        return "adc_scan_kernel"     # (the resident layout holds S <= 32)
-    return {"resident": "adc_scan_res_kernel", "dense32": "adc_mfma_kernel", "mfma16": "adc_mfma16_kernel"}.get(
-        scan, _sparse_name(S))
+_env, _sparse_name, _expected = H.scan_env, H.sparse_kernel_name, H.scan_kernel_name
 
 
 def _bits(a):
     return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
-def _device_search(index, q, k, o):
-    """scann_hip_search_batched_device on torch's current stream: (status, idx, dist, count) after the call."""
-    import torch
-    dev = torch.device("cuda:0")
-    L = hip.load()
-    p = lambda t: ctypes.c_void_p(t.data_ptr())
-    nq, dim = q.shape
-    qd = torch.from_numpy(np.ascontiguousarray(q, np.float32)).to(dev)
-    oi = torch.full((nq, k), -1, dtype=torch.int32, device=dev)
-    od = torch.zeros((nq, k), dtype=torch.float32, device=dev)
-    oc = torch.full((nq,), 7, dtype=torch.int32, device=dev)
-    st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    torch.cuda.synchronize()
-    hip.check(L.scann_hip_search_batched_device(index.h, p(qd), nq, dim, k, ctypes.byref(o), p(oi), p(od), p(oc), st))
-    status = L.scann_hip_index_last_device_status(index.h, st)
-    torch.cuda.synchronize()
-    return status, oi.cpu().numpy().view(np.uint32), od.cpu().numpy(), oc.cpu().numpy().view(np.uint32)
+_device_search = H.device_search
 
 
 def _fast_equals_staged(fast, staged, what):
