@@ -132,8 +132,8 @@ int scann_hip_bf_create(scann_hip_ctx *ctx, const float *data, uint64_t n, uint3
  * scann_hip_index_reserve, scann_hip_search_batched_device / scann_hip_index_last_device_status,
  * scann_hip_bf_search_radius, scann_hip_bf_distances, the introspection and timing calls, from concurrent
  * threads as any brute-force handle.  Entry points that read rows as f32 (scann_hip_kmeans_*,
- * scann_hip_bf_assign_nearest, Tree-X-Hybrid calls) return InvalidArgument.  opts.allow_bitmap is not applied
- * (as for f32 brute force).  opts.bf_exact has the f32 contract: large batches on large indexes (the dims and
+ * scann_hip_bf_assign_nearest, Tree-X-Hybrid calls) return InvalidArgument.  opts.allow_bitmap is honoured with
+ * the brute-force contract stated at scann_hip_search_opts (distances stay those of the row format).  opts.bf_exact has the f32 contract: large batches on large indexes (the dims and
  * sizes of the f32 shortlist, stride % 8 == 0) take the bf16-shortlist path, whose row operand is the stored
  * value itself (exact in bf16 for all three formats: only the query is split); a query it cannot prove sets
  * status Aborted, which the host entry point repeats by itself and *_device callers repeat with bf_exact = 1.
@@ -248,7 +248,25 @@ typedef struct {
      * the capacity in the last word are ignored, and datapoint indices >= capacity are not allowed
      * (allowlist.rs:97-100) -- capacity 0 allows nothing (empty rows).  Any other
      * `dyn RestrictFilter` is served by materialising is_allowed(0..n) into such a bitmap
-     * (what scann.hpp's search_with_filter does). */
+     * (what scann.hpp's search_with_filter does).
+     * Brute-force handles (f32, bf16, FP8 E4M3, int8 rows; every measure the handle serves): the reference's
+     * BruteForceSearcher has no filter argument, so the contract is stated here.  A filtered search answers
+     * exactly as an unfiltered search over a handle built from the allowed rows alone, taken in ascending
+     * datapoint order, with each returned index mapped back to its datapoint index:
+     *   - k = min(k, number of allowed rows); out_count reports it; slots past it hold 0xFFFFFFFF / +inf;
+     *   - distances are bit-identical to the unfiltered arithmetic of the same handle;
+     *   - ties are broken by TopK's (distance, index) rule (the mapping is monotone, so tie order is kept); a
+     *     disallowed row that ties with the k-th allowed row never appears and never displaces one;
+     *   - the bitmap rules above hold unchanged; NULL takes exactly the unfiltered code path.
+     * Two mechanisms, chosen per call from the allowed fraction (SCANN_HIP_BF_FILTER_COMPACT_MAX, default 1: host
+     * calls always take the first; forced by SCANN_HIP_BF_FILTER = 1 / 2): a compacted, ascending id list of the allowed rows that the kernels gather
+     * (only allowed rows are read), or the unfiltered stream with a bit test where a row becomes a candidate.
+     * Filtered calls never take the bf16-shortlist path: its acceptance proof bounds the rows OUTSIDE the
+     * shortlist, disallowed ones included, so it would have to be restated over allowed rows only; they are
+     * routed to the exact kernels (the cost: a filtered large batch runs at the bf_exact = 1 rate of its
+     * allowed rows; not measured yet).  The few-query host pipeline applies the bit test in its scan.
+     * The *_device entry point cannot learn the allowed count without a synchronisation: it takes the bit test
+     * and documents its failure mode at scann_hip_index_last_device_status. */
     const uint64_t *allow_bitmap;
     uint64_t allow_bitmap_bits;
     /* Brute-force handles.  0 (default): large batches on large indexes take the bf16-shortlist
@@ -307,7 +325,14 @@ int scann_hip_search_batched_device(scann_hip_index *index, const float *d_queri
  *                      e.g. an allow-bitmap that allows the points the bound's sample reads but
  *                      few of the others.
  * Remedy for both: search those queries again through scann_hip_search_batched (the host entry
- * point repeats such a batch once without a bound and with a buffer for the whole stream). */
+ * point repeats such a batch once without a bound and with a buffer for the whole stream).
+ * Brute-force handles with an allow-bitmap: the device entry point streams every row and tests the bitmap
+ * where a row becomes a candidate, with the bound taken over the ALLOWED rows of its 8192-row sample.  A
+ * bitmap that leaves fewer than k allowed rows in that sample gives no bound; every allowed row is then a
+ * candidate, and with more of them than the buffer sized from k holds the status is ResourceExhausted
+ * (out_count 0 for those queries, never wrong rows).  Same remedy: the host entry point counts the allowed
+ * rows and repeats over the compacted allowed rows.  A reserved handle does not allocate on such a call
+ * (pass the opts with the bitmap to scann_hip_index_reserve so that host calls do not either). */
 int scann_hip_index_last_device_status(scann_hip_index *index, void *hip_stream);
 
 /* ---- multi-GPU: leaf-sharded Tree-X-Hybrid ------------------- */
@@ -538,7 +563,17 @@ int scann_hip_kmeans_lloyd(scann_hip_index *bf_index, uint32_t col_offset, uint3
 /* BruteForceSearcher::search_radius (src/brute_force/searcher.rs:142-167) for one query: every
  * datapoint with distance <= radius, stable-sorted by distance.  Writes at most `capacity` rows;
  * *out_count receives the number found (call again with a larger capacity if it exceeds it).
- * Empty dataset -> OK with 0 rows; wrong q_dim -> InvalidArgument. */
+ * Empty dataset -> OK with 0 rows; wrong q_dim -> InvalidArgument.
+ * scann_hip_bf_search_radius_opts: the same with opts->allow_bitmap (host pointer) applied -- every ALLOWED
+ * datapoint with distance <= radius, i.e. the radius search of a handle built from the allowed rows alone,
+ * indices mapped back.  opts == NULL or a NULL bitmap is scann_hip_bf_search_radius; other fields are not read. */
+int scann_hip_bf_search_radius_opts(scann_hip_index *index, const float *query, uint32_t q_dim, float radius,
+                                    const scann_hip_search_opts *opts, uint32_t *out_idx, float *out_dist,
+                                    uint64_t capacity, uint64_t *out_count);
+/* Rows of an n-row index that an allow-bitmap (host pointer) of capacity allow_bitmap_bits allows: the set bits
+ * below min(allow_bitmap_bits, n).  This is the count the host entry points plan a filtered brute-force search
+ * with (k = min(k, count), the choice between the compacted id list and the bit test); needs no device. */
+uint64_t scann_hip_allow_bitmap_count(const uint64_t *allow_bitmap, uint64_t allow_bitmap_bits, uint64_t n);
 int scann_hip_bf_search_radius(scann_hip_index *index, const float *query, uint32_t q_dim, float radius,
                                uint32_t *out_idx, float *out_dist, uint64_t capacity,
                                uint64_t *out_count);

@@ -105,7 +105,8 @@ def build(force=False, verbose=False, extra_flags=()):
 
 
 HOST = os.path.join(HERE, "host")
-HOST_PROGRAMS = ["host_test", "ann_benchmark"]   # C++ mirror of the reference API + its benchmark CLI
+HOST_PROGRAMS = ["host_test", "ann_benchmark", "bf_filter_test"]   # C++ mirror of the reference API, its benchmark CLI,
+                                                                # filtered brute force through the mirror
 
 
 def build_host(verbose=False):

@@ -1384,13 +1384,25 @@ static int txh_search_host(scann_hip_index *ix, const float *queries, uint32_t n
 
 }  // extern "C"
 
+// scann_hip_search_opts.allow_bitmap of a brute-force search (no filter: bitmap null)
+static BfFilter bf_filter_of(const scann_hip_search_opts *opts, const Knobs &kn) {
+    BfFilter f;
+    if (opts && opts->allow_bitmap) {
+        f.bitmap = opts->allow_bitmap;
+        f.bits = opts->allow_bitmap_bits;
+    }
+    f.mechanism = kn.bf_filter;
+    f.compact_max_fraction = kn.bf_filter_compact_max;
+    return f;
+}
+
 // BruteForceSearcher::search for a handful of queries over a small dataset: the three-launch pipeline of
 // txh.hip ("Small batches") on the one-leaf exact-scan view of the rows -- every distance with the
 // one-to-many kernels' arithmetic, the k smallest (distance, index) keys = TopK -- with queries and result
 // rows in pinned host memory (no copy commands).
 static int bf_small_search_host(scann_hip_index *ix, SlotLock &sl, const float *queries, uint32_t nq,
-                                uint32_t q_stride, uint32_t k, const Knobs &kn, uint32_t *out_idx, float *out_dist,
-                                uint32_t *out_count) {
+                                uint32_t q_stride, uint32_t k, const Knobs &kn, const BfFilter &flt, uint32_t *out_idx,
+                                float *out_dist, uint32_t *out_count) {
     TxhWorkspace &ws = *sl.ws;
     const uint32_t n = (uint32_t)ix->bf.n, kk = std::min(k, n);
     ws.want(ws.tokens, (size_t)nq * 4);
@@ -1400,7 +1412,13 @@ static int bf_small_search_host(scann_hip_index *ix, SlotLock &sl, const float *
     ws.want(ws.counters, CNT_WORDS * 4);
     ws.want(ws.cand, (size_t)nq * n * 8);
     ws.want(ws.small_tickets, 64 * 4);
+    // allow-list: the scan writes SCANN_KEY_MAX for a rejected row, which the finish stage never selects
+    const uint64_t allow_bits = std::min<uint64_t>(flt.bits, n);
+    const size_t allow_words = flt.bitmap ? (size_t)((allow_bits + 63) / 64) : 0;
+    if (flt.bitmap) ws.want(ws.allow, std::max<size_t>(allow_words, 1) * 8);
     SCANN_TRY(ws.commit());
+    if (allow_words)
+        SCANN_HIP_CHECK(hipMemcpyAsync(ws.allow.p, flt.bitmap, allow_words * 8, hipMemcpyHostToDevice, sl.stream));
     const size_t qb = (size_t)nq * q_stride * 4, ob = (size_t)nq * k * 4;
     const size_t off_idx = (qb + 255) & ~(size_t)255, off_dist = off_idx + ((ob + 255) & ~(size_t)255),
                  off_cnt = off_dist + ((ob + 255) & ~(size_t)255);
@@ -1412,7 +1430,8 @@ static int bf_small_search_host(scann_hip_index *ix, SlotLock &sl, const float *
     std::memset(hp + off_flag, 0, (size_t)nq * 4);   // (stale words of an earlier call's layout: see txh_search_host)
     TxhWork w{};
     w.nq = nq; w.q_stride = q_stride; w.P = 1; w.m = kk; w.k = k; w.cap = n; w.exact_reorder = false;
-    w.no_threshold = true; w.need_sorted_cands = 0; w.allow = nullptr; w.allow_bits = 0;
+    w.no_threshold = true; w.need_sorted_cands = 0;
+    w.allow = flt.bitmap ? ws.allow.as<uint64_t>() : nullptr; w.allow_bits = flt.bitmap ? allow_bits : 0;
     w.queries = reinterpret_cast<const float *>(dp);
     w.tokens = ws.tokens.as<uint32_t>(); w.token_dists = ws.token_dists.as<float>();
     w.vbase = ws.vbase.as<uint32_t>(); w.sbase = ws.sbase.as<uint32_t>(); w.st = 1;
@@ -1461,11 +1480,12 @@ int scann_hip_search_batched(scann_hip_index *ix, const float *queries, uint32_t
         SCANN_TRY(acquire_slot(ix, &sl));
         SCANN_TRY(set_device(ix->ctx));
         const Knobs kn = read_knobs();
+        const BfFilter flt = bf_filter_of(opts, kn);
         if (kn.small && ix->bfx.rows && nq <= kSmallBatch && k <= 64)
-            return bf_small_search_host(ix, sl, queries, nq, q_stride, k, kn, out_idx, out_dist, out_count);
+            return bf_small_search_host(ix, sl, queries, nq, q_stride, k, kn, flt, out_idx, out_dist, out_count);
         if (sl.primary) ix->next_events();
-        const bool shortlist = !(opts && opts->bf_exact) && bf_shortlist_eligible(ix->bf, nq, k, kn);
-        int s = bf_search_host(ix->bf, *sl.bfw, queries, nq, q_stride, k, shortlist, kn.bf_shortlist_tail, out_idx,
+        const bool shortlist = !flt.bitmap && !(opts && opts->bf_exact) && bf_shortlist_eligible(ix->bf, nq, k, kn);
+        int s = bf_search_host(ix->bf, *sl.bfw, queries, nq, q_stride, k, shortlist, kn.bf_shortlist_tail, flt, out_idx,
                                out_dist, out_count, sl.stream, sl.primary ? ix->ev0 : nullptr,
                                sl.primary ? ix->ev1 : nullptr);
         if (sl.primary) {
@@ -1536,7 +1556,7 @@ int scann_hip_index_reserve(scann_hip_index *ix, uint32_t max_nq, uint32_t max_k
     if (!ix) return fail(SCANN_HIP_INVALID_ARGUMENT, "index is null");
     std::lock_guard<std::mutex> lock(ix->mu);
     SCANN_TRY(set_device(ix->ctx));
-    if (ix->kind == KIND_BF) return bf_reserve(ix->bf, ix->bfw, max_nq, max_k);
+    if (ix->kind == KIND_BF) return bf_reserve(ix->bf, ix->bfw, max_nq, max_k, opts && opts->allow_bitmap);
     TxhPlan p;
     SCANN_TRY(plan_txh_search(ix, max_k, opts, max_nq, false, TxhPipeline::Staged, read_knobs(), &p));
     TxhWork w;
@@ -1558,8 +1578,9 @@ int scann_hip_search_batched_device(scann_hip_index *ix, const float *d_queries,
     const Knobs kn = read_knobs();
     if (ix->kind == KIND_BF) {
         ix->next_events();
-        const bool shortlist = !(opts && opts->bf_exact) && bf_shortlist_eligible(ix->bf, nq, k, kn);
-        int s = bf_search_device(ix->bf, *dsl->bfw, d_queries, nq, q_stride, k, shortlist, kn.bf_shortlist_tail,
+        const BfFilter flt = bf_filter_of(opts, kn);   // (a device pointer on this path)
+        const bool shortlist = !flt.bitmap && !(opts && opts->bf_exact) && bf_shortlist_eligible(ix->bf, nq, k, kn);
+        int s = bf_search_device(ix->bf, *dsl->bfw, d_queries, nq, q_stride, k, shortlist, kn.bf_shortlist_tail, flt,
                                  d_out_idx, d_out_dist, d_out_count, st, ix->ev0, ix->ev1);
         if (s == SCANN_HIP_OK) s = device_slot_done(dsl, st);
         ix->timing_valid = ix->timing && s == SCANN_HIP_OK;
@@ -1903,6 +1924,16 @@ int scann_hip_bf_distances(scann_hip_index *ix, const float *queries, uint32_t n
 int scann_hip_bf_search_radius(scann_hip_index *ix, const float *query, uint32_t q_dim, float radius,
                                uint32_t *out_idx, float *out_dist, uint64_t capacity,
                                uint64_t *out_count) {
+    return scann_hip_bf_search_radius_opts(ix, query, q_dim, radius, nullptr, out_idx, out_dist, capacity, out_count);
+}
+
+uint64_t scann_hip_allow_bitmap_count(const uint64_t *allow_bitmap, uint64_t allow_bitmap_bits, uint64_t n) {
+    return allow_bitmap ? bf_allowed_count(allow_bitmap, allow_bitmap_bits, n) : 0;
+}
+
+int scann_hip_bf_search_radius_opts(scann_hip_index *ix, const float *query, uint32_t q_dim, float radius,
+                                    const scann_hip_search_opts *opts, uint32_t *out_idx, float *out_dist,
+                                    uint64_t capacity, uint64_t *out_count) {
     if (!ix || ix->kind != KIND_BF) return fail(SCANN_HIP_INVALID_ARGUMENT, "not a brute-force index");
     if (!out_count) return fail(SCANN_HIP_INVALID_ARGUMENT, "null out_count");
     *out_count = 0;
@@ -1913,8 +1944,8 @@ int scann_hip_bf_search_radius(scann_hip_index *ix, const float *query, uint32_t
     std::lock_guard<std::mutex> lock(ix->mu);
     SCANN_TRY(set_device(ix->ctx));
     SCANN_TRY(claim_primary_workspace(ix));
-    return bf_search_radius_host(ix->bf, ix->bfw, query, q_dim, radius, out_idx, out_dist, capacity,
-                                 out_count, ix->stream);
+    return bf_search_radius_host(ix->bf, ix->bfw, query, q_dim, radius, bf_filter_of(opts, read_knobs()), out_idx,
+                                 out_dist, capacity, out_count, ix->stream);
 }
 
 int scann_hip_bf_assign_nearest(scann_hip_index *ix, const float *centers, uint32_t num_centers,

@@ -25,7 +25,20 @@ struct BfIndexDev {
 struct BfWorkspace {
     DevBuf queries, sample, thr, cand_cnt, cand, counters, out_idx, out_dist, out_count;
     DevBuf q_b, q_bl, q_n2, sl_idx, sl_approx, sl_cnt, sl_exact, sl_fail;   // bf16 shortlist path
+    DevBuf allow, ids, allow_sums;   // filtered search: bitmap copy, compacted id list, per-block popcounts
 };
+
+// Allow-list of one search (scann_hip_search_opts.allow_bitmap / allow_bitmap_bits); bitmap == nullptr: none.
+// A filtered search answers as an unfiltered search over the allowed rows alone, indices mapped back.
+struct BfFilter {
+    const uint64_t *bitmap = nullptr;   // host pointer in the host entries, device pointer in bf_search_device
+    uint64_t bits = 0;
+    int mechanism = 0;                  // Knobs::bf_filter: 0 by the rule below, 1 compacted id list, 2 bit test
+    double compact_max_fraction = 0.0;  // Knobs::bf_filter_compact_max: compacted up to this allowed fraction
+};
+
+// Allowed rows of an n-row index: set bits below min(bits, n).  The host mirror of the device compaction.
+uint64_t bf_allowed_count(const uint64_t *bitmap, uint64_t bits, uint64_t n);
 
 // bf16 copy + squared norms of the rows (index creation); *max_norm = largest row norm.
 int bf_build_shortlist_data(const BfIndexDev &ix, DevBuf &rows_b, DevBuf &rows_bl, DevBuf &norm2,
@@ -35,22 +48,25 @@ bool bf_shortlist_eligible(const BfIndexDev &ix, uint32_t nq, uint32_t k, const 
 
 constexpr uint32_t kBfSampleRows = 8192;   // rows of the threshold sample (== LDS sort size)
 
-int bf_reserve(const BfIndexDev &ix, BfWorkspace &w, uint32_t max_nq, uint32_t max_k);
+// filtered: also what a filtered host search needs (the device entry reads the caller's bitmap in place)
+int bf_reserve(const BfIndexDev &ix, BfWorkspace &w, uint32_t max_nq, uint32_t max_k, bool filtered);
 
 const char *bf_pass_kernel_name(const BfIndexDev &ix, uint32_t nq);
 
 // Host-pointer entry (copies in/out, synchronises).  shortlist: take the bf16-shortlist path first
 // (bf_shortlist_eligible), whose bound misses with probability `tail`; queries it cannot verify are repeated exactly.
 int bf_search_host(const BfIndexDev &ix, BfWorkspace &w, const float *queries, uint32_t nq,
-                   uint32_t q_stride, uint32_t k, bool shortlist, double tail, uint32_t *out_idx, float *out_dist,
-                   uint32_t *out_count, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1);
+                   uint32_t q_stride, uint32_t k, bool shortlist, double tail, const BfFilter &flt, uint32_t *out_idx,
+                   float *out_dist, uint32_t *out_count, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1);
 
 // Device-pointer entry (enqueue only).
 // shortlist: the bf16-shortlist path (status Aborted in the counters if a query's result could not be verified:
-// repeat without it).
+// repeat without it).  A filtered search takes the bit test at the emit (the allowed count is not known without a
+// synchronisation) and never the shortlist; a filter that leaves fewer than k allowed rows in the 8192-row sample
+// yields no bound, and the candidate buffer may overflow: status ResourceExhausted, out_count 0 for those queries.
 int bf_search_device(const BfIndexDev &ix, BfWorkspace &w, const float *d_queries, uint32_t nq,
-                     uint32_t q_stride, uint32_t k, bool shortlist, double tail, uint32_t *d_out_idx,
-                     float *d_out_dist, uint32_t *d_out_count, hipStream_t stream, hipEvent_t ev0,
+                     uint32_t q_stride, uint32_t k, bool shortlist, double tail, const BfFilter &flt,
+                     uint32_t *d_out_idx, float *d_out_dist, uint32_t *d_out_count, hipStream_t stream, hipEvent_t ev0,
                      hipEvent_t ev1);
 // OK, or the status the last enqueued search left in the workspace counters (synchronises).
 int bf_last_status(const BfWorkspace &w, hipStream_t stream);
@@ -65,7 +81,7 @@ int bf_distances_host(const BfIndexDev &ix, BfWorkspace &w, const float *queries
 // BruteForceSearcher::search_radius for one query: all rows with distance <= radius, sorted by
 // (distance, index).  At most `capacity` rows are written; *out_count = number found.
 int bf_search_radius_host(const BfIndexDev &ix, BfWorkspace &w, const float *query, uint32_t q_stride,
-                          float radius, uint32_t *out_idx, float *out_dist, uint64_t capacity,
+                          float radius, const BfFilter &flt, uint32_t *out_idx, float *out_dist, uint64_t capacity,
                           uint64_t *out_count, hipStream_t stream);
 
 // Nearest of k centres for every row of the index (sequential-scalar SquaredL2, lowest index on

@@ -46,14 +46,32 @@ struct BfPass {
     uint32_t *cand_cnt;     // [nq]
     uint64_t *cand;         // [nq][cap]
     uint32_t cap;
+    // allow-list filter (scann_hip_search_opts.allow_bitmap); both null on an unfiltered search.
+    const uint32_t *ids;    // compacted form: real row = ids[virtual row * row_mult], ascending allowed datapoints
+    const uint64_t *allow;  // bit-test form: a row is a candidate only if its bit is set (tested at the emit)
+    uint32_t allow_bits;    // capacity of the bitmap clipped to the row count
 };
+
+// datapoint index of a virtual row (the row that is read, and the index half of its key)
+__device__ __forceinline__ uint32_t bf_real_row(const BfPass &p, uint32_t vrow) {
+    const uint32_t r = vrow * p.row_mult;
+    return p.ids ? p.ids[r] : r;
+}
+
+// RestrictFilter::is_allowed (restricts/mod.rs:17-30) on the bitmap form: indices at or past the capacity are
+// not allowed (allowlist.rs:97-100).
+__device__ __forceinline__ bool bf_row_allowed(const uint64_t *allow, uint32_t allow_bits, uint32_t row) {
+    return row < allow_bits && ((allow[row >> 6] >> (row & 63u)) & 1ull);
+}
 
 __device__ __forceinline__ void bf_emit(const BfPass &p, uint32_t q, uint32_t vrow, float dist,
                                         float Tf, uint64_t T) {
     if (!p.filter) {
         p.out[(size_t)q * p.ld + vrow] = dist;
     } else if (dist <= Tf) {
-        const uint64_t key = make_key(dist, vrow * p.row_mult);
+        const uint32_t row = bf_real_row(p, vrow);
+        if (p.allow && !bf_row_allowed(p.allow, p.allow_bits, row)) return;   // skipped before scoring: mod.rs:327-332
+        const uint64_t key = make_key(dist, row);
         if (key <= T) {
             const uint32_t pos = atomicAdd(&p.cand_cnt[q], 1u);
             if (pos < p.cap) p.cand[(size_t)q * p.cap + pos] = key;
@@ -108,7 +126,7 @@ __global__ __launch_bounds__(256) void bf_generic_kernel(BfIndexDev ix, BfPass p
     }
     const uint32_t vrow = blockIdx.x * blockDim.x + threadIdx.x;
     if (vrow >= p.nrows) return;
-    const float *row = ix.rows + (size_t)vrow * p.row_mult * ix.stride;
+    const float *row = ix.rows + (size_t)bf_real_row(p, vrow) * ix.stride;
     // The 8 AVX2 lane chains of a (query, row) pair are independent accumulators: pairs of
     // them go through the packed-f32 pipe (v_pk_add_f32 / v_pk_fma_f32: two IEEE operations per
     // instruction, same results as the scalar ones).
@@ -243,7 +261,7 @@ __global__ __launch_bounds__(256) void bf_stream_kernel(BfIndexDev ix, BfPass p)
         const float *src[8];
 #pragma unroll
         for (int i = 0; i < 8; ++i)
-            src[i] = ix.rows + (size_t)min(vrow0 + rsub + 8u * i, p.nrows - 1u) * p.row_mult * ix.stride;
+            src[i] = ix.rows + (size_t)bf_real_row(p, min(vrow0 + rsub + 8u * i, p.nrows - 1u)) * ix.stride;
         float4 s0, s1, s2, s3, s4, s5, s6, s7;
         // lanes past a short last slice re-read its last piece (never stored)
 #define SCANN_ST_FETCH(d0_)                                                                  \
@@ -311,7 +329,7 @@ __global__ __launch_bounds__(256) void bf_stream_kernel(BfIndexDev ix, BfPass p)
         }
         const uint32_t vrow = vrow0 + lane;
         if (vrow < p.nrows) {
-            const float *row = ix.rows + (size_t)vrow * p.row_mult * ix.stride;
+            const float *row = ix.rows + (size_t)bf_real_row(p, vrow) * ix.stride;
 #pragma unroll
             for (int qi = 0; qi < kStQT; ++qi) {
                 if (q0 + qi >= p.nq) continue;
@@ -389,7 +407,7 @@ __global__ __launch_bounds__(256, 2) void bf_vq_kernel(BfIndexDev ix, BfPass p, 
             const uint32_t r = e / DIM, j = e - r * DIM;
             const uint32_t vrow = t * kVqRows + r;
             stage[i] = vrow < p.nrows
-                           ? *reinterpret_cast<const float4 *>(ix.rows + (size_t)vrow * p.row_mult * ix.stride + j)
+                           ? *reinterpret_cast<const float4 *>(ix.rows + (size_t)bf_real_row(p, vrow) * ix.stride + j)
                            : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         }
     };
@@ -505,7 +523,7 @@ __global__ __launch_bounds__(256, 2) void bf_mfma_dot_kernel(BfIndexDev ix, BfPa
             const uint32_t ci = gi * 64u + lane;                  // linear chunk index in the tile
             const uint32_t r = ci / CPR, pos = ci - r * CPR;
             const uint32_t vr = min(tile * 32u + r, p.nrows - 1u);
-            const float *src = ix.rows + (size_t)vr * p.row_mult * ix.stride + 4u * (pos ^ (r & SW));
+            const float *src = ix.rows + (size_t)bf_real_row(p, vr) * ix.stride + 4u * (pos ^ (r & SW));
             __builtin_amdgcn_global_load_lds(
                 (const __attribute__((address_space(1))) void *)src,
                 (__attribute__((address_space(3))) void *)(xs + (size_t)buf * TILE_F + gi * 256u), 16, 0, 0);
@@ -1321,11 +1339,20 @@ __global__ __launch_bounds__(64) void bf_shortlist_final_kernel(
 __global__ __launch_bounds__(kBfSelectThreads) void bf_threshold_kernel(
     const float *__restrict__ sample, uint32_t ns, uint32_t row_mult, uint32_t k, int direct,
     uint64_t *__restrict__ thr, uint32_t *__restrict__ out_idx, float *__restrict__ out_dist,
-    uint32_t *__restrict__ out_count) {
+    uint32_t *__restrict__ out_count, const uint32_t *__restrict__ ids, const uint64_t *__restrict__ allow,
+    uint32_t allow_bits) {
     extern __shared__ __attribute__((aligned(16))) uint64_t skeys[];   // [next_pow2(ns)]
     const uint32_t q = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
     uint32_t n2 = 1;
     while (n2 < ns) n2 <<= 1;
+    // Key of sample i.  Under a filter the index half is the datapoint index (ids: the compacted list), and a
+    // sample whose datapoint the bitmap rejects is ABSENT (SCANN_KEY_MAX), not a distance: the bound is taken over
+    // allowed samples only -- with fewer than k of them the k-th key is SCANN_KEY_MAX, the no-bound value.
+    auto sample_key = [&](uint32_t i) -> uint64_t {
+        const uint32_t r = i * row_mult, row = ids ? ids[r] : r;
+        if (allow && !bf_row_allowed(allow, allow_bits, row)) return SCANN_KEY_MAX;
+        return make_key(sample[(size_t)q * ns + i], row);
+    };
     if (!direct) {
         // the k-th smallest sample key bounds the k-th smallest key of the whole dataset; a
         // histogram rank-select finds it without sorting the 8192 samples
@@ -1333,24 +1360,89 @@ __global__ __launch_bounds__(kBfSelectThreads) void bf_threshold_kernel(
         uint32_t *s_hist = reinterpret_cast<uint32_t *>(skeys + n2);
         uint64_t *s_list = reinterpret_cast<uint64_t *>(s_hist + cfg.bins);
         uint64_t *s_red = s_list + cfg.list;
-        for (uint32_t i = tid; i < ns; i += nt) skeys[i] = make_key(sample[(size_t)q * ns + i], i * row_mult);
+        for (uint32_t i = tid; i < ns; i += nt) skeys[i] = sample_key(i);
         __syncthreads();
         uint64_t T = SCANN_KEY_MAX;
         if (ns >= k && k > 0) T = block_select<uint64_t>(skeys, ns, k, cfg, s_hist, s_list, s_red);
         if (tid == 0) thr[q] = T;
         return;
     }
-    for (uint32_t i = tid; i < n2; i += nt)
-        skeys[i] = (i < ns) ? make_key(sample[(size_t)q * ns + i], i * row_mult) : SCANN_KEY_MAX;
+    uint32_t *s_absent = reinterpret_cast<uint32_t *>(skeys + n2);   // rows the bitmap rejects
+    if (tid == 0) *s_absent = 0;
+    __syncthreads();
+    for (uint32_t i = tid; i < n2; i += nt) {
+        const uint64_t key = (i < ns) ? sample_key(i) : SCANN_KEY_MAX;
+        if (allow && i < ns && key == SCANN_KEY_MAX) atomicAdd(s_absent, 1u);   // (no real key of an allowed row is
+        skeys[i] = key;                                                          // MAX: its index half is a row < n)
+    }
     __syncthreads();
     bitonic_sort_lds(skeys, n2);
-    const uint32_t nout = min(k, ns);
+    const uint32_t nout = min(k, ns - *s_absent);
     for (uint32_t i = tid; i < k; i += nt) {
         out_idx[(size_t)q * k + i] = (i < nout) ? (uint32_t)skeys[i] : kBfInvalid;
         out_dist[(size_t)q * k + i] =
             (i < nout) ? ordered_to_f32((uint32_t)(skeys[i] >> 32)) : __builtin_inff();
     }
     if (tid == 0) out_count[q] = nout;
+}
+
+// =====================================================================================
+// Allow-list compaction: the ascending list of allowed datapoint indices.  Word w of the bitmap covers datapoints
+// [64 w, 64 w + 64); bits at or past `bits` (the capacity clipped to the row count) are masked off.  Two launches:
+// per-block popcounts of kCompactWords words, then every block adds up the blocks before it, scans its own words
+// and writes their set bits in order.  *total = the allowed count A.
+// =====================================================================================
+constexpr uint32_t kCompactWords = 256;   // bitmap words per block = one per thread
+
+__device__ __forceinline__ uint64_t bf_allow_word(const uint64_t *allow, uint32_t bits, uint32_t w) {
+    if ((uint64_t)w * 64u >= bits) return 0;
+    const uint64_t v = allow[w];
+    const uint32_t rem = bits - w * 64u;
+    return rem >= 64u ? v : (v & ((1ull << rem) - 1ull));
+}
+
+__global__ __launch_bounds__(kCompactWords) void bf_allow_count_kernel(const uint64_t *__restrict__ allow, uint32_t bits,
+                                                                       uint32_t *__restrict__ block_sums) {
+    __shared__ uint32_t s_sum;
+    if (threadIdx.x == 0) s_sum = 0;
+    __syncthreads();
+    const uint32_t c = (uint32_t)__popcll(bf_allow_word(allow, bits, blockIdx.x * kCompactWords + threadIdx.x));
+    if (c) atomicAdd(&s_sum, c);
+    __syncthreads();
+    if (threadIdx.x == 0) block_sums[blockIdx.x] = s_sum;
+}
+
+__global__ __launch_bounds__(kCompactWords) void bf_allow_compact_kernel(const uint64_t *__restrict__ allow, uint32_t bits,
+                                                                         const uint32_t *__restrict__ block_sums,
+                                                                         uint32_t *__restrict__ ids, uint32_t ids_cap,
+                                                                         uint32_t *__restrict__ total) {
+    __shared__ uint32_t s_base, s_wave[kCompactWords / 64];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    if (tid == 0) s_base = 0;
+    __syncthreads();
+    uint32_t before = 0;
+    for (uint32_t b = tid; b < blockIdx.x; b += kCompactWords) before += block_sums[b];
+    if (before) atomicAdd(&s_base, before);
+    const uint32_t w = blockIdx.x * kCompactWords + tid;
+    uint64_t word = bf_allow_word(allow, bits, w);
+    const uint32_t c = (uint32_t)__popcll(word);
+    uint32_t incl = c;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t up = (uint32_t)__shfl_up((int)incl, o);
+        if ((int)lane >= o) incl += up;
+    }
+    if (lane == 63) s_wave[wave] = incl;
+    __syncthreads();
+    uint32_t pos = s_base + incl - c;
+    for (uint32_t w2 = 0; w2 < wave; ++w2) pos += s_wave[w2];
+    while (word) {
+        const uint32_t b = (uint32_t)__builtin_ctzll(word);
+        word &= word - 1ull;
+        if (pos < ids_cap) ids[pos] = w * 64u + b;
+        ++pos;
+    }
+    if (blockIdx.x == gridDim.x - 1 && tid == kCompactWords - 1) *total = pos;
 }
 
 // In-place stable compaction (keys <= T) by one block.
@@ -1480,7 +1572,7 @@ __global__ __launch_bounds__(256) void bf_quant_kernel(BfIndexDev ix, BfPass p) 
     const uint32_t vrow = blockIdx.x * blockDim.x + threadIdx.x;
     if (vrow >= p.nrows) return;
     const float inv = ix.inv_mult;
-    const uint8_t *row = static_cast<const uint8_t *>(ix.qrows) + (size_t)vrow * p.row_mult * ix.stride * B;
+    const uint8_t *row = static_cast<const uint8_t *>(ix.qrows) + (size_t)bf_real_row(p, vrow) * ix.stride * B;
     const bool vec = (((size_t)ix.stride * B) & 15u) == 0 && (reinterpret_cast<uintptr_t>(ix.qrows) & 15u) == 0;
     f32x2q acc[QT / 2][NCH];
 #pragma unroll
@@ -1779,15 +1871,16 @@ static int launch_pass(const BfIndexDev &ix, const BfPass &p, hipStream_t st) {
 }
 
 struct BfPlan {
-    uint32_t k, ns, rs, cap;
+    uint32_t n, k, ns, rs, cap;
     bool direct;
 };
 
-static int make_plan(const BfIndexDev &ix, uint32_t k, bool full_cap, BfPlan *pl) {
-    const uint32_t n = (uint32_t)ix.n;
+// n: the rows the passes run over -- ix.n, or the allowed count A of a compacted filtered search
+static int make_plan(uint32_t n, uint32_t k, bool full_cap, BfPlan *pl) {
     k = std::min(k, n);  // brute_force/searcher.rs:91
     if (k > kBfMaxK)
         return fail(SCANN_HIP_UNIMPLEMENTED, "k > " + std::to_string(kBfMaxK) + " on the GPU path");
+    pl->n = n;
     pl->k = k;
     pl->direct = n <= kBfSampleRows;
     pl->ns = std::min(n, kBfSampleRows);
@@ -1814,15 +1907,64 @@ static int ensure_ws(const BfIndexDev &ix, BfWorkspace &w, uint32_t nq, const Bf
     return SCANN_HIP_OK;
 }
 
-int bf_reserve(const BfIndexDev &ix, BfWorkspace &w, uint32_t max_nq, uint32_t max_k) {
+// What a pass needs of the allow-list, on the device.  ids: compacted form (nrows = allowed count); allow: bit test.
+struct BfFilterDev {
+    const uint32_t *ids = nullptr;
+    const uint64_t *allow = nullptr;
+    uint32_t allow_bits = 0;
+};
+
+uint64_t bf_allowed_count(const uint64_t *bitmap, uint64_t bits, uint64_t n) {
+    const uint64_t eff = std::min(bits, n);
+    uint64_t count = 0;
+    for (uint64_t w = 0; w * 64 < eff; ++w) {
+        const uint64_t rem = eff - w * 64;
+        count += (uint64_t)__builtin_popcountll(rem >= 64 ? bitmap[w] : (bitmap[w] & ((1ull << rem) - 1ull)));
+    }
+    return count;
+}
+
+// Host bitmap -> workspace copy (and, compacted form, the id list of its `count` allowed rows).
+static int upload_filter(const BfIndexDev &ix, BfWorkspace &w, const BfFilter &f, bool compact, uint32_t count,
+                         BfFilterDev *fd, hipStream_t st) {
+    const uint32_t bits = (uint32_t)std::min<uint64_t>(f.bits, ix.n);
+    const size_t words = ((size_t)bits + 63) / 64;
+    SCANN_TRY(w.allow.ensure(std::max<size_t>(words, 1) * 8));
+    if (words) SCANN_HIP_CHECK(hipMemcpyAsync(w.allow.p, f.bitmap, words * 8, hipMemcpyHostToDevice, st));
+    fd->allow = w.allow.as<uint64_t>();
+    fd->allow_bits = bits;
+    if (!compact) return SCANN_HIP_OK;
+    const uint32_t blocks = std::max(1u, ceil_div_u32((uint32_t)words, kCompactWords));
+    SCANN_TRY(w.ids.ensure(std::max<size_t>(count, 1) * 4));
+    SCANN_TRY(w.allow_sums.ensure((size_t)(blocks + 1) * 4));
+    uint32_t *sums = w.allow_sums.as<uint32_t>();
+    hipLaunchKernelGGL(bf_allow_count_kernel, dim3(blocks), dim3(kCompactWords), 0, st, fd->allow, bits, sums);
+    LAUNCH_CHECK();
+    hipLaunchKernelGGL(bf_allow_compact_kernel, dim3(blocks), dim3(kCompactWords), 0, st, fd->allow, bits, sums,
+                       w.ids.as<uint32_t>(), count, sums + blocks);
+    LAUNCH_CHECK();
+    fd->ids = w.ids.as<uint32_t>();
+    fd->allow = nullptr;   // every listed row is allowed
+    fd->allow_bits = 0;
+    return SCANN_HIP_OK;
+}
+
+int bf_reserve(const BfIndexDev &ix, BfWorkspace &w, uint32_t max_nq, uint32_t max_k, bool filtered) {
     if (ix.n == 0) return SCANN_HIP_OK;
     BfPlan pl;
-    SCANN_TRY(make_plan(ix, max_k, false, &pl));
+    SCANN_TRY(make_plan((uint32_t)ix.n, max_k, false, &pl));
+    if (filtered) {   // host entries: bitmap copy, id list, block sums (the device entry reads the caller's bitmap)
+        const size_t words = ((size_t)ix.n + 63) / 64;
+        SCANN_TRY(w.allow.ensure(words * 8));
+        SCANN_TRY(w.ids.ensure((size_t)ix.n * 4));
+        SCANN_TRY(w.allow_sums.ensure((size_t)(ceil_div_u32((uint32_t)words, kCompactWords) + 1) * 4));
+    }
     return ensure_ws(ix, w, max_nq, pl, false, 0, false);
 }
 
 // k_out: row pitch of the caller's output arrays (the caller's k, >= pl.k).
-static int enqueue_search(const BfIndexDev &ix, BfWorkspace &w, const BfPlan &pl,
+// fd: the allow-list; compacted form: pl was made for its allowed count and the passes run over fd.ids.
+static int enqueue_search(const BfIndexDev &ix, BfWorkspace &w, const BfPlan &pl, const BfFilterDev &fd,
                           const float *d_queries, uint32_t nq, uint32_t q_stride,
                           uint32_t *d_out_idx, float *d_out_dist, uint32_t *d_out_count,
                           hipStream_t st, hipEvent_t ev0, hipEvent_t ev1) {
@@ -1836,6 +1978,9 @@ static int enqueue_search(const BfIndexDev &ix, BfWorkspace &w, const BfPlan &pl
     a.filter = 0;
     a.out = w.sample.as<float>();
     a.ld = pl.ns;
+    a.ids = fd.ids;
+    a.allow = fd.allow;
+    a.allow_bits = fd.allow_bits;
     if (pl.direct && ev0) SCANN_HIP_CHECK(hipEventRecord(ev0, st));
     SCANN_TRY(launch_pass(ix, a, st));
     if (pl.direct && ev1) SCANN_HIP_CHECK(hipEventRecord(ev1, st));
@@ -1844,13 +1989,13 @@ static int enqueue_search(const BfIndexDev &ix, BfWorkspace &w, const BfPlan &pl
     SCANN_TRY(set_dyn_lds(bf_threshold_kernel, lds_thr));
     hipLaunchKernelGGL(bf_threshold_kernel, dim3(nq), dim3(kBfSelectThreads), lds_thr, st,
                        w.sample.as<float>(), pl.ns, pl.rs, pl.k, pl.direct ? 1 : 0,
-                       w.thr.as<uint64_t>(), d_out_idx, d_out_dist, d_out_count);
+                       w.thr.as<uint64_t>(), d_out_idx, d_out_dist, d_out_count, fd.ids, fd.allow, fd.allow_bits);
     LAUNCH_CHECK();
     if (pl.direct) return SCANN_HIP_OK;
 
     SCANN_HIP_CHECK(hipMemsetAsync(w.cand_cnt.p, 0, (size_t)nq * 4, st));
     BfPass b = a;
-    b.nrows = (uint32_t)ix.n;
+    b.nrows = fd.ids ? pl.n : (uint32_t)ix.n;
     b.row_mult = 1;
     b.filter = 1;
     b.out = nullptr;
@@ -2069,7 +2214,7 @@ static int enqueue_shortlist_search(const BfIndexDev &ix, BfWorkspace &w, uint32
     }
     hipLaunchKernelGGL(bf_threshold_kernel, dim3(nq), dim3(kBfSelectThreads), lds_thr, st, w.sample.as<float>(),
                        ns, rs, jthr, 0, w.thr.as<uint64_t>(), (uint32_t *)nullptr, (float *)nullptr,
-                       (uint32_t *)nullptr);
+                       (uint32_t *)nullptr, (const uint32_t *)nullptr, (const uint64_t *)nullptr, 0u);
     LAUNCH_CHECK();
     // 2. bf16 scores of every row, filtered by that bound
     BfPass b = a;
@@ -2134,29 +2279,57 @@ int bf_last_status(const BfWorkspace &w, hipStream_t st) {
 }
 
 int bf_search_device(const BfIndexDev &ix, BfWorkspace &w, const float *d_queries, uint32_t nq,
-                     uint32_t q_stride, uint32_t k, bool shortlist, double tail, uint32_t *d_out_idx, float *d_out_dist,
+                     uint32_t q_stride, uint32_t k, bool shortlist, double tail, const BfFilter &flt,
+                     uint32_t *d_out_idx, float *d_out_dist,
                      uint32_t *d_out_count, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1) {
     if (ix.n == 0) return fail(SCANN_HIP_INVALID_ARGUMENT, "empty dataset on the device path");
     BfPlan pl;
-    SCANN_TRY(make_plan(ix, k, false, &pl));
+    SCANN_TRY(make_plan((uint32_t)ix.n, k, false, &pl));
     if (pl.k != k)
         return fail(SCANN_HIP_INVALID_ARGUMENT, "k > dataset size on the device path (row pitch)");
+    BfFilterDev fd;
+    if (flt.bitmap) {   // bit test at the emit: the allowed count is not known without a synchronisation
+        fd.allow = flt.bitmap;
+        fd.allow_bits = (uint32_t)std::min<uint64_t>(flt.bits, ix.n);
+        shortlist = false;
+    }
     if (shortlist)
         return enqueue_shortlist_search(ix, w, k, tail, d_queries, nq, q_stride, d_out_idx, d_out_dist, d_out_count, st,
                                         ev0, ev1);
     SCANN_TRY(ensure_ws(ix, w, nq, pl, false, q_stride, false));
-    return enqueue_search(ix, w, pl, d_queries, nq, q_stride, d_out_idx, d_out_dist, d_out_count, st,
+    return enqueue_search(ix, w, pl, fd, d_queries, nq, q_stride, d_out_idx, d_out_dist, d_out_count, st,
                           ev0, ev1);
 }
 
 int bf_search_host(const BfIndexDev &ix, BfWorkspace &w, const float *queries, uint32_t nq,
-                   uint32_t q_stride, uint32_t k, bool shortlist, double tail, uint32_t *out_idx, float *out_dist,
-                   uint32_t *out_count, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1) {
-    // attempt 0: bf16 shortlist (if the search qualifies); 1: exact kernels; 2: exact, full buffers
+                   uint32_t q_stride, uint32_t k, bool shortlist, double tail, const BfFilter &flt, uint32_t *out_idx,
+                   float *out_dist, uint32_t *out_count, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1) {
+    // Filtered search: the answer of an unfiltered search over the allowed rows alone.  The allowed count A comes
+    // from the host bitmap; the bf16 shortlist is not taken (its proof would have to hold over allowed rows only).
+    uint32_t allowed = (uint32_t)ix.n;
+    bool compact = false;
+    if (flt.bitmap) {
+        allowed = (uint32_t)bf_allowed_count(flt.bitmap, flt.bits, ix.n);
+        shortlist = false;
+        if (allowed == 0) {
+            for (size_t i = 0; i < (size_t)nq * k; ++i) {
+                out_idx[i] = kBfInvalid;
+                out_dist[i] = INFINITY;
+            }
+            for (uint32_t q = 0; q < nq; ++q) out_count[q] = 0;
+            return SCANN_HIP_OK;
+        }
+        compact = flt.mechanism == 1 || (flt.mechanism == 0 && (double)allowed <= flt.compact_max_fraction * (double)ix.n);
+    }
+    // attempt 0: bf16 shortlist (if the search qualifies); 1: exact kernels; 2: exact, full buffers (a filtered
+    // search whose bit-test pass overflowed -- too few allowed rows in the sample for a bound -- repeats compacted)
     for (int attempt = shortlist ? 0 : 1; attempt < 3; ++attempt) {
+        if (attempt == 2 && flt.bitmap && flt.mechanism != 2) compact = true;
         BfPlan pl;
-        SCANN_TRY(make_plan(ix, k, attempt == 2, &pl));
+        SCANN_TRY(make_plan(compact ? allowed : (uint32_t)ix.n, std::min(k, allowed), attempt == 2, &pl));
         SCANN_TRY(ensure_ws(ix, w, nq, pl, true, q_stride, true));
+        BfFilterDev fd;
+        if (flt.bitmap) SCANN_TRY(upload_filter(ix, w, flt, compact, allowed, &fd, st));
         SCANN_HIP_CHECK(hipMemcpyAsync(w.queries.p, queries, (size_t)nq * q_stride * 4,
                                        hipMemcpyHostToDevice, st));
         if (attempt == 0)
@@ -2164,7 +2337,7 @@ int bf_search_host(const BfIndexDev &ix, BfWorkspace &w, const float *queries, u
                                                w.out_idx.as<uint32_t>(), w.out_dist.as<float>(),
                                                w.out_count.as<uint32_t>(), st, ev0, ev1));
         else
-            SCANN_TRY(enqueue_search(ix, w, pl, w.queries.as<float>(), nq, q_stride,
+            SCANN_TRY(enqueue_search(ix, w, pl, fd, w.queries.as<float>(), nq, q_stride,
                                      w.out_idx.as<uint32_t>(), w.out_dist.as<float>(),
                                      w.out_count.as<uint32_t>(), st, ev0, ev1));
         uint32_t counters[BF_CNT_N];
@@ -2205,8 +2378,8 @@ int bf_search_host(const BfIndexDev &ix, BfWorkspace &w, const float *queries, u
                 std::memcpy(&sub[(size_t)r * q_stride], queries + (size_t)redo[r] * q_stride, (size_t)q_stride * 4);
             std::vector<uint32_t> ri((size_t)nr * k), rc(nr);
             std::vector<float> rd((size_t)nr * k);
-            SCANN_TRY(bf_search_host(ix, w, sub.data(), nr, q_stride, k, false, tail, ri.data(), rd.data(), rc.data(), st,
-                                     nullptr, nullptr));
+            SCANN_TRY(bf_search_host(ix, w, sub.data(), nr, q_stride, k, false, tail, BfFilter{}, ri.data(), rd.data(),
+                                     rc.data(), st, nullptr, nullptr));
             for (uint32_t r = 0; r < nr; ++r) {
                 std::memcpy(out_idx + (size_t)redo[r] * k, &ri[(size_t)r * k], (size_t)k * 4);
                 std::memcpy(out_dist + (size_t)redo[r] * k, &rd[(size_t)r * k], (size_t)k * 4);
@@ -2267,9 +2440,8 @@ __global__ void bf_decode_keys_kernel(const uint64_t *__restrict__ keys, uint32_
 }
 
 int bf_search_radius_host(const BfIndexDev &ix, BfWorkspace &w, const float *query, uint32_t q_stride,
-                          float radius, uint32_t *out_idx, float *out_dist, uint64_t capacity,
+                          float radius, const BfFilter &flt, uint32_t *out_idx, float *out_dist, uint64_t capacity,
                           uint64_t *out_count, hipStream_t st) {
-    (void)w;
     const uint32_t n = (uint32_t)ix.n;
     DevBuf dq, dthr, dcnt, dcand, dsorted, dtmp, didx, ddist;
     SCANN_TRY(upload(dq, query, (size_t)q_stride * 4));
@@ -2279,21 +2451,37 @@ int bf_search_radius_host(const BfIndexDev &ix, BfWorkspace &w, const float *que
         *out_count = 0;
         return SCANN_HIP_OK;
     }
+    // allow-list: the same pass over the allowed rows only (compacted id list), or with the bit test at the emit
+    uint32_t allowed = n;
+    BfFilterDev fd;
+    if (flt.bitmap) {
+        allowed = (uint32_t)bf_allowed_count(flt.bitmap, flt.bits, ix.n);
+        if (allowed == 0) {
+            *out_count = 0;
+            return SCANN_HIP_OK;
+        }
+        const bool compact =
+            flt.mechanism == 1 || (flt.mechanism == 0 && (double)allowed <= flt.compact_max_fraction * (double)n);
+        SCANN_TRY(upload_filter(ix, w, flt, compact, allowed, &fd, st));
+    }
     SCANN_TRY(upload(dthr, &T, 8));
     SCANN_TRY(dcnt.ensure(4));
-    SCANN_TRY(dcand.ensure((size_t)n * 8));
+    SCANN_TRY(dcand.ensure((size_t)allowed * 8));
     SCANN_HIP_CHECK(hipMemsetAsync(dcnt.p, 0, 4, st));
     BfPass b{};
     b.queries = dq.as<float>();
     b.nq = 1;
     b.q_stride = q_stride;
-    b.nrows = n;
+    b.nrows = fd.ids ? allowed : n;
     b.row_mult = 1;
     b.filter = 1;
     b.thr = dthr.as<uint64_t>();
     b.cand_cnt = dcnt.as<uint32_t>();
     b.cand = dcand.as<uint64_t>();
-    b.cap = n;
+    b.cap = allowed;
+    b.ids = fd.ids;
+    b.allow = fd.allow;
+    b.allow_bits = fd.allow_bits;
     SCANN_TRY(launch_pass(ix, b, st));
     uint32_t cnt = 0;
     SCANN_HIP_CHECK(hipMemcpyAsync(&cnt, dcnt.p, 4, hipMemcpyDeviceToHost, st));

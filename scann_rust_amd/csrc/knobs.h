@@ -32,6 +32,10 @@
 //                                   share (2.5; 0 = worst case)
 // SCANN_HIP_BF_SHORTLIST_TAIL       miss probability of the bf16 shortlist's bound, (0, 1) (1e-6)  every call
 // SCANN_HIP_BF_SHORTLIST_MIN_QUERIES  batch size from which the bf16 shortlist is used (32)        every call
+// SCANN_HIP_BF_FILTER              filtered brute force: 1 compacted id list, 2 bit test at the     every call
+//                                   emit (default: by the allowed fraction, next knob)
+// SCANN_HIP_BF_FILTER_COMPACT_MAX   largest allowed fraction that takes the compacted list, [0, 1]  every call
+//                                   (default 1: always)
 //
 // "every call": one read_knobs() snapshot at the entry point, passed down.
 #pragma once
@@ -71,6 +75,8 @@ struct Knobs {
     double comm_fill = 2.5;
     double bf_shortlist_tail = 1e-6;
     uint32_t bf_shortlist_min_queries = 32;
+    int bf_filter = 0;                    // 0 = by bf_filter_compact_max
+    double bf_filter_compact_max = 1.0;   // (every fraction: the crossover is not measured yet)
 };
 
 // The first occurrence of a name wins, as with getenv.
@@ -119,6 +125,11 @@ inline Knobs read_knobs() {
             const double t = atof(v);
             if (t > 0.0 && t < 1.0) k.bf_shortlist_tail = t;
         } else if (is("SCANN_HIP_BF_SHORTLIST_MIN_QUERIES")) k.bf_shortlist_min_queries = (uint32_t)strtoul(v, nullptr, 10);
+        else if (is("SCANN_HIP_BF_FILTER")) k.bf_filter = atoi(v);
+        else if (is("SCANN_HIP_BF_FILTER_COMPACT_MAX")) {
+            const double f = atof(v);
+            if (f >= 0.0 && f <= 1.0) k.bf_filter_compact_max = f;
+        }
     }
     return k;
 }

@@ -4181,7 +4181,7 @@ __global__ __launch_bounds__(256) void small_scan_kernel(TxhIndexDev ix, SmallAr
             const float *row = ix.rows + (size_t)(ix.rows_csr ? csr : ix.leaf_ids[csr]) * ix.stride;
             const float dist = exact_pair_thread(ix.measure, dim, s_qe, row);
             const uint32_t vpos = vbe + j;
-            if (vpos < a.cap) oute[vpos] = make_key(dist, vpos);
+            if (vpos < a.cap) oute[vpos] = row_allowed(ix, a.allow, a.allow_bits, csr) ? make_key(dist, vpos) : SCANN_KEY_MAX;
         }
         return;
     }
@@ -5122,8 +5122,9 @@ __global__ __launch_bounds__(kSelectThreads) void small_fused_kernel(TxhIndexDev
         __syncthreads();
         if (have) {
             const float *row = ix.rows + (size_t)(ix.rows_csr ? csr : ix.leaf_ids[csr]) * ix.stride;
-            __hip_atomic_store(&out[v], make_key(exact_pair_thread(ix.measure, dim, s_qe, row), v), __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_AGENT);
+            const uint64_t key =
+                row_allowed(ix, a.allow, a.allow_bits, csr) ? make_key(exact_pair_thread(ix.measure, dim, s_qe, row), v) : SCANN_KEY_MAX;
+            __hip_atomic_store(&out[v], key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     } else if (cnt) {
         const uint32_t S = ix.S, K = ix.K, dsub = ix.dsub, kp = ix.kp;

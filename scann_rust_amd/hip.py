@@ -33,7 +33,7 @@ EXPORTS = [
     "scann_hip_assign_leaves", "scann_hip_txh_partition", "scann_hip_lut_from_query",
     "scann_hip_adc_distances", "scann_hip_lut16_distances_batch", "scann_hip_encode",
     "scann_hip_fp8_quantize", "scann_hip_fp8_dequantize", "scann_hip_fp8_distances",
-    "scann_hip_bf_distances", "scann_hip_bf_search_radius", "scann_hip_bf_assign_nearest",
+    "scann_hip_bf_distances", "scann_hip_bf_search_radius", "scann_hip_bf_search_radius_opts", "scann_hip_allow_bitmap_count", "scann_hip_bf_assign_nearest",
     "scann_hip_kmeans_init_pp", "scann_hip_kmeans_lloyd", "scann_hip_txh_pack_blocks_device", "scann_hip_index_size", "scann_hip_index_dimensionality",
     "scann_hip_index_destroy", "scann_hip_index_enable_timing",
     "scann_hip_index_last_kernel_ms",
@@ -177,6 +177,10 @@ def load():
     L.scann_hip_comm_layout.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, u64p]
     L.scann_hip_bf_search_radius.argtypes = [vp, f32p, C.c_uint32, C.c_float, u32p, f32p, C.c_uint64,
                                              C.POINTER(C.c_uint64)]
+    L.scann_hip_bf_search_radius_opts.argtypes = [vp, f32p, C.c_uint32, C.c_float, C.POINTER(SearchOpts), u32p, f32p,
+                                                  C.c_uint64, C.POINTER(C.c_uint64)]
+    L.scann_hip_allow_bitmap_count.restype = C.c_uint64
+    L.scann_hip_allow_bitmap_count.argtypes = [u64p, C.c_uint64, C.c_uint64]
     L.scann_hip_index_size.restype = C.c_uint64
     L.scann_hip_index_size.argtypes = [vp]
     L.scann_hip_index_dimensionality.restype = C.c_uint32
@@ -313,6 +317,10 @@ class Index:
                 opts.allow_bitmap, opts.allow_bitmap_bits = None, 0
         return out_idx, out_dist, out_cnt
 
+    def search_radius(self, query, radius, capacity=None, allow=None, allow_bits=None):
+        """Brute-force handles: bf_search_radius, with an optional allow-bitmap."""
+        return bf_search_radius(self, query, radius, capacity, allow=allow, allow_bits=allow_bits)
+
     def enable_timing(self, on=True):
         load().scann_hip_index_enable_timing(self.h, 1 if on else 0)
 
@@ -329,6 +337,13 @@ def _allow_capacity(allow, allow_bits):
     if not 0 <= int(allow_bits) <= allow.size * 64:
         raise ValueError("allow_bits %d exceeds the bitmap's %d words" % (allow_bits, allow.size))
     return int(allow_bits)
+
+
+def allow_bitmap_count(allow, allow_bits, n):
+    """rows of an n-row index the bitmap allows (set bits below min(allow_bits, n)): the host-side count a filtered
+    brute-force search is planned with"""
+    allow = np.ascontiguousarray(allow, np.uint64)
+    return int(load().scann_hip_allow_bitmap_count(ptr(allow, u64p), _allow_capacity(allow, allow_bits), int(n)))
 
 
 def allow_bitmap(n, allowed):
@@ -614,16 +629,24 @@ def bf_distances(index, queries):
     return out
 
 
-def bf_search_radius(index, query, radius, capacity=None):
-    """BruteForceSearcher::search_radius: (idx, dist) of every row with distance <= radius."""
+def bf_search_radius(index, query, radius, capacity=None, allow=None, allow_bits=None):
+    """BruteForceSearcher::search_radius: (idx, dist) of every row with distance <= radius.  `allow`, `allow_bits`:
+    an allow-bitmap and its capacity as in Index.search_batched -- only allowed rows are returned."""
     q = f32(query).reshape(-1)
     cap = index.size() if capacity is None else int(capacity)
     idx = np.zeros(max(cap, 1), np.uint32)
     dist = np.zeros(max(cap, 1), np.float32)
     cnt = C.c_uint64(0)
-    check(load().scann_hip_bf_search_radius(index.h, ptr(q, f32p), q.size, C.c_float(radius),
-                                            ptr(idx, u32p), ptr(dist, f32p), C.c_uint64(cap),
-                                            C.byref(cnt)))
+    if allow is not None:
+        allow = np.ascontiguousarray(allow, np.uint64)
+        o = default_opts()
+        o.allow_bitmap, o.allow_bitmap_bits = ptr(allow, u64p), _allow_capacity(allow, allow_bits)
+        check(load().scann_hip_bf_search_radius_opts(index.h, ptr(q, f32p), q.size, C.c_float(radius), C.byref(o),
+                                                     ptr(idx, u32p), ptr(dist, f32p), C.c_uint64(cap), C.byref(cnt)))
+    else:
+        check(load().scann_hip_bf_search_radius(index.h, ptr(q, f32p), q.size, C.c_float(radius),
+                                                ptr(idx, u32p), ptr(dist, f32p), C.c_uint64(cap),
+                                                C.byref(cnt)))
     n = min(int(cnt.value), cap)
     return idx[:n], dist[:n], int(cnt.value)
 

@@ -337,14 +337,40 @@ public:
         auto flat = detail::flatten(queries, &d);
         return detail::run_search(ix_.h, flat.data(), (uint32_t)queries.size(), d, d, (uint32_t)k, nullptr);
     }
+    // The reference's BruteForceSearcher takes no filter; the contract (include/scann_hip.h, allow_bitmap) is the
+    // search over the allowed rows alone, as TreeXHybridSearcher::search_with_filter skips disallowed points before
+    // scoring (tree_x_hybrid/mod.rs:327-332).  The filter is materialised once into an allow-bitmap.
+    NNResultsVector search_with_filter(const std::vector<float> &query, size_t k, const RestrictFilter *filter) const {
+        if (!filter) return search(query, k);
+        const auto bits = filter->to_bitmap(dataset_->size());
+        scann_hip_search_opts o;
+        scann_hip_search_opts_default(&o);
+        o.allow_bitmap = bits.data();
+        o.allow_bitmap_bits = bits.size() * 64;
+        return detail::run_search(ix_.h, query.data(), 1, (uint32_t)query.size(), (uint32_t)query.size(),
+                                  (uint32_t)k, &o)[0];
+    }
     NNResultsVector search_radius(const std::vector<float> &query, float radius) const {   // :142-167
+        return search_radius_with_filter(query, radius, nullptr);
+    }
+    // every ALLOWED datapoint with distance <= radius
+    NNResultsVector search_radius_with_filter(const std::vector<float> &query, float radius,
+                                              const RestrictFilter *filter) const {
         if (dataset_->size() == 0) return {};
+        std::vector<uint64_t> bits;
+        scann_hip_search_opts o;
+        scann_hip_search_opts_default(&o);
+        if (filter) {
+            bits = filter->to_bitmap(dataset_->size());
+            o.allow_bitmap = bits.data();
+            o.allow_bitmap_bits = bits.size() * 64;
+        }
         std::vector<uint32_t> idx(256);
         std::vector<float> dist(256);
         uint64_t found = 0;
         for (;;) {
-            check(scann_hip_bf_search_radius(ix_.h, query.data(), (uint32_t)query.size(), radius, idx.data(),
-                                             dist.data(), idx.size(), &found));
+            check(scann_hip_bf_search_radius_opts(ix_.h, query.data(), (uint32_t)query.size(), radius,
+                                                  filter ? &o : nullptr, idx.data(), dist.data(), idx.size(), &found));
             if (found <= idx.size()) break;
             idx.resize(found);
             dist.resize(found);
