@@ -545,6 +545,16 @@ int scann_hip_bf_distances(scann_hip_index *index, const float *queries, uint32_
  *   used instead -- and its D^2 sampling sums min_d sequentially in f32 (:318-331), an n-long
  *   dependent chain per seed; here the total and the cumulative search run in f64 with a fixed
  *   reduction tree.  The minimum distances themselves follow the reference's arithmetic.
+ *   The rule, as tests/build_model.py restates it: splitmix64(seed) output 0 mod n is the first seed; every
+ *   later seed consumes two outputs in order, u = (z >> 11) 2^-53 and fallback = z mod n; min_d[i] is the
+ *   smallest squared distance of row i to a chosen seed (strict '<': a NaN minimum stays); the seed is the
+ *   first row whose cumulative min_d reaches u * total.  total == 0 (every row already coincides with a
+ *   seed, e.g. k > number of distinct rows): rows[fallback].  total == +inf: the first row whose min_d is
+ *   +inf (the rule read in the extended reals).  total NaN (a row with a NaN element makes its min_d NaN):
+ *   rows[fallback] as well -- a second DEVIATION: no comparison of the reference's loop holds against a NaN
+ *   threshold, so it would select row 0 every time.
+ *   Because the sums are rounded f64 sums in tree order, a seed may differ from the exactly evaluated rule
+ *   only where the cumulative sum lies within (n + 1) 2^-52, relatively, of u * total.
  * scann_hip_kmeans_lloyd: the Lloyd loop of KMeans::fit_single (:210-263) from the caller's initial
  *   centres (updated in place): assign_clusters (strict '<', lowest index on ties), inertia = the f64
  *   sum of the minimum distances in datapoint order (:376; computed by a reduction tree when every
@@ -552,7 +562,12 @@ int scann_hip_bf_distances(scann_hip_index *index, const float *queries, uint32_
  *   otherwise), stop when |prev - inertia| / (prev + 1e-10) < convergence_threshold, update_centers
  *   (f64 sums in ascending datapoint order, mean cast to f32, empty cluster c takes row c % n), then
  *   the final assignment.  Bit-identical to the reference's loop from the same initial centres.
- *   Outputs may be NULL. */
+ *   Outputs may be NULL.  A row whose every distance is NaN (a NaN element in the row, or in every centre)
+ *   joins cluster 0 and adds +inf to the inertia, as assign_clusters' min_dist does.
+ * LIMIT: the assignment stages whole centres in LDS (160 KB per workgroup): 16 centres in the sequential
+ *   order, 8 in the AVX2 order, each padded to a multiple of 4 values.  sub_dim > 2560 (sequential order)
+ *   or > 5120 (AVX2 order) makes scann_hip_kmeans_lloyd return ResourceExhausted (the seeding stages no
+ *   centres and has no such limit). */
 int scann_hip_kmeans_init_pp(scann_hip_index *bf_index, uint32_t col_offset, uint32_t sub_dim, uint32_t k,
                              uint64_t seed, uint32_t simd_threshold, float *centers_out);
 int scann_hip_kmeans_lloyd(scann_hip_index *bf_index, uint32_t col_offset, uint32_t sub_dim, float *centers,
@@ -582,7 +597,13 @@ int scann_hip_bf_search_radius(scann_hip_index *index, const float *query, uint3
  * `num_centers` centres [num_centers][dim] under the partitioner's arithmetic --
  * TreePartitioner::partition(x, 1) as used by TreeXHybridSearcher::compute_residuals
  * (tree_x_hybrid/mod.rs:212-237) and KMeans::assign_clusters (trees/kmeans.rs:352-379):
- * sequential scalar SquaredL2, lowest centre index on ties.  out_dist may be NULL. */
+ * sequential scalar SquaredL2, lowest centre index on ties.  out_dist may be NULL.
+ * NaN distances order last (the partitioner's ordered sort; assign_clusters' strict '<' never selects one).
+ * A row whose EVERY distance is NaN gets centre 0 and out_dist = +inf: the two references agree on the centre
+ * and disagree on the value (partition(x, 1) reports the NaN, assign_clusters keeps its initial +inf); the
+ * library's value is assign_clusters'.
+ * LIMIT: 16 centres are staged in LDS, each padded to a multiple of 4 values: 64 * ceil(dim / 4) * 4 bytes of
+ * the workgroup's 160 KB.  dim > 2560 returns ResourceExhausted. */
 int scann_hip_bf_assign_nearest(scann_hip_index *index, const float *centers, uint32_t num_centers,
                                 uint32_t *out_assign, float *out_dist);
 

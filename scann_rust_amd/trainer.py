@@ -76,7 +76,10 @@ def train_codebook(R, S, K, iters=10, seed=42, sample=65536):
 def encode(codebook, R, chunk=65536):
     """Codebook::encode (hashes/codebook.rs:82-95, 205-215), vectorised but
     bit-identical: per subspace d = x - c; p = d*d; sum left-to-right in f32;
-    argmin takes the first (lowest) index among equal minima."""
+    argmin takes the first (lowest) index among equal minima.  The reference's strict
+    '<' against a running minimum of +inf never selects a NaN distance (and keeps code 0
+    when every distance is NaN or +inf); numpy's argmin returns the first NaN, so NaN
+    sums are mapped to +inf first."""
     codebook = np.ascontiguousarray(codebook, np.float32)
     R = np.ascontiguousarray(R, np.float32)
     S, K, dsub = codebook.shape
@@ -84,11 +87,13 @@ def encode(codebook, R, chunk=65536):
     codes = np.empty((n, S), np.uint8)
     for r0 in range(0, n, chunk):
         x = R[r0:r0 + chunk].reshape(-1, S, 1, dsub)
-        diff = x - codebook[None]                      # [c, S, K, dsub] f32
-        p = diff * diff
-        acc = p[..., 0].copy()
-        for j in range(1, dsub):
-            acc = acc + p[..., j]
+        with np.errstate(over="ignore", invalid="ignore"):
+            diff = x - codebook[None]                  # [c, S, K, dsub] f32
+            p = diff * diff
+            acc = p[..., 0].copy()
+            for j in range(1, dsub):
+                acc = acc + p[..., j]
+        acc[np.isnan(acc)] = np.inf
         codes[r0:r0 + chunk] = acc.argmin(2).astype(np.uint8)
     return codes
 

@@ -774,3 +774,99 @@ def device_search(index, q, k, o, allow=None, allow_bits=None):
         if da is not None:
             o.allow_bitmap, o.allow_bitmap_bits = None, 0
     return status, oi.cpu().numpy().view(np.uint32), od.cpu().numpy(), oc.cpu().numpy().view(np.uint32)
+
+
+# ---- rows and centres for the index-build kernels (tests/test_gpu_build.py, tests/build_model.py) -------------------
+# The brute-force families above, plus the three the build side needs: NaN rows, an all-equal set, and centre sets
+# drawn from the rows themselves.
+BUILD_FAMILIES = ("signed", "scaled-70", "scaled+56", "spread", "integers", "duplicates", "zero", "overflow", "nan",
+                  "all-equal")
+
+
+def nan_element_rows(n):
+    """rows of the nan family with ONE NaN element"""
+    return np.unique(np.array([2, n // 5, n // 2 + 3]) % max(n, 1))
+
+
+def nan_whole_row(n):
+    """the row of the nan family whose every element is NaN"""
+    return (2 * n) // 3
+
+
+def build_rows(family, n, dim, seed):
+    """[n, dim] f32 rows of one BUILD_FAMILIES member.
+    nan        signed, with a NaN in one element of three rows (the column moves with the row) and one whole-NaN row
+               (when n >= 8; smaller sets keep one NaN element in row n - 1)
+    all-equal  one signed row, n times
+    others     adversarial_rows"""
+    if family == "nan":
+        x = _signed(np.random.default_rng([seed, 13]), (n, dim))
+        if n < 8:
+            x[n - 1, (dim - 1) // 2] = np.nan
+            return x
+        for r in nan_element_rows(n):
+            x[r, int(r) % dim] = np.nan
+        x[nan_whole_row(n)] = np.nan
+        return x
+    if family == "all-equal":
+        return np.repeat(_signed(np.random.default_rng([seed, 14]), (1, dim)), n, axis=0)
+    return adversarial_rows(family, n, dim, seed)
+
+
+def centers_from_rows(rows, k, seed):
+    """[k, dim] f32 centres drawn from the rows (so that rows hit a centre exactly: distance 0), every third one a copy
+    of an earlier centre (ties between duplicated centres must go to the lowest index)"""
+    rng = np.random.default_rng([seed, 15])
+    c = np.ascontiguousarray(rows[rng.integers(0, rows.shape[0], k)], np.float32)
+    for j in range(2, k, 3):
+        c[j] = c[rng.integers(0, j)]
+    return c
+
+
+ENCODE_FAMILIES = ("dup", "equal", "nan-sub", "nan-code", "overflow", "tiny", "integers")
+
+
+def encode_inputs(family, S, K, dsub, n, seed):
+    """(codebook [S, K, dsub] f32, rows [n, S dsub] f32) on which an argmin and Codebook::encode's strict '<' against
+    a running minimum of +inf can part ways.
+    dup       two codewords of every subspace copy two others, every third row is made of such codewords (distance 0
+              to both copies): the lowest index
+    equal     every codeword of a subspace is the same: code 0
+    nan-sub   40 rows with one NaN element, one whole-NaN row: every distance of that subspace is NaN -> code 0
+    nan-code  NaN codewords are never chosen: codeword 0 of every subspace, all but the last codeword of subspace
+              S - 2 (the last one wins), every codeword of subspace S - 1 (code 0)
+    overflow  every 4th row x 1e20: distances overflow to +inf, which is not < +inf -> code 0; an infinite codeword
+              (inf - inf = NaN against nothing, +inf against everything)
+    tiny      everything x 2^-70: every squared difference is subnormal
+    integers  codewords and rows in {-2, ..., 2}: exact arithmetic, massive exact ties"""
+    rng = np.random.default_rng([seed, ENCODE_FAMILIES.index(family), S, K, dsub])
+    cb = rng.uniform(-1, 1, (S, K, dsub)).astype(np.float32)
+    x = rng.uniform(-1, 1, (n, S * dsub)).astype(np.float32)
+    if family == "dup":
+        pairs = [(K - 1 - i, i) for i in range(min(2, K // 2))]          # (copy, original), copy > original
+        for hi, lo in pairs:
+            cb[:, hi] = cb[:, lo]
+        if pairs:
+            pick = np.array([p[j] for p in pairs for j in (0, 1)])
+            x[::3] = cb[np.arange(S), rng.choice(pick, (x[::3].shape[0], S))].reshape(-1, S * dsub)
+    elif family == "equal":
+        cb[:] = cb[:, :1]
+    elif family == "nan-sub":
+        x[rng.integers(0, n, min(n, 40)), rng.integers(0, S * dsub, min(n, 40))] = np.nan
+        x[min(7, n - 1)] = np.nan
+    elif family == "nan-code":
+        cb[:, 0, dsub // 2] = np.nan
+        cb[S - 2, :K - 1] = np.nan
+        cb[S - 1] = np.nan
+    elif family == "overflow":
+        x[::4] *= np.float32(1e20)
+        cb[min(1, S - 1), K // 2] = np.float32(3e38)
+        cb[S - 1, 0] = np.inf
+    elif family == "tiny":
+        cb, x = cb * np.float32(2.0 ** -70), x * np.float32(2.0 ** -70)
+    elif family == "integers":
+        cb = rng.integers(-2, 3, (S, K, dsub)).astype(np.float32)
+        x = rng.integers(-2, 3, (n, S * dsub)).astype(np.float32)
+    else:
+        raise ValueError(family)
+    return np.ascontiguousarray(cb, np.float32), np.ascontiguousarray(x, np.float32)
