@@ -335,6 +335,73 @@ int scann_hip_search_batched_device(scann_hip_index *index, const float *d_queri
  * (pass the opts with the bitmap to scann_hip_index_reserve so that host calls do not either). */
 int scann_hip_index_last_device_status(scann_hip_index *index, void *hip_stream);
 
+/* ---- crowding: at most per_crowd_limit results per attribute (restricts/crowding.rs) --------
+ * CrowdingConstraint::apply (crowding.rs:81-104) behind every search, on the device.  For every handle kind
+ * that scann_hip_search_batched serves (f32 and quantized brute force, flat hasher, Tree-X-Hybrid, Partitioned):
+ *
+ *   crowded(query, k, depth, limit)  ==  CrowdingConstraint::apply(search(query, depth), k)
+ *
+ * where search(query, depth) is exactly what scann_hip_search_batched returns for k = depth under the same opts
+ * (allow_bitmap, pre_reorder_k, partitions_to_search, exact_reorder and bf_exact apply to it unchanged).  The rule:
+ * walk that row in order and keep entry i iff fewer than per_crowd_limit EARLIER entries of the row carry the same
+ * attribute; stop at k kept entries.  (The reference counts earlier KEPT entries; with one attribute per datapoint
+ * the two counts decide alike.)  The rule is greedy and online, hence the prefix property: if the crowded result
+ * over the first `depth` neighbours holds k entries, it is the crowded result over every deeper list that extends
+ * them -- for a brute-force handle, over the whole database.
+ *   - attributes: one u64 per DATAPOINT index, held on the device with the handle
+ *     (scann_hip_index_set_crowding_attributes).  The array may be shorter than the index: an index at or past
+ *     n_attrs has attribute 0 (get_attribute(idx).unwrap_or(0), crowding.rs:90) and crowds together with the rows
+ *     whose attribute really is 0.
+ *   - per_crowd_limit = 0 keeps nothing (empty rows, count 0); per_crowd_limit >= depth returns the first k of the row.
+ *   - a row shorter than depth (fewer rows, fewer allowed rows, fewer candidates) is walked to its count; its
+ *     sentinel slots are never looked up.
+ *   - out_count[i] = number kept; slots past it hold 0xFFFFFFFF / +inf; distances are the bits the plain search
+ *     returns.
+ *   - depth = 0 means depth = k.
+ * Errors: depth < k -> InvalidArgument; no attributes attached -> FailedPrecondition; a depth the handle does not
+ * accept as k -> the error the plain search gives for that k (brute force: k > 2048 -> Unimplemented; on the device
+ * path k > n -> InvalidArgument; hashed handles: a candidate count above 8192 -> Unimplemented); depth > 8192 ->
+ * Unimplemented in any case.
+ * Not built: CrowdingMultidimensional (crowding.rs:123-214; its accept decision depends on earlier ACCEPT decisions),
+ * MmrDiversifier, a per-query k (the _params entry point), the leaf-sharded multi-GPU entry point.
+ *
+ * The stage is one kernel launch behind the handle's final select: one wave per query walks the [nq][depth] rows in
+ * chunks of 64 with an open-addressed LDS table keyed on the full 64-bit attribute (a hash collision costs probes,
+ * never a wrong count) and leaves the loop once k entries are kept.  scann_hip_crowd_table_slots(depth) is the
+ * table's slot count, clamp(next_pow2(2 * depth), 128, SCANN_HIP_CROWD_MAX_SLOTS), 12 bytes each (at most 144 KB of
+ * the workgroup's 160 KB); the home slot of a key is mulhi32(splitmix64-finaliser(key) >> 32, slots). */
+#define SCANN_HIP_CROWD_MAX_DEPTH 8192
+#define SCANN_HIP_CROWD_MAX_SLOTS 12288
+uint32_t scann_hip_crowd_table_slots(uint32_t depth);
+/* Copies attrs[0..n_attrs) to the device.  Calling again replaces the array; n_attrs = 0 detaches it (crowded
+ * searches then fail FailedPrecondition).  Waits for the device; needs the same external synchronisation as
+ * create / destroy (no search may run on the handle meanwhile). */
+int scann_hip_index_set_crowding_attributes(scann_hip_index *index, const uint64_t *attrs, uint64_t n_attrs);
+/* Host entry point (synchronous, host pointers; opts->allow_bitmap is a host pointer).  Queries (and the bitmap) go
+ * up, the [nq][depth] rows stay in the slot's workspace between the search's final select and the crowding kernel,
+ * and only the [nq][k] answer comes back.  The search is the enqueue-only batched pipeline of the *_device entry
+ * point (not the polled pinned-staging pipeline of batches of <= 16 queries).  Where that search cannot serve the
+ * call as scann_hip_search_batched would -- its status word reports a sampled bound that missed or a candidate buffer
+ * that overflowed, a bf16-shortlist result could not be verified, a brute-force depth exceeds the index, opts asks
+ * for per-stage outputs -- the call is answered through scann_hip_search_batched itself at k = depth (with its
+ * repeats), whose rows are then sent back to the device for the crowding kernel.  Both routes give the same bits. */
+int scann_hip_search_crowded(scann_hip_index *index, const float *queries, uint32_t nq, uint32_t q_stride,
+                             uint32_t q_dim, uint32_t k, uint32_t depth, uint32_t per_crowd_limit,
+                             const scann_hip_search_opts *opts, uint32_t *out_idx, float *out_dist,
+                             uint32_t *out_count);
+/* Device entry point: device pointers, enqueued on hip_stream, never synchronises, no host round trip: the search's
+ * final select writes its [nq][depth] rows into the stream's workspace and the crowding kernel reads them there.
+ * Same stream / workspace rules and status reporting (scann_hip_index_last_device_status) as
+ * scann_hip_search_batched_device; a query the search could not finish has out_count 0.
+ * scann_hip_index_reserve_crowded = scann_hip_index_reserve for k = max_depth plus the rows of the crowding stage
+ * (max_depth = 0 means max_k); a call within the reserved sizes on the primary workspace does not allocate. */
+int scann_hip_index_reserve_crowded(scann_hip_index *index, uint32_t max_nq, uint32_t max_k, uint32_t max_depth,
+                                    const scann_hip_search_opts *opts);
+int scann_hip_search_crowded_device(scann_hip_index *index, const float *d_queries, uint32_t nq, uint32_t q_stride,
+                                    uint32_t k, uint32_t depth, uint32_t per_crowd_limit,
+                                    const scann_hip_search_opts *opts, uint32_t *d_out_idx, float *d_out_dist,
+                                    uint32_t *d_out_count, void *hip_stream);
+
 /* ---- multi-GPU: leaf-sharded Tree-X-Hybrid ------------------- */
 /* Local stage: this rank's best-m candidates per query by approximate distance, with
  * their exact distances, as (merge key u64, datapoint idx u32, exact f32) triples

@@ -17,6 +17,7 @@
 #include "bf.h"
 #include "comm.h"
 #include "common.h"
+#include "crowd.h"
 #include "knobs.h"
 #include "txh.h"
 
@@ -158,11 +159,28 @@ struct PinBuf {
 
 // An extra stream + workspaces: host-side searches of concurrent caller threads (Searcher: Send +
 // Sync, tests/stress_tests.rs:256-297) run side by side instead of queueing on one mutex.
+// Buffers of the crowding stage of one stream: the [nq][depth] rows the search leaves for it (device entry point:
+// written by the search's final select, never seen by the host) and, host entry point only, its [nq][k] result.
+struct CrowdWorkspace {
+    DevBuf idx, dist, cnt, out_idx, out_dist, out_cnt, queries, allow;
+    int ensure_rows(uint32_t nq, uint32_t depth) {
+        SCANN_TRY(idx.ensure((size_t)nq * depth * 4));
+        SCANN_TRY(dist.ensure((size_t)nq * depth * 4));
+        return cnt.ensure((size_t)nq * 4);
+    }
+    int ensure_out(uint32_t nq, uint32_t k) {
+        SCANN_TRY(out_idx.ensure((size_t)nq * k * 4));
+        SCANN_TRY(out_dist.ensure((size_t)nq * k * 4));
+        return out_cnt.ensure((size_t)nq * 4);
+    }
+};
+
 struct SearchSlot {
     std::mutex mu;
     hipStream_t stream = nullptr;
     TxhWorkspace ws;
     BfWorkspace bfw;
+    CrowdWorkspace crowd;
     PinBuf pin;
 };
 
@@ -192,6 +210,12 @@ struct scann_hip_index {
     const char *timed_kernel = "";
     DevBuf status_word;
 
+    // ---- crowding (scann_hip_index_set_crowding_attributes): one u64 per datapoint index, may be shorter ----
+    DevBuf crowd_attrs;
+    uint64_t n_crowd_attrs = 0;
+    bool has_crowd_attrs = false;
+    CrowdWorkspace crowd;     // primary slot's
+
     // ---- brute force ----
     BfIndexDev bf{};
     DevBuf bf_rows, bf_rows_b, bf_rows_bl, bf_norm2, bf_leaf;
@@ -217,8 +241,10 @@ struct scann_hip_index {
         uint64_t tick = 0;
         TxhWorkspace *ws = nullptr;
         BfWorkspace *bfw = nullptr;
+        CrowdWorkspace *crowd = nullptr;
         std::unique_ptr<TxhWorkspace> ws_own;
         std::unique_ptr<BfWorkspace> bfw_own;
+        std::unique_ptr<CrowdWorkspace> crowd_own;
     };
     static constexpr int kMaxDeviceSlots = 4;
     DeviceSlot dslots[kMaxDeviceSlots];
@@ -1135,6 +1161,7 @@ static int device_slot(scann_hip_index *ix, hipStream_t st, scann_hip_index::Dev
     if (!ds[0].ws) {
         ds[0].ws = &ix->ws;
         ds[0].bfw = &ix->bfw;
+        ds[0].crowd = &ix->crowd;
     }
     const int n = device_slot_count();
     scann_hip_index::DeviceSlot *pick = nullptr;
@@ -1152,6 +1179,8 @@ static int device_slot(scann_hip_index *ix, hipStream_t st, scann_hip_index::Dev
         pick->bfw_own.reset(new BfWorkspace());
         pick->ws = pick->ws_own.get();
         pick->bfw = pick->bfw_own.get();
+        pick->crowd_own.reset(new CrowdWorkspace());
+        pick->crowd = pick->crowd_own.get();
     }
     if (!pick->done) SCANN_HIP_CHECK(hipEventCreateWithFlags(&pick->done, hipEventDisableTiming));
     if (pick->used && pick->key != st && pick->done_valid) SCANN_HIP_CHECK(hipStreamWaitEvent(st, pick->done, 0));
@@ -1189,6 +1218,7 @@ struct SlotLock {
     hipStream_t stream = nullptr;
     TxhWorkspace *ws = nullptr;
     BfWorkspace *bfw = nullptr;
+    CrowdWorkspace *crowd = nullptr;
     PinBuf *pin = nullptr;
     bool primary = false;
 };
@@ -1225,6 +1255,7 @@ static int acquire_slot(scann_hip_index *ix, SlotLock *out) {
             out->stream = slot->stream;
             out->ws = &slot->ws;
             out->bfw = &slot->bfw;
+            out->crowd = &slot->crowd;
             out->pin = &slot->pin;
             out->primary = false;
             return SCANN_HIP_OK;
@@ -1236,6 +1267,7 @@ static int acquire_slot(scann_hip_index *ix, SlotLock *out) {
     out->stream = ix->stream;
     out->ws = &ix->ws;
     out->bfw = &ix->bfw;
+    out->crowd = &ix->crowd;
     out->pin = &ix->pin;
     out->primary = true;
     return SCANN_HIP_OK;
@@ -1551,6 +1583,15 @@ int scann_hip_search_batched_params(scann_hip_index *ix, const float *queries, u
     return SCANN_HIP_OK;
 }
 
+}  // extern "C"
+
+static int search_device_ws(scann_hip_index *ix, scann_hip_index::DeviceSlot *dsl, TxhWorkspace &ws, BfWorkspace &bfw,
+                            TxhPipeline widest, const float *d_queries, uint32_t nq, uint32_t q_stride, uint32_t k,
+                            const scann_hip_search_opts *opts, uint32_t *d_out_idx, float *d_out_dist,
+                            uint32_t *d_out_count, hipStream_t st);
+
+extern "C" {
+
 int scann_hip_index_reserve(scann_hip_index *ix, uint32_t max_nq, uint32_t max_k,
                             const scann_hip_search_opts *opts) {
     if (!ix) return fail(SCANN_HIP_INVALID_ARGUMENT, "index is null");
@@ -1575,23 +1616,38 @@ int scann_hip_search_batched_device(scann_hip_index *ix, const float *d_queries,
     SCANN_TRY(set_device(ix->ctx));
     scann_hip_index::DeviceSlot *dsl = nullptr;
     SCANN_TRY(device_slot(ix, st, &dsl));
+    return search_device_ws(ix, dsl, *dsl->ws, *dsl->bfw, TxhPipeline::Wide, d_queries, nq, q_stride, k, opts, d_out_idx,
+                            d_out_dist, d_out_count, st);
+}
+
+}  // extern "C"
+
+// The enqueue-only search in workspace (ws, bfw) on stream st, device pointers throughout.
+// dsl != null: scann_hip_search_batched_device with ix->mu held and the stream's workspace chosen (kernel timing and
+// the slot's completion event follow the call).  dsl == null: a host entry point that owns (ws, bfw) through its
+// SlotLock and synchronises by itself; it touches none of the handle's primary-slot state.
+static int search_device_ws(scann_hip_index *ix, scann_hip_index::DeviceSlot *dsl, TxhWorkspace &ws, BfWorkspace &bfw,
+                            TxhPipeline widest, const float *d_queries, uint32_t nq, uint32_t q_stride, uint32_t k,
+                            const scann_hip_search_opts *opts, uint32_t *d_out_idx, float *d_out_dist,
+                            uint32_t *d_out_count, hipStream_t st) {
     const Knobs kn = read_knobs();
     if (ix->kind == KIND_BF) {
-        ix->next_events();
+        if (dsl) ix->next_events();
         const BfFilter flt = bf_filter_of(opts, kn);   // (a device pointer on this path)
         const bool shortlist = !flt.bitmap && !(opts && opts->bf_exact) && bf_shortlist_eligible(ix->bf, nq, k, kn);
-        int s = bf_search_device(ix->bf, *dsl->bfw, d_queries, nq, q_stride, k, shortlist, kn.bf_shortlist_tail, flt,
-                                 d_out_idx, d_out_dist, d_out_count, st, ix->ev0, ix->ev1);
+        int s = bf_search_device(ix->bf, bfw, d_queries, nq, q_stride, k, shortlist, kn.bf_shortlist_tail, flt,
+                                 d_out_idx, d_out_dist, d_out_count, st, dsl ? ix->ev0 : nullptr, dsl ? ix->ev1 : nullptr);
+        if (!dsl) return s;
         if (s == SCANN_HIP_OK) s = device_slot_done(dsl, st);
         ix->timing_valid = ix->timing && s == SCANN_HIP_OK;
         ix->timed_kernel = shortlist ? "bf_bf16_kernel" : bf_pass_kernel_name(ix->bf, nq);
         return s;
     }
     TxhPlan p;
-    SCANN_TRY(plan_txh_search(ix, k, opts, nq, false, TxhPipeline::Wide, kn, &p));
+    SCANN_TRY(plan_txh_search(ix, k, opts, nq, false, widest, kn, &p));
     if (p.m == 0) return fail(SCANN_HIP_INVALID_ARGUMENT, "pre-reorder candidate count is 0");
     TxhWork w;
-    SCANN_TRY(ensure_txh_workspace(ix, *dsl->ws, p, false, q_stride, false, &w));
+    SCANN_TRY(ensure_txh_workspace(ix, ws, p, false, q_stride, false, &w));
     w.queries = d_queries;
     w.out_idx = d_out_idx;
     w.out_dist = d_out_dist;
@@ -1600,6 +1656,7 @@ int scann_hip_search_batched_device(scann_hip_index *ix, const float *d_queries,
         w.allow = opts->allow_bitmap;
         w.allow_bits = opts->allow_bitmap_bits;
     }
+    if (!dsl) return txh_launch_search(ix->tx, w, false, st, nullptr, nullptr);
     ix->last_work = w;
     ix->next_events();
     SCANN_TRY(txh_launch_search(ix->tx, w, false, st, ix->ev0,
@@ -1609,6 +1666,8 @@ int scann_hip_search_batched_device(scann_hip_index *ix, const float *d_queries,
     ix->timed_kernel = txh_kernel_name(ix->tx, p, /*pinned=*/false);
     return SCANN_HIP_OK;
 }
+
+extern "C" {
 
 int scann_hip_index_last_device_status(scann_hip_index *ix, void *hip_stream) {
     if (!ix) return fail(SCANN_HIP_INVALID_ARGUMENT, "index is null");
@@ -1634,6 +1693,189 @@ int scann_hip_index_last_device_status(scann_hip_index *ix, void *hip_stream) {
                     "candidate threshold/buffer miss on the device path (use the host entry "
                     "point, which retries without a threshold and with a full-size buffer)");
     return SCANN_HIP_OK;
+}
+
+// ---- crowding (restricts/crowding.rs) --------------------------------------------------------------------------
+uint32_t scann_hip_crowd_table_slots(uint32_t depth) { return crowd_table_slots(depth); }
+
+int scann_hip_index_set_crowding_attributes(scann_hip_index *ix, const uint64_t *attrs, uint64_t n_attrs) {
+    if (!ix) return fail(SCANN_HIP_INVALID_ARGUMENT, "index is null");
+    if (n_attrs && !attrs) return fail(SCANN_HIP_INVALID_ARGUMENT, "attrs is null");
+    std::lock_guard<std::mutex> lock(ix->mu);
+    SCANN_TRY(set_device(ix->ctx));
+    SCANN_HIP_CHECK(hipDeviceSynchronize());   // searches enqueued on caller streams may still read the old array
+    ix->crowd_attrs.release();
+    ix->n_crowd_attrs = 0;
+    ix->has_crowd_attrs = false;
+    if (n_attrs == 0) return SCANN_HIP_OK;
+    SCANN_TRY(upload(ix->crowd_attrs, attrs, (size_t)n_attrs * 8));
+    ix->n_crowd_attrs = n_attrs;
+    ix->has_crowd_attrs = true;
+    return SCANN_HIP_OK;
+}
+
+// depth = 0 means k; depth < k -> InvalidArgument; no attributes -> FailedPrecondition
+static int crowd_args(const scann_hip_index *ix, uint32_t k, uint32_t *depth) {
+    if (*depth == 0) *depth = k;
+    if (*depth < k) return fail(SCANN_HIP_INVALID_ARGUMENT, "crowding depth " + std::to_string(*depth) +
+                                                                 " is smaller than k " + std::to_string(k));
+    if (!ix->has_crowd_attrs)
+        return fail(SCANN_HIP_FAILED_PRECONDITION, "no crowding attributes attached (scann_hip_index_set_crowding_attributes)");
+    return SCANN_HIP_OK;
+}
+
+}  // extern "C"
+
+// The host entry point's first route: queries (and the allow bitmap) up, the enqueue-only search at k = depth into the
+// slot's crowding rows, the crowding kernel, the [nq][k] answer down -- the [nq][depth] rows never leave the device.
+// Taken when the enqueue-only search can serve the call as the plain host entry point would: a brute-force depth
+// within the index (its rows have pitch k = depth), no per-stage outputs.
+static bool crowd_on_device(const scann_hip_index *ix, uint32_t q_stride, uint32_t q_dim, uint32_t depth,
+                            const scann_hip_search_opts *o) {
+    if (depth > kCrowdMaxDepth || q_stride < q_dim) return false;
+    if (o && (o->tokens || o->token_dists || o->cand_idx || o->cand_dist || o->cand_count)) return false;
+    if (ix->kind == KIND_BF) return ix->bf.n > 0 && q_dim == ix->bf.dim && depth <= ix->bf.n;
+    return q_dim == ix->tx.dim;
+}
+
+// OK: the caller's arrays hold the answer.  Any other status: nothing was written that the second route does not
+// overwrite (a status the device left -- a sampled bound that missed, a candidate buffer that overflowed -- included).
+static int crowded_host_on_device(scann_hip_index *ix, const float *queries, uint32_t nq, uint32_t q_stride, uint32_t k,
+                                  uint32_t depth, uint32_t limit, const scann_hip_search_opts *opts, uint32_t *out_idx,
+                                  float *out_dist, uint32_t *out_count) {
+    SlotLock sl;
+    SCANN_TRY(acquire_slot(ix, &sl));
+    SCANN_TRY(set_device(ix->ctx));
+    CrowdWorkspace &cw = *sl.crowd;
+    const hipStream_t st = sl.stream;
+    SCANN_TRY(cw.ensure_rows(nq, depth));
+    SCANN_TRY(cw.ensure_out(nq, k));
+    SCANN_TRY(cw.queries.ensure((size_t)nq * q_stride * 4));
+    scann_hip_search_opts o;
+    scann_hip_search_opts_default(&o);
+    if (opts) o = *opts;
+    if (o.allow_bitmap) {   // host pointer -> the slot's copy (capacity 0: a pointer no row reads)
+        const size_t words = (size_t)((o.allow_bitmap_bits + 63) / 64);
+        SCANN_TRY(cw.allow.ensure(std::max<size_t>(words, 1) * 8));
+        if (words) SCANN_HIP_CHECK(hipMemcpyAsync(cw.allow.p, o.allow_bitmap, words * 8, hipMemcpyHostToDevice, st));
+        o.allow_bitmap = cw.allow.as<uint64_t>();
+    }
+    SCANN_HIP_CHECK(hipMemcpyAsync(cw.queries.p, queries, (size_t)nq * q_stride * 4, hipMemcpyHostToDevice, st));
+    // (the batched pipeline only: the few-query pipelines report an overflow through their polled host words)
+    int s = search_device_ws(ix, nullptr, *sl.ws, *sl.bfw, TxhPipeline::Staged, cw.queries.as<float>(), nq, q_stride,
+                             depth, &o, cw.idx.as<uint32_t>(), cw.dist.as<float>(), cw.cnt.as<uint32_t>(), st);
+    if (s == SCANN_HIP_OK)
+        s = crowd_launch(cw.idx.as<uint32_t>(), cw.dist.as<float>(), cw.cnt.as<uint32_t>(), nq, depth,
+                         ix->crowd_attrs.as<uint64_t>(), ix->n_crowd_attrs, k, limit, cw.out_idx.as<uint32_t>(),
+                         cw.out_dist.as<float>(), cw.out_cnt.as<uint32_t>(), st);
+    if (s != SCANN_HIP_OK) {
+        (void)hipStreamSynchronize(st);   // (the uploads read the caller's memory)
+        return s;
+    }
+    const size_t ob = (size_t)nq * k * 4;
+    SCANN_HIP_CHECK(hipMemcpyAsync(out_idx, cw.out_idx.p, ob, hipMemcpyDeviceToHost, st));
+    SCANN_HIP_CHECK(hipMemcpyAsync(out_dist, cw.out_dist.p, ob, hipMemcpyDeviceToHost, st));
+    SCANN_HIP_CHECK(hipMemcpyAsync(out_count, cw.out_cnt.p, (size_t)nq * 4, hipMemcpyDeviceToHost, st));
+    if (ix->kind == KIND_BF) return bf_last_status(*sl.bfw, st);   // (synchronises)
+    uint32_t counters[CNT_N] = {};
+    if (sl.ws->counters.p)
+        SCANN_HIP_CHECK(hipMemcpyAsync(counters, sl.ws->counters.p, sizeof(counters), hipMemcpyDeviceToHost, st));
+    SCANN_HIP_CHECK(hipStreamSynchronize(st));
+    if (counters[CNT_STATUS] != SCANN_HIP_OK) return fail((int)counters[CNT_STATUS], "device reported a search failure");
+    return SCANN_HIP_OK;
+}
+
+extern "C" {
+
+int scann_hip_search_crowded(scann_hip_index *ix, const float *queries, uint32_t nq, uint32_t q_stride,
+                             uint32_t q_dim, uint32_t k, uint32_t depth, uint32_t per_crowd_limit,
+                             const scann_hip_search_opts *opts, uint32_t *out_idx, float *out_dist,
+                             uint32_t *out_count) {
+    if (!ix) return fail(SCANN_HIP_INVALID_ARGUMENT, "index is null");
+    SCANN_TRY(crowd_args(ix, k, &depth));
+    if (nq == 0) return SCANN_HIP_OK;
+    if (!queries || !out_count || (k > 0 && (!out_idx || !out_dist)))
+        return fail(SCANN_HIP_INVALID_ARGUMENT, "null query/output pointer");
+    if (k > 0 && crowd_on_device(ix, q_stride, q_dim, depth, opts)) {
+        int s = crowded_host_on_device(ix, queries, nq, q_stride, k, depth, per_crowd_limit, opts, out_idx, out_dist,
+                                       out_count);
+        if (s == SCANN_HIP_OK) return s;
+        // anything else (a bound that missed, a buffer that overflowed, a limit of the enqueue-only search): the route
+        // below answers it, with the plain host entry point's repeats or its error
+    }
+    // search(query, depth): the plain host entry point, with its pipelines, filter planning and repeats
+    std::vector<uint32_t> ri((size_t)nq * depth), rc(nq);
+    std::vector<float> rd((size_t)nq * depth);
+    SCANN_TRY(scann_hip_search_batched(ix, queries, nq, q_stride, q_dim, depth, opts, ri.data(), rd.data(), rc.data()));
+    if (k == 0) {
+        fill_empty(nq, 0, nullptr, nullptr, out_count);
+        return SCANN_HIP_OK;
+    }
+    if (depth > kCrowdMaxDepth)
+        return fail(SCANN_HIP_UNIMPLEMENTED, "crowding depth exceeds " + std::to_string(kCrowdMaxDepth));
+    SlotLock sl;
+    SCANN_TRY(acquire_slot(ix, &sl));
+    SCANN_TRY(set_device(ix->ctx));
+    CrowdWorkspace &cw = *sl.crowd;
+    SCANN_TRY(cw.ensure_rows(nq, depth));
+    SCANN_TRY(cw.ensure_out(nq, k));
+    const hipStream_t st = sl.stream;
+    const size_t rb = (size_t)nq * depth * 4, ob = (size_t)nq * k * 4;
+    SCANN_HIP_CHECK(hipMemcpyAsync(cw.idx.p, ri.data(), rb, hipMemcpyHostToDevice, st));
+    SCANN_HIP_CHECK(hipMemcpyAsync(cw.dist.p, rd.data(), rb, hipMemcpyHostToDevice, st));
+    SCANN_HIP_CHECK(hipMemcpyAsync(cw.cnt.p, rc.data(), (size_t)nq * 4, hipMemcpyHostToDevice, st));
+    SCANN_TRY(crowd_launch(cw.idx.as<uint32_t>(), cw.dist.as<float>(), cw.cnt.as<uint32_t>(), nq, depth,
+                           ix->crowd_attrs.as<uint64_t>(), ix->n_crowd_attrs, k, per_crowd_limit,
+                           cw.out_idx.as<uint32_t>(), cw.out_dist.as<float>(), cw.out_cnt.as<uint32_t>(), st));
+    SCANN_HIP_CHECK(hipMemcpyAsync(out_idx, cw.out_idx.p, ob, hipMemcpyDeviceToHost, st));
+    SCANN_HIP_CHECK(hipMemcpyAsync(out_dist, cw.out_dist.p, ob, hipMemcpyDeviceToHost, st));
+    SCANN_HIP_CHECK(hipMemcpyAsync(out_count, cw.out_cnt.p, (size_t)nq * 4, hipMemcpyDeviceToHost, st));
+    SCANN_HIP_CHECK(hipStreamSynchronize(st));
+    return SCANN_HIP_OK;
+}
+
+int scann_hip_index_reserve_crowded(scann_hip_index *ix, uint32_t max_nq, uint32_t max_k, uint32_t max_depth,
+                                    const scann_hip_search_opts *opts) {
+    if (!ix) return fail(SCANN_HIP_INVALID_ARGUMENT, "index is null");
+    if (max_depth == 0) max_depth = max_k;
+    if (max_depth < max_k) return fail(SCANN_HIP_INVALID_ARGUMENT, "crowding depth is smaller than k");
+    if (max_depth > kCrowdMaxDepth)
+        return fail(SCANN_HIP_UNIMPLEMENTED, "crowding depth exceeds " + std::to_string(kCrowdMaxDepth));
+    SCANN_TRY(scann_hip_index_reserve(ix, max_nq, max_depth, opts));
+    std::lock_guard<std::mutex> lock(ix->mu);
+    SCANN_TRY(set_device(ix->ctx));
+    SCANN_TRY(ix->crowd.ensure_rows(max_nq, max_depth));
+    return ix->crowd.ensure_out(max_nq, std::max(1u, max_k));
+}
+
+int scann_hip_search_crowded_device(scann_hip_index *ix, const float *d_queries, uint32_t nq, uint32_t q_stride,
+                                    uint32_t k, uint32_t depth, uint32_t per_crowd_limit,
+                                    const scann_hip_search_opts *opts, uint32_t *d_out_idx, float *d_out_dist,
+                                    uint32_t *d_out_count, void *hip_stream) {
+    if (!ix) return fail(SCANN_HIP_INVALID_ARGUMENT, "index is null");
+    if (k == 0) return fail(SCANN_HIP_INVALID_ARGUMENT, "k must be > 0 on the device path");
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    std::lock_guard<std::mutex> lock(ix->mu);
+    SCANN_TRY(crowd_args(ix, k, &depth));
+    if (nq == 0) return SCANN_HIP_OK;
+    SCANN_TRY(set_device(ix->ctx));
+    scann_hip_index::DeviceSlot *dsl = nullptr;
+    SCANN_TRY(device_slot(ix, st, &dsl));
+    CrowdWorkspace &cw = *dsl->crowd;
+    if (depth > kCrowdMaxDepth) {   // past every handle's largest k: the plain search's own error where it has one
+        if (ix->kind == KIND_TXH) {
+            TxhPlan p;
+            SCANN_TRY(plan_txh_search(ix, depth, opts, nq, false, TxhPipeline::Wide, read_knobs(), &p));
+        }
+        return fail(SCANN_HIP_UNIMPLEMENTED, "crowding depth exceeds " + std::to_string(kCrowdMaxDepth));
+    }
+    SCANN_TRY(cw.ensure_rows(nq, depth));   // (no allocation after scann_hip_index_reserve_crowded)
+    SCANN_TRY(search_device_ws(ix, dsl, *dsl->ws, *dsl->bfw, TxhPipeline::Wide, d_queries, nq, q_stride, depth, opts,
+                               cw.idx.as<uint32_t>(), cw.dist.as<float>(), cw.cnt.as<uint32_t>(), st));
+    SCANN_TRY(crowd_launch(cw.idx.as<uint32_t>(), cw.dist.as<float>(), cw.cnt.as<uint32_t>(), nq, depth,
+                           ix->crowd_attrs.as<uint64_t>(), ix->n_crowd_attrs, k, per_crowd_limit, d_out_idx,
+                           d_out_dist, d_out_count, st));
+    return device_slot_done(dsl, st);
 }
 
 // ---- multi-GPU ------------------------------------------------------------------------

@@ -29,6 +29,8 @@ EXPORTS = [
     "scann_hip_txh_create",
     "scann_hip_search_opts_default", "scann_hip_search_batched", "scann_hip_search_batched_params", "scann_hip_index_reserve",
     "scann_hip_search_batched_device", "scann_hip_index_last_device_status",
+    "scann_hip_crowd_table_slots", "scann_hip_index_set_crowding_attributes", "scann_hip_search_crowded",
+    "scann_hip_index_reserve_crowded", "scann_hip_search_crowded_device",
     "scann_hip_txh_search_local_device", "scann_hip_txh_merge_device",
     "scann_hip_assign_leaves", "scann_hip_txh_partition", "scann_hip_lut_from_query",
     "scann_hip_adc_distances", "scann_hip_lut16_distances_batch", "scann_hip_encode",
@@ -139,6 +141,14 @@ def load():
     L.scann_hip_search_batched_device.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32,
                                                   C.POINTER(SearchOpts), vp, vp, vp, vp]
     L.scann_hip_index_last_device_status.argtypes = [vp, vp]
+    L.scann_hip_crowd_table_slots.restype = C.c_uint32
+    L.scann_hip_crowd_table_slots.argtypes = [C.c_uint32]
+    L.scann_hip_index_set_crowding_attributes.argtypes = [vp, u64p, C.c_uint64]
+    L.scann_hip_search_crowded.argtypes = [vp, f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                           C.c_uint32, C.POINTER(SearchOpts), u32p, f32p, u32p]
+    L.scann_hip_index_reserve_crowded.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(SearchOpts)]
+    L.scann_hip_search_crowded_device.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                  C.POINTER(SearchOpts), vp, vp, vp, vp]
     L.scann_hip_txh_search_local_device.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32,
                                                     C.POINTER(SearchOpts), vp, vp, vp, vp, vp]
     L.scann_hip_txh_merge_device.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
@@ -317,6 +327,50 @@ class Index:
                 opts.allow_bitmap, opts.allow_bitmap_bits = None, 0
         return out_idx, out_dist, out_cnt
 
+    def set_crowding_attributes(self, attrs):
+        """One uint64 crowding attribute per datapoint index (the array may be shorter than the index: missing
+        entries read as 0); None or an empty array detaches them.  scann_hip_index_set_crowding_attributes."""
+        a = np.zeros(0, np.uint64) if attrs is None else np.ascontiguousarray(attrs, np.uint64).ravel()
+        check(load().scann_hip_index_set_crowding_attributes(self.h, ptr(a, u64p) if a.size else None, a.size))
+
+    def search_crowded(self, queries, k, depth, limit, opts=None, allow=None, allow_bits=None, q_dim=None):
+        """CrowdingConstraint::apply(search(query, depth), k) with per_crowd_limit = `limit`, on the device
+        (scann_hip_search_crowded).  depth = 0 means k.  `allow`, `allow_bits` as in search_batched."""
+        q = f32(queries)
+        if q.ndim == 1:
+            q = q[None]
+        nq, qs = q.shape
+        qd = qs if q_dim is None else q_dim
+        out_idx = np.full((nq, max(k, 1)), 0xFFFFFFFF, np.uint32)
+        out_dist = np.full((nq, max(k, 1)), np.inf, np.float32)
+        out_cnt = np.zeros(nq, np.uint32)
+        o = opts if opts is not None else default_opts()
+        if allow is not None:
+            allow = np.ascontiguousarray(allow, np.uint64)
+            o.allow_bitmap, o.allow_bitmap_bits = ptr(allow, u64p), _allow_capacity(allow, allow_bits)
+        try:
+            check(load().scann_hip_search_crowded(self.h, ptr(q, f32p), nq, qs, qd, k, depth, limit, C.byref(o),
+                                                  ptr(out_idx, u32p), ptr(out_dist, f32p), ptr(out_cnt, u32p)))
+        finally:
+            if allow is not None:   # (see search_batched)
+                o.allow_bitmap, o.allow_bitmap_bits = None, 0
+        return out_idx[:, :k], out_dist[:, :k], out_cnt
+
+    def search_crowded_exact(self, query, k, limit, opts=None):
+        """Brute-force handles: the crowded k nearest neighbours over the WHOLE index, one query.  Starts at
+        depth = k and doubles it until the row holds k entries or depth has reached min(N, 2048).  Returns
+        ((idx, dist), complete): complete is True when k were kept or the whole index was walked -- by the prefix
+        property the answer then equals the rule applied to the full sorted database."""
+        n = self.size()
+        cap = min(n, 2048)
+        depth = max(1, min(k, cap))
+        while True:
+            i, d, c = self.search_crowded(query, min(k, depth), depth, limit, opts=opts)
+            c = int(c[0])
+            if c >= k or depth >= cap:
+                return (i[0, :c].copy(), d[0, :c].copy()), bool(c >= k or depth >= n)
+            depth = min(2 * depth, cap)
+
     def search_radius(self, query, radius, capacity=None, allow=None, allow_bits=None):
         """Brute-force handles: bf_search_radius, with an optional allow-bitmap."""
         return bf_search_radius(self, query, radius, capacity, allow=allow, allow_bits=allow_bits)
@@ -337,6 +391,11 @@ def _allow_capacity(allow, allow_bits):
     if not 0 <= int(allow_bits) <= allow.size * 64:
         raise ValueError("allow_bits %d exceeds the bitmap's %d words" % (allow_bits, allow.size))
     return int(allow_bits)
+
+
+def crowd_table_slots(depth):
+    """slots of the crowding kernel's LDS attribute table for rows of `depth` entries (no GPU needed)"""
+    return int(load().scann_hip_crowd_table_slots(int(depth)))
 
 
 def allow_bitmap_count(allow, allow_bits, n):

@@ -17,6 +17,7 @@
 #pragma once
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -24,6 +25,7 @@
 #include <memory>
 #include <stdexcept>
 #include <string>
+#include <unordered_map>
 #include <utility>
 #include <vector>
 
@@ -212,6 +214,74 @@ private:
     RestrictAllowlist deny_;
 };
 
+// ---- crowding (restricts/crowding.rs:10-120) --------------------------------------------------------
+struct CrowdingConfig {              // crowding.rs:10-44
+    size_t per_crowd_limit = 3;
+    bool enabled = true;
+    CrowdingConfig() = default;
+    explicit CrowdingConfig(size_t limit) : per_crowd_limit(limit), enabled(true) {}
+    static CrowdingConfig disabled() {
+        CrowdingConfig c(std::numeric_limits<size_t>::max());
+        c.enabled = false;
+        return c;
+    }
+};
+
+class CrowdingConstraint {           // crowding.rs:46-120
+public:
+    CrowdingConstraint(std::vector<uint64_t> crowding_attributes, CrowdingConfig config)
+        : attrs_(std::move(crowding_attributes)), config_(config), stamp_(next_stamp()) {}
+    bool get_attribute(DatapointIndex index, uint64_t *out) const {   // Option<u64>: false = None
+        if ((size_t)index >= attrs_.size()) return false;
+        *out = attrs_[index];
+        return true;
+    }
+    uint64_t attribute_or_zero(DatapointIndex index) const {          // get_attribute(idx).unwrap_or(0), :90
+        return (size_t)index < attrs_.size() ? attrs_[index] : 0;
+    }
+    void set_attribute(DatapointIndex index, uint64_t attribute) {    // :69-75: resize with 0
+        if ((size_t)index >= attrs_.size()) attrs_.resize((size_t)index + 1, 0);
+        attrs_[index] = attribute;
+        stamp_ = next_stamp();
+    }
+    // The plain host walk (:81-104), statement for statement -- including that it tests `len >= k` only after a push.
+    NNResultsVector apply(const NNResultsVector &results, size_t k) const {
+        if (!config_.enabled) return NNResultsVector(results.begin(), results.begin() + std::min(k, results.size()));
+        std::unordered_map<uint64_t, size_t> crowd_counts;
+        NNResultsVector filtered;
+        filtered.reserve(std::min(k, results.size()));
+        for (const auto &r : results) {
+            size_t &count = crowd_counts[attribute_or_zero(r.first)];
+            if (count < config_.per_crowd_limit) {
+                filtered.push_back(r);
+                ++count;
+                if (filtered.size() >= k) break;
+            }
+        }
+        return filtered;
+    }
+    bool would_violate(DatapointIndex index, const NNResultsVector &current_results) const {   // :107-119
+        if (!config_.enabled) return false;
+        const uint64_t attribute = attribute_or_zero(index);
+        size_t count = 0;
+        for (const auto &r : current_results) count += attribute_or_zero(r.first) == attribute ? 1 : 0;
+        return count >= config_.per_crowd_limit;
+    }
+    const CrowdingConfig &config() const { return config_; }
+    const std::vector<uint64_t> &attributes() const { return attrs_; }
+    // changes whenever the attributes do (and differs between constraints): what a searcher remembers having attached
+    uint64_t stamp() const { return stamp_; }
+
+private:
+    static uint64_t next_stamp() {
+        static std::atomic<uint64_t> s{0};
+        return ++s;
+    }
+    std::vector<uint64_t> attrs_;
+    CrowdingConfig config_;
+    uint64_t stamp_;
+};
+
 namespace detail {
 
 struct IndexHandle {
@@ -247,6 +317,35 @@ inline std::vector<NNResultsVector> run_search_params(scann_hip_index *h, const 
     std::vector<NNResultsVector> out(nq);
     for (uint32_t i = 0; i < nq; ++i)
         for (uint32_t j = 0; j < cnt[i]; ++j) out[i].emplace_back(idx[(size_t)i * pitch + j], dist[(size_t)i * pitch + j]);
+    return out;
+}
+
+// search_with_crowding of every searcher: the constraint's attributes are copied to the handle once (again only when
+// they changed), then scann_hip_search_crowded = CrowdingConstraint::apply(search(query, depth), k) on the device.
+struct CrowdAttach {
+    mutable uint64_t stamp = 0;   // (attaching needs the external synchronisation of create / destroy)
+    void ensure(scann_hip_index *h, const CrowdingConstraint &c) const {
+        if (stamp == c.stamp()) return;
+        // (an empty attribute vector still attaches: every datapoint then has attribute 0)
+        static const uint64_t zero = 0;
+        const auto &a = c.attributes();
+        check(scann_hip_index_set_crowding_attributes(h, a.empty() ? &zero : a.data(), a.empty() ? 1 : a.size()));
+        stamp = c.stamp();
+    }
+};
+
+inline NNResultsVector run_search_crowded(scann_hip_index *h, const CrowdAttach &at, const std::vector<float> &query,
+                                          size_t k, size_t depth, const CrowdingConstraint &c,
+                                          const scann_hip_search_opts *opts) {
+    at.ensure(h, c);
+    const uint32_t limit = (uint32_t)std::min<size_t>(c.config().per_crowd_limit, 0xFFFFFFFFu);
+    std::vector<uint32_t> idx(std::max<size_t>(1, k));
+    std::vector<float> dist(std::max<size_t>(1, k));
+    uint32_t cnt = 0;
+    check(scann_hip_search_crowded(h, query.data(), 1, (uint32_t)query.size(), (uint32_t)query.size(), (uint32_t)k,
+                                   (uint32_t)depth, limit, opts, idx.data(), dist.data(), &cnt));
+    NNResultsVector out;
+    for (uint32_t j = 0; j < cnt; ++j) out.emplace_back(idx[j], dist[j]);
     return out;
 }
 
@@ -350,6 +449,29 @@ public:
         return detail::run_search(ix_.h, query.data(), 1, (uint32_t)query.size(), (uint32_t)query.size(),
                                   (uint32_t)k, &o)[0];
     }
+    // CrowdingConstraint::apply(search(query, depth), k) on the device; a disabled constraint is the plain search.
+    NNResultsVector search_with_crowding(const std::vector<float> &query, size_t k, size_t depth,
+                                         const CrowdingConstraint &constraint) const {
+        if (!constraint.config().enabled) return search(query, k);
+        return detail::run_search_crowded(ix_.h, crowd_, query, k, depth, constraint, nullptr);
+    }
+    // The crowded k nearest neighbours over the WHOLE index: depth starts at k and doubles until the row holds k
+    // entries or depth has reached min(N, 2048).  second = complete: k were kept, or the whole index was walked; by
+    // the prefix property the rows then equal apply() over the full sorted database.
+    std::pair<NNResultsVector, bool> search_crowded_exact(const std::vector<float> &query, size_t k,
+                                                          const CrowdingConstraint &constraint) const {
+        const size_t n = dataset_->size(), cap = std::min<size_t>(n, 2048);
+        if (!constraint.config().enabled) return {search(query, k), true};
+        size_t depth = std::max<size_t>(1, std::min(k, cap));
+        for (;;) {
+            NNResultsVector r = search_with_crowding(query, std::min(k, depth), depth, constraint);
+            if (r.size() >= k || depth >= cap) {
+                const bool complete = r.size() >= k || depth >= n;
+                return {std::move(r), complete};
+            }
+            depth = std::min(2 * depth, cap);
+        }
+    }
     NNResultsVector search_radius(const std::vector<float> &query, float radius) const {   // :142-167
         return search_radius_with_filter(query, radius, nullptr);
     }
@@ -388,6 +510,7 @@ private:
     std::shared_ptr<DenseDataset> dataset_;
     DistanceMeasure measure_;
     detail::IndexHandle ix_;
+    detail::CrowdAttach crowd_;
 };
 
 // ---- AsymmetricHasher (hashes/hasher.rs) ---------------------------------------------------
@@ -427,6 +550,15 @@ public:
         o.pre_reorder_k = (uint32_t)pre_reorder_k;
         return detail::run_search(ix_.h, query.data(), 1, (uint32_t)query.size(), (uint32_t)query.size(),
                                   (uint32_t)k, &o)[0];
+    }
+    // CrowdingConstraint::apply(search(query, depth), k) on the device (search = the approximate search above)
+    NNResultsVector search_with_crowding(const std::vector<float> &query, size_t k, size_t depth,
+                                         const CrowdingConstraint &constraint) const {
+        if (!constraint.config().enabled || !ix_.h) return search(query, k);
+        scann_hip_search_opts o;
+        scann_hip_search_opts_default(&o);
+        o.exact_reorder = 0;
+        return detail::run_search_crowded(ix_.h, crowd_, query, k, depth, constraint, &o);
     }
     std::vector<NNResultsVector> search_batched(const std::vector<std::vector<float>> &queries, size_t k) const {
         if (queries.empty() || !ix_.h) return std::vector<NNResultsVector>(queries.size());
@@ -483,6 +615,7 @@ private:
     size_t n_ = 0, dim_ = 0;
     bool stored_ = false;
     detail::IndexHandle ix_;
+    detail::CrowdAttach crowd_;
 };
 
 // ---- TreeXHybridSearcher (tree_x_hybrid/mod.rs) ------------------------------------------------
@@ -548,6 +681,13 @@ public:
         if (!ix_.h) throw ScannError::failed_precondition("Partitioner not built");
         return detail::run_search(ix_.h, query.data(), 1, (uint32_t)query.size(), (uint32_t)query.size(),
                                   (uint32_t)k, nullptr)[0];
+    }
+    // CrowdingConstraint::apply(search(query, depth), k) on the device
+    NNResultsVector search_with_crowding(const std::vector<float> &query, size_t k, size_t depth,
+                                         const CrowdingConstraint &constraint) const {
+        if (!constraint.config().enabled) return search(query, k);
+        if (!ix_.h) throw ScannError::failed_precondition("Partitioner not built");
+        return detail::run_search_crowded(ix_.h, crowd_, query, k, depth, constraint, nullptr);
     }
     // mod.rs:245-294: disallowed datapoints are skipped before scoring.  The filter is
     // materialised once into an allow-bitmap that the scan kernels test.
@@ -643,6 +783,7 @@ private:
     std::vector<uint8_t> codes_;
     size_t n_ = 0, dim_ = 0, L_ = 0;
     detail::IndexHandle ix_;
+    detail::CrowdAttach crowd_;
 };
 
 namespace detail {
@@ -761,6 +902,20 @@ public:
         if (mode_ != SearchMode::Hashed) o.partitions_to_search = config_.partitioning.num_partitions_to_search;
         return detail::run_search(ix_.h, flat.data(), (uint32_t)qs.size(), d, d, (uint32_t)k, &o);
     }
+    // CrowdingConstraint::apply(search(query, depth), k) on the device, search as configured above
+    NNResultsVector search_with_crowding(const std::vector<float> &q, size_t k, size_t depth,
+                                         const CrowdingConstraint &constraint) const {
+        if (!constraint.config().enabled) return search(q, k);
+        if (mode_ == SearchMode::BruteForce) return bf_->search_with_crowding(q, k, depth, constraint);
+        const size_t dd = depth ? depth : k;
+        scann_hip_search_opts o;
+        scann_hip_search_opts_default(&o);
+        o.pre_reorder_k = (uint32_t)dd;
+        const bool reorder = config_.has_exact_reordering && config_.exact_reordering.num_candidates > dd;
+        o.exact_reorder = (reorder && mode_ != SearchMode::Partitioned) ? 1 : 0;
+        if (mode_ != SearchMode::Hashed) o.partitions_to_search = config_.partitioning.num_partitions_to_search;
+        return detail::run_search_crowded(ix_.h, crowd_, q, k, dd, constraint, &o);
+    }
     SearchMode search_mode() const { return mode_; }
     size_t size() const { return dataset_->size(); }
     uint64_t dimensionality() const { return dataset_->dimensionality(); }
@@ -831,6 +986,7 @@ private:
     std::vector<uint32_t> leaf_off_, leaf_ids_;
     std::vector<uint8_t> codes_;
     detail::IndexHandle ix_;
+    detail::CrowdAttach crowd_;
 };
 
 class ScannBuilder {   // scann.rs:364-426
