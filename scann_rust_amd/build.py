@@ -13,7 +13,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "_obj")
 LIB = os.path.join(HERE, "libscann_hip.so")
 SOURCES = ["api.hip", "txh.hip", "bf.hip", "index_file.hip", "comm.hip", "crowd.hip"]
-HEADERS = ["common.h", "knobs.h", "txh.h", "bf.h", "comm.h", "crowd.h", os.path.join("..", "..", "include", "scann_hip.h")]
+HEADERS = ["common.h", "knobs.h", "txh.h", "bf.h", "comm.h", "crowd.h", "launch.h", os.path.join("..", "..", "include", "scann_hip.h")]
 # -ffp-contract=off: the reference never contracts a*b+c (Rust); FMA is used only via
 # explicit fmaf()/MFMA where the reference uses _mm256_fmadd_ps.
 CFLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "-fPIC", "-Wall",

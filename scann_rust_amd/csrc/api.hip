@@ -19,6 +19,7 @@
 #include "common.h"
 #include "crowd.h"
 #include "knobs.h"
+#include "launch.h"
 #include "txh.h"
 
 namespace scann {
@@ -366,7 +367,7 @@ float scann_hip_index_last_kernel_ms(scann_hip_index *ix, const char **name) {
         // clear the error the query leaves behind, or the next search's launch check reports it as its own
         if (hipEventSynchronize(ix->evs[i][1]) != hipSuccess ||
             hipEventElapsedTime(&ms, ix->evs[i][0], ix->evs[i][1]) != hipSuccess) {
-            (void)hipGetLastError();
+            clear_last_hip_error();
             continue;
         }
         sum += ms;

@@ -15,6 +15,7 @@
 //  * top-k: a strided row sample gives a valid upper bound of the k-th best key; the full
 //    pass keeps only (distance, index) keys <= bound; a per-query LDS sort finishes.
 #include "bf.h"
+#include "launch.h"
 
 #include <hipcub/hipcub.hpp>
 
@@ -1666,35 +1667,14 @@ __global__ __launch_bounds__(256) void bf16_quantize_kernel(const float *__restr
 // =====================================================================================
 // host side
 // =====================================================================================
-#define LAUNCH_CHECK()                                                                \
-    do {                                                                              \
-        hipError_t _e = hipGetLastError();                                            \
-        if (_e != hipSuccess)                                                         \
-            return fail(SCANN_HIP_INTERNAL, std::string("kernel launch: ") + hipGetErrorString(_e)); \
-    } while (0)
-
+// row length -> template argument of the MFMA kernels (dim / 16; default: 16) and of bf_vq_kernel (dim / 8; default: 16)
 template <typename F>
-static int set_dyn_lds(F kernel, size_t bytes) {
-    // Always the same value (the CU's 160 KB), never the launch's own size: threads searching
-    // different indexes set this attribute concurrently, and a smaller value written by one of
-    // them must not undercut another's launch.
-    constexpr size_t kMaxLds = 160 * 1024;
-    if (bytes > kMaxLds) return fail(SCANN_HIP_RESOURCE_EXHAUSTED, "kernel needs more than 160 KB of LDS");
-    if (bytes > 64 * 1024)
-        SCANN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds));
-    return SCANN_HIP_OK;
+static int with_dim16(uint32_t dim, F &&f) {
+    return with_value<2, 4, 6, 8, 12, 16>((int)(dim / 16), std::forward<F>(f));
 }
-
-static int g_num_cus = 0;
-static int num_cus() {
-    if (!g_num_cus) {
-        int dev = 0, cus = 256;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        g_num_cus = cus;
-    }
-    return g_num_cus;
+template <typename F>
+static int with_dim8(uint32_t dim, F &&f) {
+    return with_value<4, 8, 12, 16>((int)(dim / 8), std::forward<F>(f));
 }
 
 template <int TS>
@@ -1705,10 +1685,7 @@ static int launch_mfma(const BfIndexDev &ix, const BfPass &p, hipStream_t st) {
     want = std::min(want, ntiles);
     const uint32_t nx = 8u * ceil_div_u32(want, 8);
     const size_t lds = (size_t)2 * 32 * (TS * 16) * sizeof(float);
-    SCANN_TRY(set_dyn_lds(bf_mfma_dot_kernel<TS>, lds));
-    hipLaunchKernelGGL(bf_mfma_dot_kernel<TS>, dim3(nx * ny), dim3(256), lds, st, ix, p, nx, ny);
-    LAUNCH_CHECK();
-    return SCANN_HIP_OK;
+    return launch(bf_mfma_dot_kernel<TS>, dim3(nx * ny), dim3(256), lds, st, ix, p, nx, ny);
 }
 
 static bool mfma_eligible(const BfIndexDev &ix) {
@@ -1739,41 +1716,22 @@ template <int FMT, int QT>
 static int launch_quant(const BfIndexDev &ix, const BfPass &p, hipStream_t st) {
     const size_t lds = (size_t)ix.dim * QT * sizeof(float);
     const dim3 grid(ceil_div_u32(p.nrows, 256), ceil_div_u32(p.nq, QT));
-    switch (ix.measure) {
-        case SCANN_HIP_SQUARED_L2:
-            SCANN_TRY(set_dyn_lds(bf_quant_kernel<FMT, SCANN_HIP_SQUARED_L2, QT>, lds));
-            hipLaunchKernelGGL((bf_quant_kernel<FMT, SCANN_HIP_SQUARED_L2, QT>), grid, dim3(256), lds, st, ix, p);
-            break;
-        case SCANN_HIP_L2:
-            SCANN_TRY(set_dyn_lds(bf_quant_kernel<FMT, SCANN_HIP_L2, QT>, lds));
-            hipLaunchKernelGGL((bf_quant_kernel<FMT, SCANN_HIP_L2, QT>), grid, dim3(256), lds, st, ix, p);
-            break;
-        case SCANN_HIP_DOT_PRODUCT:
-            SCANN_TRY(set_dyn_lds(bf_quant_kernel<FMT, SCANN_HIP_DOT_PRODUCT, QT>, lds));
-            hipLaunchKernelGGL((bf_quant_kernel<FMT, SCANN_HIP_DOT_PRODUCT, QT>), grid, dim3(256), lds, st, ix, p);
-            break;
-        default:
-            return fail(SCANN_HIP_UNIMPLEMENTED, "quantized rows: SquaredL2, L2 and DotProduct only");
-    }
-    LAUNCH_CHECK();
-    return SCANN_HIP_OK;
+    if (ix.measure > SCANN_HIP_DOT_PRODUCT)
+        return fail(SCANN_HIP_UNIMPLEMENTED, "quantized rows: SquaredL2, L2 and DotProduct only");
+    return with_dot_measure(ix.measure, [&](auto m) {
+        return launch((bf_quant_kernel<FMT, m(), QT>), grid, dim3(256), lds, st, ix, p);
+    });
 }
 
 // quantized rows: every pass (sample, filter, dense matrix, radius) on bf_quant_kernel; one query pair per
 // workgroup row for the one- and two-query searches, four pairs otherwise
 static int launch_quant_pass(const BfIndexDev &ix, const BfPass &p, hipStream_t st) {
     const bool few = p.nq <= 2;
-    switch (ix.fmt) {
-        case SCANN_HIP_ROWS_BF16:
-            return few ? launch_quant<SCANN_HIP_ROWS_BF16, 2>(ix, p, st) : launch_quant<SCANN_HIP_ROWS_BF16, 8>(ix, p, st);
-        case SCANN_HIP_ROWS_FP8_E4M3:
-            return few ? launch_quant<SCANN_HIP_ROWS_FP8_E4M3, 2>(ix, p, st)
-                       : launch_quant<SCANN_HIP_ROWS_FP8_E4M3, 8>(ix, p, st);
-        case SCANN_HIP_ROWS_INT8:
-            return few ? launch_quant<SCANN_HIP_ROWS_INT8, 2>(ix, p, st) : launch_quant<SCANN_HIP_ROWS_INT8, 8>(ix, p, st);
-        default:
-            return fail(SCANN_HIP_INVALID_ARGUMENT, "unknown row format");
-    }
+    if (ix.fmt != SCANN_HIP_ROWS_BF16 && ix.fmt != SCANN_HIP_ROWS_FP8_E4M3 && ix.fmt != SCANN_HIP_ROWS_INT8)
+        return fail(SCANN_HIP_INVALID_ARGUMENT, "unknown row format");
+    return with_value<SCANN_HIP_ROWS_BF16, SCANN_HIP_ROWS_FP8_E4M3, SCANN_HIP_ROWS_INT8>(ix.fmt, [&](auto fmt) {
+        return few ? launch_quant<fmt(), 2>(ix, p, st) : launch_quant<fmt(), 8>(ix, p, st);
+    });
 }
 
 // name of the kernel launch_pass picks for a batch of nq queries (timing reports)
@@ -1797,77 +1755,27 @@ static int launch_pass(const BfIndexDev &ix, const BfPass &p, hipStream_t st) {
         const uint32_t ngroups = ceil_div_u32(p.nrows, 64);
         const uint32_t nx = std::max(1u, std::min(ceil_div_u32(ngroups, 4), 4u * (uint32_t)num_cus()));
         dim3 grid(nx, ny);
-        switch (ix.measure) {
-            case SCANN_HIP_SQUARED_L2:
-                SCANN_TRY(set_dyn_lds(bf_stream_kernel<SCANN_HIP_SQUARED_L2>, lds));
-                hipLaunchKernelGGL(bf_stream_kernel<SCANN_HIP_SQUARED_L2>, grid, dim3(256), lds, st, ix, p);
-                break;
-            case SCANN_HIP_L2:
-                SCANN_TRY(set_dyn_lds(bf_stream_kernel<SCANN_HIP_L2>, lds));
-                hipLaunchKernelGGL(bf_stream_kernel<SCANN_HIP_L2>, grid, dim3(256), lds, st, ix, p);
-                break;
-            default:
-                SCANN_TRY(set_dyn_lds(bf_stream_kernel<SCANN_HIP_DOT_PRODUCT>, lds));
-                hipLaunchKernelGGL(bf_stream_kernel<SCANN_HIP_DOT_PRODUCT>, grid, dim3(256), lds, st, ix, p);
-                break;
-        }
-        LAUNCH_CHECK();
-        return SCANN_HIP_OK;
+        return with_dot_measure(ix.measure, [&](auto m) {
+            return launch(bf_stream_kernel<m()>, grid, dim3(256), lds, st, ix, p);
+        });
     }
-    if (mfma_eligible(ix)) {
-        switch (ix.dim / 16) {
-            case 2: return launch_mfma<2>(ix, p, st);
-            case 4: return launch_mfma<4>(ix, p, st);
-            case 6: return launch_mfma<6>(ix, p, st);
-            case 8: return launch_mfma<8>(ix, p, st);
-            case 12: return launch_mfma<12>(ix, p, st);
-            case 16: return launch_mfma<16>(ix, p, st);
-        }
-    }
+    if (mfma_eligible(ix)) return with_dim16(ix.dim, [&](auto ts) { return launch_mfma<ts()>(ix, p, st); });
     if (vq_eligible(ix, p)) {
         const uint32_t ny = ceil_div_u32(p.nq, 256);
         const uint32_t ntiles = ceil_div_u32(p.nrows, kVqRows);
         const uint32_t nx = std::max(1u, std::min(ntiles, (2u * (uint32_t)num_cus() + ny - 1) / ny));
-#define SCANN_VQ(M, DCV)                                                                          \
-    hipLaunchKernelGGL((bf_vq_kernel<M, DCV>), dim3(nx * ny), dim3(256), 0, st, ix, p, nx)
-        const bool l2 = ix.measure == SCANN_HIP_L2;
-        switch (ix.dim / 8) {
-            case 4: if (l2) SCANN_VQ(SCANN_HIP_L2, 4); else SCANN_VQ(SCANN_HIP_SQUARED_L2, 4); break;
-            case 8: if (l2) SCANN_VQ(SCANN_HIP_L2, 8); else SCANN_VQ(SCANN_HIP_SQUARED_L2, 8); break;
-            case 12: if (l2) SCANN_VQ(SCANN_HIP_L2, 12); else SCANN_VQ(SCANN_HIP_SQUARED_L2, 12); break;
-            default: if (l2) SCANN_VQ(SCANN_HIP_L2, 16); else SCANN_VQ(SCANN_HIP_SQUARED_L2, 16); break;
-        }
-#undef SCANN_VQ
-        LAUNCH_CHECK();
-        return SCANN_HIP_OK;
+        return with_value<SCANN_HIP_L2, SCANN_HIP_SQUARED_L2>(ix.measure, [&](auto m) {
+            return with_dim8(ix.dim, [&](auto dcv) {
+                return launch((bf_vq_kernel<m(), dcv()>), dim3(nx * ny), dim3(256), 0, st, ix, p, nx);
+            });
+        });
     }
     const uint32_t dimp = (ix.dim + 3u) & ~3u;
     const size_t lds = ((size_t)kBfGenQT * dimp + kBfGenQT) * sizeof(float);
     dim3 grid(ceil_div_u32(p.nrows, 256), ceil_div_u32(p.nq, kBfGenQT));
-    switch (ix.measure) {
-        case SCANN_HIP_L1:
-            SCANN_TRY(set_dyn_lds(bf_generic_kernel<SCANN_HIP_L1>, lds));
-            hipLaunchKernelGGL(bf_generic_kernel<SCANN_HIP_L1>, grid, dim3(256), lds, st, ix, p);
-            break;
-        case SCANN_HIP_COSINE:
-            SCANN_TRY(set_dyn_lds(bf_generic_kernel<SCANN_HIP_COSINE>, lds));
-            hipLaunchKernelGGL(bf_generic_kernel<SCANN_HIP_COSINE>, grid, dim3(256), lds, st, ix, p);
-            break;
-        case SCANN_HIP_SQUARED_L2:
-            SCANN_TRY(set_dyn_lds(bf_generic_kernel<SCANN_HIP_SQUARED_L2>, lds));
-            hipLaunchKernelGGL(bf_generic_kernel<SCANN_HIP_SQUARED_L2>, grid, dim3(256), lds, st, ix, p);
-            break;
-        case SCANN_HIP_L2:
-            SCANN_TRY(set_dyn_lds(bf_generic_kernel<SCANN_HIP_L2>, lds));
-            hipLaunchKernelGGL(bf_generic_kernel<SCANN_HIP_L2>, grid, dim3(256), lds, st, ix, p);
-            break;
-        default:
-            SCANN_TRY(set_dyn_lds(bf_generic_kernel<SCANN_HIP_DOT_PRODUCT>, lds));
-            hipLaunchKernelGGL(bf_generic_kernel<SCANN_HIP_DOT_PRODUCT>, grid, dim3(256), lds, st, ix, p);
-            break;
-    }
-    LAUNCH_CHECK();
-    return SCANN_HIP_OK;
+    return with_measure(ix.measure, [&](auto m) {
+        return launch(bf_generic_kernel<m()>, grid, dim3(256), lds, st, ix, p);
+    });
 }
 
 struct BfPlan {
@@ -1938,11 +1846,9 @@ static int upload_filter(const BfIndexDev &ix, BfWorkspace &w, const BfFilter &f
     SCANN_TRY(w.ids.ensure(std::max<size_t>(count, 1) * 4));
     SCANN_TRY(w.allow_sums.ensure((size_t)(blocks + 1) * 4));
     uint32_t *sums = w.allow_sums.as<uint32_t>();
-    hipLaunchKernelGGL(bf_allow_count_kernel, dim3(blocks), dim3(kCompactWords), 0, st, fd->allow, bits, sums);
-    LAUNCH_CHECK();
-    hipLaunchKernelGGL(bf_allow_compact_kernel, dim3(blocks), dim3(kCompactWords), 0, st, fd->allow, bits, sums,
-                       w.ids.as<uint32_t>(), count, sums + blocks);
-    LAUNCH_CHECK();
+    SCANN_TRY(launch(bf_allow_count_kernel, dim3(blocks), dim3(kCompactWords), 0, st, fd->allow, bits, sums));
+    SCANN_TRY(launch(bf_allow_compact_kernel, dim3(blocks), dim3(kCompactWords), 0, st, fd->allow, bits, sums,
+                     w.ids.as<uint32_t>(), count, sums + blocks));
     fd->ids = w.ids.as<uint32_t>();
     fd->allow = nullptr;   // every listed row is allowed
     fd->allow_bits = 0;
@@ -1986,11 +1892,9 @@ static int enqueue_search(const BfIndexDev &ix, BfWorkspace &w, const BfPlan &pl
     if (pl.direct && ev1) SCANN_HIP_CHECK(hipEventRecord(ev1, st));
     const SelCfg tcfg = sel_cfg(pl.ns);
     const size_t lds_thr = (size_t)next_pow2_u32(pl.ns) * 8 + (size_t)tcfg.bins * 4 + (size_t)tcfg.list * 8 + 48 * 8;
-    SCANN_TRY(set_dyn_lds(bf_threshold_kernel, lds_thr));
-    hipLaunchKernelGGL(bf_threshold_kernel, dim3(nq), dim3(kBfSelectThreads), lds_thr, st,
-                       w.sample.as<float>(), pl.ns, pl.rs, pl.k, pl.direct ? 1 : 0,
-                       w.thr.as<uint64_t>(), d_out_idx, d_out_dist, d_out_count, fd.ids, fd.allow, fd.allow_bits);
-    LAUNCH_CHECK();
+    SCANN_TRY(launch(bf_threshold_kernel, dim3(nq), dim3(kBfSelectThreads), lds_thr, st,
+                     w.sample.as<float>(), pl.ns, pl.rs, pl.k, pl.direct ? 1 : 0,
+                     w.thr.as<uint64_t>(), d_out_idx, d_out_dist, d_out_count, fd.ids, fd.allow, fd.allow_bits));
     if (pl.direct) return SCANN_HIP_OK;
 
     SCANN_HIP_CHECK(hipMemsetAsync(w.cand_cnt.p, 0, (size_t)nq * 4, st));
@@ -2010,11 +1914,9 @@ static int enqueue_search(const BfIndexDev &ix, BfWorkspace &w, const BfPlan &pl
     const SelCfg scfg = sel_cfg(kBfSortCap);
     const size_t lds_sel = (size_t)kBfSortCap * 8 + (kBfSelectThreads / 64 + 4) * 4 + (size_t)kBfMaxK * 8 +
                            (size_t)scfg.bins * 4 + (size_t)scfg.list * 8 + 48 * 8;
-    SCANN_TRY(set_dyn_lds(bf_select_kernel, lds_sel));
-    hipLaunchKernelGGL(bf_select_kernel, dim3(nq), dim3(kBfSelectThreads), lds_sel, st, pl.k, pl.cap,
-                       w.cand_cnt.as<uint32_t>(), w.cand.as<uint64_t>(), w.counters.as<uint32_t>(),
-                       d_out_idx, d_out_dist, d_out_count);
-    LAUNCH_CHECK();
+    SCANN_TRY(launch(bf_select_kernel, dim3(nq), dim3(kBfSelectThreads), lds_sel, st, pl.k, pl.cap,
+                     w.cand_cnt.as<uint32_t>(), w.cand.as<uint64_t>(), w.counters.as<uint32_t>(),
+                     d_out_idx, d_out_dist, d_out_count));
     return SCANN_HIP_OK;
 }
 
@@ -2044,26 +1946,15 @@ int bf_build_shortlist_data(const BfIndexDev &ix, DevBuf &rows_b, DevBuf &rows_b
     SCANN_TRY(mx.ensure(4));
     SCANN_HIP_CHECK(hipMemsetAsync(mx.p, 0, 4, st));
     const dim3 grid_n((uint32_t)ceil_div_u64(ix.n, 256));
-    switch (ix.fmt) {
-        case SCANN_HIP_ROWS_BF16:
-            hipLaunchKernelGGL(bf_quant_norms_kernel<SCANN_HIP_ROWS_BF16>, grid_n, dim3(256), 0, st, ix, norm2.as<float>());
-            break;
-        case SCANN_HIP_ROWS_FP8_E4M3:
-            hipLaunchKernelGGL(bf_quant_norms_kernel<SCANN_HIP_ROWS_FP8_E4M3>, grid_n, dim3(256), 0, st, ix,
-                               norm2.as<float>());
-            break;
-        case SCANN_HIP_ROWS_INT8:
-            hipLaunchKernelGGL(bf_quant_norms_kernel<SCANN_HIP_ROWS_INT8>, grid_n, dim3(256), 0, st, ix, norm2.as<float>());
-            break;
-        default:
-            hipLaunchKernelGGL(bf_to_bf16_kernel, grid_n, dim3(256), 0, st, ix.rows, ix.n, ix.dim, ix.stride,
-                               rows_b.as<uint16_t>(), rows_bl.as<uint16_t>(), norm2.as<float>());
-            break;
-    }
-    LAUNCH_CHECK();
-    hipLaunchKernelGGL(bf_max_norm_kernel, dim3(256), dim3(256), 0, st, norm2.as<float>(), ix.n,
-                       mx.as<uint32_t>());
-    LAUNCH_CHECK();
+    SCANN_TRY(with_row_format(ix.fmt, [&](auto fmt) {
+        if constexpr (fmt() != 0)
+            return launch(bf_quant_norms_kernel<fmt()>, grid_n, dim3(256), 0, st, ix, norm2.as<float>());
+        else
+            return launch(bf_to_bf16_kernel, grid_n, dim3(256), 0, st, ix.rows, ix.n, ix.dim, ix.stride,
+                          rows_b.as<uint16_t>(), rows_bl.as<uint16_t>(), norm2.as<float>());
+    }));
+    SCANN_TRY(launch(bf_max_norm_kernel, dim3(256), dim3(256), 0, st, norm2.as<float>(), ix.n,
+                     mx.as<uint32_t>()));
     uint32_t bits = 0;
     SCANN_HIP_CHECK(hipMemcpyAsync(&bits, mx.p, 4, hipMemcpyDeviceToHost, st));
     SCANN_HIP_CHECK(hipStreamSynchronize(st));
@@ -2094,68 +1985,33 @@ static int launch_bf16(const BfIndexDev &ix, const BfPass &p, const uint16_t *qb
     const uint32_t nx = 8u * ceil_div_u32(want, 8);
     const size_t lds = (size_t)kB16Ring * (2 * 32 * kB16Sub * (TS * 16) * 2 + 256) +   // (hi | lo | norms) stages
                        16;
-    if (ix.measure == SCANN_HIP_DOT_PRODUCT) {
-        SCANN_TRY(set_dyn_lds((bf_bf16_kernel<TS, SCANN_HIP_DOT_PRODUCT, FMT>), lds));
-        hipLaunchKernelGGL((bf_bf16_kernel<TS, SCANN_HIP_DOT_PRODUCT, FMT>), dim3(nx * ny), dim3(kB16Waves * 64), lds,
-                           st, ix, p, qb, qbl, qn2, nx, ny);
-    } else {
-        SCANN_TRY(set_dyn_lds((bf_bf16_kernel<TS, SCANN_HIP_SQUARED_L2, FMT>), lds));
-        hipLaunchKernelGGL((bf_bf16_kernel<TS, SCANN_HIP_SQUARED_L2, FMT>), dim3(nx * ny), dim3(kB16Waves * 64), lds,
-                           st, ix, p, qb, qbl, qn2, nx, ny);
-    }
-    LAUNCH_CHECK();
-    return SCANN_HIP_OK;
-}
-
-template <int FMT>
-static int launch_bf16_dims(const BfIndexDev &ix, const BfPass &p, const uint16_t *qb, const uint16_t *qbl,
-                            const float *qn2, hipStream_t st) {
-    switch (ix.dim / 16) {
-        case 2: return launch_bf16<2, FMT>(ix, p, qb, qbl, qn2, st);
-        case 4: return launch_bf16<4, FMT>(ix, p, qb, qbl, qn2, st);
-        case 6: return launch_bf16<6, FMT>(ix, p, qb, qbl, qn2, st);
-        case 8: return launch_bf16<8, FMT>(ix, p, qb, qbl, qn2, st);
-        case 12: return launch_bf16<12, FMT>(ix, p, qb, qbl, qn2, st);
-        default: return launch_bf16<16, FMT>(ix, p, qb, qbl, qn2, st);
-    }
+    return with_value<SCANN_HIP_DOT_PRODUCT, SCANN_HIP_SQUARED_L2>(ix.measure, [&](auto m) {
+        return launch((bf_bf16_kernel<TS, m(), FMT>), dim3(nx * ny), dim3(kB16Waves * 64), lds, st, ix, p, qb, qbl, qn2,
+                      nx, ny);
+    });
 }
 
 static int launch_bf16_pass(const BfIndexDev &ix, const BfPass &p, const uint16_t *qb, const uint16_t *qbl,
                             const float *qn2, hipStream_t st) {
-    switch (ix.fmt) {
-        case SCANN_HIP_ROWS_BF16: return launch_bf16_dims<SCANN_HIP_ROWS_BF16>(ix, p, qb, qbl, qn2, st);
-        case SCANN_HIP_ROWS_FP8_E4M3: return launch_bf16_dims<SCANN_HIP_ROWS_FP8_E4M3>(ix, p, qb, qbl, qn2, st);
-        case SCANN_HIP_ROWS_INT8: return launch_bf16_dims<SCANN_HIP_ROWS_INT8>(ix, p, qb, qbl, qn2, st);
-        default: return launch_bf16_dims<0>(ix, p, qb, qbl, qn2, st);
-    }
-}
-
-template <int FMT, int MEASURE>
-static void launch_quant_rerank(const BfIndexDev &ix, const float *d_queries, uint32_t q_stride, uint32_t kp,
-                                BfWorkspace &w, uint32_t nq, hipStream_t st) {
-    hipLaunchKernelGGL((bf_quant_rerank_kernel<FMT, MEASURE>), dim3(ceil_div_u32(kp, 256), nq), dim3(256),
-                       (size_t)ix.dim * 4, st, ix, d_queries, q_stride, kp, w.sl_idx.as<uint32_t>(),
-                       w.sl_cnt.as<uint32_t>(), w.sl_exact.as<float>());
+    return with_row_format(ix.fmt, [&](auto fmt) {
+        return with_dim16(ix.dim, [&](auto ts) { return launch_bf16<ts(), fmt()>(ix, p, qb, qbl, qn2, st); });
+    });
 }
 
 // exact re-score of the shortlist of quantized rows (SquaredL2 serves L2: the final kernel takes the root)
 template <int MEASURE>
 static int launch_rerank(const BfIndexDev &ix, const float *d_queries, uint32_t q_stride, uint32_t kp, BfWorkspace &w,
                          uint32_t nq, hipStream_t st) {
-    switch (ix.fmt) {
-        case SCANN_HIP_ROWS_BF16: launch_quant_rerank<SCANN_HIP_ROWS_BF16, MEASURE>(ix, d_queries, q_stride, kp, w, nq, st); break;
-        case SCANN_HIP_ROWS_FP8_E4M3:
-            launch_quant_rerank<SCANN_HIP_ROWS_FP8_E4M3, MEASURE>(ix, d_queries, q_stride, kp, w, nq, st);
-            break;
-        case SCANN_HIP_ROWS_INT8: launch_quant_rerank<SCANN_HIP_ROWS_INT8, MEASURE>(ix, d_queries, q_stride, kp, w, nq, st); break;
-        default:
-            hipLaunchKernelGGL(bf_rerank_kernel<MEASURE>, dim3(ceil_div_u32(kp, 32), nq), dim3(256), (size_t)ix.dim * 4, st,
-                               ix, d_queries, q_stride, kp, w.sl_idx.as<uint32_t>(), w.sl_cnt.as<uint32_t>(),
-                               w.sl_exact.as<float>());
-            break;
-    }
-    LAUNCH_CHECK();
-    return SCANN_HIP_OK;
+    return with_row_format(ix.fmt, [&](auto fmt) {
+        if constexpr (fmt() != 0)
+            return launch((bf_quant_rerank_kernel<fmt(), MEASURE>), dim3(ceil_div_u32(kp, 256), nq), dim3(256),
+                          (size_t)ix.dim * 4, st, ix, d_queries, q_stride, kp, w.sl_idx.as<uint32_t>(),
+                          w.sl_cnt.as<uint32_t>(), w.sl_exact.as<float>());
+        else
+            return launch(bf_rerank_kernel<MEASURE>, dim3(ceil_div_u32(kp, 32), nq), dim3(256), (size_t)ix.dim * 4, st,
+                          ix, d_queries, q_stride, kp, w.sl_idx.as<uint32_t>(), w.sl_cnt.as<uint32_t>(),
+                          w.sl_exact.as<float>());
+    });
 }
 
 // bf16 scores -> shortlist of kp rows -> exact re-score -> first k + verification
@@ -2180,9 +2036,8 @@ static int enqueue_shortlist_search(const BfIndexDev &ix, BfWorkspace &w, uint32
     SCANN_TRY(w.sl_cnt.ensure((size_t)nq * 4));
     SCANN_HIP_CHECK(hipMemsetAsync(w.counters.p, 0, BF_CNT_N * 4, st));
     SCANN_HIP_CHECK(hipMemsetAsync(w.cand_cnt.p, 0, (size_t)nq * 4, st));
-    hipLaunchKernelGGL(bf_q_prep_kernel, dim3(ceil_div_u32(nq, 4)), dim3(256), 0, st, d_queries, nq, ix.dim,
-                       q_stride, w.q_b.as<uint16_t>(), w.q_bl.as<uint16_t>(), w.q_n2.as<float>());
-    LAUNCH_CHECK();
+    SCANN_TRY(launch(bf_q_prep_kernel, dim3(ceil_div_u32(nq, 4)), dim3(256), 0, st, d_queries, nq, ix.dim,
+                     q_stride, w.q_b.as<uint16_t>(), w.q_bl.as<uint16_t>(), w.q_n2.as<float>()));
     // 1. bf16 scores of an evenly spaced sample -> bound of the kp-th best bf16 score
     BfPass a{};
     a.queries = d_queries;
@@ -2196,7 +2051,6 @@ static int enqueue_shortlist_search(const BfIndexDev &ix, BfWorkspace &w, uint32
     SCANN_TRY(launch_bf16_pass(ix, a, w.q_b.as<uint16_t>(), w.q_bl.as<uint16_t>(), w.q_n2.as<float>(), st));
     const SelCfg tcfg = sel_cfg(ns);
     const size_t lds_thr = (size_t)next_pow2_u32(ns) * 8 + (size_t)tcfg.bins * 4 + (size_t)tcfg.list * 8 + 48 * 8;
-    SCANN_TRY(set_dyn_lds(bf_threshold_kernel, lds_thr));
     // Sample rank of the filter bound.  The kp-th smallest sample score is a certain bound of the
     // kp-th smallest score overall but lets ~kp * rs rows through; the j-th smallest with
     // P(Poisson(kp / rs) >= j) <= 1e-6 -- the chance that j of the overall best kp fell into the
@@ -2212,10 +2066,9 @@ static int enqueue_shortlist_search(const BfIndexDev &ix, BfWorkspace &w, uint32
             cdf += term;
         }
     }
-    hipLaunchKernelGGL(bf_threshold_kernel, dim3(nq), dim3(kBfSelectThreads), lds_thr, st, w.sample.as<float>(),
-                       ns, rs, jthr, 0, w.thr.as<uint64_t>(), (uint32_t *)nullptr, (float *)nullptr,
-                       (uint32_t *)nullptr, (const uint32_t *)nullptr, (const uint64_t *)nullptr, 0u);
-    LAUNCH_CHECK();
+    SCANN_TRY(launch(bf_threshold_kernel, dim3(nq), dim3(kBfSelectThreads), lds_thr, st, w.sample.as<float>(),
+                     ns, rs, jthr, 0, w.thr.as<uint64_t>(), (uint32_t *)nullptr, (float *)nullptr,
+                     (uint32_t *)nullptr, (const uint32_t *)nullptr, (const uint64_t *)nullptr, 0u));
     // 2. bf16 scores of every row, filtered by that bound
     BfPass b = a;
     b.nrows = n;
@@ -2234,34 +2087,19 @@ static int enqueue_shortlist_search(const BfIndexDev &ix, BfWorkspace &w, uint32
     const SelCfg scfg = sel_cfg(kBfSortCap);
     const size_t lds_sel = (size_t)kBfSortCap * 8 + (kBfSelectThreads / 64 + 4) * 4 + (size_t)kBfMaxK * 8 +
                            (size_t)scfg.bins * 4 + (size_t)scfg.list * 8 + 48 * 8;
-    SCANN_TRY(set_dyn_lds(bf_select_kernel, lds_sel));
-    hipLaunchKernelGGL(bf_select_kernel, dim3(nq), dim3(kBfSelectThreads), lds_sel, st, kp, cap,
-                       w.cand_cnt.as<uint32_t>(), w.cand.as<uint64_t>(), w.counters.as<uint32_t>(),
-                       w.sl_idx.as<uint32_t>(), w.sl_approx.as<float>(), w.sl_cnt.as<uint32_t>());
-    LAUNCH_CHECK();
+    SCANN_TRY(launch(bf_select_kernel, dim3(nq), dim3(kBfSelectThreads), lds_sel, st, kp, cap,
+                     w.cand_cnt.as<uint32_t>(), w.cand.as<uint64_t>(), w.counters.as<uint32_t>(),
+                     w.sl_idx.as<uint32_t>(), w.sl_approx.as<float>(), w.sl_cnt.as<uint32_t>()));
     // 4. exact f32 score of the shortlist, 5. first k + verification
     const float err = ix.fmt ? shortlist_quant_err(ix.dim, ix.fmt) : shortlist_dot_err(ix.dim);
-    if (ix.measure == SCANN_HIP_DOT_PRODUCT) {
-        SCANN_TRY(launch_rerank<SCANN_HIP_DOT_PRODUCT>(ix, d_queries, q_stride, kp, w, nq, st));
-        hipLaunchKernelGGL(bf_shortlist_final_kernel<SCANN_HIP_DOT_PRODUCT>, dim3(nq), dim3(64), 0, st, n, k, kp,
-                           ix.max_norm, err, w.q_n2.as<float>(), w.thr.as<uint64_t>(), w.sl_idx.as<uint32_t>(), w.sl_approx.as<float>(),
-                           w.sl_cnt.as<uint32_t>(), w.sl_exact.as<float>(), w.counters.as<uint32_t>(),
-                           w.sl_fail.as<uint32_t>(), d_out_idx, d_out_dist, d_out_count);
-    } else {
-        SCANN_TRY(launch_rerank<SCANN_HIP_SQUARED_L2>(ix, d_queries, q_stride, kp, w, nq, st));
-        if (ix.measure == SCANN_HIP_L2)
-            hipLaunchKernelGGL(bf_shortlist_final_kernel<SCANN_HIP_L2>, dim3(nq), dim3(64), 0, st, n, k, kp,
-                               ix.max_norm, err, w.q_n2.as<float>(), w.thr.as<uint64_t>(), w.sl_idx.as<uint32_t>(), w.sl_approx.as<float>(),
-                               w.sl_cnt.as<uint32_t>(), w.sl_exact.as<float>(), w.counters.as<uint32_t>(),
-                               w.sl_fail.as<uint32_t>(), d_out_idx, d_out_dist, d_out_count);
-        else
-            hipLaunchKernelGGL(bf_shortlist_final_kernel<SCANN_HIP_SQUARED_L2>, dim3(nq), dim3(64), 0, st, n, k, kp,
-                               ix.max_norm, err, w.q_n2.as<float>(), w.thr.as<uint64_t>(), w.sl_idx.as<uint32_t>(), w.sl_approx.as<float>(),
-                               w.sl_cnt.as<uint32_t>(), w.sl_exact.as<float>(), w.counters.as<uint32_t>(),
-                               w.sl_fail.as<uint32_t>(), d_out_idx, d_out_dist, d_out_count);
-    }
-    LAUNCH_CHECK();
-    return SCANN_HIP_OK;
+    return with_value<SCANN_HIP_DOT_PRODUCT, SCANN_HIP_L2, SCANN_HIP_SQUARED_L2>(ix.measure, [&](auto m) {
+        constexpr int kRerank = m() == SCANN_HIP_DOT_PRODUCT ? SCANN_HIP_DOT_PRODUCT : SCANN_HIP_SQUARED_L2;
+        SCANN_TRY(launch_rerank<kRerank>(ix, d_queries, q_stride, kp, w, nq, st));
+        return launch(bf_shortlist_final_kernel<m()>, dim3(nq), dim3(64), 0, st, n, k, kp, ix.max_norm, err,
+                      w.q_n2.as<float>(), w.thr.as<uint64_t>(), w.sl_idx.as<uint32_t>(), w.sl_approx.as<float>(),
+                      w.sl_cnt.as<uint32_t>(), w.sl_exact.as<float>(), w.counters.as<uint32_t>(),
+                      w.sl_fail.as<uint32_t>(), d_out_idx, d_out_dist, d_out_count);
+    });
 }
 
 int bf_last_status(const BfWorkspace &w, hipStream_t st) {
@@ -2399,8 +2237,7 @@ int bf16_quantize_host(const float *values, uint64_t n, uint16_t *out_bits, hipS
     SCANN_TRY(upload(dv, values, (size_t)n * 4));
     SCANN_TRY(dout.ensure((size_t)n * 2));
     const uint32_t blocks = (uint32_t)std::min<uint64_t>(ceil_div_u64(n, 256), 65535);
-    hipLaunchKernelGGL(bf16_quantize_kernel, dim3(blocks), dim3(256), 0, st, dv.as<float>(), n, dout.as<uint16_t>());
-    LAUNCH_CHECK();
+    SCANN_TRY(launch(bf16_quantize_kernel, dim3(blocks), dim3(256), 0, st, dv.as<float>(), n, dout.as<uint16_t>()));
     SCANN_HIP_CHECK(hipMemcpyAsync(out_bits, dout.p, (size_t)n * 2, hipMemcpyDeviceToHost, st));
     SCANN_HIP_CHECK(hipStreamSynchronize(st));
     return SCANN_HIP_OK;
@@ -2499,9 +2336,8 @@ int bf_search_radius_host(const BfIndexDev &ix, BfWorkspace &w, const float *que
     if (nout == 0) return SCANN_HIP_OK;
     SCANN_TRY(didx.ensure((size_t)nout * 4));
     SCANN_TRY(ddist.ensure((size_t)nout * 4));
-    hipLaunchKernelGGL(bf_decode_keys_kernel, dim3(ceil_div_u32(nout, 256)), dim3(256), 0, st,
-                       dsorted.as<uint64_t>(), nout, didx.as<uint32_t>(), ddist.as<float>());
-    LAUNCH_CHECK();
+    SCANN_TRY(launch(bf_decode_keys_kernel, dim3(ceil_div_u32(nout, 256)), dim3(256), 0, st,
+                     dsorted.as<uint64_t>(), nout, didx.as<uint32_t>(), ddist.as<float>()));
     SCANN_HIP_CHECK(hipMemcpyAsync(out_idx, didx.p, (size_t)nout * 4, hipMemcpyDeviceToHost, st));
     SCANN_HIP_CHECK(hipMemcpyAsync(out_dist, ddist.p, (size_t)nout * 4, hipMemcpyDeviceToHost, st));
     SCANN_HIP_CHECK(hipStreamSynchronize(st));
@@ -2517,10 +2353,8 @@ int bf_assign_nearest_host(const BfIndexDev &ix, const float *centers, uint32_t 
     if (out_dist) SCANN_TRY(dd.ensure((size_t)ix.n * 4));
     const uint32_t dimp = (ix.dim + 3u) & ~3u;
     const size_t lds = (size_t)kAsgTC * dimp * sizeof(float);
-    SCANN_TRY(set_dyn_lds(assign_nearest_kernel, lds));
-    hipLaunchKernelGGL(assign_nearest_kernel, dim3((uint32_t)ceil_div_u64(ix.n, 256)), dim3(256), lds, st, ix,
-                       dc.as<float>(), k, di.as<uint32_t>(), out_dist ? dd.as<float>() : nullptr);
-    LAUNCH_CHECK();
+    SCANN_TRY(launch(assign_nearest_kernel, dim3((uint32_t)ceil_div_u64(ix.n, 256)), dim3(256), lds, st, ix,
+                     dc.as<float>(), k, di.as<uint32_t>(), out_dist ? dd.as<float>() : nullptr));
     SCANN_HIP_CHECK(hipMemcpyAsync(out_idx, di.p, (size_t)ix.n * 4, hipMemcpyDeviceToHost, st));
     if (out_dist) SCANN_HIP_CHECK(hipMemcpyAsync(out_dist, dd.p, (size_t)ix.n * 4, hipMemcpyDeviceToHost, st));
     SCANN_HIP_CHECK(hipStreamSynchronize(st));
@@ -2815,14 +2649,11 @@ static int km_launch_assign(const BfIndexDev &v, const float *d_centers, uint32_
     const dim3 grid((uint32_t)ceil_div_u64(v.n, 256));
     if (avx) {
         const size_t lds = (size_t)kAvxTC * dimp * sizeof(float);
-        SCANN_TRY(set_dyn_lds(assign_nearest_avx_kernel, lds));
-        hipLaunchKernelGGL(assign_nearest_avx_kernel, grid, dim3(256), lds, st, v, d_centers, k, d_assign, d_dist);
+        SCANN_TRY(launch(assign_nearest_avx_kernel, grid, dim3(256), lds, st, v, d_centers, k, d_assign, d_dist));
     } else {
         const size_t lds = (size_t)kAsgTC * dimp * sizeof(float);
-        SCANN_TRY(set_dyn_lds(assign_nearest_kernel, lds));
-        hipLaunchKernelGGL(assign_nearest_kernel, grid, dim3(256), lds, st, v, d_centers, k, d_assign, d_dist);
+        SCANN_TRY(launch(assign_nearest_kernel, grid, dim3(256), lds, st, v, d_centers, k, d_assign, d_dist));
     }
-    LAUNCH_CHECK();
     return SCANN_HIP_OK;
 }
 
@@ -2844,22 +2675,18 @@ int bf_kmeans_init_pp_host(const BfIndexDev &ix, uint32_t col_offset, uint32_t s
     SCANN_HIP_CHECK(hipMemcpyAsync(dpicks.p, &first, 4, hipMemcpyHostToDevice, st));
     for (uint32_t c = 1; c <= k; ++c) {
         uint32_t *sel = dpicks.as<uint32_t>() + (c - 1);
-        hipLaunchKernelGGL(km_mind_update_kernel, dim3(nb), dim3(256), 0, st, v, sel, c == 1 ? 1 : 0, avx,
-                           dmin.as<float>());
-        LAUNCH_CHECK();
+        SCANN_TRY(launch(km_mind_update_kernel, dim3(nb), dim3(256), 0, st, v, sel, c == 1 ? 1 : 0, avx,
+                         dmin.as<float>()));
         if (c == k) break;
-        hipLaunchKernelGGL(km_sum_f64_kernel, dim3(nb), dim3(256), 0, st, dmin.as<float>(), n,
-                           dpart.as<double>(), (uint32_t *)nullptr);
-        LAUNCH_CHECK();
+        SCANN_TRY(launch(km_sum_f64_kernel, dim3(nb), dim3(256), 0, st, dmin.as<float>(), n,
+                         dpart.as<double>(), (uint32_t *)nullptr));
         const double u = (double)(km_splitmix(s) >> 11) * (1.0 / 9007199254740992.0);
         const uint32_t fallback = (uint32_t)(km_splitmix(s) % n);
-        hipLaunchKernelGGL(km_total_pick_kernel, dim3(1), dim3(256), 0, st, dpart.as<double>(), nb,
-                           dmin.as<float>(), n, u, fallback, dtotal.as<double>(), dpicks.as<uint32_t>() + c);
-        LAUNCH_CHECK();
+        SCANN_TRY(launch(km_total_pick_kernel, dim3(1), dim3(256), 0, st, dpart.as<double>(), nb,
+                         dmin.as<float>(), n, u, fallback, dtotal.as<double>(), dpicks.as<uint32_t>() + c));
     }
-    hipLaunchKernelGGL(km_gather_rows_kernel, dim3(ceil_div_u32(k * sub_dim, 256)), dim3(256), 0, st, v,
-                       dpicks.as<uint32_t>(), k, dcent.as<float>());
-    LAUNCH_CHECK();
+    SCANN_TRY(launch(km_gather_rows_kernel, dim3(ceil_div_u32(k * sub_dim, 256)), dim3(256), 0, st, v,
+                     dpicks.as<uint32_t>(), k, dcent.as<float>()));
     SCANN_HIP_CHECK(hipMemcpyAsync(centers_out, dcent.p, (size_t)k * sub_dim * 4, hipMemcpyDeviceToHost, st));
     SCANN_HIP_CHECK(hipStreamSynchronize(st));
     return SCANN_HIP_OK;
@@ -2896,12 +2723,10 @@ int bf_kmeans_lloyd_host(const BfIndexDev &ix, uint32_t col_offset, uint32_t sub
         SCANN_TRY(km_launch_assign(v, dcent.as<float>(), k, dassign.as<uint32_t>(), ddist.as<float>(), avx, st));
         uint32_t *d_minpos = reinterpret_cast<uint32_t *>(dtotal.as<double>() + 1);
         SCANN_HIP_CHECK(hipMemsetAsync(d_minpos, 0xFF, 4, st));
-        hipLaunchKernelGGL(km_sum_f64_kernel, dim3(nb), dim3(256), 0, st, ddist.as<float>(), n,
-                           dpart.as<double>(), d_minpos);
-        LAUNCH_CHECK();
-        hipLaunchKernelGGL(km_total_pick_kernel, dim3(1), dim3(256), 0, st, dpart.as<double>(), nb,
-                           (const float *)nullptr, n, 0.0, 0u, dtotal.as<double>(), (uint32_t *)nullptr);
-        LAUNCH_CHECK();
+        SCANN_TRY(launch(km_sum_f64_kernel, dim3(nb), dim3(256), 0, st, ddist.as<float>(), n,
+                         dpart.as<double>(), d_minpos));
+        SCANN_TRY(launch(km_total_pick_kernel, dim3(1), dim3(256), 0, st, dpart.as<double>(), nb,
+                         (const float *)nullptr, n, 0.0, 0u, dtotal.as<double>(), (uint32_t *)nullptr));
         struct { double total; uint32_t minpos; uint32_t pad; } h;
         SCANN_HIP_CHECK(hipMemcpyAsync(&h, dtotal.p, 16, hipMemcpyDeviceToHost, st));
         SCANN_HIP_CHECK(hipStreamSynchronize(st));
@@ -2920,9 +2745,8 @@ int bf_kmeans_lloyd_host(const BfIndexDev &ix, uint32_t col_offset, uint32_t sub
             exact = h.total <= std::ldexp(1.0, ge + 53);
         }
         if (!exact) {
-            hipLaunchKernelGGL(km_sum_f64_sequential_kernel, dim3(1), dim3(256), 0, st, ddist.as<float>(), n,
-                               dtotal.as<double>());
-            LAUNCH_CHECK();
+            SCANN_TRY(launch(km_sum_f64_sequential_kernel, dim3(1), dim3(256), 0, st, ddist.as<float>(), n,
+                             dtotal.as<double>()));
             SCANN_HIP_CHECK(hipMemcpyAsync(&h.total, dtotal.p, 8, hipMemcpyDeviceToHost, st));
             SCANN_HIP_CHECK(hipStreamSynchronize(st));
         }
@@ -2943,20 +2767,16 @@ int bf_kmeans_lloyd_host(const BfIndexDev &ix, uint32_t col_offset, uint32_t sub
         }
         prev = inertia;
         // update_centers: members of every cluster in ascending datapoint order
-        hipLaunchKernelGGL(km_make_keys_kernel, dim3(nb), dim3(256), 0, st, dassign.as<uint32_t>(), n,
-                           dkeys.as<uint64_t>());
-        LAUNCH_CHECK();
+        SCANN_TRY(launch(km_make_keys_kernel, dim3(nb), dim3(256), 0, st, dassign.as<uint32_t>(), n,
+                         dkeys.as<uint64_t>()));
         SCANN_HIP_CHECK(hipcub::DeviceRadixSort::SortKeys(dtmp.p, tmp_bytes, dkeys.as<uint64_t>(),
                                                           dsorted.as<uint64_t>(), (int)n, 0, key_bits, st));
-        hipLaunchKernelGGL(km_offsets_kernel, dim3(ceil_div_u32(k + 1, 256)), dim3(256), 0, st,
-                           dsorted.as<uint64_t>(), n, k, doff.as<uint32_t>());
-        LAUNCH_CHECK();
-        hipLaunchKernelGGL(km_gather_sorted_kernel, dim3((uint32_t)ceil_div_u64(n * sub_dim, 256)), dim3(256), 0,
-                           st, v, dsorted.as<uint64_t>(), n, dgrows.as<float>());
-        LAUNCH_CHECK();
-        hipLaunchKernelGGL(km_update_kernel, dim3(k), dim3(256), 0, st, v, dgrows.as<float>(),
-                           doff.as<uint32_t>(), dcent.as<float>());
-        LAUNCH_CHECK();
+        SCANN_TRY(launch(km_offsets_kernel, dim3(ceil_div_u32(k + 1, 256)), dim3(256), 0, st,
+                         dsorted.as<uint64_t>(), n, k, doff.as<uint32_t>()));
+        SCANN_TRY(launch(km_gather_sorted_kernel, dim3((uint32_t)ceil_div_u64(n * sub_dim, 256)), dim3(256), 0,
+                         st, v, dsorted.as<uint64_t>(), n, dgrows.as<float>()));
+        SCANN_TRY(launch(km_update_kernel, dim3(k), dim3(256), 0, st, v, dgrows.as<float>(),
+                         doff.as<uint32_t>(), dcent.as<float>()));
     }
     // final assignment for accurate sizes / inertia (kmeans.rs:248-255)
     SCANN_TRY(assign_and_inertia(&inertia));

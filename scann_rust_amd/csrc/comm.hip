@@ -23,6 +23,7 @@
 #include "comm.h"
 #include "common.h"
 #include "knobs.h"
+#include "launch.h"
 #include "txh.h"
 
 namespace scann {
@@ -365,16 +366,14 @@ int scann_hip_txh_search_sharded_device(scann_hip_index *index, scann_hip_comm *
     unsigned char *snd = c->send[b].as<unsigned char>(), *rcv = c->recv[b].as<unsigned char>();
     {
         const uint32_t *cnt = reinterpret_cast<const uint32_t *>(soa + L.soa_count);
-        hipLaunchKernelGGL(comm_offsets_kernel, dim3(world), dim3(256), 0, S, nq, L.qr, m_local, L.cap, cnt,
-                           c->soff[b].as<uint32_t>(), snd, L.block_bytes, L.blk_flag);
-        if (hipGetLastError() != hipSuccess) return fail(SCANN_HIP_INTERNAL, "offsets kernel launch failed");
+        SCANN_TRY(launch(comm_offsets_kernel, dim3(world), dim3(256), 0, S, nq, L.qr, m_local, L.cap, cnt,
+                         c->soff[b].as<uint32_t>(), snd, L.block_bytes, L.blk_flag));
         const uint64_t work = (uint64_t)nq * m_local;
-        hipLaunchKernelGGL(comm_pack_kernel, dim3((uint32_t)ceil_div_u64(work, 256)), dim3(256), 0, S, nq, L.qr,
-                           m_local, L.cap, reinterpret_cast<const uint64_t *>(soa),
-                           reinterpret_cast<const uint32_t *>(soa + L.soa_idx),
-                           reinterpret_cast<const float *>(soa + L.soa_exact), cnt, c->soff[b].as<uint32_t>(), snd,
-                           L.block_bytes, L.blk_keys, L.blk_idx, L.blk_exact);
-        if (hipGetLastError() != hipSuccess) return fail(SCANN_HIP_INTERNAL, "pack kernel launch failed");
+        SCANN_TRY(launch(comm_pack_kernel, dim3((uint32_t)ceil_div_u64(work, 256)), dim3(256), 0, S, nq, L.qr,
+                         m_local, L.cap, reinterpret_cast<const uint64_t *>(soa),
+                         reinterpret_cast<const uint32_t *>(soa + L.soa_idx),
+                         reinterpret_cast<const float *>(soa + L.soa_exact), cnt, c->soff[b].as<uint32_t>(), snd,
+                         L.block_bytes, L.blk_keys, L.blk_idx, L.blk_exact));
     }
     SCANN_HIP_CHECK(hipEventRecord(c->ev_packed[b], S));
 
@@ -406,9 +405,8 @@ int scann_hip_txh_search_sharded_device(scann_hip_index *index, scann_hip_comm *
         note(r->GroupEnd(), "ncclGroupEnd");   // (always: also after a failed Send / Recv)
     }
     if (first != ncclSuccess) return fail(SCANN_HIP_INTERNAL, std::string(where) + ": " + r->GetErrorString(first));
-    hipLaunchKernelGGL(comm_recv_offsets_kernel, dim3(world), dim3(256), 0, C, L.qr, rcv, L.block_bytes, L.blk_flag,
-                       c->roff[b].as<uint32_t>(), r_status + rank);
-    if (hipGetLastError() != hipSuccess) return fail(SCANN_HIP_INTERNAL, "receive offsets kernel launch failed");
+    SCANN_TRY(launch(comm_recv_offsets_kernel, dim3(world), dim3(256), 0, C, L.qr, rcv, L.block_bytes, L.blk_flag,
+                     c->roff[b].as<uint32_t>(), r_status + rank));
     int ms = txh_launch_merge(world, L.qr, m_local, m, k, (size_t)L.block_bytes,
                               reinterpret_cast<const uint64_t *>(rcv + L.blk_keys),
                               reinterpret_cast<const uint32_t *>(rcv + L.blk_idx),
@@ -427,8 +425,7 @@ int scann_hip_txh_search_sharded_device(scann_hip_index *index, scann_hip_comm *
     }
     if (first != ncclSuccess) return fail(SCANN_HIP_INTERNAL, std::string(where) + ": " + r->GetErrorString(first));
     if (ms != SCANN_HIP_OK) return ms;
-    hipLaunchKernelGGL(comm_status_kernel, dim3(1), dim3(1), 0, C, world, r_status, c->status.as<uint32_t>());
-    if (hipGetLastError() != hipSuccess) return fail(SCANN_HIP_INTERNAL, "status kernel launch failed");
+    SCANN_TRY(launch(comm_status_kernel, dim3(1), dim3(1), 0, C, world, r_status, c->status.as<uint32_t>()));
     SCANN_HIP_CHECK(hipMemcpyAsync(d_out_idx, r_idx, (size_t)nq * k * 4, hipMemcpyDeviceToDevice, C));
     SCANN_HIP_CHECK(hipMemcpyAsync(d_out_dist, r_dist, (size_t)nq * k * 4, hipMemcpyDeviceToDevice, C));
     SCANN_HIP_CHECK(hipMemcpyAsync(d_out_count, r_cnt, (size_t)nq * 4, hipMemcpyDeviceToDevice, C));

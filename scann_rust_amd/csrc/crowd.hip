@@ -27,6 +27,7 @@
 #include <string>
 
 #include "crowd.h"
+#include "launch.h"
 
 namespace scann {
 
@@ -171,15 +172,8 @@ int crowd_launch(const uint32_t *rows_idx, const float *rows_dist, const uint32_
     if (!attrs) n_attrs = 0;
     const uint32_t slots = crowd_table_slots(depth);
     const size_t lds = (size_t)slots * 12;
-    // (always the CU's 160 KB, never this launch's own size: concurrent callers set the attribute side by side)
-    if (lds > 64 * 1024)
-        SCANN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(crowd_kernel),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    hipLaunchKernelGGL(crowd_kernel, dim3(nq), dim3(64), lds, st, rows_idx, rows_dist, rows_cnt, depth, attrs, n_attrs,
-                       k, limit, slots, out_idx, out_dist, out_cnt);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(SCANN_HIP_INTERNAL, std::string("kernel launch: ") + hipGetErrorString(e));
-    return SCANN_HIP_OK;
+    return launch(crowd_kernel, dim3(nq), dim3(64), lds, st, rows_idx, rows_dist, rows_cnt, depth, attrs, n_attrs, k, limit,
+                  slots, out_idx, out_dist, out_cnt);
 }
 
 }  // namespace scann

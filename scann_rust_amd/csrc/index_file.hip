@@ -14,6 +14,7 @@
 
 #include "common.h"
 #include "knobs.h"
+#include "launch.h"
 
 namespace {
 
@@ -275,7 +276,7 @@ int scann_hip_index_load_file(scann_hip_ctx *ctx, const char *path, scann_hip_in
     // that cannot pin a read-only file mapping leaves the (staged) pageable copy path.
     if (scann::read_knobs().load_pin) {
         if (hipHostRegister(m.base, m.bytes, hipHostRegisterReadOnly) == hipSuccess) m.pinned = true;
-        else (void)hipGetLastError();
+        else scann::clear_last_hip_error();
     }
     const void *p = nullptr;
     if (h.kind == 0) {

@@ -13,6 +13,7 @@
 // the reference uses _mm256_fmadd_ps.
 #include <type_traits>
 
+#include "launch.h"
 #include "txh.h"
 
 namespace scann {
@@ -677,6 +678,29 @@ struct Codec {
     }
 };
 
+// One item of the tile queue of the queue-driven scan kernels.  leaf: the largest l with tile_off[l] <= tile; its points
+// are [lb, lb + size) and its (query, leaf) pairs the slots [slot0, slot_end); local: the item's number inside the leaf,
+// from which every kernel derives its own chunk / range and quad numbers.  All wave-uniform (scalar loads).
+struct WorkItem {
+    uint32_t leaf, lb, size, local, slot0, slot_end;
+};
+__device__ __forceinline__ WorkItem decode_item(const TxhIndexDev &ix, const uint32_t *tile_off, const uint32_t *pair_off,
+                                                uint32_t tile) {
+    uint32_t lo = 0, hi = ix.L;
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (uniform_load(tile_off + mid) <= tile) lo = mid; else hi = mid;
+    }
+    WorkItem w;
+    w.leaf = lo;
+    w.lb = uniform_load(ix.leaf_off + lo);
+    w.size = uniform_load(ix.leaf_off + lo + 1) - w.lb;
+    w.local = tile - uniform_load(tile_off + lo);
+    w.slot0 = uniform_load(pair_off + lo);
+    w.slot_end = uniform_load(pair_off + lo + 1);
+    return w;
+}
+
 // Points G .. G+NP-1 of the lane against the quad's tables.
 template <typename C, int NP, int BUF, int G>
 __device__ __forceinline__ void scan_quad_compute(const float4 *lut_base,
@@ -806,20 +830,11 @@ __global__ __launch_bounds__(kScanThreads, C::WGS) void adc_scan_kernel(TxhIndex
         const uint32_t tile = __builtin_amdgcn_readfirstlane(tile_sh);
         if (tile == kInvalid) break;
 
-        // leaf = largest l with tile_off[l] <= tile
-        uint32_t lo = 0, hi = ix.L;
-        while (hi - lo > 1) {
-            uint32_t mid = (lo + hi) >> 1;
-            if (uniform_load(a.tile_off + mid) <= tile) lo = mid; else hi = mid;
-        }
-        const uint32_t leaf = lo;
-        const uint32_t lb = uniform_load(ix.leaf_off + leaf);
-        const uint32_t size = uniform_load(ix.leaf_off + leaf + 1) - lb;
+        const WorkItem item = decode_item(ix, a.tile_off, a.pair_off, tile);
+        const uint32_t lb = item.lb, size = item.size, local = item.local, slot0 = item.slot0, slot_end = item.slot_end;
         const uint32_t nchunks = (size + (uint32_t)C::TP - 1) / (uint32_t)C::TP;
-        const uint32_t local = tile - uniform_load(a.tile_off + leaf);
         const uint32_t chunk = local % nchunks, qg = local / nchunks;
-        const uint32_t slot0 = uniform_load(a.pair_off + leaf);
-        const uint32_t nquads = (uniform_load(a.pair_off + leaf + 1) - slot0) >> 2;
+        const uint32_t nquads = (slot_end - slot0) >> 2;
         const uint32_t q0 = qg * a.qpt;
         const uint32_t q1 = min(q0 + a.qpt, nquads);
         const uint32_t c0 = chunk * (uint32_t)C::TP;
@@ -1001,20 +1016,12 @@ __global__ __launch_bounds__(kResThreads, 6) void adc_scan_res_kernel(TxhIndexDe
         const uint32_t tile = __builtin_amdgcn_readfirstlane(tile_sh);
         if (tile == kInvalid) break;
 
-        uint32_t lo = 0, hi = ix.L;            // leaf = largest l with tile_off[l] <= tile
-        while (hi - lo > 1) {
-            uint32_t mid = (lo + hi) >> 1;
-            if (uniform_load(a.tile_off + mid) <= tile) lo = mid; else hi = mid;
-        }
-        const uint32_t leaf = lo;
-        const uint32_t lb = uniform_load(ix.leaf_off + leaf);
-        const uint32_t size = uniform_load(ix.leaf_off + leaf + 1) - lb;
+        const WorkItem item = decode_item(ix, a.tile_off, a.pair_off, tile);
+        const uint32_t lb = item.lb, size = item.size, local = item.local, slot0 = item.slot0, slot_end = item.slot_end;
         const uint32_t nchunks = (size + TPR - 1) / TPR;
         const uint32_t nranges = (nchunks + a.res_cl - 1) / a.res_cl;
-        const uint32_t local = tile - uniform_load(a.tile_off + leaf);
         const uint32_t range = local % nranges, qg = local / nranges;
-        const uint32_t slot0 = uniform_load(a.pair_off + leaf);
-        const uint32_t nquads = (uniform_load(a.pair_off + leaf + 1) - slot0) >> 2;
+        const uint32_t nquads = (slot_end - slot0) >> 2;
         const uint32_t q0 = qg * kResQuads;
         const uint32_t nq_t = min(kResQuads, nquads - q0);       // resident quads of this tile
         const uint32_t c_begin = range * a.res_cl, c_end = min(nchunks, c_begin + a.res_cl);
@@ -1343,6 +1350,27 @@ __device__ __forceinline__ uint32_t mask_allowed(const TxhIndexDev &ix, const ui
     return keep;
 }
 
+// Appends one prefilter survivor to query q's list: slot `dst` takes the stream position `pos` and, where the list
+// carries packed codes (cand32_codes: wave-uniform), the point's code words, read from its row `codes` of ix.codes.  A
+// slot past cap32 is dropped: the query's count still passes cap32, and adc_refine_kernel reports the overflow.
+template <int S>
+__device__ __forceinline__ void append_survivor(uint32_t *cand32, uint32_t *cand32_codes, uint32_t cap32, uint32_t q,
+                                                uint32_t dst, uint32_t pos, const uint32_t *codes) {
+    constexpr int NW = Codec<S, 4>::NWORDS;
+    if (dst < cap32) {
+        const size_t o = (size_t)q * cap32 + dst;
+        cand32[o] = pos;
+        if (cand32_codes) {
+            uint32_t cw[NW];
+            Codec<S, 4>::load_words(codes, cw);
+            Codec<S, 4>::store_words(cand32_codes + o * NW, cw);
+        }
+    }
+}
+// (The copy-outs of sp_flush_item_lanes / sp_flush_item_words write the same record from code words they loaded ahead,
+// kSpU points at a time, in the plane form of ix.codes_sp; they keep their own lines: through a shared helper
+// adc_smfmac_kernel<48, false> spilled two more VGPRs.)
+
 template <int S_>
 __global__ __launch_bounds__(kMfmaWaves * 64, (S_ <= 32 ? SCANN_MFMA_MINW : 2)) void adc_mfma_kernel(TxhIndexDev ix, MfmaArgs a) {
     typedef int v4i __attribute__((ext_vector_type(4)));
@@ -1370,19 +1398,10 @@ __global__ __launch_bounds__(kMfmaWaves * 64, (S_ <= 32 ? SCANN_MFMA_MINW : 2)) 
         // the next item's queue atomic travels while this item is computed
         uint32_t next_tile = 0;
         if (lane == 0) next_tile = grab_tile(a.counters + CNT_XQ, total_tiles);
-        uint32_t lo = 0, hi = ix.L;            // leaf = largest l with tile_off[l] <= tile
-        while (hi - lo > 1) {
-            const uint32_t mid = (lo + hi) >> 1;
-            if (uniform_load(a.tile_off + mid) <= tile) lo = mid; else hi = mid;
-        }
-        const uint32_t leaf = lo;
-        const uint32_t lb = uniform_load(ix.leaf_off + leaf);
-        const uint32_t size = uniform_load(ix.leaf_off + leaf + 1) - lb;
+        const WorkItem item = decode_item(ix, a.tile_off, a.pair_off, tile);
+        const uint32_t lb = item.lb, size = item.size, local = item.local, slot0 = item.slot0, slot_end = item.slot_end;
         const uint32_t nranges = (size + kMfmaRange - 1) / kMfmaRange;
-        const uint32_t local = tile - uniform_load(a.tile_off + leaf);
         const uint32_t range = local % nranges, pt = local / nranges;
-        const uint32_t slot0 = uniform_load(a.pair_off + leaf);
-        const uint32_t slot_end = uniform_load(a.pair_off + leaf + 1);
         const uint32_t c0 = range * kMfmaRange;
         const uint32_t npts = min(kMfmaRange, size - c0);
 
@@ -1452,15 +1471,7 @@ __global__ __launch_bounds__(kMfmaWaves * 64, (S_ <= 32 ? SCANN_MFMA_MINW : 2)) 
                 const uint32_t idx = e - s_fpre[wave][c];
                 const uint32_t j = s_stage[wave][c][idx];
                 const uint32_t dst = s_fgb[wave][c] + idx;
-                if (dst < a.cap32) {
-                    const size_t o = (size_t)s_fq[wave][c] * a.cap32 + dst;
-                    a.cand32[o] = s_fvb[wave][c] + j;
-                    if (a.cand32_codes) {   // (wave-uniform)
-                        uint32_t cw[NW];
-                        Codec<S, 4>::load_words(ix.codes + (size_t)(lb + j) * NW, cw);
-                        Codec<S, 4>::store_words(a.cand32_codes + o * NW, cw);
-                    }
-                }
+                append_survivor<S>(a.cand32, a.cand32_codes, a.cap32, s_fq[wave][c], dst, s_fvb[wave][c] + j, ix.codes + (size_t)(lb + j) * NW);
             }
         };
         auto step = [&](v16i &accN, const v16i &accO, uint32_t t) {
@@ -1524,15 +1535,7 @@ __global__ __launch_bounds__(kMfmaWaves * 64, (S_ <= 32 ? SCANN_MFMA_MINW : 2)) 
                         s_stage[wave][col][sl] = j;
                     } else {   // stage full: direct (slow) append
                         const uint32_t pos = atomicAdd(&a.cand32_cnt[pq], 1u);
-                        if (pos < a.cap32) {
-                            const size_t o = (size_t)pq * a.cap32 + pos;
-                            a.cand32[o] = vb + j;
-                            if (a.cand32_codes) {
-                                uint32_t cw[NW];
-                                Codec<S, 4>::load_words(ix.codes + (size_t)(lb + j) * NW, cw);
-                                Codec<S, 4>::store_words(a.cand32_codes + o * NW, cw);
-                            }
-                        }
+                        append_survivor<S>(a.cand32, a.cand32_codes, a.cap32, pq, pos, vb + j, ix.codes + (size_t)(lb + j) * NW);
                     }
                     ++sl;
                 } while (m16);
@@ -1929,19 +1932,10 @@ __device__ __forceinline__ void adc_smfmac_body(const TxhIndexDev &ix, const Mfm
     while (tile != kInvalid) {
         uint32_t next_tile = 0;
         if (lane == 0) next_tile = grab_tile(a.counters + CNT_XQ, total_tiles);
-        uint32_t lo = 0, hi = ix.L;            // leaf = largest l with tile_off[l] <= tile
-        while (hi - lo > 1) {
-            const uint32_t mid = (lo + hi) >> 1;
-            if (uniform_load(a.tile_off + mid) <= tile) lo = mid; else hi = mid;
-        }
-        const uint32_t leaf = lo;
-        const uint32_t lb = uniform_load(ix.leaf_off + leaf);
-        const uint32_t size = uniform_load(ix.leaf_off + leaf + 1) - lb;
+        const WorkItem item = decode_item(ix, a.tile_off, a.pair_off, tile);
+        const uint32_t lb = item.lb, size = item.size, local = item.local, slot0 = item.slot0, slot_end = item.slot_end;
         const uint32_t nranges = (size + kMfmaRange - 1) / kMfmaRange;
-        const uint32_t local = tile - uniform_load(a.tile_off + leaf);
         const uint32_t range = local % nranges, pt = local / nranges;
-        const uint32_t slot0 = uniform_load(a.pair_off + leaf);
-        const uint32_t slot_end = uniform_load(a.pair_off + leaf + 1);
         const uint32_t c0 = range * kMfmaRange;
         const uint32_t npts = min(kMfmaRange, size - c0);
 
@@ -2146,19 +2140,10 @@ __global__ __launch_bounds__(kMfmaWaves * 64, (S_ <= 32 ? 4 : 2)) void adc_mfma1
     while (tile != kInvalid) {
         uint32_t next_tile = 0;
         if (lane == 0) next_tile = grab_tile(a.counters + CNT_XQ, total_tiles);
-        uint32_t lo = 0, hi = ix.L;
-        while (hi - lo > 1) {
-            const uint32_t mid = (lo + hi) >> 1;
-            if (uniform_load(a.tile_off + mid) <= tile) lo = mid; else hi = mid;
-        }
-        const uint32_t leaf = lo;
-        const uint32_t lb = uniform_load(ix.leaf_off + leaf);
-        const uint32_t size = uniform_load(ix.leaf_off + leaf + 1) - lb;
+        const WorkItem item = decode_item(ix, a.tile_off, a.pair_off, tile);
+        const uint32_t lb = item.lb, size = item.size, local = item.local, slot0 = item.slot0, slot_end = item.slot_end;
         const uint32_t nranges = (size + kMfmaRange - 1) / kMfmaRange;
-        const uint32_t local = tile - uniform_load(a.tile_off + leaf);
         const uint32_t range = local % nranges, pt = local / nranges;
-        const uint32_t slot0 = uniform_load(a.pair_off + leaf);
-        const uint32_t slot_end = uniform_load(a.pair_off + leaf + 1);
         const uint32_t c0 = range * kMfmaRange;
         const uint32_t npts = min(kMfmaRange, size - c0);
 
@@ -2215,15 +2200,7 @@ __global__ __launch_bounds__(kMfmaWaves * 64, (S_ <= 32 ? 4 : 2)) void adc_mfma1
                 const uint32_t idx = e - s_fpre[wave][c];
                 const uint32_t j = s_stage[wave][c][idx];
                 const uint32_t dst = s_fgb[wave][c] + idx;
-                if (dst < a.cap32) {
-                    const size_t o = (size_t)s_fq[wave][c] * a.cap32 + dst;
-                    a.cand32[o] = s_fvb[wave][c] + j;
-                    if (a.cand32_codes) {
-                        uint32_t cw[NW];
-                        Codec<S, 4>::load_words(ix.codes + (size_t)(lb + j) * NW, cw);
-                        Codec<S, 4>::store_words(a.cand32_codes + o * NW, cw);
-                    }
-                }
+                append_survivor<S>(a.cand32, a.cand32_codes, a.cap32, s_fq[wave][c], dst, s_fvb[wave][c] + j, ix.codes + (size_t)(lb + j) * NW);
             }
         };
         // step(t): the MFMAs of tile t into accN, the survivor mask of tile t - 1 from accO between them, then
@@ -2299,15 +2276,7 @@ __global__ __launch_bounds__(kMfmaWaves * 64, (S_ <= 32 ? 4 : 2)) void adc_mfma1
                     } else {   // stage full: direct (slow) append
                         const uint32_t pqd = s_fq[wave][c16];
                         const uint32_t pos = atomicAdd(&a.cand32_cnt[pqd], 1u);
-                        if (pos < a.cap32) {
-                            const size_t o = (size_t)pqd * a.cap32 + pos;
-                            a.cand32[o] = s_fvb[wave][c16] + j;
-                            if (a.cand32_codes) {
-                                uint32_t cw[NW];
-                                Codec<S, 4>::load_words(ix.codes + (size_t)(lb + j) * NW, cw);
-                                Codec<S, 4>::store_words(a.cand32_codes + o * NW, cw);
-                            }
-                        }
+                        append_survivor<S>(a.cand32, a.cand32_codes, a.cap32, pqd, pos, s_fvb[wave][c16] + j, ix.codes + (size_t)(lb + j) * NW);
                     }
                     ++sl;
                 } while (m8);
@@ -2565,20 +2534,12 @@ __global__ __launch_bounds__(kScanThreads, C::WGS) void adc_sample_kernel(TxhInd
         const uint32_t tile = __builtin_amdgcn_readfirstlane(tile_sh);
         if (tile == kInvalid) break;
 
-        uint32_t lo = 0, hi = ix.L;   // leaf = largest l with stile_off[l] <= tile
-        while (hi - lo > 1) {
-            uint32_t mid = (lo + hi) >> 1;
-            if (a.stile_off[mid] <= tile) lo = mid; else hi = mid;
-        }
-        const uint32_t leaf = lo;
-        const uint32_t lb = ix.leaf_off[leaf];
-        const uint32_t size = ix.leaf_off[leaf + 1] - lb;
+        const WorkItem item = decode_item(ix, a.stile_off, a.pair_off, tile);
+        const uint32_t lb = item.lb, size = item.size, local = item.local, slot0 = item.slot0, slot_end = item.slot_end;
         const uint32_t ssize = (size + st - 1) / st;            // sampled points of the leaf
         const uint32_t nchunks = (ssize + (uint32_t)C::TP - 1) / (uint32_t)C::TP;
-        const uint32_t local = tile - a.stile_off[leaf];
         const uint32_t chunk = local % nchunks, qg = local / nchunks;
-        const uint32_t slot0 = a.pair_off[leaf];
-        const uint32_t nquads = (a.pair_off[leaf + 1] - slot0) >> 2;
+        const uint32_t nquads = (slot_end - slot0) >> 2;
         const uint32_t q0 = qg * a.qpt;
         const uint32_t q1 = min(q0 + a.qpt, nquads);
         const uint32_t c0 = chunk * (uint32_t)C::TP;
@@ -2936,19 +2897,10 @@ __global__ __launch_bounds__(256) void leaf_exact_scan_kernel(TxhIndexDev ix, Ex
         __syncthreads();
         const uint32_t tile = __builtin_amdgcn_readfirstlane(tile_sh);
         if (tile == kInvalid) break;
-        uint32_t lo = 0, hi = ix.L;   // leaf = largest l with tile_off[l] <= tile
-        while (hi - lo > 1) {
-            const uint32_t mid = (lo + hi) >> 1;
-            if (uniform_load(a.tile_off + mid) <= tile) lo = mid; else hi = mid;
-        }
-        const uint32_t leaf = lo;
-        const uint32_t lb = uniform_load(ix.leaf_off + leaf);
-        const uint32_t size = uniform_load(ix.leaf_off + leaf + 1) - lb;
+        const WorkItem item = decode_item(ix, a.tile_off, a.pair_off, tile);
+        const uint32_t lb = item.lb, size = item.size, local = item.local, slot0 = item.slot0, slot_end = item.slot_end;
         const uint32_t nchunks = (size + kExactRows - 1) / kExactRows;
-        const uint32_t local = tile - uniform_load(a.tile_off + leaf);
         const uint32_t chunk = local % nchunks, qg = local / nchunks;
-        const uint32_t slot0 = uniform_load(a.pair_off + leaf);
-        const uint32_t slot_end = uniform_load(a.pair_off + leaf + 1);
         const uint32_t s_begin = slot0 + qg * a.qpt * 4u;
         const uint32_t s_stop = min(s_begin + a.qpt * 4u, slot_end);
         const uint32_t j = chunk * kExactRows + tid;
@@ -4814,73 +4766,29 @@ __global__ __launch_bounds__(256) void encode_kernel(
 // =====================================================================================
 // launchers
 // =====================================================================================
-#define LAUNCH_CHECK()                                                                \
-    do {                                                                              \
-        hipError_t _e = hipGetLastError();                                            \
-        if (_e != hipSuccess)                                                         \
-            return fail(SCANN_HIP_INTERNAL, std::string("kernel launch: ") + hipGetErrorString(_e)); \
-    } while (0)
-
-template <typename F>
-static int set_dyn_lds(F kernel, size_t bytes) {
-    // Always the same value (the CU's 160 KB), never the launch's own size: threads searching
-    // different indexes set this attribute concurrently, and a smaller value written by one of
-    // them must not undercut another's launch.
-    constexpr size_t kMaxLds = 160 * 1024;
-    if (bytes > kMaxLds) return fail(SCANN_HIP_RESOURCE_EXHAUSTED, "kernel needs more than 160 KB of LDS");
-    if (bytes > 64 * 1024)
-        SCANN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds));
-    return SCANN_HIP_OK;
-}
-
-// The same for a kernel that also holds `static_bytes` of static LDS arrays: the attribute bounds the DYNAMIC part, and
-// static + dynamic may not exceed the CU's 160 KB (again one constant per kernel).
-template <typename F>
-static int set_dyn_lds_with_static(F kernel, size_t bytes, size_t static_bytes) {
-    constexpr size_t kMaxLds = 160 * 1024;
-    if (bytes + static_bytes > kMaxLds) return fail(SCANN_HIP_RESOURCE_EXHAUSTED, "kernel needs more than 160 KB of LDS");
-    if (bytes > 64 * 1024)   // (the attribute bounds static + dynamic: 160 KB for a kernel with static arrays is refused)
-        SCANN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            (int)(kMaxLds - static_bytes)));
-    return SCANN_HIP_OK;
-}
-
 static int launch_partition_stage(const TxhIndexDev &ix, const TxhWork &w, hipStream_t st) {
     if (ix.ah_mode) {
-        hipLaunchKernelGGL(ah_tokens_kernel, dim3(ceil_div_u32(w.nq, 256)), dim3(256), 0, st, w.nq,
-                           ix.leaf_gsize, ix.leaf_off, w.st, w.tokens, w.token_dists, w.vbase, w.sbase);
-        LAUNCH_CHECK();
+        SCANN_TRY(launch(ah_tokens_kernel, dim3(ceil_div_u32(w.nq, 256)), dim3(256), 0, st, w.nq,
+                         ix.leaf_gsize, ix.leaf_off, w.st, w.tokens, w.token_dists, w.vbase, w.sbase));
         return SCANN_HIP_OK;
     }
     // queries per single-wave block: fewer when the grid would not fill the chip (one thread per
     // centroid, so a block's work is 64 centroids x QT queries)
     const uint64_t waves16 = (uint64_t)ceil_div_u32(ix.L, 64) * ceil_div_u32(w.nq, 16);
-    if (waves16 >= 8192) {
-        const size_t lds1 = (size_t)16 * ix.dim * sizeof(float);
-        SCANN_TRY(set_dyn_lds(centroid_scores_kernel<16>, lds1));
-        hipLaunchKernelGGL(centroid_scores_kernel<16>, dim3(ceil_div_u32(ix.L, 64), ceil_div_u32(w.nq, 16)),
-                           dim3(64), lds1, st, ix.centers, ix.L, ix.dim, w.queries, w.nq, w.q_stride,
-                           w.cdist);
-    } else {
-        const size_t lds1 = (size_t)4 * ix.dim * sizeof(float);
-        SCANN_TRY(set_dyn_lds(centroid_scores_kernel<4>, lds1));
-        hipLaunchKernelGGL(centroid_scores_kernel<4>, dim3(ceil_div_u32(ix.L, 64), ceil_div_u32(w.nq, 4)),
-                           dim3(64), lds1, st, ix.centers, ix.L, ix.dim, w.queries, w.nq, w.q_stride,
-                           w.cdist);
-    }
-    LAUNCH_CHECK();
+    SCANN_TRY((with_value<16, 4>(waves16 >= 8192 ? 16 : 4, [&](auto qt) {
+        const size_t lds1 = (size_t)qt() * ix.dim * sizeof(float);
+        return launch(centroid_scores_kernel<qt()>, dim3(ceil_div_u32(ix.L, 64), ceil_div_u32(w.nq, qt())), dim3(64), lds1,
+                      st, ix.centers, ix.L, ix.dim, w.queries, w.nq, w.q_stride, w.cdist);
+    })));
     const uint32_t n2 = next_pow2_u32(ix.L);
     // select path when P is small against L: rank-select the P-th key, sort P keys instead of L
     const uint32_t p2 = (w.P * 4u <= n2) ? next_pow2_u32(std::max(1u, w.P)) : 0u;
     const SelCfg lcfg = sel_cfg(ix.L);
     const size_t lds2 = (size_t)(n2 + p2) * sizeof(uint64_t) + (size_t)lcfg.bins * 4 + (size_t)lcfg.list * 8 +
                         48 * 8 + 64 * 4;
-    SCANN_TRY(set_dyn_lds(select_leaves_kernel, lds2));
-    hipLaunchKernelGGL(select_leaves_kernel, dim3(w.nq), dim3(p2 && ix.L <= 4096 ? 256u : kSelectThreads), lds2, st,
-                       w.cdist, ix.L, n2, w.P, p2, ix.leaf_gsize, ix.leaf_off, w.st, w.tokens, w.token_dists,
-                       w.vbase, w.sbase, (const float *)nullptr, (const float *)nullptr, 0u, 0u, 0u);
-    LAUNCH_CHECK();
+    SCANN_TRY(launch(select_leaves_kernel, dim3(w.nq), dim3(p2 && ix.L <= 4096 ? 256u : kSelectThreads), lds2, st,
+                     w.cdist, ix.L, n2, w.P, p2, ix.leaf_gsize, ix.leaf_off, w.st, w.tokens, w.token_dists,
+                     w.vbase, w.sbase, (const float *)nullptr, (const float *)nullptr, 0u, 0u, 0u));
     return SCANN_HIP_OK;
 }
 
@@ -4891,18 +4799,14 @@ int txh_launch_partition_only(const TxhIndexDev &ix, const TxhWork &w, hipStream
 template <typename C>
 static int launch_scan_stages(const TxhIndexDev &ix, const TxhWork &w, hipStream_t st,
                               hipEvent_t ev0, hipEvent_t ev1) {
-    int dev = 0, cus = 256;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    const int cus = num_cus();
     if (!w.no_threshold) {
         SampleArgs sa;
         sa.pair_off = w.pair_off; sa.stile_off = w.stile_off; sa.pair_q = w.pair_q;
         sa.pair_sbase = w.pair_sbase; sa.counters = w.counters; sa.lutq = w.lutq; sa.samp = w.samp;
         sa.scap = w.scap; sa.st = w.st; sa.qpt = w.sqpt; sa.allow = w.allow; sa.allow_bits = w.allow_bits;
         const size_t lds_smp = (size_t)2 * C::LUT4 * 16 + 16;
-        SCANN_TRY(set_dyn_lds(adc_sample_kernel<C>, lds_smp));
-        hipLaunchKernelGGL(adc_sample_kernel<C>, dim3((uint32_t)cus * 8u), dim3(kScanThreads), lds_smp, st, ix, sa);
-        LAUNCH_CHECK();
+        SCANN_TRY(launch(adc_sample_kernel<C>, dim3((uint32_t)cus * 8u), dim3(kScanThreads), lds_smp, st, ix, sa));
     }
     {
         const SelCfg tcfg = sel_cfg(w.scap);
@@ -4910,22 +4814,19 @@ static int launch_scan_stages(const TxhIndexDev &ix, const TxhWork &w, hipStream
         const uint32_t nt = w.scap > 8192 ? kSelectThreads : 256u;
         // (without thr_ties the bound is on the distance alone: whole tie groups pass)
         if (w.thr_tail) {
-            hipLaunchKernelGGL(threshold_tail_kernel, dim3(w.nq), dim3(kThrTailThreads), 0, st, w.P, w.m, w.st, w.sbase,
-                               w.samp, w.scap, w.slot_of, w.thr, w.pair_thr, w.thr_ties ? w.vbase : nullptr);
+            SCANN_TRY(launch(threshold_tail_kernel, dim3(w.nq), dim3(kThrTailThreads), 0, st, w.P, w.m, w.st, w.sbase,
+                             w.samp, w.scap, w.slot_of, w.thr, w.pair_thr, w.thr_ties ? w.vbase : nullptr));
         } else {
-            SCANN_TRY(set_dyn_lds(threshold_select_kernel, lds_thr));
-            hipLaunchKernelGGL(threshold_select_kernel, dim3(w.nq), dim3(nt), lds_thr, st, w.P, w.m, w.st,
-                               (int)w.no_threshold, w.sbase, w.samp, w.scap, w.slot_of, w.thr, w.pair_thr,
-                               w.thr_ties ? w.vbase : nullptr);
+            SCANN_TRY(launch(threshold_select_kernel, dim3(w.nq), dim3(nt), lds_thr, st, w.P, w.m, w.st,
+                             (int)w.no_threshold, w.sbase, w.samp, w.scap, w.slot_of, w.thr, w.pair_thr,
+                             w.thr_ties ? w.vbase : nullptr));
         }
-        LAUNCH_CHECK();
     }
     if constexpr (C::BITS == 4) {
         if (txh_scan_is_mfma(w.scan)) {
-            hipLaunchKernelGGL(lut8_build_kernel, dim3(w.max_quads), dim3(256), 0, st, (uint32_t)C::S, w.lutq,
-                               w.counters, w.lut8, reinterpret_cast<Lut8Meta *>(w.lut8_meta), w.pair_q, w.pair_thr,
-                               w.mfma_thr1, w.scan == TxhScan::Smfmac ? 1 : 0);
-            LAUNCH_CHECK();
+            SCANN_TRY(launch(lut8_build_kernel, dim3(w.max_quads), dim3(256), 0, st, (uint32_t)C::S, w.lutq,
+                             w.counters, w.lut8, reinterpret_cast<Lut8Meta *>(w.lut8_meta), w.pair_q, w.pair_thr,
+                             w.mfma_thr1, w.scan == TxhScan::Smfmac ? 1 : 0));
             const bool codes_in_list = w.codes_in_list;
             MfmaArgs ma;
             ma.thr1 = w.mfma_thr1;
@@ -4936,19 +4837,12 @@ static int launch_scan_stages(const TxhIndexDev &ix, const TxhWork &w, hipStream
             if (ev0) SCANN_HIP_CHECK(hipEventRecord(ev0, st));
             const bool words = w.sp_words;
             const dim3 mgrid((uint32_t)cus * 4u), mblock(kMfmaWaves * 64);   // 4 workgroups per CU (4 waves each)
-            if (w.scan == TxhScan::Mfma16)
-                hipLaunchKernelGGL(adc_mfma16_kernel<C::S>, mgrid, mblock, 0, st, ix, ma);
-            else if (w.scan == TxhScan::Mfma32)
-                hipLaunchKernelGGL(adc_mfma_kernel<C::S>, mgrid, mblock, 0, st, ix, ma);
-            else if (C::S <= 32 && !words)
-                hipLaunchKernelGGL((adc_smfmac_kernel<C::S, false>), mgrid, mblock, 0, st, ix, ma);
-            else if (C::S <= 32)
-                hipLaunchKernelGGL((adc_smfmac_kernel<C::S, true>), mgrid, mblock, 0, st, ix, ma);
-            else if (!words)
-                hipLaunchKernelGGL((adc_smfmac_wide_kernel<C::S, false>), mgrid, mblock, 0, st, ix, ma);
-            else
-                hipLaunchKernelGGL((adc_smfmac_wide_kernel<C::S, true>), mgrid, mblock, 0, st, ix, ma);
-            LAUNCH_CHECK();
+            void (*scan)(TxhIndexDev, MfmaArgs) =
+                w.scan == TxhScan::Mfma16   ? adc_mfma16_kernel<C::S>
+                : w.scan == TxhScan::Mfma32 ? adc_mfma_kernel<C::S>
+                : C::S <= 32                ? (words ? adc_smfmac_kernel<C::S, true> : adc_smfmac_kernel<C::S, false>)
+                                            : (words ? adc_smfmac_wide_kernel<C::S, true> : adc_smfmac_wide_kernel<C::S, false>);
+            SCANN_TRY(launch(scan, mgrid, mblock, 0, st, ix, ma));
             if (ev1) SCANN_HIP_CHECK(hipEventRecord(ev1, st));
             RefineArgs ra;
             ra.P = w.P; ra.cap = w.cap; ra.cap32 = w.cap32; ra.tokens = w.tokens; ra.vbase = w.vbase;
@@ -4957,9 +4851,7 @@ static int launch_scan_stages(const TxhIndexDev &ix, const TxhWork &w, hipStream
             ra.allow = w.allow; ra.allow_bits = w.allow_bits;
             ra.planes = (w.scan == TxhScan::Smfmac && ra.cand32_codes) ? 1 : 0;
             const size_t lds_rf = w.P <= kRefineTablesMax ? (size_t)w.P * C::S * 16 * sizeof(float) : 16;
-            SCANN_TRY(set_dyn_lds(adc_refine_kernel<C>, lds_rf));
-            hipLaunchKernelGGL(adc_refine_kernel<C>, dim3(w.nq), dim3(kRefineThreads), lds_rf, st, ix, ra);
-            LAUNCH_CHECK();
+            SCANN_TRY(launch(adc_refine_kernel<C>, dim3(w.nq), dim3(kRefineThreads), lds_rf, st, ix, ra));
             return SCANN_HIP_OK;
         }
     }
@@ -4972,17 +4864,13 @@ static int launch_scan_stages(const TxhIndexDev &ix, const TxhWork &w, hipStream
     a.res_cl = w.res_cl;
     if constexpr (C::BITS == 4 && C::S <= 32) {
         if (w.scan == TxhScan::Resident) {
-            SCANN_TRY(set_dyn_lds(adc_scan_res_kernel<C>, res_lds_bytes<C>()));
-            hipLaunchKernelGGL(adc_scan_res_kernel<C>, dim3((uint32_t)cus * 4u), dim3(kResThreads),
-                               res_lds_bytes<C>(), st, ix, a);
-            LAUNCH_CHECK();
+            SCANN_TRY(launch(adc_scan_res_kernel<C>, dim3((uint32_t)cus * 4u), dim3(kResThreads),
+                             res_lds_bytes<C>(), st, ix, a));
             if (ev1) SCANN_HIP_CHECK(hipEventRecord(ev1, st));
             return SCANN_HIP_OK;
         }
     }
-    SCANN_TRY(set_dyn_lds(adc_scan_kernel<C>, scan_lds_bytes<C>()));
-    hipLaunchKernelGGL(adc_scan_kernel<C>, dim3(wgs), dim3(kScanThreads), scan_lds_bytes<C>(), st, ix, a);
-    LAUNCH_CHECK();
+    SCANN_TRY(launch(adc_scan_kernel<C>, dim3(wgs), dim3(kScanThreads), scan_lds_bytes<C>(), st, ix, a));
     if (ev1) SCANN_HIP_CHECK(hipEventRecord(ev1, st));
     return SCANN_HIP_OK;
 }
@@ -4990,20 +4878,15 @@ static int launch_scan_stages(const TxhIndexDev &ix, const TxhWork &w, hipStream
 // SearchMode::Partitioned: dense key lists (no threshold), one exact-distance tile kernel.
 static int launch_exact_scan(const TxhIndexDev &ix, const TxhWork &w, hipStream_t st, hipEvent_t ev0,
                              hipEvent_t ev1) {
-    int dev = 0, cus = 256;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    const int cus = num_cus();
     {   // thr = MAX for every query: select_rerank takes the k smallest of the whole stream
         const SelCfg tcfg = sel_cfg(w.scap);
         const size_t lds_thr = ((size_t)((w.scap + 3u) & ~3u) + tcfg.bins + tcfg.list) * 4 + 48 * 8;
-        SCANN_TRY(set_dyn_lds(threshold_select_kernel, lds_thr));
-        hipLaunchKernelGGL(threshold_select_kernel, dim3(w.nq), dim3(256), lds_thr, st, w.P, w.m, w.st, 1, w.sbase,
-                           w.samp, w.scap, w.slot_of, w.thr, w.pair_thr, w.vbase);
-        LAUNCH_CHECK();
+        SCANN_TRY(launch(threshold_select_kernel, dim3(w.nq), dim3(256), lds_thr, st, w.P, w.m, w.st, 1, w.sbase,
+                         w.samp, w.scap, w.slot_of, w.thr, w.pair_thr, w.vbase));
     }
-    hipLaunchKernelGGL(stream_counts_kernel, dim3(ceil_div_u32(w.nq, 256)), dim3(256), 0, st, w.nq, w.P, w.vbase,
-                       w.cand_cnt);
-    LAUNCH_CHECK();
+    SCANN_TRY(launch(stream_counts_kernel, dim3(ceil_div_u32(w.nq, 256)), dim3(256), 0, st, w.nq, w.P, w.vbase,
+                     w.cand_cnt));
     ExactScanArgs a;
     a.pair_off = w.pair_off; a.tile_off = w.tile_off; a.pair_q = w.pair_q; a.pair_vbase = w.pair_vbase;
     a.counters = w.counters; a.queries = w.queries; a.q_stride = w.q_stride; a.cand = w.cand; a.cap = w.cap;
@@ -5011,29 +4894,9 @@ static int launch_exact_scan(const TxhIndexDev &ix, const TxhWork &w, hipStream_
     const size_t lds = (size_t)a.qpt * 4 * ((ix.dim + 3u) & ~3u) * sizeof(float);
     if (ev0) SCANN_HIP_CHECK(hipEventRecord(ev0, st));
     const dim3 grid((uint32_t)cus * 8u), block(256);
-    switch (ix.measure) {
-        case SCANN_HIP_SQUARED_L2:
-            SCANN_TRY(set_dyn_lds(leaf_exact_scan_kernel<SCANN_HIP_SQUARED_L2>, lds));
-            hipLaunchKernelGGL(leaf_exact_scan_kernel<SCANN_HIP_SQUARED_L2>, grid, block, lds, st, ix, a);
-            break;
-        case SCANN_HIP_L2:
-            SCANN_TRY(set_dyn_lds(leaf_exact_scan_kernel<SCANN_HIP_L2>, lds));
-            hipLaunchKernelGGL(leaf_exact_scan_kernel<SCANN_HIP_L2>, grid, block, lds, st, ix, a);
-            break;
-        case SCANN_HIP_L1:
-            SCANN_TRY(set_dyn_lds(leaf_exact_scan_kernel<SCANN_HIP_L1>, lds));
-            hipLaunchKernelGGL(leaf_exact_scan_kernel<SCANN_HIP_L1>, grid, block, lds, st, ix, a);
-            break;
-        case SCANN_HIP_COSINE:
-            SCANN_TRY(set_dyn_lds(leaf_exact_scan_kernel<SCANN_HIP_COSINE>, lds));
-            hipLaunchKernelGGL(leaf_exact_scan_kernel<SCANN_HIP_COSINE>, grid, block, lds, st, ix, a);
-            break;
-        default:
-            SCANN_TRY(set_dyn_lds(leaf_exact_scan_kernel<SCANN_HIP_DOT_PRODUCT>, lds));
-            hipLaunchKernelGGL(leaf_exact_scan_kernel<SCANN_HIP_DOT_PRODUCT>, grid, block, lds, st, ix, a);
-            break;
-    }
-    LAUNCH_CHECK();
+    SCANN_TRY(with_measure(ix.measure, [&](auto m) {
+        return launch(leaf_exact_scan_kernel<m()>, grid, block, lds, st, ix, a);
+    }));
     if (ev1) SCANN_HIP_CHECK(hipEventRecord(ev1, st));
     return SCANN_HIP_OK;
 }
@@ -5885,57 +5748,43 @@ static int launch_search_small(const TxhIndexDev &ix, const TxhWork &w, hipStrea
         wa.wgs = std::min(256u, std::max(8u, ceil_div_u32(w.cap, 1024u)));
         wa.mins = w.wide_min; wa.ckey = w.wide_ckey; wa.ceb = w.wide_ceb; wa.cidx = w.wide_cidx; wa.ccnt = w.wide_cnt;
         const size_t lds_scan = ((size_t)ix.S * ix.kp + ix.dim) * sizeof(float);
-        SCANN_TRY(set_dyn_lds_with_static(wide_scan_kernel, std::max(lds_sel, lds_scan), 8 * 1024));   // (6160 B of static arrays)
         if (ev0) SCANN_HIP_CHECK(hipEventRecord(ev0, st));
-        hipLaunchKernelGGL(wide_scan_kernel, dim3(w.grid, w.nq), dim3(kSelectThreads), std::max(lds_sel, lds_scan), st, ix, a, f, wa);
-        LAUNCH_CHECK();
+        SCANN_TRY(launch(wide_scan_kernel, dim3(w.grid, w.nq), dim3(kSelectThreads), std::max(lds_sel, lds_scan), st, ix, a, f, wa));
         if (ev1) SCANN_HIP_CHECK(hipEventRecord(ev1, st));
         const size_t lds_f = (size_t)((ix.dim + 3u) & ~3u) * 4;
-        SCANN_TRY(set_dyn_lds_with_static(wide_filter_kernel, lds_f, 62 * 1024));   // (61840 B of static arrays)
-        hipLaunchKernelGGL(wide_filter_kernel, dim3(wa.wgs, w.nq), dim3(kSelectThreads), lds_f, st, ix, a, wa);
-        LAUNCH_CHECK();
+        SCANN_TRY(launch(wide_filter_kernel, dim3(wa.wgs, w.nq), dim3(kSelectThreads), lds_f, st, ix, a, wa));
         const size_t lds_l = (size_t)w.wide_cap2 * 8;
-        SCANN_TRY(set_dyn_lds_with_static(wide_final_kernel, lds_l, 27 * 1024));   // (26 KB of static arrays)
-        hipLaunchKernelGGL(wide_final_kernel, dim3(w.nq), dim3(kSelectThreads), lds_l, st, a, wa);
-        LAUNCH_CHECK();
+        SCANN_TRY(launch(wide_final_kernel, dim3(w.nq), dim3(kSelectThreads), lds_l, st, a, wa));
         return SCANN_HIP_OK;
     }
     if (w.fused) {   // one launch when the grid stays small
         const size_t lds_scan = ((size_t)(ix.exact_scan ? 0u : ix.S * ix.kp) + ix.dim) * sizeof(float);
         const size_t lds = std::max(lds_sel, lds_scan);
-        // (80272 B of static arrays -- the finish stage's: from ~2200 leaves the selection's dynamic part passes 64 KB, and
-        // the attribute must leave room for both)
-        SCANN_TRY(set_dyn_lds_with_static(small_fused_kernel, lds, 79 * 1024));
+        // (the finish stage's static arrays are ~78 KB: from ~2200 leaves the selection's dynamic part passes 64 KB, and
+        // launch() sets the attribute so that it leaves room for both)
         if (ev0) SCANN_HIP_CHECK(hipEventRecord(ev0, st));
-        hipLaunchKernelGGL(small_fused_kernel, dim3(w.grid, w.nq), dim3(kSelectThreads), lds, st, ix, a, f);
-        LAUNCH_CHECK();
+        SCANN_TRY(launch(small_fused_kernel, dim3(w.grid, w.nq), dim3(kSelectThreads), lds, st, ix, a, f));
         if (ev1) SCANN_HIP_CHECK(hipEventRecord(ev1, st));
         return SCANN_HIP_OK;
     }
     if (ix.ah_mode) {
-        hipLaunchKernelGGL(ah_tokens_kernel, dim3(ceil_div_u32(w.nq, 256)), dim3(256), 0, st, w.nq,
-                           ix.leaf_gsize, ix.leaf_off, w.st, w.tokens, w.token_dists, w.vbase, w.sbase);
+        SCANN_TRY(launch(ah_tokens_kernel, dim3(ceil_div_u32(w.nq, 256)), dim3(256), 0, st, w.nq,
+                         ix.leaf_gsize, ix.leaf_off, w.st, w.tokens, w.token_dists, w.vbase, w.sbase));
     } else {   // (lds_sel: + the leaf size tables and the query, the kernel's inline mode)
-        SCANN_TRY(set_dyn_lds(select_leaves_kernel, lds_sel));
-        hipLaunchKernelGGL(select_leaves_kernel, dim3(w.nq), dim3(kSelectThreads), lds_sel, st, w.cdist, ix.L, f.n_pow2, w.P,
-                           f.p_pow2, ix.leaf_gsize, ix.leaf_off, w.st, w.tokens, w.token_dists, w.vbase, w.sbase, ix.centers_t,
-                           w.queries, w.q_stride, ix.dim, ix.centers_pitch);
+        SCANN_TRY(launch(select_leaves_kernel, dim3(w.nq), dim3(kSelectThreads), lds_sel, st, w.cdist, ix.L, f.n_pow2, w.P,
+                         f.p_pow2, ix.leaf_gsize, ix.leaf_off, w.st, w.tokens, w.token_dists, w.vbase, w.sbase, ix.centers_t,
+                         w.queries, w.q_stride, ix.dim, ix.centers_pitch));
     }
-    LAUNCH_CHECK();
     // exact scans read a whole row per point (one row per thread keeps every load in flight at once); the
     // ADC scan amortises the table build of its workgroup over four points per thread
     a.chunk = ix.exact_scan ? 256u : kSmallChunk;
     const size_t lds_scan = ((size_t)(ix.exact_scan ? 0u : ix.S * ix.kp) + ix.dim) * sizeof(float);
-    SCANN_TRY(set_dyn_lds(small_scan_kernel, lds_scan));
     if (ev0) SCANN_HIP_CHECK(hipEventRecord(ev0, st));
-    hipLaunchKernelGGL(small_scan_kernel, dim3(ceil_div_u32(w.small_max_leaf, a.chunk), w.nq * w.P), dim3(256),
-                       lds_scan, st, ix, a);
-    LAUNCH_CHECK();
+    SCANN_TRY(launch(small_scan_kernel, dim3(ceil_div_u32(w.small_max_leaf, a.chunk), w.nq * w.P), dim3(256),
+                     lds_scan, st, ix, a));
     if (ev1) SCANN_HIP_CHECK(hipEventRecord(ev1, st));
     const size_t lds_fin = (size_t)ix.dim * sizeof(float);
-    SCANN_TRY(set_dyn_lds(small_finish_kernel, lds_fin));
-    hipLaunchKernelGGL(small_finish_kernel, dim3(w.nq), dim3(kSelectThreads), lds_fin, st, ix, a);
-    LAUNCH_CHECK();
+    SCANN_TRY(launch(small_finish_kernel, dim3(w.nq), dim3(kSelectThreads), lds_fin, st, ix, a));
     return SCANN_HIP_OK;
 }
 
@@ -5956,40 +5805,33 @@ int txh_launch_search(const TxhIndexDev &ix, const TxhWork &w, bool local_only, 
         h.pair_q = w.pair_q; h.pair_leaf = w.pair_leaf; h.pair_vbase = w.pair_vbase; h.pair_sbase = w.pair_sbase;
         h.slot_of = w.slot_of; h.tokens = w.tokens; h.vbase = w.vbase; h.sbase = w.sbase; h.pair_off = w.pair_off;
         h.tile_off = w.tile_off; h.stile_off = w.stile_off; h.token_dists = w.token_dists;
-        hipLaunchKernelGGL(ah_setup_kernel, dim3(1), dim3(1024), 0, st, h);
-        LAUNCH_CHECK();
+        SCANN_TRY(launch(ah_setup_kernel, dim3(1), dim3(1024), 0, st, h));
     } else {
     {
         const uint32_t work = std::max(std::max(ix.L, w.nq), w.max_slots);
-        hipLaunchKernelGGL(txh_init_kernel, dim3(std::min(1024u, ceil_div_u32(work, 256))), dim3(256), 0, st,
-                           ix.L, w.nq, w.max_slots, w.leaf_cnt, w.leaf_cursor, w.counters, w.cand_cnt,
-                           mfma ? w.cand32_cnt : nullptr, w.pair_q);
-        LAUNCH_CHECK();
+        SCANN_TRY(launch(txh_init_kernel, dim3(std::min(1024u, ceil_div_u32(work, 256))), dim3(256), 0, st,
+                         ix.L, w.nq, w.max_slots, w.leaf_cnt, w.leaf_cursor, w.counters, w.cand_cnt,
+                         mfma ? w.cand32_cnt : nullptr, w.pair_q));
     }
     SCANN_TRY(launch_partition_stage(ix, w, st));
 
     const uint32_t npairs = w.nq * w.P;
-    hipLaunchKernelGGL(worklist_count_kernel, dim3(ceil_div_u32(npairs, 256)), dim3(256), 0, st,
-                       npairs, ix.ah_mode, w.tokens, ix.leaf_off, w.leaf_cnt);
-    LAUNCH_CHECK();
-    hipLaunchKernelGGL(worklist_scan_kernel, dim3(1), dim3(1024), 0, st, ix.L, w.leaf_cnt,
-                       ix.leaf_off, wl_tp, wl_qpt, wl_cpt, scan_tile_points(ix), w.st,
-                       w.sqpt, w.pair_off, w.tile_off,
-                       w.stile_off, w.counters);
-    LAUNCH_CHECK();
-    hipLaunchKernelGGL(worklist_fill_kernel, dim3(ceil_div_u32(npairs, 256)), dim3(256), 0, st, w.nq,
-                       w.P, ix.ah_mode, w.tokens, w.vbase, w.sbase, ix.leaf_off, w.pair_off, w.leaf_cursor, w.pair_q,
-                       w.pair_leaf, w.pair_vbase, w.pair_sbase, w.slot_of);
-    LAUNCH_CHECK();
+    SCANN_TRY(launch(worklist_count_kernel, dim3(ceil_div_u32(npairs, 256)), dim3(256), 0, st,
+                     npairs, ix.ah_mode, w.tokens, ix.leaf_off, w.leaf_cnt));
+    SCANN_TRY(launch(worklist_scan_kernel, dim3(1), dim3(1024), 0, st, ix.L, w.leaf_cnt,
+                     ix.leaf_off, wl_tp, wl_qpt, wl_cpt, scan_tile_points(ix), w.st,
+                     w.sqpt, w.pair_off, w.tile_off,
+                     w.stile_off, w.counters));
+    SCANN_TRY(launch(worklist_fill_kernel, dim3(ceil_div_u32(npairs, 256)), dim3(256), 0, st, w.nq,
+                     w.P, ix.ah_mode, w.tokens, w.vbase, w.sbase, ix.leaf_off, w.pair_off, w.leaf_cursor, w.pair_q,
+                     w.pair_leaf, w.pair_vbase, w.pair_sbase, w.slot_of));
     }
     if (w.scan == TxhScan::Exact) {
         SCANN_TRY(launch_exact_scan(ix, w, st, ev0, ev1));
     } else {
     const size_t lds_lut = (size_t)4 * ix.dim * sizeof(float);
-    SCANN_TRY(set_dyn_lds(lut_build_kernel, lds_lut));
-    hipLaunchKernelGGL(lut_build_kernel, dim3(w.max_quads), dim3(256), lds_lut, st, ix, w.queries,
-                       w.q_stride, w.pair_q, w.pair_leaf, w.counters, w.lutq);
-    LAUNCH_CHECK();
+    SCANN_TRY(launch(lut_build_kernel, dim3(w.max_quads), dim3(256), lds_lut, st, ix, w.queries,
+                     w.q_stride, w.pair_q, w.pair_leaf, w.counters, w.lutq));
 
     switch (ix.code_bits * 1000 + ix.S) {
         case 4008: SCANN_TRY((launch_scan_stages<Codec<8, 4>>(ix, w, st, ev0, ev1))); break;
@@ -6035,9 +5877,7 @@ int txh_launch_search(const TxhIndexDev &ix, const TxhWork &w, bool local_only, 
     const size_t lds_sel = (size_t)lds_keys * 8 + (size_t)(kSelectThreads / 64 + 4) * 4 +
                            (size_t)scfg.bins * 4 + (size_t)scfg.list * 8 + 48 * 8 + 2 * kDecodeStage * 4;
     const uint32_t sel_threads = direct ? 512u : (lds_keys <= 4096 ? 256u : kSelectThreads);
-    SCANN_TRY(set_dyn_lds(select_rerank_kernel, lds_sel));
-    hipLaunchKernelGGL(select_rerank_kernel, dim3(w.nq), dim3(sel_threads), lds_sel, st, ix, s);
-    LAUNCH_CHECK();
+    SCANN_TRY(launch(select_rerank_kernel, dim3(w.nq), dim3(sel_threads), lds_sel, st, ix, s));
     if (!w.exact_reorder) return SCANN_HIP_OK;
     const size_t lds_rr = (size_t)ix.dim * 4;
     // int8 row filter in front of the exact re-rank (K8b): single-GPU final stage, squared L2, lists long
@@ -6053,49 +5893,32 @@ int txh_launch_search(const TxhIndexDev &ix, const TxhWork &w, bool local_only, 
         ia.q_stride = w.q_stride; ia.m = w.m; ia.cand_row = w.cand_row; ia.cand_count = w.cand_count;
         ia.lb = w.rr_lb; ia.ub = w.rr_ub;
         ia.uni_scale = ix.rows8_scale; ia.uni_E = ix.rows8_emax;
-        if (ix.rows8_fmt == 1) {
-            SCANN_TRY(set_dyn_lds(rerank_i8_kernel<1>, lds_rr));
-            hipLaunchKernelGGL(rerank_i8_kernel<1>, dim3(ceil_div_u32(w.m, kI8PerBlock), w.nq), dim3(256), lds_rr, st, ix.dim, ia);
-        } else if (ix.rows8_uniform) {
-            SCANN_TRY(set_dyn_lds((rerank_i8_kernel<0, true>), lds_rr));
-            hipLaunchKernelGGL((rerank_i8_kernel<0, true>), dim3(ceil_div_u32(w.m, kI8PerBlock), w.nq), dim3(256), lds_rr, st, ix.dim, ia);
-        } else {
-            SCANN_TRY(set_dyn_lds(rerank_i8_kernel<0>, lds_rr));
-            hipLaunchKernelGGL(rerank_i8_kernel<0>, dim3(ceil_div_u32(w.m, kI8PerBlock), w.nq), dim3(256), lds_rr, st, ix.dim, ia);
-        }
-        LAUNCH_CHECK();
+        // 1: FP8 rows; int8 rows with 2: one scale for all rows, 0: a scale per row
+        SCANN_TRY((with_value<1, 2, 0>(ix.rows8_fmt == 1 ? 1 : ix.rows8_uniform ? 2 : 0, [&](auto v) {
+            return launch((rerank_i8_kernel<v() == 1 ? 1 : 0, v() == 2>), dim3(ceil_div_u32(w.m, kI8PerBlock), w.nq),
+                          dim3(256), lds_rr, st, ix.dim, ia);
+        })));
         ShortArgs sa;
         sa.m = w.m; sa.k = w.k; sa.queries = w.queries; sa.q_stride = w.q_stride; sa.lb = w.rr_lb; sa.ub = w.rr_ub;
         sa.cand_row = w.cand_row; sa.cand_idx = w.cand_idx; sa.cand_key = w.cand_key; sa.cand_count = w.cand_count;
         sa.cand_exact = w.cand_exact; sa.out_idx = w.out_idx; sa.out_dist = w.out_dist; sa.out_count = w.out_count;
         sa.local_head = local_only ? kLocalHead : 0u;
         const size_t lds_sh = (size_t)ix.dim * 4;
-        SCANN_TRY(set_dyn_lds(rerank_short_kernel, lds_sh));
-        hipLaunchKernelGGL(rerank_short_kernel, dim3(w.nq), dim3(256), lds_sh, st, ix, sa);
-        LAUNCH_CHECK();
+        SCANN_TRY(launch(rerank_short_kernel, dim3(w.nq), dim3(256), lds_sh, st, ix, sa));
     } else {
-        SCANN_TRY(set_dyn_lds(rerank_kernel, lds_rr));
-        hipLaunchKernelGGL(rerank_kernel, dim3(ceil_div_u32(w.m, 32), w.nq), dim3(256), lds_rr, st, ix,
-                           w.queries, w.q_stride, w.m, w.cand_row, w.cand_count, w.cand_exact);
-        LAUNCH_CHECK();
+        SCANN_TRY(launch(rerank_kernel, dim3(ceil_div_u32(w.m, 32), w.nq), dim3(256), lds_rr, st, ix,
+                         w.queries, w.q_stride, w.m, w.cand_row, w.cand_count, w.cand_exact));
     }
     if (local_only) return SCANN_HIP_OK;
     if (unsorted) {
-        if (w.m <= 2048) {
-            hipLaunchKernelGGL(final_topk_kernel<256>, dim3(w.nq), dim3(256), 0, st, w.m, w.k, w.cand_count,
-                               w.cand_idx, w.cand_key, w.cand_exact, w.out_idx, w.out_dist, w.out_count);
-        } else {
-            hipLaunchKernelGGL(final_topk_kernel<1024>, dim3(w.nq), dim3(1024), 0, st, w.m, w.k, w.cand_count,
-                               w.cand_idx, w.cand_key, w.cand_exact, w.out_idx, w.out_dist, w.out_count);
-        }
-        LAUNCH_CHECK();
-        return SCANN_HIP_OK;
+        return with_value<256, 1024>(w.m <= 2048 ? 256 : 1024, [&](auto nt) {
+            return launch(final_topk_kernel<nt()>, dim3(w.nq), dim3(nt()), 0, st, w.m, w.k, w.cand_count, w.cand_idx,
+                          w.cand_key, w.cand_exact, w.out_idx, w.out_dist, w.out_count);
+        });
     }
     const size_t lds_fs = (size_t)next_pow2_u32(std::max(1u, w.m)) * 8;
-    SCANN_TRY(set_dyn_lds(final_sort_kernel, lds_fs));
-    hipLaunchKernelGGL(final_sort_kernel, dim3(w.nq), dim3(kSelectThreads), lds_fs, st, w.m, w.k,
-                       w.cand_count, w.cand_idx, w.cand_exact, w.out_idx, w.out_dist, w.out_count);
-    LAUNCH_CHECK();
+    SCANN_TRY(launch(final_sort_kernel, dim3(w.nq), dim3(kSelectThreads), lds_fs, st, w.m, w.k,
+                     w.cand_count, w.cand_idx, w.cand_exact, w.out_idx, w.out_dist, w.out_count));
     return SCANN_HIP_OK;
 }
 
@@ -6134,10 +5957,9 @@ int txh_launch_pack_blocks(uint32_t world, uint32_t nq, uint32_t m_local, const 
     if (block_bytes < need || (block_bytes & 7u))
         return fail(SCANN_HIP_INVALID_ARGUMENT, "block_bytes too small or not a multiple of 8");
     const uint64_t work = std::max<uint64_t>((uint64_t)nq * m_local, nq);
-    hipLaunchKernelGGL(pack_blocks_kernel, dim3((uint32_t)ceil_div_u64(work, 256)), dim3(256), 0, st, world, nq,
-                       m_local, d_keys, d_idx, d_exact, d_count, static_cast<unsigned char *>(d_out),
-                       block_bytes);
-    LAUNCH_CHECK();
+    SCANN_TRY(launch(pack_blocks_kernel, dim3((uint32_t)ceil_div_u64(work, 256)), dim3(256), 0, st, world, nq,
+                     m_local, d_keys, d_idx, d_exact, d_count, static_cast<unsigned char *>(d_out),
+                     block_bytes));
     return SCANN_HIP_OK;
 }
 
@@ -6153,11 +5975,9 @@ int txh_launch_merge(uint32_t world, uint32_t nq, uint32_t m_local, uint32_t m, 
         return fail(SCANN_HIP_UNIMPLEMENTED, "pre_reorder_k exceeds the LDS merge capacity");
     const uint32_t m2 = next_pow2_u32(std::max<uint32_t>(1u, m));
     const size_t lds = (size_t)m2 * 12 + 16 + (kSelectThreads / 64) * 8;
-    SCANN_TRY(set_dyn_lds(merge_kernel, lds));
-    hipLaunchKernelGGL(merge_kernel, dim3(nq), dim3(kSelectThreads), lds, st, world, nq, m_local, m, k, m2,
-                       rank_stride_bytes, d_keys, d_idx, d_exact, d_count, d_out_idx, d_out_dist,
-                       d_out_count, d_status, d_qoff);
-    LAUNCH_CHECK();
+    SCANN_TRY(launch(merge_kernel, dim3(nq), dim3(kSelectThreads), lds, st, world, nq, m_local, m, k, m2,
+                     rank_stride_bytes, d_keys, d_idx, d_exact, d_count, d_out_idx, d_out_dist,
+                     d_out_count, d_status, d_qoff));
     return SCANN_HIP_OK;
 }
 
@@ -6166,10 +5986,8 @@ int txh_launch_lut_from_query(const TxhIndexDev &ix, const float *d_queries, uin
                               float *d_out_lut, hipStream_t st) {
     if (nq == 0) return SCANN_HIP_OK;
     const size_t lds = (size_t)ix.dim * sizeof(float);
-    SCANN_TRY(set_dyn_lds(lut_from_query_kernel, lds));
-    hipLaunchKernelGGL(lut_from_query_kernel, dim3(nq), dim3(256), lds, st, ix, d_queries, q_stride,
-                       d_leaf_for_query, d_out_lut);
-    LAUNCH_CHECK();
+    SCANN_TRY(launch(lut_from_query_kernel, dim3(nq), dim3(256), lds, st, ix, d_queries, q_stride,
+                     d_leaf_for_query, d_out_lut));
     return SCANN_HIP_OK;
 }
 
@@ -6179,9 +5997,7 @@ int txh_launch_adc_distances(const TxhIndexDev &ix, const float *d_luts, uint32_
     const uint32_t gx = (uint32_t)std::min<uint64_t>(ceil_div_u64(ix.n_local, 256), 4096);
     dim3 grid(gx, nq);
     const size_t lds = (size_t)ix.S * ix.K * sizeof(float);
-    SCANN_TRY(set_dyn_lds(adc_distances_kernel, lds));
-    hipLaunchKernelGGL(adc_distances_kernel, grid, dim3(256), lds, st, ix, d_luts, d_out);
-    LAUNCH_CHECK();
+    SCANN_TRY(launch(adc_distances_kernel, grid, dim3(256), lds, st, ix, d_luts, d_out));
     return SCANN_HIP_OK;
 }
 
@@ -6189,9 +6005,8 @@ int launch_lut16_u8_batch(const uint8_t *d_packed, const uint8_t *d_lut8, uint32
                           float bias, float mult, float *d_out, hipStream_t st) {
     if (n == 0) return SCANN_HIP_OK;
     const uint32_t gx = (uint32_t)std::min<uint64_t>(ceil_div_u64(n, 256), 8192);
-    hipLaunchKernelGGL(lut16_u8_batch_kernel, dim3(gx), dim3(256), (size_t)S * 16, st, d_packed, d_lut8,
-                       S, n, bias, mult, d_out);
-    LAUNCH_CHECK();
+    SCANN_TRY(launch(lut16_u8_batch_kernel, dim3(gx), dim3(256), (size_t)S * 16, st, d_packed, d_lut8,
+                     S, n, bias, mult, d_out));
     return SCANN_HIP_OK;
 }
 
@@ -6207,34 +6022,30 @@ __global__ __launch_bounds__(256) void transpose_centers_kernel(const float *__r
 int launch_transpose_centers(const float *d_centers, uint32_t L, uint32_t dim, uint32_t pitch, float *d_out,
                              hipStream_t st) {
     if (L == 0 || dim == 0) return SCANN_HIP_OK;
-    hipLaunchKernelGGL(transpose_centers_kernel, dim3((uint32_t)std::min<uint64_t>(ceil_div_u64((uint64_t)dim * pitch, 256), 4096)),
-                       dim3(256), 0, st, d_centers, L, dim, pitch, d_out);
-    LAUNCH_CHECK();
+    SCANN_TRY(launch(transpose_centers_kernel, dim3((uint32_t)std::min<uint64_t>(ceil_div_u64((uint64_t)dim * pitch, 256), 4096)),
+                     dim3(256), 0, st, d_centers, L, dim, pitch, d_out));
     return SCANN_HIP_OK;
 }
 
 int launch_rows_fp8_build(const float *d_rows, uint64_t n, uint32_t dim, uint32_t stride, uint8_t *d_rows8,
                           void *d_meta, uint32_t *d_mismatch, hipStream_t st) {
     if (n == 0) return SCANN_HIP_OK;
-    hipLaunchKernelGGL(rows_fp8_build_kernel, dim3((uint32_t)ceil_div_u64(n, 32)), dim3(256), 0, st, d_rows, n, dim,
-                       stride, d_rows8, reinterpret_cast<float2 *>(d_meta), d_mismatch);
-    LAUNCH_CHECK();
+    SCANN_TRY(launch(rows_fp8_build_kernel, dim3((uint32_t)ceil_div_u64(n, 32)), dim3(256), 0, st, d_rows, n, dim,
+                     stride, d_rows8, reinterpret_cast<float2 *>(d_meta), d_mismatch));
     return SCANN_HIP_OK;
 }
 
 int launch_fp8_quantize(const float *d_values, uint64_t n, float scale, int format, uint8_t *d_out, hipStream_t st) {
     if (n == 0) return SCANN_HIP_OK;
-    hipLaunchKernelGGL(fp8_quantize_kernel, dim3((uint32_t)std::min<uint64_t>(ceil_div_u64(n, 256), 65535)), dim3(256), 0,
-                       st, d_values, n, scale, format, d_out);
-    LAUNCH_CHECK();
+    SCANN_TRY(launch(fp8_quantize_kernel, dim3((uint32_t)std::min<uint64_t>(ceil_div_u64(n, 256), 65535)), dim3(256), 0,
+                     st, d_values, n, scale, format, d_out));
     return SCANN_HIP_OK;
 }
 
 int launch_fp8_dequantize(const uint8_t *d_bits, uint64_t n, float scale, int format, float *d_out, hipStream_t st) {
     if (n == 0) return SCANN_HIP_OK;
-    hipLaunchKernelGGL(fp8_dequantize_kernel, dim3((uint32_t)std::min<uint64_t>(ceil_div_u64(n, 256), 65535)), dim3(256),
-                       0, st, d_bits, n, scale, format, d_out);
-    LAUNCH_CHECK();
+    SCANN_TRY(launch(fp8_dequantize_kernel, dim3((uint32_t)std::min<uint64_t>(ceil_div_u64(n, 256), 65535)), dim3(256),
+                     0, st, d_bits, n, scale, format, d_out));
     return SCANN_HIP_OK;
 }
 
@@ -6242,34 +6053,29 @@ int launch_fp8_one_to_many(const float *d_query, uint32_t dim, const uint8_t *d_
                            int dot, float *d_out, hipStream_t st) {
     if (n == 0) return SCANN_HIP_OK;
     const size_t lds = (size_t)dim * sizeof(float);
-    SCANN_TRY(set_dyn_lds(fp8_one_to_many_kernel, lds));
-    hipLaunchKernelGGL(fp8_one_to_many_kernel, dim3((uint32_t)std::min<uint64_t>(ceil_div_u64(n, 256), 65535)),
-                       dim3(256), lds, st, d_query, dim, d_db, stride, n, dot, d_out);
-    LAUNCH_CHECK();
+    SCANN_TRY(launch(fp8_one_to_many_kernel, dim3((uint32_t)std::min<uint64_t>(ceil_div_u64(n, 256), 65535)),
+                     dim3(256), lds, st, d_query, dim, d_db, stride, n, dot, d_out));
     return SCANN_HIP_OK;
 }
 
 int launch_rows_i8_build(const float *d_rows, uint64_t n, uint32_t dim, uint32_t stride, int8_t *d_rows8,
                          void *d_meta, hipStream_t st, float uni_scale) {
     if (n == 0) return SCANN_HIP_OK;
-    hipLaunchKernelGGL(rows_i8_build_kernel, dim3((uint32_t)ceil_div_u64(n, 32)), dim3(256), 0, st, d_rows, n, dim,
-                       stride, d_rows8, reinterpret_cast<float2 *>(d_meta), uni_scale);
-    LAUNCH_CHECK();
+    SCANN_TRY(launch(rows_i8_build_kernel, dim3((uint32_t)ceil_div_u64(n, 32)), dim3(256), 0, st, d_rows, n, dim,
+                     stride, d_rows8, reinterpret_cast<float2 *>(d_meta), uni_scale));
     return SCANN_HIP_OK;
 }
 
 int launch_lut16_quantize(const float *d_tables, uint32_t S, uint8_t *d_lut8, float *d_bias_mult,
                           hipStream_t st) {
     if (S == 0) return SCANN_HIP_OK;
-    hipLaunchKernelGGL(lut16_quantize_kernel, dim3(1), dim3(256), 0, st, d_tables, S, d_lut8, d_bias_mult);
-    LAUNCH_CHECK();
+    SCANN_TRY(launch(lut16_quantize_kernel, dim3(1), dim3(256), 0, st, d_tables, S, d_lut8, d_bias_mult));
     return SCANN_HIP_OK;
 }
 
 int launch_codes_sp_build(const uint32_t *d_codes, uint64_t n, uint32_t S, uint32_t *d_codes_sp, hipStream_t st) {
     if (n == 0) return SCANN_HIP_OK;
-    hipLaunchKernelGGL(codes_sp_build_kernel, dim3((uint32_t)ceil_div_u64(n, 256)), dim3(256), 0, st, d_codes, n, S, d_codes_sp);
-    LAUNCH_CHECK();
+    SCANN_TRY(launch(codes_sp_build_kernel, dim3((uint32_t)ceil_div_u64(n, 256)), dim3(256), 0, st, d_codes, n, S, d_codes_sp));
     return SCANN_HIP_OK;
 }
 
@@ -6278,9 +6084,8 @@ int launch_encode(const float *d_codebook, uint32_t S, uint32_t K, uint32_t dsub
                   uint8_t *d_out, hipStream_t st) {
     if (n == 0) return SCANN_HIP_OK;
     const uint32_t gx = (uint32_t)std::min<uint64_t>(ceil_div_u64(n * S, 256), 16384);
-    hipLaunchKernelGGL(encode_kernel, dim3(gx), dim3(256), 0, st, d_codebook, S, K, dsub, d_rows, n,
-                       stride, d_centers, d_leaf_of_row, d_out);
-    LAUNCH_CHECK();
+    SCANN_TRY(launch(encode_kernel, dim3(gx), dim3(256), 0, st, d_codebook, S, K, dsub, d_rows, n,
+                     stride, d_centers, d_leaf_of_row, d_out));
     return SCANN_HIP_OK;
 }
 

@@ -1595,6 +1595,28 @@ def test_wide_pipeline_many_leaves(monkeypatch):
         assert np.array_equal(a[0], b[0]) and np.array_equal(bits(a[1]), bits(b[1])) and np.array_equal(a[2], b[2])
 
 
+def test_wide_pipeline_long_candidate_list(monkeypatch):
+    """pre_reorder_k = 3000: wide_final_kernel's compact candidate arrays (3 m + 1024 = 10024 entries of 8 bytes) are more
+    than 64 KB of dynamic LDS next to the kernel's 26 KB of static arrays -- the smallest shape at which a wrong
+    static size in the LDS attribute fails that launch; rows equal the staged pipeline's."""
+    rows, centers, kw = _random_tree_index([30000, 4000, 3000, 3000], 32, 8, seed=83)
+    kw["partitions_to_search"] = 2
+    index = hip.txh_create(**kw)
+    index.enable_timing(True)
+    o = hip.default_opts()
+    o.partitions_to_search, o.pre_reorder_k = 2, 3000
+    q = synth.uniform_f32(4, 32, 84)
+    q[0] = centers[0] + np.float32(0.001)   # (the long leaf is in the first query's stream)
+    for nq in (1, 4):
+        monkeypatch.setenv("SCANN_HIP_WIDE", "2")
+        monkeypatch.delenv("SCANN_HIP_SMALL", raising=False)
+        a = index.search_batched(q[:nq], 10, o)
+        assert index.last_kernel_ms()[1] == "wide_scan_kernel"
+        monkeypatch.setenv("SCANN_HIP_SMALL", "0")
+        b = index.search_batched(q[:nq], 10, o)
+        assert np.array_equal(a[0], b[0]) and np.array_equal(bits(a[1]), bits(b[1])) and np.array_equal(a[2], b[2])
+
+
 def test_wide_pipeline_on_the_device_entry_points():
     """scann_hip_search_batched_device with 1-4 queries over a long stream: the wide pipeline on the caller's stream
     (a workspace per stream), rows equal to the host entry point's; calls on two streams back to back do not share
