@@ -362,8 +362,8 @@ int scann_hip_index_last_device_status(scann_hip_index *index, void *hip_stream)
  * accept as k -> the error the plain search gives for that k (brute force: k > 2048 -> Unimplemented; on the device
  * path k > n -> InvalidArgument; hashed handles: a candidate count above 8192 -> Unimplemented); depth > 8192 ->
  * Unimplemented in any case.
- * Not built: CrowdingMultidimensional (crowding.rs:123-214; its accept decision depends on earlier ACCEPT decisions),
- * MmrDiversifier, a per-query k (the _params entry point), the leaf-sharded multi-GPU entry point.
+ * CrowdingMultidimensional and MmrDiversifier (crowding.rs:123-268) are the two sections below.  Not built for any of
+ * the three: a per-query k (the _params entry point), the leaf-sharded multi-GPU entry point.
  *
  * The stage is one kernel launch behind the handle's final select: one wave per query walks the [nq][depth] rows in
  * chunks of 64 with an open-addressed LDS table keyed on the full 64-bit attribute (a hash collision costs probes,
@@ -394,13 +394,100 @@ int scann_hip_search_crowded(scann_hip_index *index, const float *queries, uint3
  * Same stream / workspace rules and status reporting (scann_hip_index_last_device_status) as
  * scann_hip_search_batched_device; a query the search could not finish has out_count 0.
  * scann_hip_index_reserve_crowded = scann_hip_index_reserve for k = max_depth plus the rows of the crowding stage
- * (max_depth = 0 means max_k); a call within the reserved sizes on the primary workspace does not allocate. */
+ * (max_depth = 0 means max_k); a call within the reserved sizes on the primary workspace does not allocate.  The
+ * multi-attribute stage below needs nothing more: scann_hip_index_reserve_crowded reserves for it as well. */
 int scann_hip_index_reserve_crowded(scann_hip_index *index, uint32_t max_nq, uint32_t max_k, uint32_t max_depth,
                                     const scann_hip_search_opts *opts);
 int scann_hip_search_crowded_device(scann_hip_index *index, const float *d_queries, uint32_t nq, uint32_t q_stride,
                                     uint32_t k, uint32_t depth, uint32_t per_crowd_limit,
                                     const scann_hip_search_opts *opts, uint32_t *d_out_idx, float *d_out_dist,
                                     uint32_t *d_out_count, void *hip_stream);
+
+/* ---- multi-attribute crowding: CrowdingMultidimensional::apply (restricts/crowding.rs:166-200) --------
+ *
+ *   crowded_md(query, k, depth, limits)  ==  CrowdingMultidimensional::apply(search(query, depth), k)
+ *
+ * with search(query, depth) as in the crowding section above.  Every datapoint carries one u64 attribute in each of
+ * n_dims dimensions ("seller", "brand", ...).  The row is walked in order; entry i is kept iff, for EVERY dimension j,
+ * fewer than limits[j] EARLIER KEPT entries carry its attribute in dimension j; the walk stops at k kept.  (Here the
+ * kept count cannot be replaced by a count of earlier entries: an entry one dimension rejects does not count in the
+ * others.)
+ *   - attributes: a [n_dims][n_attrs] u64 array, dimension-major, held on the device with the handle
+ *     (scann_hip_index_set_crowding_attributes_md); separate from the one-attribute array, setting one does not touch
+ *     the other.  n_dims <= SCANN_HIP_CROWD_MAX_DIMS.  An index at or past n_attrs has attribute 0 in every dimension.
+ *   - limits: exactly n_dims values (n_limits != n_dims -> InvalidArgument; the reference indexes limits[dim] and
+ *     panics on a short vector).  A limit of 0 in any dimension keeps nothing.
+ *   - depth <= 8192, depth = 0 means depth = k, short rows, the sentinel fill and out_count: as for the one-attribute
+ *     stage.  k = 0 returns no entry (the reference returns one: it tests the length after the push).
+ *   - n_dims * min(k, depth) > 6144 -> Unimplemented: the LDS table counts accepted entries only, at most that many
+ *     keys, and 6144 is half of the SCANN_HIP_CROWD_MAX_SLOTS slots that fit the workgroup's LDS.
+ *   - with n_dims = 1 the result equals scann_hip_search_crowded bit for bit.
+ * Errors: depth < k -> InvalidArgument; no multi-attribute array attached -> FailedPrecondition; n_dims 0 or above
+ * SCANN_HIP_CROWD_MAX_DIMS -> InvalidArgument; a depth the handle does not accept as k -> the plain search's error.
+ * One kernel launch behind the search: one wave per query, chunks of 64 entries; per chunk the lanes of equal attribute
+ * are found per dimension with ballots, and the chunk's accept decisions are the fixed point of "accepted for certain /
+ * rejected for certain / undecided" over two ballots (each iteration decides at least the lowest undecided lane).
+ * Host entry, device entry, fall-back rules, stream / workspace rules and status reporting are those of the crowded
+ * entry points; scann_hip_crowd_md_apply runs the stage alone over the caller's rows (host pointers, [nq][depth] at
+ * pitch depth, rows_count[i] <= depth else InvalidArgument). */
+#define SCANN_HIP_CROWD_MAX_DIMS 8
+/* Copies attrs[0 .. n_dims * n_attrs) to the device.  Calling again replaces the array; n_attrs = 0 detaches it.
+ * Waits for the device; same external synchronisation as scann_hip_index_set_crowding_attributes. */
+int scann_hip_index_set_crowding_attributes_md(scann_hip_index *index, const uint64_t *attrs, uint32_t n_dims,
+                                               uint64_t n_attrs);
+int scann_hip_search_crowded_md(scann_hip_index *index, const float *queries, uint32_t nq, uint32_t q_stride,
+                                uint32_t q_dim, uint32_t k, uint32_t depth, const uint32_t *limits, uint32_t n_limits,
+                                const scann_hip_search_opts *opts, uint32_t *out_idx, float *out_dist,
+                                uint32_t *out_count);
+/* limits is a HOST pointer (read during the call); everything else as scann_hip_search_crowded_device. */
+int scann_hip_search_crowded_md_device(scann_hip_index *index, const float *d_queries, uint32_t nq, uint32_t q_stride,
+                                       uint32_t k, uint32_t depth, const uint32_t *limits, uint32_t n_limits,
+                                       const scann_hip_search_opts *opts, uint32_t *d_out_idx, float *d_out_dist,
+                                       uint32_t *d_out_count, void *hip_stream);
+int scann_hip_crowd_md_apply(scann_hip_index *index, const uint32_t *rows_idx, const float *rows_dist,
+                             const uint32_t *rows_count, uint32_t nq, uint32_t depth, uint32_t k, const uint32_t *limits,
+                             uint32_t n_limits, uint32_t *out_idx, float *out_dist, uint32_t *out_count);
+
+/* ---- MMR: MmrDiversifier::apply (restricts/crowding.rs:203-268) ------------------------------------
+ *
+ *   mmr(query, k, depth, lambda)  ==  MmrDiversifier::new(lambda).apply(search(query, depth), k, sim)
+ *
+ * with search(query, depth) as in the crowding section and sim(a, b) = -DistanceMeasure::distance(row[a], row[b]) under
+ * the handle's own measure (DotProduct: the dot product; SquaredL2 / L2 / L1: the negated distance; Cosine: cos - 1), in
+ * the reference's pair arithmetic (bitwise symmetric in a and b).  Selection: entry 0 of the row first; every later
+ * round scores the entries not yet selected, in row order, as
+ *     score = lambda * (-dist) - (1 - lambda) * max_sim          (f32; two products and a subtraction, each rounded)
+ * where max_sim is the f32::max fold of sim(entry, s) over the selected entries starting from f32::MIN (a NaN similarity
+ * is ignored, a -inf one leaves f32::MIN).  The winner is the first entry whose score is strictly greater than every
+ * earlier one, the running best starting at f32::MIN; if no score exceeds f32::MIN (all NaN, -inf or <= MIN) the
+ * lowest-position remaining entry is taken.  Rounds continue until min(k, row count) entries are selected.
+ *   - entries are written in SELECTION order, not distance order; distances are the plain search's bits;
+ *     out_count = min(k, count); slots past it hold 0xFFFFFFFF / +inf; a short row is walked to its count.
+ *   - lambda outside [0, 1] is clamped (as new() does); NaN -> InvalidArgument.  k = 0: empty rows (host entry).
+ *   - depth = 0 means depth = k; depth < k -> InvalidArgument; depth > SCANN_HIP_MMR_MAX_DEPTH -> Unimplemented.
+ *   - served: handles whose f32 rows are addressable by datapoint index: f32 brute force; Tree-X-Hybrid, flat-hasher
+ *     and Partitioned handles created with `data` in datapoint order.  Unimplemented: quantized brute-force handles,
+ *     handles whose rows are held only in CSR order (data_is_csr_order), shards (leaf_sizes_global).
+ *     FailedPrecondition: a hashed handle without `data`.
+ * One kernel launch behind the search: one 256-thread workgroup per query; per round every thread folds its entries'
+ * max_sim against the LAST selected row only (a running max), then the workgroup reduces to the winner by (score,
+ * lowest position).  Candidate rows are read from global memory: k re-reads of depth rows per query, L2 traffic after
+ * the first round.  Host entry, device entry, fall-back rules, stream / workspace rules and status reporting are those
+ * of the crowded entry points; scann_hip_index_reserve_mmr is scann_hip_index_reserve_crowded with MMR's depth limit.
+ * scann_hip_mmr_apply runs the stage alone over the caller's rows (host pointers, [nq][depth] at pitch depth):
+ * rows_count[i] <= depth and every rows_idx below the row's count < the index size, else InvalidArgument. */
+#define SCANN_HIP_MMR_MAX_DEPTH 2048
+int scann_hip_search_mmr(scann_hip_index *index, const float *queries, uint32_t nq, uint32_t q_stride, uint32_t q_dim,
+                         uint32_t k, uint32_t depth, float lambda, const scann_hip_search_opts *opts, uint32_t *out_idx,
+                         float *out_dist, uint32_t *out_count);
+int scann_hip_search_mmr_device(scann_hip_index *index, const float *d_queries, uint32_t nq, uint32_t q_stride,
+                                uint32_t k, uint32_t depth, float lambda, const scann_hip_search_opts *opts,
+                                uint32_t *d_out_idx, float *d_out_dist, uint32_t *d_out_count, void *hip_stream);
+int scann_hip_index_reserve_mmr(scann_hip_index *index, uint32_t max_nq, uint32_t max_k, uint32_t max_depth,
+                                const scann_hip_search_opts *opts);
+int scann_hip_mmr_apply(scann_hip_index *index, const uint32_t *rows_idx, const float *rows_dist,
+                        const uint32_t *rows_count, uint32_t nq, uint32_t depth, uint32_t k, float lambda,
+                        uint32_t *out_idx, float *out_dist, uint32_t *out_count);
 
 /* ---- multi-GPU: leaf-sharded Tree-X-Hybrid ------------------- */
 /* Local stage: this rank's best-m candidates per query by approximate distance, with

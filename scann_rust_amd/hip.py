@@ -15,6 +15,8 @@ LIB_PATH = os.environ.get("SCANN_HIP_LIB") or os.path.join(_HERE, "libscann_hip.
 OK, INVALID_ARGUMENT, RESOURCE_EXHAUSTED, FAILED_PRECONDITION = 0, 3, 8, 9
 OUT_OF_RANGE, UNIMPLEMENTED, INTERNAL, UNAVAILABLE = 11, 12, 13, 14
 SQUARED_L2, L2, DOT_PRODUCT, L1, COSINE = 0, 1, 2, 3, 4
+MMR_MAX_DEPTH = 2048    # SCANN_HIP_MMR_MAX_DEPTH
+CROWD_MAX_DIMS = 8      # SCANN_HIP_CROWD_MAX_DIMS
 
 _CODE_NAMES = {
     0: "Ok", 1: "Cancelled", 2: "Unknown", 3: "InvalidArgument", 4: "DeadlineExceeded",
@@ -31,6 +33,9 @@ EXPORTS = [
     "scann_hip_search_batched_device", "scann_hip_index_last_device_status",
     "scann_hip_crowd_table_slots", "scann_hip_index_set_crowding_attributes", "scann_hip_search_crowded",
     "scann_hip_index_reserve_crowded", "scann_hip_search_crowded_device",
+    "scann_hip_index_set_crowding_attributes_md", "scann_hip_search_crowded_md", "scann_hip_search_crowded_md_device",
+    "scann_hip_crowd_md_apply",
+    "scann_hip_search_mmr", "scann_hip_search_mmr_device", "scann_hip_index_reserve_mmr", "scann_hip_mmr_apply",
     "scann_hip_txh_search_local_device", "scann_hip_txh_merge_device",
     "scann_hip_assign_leaves", "scann_hip_txh_partition", "scann_hip_lut_from_query",
     "scann_hip_adc_distances", "scann_hip_lut16_distances_batch", "scann_hip_encode",
@@ -149,6 +154,20 @@ def load():
     L.scann_hip_index_reserve_crowded.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(SearchOpts)]
     L.scann_hip_search_crowded_device.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                                   C.POINTER(SearchOpts), vp, vp, vp, vp]
+    L.scann_hip_index_set_crowding_attributes_md.argtypes = [vp, u64p, C.c_uint32, C.c_uint64]
+    L.scann_hip_search_crowded_md.argtypes = [vp, f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                              u32p, C.c_uint32, C.POINTER(SearchOpts), u32p, f32p, u32p]
+    L.scann_hip_search_crowded_md_device.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, u32p,
+                                                     C.c_uint32, C.POINTER(SearchOpts), vp, vp, vp, vp]
+    L.scann_hip_crowd_md_apply.argtypes = [vp, u32p, f32p, u32p, C.c_uint32, C.c_uint32, C.c_uint32, u32p, C.c_uint32,
+                                           u32p, f32p, u32p]
+    L.scann_hip_search_mmr.argtypes = [vp, f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float,
+                                       C.POINTER(SearchOpts), u32p, f32p, u32p]
+    L.scann_hip_search_mmr_device.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float,
+                                              C.POINTER(SearchOpts), vp, vp, vp, vp]
+    L.scann_hip_index_reserve_mmr.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(SearchOpts)]
+    L.scann_hip_mmr_apply.argtypes = [vp, u32p, f32p, u32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float,
+                                      u32p, f32p, u32p]
     L.scann_hip_txh_search_local_device.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32,
                                                     C.POINTER(SearchOpts), vp, vp, vp, vp, vp]
     L.scann_hip_txh_merge_device.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
@@ -370,6 +389,103 @@ class Index:
             if c >= k or depth >= cap:
                 return (i[0, :c].copy(), d[0, :c].copy()), bool(c >= k or depth >= n)
             depth = min(2 * depth, cap)
+
+    # ---- multi-attribute crowding and MMR (include/scann_hip.h) ----
+    def _staged_host(self, call, queries, k, opts, allow, allow_bits, q_dim):
+        """shared frame of the host entries of the stages: call(q_ptr, nq, q_stride, q_dim, opts_ref, oi, od, oc)"""
+        q = f32(queries)
+        if q.ndim == 1:
+            q = q[None]
+        nq, qs = q.shape
+        qd = qs if q_dim is None else q_dim
+        out_idx = np.full((nq, max(k, 1)), 0xFFFFFFFF, np.uint32)
+        out_dist = np.full((nq, max(k, 1)), np.inf, np.float32)
+        out_cnt = np.zeros(nq, np.uint32)
+        o = opts if opts is not None else default_opts()
+        if allow is not None:
+            allow = np.ascontiguousarray(allow, np.uint64)
+            o.allow_bitmap, o.allow_bitmap_bits = ptr(allow, u64p), _allow_capacity(allow, allow_bits)
+        try:
+            check(call(ptr(q, f32p), nq, qs, qd, C.byref(o), ptr(out_idx, u32p), ptr(out_dist, f32p), ptr(out_cnt, u32p)))
+        finally:
+            if allow is not None:   # (see search_batched)
+                o.allow_bitmap, o.allow_bitmap_bits = None, 0
+        return out_idx[:, :k], out_dist[:, :k], out_cnt
+
+    @staticmethod
+    def _staged_apply(call, rows_idx, rows_dist, rows_count, k):
+        """shared frame of the *_apply entries: call(ri, rd, rc, nq, depth, oi, od, oc); rows [nq][depth]"""
+        ri = np.ascontiguousarray(rows_idx, np.uint32)
+        rd = np.ascontiguousarray(rows_dist, np.float32)
+        rc = np.ascontiguousarray(rows_count, np.uint32)
+        nq, depth = ri.shape
+        assert rd.shape == ri.shape and rc.shape == (nq,)
+        out_idx = np.full((nq, max(k, 1)), 0xFFFFFFFF, np.uint32)
+        out_dist = np.full((nq, max(k, 1)), np.inf, np.float32)
+        out_cnt = np.zeros(nq, np.uint32)
+        check(call(ptr(ri, u32p), ptr(rd, f32p), ptr(rc, u32p), nq, depth, ptr(out_idx, u32p), ptr(out_dist, f32p),
+                   ptr(out_cnt, u32p)))
+        return out_idx[:, :k], out_dist[:, :k], out_cnt
+
+    def set_crowding_attributes_md(self, attrs, n_dims=None):
+        """[n_dims][n_attrs] uint64 attributes, dimension-major (a 2-D array; n_dims only for an empty one); None or
+        n_attrs = 0 detaches them.  scann_hip_index_set_crowding_attributes_md."""
+        a = np.zeros((1, 0), np.uint64) if attrs is None else np.ascontiguousarray(attrs, np.uint64)
+        if a.ndim != 2:
+            raise ValueError("attrs must be [n_dims][n_attrs]")
+        nd = a.shape[0] if n_dims is None else int(n_dims)
+        check(load().scann_hip_index_set_crowding_attributes_md(self.h, ptr(a, u64p) if a.size else None, nd, a.shape[1]))
+
+    def search_crowded_md(self, queries, k, depth, limits, opts=None, allow=None, allow_bits=None, q_dim=None):
+        """CrowdingMultidimensional::apply(search(query, depth), k) with one limit per attribute dimension, on the
+        device (scann_hip_search_crowded_md).  depth = 0 means k."""
+        lim = np.ascontiguousarray(limits, np.uint32).ravel()
+        return self._staged_host(
+            lambda q, nq, qs, qd, o, oi, od, oc: load().scann_hip_search_crowded_md(
+                self.h, q, nq, qs, qd, k, depth, ptr(lim, u32p), lim.size, o, oi, od, oc),
+            queries, k, opts, allow, allow_bits, q_dim)
+
+    def search_crowded_md_device(self, d_queries, nq, q_stride, k, depth, limits, d_out_idx, d_out_dist, d_out_count,
+                                 stream, opts=None):
+        """scann_hip_search_crowded_md_device: device addresses (integers) and a HIP stream handle; enqueue only"""
+        lim = np.ascontiguousarray(limits, np.uint32).ravel()
+        check(load().scann_hip_search_crowded_md_device(
+            self.h, vp(d_queries), nq, q_stride, k, depth, ptr(lim, u32p), lim.size,
+            C.byref(opts) if opts is not None else None, vp(d_out_idx), vp(d_out_dist), vp(d_out_count), vp(stream)))
+
+    def crowd_md_apply(self, rows_idx, rows_dist, rows_count, k, limits):
+        """CrowdingMultidimensional::apply on the caller's rows [nq][depth] (scann_hip_crowd_md_apply)"""
+        lim = np.ascontiguousarray(limits, np.uint32).ravel()
+        return self._staged_apply(
+            lambda ri, rd, rc, nq, depth, oi, od, oc: load().scann_hip_crowd_md_apply(
+                self.h, ri, rd, rc, nq, depth, k, ptr(lim, u32p), lim.size, oi, od, oc),
+            rows_idx, rows_dist, rows_count, k)
+
+    def search_mmr(self, queries, k, depth, lam, opts=None, allow=None, allow_bits=None, q_dim=None):
+        """MmrDiversifier::new(lam).apply(search(query, depth), k, sim) with sim = minus the handle's distance between
+        two stored rows, on the device (scann_hip_search_mmr).  Rows come back in selection order."""
+        return self._staged_host(
+            lambda q, nq, qs, qd, o, oi, od, oc: load().scann_hip_search_mmr(
+                self.h, q, nq, qs, qd, k, depth, C.c_float(lam), o, oi, od, oc),
+            queries, k, opts, allow, allow_bits, q_dim)
+
+    def search_mmr_device(self, d_queries, nq, q_stride, k, depth, lam, d_out_idx, d_out_dist, d_out_count, stream,
+                          opts=None):
+        """scann_hip_search_mmr_device: device addresses (integers) and a HIP stream handle; enqueue only"""
+        check(load().scann_hip_search_mmr_device(
+            self.h, vp(d_queries), nq, q_stride, k, depth, C.c_float(lam), C.byref(opts) if opts is not None else None,
+            vp(d_out_idx), vp(d_out_dist), vp(d_out_count), vp(stream)))
+
+    def reserve_mmr(self, max_nq, max_k, max_depth=0, opts=None):
+        check(load().scann_hip_index_reserve_mmr(self.h, max_nq, max_k, max_depth,
+                                                 C.byref(opts) if opts is not None else None))
+
+    def mmr_apply(self, rows_idx, rows_dist, rows_count, k, lam):
+        """MmrDiversifier::apply on the caller's rows [nq][depth] (scann_hip_mmr_apply)"""
+        return self._staged_apply(
+            lambda ri, rd, rc, nq, depth, oi, od, oc: load().scann_hip_mmr_apply(
+                self.h, ri, rd, rc, nq, depth, k, C.c_float(lam), oi, od, oc),
+            rows_idx, rows_dist, rows_count, k)
 
     def search_radius(self, query, radius, capacity=None, allow=None, allow_bits=None):
         """Brute-force handles: bf_search_radius, with an optional allow-bitmap."""

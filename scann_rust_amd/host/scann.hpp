@@ -282,6 +282,108 @@ private:
     uint64_t stamp_;
 };
 
+class CrowdingMultidimensional {     // crowding.rs:122-201
+public:
+    CrowdingMultidimensional(size_t num_dimensions, size_t num_datapoints)      // new (:134-140)
+        : attrs_(num_dimensions, std::vector<uint64_t>(num_datapoints, 0)),
+          limits_(num_dimensions, std::numeric_limits<size_t>::max()), num_datapoints_(num_datapoints), stamp_(next_stamp()) {}
+    void set_limits(std::vector<size_t> limits) { limits_ = std::move(limits); }   // :143-145
+    void set_attribute(size_t dim, DatapointIndex index, uint64_t attribute) {     // :148-155: out of range is ignored
+        if (dim < attrs_.size() && (size_t)index < attrs_[dim].size()) {
+            attrs_[dim][index] = attribute;
+            stamp_ = next_stamp();
+        }
+    }
+    std::vector<uint64_t> get_attributes(DatapointIndex index) const {             // :158-164: missing = 0
+        std::vector<uint64_t> out;
+        out.reserve(attrs_.size());
+        for (const auto &d : attrs_) out.push_back((size_t)index < d.size() ? d[index] : 0);
+        return out;
+    }
+    // The plain host walk (:167-200), statement for statement -- including that it tests `len >= k` only after a push.
+    // The reference indexes limits[dim] and panics on a short vector; here that is InvalidArgument.
+    NNResultsVector apply(const NNResultsVector &results, size_t k) const {
+        const size_t num_dims = attrs_.size();
+        if (limits_.size() < num_dims) throw ScannError::invalid_argument("fewer limits than crowding dimensions");
+        std::vector<std::unordered_map<uint64_t, size_t>> crowd_counts(num_dims);
+        NNResultsVector filtered;
+        filtered.reserve(std::min(k, results.size()));
+        for (const auto &r : results) {
+            const std::vector<uint64_t> attrs = get_attributes(r.first);
+            bool allowed = true;
+            for (size_t dim = 0; dim < num_dims; ++dim) {
+                auto it = crowd_counts[dim].find(attrs[dim]);
+                const size_t count = it == crowd_counts[dim].end() ? 0 : it->second;
+                if (count >= limits_[dim]) {
+                    allowed = false;
+                    break;
+                }
+            }
+            if (allowed) {
+                for (size_t dim = 0; dim < num_dims; ++dim) ++crowd_counts[dim][attrs[dim]];
+                filtered.push_back(r);
+                if (filtered.size() >= k) break;
+            }
+        }
+        return filtered;
+    }
+    size_t num_dimensions() const { return attrs_.size(); }
+    size_t num_datapoints() const { return num_datapoints_; }
+    const std::vector<size_t> &limits() const { return limits_; }
+    // [num_dimensions][num_datapoints], dimension-major: what scann_hip_index_set_crowding_attributes_md takes
+    std::vector<uint64_t> flat_attributes() const {
+        std::vector<uint64_t> flat;
+        flat.reserve(attrs_.size() * num_datapoints_);
+        for (const auto &d : attrs_) flat.insert(flat.end(), d.begin(), d.end());
+        return flat;
+    }
+    uint64_t stamp() const { return stamp_; }
+
+private:
+    static uint64_t next_stamp() {
+        static std::atomic<uint64_t> s{0};
+        return ++s;
+    }
+    std::vector<std::vector<uint64_t>> attrs_;
+    std::vector<size_t> limits_;
+    size_t num_datapoints_;
+    uint64_t stamp_;
+};
+
+struct MmrDiversifier {              // crowding.rs:203-268
+    float lambda;
+    explicit MmrDiversifier(float l) : lambda(l < 0.0f ? 0.0f : (l > 1.0f ? 1.0f : l)) {}   // f32::clamp (NaN stays NaN)
+    // :220-267, statement for statement; similarity_fn(a, b) -> f32
+    template <typename F>
+    NNResultsVector apply(const NNResultsVector &candidates, size_t k, F similarity_fn) const {
+        if (candidates.empty() || k == 0) return {};
+        NNResultsVector selected, remaining(candidates);
+        selected.reserve(std::min(k, candidates.size()));
+        selected.push_back(remaining.front());
+        remaining.erase(remaining.begin());
+        const float f32_min = std::numeric_limits<float>::lowest();
+        while (selected.size() < k && !remaining.empty()) {
+            size_t best_idx = 0;
+            float best_score = f32_min;
+            for (size_t i = 0; i < remaining.size(); ++i) {
+                const float rel_score = -remaining[i].second;
+                float max_sim = f32_min;
+                for (const auto &sel : selected) max_sim = std::fmax(max_sim, (float)similarity_fn(remaining[i].first, sel.first));
+                // (volatile: each product is rounded to f32 before the subtraction, whatever the compiler's contraction)
+                volatile float a = lambda * rel_score, b = (1.0f - lambda) * max_sim;
+                const float mmr_score = a - b;
+                if (mmr_score > best_score) {
+                    best_score = mmr_score;
+                    best_idx = i;
+                }
+            }
+            selected.push_back(remaining[best_idx]);
+            remaining.erase(remaining.begin() + (std::ptrdiff_t)best_idx);
+        }
+        return selected;
+    }
+};
+
 namespace detail {
 
 struct IndexHandle {
@@ -344,6 +446,48 @@ inline NNResultsVector run_search_crowded(scann_hip_index *h, const CrowdAttach 
     uint32_t cnt = 0;
     check(scann_hip_search_crowded(h, query.data(), 1, (uint32_t)query.size(), (uint32_t)query.size(), (uint32_t)k,
                                    (uint32_t)depth, limit, opts, idx.data(), dist.data(), &cnt));
+    NNResultsVector out;
+    for (uint32_t j = 0; j < cnt; ++j) out.emplace_back(idx[j], dist[j]);
+    return out;
+}
+
+// search_with_crowding_md: the attributes go to the handle once per change of the constraint, then
+// scann_hip_search_crowded_md = CrowdingMultidimensional::apply(search(query, depth), k) on the device.
+struct CrowdMdAttach {
+    mutable uint64_t stamp = 0;
+    void ensure(scann_hip_index *h, const CrowdingMultidimensional &c) const {
+        if (stamp == c.stamp()) return;
+        const std::vector<uint64_t> flat = c.flat_attributes();
+        check(scann_hip_index_set_crowding_attributes_md(h, flat.data(), (uint32_t)c.num_dimensions(), c.num_datapoints()));
+        stamp = c.stamp();
+    }
+};
+
+inline NNResultsVector run_search_crowded_md(scann_hip_index *h, const CrowdMdAttach &at, const std::vector<float> &query,
+                                             size_t k, size_t depth, const CrowdingMultidimensional &c,
+                                             const scann_hip_search_opts *opts) {
+    at.ensure(h, c);
+    std::vector<uint32_t> limits;
+    for (size_t l : c.limits()) limits.push_back((uint32_t)std::min<size_t>(l, 0xFFFFFFFFu));
+    std::vector<uint32_t> idx(std::max<size_t>(1, k));
+    std::vector<float> dist(std::max<size_t>(1, k));
+    uint32_t cnt = 0;
+    check(scann_hip_search_crowded_md(h, query.data(), 1, (uint32_t)query.size(), (uint32_t)query.size(), (uint32_t)k,
+                                      (uint32_t)depth, limits.data(), (uint32_t)limits.size(), opts, idx.data(),
+                                      dist.data(), &cnt));
+    NNResultsVector out;
+    for (uint32_t j = 0; j < cnt; ++j) out.emplace_back(idx[j], dist[j]);
+    return out;
+}
+
+// MmrDiversifier::apply(search(query, depth), k, sim) on the device, sim = minus the handle's distance of two rows
+inline NNResultsVector run_search_mmr(scann_hip_index *h, const std::vector<float> &query, size_t k, size_t depth,
+                                      const MmrDiversifier &mmr, const scann_hip_search_opts *opts) {
+    std::vector<uint32_t> idx(std::max<size_t>(1, k));
+    std::vector<float> dist(std::max<size_t>(1, k));
+    uint32_t cnt = 0;
+    check(scann_hip_search_mmr(h, query.data(), 1, (uint32_t)query.size(), (uint32_t)query.size(), (uint32_t)k,
+                               (uint32_t)depth, mmr.lambda, opts, idx.data(), dist.data(), &cnt));
     NNResultsVector out;
     for (uint32_t j = 0; j < cnt; ++j) out.emplace_back(idx[j], dist[j]);
     return out;
@@ -455,6 +599,17 @@ public:
         if (!constraint.config().enabled) return search(query, k);
         return detail::run_search_crowded(ix_.h, crowd_, query, k, depth, constraint, nullptr);
     }
+    // CrowdingMultidimensional::apply(search(query, depth), k) on the device
+    NNResultsVector search_with_crowding_md(const std::vector<float> &query, size_t k, size_t depth,
+                                            const CrowdingMultidimensional &constraint) const {
+        return detail::run_search_crowded_md(ix_.h, crowd_md_, query, k, depth, constraint, nullptr);
+    }
+    // MmrDiversifier::apply(search(query, depth), k, sim) on the device; sim(a, b) = -distance(row a, row b) under the
+    // searcher's measure.  Rows come back in selection order.
+    NNResultsVector search_with_mmr(const std::vector<float> &query, size_t k, size_t depth,
+                                    const MmrDiversifier &mmr) const {
+        return detail::run_search_mmr(ix_.h, query, k, depth, mmr, nullptr);
+    }
     // The crowded k nearest neighbours over the WHOLE index: depth starts at k and doubles until the row holds k
     // entries or depth has reached min(N, 2048).  second = complete: k were kept, or the whole index was walked; by
     // the prefix property the rows then equal apply() over the full sorted database.
@@ -511,6 +666,7 @@ private:
     DistanceMeasure measure_;
     detail::IndexHandle ix_;
     detail::CrowdAttach crowd_;
+    detail::CrowdMdAttach crowd_md_;
 };
 
 // ---- AsymmetricHasher (hashes/hasher.rs) ---------------------------------------------------
