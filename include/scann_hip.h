@@ -761,6 +761,118 @@ int scann_hip_bf_search_radius(scann_hip_index *index, const float *query, uint3
 int scann_hip_bf_assign_nearest(scann_hip_index *index, const float *centers, uint32_t num_centers,
                                 uint32_t *out_assign, float *out_dist);
 
+/* ---- mutable indexes: add, remove and update rows on a live device index (mutator/mod.rs) --------------
+ * MutableDataset (mod.rs:286-490) and the rebuild counter of IncrementalUpdater (mod.rs:527-545) over a device index,
+ * LSM style: an immutable BASE handle the caller created (and keeps alive: the mutable handle borrows it and must be
+ * destroyed first), a live bitmap over the base rows resident on the device (one bit per base datapoint; mutations
+ * flip bits with a small kernel over the batch's ids, the bitmap is never re-uploaded), and a dense, all-live DELTA
+ * segment of up to `capacity` f32 rows (stride scann_hip_compute_stride(dim)) holding added and changed rows, each with
+ * its external id.  Removing a delta row moves the last row into the hole (a device-to-device copy), so delta rows sit
+ * in arbitrary order and nothing depends on their slots.  Wrapping a base does not modify it: searching the base
+ * directly gives what it gives today.
+ * Ids: u32, stable.  Base row j has id j; add returns next_index++ starting at the base size, never reused
+ * (mod.rs:291); after a rebase base row j has id base_ids[j].  0xFFFFFFFF stays the empty-slot marker: when the next
+ * id would be 0xFFFFFFFF, add returns OutOfRange.
+ * Supported bases: f32 brute-force handles (every measure); unsharded Tree-X-Hybrid / AsymmetricHasher handles created
+ * with `data` in datapoint order (data != NULL, data_is_csr_order == 0), searched with exact_reorder = 1; the live
+ * bitmap covers datapoint indices below scann_hip_index_size(base), so a datapoint index at or past it counts as removed
+ * once any row is removed or filtered.  Unimplemented: quantized brute-force rows, SearchMode::Partitioned, shards (leaf_sizes_global),
+ * handles without rows or with rows in CSR order (at create / rebase), exact_reorder = 0 (at search: approximate and
+ * exact distances cannot be merged).  capacity 0 or above SCANN_HIP_MUTABLE_MAX_CAPACITY -> InvalidArgument.
+ *
+ * Mutations (the reference's semantics, quirks included).  Every call takes a batch of n rows / ids -- one upload and
+ * one kernel per batch; a single mutation is a batch of one.  A batch is applied in order, all or nothing: it is
+ * validated on the host first, and if any element would fail the call returns that error with nothing changed (no id
+ * consumed, no counter bump); the batch's staging buffers are allocated before anything changes, so ResourceExhausted
+ * from the device allocator leaves the handle as it was too.  A HIP error while the batch is being copied or its kernels
+ * launched (Internal) leaves the host map ahead of the device: destroy the handle.  rows: n rows of `dim` floats, row i at
+ * rows + i * row_stride.
+ *   add     dim != index dim -> InvalidArgument; more rows than the delta has free slots -> ResourceExhausted.
+ *           Appends to the delta, out_ids[i] = the new id, counter += n.
+ *   remove  an id never issued, or dropped by a rebase -> NotFound.  Removing an already removed id succeeds
+ *           (mod.rs:320-329: the set absorbs it) and still counts as a mutation.  A base row has its live bit cleared,
+ *           a delta row is swap-removed.
+ *   update  unknown id -> NotFound, dim mismatch -> InvalidArgument.  REVIVES a removed id (mod.rs:359-360).  A live
+ *           delta row is overwritten in place; a base row (live or removed) has its live bit cleared and the new row
+ *           goes to the delta under the same id; a removed former delta row goes to the delta again.  A batch that
+ *           needs more new delta slots than are free -> ResourceExhausted.
+ *   get     copies the live row (dim floats) from wherever it lives; not live -> NotFound.  exists: 1 / 0.
+ *           size: live rows.  pending: mutations since create or the last rebase; needs_rebuild(t): pending >= t.
+ *
+ * Search (host entry point; output conventions of scann_hip_search_batched: rows ascending, slots past out_count[i]
+ * hold 0xFFFFFFFF / +inf).  out_idx holds EXTERNAL ids; opts->allow_bitmap is a host bitmap over EXTERNAL ids with the
+ * capacity rule of scann_hip_search_opts (ids at or past allow_bitmap_bits are not allowed, delta ids included).
+ * One stream, three stages, one synchronisation:
+ *   1. base pass: the base's enqueue-only search (scann_hip_search_batched_device) under a device bitmap -- none when
+ *      every base row is live and there is no user filter (today's unfiltered path, shortlist included), the resident
+ *      live bitmap when rows are removed and there is no user filter, otherwise live[j] & user[id of j] from one kernel
+ *      (a word-wise AND before a rebase, a gather through base_ids after).  If, after the synchronisation, the base
+ *      reports Aborted or ResourceExhausted (scann_hip_index_last_device_status), the base pass is repeated through
+ *      scann_hip_search_batched with the same bitmap and stages 2 and 3 run again: never partial rows.
+ *   2. delta pass (delta_scan_kernel): every (query, delta row) distance by the reference's per-pair arithmetic under
+ *      the measure of the base's final distances (brute force: the handle's; tree / AH: the re-rank's), queries tiled
+ *      through LDS, the user bitmap tested on the external id; each workgroup sorts a tile of
+ *      SCANN_HIP_MUTABLE_DELTA_TILE delta rows in LDS by (distance, EXTERNAL id) and emits its first min(k, tile).
+ *   3. merge (mutable_merge_kernel): base indices mapped to external ids, the k best of base list + delta lists by
+ *      (distance, external id), out_count = min(k, found).
+ * With no mutation at all (empty delta, every row live, identity ids) the call IS scann_hip_search_batched on the base,
+ * writing straight into the caller's arrays.
+ * Contract:
+ *   - brute-force base: the answer is exactly that of scann_hip_bf_create over the live rows taken in ascending
+ *     external-id order, indices mapped back; distances bitwise identical; ties broken by (distance, external id);
+ *     k = min(k, live allowed rows) -- whatever the mix of base and delta rows: an updated row with a low id sitting in
+ *     a late delta slot still wins its ties.
+ *   - tree / AH base: the base's filtered answer under the live bitmap (the one scann_hip_search_opts documents),
+ *     merged with the exact distances of ALL live delta rows; delta rows are never subject to quantisation loss;
+ *     pre_reorder_k applies to the base only.
+ *   - a search observes every mutation whose call returned before the search was called.
+ *   - mutations and searches may come from any thread; they serialise on the handle's mutex (parallel search slots are
+ *     a documented limit).  create / destroy / rebase need external synchronisation against the BASE's other users
+ *     only in that the base must outlive the handle.
+ *   - known cost: one removed base row sends a brute-force base onto the filtered path, which never takes the
+ *     bf16 shortlist (see allow_bitmap above).
+ * Scratch: the partial lists take nq * ceil(delta rows / tile) * min(k, tile) * 8 bytes and stay with the handle: 1.3 MB at
+ * nq = 1024, k = 10 and a 16 384-row delta, but 512 MB at nq = 1024, k >= 1024 and a full 65 536-row delta (then as large
+ * as an [nq][delta] matrix of keys): split such batches.
+ * Errors: q_dim != dim, k > SCANN_HIP_MUTABLE_MAX_K -> InvalidArgument; exact_reorder = 0 or per-stage outputs on a
+ * tree / AH base -> Unimplemented.  k = 0 -> empty rows.
+ *
+ * export_live / rebase (MutableDataset::compact, mod.rs:440-471, as two calls).  export_live writes every live row
+ * (rows of scann_hip_compute_stride(dim) floats, padding zero) and its id in ascending id order to host memory; base
+ * rows are gathered on the device (prefix sum over the live bitmap + a gather kernel reading the base's f32 rows),
+ * delta rows are placed among them by id.  *out_n = live rows; capacity_rows < live rows -> ResourceExhausted with
+ * *out_n set and nothing written.  rebase swaps in a new base handle whose row j has external id base_ids[j] (strictly
+ * ascending, no 0xFFFFFFFF, else InvalidArgument; NULL = identity); n must equal scann_hip_index_size(new_base), same dim
+ * and kind constraints as create.  It empties the delta, sets every bit live, resets the counter and forgets every id
+ * not in base_ids (NotFound afterwards); next_index is kept (raised past the largest id if need be).  The caller builds
+ * new_base from the exported rows however it likes and destroys the old base afterwards.
+ * scann_hip_mutable_enable_timing / _last_stage_ms: HIP-event times (ms) of { base pass, delta scan, merge } of the
+ * last search on the three-stage route (0 for a stage that did not run). */
+typedef struct scann_hip_mutable scann_hip_mutable;
+#define SCANN_HIP_MUTABLE_MAX_CAPACITY 65536
+#define SCANN_HIP_MUTABLE_MAX_K 2048
+#define SCANN_HIP_MUTABLE_DELTA_TILE 1024
+int scann_hip_mutable_create(scann_hip_ctx *ctx, scann_hip_index *base, uint32_t capacity, scann_hip_mutable **out);
+void scann_hip_mutable_destroy(scann_hip_mutable *m);
+int scann_hip_mutable_add(scann_hip_mutable *m, const float *rows, uint32_t n, uint32_t row_stride, uint32_t dim,
+                          uint32_t *out_ids);
+int scann_hip_mutable_remove(scann_hip_mutable *m, const uint32_t *ids, uint32_t n);
+int scann_hip_mutable_update(scann_hip_mutable *m, const uint32_t *ids, const float *rows, uint32_t n,
+                             uint32_t row_stride, uint32_t dim);
+int scann_hip_mutable_get(scann_hip_mutable *m, uint32_t id, float *out_row);
+int scann_hip_mutable_exists(scann_hip_mutable *m, uint32_t id);
+uint64_t scann_hip_mutable_size(scann_hip_mutable *m);
+uint64_t scann_hip_mutable_pending(scann_hip_mutable *m);
+int scann_hip_mutable_needs_rebuild(scann_hip_mutable *m, uint64_t threshold);
+int scann_hip_mutable_search(scann_hip_mutable *m, const float *queries, uint32_t nq, uint32_t q_stride, uint32_t q_dim,
+                             uint32_t k, const scann_hip_search_opts *opts, uint32_t *out_idx, float *out_dist,
+                             uint32_t *out_count);
+int scann_hip_mutable_export_live(scann_hip_mutable *m, float *out_rows, uint32_t *out_ids, uint64_t capacity_rows,
+                                  uint64_t *out_n);
+int scann_hip_mutable_rebase(scann_hip_mutable *m, scann_hip_index *new_base, const uint32_t *base_ids, uint64_t n);
+void scann_hip_mutable_enable_timing(scann_hip_mutable *m, int enable);
+int scann_hip_mutable_last_stage_ms(scann_hip_mutable *m, float *out_ms3);
+
 /* ---- introspection ------------------------------------------------------------- */
 uint64_t scann_hip_index_size(const scann_hip_index *index);          /* Searcher::dataset_size */
 uint32_t scann_hip_index_dimensionality(const scann_hip_index *index);/* Searcher::dimensionality */

@@ -19,6 +19,7 @@
 #include "common.h"
 #include "crowd.h"
 #include "mmr.h"
+#include "mutable.h"
 #include "knobs.h"
 #include "launch.h"
 #include "txh.h"
@@ -265,6 +266,33 @@ static int set_device(const scann_hip_ctx *ctx) {
 }
 
 int scann::ctx_device(const scann_hip_ctx *ctx) { return ctx ? ctx->device : 0; }
+
+// What mutable.hip needs to know of a base handle (mutable.h): its f32 rows by datapoint index and the measure of
+// its final distances.
+int scann::index_base_view(const scann_hip_index *ix, BaseView *v) {
+    if (!ix || !v) return fail(SCANN_HIP_INVALID_ARGUMENT, "index is null");
+    *v = BaseView();
+    v->ctx = ix->ctx;
+    v->brute_force = ix->kind == KIND_BF;
+    if (ix->kind == KIND_BF) {
+        v->rows = ix->bf.rows;
+        v->n = ix->bf.n;
+        v->dim = ix->bf.dim;
+        v->stride = ix->bf.stride;
+        v->measure = ix->bf.measure;
+        v->quantized = ix->bf.fmt != 0;
+    } else {
+        v->rows = ix->tx.rows;
+        v->n = ix->tx.n_local;
+        v->dim = ix->tx.dim;
+        v->stride = ix->tx.stride;
+        v->measure = ix->tx.measure;
+        v->rows_csr = ix->tx.rows_csr != 0 && !ix->tx.ah_mode;   // (the flat hasher's one leaf is in datapoint order)
+        v->partitioned = ix->tx.exact_scan != 0;
+        v->sharded = ix->sharded;
+    }
+    return SCANN_HIP_OK;
+}
 
 extern "C" {
 

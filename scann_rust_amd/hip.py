@@ -13,10 +13,14 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SCANN_HIP_LIB") or os.path.join(_HERE, "libscann_hip.so")
 
 OK, INVALID_ARGUMENT, RESOURCE_EXHAUSTED, FAILED_PRECONDITION = 0, 3, 8, 9
+NOT_FOUND, ABORTED = 5, 10
 OUT_OF_RANGE, UNIMPLEMENTED, INTERNAL, UNAVAILABLE = 11, 12, 13, 14
 SQUARED_L2, L2, DOT_PRODUCT, L1, COSINE = 0, 1, 2, 3, 4
 MMR_MAX_DEPTH = 2048    # SCANN_HIP_MMR_MAX_DEPTH
 CROWD_MAX_DIMS = 8      # SCANN_HIP_CROWD_MAX_DIMS
+MUTABLE_MAX_CAPACITY = 65536   # SCANN_HIP_MUTABLE_MAX_CAPACITY
+MUTABLE_MAX_K = 2048           # SCANN_HIP_MUTABLE_MAX_K
+MUTABLE_DELTA_TILE = 1024      # SCANN_HIP_MUTABLE_DELTA_TILE: delta rows sorted per workgroup of the delta scan
 
 _CODE_NAMES = {
     0: "Ok", 1: "Cancelled", 2: "Unknown", 3: "InvalidArgument", 4: "DeadlineExceeded",
@@ -49,6 +53,11 @@ EXPORTS = [
     "scann_hip_abi_layout", "scann_hip_lut16_quantize",
     "scann_hip_comm_unique_id", "scann_hip_comm_create", "scann_hip_comm_destroy",
     "scann_hip_txh_search_sharded_device", "scann_hip_comm_last_status", "scann_hip_comm_layout",
+    "scann_hip_mutable_create", "scann_hip_mutable_destroy", "scann_hip_mutable_add", "scann_hip_mutable_remove",
+    "scann_hip_mutable_update", "scann_hip_mutable_get", "scann_hip_mutable_exists", "scann_hip_mutable_size",
+    "scann_hip_mutable_pending", "scann_hip_mutable_needs_rebuild", "scann_hip_mutable_search",
+    "scann_hip_mutable_export_live", "scann_hip_mutable_rebase", "scann_hip_mutable_enable_timing",
+    "scann_hip_mutable_last_stage_ms",
 ]
 
 
@@ -220,6 +229,26 @@ def load():
     L.scann_hip_index_enable_timing.restype = None
     L.scann_hip_index_last_kernel_ms.restype = C.c_float
     L.scann_hip_index_last_kernel_ms.argtypes = [vp, C.POINTER(C.c_char_p)]
+    L.scann_hip_mutable_create.argtypes = [vp, vp, C.c_uint32, C.POINTER(vp)]
+    L.scann_hip_mutable_destroy.argtypes = [vp]
+    L.scann_hip_mutable_destroy.restype = None
+    L.scann_hip_mutable_add.argtypes = [vp, f32p, C.c_uint32, C.c_uint32, C.c_uint32, u32p]
+    L.scann_hip_mutable_remove.argtypes = [vp, u32p, C.c_uint32]
+    L.scann_hip_mutable_update.argtypes = [vp, u32p, f32p, C.c_uint32, C.c_uint32, C.c_uint32]
+    L.scann_hip_mutable_get.argtypes = [vp, C.c_uint32, f32p]
+    L.scann_hip_mutable_exists.argtypes = [vp, C.c_uint32]
+    L.scann_hip_mutable_size.restype = C.c_uint64
+    L.scann_hip_mutable_size.argtypes = [vp]
+    L.scann_hip_mutable_pending.restype = C.c_uint64
+    L.scann_hip_mutable_pending.argtypes = [vp]
+    L.scann_hip_mutable_needs_rebuild.argtypes = [vp, C.c_uint64]
+    L.scann_hip_mutable_search.argtypes = [vp, f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                           C.POINTER(SearchOpts), u32p, f32p, u32p]
+    L.scann_hip_mutable_export_live.argtypes = [vp, f32p, u32p, C.c_uint64, u64p]
+    L.scann_hip_mutable_rebase.argtypes = [vp, vp, u32p, C.c_uint64]
+    L.scann_hip_mutable_enable_timing.argtypes = [vp, C.c_int]
+    L.scann_hip_mutable_enable_timing.restype = None
+    L.scann_hip_mutable_last_stage_ms.argtypes = [vp, f32p]
     _lib = L
     return L
 
@@ -498,6 +527,114 @@ class Index:
         name = C.c_char_p()
         ms = load().scann_hip_index_last_kernel_ms(self.h, C.byref(name))
         return float(ms), (name.value or b"").decode()
+
+
+class Mutable:
+    """Owns one scann_hip_mutable handle over a base Index (kept alive here): MutableDataset + the rebuild counter of
+    IncrementalUpdater (mutator/mod.rs) on the device.  Ids are u32 and stable; every mutation takes one row / id or a
+    batch of them (applied in order, all or nothing)."""
+
+    def __init__(self, base, capacity, device=0):
+        h = vp()
+        check(load().scann_hip_mutable_create(context(device), base.h, int(capacity), C.byref(h)))
+        self.h = h
+        self.base = base
+        self.dim = base.dimensionality()
+        self.stride = compute_stride(self.dim)
+
+    def close(self):
+        if self.h:
+            load().scann_hip_mutable_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def _rows(rows):
+        r = f32(rows)
+        return r[None] if r.ndim == 1 else r
+
+    def add(self, rows):
+        """one row -> its id; [n][dim] rows -> uint32 ids"""
+        r = self._rows(rows)
+        ids = np.zeros(r.shape[0], np.uint32)
+        check(load().scann_hip_mutable_add(self.h, ptr(r, f32p), r.shape[0], r.shape[1], r.shape[1], ptr(ids, u32p)))
+        return int(ids[0]) if np.ndim(rows) == 1 else ids
+
+    def remove(self, ids):
+        i = np.ascontiguousarray(np.atleast_1d(ids), np.uint32)
+        check(load().scann_hip_mutable_remove(self.h, ptr(i, u32p), i.size))
+
+    def update(self, ids, rows):
+        i = np.ascontiguousarray(np.atleast_1d(ids), np.uint32)
+        r = self._rows(rows)
+        if r.shape[0] != i.size:
+            raise ValueError("update: %d ids, %d rows" % (i.size, r.shape[0]))
+        check(load().scann_hip_mutable_update(self.h, ptr(i, u32p), ptr(r, f32p), i.size, r.shape[1], r.shape[1]))
+
+    def get(self, id):
+        out = np.zeros(self.dim, np.float32)
+        check(load().scann_hip_mutable_get(self.h, int(id), ptr(out, f32p)))
+        return out
+
+    def exists(self, id):
+        return bool(load().scann_hip_mutable_exists(self.h, int(id)))
+
+    def size(self):
+        return int(load().scann_hip_mutable_size(self.h))
+
+    def pending(self):
+        return int(load().scann_hip_mutable_pending(self.h))
+
+    def needs_rebuild(self, threshold):
+        return bool(load().scann_hip_mutable_needs_rebuild(self.h, int(threshold)))
+
+    def search_batched(self, queries, k, opts=None, allow=None, allow_bits=None):
+        """out_idx holds external ids; `allow` is a uint64 bitmap over external ids, `allow_bits` its capacity"""
+        q = f32(queries)
+        if q.ndim == 1:
+            q = q[None]
+        nq, qs = q.shape
+        out_idx = np.full((nq, max(k, 1)), 0xFFFFFFFF, np.uint32)
+        out_dist = np.full((nq, max(k, 1)), np.inf, np.float32)
+        out_cnt = np.zeros(nq, np.uint32)
+        o = default_opts()
+        if opts is not None:        # a copy: the caller's opts (and a filter it carries) are left as they are
+            C.memmove(C.byref(o), C.byref(opts), C.sizeof(SearchOpts))
+        if allow is not None:
+            allow = np.ascontiguousarray(allow, np.uint64)
+            o.allow_bitmap, o.allow_bitmap_bits = ptr(allow, u64p), _allow_capacity(allow, allow_bits)
+        check(load().scann_hip_mutable_search(self.h, ptr(q, f32p), nq, qs, qs, k, C.byref(o), ptr(out_idx, u32p),
+                                              ptr(out_dist, f32p), ptr(out_cnt, u32p)))
+        return out_idx[:, :k], out_dist[:, :k], out_cnt
+
+    def export_live(self):
+        """(rows [n][dim], ids [n]) of every live row, ascending by id"""
+        n = self.size()
+        rows = np.zeros((max(n, 1), self.stride), np.float32)
+        ids = np.zeros(max(n, 1), np.uint32)
+        got = C.c_uint64(0)
+        check(load().scann_hip_mutable_export_live(self.h, ptr(rows, f32p), ptr(ids, u32p), rows.shape[0], C.byref(got)))
+        return np.ascontiguousarray(rows[:got.value, :self.dim]), ids[:got.value]
+
+    def rebase(self, new_base, base_ids=None):
+        """swap in `new_base`, whose row j has external id base_ids[j] (None = identity); the old base is released"""
+        b = None if base_ids is None else np.ascontiguousarray(base_ids, np.uint32)
+        check(load().scann_hip_mutable_rebase(self.h, new_base.h, ptr(b, u32p), new_base.size()))
+        self.base = new_base
+
+    def enable_timing(self, on=True):
+        load().scann_hip_mutable_enable_timing(self.h, 1 if on else 0)
+
+    def last_stage_ms(self):
+        """HIP-event ms of (base pass, delta scan, merge) of the last three-stage search"""
+        out = np.zeros(3, np.float32)
+        check(load().scann_hip_mutable_last_stage_ms(self.h, ptr(out, f32p)))
+        return tuple(float(x) for x in out)
 
 
 def _allow_capacity(allow, allow_bits):

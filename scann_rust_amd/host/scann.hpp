@@ -8,6 +8,7 @@
 //   scann::AsymmetricHasher(+Config)    hashes/hasher.rs:19-258
 //   scann::TreeXHybridSearcher(+Config) tree_x_hybrid/mod.rs:23-418
 //   scann::ScannBuilder / scann::Scann  scann.rs:35-56, 364-426
+//   scann::MutableIndex                 mutator/mod.rs:233-490 (MutableDataset), 492-560 (IncrementalUpdater's counter)
 //   scann::ScannError / ErrorCode       error.rs:10-147
 //
 // All distance computation and top-k selection runs in libscann_hip.so on the GPU.  Index
@@ -660,6 +661,7 @@ public:
     uint64_t dimensionality() const { return dataset_->dimensionality(); }
     DistanceMeasure distance_measure() const { return measure_; }
     const DenseDataset &dataset() const { return *dataset_; }
+    scann_hip_index *handle() const { return ix_.h; }   // (borrowed by MutableIndex)
 
 private:
     std::shared_ptr<DenseDataset> dataset_;
@@ -667,6 +669,126 @@ private:
     detail::IndexHandle ix_;
     detail::CrowdAttach crowd_;
     detail::CrowdMdAttach crowd_md_;
+};
+
+// ---- MutableIndex: MutableDataset (mutator/mod.rs:233-490) over a live brute-force index -------------
+// add / remove / update / get / exists / size / compact as MutableDataset names them, plus the rebuild counter of
+// IncrementalUpdater (:527-545).  Rows live on the device: an immutable base searcher, a live bitmap over its rows and a
+// delta segment of `capacity` rows (include/scann_hip.h "mutable indexes").  Ids are stable and never reused; search
+// returns them.  compact() exports the live rows, builds a new base from them and rebases: the delta is empty again and
+// removed ids are forgotten (NotFound), as after the reference's compact().  Brute-force bases only: the C ABI also takes
+// Tree-X-Hybrid and flat-hasher bases (scann_hip_mutable_create over their handles), which this mirror does not wrap.
+class MutableIndex {
+public:
+    MutableIndex(std::shared_ptr<BruteForceSearcher> base, size_t capacity, int device = 0)
+        : base_(std::move(base)), device_(device) {
+        check(scann_hip_mutable_create(context(device), base_->handle(), (uint32_t)std::min<size_t>(capacity, 0xFFFFFFFFu), &h_));
+    }
+    MutableIndex(const MutableIndex &) = delete;
+    MutableIndex &operator=(const MutableIndex &) = delete;
+    ~MutableIndex() { if (h_) scann_hip_mutable_destroy(h_); }   // (before base_: the handle borrows it)
+
+    DatapointIndex add(const std::vector<float> &data) {                       // :286-317
+        DatapointIndex id = 0;
+        check(scann_hip_mutable_add(h_, data.data(), 1, (uint32_t)data.size(), (uint32_t)data.size(), &id));
+        return id;
+    }
+    std::vector<DatapointIndex> add_batch(const std::vector<std::vector<float>> &rows) {
+        if (rows.empty()) return {};
+        uint32_t d;
+        auto flat = detail::flatten(rows, &d);
+        std::vector<DatapointIndex> ids(rows.size());
+        check(scann_hip_mutable_add(h_, flat.data(), (uint32_t)rows.size(), d, d, ids.data()));
+        return ids;
+    }
+    void remove(DatapointIndex index) { check(scann_hip_mutable_remove(h_, &index, 1)); }            // :320-330
+    void remove_batch(const std::vector<DatapointIndex> &ids) {
+        check(scann_hip_mutable_remove(h_, ids.data(), (uint32_t)ids.size()));
+    }
+    void update(DatapointIndex index, const std::vector<float> &data) {                             // :333-364
+        check(scann_hip_mutable_update(h_, &index, data.data(), 1, (uint32_t)data.size(), (uint32_t)data.size()));
+    }
+    void update_batch(const std::vector<DatapointIndex> &ids, const std::vector<std::vector<float>> &rows) {
+        if (ids.size() != rows.size()) throw ScannError::invalid_argument("update_batch: ids and rows differ in length");
+        if (rows.empty()) return;
+        uint32_t d;
+        auto flat = detail::flatten(rows, &d);
+        check(scann_hip_mutable_update(h_, ids.data(), flat.data(), (uint32_t)ids.size(), d, d));
+    }
+    // Option<Vec<f32>> (:367-375): false = None
+    bool get(DatapointIndex index, std::vector<float> *out) const {
+        std::vector<float> row(base_->dimensionality());
+        const int s = scann_hip_mutable_get(h_, index, row.data());
+        if (s == SCANN_HIP_NOT_FOUND) return false;
+        check(s);
+        if (out) *out = std::move(row);
+        return true;
+    }
+    bool exists(DatapointIndex index) const { return scann_hip_mutable_exists(h_, index) != 0; }
+    size_t size() const { return (size_t)scann_hip_mutable_size(h_); }
+    uint64_t dimensionality() const { return base_->dimensionality(); }
+    size_t pending() const { return (size_t)scann_hip_mutable_pending(h_); }
+    bool needs_rebuild(size_t threshold) const { return scann_hip_mutable_needs_rebuild(h_, threshold) != 0; }   // :527-545
+
+    // `filter` is asked about EXTERNAL ids below `filter_capacity` (ids at or past it are not allowed)
+    NNResultsVector search(const std::vector<float> &query, size_t k, const RestrictFilter *filter = nullptr,
+                           size_t filter_capacity = 0) const {
+        return search_batched({query}, k, filter, filter_capacity)[0];
+    }
+    std::vector<NNResultsVector> search_batched(const std::vector<std::vector<float>> &queries, size_t k,
+                                                const RestrictFilter *filter = nullptr, size_t filter_capacity = 0) const {
+        if (queries.empty()) return {};
+        uint32_t d;
+        auto flat = detail::flatten(queries, &d);
+        const uint32_t nq = (uint32_t)queries.size(), kk = (uint32_t)k;
+        scann_hip_search_opts o;
+        scann_hip_search_opts_default(&o);
+        std::vector<uint64_t> bits;
+        if (filter) {
+            bits = filter->to_bitmap(filter_capacity);
+            if (bits.empty()) bits.push_back(0);
+            o.allow_bitmap = bits.data();
+            o.allow_bitmap_bits = filter_capacity;
+        }
+        std::vector<uint32_t> idx((size_t)nq * std::max(1u, kk)), cnt(nq);
+        std::vector<float> dist((size_t)nq * std::max(1u, kk));
+        check(scann_hip_mutable_search(h_, flat.data(), nq, d, d, kk, &o, idx.data(), dist.data(), cnt.data()));
+        std::vector<NNResultsVector> out(nq);
+        for (uint32_t i = 0; i < nq; ++i)
+            for (uint32_t j = 0; j < cnt[i]; ++j) out[i].emplace_back(idx[(size_t)i * kk + j], dist[(size_t)i * kk + j]);
+        return out;
+    }
+
+    // every live row and its id, ascending by id
+    std::pair<DenseDataset, std::vector<DatapointIndex>> export_live() const {
+        const size_t n = size();
+        const uint32_t dim = (uint32_t)base_->dimensionality(), stride = scann_hip_compute_stride(dim);
+        std::vector<float> rows(std::max<size_t>(n, 1) * stride);
+        std::vector<DatapointIndex> ids(std::max<size_t>(n, 1));
+        uint64_t got = 0;
+        check(scann_hip_mutable_export_live(h_, rows.data(), ids.data(), std::max<size_t>(n, 1), &got));
+        ids.resize(got);
+        std::vector<float> flat(got * dim);
+        for (size_t i = 0; i < got; ++i) std::memcpy(&flat[i * dim], &rows[i * stride], (size_t)dim * 4);
+        return {got ? DenseDataset::from_flat(flat, dim) : DenseDataset(), std::move(ids)};
+    }
+    // new_base's row j has external id base_ids[j] (strictly ascending); nullptr = identity
+    void rebase(std::shared_ptr<BruteForceSearcher> new_base, const std::vector<DatapointIndex> *base_ids) {
+        check(scann_hip_mutable_rebase(h_, new_base->handle(), base_ids ? base_ids->data() : nullptr, new_base->dataset_size()));
+        base_ = std::move(new_base);   // (the old base is destroyed after the swap)
+    }
+    void compact() {                                                                                // :440-471
+        auto live = export_live();
+        if (live.second.empty()) throw ScannError::failed_precondition("compact: no live rows to build a base from");
+        auto nb = std::make_shared<BruteForceSearcher>(std::move(live.first), base_->distance_measure(), device_);
+        rebase(std::move(nb), &live.second);
+    }
+    const BruteForceSearcher &base() const { return *base_; }
+
+private:
+    std::shared_ptr<BruteForceSearcher> base_;
+    int device_;
+    scann_hip_mutable *h_ = nullptr;
 };
 
 // ---- AsymmetricHasher (hashes/hasher.rs) ---------------------------------------------------
