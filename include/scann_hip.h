@@ -624,6 +624,14 @@ int scann_hip_bf_write_file(const char *path, const float *data, uint64_t n, uin
                             uint32_t stride, int measure);
 int scann_hip_index_file_info(const char *path, scann_hip_file_info *out_info);
 int scann_hip_index_load_file(scann_hip_ctx *ctx, const char *path, scann_hip_index **out_index);
+/* Writes a HANDLE to the container: its arrays are read back from the device and stored in the sections of
+ * scann_hip_txh_write_file / scann_hip_bf_write_file (codes in the PackedCodes4Bit byte layout with codes_packed4 = 1
+ * when num_codes <= 16, one byte per subspace otherwise; a handle created without rows has no "data" section, and as
+ * it keeps no row count, n_rows is written as the smallest count that holds every datapoint index).  This is
+ * how an index made by scann_hip_fold_mutable is persisted; scann_hip_index_load_file on the file gives a handle that
+ * searches identically.  Any unsharded f32 brute-force, tree, hasher or Partitioned handle; quantized brute-force
+ * rows and shards (leaf_sizes_global) -> Unimplemented.  Transient host memory: one copy of the index. */
+int scann_hip_index_write_file(const scann_hip_index *index, const char *path);
 
 /* ---- building blocks exposed for parity tests / callers ---------------------- */
 /* TreePartitioner::partition for a batch (tree_partitioner.rs:196-229). */
@@ -847,11 +855,57 @@ int scann_hip_bf_assign_nearest(scann_hip_index *index, const float *centers, ui
  * not in base_ids (NotFound afterwards); next_index is kept (raised past the largest id if need be).  The caller builds
  * new_base from the exported rows however it likes and destroys the old base afterwards.
  * scann_hip_mutable_enable_timing / _last_stage_ms: HIP-event times (ms) of { base pass, delta scan, merge } of the
- * last search on the three-stage route (0 for a stage that did not run). */
+ * last search on the three-stage route (0 for a stage that did not run).
+ *
+ * fold (MutableDataset::compact, mod.rs:440-471, in ONE call and without the rows visiting the host): builds a new
+ * immutable base from the live rows ON THE DEVICE, keeping the trained model, and rebases the handle onto it.  Let the
+ * live ids in ascending order be i_0 < ... < i_{n'-1}, base and delta rows alike: new datapoint j is the live row of id
+ * i_j (export_live's order), out_base_ids[j] = i_j, rows are bit-copies with stride scann_hip_compute_stride(dim) and
+ * zero padding, gathered on the device.
+ *   - brute-force base: *out_new_base equals scann_hip_bf_create over those rows under the same measure in every
+ *     observable way, shortlist copies included.
+ *   - tree base: centres, codebook, use_residuals, partitions_to_search, multiplier and measure are unchanged.  A live
+ *     base row keeps its leaf and its code words bit for bit (never re-assigned, never re-encoded).  A delta row gets
+ *     token = TreePartitioner::partition(x, 1) with the arithmetic and tie / NaN rules of scann_hip_bf_assign_nearest
+ *     (lowest centre on ties, centre 0 when no distance compares below +inf) and the code Codebook::encode(x -
+ *     centre[token]) (encode(x) when use_residuals = 0; strict '<': lowest code on ties).  Leaf l holds
+ *     { j : token(j) = l } in ASCENDING j: array for array what TreeXHybridSearcher::build (mod.rs:162-204) gives over
+ *     the live rows with the model frozen.
+ *   - flat hasher base: codes'[j] = the old code of a base row, encode(x) of a delta row.
+ *   The derived structures (transposed centres, sparse-MFMA operand planes, 8-bit re-rank rows and their uniform-scale
+ *   decision, the sorted leaf sizes the planner reads) are built by the code the create functions run after their
+ *   upload.  Not re-trained, not re-balanced: after many folds of drifting data the caller still rebuilds.
+ * Handle state: rebased onto *out_new_base inside the call (the effects of scann_hip_mutable_rebase with out_base_ids):
+ * empty delta, every bit live, counter reset, next_index kept, every id keeps meaning the same row.  The caller owns
+ * *out_new_base and destroys the OLD base afterwards.  out_base_ids may be NULL; with out_base_ids != NULL,
+ * capacity_rows < n' -> ResourceExhausted with *out_n = n' and nothing changed.  *out_n = n' on success.
+ * Preconditions of a tree base, each FailedPrecondition with the handle untouched: n_local == n_rows; every old leaf
+ * strictly ascending in datapoint index (what the reference's build and trainer.py produce; checked on the device);
+ * the live rows reached through the leaves number what the live bitmap counts (no datapoint in two leaves or in none).
+ * No live row -> InvalidArgument ("Cannot build from empty dataset").  Any failure before the swap leaves the handle
+ * exactly as it was and frees what the call allocated.  The call holds the handle's mutex: searches and mutations
+ * wait.  Old and new index are resident at once: a transient 2x of the index's device memory until the caller
+ * destroys the old base.
+ * Device work: per SCANN_HIP_FOLD_CHUNK CSR positions one workgroup counts the surviving entries (one ballot per wave,
+ * kept as a bitmap over CSR positions) and checks the ascending rule; a scan over the chunk counts and one over the
+ * delta's per-leaf histogram give the new offsets; survivors and delta entries are scattered to
+ * new_off[leaf] + (survivors of the leaf before) + (delta entries of the leaf before) -- the cross counts by binary
+ * search, a leaf of any length being shared by as many workgroups as it has chunks; rows are gathered by export_live's
+ * kernels into device memory.  Device-to-host traffic: the L + 1 new offsets with one flag word, and what the create
+ * functions' second half reads.  out_base_ids comes from the host's own id tables.
+ * scann_hip_fold_mutable_stage_ms: times (ms) of the last successful fold's { row gather, assign + encode of the delta
+ * rows, count + scans, code / id scatter, finish half with the swap }.  The first four are HIP-event spans that hold the
+ * stage's kernels and nothing else: the call allocates and uploads everything before the first event, and the
+ * read-back of the offsets with its synchronisation lies between the third and the fourth span, inside none.  A span
+ * still counts the launch gaps between its kernels.  The fifth is taken by the host clock.  Zeros before the first
+ * fold; the three middle stages are exactly 0 for a brute-force base, which has no such kernels.
+ * The two fold functions are named scann_hip_fold_mutable*, not scann_hip_mutable_fold*: they belong to this block and
+ * are declared with it below. */
 typedef struct scann_hip_mutable scann_hip_mutable;
 #define SCANN_HIP_MUTABLE_MAX_CAPACITY 65536
 #define SCANN_HIP_MUTABLE_MAX_K 2048
 #define SCANN_HIP_MUTABLE_DELTA_TILE 1024
+#define SCANN_HIP_FOLD_CHUNK 1024
 int scann_hip_mutable_create(scann_hip_ctx *ctx, scann_hip_index *base, uint32_t capacity, scann_hip_mutable **out);
 void scann_hip_mutable_destroy(scann_hip_mutable *m);
 int scann_hip_mutable_add(scann_hip_mutable *m, const float *rows, uint32_t n, uint32_t row_stride, uint32_t dim,
@@ -872,6 +926,10 @@ int scann_hip_mutable_export_live(scann_hip_mutable *m, float *out_rows, uint32_
 int scann_hip_mutable_rebase(scann_hip_mutable *m, scann_hip_index *new_base, const uint32_t *base_ids, uint64_t n);
 void scann_hip_mutable_enable_timing(scann_hip_mutable *m, int enable);
 int scann_hip_mutable_last_stage_ms(scann_hip_mutable *m, float *out_ms3);
+/* fold (above): the compaction of a scann_hip_mutable handle */
+int scann_hip_fold_mutable(scann_hip_mutable *m, scann_hip_index **out_new_base, uint32_t *out_base_ids,
+                           uint64_t capacity_rows, uint64_t *out_n);
+int scann_hip_fold_mutable_stage_ms(scann_hip_mutable *m, float *out_ms5);
 
 /* ---- introspection ------------------------------------------------------------- */
 uint64_t scann_hip_index_size(const scann_hip_index *index);          /* Searcher::dataset_size */

@@ -12,8 +12,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "_obj")
 LIB = os.path.join(HERE, "libscann_hip.so")
-SOURCES = ["api.hip", "txh.hip", "bf.hip", "index_file.hip", "comm.hip", "crowd.hip", "mmr.hip", "mutable.hip"]
-HEADERS = ["common.h", "knobs.h", "txh.h", "bf.h", "comm.h", "crowd.h", "mmr.h", "mutable.h", "pair.h", "launch.h", os.path.join("..", "..", "include", "scann_hip.h")]
+SOURCES = ["api.hip", "txh.hip", "bf.hip", "index_file.hip", "comm.hip", "crowd.hip", "mmr.hip", "mutable.hip", "fold.hip"]
+HEADERS = ["common.h", "knobs.h", "txh.h", "bf.h", "comm.h", "crowd.h", "mmr.h", "mutable.h", "fold.h", "index_arrays.h", "pair.h", "launch.h", os.path.join("..", "..", "include", "scann_hip.h")]
 # -ffp-contract=off: the reference never contracts a*b+c (Rust); FMA is used only via
 # explicit fmaf()/MFMA where the reference uses _mm256_fmadd_ps.
 CFLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "-fPIC", "-Wall",
@@ -107,7 +107,7 @@ def build(force=False, verbose=False, extra_flags=()):
 HOST = os.path.join(HERE, "host")
 HOST_PROGRAMS = ["host_test", "ann_benchmark", "bf_filter_test",   # C++ mirror of the reference API, its benchmark CLI,
                  "crowding_test", "diversify_test",              # filtered brute force, crowding, multi-attribute
-                 "mutable_test"]                                 # crowding and MMR, mutable indexes through the mirror
+                 "mutable_test", "fold_test"]                    # crowding and MMR, mutable indexes and their fold through the mirror
 
 
 def build_host(verbose=False):

@@ -18,6 +18,7 @@
 #include "comm.h"
 #include "common.h"
 #include "crowd.h"
+#include "index_arrays.h"
 #include "mmr.h"
 #include "mutable.h"
 #include "knobs.h"
@@ -258,6 +259,7 @@ struct scann_hip_index {
     DeviceSlot dslots[kMaxDeviceSlots];
     uint64_t dslot_tick = 0;
     bool sharded = false;     // created with leaf_sizes_global: local leaves are a subset of the global stream
+    uint64_t n_rows = 0;      // rows of d_rows (0: the handle stores none)
 };
 
 static int set_device(const scann_hip_ctx *ctx) {
@@ -290,6 +292,160 @@ int scann::index_base_view(const scann_hip_index *ix, BaseView *v) {
         v->rows_csr = ix->tx.rows_csr != 0 && !ix->tx.ah_mode;   // (the flat hasher's one leaf is in datapoint order)
         v->partitioned = ix->tx.exact_scan != 0;
         v->sharded = ix->sharded;
+    }
+    return SCANN_HIP_OK;
+}
+
+static int index_common_init(scann_hip_index *ix);
+static int bf_finish(scann_hip_index *ix, uint64_t n, uint32_t dim, uint32_t stride, int measure);
+static int txh_finish(scann_hip_index *ix, const scann_hip_txh_desc *d, const std::vector<uint32_t> &off);
+
+int scann::index_fold_view(const scann_hip_index *ix, FoldView *v) {
+    if (!ix || !v || ix->kind != KIND_TXH) return fail(SCANN_HIP_INVALID_ARGUMENT, "not a tree / hasher index");
+    const TxhIndexDev &t = ix->tx;
+    *v = FoldView();
+    v->L = t.L; v->S = t.S; v->K = t.K; v->dsub = t.dsub; v->nw = t.nw;
+    v->ah = t.ah_mode; v->use_residuals = t.use_residuals;
+    v->n_local = t.n_local; v->n_rows = ix->n_rows;
+    v->leaf_off = t.leaf_off; v->leaf_ids = t.leaf_ids; v->codes = t.codes;
+    v->centers = t.centers; v->codebook = t.codebook;
+    return SCANN_HIP_OK;
+}
+
+// scalar fields of the descriptor a tree / hasher handle was created from
+static void txh_desc_of(const scann_hip_index *ix, scann_hip_txh_desc *d) {
+    const TxhIndexDev &t = ix->tx;
+    std::memset(d, 0, sizeof(*d));
+    d->n_rows = ix->n_rows;
+    d->n_local = t.n_local;
+    d->dim = t.dim;
+    d->stride = t.stride;
+    d->num_partitions = t.ah_mode ? 0u : t.L;
+    d->num_subspaces = t.S;
+    d->num_codes = t.exact_scan ? 0u : t.K;
+    d->dims_per_subspace = t.dsub;
+    d->distance_measure = t.measure;
+    d->data_is_csr_order = (t.rows_csr && !t.ah_mode) ? 1 : 0;
+    d->codes_packed4 = (!t.exact_scan && t.code_bits == 4) ? 1 : 0;
+    d->use_residuals = t.use_residuals;
+    d->partitions_to_search = t.ah_mode ? 0u : ix->default_P;
+    d->pre_reorder_multiplier = ix->multiplier;
+}
+
+int scann::index_fold_bf(const scann_hip_index *old, DevBuf &rows, uint64_t n, uint32_t stride, scann_hip_index **out) {
+    DevBuf held;
+    held.take(rows);
+    if (!old || !out || old->kind != KIND_BF) return fail(SCANN_HIP_INVALID_ARGUMENT, "not a brute-force index");
+    SCANN_TRY(set_device(old->ctx));
+    auto *ix = new scann_hip_index();
+    ix->ctx = old->ctx;
+    ix->kind = KIND_BF;
+    ix->bf_rows.take(held);
+    int s = index_common_init(ix);
+    if (s == SCANN_HIP_OK) s = bf_finish(ix, n, old->bf.dim, stride, old->bf.measure);
+    if (s != SCANN_HIP_OK) {
+        scann_hip_index_destroy(ix);
+        return s;
+    }
+    *out = ix;
+    return SCANN_HIP_OK;
+}
+
+int scann::index_fold_txh(const scann_hip_index *old, DevBuf &rows, DevBuf &codes, DevBuf &leaf_off, DevBuf &leaf_ids,
+                          const std::vector<uint32_t> &off, uint64_t n, uint32_t stride, scann_hip_index **out) {
+    DevBuf h_rows, h_codes, h_off, h_ids;
+    h_rows.take(rows);
+    h_codes.take(codes);
+    h_off.take(leaf_off);
+    h_ids.take(leaf_ids);
+    if (!old || !out || old->kind != KIND_TXH) return fail(SCANN_HIP_INVALID_ARGUMENT, "not a tree / hasher index");
+    const TxhIndexDev &t = old->tx;
+    if (off.size() != (size_t)t.L + 1) return fail(SCANN_HIP_INTERNAL, "fold: leaf offsets of the wrong length");
+    SCANN_TRY(set_device(old->ctx));
+    auto *ix = new scann_hip_index();
+    ix->ctx = old->ctx;
+    ix->kind = KIND_TXH;
+    auto bail = [&](int s) {
+        scann_hip_index_destroy(ix);
+        return s;
+    };
+    int s = index_common_init(ix);
+    if (s != SCANN_HIP_OK) return bail(s);
+    ix->d_rows.take(h_rows);
+    ix->d_codes.take(h_codes);
+    ix->d_leaf_off.take(h_off);
+    if (!t.ah_mode) ix->d_leaf_ids.take(h_ids);
+    scann_hip_txh_desc d;
+    txh_desc_of(old, &d);
+    d.n_rows = n;
+    d.n_local = n;
+    d.stride = stride;
+    d.data = ix->d_rows.as<float>();   // (txh_finish asks only whether rows are stored)
+    ix->n_rows = n;
+    std::vector<uint32_t> gsz(t.L);
+    for (uint32_t l = 0; l < t.L; ++l) gsz[l] = off[l + 1] - off[l];
+    if ((s = upload(ix->d_leaf_gsize, gsz.data(), (size_t)t.L * 4)) != SCANN_HIP_OK) return bail(s);
+    const size_t cb_bytes = (size_t)t.S * t.K * t.dsub * 4;
+    if ((s = ix->d_codebook.ensure(cb_bytes)) != SCANN_HIP_OK) return bail(s);
+    if (hipMemcpy(ix->d_codebook.p, t.codebook, cb_bytes, hipMemcpyDeviceToDevice) != hipSuccess)
+        return bail(fail(SCANN_HIP_INTERNAL, "fold: codebook copy failed"));
+    if (!t.ah_mode) {
+        const size_t c_bytes = (size_t)t.L * t.dim * 4;
+        if ((s = ix->d_centers.ensure(c_bytes)) != SCANN_HIP_OK) return bail(s);
+        if (hipMemcpy(ix->d_centers.p, t.centers, c_bytes, hipMemcpyDeviceToDevice) != hipSuccess)
+            return bail(fail(SCANN_HIP_INTERNAL, "fold: centre copy failed"));
+    }
+    if ((s = txh_finish(ix, &d, off)) != SCANN_HIP_OK) return bail(s);
+    *out = ix;
+    return SCANN_HIP_OK;
+}
+
+int scann::index_download(const scann_hip_index *ix, IndexHostArrays *o) {
+    if (!ix || !o) return fail(SCANN_HIP_INVALID_ARGUMENT, "index is null");
+    SCANN_TRY(set_device(ix->ctx));
+    auto down = [](auto &vec, const void *src, size_t count) -> int {
+        vec.resize(count);
+        if (count) SCANN_HIP_CHECK(hipMemcpy(vec.data(), src, count * sizeof(vec[0]), hipMemcpyDeviceToHost));
+        return SCANN_HIP_OK;
+    };
+    scann_hip_txh_desc &d = o->d;
+    if (ix->kind == KIND_BF) {
+        if (ix->bf.fmt) return fail(SCANN_HIP_UNIMPLEMENTED, "index_write_file: quantized brute-force rows are not written");
+        o->brute_force = true;
+        std::memset(&d, 0, sizeof(d));
+        d.n_rows = d.n_local = ix->bf.n;
+        d.dim = ix->bf.dim;
+        d.stride = ix->bf.stride;
+        d.distance_measure = ix->bf.measure;
+        SCANN_TRY(down(o->data, ix->bf.rows, (size_t)ix->bf.n * ix->bf.stride));
+        d.data = o->data.data();
+        return SCANN_HIP_OK;
+    }
+    if (ix->sharded) return fail(SCANN_HIP_UNIMPLEMENTED, "index_write_file: shards (leaf_sizes_global) are not written");
+    const TxhIndexDev &t = ix->tx;
+    o->brute_force = false;
+    txh_desc_of(ix, &d);
+    if (t.rows) {
+        SCANN_TRY(down(o->data, t.rows, (size_t)ix->n_rows * t.stride));
+        d.data = o->data.data();
+    }
+    if (!t.ah_mode) {
+        SCANN_TRY(down(o->centers, t.centers, (size_t)t.L * t.dim));
+        SCANN_TRY(down(o->leaf_offsets, t.leaf_off, (size_t)t.L + 1));
+        SCANN_TRY(down(o->leaf_ids, t.leaf_ids, (size_t)t.n_local));
+        d.centers = o->centers.data();
+        d.leaf_offsets = o->leaf_offsets.data();
+        d.leaf_ids = o->leaf_ids.data();
+    }
+    if (!t.rows) {   // a handle created without rows keeps no row count: the smallest that holds every datapoint index
+        d.n_rows = t.n_local;
+        for (uint32_t id : o->leaf_ids) d.n_rows = std::max<uint64_t>(d.n_rows, (uint64_t)id + 1);
+    }
+    if (!t.exact_scan) {
+        SCANN_TRY(down(o->codebook, t.codebook, (size_t)t.S * t.K * t.dsub));
+        SCANN_TRY(down(o->codes, t.codes, (size_t)t.n_local * t.nw));
+        d.codebook = o->codebook.data();
+        d.codes = reinterpret_cast<const uint8_t *>(o->codes.data());   // little-endian words == the file's byte layout
     }
     return SCANN_HIP_OK;
 }
@@ -429,10 +585,21 @@ int scann_hip_bf_create(scann_hip_ctx *ctx, const float *data, uint64_t n, uint3
     ix->kind = KIND_BF;
     int s = index_common_init(ix);
     if (s == SCANN_HIP_OK) s = upload(ix->bf_rows, data, (size_t)n * stride * sizeof(float));
+    if (s == SCANN_HIP_OK) s = bf_finish(ix, n, dim, stride, measure);
     if (s != SCANN_HIP_OK) {
         scann_hip_index_destroy(ix);
         return s;
     }
+    *out = ix;
+    return SCANN_HIP_OK;
+}
+
+}  // extern "C"
+
+// The second half of scann_hip_bf_create: the f32 rows are in ix->bf_rows on the device.  scann_hip_fold_mutable ends
+// here too, with rows its gather wrote.  The caller destroys the handle on failure.
+static int bf_finish(scann_hip_index *ix, uint64_t n, uint32_t dim, uint32_t stride, int measure) {
+    int s = SCANN_HIP_OK;
     ix->bf.rows = ix->bf_rows.as<float>();
     ix->bf.n = n;
     ix->bf.dim = dim;
@@ -445,10 +612,7 @@ int scann_hip_bf_create(scann_hip_ctx *ctx, const float *data, uint64_t n, uint3
     if (n > 0 && n <= kSmallMaxStream) {   // view for the three-launch small-batch pipeline (txh.hip)
         const uint32_t leaf[3] = {0u, (uint32_t)n, (uint32_t)n};   // leaf_off[0..1], leaf_gsize[0]
         s = upload(ix->bf_leaf, leaf, sizeof(leaf));
-        if (s != SCANN_HIP_OK) {
-            scann_hip_index_destroy(ix);
-            return s;
-        }
+        if (s != SCANN_HIP_OK) return s;
         TxhIndexDev &t = ix->bfx;
         t.dim = dim; t.stride = stride; t.L = 1; t.S = 0; t.K = 16; t.dsub = 0; t.nw = 0; t.code_bits = 4; t.kp = 16;
         t.n_local = n; t.centers = nullptr; t.leaf_off = ix->bf_leaf.as<uint32_t>();
@@ -459,19 +623,17 @@ int scann_hip_bf_create(scann_hip_ctx *ctx, const float *data, uint64_t n, uint3
     if ((stride & 3u) == 0) {   // bf16 copy + norms for the shortlist path (big indexes only)
         s = bf_build_shortlist_data(ix->bf, ix->bf_rows_b, ix->bf_rows_bl, ix->bf_norm2, &ix->bf.max_norm,
                                     ix->stream);
-        if (s != SCANN_HIP_OK) {
-            scann_hip_index_destroy(ix);
-            return s;
-        }
+        if (s != SCANN_HIP_OK) return s;
         if (ix->bf_rows_b.p) {
             ix->bf.rows_b = ix->bf_rows_b.as<uint16_t>();
             ix->bf.rows_bl = ix->bf_rows_bl.as<uint16_t>();
             ix->bf.norm2 = ix->bf_norm2.as<float>();
         }
     }
-    *out = ix;
     return SCANN_HIP_OK;
 }
+
+extern "C" {
 
 // Rows the caller stores quantized (scann_hip.h): uploaded as given, no f32 copy and no small-batch view (bfx stays
 // empty); the bf16 shortlist reads the rows themselves and needs only their squared norms.
@@ -619,10 +781,6 @@ int scann::txh_create_checked(scann_hip_ctx *ctx, const scann_hip_txh_desc *d, s
         for (uint32_t l = 0; l < L; ++l)
             gsz[l] = d->leaf_sizes_global ? d->leaf_sizes_global[l] : off[l + 1] - off[l];
     }
-    ix->local_sizes_desc.resize(L);
-    for (uint32_t l = 0; l < L; ++l) ix->local_sizes_desc[l] = off[l + 1] - off[l];
-    std::sort(ix->local_sizes_desc.begin(), ix->local_sizes_desc.end(), std::greater<uint32_t>());
-
     // packed codes: [n][nw] words, nibble nb of word wi = subspace 8*wi+nb
     // (PackedCodes4Bit layout, hashes/lut16.rs:43-61, read little-endian)
     std::vector<uint32_t> words;
@@ -675,6 +833,29 @@ int scann::txh_create_checked(scann_hip_ctx *ctx, const scann_hip_txh_desc *d, s
             return bail(s);
     }
 
+    ix->n_rows = d->data ? d->n_rows : 0;
+    if ((s = txh_finish(ix, d, off)) != SCANN_HIP_OK) return bail(s);
+    *out = ix;
+    return SCANN_HIP_OK;
+}
+
+// The second half of every tree / hasher create: the handle's arrays are on the device (d_leaf_off, d_leaf_gsize,
+// d_codes, d_codebook, d_centers, d_leaf_ids, d_rows), `off` is the host copy of the leaf offsets.  Reads the scalar
+// fields of `d` and whether d->data / d->leaf_sizes_global are set, never the host arrays: scann_hip_fold_mutable ends
+// here too, with arrays its kernels wrote.  The caller destroys the handle on failure.
+static int txh_finish(scann_hip_index *ix, const scann_hip_txh_desc *d, const std::vector<uint32_t> &off) {
+    const bool ah = d->num_partitions == 0;
+    const bool exact = d->num_subspaces == 0;
+    const uint32_t S = d->num_subspaces, K = exact ? 16u : d->num_codes, dsub = d->dims_per_subspace;
+    const uint32_t bits = K <= 16 ? 4u : 8u;
+    const uint32_t L = ah ? 1u : d->num_partitions;
+    const uint32_t nw = bits == 4 ? S / 8 : S / 4;
+    const uint64_t n = d->n_local;
+    int s = SCANN_HIP_OK;
+    ix->local_sizes_desc.resize(L);
+    for (uint32_t l = 0; l < L; ++l) ix->local_sizes_desc[l] = off[l + 1] - off[l];
+    std::sort(ix->local_sizes_desc.begin(), ix->local_sizes_desc.end(), std::greater<uint32_t>());
+
     TxhIndexDev &t = ix->tx;
     t.dim = d->dim;
     t.stride = d->stride;
@@ -691,11 +872,11 @@ int scann::txh_create_checked(scann_hip_ctx *ctx, const scann_hip_txh_desc *d, s
     t.centers_pitch = 0;
     if (!ah && L <= 4096) {   // transposed centroids: the small-batch leaf selection reads them coalesced (txh.hip)
         const uint32_t pitch = (L + 63u) & ~63u;
-        if ((s = ix->d_centers_t.ensure((size_t)pitch * d->dim * 4)) != SCANN_HIP_OK) return bail(s);
+        if ((s = ix->d_centers_t.ensure((size_t)pitch * d->dim * 4)) != SCANN_HIP_OK) return s;
         if ((s = launch_transpose_centers(ix->d_centers.as<float>(), L, d->dim, pitch, ix->d_centers_t.as<float>(),
                                           ix->stream)) != SCANN_HIP_OK)
-            return bail(s);
-        if (hipStreamSynchronize(ix->stream) != hipSuccess) return bail(fail(SCANN_HIP_INTERNAL, "centroid transpose failed"));
+            return s;
+        if (hipStreamSynchronize(ix->stream) != hipSuccess) return fail(SCANN_HIP_INTERNAL, "centroid transpose failed");
         t.centers_t = ix->d_centers_t.as<float>();
         t.centers_pitch = pitch;
     }
@@ -709,10 +890,10 @@ int scann::txh_create_checked(scann_hip_ctx *ctx, const scann_hip_txh_desc *d, s
     // per point.  SCANN_HIP_SMFMAC=0: not built, the dense integer-MFMA prefilter is used instead.
     {
         if (!exact && bits == 4 && kn.smfmac) {
-            if ((s = ix->d_codes_sp.ensure((size_t)n * sp_words(S) * 4)) != SCANN_HIP_OK) return bail(s);
+            if ((s = ix->d_codes_sp.ensure((size_t)n * sp_words(S) * 4)) != SCANN_HIP_OK) return s;
             if ((s = launch_codes_sp_build(ix->d_codes.as<uint32_t>(), n, S, ix->d_codes_sp.as<uint32_t>(), ix->stream)) != SCANN_HIP_OK)
-                return bail(s);
-            if (hipStreamSynchronize(ix->stream) != hipSuccess) return bail(fail(SCANN_HIP_INTERNAL, "code plane build failed"));
+                return s;
+            if (hipStreamSynchronize(ix->stream) != hipSuccess) return fail(SCANN_HIP_INTERNAL, "code plane build failed");
             t.codes_sp = ix->d_codes_sp.as<uint32_t>();
         }
     }
@@ -734,27 +915,27 @@ int scann::txh_create_checked(scann_hip_ctx *ctx, const scann_hip_txh_desc *d, s
         const bool want = d->data && !exact && d->distance_measure == SCANN_HIP_SQUARED_L2 && (d->dim & 15u) == 0 &&
                           (mode == 2 || (mode == 1 && d->n_rows >= 65536));
         if (want) {
-            if ((s = ix->d_rows8.ensure((size_t)d->n_rows * d->dim)) != SCANN_HIP_OK) return bail(s);
-            if ((s = ix->d_rows8_meta.ensure((size_t)d->n_rows * 8)) != SCANN_HIP_OK) return bail(s);
+            if ((s = ix->d_rows8.ensure((size_t)d->n_rows * d->dim)) != SCANN_HIP_OK) return s;
+            if ((s = ix->d_rows8_meta.ensure((size_t)d->n_rows * 8)) != SCANN_HIP_OK) return s;
             if (fp8) {
                 DevBuf mism;
-                if ((s = mism.ensure(4)) != SCANN_HIP_OK) return bail(s);
-                if (hipMemsetAsync(mism.p, 0, 4, ix->stream) != hipSuccess) return bail(fail(SCANN_HIP_INTERNAL, "memset failed"));
+                if ((s = mism.ensure(4)) != SCANN_HIP_OK) return s;
+                if (hipMemsetAsync(mism.p, 0, 4, ix->stream) != hipSuccess) return fail(SCANN_HIP_INTERNAL, "memset failed");
                 if ((s = launch_rows_fp8_build(ix->d_rows.as<float>(), d->n_rows, d->dim, d->stride,
                                                ix->d_rows8.as<uint8_t>(), ix->d_rows8_meta.p, mism.as<uint32_t>(),
                                                ix->stream)) != SCANN_HIP_OK)
-                    return bail(s);
+                    return s;
                 uint32_t bad = 0;
                 if (hipMemcpyAsync(&bad, mism.p, 4, hipMemcpyDeviceToHost, ix->stream) != hipSuccess ||
                     hipStreamSynchronize(ix->stream) != hipSuccess)
-                    return bail(fail(SCANN_HIP_INTERNAL, "fp8 row build failed"));
-                if (bad) return bail(fail(SCANN_HIP_INTERNAL, "v_cvt_f32_fp8 decodes the reference's E4M3 codes differently"));
+                    return fail(SCANN_HIP_INTERNAL, "fp8 row build failed");
+                if (bad) return fail(SCANN_HIP_INTERNAL, "v_cvt_f32_fp8 decodes the reference's E4M3 codes differently");
                 t.rows8_fmt = 1;
             } else {
                 if ((s = launch_rows_i8_build(ix->d_rows.as<float>(), d->n_rows, d->dim, d->stride, ix->d_rows8.as<int8_t>(),
                                               ix->d_rows8_meta.p, ix->stream)) != SCANN_HIP_OK)
-                    return bail(s);
-                if (hipStreamSynchronize(ix->stream) != hipSuccess) return bail(fail(SCANN_HIP_INTERNAL, "int8 row build failed"));
+                    return s;
+                if (hipStreamSynchronize(ix->stream) != hipSuccess) return fail(SCANN_HIP_INTERNAL, "int8 row build failed");
                 // Rows of EQUAL magnitude (largest per-row scale within 2 % of the mean scale, every row finite): ONE
                 // scale and ONE error bound (the largest ||x - x~||) for all rows, so that the filter pass gathers a
                 // candidate's 128-byte row and nothing else -- the per-row {scale, error} pair is a second random
@@ -766,7 +947,7 @@ int scann::txh_create_checked(scann_hip_ctx *ctx, const scann_hip_txh_desc *d, s
                 if (kn.rerank_uniform != 0) {
                     std::vector<float> meta((size_t)d->n_rows * 2);
                     if (hipMemcpy(meta.data(), ix->d_rows8_meta.p, meta.size() * 4, hipMemcpyDeviceToHost) != hipSuccess)
-                        return bail(fail(SCANN_HIP_INTERNAL, "int8 row meta copy failed"));
+                        return fail(SCANN_HIP_INTERNAL, "int8 row meta copy failed");
                     double sum = 0.0;
                     float smax = 0.0f;
                     bool finite = true;
@@ -779,9 +960,9 @@ int scann::txh_create_checked(scann_hip_ctx *ctx, const scann_hip_txh_desc *d, s
                     if (finite && d->n_rows > 0 && (double)smax <= spread * (sum / (double)d->n_rows)) {
                         if ((s = launch_rows_i8_build(ix->d_rows.as<float>(), d->n_rows, d->dim, d->stride, ix->d_rows8.as<int8_t>(),
                                                       ix->d_rows8_meta.p, ix->stream, smax)) != SCANN_HIP_OK)
-                            return bail(s);
+                            return s;
                         if (hipMemcpy(meta.data(), ix->d_rows8_meta.p, meta.size() * 4, hipMemcpyDeviceToHost) != hipSuccess)
-                            return bail(fail(SCANN_HIP_INTERNAL, "int8 row meta copy failed"));
+                            return fail(SCANN_HIP_INTERNAL, "int8 row meta copy failed");
                         float emax = 0.0f;
                         for (uint64_t r = 0; r < d->n_rows; ++r) emax = std::max(emax, meta[2 * r + 1]);
                         if (emax < INFINITY) {
@@ -804,7 +985,6 @@ int scann::txh_create_checked(scann_hip_ctx *ctx, const scann_hip_txh_desc *d, s
     ix->sharded = d->leaf_sizes_global != nullptr;
     ix->default_P = ah ? 1u : std::max(1u, d->partitions_to_search);
     ix->multiplier = d->pre_reorder_multiplier;
-    *out = ix;
     return SCANN_HIP_OK;
 }
 

@@ -88,6 +88,9 @@ int bf_search_radius_host(const BfIndexDev &ix, BfWorkspace &w, const float *que
 // ties): TreePartitioner::partition(x, 1) / KMeans::assign_clusters.
 int bf_assign_nearest_host(const BfIndexDev &ix, const float *centers, uint32_t k, uint32_t *out_idx,
                            float *out_dist, hipStream_t stream);
+// The same with centres, assignments and (optional) distances on the device; enqueue only.  Reads ix.rows, n, dim, stride.
+int bf_assign_nearest_device(const BfIndexDev &ix, const float *d_centers, uint32_t k, uint32_t *d_out_idx,
+                             float *d_out_dist, hipStream_t stream);
 
 // K-means over the rows of the index (optionally the column window [col_offset, col_offset +
 // sub_dim)): k-means++ seeding (trees/kmeans.rs:295-349, splitmix64 stream) and the Lloyd loop of

@@ -2344,6 +2344,16 @@ int bf_search_radius_host(const BfIndexDev &ix, BfWorkspace &w, const float *que
     return SCANN_HIP_OK;
 }
 
+// centres, assignments and (optional) distances on the device; enqueue only.  Reads ix.rows, n, dim and stride.
+int bf_assign_nearest_device(const BfIndexDev &ix, const float *d_centers, uint32_t k, uint32_t *d_out_idx,
+                             float *d_out_dist, hipStream_t st) {
+    if (ix.n == 0) return SCANN_HIP_OK;
+    const uint32_t dimp = (ix.dim + 3u) & ~3u;
+    const size_t lds = (size_t)kAsgTC * dimp * sizeof(float);
+    return launch(assign_nearest_kernel, dim3((uint32_t)ceil_div_u64(ix.n, 256)), dim3(256), lds, st, ix, d_centers, k,
+                  d_out_idx, d_out_dist);
+}
+
 int bf_assign_nearest_host(const BfIndexDev &ix, const float *centers, uint32_t k, uint32_t *out_idx,
                            float *out_dist, hipStream_t st) {
     if (ix.n == 0) return SCANN_HIP_OK;
@@ -2351,10 +2361,7 @@ int bf_assign_nearest_host(const BfIndexDev &ix, const float *centers, uint32_t 
     SCANN_TRY(upload(dc, centers, (size_t)k * ix.dim * 4));
     SCANN_TRY(di.ensure((size_t)ix.n * 4));
     if (out_dist) SCANN_TRY(dd.ensure((size_t)ix.n * 4));
-    const uint32_t dimp = (ix.dim + 3u) & ~3u;
-    const size_t lds = (size_t)kAsgTC * dimp * sizeof(float);
-    SCANN_TRY(launch(assign_nearest_kernel, dim3((uint32_t)ceil_div_u64(ix.n, 256)), dim3(256), lds, st, ix,
-                     dc.as<float>(), k, di.as<uint32_t>(), out_dist ? dd.as<float>() : nullptr));
+    SCANN_TRY(bf_assign_nearest_device(ix, dc.as<float>(), k, di.as<uint32_t>(), out_dist ? dd.as<float>() : nullptr, st));
     SCANN_HIP_CHECK(hipMemcpyAsync(out_idx, di.p, (size_t)ix.n * 4, hipMemcpyDeviceToHost, st));
     if (out_dist) SCANN_HIP_CHECK(hipMemcpyAsync(out_dist, dd.p, (size_t)ix.n * 4, hipMemcpyDeviceToHost, st));
     SCANN_HIP_CHECK(hipStreamSynchronize(st));

@@ -55,6 +55,14 @@ struct DevBuf {
         bytes = need;
         return SCANN_HIP_OK;
     }
+    // takes o's allocation (o is left empty)
+    void take(DevBuf &o) {
+        release();
+        p = o.p;
+        bytes = o.bytes;
+        o.p = nullptr;
+        o.bytes = 0;
+    }
     template <typename T>
     T *as() const { return static_cast<T *>(p); }
 };

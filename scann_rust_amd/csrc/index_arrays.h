@@ -1,0 +1,18 @@
+// index_arrays.h -- a handle's arrays read back to the host (api.hip), for scann_hip_index_write_file (index_file.hip).
+#pragma once
+#include <vector>
+
+#include "common.h"
+
+namespace scann {
+
+// Host copies of a handle's arrays, as scann_hip_index_write_file stores them (index_file.hip).
+struct IndexHostArrays {
+    bool brute_force = false;
+    scann_hip_txh_desc d{};   // scalar fields; the pointers address the vectors below
+    std::vector<float> data, centers, codebook;
+    std::vector<uint32_t> leaf_offsets, leaf_ids, codes;   // codes: the device's packed words
+};
+int index_download(const scann_hip_index *ix, IndexHostArrays *out);
+
+}  // namespace scann

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "common.h"
+#include "index_arrays.h"
 #include "knobs.h"
 #include "launch.h"
 
@@ -238,6 +239,15 @@ int scann_hip_bf_write_file(const char *path, const float *data, uint64_t n, uin
     std::vector<PendingSection> secs;
     secs.push_back({"data", DT_F32, data, n * stride * 4});
     return write_container(path, h, secs);
+}
+
+int scann_hip_index_write_file(const scann_hip_index *index, const char *path) {
+    if (!index || !path) return fail(SCANN_HIP_INVALID_ARGUMENT, "index/path is null");
+    scann::IndexHostArrays a;
+    SCANN_TRY(scann::index_download(index, &a));
+    if (a.brute_force)
+        return scann_hip_bf_write_file(path, a.d.data, a.d.n_rows, a.d.dim, a.d.stride, a.d.distance_measure);
+    return scann_hip_txh_write_file(path, &a.d);
 }
 
 int scann_hip_index_file_info(const char *path, scann_hip_file_info *out) {

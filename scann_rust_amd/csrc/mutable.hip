@@ -19,6 +19,7 @@
 //                              word (one workgroup), live base rows gathered to their final position (rank among live
 //                              base rows + delta ids below), delta rows scattered between them
 #include <algorithm>
+#include <chrono>
 #include <cstring>
 #include <memory>
 #include <mutex>
@@ -27,10 +28,13 @@
 #include <unordered_set>
 #include <vector>
 
+#include "bf.h"
 #include "comm.h"
+#include "fold.h"
 #include "launch.h"
 #include "mutable.h"
 #include "pair.h"
+#include "txh.h"
 
 namespace scann {
 
@@ -287,6 +291,8 @@ struct scann_hip_mutable {
     bool timing = false;
     hipEvent_t ev[6] = {};
     bool ran[3] = {false, false, false};
+    hipEvent_t fev[6] = {};    // fold: created by the first fold
+    float fold_ms[5] = {};     // stages of the last fold (scann_hip_fold_mutable_stage_ms)
 
     uint32_t n_delta() const { return (uint32_t)delta_ids.size(); }
     static constexpr uint64_t kNoRow = ~0ull;
@@ -432,6 +438,83 @@ int delta_and_merge(scann_hip_mutable *m, uint32_t nq, uint32_t q_stride, uint32
     return SCANN_HIP_OK;
 }
 
+// The live rows in ascending external id (export_live's and fold's order): order / sorted = the delta slots / ids in
+// ascending id, dest[slot] = final position of a delta row, out_ids[position] = id (live base ids and delta ids merged).
+struct LiveOrder {
+    std::vector<uint32_t> order, sorted, dest;
+};
+
+void plan_live_order(const scann_hip_mutable *m, LiveOrder *lo, uint32_t *out_ids) {
+    const uint32_t nd = m->n_delta();
+    std::vector<uint32_t> &order = lo->order, &sorted = lo->sorted, &dest = lo->dest;
+    order.resize(nd);
+    sorted.resize(nd);
+    dest.assign(std::max(nd, 1u), 0u);
+    for (uint32_t s = 0; s < nd; ++s) order[s] = s;
+    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return m->delta_ids[a] < m->delta_ids[b]; });
+    for (uint32_t i = 0; i < nd; ++i) sorted[i] = m->delta_ids[order[i]];
+    uint64_t pos = 0;
+    uint32_t di = 0;
+    for (uint64_t j = 0; j < m->n_base; ++j) {
+        if ((j & 63u) == 0 && m->live[j >> 6] == 0) {   // (a word of removed rows)
+            j += 63;
+            continue;
+        }
+        if (!m->bit(j)) continue;
+        const uint32_t ext = m->identity ? (uint32_t)j : m->base_ids[j];
+        while (di < nd && sorted[di] < ext) {
+            dest[order[di]] = (uint32_t)pos;
+            out_ids[pos++] = sorted[di++];
+        }
+        out_ids[pos++] = ext;
+    }
+    while (di < nd) {
+        dest[order[di]] = (uint32_t)pos;
+        out_ids[pos++] = sorted[di++];
+    }
+}
+
+// What gather_live_rows reads, allocated and uploaded on the handle's stream: the sorted delta ids (x_sorted) and the
+// delta rows' destinations (x_dest); room for the word-prefix of the live bitmap (x_prefix).
+int gather_prepare(scann_hip_mutable *m, const LiveOrder &lo) {
+    const uint32_t nd = m->n_delta();
+    const uint64_t words = (m->n_base + 63) / 64;
+    SCANN_TRY(m->x_prefix.ensure(std::max<uint64_t>(words, 1) * 4));
+    SCANN_TRY(m->x_sorted.ensure(std::max<size_t>(nd, 1) * 4));
+    SCANN_TRY(m->x_dest.ensure(std::max<size_t>(nd, 1) * 4));
+    if (nd) {
+        SCANN_HIP_CHECK(hipMemcpyAsync(m->x_sorted.p, lo.sorted.data(), (size_t)nd * 4, hipMemcpyHostToDevice, m->st));
+        SCANN_HIP_CHECK(hipMemcpyAsync(m->x_dest.p, lo.dest.data(), (size_t)nd * 4, hipMemcpyHostToDevice, m->st));
+    }
+    return SCANN_HIP_OK;
+}
+
+// The live rows in that order into out ([live rows][stride] floats, device memory), on the handle's stream, after
+// gather_prepare: kernel launches only.  The word-prefix of the live bitmap (x_prefix) and the sorted delta ids
+// (x_sorted) stay on the device for the caller.
+int gather_live_rows(scann_hip_mutable *m, float4 *out) {
+    const uint32_t nd = m->n_delta();
+    const hipStream_t st = m->st;
+    const uint32_t stride4 = m->stride / 4;
+    const uint64_t words = (m->n_base + 63) / 64;
+    if (words)
+        SCANN_TRY(launch(live_prefix_kernel, dim3(1), dim3(1024), 0, st, m->d_live.as<uint64_t>(), words,
+                         m->x_prefix.as<uint32_t>()));
+    if (m->live_base > 0) {
+        const uint64_t threads = m->n_base * stride4;
+        SCANN_TRY(launch(gather_live_kernel, dim3((uint32_t)ceil_div_u64(threads, 256)), dim3(256), 0, st, m->bv.rows, m->dim,
+                         m->bv.stride, stride4, m->d_live.as<uint64_t>(), m->x_prefix.as<uint32_t>(), m->n_base,
+                         m->identity ? (const uint32_t *)nullptr : m->d_base_ids.as<uint32_t>(), m->x_sorted.as<uint32_t>(),
+                         nd, out));
+    }
+    if (nd) {
+        const uint64_t threads = (uint64_t)nd * stride4;
+        SCANN_TRY(launch(scatter_delta_kernel, dim3((uint32_t)ceil_div_u64(threads, 256)), dim3(256), 0, st,
+                         m->d_delta.as<float4>(), stride4, m->x_dest.as<uint32_t>(), nd, out));
+    }
+    return SCANN_HIP_OK;
+}
+
 void fill_rows_empty(uint32_t nq, uint32_t k, uint32_t *out_idx, float *out_dist, uint32_t *out_count) {
     for (size_t i = 0; i < (size_t)nq * k; ++i) {
         out_idx[i] = kMutInvalid;
@@ -447,6 +530,39 @@ int download_rows(scann_hip_mutable *m, const DevBuf &i, const DevBuf &d, const 
     SCANN_HIP_CHECK(hipMemcpyAsync(out_dist, d.p, ob, hipMemcpyDeviceToHost, m->st));
     SCANN_HIP_CHECK(hipMemcpyAsync(out_count, c.p, (size_t)nq * 4, hipMemcpyDeviceToHost, m->st));
     return SCANN_HIP_OK;
+}
+
+// scann_hip_mutable_rebase under the handle's mutex.  Everything that can fail for want of memory comes first: a
+// failure leaves the handle as it was.
+int rebase_locked(scann_hip_mutable *m, scann_hip_index *new_base, const uint32_t *base_ids, uint64_t n) {
+    BaseView bv;
+    SCANN_TRY(check_base(new_base, &bv));
+    if (bv.dim != m->dim) return fail(SCANN_HIP_INVALID_ARGUMENT, "rebase: the new base has another dimensionality");
+    if (n != bv.n) return fail(SCANN_HIP_INVALID_ARGUMENT, "rebase: n differs from the new base's size");
+    if (n >= 0xFFFFFFFFull) return fail(SCANN_HIP_OUT_OF_RANGE, "base has too many rows for u32 ids");
+    if (base_ids)
+        for (uint64_t j = 0; j < n; ++j)
+            if (base_ids[j] == kMutInvalid || (j > 0 && base_ids[j] <= base_ids[j - 1]))
+                return fail(SCANN_HIP_INVALID_ARGUMENT, "rebase: base_ids must be strictly ascending");
+    SCANN_TRY(set_dev(m));
+    SCANN_TRY(sync(m));
+    DevBuf new_ids, new_live;
+    if (base_ids) SCANN_TRY(upload(new_ids, base_ids, n * 4));
+    SCANN_TRY(new_live.ensure((n + 63) / 64 * 8));
+    m->d_live.take(new_live);
+    m->base = new_base;
+    m->bv = bv;
+    m->n_base = n;
+    m->identity = base_ids == nullptr;
+    m->base_ids.clear();
+    uint64_t past = n;   // one past the largest id in use
+    if (base_ids) {
+        m->base_ids.assign(base_ids, base_ids + n);
+        m->d_base_ids.take(new_ids);
+        past = n ? (uint64_t)base_ids[n - 1] + 1 : 0;
+    }
+    if (past > m->next_index) m->next_index = (uint32_t)past;
+    return reset_state(m);
 }
 
 }  // namespace
@@ -487,6 +603,8 @@ void scann_hip_mutable_destroy(scann_hip_mutable *m) {
         (void)hipStreamDestroy(m->st);
     }
     for (auto &e : m->ev)
+        if (e) (void)hipEventDestroy(e);
+    for (auto &e : m->fev)
         if (e) (void)hipEventDestroy(e);
     delete m;
 }
@@ -807,53 +925,12 @@ int scann_hip_mutable_export_live(scann_hip_mutable *m, float *out_rows, uint32_
     if (n_live == 0) return SCANN_HIP_OK;
     if (!out_rows || !out_ids) return fail(SCANN_HIP_INVALID_ARGUMENT, "null out_rows/out_ids");
     SCANN_TRY(set_dev(m));
-    // ids: live base ids and the sorted delta ids, merged; dest[slot] = final position of a delta row
-    std::vector<uint32_t> order(nd), sorted(nd), dest(std::max(nd, 1u));
-    for (uint32_t s = 0; s < nd; ++s) order[s] = s;
-    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return m->delta_ids[a] < m->delta_ids[b]; });
-    for (uint32_t i = 0; i < nd; ++i) sorted[i] = m->delta_ids[order[i]];
-    uint64_t pos = 0;
-    uint32_t di = 0;
-    for (uint64_t j = 0; j < m->n_base; ++j) {
-        if ((j & 63u) == 0 && m->live[j >> 6] == 0) {   // (a word of removed rows)
-            j += 63;
-            continue;
-        }
-        if (!m->bit(j)) continue;
-        const uint32_t ext = m->identity ? (uint32_t)j : m->base_ids[j];
-        while (di < nd && sorted[di] < ext) {
-            dest[order[di]] = (uint32_t)pos;
-            out_ids[pos++] = sorted[di++];
-        }
-        out_ids[pos++] = ext;
-    }
-    while (di < nd) {
-        dest[order[di]] = (uint32_t)pos;
-        out_ids[pos++] = sorted[di++];
-    }
+    LiveOrder lo;
+    plan_live_order(m, &lo, out_ids);
     const hipStream_t st = m->st;
-    const uint32_t stride4 = m->stride / 4;
     SCANN_TRY(m->x_out.ensure((size_t)n_live * m->stride * 4));
-    if (m->live_base > 0) {
-        const uint64_t words = (m->n_base + 63) / 64;
-        SCANN_TRY(m->x_prefix.ensure(words * 4));
-        SCANN_TRY(m->x_sorted.ensure(std::max<size_t>(nd, 1) * 4));
-        if (nd) SCANN_HIP_CHECK(hipMemcpyAsync(m->x_sorted.p, sorted.data(), (size_t)nd * 4, hipMemcpyHostToDevice, st));
-        SCANN_TRY(launch(live_prefix_kernel, dim3(1), dim3(1024), 0, st, m->d_live.as<uint64_t>(), words,
-                         m->x_prefix.as<uint32_t>()));
-        const uint64_t threads = m->n_base * stride4;
-        SCANN_TRY(launch(gather_live_kernel, dim3((uint32_t)ceil_div_u64(threads, 256)), dim3(256), 0, st, m->bv.rows, m->dim,
-                         m->bv.stride, stride4, m->d_live.as<uint64_t>(), m->x_prefix.as<uint32_t>(), m->n_base,
-                         m->identity ? (const uint32_t *)nullptr : m->d_base_ids.as<uint32_t>(), m->x_sorted.as<uint32_t>(),
-                         nd, m->x_out.as<float4>()));
-    }
-    if (nd) {
-        SCANN_TRY(m->x_dest.ensure((size_t)nd * 4));
-        SCANN_HIP_CHECK(hipMemcpyAsync(m->x_dest.p, dest.data(), (size_t)nd * 4, hipMemcpyHostToDevice, st));
-        const uint64_t threads = (uint64_t)nd * stride4;
-        SCANN_TRY(launch(scatter_delta_kernel, dim3((uint32_t)ceil_div_u64(threads, 256)), dim3(256), 0, st,
-                         m->d_delta.as<float4>(), stride4, m->x_dest.as<uint32_t>(), nd, m->x_out.as<float4>()));
-    }
+    SCANN_TRY(gather_prepare(m, lo));
+    SCANN_TRY(gather_live_rows(m, m->x_out.as<float4>()));
     SCANN_HIP_CHECK(hipMemcpyAsync(out_rows, m->x_out.p, (size_t)n_live * m->stride * 4, hipMemcpyDeviceToHost, st));
     SCANN_TRY(sync(m));
     m->x_out.release();   // (as large as the index: not kept)
@@ -863,30 +940,154 @@ int scann_hip_mutable_export_live(scann_hip_mutable *m, float *out_rows, uint32_
 int scann_hip_mutable_rebase(scann_hip_mutable *m, scann_hip_index *new_base, const uint32_t *base_ids, uint64_t n) {
     if (!m || !new_base) return fail(SCANN_HIP_INVALID_ARGUMENT, "null handle/new_base");
     std::lock_guard<std::mutex> lock(m->mu);
-    BaseView bv;
-    SCANN_TRY(check_base(new_base, &bv));
-    if (bv.dim != m->dim) return fail(SCANN_HIP_INVALID_ARGUMENT, "rebase: the new base has another dimensionality");
-    if (n != bv.n) return fail(SCANN_HIP_INVALID_ARGUMENT, "rebase: n differs from the new base's size");
-    if (n >= 0xFFFFFFFFull) return fail(SCANN_HIP_OUT_OF_RANGE, "base has too many rows for u32 ids");
-    if (base_ids)
-        for (uint64_t j = 0; j < n; ++j)
-            if (base_ids[j] == kMutInvalid || (j > 0 && base_ids[j] <= base_ids[j - 1]))
-                return fail(SCANN_HIP_INVALID_ARGUMENT, "rebase: base_ids must be strictly ascending");
-    SCANN_TRY(set_dev(m));
-    SCANN_TRY(sync(m));
-    m->base = new_base;
-    m->bv = bv;
-    m->n_base = n;
-    m->identity = base_ids == nullptr;
-    m->base_ids.clear();
-    uint64_t past = n;   // one past the largest id in use
-    if (base_ids) {
-        m->base_ids.assign(base_ids, base_ids + n);
-        SCANN_TRY(upload(m->d_base_ids, base_ids, n * 4));
-        past = n ? (uint64_t)base_ids[n - 1] + 1 : 0;
+    return rebase_locked(m, new_base, base_ids, n);
+}
+
+int scann_hip_fold_mutable_stage_ms(scann_hip_mutable *m, float *out_ms5) {
+    if (!m || !out_ms5) return fail(SCANN_HIP_INVALID_ARGUMENT, "null handle/out");
+    std::lock_guard<std::mutex> lock(m->mu);
+    for (int s = 0; s < 5; ++s) out_ms5[s] = m->fold_ms[s];
+    return SCANN_HIP_OK;
+}
+
+int scann_hip_fold_mutable(scann_hip_mutable *m, scann_hip_index **out_new_base, uint32_t *out_base_ids,
+                           uint64_t capacity_rows, uint64_t *out_n) {
+    if (!m || !out_new_base || !out_n) return fail(SCANN_HIP_INVALID_ARGUMENT, "null handle/out_new_base/out_n");
+    std::lock_guard<std::mutex> lock(m->mu);
+    const uint32_t nd = m->n_delta();
+    const uint64_t n_live = m->live_base + nd;
+    *out_n = n_live;
+    if (out_base_ids && capacity_rows < n_live)
+        return fail(SCANN_HIP_RESOURCE_EXHAUSTED, "fold: capacity_rows is below the live count");
+    if (n_live == 0) return fail(SCANN_HIP_INVALID_ARGUMENT, "Cannot build from empty dataset");
+    FoldView fv;
+    if (!m->bv.brute_force) {
+        SCANN_TRY(index_fold_view(m->base, &fv));
+        if (fv.n_local != fv.n_rows || fv.n_local != m->n_base)
+            return fail(SCANN_HIP_FAILED_PRECONDITION, "fold: the base must index every row it stores (n_local == n_rows)");
     }
-    if (past > m->next_index) m->next_index = (uint32_t)past;
-    return reset_state(m);
+    SCANN_TRY(set_dev(m));
+    const hipStream_t st = m->st;
+    for (auto &e : m->fev)
+        if (!e) SCANN_HIP_CHECK(hipEventCreate(&e));
+    std::vector<uint32_t> ids(n_live);
+    LiveOrder lo;
+    plan_live_order(m, &lo, ids.data());
+    DevBuf rows, codes, leaf_off, leaf_ids;   // the new index's arrays: freed here unless a handle takes them
+    DevBuf tok, code8, order, dj, scratch;
+    std::vector<uint32_t> off;
+    const bool tree = !m->bv.brute_force;
+    const uint32_t L = fv.L;
+    FoldArgs a;
+    // ---- every allocation and every copy from the host comes first: between two of the events below the stream holds
+    // kernels only, so an event span is device time
+    SCANN_TRY(rows.ensure((size_t)n_live * m->stride * 4));
+    SCANN_TRY(gather_prepare(m, lo));
+    if (tree) {
+        SCANN_TRY(code8.ensure((size_t)std::max(nd, 1u) * fv.S));
+        if (!fv.ah) SCANN_TRY(tok.ensure((size_t)std::max(nd, 1u) * 4));
+        std::vector<uint32_t> djv(std::max(nd, 1u));
+        for (uint32_t i = 0; i < nd; ++i) djv[i] = lo.dest[lo.order[i]];
+        SCANN_TRY(upload(order, lo.order.data(), (size_t)nd * 4));
+        SCANN_TRY(upload(dj, djv.data(), (size_t)nd * 4));
+        SCANN_TRY(codes.ensure((size_t)n_live * fv.nw * 4));
+        SCANN_TRY(leaf_off.ensure(((size_t)L + 1) * 4));
+        if (!fv.ah) SCANN_TRY(leaf_ids.ensure((size_t)n_live * 4));
+        const uint64_t chunks = ceil_div_u64(m->n_base, kMutFoldChunk);
+        // scratch, every part a multiple of 8 bytes: sbits | cpref | sbase | doff | new_off | dtok | drank | dlist | flag
+        auto r8 = [](uint64_t b) { return (b + 7) & ~7ull; };
+        const uint64_t b_sbits = chunks * (kMutFoldChunk / 64) * 8, b_cpref = r8((chunks + 1) * 4), b_l = r8(((uint64_t)L + 2) * 4),
+                       b_d = r8((uint64_t)std::max(nd, 1u) * 4);
+        SCANN_TRY(scratch.ensure(b_sbits + b_cpref + 3 * b_l + 3 * b_d + 8));
+        char *sp = scratch.as<char>();
+        a.leaf_off = fv.leaf_off; a.leaf_ids = fv.leaf_ids; a.codes = fv.codes;
+        a.L = L; a.nw = fv.nw; a.S = fv.S; a.bits = fv.K <= 16 ? 4u : 8u; a.n = m->n_base;
+        a.live = m->d_live.as<uint64_t>(); a.live_prefix = m->x_prefix.as<uint32_t>();
+        a.base_ids = m->identity ? nullptr : m->d_base_ids.as<uint32_t>();
+        a.nd = nd; a.sorted_ids = m->x_sorted.as<uint32_t>(); a.order = order.as<uint32_t>(); a.dj = dj.as<uint32_t>();
+        a.tok_slot = fv.ah ? nullptr : tok.as<uint32_t>(); a.code8 = code8.as<uint8_t>();
+        a.sbits = reinterpret_cast<uint64_t *>(sp); sp += b_sbits;
+        a.cpref = reinterpret_cast<uint32_t *>(sp); sp += b_cpref;
+        a.sbase = reinterpret_cast<uint32_t *>(sp); sp += b_l;
+        a.doff = reinterpret_cast<uint32_t *>(sp); sp += b_l;
+        a.new_off = reinterpret_cast<uint32_t *>(sp); sp += b_l;
+        a.dtok = reinterpret_cast<uint32_t *>(sp); sp += b_d;
+        a.drank = reinterpret_cast<uint32_t *>(sp); sp += b_d;
+        a.dlist = reinterpret_cast<uint32_t *>(sp); sp += b_d;
+        a.flag = reinterpret_cast<uint32_t *>(sp);
+        a.new_ids = fv.ah ? nullptr : leaf_ids.as<uint32_t>();
+        a.new_codes = codes.as<uint32_t>();
+        a.n_new = n_live;
+        SCANN_TRY(fold_clear(a, st));
+    }
+    // ---- rows: export_live's kernels, writing to the new index's own buffer (they leave the bitmap's word prefix and
+    // the sorted delta ids on the device for the passes below)
+    SCANN_HIP_CHECK(hipEventRecord(m->fev[0], st));
+    SCANN_TRY(gather_live_rows(m, rows.as<float4>()));
+    SCANN_HIP_CHECK(hipEventRecord(m->fev[1], st));
+    if (tree) {
+        // ---- delta rows: leaf and code, by the partitioner's and the codebook's own kernels (delta slot order)
+        if (nd) {
+            if (!fv.ah) {
+                BfIndexDev dv{};
+                dv.rows = m->d_delta.as<float>();
+                dv.n = nd;
+                dv.dim = m->dim;
+                dv.stride = m->stride;
+                SCANN_TRY(bf_assign_nearest_device(dv, fv.centers, L, tok.as<uint32_t>(), nullptr, st));
+            }
+            const bool res = !fv.ah && fv.use_residuals;
+            SCANN_TRY(launch_encode(fv.codebook, fv.S, fv.K, fv.dsub, m->d_delta.as<float>(), nd, m->stride,
+                                    res ? fv.centers : nullptr, res ? tok.as<uint32_t>() : nullptr, code8.as<uint8_t>(), st));
+        }
+        SCANN_HIP_CHECK(hipEventRecord(m->fev[2], st));
+        // ---- pass 1: counts, scans, new offsets
+        SCANN_TRY(fold_count(a, st));
+        SCANN_HIP_CHECK(hipEventRecord(m->fev[3], st));
+        // ---- the offsets and the flag word come to the host (outside every span): the preconditions are decided
+        // before anything is scattered
+        off.resize((size_t)L + 2);
+        SCANN_HIP_CHECK(hipMemcpyAsync(off.data(), a.new_off, off.size() * 4, hipMemcpyDeviceToHost, st));
+        SCANN_HIP_CHECK(hipMemcpyAsync(leaf_off.p, a.new_off, ((size_t)L + 1) * 4, hipMemcpyDeviceToDevice, st));
+        SCANN_TRY(sync(m));
+        const uint32_t flag = off.back();
+        off.pop_back();
+        if (flag & 2u) return fail(SCANN_HIP_FAILED_PRECONDITION, "fold: the base holds a datapoint index outside its rows");
+        if (flag & 1u)
+            return fail(SCANN_HIP_FAILED_PRECONDITION, "fold: every leaf of the base must be strictly ascending in datapoint index");
+        if (off[L] != n_live)
+            return fail(SCANN_HIP_FAILED_PRECONDITION,
+                        "fold: the leaves reach " + std::to_string(off[L] - nd) + " live rows, the live bitmap counts " +
+                            std::to_string(m->live_base) + " (a datapoint in two leaves or in none)");
+        // ---- pass 2: the stable scatter
+        SCANN_HIP_CHECK(hipEventRecord(m->fev[4], st));
+        SCANN_TRY(fold_scatter(a, st));
+        SCANN_HIP_CHECK(hipEventRecord(m->fev[5], st));
+    }
+    SCANN_TRY(sync(m));
+    const auto t_finish = std::chrono::steady_clock::now();
+    // ---- the second half of the create functions, on the new arrays
+    scann_hip_index *nb = nullptr;
+    if (m->bv.brute_force) SCANN_TRY(index_fold_bf(m->base, rows, n_live, m->stride, &nb));
+    else SCANN_TRY(index_fold_txh(m->base, rows, codes, leaf_off, leaf_ids, off, n_live, m->stride, &nb));
+    // ---- the swap (ids that are 0 .. n' - 1 are the identity)
+    const bool identity = ids.back() == n_live - 1;
+    int s = set_dev(m);
+    if (s == SCANN_HIP_OK) s = rebase_locked(m, nb, identity ? nullptr : ids.data(), n_live);
+    if (s != SCANN_HIP_OK) {
+        scann_hip_index_destroy(nb);
+        return s;
+    }
+    // (a brute-force base has no middle stages: their events were not recorded)
+    static const int span[4][2] = {{0, 1}, {1, 2}, {2, 3}, {4, 5}};
+    for (int e = 0; e < 4; ++e) {
+        m->fold_ms[e] = 0.0f;
+        if (e == 0 || tree) (void)hipEventElapsedTime(&m->fold_ms[e], m->fev[span[e][0]], m->fev[span[e][1]]);
+    }
+    m->fold_ms[4] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_finish).count();
+    if (out_base_ids) std::memcpy(out_base_ids, ids.data(), (size_t)n_live * 4);
+    *out_new_base = nb;
+    return SCANN_HIP_OK;
 }
 
 }  // extern "C"

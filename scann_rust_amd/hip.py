@@ -21,6 +21,7 @@ CROWD_MAX_DIMS = 8      # SCANN_HIP_CROWD_MAX_DIMS
 MUTABLE_MAX_CAPACITY = 65536   # SCANN_HIP_MUTABLE_MAX_CAPACITY
 MUTABLE_MAX_K = 2048           # SCANN_HIP_MUTABLE_MAX_K
 MUTABLE_DELTA_TILE = 1024      # SCANN_HIP_MUTABLE_DELTA_TILE: delta rows sorted per workgroup of the delta scan
+FOLD_CHUNK = 1024              # SCANN_HIP_FOLD_CHUNK: CSR positions per workgroup of the fold's count and scatter passes
 
 _CODE_NAMES = {
     0: "Ok", 1: "Cancelled", 2: "Unknown", 3: "InvalidArgument", 4: "DeadlineExceeded",
@@ -57,7 +58,8 @@ EXPORTS = [
     "scann_hip_mutable_update", "scann_hip_mutable_get", "scann_hip_mutable_exists", "scann_hip_mutable_size",
     "scann_hip_mutable_pending", "scann_hip_mutable_needs_rebuild", "scann_hip_mutable_search",
     "scann_hip_mutable_export_live", "scann_hip_mutable_rebase", "scann_hip_mutable_enable_timing",
-    "scann_hip_mutable_last_stage_ms",
+    "scann_hip_mutable_last_stage_ms", "scann_hip_fold_mutable", "scann_hip_fold_mutable_stage_ms",
+    "scann_hip_index_write_file",
 ]
 
 
@@ -249,6 +251,9 @@ def load():
     L.scann_hip_mutable_enable_timing.argtypes = [vp, C.c_int]
     L.scann_hip_mutable_enable_timing.restype = None
     L.scann_hip_mutable_last_stage_ms.argtypes = [vp, f32p]
+    L.scann_hip_fold_mutable.argtypes = [vp, C.POINTER(vp), u32p, C.c_uint64, u64p]
+    L.scann_hip_fold_mutable_stage_ms.argtypes = [vp, f32p]
+    L.scann_hip_index_write_file.argtypes = [vp, C.c_char_p]
     _lib = L
     return L
 
@@ -627,6 +632,25 @@ class Mutable:
         check(load().scann_hip_mutable_rebase(self.h, new_base.h, ptr(b, u32p), new_base.size()))
         self.base = new_base
 
+    def fold(self):
+        """Fold the delta and the tombstones into a new base ON THE DEVICE, keeping the trained model, and rebase onto
+        it (scann_hip_fold_mutable).  Returns (new base Index, base_ids): new datapoint j is the live row of id
+        base_ids[j].  The old base is released once nothing else holds it."""
+        n = self.size()
+        ids = np.zeros(max(n, 1), np.uint32)
+        got = C.c_uint64(0)
+        h = vp()
+        check(load().scann_hip_fold_mutable(self.h, C.byref(h), ptr(ids, u32p), ids.size, C.byref(got)))
+        new_base = Index(h)
+        self.base = new_base
+        return new_base, ids[:got.value]
+
+    def fold_stage_ms(self):
+        """ms of (row gather, delta assign + encode, count + scans, scatter, finish half) of the last fold"""
+        out = np.zeros(5, np.float32)
+        check(load().scann_hip_fold_mutable_stage_ms(self.h, ptr(out, f32p)))
+        return tuple(float(x) for x in out)
+
     def enable_timing(self, on=True):
         load().scann_hip_mutable_enable_timing(self.h, 1 if on else 0)
 
@@ -744,6 +768,11 @@ def index_file_info(path):
     info = FileInfo()
     check(load().scann_hip_index_file_info(os.fsencode(path), C.byref(info)))
     return {name: getattr(info, name) for name, _ in FileInfo._fields_}
+
+
+def index_write_file(index, path):
+    """Write a handle's arrays, read back from the device, to the index container (scann_hip_index_write_file)."""
+    check(load().scann_hip_index_write_file(index.h, os.fsencode(path)))
 
 
 def load_file(path, device=0):

@@ -586,7 +586,7 @@ public:
     // scoring (tree_x_hybrid/mod.rs:327-332).  The filter is materialised once into an allow-bitmap.
     NNResultsVector search_with_filter(const std::vector<float> &query, size_t k, const RestrictFilter *filter) const {
         if (!filter) return search(query, k);
-        const auto bits = filter->to_bitmap(dataset_->size());
+        const auto bits = filter->to_bitmap(dataset_size());
         scann_hip_search_opts o;
         scann_hip_search_opts_default(&o);
         o.allow_bitmap = bits.data();
@@ -616,7 +616,7 @@ public:
     // the prefix property the rows then equal apply() over the full sorted database.
     std::pair<NNResultsVector, bool> search_crowded_exact(const std::vector<float> &query, size_t k,
                                                           const CrowdingConstraint &constraint) const {
-        const size_t n = dataset_->size(), cap = std::min<size_t>(n, 2048);
+        const size_t n = dataset_size(), cap = std::min<size_t>(n, 2048);
         if (!constraint.config().enabled) return {search(query, k), true};
         size_t depth = std::max<size_t>(1, std::min(k, cap));
         for (;;) {
@@ -634,12 +634,12 @@ public:
     // every ALLOWED datapoint with distance <= radius
     NNResultsVector search_radius_with_filter(const std::vector<float> &query, float radius,
                                               const RestrictFilter *filter) const {
-        if (dataset_->size() == 0) return {};
+        if (dataset_size() == 0) return {};
         std::vector<uint64_t> bits;
         scann_hip_search_opts o;
         scann_hip_search_opts_default(&o);
         if (filter) {
-            bits = filter->to_bitmap(dataset_->size());
+            bits = filter->to_bitmap(dataset_size());
             o.allow_bitmap = bits.data();
             o.allow_bitmap_bits = bits.size() * 64;
         }
@@ -657,13 +657,21 @@ public:
         for (size_t i = 0; i < found; ++i) r[i] = {idx[i], dist[i]};
         return r;
     }
-    size_t dataset_size() const { return dataset_->size(); }
-    uint64_t dimensionality() const { return dataset_->dimensionality(); }
+    size_t dataset_size() const { return (size_t)scann_hip_index_size(ix_.h); }
+    uint64_t dimensionality() const { return scann_hip_index_dimensionality(ix_.h); }
     DistanceMeasure distance_measure() const { return measure_; }
+    // the host rows the searcher was built from; EMPTY for a base made on the device by MutableIndex::compact (its rows
+    // never visited the host: MutableIndex::export_live reads them back)
     const DenseDataset &dataset() const { return *dataset_; }
     scann_hip_index *handle() const { return ix_.h; }   // (borrowed by MutableIndex)
 
 private:
+    friend class MutableIndex;
+    // adopts a handle scann_hip_fold_mutable made
+    BruteForceSearcher(scann_hip_index *adopted, DistanceMeasure measure)
+        : dataset_(std::make_shared<DenseDataset>()), measure_(measure) {
+        ix_.h = adopted;
+    }
     std::shared_ptr<DenseDataset> dataset_;
     DistanceMeasure measure_;
     detail::IndexHandle ix_;
@@ -675,7 +683,7 @@ private:
 // add / remove / update / get / exists / size / compact as MutableDataset names them, plus the rebuild counter of
 // IncrementalUpdater (:527-545).  Rows live on the device: an immutable base searcher, a live bitmap over its rows and a
 // delta segment of `capacity` rows (include/scann_hip.h "mutable indexes").  Ids are stable and never reused; search
-// returns them.  compact() exports the live rows, builds a new base from them and rebases: the delta is empty again and
+// returns them.  compact() folds the live rows into a new base on the device and rebases onto it: the delta is empty again and
 // removed ids are forgotten (NotFound), as after the reference's compact().  Brute-force bases only: the C ABI also takes
 // Tree-X-Hybrid and flat-hasher bases (scann_hip_mutable_create over their handles), which this mirror does not wrap.
 class MutableIndex {
@@ -777,11 +785,19 @@ public:
         check(scann_hip_mutable_rebase(h_, new_base->handle(), base_ids ? base_ids->data() : nullptr, new_base->dataset_size()));
         base_ = std::move(new_base);   // (the old base is destroyed after the swap)
     }
-    void compact() {                                                                                // :440-471
-        auto live = export_live();
-        if (live.second.empty()) throw ScannError::failed_precondition("compact: no live rows to build a base from");
-        auto nb = std::make_shared<BruteForceSearcher>(std::move(live.first), base_->distance_measure(), device_);
-        rebase(std::move(nb), &live.second);
+    // MutableDataset::compact (:440-471) in one call and on the device (scann_hip_fold_mutable): the live rows become the
+    // new base without visiting the host, the delta is emptied, removed ids are forgotten.  Returns the external id of
+    // every row of the new base.  The new base has no host copy of its rows (base().dataset() is empty).
+    std::vector<DatapointIndex> compact() {
+        const size_t n = size();
+        if (n == 0) throw ScannError::failed_precondition("compact: no live rows to build a base from");
+        std::vector<DatapointIndex> ids(n);
+        scann_hip_index *nb = nullptr;
+        uint64_t got = 0;
+        check(scann_hip_fold_mutable(h_, &nb, ids.data(), ids.size(), &got));
+        ids.resize(got);
+        base_ = std::shared_ptr<BruteForceSearcher>(new BruteForceSearcher(nb, base_->distance_measure()));   // (the old base is destroyed after the swap)
+        return ids;
     }
     const BruteForceSearcher &base() const { return *base_; }
 
