@@ -334,6 +334,12 @@ int scann_hip_search_batched_device(scann_hip_index *index, const float *d_queri
  * rows and repeats over the compacted allowed rows.  A reserved handle does not allocate on such a call
  * (pass the opts with the bitmap to scann_hip_index_reserve so that host calls do not either). */
 int scann_hip_index_last_device_status(scann_hip_index *index, void *hip_stream);
+/* Debugging aid of the batched Tree-X-Hybrid / AsymmetricHasher pipeline: copies the filter bounds thr[0 .. nq) of
+ * the last batched search enqueued on hip_stream (its workspace, else the primary one) to out_bounds.  A bound is
+ * the merge key (ordered approximate distance << 32 | stream position) at or under which a scanned point becomes a
+ * candidate, UINT64_MAX = no bound.  The CALLER synchronises hip_stream first; the copy itself is synchronous.
+ * OutOfRange when the workspace has never held nq bounds. */
+int scann_hip_index_debug_filter_bounds(scann_hip_index *index, void *hip_stream, uint32_t nq, uint64_t *out_bounds);
 
 /* ---- crowding: at most per_crowd_limit results per attribute (restricts/crowding.rs) --------
  * CrowdingConstraint::apply (crowding.rs:81-104) behind every search, on the device.  For every handle kind

@@ -1184,6 +1184,10 @@ static int plan_txh_search(const scann_hip_index *ix, uint32_t k, const scann_hi
     p.thr_ties = kn.thr_ties;
     // a bound in the low tail of a long sample: threshold_tail_kernel
     p.thr_tail = kn.thr_tail && !p.no_threshold && sample_rank(m, p.st) <= kThrTailMaxRank && p.scap > 4096;
+    // ... of a flat hasher in front of an MFMA prefilter: the sample as integer-MFMA sums over the plain quantised
+    // tables, the exact f32 arithmetic only on its low tail (adc_sample_mfma_kernel, threshold_tail16_kernel)
+    p.sample_mfma = kn.sample_mfma && p.thr_tail && p.thr_ties && txh_scan_is_mfma(p.scan) && t.ah_mode && t.L == 1 &&
+                    P == 1 && t.code_bits == 4;
     p.select_direct = kn.select_direct;
     // int8 re-rank filter: lists of a few hundred candidates and more
     p.use_i8 = t.rows8 && exact_reorder && m >= kn.rerank_i8_min && m > 4 * k;
@@ -1244,7 +1248,7 @@ static int ensure_txh_workspace(scann_hip_index *ix, TxhWorkspace &s, const TxhP
     s.want(s.sbase, (size_t)nq * (P + 2) * 4);
     s.want(s.pair_sbase, (size_t)max_slots * 4);
     s.want(s.stile_off, (size_t)(L + 1) * 4);
-    s.want(s.samp, (size_t)nq * p.scap * 4);
+    s.want(s.samp, (size_t)nq * p.scap * (p.sample_mfma ? 2 : 4));
     s.want(s.leaf_cnt, (size_t)L * 4);
     s.want(s.leaf_cursor, (size_t)L * 4);
     s.want(s.pair_off, (size_t)(L + 1) * 4);
@@ -1907,6 +1911,22 @@ int scann_hip_index_last_device_status(scann_hip_index *ix, void *hip_stream) {
         return fail((int)counters[CNT_STATUS],
                     "candidate threshold/buffer miss on the device path (use the host entry "
                     "point, which retries without a threshold and with a full-size buffer)");
+    return SCANN_HIP_OK;
+}
+
+int scann_hip_index_debug_filter_bounds(scann_hip_index *ix, void *hip_stream, uint32_t nq, uint64_t *out_bounds) {
+    if (!ix || ix->kind != KIND_TXH) return fail(SCANN_HIP_INVALID_ARGUMENT, "not a tree / hasher index");
+    if (nq && !out_bounds) return fail(SCANN_HIP_INVALID_ARGUMENT, "out_bounds is null");
+    SCANN_TRY(set_device(ix->ctx));
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    std::lock_guard<std::mutex> lock(ix->mu);
+    // the workspace bound to this stream (else the primary one)
+    const TxhWorkspace *ws = &ix->ws;
+    for (auto &d : ix->dslots)
+        if (d.used && d.key == st && d.ws) ws = d.ws;
+    if (!ws->thr.p || ws->thr.bytes < (size_t)nq * 8)
+        return fail(SCANN_HIP_OUT_OF_RANGE, "no batched search of that many queries has run in this workspace");
+    SCANN_HIP_CHECK(hipMemcpy(out_bounds, ws->thr.p, (size_t)nq * 8, hipMemcpyDeviceToHost));
     return SCANN_HIP_OK;
 }
 

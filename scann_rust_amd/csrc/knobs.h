@@ -25,6 +25,8 @@
 //                                   prefilter (default: word-parallel on tree indexes)
 // SCANN_HIP_THR_TIES                0: filter bound on the distance alone (diagnostics)            every call
 // SCANN_HIP_THR_TAIL                0: filter bound by the full histogram select                   every call
+// SCANN_HIP_SAMPLE_MFMA             0: flat hashers score the bound's sample with the f32 gather   every call
+//                                   (default: integer-MFMA sample, exact re-score of its low tail)
 // SCANN_HIP_FUSED                   0: small batches always as three launches                      every call
 // SCANN_HIP_SELECT_DIRECT           0: stage long candidate lists in LDS for the unsorted select   every call
 // SCANN_HIP_LOCAL_PRUNE             0: multi-GPU local stage re-ranks every candidate exactly      every call
@@ -69,6 +71,7 @@ struct Knobs {
     int sp_words = -1;                    // -1 = by index kind
     bool thr_ties = true;
     bool thr_tail = true;
+    bool sample_mfma = true;
     bool fused = true;
     bool select_direct = true;
     bool local_prune = true;
@@ -115,6 +118,7 @@ inline Knobs read_knobs() {
         else if (is("SCANN_HIP_SP_WORDS")) k.sp_words = atoi(v) != 0 ? 1 : 0;
         else if (is("SCANN_HIP_THR_TIES")) k.thr_ties = atoi(v) != 0;
         else if (is("SCANN_HIP_THR_TAIL")) k.thr_tail = atoi(v) != 0;
+        else if (is("SCANN_HIP_SAMPLE_MFMA")) k.sample_mfma = atoi(v) != 0;
         else if (is("SCANN_HIP_FUSED")) k.fused = atoi(v) != 0;
         else if (is("SCANN_HIP_SELECT_DIRECT")) k.select_direct = atoi(v) != 0;
         else if (is("SCANN_HIP_LOCAL_PRUNE")) k.local_prune = atoi(v) != 0;

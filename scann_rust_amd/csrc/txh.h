@@ -159,6 +159,7 @@ struct TxhPlan {
     bool codes_in_list;        // prefilter survivors carry their packed codes / plane rows
     bool thr_ties;             // filter bound on (distance, stream position); false: on the distance alone
     bool thr_tail;             // filter bound by threshold_tail_kernel (else threshold_select_kernel)
+    bool sample_mfma;          // flat hashers: the sample as integer-MFMA sums (u16), bound by threshold_tail16_kernel
     bool fused;                // small pipeline in one launch (small_fused_kernel)
     uint32_t chunk, grid;      // one-launch small / wide pipeline: stream positions per workgroup, workgroups per query
     uint32_t small_max_leaf;   // longest local leaf (grid of the three-launch small scan)
@@ -198,7 +199,8 @@ struct TxhWork : TxhPlan {
     uint32_t *sbase;           // [nq][P+2] prefix of per-leaf sample counts; [P]=samples, [P+1]=local points
     uint32_t *pair_sbase;      // [max_slots]
     uint32_t *stile_off;       // [L+1] tile table of the sample pass
-    uint32_t *samp;            // [nq][scap] ordered(approx distance) of the sampled points
+    uint32_t *samp;            // [nq][scap] ordered(approx distance) of the sampled points; with sample_mfma
+                               // [nq][scap] u16: their quantised sums (adc_sample_mfma_kernel)
     uint32_t *leaf_cnt;        // [L]
     uint32_t *leaf_cursor;     // [L]
     uint32_t *pair_off;        // [L+1] (slots, padded to quads)

@@ -1205,7 +1205,9 @@ __device__ __forceinline__ int mfma_pass_bound(uint32_t S, uint32_t pq, uint64_t
     return thr + 1;
 }
 
-// fold != 0 (adc_smfmac_kernel): the pass bound is folded INTO the tables, so that a point passes iff its integer sum
+// Three modes.  fold == 0 (dense prefilters): plain tables q - 128 and the pair's pass bound in thr1.  fold < 0 (K5d, ahead
+// of any bound): the same plain tables and meta; pair_thr is not read and thr1 is not written.  fold > 0
+// (adc_smfmac_kernel), the rest of this comment: the pass bound is folded INTO the tables, so that a point passes iff its integer sum
 // is negative (the sparse MFMA accumulates in place: there is no free zero / bound operand, and the sign test is one
 // vector instruction per result instead of two).  With qmax = the largest quantised sum a passing point can have (as
 // in mfma_pass_bound), D = 128 S - 1 - qmax >= 0 is spread over the subspaces, d_s = D / S (+ 1 for the first D % S),
@@ -1257,7 +1259,7 @@ __global__ __launch_bounds__(256) void lut8_build_kernel(uint32_t S, const float
         }
         double sc = (s_bad[tid] || !(r > 0.0f)) ? 0.0 : (double)r / 255.0;
         const size_t slot = (size_t)quad * 4 + tid;
-        if (fold) {
+        if (fold > 0) {
             int mode = 1, dbase = 0, drem = 0;
             const uint64_t T = pair_thr[slot];
             if (pair_q[slot] == kInvalid) {
@@ -1287,10 +1289,11 @@ __global__ __launch_bounds__(256) void lut8_build_kernel(uint32_t S, const float
             s_dbase[tid] = dbase;
             s_drem[tid] = drem;
             thr1[slot] = 0;
-        } else {
+        } else if (fold == 0) {
             // (the pair's pass bound right away: the filter bounds are known by now -- one launch less)
             thr1[slot] = mfma_pass_bound(S, pair_q[slot], pair_thr[slot], bias, sc);
         }
+        // (fold < 0: nothing here -- the plain tables ahead of any bound; pair_thr and thr1 are not touched)
         s_scale[tid] = sc;
         Lut8Meta m;
         m.bias_sum = bias;
@@ -1310,7 +1313,7 @@ __global__ __launch_bounds__(256) void lut8_build_kernel(uint32_t S, const float
                 q = q < 0 ? 0 : (q > 255 ? 255 : q);
             }
             int e = q - 128;
-            if (fold) {
+            if (fold > 0) {
                 const int mode = s_mode[p];
                 e += s_dbase[p] + ((int)sub < s_drem[p] ? 1 : 0);
                 e = mode == 1 ? -128 : mode == 2 ? 127 : (e > 127 ? 127 : e);
@@ -2844,6 +2847,310 @@ __global__ __launch_bounds__(kThrTailThreads) void threshold_tail_kernel(
         if (sb[mid] <= slot) lo = mid; else hi = mid;
     }
     publish(((uint64_t)v << 32) | (vb[lo] + (slot - sb[lo]) * st));
+}
+
+// =====================================================================================
+// K5d: the flat hasher's sample on the matrix cores, K5e: its bound from the low tail.
+//
+// adc_sample_kernel scores the sample with the f32 LDS gather and threshold_tail_kernel reads every one of those
+// f32 values twice -- to find ONE number per query, the J-th smallest sample key, which only the lowest ~1 % of the
+// samples can influence.  In front of an MFMA prefilter (flat hasher, 4-bit codes, plan: sample_mfma) the sample is
+// scored the way the prefilter scores the scan: lut8_build_kernel(fold < 0) quantises the plain tables before any
+// bound exists, adc_sample_mfma_kernel writes the integer sums u = sum q_s in [0, 255 S] as u16 (half the bytes),
+// and threshold_tail16_kernel applies the reference's f32 arithmetic to the few hundred samples whose sums are low
+// enough to matter.  The published bound is the J-th smallest f32 sample key, bit for bit what K5a + K5c publish:
+//   * pivot P = the J-th smallest of the 512 values the threads keep (two smallest each): at least J samples have
+//     u <= P, and a sample with sum u has f32 distance D <= (bias + sc (u + S (0.5 + 1e-9))) (1 + S 2^-23) (every
+//     table entry v satisfies |v - (mn_s + sc q)| <= sc (0.5 + 1e-9); the factor covers the sequential f32 adds of
+//     non-negative terms), so Dmax = that expression at u = P is an upper bound of the J-th smallest f32 distance;
+//   * a sample with D <= Dmax has u <= qlim = floor((Dmax (1 + S 2^-23) - bias) / sc + S / 2 + 1) (the pass bound
+//     of mfma_pass_bound): the samples with u <= qlim contain every sample at or under the J-th smallest f32
+//     distance, and the J-th smallest exact key among them is the J-th smallest of the whole sample.
+// More than kThrTailList samples under qlim (tie-heavy or badly scaled tables): the bound is (Dmax, MAX), valid and
+// looser, as threshold_tail_kernel's flood case.  A table that cannot be quantised (scale = 0: NaN, negative or
+// infinite entries, all entries equal) takes threshold_tail_kernel's two passes over f32 distances computed on the
+// fly, sample to thread as there: the same bound in every case, for that query only.
+// One leaf, one pair per query (P = 1, the plan guarantees it): sample i is point i * st, sample slot = sample index,
+// slot_of[q] is valid wherever the index has points (an empty index has no samples: J = 0).  The publish loop over
+// tokens and the token search at the end of threshold_tail16_kernel only mirror threshold_tail_kernel's skeleton.
+// Under an allow-bitmap every column lane of a tile tests the same 16 sample rows (32 x redundant, L1-served reads): the
+// filtered sample is still a few percent of the scan's work, so the mask is not shared across lanes.
+// =====================================================================================
+constexpr uint32_t kSmpTiles = 8;   // 32-sample tiles per item (wave) of adc_sample_mfma_kernel
+
+struct SampleMfmaArgs {
+    const uint32_t *pair_off, *pair_q, *pair_sbase;
+    const int8_t *lut8;
+    uint16_t *samp16;         // [nq][scap]
+    uint32_t scap, st;
+    const uint64_t *allow;
+    uint64_t allow_bits;
+};
+
+// Operands as adc_mfma_kernel: lane (col, h) holds the table fragments of pair slot `col` of the item's 32-pair tile
+// (subspaces of parity h), the A fragment of a (sample, subspace pair) is one row of the LDS identity table, register
+// r of the result is sample row (r & 3) + 8 (r >> 2) + 4 h of the tile: four consecutive samples of one query per
+// register group, one 8-byte store.  Items = (pair tile, kSmpTiles sample tiles), one per wave, grid-strided.
+template <int S_>
+__global__ __launch_bounds__(256, (S_ <= 32 ? 3 : 2)) void adc_sample_mfma_kernel(TxhIndexDev ix, SampleMfmaArgs a) {
+    typedef int v4i __attribute__((ext_vector_type(4)));
+    typedef int v16i __attribute__((ext_vector_type(16)));
+    constexpr int S = S_, KS = S / 2, NW = S / 8;
+    __shared__ __attribute__((aligned(16))) uint32_t s_ident[64];                 // 16 one-hot rows of 16 bytes
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t col = lane & 31u, h = lane >> 5;
+    if (tid < 64) {
+        const uint32_t c = tid >> 2, wsel = tid & 3u;
+        s_ident[tid] = (wsel == (c >> 2)) ? (1u << (8 * (c & 3u))) : 0u;
+    }
+    __syncthreads();
+    const char *ident = reinterpret_cast<const char *>(s_ident);
+    const uint32_t lb = uniform_load(ix.leaf_off), size = uniform_load(ix.leaf_off + 1) - lb;
+    const uint32_t slot0 = uniform_load(a.pair_off), slot_end = uniform_load(a.pair_off + 1);
+    const uint32_t st = a.st, ssize = min((size + st - 1) / st, a.scap);   // sampled points of the leaf
+    const uint32_t ntile = (ssize + 31u) >> 5, nrange = (ntile + kSmpTiles - 1) / kSmpTiles;
+    const uint32_t npt = (slot_end - slot0 + 31u) >> 5;
+    const uint32_t nitems = npt * nrange, nwaves = gridDim.x * 4u;
+    for (uint32_t item = blockIdx.x * 4u + wave; item < nitems; item += nwaves) {
+        // (neighbouring waves: the same samples against different pair tiles -- their code rows come from L1 / L2)
+        const uint32_t pt = item % npt, range = item / npt;
+        const uint32_t slot = slot0 + pt * 32u + col;
+        const bool pair_ok = slot < slot_end;
+        const uint32_t pq = pair_ok ? a.pair_q[slot] : kInvalid;
+        const uint32_t sb = pair_ok ? a.pair_sbase[slot] : 0u;
+        v4i b[KS];
+        {
+            const int8_t *bsrc = a.lut8 + ((size_t)(pair_ok ? slot : slot0) * S + h) * 16;   // padding columns: any table
+#pragma unroll
+            for (int t = 0; t < KS; ++t) b[t] = *reinterpret_cast<const v4i *>(bsrc + (size_t)t * 32);
+        }
+        uint16_t *dst = a.samp16 + (size_t)(pq == kInvalid ? 0u : pq) * a.scap + sb;
+        const uint32_t t0 = range * kSmpTiles, t1 = min(t0 + kSmpTiles, ntile);
+        uint32_t wn[NW];
+        {
+            const uint32_t j = t0 * 32u + col;
+            Codec<S, 4>::load_words(ix.codes + (size_t)(lb + (j < ssize ? j * st : 0u)) * NW, wn);
+        }
+        for (uint32_t t = t0; t < t1; ++t) {
+            // nibbles of this lane's subspace parity h, pre-shifted to byte offsets code * 16
+            uint32_t rg[NW];
+#pragma unroll
+            for (int wi = 0; wi < NW; ++wi) rg[wi] = h ? (wn[wi] & 0xF0F0F0F0u) : ((wn[wi] & 0x0F0F0F0Fu) << 4);
+            if (t + 1 < t1) {   // the next tile's codes travel under this tile's MFMAs
+                const uint32_t j = (t + 1) * 32u + col;
+                Codec<S, 4>::load_words(ix.codes + (size_t)(lb + (j < ssize ? j * st : 0u)) * NW, wn);
+            }
+            v16i acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+            for (int kt = 0; kt < KS; ++kt) {
+                const uint32_t off = (rg[kt >> 2] >> (8 * (kt & 3))) & 0xFFu;   // code * 16 of subspace 2 kt + h
+                const v4i av = *reinterpret_cast<const v4i *>(ident + off);
+                acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(av, b[kt], acc, 0, 0, 0);
+            }
+            if (pq == kInvalid) continue;   // padding column: nothing to write
+            const uint32_t base = t * 32u + 4u * h;
+            uint32_t rej = 0;   // search_with_filter: bit r = the sample of register r is rejected (absent)
+            if (a.allow) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const uint32_t i = base + (uint32_t)((r & 3) + 8 * (r >> 2));
+                    const bool ok = i < ssize && row_allowed(ix, a.allow, a.allow_bits, lb + i * st);
+                    rej |= (ok ? 0u : 1u) << r;
+                }
+            }
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const uint32_t i0 = base + 8u * (uint32_t)g;
+                if (i0 >= ssize) continue;
+                uint32_t u[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e)   // [0, 255 S], or the absent mark
+                    u[e] = ((rej >> (4 * g + e)) & 1u) ? 0xFFFFu : (uint32_t)(acc[4 * g + e] + 128 * S);
+                if (i0 + 3u < ssize) {   // (rows of samp16 and i0 are multiples of four entries: 8-byte aligned)
+                    *reinterpret_cast<uint2 *>(dst + i0) = make_uint2(u[0] | (u[1] << 16), u[2] | (u[3] << 16));
+                } else {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e)
+                        if (i0 + e < ssize) dst[i0 + e] = (uint16_t)u[e];
+                }
+            }
+        }
+    }
+}
+
+struct Tail16Args {
+    uint32_t P, m, st, scap;
+    const uint32_t *sbase, *slot_of, *tokens, *vbase;
+    const uint16_t *samp16;
+    const float *lutq;
+    const Lut8Meta *meta;
+    uint64_t *thr, *pair_thr;
+};
+
+template <int S_>
+__global__ __launch_bounds__(kThrTailThreads) void threshold_tail16_kernel(TxhIndexDev ix, Tail16Args a) {
+    constexpr int S = S_, NW = S / 8;
+    __shared__ float s_tab[S * 16];   // the query's f32 table, de-interleaved: [s][16]
+    __shared__ uint32_t s_kept[2 * kThrTailThreads];
+    __shared__ uint32_t s_hist[1024];
+    __shared__ uint64_t s_slist[256];
+    __shared__ uint64_t s_red[48];
+    __shared__ uint64_t s_keys[kThrTailList];
+    __shared__ uint32_t s_cnt[2];
+    const uint32_t q = blockIdx.x, tid = threadIdx.x, nt = kThrTailThreads, P = a.P;
+    const uint32_t *sb = a.sbase + (size_t)q * (P + 2), *vb = a.vbase + (size_t)q * (P + 1);
+    const uint32_t ns = min(sb[P], a.scap);
+    const uint32_t total = sb[P + 1];
+    const uint32_t J = total <= a.m ? 0u : sample_rank(a.m, a.st);
+    auto publish = [&](uint64_t T) {
+        if (tid == 0) a.thr[q] = T;
+        for (uint32_t r = tid; r < P; r += nt) {
+            const uint32_t sl = a.slot_of[(size_t)q * P + r];
+            if (sl != kInvalid) a.pair_thr[sl] = T;
+        }
+    };
+    if (J == 0 || ns < J) {   // block-uniform (an empty index, whose queries have no pair slot, ends here: J = 0)
+        publish(SCANN_KEY_MAX);
+        return;
+    }
+    const uint32_t tslot = a.slot_of[(size_t)q * P];   // P == 1: the query's one pair slot
+    for (uint32_t e = tid; e < (uint32_t)S * 16u; e += nt)
+        s_tab[e] = a.lutq[((size_t)(tslot >> 2) * S * 16 + e) * 4 + (tslot & 3u)];
+    const Lut8Meta mt = a.meta[tslot];
+    const bool exact = !(mt.scale > 0.0);   // table not quantised: f32 distances in both passes (block-uniform)
+    const uint32_t row0 = ix.leaf_off[a.tokens[(size_t)q * P]];
+    if (tid < 2) s_cnt[tid] = 0;
+    __syncthreads();
+    // the reference's distance of sample slot i (hashes/lut.rs:74-82: subspace order)
+    auto dist = [&](uint32_t i) {
+        uint32_t w[NW];
+        Codec<S, 4>::load_words(ix.codes + (size_t)(row0 + (i - sb[0]) * a.st) * NW, w);
+        float acc = 0.0f;
+#pragma unroll
+        for (int s2 = 0; s2 < S; ++s2) {
+            const float tv = s_tab[s2 * 16 + ((w[s2 >> 3] >> (4 * (s2 & 7))) & 15u)];
+            acc = s2 == 0 ? tv : acc + tv;
+        }
+        return acc;
+    };
+    // rows of samp16 are 8-byte aligned (scap % 4 == 0): four samples per load; entries past ns and samples the
+    // allow-bitmap rejected (0xFFFF) count as absent
+    const uint2 *src = reinterpret_cast<const uint2 *>(a.samp16 + (size_t)q * a.scap);
+    const uint32_t n4 = (ns + 3u) >> 2;
+    auto value = [&](uint2 v, uint32_t i4, int c) {   // sample 4 i4 + c of the row, as this pass sees it
+        const uint32_t x = ((c < 2 ? v.x : v.y) >> (16 * (c & 1))) & 0xFFFFu;
+        return (4u * i4 + (uint32_t)c >= ns || x == 0xFFFFu) ? 0xFFFFFFFFu : x;
+    };
+    uint32_t m0 = 0xFFFFFFFFu, m1 = 0xFFFFFFFFu;   // the two smallest of this thread's samples, m0 <= m1
+    auto keep = [&](uint32_t x) {
+        const uint32_t hi = x > m0 ? x : m0;
+        m0 = x < m0 ? x : m0;
+        m1 = hi < m1 ? hi : m1;
+    };
+    constexpr int LU = 8;   // 8-byte loads in flight per thread
+    if (!exact) {
+        for (uint32_t i0 = 0; i0 < n4; i0 += LU * nt) {
+            uint2 v[LU];
+#pragma unroll
+            for (int u = 0; u < LU; ++u) {
+                const uint32_t i4 = i0 + u * nt + tid;
+                v[u] = i4 < n4 ? src[i4] : make_uint2(~0u, ~0u);
+            }
+#pragma unroll
+            for (int u = 0; u < LU; ++u)
+#pragma unroll
+                for (int c = 0; c < 4; ++c) keep(value(v[u], i0 + u * nt + tid, c));
+        }
+    } else {   // (thread tid takes the samples threshold_tail_kernel gives it: the same kept values, the same pivot)
+        for (uint32_t i4 = tid; i4 < n4; i4 += nt) {
+            const uint2 v = src[i4];
+#pragma unroll 1
+            for (int c = 0; c < 4; ++c)
+                keep(value(v, i4, c) == 0xFFFFFFFFu ? 0xFFFFFFFFu : f32_to_ordered(dist(4u * i4 + (uint32_t)c)));
+        }
+    }
+    s_kept[2 * tid] = m0;
+    s_kept[2 * tid + 1] = m1;
+    __syncthreads();
+    const SelCfg cfg = sel_cfg(kThrTailList);   // bins 1024, list 256
+    const uint32_t pivot = block_select<uint32_t>(s_kept, 2 * nt, J, cfg, s_hist, reinterpret_cast<uint32_t *>(s_slist), s_red);
+    __syncthreads();
+    // collect limit (in the unit of the pass's values) and the ordered distance of the flood bound; with fewer than J
+    // kept values present the limit is "every present value"
+    uint32_t lim, flood;
+    if (exact) {
+        lim = flood = pivot == 0xFFFFFFFFu ? 0xFFFFFFFEu : pivot;
+    } else if (pivot == 0xFFFFFFFFu) {
+        lim = 0xFFFEu;
+        flood = 0xFFFFFFFEu;
+    } else {
+        const double Sd = (double)S, eps = Sd * 1.1920928955078125e-07;
+        const double Dmax = (mt.bias_sum + mt.scale * ((double)pivot + Sd * (0.5 + 1e-9))) * (1.0 + eps);
+        const double ql = floor((Dmax * (1.0 + eps) - mt.bias_sum) / mt.scale + 0.5 * Sd + 1.0);
+        lim = ql >= 65534.0 ? 0xFFFEu : (uint32_t)ql;
+        float Df = (float)Dmax;   // rounded up: the bound must not fall under Dmax
+        if ((double)Df < Dmax) Df = __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, Df) + 1u);
+        flood = f32_to_ordered(Df);
+    }
+    if (!exact) {
+        for (uint32_t i0 = 0; i0 < n4; i0 += LU * nt) {
+            uint2 v[LU];
+#pragma unroll
+            for (int u = 0; u < LU; ++u) {
+                const uint32_t i4 = i0 + u * nt + tid;
+                v[u] = i4 < n4 ? src[i4] : make_uint2(~0u, ~0u);
+            }
+#pragma unroll
+            for (int u = 0; u < LU; ++u)
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    const uint32_t i4 = i0 + u * nt + tid;
+                    if (value(v[u], i4, c) <= lim) {
+                        const uint32_t pos = atomicAdd(&s_cnt[0], 1u);
+                        if (pos < kThrTailList) s_keys[pos] = 4u * i4 + (uint32_t)c;
+                    }
+                }
+        }
+    } else {
+        for (uint32_t i4 = tid; i4 < n4; i4 += nt) {
+            const uint2 v = src[i4];
+#pragma unroll 1
+            for (int c = 0; c < 4; ++c) {
+                if (value(v, i4, c) == 0xFFFFFFFFu) continue;
+                const uint32_t i = 4u * i4 + (uint32_t)c, x = f32_to_ordered(dist(i));
+                if (x <= lim) {
+                    const uint32_t pos = atomicAdd(&s_cnt[0], 1u);
+                    if (pos < kThrTailList) s_keys[pos] = ((uint64_t)x << 32) | i;
+                }
+            }
+        }
+    }
+    __syncthreads();
+    const uint32_t n_le = s_cnt[0];
+    if (n_le < J) {   // fewer than J present samples in all: no bound
+        publish(SCANN_KEY_MAX);
+        return;
+    }
+    if (n_le > kThrTailList) {   // the list floods: (Dmax, MAX) is at or above the J-th smallest key
+        publish(((uint64_t)flood << 32) | 0xFFFFFFFFu);
+        return;
+    }
+    if (!exact) {   // the collected slots -> their exact keys (each entry by the thread that rewrites it)
+        for (uint32_t e = tid; e < n_le; e += nt) {
+            const uint32_t i = (uint32_t)s_keys[e];
+            s_keys[e] = make_key(dist(i), i);
+        }
+        __syncthreads();
+    }
+    const uint64_t key = block_select<uint64_t>(s_keys, n_le, J, cfg, s_hist, s_slist, s_red);
+    const uint32_t v = (uint32_t)(key >> 32), slot = (uint32_t)key;
+    // stream position of that sample: token r = the largest with sb[r] <= slot
+    uint32_t lo = 0, hi = P;
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (sb[mid] <= slot) lo = mid; else hi = mid;
+    }
+    publish(((uint64_t)v << 32) | (vb[lo] + (slot - sb[lo]) * a.st));
 }
 
 // =====================================================================================
@@ -4722,7 +5029,24 @@ template <typename C>
 static int launch_scan_stages(const TxhIndexDev &ix, const TxhWork &w, hipStream_t st,
                               hipEvent_t ev0, hipEvent_t ev1) {
     const int cus = num_cus();
-    if (!w.no_threshold) {
+    if constexpr (C::BITS == 4) {
+        if (w.sample_mfma) {   // flat hasher in front of an MFMA prefilter (K5d / K5e): plain tables, integer sample, tail bound
+            Lut8Meta *meta = reinterpret_cast<Lut8Meta *>(w.lut8_meta);
+            SCANN_TRY(launch(lut8_build_kernel, dim3(w.max_quads), dim3(256), 0, st, (uint32_t)C::S, w.lutq, w.counters,
+                             w.lut8, meta, w.pair_q, w.pair_thr, w.mfma_thr1, -1));
+            SampleMfmaArgs sm;
+            sm.pair_off = w.pair_off; sm.pair_q = w.pair_q; sm.pair_sbase = w.pair_sbase; sm.lut8 = w.lut8;
+            sm.samp16 = reinterpret_cast<uint16_t *>(w.samp); sm.scap = w.scap; sm.st = w.st;
+            sm.allow = w.allow; sm.allow_bits = w.allow_bits;
+            SCANN_TRY(launch(adc_sample_mfma_kernel<C::S>, dim3((uint32_t)cus * 4u), dim3(256), 0, st, ix, sm));
+            Tail16Args ta;
+            ta.P = w.P; ta.m = w.m; ta.st = w.st; ta.scap = w.scap; ta.sbase = w.sbase; ta.slot_of = w.slot_of;
+            ta.tokens = w.tokens; ta.vbase = w.vbase; ta.samp16 = sm.samp16; ta.lutq = w.lutq; ta.meta = meta;
+            ta.thr = w.thr; ta.pair_thr = w.pair_thr;
+            SCANN_TRY(launch(threshold_tail16_kernel<C::S>, dim3(w.nq), dim3(kThrTailThreads), 0, st, ix, ta));
+        }
+    }
+    if (!w.no_threshold && !w.sample_mfma) {
         SampleArgs sa;
         sa.pair_off = w.pair_off; sa.stile_off = w.stile_off; sa.pair_q = w.pair_q;
         sa.pair_sbase = w.pair_sbase; sa.counters = w.counters; sa.lutq = w.lutq; sa.samp = w.samp;
@@ -4730,7 +5054,7 @@ static int launch_scan_stages(const TxhIndexDev &ix, const TxhWork &w, hipStream
         const size_t lds_smp = (size_t)2 * C::LUT4 * 16 + 16;
         SCANN_TRY(launch(adc_sample_kernel<C>, dim3((uint32_t)cus * 8u), dim3(kScanThreads), lds_smp, st, ix, sa));
     }
-    {
+    if (!w.sample_mfma) {
         const SelCfg tcfg = sel_cfg(w.scap);
         const size_t lds_thr = ((size_t)((w.scap + 3u) & ~3u) + tcfg.bins + tcfg.list) * 4 + 48 * 8;
         const uint32_t nt = w.scap > 8192 ? kSelectThreads : 256u;

@@ -35,7 +35,7 @@ EXPORTS = [
     "scann_hip_compute_stride", "scann_hip_bf_create", "scann_hip_bf_create_quantized", "scann_hip_bf16_quantize",
     "scann_hip_txh_create",
     "scann_hip_search_opts_default", "scann_hip_search_batched", "scann_hip_search_batched_params", "scann_hip_index_reserve",
-    "scann_hip_search_batched_device", "scann_hip_index_last_device_status",
+    "scann_hip_search_batched_device", "scann_hip_index_last_device_status", "scann_hip_index_debug_filter_bounds",
     "scann_hip_crowd_table_slots", "scann_hip_index_set_crowding_attributes", "scann_hip_search_crowded",
     "scann_hip_index_reserve_crowded", "scann_hip_search_crowded_device",
     "scann_hip_index_set_crowding_attributes_md", "scann_hip_search_crowded_md", "scann_hip_search_crowded_md_device",
@@ -157,6 +157,7 @@ def load():
     L.scann_hip_search_batched_device.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32,
                                                   C.POINTER(SearchOpts), vp, vp, vp, vp]
     L.scann_hip_index_last_device_status.argtypes = [vp, vp]
+    L.scann_hip_index_debug_filter_bounds.argtypes = [vp, vp, C.c_uint32, u64p]
     L.scann_hip_crowd_table_slots.restype = C.c_uint32
     L.scann_hip_crowd_table_slots.argtypes = [C.c_uint32]
     L.scann_hip_index_set_crowding_attributes.argtypes = [vp, u64p, C.c_uint64]
@@ -532,6 +533,13 @@ class Index:
         name = C.c_char_p()
         ms = load().scann_hip_index_last_kernel_ms(self.h, C.byref(name))
         return float(ms), (name.value or b"").decode()
+
+    def debug_filter_bounds(self, nq, stream=0):
+        """The filter bounds (uint64 merge keys, all ones = none) of the last batched search enqueued on `stream`
+        (a HIP stream handle), which the caller has synchronised.  scann_hip_index_debug_filter_bounds."""
+        out = np.zeros(nq, np.uint64)
+        check(load().scann_hip_index_debug_filter_bounds(self.h, vp(stream), nq, ptr(out, u64p)))
+        return out
 
 
 class Mutable:
