@@ -12,8 +12,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "_obj")
 LIB = os.path.join(HERE, "libscann_hip.so")
-SOURCES = ["api.hip", "txh.hip", "bf.hip", "index_file.hip", "comm.hip", "crowd.hip", "mmr.hip", "mutable.hip", "fold.hip"]
-HEADERS = ["common.h", "knobs.h", "txh.h", "bf.h", "comm.h", "crowd.h", "mmr.h", "mutable.h", "fold.h", "index_arrays.h", "pair.h", "launch.h", os.path.join("..", "..", "include", "scann_hip.h")]
+# the units of the tree / flat-hasher search
+TXH_SOURCES = ["txh.hip", "txh_partition.hip", "txh_prefilter.hip", "txh_rows.hip", "txh_blocks.hip"]
+SOURCES = ["api.hip"] + TXH_SOURCES + ["bf.hip", "index_file.hip", "comm.hip", "crowd.hip", "mmr.hip", "mutable.hip", "fold.hip"]
+HEADERS = ["common.h", "knobs.h", "txh.h", "txh_dev.h", "txh_stages.h", "bf.h", "comm.h", "crowd.h", "mmr.h", "mutable.h", "fold.h", "index_arrays.h", "pair.h", "launch.h", os.path.join("..", "..", "include", "scann_hip.h")]
 # -ffp-contract=off: the reference never contracts a*b+c (Rust); FMA is used only via
 # explicit fmaf()/MFMA where the reference uses _mm256_fmadd_ps.
 CFLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "-fPIC", "-Wall",
@@ -63,7 +65,16 @@ def _stale_objects(force, extra_flags):
     return out
 
 
-def build_variant(name, extra_flags, only=("txh.hip",)):
+def _jobs(n):
+    """Compiles side by side: MAX_JOBS when it is set, else the CPU count; never more than 16 or than there is to do."""
+    try:
+        limit = int(os.environ.get("MAX_JOBS", ""))
+    except ValueError:
+        limit = os.cpu_count() or 1
+    return max(1, min(n, limit, 16))
+
+
+def build_variant(name, extra_flags, only=tuple(TXH_SOURCES)):
     """A tuning variant of the library: `only` sources recompiled with extra -D flags, the other objects
     reused; written to libscann_hip_<name>.so (select with SCANN_HIP_LIB)."""
     build()
@@ -95,7 +106,7 @@ def build(force=False, verbose=False, extra_flags=()):
             print(" ".join(cmd), flush=True)
         subprocess.check_call(cmd, cwd=CSRC)
 
-    with ThreadPoolExecutor(max_workers=max(1, min(len(todo), os.cpu_count() or 1))) as ex:
+    with ThreadPoolExecutor(max_workers=_jobs(len(todo))) as ex:
         list(ex.map(compile_one, todo))
     cmd = [hipcc] + LDFLAGS + ["-o", LIB] + objs
     if verbose:

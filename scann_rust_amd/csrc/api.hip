@@ -886,7 +886,7 @@ static int txh_finish(scann_hip_index *ix, const scann_hip_txh_desc *d, const st
     t.codes = exact ? nullptr : ix->d_codes.as<uint32_t>();
     t.codes_sp = nullptr;
     const Knobs kn = read_knobs();
-    // operand planes of the sparse-MFMA prefilter (txh.hip K6e): a second copy of the 4-bit codes, S/2 .. 2 S bytes
+    // operand planes of the sparse-MFMA prefilter (txh_prefilter.hip K6e): a second copy of the 4-bit codes, S/2 .. 2 S bytes
     // per point.  SCANN_HIP_SMFMAC=0: not built, the dense integer-MFMA prefilter is used instead.
     {
         if (!exact && bits == 4 && kn.smfmac) {
@@ -1137,7 +1137,7 @@ static int plan_txh_search(const scann_hip_index *ix, uint32_t k, const scann_hi
     if (kn.resident == 0) resident = false;
     if (kn.resident == 2) resident = res_layout;
     if (kn.res_cl) p.res_cl = kn.res_cl;
-    // Integer-MFMA prefilter + exact refine (txh.hip K6d): 4-bit codes, a filter bound to prove
+    // Integer-MFMA prefilter + exact refine (txh_prefilter.hip K6d): 4-bit codes, a filter bound to prove
     // against, and enough pairs per leaf to fill 32-column MFMA tiles (a leaf scanned by few
     // queries would leave most columns empty; the LDS-gather kernels take those).
     // Leaves scanned by 8-24 queries (2-5 quads: typical Tree-X-Hybrid batches) take the 16-column form

@@ -787,7 +787,7 @@ typedef float f32x2q __attribute__((ext_vector_type(2)));
 template <int FMT>
 __host__ __device__ constexpr uint32_t quant_bytes() { return FMT == SCANN_HIP_ROWS_BF16 ? 2u : 1u; }
 
-// fp8_to_f32(b, 0) of txh.hip without branches: exponent field e and mantissa m as one 7-bit field em shifted
+// fp8_to_f32(b, 0) of txh_rows.hip without branches: exponent field e and mantissa m as one 7-bit field em shifted
 // into place, biased by 120 = 127 - 7, one binade lower when e == 0 (2^-8 * (1 + m/8)), zero when em == 0.
 // The branchy form makes the compiler decode a whole 64-element block into registers before using it.
 __device__ __forceinline__ float fp8_e4m3_to_f32(uint32_t b) {

@@ -104,7 +104,7 @@ struct TxhIndexDev {
     const uint32_t *leaf_ids;     // [n_local] datapoint index of CSR row; nullptr = identity
     const uint32_t *codes;        // [n_local][nw] packed 4-bit codes, 8 subspaces per word
     const uint32_t *codes_sp;     // [n_local][sp_words(S)] the same codes as operand planes of the 2:4-sparse MFMA prefilter
-                                  // (txh.hip K6e; 4-bit codes only), or nullptr
+                                  // (txh_prefilter.hip K6e; 4-bit codes only), or nullptr
     const float *rows;            // re-rank rows; CSR order if rows_csr else by datapoint idx
     const int8_t *rows8;          // the same rows as int8 (per-row scale) for the re-rank filter, or nullptr
     int rows8_fmt;                // 0 = int8, 1 = the reference's FP8 E4M3 codes (quantization/fp8.rs)
@@ -119,7 +119,7 @@ struct TxhIndexDev {
     int exact_scan;               // SearchMode::Partitioned: no codes, rows of the leaves scored exactly
 };
 
-// points of one scan tile chunk for this index's code layout (Codec<S, bits>::TP in txh.hip)
+// points of one scan tile chunk for this index's code layout (Codec<S, bits>::TP in txh_dev.h)
 static inline uint32_t scan_tile_points(const TxhIndexDev &ix) {
     return kScanThreads * (ix.code_bits == 4 ? kScanPPT : 8u);
 }
@@ -273,7 +273,7 @@ int launch_rows_i8_build(const float *d_rows, uint64_t n, uint32_t dim, uint32_t
 int launch_lut16_quantize(const float *d_tables, uint32_t S, uint8_t *d_lut8, float *d_bias_mult,
                           hipStream_t stream);
 
-// Operand planes of the sparse-MFMA prefilter (txh.hip K6e) from the packed 4-bit codes: words per point and the
+// Operand planes of the sparse-MFMA prefilter (txh_prefilter.hip K6e) from the packed 4-bit codes: words per point and the
 // build kernel.
 static inline uint32_t sp_words(uint32_t S) { return 4u * ((((S - 4u) / 4u + 1u) + 7u) / 8u); }
 int launch_codes_sp_build(const uint32_t *d_codes, uint64_t n, uint32_t S, uint32_t *d_codes_sp, hipStream_t stream);

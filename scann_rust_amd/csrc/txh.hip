@@ -1,9 +1,9 @@
 // txh.hip -- HIP kernels of the Tree-X-Hybrid / AsymmetricHasher search path (gfx950).
 //
 // Pipeline per query batch (reference: tree_x_hybrid/mod.rs:245-364):
-//   centroid_scores -> select_leaves            TreePartitioner::partition
-//   count/scan/fill worklist                    (groups (query, leaf) pairs by leaf)
-//   lut_build                                   residual + LookupTable::from_query
+//   centroid_scores -> select_leaves            TreePartitioner::partition            (K1: txh_partition.hip)
+//   count/scan/fill worklist                    (groups (query, leaf) pairs by leaf)  (txh_partition.hip)
+//   lut_build                                   residual + LookupTable::from_query    (txh_partition.hip)
 //   sample_threshold                            valid upper bound of the m-th best key
 //   adc_scan (dominant, LDS-staged LUT16)       LookupTable::compute_distance + FastTopNeighbors
 //   select_rerank                               merge/sort/truncate + reorder_results
@@ -15,62 +15,10 @@
 
 #include "launch.h"
 #include "pair.h"
-#include "txh.h"
+#include "txh_dev.h"
+#include "txh_stages.h"
 
 namespace scann {
-
-// =====================================================================================
-// K1: centroid scores.  partitioning/tree_partitioner.rs:175-192: strictly sequential
-// scalar sum of (q_j - c_j)^2, no FMA.  One thread per centroid, QT queries per block
-// broadcast from LDS.
-// =====================================================================================
-template <int kCsQT>
-__global__ __launch_bounds__(64) void centroid_scores_kernel(
-    const float *__restrict__ centers, uint32_t L, uint32_t dim,
-    const float *__restrict__ queries, uint32_t nq, uint32_t q_stride,
-    float *__restrict__ out) {
-    extern __shared__ __attribute__((aligned(16))) float qs[];  // [kCsQT][dim]
-    const uint32_t q0 = blockIdx.y * kCsQT;
-    for (uint32_t i = threadIdx.x; i < kCsQT * dim; i += blockDim.x) {
-        uint32_t qi = i / dim, j = i - qi * dim;
-        qs[i] = (q0 + qi < nq) ? queries[(size_t)(q0 + qi) * q_stride + j] : 0.0f;
-    }
-    __syncthreads();
-    const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= L) return;
-    float acc[kCsQT];
-#pragma unroll
-    for (int qi = 0; qi < kCsQT; ++qi) acc[qi] = 0.0f;
-    const float *crow = centers + (size_t)c * dim;
-    if ((dim & 3u) == 0) {
-        for (uint32_t j = 0; j < dim; j += 4) {
-            const float4 cv = *reinterpret_cast<const float4 *>(crow + j);
-#pragma unroll
-            for (int qi = 0; qi < kCsQT; ++qi) {
-                const float4 qv = *reinterpret_cast<const float4 *>(qs + qi * dim + j);
-                float d0 = qv.x - cv.x, d1 = qv.y - cv.y, d2 = qv.z - cv.z, d3 = qv.w - cv.w;
-                float a = acc[qi];
-                a = a + d0 * d0;
-                a = a + d1 * d1;
-                a = a + d2 * d2;
-                a = a + d3 * d3;
-                acc[qi] = a;
-            }
-        }
-    } else {
-        for (uint32_t j = 0; j < dim; ++j) {
-            const float cv = crow[j];
-#pragma unroll
-            for (int qi = 0; qi < kCsQT; ++qi) {
-                float d = qs[qi * dim + j] - cv;
-                acc[qi] = acc[qi] + d * d;
-            }
-        }
-    }
-#pragma unroll
-    for (int qi = 0; qi < kCsQT; ++qi)
-        if (q0 + qi < nq) out[(size_t)(q0 + qi) * L + c] = acc[qi];
-}
 
 // =====================================================================================
 // K2: select leaves.  tree_partitioner.rs:206-228: stable sort of ALL L (dist, id) by
@@ -307,298 +255,6 @@ __global__ __launch_bounds__(kSelectThreads) void select_leaves_kernel(
                        tokens, token_dists, vbase, sbase, centers_inline, queries, q_stride, dim, centers_pitch);
 }
 
-// AsymmetricHasher mode: one implicit leaf (id 0) for every query.
-__global__ void ah_tokens_kernel(uint32_t nq, const uint32_t *__restrict__ leaf_gsize,
-                                 const uint32_t *__restrict__ leaf_off, uint32_t st,
-                                 uint32_t *__restrict__ tokens, float *__restrict__ token_dists,
-                                 uint32_t *__restrict__ vbase, uint32_t *__restrict__ sbase) {
-    uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
-    if (q >= nq) return;
-    tokens[q] = 0;
-    token_dists[q] = 0.0f;
-    vbase[2 * q] = 0;
-    vbase[2 * q + 1] = leaf_gsize[0];
-    const uint32_t sz = leaf_off[1] - leaf_off[0];
-    sbase[3 * q] = 0;
-    sbase[3 * q + 1] = (sz + st - 1) / st;
-    sbase[3 * q + 2] = sz;
-}
-
-// =====================================================================================
-// K3: worklist -- group (query, rank) pairs by leaf so that every leaf's codes are read
-// once per batch and shared by all queries that selected it.
-// =====================================================================================
-// One launch instead of five memsets: zero the per-batch counters, mark all pair slots free.
-__global__ void txh_init_kernel(uint32_t L, uint32_t nq, uint32_t max_slots,
-                                uint32_t *__restrict__ leaf_cnt, uint32_t *__restrict__ leaf_cursor,
-                                uint32_t *__restrict__ counters, uint32_t *__restrict__ cand_cnt,
-                                uint32_t *__restrict__ cand32_cnt, uint32_t *__restrict__ pair_q) {
-    const uint32_t i0 = blockIdx.x * blockDim.x + threadIdx.x, step = gridDim.x * blockDim.x;
-    for (uint32_t i = i0; i < L; i += step) {
-        leaf_cnt[i] = 0;
-        leaf_cursor[i] = 0;
-    }
-    for (uint32_t i = i0; i < nq; i += step) {
-        cand_cnt[i] = 0;
-        if (cand32_cnt) cand32_cnt[i] = 0;
-    }
-    for (uint32_t i = i0; i < max_slots; i += step) pair_q[i] = kInvalid;
-    for (uint32_t i = i0; i < CNT_WORDS; i += step) counters[i] = 0;
-}
-
-// ah != 0: one implicit leaf selected by every query -- no atomics (1024 same-address global
-// atomics cost more than the whole LUT build).
-__global__ void worklist_count_kernel(uint32_t npairs, int ah, const uint32_t *__restrict__ tokens,
-                                      const uint32_t *__restrict__ leaf_off,
-                                      uint32_t *__restrict__ leaf_cnt) {
-    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (ah) {
-        if (i == 0) leaf_cnt[0] = leaf_off[1] > leaf_off[0] ? npairs : 0u;
-        return;
-    }
-    if (i >= npairs) return;
-    uint32_t leaf = tokens[i];
-    if (leaf_off[leaf + 1] > leaf_off[leaf]) atomicAdd(&leaf_cnt[leaf], 1u);
-}
-
-__global__ __launch_bounds__(1024) void worklist_scan_kernel(
-    uint32_t L, const uint32_t *__restrict__ leaf_cnt, const uint32_t *__restrict__ leaf_off,
-    uint32_t tp, uint32_t quads_per_tile, uint32_t chunks_per_tile, uint32_t stp, uint32_t st,
-    uint32_t squads_per_tile,
-    uint32_t *__restrict__ pair_off, uint32_t *__restrict__ tile_off,
-    uint32_t *__restrict__ stile_off, uint32_t *__restrict__ counters) {
-    __shared__ uint32_t s_pairs[1024], s_tiles[1024], s_stiles[1024];
-    const uint32_t t = threadIdx.x;
-    const uint32_t per = (L + 1023) / 1024;
-    const uint32_t b = t * per, e = min(L, b + per);
-    // tiles of the scan (all points) and of the sample pass (every st-th point)
-    auto tiles_of = [&](uint32_t c, uint32_t pad, uint32_t sz, uint32_t *smp) {
-        if (!c) { *smp = 0; return 0u; }
-        const uint32_t ssz = (sz + st - 1) / st;
-        *smp = ((ssz + stp - 1) / stp) * ((pad / 4 + squads_per_tile - 1) / squads_per_tile);
-        const uint32_t nch = (sz + tp - 1) / tp;
-        return ((nch + chunks_per_tile - 1) / chunks_per_tile) * ((pad / 4 + quads_per_tile - 1) / quads_per_tile);
-    };
-    uint32_t sp = 0, stl = 0, sst = 0;
-    for (uint32_t l = b; l < e; ++l) {
-        uint32_t c = leaf_cnt[l];
-        uint32_t pad = (c + 3u) & ~3u;
-        uint32_t sz = leaf_off[l + 1] - leaf_off[l];
-        uint32_t smp;
-        sp += pad;
-        stl += tiles_of(c, pad, sz, &smp);
-        sst += smp;
-    }
-    s_pairs[t] = sp;
-    s_tiles[t] = stl;
-    s_stiles[t] = sst;
-    __syncthreads();
-    for (uint32_t off = 1; off < 1024; off <<= 1) {  // Hillis-Steele inclusive scan
-        uint32_t a = 0, c2 = 0, c3 = 0;
-        if (t >= off) {
-            a = s_pairs[t - off];
-            c2 = s_tiles[t - off];
-            c3 = s_stiles[t - off];
-        }
-        __syncthreads();
-        s_pairs[t] += a;
-        s_tiles[t] += c2;
-        s_stiles[t] += c3;
-        __syncthreads();
-    }
-    uint32_t bp = s_pairs[t] - sp, bt = s_tiles[t] - stl, bs = s_stiles[t] - sst;
-    for (uint32_t l = b; l < e; ++l) {
-        uint32_t c = leaf_cnt[l];
-        uint32_t pad = (c + 3u) & ~3u;
-        uint32_t sz = leaf_off[l + 1] - leaf_off[l];
-        uint32_t smp;
-        pair_off[l] = bp;
-        tile_off[l] = bt;
-        stile_off[l] = bs;
-        bp += pad;
-        bt += tiles_of(c, pad, sz, &smp);
-        bs += smp;
-    }
-    if (t == 1023) {
-        pair_off[L] = s_pairs[1023];
-        tile_off[L] = s_tiles[1023];
-        stile_off[L] = s_stiles[1023];
-        counters[CNT_TOTAL_QUADS] = s_pairs[1023] / 4;
-        counters[CNT_TOTAL_TILES] = s_tiles[1023];
-        counters[CNT_TOTAL_STILES] = s_stiles[1023];
-    }
-}
-
-// AsymmetricHasher mode (one leaf, every query's only token): everything txh_init_kernel, ah_tokens_kernel and
-// the three worklist kernels write is known from nq alone -- one single-workgroup kernel instead of five
-// launches (~4.5 us of dispatch each).  Same arrays, same values.
-struct AhSetupArgs {
-    uint32_t nq, max_slots, st, tp, quads_per_tile, chunks_per_tile, stp, squads_per_tile;
-    const uint32_t *leaf_gsize, *leaf_off;
-    uint32_t *leaf_cnt, *leaf_cursor, *counters, *cand_cnt, *cand32_cnt, *pair_q, *pair_leaf, *pair_vbase, *pair_sbase,
-        *slot_of, *tokens, *vbase, *sbase, *pair_off, *tile_off, *stile_off;
-    float *token_dists;
-};
-
-__global__ __launch_bounds__(1024) void ah_setup_kernel(AhSetupArgs a) {
-    const uint32_t tid = threadIdx.x, nt = blockDim.x;
-    const uint32_t sz = a.leaf_off[1] - a.leaf_off[0], gs = a.leaf_gsize[0];
-    const uint32_t c = sz ? a.nq : 0u, pad = (c + 3u) & ~3u;
-    const uint32_t ssz = (sz + a.st - 1) / a.st;
-    for (uint32_t i = tid; i < a.max_slots; i += nt) a.pair_q[i] = (sz && i < a.nq) ? i : kInvalid;   // slot of query i = i
-    for (uint32_t i = tid; i < CNT_WORDS; i += nt) {
-        uint32_t v = 0;
-        if (c) {
-            const uint32_t nch = (sz + a.tp - 1) / a.tp;
-            if (i == CNT_TOTAL_QUADS) v = pad / 4;
-            if (i == CNT_TOTAL_TILES)
-                v = ((nch + a.chunks_per_tile - 1) / a.chunks_per_tile) * ((pad / 4 + a.quads_per_tile - 1) / a.quads_per_tile);
-            if (i == CNT_TOTAL_STILES)
-                v = ((ssz + a.stp - 1) / a.stp) * ((pad / 4 + a.squads_per_tile - 1) / a.squads_per_tile);
-        }
-        a.counters[i] = v;
-    }
-    for (uint32_t q = tid; q < a.nq; q += nt) {
-        a.cand_cnt[q] = 0;
-        if (a.cand32_cnt) a.cand32_cnt[q] = 0;
-        a.tokens[q] = 0;
-        a.token_dists[q] = 0.0f;
-        a.vbase[2 * q] = 0;
-        a.vbase[2 * q + 1] = gs;
-        a.sbase[3 * q] = 0;
-        a.sbase[3 * q + 1] = ssz;
-        a.sbase[3 * q + 2] = sz;
-        if (sz) {
-            a.pair_leaf[q] = 0;
-            a.pair_vbase[q] = 0;
-            a.pair_sbase[q] = 0;
-        }
-        a.slot_of[q] = sz ? q : kInvalid;
-    }
-    if (tid == 0) {
-        a.leaf_cnt[0] = c;
-        a.leaf_cursor[0] = 0;
-        uint32_t tiles = 0, stiles = 0;
-        if (c) {
-            const uint32_t nch = (sz + a.tp - 1) / a.tp;
-            tiles = ((nch + a.chunks_per_tile - 1) / a.chunks_per_tile) * ((pad / 4 + a.quads_per_tile - 1) / a.quads_per_tile);
-            stiles = ((ssz + a.stp - 1) / a.stp) * ((pad / 4 + a.squads_per_tile - 1) / a.squads_per_tile);
-        }
-        a.pair_off[0] = 0;
-        a.pair_off[1] = pad;
-        a.tile_off[0] = 0;
-        a.tile_off[1] = tiles;
-        a.stile_off[0] = 0;
-        a.stile_off[1] = stiles;
-    }
-}
-
-__global__ void worklist_fill_kernel(uint32_t nq, uint32_t P, int ah, const uint32_t *__restrict__ tokens,
-                                     const uint32_t *__restrict__ vbase,
-                                     const uint32_t *__restrict__ sbase,
-                                     const uint32_t *__restrict__ leaf_off,
-                                     const uint32_t *__restrict__ pair_off,
-                                     uint32_t *__restrict__ leaf_cursor,
-                                     uint32_t *__restrict__ pair_q, uint32_t *__restrict__ pair_leaf,
-                                     uint32_t *__restrict__ pair_vbase,
-                                     uint32_t *__restrict__ pair_sbase,
-                                     uint32_t *__restrict__ slot_of) {
-    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= nq * P) return;
-    uint32_t q = i / P, r = i - q * P;
-    uint32_t leaf = tokens[i];
-    uint32_t slot = kInvalid;
-    if (leaf_off[leaf + 1] > leaf_off[leaf]) {
-        slot = pair_off[leaf] + (ah ? i : atomicAdd(&leaf_cursor[leaf], 1u));
-        pair_q[slot] = q;
-        pair_leaf[slot] = leaf;
-        pair_vbase[slot] = vbase[(size_t)q * (P + 1) + r];
-        pair_sbase[slot] = sbase[(size_t)q * (P + 2) + r];
-    }
-    slot_of[i] = slot;
-}
-
-// =====================================================================================
-// K4: LUT build.  tree_x_hybrid/mod.rs:309-319 + hashes/lut.rs:47-70 +
-// hashes/codebook.rs:98-115: q' = q - centroid (if residual); LUT[s][c] = sequential
-// scalar sum over dsub of (q'_j - cb_j)^2.  Output layout is quad-interleaved
-// [quad][s][kp][4] (kp = 16 or 256 slots) so that the scan reads four queries' entries with
-// one ds_read_b128.
-// =====================================================================================
-__global__ __launch_bounds__(256) void lut_build_kernel(
-    TxhIndexDev ix, const float *__restrict__ queries, uint32_t q_stride,
-    const uint32_t *__restrict__ pair_q, const uint32_t *__restrict__ pair_leaf,
-    const uint32_t *__restrict__ counters, float *__restrict__ lutq) {
-    extern __shared__ float qres[];  // [4][dim]
-    const uint32_t quad = blockIdx.x;
-    if (quad >= counters[CNT_TOTAL_QUADS]) return;
-    const uint32_t dim = ix.dim;
-    for (uint32_t i = threadIdx.x; i < 4 * dim; i += blockDim.x) {
-        uint32_t p = i / dim, j = i - p * dim;
-        uint32_t q = pair_q[quad * 4 + p];
-        float v = 0.0f;
-        if (q != kInvalid) {
-            v = queries[(size_t)q * q_stride + j];
-            if (ix.use_residuals) v = v - ix.centers[(size_t)pair_leaf[quad * 4 + p] * dim + j];
-        }
-        qres[i] = v;
-    }
-    __syncthreads();
-    const uint32_t S = ix.S, K = ix.K, dsub = ix.dsub, kp = ix.kp;   // kp = 16 or 256 table slots
-    float4 *out = reinterpret_cast<float4 *>(lutq) + (size_t)quad * S * kp;
-    for (uint32_t e = threadIdx.x; e < S * kp; e += blockDim.x) {
-        uint32_t s = e / kp, c = e - s * kp;
-        float r[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-        if (c < K) {
-            const float *cb = ix.codebook + ((size_t)s * K + c) * dsub;
-            for (uint32_t j = 0; j < dsub; ++j) {
-                float cv = cb[j];
-#pragma unroll
-                for (int p = 0; p < 4; ++p) {
-                    float d = qres[p * dim + s * dsub + j] - cv;
-                    r[p] = r[p] + d * d;
-                }
-            }
-        }
-        out[e] = make_float4(r[0], r[1], r[2], r[3]);
-    }
-}
-
-// Plain LookupTable::from_query for callers/tests: out [nq][S][K].
-__global__ __launch_bounds__(256) void lut_from_query_kernel(
-    TxhIndexDev ix, const float *__restrict__ queries, uint32_t q_stride,
-    const uint32_t *__restrict__ leaf_for_query, float *__restrict__ out) {
-    extern __shared__ float qres[];  // [dim]
-    const uint32_t q = blockIdx.x, dim = ix.dim;
-    for (uint32_t j = threadIdx.x; j < dim; j += blockDim.x) {
-        float v = queries[(size_t)q * q_stride + j];
-        if (leaf_for_query) v = v - ix.centers[(size_t)leaf_for_query[q] * dim + j];
-        qres[j] = v;
-    }
-    __syncthreads();
-    const uint32_t S = ix.S, K = ix.K, dsub = ix.dsub;
-    for (uint32_t e = threadIdx.x; e < S * K; e += blockDim.x) {
-        uint32_t s = e / K;
-        const float *cb = ix.codebook + (size_t)e * dsub;
-        float r = 0.0f;
-        for (uint32_t j = 0; j < dsub; ++j) {
-            float d = qres[s * dsub + j] - cb[j];
-            r = r + d * d;
-        }
-        out[(size_t)q * S * K + e] = r;
-    }
-}
-
-// RestrictFilter::is_allowed (restricts/mod.rs:17-30) for the allow-bitmap form of
-// search_with_filter (tree_x_hybrid/mod.rs:327-332): bit i of the bitmap = datapoint i.
-// Indices at or beyond the bitmap's capacity are not allowed (allowlist.rs:97-100).
-__device__ __forceinline__ bool row_allowed(const TxhIndexDev &ix, const uint64_t *allow,
-                                            uint64_t allow_bits, uint32_t csr) {
-    if (!allow) return true;
-    const uint32_t idx = ix.leaf_ids ? ix.leaf_ids[csr] : csr;
-    return idx < allow_bits && ((allow[idx >> 6] >> (idx & 63u)) & 1ull);
-}
-
 // =====================================================================================
 // K6: ADC scan -- the dominant kernel.  hashes/lut.rs:74-82 driven by the loop at
 // tree_x_hybrid/mod.rs:324-336 / hashes/hasher.rs:179-182.
@@ -612,96 +268,6 @@ __device__ __forceinline__ bool row_allowed(const TxhIndexDev &ix, const uint64_
 // the query's candidate list.  Tiles are pulled from an atomic queue so ragged leaves
 // balance across the 256 CUs.
 // =====================================================================================
-// Code layouts the scan understands.  BITS = 4: K <= 16, 8 subspaces per u32 word
-// (PackedCodes4Bit, hashes/lut16.rs:43-61), 16-entry tables.  BITS = 8: 16 < K <= 256 (the
-// reference's default 256 x 8 codebooks, hashes/hasher.rs:36-46), one byte per subspace, 4
-// subspaces per word, 256-entry tables.  A subspace's quad-interleaved table is KP x 16 B.
-template <int S_, int BITS_>
-struct Codec {
-    static constexpr int S = S_, BITS = BITS_;
-    static constexpr int NWORDS = BITS == 4 ? S / 8 : S / 4;      // packed u32 words per point
-    static constexpr int REGS = BITS == 4 ? 2 * NWORDS : NWORDS;  // registers per point in the scan
-    static constexpr int KP = BITS == 4 ? 16 : 256;               // table entries per subspace
-    static constexpr int SUB_BYTES = KP * 16;
-    static constexpr int LUT4 = S * KP;                           // float4 per quad
-    // points per thread per tile chunk: byte-code tables are 16x larger per subspace and there
-    // are 4x fewer subspaces, so a tile takes 4x more points per staged table
-    static constexpr int PPT = BITS == 4 ? (int)kScanPPT : 8;
-    static constexpr int TP = (int)kScanThreads * PPT;            // points per tile chunk
-    static_assert((S - 1) * SUB_BYTES < 65536, "ds_read immediate offset");
-    // workgroups per CU the kernel is built for (LDS: two LUT buffers + survivor stage)
-    static constexpr int WGS = BITS == 4 ? (S <= 32 ? (int)kScanWaves : 3)
-                                         : (2 * LUT4 * 16 + 12288 <= 40 * 1024 ? 4
-                                            : 2 * LUT4 * 16 + 12288 <= 80 * 1024 ? 2 : 1);
-    // packed words -> register form: 4-bit codes pre-shifted to "code * 16" bytes
-    __device__ static __forceinline__ void unpack(const uint32_t (&w)[NWORDS], uint32_t (&r)[REGS]) {
-        if constexpr (BITS == 4) {
-#pragma unroll
-            for (int wi = 0; wi < NWORDS; ++wi) {
-                r[2 * wi] = (w[wi] & 0x0F0F0F0Fu) << 4;
-                r[2 * wi + 1] = w[wi] & 0xF0F0F0F0u;
-            }
-        } else {
-#pragma unroll
-            for (int wi = 0; wi < NWORDS; ++wi) r[wi] = w[wi];
-        }
-    }
-    // byte offset of subspace s's code inside that subspace's table (code * 16)
-    __device__ static __forceinline__ uint32_t offset(const uint32_t (&r)[REGS], int s) {
-        if constexpr (BITS == 4) {
-            const int wi = s >> 3, b = (s >> 1) & 3, h = s & 1;
-            return (r[2 * wi + h] >> (8 * b)) & 0xFFu;
-        } else {
-            return ((r[s >> 2] >> (8 * (s & 3))) & 0xFFu) << 4;
-        }
-    }
-    __device__ static __forceinline__ void load_words(const uint32_t *src, uint32_t (&w)[NWORDS]) {
-        if constexpr (NWORDS == 4) {
-            const uint4 v = *reinterpret_cast<const uint4 *>(src);
-            w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
-        } else if constexpr (NWORDS == 2) {
-            const uint2 v = *reinterpret_cast<const uint2 *>(src);
-            w[0] = v.x; w[1] = v.y;
-        } else {
-#pragma unroll
-            for (int wi = 0; wi < NWORDS; ++wi) w[wi] = src[wi];
-        }
-    }
-    __device__ static __forceinline__ void store_words(uint32_t *dst, const uint32_t (&w)[NWORDS]) {
-        if constexpr (NWORDS == 4) {
-            *reinterpret_cast<uint4 *>(dst) = make_uint4(w[0], w[1], w[2], w[3]);
-        } else if constexpr (NWORDS == 2) {
-            *reinterpret_cast<uint2 *>(dst) = make_uint2(w[0], w[1]);
-        } else {
-#pragma unroll
-            for (int wi = 0; wi < NWORDS; ++wi) dst[wi] = w[wi];
-        }
-    }
-};
-
-// One item of the tile queue of the queue-driven scan kernels.  leaf: the largest l with tile_off[l] <= tile; its points
-// are [lb, lb + size) and its (query, leaf) pairs the slots [slot0, slot_end); local: the item's number inside the leaf,
-// from which every kernel derives its own chunk / range and quad numbers.  All wave-uniform (scalar loads).
-struct WorkItem {
-    uint32_t leaf, lb, size, local, slot0, slot_end;
-};
-__device__ __forceinline__ WorkItem decode_item(const TxhIndexDev &ix, const uint32_t *tile_off, const uint32_t *pair_off,
-                                                uint32_t tile) {
-    uint32_t lo = 0, hi = ix.L;
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (uniform_load(tile_off + mid) <= tile) lo = mid; else hi = mid;
-    }
-    WorkItem w;
-    w.leaf = lo;
-    w.lb = uniform_load(ix.leaf_off + lo);
-    w.size = uniform_load(ix.leaf_off + lo + 1) - w.lb;
-    w.local = tile - uniform_load(tile_off + lo);
-    w.slot0 = uniform_load(pair_off + lo);
-    w.slot_end = uniform_load(pair_off + lo + 1);
-    return w;
-}
-
 // Points G .. G+NP-1 of the lane against the quad's tables.
 template <typename C, int NP, int BUF, int G>
 __device__ __forceinline__ void scan_quad_compute(const float4 *lut_base,
@@ -764,21 +330,6 @@ __device__ __forceinline__ void scan_quad_dispatch(const float4 *lut_s, uint32_t
         if (nsub > 4) scan_quad_compute<C, 2, BUF, 4>(lut_s, regs, acc);
         if (nsub > 6) scan_quad_compute<C, 2, BUF, 6>(lut_s, regs, acc);
     }
-}
-
-// Next tile of this workgroup: XCD x (blockIdx % 8) owns tiles t = x (mod 8) in queue x and
-// steals from the other queues when its own is dry.  kInvalid = no tiles left.
-__device__ __forceinline__ uint32_t grab_tile(uint32_t *queues, uint32_t total_tiles) {
-    const uint32_t xcd = blockIdx.x & 7u;
-    for (uint32_t a2 = 0; a2 < 8u; ++a2) {
-        const uint32_t x = (xcd + a2) & 7u;
-        const uint32_t nx = (total_tiles + 7u - x) >> 3;   // tiles = x (mod 8)
-        uint32_t *ctr = queues + x * CNT_XQ_STRIDE;
-        if (a2 && __hip_atomic_load(ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= nx) continue;
-        const uint32_t l = atomicAdd(ctr, 1u);
-        if (l < nx) return l * 8u + x;
-    }
-    return kInvalid;
 }
 
 #ifndef SCANN_SCAN_STAGE
@@ -1138,1367 +689,6 @@ __global__ __launch_bounds__(kResThreads, 6) void adc_scan_res_kernel(TxhIndexDe
             }
         }
     }
-}
-
-// =====================================================================================
-// K6d: ADC scan as an integer-MFMA prefilter + exact refine (4-bit codes, threshold known).
-//
-// The f32 scan above is bound by the LDS table gather (one ds_read_b128 per point, subspace and
-// quad of queries).  The same sums over QUANTISED tables are a matrix product:
-//     one-hot(codes) [points x (S*16)]  x  lut8 [(S*16) x pairs]   (u8 tables as i8 minus 128)
-// which v_mfma_i32_32x32x32_i8 computes exactly (integer) at 1024 MAC/clk/SIMD: a 32-point x
-// 32-pair tile costs S/2 MFMAs.  The integer sum BOUNDS the reference's f32 sum: with per-subspace
-// offsets mn_s and one scale sc per pair, every table entry v satisfies |v - (mn_s + sc*q)| <=
-// sc*(0.5 + 1e-9), so a point whose f32 sum passes the filter bound T has
-//     sum_q <= (T*(1 + S*2^-23) - sum mn_s)/sc + S/2 + 1
-// (the factor covers the rounding of the sequential f32 adds of non-negative terms).  Points under
-// that integer bound -- the true survivors plus ~10 % -- are listed per query as stream positions,
-// and adc_refine_kernel recomputes THEIR distances with the reference's arithmetic (f32 tables,
-// subspace order: hashes/lut.rs:74-82), forms the merge keys and applies the exact filter.  The
-// candidate lists handed to select_rerank_kernel are therefore identical to adc_scan_kernel's:
-// the same shortlist-plus-proof pattern as the bf16 brute-force pass (bf.hip).
-//
-// Work decomposition: every WAVE pulls its own items (leaf, tile of 32 pair slots, range of
-// kMfmaRange points) from the tile queues; the pair tile's tables are the wave's B fragments for
-// the whole item (S/2 x 4 VGPRs), the A fragment of a (point, subspace pair) is one row of a
-// 16 x 16-byte identity table in LDS (one conflict-free ds_read_b128 at offset code * 16), the
-// 16 results of a lane belong to ONE pair (column) and are compared with that pair's bound.
-// Survivors are staged per (wave, pair) in LDS and written at the end of the item as one
-// contiguous segment per pair behind ONE returning atomic per pair.
-// =====================================================================================
-#ifndef SCANN_MFMA_RANGE
-#define SCANN_MFMA_RANGE 2048
-#endif
-constexpr uint32_t kMfmaRange = SCANN_MFMA_RANGE;     // points per item
-constexpr uint32_t kMfmaStage = 56;       // staged survivors per (wave, pair)
-constexpr uint32_t kMfmaWaves = 4;        // waves per workgroup
-#ifndef SCANN_MFMA_MINW
-#define SCANN_MFMA_MINW 3
-#endif
-#ifndef SCANN_MFMA_DEPTH
-#define SCANN_MFMA_DEPTH 3
-#endif
-constexpr int kMfmaDepth = SCANN_MFMA_DEPTH;   // one-hot LDS reads in flight per wave
-constexpr uint32_t kRefineTablesMax = 40; // pair tables (2 KB each at S = 32) staged in LDS by the refine
-
-struct Lut8Meta {
-    double bias_sum;   // sum over subspaces of the per-subspace minimum
-    double scale;      // table step; 0 = this pair is not prefiltered (every point passes)
-};
-
-// lutq [quad][s][16][4] f32 -> lut8 [slot][s][16] i8 (quantised value - 128) + meta[slot]
-// Pass bound of a pair slot on the integer sums (see the derivation above), as thr + 1: a point passes iff
-// acc - thr1 < 0.  Sums lie in [-128 S, 127 S]; the bound is clamped just outside that range (everything
-// passes: no filter bound, or a table that is not quantised; nothing passes: padding slots).
-__device__ __forceinline__ int mfma_pass_bound(uint32_t S, uint32_t pq, uint64_t T, double bias_sum, double scale) {
-    const int lim = 128 * (int)S + 8;
-    int thr = -lim;
-    if (pq != kInvalid) {
-        thr = lim;
-        if (T != SCANN_KEY_MAX && scale > 0.0) {
-            const double Tf = (double)ordered_to_f32((uint32_t)(T >> 32));
-            const double qmax = floor((Tf * (1.0 + (double)S * 1.1920928955078125e-07) - bias_sum) / scale +
-                                      0.5 * (double)S + 1.0) - 128.0 * (double)S;
-            thr = qmax >= (double)lim ? lim : (qmax <= -(double)lim ? -lim : (int)qmax);
-        }
-    }
-    return thr + 1;
-}
-
-// Three modes.  fold == 0 (dense prefilters): plain tables q - 128 and the pair's pass bound in thr1.  fold < 0 (K5d, ahead
-// of any bound): the same plain tables and meta; pair_thr is not read and thr1 is not written.  fold > 0
-// (adc_smfmac_kernel), the rest of this comment: the pass bound is folded INTO the tables, so that a point passes iff its integer sum
-// is negative (the sparse MFMA accumulates in place: there is no free zero / bound operand, and the sign test is one
-// vector instruction per result instead of two).  With qmax = the largest quantised sum a passing point can have (as
-// in mfma_pass_bound), D = 128 S - 1 - qmax >= 0 is spread over the subspaces, d_s = D / S (+ 1 for the first D % S),
-// and the entries are e = min(127, q - 128 + d_s): sum(q - 128 + d_s) = sum q - qmax - 1 < 0 <=> sum q <= qmax; the
-// clamp at 127 only lowers sums (more points pass, never fewer) and d_s >= 0 means no entry is clamped from below.
-// A bound with qmax > 128 S - 1 (more than half of the table range: a very loose filter) gets a coarser scale first,
-// sc' = (T' - bias) / (127.5 S - 3): every entry still satisfies |v - (mn_s + sc' q)| <= sc' (0.5 + 1e-9), q <= 255.
-// All-pass pairs (no bound, unquantisable table) store -128 everywhere, padding slots of a quad and bounds no point
-// can meet store 127 (sums >= 0).
-__global__ __launch_bounds__(256) void lut8_build_kernel(uint32_t S, const float *__restrict__ lutq,
-                                                        const uint32_t *__restrict__ counters,
-                                                        int8_t *__restrict__ lut8, Lut8Meta *__restrict__ meta,
-                                                        const uint32_t *__restrict__ pair_q,
-                                                        const uint64_t *__restrict__ pair_thr, int *__restrict__ thr1,
-                                                        int fold) {
-    __shared__ float s_min[4][64], s_rng[4][64];
-    __shared__ double s_scale[4];
-    __shared__ int s_bad[4], s_mode[4], s_dbase[4], s_drem[4];   // fold: 0 = quantise, 1 = all pass, 2 = none pass
-    const uint32_t quad = blockIdx.x, tid = threadIdx.x;
-    if (quad >= counters[CNT_TOTAL_QUADS]) return;
-    const float4 *src = reinterpret_cast<const float4 *>(lutq) + (size_t)quad * S * 16;
-    if (tid < 4) s_bad[tid] = 0;
-    __syncthreads();
-    const uint32_t p = tid & 3u, sub = tid >> 2;    // thread = (pair of the quad, subspace)
-    float v[16];
-    if (sub < S) {
-        float mn = __builtin_inff(), mx = -__builtin_inff();
-        bool bad = false;
-#pragma unroll
-        for (int c = 0; c < 16; ++c) {
-            const float4 e = src[sub * 16 + c];
-            const float x = p == 0 ? e.x : p == 1 ? e.y : p == 2 ? e.z : e.w;
-            v[c] = x;
-            bad = bad || !(x >= 0.0f) || !(x < __builtin_inff());   // NaN, negative, infinite
-            mn = fminf(mn, x);
-            mx = fmaxf(mx, x);
-        }
-        s_min[p][sub] = mn;
-        s_rng[p][sub] = mx - mn;
-        if (bad) atomicOr(&s_bad[p], 1);
-    }
-    __syncthreads();
-    if (tid < 4) {
-        double bias = 0.0;
-        float r = 0.0f;
-        for (uint32_t j = 0; j < S; ++j) {
-            bias += (double)s_min[tid][j];
-            r = fmaxf(r, s_rng[tid][j]);
-        }
-        double sc = (s_bad[tid] || !(r > 0.0f)) ? 0.0 : (double)r / 255.0;
-        const size_t slot = (size_t)quad * 4 + tid;
-        if (fold > 0) {
-            int mode = 1, dbase = 0, drem = 0;
-            const uint64_t T = pair_thr[slot];
-            if (pair_q[slot] == kInvalid) {
-                mode = 2;
-            } else if (T != SCANN_KEY_MAX && sc > 0.0) {
-                const double Tf = (double)ordered_to_f32((uint32_t)(T >> 32));
-                const double tq = Tf * (1.0 + (double)S * 1.1920928955078125e-07) - bias;
-                const double lim = 128.0 * (double)S - 1.0;
-                if (tq < 3.0e38) {   // (false for a NaN bound: everything passes)
-                    double qmax = floor(tq / sc + 0.5 * (double)S + 1.0);
-                    if (qmax > lim) {
-                        const double sc2 = tq / (lim - 0.5 * (double)S - 2.0) * (1.0 + 1e-12);
-                        sc = sc2 > sc ? sc2 : sc;
-                        qmax = floor(tq / sc + 0.5 * (double)S + 1.0);
-                    }
-                    if (qmax < 0.0) {
-                        mode = 2;
-                    } else if (qmax <= lim) {
-                        const int delta = (int)(lim - qmax);
-                        mode = 0;
-                        dbase = delta / (int)S;
-                        drem = delta % (int)S;
-                    }
-                }
-            }
-            s_mode[tid] = mode;
-            s_dbase[tid] = dbase;
-            s_drem[tid] = drem;
-            thr1[slot] = 0;
-        } else if (fold == 0) {
-            // (the pair's pass bound right away: the filter bounds are known by now -- one launch less)
-            thr1[slot] = mfma_pass_bound(S, pair_q[slot], pair_thr[slot], bias, sc);
-        }
-        // (fold < 0: nothing here -- the plain tables ahead of any bound; pair_thr and thr1 are not touched)
-        s_scale[tid] = sc;
-        Lut8Meta m;
-        m.bias_sum = bias;
-        m.scale = sc;
-        meta[slot] = m;
-    }
-    __syncthreads();
-    if (sub < S) {
-        const double sc = s_scale[p], mn = (double)s_min[p][sub];
-        uint32_t w[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-        for (int c = 0; c < 16; ++c) {
-            int q = 0;
-            if (sc > 0.0) {
-                const double t = ((double)v[c] - mn) / sc;
-                q = (int)floor(t + 0.5);
-                q = q < 0 ? 0 : (q > 255 ? 255 : q);
-            }
-            int e = q - 128;
-            if (fold > 0) {
-                const int mode = s_mode[p];
-                e += s_dbase[p] + ((int)sub < s_drem[p] ? 1 : 0);
-                e = mode == 1 ? -128 : mode == 2 ? 127 : (e > 127 ? 127 : e);
-            }
-            w[c >> 2] |= (uint32_t)(e & 0xFF) << (8 * (c & 3));
-        }
-        *reinterpret_cast<uint4 *>(lut8 + (((size_t)quad * 4 + p) * S + sub) * 16) = make_uint4(w[0], w[1], w[2], w[3]);
-    }
-}
-
-struct MfmaArgs {
-    const int *thr1;          // [slots] pass bound + 1 (lut8_build_kernel)
-    const uint32_t *pair_off, *tile_off, *pair_q, *pair_vbase;
-    uint32_t *counters;
-    const int8_t *lut8;
-    const Lut8Meta *meta;
-    const uint64_t *pair_thr;
-    uint32_t *cand32_cnt;     // [nq]
-    uint32_t *cand32;         // [nq][cap32] stream positions of the prefilter's survivors
-    uint32_t *cand32_codes;   // [nq][cap32][S/8] their packed codes: the refine reads them in list order
-    uint32_t cap32;
-    const uint64_t *allow;    // the search's allow-bitmap (or nullptr): disallowed survivors never enter the lists,
-    uint64_t allow_bits;      // so that the filter bounds them as it bounds the gather scan's (cap32 assumes it)
-};
-
-// The survivor mask `m` of a prefilter tile without its disallowed points: bit b of m stands for the point at leaf
-// position pos_of(b) (CSR row lb + pos_of(b)).  Walks the set bits only (a few per tile); callers take this branch
-// only when a bitmap is present, so an unfiltered scan runs none of it.
-template <typename F>
-__device__ __forceinline__ uint32_t mask_allowed(const TxhIndexDev &ix, const uint64_t *allow, uint64_t allow_bits,
-                                                 uint32_t lb, uint32_t m, F pos_of) {
-    uint32_t keep = 0;
-    while (m) {
-        const uint32_t b = (uint32_t)__ffs((int)m) - 1u;
-        m &= m - 1u;
-        if (row_allowed(ix, allow, allow_bits, lb + pos_of(b))) keep |= 1u << b;
-    }
-    return keep;
-}
-
-// Appends one prefilter survivor to query q's list: slot `dst` takes the stream position `pos` and, where the list
-// carries packed codes (cand32_codes: wave-uniform), the point's code words, read from its row `codes` of ix.codes.  A
-// slot past cap32 is dropped: the query's count still passes cap32, and adc_refine_kernel reports the overflow.
-template <int S>
-__device__ __forceinline__ void append_survivor(uint32_t *cand32, uint32_t *cand32_codes, uint32_t cap32, uint32_t q,
-                                                uint32_t dst, uint32_t pos, const uint32_t *codes) {
-    constexpr int NW = Codec<S, 4>::NWORDS;
-    if (dst < cap32) {
-        const size_t o = (size_t)q * cap32 + dst;
-        cand32[o] = pos;
-        if (cand32_codes) {
-            uint32_t cw[NW];
-            Codec<S, 4>::load_words(codes, cw);
-            Codec<S, 4>::store_words(cand32_codes + o * NW, cw);
-        }
-    }
-}
-// (The copy-outs of sp_flush_item_lanes / sp_flush_item_words write the same record from code words they loaded ahead,
-// kSpU points at a time, in the plane form of ix.codes_sp; they keep their own lines: through a shared helper
-// adc_smfmac_kernel<48, false> spilled two more VGPRs.)
-
-template <int S_>
-__global__ __launch_bounds__(kMfmaWaves * 64, (S_ <= 32 ? SCANN_MFMA_MINW : 2)) void adc_mfma_kernel(TxhIndexDev ix, MfmaArgs a) {
-    typedef int v4i __attribute__((ext_vector_type(4)));
-    typedef int v16i __attribute__((ext_vector_type(16)));
-    constexpr int S = S_, KS = S / 2, NW = S / 8;
-    __shared__ __attribute__((aligned(16))) uint32_t s_ident[64];                 // 16 one-hot rows of 16 bytes
-    __shared__ uint32_t s_stage[kMfmaWaves][32][kMfmaStage];
-    __shared__ uint32_t s_cnt[kMfmaWaves][32];
-    __shared__ uint32_t s_fpre[kMfmaWaves][32], s_fq[kMfmaWaves][32], s_fgb[kMfmaWaves][32], s_fvb[kMfmaWaves][32];   // flush: per pair
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    const uint32_t col = lane & 31u, h = lane >> 5;
-    // row c (16 bytes = words 4c .. 4c+3): byte c set to 1  ->  word 4c + (c >> 2) holds 1 << 8*(c & 3)
-    if (tid < 64) {
-        const uint32_t c = tid >> 2, wsel = tid & 3u;
-        s_ident[tid] = (wsel == (c >> 2)) ? (1u << (8 * (c & 3u))) : 0u;
-    }
-    __syncthreads();
-    const uint32_t total_tiles = a.counters[CNT_TOTAL_TILES];
-    const char *ident = reinterpret_cast<const char *>(s_ident);
-
-    uint32_t tile = 0;
-    if (lane == 0) tile = grab_tile(a.counters + CNT_XQ, total_tiles);
-    tile = __builtin_amdgcn_readfirstlane(tile);
-    while (tile != kInvalid) {
-        // the next item's queue atomic travels while this item is computed
-        uint32_t next_tile = 0;
-        if (lane == 0) next_tile = grab_tile(a.counters + CNT_XQ, total_tiles);
-        const WorkItem item = decode_item(ix, a.tile_off, a.pair_off, tile);
-        const uint32_t lb = item.lb, size = item.size, local = item.local, slot0 = item.slot0, slot_end = item.slot_end;
-        const uint32_t nranges = (size + kMfmaRange - 1) / kMfmaRange;
-        const uint32_t range = local % nranges, pt = local / nranges;
-        const uint32_t c0 = range * kMfmaRange;
-        const uint32_t npts = min(kMfmaRange, size - c0);
-
-        // this lane's pair (column): tables, bound, key base
-        const uint32_t slot = slot0 + pt * 32u + col;
-        const bool pair_ok = slot < slot_end;
-        const uint32_t pq = pair_ok ? a.pair_q[slot] : kInvalid;
-        const uint32_t vb = pair_ok ? a.pair_vbase[slot] : 0u;
-        v4i b[KS];
-        {
-            const int8_t *bsrc = a.lut8 + ((size_t)(pair_ok ? slot : slot0) * S + h) * 16;   // padding columns: any table
-#pragma unroll
-            for (int t = 0; t < KS; ++t) b[t] = *reinterpret_cast<const v4i *>(bsrc + (size_t)t * 32);
-        }
-        const int thr1 = pair_ok ? a.thr1[slot] : -(128 * S + 7);   // a point passes iff acc - thr1 < 0
-        if (lane < 32) s_cnt[wave][lane] = 0;
-        // (s_cnt / s_stage are private to the wave: no workgroup barrier anywhere in this loop)
-
-        const uint32_t ntile = (npts + 31u) >> 5;
-        uint32_t wn[NW];
-        {
-            const uint32_t j = c0 + col;
-            Codec<S, 4>::load_words(ix.codes + (size_t)(lb + (j < size ? j : 0u)) * NW, wn);
-        }
-        // Software pipeline over the item's tiles, two accumulators: step(t) issues the MFMA chain of tile
-        // t and, between its MFMAs (their shadow hides ~6 vector instructions each), builds the survivor
-        // mask of tile t - 1 from the other accumulator; then the (rare, branchy) survivor staging of
-        // tile t - 1.  One extra step drains the last tile (its MFMAs run on stale codes and are dropped).
-        // Staged survivors -> the queries' lists: ONE returning atomic per flushed pair (all of them in one
-        // wave instruction), then one contiguous segment per pair.  all = false flushes only the pairs
-        // whose stage could overflow in the next tile (a tile adds at most 32 per pair): dense pairs --
-        // the nearest leaves of a query, where a large share of the points pass -- flush often, sparse
-        // ones once per item.
-        auto flush = [&](bool all) {
-            uint32_t n = 0, gbase = 0;
-            if (lane < 32) {
-                n = min(s_cnt[wave][lane], kMfmaStage);
-                if (!all && n + 32u <= kMfmaStage) n = 0;
-                if (n) {
-                    gbase = atomicAdd(&a.cand32_cnt[pq], n);
-                    s_cnt[wave][lane] = 0;
-                }
-            }
-            // all flushed pairs as ONE list spread over the 64 lanes: entry e belongs to the pair c with
-            // pre[c] <= e < pre[c] + n[c]; its position and its packed codes (the tile's lines are still in
-            // L2) go to slot gbase[c] + (e - pre[c]) of the query's list
-            uint32_t incl = n;
-#pragma unroll
-            for (int o = 1; o < 32; o <<= 1) {
-                const uint32_t up = (uint32_t)__shfl_up((int)incl, o);
-                if ((int)lane >= o) incl += up;
-            }
-            const uint32_t total = (uint32_t)__shfl((int)incl, 31);
-            if (total == 0) return;
-            if (lane < 32) {
-                s_fpre[wave][lane] = incl - n;
-                s_fq[wave][lane] = pq == kInvalid ? 0u : pq;
-                s_fgb[wave][lane] = gbase;
-                s_fvb[wave][lane] = vb;
-            }
-            // (per-pair values through LDS, not shuffles: the loop's last pass runs with lanes switched off)
-            for (uint32_t e = lane; e < total; e += 64u) {
-                uint32_t c = 0;
-#pragma unroll
-                for (uint32_t stp = 16; stp; stp >>= 1)
-                    if (s_fpre[wave][c + stp] <= e) c += stp;
-                const uint32_t idx = e - s_fpre[wave][c];
-                const uint32_t j = s_stage[wave][c][idx];
-                const uint32_t dst = s_fgb[wave][c] + idx;
-                append_survivor<S>(a.cand32, a.cand32_codes, a.cap32, s_fq[wave][c], dst, s_fvb[wave][c] + j, ix.codes + (size_t)(lb + j) * NW);
-            }
-        };
-        auto step = [&](v16i &accN, const v16i &accO, uint32_t t) {
-            // nibbles of this lane's subspace parity h, pre-shifted to byte offsets code * 16
-            uint32_t rg[NW];
-#pragma unroll
-            for (int wi = 0; wi < NW; ++wi) rg[wi] = h ? (wn[wi] & 0xF0F0F0F0u) : ((wn[wi] & 0x0F0F0F0Fu) << 4);
-            if (t + 1 < ntile) {
-                const uint32_t j = c0 + (t + 1) * 32u + col;
-                Codec<S, 4>::load_words(ix.codes + (size_t)(lb + (j < size ? j : 0u)) * NW, wn);
-            }
-            accN = v16i{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-            // A fragments: kMfmaDepth one-hot rows in flight ahead of the MFMA that consumes them
-            constexpr int D = kMfmaDepth < KS ? kMfmaDepth : KS;
-            v4i av[D + 1];
-            auto onehot = [&](int kt) {
-                const uint32_t off = (rg[kt >> 2] >> (8 * (kt & 3))) & 0xFFu;   // code * 16 of subspace 2 kt + h
-                return *reinterpret_cast<const v4i *>(ident + off);
-            };
-#pragma unroll
-            for (int kt = 0; kt < D; ++kt) av[kt] = onehot(kt);
-            // lane (col, h), register r: point row (r & 3) + 8 * (r >> 2) + 4 * h of the tile.  Survivor
-            // bits of the lane's 16 results without a branch per result (a tile holds ~10 survivors among
-            // 1024 results): v_sub + v_alignbit shift the sign of acc - thr1 into the mask, so result r
-            // ends up at bit 15 - r.
-            uint32_t m16 = 0;
-            // the MFMA chain issues ahead of the other waves' staging / flush streams (s_setprio: -2 % kernel time)
-            __builtin_amdgcn_s_setprio(2);
-#pragma unroll
-            for (int kt = 0; kt < KS; ++kt) {
-                if (kt + D < KS) av[(kt + D) % (D + 1)] = onehot(kt + D);
-                accN = __builtin_amdgcn_mfma_i32_32x32x32_i8(av[kt % (D + 1)], b[kt], accN, 0, 0, 0);
-#pragma unroll
-                for (int r = kt * 16 / KS; r < (kt + 1) * 16 / KS; ++r)
-                    m16 = __builtin_amdgcn_alignbit(m16, (uint32_t)(accO[r] - thr1), 31);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            __builtin_amdgcn_s_setprio(0);
-            if (t == 0) return;                // nothing before the first tile (wave-uniform)
-            const uint32_t base = c0 + (t - 1) * 32u + 4u * h;
-            if (t == ntile && (npts & 31u)) {  // partial last tile: rows past the leaf's end are padding
-                uint32_t okm = 0;
-#pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    okm |= (base + (uint32_t)((r & 3) + 8 * (r >> 2)) < size ? 1u : 0u) << (15 - r);
-                m16 &= okm;
-            }
-            if (a.allow && m16)                // search_with_filter: disallowed points are not survivors
-                m16 = mask_allowed(ix, a.allow, a.allow_bits, lb, m16, [&](uint32_t b) {
-                    const uint32_t r = 15u - b;
-                    return base + (r & 3u) + ((r >> 2) << 3);
-                });
-            bool risk = false;                 // this lane's pair could overflow its stage in the next tile
-            if (m16) {
-                uint32_t sl = atomicAdd(&s_cnt[wave][col], (uint32_t)__popc(m16));   // one LDS atomic per lane
-                do {
-                    const uint32_t r = 15u - ((uint32_t)__ffs((int)m16) - 1u);
-                    m16 &= m16 - 1u;
-                    const uint32_t j = base + (r & 3u) + ((r >> 2) << 3);
-                    if (sl < kMfmaStage) {
-                        s_stage[wave][col][sl] = j;
-                    } else {   // stage full: direct (slow) append
-                        const uint32_t pos = atomicAdd(&a.cand32_cnt[pq], 1u);
-                        append_survivor<S>(a.cand32, a.cand32_codes, a.cap32, pq, pos, vb + j, ix.codes + (size_t)(lb + j) * NW);
-                    }
-                    ++sl;
-                } while (m16);
-                risk = sl + 32u > kMfmaStage;   // (the lane that appended last to a pair saw its full count)
-            }
-            if (__any(risk)) flush(false);
-        };
-        // (tile 0 is peeled: inside the loop t >= 1 is known, so the compiler keeps the mask build between
-        // the MFMAs in BOTH instances instead of sinking it below a `t == 0` branch)
-        v16i accA = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, accB = accA;
-        step(accA, accB, 0u);
-        for (uint32_t tl = 1; tl <= ntile; tl += 2) {
-            step(accB, accA, tl);
-            if (tl + 1 <= ntile) step(accA, accB, tl + 1);
-        }
-        flush(true);
-        tile = __builtin_amdgcn_readfirstlane(next_tile);
-    }
-}
-
-// =====================================================================================
-// K6e: the 32-pair prefilter on the 2:4 STRUCTURED-SPARSE MFMA (v_smfmac_i32_32x32x64_i8).
-//
-// A one-hot row has one non-zero per 16 K-elements, so it satisfies 2:4 sparsity by construction: the
-// sparse instruction multiplies a COMPRESSED A (two values per group of four K-elements + a 2-bit position
-// each) with a dense 64-deep B in the time the dense instruction takes for K = 32 -- four subspaces per MFMA
-// slot instead of two (tools/micro/smfmac_probe.hip: 21.5-26 ns against 19.4-25 ns per instruction per SIMD).
-// Operand layout (probed on the hardware, same tool): A lane (m, ha) holds row m; its compressed byte b (value slot
-// b & 1 of group (b >> 1) & 3 of half b >> 3) with position i multiplies B lane (n, hb = b >> 3), byte 16 ha + 4
-// ((b >> 1) & 3) + i; the selection is a plain mux (equal or descending positions of a group's two values work).
-// Sparse MFMA kt therefore covers subspaces s0 .. s0 + 3 (s0 = 4 + 4 kt): B lane (n, hb) = the 32 table bytes of
-// subspaces s0 + 2 hb, s0 + 2 hb + 1 of pair n (contiguous in lut8), A lane (m, ha) = the codes ca = code[s0 + ha]
-// (bytes 0..7) and cb = code[s0 + 2 + ha] (bytes 8..15) of point m: value 1 at byte 2 (ca >> 2) / 8 + 2 (cb >> 2),
-// positions (ca & 3) / (cb & 3) replicated over the half's four groups (the other groups hold zeros).
-//
-// The sparse instruction accumulates in place (no C operand), so a tile starts with two DENSE MFMAs (subspaces 0..3,
-// C = the inline constant 0: no accumulator clearing on the vector pipe) followed by (S - 4) / 4 sparse ones: 9 MFMA
-// slots per 32 x 32 tile at S = 32 instead of 16.  Both A operands come from 16-row LDS tables (conflict-free
-// ds_read_b128 / ds_read_b32: lanes with equal rows broadcast); their row numbers are precomputed per point at index
-// creation as two nibble PLANES (codes_sp: V = (ca >> 2) | (cb >> 2) << 2 picks the value row, N = (ca & 3) |
-// (cb & 3) << 2 the position word; the last nibble of each plane is the raw code of dense MFMA 0 / 1), so a tile
-// costs 7 unpack instructions + 2 byte extractions per sparse MFMA.  The pass bound lives in the tables
-// (lut8_build_kernel, fold): a point passes iff its sum is negative -- one v_alignbit per result.
-// Items, survivor staging, flush and lists as in adc_mfma_kernel; candidate lists identical (the refine is exact).
-// =====================================================================================
-#ifndef SCANN_SP_STAGE
-#define SCANN_SP_STAGE 512
-#endif
-constexpr uint32_t kSpStage = SCANN_SP_STAGE;   // adc_smfmac_kernel: list entries staged per flush round (per wave)
-#ifndef SCANN_SP_U
-#define SCANN_SP_U 8
-#endif
-constexpr uint32_t kSpU = SCANN_SP_U;         // ... and code rows in flight per lane in the copy phase
-
-template <int S_>
-struct SpLayout {
-    static constexpr int NS = (S_ - 4) / 4;      // sparse MFMAs per tile
-    static constexpr int NIB = NS + 1;           // nibbles per plane (the last one: a dense MFMA's raw code)
-    static constexpr int NWP = (NIB + 7) / 8;    // words per plane
-    static constexpr int SPW = 4 * NWP;          // words per point: [ha][plane V, N][word]
-};
-
-__global__ __launch_bounds__(256) void codes_sp_build_kernel(const uint32_t *__restrict__ codes, uint64_t n, uint32_t S,
-                                                            uint32_t *__restrict__ out) {
-    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t nw = S / 8, ns = (S - 4) / 4, nwp = (ns + 1 + 7) / 8;
-    const uint32_t *w = codes + i * nw;
-    auto code = [&](uint32_t sub) { return (w[sub >> 3] >> (4 * (sub & 7u))) & 15u; };
-    uint32_t *o = out + i * 4 * nwp;
-    for (uint32_t ha = 0; ha < 2; ++ha)
-        for (uint32_t wi = 0; wi < nwp; ++wi) {
-            uint32_t v = 0, nn = 0;
-            for (uint32_t j = 8 * wi; j < 8 * wi + 8 && j <= ns; ++j) {
-                uint32_t vn, nb;
-                if (j < ns) {
-                    const uint32_t ca = code(4 + 4 * j + ha), cb = code(4 + 4 * j + 2 + ha);
-                    vn = (ca >> 2) | ((cb >> 2) << 2);
-                    nb = (ca & 3u) | ((cb & 3u) << 2);
-                } else {   // dense MFMA 0 scores subspace ha, dense MFMA 1 subspace 2 + ha
-                    vn = code(ha);
-                    nb = code(2 + ha);
-                }
-                v |= vn << (4 * (j & 7u));
-                nn |= nb << (4 * (j & 7u));
-            }
-            o[(ha * 2 + 0) * nwp + wi] = v;
-            o[(ha * 2 + 1) * nwp + wi] = nn;
-        }
-}
-
-// inclusive prefix sum over the 64 lanes of a wave: DPP row shifts inside the 16-lane rows, then the row broadcasts
-// (six v_add with a DPP operand; no LDS round trips)
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false);   // row_shr:1
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false);   // row_shr:2
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false);   // row_shr:4
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false);   // row_shr:8
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);   // row_bcast:15 into rows 1, 3
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false);   // row_bcast:31 into rows 2, 3
-    return v;
-}
-
-// search_with_filter in the sparse prefilter: lane (col, h) drops the disallowed points from its own words of the item's
-// survivor bitmap (words[tt * 64], tt < ntt; see adc_smfmac_body: word [tt][h][col] = the masks of tiles 2 tt (low half)
-// and 2 tt + 1, result r of a tile -- point row (r & 3) + 8 (r >> 2) + 4 h -- at bit 15 - r), before the flush counts
-// them.  Called at the top of the flushes, where the tile loop's registers are dead, and only when a bitmap is present.
-__device__ __forceinline__ void sp_filter_words(const TxhIndexDev &ix, const uint64_t *allow, uint64_t allow_bits,
-                                                uint32_t *words, uint32_t ntt, uint32_t c0, uint32_t lb, uint32_t h) {
-    for (uint32_t tt = 0; tt < ntt; ++tt) {
-        const uint32_t wd = words[tt * 64u];
-        if (wd)
-            words[tt * 64u] = mask_allowed(ix, allow, allow_bits, lb, wd, [&](uint32_t b) {
-                const uint32_t r = 15u - (b & 15u);
-                return c0 + (2u * tt + (b >> 4)) * 32u + 4u * h + (r & 3u) + ((r >> 2) << 3);
-            });
-    }
-    __builtin_amdgcn_wave_barrier();   // (the word-parallel flush reads the other lanes' words)
-}
-
-#ifndef SCANN_SP_FLUSH_INLINE
-#define SCANN_SP_FLUSH_INLINE __forceinline__
-#endif
-// The flush for FLAT hashers (one leaf, every pair sparse: ~0.4 survivors per bitmap word at C3): lane (col, h) keeps
-// its own 32 words in registers and walks their bits itself, in rounds of kSpStage staged entries; the copy-out is the
-// same as in sp_flush_item_words.  No per-pair round trip through LDS and the wave scan: 0.35 ms at C3 against
-// 0.44 ms for the word-parallel form -- which wins wherever pairs are dense (tree indexes: 10M x 128, P = 25, m = 1000:
-// scan 0.27 ms against 0.71 ms), because a lane walking its own survivors takes them one by one.
-template <int S>
-__device__ SCANN_SP_FLUSH_INLINE void sp_flush_item_lanes(const uint32_t *__restrict__ codes_sp, const TxhIndexDev &ix,
-                                                        const uint64_t *allow, uint64_t allow_bits, uint32_t *__restrict__ cand32_cnt,
-                                                        uint32_t *__restrict__ cand32, uint32_t *__restrict__ cand32_codes,
-                                                        uint32_t cap32, uint32_t *bits, uint2 *stage, uint32_t *s_fq,
-                                                        uint32_t *s_fvb, uint32_t *s_fgb, uint32_t ntile, uint32_t c0,
-                                                        uint32_t lb, uint32_t pq, uint32_t vb) {
-    constexpr int SPW = SpLayout<S>::SPW;
-    constexpr int TTM = (int)(kMfmaRange / 64);
-    const uint32_t lane = threadIdx.x & 63u, col = lane & 31u, h = lane >> 5;
-    const uint32_t ntt = (ntile + 1u) >> 1;
-    if (allow) sp_filter_words(ix, allow, allow_bits, bits, ntt, c0, lb, h);
-    uint32_t w[TTM];
-    uint32_t cnt = 0;
-#pragma unroll
-    for (int tt = 0; tt < TTM; ++tt) {
-        w[tt] = (uint32_t)tt < ntt ? bits[tt * 64] : 0u;
-        cnt += (uint32_t)__popc(w[tt]);
-    }
-    const uint32_t other = (uint32_t)__shfl_xor((int)cnt, 32);
-    const uint32_t n_pair = cnt + other;
-    uint32_t incl = n_pair;   // prefix over the pairs, computed alike in both halves of the wave
-#pragma unroll
-    for (int o = 1; o < 32; o <<= 1) {
-        const uint32_t up = (uint32_t)__shfl_up((int)incl, o, 32);
-        if ((int)col >= o) incl += up;
-    }
-    const uint32_t total = (uint32_t)__shfl((int)incl, 31, 32);
-    if (total == 0) return;
-    uint32_t gbase = 0;
-    if (h == 0 && n_pair) gbase = atomicAdd(&cand32_cnt[pq], n_pair);   // (padding pairs have no bits)
-    if (lane < 32) {
-        s_fq[lane] = pq == kInvalid ? 0u : pq;
-        s_fvb[lane] = vb;
-    }
-    uint32_t sq = incl - n_pair + (h ? other : 0u);   // this lane's first entry in the wave's staging order
-    uint32_t rel = h ? other : 0u;                    // ... and its position in the pair's segment
-    for (uint32_t base = 0; base < total; base += kSpStage) {
-        const uint32_t lim = base + kSpStage;
-#pragma unroll
-        for (int tt = 0; tt < TTM; ++tt) {
-            while (w[tt] && sq < lim) {
-                const uint32_t bpos = (uint32_t)__ffs((int)w[tt]) - 1u;
-                w[tt] &= w[tt] - 1u;
-                const uint32_t r = 15u - (bpos & 15u);
-                const uint32_t jrel = (2u * (uint32_t)tt + (bpos >> 4)) * 32u + 4u * h + (r & 3u) + ((r >> 2) << 3);
-                stage[sq - base] = make_uint2(rel, (col << 16) | jrel);
-                ++sq;
-                ++rel;
-            }
-        }
-        if (base == 0 && lane < 32) s_fgb[lane] = gbase;   // (the atomics have travelled under the walk)
-        __builtin_amdgcn_wave_barrier();
-        const uint32_t n = min(kSpStage, total - base);
-        for (uint32_t e0 = 0; e0 < n; e0 += 64u * kSpU) {
-            uint2 ent[kSpU];
-            uint4 cw[kSpU][SPW / 4];
-#pragma unroll
-            for (int u = 0; u < (int)kSpU; ++u) {
-                const uint32_t e = e0 + lane + 64u * (uint32_t)u;
-                ent[u] = e < n ? stage[e] : make_uint2(0xFFFFFFFFu, 0u);
-            }
-            if (cand32_codes) {   // (wave-uniform)
-#pragma unroll
-                for (int u = 0; u < (int)kSpU; ++u)
-#pragma unroll
-                    for (int x = 0; x < SPW / 4; ++x)
-                        cw[u][x] = reinterpret_cast<const uint4 *>(codes_sp + (size_t)(lb + c0 + (ent[u].y & 0xFFFFu)) * SPW)[x];
-            } else {   // (defined on every path: a conditionally initialised array stays in scratch memory -- 16 scratch
-                       // round trips per copy-out, 0.41 instead of 0.35 ms at C3)
-#pragma unroll
-                for (int u = 0; u < (int)kSpU; ++u)
-#pragma unroll
-                    for (int x = 0; x < SPW / 4; ++x) cw[u][x] = make_uint4(0u, 0u, 0u, 0u);
-            }
-#pragma unroll
-            for (int u = 0; u < (int)kSpU; ++u) {
-                if (ent[u].x != 0xFFFFFFFFu) {
-                    const uint32_t c = ent[u].y >> 16;
-                    const uint32_t dst = s_fgb[c] + ent[u].x;
-                    if (dst < cap32) {
-                        const size_t o = (size_t)s_fq[c] * cap32 + dst;
-                        cand32[o] = s_fvb[c] + c0 + (ent[u].y & 0xFFFFu);
-                        if (cand32_codes) {
-#pragma unroll
-                            for (int x = 0; x < SPW / 4; ++x) reinterpret_cast<uint4 *>(cand32_codes + o * SPW)[x] = cw[u][x];
-                        }
-                    }
-                }
-            }
-        }
-        __builtin_amdgcn_wave_barrier();
-    }
-}
-
-// The flush of adc_smfmac_kernel: the item's survivor bitmap -> the queries' lists.  The tile loop left word
-// [tt][h][col] = the masks of tiles 2 tt, 2 tt + 1 of lane (col, h).
-//   1. every lane counts the bits of its own words; the two lanes of a pair share ONE returning atomic for the pair's
-//      segment of the query's list (issued now, consumed in step 3);
-//   2. pair by pair, the 64 lanes take the pair's 64 words ONE WORD EACH: a DPP prefix sum gives every word its offset
-//      in the segment, and each lane stages (offset, pair, point) of its word's bits in LDS.  A pair whose every point
-//      passes (a query's nearest leaf in a tree index) costs 32 rounds here, not the 2048 a lane walking its own
-//      survivors one by one would need; a sparse pair (0.2 bits per word on a flat 1M index) costs two;
-//   3. whenever the stage is full (kSpStage entries) or the pairs are done, the 64 lanes copy the staged entries to the
-//      lists side by side, each with up to kSpU row loads in flight.  What travels with a position (flat hashers) is
-//      the point's PLANE row (codes_sp: the lines the tile loop has just read, still in L2 -- the packed codes were
-//      last touched at index creation); adc_refine_kernel decodes it (RefineArgs::planes).
-template <int S>
-__device__ SCANN_SP_FLUSH_INLINE void sp_flush_item_words(const uint32_t *__restrict__ codes_sp, const TxhIndexDev &ix,
-                                                        const uint64_t *allow, uint64_t allow_bits, uint32_t *__restrict__ cand32_cnt,
-                                                        uint32_t *__restrict__ cand32, uint32_t *__restrict__ cand32_codes,
-                                                        uint32_t cap32, uint32_t *bits_w, uint2 *stage, uint32_t *s_fq,
-                                                        uint32_t *s_fvb, uint32_t *s_fgb, uint32_t ntile, uint32_t c0,
-                                                        uint32_t lb, uint32_t pq, uint32_t vb) {
-    constexpr int SPW = SpLayout<S>::SPW;
-    constexpr int TTM = (int)(kMfmaRange / 64);
-    static_assert(TTM == 32, "the flush maps the 64 words of a pair onto the 64 lanes");
-    const uint32_t lane = threadIdx.x & 63u, h = lane >> 5;
-    const uint32_t ntt = (ntile + 1u) >> 1;
-    if (allow) sp_filter_words(ix, allow, allow_bits, bits_w + lane, ntt, c0, lb, h);
-    uint32_t cnt = 0;
-#pragma unroll
-    for (int tt = 0; tt < TTM; ++tt) cnt += (uint32_t)tt < ntt ? (uint32_t)__popc(bits_w[tt * 64 + lane]) : 0u;
-    const uint32_t n_pair = cnt + (uint32_t)__shfl_xor((int)cnt, 32);   // (the same in both lanes of a pair)
-    if (!__any(n_pair != 0)) return;
-    uint32_t gbase = 0;
-    if (h == 0 && n_pair) gbase = atomicAdd(&cand32_cnt[pq], n_pair);   // (padding pairs have no bits)
-    if (lane < 32) {
-        s_fq[lane] = pq == kInvalid ? 0u : pq;
-        s_fvb[lane] = vb;
-    }
-    bool fgb_done = false;
-    // step 3: stage[0 .. n) -> the lists
-    auto copy_out = [&](uint32_t n) {
-        if (!fgb_done) {   // (wave-uniform; the atomics have travelled under the first pairs' staging)
-            if (lane < 32) s_fgb[lane] = gbase;
-            fgb_done = true;
-        }
-        __builtin_amdgcn_wave_barrier();
-        for (uint32_t e0 = 0; e0 < n; e0 += 64u * kSpU) {
-            uint2 ent[kSpU];
-            uint4 cw[kSpU][SPW / 4];
-#pragma unroll
-            for (int u = 0; u < (int)kSpU; ++u) {
-                const uint32_t e = e0 + lane + 64u * (uint32_t)u;
-                ent[u] = e < n ? stage[e] : make_uint2(0xFFFFFFFFu, 0u);
-            }
-            if (cand32_codes) {   // (wave-uniform)
-#pragma unroll
-                for (int u = 0; u < (int)kSpU; ++u)
-#pragma unroll
-                    for (int x = 0; x < SPW / 4; ++x)
-                        cw[u][x] = reinterpret_cast<const uint4 *>(codes_sp + (size_t)(lb + c0 + (ent[u].y & 0xFFFFu)) * SPW)[x];
-            } else {   // (defined on every path: a conditionally initialised array stays in scratch memory -- 16 scratch
-                       // round trips per copy-out, 0.41 instead of 0.35 ms at C3)
-#pragma unroll
-                for (int u = 0; u < (int)kSpU; ++u)
-#pragma unroll
-                    for (int x = 0; x < SPW / 4; ++x) cw[u][x] = make_uint4(0u, 0u, 0u, 0u);
-            }
-#pragma unroll
-            for (int u = 0; u < (int)kSpU; ++u) {
-                if (ent[u].x != 0xFFFFFFFFu) {
-                    const uint32_t c = ent[u].y >> 16;
-                    const uint32_t dst = s_fgb[c] + ent[u].x;
-                    if (dst < cap32) {
-                        const size_t o = (size_t)s_fq[c] * cap32 + dst;
-                        cand32[o] = s_fvb[c] + c0 + (ent[u].y & 0xFFFFu);
-                        if (cand32_codes) {
-#pragma unroll
-                            for (int x = 0; x < SPW / 4; ++x) reinterpret_cast<uint4 *>(cand32_codes + o * SPW)[x] = cw[u][x];
-                        }
-                    }
-                }
-            }
-        }
-        __builtin_amdgcn_wave_barrier();
-    };
-    // step 2: lane = word (tt, hh) of the current pair
-    const uint32_t tt = lane & 31u, hh = lane >> 5;
-    const uint32_t woff = tt * 64u + hh * 32u;
-    const bool wok = tt < ntt;
-    auto jrel_of = [&](uint32_t bpos) {
-        const uint32_t r = 15u - (bpos & 15u);
-        return (2u * tt + (bpos >> 4)) * 32u + 4u * hh + (r & 3u) + ((r >> 2) << 3);
-    };
-    // (one copy_out site: the stage is filled with as many pairs -- or as much of a dense pair -- as fit, then copied)
-    uint32_t c = 0, r0 = 0;   // current pair; entries of it already copied out (a dense pair spans several rounds)
-    for (;;) {
-        uint32_t fill = 0;
-        while (c < 32u) {
-            const uint32_t n_c = (uint32_t)__builtin_amdgcn_readlane((int)n_pair, (int)c);
-            if (n_c == 0) {   // (wave-uniform)
-                ++c;
-                continue;
-            }
-            const uint32_t rem = n_c - r0;
-            if (fill && fill + min(rem, kSpStage) > kSpStage) break;   // no room: copy out first
-            const uint32_t take = min(rem, kSpStage - fill);           // entries [r0, r0 + take) of the pair's segment
-            const uint32_t w = wok ? bits_w[woff + c] : 0u;
-            const uint32_t p = (uint32_t)__popc(w);
-            uint32_t x = w, i = wave_incl_scan(p) - p;
-            while (x) {
-                const uint32_t bpos = (uint32_t)__ffs((int)x) - 1u;
-                x &= x - 1u;
-                if (i - r0 < take) stage[fill + i - r0] = make_uint2(i, (c << 16) | jrel_of(bpos));
-                ++i;
-            }
-            fill += take;
-            r0 += take;
-            if (r0 < n_c) break;   // a dense pair: the rest after this copy-out
-            ++c;
-            r0 = 0;
-        }
-        if (!fill) break;
-        copy_out(fill);
-    }
-}
-
-template <int S_, bool WORDS>   // WORDS: the word-parallel flush (tree indexes); else lanes walk their own words (flat)
-__device__ __forceinline__ void adc_smfmac_body(const TxhIndexDev &ix, const MfmaArgs &a) {
-    typedef int v4i __attribute__((ext_vector_type(4)));
-    typedef int v8i __attribute__((ext_vector_type(8)));
-    typedef int v16i __attribute__((ext_vector_type(16)));
-    typedef SpLayout<S_> SP;
-    constexpr int S = S_, NS = SP::NS, KT = NS + 2, NWP = SP::NWP, SPW = SP::SPW;
-    constexpr int D = kMfmaDepth < KT ? kMfmaDepth : KT;      // operands in flight ahead of the MFMA that consumes them
-    constexpr uint32_t kTT = kMfmaRange / 64;                   // tile pairs per item
-    __shared__ __attribute__((aligned(16))) uint32_t s_ident[64];   // dense A: 16 one-hot rows of 16 bytes
-    __shared__ __attribute__((aligned(16))) uint32_t s_vtab[64];    // sparse A values: row V = (ga | gb << 2)
-    __shared__ uint32_t s_ntab[16];                                 // sparse A positions: word N = (ia | ib << 2)
-    // survivor bitmap of the wave's item: word [tt][h][col] = the 16-bit masks of tiles 2 tt (low half) and 2 tt + 1 of
-    // lane (col, h).  Written once per two tiles with one conflict-free ds_write_b32; no atomics, no branches and no
-    // waits in the tile loop -- the item's flush turns it into list entries.
-    __shared__ uint32_t s_bits[kMfmaWaves][kTT][64];
-    __shared__ uint2 s_stage[kMfmaWaves][kSpStage];                                  // flush: staged list entries
-    __shared__ uint32_t s_fq[kMfmaWaves][32], s_fvb[kMfmaWaves][32], s_fgb[kMfmaWaves][32];   // flush: per pair
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    const uint32_t col = lane & 31u, h = lane >> 5;
-    if (tid < 64) {
-        const uint32_t c = tid >> 2, wsel = tid & 3u;
-        s_ident[tid] = (wsel == (c >> 2)) ? (1u << (8 * (c & 3u))) : 0u;
-        // row V, word wsel: words 0, 1 = bytes 0..7 (group ga = V & 3: value 1 at byte 2 ga), words 2, 3 = bytes 8..15 (gb = V >> 2)
-        const uint32_t g = wsel < 2 ? (c & 3u) : (c >> 2);
-        s_vtab[tid] = ((g >> 1) == (wsel & 1u)) ? (1u << (16 * (g & 1u))) : 0u;
-        if (tid < 16) s_ntab[tid] = (tid & 3u) * 0x1111u | (tid >> 2) * 0x11110000u;
-    }
-    __syncthreads();
-    const uint32_t total_tiles = a.counters[CNT_TOTAL_TILES];
-    const char *ident = reinterpret_cast<const char *>(s_ident);
-    const char *vtab = reinterpret_cast<const char *>(s_vtab);
-    const char *ntab = reinterpret_cast<const char *>(s_ntab);
-    uint32_t *bits = &s_bits[wave][0][lane];
-
-    struct Planes {   // one tile's operand planes as LDS byte offsets (see step)
-        uint32_t ve[NWP], vo[NWP], ne[NWP], no[NWP], d1;
-    };
-    struct Ops {      // the first D operands of a tile, fetched during the previous tile's MFMA chain
-        v4i av[D];
-        int iv[D];
-    };
-
-    uint32_t tile = 0;
-    if (lane == 0) tile = grab_tile(a.counters + CNT_XQ, total_tiles);
-    tile = __builtin_amdgcn_readfirstlane(tile);
-    while (tile != kInvalid) {
-        uint32_t next_tile = 0;
-        if (lane == 0) next_tile = grab_tile(a.counters + CNT_XQ, total_tiles);
-        const WorkItem item = decode_item(ix, a.tile_off, a.pair_off, tile);
-        const uint32_t lb = item.lb, size = item.size, local = item.local, slot0 = item.slot0, slot_end = item.slot_end;
-        const uint32_t nranges = (size + kMfmaRange - 1) / kMfmaRange;
-        const uint32_t range = local % nranges, pt = local / nranges;
-        const uint32_t c0 = range * kMfmaRange;
-        const uint32_t npts = min(kMfmaRange, size - c0);
-
-        // this lane's pair (column): tables (the pass bound is folded into them), key base
-        const uint32_t slot = slot0 + pt * 32u + col;
-        const bool pair_ok = slot < slot_end;
-        const uint32_t pq = pair_ok ? a.pair_q[slot] : kInvalid;
-        const uint32_t vb = pair_ok ? a.pair_vbase[slot] : 0u;
-        v4i bd[2];
-        v8i bs[NS];
-        {
-            const int8_t *bsrc = a.lut8 + (size_t)(pair_ok ? slot : slot0) * S * 16;
-#pragma unroll
-            for (int d = 0; d < 2; ++d) bd[d] = *reinterpret_cast<const v4i *>(bsrc + (size_t)(2 * d + h) * 16);
-#pragma unroll
-            for (int kt = 0; kt < NS; ++kt) {
-                const v4i x0 = *reinterpret_cast<const v4i *>(bsrc + (size_t)(4 + 4 * kt + 2 * h) * 16);
-                const v4i x1 = *reinterpret_cast<const v4i *>(bsrc + (size_t)(4 + 4 * kt + 2 * h) * 16 + 16);
-                bs[kt] = v8i{x0[0], x0[1], x0[2], x0[3], x1[0], x1[1], x1[2], x1[3]};
-            }
-            if (!pair_ok) {   // padding columns: every entry 127, sums stay positive (nothing passes)
-                const int k7 = 0x7F7F7F7F;
-#pragma unroll
-                for (int d = 0; d < 2; ++d) bd[d] = v4i{k7, k7, k7, k7};
-#pragma unroll
-                for (int kt = 0; kt < NS; ++kt) bs[kt] = v8i{k7, k7, k7, k7, k7, k7, k7, k7};
-            }
-        }
-
-        const uint32_t ntile = (npts + 31u) >> 5;
-        static_assert(NWP == 1 || NWP == 2, "plane words");
-        struct Raw {
-            uint32_t wv[NWP], wn[NWP];
-        };
-        auto load_planes = [&](uint32_t t) {   // raw planes of tile t (rows past the leaf's end: any row, masked later)
-            const uint32_t j = c0 + t * 32u + col;
-            const uint32_t *src = ix.codes_sp + (size_t)(lb + (j < size ? j : 0u)) * SPW + h * 2u * NWP;
-            Raw r;
-            if constexpr (NWP == 1) {
-                const uint2 v = *reinterpret_cast<const uint2 *>(src);
-                r.wv[0] = v.x; r.wn[0] = v.y;
-            } else {
-                const uint4 v = *reinterpret_cast<const uint4 *>(src);
-                r.wv[0] = v.x; r.wv[1] = v.y; r.wn[0] = v.z; r.wn[1] = v.w;
-            }
-            return r;
-        };
-        // planes -> LDS byte offsets: nibble j of the V plane times 16 (a 16-byte row), of the N plane times 4
-        auto unpack = [&](const Raw &r) {
-            Planes p;
-#pragma unroll
-            for (int wi = 0; wi < NWP; ++wi) {
-                p.ve[wi] = r.wv[wi] & 0xF0F0F0F0u;
-                p.vo[wi] = (r.wv[wi] << 4) & 0xF0F0F0F0u;
-                p.ne[wi] = (r.wn[wi] >> 2) & 0x3C3C3C3Cu;
-                p.no[wi] = (r.wn[wi] << 2) & 0x3C3C3C3Cu;
-                // (opaque to the optimiser: it would otherwise re-derive every offset from the plane word with a
-                // shift and a mask of its own -- two vector instructions per offset instead of one byte extraction)
-                asm volatile("" : "+v"(p.ve[wi]), "+v"(p.vo[wi]), "+v"(p.ne[wi]), "+v"(p.no[wi]));
-            }
-            p.d1 = ((r.wn[NS >> 3] >> (4 * (NS & 7))) & 15u) << 4;   // dense MFMA 1: raw code, last nibble of the N plane
-            return p;
-        };
-        auto voff = [&](const Planes &p, int j) { return (((j & 1) ? p.ve[j >> 3] : p.vo[j >> 3]) >> (8 * ((j & 7) >> 1))) & 0xFFu; };
-        auto noff = [&](const Planes &p, int j) { return (((j & 1) ? p.ne[j >> 3] : p.no[j >> 3]) >> (8 * ((j & 7) >> 1))) & 0xFFu; };
-        // operands of MFMA oi: 0, 1 dense (identity rows), 2 .. sparse (value row + position word)
-        auto fetch = [&](const Planes &p, int oi, v4i &av, int &iv) {
-            if (oi == 0) {
-                av = *reinterpret_cast<const v4i *>(ident + voff(p, NS));
-            } else if (oi == 1) {
-                av = *reinterpret_cast<const v4i *>(ident + p.d1);
-            } else {
-                av = *reinterpret_cast<const v4i *>(vtab + voff(p, oi - 2));
-                iv = *reinterpret_cast<const int *>(ntab + noff(p, oi - 2));
-            }
-        };
-        // Software pipeline over the item's tiles.  step(t): the MFMA chain of tile t into accN; between its MFMAs
-        // the survivor mask of tile t - 1 from accO (the sign of each result), the operand reads of the chain's
-        // later MFMAs and -- in its last D slots -- of the FIRST D MFMAs of tile t + 1, so that no chain starts with
-        // an exposed LDS round trip; the global load of tile t + 2's planes is issued at the top.  One extra step
-        // drains the last tile (its MFMAs run on stale operands and are dropped).
-        Raw rawn = load_planes(ntile > 1 ? 1u : 0u);
-        Planes pl = unpack(load_planes(0u));
-        Ops ops;
-#pragma unroll
-        for (int oi = 0; oi < D; ++oi) fetch(pl, oi, ops.av[oi], ops.iv[oi]);
-        uint32_t mlo = 0;
-        auto step = [&](v16i &accN, const v16i &accO, uint32_t t, auto hi_half) {
-            const Planes pn = unpack(rawn);                        // tile t + 1 (loaded during step t - 1)
-            if (t + 2 < ntile) rawn = load_planes(t + 2);
-            v4i av[KT];
-            int iv[KT];
-            Ops nops;
-#pragma unroll
-            for (int oi = 0; oi < D; ++oi) {
-                av[oi] = ops.av[oi];
-                iv[oi] = ops.iv[oi];
-            }
-            // lane (col, h), register r: point row (r & 3) + 8 * (r >> 2) + 4 * h of the tile; result r's sign
-            // (negative = passes) ends up at bit 15 - r of the mask
-            uint32_t m16 = 0;
-            __builtin_amdgcn_s_setprio(2);
-#pragma unroll
-            for (int oi = 0; oi < KT; ++oi) {
-                if (oi + D < KT) fetch(pl, oi + D, av[oi + D], iv[oi + D]);
-                else fetch(pn, oi + D - KT, nops.av[oi + D - KT], nops.iv[oi + D - KT]);
-                if (oi == 0)
-                    accN = __builtin_amdgcn_mfma_i32_32x32x32_i8(av[0], bd[0], v16i{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, 0, 0, 0);
-                else if (oi == 1)
-                    accN = __builtin_amdgcn_mfma_i32_32x32x32_i8(av[1], bd[1], accN, 0, 0, 0);
-                else
-                    accN = __builtin_amdgcn_smfmac_i32_32x32x64_i8(av[oi], bs[oi - 2], accN, iv[oi], 0, 0);
-#pragma unroll
-                for (int r = oi * 16 / KT; r < (oi + 1) * 16 / KT; ++r)
-                    m16 = __builtin_amdgcn_alignbit(m16, (uint32_t)accO[r], 31);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            __builtin_amdgcn_s_setprio(0);
-            ops = nops;
-            pl = pn;
-            if (t == 0) return;                // nothing before the first tile (wave-uniform)
-            if (t == ntile && (npts & 31u)) {  // partial last tile: rows past the leaf's end are padding
-                const uint32_t base = c0 + (t - 1) * 32u + 4u * h;
-                uint32_t okm = 0;
-#pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    okm |= (base + (uint32_t)((r & 3) + 8 * (r >> 2)) < size ? 1u : 0u) << (15 - r);
-                m16 &= okm;
-            }
-            if constexpr (decltype(hi_half)::value) {
-                bits[((t - 1) >> 1) * 64u] = mlo | (m16 << 16);
-            } else {
-                mlo = m16;
-            }
-        };
-        // (tile 0 is peeled: inside the loop t >= 1 is known, so the compiler keeps the mask build between
-        // the MFMAs in BOTH instances instead of sinking it below a `t == 0` branch)
-        v16i accA = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, accB = accA;
-        step(accA, accB, 0u, std::false_type());
-        for (uint32_t tl = 1; tl <= ntile; tl += 2) {
-            step(accB, accA, tl, std::false_type());                          // mask of tile tl - 1 (even): low half
-            if (tl + 1 <= ntile) step(accA, accB, tl + 1, std::true_type());  // mask of tile tl (odd): high half, write
-        }
-        if (ntile & 1u) bits[(ntile >> 1) * 64u] = mlo;   // the last tile had an even number: its word has no high half
-        // ---- flush: the item's bitmap -> the queries' lists (sp_flush_item: its own function, so that its registers
-        // are allocated apart from the tile loop's -- inlined, the loop spilled its table fragments)
-        if constexpr (WORDS)
-            sp_flush_item_words<S>(ix.codes_sp, ix, a.allow, a.allow_bits, a.cand32_cnt, a.cand32, a.cand32_codes, a.cap32, &s_bits[wave][0][0],
-                                   s_stage[wave], s_fq[wave], s_fvb[wave], s_fgb[wave], ntile, c0, lb, pq, vb);
-        else
-            sp_flush_item_lanes<S>(ix.codes_sp, ix, a.allow, a.allow_bits, a.cand32_cnt, a.cand32, a.cand32_codes, a.cap32, bits, s_stage[wave],
-                                   s_fq[wave], s_fvb[wave], s_fgb[wave], ntile, c0, lb, pq, vb);
-        tile = __builtin_amdgcn_readfirstlane(next_tile);
-    }
-}
-
-// S <= 32: three waves per SIMD (the pair tile's table fragments alone are 64 registers); S = 48, 64: two.  (Capping the
-// registers at 144 to leave room for a wave of another stream's kernel was tried: amdgpu_num_vgpr is ignored by this
-// compiler, and two waves per SIMD (two workgroups per CU) cost the scan 10 % and gained the two-stream step nothing.)
-#ifndef SCANN_SP_VGPRS
-#define SCANN_SP_VGPRS 144
-#endif
-template <int S_, bool WORDS>
-__global__ __launch_bounds__(kMfmaWaves * 64, SCANN_MFMA_MINW) __attribute__((amdgpu_num_vgpr(SCANN_SP_VGPRS)))
-void adc_smfmac_kernel(TxhIndexDev ix, MfmaArgs a) {
-    adc_smfmac_body<S_, WORDS>(ix, a);
-}
-template <int S_, bool WORDS>
-__global__ __launch_bounds__(kMfmaWaves * 64, 2) void adc_smfmac_wide_kernel(TxhIndexDev ix, MfmaArgs a) {   // S = 48, 64
-    adc_smfmac_body<S_, WORDS>(ix, a);
-}
-
-// The prefilter with 16-pair tiles on v_mfma_i32_16x16x64_i8, for leaves scanned by 8-24 queries of the batch
-// (typical Tree-X-Hybrid batches: 1024 queries x 10 leaves over 1000 leaves): a 32-pair tile would be a
-// third full there.  A tile = 32 points (two groups of 16) x 16 pairs = 2 x S/4 MFMAs of 4 subspaces each, two
-// independent accumulator chains of 4 registers.  Lane (c16 = lane & 15, kb = lane >> 4): A row = point c16 of
-// the group, K block kb = subspace 4 kt + kb (one-hot row from the LDS identity table); B column = pair c16;
-// results D[row 4 kb + r][column c16], r = 0..3.  Items, bounds, staging, flush and lists as in adc_mfma_kernel
-// (the worklist is built with 4 quads per tile).  Measured as a 32-pair kernel (two halves) this shape lost to
-// adc_mfma_kernel (more vector work per tile); here it replaces the f32 LDS-gather scan.
-template <int S_>
-__global__ __launch_bounds__(kMfmaWaves * 64, (S_ <= 32 ? 4 : 2)) void adc_mfma16_kernel(TxhIndexDev ix, MfmaArgs a) {
-    typedef int v4i __attribute__((ext_vector_type(4)));
-    constexpr int S = S_, KT = S / 4, NW = S / 8, NP = (NW + 1) / 2;
-    __shared__ __attribute__((aligned(16))) uint32_t s_ident[64];                 // 16 one-hot rows of 16 bytes
-    __shared__ uint32_t s_stage[kMfmaWaves][16][kMfmaStage];
-    __shared__ uint32_t s_cnt[kMfmaWaves][16];
-    __shared__ uint32_t s_fpre[kMfmaWaves][16], s_fq[kMfmaWaves][16], s_fgb[kMfmaWaves][16], s_fvb[kMfmaWaves][16];   // per pair
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    const uint32_t c16 = lane & 15u, kb = lane >> 4;
-    if (tid < 64) {
-        const uint32_t c = tid >> 2, wsel = tid & 3u;
-        s_ident[tid] = (wsel == (c >> 2)) ? (1u << (8 * (c & 3u))) : 0u;
-    }
-    __syncthreads();
-    const uint32_t total_tiles = a.counters[CNT_TOTAL_TILES];
-    const char *ident = reinterpret_cast<const char *>(s_ident);
-
-    uint32_t tile = 0;
-    if (lane == 0) tile = grab_tile(a.counters + CNT_XQ, total_tiles);
-    tile = __builtin_amdgcn_readfirstlane(tile);
-    while (tile != kInvalid) {
-        uint32_t next_tile = 0;
-        if (lane == 0) next_tile = grab_tile(a.counters + CNT_XQ, total_tiles);
-        const WorkItem item = decode_item(ix, a.tile_off, a.pair_off, tile);
-        const uint32_t lb = item.lb, size = item.size, local = item.local, slot0 = item.slot0, slot_end = item.slot_end;
-        const uint32_t nranges = (size + kMfmaRange - 1) / kMfmaRange;
-        const uint32_t range = local % nranges, pt = local / nranges;
-        const uint32_t c0 = range * kMfmaRange;
-        const uint32_t npts = min(kMfmaRange, size - c0);
-
-        // this lane's pair (column c16 of the tile): tables, bound; query and key base go to LDS for the flush
-        const uint32_t slot = slot0 + pt * 16u + c16;
-        const bool pair_ok = slot < slot_end;
-        if (lane < 16) {
-            s_cnt[wave][lane] = 0;
-            s_fq[wave][lane] = pair_ok ? a.pair_q[slot] : kInvalid;
-            s_fvb[wave][lane] = pair_ok ? a.pair_vbase[slot] : 0u;
-        }
-        v4i b[KT];
-        {
-            const int8_t *bsrc = a.lut8 + ((size_t)(pair_ok ? slot : slot0) * S + kb) * 16;   // padding columns: any table
-#pragma unroll
-            for (int kt = 0; kt < KT; ++kt) b[kt] = *reinterpret_cast<const v4i *>(bsrc + (size_t)kt * 64);
-        }
-        const int thr1 = pair_ok ? a.thr1[slot] : -(128 * S + 7);   // a point passes iff acc - thr1 < 0
-
-        const uint32_t ntile = (npts + 31u) >> 5;
-        uint32_t wn[2][NW];
-#pragma unroll
-        for (int g = 0; g < 2; ++g) {
-            const uint32_t j = c0 + 16u * g + c16;
-            Codec<S, 4>::load_words(ix.codes + (size_t)(lb + (j < size ? j : 0u)) * NW, wn[g]);
-        }
-        auto flush = [&](bool all) {
-            uint32_t n = 0, gbase = 0;
-            if (lane < 16) {
-                n = min(s_cnt[wave][lane], kMfmaStage);
-                if (!all && n + 32u <= kMfmaStage) n = 0;
-                if (n) {
-                    gbase = atomicAdd(&a.cand32_cnt[s_fq[wave][lane]], n);
-                    s_cnt[wave][lane] = 0;
-                }
-            }
-            uint32_t incl = n;
-#pragma unroll
-            for (int o = 1; o < 16; o <<= 1) {
-                const uint32_t up = (uint32_t)__shfl_up((int)incl, o);
-                if ((int)lane >= o) incl += up;
-            }
-            const uint32_t total = (uint32_t)__shfl((int)incl, 15);
-            if (total == 0) return;
-            if (lane < 16) {
-                s_fpre[wave][lane] = incl - n;
-                s_fgb[wave][lane] = gbase;
-            }
-            for (uint32_t e = lane; e < total; e += 64u) {
-                uint32_t c = 0;
-#pragma unroll
-                for (uint32_t stp = 8; stp; stp >>= 1)
-                    if (s_fpre[wave][c + stp] <= e) c += stp;
-                const uint32_t idx = e - s_fpre[wave][c];
-                const uint32_t j = s_stage[wave][c][idx];
-                const uint32_t dst = s_fgb[wave][c] + idx;
-                append_survivor<S>(a.cand32, a.cand32_codes, a.cap32, s_fq[wave][c], dst, s_fvb[wave][c] + j, ix.codes + (size_t)(lb + j) * NW);
-            }
-        };
-        // step(t): the MFMAs of tile t into accN, the survivor mask of tile t - 1 from accO between them, then
-        // the staging of tile t - 1's survivors
-        auto step = [&](v4i (&accN)[2], const v4i (&accO)[2], uint32_t t) {
-            // byte kt' of pk[g][i] = code * 16 of subspace 4 kt + kb, kt = 4 i + {0, 2, 1, 3}[kt']
-            uint32_t pk[2][NP];
-#pragma unroll
-            for (int g = 0; g < 2; ++g)
-#pragma unroll
-                for (int i = 0; i < NP; ++i) {
-                    const uint32_t y0 = (wn[g][2 * i] >> (4u * kb)) & 0x000F000Fu;
-                    const uint32_t y1 = (2 * i + 1 < NW) ? ((wn[g][(2 * i + 1 < NW) ? 2 * i + 1 : 0] >> (4u * kb)) & 0x000F000Fu) : 0u;
-                    pk[g][i] = (y0 | (y1 << 8)) << 4;
-                }
-            if (t + 1 < ntile) {
-#pragma unroll
-                for (int g = 0; g < 2; ++g) {
-                    const uint32_t j = c0 + (t + 1) * 32u + 16u * g + c16;
-                    Codec<S, 4>::load_words(ix.codes + (size_t)(lb + (j < size ? j : 0u)) * NW, wn[g]);
-                }
-            }
-            accN[0] = v4i{0, 0, 0, 0};
-            accN[1] = v4i{0, 0, 0, 0};
-            constexpr int NA = 2 * KT;                        // MFMAs per tile, in order (kt, g)
-            constexpr int D = kMfmaDepth < NA ? kMfmaDepth : NA;
-            v4i av[D + 1];
-            auto onehot = [&](int ai) {
-                const int kt = ai >> 1, g = ai & 1;
-                const int byte = ((kt & 1) << 1) | ((kt >> 1) & 1);   // kt & 3 -> {0, 2, 1, 3}
-                const uint32_t off = (pk[g][kt >> 2] >> (8 * byte)) & 0xFFu;
-                return *reinterpret_cast<const v4i *>(ident + off);
-            };
-#pragma unroll
-            for (int ai = 0; ai < D; ++ai) av[ai] = onehot(ai);
-            uint32_t m8 = 0;   // survivor bits: result (g, r) at bit 7 - (4 g + r)
-            __builtin_amdgcn_s_setprio(2);
-#pragma unroll
-            for (int ai = 0; ai < NA; ++ai) {
-                const int kt = ai >> 1, g = ai & 1;
-                if (ai + D < NA) av[(ai + D) % (D + 1)] = onehot(ai + D);
-                accN[g] = __builtin_amdgcn_mfma_i32_16x16x64_i8(av[ai % (D + 1)], b[kt], accN[g], 0, 0, 0);
-#pragma unroll
-                for (int ri = ai * 8 / NA; ri < (ai + 1) * 8 / NA; ++ri)
-                    m8 = __builtin_amdgcn_alignbit(m8, (uint32_t)(accO[ri >> 2][ri & 3] - thr1), 31);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            __builtin_amdgcn_s_setprio(0);
-            if (t == 0) return;
-            const uint32_t base = c0 + (t - 1) * 32u + 4u * kb;
-            if (t == ntile && (npts & 31u)) {  // partial last tile: rows past the leaf's end are padding
-                uint32_t okm = 0;
-#pragma unroll
-                for (int ri = 0; ri < 8; ++ri)
-                    okm |= (base + 16u * (uint32_t)(ri >> 2) + (uint32_t)(ri & 3) < size ? 1u : 0u) << (7 - ri);
-                m8 &= okm;
-            }
-            bool risk = false;
-            m8 &= 0xFFu;
-            if (a.allow && m8)                 // search_with_filter: disallowed points are not survivors
-                m8 = mask_allowed(ix, a.allow, a.allow_bits, lb, m8, [&](uint32_t b) {
-                    const uint32_t qi = 7u - b;
-                    return base + 16u * (qi >> 2) + (qi & 3u);
-                });
-            if (m8) {
-                uint32_t sl = atomicAdd(&s_cnt[wave][c16], (uint32_t)__popc(m8));
-                do {
-                    const uint32_t qi = 7u - ((uint32_t)__ffs((int)m8) - 1u);
-                    m8 &= m8 - 1u;
-                    const uint32_t j = base + 16u * (qi >> 2) + (qi & 3u);
-                    if (sl < kMfmaStage) {
-                        s_stage[wave][c16][sl] = j;
-                    } else {   // stage full: direct (slow) append
-                        const uint32_t pqd = s_fq[wave][c16];
-                        const uint32_t pos = atomicAdd(&a.cand32_cnt[pqd], 1u);
-                        append_survivor<S>(a.cand32, a.cand32_codes, a.cap32, pqd, pos, s_fvb[wave][c16] + j, ix.codes + (size_t)(lb + j) * NW);
-                    }
-                    ++sl;
-                } while (m8);
-                risk = sl + 32u > kMfmaStage;
-            }
-            if (__any(risk)) flush(false);
-        };
-        v4i accA[2], accB[2];
-        accA[0] = accA[1] = accB[0] = accB[1] = v4i{0, 0, 0, 0};
-        step(accA, accB, 0u);
-        for (uint32_t tl = 1; tl <= ntile; tl += 2) {
-            step(accB, accA, tl);
-            if (tl + 1 <= ntile) step(accA, accB, tl + 1);
-        }
-        flush(true);
-        tile = __builtin_amdgcn_readfirstlane(next_tile);
-    }
-}
-
-// Exact refine of the prefilter's survivors: block per query.  Recomputes the reference's f32 sums
-// (LookupTable::compute_distance, hashes/lut.rs:74-82: acc = lut[0][c0]; acc += lut[s][cs], s
-// ascending), forms the merge keys and keeps key <= T -- exactly adc_scan_kernel's survivors.
-struct RefineArgs {
-    uint32_t P, cap, cap32;
-    const uint32_t *tokens, *vbase, *slot_of;
-    const float *lutq;
-    const uint64_t *thr;
-    const uint32_t *cand32_cnt, *cand32, *cand32_codes;
-    uint32_t *cand_cnt;
-    uint64_t *cand;
-    uint32_t *counters;
-    const uint64_t *allow;
-    uint64_t allow_bits;
-    int planes;   // cand32_codes holds codes_sp plane rows (adc_smfmac_kernel), not packed codes
-};
-
-// code of subspace s from a point's plane row (SpLayout: [ha][plane V, N][word]); ca / cb = the code nibbles of the
-// first / second subspace each sparse MFMA takes from parity ha, rebuilt word-parallel by sp_row_decode
-template <int S>
-struct SpRow {
-    static constexpr int NWP = SpLayout<S>::NWP, NS = SpLayout<S>::NS;
-    uint32_t ca[2][NWP], cb[2][NWP], dv[2], dn[2];   // dv / dn: the dense MFMAs' raw codes (subspaces ha, 2 + ha)
-    __device__ __forceinline__ void decode(const uint32_t *row) {
-#pragma unroll
-        for (int ha = 0; ha < 2; ++ha) {
-#pragma unroll
-            for (int wi = 0; wi < NWP; ++wi) {
-                const uint32_t v = row[(ha * 2 + 0) * NWP + wi], n = row[(ha * 2 + 1) * NWP + wi];
-                ca[ha][wi] = ((v & 0x33333333u) << 2) | (n & 0x33333333u);
-                cb[ha][wi] = (v & 0xCCCCCCCCu) | ((n >> 2) & 0x33333333u);
-            }
-            dv[ha] = (row[(ha * 2 + 0) * NWP + (NS >> 3)] >> (4 * (NS & 7))) & 15u;
-            dn[ha] = (row[(ha * 2 + 1) * NWP + (NS >> 3)] >> (4 * (NS & 7))) & 15u;
-        }
-    }
-    __device__ __forceinline__ uint32_t code(int s) const {   // s: compile-time after unrolling
-        if (s < 4) return (s >> 1) ? dn[s & 1] : dv[s & 1];
-        const int kt = (s - 4) >> 2, q = (s - 4) & 3, ha = q & 1;
-        const uint32_t src = (q >> 1) ? cb[ha][kt >> 3] : ca[ha][kt >> 3];
-        return (src >> (4 * (kt & 7))) & 15u;
-    }
-};
-
-#ifndef SCANN_REFINE_THREADS
-#define SCANN_REFINE_THREADS 256
-#endif
-#ifndef SCANN_REFINE_U
-#define SCANN_REFINE_U 4
-#endif
-constexpr uint32_t kRefineThreads = SCANN_REFINE_THREADS;
-
-template <typename C>
-__global__ __launch_bounds__(kRefineThreads) void adc_refine_kernel(TxhIndexDev ix, RefineArgs a) {
-    constexpr int S = C::S, NW = C::NWORDS;
-    // words per list entry: packed codes, or (4-bit codes behind the sparse-MFMA prefilter) the point's plane row
-    constexpr int SPW = C::BITS == 4 ? (int)(4 * ((((S - 4) / 4 + 1) + 7) / 8)) : NW;
-    constexpr int RW = SPW > NW ? SPW : NW;
-    const bool planes = C::BITS == 4 && a.planes;   // (block-uniform)
-    const uint32_t ew = planes ? (uint32_t)SPW : (uint32_t)NW;
-    extern __shared__ __attribute__((aligned(16))) float s_tab[];       // [min(P, kRefineTablesMax)][S][16]
-    __shared__ uint32_t s_dvb[kDecodeStage], s_drow[kDecodeStage], s_slot[kDecodeStage], s_out;
-    const uint32_t q = blockIdx.x, tid = threadIdx.x, lane = tid & 63u;
-    const uint32_t P = a.P;
-    const uint32_t cnt = a.cand32_cnt[q];
-    if (cnt > a.cap32) {   // list overflow: report, never a wrong row
-        if (tid == 0) {
-            atomicMax(&a.counters[CNT_STATUS], (uint32_t)SCANN_HIP_RESOURCE_EXHAUSTED);
-            a.cand_cnt[q] = a.cap + 1u;
-        }
-        return;
-    }
-    const uint64_t T = a.thr[q];
-    const bool staged = P <= kDecodeStage;
-    const bool tabs = P <= kRefineTablesMax;
-    const uint32_t *vbq = a.vbase + (size_t)q * (P + 1);
-    if (staged)
-        for (uint32_t r = tid; r < P; r += kRefineThreads) {
-            s_dvb[r] = vbq[r];
-            s_drow[r] = ix.leaf_off[a.tokens[(size_t)q * P + r]];
-            s_slot[r] = a.slot_of[(size_t)q * P + r];
-        }
-    if (tid == 0) s_out = 0;
-    __syncthreads();
-    if (tabs) {   // this query's pair tables, de-interleaved: [r][s][16]
-        for (uint32_t e = tid; e < P * S * 16; e += kRefineThreads) {
-            const uint32_t r = e / (S * 16), sc = e - r * (S * 16);
-            const uint32_t slot = staged ? s_slot[r] : a.slot_of[(size_t)q * P + r];
-            s_tab[e] = slot == kInvalid ? 0.0f : a.lutq[((size_t)(slot >> 2) * S * 16 + sc) * 4 + (slot & 3u)];
-        }
-        __syncthreads();
-    }
-    uint64_t *out = a.cand + (size_t)q * a.cap;
-    const uint32_t *list = a.cand32 + (size_t)q * a.cap32;
-    const uint32_t *list_codes = a.cand32_codes ? a.cand32_codes + (size_t)q * a.cap32 * ew : nullptr;
-    constexpr int U = SCANN_REFINE_U;   // entries per thread per pass: their dependent loads (position -> codes) overlap
-    for (uint32_t b0 = 0; b0 < cnt; b0 += kRefineThreads * U) {
-        uint32_t vpos[U], csr[U], lo_[U];
-        uint32_t w[U][RW];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const uint32_t e = b0 + tid + kRefineThreads * u;
-            vpos[u] = e < cnt ? list[e] : 0xFFFFFFFFu;
-            if (a.cand32_codes) {   // (written with the position)
-                const uint32_t *src = list_codes + (size_t)(e < cnt ? e : 0u) * ew;
-                if (planes) {
-#pragma unroll
-                    for (int x = 0; x < SPW / 4; ++x) {
-                        const uint4 v = reinterpret_cast<const uint4 *>(src)[x];
-                        w[u][4 * x] = v.x; w[u][4 * x + 1] = v.y; w[u][4 * x + 2] = v.z; w[u][4 * x + 3] = v.w;
-                    }
-                } else {
-                    uint32_t t[NW];
-                    C::load_words(src, t);
-#pragma unroll
-                    for (int x = 0; x < NW; ++x) w[u][x] = t[x];
-                }
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            uint32_t lo = 0, hi = P;
-            const uint32_t vp = vpos[u] == 0xFFFFFFFFu ? 0u : vpos[u];
-            while (hi - lo > 1) {
-                const uint32_t mid = (lo + hi) >> 1;
-                if ((staged ? s_dvb[mid] : vbq[mid]) <= vp) lo = mid; else hi = mid;
-            }
-            lo_[u] = lo;
-            csr[u] = (staged ? s_drow[lo] : ix.leaf_off[a.tokens[(size_t)q * P + lo]]) + (vp - (staged ? s_dvb[lo] : vbq[lo]));
-            if (!a.cand32_codes) {
-                uint32_t t[NW];
-                C::load_words(ix.codes + (size_t)(vpos[u] == 0xFFFFFFFFu ? 0u : csr[u]) * NW, t);
-#pragma unroll
-                for (int x = 0; x < NW; ++x) w[u][x] = t[x];
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            bool keep = false;
-            uint64_t key = 0;
-            if (vpos[u] != 0xFFFFFFFFu) {
-                float acc = 0.0f;
-                bool done = false;
-                if constexpr (C::BITS == 4) {
-                    if (planes && tabs) {   // (the sparse prefilter runs with staged tables: P <= kRefineTablesMax or not, both forms)
-                        SpRow<S> row;
-                        row.decode(w[u]);
-                        const float *tb = s_tab + lo_[u] * (S * 16);
-#pragma unroll
-                        for (int s2 = 0; s2 < S; ++s2) {
-                            const float tv = tb[s2 * 16 + row.code(s2)];
-                            acc = s2 == 0 ? tv : acc + tv;
-                        }
-                        done = true;
-                    } else if (planes) {
-                        SpRow<S> row;
-                        row.decode(w[u]);
-                        const uint32_t slot = staged ? s_slot[lo_[u]] : a.slot_of[(size_t)q * P + lo_[u]];
-                        const float *tb = a.lutq + (size_t)(slot >> 2) * S * 64 + (slot & 3u);
-#pragma unroll
-                        for (int s2 = 0; s2 < S; ++s2) {
-                            const float tv = tb[(s2 * 16 + row.code(s2)) * 4];
-                            acc = s2 == 0 ? tv : acc + tv;
-                        }
-                        done = true;
-                    }
-                }
-                if (done) {
-                } else if (tabs) {
-                    const float *tb = s_tab + lo_[u] * (S * 16);
-#pragma unroll
-                    for (int s2 = 0; s2 < S; ++s2) {
-                        const uint32_t code = (w[u][s2 >> 3] >> (4 * (s2 & 7))) & 15u;
-                        const float tv = tb[s2 * 16 + code];
-                        acc = s2 == 0 ? tv : acc + tv;
-                    }
-                } else {
-                    const uint32_t slot = staged ? s_slot[lo_[u]] : a.slot_of[(size_t)q * P + lo_[u]];
-                    const float *tb = a.lutq + (size_t)(slot >> 2) * S * 64 + (slot & 3u);
-#pragma unroll
-                    for (int s2 = 0; s2 < S; ++s2) {   // (fully unrolled: a dynamic index would push w[] to scratch)
-                        const uint32_t code = (w[u][s2 >> 3] >> (4 * (s2 & 7))) & 15u;
-                        const float tv = tb[(s2 * 16 + code) * 4];
-                        acc = s2 == 0 ? tv : acc + tv;
-                    }
-                }
-                key = make_key(acc, vpos[u]);
-                keep = key <= T && row_allowed(ix, a.allow, a.allow_bits, csr[u]);
-            }
-            uint32_t wtot;
-            const uint32_t wpre = wave_prefix_count(keep, &wtot);
-            uint32_t base = 0;
-            if (lane == 0 && wtot) base = atomicAdd(&s_out, wtot);
-            base = (uint32_t)__shfl((int)base, 0);
-            if (keep && base + wpre < a.cap) out[base + wpre] = key;
-        }
-    }
-    __syncthreads();
-    if (tid == 0) a.cand_cnt[q] = s_out;   // > cap: select_rerank reports the overflow
 }
 
 // =====================================================================================
@@ -3895,232 +2085,6 @@ __global__ __launch_bounds__(NT) void final_topk_kernel(
 //                        arithmetic), the k best by (exact, merge key), output rows
 // =====================================================================================
 // uni_scale > 0: every row with that one scale (the store of rerank_i8_kernel's UNIFORM form, see the launcher)
-__global__ __launch_bounds__(256) void rows_i8_build_kernel(const float *__restrict__ rows, uint64_t n, uint32_t dim,
-                                                            uint32_t stride, int8_t *__restrict__ rows8,
-                                                            float2 *__restrict__ meta, float uni_scale) {
-    // 8 lanes per row
-    const uint64_t r = (uint64_t)blockIdx.x * 32 + (threadIdx.x >> 3);
-    const uint32_t l8 = threadIdx.x & 7u;
-    const bool act = r < n;
-    const float *row = rows + (act ? r : 0) * stride;
-    float mx = 0.0f;
-    for (uint32_t j = l8; j < dim; j += 8) mx = fmaxf(mx, fabsf(row[j]));
-    mx = fmaxf(mx, __shfl_xor(mx, 1, 8));
-    mx = fmaxf(mx, __shfl_xor(mx, 2, 8));
-    mx = fmaxf(mx, __shfl_xor(mx, 4, 8));
-    const bool finite = mx < __builtin_inff();      // (NaN rows: mx stays finite-or-NaN; the error below turns NaN)
-    const float sc = uni_scale > 0.0f ? uni_scale : (mx > 0.0f && finite) ? mx / 127.0f : 1.0f;
-    float err = 0.0f;
-    for (uint32_t j = l8; j < dim; j += 8) {
-        const float x = row[j];
-        float t = rintf(x / sc);
-        t = fminf(fmaxf(t, -127.0f), 127.0f);
-        if (act) rows8[r * dim + j] = (int8_t)(t == t ? (int)t : 0);
-        const float e = x - sc * (t == t ? t : 0.0f);
-        err = err + e * e;
-    }
-    err += __shfl_xor(err, 1, 8);
-    err += __shfl_xor(err, 2, 8);
-    err += __shfl_xor(err, 4, 8);
-    if (act && l8 == 0) {
-        // E rounded up a little (the sum above is f32); a NaN / infinite row gets E = +inf: never filtered out
-        float E = sqrtf(err) * 1.0001f + 1e-30f;
-        if (!(E == E) || !finite) E = __builtin_inff();
-        meta[r] = make_float2(sc, E);
-    }
-}
-
-// ---- the reference's FP8 codec (quantization/fp8.rs:80-203), bit for bit -----------------------------
-// format 0 = E4M3 (bias 7, 3 mantissa bits, max code 0x7E), 1 = E5M2 (bias 15, 2 bits, max code 0x7C).
-// NOT the hardware conversion: the mantissa carry wraps without bumping the exponent, the top exponent
-// field only ever encodes the maximum, values under the smallest normal flush to (signed) zero.
-__device__ __forceinline__ uint32_t fp8_from_f32(float value, int format) {
-    const int mbits = format ? 2 : 3, bias = format ? 15 : 7, emax = format ? 31 : 15;
-    const uint32_t maxcode = format ? 0x7Cu : 0x7Eu;
-    if (value == 0.0f) return 0u;
-    const uint32_t bits = __float_as_uint(value);
-    const uint32_t sign = bits >> 31;
-    const int exp = (int)((bits >> 23) & 0xFFu);
-    const uint32_t mantissa = bits & 0x7FFFFFu;
-    if (exp == 0xFF) return (sign << 7) | maxcode;
-    const int e8 = exp - 127 + bias;
-    if (e8 <= 0) return sign << 7;
-    if (e8 >= emax) return (sign << 7) | maxcode;
-    const uint32_t m = ((mantissa >> (23 - mbits)) + ((mantissa >> (22 - mbits)) & 1u)) & ((1u << mbits) - 1u);
-    return (sign << 7) | ((uint32_t)e8 << mbits) | m;
-}
-
-__device__ __forceinline__ float fp8_to_f32(uint32_t b, int format) {
-    const int mbits = format ? 2 : 3, bias = format ? 15 : 7;
-    const uint32_t sign = (b >> 7) & 1u;
-    const int exp = (int)((b >> mbits) & (format ? 0x1Fu : 0xFu));
-    const uint32_t mantissa = b & ((1u << mbits) - 1u);
-    if (exp == 0 && mantissa == 0) return sign ? -0.0f : 0.0f;
-    const int e32 = exp == 0 ? 126 - bias : exp - bias + 127;
-    return __uint_as_float((sign << 31) | ((uint32_t)e32 << 23) | (mantissa << (23 - mbits)));
-}
-
-// Quantizer::quantize / dequantize over Fp8Quantizer (fp8.rs:247-268)
-__global__ __launch_bounds__(256) void fp8_quantize_kernel(const float *__restrict__ values, uint64_t n, float scale,
-                                                           int format, uint8_t *__restrict__ out) {
-    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256)
-        out[i] = (uint8_t)fp8_from_f32(values[i] * scale, format);
-}
-
-__global__ __launch_bounds__(256) void fp8_dequantize_kernel(const uint8_t *__restrict__ bits, uint64_t n, float scale,
-                                                             int format, float *__restrict__ out) {
-    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256)
-        out[i] = fp8_to_f32(bits[i], format) / scale;
-}
-
-// one_to_many_fp8_float_{squared_l2, dot_product} (distance_measures/one_to_many_asymmetric.rs:327-377):
-// E4M3 rows, one sequential f32 sum per row (no FMA), the dot product negated.
-__global__ __launch_bounds__(256) void fp8_one_to_many_kernel(const float *__restrict__ query, uint32_t dim,
-                                                              const uint8_t *__restrict__ db, uint64_t stride,
-                                                              uint64_t n, int dot, float *__restrict__ out) {
-    extern __shared__ float s_q8[];   // [dim]
-    for (uint32_t j = threadIdx.x; j < dim; j += 256) s_q8[j] = query[j];
-    __syncthreads();
-    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) {
-        const uint8_t *row = db + i * stride;
-        float sum = 0.0f;
-        if (dot) {
-            for (uint32_t j = 0; j < dim; ++j) sum = sum + s_q8[j] * fp8_to_f32(row[j], 0);
-            out[i] = -sum;
-        } else {
-            for (uint32_t j = 0; j < dim; ++j) {
-                const float diff = s_q8[j] - fp8_to_f32(row[j], 0);
-                sum = sum + diff * diff;
-            }
-            out[i] = sum;
-        }
-    }
-}
-
-// The FP8 row store of the re-rank filter: the reference's E4M3 codec with Fp8Quantizer::calibrate_scale
-// per row (scale = 448 / max|x|, fp8.rs:238-244); the filter decodes with v_cvt_pk_f32_fp8 (gfx950: OCP
-// E4M3 -- equal to the reference's decode on every code its encoder emits) as x~ = dec * (1 / scale), and E
-// is computed from that same expression.  `mismatch` counts codes the hardware decodes differently
-// (never, unless the conversion instruction means another format: the create call then fails).
-__global__ __launch_bounds__(256) void rows_fp8_build_kernel(const float *__restrict__ rows, uint64_t n, uint32_t dim,
-                                                             uint32_t stride, uint8_t *__restrict__ rows8,
-                                                             float2 *__restrict__ meta, uint32_t *__restrict__ mismatch) {
-    const uint64_t r = (uint64_t)blockIdx.x * 32 + (threadIdx.x >> 3);
-    const uint32_t l8 = threadIdx.x & 7u;
-    const bool act = r < n;
-    const float *row = rows + (act ? r : 0) * stride;
-    float mx = 0.0f;
-    for (uint32_t j = l8; j < dim; j += 8) mx = fmaxf(mx, fabsf(row[j]));
-    mx = fmaxf(mx, __shfl_xor(mx, 1, 8));
-    mx = fmaxf(mx, __shfl_xor(mx, 2, 8));
-    mx = fmaxf(mx, __shfl_xor(mx, 4, 8));
-    const bool finite = mx < __builtin_inff();
-    const float scale = 448.0f / fmaxf(finite ? mx : 1.0f, 1e-10f);
-    const float inv = 1.0f / scale;
-    float err = 0.0f;
-    uint32_t bad = 0;
-    for (uint32_t j = l8; j < dim; j += 8) {
-        const float x = row[j];
-        const uint32_t b = fp8_from_f32(x * scale, 0);
-        const float hw = __builtin_amdgcn_cvt_f32_fp8((int)b, 0);
-        bad += (__float_as_uint(hw) != __float_as_uint(fp8_to_f32(b, 0))) ? 1u : 0u;
-        if (act) rows8[r * dim + j] = (uint8_t)b;
-        const float e = x - hw * inv;
-        err = err + e * e;
-    }
-    err += __shfl_xor(err, 1, 8);
-    err += __shfl_xor(err, 2, 8);
-    err += __shfl_xor(err, 4, 8);
-    if (act && bad) atomicAdd(mismatch, bad);
-    if (act && l8 == 0) {
-        float E = sqrtf(err) * 1.0001f + 1e-30f;
-        if (!(E == E) || !finite) E = __builtin_inff();
-        meta[r] = make_float2(inv, E);
-    }
-}
-
-struct I8RerankArgs {
-    const int8_t *rows8;      // [n_rows][dim] int8, or the reference's E4M3 codes (FMT = 1)
-    const float2 *meta;       // [n_rows] {dequantisation factor, error norm}
-    float uni_scale, uni_E;   // UNI form: one dequantisation factor and one error bound for every row (no meta gather)
-    const float *queries;
-    uint32_t q_stride, m;
-    const uint32_t *cand_row, *cand_count;
-    uint32_t *lb, *ub;        // [nq][m] ordered(L), ordered(U)
-};
-
-constexpr uint32_t kI8PerBlock = 256;   // candidates per block (8 lanes each, 8 rounds): amortises the query staging
-
-template <int FMT, bool UNI = false>   // 0 = int8 rows, 1 = FP8 (E4M3) rows
-__global__ __launch_bounds__(256) void rerank_i8_kernel(uint32_t dim, I8RerankArgs a) {
-    typedef float v2f __attribute__((ext_vector_type(2)));
-    extern __shared__ __attribute__((aligned(16))) float s_q[];   // [dim]
-    const uint32_t q = blockIdx.y, tid = threadIdx.x;
-    const uint32_t nsel = a.cand_count[q];
-    const uint32_t c0 = blockIdx.x * kI8PerBlock;
-    if (c0 >= nsel) return;   // uniform
-    for (uint32_t j = tid; j < dim; j += 256) s_q[j] = a.queries[(size_t)q * a.q_stride + j];
-    __syncthreads();
-    const uint32_t l8 = tid & 7u;
-    constexpr int R = kI8PerBlock / 32;
-    uint32_t row[R];
-#pragma unroll
-    for (int it = 0; it < R; ++it) {   // the rounds' row ids first: their gathers then overlap
-        const uint32_t c = c0 + (uint32_t)it * 32u + (tid >> 3);
-        row[it] = c < nsel ? a.cand_row[(size_t)q * a.m + c] : 0u;
-    }
-#pragma unroll
-    for (int it = 0; it < R; ++it) {
-        const uint32_t c = c0 + (uint32_t)it * 32u + (tid >> 3);
-        const bool act = c < nsel;
-        const float2 me = UNI ? make_float2(a.uni_scale, a.uni_E) : a.meta[row[it]];
-        const int8_t *r8 = a.rows8 + (size_t)row[it] * dim;
-        float acc = 0.0f;
-        for (uint32_t j0 = l8 * 16u; j0 < dim; j0 += 128u) {   // 16 dims per lane per pass (dim % 16 == 0)
-            const uint4 v = *reinterpret_cast<const uint4 *>(r8 + j0);
-            const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-            if constexpr (FMT == 1) {
-#pragma unroll
-                for (int wi = 0; wi < 4; ++wi) {
-                    const v2f lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[wi], false);
-                    const v2f hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[wi], true);
-                    const float xs[4] = {lo.x, lo.y, hi.x, hi.y};
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        const float d = s_q[j0 + wi * 4 + i] - xs[i] * me.x;
-                        acc = fmaf(d, d, acc);
-                    }
-                }
-            } else {
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    const float x = me.x * (float)(int)(int8_t)(w[i >> 2] >> (8 * (i & 3)));
-                    const float d = s_q[j0 + i] - x;
-                    acc = fmaf(d, d, acc);
-                }
-            }
-        }
-        acc += __shfl_xor(acc, 1, 8);
-        acc += __shfl_xor(acc, 2, 8);
-        acc += __shfl_xor(acc, 4, 8);
-        if (act && l8 == 0) {
-            const float E = me.y;
-            // | d_f32 - d~ | <= 2 sqrt(d~) E + E^2 (triangle inequality on the real values) + the f32 rounding
-            // of the two dim-term sums (each <= (dim + 4) 2^-24 relative) + slack on the bound itself
-            const float slack = (2.0f * sqrtf(acc) * E + E * E) * 1.0001f + acc * ((float)(dim + 8) * 1.2e-7f) + 1e-30f;
-            float L = acc - slack, U = acc + slack;
-            // NaN or overflow anywhere (an infinite d~ would make L = inf - inf = NaN, which orders above +inf and
-            // drops the candidate): never filtered out, never a bound for others
-            if (!(slack < __builtin_inff()) || !(acc < __builtin_inff())) {
-                L = -__builtin_inff();
-                U = __builtin_inff();
-            }
-            a.lb[(size_t)q * a.m + c] = f32_to_ordered(L);
-            a.ub[(size_t)q * a.m + c] = f32_to_ordered(U);
-        }
-    }
-}
-
 constexpr uint32_t kShortMaxFast = 1024;   // shortlists up to this size finish inside rerank_short_kernel
 
 struct ShortArgs {
@@ -4870,145 +2834,13 @@ __global__ __launch_bounds__(kSelectThreads) void merge_kernel(
 }
 
 // =====================================================================================
-// Building blocks exposed through the C ABI
-// =====================================================================================
-// All-pairs ADC distances for explicit f32 LUTs [nq][S][K]: out [nq][n_local].
-// hashes/lut.rs:74-82: sum = 0.0; for s ascending: sum += lut[s][code[s]].
-__global__ __launch_bounds__(256) void adc_distances_kernel(TxhIndexDev ix,
-                                                            const float *__restrict__ luts,
-                                                            float *__restrict__ out) {
-    extern __shared__ float slut[];   // [S][K]
-    const uint32_t q = blockIdx.y, S = ix.S, K = ix.K, nw = ix.nw;
-    const uint32_t bits = ix.code_bits, per = 32u / bits, mask = (1u << bits) - 1u;
-    for (uint32_t e = threadIdx.x; e < S * K; e += blockDim.x) slut[e] = luts[(size_t)q * S * K + e];
-    __syncthreads();
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < ix.n_local;
-         i += (uint64_t)gridDim.x * blockDim.x) {
-        float acc = 0.0f;
-        for (uint32_t sub = 0; sub < S; ++sub) {
-            const uint32_t w = ix.codes[i * nw + sub / per];
-            const uint32_t code = (w >> (bits * (sub % per))) & mask;
-            acc = acc + slut[sub * K + (code < K ? code : 0u)];
-        }
-        out[(size_t)q * ix.n_local + i] = acc;
-    }
-}
-
-// Lut16SimdTables::compute_distances_batch (hashes/lut16_simd.rs:119-141 over
-// simd/dispatch.rs:259-295): u32 sum of u8 table entries, then sum * mult + bias * S.
-__global__ __launch_bounds__(256) void lut16_u8_batch_kernel(
-    const uint8_t *__restrict__ packed, const uint8_t *__restrict__ lut8, uint32_t S,
-    uint64_t n, float bias, float mult, float *__restrict__ out) {
-    extern __shared__ uint8_t s_lut8[];  // [S*16]
-    for (uint32_t e = threadIdx.x; e < S * 16; e += blockDim.x) s_lut8[e] = lut8[e];
-    __syncthreads();
-    const uint32_t bpp = (S + 1) / 2;
-    const float bias_total = bias * (float)S;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-         i += (uint64_t)gridDim.x * blockDim.x) {
-        const uint8_t *row = packed + i * bpp;
-        uint32_t sum = 0, sub = 0;
-        for (uint32_t b = 0; b < bpp; ++b) {
-            const uint32_t byte = row[b];
-            if (sub < S) { sum += s_lut8[sub * 16 + (byte & 15u)]; ++sub; }
-            if (sub < S) { sum += s_lut8[sub * 16 + (byte >> 4)]; ++sub; }
-        }
-        const float r = (float)sum * mult;
-        out[i] = r + bias_total;
-    }
-}
-
-// Lut16SimdTables::from_float_tables (hashes/lut16_simd.rs:39-90): global min / max of the S x 16
-// entries (f32::min / f32::max: a NaN operand is ignored), range = max - min, scale = 255 / range
-// (1 when range < 1e-10), lut8 = round((v - min) * scale) as u8 (round half away from zero; `as u8`
-// saturates and maps NaN to 0), bias = min, multiplier = 1 / scale (1 in the degenerate case).
-__global__ __launch_bounds__(256) void lut16_quantize_kernel(const float *__restrict__ tables, uint32_t S,
-                                                             uint8_t *__restrict__ lut8,
-                                                             float *__restrict__ bias_mult) {
-    __shared__ float s_min[4], s_max[4];
-    const uint32_t tid = threadIdx.x, n = S * 16;
-    float mn = 3.40282347e+38f, mx = -3.40282347e+38f;   // f32::MAX / f32::MIN
-    for (uint32_t i = tid; i < n; i += 256) {
-        const float v = tables[i];
-        mn = fminf(mn, v);
-        mx = fmaxf(mx, v);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        mn = fminf(mn, __shfl_xor(mn, o));
-        mx = fmaxf(mx, __shfl_xor(mx, o));
-    }
-    if ((tid & 63u) == 0) {
-        s_min[tid >> 6] = mn;
-        s_max[tid >> 6] = mx;
-    }
-    __syncthreads();
-    mn = fminf(fminf(s_min[0], s_min[1]), fminf(s_min[2], s_min[3]));
-    mx = fmaxf(fmaxf(s_max[0], s_max[1]), fmaxf(s_max[2], s_max[3]));
-    const float range = mx - mn;
-    const bool degenerate = range < 1e-10f;
-    const float scale = degenerate ? 1.0f : 255.0f / range;
-    for (uint32_t i = tid; i < n; i += 256) {
-        const float r = roundf((tables[i] - mn) * scale);
-        lut8[i] = !(r > 0.0f) ? (uint8_t)0 : (r >= 255.0f ? (uint8_t)255 : (uint8_t)r);
-    }
-    if (tid == 0) {
-        bias_mult[0] = mn;
-        bias_mult[1] = degenerate ? 1.0f : 1.0f / scale;
-    }
-}
-
-// Codebook::encode (hashes/codebook.rs:82-95): per subspace argmin over K with strict '<'.
-__global__ __launch_bounds__(256) void encode_kernel(
-    const float *__restrict__ codebook, uint32_t S, uint32_t K, uint32_t dsub,
-    const float *__restrict__ rows, uint64_t n, uint32_t stride,
-    const float *__restrict__ centers, const uint32_t *__restrict__ leaf_of_row,
-    uint8_t *__restrict__ out) {
-    const uint64_t total = n * S;
-    for (uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total;
-         e += (uint64_t)gridDim.x * blockDim.x) {
-        const uint64_t i = e / S;
-        const uint32_t s = (uint32_t)(e - i * S);
-        const float *x = rows + i * stride + s * dsub;
-        const float *cen = centers ? centers + (size_t)leaf_of_row[i] * (S * dsub) + s * dsub
-                                   : nullptr;
-        float best = __builtin_inff();
-        uint32_t bi = 0;
-        for (uint32_t c = 0; c < K; ++c) {
-            const float *cb = codebook + ((size_t)s * K + c) * dsub;
-            float d = 0.0f;
-            for (uint32_t j = 0; j < dsub; ++j) {
-                float xv = x[j];
-                if (cen) xv = xv - cen[j];
-                const float t = xv - cb[j];
-                d = d + t * t;
-            }
-            if (d < best) {
-                best = d;
-                bi = c;
-            }
-        }
-        out[e] = (uint8_t)bi;
-    }
-}
-
-// =====================================================================================
 // launchers
 // =====================================================================================
 static int launch_partition_stage(const TxhIndexDev &ix, const TxhWork &w, hipStream_t st) {
     if (ix.ah_mode) {
-        SCANN_TRY(launch(ah_tokens_kernel, dim3(ceil_div_u32(w.nq, 256)), dim3(256), 0, st, w.nq,
-                         ix.leaf_gsize, ix.leaf_off, w.st, w.tokens, w.token_dists, w.vbase, w.sbase));
-        return SCANN_HIP_OK;
+        return launch_ah_tokens(ix, w, st);
     }
-    // queries per single-wave block: fewer when the grid would not fill the chip (one thread per
-    // centroid, so a block's work is 64 centroids x QT queries)
-    const uint64_t waves16 = (uint64_t)ceil_div_u32(ix.L, 64) * ceil_div_u32(w.nq, 16);
-    SCANN_TRY((with_value<16, 4>(waves16 >= 8192 ? 16 : 4, [&](auto qt) {
-        const size_t lds1 = (size_t)qt() * ix.dim * sizeof(float);
-        return launch(centroid_scores_kernel<qt()>, dim3(ceil_div_u32(ix.L, 64), ceil_div_u32(w.nq, qt())), dim3(64), lds1,
-                      st, ix.centers, ix.L, ix.dim, w.queries, w.nq, w.q_stride, w.cdist);
-    })));
+    SCANN_TRY(launch_centroid_scores(ix, w, st));
     const uint32_t n2 = next_pow2_u32(ix.L);
     // select path when P is small against L: rank-select the P-th key, sort P keys instead of L
     const uint32_t p2 = (w.P * 4u <= n2) ? next_pow2_u32(std::max(1u, w.P)) : 0u;
@@ -5025,112 +2857,97 @@ int txh_launch_partition_only(const TxhIndexDev &ix, const TxhWork &w, hipStream
     return launch_partition_stage(ix, w, st);
 }
 
-template <typename C>
-static int launch_scan_stages(const TxhIndexDev &ix, const TxhWork &w, hipStream_t st,
-                              hipEvent_t ev0, hipEvent_t ev1) {
-    const int cus = num_cus();
-    if constexpr (C::BITS == 4) {
-        if (w.sample_mfma) {   // flat hasher in front of an MFMA prefilter (K5d / K5e): plain tables, integer sample, tail bound
+static size_t threshold_select_lds(uint32_t scap) {
+    const SelCfg tcfg = sel_cfg(scap);
+    return ((size_t)((scap + 3u) & ~3u) + tcfg.bins + tcfg.list) * 4 + 48 * 8;
+}
+
+// K5a + K5b / K5c: the f32 sample of every query's stream and the filter bound from it
+static int launch_gather_bound(const TxhIndexDev &ix, const TxhWork &w, hipStream_t st) {
+    if (!w.no_threshold) {
+        SCANN_TRY(with_codec(ix, [&](auto codec) -> int {
+            using C = decltype(codec);
+            SampleArgs sa;
+            sa.pair_off = w.pair_off; sa.stile_off = w.stile_off; sa.pair_q = w.pair_q;
+            sa.pair_sbase = w.pair_sbase; sa.counters = w.counters; sa.lutq = w.lutq; sa.samp = w.samp;
+            sa.scap = w.scap; sa.st = w.st; sa.qpt = w.sqpt; sa.allow = w.allow; sa.allow_bits = w.allow_bits;
+            const size_t lds_smp = (size_t)2 * C::LUT4 * 16 + 16;
+            return launch(adc_sample_kernel<C>, dim3((uint32_t)num_cus() * 8u), dim3(kScanThreads), lds_smp, st, ix, sa);
+        }));
+    }
+    const uint32_t nt = w.scap > 8192 ? kSelectThreads : 256u;
+    // (without thr_ties the bound is on the distance alone: whole tie groups pass)
+    if (w.thr_tail) {
+        SCANN_TRY(launch(threshold_tail_kernel, dim3(w.nq), dim3(kThrTailThreads), 0, st, w.P, w.m, w.st, w.sbase,
+                         w.samp, w.scap, w.slot_of, w.thr, w.pair_thr, w.thr_ties ? w.vbase : nullptr));
+    } else {
+        SCANN_TRY(launch(threshold_select_kernel, dim3(w.nq), dim3(nt), threshold_select_lds(w.scap), st, w.P, w.m, w.st,
+                         (int)w.no_threshold, w.sbase, w.samp, w.scap, w.slot_of, w.thr, w.pair_thr,
+                         w.thr_ties ? w.vbase : nullptr));
+    }
+    return SCANN_HIP_OK;
+}
+
+// thr = MAX for every query: select_rerank takes the k smallest of the whole stream
+static int launch_open_bound(const TxhWork &w, hipStream_t st) {
+    SCANN_TRY(launch(threshold_select_kernel, dim3(w.nq), dim3(256), threshold_select_lds(w.scap), st, w.P, w.m, w.st, 1,
+                     w.sbase, w.samp, w.scap, w.slot_of, w.thr, w.pair_thr, w.vbase));
+    return SCANN_HIP_OK;
+}
+
+// K6 / K6b: the f32 gather scan or its resident-table form
+static int launch_gather_scan(const TxhIndexDev &ix, const TxhWork &w, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1) {
+    return with_codec(ix, [&](auto codec) -> int {
+        using C = decltype(codec);
+        const int cus = num_cus();
+        ScanArgs a;
+        a.pair_off = w.pair_off; a.tile_off = w.tile_off; a.pair_q = w.pair_q;
+        a.pair_vbase = w.pair_vbase; a.counters = w.counters; a.lutq = w.lutq; a.pair_thr = w.pair_thr;
+        a.cand_cnt = w.cand_cnt; a.cand = w.cand; a.cap = w.cap; a.qpt = w.qpt; a.allow = w.allow; a.allow_bits = w.allow_bits;
+        if (ev0) SCANN_HIP_CHECK(hipEventRecord(ev0, st));
+        const uint32_t wgs = (uint32_t)cus * 8u;
+        a.res_cl = w.res_cl;
+        if constexpr (C::BITS == 4 && C::S <= 32) {
+            if (w.scan == TxhScan::Resident) {
+                SCANN_TRY(launch(adc_scan_res_kernel<C>, dim3((uint32_t)cus * 4u), dim3(kResThreads),
+                                 res_lds_bytes<C>(), st, ix, a));
+                if (ev1) SCANN_HIP_CHECK(hipEventRecord(ev1, st));
+                return SCANN_HIP_OK;
+            }
+        }
+        SCANN_TRY(launch(adc_scan_kernel<C>, dim3(wgs), dim3(kScanThreads), scan_lds_bytes<C>(), st, ix, a));
+        if (ev1) SCANN_HIP_CHECK(hipEventRecord(ev1, st));
+        return SCANN_HIP_OK;
+    });
+}
+
+// K5d + K5e: flat hasher in front of an MFMA prefilter: plain tables, integer sample, tail bound
+static int launch_sample_mfma_bound(const TxhIndexDev &ix, const TxhWork &w, hipStream_t st) {
+    return with_codec(ix, [&](auto codec) -> int {
+        using C = decltype(codec);
+        if constexpr (C::BITS == 4) {
             Lut8Meta *meta = reinterpret_cast<Lut8Meta *>(w.lut8_meta);
-            SCANN_TRY(launch(lut8_build_kernel, dim3(w.max_quads), dim3(256), 0, st, (uint32_t)C::S, w.lutq, w.counters,
-                             w.lut8, meta, w.pair_q, w.pair_thr, w.mfma_thr1, -1));
+            SCANN_TRY(launch_lut8_build(w, (uint32_t)C::S, -1, st));
             SampleMfmaArgs sm;
             sm.pair_off = w.pair_off; sm.pair_q = w.pair_q; sm.pair_sbase = w.pair_sbase; sm.lut8 = w.lut8;
             sm.samp16 = reinterpret_cast<uint16_t *>(w.samp); sm.scap = w.scap; sm.st = w.st;
             sm.allow = w.allow; sm.allow_bits = w.allow_bits;
-            SCANN_TRY(launch(adc_sample_mfma_kernel<C::S>, dim3((uint32_t)cus * 4u), dim3(256), 0, st, ix, sm));
+            SCANN_TRY(launch(adc_sample_mfma_kernel<C::S>, dim3((uint32_t)num_cus() * 4u), dim3(256), 0, st, ix, sm));
             Tail16Args ta;
             ta.P = w.P; ta.m = w.m; ta.st = w.st; ta.scap = w.scap; ta.sbase = w.sbase; ta.slot_of = w.slot_of;
             ta.tokens = w.tokens; ta.vbase = w.vbase; ta.samp16 = sm.samp16; ta.lutq = w.lutq; ta.meta = meta;
             ta.thr = w.thr; ta.pair_thr = w.pair_thr;
             SCANN_TRY(launch(threshold_tail16_kernel<C::S>, dim3(w.nq), dim3(kThrTailThreads), 0, st, ix, ta));
         }
-    }
-    if (!w.no_threshold && !w.sample_mfma) {
-        SampleArgs sa;
-        sa.pair_off = w.pair_off; sa.stile_off = w.stile_off; sa.pair_q = w.pair_q;
-        sa.pair_sbase = w.pair_sbase; sa.counters = w.counters; sa.lutq = w.lutq; sa.samp = w.samp;
-        sa.scap = w.scap; sa.st = w.st; sa.qpt = w.sqpt; sa.allow = w.allow; sa.allow_bits = w.allow_bits;
-        const size_t lds_smp = (size_t)2 * C::LUT4 * 16 + 16;
-        SCANN_TRY(launch(adc_sample_kernel<C>, dim3((uint32_t)cus * 8u), dim3(kScanThreads), lds_smp, st, ix, sa));
-    }
-    if (!w.sample_mfma) {
-        const SelCfg tcfg = sel_cfg(w.scap);
-        const size_t lds_thr = ((size_t)((w.scap + 3u) & ~3u) + tcfg.bins + tcfg.list) * 4 + 48 * 8;
-        const uint32_t nt = w.scap > 8192 ? kSelectThreads : 256u;
-        // (without thr_ties the bound is on the distance alone: whole tie groups pass)
-        if (w.thr_tail) {
-            SCANN_TRY(launch(threshold_tail_kernel, dim3(w.nq), dim3(kThrTailThreads), 0, st, w.P, w.m, w.st, w.sbase,
-                             w.samp, w.scap, w.slot_of, w.thr, w.pair_thr, w.thr_ties ? w.vbase : nullptr));
-        } else {
-            SCANN_TRY(launch(threshold_select_kernel, dim3(w.nq), dim3(nt), lds_thr, st, w.P, w.m, w.st,
-                             (int)w.no_threshold, w.sbase, w.samp, w.scap, w.slot_of, w.thr, w.pair_thr,
-                             w.thr_ties ? w.vbase : nullptr));
-        }
-    }
-    if constexpr (C::BITS == 4) {
-        if (txh_scan_is_mfma(w.scan)) {
-            SCANN_TRY(launch(lut8_build_kernel, dim3(w.max_quads), dim3(256), 0, st, (uint32_t)C::S, w.lutq,
-                             w.counters, w.lut8, reinterpret_cast<Lut8Meta *>(w.lut8_meta), w.pair_q, w.pair_thr,
-                             w.mfma_thr1, w.scan == TxhScan::Smfmac ? 1 : 0));
-            const bool codes_in_list = w.codes_in_list;
-            MfmaArgs ma;
-            ma.thr1 = w.mfma_thr1;
-            ma.pair_off = w.pair_off; ma.tile_off = w.tile_off; ma.pair_q = w.pair_q; ma.pair_vbase = w.pair_vbase;
-            ma.counters = w.counters; ma.lut8 = w.lut8; ma.meta = reinterpret_cast<const Lut8Meta *>(w.lut8_meta);
-            ma.pair_thr = w.pair_thr; ma.cand32_cnt = w.cand32_cnt; ma.cand32 = w.cand32; ma.cand32_codes = codes_in_list ? w.cand32_codes : nullptr; ma.cap32 = w.cap32;
-            ma.allow = w.allow; ma.allow_bits = w.allow_bits;
-            if (ev0) SCANN_HIP_CHECK(hipEventRecord(ev0, st));
-            const bool words = w.sp_words;
-            const dim3 mgrid((uint32_t)cus * 4u), mblock(kMfmaWaves * 64);   // 4 workgroups per CU (4 waves each)
-            void (*scan)(TxhIndexDev, MfmaArgs) =
-                w.scan == TxhScan::Mfma16   ? adc_mfma16_kernel<C::S>
-                : w.scan == TxhScan::Mfma32 ? adc_mfma_kernel<C::S>
-                : C::S <= 32                ? (words ? adc_smfmac_kernel<C::S, true> : adc_smfmac_kernel<C::S, false>)
-                                            : (words ? adc_smfmac_wide_kernel<C::S, true> : adc_smfmac_wide_kernel<C::S, false>);
-            SCANN_TRY(launch(scan, mgrid, mblock, 0, st, ix, ma));
-            if (ev1) SCANN_HIP_CHECK(hipEventRecord(ev1, st));
-            RefineArgs ra;
-            ra.P = w.P; ra.cap = w.cap; ra.cap32 = w.cap32; ra.tokens = w.tokens; ra.vbase = w.vbase;
-            ra.slot_of = w.slot_of; ra.lutq = w.lutq; ra.thr = w.thr; ra.cand32_cnt = w.cand32_cnt;
-            ra.cand32 = w.cand32; ra.cand32_codes = codes_in_list ? w.cand32_codes : nullptr; ra.cand_cnt = w.cand_cnt; ra.cand = w.cand; ra.counters = w.counters;
-            ra.allow = w.allow; ra.allow_bits = w.allow_bits;
-            ra.planes = (w.scan == TxhScan::Smfmac && ra.cand32_codes) ? 1 : 0;
-            const size_t lds_rf = w.P <= kRefineTablesMax ? (size_t)w.P * C::S * 16 * sizeof(float) : 16;
-            SCANN_TRY(launch(adc_refine_kernel<C>, dim3(w.nq), dim3(kRefineThreads), lds_rf, st, ix, ra));
-            return SCANN_HIP_OK;
-        }
-    }
-    ScanArgs a;
-    a.pair_off = w.pair_off; a.tile_off = w.tile_off; a.pair_q = w.pair_q;
-    a.pair_vbase = w.pair_vbase; a.counters = w.counters; a.lutq = w.lutq; a.pair_thr = w.pair_thr;
-    a.cand_cnt = w.cand_cnt; a.cand = w.cand; a.cap = w.cap; a.qpt = w.qpt; a.allow = w.allow; a.allow_bits = w.allow_bits;
-    if (ev0) SCANN_HIP_CHECK(hipEventRecord(ev0, st));
-    const uint32_t wgs = (uint32_t)cus * 8u;
-    a.res_cl = w.res_cl;
-    if constexpr (C::BITS == 4 && C::S <= 32) {
-        if (w.scan == TxhScan::Resident) {
-            SCANN_TRY(launch(adc_scan_res_kernel<C>, dim3((uint32_t)cus * 4u), dim3(kResThreads),
-                             res_lds_bytes<C>(), st, ix, a));
-            if (ev1) SCANN_HIP_CHECK(hipEventRecord(ev1, st));
-            return SCANN_HIP_OK;
-        }
-    }
-    SCANN_TRY(launch(adc_scan_kernel<C>, dim3(wgs), dim3(kScanThreads), scan_lds_bytes<C>(), st, ix, a));
-    if (ev1) SCANN_HIP_CHECK(hipEventRecord(ev1, st));
-    return SCANN_HIP_OK;
+        return SCANN_HIP_OK;
+    });
 }
 
 // SearchMode::Partitioned: dense key lists (no threshold), one exact-distance tile kernel.
 static int launch_exact_scan(const TxhIndexDev &ix, const TxhWork &w, hipStream_t st, hipEvent_t ev0,
                              hipEvent_t ev1) {
     const int cus = num_cus();
-    {   // thr = MAX for every query: select_rerank takes the k smallest of the whole stream
-        const SelCfg tcfg = sel_cfg(w.scap);
-        const size_t lds_thr = ((size_t)((w.scap + 3u) & ~3u) + tcfg.bins + tcfg.list) * 4 + 48 * 8;
-        SCANN_TRY(launch(threshold_select_kernel, dim3(w.nq), dim3(256), lds_thr, st, w.P, w.m, w.st, 1, w.sbase,
-                         w.samp, w.scap, w.slot_of, w.thr, w.pair_thr, w.vbase));
-    }
+    SCANN_TRY(launch_open_bound(w, st));
     SCANN_TRY(launch(stream_counts_kernel, dim3(ceil_div_u32(w.nq, 256)), dim3(256), 0, st, w.nq, w.P, w.vbase,
                      w.cand_cnt));
     ExactScanArgs a;
@@ -5144,6 +2961,83 @@ static int launch_exact_scan(const TxhIndexDev &ix, const TxhWork &w, hipStream_
         return launch(leaf_exact_scan_kernel<m()>, grid, block, lds, st, ix, a);
     }));
     if (ev1) SCANN_HIP_CHECK(hipEventRecord(ev1, st));
+    return SCANN_HIP_OK;
+}
+
+// the candidates may leave the select in any order: the final stage orders them by 96-bit keys (K9b)
+static bool select_unsorted(const TxhWork &w, bool local_only) {
+    return w.exact_reorder && !local_only && !w.need_sorted_cands && w.k <= kTopkMaxK;
+}
+
+static int launch_select(const TxhIndexDev &ix, const TxhWork &w, bool local_only, hipStream_t st) {
+    SelectArgs s;
+    s.P = w.P; s.m = w.m; s.k = w.k; s.cap = w.cap;
+    s.exact_reorder = w.exact_reorder; s.local_only = local_only ? 1 : 0;
+    const bool unsorted = select_unsorted(w, local_only);
+    s.unsorted = unsorted ? 1 : 0;
+    s.queries = w.queries; s.q_stride = w.q_stride; s.tokens = w.tokens; s.vbase = w.vbase;
+    s.thr = w.thr; s.cand_row = w.cand_row;
+    s.cand_cnt = w.cand_cnt; s.cand = w.cand; s.counters = w.counters; s.cand_key = w.cand_key;
+    s.cand_idx = w.cand_idx; s.cand_dist = w.cand_dist; s.cand_exact = w.cand_exact;
+    s.cand_count = w.cand_count; s.out_idx = w.out_idx; s.out_dist = w.out_dist;
+    s.out_count = w.out_count;
+    // LDS key array: the candidate capacity rounded up to a power of two (bitonic path), at
+    // most kSortCap; small lists run with 256-thread blocks so several fit a CU
+    // (sorted path: room for the m keys that are kept -- a longer list is rank-selected straight from global
+    // memory first, so the bitonic sort runs over pow2(m) keys, not pow2(capacity): half the stages' work at
+    // capacity ~1.4 m)
+    uint32_t lds_keys = std::min(kSortCap, next_pow2_u32(std::max(unsorted ? w.cap : std::min(w.cap, w.m), 64u)));
+    // unsorted selection of a long list: straight from the global list, 512-thread workgroups with ~30 KB of
+    // LDS (without select_direct: stage the keys as before)
+    const bool direct = unsorted && w.select_direct && lds_keys > 4096u;
+    s.direct = direct ? 1u : 0u;
+    s.sel_n = w.cap;
+    if (direct) lds_keys = 64;
+    s.lds_keys = lds_keys;
+    const SelCfg scfg = sel_cfg(direct ? w.cap : lds_keys);
+    const size_t lds_sel = (size_t)lds_keys * 8 + (size_t)(kSelectThreads / 64 + 4) * 4 +
+                           (size_t)scfg.bins * 4 + (size_t)scfg.list * 8 + 48 * 8 + 2 * kDecodeStage * 4;
+    const uint32_t sel_threads = direct ? 512u : (lds_keys <= 4096 ? 256u : kSelectThreads);
+    SCANN_TRY(launch(select_rerank_kernel, dim3(w.nq), dim3(sel_threads), lds_sel, st, ix, s));
+    return SCANN_HIP_OK;
+}
+
+static int launch_rerank(const TxhIndexDev &ix, const TxhWork &w, bool local_only, hipStream_t st) {
+    const bool unsorted = select_unsorted(w, local_only);
+    const size_t lds_rr = (size_t)ix.dim * 4;
+    // int8 row filter in front of the exact re-rank (K8b): single-GPU final stage, squared L2, lists long
+    // enough for the two extra kernels to pay
+    // (the local stage of a leaf-sharded search takes the same two kernels in their prefix form: ShortArgs::local_head;
+    // without local_prune: every local candidate re-ranked exactly, as before)
+    const bool i8_local = local_only && w.local_prune && w.exact_reorder && !w.need_sorted_cands && w.k <= kTopkMaxK &&
+                          w.m > 2 * kLocalHead;
+    const bool i8 = (unsorted || i8_local) && w.use_i8 && ix.rows8 && ix.measure == SCANN_HIP_SQUARED_L2 && (ix.dim & 15u) == 0;
+    if (i8) {
+        SCANN_TRY(launch_rerank_i8(ix, w, st));
+        ShortArgs sa;
+        sa.m = w.m; sa.k = w.k; sa.queries = w.queries; sa.q_stride = w.q_stride; sa.lb = w.rr_lb; sa.ub = w.rr_ub;
+        sa.cand_row = w.cand_row; sa.cand_idx = w.cand_idx; sa.cand_key = w.cand_key; sa.cand_count = w.cand_count;
+        sa.cand_exact = w.cand_exact; sa.out_idx = w.out_idx; sa.out_dist = w.out_dist; sa.out_count = w.out_count;
+        sa.local_head = local_only ? kLocalHead : 0u;
+        const size_t lds_sh = (size_t)ix.dim * 4;
+        SCANN_TRY(launch(rerank_short_kernel, dim3(w.nq), dim3(256), lds_sh, st, ix, sa));
+    } else {
+        SCANN_TRY(launch(rerank_kernel, dim3(ceil_div_u32(w.m, 32), w.nq), dim3(256), lds_rr, st, ix,
+                         w.queries, w.q_stride, w.m, w.cand_row, w.cand_count, w.cand_exact));
+    }
+    return SCANN_HIP_OK;
+}
+
+static int launch_final(const TxhWork &w, hipStream_t st) {
+    if (select_unsorted(w, false)) {
+        return with_value<256, 1024>(w.m <= 2048 ? 256 : 1024, [&](auto nt) {
+            return launch(final_topk_kernel<nt()>, dim3(w.nq), dim3(nt()), 0, st, w.m, w.k, w.cand_count, w.cand_idx,
+                          w.cand_key, w.cand_exact, w.out_idx, w.out_dist, w.out_count);
+        });
+    }
+    const size_t lds_fs = (size_t)next_pow2_u32(std::max(1u, w.m)) * 8;
+    SCANN_TRY(launch(final_sort_kernel, dim3(w.nq), dim3(kSelectThreads), lds_fs, st, w.m, w.k,
+                     w.cand_count, w.cand_idx, w.cand_exact, w.out_idx, w.out_dist, w.out_count));
     return SCANN_HIP_OK;
 }
 
@@ -6014,8 +3908,7 @@ static int launch_search_small(const TxhIndexDev &ix, const TxhWork &w, hipStrea
         return SCANN_HIP_OK;
     }
     if (ix.ah_mode) {
-        SCANN_TRY(launch(ah_tokens_kernel, dim3(ceil_div_u32(w.nq, 256)), dim3(256), 0, st, w.nq,
-                         ix.leaf_gsize, ix.leaf_off, w.st, w.tokens, w.token_dists, w.vbase, w.sbase));
+        SCANN_TRY(launch_ah_tokens(ix, w, st));
     } else {   // (lds_sel: + the leaf size tables and the query, the kernel's inline mode)
         SCANN_TRY(launch(select_leaves_kernel, dim3(w.nq), dim3(kSelectThreads), lds_sel, st, w.cdist, ix.L, f.n_pow2, w.P,
                          f.p_pow2, ix.leaf_gsize, ix.leaf_off, w.st, w.tokens, w.token_dists, w.vbase, w.sbase, ix.centers_t,
@@ -6034,138 +3927,48 @@ static int launch_search_small(const TxhIndexDev &ix, const TxhWork &w, hipStrea
     return SCANN_HIP_OK;
 }
 
+// The work lists follow the scan kernel's items.
+static WorkTiling work_tiling(const TxhIndexDev &ix, const TxhWork &w) {
+    switch (w.scan) {
+        case TxhScan::Exact: return {kExactRows, exact_quads_per_tile(ix.dim), 1u};
+        case TxhScan::Mfma16: return {kMfmaRange, 4u, 1u};
+        case TxhScan::Mfma32:
+        case TxhScan::Smfmac: return {kMfmaRange, 8u, 1u};
+        case TxhScan::Resident: return {kResThreads * kScanPPT, kResQuads, w.res_cl};
+        default: return {scan_tile_points(ix), w.qpt, 1u};
+    }
+}
+
 int txh_launch_search(const TxhIndexDev &ix, const TxhWork &w, bool local_only, hipStream_t st,
                       hipEvent_t ev0, hipEvent_t ev1) {
     if (w.nq == 0) return SCANN_HIP_OK;
     if (w.pipeline != TxhPipeline::Staged && !local_only && !w.need_sorted_cands) return launch_search_small(ix, w, st, ev0, ev1);
-    const bool mfma = txh_scan_is_mfma(w.scan);
-    const uint32_t wl_tp = w.scan == TxhScan::Exact ? kExactRows : mfma ? kMfmaRange : w.scan == TxhScan::Resident ? kResThreads * kScanPPT : scan_tile_points(ix);
-    const uint32_t wl_qpt = w.scan == TxhScan::Exact ? exact_quads_per_tile(ix.dim) : w.scan == TxhScan::Mfma16 ? 4u : mfma ? 8u : w.scan == TxhScan::Resident ? kResQuads : w.qpt;
-    const uint32_t wl_cpt = w.scan == TxhScan::Resident ? w.res_cl : 1u;
+    // partition and work lists
+    const WorkTiling tiling = work_tiling(ix, w);
     if (ix.ah_mode && ix.L == 1 && w.P == 1) {
-        AhSetupArgs h;
-        h.nq = w.nq; h.max_slots = w.max_slots; h.st = w.st; h.tp = wl_tp; h.quads_per_tile = wl_qpt;
-        h.chunks_per_tile = wl_cpt; h.stp = scan_tile_points(ix); h.squads_per_tile = w.sqpt;
-        h.leaf_gsize = ix.leaf_gsize; h.leaf_off = ix.leaf_off; h.leaf_cnt = w.leaf_cnt; h.leaf_cursor = w.leaf_cursor;
-        h.counters = w.counters; h.cand_cnt = w.cand_cnt; h.cand32_cnt = mfma ? w.cand32_cnt : nullptr;
-        h.pair_q = w.pair_q; h.pair_leaf = w.pair_leaf; h.pair_vbase = w.pair_vbase; h.pair_sbase = w.pair_sbase;
-        h.slot_of = w.slot_of; h.tokens = w.tokens; h.vbase = w.vbase; h.sbase = w.sbase; h.pair_off = w.pair_off;
-        h.tile_off = w.tile_off; h.stile_off = w.stile_off; h.token_dists = w.token_dists;
-        SCANN_TRY(launch(ah_setup_kernel, dim3(1), dim3(1024), 0, st, h));
+        SCANN_TRY(launch_ah_setup(ix, w, tiling, st));
     } else {
-    {
-        const uint32_t work = std::max(std::max(ix.L, w.nq), w.max_slots);
-        SCANN_TRY(launch(txh_init_kernel, dim3(std::min(1024u, ceil_div_u32(work, 256))), dim3(256), 0, st,
-                         ix.L, w.nq, w.max_slots, w.leaf_cnt, w.leaf_cursor, w.counters, w.cand_cnt,
-                         mfma ? w.cand32_cnt : nullptr, w.pair_q));
-    }
-    SCANN_TRY(launch_partition_stage(ix, w, st));
-
-    const uint32_t npairs = w.nq * w.P;
-    SCANN_TRY(launch(worklist_count_kernel, dim3(ceil_div_u32(npairs, 256)), dim3(256), 0, st,
-                     npairs, ix.ah_mode, w.tokens, ix.leaf_off, w.leaf_cnt));
-    SCANN_TRY(launch(worklist_scan_kernel, dim3(1), dim3(1024), 0, st, ix.L, w.leaf_cnt,
-                     ix.leaf_off, wl_tp, wl_qpt, wl_cpt, scan_tile_points(ix), w.st,
-                     w.sqpt, w.pair_off, w.tile_off,
-                     w.stile_off, w.counters));
-    SCANN_TRY(launch(worklist_fill_kernel, dim3(ceil_div_u32(npairs, 256)), dim3(256), 0, st, w.nq,
-                     w.P, ix.ah_mode, w.tokens, w.vbase, w.sbase, ix.leaf_off, w.pair_off, w.leaf_cursor, w.pair_q,
-                     w.pair_leaf, w.pair_vbase, w.pair_sbase, w.slot_of));
+        SCANN_TRY(launch_work_init(ix, w, st));
+        SCANN_TRY(launch_partition_stage(ix, w, st));
+        SCANN_TRY(launch_work_lists(ix, w, tiling, st));
     }
     if (w.scan == TxhScan::Exact) {
         SCANN_TRY(launch_exact_scan(ix, w, st, ev0, ev1));
     } else {
-    const size_t lds_lut = (size_t)4 * ix.dim * sizeof(float);
-    SCANN_TRY(launch(lut_build_kernel, dim3(w.max_quads), dim3(256), lds_lut, st, ix, w.queries,
-                     w.q_stride, w.pair_q, w.pair_leaf, w.counters, w.lutq));
-
-    switch (ix.code_bits * 1000 + ix.S) {
-        case 4008: SCANN_TRY((launch_scan_stages<Codec<8, 4>>(ix, w, st, ev0, ev1))); break;
-        case 4016: SCANN_TRY((launch_scan_stages<Codec<16, 4>>(ix, w, st, ev0, ev1))); break;
-        case 4024: SCANN_TRY((launch_scan_stages<Codec<24, 4>>(ix, w, st, ev0, ev1))); break;
-        case 4032: SCANN_TRY((launch_scan_stages<Codec<32, 4>>(ix, w, st, ev0, ev1))); break;
-        case 4048: SCANN_TRY((launch_scan_stages<Codec<48, 4>>(ix, w, st, ev0, ev1))); break;
-        case 4064: SCANN_TRY((launch_scan_stages<Codec<64, 4>>(ix, w, st, ev0, ev1))); break;
-        case 8004: SCANN_TRY((launch_scan_stages<Codec<4, 8>>(ix, w, st, ev0, ev1))); break;
-        case 8008: SCANN_TRY((launch_scan_stages<Codec<8, 8>>(ix, w, st, ev0, ev1))); break;
-        case 8016: SCANN_TRY((launch_scan_stages<Codec<16, 8>>(ix, w, st, ev0, ev1))); break;
-        default:
-            return fail(SCANN_HIP_UNIMPLEMENTED,
-                        "num_subspaces must be 8,16,24,32,48,64 (num_codes <= 16) or 4,8,16 (num_codes <= 256)");
+        // tables, bound, scan
+        SCANN_TRY(launch_lut_build(ix, w, st));
+        SCANN_TRY(with_codec(ix, [](auto) { return (int)SCANN_HIP_OK; }));   // an unsupported code layout ends the call here
+        if (w.sample_mfma) SCANN_TRY(launch_sample_mfma_bound(ix, w, st));
+        else SCANN_TRY(launch_gather_bound(ix, w, st));
+        if (ix.code_bits == 4 && txh_scan_is_mfma(w.scan)) SCANN_TRY(launch_prefilter_refine(ix, w, st, ev0, ev1));
+        else SCANN_TRY(launch_gather_scan(ix, w, st, ev0, ev1));
     }
-    }
-
-    SelectArgs s;
-    s.P = w.P; s.m = w.m; s.k = w.k; s.cap = w.cap;
-    s.exact_reorder = w.exact_reorder; s.local_only = local_only ? 1 : 0;
-    const bool unsorted = w.exact_reorder && !local_only && !w.need_sorted_cands && w.k <= kTopkMaxK;
-    s.unsorted = unsorted ? 1 : 0;
-    s.queries = w.queries; s.q_stride = w.q_stride; s.tokens = w.tokens; s.vbase = w.vbase;
-    s.thr = w.thr; s.cand_row = w.cand_row;
-    s.cand_cnt = w.cand_cnt; s.cand = w.cand; s.counters = w.counters; s.cand_key = w.cand_key;
-    s.cand_idx = w.cand_idx; s.cand_dist = w.cand_dist; s.cand_exact = w.cand_exact;
-    s.cand_count = w.cand_count; s.out_idx = w.out_idx; s.out_dist = w.out_dist;
-    s.out_count = w.out_count;
-    // LDS key array: the candidate capacity rounded up to a power of two (bitonic path), at
-    // most kSortCap; small lists run with 256-thread blocks so several fit a CU
-    // (sorted path: room for the m keys that are kept -- a longer list is rank-selected straight from global
-    // memory first, so the bitonic sort runs over pow2(m) keys, not pow2(capacity): half the stages' work at
-    // capacity ~1.4 m)
-    uint32_t lds_keys = std::min(kSortCap, next_pow2_u32(std::max(unsorted ? w.cap : std::min(w.cap, w.m), 64u)));
-    // unsorted selection of a long list: straight from the global list, 512-thread workgroups with ~30 KB of
-    // LDS (without select_direct: stage the keys as before)
-    const bool direct = unsorted && w.select_direct && lds_keys > 4096u;
-    s.direct = direct ? 1u : 0u;
-    s.sel_n = w.cap;
-    if (direct) lds_keys = 64;
-    s.lds_keys = lds_keys;
-    const SelCfg scfg = sel_cfg(direct ? w.cap : lds_keys);
-    const size_t lds_sel = (size_t)lds_keys * 8 + (size_t)(kSelectThreads / 64 + 4) * 4 +
-                           (size_t)scfg.bins * 4 + (size_t)scfg.list * 8 + 48 * 8 + 2 * kDecodeStage * 4;
-    const uint32_t sel_threads = direct ? 512u : (lds_keys <= 4096 ? 256u : kSelectThreads);
-    SCANN_TRY(launch(select_rerank_kernel, dim3(w.nq), dim3(sel_threads), lds_sel, st, ix, s));
+    // select, re-rank, final
+    SCANN_TRY(launch_select(ix, w, local_only, st));
     if (!w.exact_reorder) return SCANN_HIP_OK;
-    const size_t lds_rr = (size_t)ix.dim * 4;
-    // int8 row filter in front of the exact re-rank (K8b): single-GPU final stage, squared L2, lists long
-    // enough for the two extra kernels to pay
-    // (the local stage of a leaf-sharded search takes the same two kernels in their prefix form: ShortArgs::local_head;
-    // without local_prune: every local candidate re-ranked exactly, as before)
-    const bool i8_local = local_only && w.local_prune && w.exact_reorder && !w.need_sorted_cands && w.k <= kTopkMaxK &&
-                          w.m > 2 * kLocalHead;
-    const bool i8 = (unsorted || i8_local) && w.use_i8 && ix.rows8 && ix.measure == SCANN_HIP_SQUARED_L2 && (ix.dim & 15u) == 0;
-    if (i8) {
-        I8RerankArgs ia;
-        ia.rows8 = ix.rows8; ia.meta = reinterpret_cast<const float2 *>(ix.rows8_meta); ia.queries = w.queries;
-        ia.q_stride = w.q_stride; ia.m = w.m; ia.cand_row = w.cand_row; ia.cand_count = w.cand_count;
-        ia.lb = w.rr_lb; ia.ub = w.rr_ub;
-        ia.uni_scale = ix.rows8_scale; ia.uni_E = ix.rows8_emax;
-        // 1: FP8 rows; int8 rows with 2: one scale for all rows, 0: a scale per row
-        SCANN_TRY((with_value<1, 2, 0>(ix.rows8_fmt == 1 ? 1 : ix.rows8_uniform ? 2 : 0, [&](auto v) {
-            return launch((rerank_i8_kernel<v() == 1 ? 1 : 0, v() == 2>), dim3(ceil_div_u32(w.m, kI8PerBlock), w.nq),
-                          dim3(256), lds_rr, st, ix.dim, ia);
-        })));
-        ShortArgs sa;
-        sa.m = w.m; sa.k = w.k; sa.queries = w.queries; sa.q_stride = w.q_stride; sa.lb = w.rr_lb; sa.ub = w.rr_ub;
-        sa.cand_row = w.cand_row; sa.cand_idx = w.cand_idx; sa.cand_key = w.cand_key; sa.cand_count = w.cand_count;
-        sa.cand_exact = w.cand_exact; sa.out_idx = w.out_idx; sa.out_dist = w.out_dist; sa.out_count = w.out_count;
-        sa.local_head = local_only ? kLocalHead : 0u;
-        const size_t lds_sh = (size_t)ix.dim * 4;
-        SCANN_TRY(launch(rerank_short_kernel, dim3(w.nq), dim3(256), lds_sh, st, ix, sa));
-    } else {
-        SCANN_TRY(launch(rerank_kernel, dim3(ceil_div_u32(w.m, 32), w.nq), dim3(256), lds_rr, st, ix,
-                         w.queries, w.q_stride, w.m, w.cand_row, w.cand_count, w.cand_exact));
-    }
+    SCANN_TRY(launch_rerank(ix, w, local_only, st));
     if (local_only) return SCANN_HIP_OK;
-    if (unsorted) {
-        return with_value<256, 1024>(w.m <= 2048 ? 256 : 1024, [&](auto nt) {
-            return launch(final_topk_kernel<nt()>, dim3(w.nq), dim3(nt()), 0, st, w.m, w.k, w.cand_count, w.cand_idx,
-                          w.cand_key, w.cand_exact, w.out_idx, w.out_dist, w.out_count);
-        });
-    }
-    const size_t lds_fs = (size_t)next_pow2_u32(std::max(1u, w.m)) * 8;
-    SCANN_TRY(launch(final_sort_kernel, dim3(w.nq), dim3(kSelectThreads), lds_fs, st, w.m, w.k,
-                     w.cand_count, w.cand_idx, w.cand_exact, w.out_idx, w.out_dist, w.out_count));
-    return SCANN_HIP_OK;
+    return launch_final(w, st);
 }
 
 // Per-destination blocks for the all_to_all exchange: rank d merges the queries
@@ -6224,114 +4027,6 @@ int txh_launch_merge(uint32_t world, uint32_t nq, uint32_t m_local, uint32_t m, 
     SCANN_TRY(launch(merge_kernel, dim3(nq), dim3(kSelectThreads), lds, st, world, nq, m_local, m, k, m2,
                      rank_stride_bytes, d_keys, d_idx, d_exact, d_count, d_out_idx, d_out_dist,
                      d_out_count, d_status, d_qoff));
-    return SCANN_HIP_OK;
-}
-
-int txh_launch_lut_from_query(const TxhIndexDev &ix, const float *d_queries, uint32_t nq,
-                              uint32_t q_stride, const uint32_t *d_leaf_for_query,
-                              float *d_out_lut, hipStream_t st) {
-    if (nq == 0) return SCANN_HIP_OK;
-    const size_t lds = (size_t)ix.dim * sizeof(float);
-    SCANN_TRY(launch(lut_from_query_kernel, dim3(nq), dim3(256), lds, st, ix, d_queries, q_stride,
-                     d_leaf_for_query, d_out_lut));
-    return SCANN_HIP_OK;
-}
-
-int txh_launch_adc_distances(const TxhIndexDev &ix, const float *d_luts, uint32_t nq, float *d_out,
-                             hipStream_t st) {
-    if (nq == 0 || ix.n_local == 0) return SCANN_HIP_OK;
-    const uint32_t gx = (uint32_t)std::min<uint64_t>(ceil_div_u64(ix.n_local, 256), 4096);
-    dim3 grid(gx, nq);
-    const size_t lds = (size_t)ix.S * ix.K * sizeof(float);
-    SCANN_TRY(launch(adc_distances_kernel, grid, dim3(256), lds, st, ix, d_luts, d_out));
-    return SCANN_HIP_OK;
-}
-
-int launch_lut16_u8_batch(const uint8_t *d_packed, const uint8_t *d_lut8, uint32_t S, uint64_t n,
-                          float bias, float mult, float *d_out, hipStream_t st) {
-    if (n == 0) return SCANN_HIP_OK;
-    const uint32_t gx = (uint32_t)std::min<uint64_t>(ceil_div_u64(n, 256), 8192);
-    SCANN_TRY(launch(lut16_u8_batch_kernel, dim3(gx), dim3(256), (size_t)S * 16, st, d_packed, d_lut8,
-                     S, n, bias, mult, d_out));
-    return SCANN_HIP_OK;
-}
-
-__global__ __launch_bounds__(256) void transpose_centers_kernel(const float *__restrict__ centers, uint32_t L,
-                                                                uint32_t dim, uint32_t pitch, float *__restrict__ out) {
-    const uint64_t total = (uint64_t)dim * pitch;
-    for (uint64_t e = (uint64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (uint64_t)gridDim.x * 256) {
-        const uint32_t j = (uint32_t)(e / pitch), c = (uint32_t)(e - (uint64_t)j * pitch);
-        out[e] = c < L ? centers[(size_t)c * dim + j] : 0.0f;
-    }
-}
-
-int launch_transpose_centers(const float *d_centers, uint32_t L, uint32_t dim, uint32_t pitch, float *d_out,
-                             hipStream_t st) {
-    if (L == 0 || dim == 0) return SCANN_HIP_OK;
-    SCANN_TRY(launch(transpose_centers_kernel, dim3((uint32_t)std::min<uint64_t>(ceil_div_u64((uint64_t)dim * pitch, 256), 4096)),
-                     dim3(256), 0, st, d_centers, L, dim, pitch, d_out));
-    return SCANN_HIP_OK;
-}
-
-int launch_rows_fp8_build(const float *d_rows, uint64_t n, uint32_t dim, uint32_t stride, uint8_t *d_rows8,
-                          void *d_meta, uint32_t *d_mismatch, hipStream_t st) {
-    if (n == 0) return SCANN_HIP_OK;
-    SCANN_TRY(launch(rows_fp8_build_kernel, dim3((uint32_t)ceil_div_u64(n, 32)), dim3(256), 0, st, d_rows, n, dim,
-                     stride, d_rows8, reinterpret_cast<float2 *>(d_meta), d_mismatch));
-    return SCANN_HIP_OK;
-}
-
-int launch_fp8_quantize(const float *d_values, uint64_t n, float scale, int format, uint8_t *d_out, hipStream_t st) {
-    if (n == 0) return SCANN_HIP_OK;
-    SCANN_TRY(launch(fp8_quantize_kernel, dim3((uint32_t)std::min<uint64_t>(ceil_div_u64(n, 256), 65535)), dim3(256), 0,
-                     st, d_values, n, scale, format, d_out));
-    return SCANN_HIP_OK;
-}
-
-int launch_fp8_dequantize(const uint8_t *d_bits, uint64_t n, float scale, int format, float *d_out, hipStream_t st) {
-    if (n == 0) return SCANN_HIP_OK;
-    SCANN_TRY(launch(fp8_dequantize_kernel, dim3((uint32_t)std::min<uint64_t>(ceil_div_u64(n, 256), 65535)), dim3(256),
-                     0, st, d_bits, n, scale, format, d_out));
-    return SCANN_HIP_OK;
-}
-
-int launch_fp8_one_to_many(const float *d_query, uint32_t dim, const uint8_t *d_db, uint64_t stride, uint64_t n,
-                           int dot, float *d_out, hipStream_t st) {
-    if (n == 0) return SCANN_HIP_OK;
-    const size_t lds = (size_t)dim * sizeof(float);
-    SCANN_TRY(launch(fp8_one_to_many_kernel, dim3((uint32_t)std::min<uint64_t>(ceil_div_u64(n, 256), 65535)),
-                     dim3(256), lds, st, d_query, dim, d_db, stride, n, dot, d_out));
-    return SCANN_HIP_OK;
-}
-
-int launch_rows_i8_build(const float *d_rows, uint64_t n, uint32_t dim, uint32_t stride, int8_t *d_rows8,
-                         void *d_meta, hipStream_t st, float uni_scale) {
-    if (n == 0) return SCANN_HIP_OK;
-    SCANN_TRY(launch(rows_i8_build_kernel, dim3((uint32_t)ceil_div_u64(n, 32)), dim3(256), 0, st, d_rows, n, dim,
-                     stride, d_rows8, reinterpret_cast<float2 *>(d_meta), uni_scale));
-    return SCANN_HIP_OK;
-}
-
-int launch_lut16_quantize(const float *d_tables, uint32_t S, uint8_t *d_lut8, float *d_bias_mult,
-                          hipStream_t st) {
-    if (S == 0) return SCANN_HIP_OK;
-    SCANN_TRY(launch(lut16_quantize_kernel, dim3(1), dim3(256), 0, st, d_tables, S, d_lut8, d_bias_mult));
-    return SCANN_HIP_OK;
-}
-
-int launch_codes_sp_build(const uint32_t *d_codes, uint64_t n, uint32_t S, uint32_t *d_codes_sp, hipStream_t st) {
-    if (n == 0) return SCANN_HIP_OK;
-    SCANN_TRY(launch(codes_sp_build_kernel, dim3((uint32_t)ceil_div_u64(n, 256)), dim3(256), 0, st, d_codes, n, S, d_codes_sp));
-    return SCANN_HIP_OK;
-}
-
-int launch_encode(const float *d_codebook, uint32_t S, uint32_t K, uint32_t dsub, const float *d_rows,
-                  uint64_t n, uint32_t stride, const float *d_centers, const uint32_t *d_leaf_of_row,
-                  uint8_t *d_out, hipStream_t st) {
-    if (n == 0) return SCANN_HIP_OK;
-    const uint32_t gx = (uint32_t)std::min<uint64_t>(ceil_div_u64(n * S, 256), 16384);
-    SCANN_TRY(launch(encode_kernel, dim3(gx), dim3(256), 0, st, d_codebook, S, K, dsub, d_rows, n,
-                     stride, d_centers, d_leaf_of_row, d_out));
     return SCANN_HIP_OK;
 }
 

@@ -327,7 +327,7 @@ def adversarial_pq(family, n, dim, S, nq, seed):
 
 def pq_loose_bound_reached(codebook, codes, q, m):
     """True when the m-th smallest approximate distance of q puts the sparse prefilter's bound past half of the int8
-    sum range (txh.hip lut8_build_kernel: qmax > 128 S - 1 takes the coarser scale; the sampled bound is >= it)."""
+    sum range (txh_prefilter.hip lut8_build_kernel: qmax > 128 S - 1 takes the coarser scale; the sampled bound is >= it)."""
     t = pq_tables(codebook, q).astype(np.float64)
     S = t.shape[0]
     _, od = orc.ah_search(codebook, codes, q, m)

@@ -1,7 +1,7 @@
 """Flat hasher (AH) and tree (Tree-X-Hybrid) searches at every subspace count the scan kernels are compiled for, and on
 explicit codebooks built to hit the int8 prefilter's special cases, each compared with the ORACLE.
 
-txh.hip launch_scan_stages takes 4-bit codes at S = 8, 16, 24, 32, 48 and 64.  Every scan it can launch there is forced
+with_codec (txh_dev.h) takes 4-bit codes at S = 8, 16, 24, 32, 48 and 64.  Every scan it can launch there is forced
 through its knobs and asserted by the name scann_hip_index_last_kernel_ms reports:
 
     gather      SCANN_HIP_MFMA=0 SCANN_HIP_RESIDENT=0                adc_scan_kernel

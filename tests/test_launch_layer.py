@@ -36,10 +36,24 @@ def test_static_lds_sizes_are_not_typed_by_hand():
 
 
 def test_the_kernel_files_launch_through_launch_h():
-    for f in ("txh.hip", "bf.hip", "comm.hip", "crowd.hip"):
+    for f in ("txh.hip", "txh_partition.hip", "txh_prefilter.hip", "txh_rows.hip", "txh_blocks.hip",
+              "bf.hip", "comm.hip", "crowd.hip"):
         text = _read(os.path.join(CSRC, f))
         assert '#include "launch.h"' in text, f
         assert re.search(r"\blaunch\(", text), f
+
+
+def test_every_source_and_header_is_in_the_build():
+    """A source the build does not list is not compiled; a header it does not list neither triggers a rebuild nor
+    enters src_sha256.  txh.h is the tree search's interface: the units' internal headers stay behind it."""
+    from scann_rust_amd import build
+    files = os.listdir(CSRC)
+    assert sorted(f for f in files if f.endswith(".hip")) == sorted(build.SOURCES)
+    assert [f for f in files if f.endswith(".h") and f not in build.HEADERS] == []
+    assert re.findall(r'#include\s+"(txh_dev|txh_stages)\.h"', _read(os.path.join(CSRC, "txh.h"))) == []
+    for f in files:   # and only the tree-search units include them
+        if not f.startswith("txh"):
+            assert re.findall(r'#include\s+"(txh_dev|txh_stages)\.h"', _read(os.path.join(CSRC, f))) == [], f
 
 
 def test_launch_h_is_a_build_dependency():
