@@ -340,6 +340,16 @@ int scann_hip_index_last_device_status(scann_hip_index *index, void *hip_stream)
  * candidate, UINT64_MAX = no bound.  The CALLER synchronises hip_stream first; the copy itself is synchronous.
  * OutOfRange when the workspace has never held nq bounds. */
 int scann_hip_index_debug_filter_bounds(scann_hip_index *index, void *hip_stream, uint32_t nq, uint64_t *out_bounds);
+/* Debugging aid of the 8-bit row filter in front of the exact re-rank: copies what the last batched search enqueued on
+ * hip_stream (its workspace, else the primary one) left there for nq queries of pre_reorder_k = m: the ordered lower
+ * and upper bounds of every candidate's exact distance (out_lb, out_ub: [nq][m] u32, the order-preserving image of
+ * an f32), the candidates' re-rank rows (out_rows: [nq][m]) and their number per query (out_counts: [nq]; 0x80000000 for a
+ * query whose result rows the shortlist kernel wrote itself: its candidates are still in place, their number is not
+ * kept); entries at and beyond a query's count are unspecified.  The bounds are those of the last search that ran the filter.  The
+ * CALLER synchronises hip_stream first; the copies are synchronous.  OutOfRange when the workspace has never held a
+ * filtered re-rank of that size. */
+int scann_hip_index_debug_rerank_brackets(scann_hip_index *index, void *hip_stream, uint32_t nq, uint32_t m, uint32_t *out_lb,
+                                          uint32_t *out_ub, uint32_t *out_rows, uint32_t *out_counts);
 
 /* ---- crowding: at most per_crowd_limit results per attribute (restricts/crowding.rs) --------
  * CrowdingConstraint::apply (crowding.rs:81-104) behind every search, on the device.  For every handle kind

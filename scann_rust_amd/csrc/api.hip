@@ -1191,6 +1191,7 @@ static int plan_txh_search(const scann_hip_index *ix, uint32_t k, const scann_hi
     p.select_direct = kn.select_direct;
     // int8 re-rank filter: lists of a few hundred candidates and more
     p.use_i8 = t.rows8 && exact_reorder && m >= kn.rerank_i8_min && m > 4 * k;
+    p.i8_expand = kn.rerank_expand;
     p.local_prune = kn.local_prune;
     *out = p;
     return SCANN_HIP_OK;
@@ -1927,6 +1928,29 @@ int scann_hip_index_debug_filter_bounds(scann_hip_index *ix, void *hip_stream, u
     if (!ws->thr.p || ws->thr.bytes < (size_t)nq * 8)
         return fail(SCANN_HIP_OUT_OF_RANGE, "no batched search of that many queries has run in this workspace");
     SCANN_HIP_CHECK(hipMemcpy(out_bounds, ws->thr.p, (size_t)nq * 8, hipMemcpyDeviceToHost));
+    return SCANN_HIP_OK;
+}
+
+int scann_hip_index_debug_rerank_brackets(scann_hip_index *ix, void *hip_stream, uint32_t nq, uint32_t m, uint32_t *out_lb,
+                                          uint32_t *out_ub, uint32_t *out_rows, uint32_t *out_counts) {
+    if (!ix || ix->kind != KIND_TXH) return fail(SCANN_HIP_INVALID_ARGUMENT, "not a tree / hasher index");
+    if (nq && m && (!out_lb || !out_ub || !out_rows || !out_counts))
+        return fail(SCANN_HIP_INVALID_ARGUMENT, "an output is null");
+    SCANN_TRY(set_device(ix->ctx));
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    std::lock_guard<std::mutex> lock(ix->mu);
+    // the workspace bound to this stream (else the primary one)
+    const TxhWorkspace *ws = &ix->ws;
+    for (auto &d : ix->dslots)
+        if (d.used && d.key == st && d.ws) ws = d.ws;
+    const size_t list = (size_t)nq * m * 4;
+    if (!ws->rr_lb.p || !ws->rr_ub.p || !ws->cand_row.p || !ws->cand_count.p || ws->rr_lb.bytes < list ||
+        ws->rr_ub.bytes < list || ws->cand_row.bytes < list || ws->cand_count.bytes < (size_t)nq * 4)
+        return fail(SCANN_HIP_OUT_OF_RANGE, "no filtered re-rank of that many queries and candidates has run in this workspace");
+    SCANN_HIP_CHECK(hipMemcpy(out_lb, ws->rr_lb.p, list, hipMemcpyDeviceToHost));
+    SCANN_HIP_CHECK(hipMemcpy(out_ub, ws->rr_ub.p, list, hipMemcpyDeviceToHost));
+    SCANN_HIP_CHECK(hipMemcpy(out_rows, ws->cand_row.p, list, hipMemcpyDeviceToHost));
+    SCANN_HIP_CHECK(hipMemcpy(out_counts, ws->cand_count.p, (size_t)nq * 4, hipMemcpyDeviceToHost));
     return SCANN_HIP_OK;
 }
 

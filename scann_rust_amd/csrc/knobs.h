@@ -21,6 +21,9 @@
 // SCANN_HIP_MFMA                    0: f32 LUT scan only, 2 / 3: 32- / 16-pair integer-MFMA        every call
 //                                   prefilter whenever it applies
 // SCANN_HIP_RERANK_I8_MIN           shortest candidate list the int8 filter takes (512)            every call
+// SCANN_HIP_RERANK_EXPAND           0: the filter's brackets per dimension, (q - s x8)^2, finished  every call
+//                                   round by round (default: one epilogue a wave; one-scale int8
+//                                   store by the expanded square; per-row int8 store always as 0)
 // SCANN_HIP_SP_WORDS                0 / 1: lane-walk / word-parallel survivor flush of the sparse  every call
 //                                   prefilter (default: word-parallel on tree indexes)
 // SCANN_HIP_THR_TIES                0: filter bound on the distance alone (diagnostics)            every call
@@ -68,6 +71,7 @@ struct Knobs {
     uint32_t res_cl = 0;                  // 0 = from the work size
     int mfma = 1;
     uint32_t rerank_i8_min = 512;
+    bool rerank_expand = true;
     int sp_words = -1;                    // -1 = by index kind
     bool thr_ties = true;
     bool thr_tail = true;
@@ -115,6 +119,7 @@ inline Knobs read_knobs() {
         else if (is("SCANN_HIP_RES_CL")) k.res_cl = (uint32_t)std::max(1, atoi(v));
         else if (is("SCANN_HIP_MFMA")) k.mfma = atoi(v);
         else if (is("SCANN_HIP_RERANK_I8_MIN")) k.rerank_i8_min = (uint32_t)std::max(1, atoi(v));
+        else if (is("SCANN_HIP_RERANK_EXPAND")) k.rerank_expand = atoi(v) != 0;
         else if (is("SCANN_HIP_SP_WORDS")) k.sp_words = atoi(v) != 0 ? 1 : 0;
         else if (is("SCANN_HIP_THR_TIES")) k.thr_ties = atoi(v) != 0;
         else if (is("SCANN_HIP_THR_TAIL")) k.thr_tail = atoi(v) != 0;

@@ -161,7 +161,65 @@ struct I8RerankArgs {
 
 constexpr uint32_t kI8PerBlock = 256;   // candidates per block (8 lanes each, 8 rounds): amortises the query staging
 
-template <int FMT, bool UNI = false>   // 0 = int8 rows, 1 = FP8 (E4M3) rows
+// DPP exchanges inside a group of 8 lanes (no LDS crossbar): quad_perm [1,0,3,2], quad_perm [2,3,0,1], and
+// row_half_mirror (lane i <-> 7 - i, the other quad of the group)
+constexpr int kDppXor1 = 0xB1, kDppXor2 = 0x4E, kDppHalfMirror = 0x141;
+template <int CTRL> __device__ __forceinline__ int dpp_get(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, true); }
+template <int CTRL> __device__ __forceinline__ float dpp_get(float v) {
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));
+}
+
+// the sum over a group's 8 lanes, the same bits in each of them (every step adds the same two values in both lanes)
+__device__ __forceinline__ float sum8(float v) {
+    v += dpp_get<kDppXor1>(v);
+    v += dpp_get<kDppXor2>(v);
+    return v + dpp_get<kDppHalfMirror>(v);
+}
+
+// v[r] in every lane of a group -> lane l8 gets the group's sum of v[l8]: three exchange steps, each halving the
+// rounds a lane still carries (7 exchanges, against 8 x 3 for a full sum per round plus the moves)
+template <typename T> __device__ __forceinline__ T sum8_transposed(const T (&v)[8], uint32_t l8) {
+    const bool h4 = l8 & 4u, h2 = l8 & 2u, h1 = l8 & 1u;
+    T a[4], b[2];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) a[i] = (h4 ? v[i + 4] : v[i]) + dpp_get<kDppHalfMirror>(h4 ? v[i] : v[i + 4]);
+#pragma unroll
+    for (int i = 0; i < 2; ++i) b[i] = (h2 ? a[i + 2] : a[i]) + dpp_get<kDppXor2>(h2 ? a[i] : a[i + 2]);
+    return (h1 ? b[1] : b[0]) + dpp_get<kDppXor1>(h1 ? b[0] : b[1]);
+}
+
+// [L, U] around the exact f32 distance from d~ = acc, the row's error norm E and B, a bound on what the arithmetic
+// that produced acc lost beyond the (dim + 8) 1.2e-7 |acc| of two dim-term f32 sums (0 for the per-dimension form).
+//   | d_f32 - d~ | <= 2 sqrt(d~) E + E^2 (triangle inequality on the real values; d~ itself known to +- B, hence
+//   sqrt(max(acc, 0) + B)) + the f32 rounding of the sums + B + slack on the bound itself
+template <bool EXPANDED>   // false: acc is a sum of squares (>= 0 or NaN), B = 0
+__device__ __forceinline__ void store_bracket(const I8RerankArgs &a, size_t at, uint32_t dim, float acc, float E, float B) {
+    const float slack = EXPANDED ? (2.0f * sqrtf(fmaxf(acc, 0.0f) + B) * E + E * E) * 1.0001f +
+                                       fabsf(acc) * ((float)(dim + 8) * 1.2e-7f) + B + 1e-30f
+                                 : (2.0f * sqrtf(acc) * E + E * E) * 1.0001f + acc * ((float)(dim + 8) * 1.2e-7f) + 1e-30f;
+    float L = acc - slack, U = acc + slack;
+    // NaN or overflow anywhere (an infinite d~ would make L = inf - inf = NaN, which orders above +inf and
+    // drops the candidate): never filtered out, never a bound for others
+    if (!(slack < __builtin_inff()) || !(acc < __builtin_inff())) {
+        L = -__builtin_inff();
+        U = __builtin_inff();
+    }
+    a.lb[at] = f32_to_ordered(L);
+    a.ub[at] = f32_to_ordered(U);
+}
+
+// FMT: 0 = int8 rows, 1 = FP8 (E4M3) rows.
+// EX (SCANN_HIP_RERANK_EXPAND): 0 = d~ summed per dimension as (q - s x8)^2, one epilogue per round in lane 0 of each
+// group.  1, 2, 3 = one epilogue per wave: the 8 rounds leave their sums transposed, lane l8 of a group holding round
+// l8's, so that 64 lanes finish 64 candidates at once; int8 rows of the one-scale store by the expanded square
+//     d~ = Q2 - 2 s D + s^2 N,   N = sum x8^2 (exact, v_dot4 on the packed bytes),   D = sum q x8 (f32, one convert and
+// one FMA per dimension),   Q2 = |q|^2
+// with the lane's 16-dim slices of the query in registers for 2: one, 3: two 128-dim passes, 1: read from LDS (any dim);
+// FP8 rows keep the per-dimension sum (EX = 1).  int8 rows with a scale per row stay on EX = 0 whatever the knob says:
+// they go with rows of unequal magnitude, and on the clustered 10M x 128 set (candidates nearly equidistant,
+// |q|^2 >> d) the expanded form's cancellation term B lengthened the shortlists: rerank_short_kernel 130 -> 340 us at
+// m = 8192, 800 k -> 670 k QPS (profiles/rerank_expand_10m_perrow_expanded_*).
+template <int FMT, bool UNI = false, int EX = 0>
 __global__ __launch_bounds__(256) void rerank_i8_kernel(uint32_t dim, I8RerankArgs a) {
     typedef float v2f __attribute__((ext_vector_type(2)));
     extern __shared__ __attribute__((aligned(16))) float s_q[];   // [dim]
@@ -179,54 +237,134 @@ __global__ __launch_bounds__(256) void rerank_i8_kernel(uint32_t dim, I8RerankAr
         const uint32_t c = c0 + (uint32_t)it * 32u + (tid >> 3);
         row[it] = c < nsel ? a.cand_row[(size_t)q * a.m + c] : 0u;
     }
+    if constexpr (EX == 0) {
 #pragma unroll
-    for (int it = 0; it < R; ++it) {
-        const uint32_t c = c0 + (uint32_t)it * 32u + (tid >> 3);
-        const bool act = c < nsel;
-        const float2 me = UNI ? make_float2(a.uni_scale, a.uni_E) : a.meta[row[it]];
-        const int8_t *r8 = a.rows8 + (size_t)row[it] * dim;
-        float acc = 0.0f;
-        for (uint32_t j0 = l8 * 16u; j0 < dim; j0 += 128u) {   // 16 dims per lane per pass (dim % 16 == 0)
-            const uint4 v = *reinterpret_cast<const uint4 *>(r8 + j0);
-            const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-            if constexpr (FMT == 1) {
+        for (int it = 0; it < R; ++it) {
+            const uint32_t c = c0 + (uint32_t)it * 32u + (tid >> 3);
+            const bool act = c < nsel;
+            const float2 me = UNI ? make_float2(a.uni_scale, a.uni_E) : a.meta[row[it]];
+            const int8_t *r8 = a.rows8 + (size_t)row[it] * dim;
+            float acc = 0.0f;
+            for (uint32_t j0 = l8 * 16u; j0 < dim; j0 += 128u) {   // 16 dims per lane per pass (dim % 16 == 0)
+                const uint4 v = *reinterpret_cast<const uint4 *>(r8 + j0);
+                const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+                if constexpr (FMT == 1) {
 #pragma unroll
-                for (int wi = 0; wi < 4; ++wi) {
-                    const v2f lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[wi], false);
-                    const v2f hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[wi], true);
-                    const float xs[4] = {lo.x, lo.y, hi.x, hi.y};
+                    for (int wi = 0; wi < 4; ++wi) {
+                        const v2f lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[wi], false);
+                        const v2f hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[wi], true);
+                        const float xs[4] = {lo.x, lo.y, hi.x, hi.y};
 #pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        const float d = s_q[j0 + wi * 4 + i] - xs[i] * me.x;
+                        for (int i = 0; i < 4; ++i) {
+                            const float d = s_q[j0 + wi * 4 + i] - xs[i] * me.x;
+                            acc = fmaf(d, d, acc);
+                        }
+                    }
+                } else {
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) {
+                        const float x = me.x * (float)(int)(int8_t)(w[i >> 2] >> (8 * (i & 3)));
+                        const float d = s_q[j0 + i] - x;
                         acc = fmaf(d, d, acc);
                     }
                 }
-            } else {
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    const float x = me.x * (float)(int)(int8_t)(w[i >> 2] >> (8 * (i & 3)));
-                    const float d = s_q[j0 + i] - x;
-                    acc = fmaf(d, d, acc);
-                }
             }
+            acc += __shfl_xor(acc, 1, 8);
+            acc += __shfl_xor(acc, 2, 8);
+            acc += __shfl_xor(acc, 4, 8);
+            if (act && l8 == 0) store_bracket<false>(a, (size_t)q * a.m + c, dim, acc, me.y, 0.0f);
         }
-        acc += __shfl_xor(acc, 1, 8);
-        acc += __shfl_xor(acc, 2, 8);
-        acc += __shfl_xor(acc, 4, 8);
-        if (act && l8 == 0) {
-            const float E = me.y;
-            // | d_f32 - d~ | <= 2 sqrt(d~) E + E^2 (triangle inequality on the real values) + the f32 rounding
-            // of the two dim-term sums (each <= (dim + 4) 2^-24 relative) + slack on the bound itself
-            const float slack = (2.0f * sqrtf(acc) * E + E * E) * 1.0001f + acc * ((float)(dim + 8) * 1.2e-7f) + 1e-30f;
-            float L = acc - slack, U = acc + slack;
-            // NaN or overflow anywhere (an infinite d~ would make L = inf - inf = NaN, which orders above +inf and
-            // drops the candidate): never filtered out, never a bound for others
-            if (!(slack < __builtin_inff()) || !(acc < __builtin_inff())) {
-                L = -__builtin_inff();
-                U = __builtin_inff();
+    } else {
+        // the candidate this lane finishes: round l8 of its group (its meta line is in flight under the rounds)
+        const uint32_t ce = c0 + l8 * 32u + (tid >> 3);
+        const bool acte = ce < nsel;
+        const float2 mee = UNI ? make_float2(a.uni_scale, a.uni_E) : a.meta[acte ? a.cand_row[(size_t)q * a.m + ce] : 0u];
+        if constexpr (FMT == 1) {
+            float accv[R];
+#pragma unroll
+            for (int it = 0; it < R; ++it) {
+                const float inv = a.meta[row[it]].x;
+                const int8_t *r8 = a.rows8 + (size_t)row[it] * dim;
+                float acc = 0.0f;
+                for (uint32_t j0 = l8 * 16u; j0 < dim; j0 += 128u) {
+                    const uint4 v = *reinterpret_cast<const uint4 *>(r8 + j0);
+                    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+                    for (int wi = 0; wi < 4; ++wi) {
+                        const v2f lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[wi], false);
+                        const v2f hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[wi], true);
+                        const float xs[4] = {lo.x, lo.y, hi.x, hi.y};
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) {
+                            const float d = s_q[j0 + wi * 4 + i] - xs[i] * inv;
+                            acc = fmaf(d, d, acc);
+                        }
+                    }
+                }
+                accv[it] = acc;
             }
-            a.lb[(size_t)q * a.m + c] = f32_to_ordered(L);
-            a.ub[(size_t)q * a.m + c] = f32_to_ordered(U);
+            const float acc = sum8_transposed(accv, l8);
+            if (acte) store_bracket<false>(a, (size_t)q * a.m + ce, dim, acc, mee.y, 0.0f);
+        } else {
+            constexpr int NP = EX - 1;   // 128-dim passes with the query slice in registers (0: LDS)
+            float qr[NP > 0 ? NP : 1][16];
+            float q2 = 0.0f;             // |q|^2: the lane's slices in dimension order, then the group's 8 partial sums
+            if constexpr (NP > 0) {
+#pragma unroll
+                for (int p = 0; p < NP; ++p) {
+                    const uint32_t j0 = l8 * 16u + (uint32_t)p * 128u;
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) {
+                        qr[p][i] = j0 < dim ? s_q[j0 + i] : 0.0f;
+                        q2 = fmaf(qr[p][i], qr[p][i], q2);
+                    }
+                }
+            } else {
+                for (uint32_t j0 = l8 * 16u; j0 < dim; j0 += 128u)
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) q2 = fmaf(s_q[j0 + i], s_q[j0 + i], q2);
+            }
+            q2 = sum8(q2);
+            float Dv[R];
+            int Nv[R];
+#pragma unroll
+            for (int it = 0; it < R; ++it) {
+                const int8_t *r8 = a.rows8 + (size_t)row[it] * dim;
+                float D = 0.0f;
+                int N = 0;
+                auto pass = [&](uint32_t j0, int &Np, auto qat) {
+                    const uint4 v = *reinterpret_cast<const uint4 *>(r8 + j0);
+                    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+                    for (int wi = 0; wi < 4; ++wi) Np = __builtin_amdgcn_sdot4((int)w[wi], (int)w[wi], Np, false);
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) D = fmaf(qat(i), (float)(int)(int8_t)(w[i >> 2] >> (8 * (i & 3))), D);
+                };
+                if constexpr (NP > 0) {
+                    // no branch around a slice past the row's end: the lane reads the row's first 16 bytes instead,
+                    // which its zero query slice keeps out of D and the select keeps out of N
+#pragma unroll
+                    for (int p = 0; p < NP; ++p) {
+                        const uint32_t j0 = l8 * 16u + (uint32_t)p * 128u;
+                        int Np = 0;
+                        pass(j0 < dim ? j0 : 0u, Np, [&](int i) { return qr[p][i]; });
+                        N += j0 < dim ? Np : 0;
+                    }
+                } else {
+                    for (uint32_t j0 = l8 * 16u; j0 < dim; j0 += 128u) pass(j0, N, [&](int i) { return s_q[j0 + i]; });
+                }
+                Dv[it] = D;
+                Nv[it] = N;
+            }
+            const float D = sum8_transposed(Dv, l8);
+            const float Nf = (float)sum8_transposed(Nv, l8);   // <= dim 127^2: exact in f32 up to dim 1040
+            const float s = mee.x;
+            const float acc = (q2 - (2.0f * s) * D) + (s * s) * Nf;
+            // the three terms cancel down to d~: each carries a rounding of up to (dim + 8) 2^-24 of its own
+            // magnitude, and Q2 + 2 s |D| + s^2 N <= (|q| + s |x8|)^2
+            const float rt = sqrtf(q2) + s * sqrtf(Nf);
+            const float B = rt * rt * ((float)(dim + 8) * 1.2e-7f);
+            if (acte) store_bracket<true>(a, (size_t)q * a.m + ce, dim, acc, mee.y, B);
         }
     }
 }
@@ -239,10 +377,16 @@ int launch_rerank_i8(const TxhIndexDev &ix, const TxhWork &w, hipStream_t st) {
     ia.q_stride = w.q_stride; ia.m = w.m; ia.cand_row = w.cand_row; ia.cand_count = w.cand_count;
     ia.lb = w.rr_lb; ia.ub = w.rr_ub;
     ia.uni_scale = ix.rows8_scale; ia.uni_E = ix.rows8_emax;
+    const bool fp8 = ix.rows8_fmt == 1;
+    const int ex = !w.i8_expand || (!fp8 && !ix.rows8_uniform) ? 0 : fp8 || ix.dim > 256 ? 1 : ix.dim <= 128 ? 2 : 3;
     // 1: FP8 rows; int8 rows with 2: one scale for all rows, 0: a scale per row
-    return with_value<1, 2, 0>(ix.rows8_fmt == 1 ? 1 : ix.rows8_uniform ? 2 : 0, [&](auto v) {
-        return launch((rerank_i8_kernel<v() == 1 ? 1 : 0, v() == 2>), dim3(ceil_div_u32(w.m, kI8PerBlock), w.nq),
-                      dim3(256), lds_rr, st, ix.dim, ia);
+    return with_value<1, 2, 0>(fp8 ? 1 : ix.rows8_uniform ? 2 : 0, [&](auto v) {
+        return with_value<0, 1, 2, 3>(ex, [&](auto e) {
+            // (per-row int8: EX = 0 only; FP8: 0 or 1; the register forms are the one-scale store's)
+            constexpr int EX = v() == 0 ? 0 : (v() == 1 && e() > 1) ? 1 : e();
+            return launch((rerank_i8_kernel<v() == 1 ? 1 : 0, v() == 2, EX>), dim3(ceil_div_u32(w.m, kI8PerBlock), w.nq),
+                          dim3(256), lds_rr, st, ix.dim, ia);
+        });
     });
 }
 

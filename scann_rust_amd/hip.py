@@ -36,6 +36,7 @@ EXPORTS = [
     "scann_hip_txh_create",
     "scann_hip_search_opts_default", "scann_hip_search_batched", "scann_hip_search_batched_params", "scann_hip_index_reserve",
     "scann_hip_search_batched_device", "scann_hip_index_last_device_status", "scann_hip_index_debug_filter_bounds",
+    "scann_hip_index_debug_rerank_brackets",
     "scann_hip_crowd_table_slots", "scann_hip_index_set_crowding_attributes", "scann_hip_search_crowded",
     "scann_hip_index_reserve_crowded", "scann_hip_search_crowded_device",
     "scann_hip_index_set_crowding_attributes_md", "scann_hip_search_crowded_md", "scann_hip_search_crowded_md_device",
@@ -158,6 +159,7 @@ def load():
                                                   C.POINTER(SearchOpts), vp, vp, vp, vp]
     L.scann_hip_index_last_device_status.argtypes = [vp, vp]
     L.scann_hip_index_debug_filter_bounds.argtypes = [vp, vp, C.c_uint32, u64p]
+    L.scann_hip_index_debug_rerank_brackets.argtypes = [vp, vp, C.c_uint32, C.c_uint32, u32p, u32p, u32p, u32p]
     L.scann_hip_crowd_table_slots.restype = C.c_uint32
     L.scann_hip_crowd_table_slots.argtypes = [C.c_uint32]
     L.scann_hip_index_set_crowding_attributes.argtypes = [vp, u64p, C.c_uint64]
@@ -540,6 +542,17 @@ class Index:
         out = np.zeros(nq, np.uint64)
         check(load().scann_hip_index_debug_filter_bounds(self.h, vp(stream), nq, ptr(out, u64p)))
         return out
+
+    def debug_rerank_brackets(self, nq, m, stream=0):
+        """(lb, ub, rows, counts) of the 8-bit row filter after the last batched search of nq queries with
+        pre_reorder_k = m enqueued on `stream` (a HIP stream handle), which the caller has synchronised: ordered u32
+        bounds [nq, m], re-rank rows [nq, m], candidates per query [nq] (0x80000000 where the shortlist kernel finished
+        the query itself).  scann_hip_index_debug_rerank_brackets."""
+        lb, ub, rows = (np.zeros((nq, m), np.uint32) for _ in range(3))
+        counts = np.zeros(nq, np.uint32)
+        check(load().scann_hip_index_debug_rerank_brackets(self.h, vp(stream), nq, m, ptr(lb, u32p), ptr(ub, u32p),
+                                                           ptr(rows, u32p), ptr(counts, u32p)))
+        return lb, ub, rows, counts
 
 
 class Mutable:
