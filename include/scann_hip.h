@@ -276,6 +276,23 @@ typedef struct {
      * Aborted: the host entry point repeats the batch on the exact kernels by itself, callers of the
      * *_device entry point repeat it with bf_exact = 1.  1: exact kernels only. */
     int32_t bf_exact;
+    /* Per-query allow-lists: the distance, in 64-bit words, from the bitmap of query i of the call to the bitmap of
+     * query i + 1.  0 (default): allow_bitmap is ONE bitmap for the whole batch -- exactly the behaviour and the code
+     * path described at allow_bitmap.  Non-zero: query i reads words [i * stride, i * stride + ceil(allow_bitmap_bits
+     * / 64)) of allow_bitmap, so a batch carries one filter per query (per-user ACLs, per-tenant subsets).  All
+     * bitmaps of a call share the capacity allow_bitmap_bits and every rule stated at allow_bitmap holds per query,
+     * unchanged: bits at or past the capacity are ignored, datapoint indices at or past it are not allowed, capacity
+     * 0 allows nothing.  Words between one query's last word and the next query's first are never read.  A
+     * non-zero stride below ceil(allow_bitmap_bits / 64) is InvalidArgument; with allow_bitmap = NULL the field is
+     * ignored (there is no filter).  The host entry points copy nq * stride words to the device
+     * (scann_hip_index_reserve sizes that copy from allow_bitmap_bits, the stride and max_nq when its opts carry a
+     * non-NULL bitmap); the *_device entry points read them in place.  scann_hip_search_batched_params carries
+     * bitmap row i with query i into its per-k groups; crowded, multi-attribute crowded and MMR searches forward
+     * the field.  scann_hip_allow_bitmaps_from_ids[_device] builds such a block from id lists.
+     * Unimplemented with a non-zero stride (and a non-NULL bitmap): brute-force handles (their filtered
+     * k = min(k, allowed rows) and their compaction are per bitmap), scann_hip_mutable_search,
+     * scann_hip_txh_search_local_device / scann_hip_txh_search_sharded_device, radius search. */
+    uint64_t allow_bitmap_stride;
 } scann_hip_search_opts;
 
 void scann_hip_search_opts_default(scann_hip_search_opts *opts);
@@ -767,6 +784,20 @@ int scann_hip_bf_search_radius_opts(scann_hip_index *index, const float *query, 
  * below min(allow_bitmap_bits, n).  This is the count the host entry points plan a filtered brute-force search
  * with (k = min(k, count), the choice between the compacted id list and the bit test); needs no device. */
 uint64_t scann_hip_allow_bitmap_count(const uint64_t *allow_bitmap, uint64_t allow_bitmap_bits, uint64_t n);
+
+/* RestrictAllowlist::from_indices (restricts/allowlist.rs:27-40) for a whole batch: the strided bitmap block of
+ * scann_hip_search_opts.allow_bitmap_stride from per-query id lists.  Query i's ids are ids[offsets[i] ..
+ * offsets[i + 1]) (offsets: nq + 1 ascending values); bit id of its bitmap -- words [i * stride_words, i *
+ * stride_words + ceil(bits / 64)) of out_words -- is set for every id < bits.  All nq * stride_words words are
+ * written, the gap words as zero; an id at or past `bits` is ignored; duplicates and unsorted lists are fine.
+ * stride_words < ceil(bits / 64) -> InvalidArgument.  Host form: host pointers, no context, no GPU.  Device form:
+ * device pointers, a clear and one scatter kernel (64-bit atomic OR) enqueued on hip_stream, no synchronisation;
+ * its output is bitwise the host form's. */
+int scann_hip_allow_bitmaps_from_ids(const uint32_t *ids, const uint64_t *offsets, uint32_t nq, uint64_t bits,
+                                     uint64_t stride_words, uint64_t *out_words);
+int scann_hip_allow_bitmaps_from_ids_device(scann_hip_ctx *ctx, const uint32_t *d_ids, const uint64_t *d_offsets,
+                                            uint32_t nq, uint64_t bits, uint64_t stride_words, uint64_t *d_out_words,
+                                            void *hip_stream);
 int scann_hip_bf_search_radius(scann_hip_index *index, const float *query, uint32_t q_dim, float radius,
                                uint32_t *out_idx, float *out_dist, uint64_t capacity,
                                uint64_t *out_count);

@@ -14,6 +14,7 @@
 #include <string>
 #include <vector>
 
+#include "allow.h"
 #include "bf.h"
 #include "comm.h"
 #include "common.h"
@@ -1528,6 +1529,7 @@ static int txh_search_host(scann_hip_index *ix, const float *queries, uint32_t n
     const hipStream_t stream = sl.stream;
     SCANN_TRY(set_device(ix->ctx));
     const Knobs kn = read_knobs();
+    SCANN_TRY(check_allow_stride(opts));
     for (int attempt = 0; attempt < 2; ++attempt) {
         TxhPlan p;
         SCANN_TRY(plan_txh_search(ix, k, opts, nq, /*retry=*/attempt == 1, TxhPipeline::Wide, kn, &p));
@@ -1540,7 +1542,8 @@ static int txh_search_host(scann_hip_index *ix, const float *queries, uint32_t n
         // (a filter of capacity 0 still binds a workspace bitmap -- of one word, read by no row -- so that it allows
         // nothing whatever an earlier call left in the workspace: a null bitmap would allow every row)
         const bool filtered = opts && opts->allow_bitmap;
-        const size_t allow_words = filtered ? (size_t)((opts->allow_bitmap_bits + 63) / 64) : 0;
+        // (per-query bitmaps: nq of them, allow_bitmap_stride words apart; the repeat below uploads them again)
+        const size_t allow_words = filtered ? allow_copy_words(opts, nq) : 0;
         SCANN_TRY(ensure_txh_workspace(ix, ws, p, true, q_stride, true, &w, filtered ? std::max<size_t>(allow_words, 1) * 8 : 0));
         // (cand_count alone also takes the staged pipeline: the small-batch one keeps no candidate counts)
         w.need_sorted_cands = (opts && (opts->cand_idx || opts->cand_dist || opts->cand_count)) ? 1 : 0;
@@ -1589,6 +1592,7 @@ static int txh_search_host(scann_hip_index *ix, const float *queries, uint32_t n
                                                hipMemcpyHostToDevice, stream));
             w.allow = ws.allow.as<uint64_t>();
             w.allow_bits = opts->allow_bitmap_bits;
+            w.allow_stride = allow_stride_of(opts);
         }
         SCANN_HIP_CHECK(hipMemcpyAsync(ws.queries.p, queries, (size_t)nq * q_stride * 4,
                                        hipMemcpyHostToDevice, stream));
@@ -1715,6 +1719,7 @@ int scann_hip_search_batched(scann_hip_index *ix, const float *queries, uint32_t
     if (!queries || !out_count || (k > 0 && (!out_idx || !out_dist)))
         return fail(SCANN_HIP_INVALID_ARGUMENT, "null query/output pointer");
     if (ix->kind == KIND_BF) {
+        SCANN_TRY(refuse_allow_stride(opts, "brute-force handles"));
         if (ix->bf.n == 0) {  // brute_force/searcher.rs:78-80: Ok(empty) before the dim check
             fill_empty(nq, k, out_idx, out_dist, out_count);
             return SCANN_HIP_OK;
@@ -1776,6 +1781,13 @@ int scann_hip_search_batched_params(scann_hip_index *ix, const float *queries, u
     for (uint32_t i = 0; i < nq; ++i) order[i] = i;
     std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return k_per_query[a] < k_per_query[b]; });
     std::vector<float> qbuf;
+    // per-query bitmaps travel with their queries: bitmap row order[i] goes where query order[i] goes (packed at
+    // the bitmap's own length; brute-force handles refuse the stride in the call below)
+    SCANN_TRY(check_allow_stride(opts));
+    const uint64_t astride = allow_stride_of(opts), awords = astride ? allow_words(opts->allow_bitmap_bits) : 0;
+    std::vector<uint64_t> abuf;
+    scann_hip_search_opts gopts;
+    if (astride) gopts = *opts;
     std::vector<uint32_t> gi, gc;
     std::vector<float> gd;
     for (uint32_t a0 = 0; a0 < nq;) {
@@ -1789,7 +1801,15 @@ int scann_hip_search_batched_params(scann_hip_index *ix, const float *queries, u
         gi.assign((size_t)g * std::max(1u, k), 0xFFFFFFFFu);
         gd.assign((size_t)g * std::max(1u, k), INFINITY);
         gc.assign(g, 0u);
-        SCANN_TRY(scann_hip_search_batched(ix, qbuf.data(), g, q_stride, q_dim, k, opts, gi.data(), gd.data(), gc.data()));
+        if (astride && awords) {
+            abuf.resize((size_t)g * awords);
+            for (uint32_t j = 0; j < g; ++j)
+                std::memcpy(&abuf[(size_t)j * awords], opts->allow_bitmap + (size_t)order[a0 + j] * astride, (size_t)awords * 8);
+            gopts.allow_bitmap = abuf.data();
+            gopts.allow_bitmap_stride = awords;
+        }
+        SCANN_TRY(scann_hip_search_batched(ix, qbuf.data(), g, q_stride, q_dim, k, astride ? &gopts : opts, gi.data(), gd.data(),
+                                           gc.data()));
         for (uint32_t j = 0; j < g; ++j) {
             const uint32_t q = order[a0 + j];
             out_count[q] = gc[j];
@@ -1821,7 +1841,10 @@ int scann_hip_index_reserve(scann_hip_index *ix, uint32_t max_nq, uint32_t max_k
     TxhPlan p;
     SCANN_TRY(plan_txh_search(ix, max_k, opts, max_nq, false, TxhPipeline::Staged, read_knobs(), &p));
     TxhWork w;
-    return ensure_txh_workspace(ix, ix->ws, p, false, 0, false, &w);
+    // (a host call's copy of its bitmap, or of its max_nq bitmaps allow_bitmap_stride words apart)
+    SCANN_TRY(check_allow_stride(opts));
+    const size_t allow_bytes = opts && opts->allow_bitmap ? std::max<size_t>(allow_copy_words(opts, max_nq), 1) * 8 : 0;
+    return ensure_txh_workspace(ix, ix->ws, p, false, 0, false, &w, allow_bytes);
 }
 
 int scann_hip_search_batched_device(scann_hip_index *ix, const float *d_queries, uint32_t nq,
@@ -1852,6 +1875,7 @@ static int search_device_ws(scann_hip_index *ix, scann_hip_index::DeviceSlot *ds
                             uint32_t *d_out_count, hipStream_t st) {
     const Knobs kn = read_knobs();
     if (ix->kind == KIND_BF) {
+        SCANN_TRY(refuse_allow_stride(opts, "brute-force handles"));
         if (dsl) ix->next_events();
         const BfFilter flt = bf_filter_of(opts, kn);   // (a device pointer on this path)
         const bool shortlist = !flt.bitmap && !(opts && opts->bf_exact) && bf_shortlist_eligible(ix->bf, nq, k, kn);
@@ -1864,6 +1888,7 @@ static int search_device_ws(scann_hip_index *ix, scann_hip_index::DeviceSlot *ds
         return s;
     }
     TxhPlan p;
+    SCANN_TRY(check_allow_stride(opts));
     SCANN_TRY(plan_txh_search(ix, k, opts, nq, false, widest, kn, &p));
     if (p.m == 0) return fail(SCANN_HIP_INVALID_ARGUMENT, "pre-reorder candidate count is 0");
     TxhWork w;
@@ -1875,6 +1900,7 @@ static int search_device_ws(scann_hip_index *ix, scann_hip_index::DeviceSlot *ds
     if (opts && opts->allow_bitmap) {   // device pointer on this path
         w.allow = opts->allow_bitmap;
         w.allow_bits = opts->allow_bitmap_bits;
+        w.allow_stride = opts->allow_bitmap_stride;
     }
     if (!dsl) return txh_launch_search(ix->tx, w, false, st, nullptr, nullptr);
     ix->last_work = w;
@@ -2105,8 +2131,9 @@ static int staged_host_on_device(scann_hip_index *ix, const Stage &sg, const flo
     scann_hip_search_opts o;
     scann_hip_search_opts_default(&o);
     if (opts) o = *opts;
+    SCANN_TRY(check_allow_stride(&o));
     if (o.allow_bitmap) {   // host pointer -> the slot's copy (capacity 0: a pointer no row reads)
-        const size_t words = (size_t)((o.allow_bitmap_bits + 63) / 64);
+        const size_t words = allow_copy_words(&o, nq);   // (one bitmap, or nq of them allow_bitmap_stride words apart)
         SCANN_TRY(cw.allow.ensure(std::max<size_t>(words, 1) * 8));
         if (words) SCANN_HIP_CHECK(hipMemcpyAsync(cw.allow.p, o.allow_bitmap, words * 8, hipMemcpyHostToDevice, st));
         o.allow_bitmap = cw.allow.as<uint64_t>();
@@ -2356,6 +2383,7 @@ int scann_hip_txh_search_local_device(scann_hip_index *ix, const float *d_querie
                                       uint32_t *d_idx, float *d_exact, uint32_t *d_count,
                                       void *hip_stream) {
     if (!ix || ix->kind != KIND_TXH) return fail(SCANN_HIP_INVALID_ARGUMENT, "not a tree index");
+    SCANN_TRY(refuse_allow_stride(opts, "the leaf-sharded search"));
     if (nq == 0) return SCANN_HIP_OK;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     std::lock_guard<std::mutex> lock(ix->mu);
@@ -2650,6 +2678,7 @@ int scann_hip_bf_search_radius_opts(scann_hip_index *ix, const float *query, uin
     if (!ix || ix->kind != KIND_BF) return fail(SCANN_HIP_INVALID_ARGUMENT, "not a brute-force index");
     if (!out_count) return fail(SCANN_HIP_INVALID_ARGUMENT, "null out_count");
     *out_count = 0;
+    SCANN_TRY(refuse_allow_stride(opts, "radius search"));
     if (ix->bf.n == 0) return SCANN_HIP_OK;   // searcher.rs:143-145
     if (!query || q_dim != ix->bf.dim)        // searcher.rs:148-152
         return fail(SCANN_HIP_INVALID_ARGUMENT, "Query dimensionality does not match dataset");

@@ -20,6 +20,7 @@
 #include <mutex>
 #include <string>
 
+#include "allow.h"
 #include "comm.h"
 #include "common.h"
 #include "knobs.h"
@@ -325,6 +326,7 @@ int scann_hip_txh_search_sharded_device(scann_hip_index *index, scann_hip_comm *
                                         uint32_t *d_out_idx, float *d_out_dist, uint32_t *d_out_count,
                                         void *hip_stream) {
     if (!index || !c) return fail(SCANN_HIP_INVALID_ARGUMENT, "index/comm is null");
+    SCANN_TRY(refuse_allow_stride(opts, "the leaf-sharded search"));
     if (nq == 0) return SCANN_HIP_OK;
     if (k == 0 || !d_queries || !d_out_idx || !d_out_dist || !d_out_count)
         return fail(SCANN_HIP_INVALID_ARGUMENT, "k must be > 0 and the buffers non-null");

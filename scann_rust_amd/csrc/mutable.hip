@@ -28,6 +28,7 @@
 #include <unordered_set>
 #include <vector>
 
+#include "allow.h"
 #include "bf.h"
 #include "comm.h"
 #include "fold.h"
@@ -802,6 +803,7 @@ int scann_hip_mutable_search(scann_hip_mutable *m, const float *queries, uint32_
     scann_hip_search_opts o;
     scann_hip_search_opts_default(&o);
     if (opts) o = *opts;
+    SCANN_TRY(refuse_allow_stride(&o, "mutable indexes"));
     if (!m->bv.brute_force) {
         if (!o.exact_reorder)
             return fail(SCANN_HIP_UNIMPLEMENTED, "mutable search needs exact_reorder = 1 (approximate and exact distances cannot be merged)");

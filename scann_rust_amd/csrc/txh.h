@@ -176,6 +176,7 @@ struct TxhWork : TxhPlan {
     int need_sorted_cands;     // the caller reads cand_* (parity outputs): keep them sorted
     const uint64_t *allow;     // device allow-bitmap (bit = datapoint index) or nullptr
     uint64_t allow_bits;       // bitmap capacity in bits; indices >= capacity are not allowed
+    uint64_t allow_stride;     // 64-bit words from query i's bitmap to query i + 1's; 0 = one bitmap for the batch
     const float *queries;      // device
     float *cdist;              // [nq][L]
     uint32_t *tokens;          // [nq][P]

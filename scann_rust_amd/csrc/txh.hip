@@ -359,7 +359,7 @@ __host__ __device__ constexpr size_t scan_lds_bytes() {
 }
 
 template <typename C>
-__global__ __launch_bounds__(kScanThreads, C::WGS) void adc_scan_kernel(TxhIndexDev ix, ScanArgs a) {
+__device__ __forceinline__ void adc_scan_body(TxhIndexDev ix, ScanArgs a, const uint64_t allow_stride) {
     constexpr int LUT4 = C::LUT4;                                   // float4 per quad
     constexpr int STG = (LUT4 + kScanThreads - 1) / kScanThreads;   // staged float4 / thread
     extern __shared__ __attribute__((aligned(16))) float4 lut_s[];  // [2 * LUT4]
@@ -482,7 +482,7 @@ __global__ __launch_bounds__(kScanThreads, C::WGS) void adc_scan_kernel(TxhIndex
                             const uint32_t j = c0 + tid + kScanThreads * i;
                             if (j < size) {
                                 const uint64_t key = make_key(acc[p][i], vb + j);
-                                if (key <= T && row_allowed(ix, a.allow, a.allow_bits, lb + j)) {
+                                if (key <= T && row_allowed(ix, a.allow, allow_stride, pq, a.allow_bits, lb + j)) {
                                     const uint32_t sl = atomicAdd(&ccnt_s[buf][p], 1u);
                                     if (sl < kScanStage) {
                                         ckey_s[buf][p][sl] = key;
@@ -523,6 +523,16 @@ __global__ __launch_bounds__(kScanThreads, C::WGS) void adc_scan_kernel(TxhIndex
         }
     }
 }
+// One bitmap for the batch, or none: the kernel every search without allow_bitmap_stride runs (its code is that of the
+// body with the stride folded to 0).  _pq: one bitmap per query, allow_stride words apart.
+template <typename C>
+__global__ __launch_bounds__(kScanThreads, C::WGS) void adc_scan_kernel(TxhIndexDev ix, ScanArgs a) {
+    adc_scan_body<C>(ix, a, 0);
+}
+template <typename C>
+__global__ __launch_bounds__(kScanThreads, C::WGS) void adc_scan_pq_kernel(TxhIndexDev ix, ScanArgs a, uint64_t allow_stride) {
+    adc_scan_body<C>(ix, a, allow_stride);
+}
 
 // =====================================================================================
 // K6b: ADC scan with RESIDENT tables, for long leaves (AsymmetricHasher mode, big partitions).
@@ -547,6 +557,9 @@ __host__ __device__ constexpr size_t res_lds_bytes() {
 
 template <typename C>
 __global__ __launch_bounds__(kResThreads, 6) void adc_scan_res_kernel(TxhIndexDev ix, ScanArgs a) {
+    // (PqCodec<C>: one bitmap per query; the launch packs the stride next to the capacity, see pq_allow_bits)
+    constexpr bool PQ = C::PQ;
+    const uint64_t allow_bits = pq_capacity<PQ>(a.allow_bits), allow_stride = pq_stride<PQ>(a.allow_bits);
     static_assert(C::PPT == 2, "resident-table scan: 2 points per thread");
     constexpr int LUT4 = C::LUT4;
     constexpr int NQS = kResQuads * 4;                                   // resident (query, leaf) pairs
@@ -656,7 +669,7 @@ __global__ __launch_bounds__(kResThreads, 6) void adc_scan_res_kernel(TxhIndexDe
                                 const uint32_t j = c0 + tid + kResThreads * i;
                                 if (j < size) {
                                     const uint64_t key = make_key(acc[p][i], vb + j);
-                                    if (key <= T && row_allowed(ix, a.allow, a.allow_bits, lb + j)) {
+                                    if (key <= T && row_allowed_if<PQ>(ix, a.allow, allow_stride, pq, allow_bits, lb + j)) {
                                         const uint32_t sl = atomicAdd(&scnt[wave][buf][qd * 4 + p], 1u);
                                         if (sl < kResStage) {
                                             skey[wave][buf][qd * 4 + p][sl] = key;
@@ -714,6 +727,9 @@ struct SampleArgs {
 
 template <typename C>
 __global__ __launch_bounds__(kScanThreads, C::WGS) void adc_sample_kernel(TxhIndexDev ix, SampleArgs a) {
+    // (PqCodec<C>: one bitmap per query; the launch packs the stride next to the capacity, see pq_allow_bits)
+    constexpr bool PQ = C::PQ;
+    const uint64_t allow_bits = pq_capacity<PQ>(a.allow_bits), allow_stride = pq_stride<PQ>(a.allow_bits);
     constexpr int LUT4 = C::LUT4;
     constexpr int STG = (LUT4 + kScanThreads - 1) / kScanThreads;
     extern __shared__ __attribute__((aligned(16))) float4 lut_s[];   // [2 * LUT4] + tile slot
@@ -746,7 +762,8 @@ __global__ __launch_bounds__(kScanThreads, C::WGS) void adc_sample_kernel(TxhInd
         for (int i = 0; i < C::PPT; ++i) {
             const uint32_t j = c0 + tid + kScanThreads * i;
             const uint32_t row = lb + (j < ssize ? j * st : 0u);
-            ok[i] = j < ssize && row_allowed(ix, a.allow, a.allow_bits, row);
+            // (per-query bitmaps: the sample's own bit is tested where it is written, once per query of the quad)
+            ok[i] = j < ssize && (PQ || row_allowed(ix, a.allow, allow_bits, row));
             uint32_t w[C::NWORDS];
             C::load_words(ix.codes + (size_t)row * C::NWORDS, w);
             C::unpack(w, regs[i]);
@@ -800,7 +817,13 @@ __global__ __launch_bounds__(kScanThreads, C::WGS) void adc_sample_kernel(TxhInd
 #pragma unroll
                 for (int i = 0; i < C::PPT; ++i) {
                     const uint32_t j = c0 + tid + kScanThreads * i;
-                    if (i < (int)nsub && j < ssize) dst[j] = ok[i] ? f32_to_ordered(acc[p][i]) : 0xFFFFFFFFu;
+                    if constexpr (PQ) {   // the sample is absent for this query only
+                        if (i < (int)nsub && j < ssize)
+                            dst[j] = row_allowed(ix, a.allow, allow_stride, f_pq[p], allow_bits, lb + j * st)
+                                         ? f32_to_ordered(acc[p][i]) : 0xFFFFFFFFu;
+                    } else {
+                        if (i < (int)nsub && j < ssize) dst[j] = ok[i] ? f32_to_ordered(acc[p][i]) : 0xFFFFFFFFu;
+                    }
                 }
             }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the LDS-DMA prefetch has landed
@@ -1082,7 +1105,7 @@ struct SampleMfmaArgs {
 // r of the result is sample row (r & 3) + 8 (r >> 2) + 4 h of the tile: four consecutive samples of one query per
 // register group, one 8-byte store.  Items = (pair tile, kSmpTiles sample tiles), one per wave, grid-strided.
 template <int S_>
-__global__ __launch_bounds__(256, (S_ <= 32 ? 3 : 2)) void adc_sample_mfma_kernel(TxhIndexDev ix, SampleMfmaArgs a) {
+__device__ __forceinline__ void adc_sample_mfma_body(TxhIndexDev ix, SampleMfmaArgs a, const uint64_t allow_stride) {
     typedef int v4i __attribute__((ext_vector_type(4)));
     typedef int v16i __attribute__((ext_vector_type(16)));
     constexpr int S = S_, KS = S / 2, NW = S / 8;
@@ -1144,7 +1167,7 @@ __global__ __launch_bounds__(256, (S_ <= 32 ? 3 : 2)) void adc_sample_mfma_kerne
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const uint32_t i = base + (uint32_t)((r & 3) + 8 * (r >> 2));
-                    const bool ok = i < ssize && row_allowed(ix, a.allow, a.allow_bits, lb + i * st);
+                    const bool ok = i < ssize && row_allowed(ix, a.allow, allow_stride, pq, a.allow_bits, lb + i * st);
                     rej |= (ok ? 0u : 1u) << r;
                 }
             }
@@ -1166,6 +1189,16 @@ __global__ __launch_bounds__(256, (S_ <= 32 ? 3 : 2)) void adc_sample_mfma_kerne
             }
         }
     }
+}
+// One bitmap for the batch, or none: the kernel every search without allow_bitmap_stride runs (its code is that of the
+// body with the stride folded to 0).  _pq: one bitmap per query, allow_stride words apart.
+template <int S_>
+__global__ __launch_bounds__(256, (S_ <= 32 ? 3 : 2)) void adc_sample_mfma_kernel(TxhIndexDev ix, SampleMfmaArgs a) {
+    adc_sample_mfma_body<S_>(ix, a, 0);
+}
+template <int S_>
+__global__ __launch_bounds__(256, (S_ <= 32 ? 3 : 2)) void adc_sample_mfma_pq_kernel(TxhIndexDev ix, SampleMfmaArgs a, uint64_t allow_stride) {
+    adc_sample_mfma_body<S_>(ix, a, allow_stride);
 }
 
 struct Tail16Args {
@@ -2295,7 +2328,7 @@ struct SmallArgs {
     uint64_t *cand;           // [nq][cap] dense: key of stream position v at cand[q][v]
     uint32_t *counters;
     const uint64_t *allow;
-    uint64_t allow_bits;
+    uint64_t allow_bits, allow_stride;
     uint32_t *out_idx;
     float *out_dist;
     uint32_t *out_count;
@@ -2326,7 +2359,7 @@ __global__ __launch_bounds__(256) void small_scan_kernel(TxhIndexDev ix, SmallAr
             const float *row = ix.rows + (size_t)(ix.rows_csr ? csr : ix.leaf_ids[csr]) * ix.stride;
             const float dist = exact_pair_thread(ix.measure, dim, s_qe, row);
             const uint32_t vpos = vbe + j;
-            if (vpos < a.cap) oute[vpos] = row_allowed(ix, a.allow, a.allow_bits, csr) ? make_key(dist, vpos) : SCANN_KEY_MAX;
+            if (vpos < a.cap) oute[vpos] = row_allowed(ix, a.allow, a.allow_stride, q, a.allow_bits, csr) ? make_key(dist, vpos) : SCANN_KEY_MAX;
         }
         return;
     }
@@ -2363,7 +2396,7 @@ __global__ __launch_bounds__(256) void small_scan_kernel(TxhIndexDev ix, SmallAr
         }
         const uint32_t vpos = vb + j;
         if (vpos < a.cap)
-            out[vpos] = row_allowed(ix, a.allow, a.allow_bits, lb + j) ? make_key(acc, vpos) : SCANN_KEY_MAX;
+            out[vpos] = row_allowed(ix, a.allow, a.allow_stride, q, a.allow_bits, lb + j) ? make_key(acc, vpos) : SCANN_KEY_MAX;
     }
 }
 
@@ -2872,6 +2905,10 @@ static int launch_gather_bound(const TxhIndexDev &ix, const TxhWork &w, hipStrea
             sa.pair_sbase = w.pair_sbase; sa.counters = w.counters; sa.lutq = w.lutq; sa.samp = w.samp;
             sa.scap = w.scap; sa.st = w.st; sa.qpt = w.sqpt; sa.allow = w.allow; sa.allow_bits = w.allow_bits;
             const size_t lds_smp = (size_t)2 * C::LUT4 * 16 + 16;
+            if (w.allow && w.allow_stride) {   // one bitmap per query
+                sa.allow_bits = pq_allow_bits(w.allow_bits, w.allow_stride);
+                return launch(adc_sample_kernel<PqCodec<C>>, dim3((uint32_t)num_cus() * 8u), dim3(kScanThreads), lds_smp, st, ix, sa);
+            }
             return launch(adc_sample_kernel<C>, dim3((uint32_t)num_cus() * 8u), dim3(kScanThreads), lds_smp, st, ix, sa);
         }));
     }
@@ -2907,15 +2944,26 @@ static int launch_gather_scan(const TxhIndexDev &ix, const TxhWork &w, hipStream
         if (ev0) SCANN_HIP_CHECK(hipEventRecord(ev0, st));
         const uint32_t wgs = (uint32_t)cus * 8u;
         a.res_cl = w.res_cl;
+        const bool pq = w.allow && w.allow_stride;   // one bitmap per query: the _pq instantiations
         if constexpr (C::BITS == 4 && C::S <= 32) {
             if (w.scan == TxhScan::Resident) {
-                SCANN_TRY(launch(adc_scan_res_kernel<C>, dim3((uint32_t)cus * 4u), dim3(kResThreads),
-                                 res_lds_bytes<C>(), st, ix, a));
+                if (pq) {
+                    ScanArgs ap = a;
+                    ap.allow_bits = pq_allow_bits(w.allow_bits, w.allow_stride);
+                    SCANN_TRY(launch(adc_scan_res_kernel<PqCodec<C>>, dim3((uint32_t)cus * 4u), dim3(kResThreads),
+                                     res_lds_bytes<C>(), st, ix, ap));
+                } else {
+                    SCANN_TRY(launch(adc_scan_res_kernel<C>, dim3((uint32_t)cus * 4u), dim3(kResThreads),
+                                     res_lds_bytes<C>(), st, ix, a));
+                }
                 if (ev1) SCANN_HIP_CHECK(hipEventRecord(ev1, st));
                 return SCANN_HIP_OK;
             }
         }
-        SCANN_TRY(launch(adc_scan_kernel<C>, dim3(wgs), dim3(kScanThreads), scan_lds_bytes<C>(), st, ix, a));
+        if (pq)
+            SCANN_TRY(launch(adc_scan_pq_kernel<C>, dim3(wgs), dim3(kScanThreads), scan_lds_bytes<C>(), st, ix, a, w.allow_stride));
+        else
+            SCANN_TRY(launch(adc_scan_kernel<C>, dim3(wgs), dim3(kScanThreads), scan_lds_bytes<C>(), st, ix, a));
         if (ev1) SCANN_HIP_CHECK(hipEventRecord(ev1, st));
         return SCANN_HIP_OK;
     });
@@ -2932,7 +2980,11 @@ static int launch_sample_mfma_bound(const TxhIndexDev &ix, const TxhWork &w, hip
             sm.pair_off = w.pair_off; sm.pair_q = w.pair_q; sm.pair_sbase = w.pair_sbase; sm.lut8 = w.lut8;
             sm.samp16 = reinterpret_cast<uint16_t *>(w.samp); sm.scap = w.scap; sm.st = w.st;
             sm.allow = w.allow; sm.allow_bits = w.allow_bits;
-            SCANN_TRY(launch(adc_sample_mfma_kernel<C::S>, dim3((uint32_t)num_cus() * 4u), dim3(256), 0, st, ix, sm));
+            if (w.allow && w.allow_stride)   // one bitmap per query
+                SCANN_TRY(launch(adc_sample_mfma_pq_kernel<C::S>, dim3((uint32_t)num_cus() * 4u), dim3(256), 0, st, ix, sm,
+                                 w.allow_stride));
+            else
+                SCANN_TRY(launch(adc_sample_mfma_kernel<C::S>, dim3((uint32_t)num_cus() * 4u), dim3(256), 0, st, ix, sm));
             Tail16Args ta;
             ta.P = w.P; ta.m = w.m; ta.st = w.st; ta.scap = w.scap; ta.sbase = w.sbase; ta.slot_of = w.slot_of;
             ta.tokens = w.tokens; ta.vbase = w.vbase; ta.samp16 = sm.samp16; ta.lutq = w.lutq; ta.meta = meta;
@@ -3126,7 +3178,7 @@ __global__ __launch_bounds__(kSelectThreads) void small_fused_kernel(TxhIndexDev
         if (have) {
             const float *row = ix.rows + (size_t)(ix.rows_csr ? csr : ix.leaf_ids[csr]) * ix.stride;
             const uint64_t key =
-                row_allowed(ix, a.allow, a.allow_bits, csr) ? make_key(exact_pair_thread(ix.measure, dim, s_qe, row), v) : SCANN_KEY_MAX;
+                row_allowed(ix, a.allow, a.allow_stride, q, a.allow_bits, csr) ? make_key(exact_pair_thread(ix.measure, dim, s_qe, row), v) : SCANN_KEY_MAX;
             __hip_atomic_store(&out[v], key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     } else if (cnt) {
@@ -3180,7 +3232,7 @@ __global__ __launch_bounds__(kSelectThreads) void small_fused_kernel(TxhIndexDev
                     const float tv = s_lut[sub * kp + code];
                     acc = sub == 0 ? tv : acc + tv;
                 }
-                __hip_atomic_store(&out[v], row_allowed(ix, a.allow, a.allow_bits, csr) ? make_key(acc, v) : SCANN_KEY_MAX,
+                __hip_atomic_store(&out[v], row_allowed(ix, a.allow, a.allow_stride, q, a.allow_bits, csr) ? make_key(acc, v) : SCANN_KEY_MAX,
                                    __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
             __syncthreads();   // (the tables are rebuilt for the next leaf)
@@ -3388,7 +3440,7 @@ __global__ __launch_bounds__(kSelectThreads) void wide_scan_kernel(TxhIndexDev i
                     acc = sub == 0 ? tv : acc + tv;
                 }
             }
-            const uint64_t key = row_allowed(ix, a.allow, a.allow_bits, csr) ? make_key(acc, v) : SCANN_KEY_MAX;
+            const uint64_t key = row_allowed(ix, a.allow, a.allow_stride, q, a.allow_bits, csr) ? make_key(acc, v) : SCANN_KEY_MAX;
             out[v] = key;
             d32[it] = (uint32_t)(key >> 32);
         }
@@ -3869,7 +3921,7 @@ static int launch_search_small(const TxhIndexDev &ix, const TxhWork &w, hipStrea
     SmallArgs a;
     a.nq = w.nq; a.P = w.P; a.m = w.m; a.k = w.k; a.cap = w.cap; a.q_stride = w.q_stride;
     a.exact_reorder = w.exact_reorder; a.queries = w.queries; a.tokens = w.tokens; a.vbase = w.vbase;
-    a.cand = w.cand; a.counters = w.counters; a.allow = w.allow; a.allow_bits = w.allow_bits;
+    a.cand = w.cand; a.counters = w.counters; a.allow = w.allow; a.allow_bits = w.allow_bits; a.allow_stride = w.allow_stride;
     a.out_idx = w.out_idx; a.out_dist = w.out_dist; a.out_count = w.out_count;
     a.done = w.small_done; a.seq = w.small_seq; a.chunk = w.chunk;
     // the one-launch forms: every workgroup repeats the leaf selection

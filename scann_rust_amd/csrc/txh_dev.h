@@ -8,14 +8,50 @@
 
 namespace scann {
 
+// Per-query allow-lists (scann_hip_search_opts.allow_bitmap_stride): query q of the call reads the bitmap that starts
+// `stride` 64-bit words after query q - 1's; stride 0 = one bitmap for the whole batch.  Every site forms this address
+// inside its branch on the (wave-uniform) base pointer, so an unfiltered search executes none of it.
+__device__ __forceinline__ const uint64_t *query_allow(const uint64_t *allow, uint64_t stride, uint32_t q) {
+    return allow + (size_t)q * stride;
+}
 // RestrictFilter::is_allowed (restricts/mod.rs:17-30) for the allow-bitmap form of
 // search_with_filter (tree_x_hybrid/mod.rs:327-332): bit i of the bitmap = datapoint i.
 // Indices at or beyond the bitmap's capacity are not allowed (allowlist.rs:97-100).
-__device__ __forceinline__ bool row_allowed(const TxhIndexDev &ix, const uint64_t *allow,
-                                            uint64_t allow_bits, uint32_t csr) {
+// The six-argument form tests the bitmap of query q (query_allow).
+__device__ __forceinline__ bool row_allowed(const TxhIndexDev &ix, const uint64_t *allow, uint64_t allow_bits, uint32_t csr) {
     if (!allow) return true;
     const uint32_t idx = ix.leaf_ids ? ix.leaf_ids[csr] : csr;
     return idx < allow_bits && ((allow[idx >> 6] >> (idx & 63u)) & 1ull);
+}
+__device__ __forceinline__ bool row_allowed(const TxhIndexDev &ix, const uint64_t *allow, uint64_t stride, uint32_t q,
+                                            uint64_t allow_bits, uint32_t csr) {
+    if (!allow) return true;
+    return row_allowed(ix, query_allow(allow, stride, q), allow_bits, csr);
+}
+// the test of a kernel with a per-query instantiation: PQ = false is the one-bitmap form, word for word
+template <bool PQ>
+__device__ __forceinline__ bool row_allowed_if(const TxhIndexDev &ix, const uint64_t *allow, uint64_t stride, uint32_t q,
+                                               uint64_t allow_bits, uint32_t csr) {
+    if constexpr (PQ) return row_allowed(ix, allow, stride, q, allow_bits, csr);
+    else return row_allowed(ix, allow, allow_bits, csr);
+}
+
+// A kernel whose one-bitmap form must keep its registers to the last one takes no stride argument: its
+// per-query form is the instantiation for PqCodec<C>, launched with the stride packed above the capacity in the
+// allow_bits it already takes.  Both fit 32 bits: a datapoint index is a u32 and 0xFFFFFFFF is none, so a capacity
+// clamps to 2^32 - 1 exactly; a stride of 2^32 words (32 GiB per query) is refused by the entry points.
+static inline uint64_t pq_allow_bits(uint64_t allow_bits, uint64_t stride) {
+    return (stride << 32) | (allow_bits < 0xFFFFFFFFull ? allow_bits : 0xFFFFFFFFull);
+}
+template <bool PQ>
+__device__ __forceinline__ uint64_t pq_capacity(uint64_t allow_bits) {
+    if constexpr (PQ) return allow_bits & 0xFFFFFFFFull;
+    else return allow_bits;
+}
+template <bool PQ>
+__device__ __forceinline__ uint64_t pq_stride(uint64_t allow_bits) {
+    if constexpr (PQ) return allow_bits >> 32;
+    else return 0;
 }
 
 // Code layouts the scan understands.  BITS = 4: K <= 16, 8 subspaces per u32 word
@@ -25,6 +61,7 @@ __device__ __forceinline__ bool row_allowed(const TxhIndexDev &ix, const uint64_
 template <int S_, int BITS_>
 struct Codec {
     static constexpr int S = S_, BITS = BITS_;
+    static constexpr bool PQ = false;                             // (PqCodec: the per-query instantiation of a kernel)
     static constexpr int NWORDS = BITS == 4 ? S / 8 : S / 4;      // packed u32 words per point
     static constexpr int REGS = BITS == 4 ? 2 * NWORDS : NWORDS;  // registers per point in the scan
     static constexpr int KP = BITS == 4 ? 16 : 256;               // table entries per subspace
@@ -83,6 +120,12 @@ struct Codec {
             for (int wi = 0; wi < NWORDS; ++wi) dst[wi] = w[wi];
         }
     }
+};
+
+// the same layout, naming the per-query instantiation of a kernel (pq_allow_bits)
+template <typename C>
+struct PqCodec : C {
+    static constexpr bool PQ = true;
 };
 
 // with_codec(ix, f) calls f(Codec<S, BITS>{}) for the index's code layout and returns what f returns; only the listed

@@ -198,15 +198,17 @@ struct MfmaArgs {
 
 // The survivor mask `m` of a prefilter tile without its disallowed points: bit b of m stands for the point at leaf
 // position pos_of(b) (CSR row lb + pos_of(b)).  Walks the set bits only (a few per tile); callers take this branch
-// only when a bitmap is present, so an unfiltered scan runs none of it.
+// only when a bitmap is present, so an unfiltered scan runs none of it.  q: the query the mask belongs to (the lane's
+// pair); its bitmap's address is formed once, here.
 template <typename F>
-__device__ __forceinline__ uint32_t mask_allowed(const TxhIndexDev &ix, const uint64_t *allow, uint64_t allow_bits,
-                                                 uint32_t lb, uint32_t m, F pos_of) {
+__device__ __forceinline__ uint32_t mask_allowed(const TxhIndexDev &ix, const uint64_t *allow, uint64_t stride, uint32_t q,
+                                                 uint64_t allow_bits, uint32_t lb, uint32_t m, F pos_of) {
+    allow = query_allow(allow, stride, q);
     uint32_t keep = 0;
     while (m) {
         const uint32_t b = (uint32_t)__ffs((int)m) - 1u;
         m &= m - 1u;
-        if (row_allowed(ix, allow, allow_bits, lb + pos_of(b))) keep |= 1u << b;
+        if (row_allowed(ix, allow, 0, 0, allow_bits, lb + pos_of(b))) keep |= 1u << b;
     }
     return keep;
 }
@@ -233,7 +235,7 @@ __device__ __forceinline__ void append_survivor(uint32_t *cand32, uint32_t *cand
 // adc_smfmac_kernel<48, false> spilled two more VGPRs.)
 
 template <int S_>
-__global__ __launch_bounds__(kMfmaWaves * 64, (S_ <= 32 ? SCANN_MFMA_MINW : 2)) void adc_mfma_kernel(TxhIndexDev ix, MfmaArgs a) {
+__device__ __forceinline__ void adc_mfma_body(TxhIndexDev ix, MfmaArgs a, const uint64_t allow_stride) {
     typedef int v4i __attribute__((ext_vector_type(4)));
     typedef int v16i __attribute__((ext_vector_type(16)));
     constexpr int S = S_, KS = S / 2, NW = S / 8;
@@ -381,7 +383,7 @@ __global__ __launch_bounds__(kMfmaWaves * 64, (S_ <= 32 ? SCANN_MFMA_MINW : 2)) 
                 m16 &= okm;
             }
             if (a.allow && m16)                // search_with_filter: disallowed points are not survivors
-                m16 = mask_allowed(ix, a.allow, a.allow_bits, lb, m16, [&](uint32_t b) {
+                m16 = mask_allowed(ix, a.allow, allow_stride, pq, a.allow_bits, lb, m16, [&](uint32_t b) {
                     const uint32_t r = 15u - b;
                     return base + (r & 3u) + ((r >> 2) << 3);
                 });
@@ -415,6 +417,16 @@ __global__ __launch_bounds__(kMfmaWaves * 64, (S_ <= 32 ? SCANN_MFMA_MINW : 2)) 
         flush(true);
         tile = __builtin_amdgcn_readfirstlane(next_tile);
     }
+}
+// One bitmap for the batch, or none: the kernel every search without allow_bitmap_stride runs (its code is that of the
+// body with the stride folded to 0).  _pq: one bitmap per query, allow_stride words apart.
+template <int S_>
+__global__ __launch_bounds__(kMfmaWaves * 64, (S_ <= 32 ? SCANN_MFMA_MINW : 2)) void adc_mfma_kernel(TxhIndexDev ix, MfmaArgs a) {
+    adc_mfma_body<S_>(ix, a, 0);
+}
+template <int S_>
+__global__ __launch_bounds__(kMfmaWaves * 64, (S_ <= 32 ? SCANN_MFMA_MINW : 2)) void adc_mfma_pq_kernel(TxhIndexDev ix, MfmaArgs a, uint64_t allow_stride) {
+    adc_mfma_body<S_>(ix, a, allow_stride);
 }
 
 // =====================================================================================
@@ -503,13 +515,14 @@ __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
 // search_with_filter in the sparse prefilter: lane (col, h) drops the disallowed points from its own words of the item's
 // survivor bitmap (words[tt * 64], tt < ntt; see adc_smfmac_body: word [tt][h][col] = the masks of tiles 2 tt (low half)
 // and 2 tt + 1, result r of a tile -- point row (r & 3) + 8 (r >> 2) + 4 h -- at bit 15 - r), before the flush counts
-// them.  Called at the top of the flushes, where the tile loop's registers are dead, and only when a bitmap is present.
-__device__ __forceinline__ void sp_filter_words(const TxhIndexDev &ix, const uint64_t *allow, uint64_t allow_bits,
-                                                uint32_t *words, uint32_t ntt, uint32_t c0, uint32_t lb, uint32_t h) {
+// them.  pq: the query of the lane's pair (padding pairs have no bits, so their query is never used).  Called at the top
+// of the flushes, where the tile loop's registers are dead, and only when a bitmap is present.
+__device__ __forceinline__ void sp_filter_words(const TxhIndexDev &ix, const uint64_t *allow, uint64_t stride, uint32_t pq,
+                                                uint64_t allow_bits, uint32_t *words, uint32_t ntt, uint32_t c0, uint32_t lb, uint32_t h) {
     for (uint32_t tt = 0; tt < ntt; ++tt) {
         const uint32_t wd = words[tt * 64u];
         if (wd)
-            words[tt * 64u] = mask_allowed(ix, allow, allow_bits, lb, wd, [&](uint32_t b) {
+            words[tt * 64u] = mask_allowed(ix, allow, stride, pq, allow_bits, lb, wd, [&](uint32_t b) {
                 const uint32_t r = 15u - (b & 15u);
                 return c0 + (2u * tt + (b >> 4)) * 32u + 4u * h + (r & 3u) + ((r >> 2) << 3);
             });
@@ -527,7 +540,7 @@ __device__ __forceinline__ void sp_filter_words(const TxhIndexDev &ix, const uin
 // scan 0.27 ms against 0.71 ms), because a lane walking its own survivors takes them one by one.
 template <int S>
 __device__ SCANN_SP_FLUSH_INLINE void sp_flush_item_lanes(const uint32_t *__restrict__ codes_sp, const TxhIndexDev &ix,
-                                                        const uint64_t *allow, uint64_t allow_bits, uint32_t *__restrict__ cand32_cnt,
+                                                        const uint64_t *allow, uint64_t allow_bits, uint64_t allow_stride, uint32_t *__restrict__ cand32_cnt,
                                                         uint32_t *__restrict__ cand32, uint32_t *__restrict__ cand32_codes,
                                                         uint32_t cap32, uint32_t *bits, uint2 *stage, uint32_t *s_fq,
                                                         uint32_t *s_fvb, uint32_t *s_fgb, uint32_t ntile, uint32_t c0,
@@ -536,7 +549,7 @@ __device__ SCANN_SP_FLUSH_INLINE void sp_flush_item_lanes(const uint32_t *__rest
     constexpr int TTM = (int)(kMfmaRange / 64);
     const uint32_t lane = threadIdx.x & 63u, col = lane & 31u, h = lane >> 5;
     const uint32_t ntt = (ntile + 1u) >> 1;
-    if (allow) sp_filter_words(ix, allow, allow_bits, bits, ntt, c0, lb, h);
+    if (allow) sp_filter_words(ix, allow, allow_stride, pq, allow_bits, bits, ntt, c0, lb, h);
     uint32_t w[TTM];
     uint32_t cnt = 0;
 #pragma unroll
@@ -634,7 +647,7 @@ __device__ SCANN_SP_FLUSH_INLINE void sp_flush_item_lanes(const uint32_t *__rest
 //      last touched at index creation); adc_refine_kernel decodes it (RefineArgs::planes).
 template <int S>
 __device__ SCANN_SP_FLUSH_INLINE void sp_flush_item_words(const uint32_t *__restrict__ codes_sp, const TxhIndexDev &ix,
-                                                        const uint64_t *allow, uint64_t allow_bits, uint32_t *__restrict__ cand32_cnt,
+                                                        const uint64_t *allow, uint64_t allow_bits, uint64_t allow_stride, uint32_t *__restrict__ cand32_cnt,
                                                         uint32_t *__restrict__ cand32, uint32_t *__restrict__ cand32_codes,
                                                         uint32_t cap32, uint32_t *bits_w, uint2 *stage, uint32_t *s_fq,
                                                         uint32_t *s_fvb, uint32_t *s_fgb, uint32_t ntile, uint32_t c0,
@@ -644,7 +657,7 @@ __device__ SCANN_SP_FLUSH_INLINE void sp_flush_item_words(const uint32_t *__rest
     static_assert(TTM == 32, "the flush maps the 64 words of a pair onto the 64 lanes");
     const uint32_t lane = threadIdx.x & 63u, h = lane >> 5;
     const uint32_t ntt = (ntile + 1u) >> 1;
-    if (allow) sp_filter_words(ix, allow, allow_bits, bits_w + lane, ntt, c0, lb, h);
+    if (allow) sp_filter_words(ix, allow, allow_stride, pq, allow_bits, bits_w + lane, ntt, c0, lb, h);
     uint32_t cnt = 0;
 #pragma unroll
     for (int tt = 0; tt < TTM; ++tt) cnt += (uint32_t)tt < ntt ? (uint32_t)__popc(bits_w[tt * 64 + lane]) : 0u;
@@ -745,7 +758,7 @@ __device__ SCANN_SP_FLUSH_INLINE void sp_flush_item_words(const uint32_t *__rest
 }
 
 template <int S_, bool WORDS>   // WORDS: the word-parallel flush (tree indexes); else lanes walk their own words (flat)
-__device__ __forceinline__ void adc_smfmac_body(const TxhIndexDev &ix, const MfmaArgs &a) {
+__device__ __forceinline__ void adc_smfmac_body(const TxhIndexDev &ix, const MfmaArgs &a, const uint64_t allow_stride) {
     typedef int v4i __attribute__((ext_vector_type(4)));
     typedef int v8i __attribute__((ext_vector_type(8)));
     typedef int v16i __attribute__((ext_vector_type(16)));
@@ -944,10 +957,10 @@ __device__ __forceinline__ void adc_smfmac_body(const TxhIndexDev &ix, const Mfm
         // ---- flush: the item's bitmap -> the queries' lists (sp_flush_item: its own function, so that its registers
         // are allocated apart from the tile loop's -- inlined, the loop spilled its table fragments)
         if constexpr (WORDS)
-            sp_flush_item_words<S>(ix.codes_sp, ix, a.allow, a.allow_bits, a.cand32_cnt, a.cand32, a.cand32_codes, a.cap32, &s_bits[wave][0][0],
+            sp_flush_item_words<S>(ix.codes_sp, ix, a.allow, a.allow_bits, allow_stride, a.cand32_cnt, a.cand32, a.cand32_codes, a.cap32, &s_bits[wave][0][0],
                                    s_stage[wave], s_fq[wave], s_fvb[wave], s_fgb[wave], ntile, c0, lb, pq, vb);
         else
-            sp_flush_item_lanes<S>(ix.codes_sp, ix, a.allow, a.allow_bits, a.cand32_cnt, a.cand32, a.cand32_codes, a.cap32, bits, s_stage[wave],
+            sp_flush_item_lanes<S>(ix.codes_sp, ix, a.allow, a.allow_bits, allow_stride, a.cand32_cnt, a.cand32, a.cand32_codes, a.cap32, bits, s_stage[wave],
                                    s_fq[wave], s_fvb[wave], s_fgb[wave], ntile, c0, lb, pq, vb);
         tile = __builtin_amdgcn_readfirstlane(next_tile);
     }
@@ -962,11 +975,21 @@ __device__ __forceinline__ void adc_smfmac_body(const TxhIndexDev &ix, const Mfm
 template <int S_, bool WORDS>
 __global__ __launch_bounds__(kMfmaWaves * 64, SCANN_MFMA_MINW) __attribute__((amdgpu_num_vgpr(SCANN_SP_VGPRS)))
 void adc_smfmac_kernel(TxhIndexDev ix, MfmaArgs a) {
-    adc_smfmac_body<S_, WORDS>(ix, a);
+    adc_smfmac_body<S_, WORDS>(ix, a, 0);
 }
 template <int S_, bool WORDS>
 __global__ __launch_bounds__(kMfmaWaves * 64, 2) void adc_smfmac_wide_kernel(TxhIndexDev ix, MfmaArgs a) {   // S = 48, 64
-    adc_smfmac_body<S_, WORDS>(ix, a);
+    adc_smfmac_body<S_, WORDS>(ix, a, 0);
+}
+// (_pq: one bitmap per query, allow_stride words apart; see adc_mfma_pq_kernel)
+template <int S_, bool WORDS>
+__global__ __launch_bounds__(kMfmaWaves * 64, SCANN_MFMA_MINW) __attribute__((amdgpu_num_vgpr(SCANN_SP_VGPRS)))
+void adc_smfmac_pq_kernel(TxhIndexDev ix, MfmaArgs a, uint64_t allow_stride) {
+    adc_smfmac_body<S_, WORDS>(ix, a, allow_stride);
+}
+template <int S_, bool WORDS>
+__global__ __launch_bounds__(kMfmaWaves * 64, 2) void adc_smfmac_wide_pq_kernel(TxhIndexDev ix, MfmaArgs a, uint64_t allow_stride) {
+    adc_smfmac_body<S_, WORDS>(ix, a, allow_stride);
 }
 
 // The prefilter with 16-pair tiles on v_mfma_i32_16x16x64_i8, for leaves scanned by 8-24 queries of the batch
@@ -978,7 +1001,7 @@ __global__ __launch_bounds__(kMfmaWaves * 64, 2) void adc_smfmac_wide_kernel(Txh
 // (the worklist is built with 4 quads per tile).  Measured as a 32-pair kernel (two halves) this shape lost to
 // adc_mfma_kernel (more vector work per tile); here it replaces the f32 LDS-gather scan.
 template <int S_>
-__global__ __launch_bounds__(kMfmaWaves * 64, (S_ <= 32 ? 4 : 2)) void adc_mfma16_kernel(TxhIndexDev ix, MfmaArgs a) {
+__device__ __forceinline__ void adc_mfma16_body(TxhIndexDev ix, MfmaArgs a, const uint64_t allow_stride) {
     typedef int v4i __attribute__((ext_vector_type(4)));
     constexpr int S = S_, KT = S / 4, NW = S / 8, NP = (NW + 1) / 2;
     __shared__ __attribute__((aligned(16))) uint32_t s_ident[64];                 // 16 one-hot rows of 16 bytes
@@ -1122,7 +1145,7 @@ __global__ __launch_bounds__(kMfmaWaves * 64, (S_ <= 32 ? 4 : 2)) void adc_mfma1
             bool risk = false;
             m8 &= 0xFFu;
             if (a.allow && m8)                 // search_with_filter: disallowed points are not survivors
-                m8 = mask_allowed(ix, a.allow, a.allow_bits, lb, m8, [&](uint32_t b) {
+                m8 = mask_allowed(ix, a.allow, allow_stride, s_fq[wave][c16], a.allow_bits, lb, m8, [&](uint32_t b) {
                     const uint32_t qi = 7u - b;
                     return base + 16u * (qi >> 2) + (qi & 3u);
                 });
@@ -1156,6 +1179,16 @@ __global__ __launch_bounds__(kMfmaWaves * 64, (S_ <= 32 ? 4 : 2)) void adc_mfma1
         tile = __builtin_amdgcn_readfirstlane(next_tile);
     }
 }
+// One bitmap for the batch, or none: the kernel every search without allow_bitmap_stride runs (its code is that of the
+// body with the stride folded to 0).  _pq: one bitmap per query, allow_stride words apart.
+template <int S_>
+__global__ __launch_bounds__(kMfmaWaves * 64, (S_ <= 32 ? 4 : 2)) void adc_mfma16_kernel(TxhIndexDev ix, MfmaArgs a) {
+    adc_mfma16_body<S_>(ix, a, 0);
+}
+template <int S_>
+__global__ __launch_bounds__(kMfmaWaves * 64, (S_ <= 32 ? 4 : 2)) void adc_mfma16_pq_kernel(TxhIndexDev ix, MfmaArgs a, uint64_t allow_stride) {
+    adc_mfma16_body<S_>(ix, a, allow_stride);
+}
 
 // Exact refine of the prefilter's survivors: block per query.  Recomputes the reference's f32 sums
 // (LookupTable::compute_distance, hashes/lut.rs:74-82: acc = lut[0][c0]; acc += lut[s][cs], s
@@ -1170,7 +1203,7 @@ struct RefineArgs {
     uint64_t *cand;
     uint32_t *counters;
     const uint64_t *allow;
-    uint64_t allow_bits;
+    uint64_t allow_bits, allow_stride;
     int planes;   // cand32_codes holds codes_sp plane rows (adc_smfmac_kernel), not packed codes
 };
 
@@ -1344,7 +1377,7 @@ __global__ __launch_bounds__(kRefineThreads) void adc_refine_kernel(TxhIndexDev 
                     }
                 }
                 key = make_key(acc, vpos[u]);
-                keep = key <= T && row_allowed(ix, a.allow, a.allow_bits, csr[u]);
+                keep = key <= T && row_allowed(ix, a.allow, a.allow_stride, q, a.allow_bits, csr[u]);
             }
             uint32_t wtot;
             const uint32_t wpre = wave_prefix_count(keep, &wtot);
@@ -1385,18 +1418,27 @@ int launch_prefilter_refine(const TxhIndexDev &ix, const TxhWork &w, hipStream_t
             if (ev0) SCANN_HIP_CHECK(hipEventRecord(ev0, st));
             const bool words = w.sp_words;
             const dim3 mgrid((uint32_t)cus * 4u), mblock(kMfmaWaves * 64);   // 4 workgroups per CU (4 waves each)
-            void (*scan)(TxhIndexDev, MfmaArgs) =
-                w.scan == TxhScan::Mfma16   ? adc_mfma16_kernel<C::S>
-                : w.scan == TxhScan::Mfma32 ? adc_mfma_kernel<C::S>
-                : C::S <= 32                ? (words ? adc_smfmac_kernel<C::S, true> : adc_smfmac_kernel<C::S, false>)
-                                            : (words ? adc_smfmac_wide_kernel<C::S, true> : adc_smfmac_wide_kernel<C::S, false>);
-            SCANN_TRY(launch(scan, mgrid, mblock, 0, st, ix, ma));
+            if (w.allow && w.allow_stride) {   // one bitmap per query: the instantiation that forms the query's address
+                void (*scan)(TxhIndexDev, MfmaArgs, uint64_t) =
+                    w.scan == TxhScan::Mfma16   ? adc_mfma16_pq_kernel<C::S>
+                    : w.scan == TxhScan::Mfma32 ? adc_mfma_pq_kernel<C::S>
+                    : C::S <= 32                ? (words ? adc_smfmac_pq_kernel<C::S, true> : adc_smfmac_pq_kernel<C::S, false>)
+                                                : (words ? adc_smfmac_wide_pq_kernel<C::S, true> : adc_smfmac_wide_pq_kernel<C::S, false>);
+                SCANN_TRY(launch(scan, mgrid, mblock, 0, st, ix, ma, w.allow_stride));
+            } else {
+                void (*scan)(TxhIndexDev, MfmaArgs) =
+                    w.scan == TxhScan::Mfma16   ? adc_mfma16_kernel<C::S>
+                    : w.scan == TxhScan::Mfma32 ? adc_mfma_kernel<C::S>
+                    : C::S <= 32                ? (words ? adc_smfmac_kernel<C::S, true> : adc_smfmac_kernel<C::S, false>)
+                                                : (words ? adc_smfmac_wide_kernel<C::S, true> : adc_smfmac_wide_kernel<C::S, false>);
+                SCANN_TRY(launch(scan, mgrid, mblock, 0, st, ix, ma));
+            }
             if (ev1) SCANN_HIP_CHECK(hipEventRecord(ev1, st));
             RefineArgs ra;
             ra.P = w.P; ra.cap = w.cap; ra.cap32 = w.cap32; ra.tokens = w.tokens; ra.vbase = w.vbase;
             ra.slot_of = w.slot_of; ra.lutq = w.lutq; ra.thr = w.thr; ra.cand32_cnt = w.cand32_cnt;
             ra.cand32 = w.cand32; ra.cand32_codes = codes_in_list ? w.cand32_codes : nullptr; ra.cand_cnt = w.cand_cnt; ra.cand = w.cand; ra.counters = w.counters;
-            ra.allow = w.allow; ra.allow_bits = w.allow_bits;
+            ra.allow = w.allow; ra.allow_bits = w.allow_bits; ra.allow_stride = w.allow_stride;
             ra.planes = (w.scan == TxhScan::Smfmac && ra.cand32_codes) ? 1 : 0;
             const size_t lds_rf = w.P <= kRefineTablesMax ? (size_t)w.P * C::S * 16 * sizeof(float) : 16;
             SCANN_TRY(launch(adc_refine_kernel<C>, dim3(w.nq), dim3(kRefineThreads), lds_rf, st, ix, ra));

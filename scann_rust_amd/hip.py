@@ -46,7 +46,7 @@ EXPORTS = [
     "scann_hip_assign_leaves", "scann_hip_txh_partition", "scann_hip_lut_from_query",
     "scann_hip_adc_distances", "scann_hip_lut16_distances_batch", "scann_hip_encode",
     "scann_hip_fp8_quantize", "scann_hip_fp8_dequantize", "scann_hip_fp8_distances",
-    "scann_hip_bf_distances", "scann_hip_bf_search_radius", "scann_hip_bf_search_radius_opts", "scann_hip_allow_bitmap_count", "scann_hip_bf_assign_nearest",
+    "scann_hip_bf_distances", "scann_hip_bf_search_radius", "scann_hip_bf_search_radius_opts", "scann_hip_allow_bitmap_count", "scann_hip_allow_bitmaps_from_ids", "scann_hip_allow_bitmaps_from_ids_device", "scann_hip_bf_assign_nearest",
     "scann_hip_kmeans_init_pp", "scann_hip_kmeans_lloyd", "scann_hip_txh_pack_blocks_device", "scann_hip_index_size", "scann_hip_index_dimensionality",
     "scann_hip_index_destroy", "scann_hip_index_enable_timing",
     "scann_hip_index_last_kernel_ms",
@@ -116,6 +116,7 @@ class SearchOpts(C.Structure):
         ("cand_idx", u32p), ("cand_dist", f32p), ("cand_count", u32p),
         ("allow_bitmap", u64p), ("allow_bitmap_bits", C.c_uint64),
         ("bf_exact", C.c_int32),
+        ("allow_bitmap_stride", C.c_uint64),
     ]
 
 
@@ -224,6 +225,8 @@ def load():
                                                   C.c_uint64, C.POINTER(C.c_uint64)]
     L.scann_hip_allow_bitmap_count.restype = C.c_uint64
     L.scann_hip_allow_bitmap_count.argtypes = [u64p, C.c_uint64, C.c_uint64]
+    L.scann_hip_allow_bitmaps_from_ids.argtypes = [u32p, u64p, C.c_uint32, C.c_uint64, C.c_uint64, u64p]
+    L.scann_hip_allow_bitmaps_from_ids_device.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint64, C.c_uint64, vp, vp]
     L.scann_hip_index_size.restype = C.c_uint64
     L.scann_hip_index_size.argtypes = [vp]
     L.scann_hip_index_dimensionality.restype = C.c_uint32
@@ -322,7 +325,9 @@ class Index:
 
     def search_batched(self, queries, k, opts=None, q_dim=None, stages=False, allow=None, allow_bits=None):
         """`allow`: optional uint64 allow-bitmap (see allow_bitmap()) = search_with_filter.  `allow_bits`: its
-        capacity in bits (default: every word, allow.size * 64); indices at or past it are not allowed."""
+        capacity in bits (default: every word, allow.size * 64); indices at or past it are not allowed.  A 2-D
+        `allow` [nq, words] is one bitmap per query (allow_bitmap_stride = words; see allow_bitmaps_from_ids());
+        `allow_bits` is then the capacity every row shares (default words * 64)."""
         q = f32(queries)
         if q.ndim == 1:
             q = q[None]
@@ -334,8 +339,7 @@ class Index:
         o = opts if opts is not None else default_opts()
         extra = None
         if allow is not None:
-            allow = np.ascontiguousarray(allow, np.uint64)
-            o.allow_bitmap, o.allow_bitmap_bits = ptr(allow, u64p), _allow_capacity(allow, allow_bits)
+            allow = _bind_allow(o, allow, allow_bits, nq)
         if stages:
             P = o.partitions_to_search or 4096
             m = o.pre_reorder_k or 4096
@@ -355,7 +359,7 @@ class Index:
             if stages:
                 o.tokens = o.token_dists = o.cand_idx = o.cand_dist = o.cand_count = None
             if allow is not None:
-                o.allow_bitmap, o.allow_bitmap_bits = None, 0
+                o.allow_bitmap, o.allow_bitmap_bits, o.allow_bitmap_stride = None, 0, 0
         if stages:
             return out_idx[:, :k], out_dist[:, :k], out_cnt, extra
         return out_idx[:, :k], out_dist[:, :k], out_cnt
@@ -372,15 +376,14 @@ class Index:
         if allow is not None:
             if opts is None:
                 opts = default_opts()
-            allow = np.ascontiguousarray(allow, np.uint64)
-            opts.allow_bitmap, opts.allow_bitmap_bits = ptr(allow, u64p), _allow_capacity(allow, allow_bits)
+            allow = _bind_allow(opts, allow, allow_bits, nq)
         try:
             check(load().scann_hip_search_batched_params(self.h, ptr(q, f32p), nq, qs, qs, ptr(ks, u32p),
                                                          C.byref(opts) if opts is not None else None, pitch,
                                                          ptr(out_idx, u32p), ptr(out_dist, f32p), ptr(out_cnt, u32p)))
         finally:
             if allow is not None:   # (see search_batched)
-                opts.allow_bitmap, opts.allow_bitmap_bits = None, 0
+                opts.allow_bitmap, opts.allow_bitmap_bits, opts.allow_bitmap_stride = None, 0, 0
         return out_idx, out_dist, out_cnt
 
     def set_crowding_attributes(self, attrs):
@@ -402,14 +405,13 @@ class Index:
         out_cnt = np.zeros(nq, np.uint32)
         o = opts if opts is not None else default_opts()
         if allow is not None:
-            allow = np.ascontiguousarray(allow, np.uint64)
-            o.allow_bitmap, o.allow_bitmap_bits = ptr(allow, u64p), _allow_capacity(allow, allow_bits)
+            allow = _bind_allow(o, allow, allow_bits, nq)
         try:
             check(load().scann_hip_search_crowded(self.h, ptr(q, f32p), nq, qs, qd, k, depth, limit, C.byref(o),
                                                   ptr(out_idx, u32p), ptr(out_dist, f32p), ptr(out_cnt, u32p)))
         finally:
             if allow is not None:   # (see search_batched)
-                o.allow_bitmap, o.allow_bitmap_bits = None, 0
+                o.allow_bitmap, o.allow_bitmap_bits, o.allow_bitmap_stride = None, 0, 0
         return out_idx[:, :k], out_dist[:, :k], out_cnt
 
     def search_crowded_exact(self, query, k, limit, opts=None):
@@ -440,13 +442,12 @@ class Index:
         out_cnt = np.zeros(nq, np.uint32)
         o = opts if opts is not None else default_opts()
         if allow is not None:
-            allow = np.ascontiguousarray(allow, np.uint64)
-            o.allow_bitmap, o.allow_bitmap_bits = ptr(allow, u64p), _allow_capacity(allow, allow_bits)
+            allow = _bind_allow(o, allow, allow_bits, nq)
         try:
             check(call(ptr(q, f32p), nq, qs, qd, C.byref(o), ptr(out_idx, u32p), ptr(out_dist, f32p), ptr(out_cnt, u32p)))
         finally:
             if allow is not None:   # (see search_batched)
-                o.allow_bitmap, o.allow_bitmap_bits = None, 0
+                o.allow_bitmap, o.allow_bitmap_bits, o.allow_bitmap_stride = None, 0, 0
         return out_idx[:, :k], out_dist[:, :k], out_cnt
 
     @staticmethod
@@ -683,12 +684,34 @@ class Mutable:
 
 
 def _allow_capacity(allow, allow_bits):
-    """allow_bitmap_bits of a bitmap of allow.size words: every word, or the caller's capacity (at most that)"""
+    """allow_bitmap_bits of a bitmap of allow.size words (2-D: of each row's words): every word, or the caller's
+    capacity (at most that)"""
+    words = allow.shape[-1] if allow.ndim == 2 else allow.size
     if allow_bits is None:
-        return allow.size * 64
-    if not 0 <= int(allow_bits) <= allow.size * 64:
-        raise ValueError("allow_bits %d exceeds the bitmap's %d words" % (allow_bits, allow.size))
+        return words * 64
+    if not 0 <= int(allow_bits) <= words * 64:
+        raise ValueError("allow_bits %d exceeds the bitmap's %d words" % (allow_bits, words))
     return int(allow_bits)
+
+
+def _bind_allow(o, allow, allow_bits, nq):
+    """Points the opts at an allow-bitmap for one call and returns the array the pointer reads (keep it alive across
+    the call).  1-D: one bitmap for the batch.  2-D [nq, words]: one bitmap per query, its row pitch the stride."""
+    allow = np.ascontiguousarray(allow, np.uint64)
+    if allow.ndim == 2:
+        if allow.shape[0] != nq:
+            raise ValueError("a 2-D allow block needs one row per query: %d rows, %d queries" % (allow.shape[0], nq))
+        o.allow_bitmap_stride = allow.shape[1]
+        if allow.shape[1] == 0:   # (no words: capacity 0, nothing allowed; the library needs a non-null pointer)
+            allow = np.zeros((nq, 1), np.uint64)
+            o.allow_bitmap, o.allow_bitmap_bits, o.allow_bitmap_stride = ptr(allow, u64p), 0, 0
+            return allow
+    elif allow.ndim != 1:
+        raise ValueError("allow must be a 1-D bitmap or a 2-D [nq, words] block")
+    else:
+        o.allow_bitmap_stride = 0
+    o.allow_bitmap, o.allow_bitmap_bits = ptr(allow, u64p), _allow_capacity(allow, allow_bits)
+    return allow
 
 
 def crowd_table_slots(depth):
@@ -701,6 +724,33 @@ def allow_bitmap_count(allow, allow_bits, n):
     brute-force search is planned with"""
     allow = np.ascontiguousarray(allow, np.uint64)
     return int(load().scann_hip_allow_bitmap_count(ptr(allow, u64p), _allow_capacity(allow, allow_bits), int(n)))
+
+
+def allow_bitmaps_from_ids(ids, offsets, bits, stride_words=None):
+    """[nq, stride_words] uint64 block of per-query allow-bitmaps of capacity `bits` from id lists: query i's ids are
+    ids[offsets[i]:offsets[i + 1]] (RestrictAllowlist::from_indices per query; ids at or past `bits` are ignored,
+    duplicates and any order are fine).  stride_words defaults to ceil(bits / 64).  Host arithmetic, no GPU.  Pass
+    the block as `allow=` (2-D) with allow_bits=bits."""
+    ids = np.ascontiguousarray(ids, np.uint32).ravel()
+    off = np.ascontiguousarray(offsets, np.uint64).ravel()
+    if off.size < 1:
+        raise ValueError("offsets needs nq + 1 entries")
+    nq = off.size - 1
+    if int(off[-1]) > ids.size:
+        raise ValueError("offsets run past the id array")
+    words = (int(bits) + 63) // 64
+    stride = words if stride_words is None else int(stride_words)
+    out = np.empty((nq, stride), np.uint64)
+    check(load().scann_hip_allow_bitmaps_from_ids(ptr(ids, u32p) if ids.size else None, ptr(off, u64p), nq, int(bits),
+                                                  stride, ptr(out, u64p) if out.size else None))
+    return out
+
+
+def allow_bitmaps_from_ids_device(d_ids, d_offsets, nq, bits, stride_words, d_out_words, stream=0, device=0):
+    """scann_hip_allow_bitmaps_from_ids_device: device addresses (integers) and a HIP stream handle; a clear and one
+    scatter kernel are enqueued, nothing is synchronised.  d_out_words holds nq * stride_words uint64."""
+    check(load().scann_hip_allow_bitmaps_from_ids_device(context(device), vp(d_ids), vp(d_offsets), int(nq), int(bits),
+                                                         int(stride_words), vp(d_out_words), vp(stream)))
 
 
 def allow_bitmap(n, allowed):

@@ -504,6 +504,43 @@ inline std::vector<float> flatten(const std::vector<std::vector<float>> &qs, uin
     return flat;
 }
 
+// One allow-bitmap per query for scann_hip_search_opts.allow_bitmap_stride: row i = filters[i]->to_bitmap(n), a null
+// entry = every datapoint below n; rows are ceil(n / 64) words apart (*stride_words).
+inline std::vector<uint64_t> materialise_filters(const std::vector<const RestrictFilter *> &filters, size_t n,
+                                                 uint64_t *stride_words) {
+    const size_t words = (n + 63) / 64;
+    std::vector<uint64_t> block(filters.size() * words, 0);
+    for (size_t i = 0; i < filters.size(); ++i) {
+        uint64_t *row = block.data() + i * words;
+        if (filters[i]) {
+            const auto w = filters[i]->to_bitmap(n);
+            std::copy(w.begin(), w.begin() + std::min(w.size(), words), row);
+        } else {
+            std::fill(row, row + words, ~0ull);
+            if (n & 63) row[words - 1] = (1ull << (n & 63)) - 1;
+        }
+    }
+    *stride_words = words;
+    return block;
+}
+
+// search_with_filter for a batch: query i under filters[i] (null = no filter for that query), one call
+inline std::vector<NNResultsVector> run_search_filters(scann_hip_index *h, const std::vector<std::vector<float>> &queries,
+                                                       size_t k, const std::vector<const RestrictFilter *> &filters,
+                                                       size_t n, scann_hip_search_opts o) {
+    if (queries.size() != filters.size()) throw ScannError::invalid_argument("one filter (or null) per query");
+    if (queries.empty()) return {};
+    uint32_t d;
+    const auto flat = flatten(queries, &d);
+    uint64_t stride = 0;
+    const auto block = materialise_filters(filters, n, &stride);
+    const uint64_t none = 0;   // (n = 0: capacity 0, a non-null pointer no row reads)
+    o.allow_bitmap = block.empty() ? &none : block.data();
+    o.allow_bitmap_bits = n;
+    o.allow_bitmap_stride = stride;
+    return run_search(h, flat.data(), (uint32_t)queries.size(), d, d, (uint32_t)k, &o);
+}
+
 // splitmix64: the documented counter-based generator of this build (not rand::StdRng).
 inline uint64_t splitmix(uint64_t &s) {
     uint64_t z = (s += 0x9E3779B97F4A7C15ull);
@@ -863,6 +900,16 @@ public:
         o.exact_reorder = 0;
         return detail::run_search(ix_.h, flat.data(), (uint32_t)queries.size(), d, d, (uint32_t)k, &o);
     }
+    // search_with_filter for a batch: query i under filters[i] (null = everything allowed), materialised into one
+    // strided bitmap block (scann_hip_search_opts.allow_bitmap_stride) and searched in one call
+    std::vector<NNResultsVector> search_batched_with_filters(const std::vector<std::vector<float>> &queries, size_t k,
+                                                             const std::vector<const RestrictFilter *> &filters) const {
+        if (!ix_.h) return std::vector<NNResultsVector>(queries.size());
+        scann_hip_search_opts o;
+        scann_hip_search_opts_default(&o);
+        o.exact_reorder = 0;
+        return detail::run_search_filters(ix_.h, queries, k, filters, num_datapoints(), o);
+    }
     size_t num_datapoints() const { return n_; }
     size_t dimensionality() const { return dim_; }
     const std::vector<float> &codebook() const { return codebook_; }
@@ -1003,6 +1050,15 @@ public:
         uint32_t d;
         auto flat = detail::flatten(queries, &d);
         return detail::run_search(ix_.h, flat.data(), (uint32_t)queries.size(), d, d, (uint32_t)k, nullptr);
+    }
+    // search_with_filter for a batch: query i under filters[i] (null = everything allowed), materialised into one
+    // strided bitmap block (scann_hip_search_opts.allow_bitmap_stride) and searched in one call
+    std::vector<NNResultsVector> search_batched_with_filters(const std::vector<std::vector<float>> &queries, size_t k,
+                                                             const std::vector<const RestrictFilter *> &filters) const {
+        if (!ix_.h) throw ScannError::failed_precondition("Partitioner not built");
+        scann_hip_search_opts o;
+        scann_hip_search_opts_default(&o);
+        return detail::run_search_filters(ix_.h, queries, k, filters, num_datapoints(), o);
     }
     // Searcher::search_batched_with_params (tree_x_hybrid/mod.rs:399-409): params[i].num_neighbors per query
     std::vector<NNResultsVector> search_batched_with_params(const std::vector<std::vector<float>> &queries,
