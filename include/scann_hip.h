@@ -220,6 +220,31 @@ typedef struct {
 int scann_hip_txh_create(scann_hip_ctx *ctx, const scann_hip_txh_desc *desc,
                          scann_hip_index **out_index);
 
+/* A Tree-X-Hybrid / AsymmetricHasher index whose re-rank rows the caller stores quantized: the reordering stage of
+ * ScalarQuantizedBruteForceSearcher and its bf16 / FP8 siblings behind the tree or the hasher.  desc->data must be
+ * NULL; `rows` holds desc->n_rows rows of desc->stride ELEMENTS of row_format (SCANN_HIP_ROWS_BF16, _FP8_E4M3 or
+ * _INT8), indexed as desc->data would be (by datapoint index; AsymmetricHasher mode: datapoint = CSR order); elements
+ * past dim are never read.  inv_multiplier has the meaning documented at scann_hip_bf_create_quantized.
+ * Every stage before the re-rank is that of scann_hip_txh_create.  The merged candidates of a query then each get the
+ * distance a scann_hip_bf_create_quantized handle gives the same query and stored row under the same format,
+ * distance_measure and inv_multiplier, bit for bit (bf16 / FP8: one sequential f32 sum, no FMA; int8: 8 FMA lane
+ * chains, the fixed horizontal sum, an unfused tail; DotProduct negated, L2 = sqrtf of the squared sum), are stably
+ * sorted by it in merged order and truncated to k.  NaN and infinite distances order as on an f32 handle;
+ * exact_reorder = 0 returns approximate distances and reads no rows.
+ * The device holds the rows as given: no f32 copy and no 8-bit shadow store of the re-rank filter.  Every batch size
+ * takes the batched pipeline (the few-query pipelines re-rank from f32 rows).
+ * Works unchanged: scann_hip_search_batched(_params), scann_hip_index_reserve, scann_hip_search_batched_device,
+ * scann_hip_index_last_device_status, the crowded searches, allow-bitmaps per call and per query, the stage outputs,
+ * timing, scann_hip_index_write_file / scann_hip_index_load_file (sections "rows_q" and "rows_q_meta" = {format,
+ * inv_multiplier bits} in place of "data"; scann_hip_file_info.has_data is 0).
+ * Unimplemented on such a handle, each message naming quantized rows: scann_hip_search_mmr*, scann_hip_mutable_create /
+ * _rebase onto it, scann_hip_txh_search_local_device / _sharded_device, scann_hip_index_debug_rerank_brackets.
+ * Errors: all of scann_hip_txh_create's; desc->data != NULL, rows == NULL, unknown row_format, non-finite
+ * inv_multiplier for INT8 -> InvalidArgument; distance_measure L1 / Cosine, leaf_sizes_global != NULL,
+ * data_is_csr_order with partitions, SearchMode::Partitioned (no codes) -> Unimplemented. */
+int scann_hip_txh_create_quantized(scann_hip_ctx *ctx, const scann_hip_txh_desc *desc, const void *rows,
+                                   int row_format, float inv_multiplier, scann_hip_index **out_index);
+
 typedef struct {
     /* 0 = the index default.  SearchParameters.num_leaves_to_search is ignored by
      * the reference searcher; this knob exists for sweeps. */
@@ -662,8 +687,9 @@ int scann_hip_index_load_file(scann_hip_ctx *ctx, const char *path, scann_hip_in
  * when num_codes <= 16, one byte per subspace otherwise; a handle created without rows has no "data" section, and as
  * it keeps no row count, n_rows is written as the smallest count that holds every datapoint index).  This is
  * how an index made by scann_hip_fold_mutable is persisted; scann_hip_index_load_file on the file gives a handle that
- * searches identically.  Any unsharded f32 brute-force, tree, hasher or Partitioned handle; quantized brute-force
- * rows and shards (leaf_sizes_global) -> Unimplemented.  Transient host memory: one copy of the index. */
+ * searches identically.  Any unsharded f32 brute-force, tree, hasher or Partitioned handle, and tree / hasher handles
+ * over quantized rows (scann_hip_txh_create_quantized: "rows_q" / "rows_q_meta" instead of "data"); quantized
+ * brute-force rows and shards (leaf_sizes_global) -> Unimplemented.  Transient host memory: one copy of the index. */
 int scann_hip_index_write_file(const scann_hip_index *index, const char *path);
 
 /* ---- building blocks exposed for parity tests / callers ---------------------- */
@@ -981,6 +1007,10 @@ int scann_hip_fold_mutable_stage_ms(scann_hip_mutable *m, float *out_ms5);
 /* ---- introspection ------------------------------------------------------------- */
 uint64_t scann_hip_index_size(const scann_hip_index *index);          /* Searcher::dataset_size */
 uint32_t scann_hip_index_dimensionality(const scann_hip_index *index);/* Searcher::dimensionality */
+/* Bytes of the handle's persistent device allocations, any handle kind: rows (f32 or quantized), the 8-bit and bf16
+ * shadow stores and their per-row data, codes, sparse operand planes, ids, leaf tables, centres, codebook, attached
+ * crowding attributes.  Search workspaces are not counted.  NULL -> 0. */
+uint64_t scann_hip_index_device_bytes(const scann_hip_index *index);
 void scann_hip_index_destroy(scann_hip_index *index);
 
 /* Kernel timing hook for bench.py: mean HIP-event time (ms) of the dominant kernel over

@@ -235,6 +235,9 @@ struct scann_hip_index {
     // ---- tree-x-hybrid / AH ----
     TxhIndexDev tx{};
     DevBuf d_centers, d_centers_t, d_leaf_off, d_leaf_gsize, d_leaf_ids, d_codes, d_codes_sp, d_rows, d_codebook, d_rows8, d_rows8_meta;
+    DevBuf d_qrows;           // scann_hip_txh_create_quantized: the re-rank rows as given (d_rows, d_rows8 stay empty)
+    int q_fmt = 0;            // ... their SCANN_HIP_ROWS_* format (0: f32 rows or none) and the int8 inv_multiplier
+    float q_inv = 1.0f;
     std::vector<uint32_t> local_sizes_desc;  // local leaf sizes, descending, prefix-summed
     uint32_t default_P = 0;
     float multiplier = 3.0f;
@@ -260,7 +263,7 @@ struct scann_hip_index {
     DeviceSlot dslots[kMaxDeviceSlots];
     uint64_t dslot_tick = 0;
     bool sharded = false;     // created with leaf_sizes_global: local leaves are a subset of the global stream
-    uint64_t n_rows = 0;      // rows of d_rows (0: the handle stores none)
+    uint64_t n_rows = 0;      // rows of d_rows / d_qrows (0: the handle stores none)
 };
 
 static int set_device(const scann_hip_ctx *ctx) {
@@ -286,6 +289,7 @@ int scann::index_base_view(const scann_hip_index *ix, BaseView *v) {
         v->quantized = ix->bf.fmt != 0;
     } else {
         v->rows = ix->tx.rows;
+        v->quantized = ix->tx.qfmt != 0;
         v->n = ix->tx.n_local;
         v->dim = ix->tx.dim;
         v->stride = ix->tx.stride;
@@ -438,7 +442,14 @@ int scann::index_download(const scann_hip_index *ix, IndexHostArrays *o) {
         d.leaf_offsets = o->leaf_offsets.data();
         d.leaf_ids = o->leaf_ids.data();
     }
-    if (!t.rows) {   // a handle created without rows keeps no row count: the smallest that holds every datapoint index
+    if (t.qrows) {
+        o->rows_q.resize((size_t)ix->n_rows * t.stride * (t.qfmt == SCANN_HIP_ROWS_BF16 ? 2 : 1));
+        if (!o->rows_q.empty())
+            SCANN_HIP_CHECK(hipMemcpy(o->rows_q.data(), t.qrows, o->rows_q.size(), hipMemcpyDeviceToHost));
+        o->rows_q_fmt = t.qfmt;
+        o->rows_q_inv = t.inv_mult;
+    }
+    if (!t.rows && !t.qrows) {   // a handle created without rows keeps no row count: the smallest that holds every datapoint index
         d.n_rows = t.n_local;
         for (uint32_t id : o->leaf_ids) d.n_rows = std::max<uint64_t>(d.n_rows, (uint64_t)id + 1);
     }
@@ -697,9 +708,10 @@ int scann_hip_bf16_quantize(scann_hip_ctx *ctx, const float *values, uint64_t n,
 // content_status: what inconsistent array CONTENTS are reported as (InvalidArgument for caller-built
 // descriptors, DataLoss for index files, whose section sizes were already checked)
 int scann::txh_create_checked(scann_hip_ctx *ctx, const scann_hip_txh_desc *d, scann_hip_index **out,
-                              int content_status) {
+                              int content_status, const void *qrows, int qfmt, float qinv) {
     if (!ctx || !d || !out) return fail(SCANN_HIP_INVALID_ARGUMENT, "null ctx/desc/out_index");
     const bool ah = d->num_partitions == 0;
+    const bool has_rows = d->data || qrows;   // re-rank rows, f32 or quantized: indexed and validated alike
     if (d->n_local == 0)  // tree_x_hybrid/mod.rs:132-134, hashes/hasher.rs:110-112
         return fail(SCANN_HIP_INVALID_ARGUMENT, "Cannot build from empty dataset");
     if (d->n_local >= 0xFFFFFFFFull) return fail(SCANN_HIP_OUT_OF_RANGE, "DatapointIndex is u32");
@@ -744,16 +756,16 @@ int scann::txh_create_checked(scann_hip_ctx *ctx, const scann_hip_txh_desc *d, s
                 return fail(content_status, "leaf_sizes_global smaller than the local leaf");
         }
         // the re-rank and the exact leaf scan read data + leaf_ids[row] * stride
-        if (d->data && !d->data_is_csr_order)
+        if (has_rows && !d->data_is_csr_order)
             for (uint64_t i = 0; i < d->n_local; ++i)
                 if (d->leaf_ids[i] >= d->n_rows)
                     return fail(content_status, "leaf_ids entry " + std::to_string(i) + " >= n_rows");
     }
-    if (d->data && d->stride < d->dim) return fail(SCANN_HIP_INVALID_ARGUMENT, "stride < dim");
-    if (d->data && d->data_is_csr_order && d->n_rows != d->n_local)
+    if (has_rows && d->stride < d->dim) return fail(SCANN_HIP_INVALID_ARGUMENT, "stride < dim");
+    if (has_rows && d->data_is_csr_order && d->n_rows != d->n_local)
         return fail(SCANN_HIP_INVALID_ARGUMENT, "CSR-ordered data must have n_local rows");
     // AsymmetricHasher mode reads row i of data for CSR row i
-    if (d->data && ah && d->n_rows < d->n_local)
+    if (has_rows && ah && d->n_rows < d->n_local)
         return fail(content_status, "data has fewer rows than the index has points");
     SCANN_TRY(set_device(ctx));
 
@@ -834,7 +846,13 @@ int scann::txh_create_checked(scann_hip_ctx *ctx, const scann_hip_txh_desc *d, s
             return bail(s);
     }
 
-    ix->n_rows = d->data ? d->n_rows : 0;
+    if (qrows) {   // as given: no f32 copy, and txh_finish builds no 8-bit shadow store without d->data
+        const size_t qbytes = (size_t)d->n_rows * d->stride * (qfmt == SCANN_HIP_ROWS_BF16 ? 2 : 1);
+        if ((s = upload(ix->d_qrows, qrows, qbytes)) != SCANN_HIP_OK) return bail(s);
+        ix->q_fmt = qfmt;
+        ix->q_inv = qfmt == SCANN_HIP_ROWS_INT8 ? qinv : 1.0f;
+    }
+    ix->n_rows = has_rows ? d->n_rows : 0;
     if ((s = txh_finish(ix, d, off)) != SCANN_HIP_OK) return bail(s);
     *out = ix;
     return SCANN_HIP_OK;
@@ -903,6 +921,9 @@ static int txh_finish(scann_hip_index *ix, const scann_hip_txh_desc *d, const st
     t.rows = d->data ? ix->d_rows.as<float>() : nullptr;
     t.rows8 = nullptr;
     t.rows8_meta = nullptr;
+    t.qrows = ix->q_fmt ? ix->d_qrows.p : nullptr;
+    t.qfmt = ix->q_fmt;
+    t.inv_mult = ix->q_inv;
     // 8-bit copy of the rows for the re-rank filter (txh.hip K8b): +25 % of the row bytes.  Large indexes
     // only (the filter pays for long candidate lists); SCANN_HIP_RERANK_I8 = 0 never, 2 always.
     // SCANN_HIP_RERANK_STORE = int8 (default: per-row scaled integers, the tighter filter) or fp8 (the
@@ -995,6 +1016,47 @@ int scann_hip_txh_create(scann_hip_ctx *ctx, const scann_hip_txh_desc *d, scann_
     return scann::txh_create_checked(ctx, d, out, SCANN_HIP_INVALID_ARGUMENT);
 }
 
+}  // extern "C"
+
+// What scann_hip_txh_create_quantized and the index-file loader ask of a descriptor and its quantized rows before
+// the checks of scann_hip_txh_create.
+int scann::txh_quantized_args(const scann_hip_txh_desc *d, const void *rows, int row_format, float inv_multiplier) {
+    if (!d) return fail(SCANN_HIP_INVALID_ARGUMENT, "null ctx/desc/out_index");
+    if (d->data) return fail(SCANN_HIP_INVALID_ARGUMENT, "quantized rows: desc.data must be NULL (the rows are the `rows` argument)");
+    if (!rows) return fail(SCANN_HIP_INVALID_ARGUMENT, "quantized rows: rows is null");
+    if (row_format != SCANN_HIP_ROWS_BF16 && row_format != SCANN_HIP_ROWS_FP8_E4M3 && row_format != SCANN_HIP_ROWS_INT8)
+        return fail(SCANN_HIP_INVALID_ARGUMENT, "quantized rows: unknown row format " + std::to_string(row_format));
+    if (row_format == SCANN_HIP_ROWS_INT8 && !std::isfinite(inv_multiplier))
+        return fail(SCANN_HIP_INVALID_ARGUMENT, "quantized rows: inv_multiplier is not finite");
+    if (d->distance_measure == SCANN_HIP_L1 || d->distance_measure == SCANN_HIP_COSINE)
+        return fail(SCANN_HIP_UNIMPLEMENTED, "quantized rows: SquaredL2, L2 and DotProduct only");
+    if (d->leaf_sizes_global || (d->data_is_csr_order && d->num_partitions))
+        return fail(SCANN_HIP_UNIMPLEMENTED, "quantized rows in a leaf-sharded index are not built");
+    if (!d->codebook && !d->codes && d->num_subspaces == 0)
+        return fail(SCANN_HIP_UNIMPLEMENTED, "quantized rows in SearchMode::Partitioned (no codes) are not built");
+    return SCANN_HIP_OK;
+}
+
+extern "C" {
+
+int scann_hip_txh_create_quantized(scann_hip_ctx *ctx, const scann_hip_txh_desc *d, const void *rows, int row_format,
+                                   float inv_multiplier, scann_hip_index **out) {
+    if (!ctx || !d || !out) return fail(SCANN_HIP_INVALID_ARGUMENT, "null ctx/desc/out_index");
+    SCANN_TRY(scann::txh_quantized_args(d, rows, row_format, inv_multiplier));
+    return scann::txh_create_checked(ctx, d, out, SCANN_HIP_INVALID_ARGUMENT, rows, row_format, inv_multiplier);
+}
+
+uint64_t scann_hip_index_device_bytes(const scann_hip_index *ix) {
+    if (!ix) return 0;
+    uint64_t sum = 0;
+    for (const DevBuf *b : {&ix->bf_rows, &ix->bf_rows_b, &ix->bf_rows_bl, &ix->bf_norm2, &ix->bf_leaf, &ix->d_centers,
+                            &ix->d_centers_t, &ix->d_leaf_off, &ix->d_leaf_gsize, &ix->d_leaf_ids, &ix->d_codes,
+                            &ix->d_codes_sp, &ix->d_rows, &ix->d_codebook, &ix->d_rows8, &ix->d_rows8_meta, &ix->d_qrows,
+                            &ix->crowd_attrs, &ix->crowd_md_attrs})
+        if (b->p) sum += b->bytes;
+    return sum;
+}
+
 // ---- per-call planning --------------------------------------------------------------
 static uint64_t max_stream(const scann_hip_index *ix, uint32_t P) {
     uint64_t s = 0;
@@ -1038,6 +1100,9 @@ static int plan_txh_search(const scann_hip_index *ix, uint32_t k, const scann_hi
     const TxhIndexDev &t = ix->tx;
     bool full_cap = retry;
     if (retry && widest == TxhPipeline::Wide) widest = TxhPipeline::Small;
+    // rows stored quantized: the small and wide pipelines re-rank inside their finish kernels from f32 rows, so every
+    // batch size takes the staged pipeline, whose re-rank is a kernel of its own
+    if (t.qfmt) widest = TxhPipeline::Staged;
     uint32_t P = o->partitions_to_search ? o->partitions_to_search : ix->default_P;
     P = std::min(P, t.L);  // tree_partitioner.rs:214
     if (t.ah_mode) P = 1;
@@ -1061,7 +1126,7 @@ static int plan_txh_search(const scann_hip_index *ix, uint32_t k, const scann_hi
         return fail(SCANN_HIP_UNIMPLEMENTED,
                     "pre-reorder candidate count " + std::to_string(m) + " exceeds " +
                         std::to_string(kMaxPreReorderK));
-    if (exact_reorder && !t.rows)  // hasher.rs:194-197
+    if (exact_reorder && !t.rows && !t.qrows)  // hasher.rs:194-197
         return fail(SCANN_HIP_FAILED_PRECONDITION, "Dataset not stored");
     const uint64_t stream = std::max<uint64_t>(1, max_stream(ix, P));
     const uint64_t ms = std::min<uint64_t>(stream, 0xFFFFFFFFull);
@@ -1193,7 +1258,7 @@ static int plan_txh_search(const scann_hip_index *ix, uint32_t k, const scann_hi
     // int8 re-rank filter: lists of a few hundred candidates and more
     p.use_i8 = t.rows8 && exact_reorder && m >= kn.rerank_i8_min && m > 4 * k;
     p.i8_expand = kn.rerank_expand;
-    p.local_prune = kn.local_prune;
+    p.local_prune = kn.local_prune && !t.qfmt;
     *out = p;
     return SCANN_HIP_OK;
 }
@@ -1217,6 +1282,7 @@ static const char *txh_kernel_name(const TxhIndexDev &t, const TxhPlan &p, bool 
 
 int scann::txh_resolve_m(scann_hip_index *ix, uint32_t k, const scann_hip_search_opts *opts, uint32_t *out_m) {
     if (!ix || ix->kind != KIND_TXH) return fail(SCANN_HIP_INVALID_ARGUMENT, "not a tree index");
+    if (ix->tx.qfmt) return fail(SCANN_HIP_UNIMPLEMENTED, "the leaf-sharded search over quantized rows is not built");
     scann_hip_search_opts o;
     if (opts) o = *opts; else scann_hip_search_opts_default(&o);
     o.exact_reorder = 1;
@@ -1960,6 +2026,8 @@ int scann_hip_index_debug_filter_bounds(scann_hip_index *ix, void *hip_stream, u
 int scann_hip_index_debug_rerank_brackets(scann_hip_index *ix, void *hip_stream, uint32_t nq, uint32_t m, uint32_t *out_lb,
                                           uint32_t *out_ub, uint32_t *out_rows, uint32_t *out_counts) {
     if (!ix || ix->kind != KIND_TXH) return fail(SCANN_HIP_INVALID_ARGUMENT, "not a tree / hasher index");
+    if (ix->tx.qfmt)
+        return fail(SCANN_HIP_UNIMPLEMENTED, "a handle over quantized rows has no re-rank row filter: no brackets to read");
     if (nq && m && (!out_lb || !out_ub || !out_rows || !out_counts))
         return fail(SCANN_HIP_INVALID_ARGUMENT, "an output is null");
     SCANN_TRY(set_device(ix->ctx));
@@ -2042,6 +2110,7 @@ static int mmr_rows(const scann_hip_index *ix, const float **rows, uint64_t *n, 
         return SCANN_HIP_OK;
     }
     if (ix->sharded) return fail(SCANN_HIP_UNIMPLEMENTED, "MMR on a shard (leaf_sizes_global) is not built");
+    if (ix->tx.qfmt) return fail(SCANN_HIP_UNIMPLEMENTED, "MMR over quantized rows is not built");
     if (!ix->tx.rows) return fail(SCANN_HIP_FAILED_PRECONDITION, "MMR needs the handle's f32 rows (desc.data)");
     if (ix->tx.rows_csr && !ix->tx.ah_mode)
         return fail(SCANN_HIP_UNIMPLEMENTED, "MMR over rows held in CSR order is not built");
@@ -2383,6 +2452,7 @@ int scann_hip_txh_search_local_device(scann_hip_index *ix, const float *d_querie
                                       uint32_t *d_idx, float *d_exact, uint32_t *d_count,
                                       void *hip_stream) {
     if (!ix || ix->kind != KIND_TXH) return fail(SCANN_HIP_INVALID_ARGUMENT, "not a tree index");
+    if (ix->tx.qfmt) return fail(SCANN_HIP_UNIMPLEMENTED, "the local stage of a sharded search over quantized rows is not built");
     SCANN_TRY(refuse_allow_stride(opts, "the leaf-sharded search"));
     if (nq == 0) return SCANN_HIP_OK;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);

@@ -15,8 +15,12 @@ namespace scann {
 void set_last_error(const std::string &msg);
 int fail(int status, const std::string &msg);
 // scann_hip_txh_create with the status reported for inconsistent array CONTENTS (api.hip)
+// qrows != nullptr: scann_hip_txh_create_quantized -- d->data is NULL and the re-rank rows are qrows, n_rows rows of
+// d->stride elements of qfmt (SCANN_HIP_ROWS_*), int8 values scaled by qinv
 int txh_create_checked(scann_hip_ctx *ctx, const scann_hip_txh_desc *d, scann_hip_index **out,
-                       int content_status);
+                       int content_status, const void *qrows = nullptr, int qfmt = 0, float qinv = 1.0f);
+// the argument checks scann_hip_txh_create_quantized makes before those of scann_hip_txh_create (api.hip)
+int txh_quantized_args(const scann_hip_txh_desc *d, const void *rows, int row_format, float inv_multiplier);
 
 #define SCANN_HIP_CHECK(expr)                                                         \
     do {                                                                              \

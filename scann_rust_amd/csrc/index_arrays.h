@@ -12,6 +12,9 @@ struct IndexHostArrays {
     scann_hip_txh_desc d{};   // scalar fields; the pointers address the vectors below
     std::vector<float> data, centers, codebook;
     std::vector<uint32_t> leaf_offsets, leaf_ids, codes;   // codes: the device's packed words
+    std::vector<uint8_t> rows_q;                           // quantized re-rank rows as stored (d.data is then null) ...
+    int rows_q_fmt = 0;                                    // ... their SCANN_HIP_ROWS_* format, 0 = none ...
+    float rows_q_inv = 1.0f;                               // ... and the int8 inv_multiplier
 };
 int index_download(const scann_hip_index *ix, IndexHostArrays *out);
 

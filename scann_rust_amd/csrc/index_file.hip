@@ -6,6 +6,7 @@
 #include <unistd.h>
 
 #include <cerrno>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -181,11 +182,10 @@ int section(const Mapping &m, const char *path, const char *name, uint64_t want,
     return SCANN_HIP_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int scann_hip_txh_write_file(const char *path, const scann_hip_txh_desc *d) {
+// scann_hip_txh_write_file, and with rows_q != nullptr the file of a handle over quantized rows: no `data` section,
+// the rows' bytes in `rows_q`, {format, inv_multiplier bits} in `rows_q_meta`
+int write_txh(const char *path, const scann_hip_txh_desc *d, const void *rows_q, uint64_t rows_q_bytes, int rows_q_fmt,
+              float rows_q_inv) {
     if (!path || !d) return fail(SCANN_HIP_INVALID_ARGUMENT, "path/desc is null");
     const bool ah = d->num_partitions == 0;
     const bool exact = !d->codebook && !d->codes && d->num_subspaces == 0;
@@ -210,6 +210,12 @@ int scann_hip_txh_write_file(const char *path, const scann_hip_txh_desc *d) {
     h.pre_reorder_multiplier = d->pre_reorder_multiplier;
     std::vector<PendingSection> secs;
     if (d->data) secs.push_back({"data", DT_F32, d->data, (uint64_t)d->n_rows * d->stride * 4});
+    uint32_t q_meta[2] = {(uint32_t)rows_q_fmt, 0u};
+    std::memcpy(&q_meta[1], &rows_q_inv, 4);
+    if (rows_q) {
+        secs.push_back({"rows_q", DT_U8, rows_q, rows_q_bytes});
+        secs.push_back({"rows_q_meta", DT_U32, q_meta, sizeof(q_meta)});
+    }
     if (!ah) {
         secs.push_back({"centers", DT_F32, d->centers, (uint64_t)d->num_partitions * d->dim * 4});
         secs.push_back({"leaf_offsets", DT_U32, d->leaf_offsets, ((uint64_t)d->num_partitions + 1) * 4});
@@ -224,6 +230,14 @@ int scann_hip_txh_write_file(const char *path, const scann_hip_txh_desc *d) {
         secs.push_back({"codes", DT_U8, d->codes, d->n_local * bpp});
     }
     return write_container(path, h, secs);
+}
+
+}  // namespace
+
+extern "C" {
+
+int scann_hip_txh_write_file(const char *path, const scann_hip_txh_desc *d) {
+    return write_txh(path, d, nullptr, 0, 0, 1.0f);
 }
 
 int scann_hip_bf_write_file(const char *path, const float *data, uint64_t n, uint32_t dim, uint32_t stride,
@@ -247,6 +261,7 @@ int scann_hip_index_write_file(const scann_hip_index *index, const char *path) {
     SCANN_TRY(scann::index_download(index, &a));
     if (a.brute_force)
         return scann_hip_bf_write_file(path, a.d.data, a.d.n_rows, a.d.dim, a.d.stride, a.d.distance_measure);
+    if (a.rows_q_fmt) return write_txh(path, &a.d, a.rows_q.data(), a.rows_q.size(), a.rows_q_fmt, a.rows_q_inv);
     return scann_hip_txh_write_file(path, &a.d);
 }
 
@@ -329,6 +344,22 @@ int scann_hip_index_load_file(scann_hip_ctx *ctx, const char *path, scann_hip_in
         d.codebook = static_cast<const float *>(p);
         SCANN_TRY(section(m, path, "codes", bytes3(h.n_local, bpp, 1), true, &p));
         d.codes = static_cast<const uint8_t *>(p);
+    }
+    if (m.find("rows_q")) {   // a handle over quantized rows: the rows as stored, their format and inv_multiplier
+        SCANN_TRY(section(m, path, "rows_q_meta", 8, true, &p));
+        uint32_t meta[2];
+        std::memcpy(meta, p, 8);
+        const int fmt = (int)meta[0];
+        float inv;
+        std::memcpy(&inv, &meta[1], 4);
+        if (fmt != SCANN_HIP_ROWS_BF16 && fmt != SCANN_HIP_ROWS_FP8_E4M3 && fmt != SCANN_HIP_ROWS_INT8)
+            return fail(SCANN_HIP_DATA_LOSS, std::string(path) + ": rows_q_meta names no row format");
+        if (fmt == SCANN_HIP_ROWS_INT8 && !std::isfinite(inv))
+            return fail(SCANN_HIP_DATA_LOSS, std::string(path) + ": rows_q_meta holds a non-finite inv_multiplier");
+        if (d.data) return fail(SCANN_HIP_DATA_LOSS, std::string(path) + ": both 'data' and 'rows_q' sections");
+        SCANN_TRY(section(m, path, "rows_q", bytes3(h.n_rows, h.stride, fmt == SCANN_HIP_ROWS_BF16 ? 2 : 1), true, &p));
+        SCANN_TRY(scann::txh_quantized_args(&d, p, fmt, inv));
+        return scann::txh_create_checked(ctx, &d, out, SCANN_HIP_DATA_LOSS, p, fmt, inv);
     }
     return scann::txh_create_checked(ctx, &d, out, SCANN_HIP_DATA_LOSS);
 }

@@ -117,6 +117,11 @@ struct TxhIndexDev {
     int ah_mode;                  // single implicit leaf, no centroid stage
     int measure;                  // measure of the exact re-rank and of the exact leaf scan
     int exact_scan;               // SearchMode::Partitioned: no codes, rows of the leaves scored exactly
+    // scann_hip_txh_create_quantized: the re-rank rows as the caller stores them (indexed as `rows` would be, `stride`
+    // ELEMENTS apart); `rows` and `rows8` are then nullptr and the re-rank is rerank_quant_kernel (txh_rows.hip)
+    const void *qrows;
+    int qfmt;                     // SCANN_HIP_ROWS_BF16 / _FP8_E4M3 / _INT8; 0 = f32 rows or none
+    float inv_mult;               // int8 rows: value = (float)i8 * inv_mult
 };
 
 // points of one scan tile chunk for this index's code layout (Codec<S, bits>::TP in txh_dev.h)

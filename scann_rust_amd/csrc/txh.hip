@@ -3055,6 +3055,8 @@ static int launch_select(const TxhIndexDev &ix, const TxhWork &w, bool local_onl
 }
 
 static int launch_rerank(const TxhIndexDev &ix, const TxhWork &w, bool local_only, hipStream_t st) {
+    // rows stored quantized: every candidate scored from its stored row (txh_rows.hip K8q); the final kernels finish
+    if (ix.qfmt) return launch_rerank_quant(ix, w, st);
     const bool unsorted = select_unsorted(w, local_only);
     const size_t lds_rr = (size_t)ix.dim * 4;
     // int8 row filter in front of the exact re-rank (K8b): single-GPU final stage, squared L2, lists long

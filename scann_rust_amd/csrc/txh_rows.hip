@@ -1,6 +1,8 @@
 // txh_rows.hip -- the 8-bit row stores of the exact re-rank's row filter (K8b, described in txh.hip): the int8 and FP8
-// store builds, the reference's FP8 codec, and rerank_i8_kernel, which brackets every candidate from its 8-bit row.
+// store builds, the reference's FP8 codec, and rerank_i8_kernel, which brackets every candidate from its 8-bit row;
+// and rerank_quant_kernel (K8q), the re-rank of a handle whose rows the caller stores as bf16, FP8 E4M3 or int8.
 #include "launch.h"
+#include "quant.h"
 #include "txh_stages.h"
 
 namespace scann {
@@ -386,6 +388,128 @@ int launch_rerank_i8(const TxhIndexDev &ix, const TxhWork &w, hipStream_t st) {
             constexpr int EX = v() == 0 ? 0 : (v() == 1 && e() > 1) ? 1 : e();
             return launch((rerank_i8_kernel<v() == 1 ? 1 : 0, v() == 2, EX>), dim3(ceil_div_u32(w.m, kI8PerBlock), w.nq),
                           dim3(256), lds_rr, st, ix.dim, ia);
+        });
+    });
+}
+
+// =====================================================================================
+// K8q: re-rank over rows stored quantized (scann_hip_txh_create_quantized).  Every candidate gets the distance a
+// quantized brute-force handle gives the same query and row (bf_quant_kernel's arithmetic, quant.h): bf16 / FP8 one
+// sequential f32 sum, no FMA; int8 8 FMA chains over full 8-element chunks, horizontal_sum_avx, an unfused tail.
+// A sequential sum cannot be split over lanes, so one lane owns one candidate -- and 64 lanes walking 64 different
+// rows straight from global memory would fetch a cache line per lane and step.  Instead the workgroup's 256 candidate
+// rows pass through LDS in pieces of 128 bytes (one cache line): a group of 8 lanes loads one row's piece as 8 x 16
+// bytes, a wave 8 rows per instruction, and every lane has its 8 rows' loads in flight before the first LDS store.
+// Row pitch 33 dwords: lane t reads dword 33 t + j, bank (t + j) mod 32 -- no conflict among the 32 lanes of a
+// ds_read_b32 group; the stores (row r, dword 4 l8 + i -> bank (r + 4 l8 + i) mod 32, r < 4 per group) have none either.
+// The gather of one workgroup overlaps the chains of the others on its CU (35 KB of LDS: four workgroups per CU).
+// Rows whose byte stride or base is not a multiple of 16, and the piece that holds a row's last bytes when those are
+// not 16, are copied byte by byte: no element past dim is read.  Row offsets are 64-bit.
+// =====================================================================================
+constexpr uint32_t kQrTile = 256;                  // candidates per workgroup, one per lane
+constexpr uint32_t kQrPiece = 128;                 // row bytes in LDS at a time
+constexpr uint32_t kQrPitchW = kQrPiece / 4 + 1;   // dwords from one row's piece to the next
+
+static inline size_t rerank_quant_lds(uint32_t dim) {
+    return ((size_t)((dim + 3u) & ~3u) + kQrTile + (size_t)kQrTile * kQrPitchW) * 4;
+}
+
+template <int FMT, int MEASURE>
+__global__ __launch_bounds__(256) void rerank_quant_kernel(TxhIndexDev ix, const float *__restrict__ queries,
+                                                           uint32_t q_stride, uint32_t m,
+                                                           const uint32_t *__restrict__ cand_row,
+                                                           const uint32_t *__restrict__ cand_count,
+                                                           float *__restrict__ cand_exact) {
+    constexpr uint32_t B = quant_bytes<FMT>(), EPW = 4 / B;   // bytes per element, elements per dword
+    constexpr bool FUSED = FMT == SCANN_HIP_ROWS_INT8;
+    constexpr int NCH = FUSED ? 8 : 1;
+    extern __shared__ __attribute__((aligned(16))) float s_q[];   // [dim, padded to 4] query | [256] rows | [256][33] tile
+    const uint32_t q = blockIdx.y, tid = threadIdx.x, dim = ix.dim;
+    const uint32_t nsel = cand_count[q];
+    const uint32_t c0 = blockIdx.x * kQrTile;
+    if (c0 >= nsel) return;   // uniform
+    const uint32_t cnt = min(kQrTile, nsel - c0);
+    uint32_t *s_row = reinterpret_cast<uint32_t *>(s_q + ((dim + 3u) & ~3u));
+    uint32_t *s_tile = s_row + kQrTile;
+    for (uint32_t j = tid; j < dim; j += 256) s_q[j] = queries[(size_t)q * q_stride + j];
+    s_row[tid] = tid < cnt ? cand_row[(size_t)q * m + c0 + tid] : 0u;
+    __syncthreads();
+    const uint8_t *base = static_cast<const uint8_t *>(ix.qrows);
+    const size_t row_bytes = (size_t)ix.stride * B;
+    const bool vec = (row_bytes & 15u) == 0 && (reinterpret_cast<uintptr_t>(base) & 15u) == 0;
+    const uint32_t l8 = tid & 7u, g = tid >> 3, off = l8 * 16u;
+    const uint32_t dim_bytes = dim * B;
+    const bool act = tid < cnt;
+    const float inv = ix.inv_mult;
+    const uint32_t *trow = s_tile + (size_t)tid * kQrPitchW;
+    f32x2q acc[NCH];
+#pragma unroll
+    for (int t = 0; t < NCH; ++t) acc[t] = f32x2q{0.0f, 0.0f};
+    for (uint32_t b0 = 0; b0 < dim_bytes; b0 += kQrPiece) {
+        const uint32_t valid = min(kQrPiece, dim_bytes - b0);                  // bytes of the rows in this piece
+        const uint32_t nb = off < valid ? min(16u, valid - off) : 0u;          // ... of them in this lane's 16
+        if (vec && nb == 16u) {
+            uint4 v[8];
+#pragma unroll
+            for (int p = 0; p < 8; ++p) {   // the 8 rows' loads first: all in flight together
+                const uint32_t r = g + 32u * p;
+                v[p] = make_uint4(0u, 0u, 0u, 0u);
+                if (r < cnt) v[p] = *reinterpret_cast<const uint4 *>(base + (size_t)s_row[r] * row_bytes + b0 + off);
+            }
+#pragma unroll
+            for (int p = 0; p < 8; ++p) {
+                const uint32_t r = g + 32u * p;
+                if (r < cnt) {
+                    uint32_t *d = s_tile + (size_t)r * kQrPitchW + l8 * 4u;
+                    d[0] = v[p].x; d[1] = v[p].y; d[2] = v[p].z; d[3] = v[p].w;
+                }
+            }
+        } else if (nb) {
+            for (uint32_t r = g; r < cnt; r += 32u) {
+                const uint8_t *src = base + (size_t)s_row[r] * row_bytes + b0 + off;
+                uint8_t *d = reinterpret_cast<uint8_t *>(s_tile + (size_t)r * kQrPitchW) + off;
+                for (uint32_t i = 0; i < nb; ++i) d[i] = src[i];
+            }
+        }
+        __syncthreads();
+        const uint32_t e0 = b0 / B, ne = valid / B, full = ne & ~7u;
+        if (act) {
+            for (uint32_t j = 0; j < full; j += 8) {   // full 8-element chunks (int8: the FMA chains)
+                uint32_t w[8 / EPW];
+#pragma unroll
+                for (int i = 0; i < (int)(8 / EPW); ++i) w[i] = trow[j / EPW + i];
+#pragma unroll
+                for (int t = 0; t < 8; ++t)
+                    quant_step<MEASURE, FUSED>(acc[FUSED ? t : 0], f32x2q{s_q[e0 + j + t], 0.0f},
+                                               quant_decode<FMT>(w[t / (int)EPW], t % (int)EPW, inv));
+            }
+            if (b0 + kQrPiece >= dim_bytes) {   // the row's last piece: the tail, then the result
+                f32x2q r = acc[0];
+                if constexpr (FUSED)   // horizontal_sum_avx
+                    r = ((acc[0] + acc[4]) + (acc[1] + acc[5])) + ((acc[2] + acc[6]) + (acc[3] + acc[7]));
+                for (uint32_t j = full; j < ne; ++j)   // bf16 / FP8: the rest of the sequential sum; int8: the unfused tail
+                    quant_step<MEASURE, false>(r, f32x2q{s_q[e0 + j], 0.0f},
+                                               quant_decode<FMT>(trow[j / EPW], (int)(j % EPW), inv));
+                float dist = r.x;
+                if (MEASURE == SCANN_HIP_DOT_PRODUCT) dist = -dist;
+                if (MEASURE == SCANN_HIP_L2) dist = sqrtf(dist);
+                cand_exact[(size_t)q * m + c0 + tid] = dist;
+            }
+        }
+        __syncthreads();   // the next piece overwrites the tile
+    }
+}
+
+int launch_rerank_quant(const TxhIndexDev &ix, const TxhWork &w, hipStream_t st) {
+    return with_row_format(ix.qfmt, [&](auto fmt) {
+        return with_dot_measure(ix.measure, [&](auto ms) {
+            if constexpr (fmt() == 0) {
+                return fail(SCANN_HIP_INTERNAL, "quantized re-rank without quantized rows");
+            } else {
+                return launch((rerank_quant_kernel<fmt(), ms()>), dim3(ceil_div_u32(w.m, kQrTile), w.nq), dim3(256),
+                              rerank_quant_lds(ix.dim), st, ix, w.queries, w.q_stride, w.m, w.cand_row, w.cand_count,
+                              w.cand_exact);
+            }
         });
     });
 }

@@ -26,5 +26,7 @@ int launch_prefilter_refine(const TxhIndexDev &ix, const TxhWork &w, hipStream_t
 
 // ---- txh_rows.hip: the 8-bit row stores of the re-rank filter (K8b) ----
 int launch_rerank_i8(const TxhIndexDev &ix, const TxhWork &w, hipStream_t st);
+// ... and the re-rank of a handle whose rows are stored quantized (ix.qrows): cand_exact of every candidate
+int launch_rerank_quant(const TxhIndexDev &ix, const TxhWork &w, hipStream_t st);
 
 }  // namespace scann

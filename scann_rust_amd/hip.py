@@ -33,7 +33,7 @@ _CODE_NAMES = {
 EXPORTS = [
     "scann_hip_init", "scann_hip_shutdown", "scann_hip_last_error", "scann_hip_version",
     "scann_hip_compute_stride", "scann_hip_bf_create", "scann_hip_bf_create_quantized", "scann_hip_bf16_quantize",
-    "scann_hip_txh_create",
+    "scann_hip_txh_create", "scann_hip_txh_create_quantized", "scann_hip_index_device_bytes",
     "scann_hip_search_opts_default", "scann_hip_search_batched", "scann_hip_search_batched_params", "scann_hip_index_reserve",
     "scann_hip_search_batched_device", "scann_hip_index_last_device_status", "scann_hip_index_debug_filter_bounds",
     "scann_hip_index_debug_rerank_brackets",
@@ -145,6 +145,9 @@ def load():
                                                 C.c_int, C.POINTER(vp)]
     L.scann_hip_bf16_quantize.argtypes = [vp, f32p, C.c_uint64, u16p]
     L.scann_hip_txh_create.argtypes = [vp, C.POINTER(TxhDesc), C.POINTER(vp)]
+    L.scann_hip_txh_create_quantized.argtypes = [vp, C.POINTER(TxhDesc), vp, C.c_int, C.c_float, C.POINTER(vp)]
+    L.scann_hip_index_device_bytes.restype = C.c_uint64
+    L.scann_hip_index_device_bytes.argtypes = [vp]
     L.scann_hip_txh_write_file.argtypes = [C.c_char_p, C.POINTER(TxhDesc)]
     L.scann_hip_bf_write_file.argtypes = [C.c_char_p, f32p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int]
     L.scann_hip_index_file_info.argtypes = [C.c_char_p, C.POINTER(FileInfo)]
@@ -322,6 +325,11 @@ class Index:
 
     def dimensionality(self):
         return int(load().scann_hip_index_dimensionality(self.h))
+
+    def device_bytes(self):
+        """Bytes of the handle's persistent device allocations, search workspaces excluded
+        (scann_hip_index_device_bytes)."""
+        return int(load().scann_hip_index_device_bytes(self.h))
 
     def search_batched(self, queries, k, opts=None, q_dim=None, stages=False, allow=None, allow_bits=None):
         """`allow`: optional uint64 allow-bitmap (see allow_bitmap()) = search_with_filter.  `allow_bits`: its
@@ -821,6 +829,23 @@ def txh_create(*, data, n_rows, dim, stride, centers, leaf_offsets, leaf_ids, co
                         data_is_csr_order=data_is_csr_order, distance_measure=distance_measure)
     h = vp()
     check(load().scann_hip_txh_create(context(device), C.byref(d), C.byref(h)))
+    return Index(h)
+
+
+def txh_create_quantized(*, rows, fmt, inv_multiplier=1.0, device=0, **desc):
+    """A tree / hasher index whose re-rank rows are stored as bf16 bits (uint16), the reference's E4M3 codes (uint8) or
+    int8 (value = i8 * inv_multiplier): scann_hip_txh_create_quantized.  `rows` [n_rows, stride] elements, indexed as
+    txh_create's data; `desc`: txh_create's keyword arguments without data."""
+    if desc.get("data") is not None:
+        raise ValueError("txh_create_quantized takes rows=, not data=")
+    desc["data"] = None
+    d, keep = _txh_desc(**desc)
+    r = None if rows is None else np.ascontiguousarray(rows).view(_ROWS_DTYPE.get(fmt, np.uint8))
+    if r is not None and r.size < d.n_rows * d.stride:
+        raise ValueError("rows holds %d elements, n_rows * stride = %d" % (r.size, d.n_rows * d.stride))
+    h = vp()
+    check(load().scann_hip_txh_create_quantized(context(device), C.byref(d), r.ctypes.data if r is not None else None,
+                                                fmt, float(np.float32(inv_multiplier)), C.byref(h)))
     return Index(h)
 
 

@@ -131,6 +131,25 @@ static void tree_x_hybrid_tests() {
         try { TreeXHybridSearcher::load(path); } catch (const ScannError &e) { missing = e.code == ErrorCode::NotFound; }
         EXPECT(missing);
     }
+    {   // the same index over bf16 rows (with_quantized_rows): sin values lose little in bf16, and a saved file reloads
+        const DenseDataset ds = sin_dataset(500, 32);
+        std::vector<uint16_t> rows16(500 * 37, 0x7FC0);   // stride 37: junk in the padding
+        for (size_t i = 0; i < 500; ++i) {
+            uint16_t tmp[32];
+            EXPECT(scann_hip_bf16_quantize(context(0), ds.get(i), 32, tmp) == SCANN_HIP_OK);
+            std::copy(tmp, tmp + 32, rows16.begin() + i * 37);
+        }
+        auto qs = s.with_quantized_rows(rows16.data(), SCANN_HIP_ROWS_BF16, 1.0f, 37);
+        auto qr = qs.search(q, 10);
+        EXPECT(qr.size() == 10);
+        sorted(qr);
+        for (auto &p : qr) EXPECT(p.first < 500 && p.second == p.second);
+        const std::string path = "/tmp/scann_host_test_q_" + std::to_string((long)getpid()) + ".scannidx";
+        qs.save(path);
+        auto loaded = TreeXHybridSearcher::load(path);
+        EXPECT(loaded.search(q, 10) == qr);
+        std::remove(path.c_str());
+    }
     // TreeXHybridConfig::default(): 100 partitions, search 10, 256 codes x 8 subspaces (mod.rs:37-48)
     TreeXHybridSearcher dflt{TreeXHybridConfig()};
     dflt.build(sin_dataset(3000, 32));

@@ -1081,8 +1081,29 @@ public:
     // without a second host copy.
     void save(const std::string &path) const {
         if (!ix_.h || !dataset_) throw ScannError::failed_precondition("Partitioner not built");
+        if (quantized_) {   // the rows live on the device only, as stored: sections rows_q / rows_q_meta
+            check(scann_hip_index_write_file(ix_.h, path.c_str()));
+            return;
+        }
         const scann_hip_txh_desc d = desc();
         check(scann_hip_txh_write_file(path.c_str(), &d));
+    }
+    // This searcher's trained index (centres, codebook, codes) over re-rank rows the caller stores quantized
+    // (scann_hip_txh_create_quantized): n rows of `stride` elements of row_format (SCANN_HIP_ROWS_BF16 / _FP8_E4M3 /
+    // _INT8; int8 value = i8 * inv_multiplier), by datapoint index.  The new searcher keeps no f32 rows on the device;
+    // it re-ranks with the arithmetic of a quantized brute-force handle.  load() reads a file it saved.
+    TreeXHybridSearcher with_quantized_rows(const void *rows, int row_format, float inv_multiplier, uint32_t stride) const {
+        if (!ix_.h || !dataset_) throw ScannError::failed_precondition("Partitioner not built");
+        TreeXHybridSearcher s(config_, device_);
+        s.dataset_ = dataset_;
+        s.centers_ = centers_; s.codebook_ = codebook_; s.leaf_off_ = leaf_off_; s.leaf_ids_ = leaf_ids_; s.codes_ = codes_;
+        s.n_ = n_; s.dim_ = dim_;
+        s.quantized_ = true;
+        scann_hip_txh_desc d = s.desc();
+        d.data = nullptr;
+        d.stride = stride;
+        check(scann_hip_txh_create_quantized(context(device_), &d, rows, row_format, inv_multiplier, &s.ix_.h));
+        return s;
     }
     static TreeXHybridSearcher load(const std::string &path, int device = 0) {
         scann_hip_file_info info;
@@ -1132,6 +1153,7 @@ private:
     std::vector<uint32_t> leaf_off_, leaf_ids_;
     std::vector<uint8_t> codes_;
     size_t n_ = 0, dim_ = 0, L_ = 0;
+    bool quantized_ = false;   // with_quantized_rows: the handle's rows are quantized, dataset_ only names the model's rows
     detail::IndexHandle ix_;
     detail::CrowdAttach crowd_;
 };

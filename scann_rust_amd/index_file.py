@@ -13,6 +13,7 @@ VERSION = 1
 ALIGN = 4096
 _DTYPES = {0: np.float32, 1: np.uint32, 2: np.uint8}
 _CODES = {np.dtype(np.float32): 0, np.dtype(np.uint32): 1, np.dtype(np.uint8): 2}
+_ROWS_Q_DTYPES = {1: np.uint16, 2: np.uint8, 3: np.int8}   # SCANN_HIP_ROWS_BF16 / _FP8_E4M3 / _INT8
 # magic, version, kind, n_rows, n_local, file_bytes, dim, stride, L, S, K, dsub, measure, csr, packed4,
 # residuals, partitions_to_search, multiplier, n_sections
 _HEADER = struct.Struct("<8sIIQQQIIIIIIiiiiIfI")
@@ -56,6 +57,12 @@ def arrays(path):
     out = dict(h)
     if "data" in s:
         out["data"] = s["data"].reshape(h["n_rows"], h["stride"])
+    if "rows_q" in s:   # a handle over quantized rows (hip.txh_create_quantized): no "data"
+        fmt = int(s["rows_q_meta"][0])
+        out["rows_q_meta"] = s["rows_q_meta"]
+        out["fmt"] = fmt
+        out["inv_multiplier"] = float(np.asarray(s["rows_q_meta"][1:2]).view(np.float32)[0])
+        out["rows_q"] = s["rows_q"].view(_ROWS_Q_DTYPES[fmt]).reshape(h["n_rows"], h["stride"])
     if h["kind"] == 1:
         if h["num_partitions"]:
             out["centers"] = s["centers"].reshape(h["num_partitions"], h["dim"])
@@ -68,6 +75,13 @@ def arrays(path):
             bpp = (h["num_subspaces"] + 1) // 2 if h["codes_packed4"] else h["num_subspaces"]
             out["codes"] = s["codes"].reshape(h["n_local"], bpp)
     return out
+
+
+def rows_q_sections(rows, fmt, inv_multiplier=1.0):
+    """The two sections of quantized re-rank rows for write(): the rows' bytes and {format, inv_multiplier bits}."""
+    r = np.ascontiguousarray(rows).view(_ROWS_Q_DTYPES[fmt])
+    meta = np.array([fmt, np.array([inv_multiplier], np.float32).view(np.uint32)[0]], np.uint32)
+    return [("rows_q", r.reshape(-1).view(np.uint8)), ("rows_q_meta", meta)]
 
 
 def write(path, *, kind, n_rows, n_local, dim, stride, num_partitions=0, num_subspaces=0, num_codes=0,
