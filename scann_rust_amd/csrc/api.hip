@@ -1242,6 +1242,15 @@ static int plan_txh_search(const scann_hip_index *ix, uint32_t k, const scann_hi
     }
     // the sparse kernel's flush: lanes walk their own words on flat hashers, word-parallel on tree indexes
     p.sp_words = kn.sp_words < 0 ? !t.ah_mode : kn.sp_words != 0;
+    // ... and its items: 64 pairs x 1024 points (two column tiles share every point tile's operands) where that form is
+    // compiled -- S <= 32, lane-walk flush -- on flat hashers whose padding costs at most about one column tile in eight:
+    // an even number of 32-pair tiles, or more than 224 queries.  SCANN_HIP_SP_PAIRS = 32 / 64 forces a form.
+    {
+        const bool compiled = p.scan == TxhScan::Smfmac && t.S <= 32 && !p.sp_words;
+        const uint64_t tiles32 = (quads + 7) / 8;
+        const bool flat = t.ah_mode && L == 1 && P == 1;
+        p.sp_pairs64 = compiled && (kn.sp_pairs ? kn.sp_pairs == 64 : flat && (tiles32 % 2 == 0 || nq > 224));
+    }
     // The survivors' codes travel with their positions for flat hashers: their ~12 k survivors per query
     // are spread over the whole code array (random 16-byte gathers from 16 MB: refine 145 -> 65 us at
     // C3).  In a tree index the survivors sit densely in the query's nearest leaves, the gathers hit

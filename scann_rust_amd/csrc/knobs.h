@@ -26,6 +26,9 @@
 //                                   store by the expanded square; per-row int8 store always as 0)
 // SCANN_HIP_SP_WORDS                0 / 1: lane-walk / word-parallel survivor flush of the sparse  every call
 //                                   prefilter (default: word-parallel on tree indexes)
+// SCANN_HIP_SP_PAIRS                32 / 64: pairs per item of the sparse prefilter, where the     every call
+//                                   64-pair form is compiled (S <= 32, lane-walk flush); default:
+//                                   by the batch, flat hashers only
 // SCANN_HIP_THR_TIES                0: filter bound on the distance alone (diagnostics)            every call
 // SCANN_HIP_THR_TAIL                0: filter bound by the full histogram select                   every call
 // SCANN_HIP_SAMPLE_MFMA             0: flat hashers score the bound's sample with the f32 gather   every call
@@ -73,6 +76,7 @@ struct Knobs {
     uint32_t rerank_i8_min = 512;
     bool rerank_expand = true;
     int sp_words = -1;                    // -1 = by index kind
+    int sp_pairs = 0;                     // 0 = by the batch (api.hip plan_txh_search)
     bool thr_ties = true;
     bool thr_tail = true;
     bool sample_mfma = true;
@@ -121,7 +125,10 @@ inline Knobs read_knobs() {
         else if (is("SCANN_HIP_RERANK_I8_MIN")) k.rerank_i8_min = (uint32_t)std::max(1, atoi(v));
         else if (is("SCANN_HIP_RERANK_EXPAND")) k.rerank_expand = atoi(v) != 0;
         else if (is("SCANN_HIP_SP_WORDS")) k.sp_words = atoi(v) != 0 ? 1 : 0;
-        else if (is("SCANN_HIP_THR_TIES")) k.thr_ties = atoi(v) != 0;
+        else if (is("SCANN_HIP_SP_PAIRS")) {
+            const int n = atoi(v);
+            if (n == 32 || n == 64) k.sp_pairs = n;
+        } else if (is("SCANN_HIP_THR_TIES")) k.thr_ties = atoi(v) != 0;
         else if (is("SCANN_HIP_THR_TAIL")) k.thr_tail = atoi(v) != 0;
         else if (is("SCANN_HIP_SAMPLE_MFMA")) k.sample_mfma = atoi(v) != 0;
         else if (is("SCANN_HIP_FUSED")) k.fused = atoi(v) != 0;

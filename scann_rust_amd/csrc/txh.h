@@ -161,6 +161,7 @@ struct TxhPlan {
     uint32_t res_cl;           // chunks per tile of the resident-table scan
     uint32_t cap32;            // survivors per query of the MFMA prefilter
     bool sp_words;             // sparse prefilter's survivor flush: word-parallel (else lanes walk their own words)
+    bool sp_pairs64;           // sparse prefilter's items: 64 pairs x 1024 points (else 32 x 2048); S <= 32, lane-walk flush
     bool codes_in_list;        // prefilter survivors carry their packed codes / plane rows
     bool thr_ties;             // filter bound on (distance, stream position); false: on the distance alone
     bool thr_tail;             // filter bound by threshold_tail_kernel (else threshold_select_kernel)

@@ -3986,8 +3986,8 @@ static WorkTiling work_tiling(const TxhIndexDev &ix, const TxhWork &w) {
     switch (w.scan) {
         case TxhScan::Exact: return {kExactRows, exact_quads_per_tile(ix.dim), 1u};
         case TxhScan::Mfma16: return {kMfmaRange, 4u, 1u};
-        case TxhScan::Mfma32:
-        case TxhScan::Smfmac: return {kMfmaRange, 8u, 1u};
+        case TxhScan::Mfma32: return {kMfmaRange, 8u, 1u};
+        case TxhScan::Smfmac: return w.sp_pairs64 ? WorkTiling{kSpRange64, 16u, 1u} : WorkTiling{kMfmaRange, 8u, 1u};
         case TxhScan::Resident: return {kResThreads * kScanPPT, kResQuads, w.res_cl};
         default: return {scan_tile_points(ix), w.qpt, 1u};
     }

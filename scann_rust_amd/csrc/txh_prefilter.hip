@@ -462,6 +462,18 @@ constexpr uint32_t kSpStage = SCANN_SP_STAGE;   // adc_smfmac_kernel: list entri
 #define SCANN_SP_U 8
 #endif
 constexpr uint32_t kSpU = SCANN_SP_U;         // ... and code rows in flight per lane in the copy phase
+#ifndef SCANN_SP_STAGE64
+#define SCANN_SP_STAGE64 1024   // (two workgroups per CU: 69 KB each; an item's ~800 entries at C3 in one round)
+#endif
+
+// Shape of a wave's item by its column tiles: CT = 1, 32 (query, leaf) pairs x kMfmaRange points; CT = 2, 64 pairs x
+// kSpRange64 points -- the same MFMAs per item, and with half the points the same 32 bitmap words per lane.
+template <int CT>
+struct SpItem {
+    static constexpr uint32_t RANGE = CT == 2 ? kSpRange64 : kMfmaRange;      // points
+    static constexpr uint32_t STAGE = CT == 2 ? SCANN_SP_STAGE64 : kSpStage;   // list entries staged per flush round
+    static constexpr int TTM = (int)(RANGE / 64);                              // tile pairs (bitmap words per lane and column tile)
+};
 
 template <int S_>
 struct SpLayout {
@@ -538,60 +550,127 @@ __device__ __forceinline__ void sp_filter_words(const TxhIndexDev &ix, const uin
 // same as in sp_flush_item_words.  No per-pair round trip through LDS and the wave scan: 0.35 ms at C3 against
 // 0.44 ms for the word-parallel form -- which wins wherever pairs are dense (tree indexes: 10M x 128, P = 25, m = 1000:
 // scan 0.27 ms against 0.71 ms), because a lane walking its own survivors takes them one by one.
-template <int S>
+// CT = 2 (64 pairs): lane (col, h) owns pair col of both column tiles, words [ct][tt] of the bitmap; the pairs are
+// numbered ct * 32 + col in the prefix, the stage entries and the s_fq / s_fvb / s_fgb rows, and lane (col, h) issues
+// the atomic of pair h * 32 + col (one returning atomic per live pair, all 64 in one instruction).
+template <int S, int CT>
 __device__ SCANN_SP_FLUSH_INLINE void sp_flush_item_lanes(const uint32_t *__restrict__ codes_sp, const TxhIndexDev &ix,
                                                         const uint64_t *allow, uint64_t allow_bits, uint64_t allow_stride, uint32_t *__restrict__ cand32_cnt,
                                                         uint32_t *__restrict__ cand32, uint32_t *__restrict__ cand32_codes,
                                                         uint32_t cap32, uint32_t *bits, uint2 *stage, uint32_t *s_fq,
                                                         uint32_t *s_fvb, uint32_t *s_fgb, uint32_t ntile, uint32_t c0,
-                                                        uint32_t lb, uint32_t pq, uint32_t vb) {
+                                                        uint32_t lb, const uint32_t (&pq)[CT], const uint32_t (&vb)[CT]) {
     constexpr int SPW = SpLayout<S>::SPW;
-    constexpr int TTM = (int)(kMfmaRange / 64);
-    const uint32_t lane = threadIdx.x & 63u, col = lane & 31u, h = lane >> 5;
+    constexpr int TTM = SpItem<CT>::TTM;
+    constexpr uint32_t STAGE = SpItem<CT>::STAGE;
+    uint32_t lane = threadIdx.x & 63u;
+    // (CT = 2, opaque per item: the optimiser otherwise forms the walk's 32 per-word entry bases once per kernel and
+    // keeps them across the tile loop, whose two table sets leave no room -- they went to scratch memory)
+    if constexpr (CT == 2) asm volatile("" : "+v"(lane));
+    const uint32_t col = lane & 31u, h = lane >> 5;
     const uint32_t ntt = (ntile + 1u) >> 1;
-    if (allow) sp_filter_words(ix, allow, allow_stride, pq, allow_bits, bits, ntt, c0, lb, h);
-    uint32_t w[TTM];
-    uint32_t cnt = 0;
+    if (allow) {
 #pragma unroll
-    for (int tt = 0; tt < TTM; ++tt) {
-        w[tt] = (uint32_t)tt < ntt ? bits[tt * 64] : 0u;
-        cnt += (uint32_t)__popc(w[tt]);
+        for (int ct = 0; ct < CT; ++ct) sp_filter_words(ix, allow, allow_stride, pq[ct], allow_bits, bits + ct * TTM * 64, ntt, c0, lb, h);
     }
-    const uint32_t other = (uint32_t)__shfl_xor((int)cnt, 32);
-    const uint32_t n_pair = cnt + other;
-    uint32_t incl = n_pair;   // prefix over the pairs, computed alike in both halves of the wave
+    // CT = 1: the lane's words stay in registers and are walked one after the other.  CT = 2: only a mask `nz` of its
+    // non-empty words does, and the walk pops the words off it (below).
+    constexpr bool MASKED = CT == 2;
+    static_assert(!MASKED || CT * TTM <= 32, "one mask bit per bitmap word of the lane");
+    uint32_t w[MASKED ? 1 : CT][MASKED ? 1 : TTM];
+    uint32_t nz = 0;
+    uint32_t cnt[CT], other[CT], n_pair[CT], incl[CT];
+    uint32_t total = 0;
 #pragma unroll
-    for (int o = 1; o < 32; o <<= 1) {
-        const uint32_t up = (uint32_t)__shfl_up((int)incl, o, 32);
-        if ((int)col >= o) incl += up;
-    }
-    const uint32_t total = (uint32_t)__shfl((int)incl, 31, 32);
-    if (total == 0) return;
-    uint32_t gbase = 0;
-    if (h == 0 && n_pair) gbase = atomicAdd(&cand32_cnt[pq], n_pair);   // (padding pairs have no bits)
-    if (lane < 32) {
-        s_fq[lane] = pq == kInvalid ? 0u : pq;
-        s_fvb[lane] = vb;
-    }
-    uint32_t sq = incl - n_pair + (h ? other : 0u);   // this lane's first entry in the wave's staging order
-    uint32_t rel = h ? other : 0u;                    // ... and its position in the pair's segment
-    for (uint32_t base = 0; base < total; base += kSpStage) {
-        const uint32_t lim = base + kSpStage;
+    for (int ct = 0; ct < CT; ++ct) {
+        cnt[ct] = 0;
 #pragma unroll
         for (int tt = 0; tt < TTM; ++tt) {
-            while (w[tt] && sq < lim) {
-                const uint32_t bpos = (uint32_t)__ffs((int)w[tt]) - 1u;
-                w[tt] &= w[tt] - 1u;
+            const uint32_t x = (uint32_t)tt < ntt ? bits[(ct * TTM + tt) * 64] : 0u;
+            if constexpr (MASKED) nz |= x ? 1u << (ct * TTM + tt) : 0u;
+            else w[ct][tt] = x;
+            cnt[ct] += (uint32_t)__popc(x);
+        }
+        other[ct] = (uint32_t)__shfl_xor((int)cnt[ct], 32);
+        n_pair[ct] = cnt[ct] + other[ct];
+        incl[ct] = n_pair[ct];   // prefix over the pairs, computed alike in both halves of the wave
+#pragma unroll
+        for (int o = 1; o < 32; o <<= 1) {
+            const uint32_t up = (uint32_t)__shfl_up((int)incl[ct], o, 32);
+            if ((int)col >= o) incl[ct] += up;
+        }
+        incl[ct] += total;       // (the column tiles one after the other)
+        total = (uint32_t)__shfl((int)incl[ct], 31, 32);
+    }
+    if (total == 0) return;
+    // the pair this lane speaks for in the per-pair rows: col (lanes 0..31); CT = 2: pair lane
+    const bool second = CT == 2 && h;
+    const uint32_t my_n = second ? n_pair[CT - 1] : n_pair[0], my_q = second ? pq[CT - 1] : pq[0];
+    const bool speaks = CT == 2 || h == 0;
+    uint32_t gbase = 0;
+    if (speaks && my_n) gbase = atomicAdd(&cand32_cnt[my_q], my_n);   // (padding pairs have no bits)
+    if (speaks) {
+        s_fq[lane] = my_q == kInvalid ? 0u : my_q;
+        s_fvb[lane] = second ? vb[CT - 1] : vb[0];
+    }
+    uint32_t sq[CT], rel[CT];
+#pragma unroll
+    for (int ct = 0; ct < CT; ++ct) {
+        sq[ct] = incl[ct] - n_pair[ct] + (h ? other[ct] : 0u);   // this lane's first entry in the wave's staging order
+        rel[ct] = h ? other[ct] : 0u;                            // ... and its position in the pair's segment
+    }
+    // MASKED walk: (wcur, wi) = what is left of the word being walked and its number ct * TTM + tt, (sqc, relc) = the
+    // entry counters of its column tile; all of them carry over from round to round.
+    uint32_t wcur = 0, wi = 0, ctc = 0, sqc = sq[0], relc = rel[0];
+    for (uint32_t base = 0; base < total; base += STAGE) {
+        const uint32_t lim = base + STAGE;
+        if constexpr (MASKED) {
+            // One loop over the lane's set bits, whichever word they are in: a wave takes as many trips as its fullest
+            // lane has survivors (~20 at 0.4 survivors per word), where the loop per word of the CT = 1 form takes as
+            // many as the fullest lane of EVERY word (~2.5 x 32).  The words come back from LDS one at a time (a
+            // lane's own column: conflict-free); a lane's entries of column tile 0 precede those of tile 1 in the
+            // staging order as its words do in the mask, so a round ends for it at the first entry past the stage.
+            for (;;) {
+                if (wcur == 0) {
+                    if (nz == 0) break;
+                    wi = (uint32_t)__ffs((int)nz) - 1u;
+                    nz &= nz - 1u;
+                    wcur = bits[wi * 64u];
+                    if (wi >= (uint32_t)TTM && ctc == 0) {   // the lane's first word of column tile 1
+                        ctc = 1;
+                        sqc = sq[CT - 1];
+                        relc = rel[CT - 1];
+                    }
+                }
+                if (sqc >= lim) break;
+                const uint32_t bpos = (uint32_t)__ffs((int)wcur) - 1u;
+                wcur &= wcur - 1u;
                 const uint32_t r = 15u - (bpos & 15u);
-                const uint32_t jrel = (2u * (uint32_t)tt + (bpos >> 4)) * 32u + 4u * h + (r & 3u) + ((r >> 2) << 3);
-                stage[sq - base] = make_uint2(rel, (col << 16) | jrel);
-                ++sq;
-                ++rel;
+                const uint32_t jrel = (2u * (wi - ctc * (uint32_t)TTM) + (bpos >> 4)) * 32u + 4u * h + (r & 3u) + ((r >> 2) << 3);
+                stage[sqc - base] = make_uint2(relc, ((ctc * 32u + col) << 16) | jrel);
+                ++sqc;
+                ++relc;
+            }
+        } else {
+#pragma unroll
+            for (int ct = 0; ct < CT; ++ct) {
+#pragma unroll
+                for (int tt = 0; tt < TTM; ++tt) {
+                    while (w[ct][tt] && sq[ct] < lim) {
+                        const uint32_t bpos = (uint32_t)__ffs((int)w[ct][tt]) - 1u;
+                        w[ct][tt] &= w[ct][tt] - 1u;
+                        const uint32_t r = 15u - (bpos & 15u);
+                        const uint32_t jrel = (2u * (uint32_t)tt + (bpos >> 4)) * 32u + 4u * h + (r & 3u) + ((r >> 2) << 3);
+                        stage[sq[ct] - base] = make_uint2(rel[ct], (((uint32_t)ct * 32u + col) << 16) | jrel);
+                        ++sq[ct];
+                        ++rel[ct];
+                    }
+                }
             }
         }
-        if (base == 0 && lane < 32) s_fgb[lane] = gbase;   // (the atomics have travelled under the walk)
+        if (base == 0 && speaks) s_fgb[lane] = gbase;   // (the atomics have travelled under the walk)
         __builtin_amdgcn_wave_barrier();
-        const uint32_t n = min(kSpStage, total - base);
+        const uint32_t n = min(STAGE, total - base);
         for (uint32_t e0 = 0; e0 < n; e0 += 64u * kSpU) {
             uint2 ent[kSpU];
             uint4 cw[kSpU][SPW / 4];
@@ -757,24 +836,33 @@ __device__ SCANN_SP_FLUSH_INLINE void sp_flush_item_words(const uint32_t *__rest
     }
 }
 
-template <int S_, bool WORDS>   // WORDS: the word-parallel flush (tree indexes); else lanes walk their own words (flat)
+// WORDS: the word-parallel flush (tree indexes); else lanes walk their own words (flat).  CT: column tiles of 32 pairs
+// scored against each point tile.  With CT = 2 the point side of a tile step -- the plane words, their unpacking, the
+// byte extractions and every LDS operand read -- is paid once for two MFMA chains (18 MFMAs at S = 32), the wave holds
+// both tiles' tables (128 registers at S = 32) and two accumulator pairs, and runs at two waves per SIMD.
+template <int S_, bool WORDS, int CT>
 __device__ __forceinline__ void adc_smfmac_body(const TxhIndexDev &ix, const MfmaArgs &a, const uint64_t allow_stride) {
     typedef int v4i __attribute__((ext_vector_type(4)));
     typedef int v8i __attribute__((ext_vector_type(8)));
     typedef int v16i __attribute__((ext_vector_type(16)));
     typedef SpLayout<S_> SP;
+    static_assert(CT == 1 || (CT == 2 && !WORDS && S_ <= 32), "64-pair items: lane-walk flush, S <= 32");
     constexpr int S = S_, NS = SP::NS, KT = NS + 2, NWP = SP::NWP, SPW = SP::SPW;
-    constexpr int D = kMfmaDepth < KT ? kMfmaDepth : KT;      // operands in flight ahead of the MFMA that consumes them
-    constexpr uint32_t kTT = kMfmaRange / 64;                   // tile pairs per item
+    // operands in flight ahead of the MFMA that consumes them (CT = 2: every operand feeds two MFMAs, so about the same
+    // cover in MFMA slots from fewer registers)
+    constexpr int DEPTH = (kMfmaDepth + CT - 1) / CT;
+    constexpr int D = DEPTH < KT ? DEPTH : KT;
+    constexpr uint32_t kRange = SpItem<CT>::RANGE;              // points per item
+    constexpr uint32_t kTT = kRange / 64;                       // tile pairs per item
     __shared__ __attribute__((aligned(16))) uint32_t s_ident[64];   // dense A: 16 one-hot rows of 16 bytes
     __shared__ __attribute__((aligned(16))) uint32_t s_vtab[64];    // sparse A values: row V = (ga | gb << 2)
     __shared__ uint32_t s_ntab[16];                                 // sparse A positions: word N = (ia | ib << 2)
-    // survivor bitmap of the wave's item: word [tt][h][col] = the 16-bit masks of tiles 2 tt (low half) and 2 tt + 1 of
-    // lane (col, h).  Written once per two tiles with one conflict-free ds_write_b32; no atomics, no branches and no
-    // waits in the tile loop -- the item's flush turns it into list entries.
-    __shared__ uint32_t s_bits[kMfmaWaves][kTT][64];
-    __shared__ uint2 s_stage[kMfmaWaves][kSpStage];                                  // flush: staged list entries
-    __shared__ uint32_t s_fq[kMfmaWaves][32], s_fvb[kMfmaWaves][32], s_fgb[kMfmaWaves][32];   // flush: per pair
+    // survivor bitmap of the wave's item: word [ct][tt][h][col] = the 16-bit masks of tiles 2 tt (low half) and 2 tt + 1
+    // of lane (col, h) in column tile ct.  Written once per two tiles with one conflict-free ds_write_b32; no atomics, no
+    // branches and no waits in the tile loop -- the item's flush turns it into list entries.
+    __shared__ uint32_t s_bits[kMfmaWaves][CT * kTT][64];
+    __shared__ uint2 s_stage[kMfmaWaves][SpItem<CT>::STAGE];                         // flush: staged list entries
+    __shared__ uint32_t s_fq[kMfmaWaves][32 * CT], s_fvb[kMfmaWaves][32 * CT], s_fgb[kMfmaWaves][32 * CT];   // flush: per pair
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const uint32_t col = lane & 31u, h = lane >> 5;
     if (tid < 64) {
@@ -808,34 +896,36 @@ __device__ __forceinline__ void adc_smfmac_body(const TxhIndexDev &ix, const Mfm
         if (lane == 0) next_tile = grab_tile(a.counters + CNT_XQ, total_tiles);
         const WorkItem item = decode_item(ix, a.tile_off, a.pair_off, tile);
         const uint32_t lb = item.lb, size = item.size, local = item.local, slot0 = item.slot0, slot_end = item.slot_end;
-        const uint32_t nranges = (size + kMfmaRange - 1) / kMfmaRange;
+        const uint32_t nranges = (size + kRange - 1) / kRange;
         const uint32_t range = local % nranges, pt = local / nranges;
-        const uint32_t c0 = range * kMfmaRange;
-        const uint32_t npts = min(kMfmaRange, size - c0);
+        const uint32_t c0 = range * kRange;
+        const uint32_t npts = min(kRange, size - c0);
 
-        // this lane's pair (column): tables (the pass bound is folded into them), key base
-        const uint32_t slot = slot0 + pt * 32u + col;
-        const bool pair_ok = slot < slot_end;
-        const uint32_t pq = pair_ok ? a.pair_q[slot] : kInvalid;
-        const uint32_t vb = pair_ok ? a.pair_vbase[slot] : 0u;
-        v4i bd[2];
-        v8i bs[NS];
-        {
+        // this lane's pair (column) of each column tile: tables (the pass bound is folded into them), key base
+        uint32_t pq[CT], vb[CT];
+        v4i bd[CT][2];
+        v8i bs[CT][NS];
+#pragma unroll
+        for (int ct = 0; ct < CT; ++ct) {
+            const uint32_t slot = slot0 + pt * (32u * CT) + (uint32_t)ct * 32u + col;
+            const bool pair_ok = slot < slot_end;
+            pq[ct] = pair_ok ? a.pair_q[slot] : kInvalid;
+            vb[ct] = pair_ok ? a.pair_vbase[slot] : 0u;
             const int8_t *bsrc = a.lut8 + (size_t)(pair_ok ? slot : slot0) * S * 16;
 #pragma unroll
-            for (int d = 0; d < 2; ++d) bd[d] = *reinterpret_cast<const v4i *>(bsrc + (size_t)(2 * d + h) * 16);
+            for (int d = 0; d < 2; ++d) bd[ct][d] = *reinterpret_cast<const v4i *>(bsrc + (size_t)(2 * d + h) * 16);
 #pragma unroll
             for (int kt = 0; kt < NS; ++kt) {
                 const v4i x0 = *reinterpret_cast<const v4i *>(bsrc + (size_t)(4 + 4 * kt + 2 * h) * 16);
                 const v4i x1 = *reinterpret_cast<const v4i *>(bsrc + (size_t)(4 + 4 * kt + 2 * h) * 16 + 16);
-                bs[kt] = v8i{x0[0], x0[1], x0[2], x0[3], x1[0], x1[1], x1[2], x1[3]};
+                bs[ct][kt] = v8i{x0[0], x0[1], x0[2], x0[3], x1[0], x1[1], x1[2], x1[3]};
             }
             if (!pair_ok) {   // padding columns: every entry 127, sums stay positive (nothing passes)
                 const int k7 = 0x7F7F7F7F;
 #pragma unroll
-                for (int d = 0; d < 2; ++d) bd[d] = v4i{k7, k7, k7, k7};
+                for (int d = 0; d < 2; ++d) bd[ct][d] = v4i{k7, k7, k7, k7};
 #pragma unroll
-                for (int kt = 0; kt < NS; ++kt) bs[kt] = v8i{k7, k7, k7, k7, k7, k7, k7, k7};
+                for (int kt = 0; kt < NS; ++kt) bs[ct][kt] = v8i{k7, k7, k7, k7, k7, k7, k7, k7};
             }
         }
 
@@ -896,8 +986,12 @@ __device__ __forceinline__ void adc_smfmac_body(const TxhIndexDev &ix, const Mfm
         Ops ops;
 #pragma unroll
         for (int oi = 0; oi < D; ++oi) fetch(pl, oi, ops.av[oi], ops.iv[oi]);
-        uint32_t mlo = 0;
-        auto step = [&](v16i &accN, const v16i &accO, uint32_t t, auto hi_half) {
+        uint32_t mlo[CT];
+#pragma unroll
+        for (int ct = 0; ct < CT; ++ct) mlo[ct] = 0;
+        // (CT = 2: every operand is fetched once and issued to both column tiles' chains, ct = 0 then ct = 1, so that
+        // consecutive MFMAs never depend on each other; both masks are built in the same shadow)
+        auto step = [&](v16i (&accN)[CT], const v16i (&accO)[CT], uint32_t t, auto hi_half) {
             const Planes pn = unpack(rawn);                        // tile t + 1 (loaded during step t - 1)
             if (t + 2 < ntile) rawn = load_planes(t + 2);
             v4i av[KT];
@@ -910,21 +1004,27 @@ __device__ __forceinline__ void adc_smfmac_body(const TxhIndexDev &ix, const Mfm
             }
             // lane (col, h), register r: point row (r & 3) + 8 * (r >> 2) + 4 * h of the tile; result r's sign
             // (negative = passes) ends up at bit 15 - r of the mask
-            uint32_t m16 = 0;
+            uint32_t m16[CT];
+#pragma unroll
+            for (int ct = 0; ct < CT; ++ct) m16[ct] = 0;
             __builtin_amdgcn_s_setprio(2);
 #pragma unroll
             for (int oi = 0; oi < KT; ++oi) {
                 if (oi + D < KT) fetch(pl, oi + D, av[oi + D], iv[oi + D]);
                 else fetch(pn, oi + D - KT, nops.av[oi + D - KT], nops.iv[oi + D - KT]);
-                if (oi == 0)
-                    accN = __builtin_amdgcn_mfma_i32_32x32x32_i8(av[0], bd[0], v16i{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, 0, 0, 0);
-                else if (oi == 1)
-                    accN = __builtin_amdgcn_mfma_i32_32x32x32_i8(av[1], bd[1], accN, 0, 0, 0);
-                else
-                    accN = __builtin_amdgcn_smfmac_i32_32x32x64_i8(av[oi], bs[oi - 2], accN, iv[oi], 0, 0);
+#pragma unroll
+                for (int ct = 0; ct < CT; ++ct) {
+                    if (oi == 0)
+                        accN[ct] = __builtin_amdgcn_mfma_i32_32x32x32_i8(av[0], bd[ct][0], v16i{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, 0, 0, 0);
+                    else if (oi == 1)
+                        accN[ct] = __builtin_amdgcn_mfma_i32_32x32x32_i8(av[1], bd[ct][1], accN[ct], 0, 0, 0);
+                    else
+                        accN[ct] = __builtin_amdgcn_smfmac_i32_32x32x64_i8(av[oi], bs[ct][oi - 2], accN[ct], iv[oi], 0, 0);
+                }
 #pragma unroll
                 for (int r = oi * 16 / KT; r < (oi + 1) * 16 / KT; ++r)
-                    m16 = __builtin_amdgcn_alignbit(m16, (uint32_t)accO[r], 31);
+#pragma unroll
+                    for (int ct = 0; ct < CT; ++ct) m16[ct] = __builtin_amdgcn_alignbit(m16[ct], (uint32_t)accO[ct][r], 31);
                 __builtin_amdgcn_sched_barrier(0);
             }
             __builtin_amdgcn_s_setprio(0);
@@ -937,31 +1037,40 @@ __device__ __forceinline__ void adc_smfmac_body(const TxhIndexDev &ix, const Mfm
 #pragma unroll
                 for (int r = 0; r < 16; ++r)
                     okm |= (base + (uint32_t)((r & 3) + 8 * (r >> 2)) < size ? 1u : 0u) << (15 - r);
-                m16 &= okm;
+#pragma unroll
+                for (int ct = 0; ct < CT; ++ct) m16[ct] &= okm;
             }
-            if constexpr (decltype(hi_half)::value) {
-                bits[((t - 1) >> 1) * 64u] = mlo | (m16 << 16);
-            } else {
-                mlo = m16;
+#pragma unroll
+            for (int ct = 0; ct < CT; ++ct) {
+                if constexpr (decltype(hi_half)::value) {
+                    bits[((uint32_t)ct * kTT + ((t - 1) >> 1)) * 64u] = mlo[ct] | (m16[ct] << 16);
+                } else {
+                    mlo[ct] = m16[ct];
+                }
             }
         };
         // (tile 0 is peeled: inside the loop t >= 1 is known, so the compiler keeps the mask build between
         // the MFMAs in BOTH instances instead of sinking it below a `t == 0` branch)
-        v16i accA = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, accB = accA;
+        v16i accA[CT], accB[CT];
+#pragma unroll
+        for (int ct = 0; ct < CT; ++ct) accA[ct] = accB[ct] = v16i{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
         step(accA, accB, 0u, std::false_type());
         for (uint32_t tl = 1; tl <= ntile; tl += 2) {
             step(accB, accA, tl, std::false_type());                          // mask of tile tl - 1 (even): low half
             if (tl + 1 <= ntile) step(accA, accB, tl + 1, std::true_type());  // mask of tile tl (odd): high half, write
         }
-        if (ntile & 1u) bits[(ntile >> 1) * 64u] = mlo;   // the last tile had an even number: its word has no high half
+        if (ntile & 1u) {   // the last tile had an even number: its word has no high half
+#pragma unroll
+            for (int ct = 0; ct < CT; ++ct) bits[((uint32_t)ct * kTT + (ntile >> 1)) * 64u] = mlo[ct];
+        }
         // ---- flush: the item's bitmap -> the queries' lists (sp_flush_item: its own function, so that its registers
         // are allocated apart from the tile loop's -- inlined, the loop spilled its table fragments)
         if constexpr (WORDS)
             sp_flush_item_words<S>(ix.codes_sp, ix, a.allow, a.allow_bits, allow_stride, a.cand32_cnt, a.cand32, a.cand32_codes, a.cap32, &s_bits[wave][0][0],
-                                   s_stage[wave], s_fq[wave], s_fvb[wave], s_fgb[wave], ntile, c0, lb, pq, vb);
+                                   s_stage[wave], s_fq[wave], s_fvb[wave], s_fgb[wave], ntile, c0, lb, pq[0], vb[0]);
         else
-            sp_flush_item_lanes<S>(ix.codes_sp, ix, a.allow, a.allow_bits, allow_stride, a.cand32_cnt, a.cand32, a.cand32_codes, a.cap32, bits, s_stage[wave],
-                                   s_fq[wave], s_fvb[wave], s_fgb[wave], ntile, c0, lb, pq, vb);
+            sp_flush_item_lanes<S, CT>(ix.codes_sp, ix, a.allow, a.allow_bits, allow_stride, a.cand32_cnt, a.cand32, a.cand32_codes, a.cap32, bits, s_stage[wave],
+                                       s_fq[wave], s_fvb[wave], s_fgb[wave], ntile, c0, lb, pq, vb);
         tile = __builtin_amdgcn_readfirstlane(next_tile);
     }
 }
@@ -975,21 +1084,30 @@ __device__ __forceinline__ void adc_smfmac_body(const TxhIndexDev &ix, const Mfm
 template <int S_, bool WORDS>
 __global__ __launch_bounds__(kMfmaWaves * 64, SCANN_MFMA_MINW) __attribute__((amdgpu_num_vgpr(SCANN_SP_VGPRS)))
 void adc_smfmac_kernel(TxhIndexDev ix, MfmaArgs a) {
-    adc_smfmac_body<S_, WORDS>(ix, a, 0);
+    adc_smfmac_body<S_, WORDS, 1>(ix, a, 0);
 }
 template <int S_, bool WORDS>
 __global__ __launch_bounds__(kMfmaWaves * 64, 2) void adc_smfmac_wide_kernel(TxhIndexDev ix, MfmaArgs a) {   // S = 48, 64
-    adc_smfmac_body<S_, WORDS>(ix, a, 0);
+    adc_smfmac_body<S_, WORDS, 1>(ix, a, 0);
 }
 // (_pq: one bitmap per query, allow_stride words apart; see adc_mfma_pq_kernel)
 template <int S_, bool WORDS>
 __global__ __launch_bounds__(kMfmaWaves * 64, SCANN_MFMA_MINW) __attribute__((amdgpu_num_vgpr(SCANN_SP_VGPRS)))
 void adc_smfmac_pq_kernel(TxhIndexDev ix, MfmaArgs a, uint64_t allow_stride) {
-    adc_smfmac_body<S_, WORDS>(ix, a, allow_stride);
+    adc_smfmac_body<S_, WORDS, 1>(ix, a, allow_stride);
 }
 template <int S_, bool WORDS>
 __global__ __launch_bounds__(kMfmaWaves * 64, 2) void adc_smfmac_wide_pq_kernel(TxhIndexDev ix, MfmaArgs a, uint64_t allow_stride) {
-    adc_smfmac_body<S_, WORDS>(ix, a, allow_stride);
+    adc_smfmac_body<S_, WORDS, 1>(ix, a, allow_stride);
+}
+// The 64-pair form (CT = 2; S <= 32, lane-walk flush): two tiles' tables and two accumulator pairs, two waves per SIMD.
+template <int S_>
+__global__ __launch_bounds__(kMfmaWaves * 64, 2) void adc_smfmac_kernel64(TxhIndexDev ix, MfmaArgs a) {
+    adc_smfmac_body<S_, false, 2>(ix, a, 0);
+}
+template <int S_>
+__global__ __launch_bounds__(kMfmaWaves * 64, 2) void adc_smfmac_pq_kernel64(TxhIndexDev ix, MfmaArgs a, uint64_t allow_stride) {
+    adc_smfmac_body<S_, false, 2>(ix, a, allow_stride);
 }
 
 // The prefilter with 16-pair tiles on v_mfma_i32_16x16x64_i8, for leaves scanned by 8-24 queries of the batch
@@ -1418,7 +1536,16 @@ int launch_prefilter_refine(const TxhIndexDev &ix, const TxhWork &w, hipStream_t
             if (ev0) SCANN_HIP_CHECK(hipEventRecord(ev0, st));
             const bool words = w.sp_words;
             const dim3 mgrid((uint32_t)cus * 4u), mblock(kMfmaWaves * 64);   // 4 workgroups per CU (4 waves each)
-            if (w.allow && w.allow_stride) {   // one bitmap per query: the instantiation that forms the query's address
+            if (w.scan == TxhScan::Smfmac && w.sp_pairs64) {   // 64-pair items: two resident workgroups per CU
+                if constexpr (C::S <= 32) {
+                    if (words) return fail(SCANN_HIP_INTERNAL, "64-pair items take the lane-walk flush");
+                    const dim3 grid64((uint32_t)cus * 2u);
+                    if (w.allow && w.allow_stride) SCANN_TRY(launch(adc_smfmac_pq_kernel64<C::S>, grid64, mblock, 0, st, ix, ma, w.allow_stride));
+                    else SCANN_TRY(launch(adc_smfmac_kernel64<C::S>, grid64, mblock, 0, st, ix, ma));
+                } else {
+                    return fail(SCANN_HIP_INTERNAL, "64-pair items are compiled for S <= 32");
+                }
+            } else if (w.allow && w.allow_stride) {   // one bitmap per query: the instantiation that forms the query's address
                 void (*scan)(TxhIndexDev, MfmaArgs, uint64_t) =
                     w.scan == TxhScan::Mfma16   ? adc_mfma16_pq_kernel<C::S>
                     : w.scan == TxhScan::Mfma32 ? adc_mfma_pq_kernel<C::S>
