@@ -824,6 +824,85 @@ int scann_hip_allow_bitmaps_from_ids(const uint32_t *ids, const uint64_t *offset
 int scann_hip_allow_bitmaps_from_ids_device(scann_hip_ctx *ctx, const uint32_t *d_ids, const uint64_t *d_offsets,
                                             uint32_t nq, uint64_t bits, uint64_t stride_words, uint64_t *d_out_words,
                                             void *hip_stream);
+
+/* ---- tag filters: a device-resident token map that writes per-query bitmaps (restricts/allowlist.rs:184-244) ----
+ * RestrictTokenMap: each datapoint carries any number of u64 tokens; create_allowlist(tokens) allows a datapoint that
+ * has at least one of the tokens.  The handle holds the map on the device -- the distinct tokens ascending, a CSR of
+ * offsets, the concatenated ascending postings -- uploaded once and shared by every query of every batch; a batch
+ * sends a few tokens per query and one kernel writes the strided bitmap block of
+ * scann_hip_search_opts.allow_bitmap_stride.
+ *   create   pair i is add_token(indices[i], tokens[i]) (:206-211).  The bitmap of a token set is a set union and
+ *            RestrictAllowlist::add ignores an index at or past the capacity (:59-65), so the pairs are sorted by
+ *            (token, index) on the host, duplicates and indices >= num_datapoints dropped.  n_pairs = 0 gives a valid
+ *            empty map.  num_datapoints >= 2^32 - 1 -> OutOfRange; null arrays with n_pairs > 0 -> InvalidArgument.
+ *            A created map does not change (add_token after create: build a new map).
+ *   num_tokens        distinct tokens as given (HashMap::len, :241-243): a token whose every index was out of range
+ *                     still counts.
+ *   get_indices       the STORED posting: ascending, deduplicated, below num_datapoints.  DEPARTURE from the reference,
+ *                     whose get_indices (:221-223) returns insertion order with duplicates and out-of-range indices
+ *                     (scann.hpp's host RestrictTokenMap keeps that order).  *out_n receives the count; an unknown
+ *                     token gives 0 and Ok (the reference's None); capacity < count -> ResourceExhausted with *out_n
+ *                     set and nothing written.
+ * Bitmaps of a batch (create_allowlist per query, :226-238): query i names q tokens[offsets[i] .. offsets[i + 1])
+ * (offsets: nq + 1 ascending values); bit j of its bitmap -- words [i * stride_words, i * stride_words +
+ * ceil(num_datapoints / 64)) -- is set iff some named token has j in its posting.  The capacity is the map's
+ * num_datapoints (pass it as allow_bitmap_bits).  The contract is that of scann_hip_allow_bitmaps_from_ids: all nq *
+ * stride_words words are written, gap words as zero; stride_words < ceil(bits / 64) or >= 2^32 -> InvalidArgument.
+ * Unknown tokens, repeated tokens and empty lists are fine (an empty list gives an all-zero bitmap).
+ *   _device           device pointers; ONE kernel enqueued on hip_stream: no clear, no global atomic, no
+ *                     synchronisation, no count visits the host.  A search enqueued on the same stream right after it
+ *                     reads the block in place.  Workgroup (t, y) assembles tile t (SCANN_HIP_TOKEN_TILE_BITS bits) of
+ *                     the bitmaps of queries y, y + gridDim.y, ... in LDS and stores it once, 16 bytes a lane.
+ *   (no suffix)       host pointers, synchronous: lists up, the same kernel, the block back.  One call at a time per
+ *                     map (serialised inside).
+ *   scann_hip_allow_bitmaps_from_tokens   stateless, on the host, no context, no GPU: the model and the form for
+ *                     machines without a device.  The two handle forms give its output bitwise. */
+typedef struct scann_hip_token_map scann_hip_token_map;
+#define SCANN_HIP_TOKEN_TILE_BITS 65536
+int scann_hip_token_map_create(scann_hip_ctx *ctx, uint64_t num_datapoints, const uint32_t *indices,
+                               const uint64_t *tokens, uint64_t n_pairs, scann_hip_token_map **out);
+void scann_hip_token_map_destroy(scann_hip_token_map *m);
+uint64_t scann_hip_token_map_num_tokens(const scann_hip_token_map *m);
+uint64_t scann_hip_token_map_num_datapoints(const scann_hip_token_map *m);
+int scann_hip_token_map_get_indices(const scann_hip_token_map *m, uint64_t token, uint32_t *out, uint64_t capacity,
+                                    uint64_t *out_n);
+int scann_hip_token_map_allow_bitmaps_device(const scann_hip_token_map *m, const uint64_t *d_tokens,
+                                             const uint64_t *d_offsets, uint32_t nq, uint64_t stride_words,
+                                             uint64_t *d_out_words, void *hip_stream);
+int scann_hip_token_map_allow_bitmaps(scann_hip_token_map *m, const uint64_t *tokens, const uint64_t *offsets,
+                                      uint32_t nq, uint64_t stride_words, uint64_t *out_words);
+int scann_hip_allow_bitmaps_from_tokens(const uint32_t *indices, const uint64_t *tokens, uint64_t n_pairs,
+                                        uint64_t num_datapoints, const uint64_t *q_tokens, const uint64_t *q_offsets,
+                                        uint32_t nq, uint64_t stride_words, uint64_t *out_words);
+/* search_with_filter(create_allowlist(tokens of query i)) for a batch on a tree or flat-hasher handle, host pointers,
+ * synchronous: queries and token lists go up, the block is built on the device by the map's kernel and
+ * scann_hip_search_batched_device reads it on the same stream with nothing between the two enqueues; the rows come
+ * back.  opts as for scann_hip_search_batched, with allow_bitmap NULL (set -> InvalidArgument: the lists are the
+ * filter); index and map live on the same device.  Where the enqueue-only search reports Aborted or ResourceExhausted
+ * (scann_hip_index_last_device_status), the batch is answered by scann_hip_search_batched under the same block.
+ * Brute-force handles refuse per-query bitmaps as before (Unimplemented).  k = 0 -> InvalidArgument. */
+int scann_hip_search_batched_tokens(scann_hip_index *index, scann_hip_token_map *m, const float *queries, uint32_t nq,
+                                    uint32_t q_stride, uint32_t q_dim, uint32_t k, const scann_hip_search_opts *opts,
+                                    const uint64_t *q_tokens, const uint64_t *q_offsets, uint32_t *out_idx,
+                                    float *out_dist, uint32_t *out_count);
+
+/* AndFilter / OrFilter / NotFilter (restricts/mod.rs:98-170) over strided bitmap blocks: the token map gives OR within
+ * one attribute; "tenant X AND category in {..}" is an AND across two blocks.  Words [0, ceil(bits / 64)) of row i of
+ * out = op(row i of a, row i of b); the last word is masked to `bits`, so NOT never sets a bit at or past the
+ * capacity; gap words of out are not touched.  stride_a / stride_b = 0: one bitmap shared by all queries.  out may be
+ * exactly a or b (same pointer, same stride).  SCANN_HIP_ALLOW_NOT does not read b (NULL is fine).  Unknown op, a
+ * non-zero operand stride or an output stride below ceil(bits / 64) -> InvalidArgument.  Device form: device
+ * pointers, one streaming kernel enqueued on hip_stream (16 bytes a lane where every row is 16-byte aligned), no
+ * synchronisation.  Host form: host pointers, no context, no GPU; the model.  RangeFilter is not built. */
+#define SCANN_HIP_ALLOW_AND 1
+#define SCANN_HIP_ALLOW_OR 2
+#define SCANN_HIP_ALLOW_ANDNOT 3 /* a & ~b */
+#define SCANN_HIP_ALLOW_NOT 4    /* ~a */
+int scann_hip_allow_bitmaps_combine(int op, const uint64_t *a, uint64_t stride_a, const uint64_t *b, uint64_t stride_b,
+                                    uint32_t nq, uint64_t bits, uint64_t *out, uint64_t stride_out);
+int scann_hip_allow_bitmaps_combine_device(scann_hip_ctx *ctx, int op, const uint64_t *d_a, uint64_t stride_a,
+                                           const uint64_t *d_b, uint64_t stride_b, uint32_t nq, uint64_t bits,
+                                           uint64_t *d_out, uint64_t stride_out, void *hip_stream);
 int scann_hip_bf_search_radius(scann_hip_index *index, const float *query, uint32_t q_dim, float radius,
                                uint32_t *out_idx, float *out_dist, uint64_t capacity,
                                uint64_t *out_count);

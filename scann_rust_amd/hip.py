@@ -22,6 +22,8 @@ MUTABLE_MAX_CAPACITY = 65536   # SCANN_HIP_MUTABLE_MAX_CAPACITY
 MUTABLE_MAX_K = 2048           # SCANN_HIP_MUTABLE_MAX_K
 MUTABLE_DELTA_TILE = 1024      # SCANN_HIP_MUTABLE_DELTA_TILE: delta rows sorted per workgroup of the delta scan
 FOLD_CHUNK = 1024              # SCANN_HIP_FOLD_CHUNK: CSR positions per workgroup of the fold's count and scatter passes
+TOKEN_TILE_BITS = 65536        # SCANN_HIP_TOKEN_TILE_BITS: bits of one query's bitmap a workgroup of the token-map kernel assembles in LDS
+ALLOW_AND, ALLOW_OR, ALLOW_ANDNOT, ALLOW_NOT = 1, 2, 3, 4   # SCANN_HIP_ALLOW_*: ops of allow_bitmaps_combine
 
 _CODE_NAMES = {
     0: "Ok", 1: "Cancelled", 2: "Unknown", 3: "InvalidArgument", 4: "DeadlineExceeded",
@@ -61,6 +63,10 @@ EXPORTS = [
     "scann_hip_mutable_export_live", "scann_hip_mutable_rebase", "scann_hip_mutable_enable_timing",
     "scann_hip_mutable_last_stage_ms", "scann_hip_fold_mutable", "scann_hip_fold_mutable_stage_ms",
     "scann_hip_index_write_file",
+    "scann_hip_token_map_create", "scann_hip_token_map_destroy", "scann_hip_token_map_num_tokens",
+    "scann_hip_token_map_num_datapoints", "scann_hip_token_map_get_indices", "scann_hip_token_map_allow_bitmaps_device",
+    "scann_hip_token_map_allow_bitmaps", "scann_hip_allow_bitmaps_from_tokens", "scann_hip_search_batched_tokens",
+    "scann_hip_allow_bitmaps_combine", "scann_hip_allow_bitmaps_combine_device",
 ]
 
 
@@ -263,6 +269,24 @@ def load():
     L.scann_hip_fold_mutable.argtypes = [vp, C.POINTER(vp), u32p, C.c_uint64, u64p]
     L.scann_hip_fold_mutable_stage_ms.argtypes = [vp, f32p]
     L.scann_hip_index_write_file.argtypes = [vp, C.c_char_p]
+    L.scann_hip_token_map_create.argtypes = [vp, C.c_uint64, u32p, u64p, C.c_uint64, C.POINTER(vp)]
+    L.scann_hip_token_map_destroy.argtypes = [vp]
+    L.scann_hip_token_map_destroy.restype = None
+    L.scann_hip_token_map_num_tokens.restype = C.c_uint64
+    L.scann_hip_token_map_num_tokens.argtypes = [vp]
+    L.scann_hip_token_map_num_datapoints.restype = C.c_uint64
+    L.scann_hip_token_map_num_datapoints.argtypes = [vp]
+    L.scann_hip_token_map_get_indices.argtypes = [vp, C.c_uint64, u32p, C.c_uint64, u64p]
+    L.scann_hip_token_map_allow_bitmaps_device.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint64, vp, vp]
+    L.scann_hip_token_map_allow_bitmaps.argtypes = [vp, u64p, u64p, C.c_uint32, C.c_uint64, u64p]
+    L.scann_hip_allow_bitmaps_from_tokens.argtypes = [u32p, u64p, C.c_uint64, C.c_uint64, u64p, u64p, C.c_uint32,
+                                                      C.c_uint64, u64p]
+    L.scann_hip_search_batched_tokens.argtypes = [vp, vp, f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                  C.POINTER(SearchOpts), u64p, u64p, u32p, f32p, u32p]
+    L.scann_hip_allow_bitmaps_combine.argtypes = [C.c_int, u64p, C.c_uint64, u64p, C.c_uint64, C.c_uint32, C.c_uint64,
+                                                  u64p, C.c_uint64]
+    L.scann_hip_allow_bitmaps_combine_device.argtypes = [vp, C.c_int, vp, C.c_uint64, vp, C.c_uint64, C.c_uint32,
+                                                         C.c_uint64, vp, C.c_uint64, vp]
     _lib = L
     return L
 
@@ -759,6 +783,157 @@ def allow_bitmaps_from_ids_device(d_ids, d_offsets, nq, bits, stride_words, d_ou
     scatter kernel are enqueued, nothing is synchronised.  d_out_words holds nq * stride_words uint64."""
     check(load().scann_hip_allow_bitmaps_from_ids_device(context(device), vp(d_ids), vp(d_offsets), int(nq), int(bits),
                                                          int(stride_words), vp(d_out_words), vp(stream)))
+
+
+def _token_lists(token_lists):
+    """(tokens uint64, offsets uint64[nq + 1]) of a list of per-query token lists"""
+    lists = [np.ascontiguousarray(t, np.uint64).ravel() for t in token_lists]
+    tokens = np.concatenate(lists + [np.zeros(0, np.uint64)]).astype(np.uint64)
+    offsets = np.concatenate([[0], np.cumsum([t.size for t in lists])]).astype(np.uint64)
+    return tokens, offsets
+
+
+def _token_pairs(indices, tokens):
+    idx = np.ascontiguousarray(indices, np.uint32).ravel()
+    tok = np.ascontiguousarray(tokens, np.uint64).ravel()
+    if idx.size != tok.size:
+        raise ValueError("one token per index: %d indices, %d tokens" % (idx.size, tok.size))
+    return idx, tok
+
+
+class TokenMap:
+    """Owns one scann_hip_token_map: RestrictTokenMap (restricts/allowlist.rs:184-244) resident on the device.  Pair i
+    is add_token(indices[i], tokens[i]); indices at or past num_datapoints are ignored; the map does not change after
+    it is created."""
+
+    def __init__(self, num_datapoints, indices, tokens, device=0):
+        idx, tok = _token_pairs(indices, tokens)
+        self.h = vp()
+        self.device = device
+        check(load().scann_hip_token_map_create(context(device), int(num_datapoints), ptr(idx, u32p) if idx.size else None,
+                                                ptr(tok, u64p) if tok.size else None, idx.size, C.byref(self.h)))
+
+    def close(self):
+        if self.h:
+            load().scann_hip_token_map_destroy(self.h)
+            self.h = None
+
+    destroy = close
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def num_tokens(self):
+        return int(load().scann_hip_token_map_num_tokens(self.h))
+
+    def num_datapoints(self):
+        return int(load().scann_hip_token_map_num_datapoints(self.h))
+
+    def get_indices(self, token):
+        """the stored posting of `token`: ascending, deduplicated, in range (the reference keeps insertion order);
+        an unknown token gives an empty array"""
+        n = C.c_uint64(0)
+        L = load()
+        status = L.scann_hip_token_map_get_indices(self.h, int(token), None, 0, C.byref(n))
+        if status not in (OK, RESOURCE_EXHAUSTED):
+            check(status)
+        out = np.empty(n.value, np.uint32)
+        if n.value:
+            check(L.scann_hip_token_map_get_indices(self.h, int(token), ptr(out, u32p), out.size, C.byref(n)))
+        return out
+
+    def allow_bitmaps(self, token_lists, stride_words=None):
+        """[nq, stride_words] uint64 block: row i allows the datapoints that carry at least one token of
+        token_lists[i] (create_allowlist per query), built by the device kernel.  stride_words defaults to
+        ceil(num_datapoints / 64).  Pass the block as `allow=` (2-D) with allow_bits=num_datapoints()."""
+        tok, off = _token_lists(token_lists)
+        nq = off.size - 1
+        stride = (self.num_datapoints() + 63) // 64 if stride_words is None else int(stride_words)
+        out = np.empty((nq, stride), np.uint64)
+        check(load().scann_hip_token_map_allow_bitmaps(self.h, ptr(tok, u64p) if tok.size else None, ptr(off, u64p), nq,
+                                                       stride, ptr(out, u64p) if out.size else None))
+        return out
+
+    def allow_bitmaps_device(self, d_tokens, d_offsets, nq, stride_words, d_out_words, stream=0):
+        """scann_hip_token_map_allow_bitmaps_device: device addresses (integers) and a HIP stream handle; one kernel
+        is enqueued, nothing is synchronised.  d_out_words holds nq * stride_words uint64."""
+        check(load().scann_hip_token_map_allow_bitmaps_device(self.h, vp(d_tokens), vp(d_offsets), int(nq),
+                                                              int(stride_words), vp(d_out_words), vp(stream)))
+
+    def search_batched(self, index, queries, k, token_lists, opts=None, q_dim=None):
+        """scann_hip_search_batched_tokens: query i of a tree / flat-hasher Index under the tokens of token_lists[i];
+        the block is built on the device and searched on the same stream.  Returns (idx, dist, count)."""
+        q = f32(queries)
+        if q.ndim == 1:
+            q = q[None]
+        nq, qs = q.shape
+        tok, off = _token_lists(token_lists)
+        if off.size - 1 != nq:
+            raise ValueError("one token list per query: %d lists, %d queries" % (off.size - 1, nq))
+        out_idx = np.full((nq, max(k, 1)), 0xFFFFFFFF, np.uint32)
+        out_dist = np.full((nq, max(k, 1)), np.inf, np.float32)
+        out_cnt = np.zeros(nq, np.uint32)
+        check(load().scann_hip_search_batched_tokens(index.h, self.h, ptr(q, f32p), nq, qs, qs if q_dim is None else q_dim,
+                                                     k, C.byref(opts) if opts is not None else None,
+                                                     ptr(tok, u64p) if tok.size else None, ptr(off, u64p),
+                                                     ptr(out_idx, u32p), ptr(out_dist, f32p), ptr(out_cnt, u32p)))
+        return out_idx, out_dist, out_cnt
+
+
+def allow_bitmaps_from_tokens(indices, tokens, num_datapoints, token_lists, stride_words=None):
+    """The stateless host form of TokenMap(...).allow_bitmaps(token_lists): no context, no GPU; the model the device
+    forms equal bitwise."""
+    idx, tok = _token_pairs(indices, tokens)
+    qt, off = _token_lists(token_lists)
+    nq = off.size - 1
+    stride = (int(num_datapoints) + 63) // 64 if stride_words is None else int(stride_words)
+    out = np.empty((nq, stride), np.uint64)
+    check(load().scann_hip_allow_bitmaps_from_tokens(ptr(idx, u32p) if idx.size else None, ptr(tok, u64p) if tok.size else None,
+                                                     idx.size, int(num_datapoints), ptr(qt, u64p) if qt.size else None,
+                                                     ptr(off, u64p), nq, stride, ptr(out, u64p) if out.size else None))
+    return out
+
+
+def allow_bitmaps_combine(op, a, b, bits, out=None):
+    """AndFilter / OrFilter / NotFilter over bitmap blocks on the host (scann_hip_allow_bitmaps_combine): op is
+    ALLOW_AND, ALLOW_OR, ALLOW_ANDNOT (a & ~b) or ALLOW_NOT (~a, b unused).  a and b are [nq, stride] blocks or 1-D
+    bitmaps shared by all queries (with no 2-D operand, nq is out's row count, else 1).  Words below ceil(bits / 64) of `out`
+    (default: a zeroed [nq, ceil(bits / 64)] block) are written, the last masked to bits; its gap words are left."""
+    words = (int(bits) + 63) // 64
+
+    def operand(x):
+        if x is None:
+            return None, 0, None
+        x = np.ascontiguousarray(x, np.uint64)
+        return x, (x.shape[1] if x.ndim == 2 else 0), (x.shape[0] if x.ndim == 2 else None)
+
+    a, sa, na = operand(a)
+    b, sb, nb = operand(b)
+    nq = na if na is not None else nb
+    if nq is None:   # only shared operands: as many rows as `out` has, else one
+        nq = out.shape[0] if out is not None and out.ndim == 2 else 1
+    for x, s in ((a, sa), (b, sb)):
+        if x is not None and s == 0 and x.size < words:
+            raise ValueError("a shared bitmap needs ceil(bits / 64) = %d words" % words)
+    if out is None:
+        out = np.zeros((nq, words), np.uint64)
+    if out.dtype != np.uint64 or out.ndim != 2 or out.shape[0] != nq or not out.flags.c_contiguous:
+        raise ValueError("out must be a C-contiguous [nq, stride] uint64 block")
+    check(load().scann_hip_allow_bitmaps_combine(int(op), ptr(a, u64p), sa, ptr(b, u64p), sb, nq, int(bits),
+                                                 ptr(out, u64p) if out.size else None, out.shape[1]))
+    return out
+
+
+def allow_bitmaps_combine_device(op, d_a, stride_a, d_b, stride_b, nq, bits, d_out, stride_out, stream=0, device=0):
+    """scann_hip_allow_bitmaps_combine_device: device addresses (integers; d_b = 0 for ALLOW_NOT), strides in words (0:
+    one bitmap shared by all queries) and a HIP stream handle; one kernel is enqueued, nothing is synchronised.  d_out
+    may be d_a or d_b with the same stride."""
+    check(load().scann_hip_allow_bitmaps_combine_device(context(device), int(op), vp(d_a), int(stride_a), vp(d_b or None),
+                                                        int(stride_b), int(nq), int(bits), vp(d_out), int(stride_out),
+                                                        vp(stream)))
 
 
 def allow_bitmap(n, allowed):

@@ -215,6 +215,69 @@ private:
     RestrictAllowlist deny_;
 };
 
+// A RestrictTokenMap resident on the device (scann_hip_token_map): what RestrictTokenMap::to_device returns.  The
+// map is a snapshot: tokens added to the host map afterwards are not in it (build a new one).
+class DeviceTokenMap {
+public:
+    DeviceTokenMap() = default;
+    explicit DeviceTokenMap(scann_hip_token_map *h) : h_(h) {}
+    DeviceTokenMap(const DeviceTokenMap &) = delete;
+    DeviceTokenMap &operator=(const DeviceTokenMap &) = delete;
+    DeviceTokenMap(DeviceTokenMap &&o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+    DeviceTokenMap &operator=(DeviceTokenMap &&o) noexcept {
+        if (this != &o) { reset(); h_ = o.h_; o.h_ = nullptr; }
+        return *this;
+    }
+    ~DeviceTokenMap() { reset(); }
+    void reset() { if (h_) scann_hip_token_map_destroy(h_); h_ = nullptr; }
+    scann_hip_token_map *handle() const { return h_; }
+    size_t num_tokens() const { return h_ ? (size_t)scann_hip_token_map_num_tokens(h_) : 0; }
+    size_t num_datapoints() const { return h_ ? (size_t)scann_hip_token_map_num_datapoints(h_) : 0; }
+
+private:
+    scann_hip_token_map *h_ = nullptr;
+};
+
+// Token-based filtering for multi-valued attributes (allowlist.rs:184-244): each datapoint carries any number of
+// tokens; the filter allows datapoints that have at least one of the query's tokens.  The host type is the
+// reference's: get_indices keeps insertion order, duplicates and out-of-range indices.
+class RestrictTokenMap {
+public:
+    explicit RestrictTokenMap(size_t num_datapoints) : num_datapoints_(num_datapoints) {}                    // :198-203
+    void add_token(DatapointIndex index, uint64_t token) { token_to_indices_[token].push_back(index); }      // :206-211
+    void set_tokens(DatapointIndex index, const std::vector<uint64_t> &tokens) {                              // :214-218
+        for (uint64_t t : tokens) add_token(index, t);
+    }
+    // nullptr for an unknown token (the reference's None)
+    const std::vector<DatapointIndex> *get_indices(uint64_t token) const {                                    // :221-223
+        const auto it = token_to_indices_.find(token);
+        return it == token_to_indices_.end() ? nullptr : &it->second;
+    }
+    RestrictAllowlist create_allowlist(const std::vector<uint64_t> &tokens) const {                           // :226-238
+        RestrictAllowlist a(num_datapoints_);
+        for (uint64_t t : tokens)
+            if (const auto *ix = get_indices(t))
+                for (DatapointIndex i : *ix) a.add(i);
+        return a;
+    }
+    size_t num_tokens() const { return token_to_indices_.size(); }                                            // :241-243
+    size_t num_datapoints() const { return num_datapoints_; }
+    // The map as it stands, uploaded once: scann_hip_token_map_create over every (index, token) pair.
+    DeviceTokenMap to_device(scann_hip_ctx *ctx) const {
+        std::vector<uint32_t> idx;
+        std::vector<uint64_t> tok;
+        for (const auto &kv : token_to_indices_)
+            for (DatapointIndex i : kv.second) { idx.push_back(i); tok.push_back(kv.first); }
+        scann_hip_token_map *h = nullptr;
+        check(scann_hip_token_map_create(ctx, num_datapoints_, idx.data(), tok.data(), idx.size(), &h));
+        return DeviceTokenMap(h);
+    }
+
+private:
+    std::unordered_map<uint64_t, std::vector<DatapointIndex>> token_to_indices_;
+    size_t num_datapoints_;
+};
+
 // ---- crowding (restricts/crowding.rs:10-120) --------------------------------------------------------
 struct CrowdingConfig {              // crowding.rs:10-44
     size_t per_crowd_limit = 3;
@@ -539,6 +602,32 @@ inline std::vector<NNResultsVector> run_search_filters(scann_hip_index *h, const
     o.allow_bitmap_bits = n;
     o.allow_bitmap_stride = stride;
     return run_search(h, flat.data(), (uint32_t)queries.size(), d, d, (uint32_t)k, &o);
+}
+
+// search_with_filter(map.create_allowlist(token_lists[i])) for a batch: the block is built on the device from the
+// resident map and searched on the same stream (scann_hip_search_batched_tokens)
+inline std::vector<NNResultsVector> run_search_tokens(scann_hip_index *h, const std::vector<std::vector<float>> &queries,
+                                                      size_t k, const std::vector<std::vector<uint64_t>> &token_lists,
+                                                      const DeviceTokenMap &map, const scann_hip_search_opts &o) {
+    if (queries.size() != token_lists.size()) throw ScannError::invalid_argument("one token list per query");
+    if (!map.handle()) throw ScannError::failed_precondition("the token map is not on the device");
+    if (queries.empty()) return {};
+    uint32_t d;
+    const auto flat = flatten(queries, &d);
+    const uint32_t nq = (uint32_t)queries.size(), kk = (uint32_t)k;
+    std::vector<uint64_t> tok, off(1, 0);
+    for (const auto &l : token_lists) {
+        tok.insert(tok.end(), l.begin(), l.end());
+        off.push_back(tok.size());
+    }
+    std::vector<uint32_t> idx((size_t)nq * std::max(1u, kk)), cnt(nq);
+    std::vector<float> dist((size_t)nq * std::max(1u, kk));
+    check(scann_hip_search_batched_tokens(h, map.handle(), flat.data(), nq, d, d, kk, &o, tok.data(), off.data(), idx.data(),
+                                          dist.data(), cnt.data()));
+    std::vector<NNResultsVector> out(nq);
+    for (uint32_t i = 0; i < nq; ++i)
+        for (uint32_t j = 0; j < cnt[i]; ++j) out[i].emplace_back(idx[(size_t)i * kk + j], dist[(size_t)i * kk + j]);
+    return out;
 }
 
 // splitmix64: the documented counter-based generator of this build (not rand::StdRng).
@@ -910,6 +999,17 @@ public:
         o.exact_reorder = 0;
         return detail::run_search_filters(ix_.h, queries, k, filters, num_datapoints(), o);
     }
+    // query i under device_map's create_allowlist(token_lists[i]): the bitmap block is built on the device from the
+    // resident map and searched on the same stream; no bitmap or id list crosses from the host
+    std::vector<NNResultsVector> search_batched_with_tokens(const std::vector<std::vector<float>> &queries, size_t k,
+                                                            const std::vector<std::vector<uint64_t>> &token_lists,
+                                                            const DeviceTokenMap &device_map) const {
+        if (!ix_.h) return std::vector<NNResultsVector>(queries.size());
+        scann_hip_search_opts o;
+        scann_hip_search_opts_default(&o);
+        o.exact_reorder = 0;
+        return detail::run_search_tokens(ix_.h, queries, k, token_lists, device_map, o);
+    }
     size_t num_datapoints() const { return n_; }
     size_t dimensionality() const { return dim_; }
     const std::vector<float> &codebook() const { return codebook_; }
@@ -1059,6 +1159,16 @@ public:
         scann_hip_search_opts o;
         scann_hip_search_opts_default(&o);
         return detail::run_search_filters(ix_.h, queries, k, filters, num_datapoints(), o);
+    }
+    // query i under device_map's create_allowlist(token_lists[i]): the bitmap block is built on the device from the
+    // resident map and searched on the same stream; no bitmap or id list crosses from the host
+    std::vector<NNResultsVector> search_batched_with_tokens(const std::vector<std::vector<float>> &queries, size_t k,
+                                                            const std::vector<std::vector<uint64_t>> &token_lists,
+                                                            const DeviceTokenMap &device_map) const {
+        if (!ix_.h) throw ScannError::failed_precondition("Partitioner not built");
+        scann_hip_search_opts o;
+        scann_hip_search_opts_default(&o);
+        return detail::run_search_tokens(ix_.h, queries, k, token_lists, device_map, o);
     }
     // Searcher::search_batched_with_params (tree_x_hybrid/mod.rs:399-409): params[i].num_neighbors per query
     std::vector<NNResultsVector> search_batched_with_params(const std::vector<std::vector<float>> &queries,
