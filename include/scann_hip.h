@@ -152,6 +152,72 @@ int scann_hip_bf_create_quantized(scann_hip_ctx *ctx, const void *rows, uint64_t
  * ((bits >> 16) | 0x40). */
 int scann_hip_bf16_quantize(scann_hip_ctx *ctx, const float *values, uint64_t n, uint16_t *out_bits);
 
+/* ---- scalar quantizer: quantized handles from f32 handles, on the device ------------------------------------
+ * QuantizationStats::from_dataset (quantization/mod.rs:75-110), ScalarQuantizer::calibrate / quantize_value /
+ * dequantize_value (quantization/scalar.rs:103-172) and ScalarQuantizedBruteForceSearcher::new(&dataset, config)
+ * (brute_force/scalar_quantized.rs).  All f32 arithmetic is unfused.
+ *
+ * Modes (the reference's ScalarQuantizerConfig, and one of this library's own):
+ *   SCANN_HIP_SQ_STDDEV     the default config; a = num_std_devs (3.0): r = a * std_dev,
+ *                           min = max(mean - r, stats.min), max = min(mean + r, stats.max)
+ *   SCANN_HIP_SQ_SYMMETRIC  symmetric(): abs_max = max(|stats.min|, |stats.max|), range [-abs_max, abs_max]
+ *   SCANN_HIP_SQ_RANGE      with_range(a, b): min = a, max = b
+ *   SCANN_HIP_SQ_SIGNED     this library's: m = max|x|, s = (float)((double)m / 127.0) (1 when m == 0),
+ *                           code = clip(rintf(x / s), -127, 127) with a correctly rounded division; params4 =
+ *                           {-m, m, s, 1 / s}, zero_point 0; bits must be 8; non-finite values are InvalidArgument.
+ * For the three reference modes, with levels = (1 << bits) - 1, bits 4 or 8, and range = max - min:
+ *   range > 1e-10: scale = range / levels, inv_scale = levels / range, zero_point = roundf(-min * inv_scale) as i32;
+ *   otherwise scale = inv_scale = 1, zero_point = 0.  min > max or a NaN bound -> InvalidArgument.
+ *   code = clamp(roundf((clamp(v, min, max) - min) * inv_scale) as i32, 0, levels) stored as i8 with wrap (128..255
+ *   become -128..-1, the reference's offset-binary bytes); a NaN value gives code 0.
+ *   dequantize = (float)(uint8_t)code * scale + min.  (SCANN_HIP_SQ_SIGNED: (float)code * scale.)
+ * WHAT THE SEARCHERS READ: a quantized handle reads int8 bytes as SIGNED, value = i8 * inv_multiplier, and knows no
+ * min_value -- exactly ScalarQuantizedBruteForceSearcher (scalar_quantized.rs:198-225).  Rows quantized in one of
+ * the three reference modes therefore reproduce the reference INCLUDING that reading of its offset-binary bytes;
+ * SCANN_HIP_SQ_SIGNED is the mode whose codes mean what the searcher reads.
+ *
+ * params4 = {min, max, scale, inv_scale}; stats4 = {min, max, mean, std_dev}. */
+#define SCANN_HIP_SQ_STDDEV 0
+#define SCANN_HIP_SQ_SYMMETRIC 1
+#define SCANN_HIP_SQ_RANGE 2
+#define SCANN_HIP_SQ_SIGNED 3
+/* Stats over the n * dim logical values of the f32 rows resident in `index` (stride padding is never read): min and
+ * max fold with fminf / fmaxf from f32::MAX / f32::MIN (a NaN operand is ignored; which of -0.0 and +0.0 wins a tie is
+ * the platform's choice, as in the reference); sum and sum of squares in f64 in a FIXED order that depends on
+ * (n, dim) only -- the same run to run, on any grid, at any stride; mean = (sum / count) as f32,
+ * variance = ((sum_sq - sum * sum / count) / (count - 1)) as f32 (0 when count == 1), std_dev = sqrtf(variance).
+ * Sources and errors: those of scann_hip_index_quantize_rows. */
+int scann_hip_index_quantization_stats(scann_hip_index *index, float *out_stats4);
+/* Host arithmetic, no GPU and no context needed.  Nothing is written on an error.  a, b: see the modes. */
+int scann_hip_scalar_quantizer_calibrate(const float *stats4, uint32_t bits, int mode, float a, float b,
+                                         float *out_params4, int32_t *out_zero_point);
+int scann_hip_scalar_quantize(const float *values, uint64_t n, uint32_t bits, int mode, const float *params4,
+                              int8_t *out);
+int scann_hip_scalar_dequantize(const int8_t *codes, uint64_t n, int mode, const float *params4, float *out);
+/* The quantize pass on device memory: n rows of dim f32 values at `stride` -> n rows of out_stride codes; columns
+ * dim .. out_stride - 1 are written as 0; nothing past n * out_stride bytes is written.  One kernel is enqueued on
+ * hip_stream, nothing is synchronised.  SCANN_HIP_SQ_SIGNED here maps NaN to 0 and +-inf to +-127 (a stream-ordered
+ * call cannot refuse them).  out_stride < dim, stride < dim, dim == 0, a bad mode / bits / range -> InvalidArgument. */
+int scann_hip_scalar_quantize_device(scann_hip_ctx *ctx, const float *d_rows, uint64_t n, uint32_t dim, uint32_t stride,
+                                     uint32_t bits, int mode, const float *params4, int8_t *d_out, uint32_t out_stride,
+                                     void *hip_stream);
+/* A NEW handle over the rows of `src` stored as row_format (SCANN_HIP_ROWS_*), made on the device from the f32 rows
+ * resident in src: no row visits the host.  src is left untouched and stays usable; destroy it to reclaim its memory.
+ * INT8: stats, calibrate(bits, mode, a, b), quantize; the handle's inv_multiplier is the calibrated scale.  BF16 /
+ * FP8_E4M3: the arithmetic of scann_hip_bf16_quantize / scann_hip_fp8_quantize(scale 1); bits, mode, a, b are
+ * ignored and out_params4 / out_zero_point are written as {0, 0, 1, 1} / 0.  Output rows keep src's stride in
+ * ELEMENTS, pad columns 0.  out_params4 / out_zero_point may be NULL.
+ * A brute-force src gives what scann_hip_bf_create_quantized builds from the same bytes, measure and inv_multiplier;
+ * a Tree-X-Hybrid / AsymmetricHasher src with f32 rows gives what scann_hip_txh_create_quantized builds from the same
+ * descriptor and bytes (its small arrays -- centres, CSR, codes, codebook -- are read back and uploaded again; the
+ * rows are not).  Every search entry point, every refusal and scann_hip_index_device_bytes are those of that twin.
+ * Errors (*out_index is not written): n == 0 ("Cannot quantize empty dataset", scalar.rs:199-201), src already
+ * quantized, unknown row_format, a bad mode / bits / range, non-finite rows in SCANN_HIP_SQ_SIGNED -> InvalidArgument;
+ * a tree handle without rows -> FailedPrecondition; L1 / Cosine, leaf-sharded, SearchMode::Partitioned and
+ * CSR-ordered rows with partitions -> Unimplemented. */
+int scann_hip_index_quantize_rows(scann_hip_index *src, int row_format, uint32_t bits, int mode, float a, float b,
+                                  scann_hip_index **out_index, float *out_params4, int32_t *out_zero_point);
+
 /* ---- Tree-X-Hybrid / AsymmetricHasher ------------------------------------ */
 /* The trained index TreeXHybridSearcher::build (tree_x_hybrid/mod.rs:131-209)
  * or AsymmetricHasher::build (hashes/hasher.rs:109-134) produced, flattened:

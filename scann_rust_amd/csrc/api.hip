@@ -24,6 +24,7 @@
 #include "mutable.h"
 #include "knobs.h"
 #include "launch.h"
+#include "scalarq.h"
 #include "txh.h"
 
 namespace scann {
@@ -303,6 +304,8 @@ int scann::index_base_view(const scann_hip_index *ix, BaseView *v) {
 
 static int index_common_init(scann_hip_index *ix);
 static int bf_finish(scann_hip_index *ix, uint64_t n, uint32_t dim, uint32_t stride, int measure);
+static int bf_finish_quantized(scann_hip_index *ix, uint64_t n, uint32_t dim, uint32_t stride, int row_format,
+                               float inv_multiplier, int measure);
 static int txh_finish(scann_hip_index *ix, const scann_hip_txh_desc *d, const std::vector<uint32_t> &off);
 
 int scann::index_fold_view(const scann_hip_index *ix, FoldView *v) {
@@ -405,7 +408,7 @@ int scann::index_fold_txh(const scann_hip_index *old, DevBuf &rows, DevBuf &code
     return SCANN_HIP_OK;
 }
 
-int scann::index_download(const scann_hip_index *ix, IndexHostArrays *o) {
+int scann::index_download(const scann_hip_index *ix, IndexHostArrays *o, bool with_rows) {
     if (!ix || !o) return fail(SCANN_HIP_INVALID_ARGUMENT, "index is null");
     SCANN_TRY(set_device(ix->ctx));
     auto down = [](auto &vec, const void *src, size_t count) -> int {
@@ -430,7 +433,7 @@ int scann::index_download(const scann_hip_index *ix, IndexHostArrays *o) {
     const TxhIndexDev &t = ix->tx;
     o->brute_force = false;
     txh_desc_of(ix, &d);
-    if (t.rows) {
+    if (t.rows && with_rows) {
         SCANN_TRY(down(o->data, t.rows, (size_t)ix->n_rows * t.stride));
         d.data = o->data.data();
     }
@@ -442,7 +445,7 @@ int scann::index_download(const scann_hip_index *ix, IndexHostArrays *o) {
         d.leaf_offsets = o->leaf_offsets.data();
         d.leaf_ids = o->leaf_ids.data();
     }
-    if (t.qrows) {
+    if (t.qrows && with_rows) {
         o->rows_q.resize((size_t)ix->n_rows * t.stride * (t.qfmt == SCANN_HIP_ROWS_BF16 ? 2 : 1));
         if (!o->rows_q.empty())
             SCANN_HIP_CHECK(hipMemcpy(o->rows_q.data(), t.qrows, o->rows_q.size(), hipMemcpyDeviceToHost));
@@ -645,6 +648,23 @@ static int bf_finish(scann_hip_index *ix, uint64_t n, uint32_t dim, uint32_t str
     return SCANN_HIP_OK;
 }
 
+// The second half of scann_hip_bf_create_quantized: the rows are in ix->bf_rows on the device, as given or written by
+// the quantize pass of scann_hip_index_quantize_rows.  The caller destroys the handle on failure.
+static int bf_finish_quantized(scann_hip_index *ix, uint64_t n, uint32_t dim, uint32_t stride, int row_format,
+                               float inv_multiplier, int measure) {
+    ix->bf.rows = nullptr;
+    ix->bf.n = n;
+    ix->bf.dim = dim;
+    ix->bf.stride = stride;
+    ix->bf.measure = measure;
+    ix->bf.fmt = row_format;
+    ix->bf.qrows = ix->bf_rows.p;
+    ix->bf.inv_mult = row_format == SCANN_HIP_ROWS_INT8 ? inv_multiplier : 1.0f;
+    SCANN_TRY(bf_build_shortlist_data(ix->bf, ix->bf_rows_b, ix->bf_rows_bl, ix->bf_norm2, &ix->bf.max_norm, ix->stream));
+    if (ix->bf_norm2.p) ix->bf.norm2 = ix->bf_norm2.as<float>();
+    return SCANN_HIP_OK;
+}
+
 extern "C" {
 
 // Rows the caller stores quantized (scann_hip.h): uploaded as given, no f32 copy and no small-batch view (bfx stays
@@ -674,20 +694,11 @@ int scann_hip_bf_create_quantized(scann_hip_ctx *ctx, const void *rows, uint64_t
         scann_hip_index_destroy(ix);
         return s;
     }
-    ix->bf.rows = nullptr;
-    ix->bf.n = n;
-    ix->bf.dim = dim;
-    ix->bf.stride = stride;
-    ix->bf.measure = measure;
-    ix->bf.fmt = row_format;
-    ix->bf.qrows = ix->bf_rows.p;
-    ix->bf.inv_mult = row_format == SCANN_HIP_ROWS_INT8 ? inv_multiplier : 1.0f;
-    s = bf_build_shortlist_data(ix->bf, ix->bf_rows_b, ix->bf_rows_bl, ix->bf_norm2, &ix->bf.max_norm, ix->stream);
+    s = bf_finish_quantized(ix, n, dim, stride, row_format, inv_multiplier, measure);
     if (s != SCANN_HIP_OK) {
         scann_hip_index_destroy(ix);
         return s;
     }
-    if (ix->bf_norm2.p) ix->bf.norm2 = ix->bf_norm2.as<float>();
     *out = ix;
     return SCANN_HIP_OK;
 }
@@ -708,10 +719,10 @@ int scann_hip_bf16_quantize(scann_hip_ctx *ctx, const float *values, uint64_t n,
 // content_status: what inconsistent array CONTENTS are reported as (InvalidArgument for caller-built
 // descriptors, DataLoss for index files, whose section sizes were already checked)
 int scann::txh_create_checked(scann_hip_ctx *ctx, const scann_hip_txh_desc *d, scann_hip_index **out,
-                              int content_status, const void *qrows, int qfmt, float qinv) {
+                              int content_status, const void *qrows, int qfmt, float qinv, DevBuf *qrows_dev) {
     if (!ctx || !d || !out) return fail(SCANN_HIP_INVALID_ARGUMENT, "null ctx/desc/out_index");
     const bool ah = d->num_partitions == 0;
-    const bool has_rows = d->data || qrows;   // re-rank rows, f32 or quantized: indexed and validated alike
+    const bool has_rows = d->data || qrows || qrows_dev;   // re-rank rows, f32 or quantized: indexed and validated alike
     if (d->n_local == 0)  // tree_x_hybrid/mod.rs:132-134, hashes/hasher.rs:110-112
         return fail(SCANN_HIP_INVALID_ARGUMENT, "Cannot build from empty dataset");
     if (d->n_local >= 0xFFFFFFFFull) return fail(SCANN_HIP_OUT_OF_RANGE, "DatapointIndex is u32");
@@ -849,6 +860,10 @@ int scann::txh_create_checked(scann_hip_ctx *ctx, const scann_hip_txh_desc *d, s
     if (qrows) {   // as given: no f32 copy, and txh_finish builds no 8-bit shadow store without d->data
         const size_t qbytes = (size_t)d->n_rows * d->stride * (qfmt == SCANN_HIP_ROWS_BF16 ? 2 : 1);
         if ((s = upload(ix->d_qrows, qrows, qbytes)) != SCANN_HIP_OK) return bail(s);
+        ix->q_fmt = qfmt;
+        ix->q_inv = qfmt == SCANN_HIP_ROWS_INT8 ? qinv : 1.0f;
+    } else if (qrows_dev) {   // the same rows, written on the device by the quantize pass
+        ix->d_qrows.take(*qrows_dev);
         ix->q_fmt = qfmt;
         ix->q_inv = qfmt == SCANN_HIP_ROWS_INT8 ? qinv : 1.0f;
     }
@@ -1044,6 +1059,120 @@ int scann_hip_txh_create_quantized(scann_hip_ctx *ctx, const scann_hip_txh_desc 
     if (!ctx || !d || !out) return fail(SCANN_HIP_INVALID_ARGUMENT, "null ctx/desc/out_index");
     SCANN_TRY(scann::txh_quantized_args(d, rows, row_format, inv_multiplier));
     return scann::txh_create_checked(ctx, d, out, SCANN_HIP_INVALID_ARGUMENT, rows, row_format, inv_multiplier);
+}
+
+}  // extern "C"
+
+// ---- scalar quantizer over a handle's f32 rows (scalarq.h) ------------------------------------------
+// The f32 rows scann_hip_index_quantization_stats and scann_hip_index_quantize_rows read, or why there are none.
+struct SqSource {
+    const float *rows = nullptr;
+    uint64_t n = 0;
+    uint32_t dim = 0, stride = 0;
+    int measure = 0;
+};
+
+static int sq_source(const scann_hip_index *ix, SqSource *o) {
+    if (!ix) return fail(SCANN_HIP_INVALID_ARGUMENT, "index is null");
+    if (ix->kind == KIND_BF) {
+        if (ix->bf.fmt) return fail(SCANN_HIP_INVALID_ARGUMENT, "the index already holds quantized rows");
+        if (ix->bf.n == 0) return fail(SCANN_HIP_INVALID_ARGUMENT, "Cannot quantize empty dataset");
+        if (ix->bf.measure == SCANN_HIP_L1 || ix->bf.measure == SCANN_HIP_COSINE)
+            return fail(SCANN_HIP_UNIMPLEMENTED, "quantized rows: SquaredL2, L2 and DotProduct only");
+        *o = SqSource{ix->bf.rows, ix->bf.n, ix->bf.dim, ix->bf.stride, ix->bf.measure};
+        return SCANN_HIP_OK;
+    }
+    const TxhIndexDev &t = ix->tx;
+    if (t.qfmt) return fail(SCANN_HIP_INVALID_ARGUMENT, "the index already holds quantized rows");
+    if (t.measure == SCANN_HIP_L1 || t.measure == SCANN_HIP_COSINE)
+        return fail(SCANN_HIP_UNIMPLEMENTED, "quantized rows: SquaredL2, L2 and DotProduct only");
+    if (ix->sharded || (t.rows_csr && !t.ah_mode))
+        return fail(SCANN_HIP_UNIMPLEMENTED, "quantized rows in a leaf-sharded index are not built");
+    if (t.exact_scan) return fail(SCANN_HIP_UNIMPLEMENTED, "quantized rows in SearchMode::Partitioned (no codes) are not built");
+    if (!t.rows || ix->n_rows == 0) return fail(SCANN_HIP_FAILED_PRECONDITION, "the index stores no rows to quantize");
+    *o = SqSource{t.rows, ix->n_rows, t.dim, t.stride, t.measure};
+    return SCANN_HIP_OK;
+}
+
+extern "C" {
+
+int scann_hip_index_quantization_stats(scann_hip_index *ix, float *out_stats4) {
+    if (!ix || !out_stats4) return fail(SCANN_HIP_INVALID_ARGUMENT, "null index/output");
+    SqSource src;
+    SCANN_TRY(sq_source(ix, &src));
+    SCANN_TRY(set_device(ix->ctx));
+    SqPartial sums;
+    {
+        std::lock_guard<std::mutex> lock(ix->mu);
+        SCANN_TRY(sq_stats_device(src.rows, src.n, src.dim, src.stride, ix->stream, &sums));
+    }
+    sq_stats_finish(sums, src.n * src.dim, out_stats4);
+    return SCANN_HIP_OK;
+}
+
+int scann_hip_index_quantize_rows(scann_hip_index *src_ix, int row_format, uint32_t bits, int mode, float a, float b,
+                                  scann_hip_index **out, float *out_params4, int32_t *out_zero_point) {
+    if (!src_ix || !out) return fail(SCANN_HIP_INVALID_ARGUMENT, "null index/out_index");
+    if (row_format != SCANN_HIP_ROWS_BF16 && row_format != SCANN_HIP_ROWS_FP8_E4M3 && row_format != SCANN_HIP_ROWS_INT8)
+        return fail(SCANN_HIP_INVALID_ARGUMENT, "unknown row format " + std::to_string(row_format));
+    SqSource src;
+    SCANN_TRY(sq_source(src_ix, &src));
+    SCANN_TRY(set_device(src_ix->ctx));
+    SqParams p{0.0f, 0.0f, 1.0f, 1.0f, 255};
+    int32_t zp = 0;
+    const size_t qbytes = (size_t)src.n * src.stride * (row_format == SCANN_HIP_ROWS_BF16 ? 2 : 1);
+    DevBuf qrows;
+    {
+        std::lock_guard<std::mutex> lock(src_ix->mu);   // the source's primary stream runs both passes
+        if (row_format == SCANN_HIP_ROWS_INT8) {
+            // a bad mode / bits / range is refused before any device work
+            const float probe[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+            SqParams tmp{};
+            int32_t tz = 0;
+            SCANN_TRY(sq_calibrate(probe, bits, mode, a, b, &tmp, &tz));
+            SqPartial sums;
+            SCANN_TRY(sq_stats_device(src.rows, src.n, src.dim, src.stride, src_ix->stream, &sums));
+            if (mode == SCANN_HIP_SQ_SIGNED && sums.nonfinite)
+                return fail(SCANN_HIP_INVALID_ARGUMENT, "scalar quantizer: the signed mode needs finite values");
+            float stats4[4];
+            sq_stats_finish(sums, src.n * src.dim, stats4);
+            SCANN_TRY(sq_calibrate(stats4, bits, mode, a, b, &p, &zp));
+        }
+        SCANN_TRY(qrows.ensure(qbytes));
+        SCANN_TRY(launch_sq_quantize(src.rows, src.n, src.dim, src.stride, row_format, mode, p, qrows.p, src.stride,
+                                     src_ix->stream));
+        SCANN_HIP_CHECK(hipStreamSynchronize(src_ix->stream));
+    }
+    const float inv = row_format == SCANN_HIP_ROWS_INT8 ? p.scale : 1.0f;
+    scann_hip_index *ix = nullptr;
+    if (src_ix->kind == KIND_BF) {
+        if (row_format == SCANN_HIP_ROWS_INT8 && !std::isfinite(inv))
+            return fail(SCANN_HIP_INVALID_ARGUMENT, "inv_multiplier is not finite");
+        ix = new scann_hip_index();
+        ix->ctx = src_ix->ctx;
+        ix->kind = KIND_BF;
+        ix->bf_rows.take(qrows);
+        int s = index_common_init(ix);
+        if (s == SCANN_HIP_OK) s = bf_finish_quantized(ix, src.n, src.dim, src.stride, row_format, inv, src.measure);
+        if (s != SCANN_HIP_OK) {
+            scann_hip_index_destroy(ix);
+            return s;
+        }
+    } else {
+        IndexHostArrays arrays;   // centres, CSR, codes, codebook: small next to the rows, which stay on the device
+        SCANN_TRY(index_download(src_ix, &arrays, false));
+        SCANN_TRY(txh_quantized_args(&arrays.d, qrows.p, row_format, inv));
+        SCANN_TRY(txh_create_checked(src_ix->ctx, &arrays.d, &ix, SCANN_HIP_INTERNAL, nullptr, row_format, inv, &qrows));
+    }
+    if (out_params4) {
+        out_params4[0] = p.mn;
+        out_params4[1] = p.mx;
+        out_params4[2] = p.scale;
+        out_params4[3] = p.inv_scale;
+    }
+    if (out_zero_point) *out_zero_point = zp;
+    *out = ix;
+    return SCANN_HIP_OK;
 }
 
 uint64_t scann_hip_index_device_bytes(const scann_hip_index *ix) {

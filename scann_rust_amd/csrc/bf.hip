@@ -1608,16 +1608,11 @@ __global__ __launch_bounds__(256) void bf_quant_kernel(BfIndexDev ix, BfPass p) 
     }
 }
 
-// half::bf16::from_f32 (quantization/bfloat16.rs:13-30): NaN keeps its top bits with the quiet bit set;
-// otherwise round to nearest even on bit 15 (inf stays inf, the largest finite values round up to inf).
+// half::bf16::from_f32 over n values (bf16_from_f32, quant.h)
 __global__ __launch_bounds__(256) void bf16_quantize_kernel(const float *__restrict__ values, uint64_t n,
                                                             uint16_t *__restrict__ out) {
     for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) {
-        const uint32_t x = __float_as_uint(values[i]);
-        uint32_t b;
-        if ((x & 0x7FFFFFFFu) > 0x7F800000u) b = (x >> 16) | 0x40u;
-        else b = (x >> 16) + (((x & 0x8000u) && (x & 0x17FFFu)) ? 1u : 0u);
-        out[i] = (uint16_t)b;
+        out[i] = (uint16_t)bf16_from_f32(values[i]);
     }
 }
 

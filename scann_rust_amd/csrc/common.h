@@ -16,9 +16,12 @@ void set_last_error(const std::string &msg);
 int fail(int status, const std::string &msg);
 // scann_hip_txh_create with the status reported for inconsistent array CONTENTS (api.hip)
 // qrows != nullptr: scann_hip_txh_create_quantized -- d->data is NULL and the re-rank rows are qrows, n_rows rows of
-// d->stride elements of qfmt (SCANN_HIP_ROWS_*), int8 values scaled by qinv
+// d->stride elements of qfmt (SCANN_HIP_ROWS_*), int8 values scaled by qinv.  qrows_dev (with qrows == nullptr): the same
+// rows already on the device, in an allocation the new handle takes over (scann_hip_index_quantize_rows)
+struct DevBuf;
 int txh_create_checked(scann_hip_ctx *ctx, const scann_hip_txh_desc *d, scann_hip_index **out,
-                       int content_status, const void *qrows = nullptr, int qfmt = 0, float qinv = 1.0f);
+                       int content_status, const void *qrows = nullptr, int qfmt = 0, float qinv = 1.0f,
+                       DevBuf *qrows_dev = nullptr);
 // the argument checks scann_hip_txh_create_quantized makes before those of scann_hip_txh_create (api.hip)
 int txh_quantized_args(const scann_hip_txh_desc *d, const void *rows, int row_format, float inv_multiplier);
 

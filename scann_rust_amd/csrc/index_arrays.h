@@ -16,6 +16,7 @@ struct IndexHostArrays {
     int rows_q_fmt = 0;                                    // ... their SCANN_HIP_ROWS_* format, 0 = none ...
     float rows_q_inv = 1.0f;                               // ... and the int8 inv_multiplier
 };
-int index_download(const scann_hip_index *ix, IndexHostArrays *out);
+// with_rows = false: everything but the f32 / quantized rows (d.data stays null; d.n_rows is still the handle's)
+int index_download(const scann_hip_index *ix, IndexHostArrays *out, bool with_rows = true);
 
 }  // namespace scann

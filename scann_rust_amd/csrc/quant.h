@@ -20,6 +20,35 @@ __device__ __forceinline__ float fp8_e4m3_to_f32(uint32_t b) {
     return __uint_as_float(((b & 0x80u) << 24) | mag);
 }
 
+// ---- encoders (the quantize entry points of bf.hip / txh_rows.hip and the row passes of scalarq.hip) ----
+// half::bf16::from_f32 (quantization/bfloat16.rs:13-30): NaN keeps its top bits with the quiet bit set;
+// otherwise round to nearest even on bit 15 (inf stays inf, the largest finite values round up to inf).
+__device__ __forceinline__ uint32_t bf16_from_f32(float value) {
+    const uint32_t x = __float_as_uint(value);
+    if ((x & 0x7FFFFFFFu) > 0x7F800000u) return ((x >> 16) | 0x40u) & 0xFFFFu;
+    return ((x >> 16) + (((x & 0x8000u) && (x & 0x17FFFu)) ? 1u : 0u)) & 0xFFFFu;
+}
+
+// The reference's FP8 encoder (quantization/fp8.rs:80-140), bit for bit.
+// format 0 = E4M3 (bias 7, 3 mantissa bits, max code 0x7E), 1 = E5M2 (bias 15, 2 bits, max code 0x7C).
+// NOT the hardware conversion: the mantissa carry wraps without bumping the exponent, the top exponent
+// field only ever encodes the maximum, values under the smallest normal flush to (signed) zero.
+__device__ __forceinline__ uint32_t fp8_from_f32(float value, int format) {
+    const int mbits = format ? 2 : 3, bias = format ? 15 : 7, emax = format ? 31 : 15;
+    const uint32_t maxcode = format ? 0x7Cu : 0x7Eu;
+    if (value == 0.0f) return 0u;
+    const uint32_t bits = __float_as_uint(value);
+    const uint32_t sign = bits >> 31;
+    const int exp = (int)((bits >> 23) & 0xFFu);
+    const uint32_t mantissa = bits & 0x7FFFFFu;
+    if (exp == 0xFF) return (sign << 7) | maxcode;
+    const int e8 = exp - 127 + bias;
+    if (e8 <= 0) return sign << 7;
+    if (e8 >= emax) return (sign << 7) | maxcode;
+    const uint32_t m = ((mantissa >> (23 - mbits)) + ((mantissa >> (22 - mbits)) & 1u)) & ((1u << mbits) - 1u);
+    return (sign << 7) | ((uint32_t)e8 << mbits) | m;
+}
+
 // element `sub` of a 32-bit word of packed row elements
 template <int FMT>
 __device__ __forceinline__ float quant_decode(uint32_t w, int sub, float inv) {

@@ -43,25 +43,7 @@ __global__ __launch_bounds__(256) void rows_i8_build_kernel(const float *__restr
 }
 
 // ---- the reference's FP8 codec (quantization/fp8.rs:80-203), bit for bit -----------------------------
-// format 0 = E4M3 (bias 7, 3 mantissa bits, max code 0x7E), 1 = E5M2 (bias 15, 2 bits, max code 0x7C).
-// NOT the hardware conversion: the mantissa carry wraps without bumping the exponent, the top exponent
-// field only ever encodes the maximum, values under the smallest normal flush to (signed) zero.
-__device__ __forceinline__ uint32_t fp8_from_f32(float value, int format) {
-    const int mbits = format ? 2 : 3, bias = format ? 15 : 7, emax = format ? 31 : 15;
-    const uint32_t maxcode = format ? 0x7Cu : 0x7Eu;
-    if (value == 0.0f) return 0u;
-    const uint32_t bits = __float_as_uint(value);
-    const uint32_t sign = bits >> 31;
-    const int exp = (int)((bits >> 23) & 0xFFu);
-    const uint32_t mantissa = bits & 0x7FFFFFu;
-    if (exp == 0xFF) return (sign << 7) | maxcode;
-    const int e8 = exp - 127 + bias;
-    if (e8 <= 0) return sign << 7;
-    if (e8 >= emax) return (sign << 7) | maxcode;
-    const uint32_t m = ((mantissa >> (23 - mbits)) + ((mantissa >> (22 - mbits)) & 1u)) & ((1u << mbits) - 1u);
-    return (sign << 7) | ((uint32_t)e8 << mbits) | m;
-}
-
+// (the encoder fp8_from_f32: quant.h, shared with the f32 -> FP8 row pass of scalarq.hip)
 __device__ __forceinline__ float fp8_to_f32(uint32_t b, int format) {
     const int mbits = format ? 2 : 3, bias = format ? 15 : 7;
     const uint32_t sign = (b >> 7) & 1u;

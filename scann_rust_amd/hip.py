@@ -67,6 +67,8 @@ EXPORTS = [
     "scann_hip_token_map_num_datapoints", "scann_hip_token_map_get_indices", "scann_hip_token_map_allow_bitmaps_device",
     "scann_hip_token_map_allow_bitmaps", "scann_hip_allow_bitmaps_from_tokens", "scann_hip_search_batched_tokens",
     "scann_hip_allow_bitmaps_combine", "scann_hip_allow_bitmaps_combine_device",
+    "scann_hip_index_quantization_stats", "scann_hip_scalar_quantizer_calibrate", "scann_hip_scalar_quantize",
+    "scann_hip_scalar_dequantize", "scann_hip_scalar_quantize_device", "scann_hip_index_quantize_rows",
 ]
 
 
@@ -84,6 +86,8 @@ u32p = C.POINTER(C.c_uint32)
 u64p = C.POINTER(C.c_uint64)
 u16p = C.POINTER(C.c_uint16)
 u8p = C.POINTER(C.c_uint8)
+i8p = C.POINTER(C.c_int8)
+i32p = C.POINTER(C.c_int32)
 vp = C.c_void_p
 
 
@@ -287,6 +291,14 @@ def load():
                                                   u64p, C.c_uint64]
     L.scann_hip_allow_bitmaps_combine_device.argtypes = [vp, C.c_int, vp, C.c_uint64, vp, C.c_uint64, C.c_uint32,
                                                          C.c_uint64, vp, C.c_uint64, vp]
+    L.scann_hip_index_quantization_stats.argtypes = [vp, f32p]
+    L.scann_hip_scalar_quantizer_calibrate.argtypes = [f32p, C.c_uint32, C.c_int, C.c_float, C.c_float, f32p, i32p]
+    L.scann_hip_scalar_quantize.argtypes = [f32p, C.c_uint64, C.c_uint32, C.c_int, f32p, i8p]
+    L.scann_hip_scalar_dequantize.argtypes = [i8p, C.c_uint64, C.c_int, f32p, f32p]
+    L.scann_hip_scalar_quantize_device.argtypes = [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, f32p,
+                                                   vp, C.c_uint32, vp]
+    L.scann_hip_index_quantize_rows.argtypes = [vp, C.c_int, C.c_uint32, C.c_int, C.c_float, C.c_float, C.POINTER(vp),
+                                                f32p, i32p]
     _lib = L
     return L
 
@@ -586,6 +598,22 @@ class Index:
         check(load().scann_hip_index_debug_rerank_brackets(self.h, vp(stream), nq, m, ptr(lb, u32p), ptr(ub, u32p),
                                                            ptr(rows, u32p), ptr(counts, u32p)))
         return lb, ub, rows, counts
+
+
+    def quantize_rows(self, fmt, mode=None, bits=8, num_std_devs=3.0, value_range=None):
+        """A NEW Index over this handle's f32 rows stored as `fmt` (ROWS_BF16, ROWS_FP8_E4M3, ROWS_INT8), made on the
+        device (scann_hip_index_quantize_rows); this handle stays as it is.  INT8: `mode` (default SQ_SIGNED, the mode
+        whose codes mean what the searcher reads; SQ_STDDEV / SQ_SYMMETRIC / SQ_RANGE reproduce the reference,
+        offset-binary bytes read as signed included), `bits`, `num_std_devs` (SQ_STDDEV), `value_range` = (min, max)
+        (SQ_RANGE).  Returns (Index, params): params = {min, max, scale, inv_scale, zero_point}."""
+        mode = SQ_SIGNED if mode is None else mode
+        a, b = _sq_ab(mode, num_std_devs, value_range)
+        h = vp()
+        params = np.zeros(4, np.float32)
+        zp = C.c_int32(0)
+        check(load().scann_hip_index_quantize_rows(self.h, int(fmt), int(bits), int(mode), a, b, C.byref(h),
+                                                   ptr(params, f32p), C.byref(zp)))
+        return Index(h), _sq_params(params, zp.value)
 
 
 class Mutable:
@@ -989,6 +1017,79 @@ def symmetric_int8(rows):
     s = np.float32(m / 127.0) if m > 0 else np.float32(1.0)
     codes = np.clip(np.rint(x / s), -127, 127).astype(np.int8)
     return codes, float(s)
+
+
+SQ_STDDEV, SQ_SYMMETRIC, SQ_RANGE, SQ_SIGNED = 0, 1, 2, 3   # SCANN_HIP_SQ_*
+
+
+def _sq_ab(mode, num_std_devs, value_range):
+    """the (a, b) arguments of the C entry points for a mode"""
+    if mode == SQ_RANGE:
+        if value_range is None:
+            raise ValueError("SQ_RANGE needs value_range=(min, max)")
+        return C.c_float(value_range[0]), C.c_float(value_range[1])
+    return C.c_float(num_std_devs), C.c_float(0.0)
+
+
+def _sq_params(params4, zero_point):
+    return {"min": float(params4[0]), "max": float(params4[1]), "scale": float(params4[2]),
+            "inv_scale": float(params4[3]), "zero_point": int(zero_point)}
+
+
+def quantization_stats(index):
+    """QuantizationStats::from_dataset over the f32 rows resident in `index`, on the device
+    (scann_hip_index_quantization_stats): float32 [min, max, mean, std_dev]."""
+    out = np.zeros(4, np.float32)
+    check(load().scann_hip_index_quantization_stats(index.h, ptr(out, f32p)))
+    return out
+
+
+class ScalarQuantizer:
+    """ScalarQuantizer (quantization/scalar.rs) through the library's stateless host functions: no GPU needed.
+    mode SQ_STDDEV (the default config), SQ_SYMMETRIC, SQ_RANGE (value_range) or this library's SQ_SIGNED
+    (hip.symmetric_int8 bit for bit).  calibrate(stats) takes [min, max, mean, std_dev]."""
+
+    def __init__(self, bits=8, mode=SQ_STDDEV, num_std_devs=3.0, value_range=None):
+        self.bits, self.mode = int(bits), int(mode)
+        self.num_std_devs, self.value_range = num_std_devs, value_range
+        self.params = np.array([0.0, 1.0, 1.0, 1.0], np.float32)   # ScalarQuantizer::new
+        self.zero_point = 0
+
+    def calibrate(self, stats):
+        st = np.ascontiguousarray(stats, np.float32).ravel()
+        if st.size != 4:
+            raise ValueError("stats is [min, max, mean, std_dev]")
+        a, b = _sq_ab(self.mode, self.num_std_devs, self.value_range)
+        params = np.zeros(4, np.float32)
+        zp = C.c_int32(0)
+        check(load().scann_hip_scalar_quantizer_calibrate(ptr(st, f32p), self.bits, self.mode, a, b, ptr(params, f32p),
+                                                          C.byref(zp)))
+        self.params, self.zero_point = params, int(zp.value)
+        return _sq_params(params, zp.value)
+
+    def quantize(self, values, out=None):
+        v = f32(values)
+        if out is None:
+            out = np.zeros(v.shape, np.int8)
+        check(load().scann_hip_scalar_quantize(ptr(v, f32p) if v.size else None, v.size, self.bits, self.mode,
+                                               ptr(self.params, f32p), ptr(out, i8p) if v.size else None))
+        return out
+
+    def dequantize(self, codes, out=None):
+        c = np.ascontiguousarray(codes, np.int8)
+        if out is None:
+            out = np.zeros(c.shape, np.float32)
+        check(load().scann_hip_scalar_dequantize(ptr(c, i8p) if c.size else None, c.size, self.mode,
+                                                 ptr(self.params, f32p), ptr(out, f32p) if c.size else None))
+        return out
+
+
+def scalar_quantize_device(d_rows, n, dim, stride, d_out, out_stride, params4, bits=8, mode=SQ_STDDEV, stream=0, device=0):
+    """scann_hip_scalar_quantize_device: device addresses (integers) and a HIP stream handle; one kernel is enqueued,
+    nothing is synchronised.  d_out holds n * out_stride int8; params4 = [min, max, scale, inv_scale]."""
+    p = np.ascontiguousarray(params4, np.float32).ravel()
+    check(load().scann_hip_scalar_quantize_device(context(device), vp(d_rows), int(n), int(dim), int(stride), int(bits),
+                                                  int(mode), ptr(p, f32p), vp(d_out), int(out_stride), vp(stream or None)))
 
 
 def txh_create(*, data, n_rows, dim, stride, centers, leaf_offsets, leaf_ids, codebook, codes,

@@ -5,6 +5,8 @@
 //
 //   scann::DenseDataset                 data_format/dataset.rs:46-280
 //   scann::BruteForceSearcher           brute_force/searcher.rs:18-208
+//   scann::QuantizationStats, ScalarQuantizer(+Config), QuantizedDataset   quantization/mod.rs:62-145, scalar.rs:10-300
+//   scann::ScalarQuantizedBruteForceSearcher(+Config)   brute_force/scalar_quantized.rs:24-348 (`create` is its `new`)
 //   scann::AsymmetricHasher(+Config)    hashes/hasher.rs:19-258
 //   scann::TreeXHybridSearcher(+Config) tree_x_hybrid/mod.rs:23-418
 //   scann::ScannBuilder / scann::Scann  scann.rs:35-56, 364-426
@@ -803,6 +805,246 @@ private:
     detail::IndexHandle ix_;
     detail::CrowdAttach crowd_;
     detail::CrowdMdAttach crowd_md_;
+};
+
+// ---- scalar quantizer (quantization/mod.rs:62-145, quantization/scalar.rs:10-177) ----------------------------
+struct QuantizationStats {
+    float min_value = 0.0f, max_value = 0.0f, mean = 0.0f, std_dev = 0.0f;
+    // the reference's sequential f64 sums over the logical values, on the host
+    static QuantizationStats from_dataset(const DenseDataset &ds) {
+        float mn = std::numeric_limits<float>::max(), mx = std::numeric_limits<float>::lowest();
+        double sum = 0.0, sum_sq = 0.0;
+        uint64_t count = 0;
+        for (size_t i = 0; i < ds.size(); ++i)
+            for (uint32_t j = 0; j < ds.dimensionality(); ++j) {
+                const float v = ds.get(i)[j];
+                mn = std::fmin(mn, v);
+                mx = std::fmax(mx, v);
+                sum += (double)v;
+                sum_sq += (double)v * (double)v;
+                ++count;
+            }
+        QuantizationStats s;
+        s.min_value = mn;
+        s.max_value = mx;
+        s.mean = count ? (float)(sum / (double)count) : 0.0f;
+        const float var = count > 1 ? (float)((sum_sq - sum * sum / (double)count) / (double)(count - 1)) : 0.0f;
+        s.std_dev = std::sqrt(var);
+        return s;
+    }
+    static QuantizationStats from_vecs(const std::vector<std::vector<float>> &data) {
+        return from_dataset(DenseDataset::from_vecs(data));
+    }
+    // the same statistics of the f32 rows resident in a handle, reduced on the device (scann_hip_index_quantization_stats)
+    static QuantizationStats from_index(scann_hip_index *h) {
+        float st[4];
+        check(scann_hip_index_quantization_stats(h, st));
+        QuantizationStats s;
+        s.min_value = st[0]; s.max_value = st[1]; s.mean = st[2]; s.std_dev = st[3];
+        return s;
+    }
+};
+
+struct ScalarQuantizerConfig {       // scalar.rs:10-67
+    size_t bits = 8;
+    bool has_range = false;          // min_value / max_value: Some
+    float min_value = 0.0f, max_value = 0.0f;
+    bool is_symmetric = false;
+    float num_std_devs = 3.0f;
+    static ScalarQuantizerConfig int8() { return ScalarQuantizerConfig{}; }
+    static ScalarQuantizerConfig int4() {
+        ScalarQuantizerConfig c;
+        c.bits = 4;
+        return c;
+    }
+    ScalarQuantizerConfig with_range(float mn, float mx) const {
+        ScalarQuantizerConfig c = *this;
+        c.has_range = true;
+        c.min_value = mn;
+        c.max_value = mx;
+        return c;
+    }
+    ScalarQuantizerConfig symmetric() const {
+        ScalarQuantizerConfig c = *this;
+        c.is_symmetric = true;
+        return c;
+    }
+    // mode and (a, b) of the C entry points: an explicit range wins over symmetric, as in calibrate()
+    int mode() const { return has_range ? SCANN_HIP_SQ_RANGE : (is_symmetric ? SCANN_HIP_SQ_SYMMETRIC : SCANN_HIP_SQ_STDDEV); }
+    float a() const { return has_range ? min_value : num_std_devs; }
+    float b() const { return has_range ? max_value : 0.0f; }
+};
+
+class ScalarQuantizer {              // scalar.rs:69-177, through the library's stateless host functions
+public:
+    explicit ScalarQuantizer(ScalarQuantizerConfig config = ScalarQuantizerConfig{}) : config_(config) {}
+    void calibrate(const QuantizationStats &stats) {
+        const float st[4] = {stats.min_value, stats.max_value, stats.mean, stats.std_dev};
+        check(scann_hip_scalar_quantizer_calibrate(st, (uint32_t)config_.bits, config_.mode(), config_.a(), config_.b(),
+                                                   params_, &zero_point_));
+    }
+    void calibrate_from_dataset(const DenseDataset &ds) { calibrate(QuantizationStats::from_dataset(ds)); }
+    // adopts what scann_hip_index_quantize_rows calibrated on the device
+    void set_params(const float *params4, int32_t zero_point) {
+        std::memcpy(params_, params4, sizeof(params_));
+        zero_point_ = zero_point;
+    }
+    float scale() const { return params_[2]; }
+    int32_t zero_point() const { return zero_point_; }
+    float min_value() const { return params_[0]; }
+    float max_value() const { return params_[1]; }
+    size_t bits() const { return config_.bits; }
+    const ScalarQuantizerConfig &config() const { return config_; }
+    int8_t quantize_value(float value) const { return quantize({value})[0]; }
+    float dequantize_value(int8_t q) const { return dequantize({q})[0]; }
+    std::vector<int8_t> quantize(const std::vector<float> &values) const {
+        std::vector<int8_t> out(values.size());
+        check(scann_hip_scalar_quantize(values.data(), values.size(), (uint32_t)config_.bits, config_.mode(), params_,
+                                        out.data()));
+        return out;
+    }
+    std::vector<float> dequantize(const std::vector<int8_t> &codes) const {
+        std::vector<float> out(codes.size());
+        check(scann_hip_scalar_dequantize(codes.data(), codes.size(), config_.mode(), params_, out.data()));
+        return out;
+    }
+
+private:
+    ScalarQuantizerConfig config_;
+    float params_[4] = {0.0f, 1.0f, 1.0f, 1.0f};   // ScalarQuantizer::new: min 0, max 1, scale 1, inv_scale 1
+    int32_t zero_point_ = 0;
+};
+
+class QuantizedDataset {             // scalar.rs:179-300: stride == dimensionality, codes on the host
+public:
+    static QuantizedDataset from_dataset(const DenseDataset &ds, ScalarQuantizer quantizer) {
+        if (ds.is_empty()) throw ScannError::invalid_argument("Cannot quantize empty dataset");
+        quantizer.calibrate_from_dataset(ds);
+        QuantizedDataset q(std::move(quantizer));
+        q.n_ = ds.size();
+        q.dim_ = ds.dimensionality();
+        std::vector<float> flat(q.n_ * q.dim_);
+        for (size_t i = 0; i < q.n_; ++i) std::memcpy(&flat[i * q.dim_], ds.get(i), q.dim_ * 4);
+        q.data_ = q.quantizer_.quantize(flat);
+        return q;
+    }
+    size_t size() const { return n_; }
+    size_t dimensionality() const { return dim_; }
+    const std::vector<int8_t> &raw_data() const { return data_; }
+    const ScalarQuantizer &quantizer() const { return quantizer_; }
+    std::vector<float> get_dequantized(DatapointIndex i) const {
+        return quantizer_.dequantize(std::vector<int8_t>(data_.begin() + (size_t)i * dim_, data_.begin() + ((size_t)i + 1) * dim_));
+    }
+
+private:
+    explicit QuantizedDataset(ScalarQuantizer q) : quantizer_(std::move(q)) {}
+    std::vector<int8_t> data_;
+    size_t n_ = 0, dim_ = 0;
+    ScalarQuantizer quantizer_;
+};
+
+// ---- ScalarQuantizedBruteForceSearcher (brute_force/scalar_quantized.rs:24-348) --------------------------------
+struct ScalarQuantizedConfig {
+    ScalarQuantizerConfig quantizer_config;
+    DistanceMeasure distance_measure = DistanceMeasure::SquaredL2;
+    bool parallel = true;                    // (the device runs every batch at once: kept for the signature)
+    size_t parallel_batch_threshold = 100;
+    static ScalarQuantizedConfig squared_l2() { return ScalarQuantizedConfig{}; }
+    static ScalarQuantizedConfig dot_product() { return ScalarQuantizedConfig{}.with_distance(DistanceMeasure::DotProduct); }
+    ScalarQuantizedConfig with_distance(DistanceMeasure d) const {
+        ScalarQuantizedConfig c = *this;
+        c.distance_measure = d;
+        return c;
+    }
+    ScalarQuantizedConfig with_parallel(bool p) const {
+        ScalarQuantizedConfig c = *this;
+        c.parallel = p;
+        return c;
+    }
+};
+
+// The reference reads the quantizer's offset-binary bytes as SIGNED and ignores min_value (:198-225); so does the
+// library (include/scann_hip.h "scalar quantizer"), and so does this class.
+class ScalarQuantizedBruteForceSearcher {
+public:
+    // new(&dataset, config): the f32 rows are uploaded once, quantized ON THE DEVICE (scann_hip_index_quantize_rows:
+    // stats, calibrate, quantize) and the f32 handle is released.
+    static ScalarQuantizedBruteForceSearcher create(const DenseDataset &dataset, ScalarQuantizedConfig config, int device = 0) {
+        if (dataset.is_empty()) throw ScannError::invalid_argument("Cannot quantize empty dataset");
+        detail::IndexHandle f32;
+        check(scann_hip_bf_create(context(device), dataset.raw_data(), dataset.size(), dataset.dimensionality(),
+                                  dataset.stride(), (int)config.distance_measure, &f32.h));
+        ScalarQuantizedBruteForceSearcher s(config.distance_measure, ScalarQuantizer(config.quantizer_config));
+        const ScalarQuantizerConfig &qc = config.quantizer_config;
+        float params[4];
+        int32_t zp = 0;
+        check(scann_hip_index_quantize_rows(f32.h, SCANN_HIP_ROWS_INT8, (uint32_t)qc.bits, qc.mode(), qc.a(), qc.b(),
+                                            &s.ix_.h, params, &zp));
+        s.quantizer_.set_params(params, zp);
+        s.n_ = dataset.size();
+        s.dim_ = dataset.dimensionality();
+        s.stride_ = dataset.stride();
+        return s;
+    }
+    static ScalarQuantizedBruteForceSearcher from_quantized(const QuantizedDataset &q, DistanceMeasure measure, int device = 0) {
+        ScalarQuantizedBruteForceSearcher s(measure, q.quantizer());
+        check(scann_hip_bf_create_quantized(context(device), q.raw_data().data(), q.size(), (uint32_t)q.dimensionality(),
+                                            (uint32_t)q.dimensionality(), SCANN_HIP_ROWS_INT8, q.quantizer().scale(),
+                                            (int)measure, &s.ix_.h));
+        s.n_ = q.size();
+        s.dim_ = s.stride_ = q.dimensionality();
+        return s;
+    }
+    NNResultsVector search(const std::vector<float> &query, size_t k) const {   // :168-184
+        if (n_ == 0) return {};
+        if (query.size() != dim_)
+            throw ScannError::invalid_argument("Query dimensionality " + std::to_string(query.size()) +
+                                               " does not match dataset dimensionality " + std::to_string(dim_));
+        return detail::run_search(ix_.h, query.data(), 1, (uint32_t)query.size(), (uint32_t)query.size(), (uint32_t)k,
+                                  nullptr)[0];
+    }
+    std::vector<NNResultsVector> search_batched(const std::vector<std::vector<float>> &queries, size_t k) const {
+        if (queries.empty()) return {};                                          // :293-295
+        uint32_t d;
+        auto flat = detail::flatten(queries, &d);
+        return detail::run_search(ix_.h, flat.data(), (uint32_t)queries.size(), d, d, (uint32_t)k, nullptr);
+    }
+    NNResultsVector search_radius(const std::vector<float> &query, float radius) const {   // :260-285
+        if (n_ == 0) return {};
+        if (query.size() != dim_) throw ScannError::invalid_argument("Query dimensionality does not match dataset");
+        std::vector<uint32_t> idx(256);
+        std::vector<float> dist(256);
+        uint64_t found = 0;
+        for (;;) {
+            check(scann_hip_bf_search_radius(ix_.h, query.data(), (uint32_t)query.size(), radius, idx.data(), dist.data(),
+                                             idx.size(), &found));
+            if (found <= idx.size()) break;
+            idx.resize(found);
+            dist.resize(found);
+        }
+        NNResultsVector r(found);
+        for (size_t i = 0; i < found; ++i) r[i] = {idx[i], dist[i]};
+        return r;
+    }
+    // bytes the handle keeps on the device: the rows at their stride, plus a squared norm per row where the index
+    // qualifies for the shortlist (the reference counts codes + norms, :329-333)
+    size_t memory_usage() const { return (size_t)scann_hip_index_device_bytes(ix_.h); }
+    float compression_ratio() const {                                            // :336-347
+        const size_t quantized = n_ * stride_;
+        return quantized ? (float)(n_ * dim_ * sizeof(float)) / (float)quantized : 0.0f;
+    }
+    const ScalarQuantizer &quantizer() const { return quantizer_; }
+    DistanceMeasure distance_measure() const { return measure_; }
+    size_t dataset_size() const { return n_; }
+    uint64_t dimensionality() const { return dim_; }
+    scann_hip_index *handle() const { return ix_.h; }
+
+private:
+    ScalarQuantizedBruteForceSearcher(DistanceMeasure m, ScalarQuantizer q) : measure_(m), quantizer_(std::move(q)) {}
+    DistanceMeasure measure_;
+    ScalarQuantizer quantizer_;
+    detail::IndexHandle ix_;
+    size_t n_ = 0, dim_ = 0, stride_ = 0;
 };
 
 // ---- MutableIndex: MutableDataset (mutator/mod.rs:233-490) over a live brute-force index -------------
