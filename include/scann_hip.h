@@ -851,10 +851,10 @@ int scann_hip_bf_distances(scann_hip_index *index, const float *queries, uint32_
  *   the final assignment.  Bit-identical to the reference's loop from the same initial centres.
  *   Outputs may be NULL.  A row whose every distance is NaN (a NaN element in the row, or in every centre)
  *   joins cluster 0 and adds +inf to the inertia, as assign_clusters' min_dist does.
- * LIMIT: the assignment stages whole centres in LDS (160 KB per workgroup): 16 centres in the sequential
- *   order, 8 in the AVX2 order, each padded to a multiple of 4 values.  sub_dim > 2560 (sequential order)
- *   or > 5120 (AVX2 order) makes scann_hip_kmeans_lloyd return ResourceExhausted (the seeding stages no
- *   centres and has no such limit). */
+ * LIMIT: the assignment stages whole centres in LDS (160 KB per workgroup), each padded to a multiple of 4
+ *   values: 16 centres in the sequential order (8 where 16 do not fit, sub_dim > 2560), 8 in the AVX2 order.
+ *   sub_dim > 5120 makes scann_hip_kmeans_lloyd return ResourceExhausted in either order (the seeding stages
+ *   no centres and has no such limit). */
 int scann_hip_kmeans_init_pp(scann_hip_index *bf_index, uint32_t col_offset, uint32_t sub_dim, uint32_t k,
                              uint64_t seed, uint32_t simd_threshold, float *centers_out);
 int scann_hip_kmeans_lloyd(scann_hip_index *bf_index, uint32_t col_offset, uint32_t sub_dim, float *centers,
@@ -983,7 +983,8 @@ int scann_hip_bf_search_radius(scann_hip_index *index, const float *query, uint3
  * and disagree on the value (partition(x, 1) reports the NaN, assign_clusters keeps its initial +inf); the
  * library's value is assign_clusters'.
  * LIMIT: 16 centres are staged in LDS, each padded to a multiple of 4 values: 64 * ceil(dim / 4) * 4 bytes of
- * the workgroup's 160 KB.  dim > 2560 returns ResourceExhausted. */
+ * the workgroup's 160 KB; 8 centres where 16 do not fit (dim > 2560; the result does not depend on the tile).
+ * dim > 5120 returns ResourceExhausted. */
 int scann_hip_bf_assign_nearest(scann_hip_index *index, const float *centers, uint32_t num_centers,
                                 uint32_t *out_assign, float *out_dist);
 

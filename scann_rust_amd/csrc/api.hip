@@ -1271,7 +1271,7 @@ static int plan_txh_search(const scann_hip_index *ix, uint32_t k, const scann_hi
     // list slots, and a shard's local leaves leave holes in them.
     p.pipeline = TxhPipeline::Staged;
     if (widest != TxhPipeline::Staged && kn.small && nq <= kSmallBatch && !ix->sharded && m <= kSmallMaxCandidates &&
-        k <= 64 && ms <= kSmallMaxStream && t.L <= 4096)
+        k <= 64 && ms <= kSmallMaxStream && t.L <= 4096 && (!t.exact_scan || txh_exact_scan_fits(t)))
         p.pipeline = TxhPipeline::Small;
     // Fewer queries still, over a long stream: the wide pipeline (three launches, every stage spread over the chip).
     // Its scan rebuilds the tables per leaf inside a workgroup of 1024 stream positions: leaves of >= 512 points
@@ -1942,7 +1942,8 @@ int scann_hip_search_batched(scann_hip_index *ix, const float *queries, uint32_t
         SCANN_TRY(set_device(ix->ctx));
         const Knobs kn = read_knobs();
         const BfFilter flt = bf_filter_of(opts, kn);
-        if (kn.small && ix->bfx.rows && nq <= kSmallBatch && k <= 64)
+        // (past the pass kernels' dim the small pipeline is not taken either: the search below refuses at every nq)
+        if (kn.small && ix->bfx.rows && nq <= kSmallBatch && k <= 64 && bf_pass_fits(ix->bf))
             return bf_small_search_host(ix, sl, queries, nq, q_stride, k, kn, flt, out_idx, out_dist, out_count);
         if (sl.primary) ix->next_events();
         const bool shortlist = !flt.bitmap && !(opts && opts->bf_exact) && bf_shortlist_eligible(ix->bf, nq, k, kn);

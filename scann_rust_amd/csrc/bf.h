@@ -52,6 +52,10 @@ constexpr uint32_t kBfSampleRows = 8192;   // rows of the threshold sample (== L
 int bf_reserve(const BfIndexDev &ix, BfWorkspace &w, uint32_t max_nq, uint32_t max_k, bool filtered);
 
 const char *bf_pass_kernel_name(const BfIndexDev &ix, uint32_t nq);
+// true if the pass kernels accept this index's dim at EVERY batch size (the last resort's queries fit the LDS): a
+// caller with a path of its own for some batch sizes must not take it past this ceiling, or the dims it refuses
+// would depend on the batch size
+bool bf_pass_fits(const BfIndexDev &ix);
 
 // Host-pointer entry (copies in/out, synchronises).  shortlist: take the bf16-shortlist path first
 // (bf_shortlist_eligible), whose bound misses with probability `tail`; queries it cannot verify are repeated exactly.

@@ -601,12 +601,14 @@ __global__ __launch_bounds__(256, 2) void bf_mfma_dot_kernel(BfIndexDev ix, BfPa
 // One thread per row; centres are staged in LDS tiles and read as broadcasts.
 // =====================================================================================
 constexpr int kAsgTC = 16;   // centres per LDS tile
+constexpr int kAsgTCWide = 8;   // ... when 16 rows of dimp floats exceed the LDS (dim > 2560): reaches dim 5120
 constexpr int kAsgDJ = 32;   // row values held in registers at a time
 
+template <int TC>
 __global__ __launch_bounds__(256) void assign_nearest_kernel(BfIndexDev ix, const float *__restrict__ centers,
                                                              uint32_t k, uint32_t *__restrict__ out_idx,
                                                              float *__restrict__ out_dist) {
-    extern __shared__ __attribute__((aligned(16))) float cs[];   // [kAsgTC][dimp]
+    extern __shared__ __attribute__((aligned(16))) float cs[];   // [TC][dimp]
     const uint32_t dim = ix.dim, dimp = (dim + 3u) & ~3u;
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const bool act = i < ix.n;
@@ -614,15 +616,15 @@ __global__ __launch_bounds__(256) void assign_nearest_kernel(BfIndexDev ix, cons
     const bool vec = ((ix.stride & 3u) == 0) && ((reinterpret_cast<uintptr_t>(ix.rows) & 15u) == 0);
     float best = __builtin_inff();
     uint32_t bi = 0;
-    for (uint32_t c0 = 0; c0 < k; c0 += kAsgTC) {
-        for (uint32_t e = threadIdx.x; e < kAsgTC * dimp; e += blockDim.x) {
+    for (uint32_t c0 = 0; c0 < k; c0 += TC) {
+        for (uint32_t e = threadIdx.x; e < TC * dimp; e += blockDim.x) {
             const uint32_t c = e / dimp, j = e - c * dimp;
             cs[e] = (c0 + c < k && j < dim) ? centers[(size_t)(c0 + c) * dim + j] : 0.0f;
         }
         __syncthreads();
-        float acc[kAsgTC];
+        float acc[TC];
 #pragma unroll
-        for (int c = 0; c < kAsgTC; ++c) acc[c] = 0.0f;
+        for (int c = 0; c < TC; ++c) acc[c] = 0.0f;
         for (uint32_t j0 = 0; j0 < dim; j0 += kAsgDJ) {
             float x[kAsgDJ];
             if (vec && j0 + kAsgDJ <= dim) {
@@ -637,7 +639,7 @@ __global__ __launch_bounds__(256) void assign_nearest_kernel(BfIndexDev ix, cons
             }
             const uint32_t nj = min((uint32_t)kAsgDJ, dim - j0);
 #pragma unroll
-            for (int c = 0; c < kAsgTC; ++c) {
+            for (int c = 0; c < TC; ++c) {
                 const float *cr = cs + c * dimp + j0;
                 float a = acc[c];
                 if (nj == (uint32_t)kAsgDJ) {
@@ -658,7 +660,7 @@ __global__ __launch_bounds__(256) void assign_nearest_kernel(BfIndexDev ix, cons
             }
         }
 #pragma unroll
-        for (int c = 0; c < kAsgTC; ++c)
+        for (int c = 0; c < TC; ++c)
             if (c0 + c < k && acc[c] < best) {
                 best = acc[c];
                 bi = c0 + c;
@@ -669,6 +671,17 @@ __global__ __launch_bounds__(256) void assign_nearest_kernel(BfIndexDev ix, cons
         out_idx[i] = bi;
         if (out_dist) out_dist[i] = best;
     }
+}
+
+// The tile size a launch of assign_nearest_kernel takes: the tiles are walked in centre order and the minimum is
+// strict, so the result does not depend on it.
+template <typename... Args>
+static int launch_assign_nearest(uint32_t dim, dim3 grid, hipStream_t st, Args &&...args) {
+    const uint32_t dimp = (dim + 3u) & ~3u;
+    const int tc = (size_t)kAsgTC * dimp * sizeof(float) <= kMaxLdsBytes ? kAsgTC : kAsgTCWide;
+    return with_value<kAsgTC, kAsgTCWide>(tc, [&](auto t) {
+        return launch(assign_nearest_kernel<t()>, grid, dim3(256), (size_t)t() * dimp * sizeof(float), st, args...);
+    });
 }
 
 // The same assignment with squared_l2_avx2's summation order (simd/x86.rs:139-165), taken by
@@ -1657,10 +1670,18 @@ static bool vq_eligible(const BfIndexDev &ix, const BfPass &p) {
     return p.nq >= 128;
 }
 
-// streaming kernel: a few queries (at most 16, one database pass per 8), 16-byte-loadable rows
+// LDS of bf_stream_kernel: kStQT queries and the four waves' staging slices (the kernel has no static arrays)
+static size_t stream_lds_bytes(uint32_t dim) {
+    const uint32_t dimp = (dim + 3u) & ~3u;
+    return ((size_t)kStQT * dimp + 4u * 64u * kStLd) * sizeof(float);
+}
+
+// streaming kernel: a few queries (at most 16, one database pass per 8), 16-byte-loadable rows, and a dim whose
+// queries fit the LDS beside the staging slices (up to 3968; wider rows take bf_generic_kernel: the same arithmetic)
 static bool stream_eligible(const BfIndexDev &ix, const BfPass &p) {
     if (ix.measure > SCANN_HIP_DOT_PRODUCT) return false;   // L1 / Cosine: the pair-at-a-time kernel
     if ((ix.stride & 3u) || (reinterpret_cast<uintptr_t>(ix.rows) & 15u) || ix.dim < 8) return false;
+    if (stream_lds_bytes(ix.dim) > kMaxLdsBytes) return false;
     return p.nq <= 16;
 }
 
@@ -1678,7 +1699,8 @@ static int launch_quant(const BfIndexDev &ix, const BfPass &p, hipStream_t st) {
 // quantized rows: every pass (sample, filter, dense matrix, radius) on bf_quant_kernel; one query pair per
 // workgroup row for the one- and two-query searches, four pairs otherwise
 static int launch_quant_pass(const BfIndexDev &ix, const BfPass &p, hipStream_t st) {
-    const bool few = p.nq <= 2;
+    // (one pair too where four pairs of queries exceed the LDS, dim > 5120: the same arithmetic per pair of values)
+    const bool few = p.nq <= 2 || (size_t)ix.dim * 8 * sizeof(float) > kMaxLdsBytes;
     if (ix.fmt != SCANN_HIP_ROWS_BF16 && ix.fmt != SCANN_HIP_ROWS_FP8_E4M3 && ix.fmt != SCANN_HIP_ROWS_INT8)
         return fail(SCANN_HIP_INVALID_ARGUMENT, "unknown row format");
     return with_value<SCANN_HIP_ROWS_BF16, SCANN_HIP_ROWS_FP8_E4M3, SCANN_HIP_ROWS_INT8>(ix.fmt, [&](auto fmt) {
@@ -1697,12 +1719,21 @@ const char *bf_pass_kernel_name(const BfIndexDev &ix, uint32_t nq) {
     return "bf_generic_kernel";
 }
 
+// LDS of bf_generic_kernel, the pass every f32 search can end in (no static arrays)
+static size_t generic_lds_bytes(uint32_t dim) {
+    const uint32_t dimp = (dim + 3u) & ~3u;
+    return ((size_t)kBfGenQT * dimp + kBfGenQT) * sizeof(float);
+}
+
+bool bf_pass_fits(const BfIndexDev &ix) {
+    return ix.fmt ? (size_t)ix.dim * 2 * sizeof(float) <= kMaxLdsBytes : generic_lds_bytes(ix.dim) <= kMaxLdsBytes;
+}
+
 static int launch_pass(const BfIndexDev &ix, const BfPass &p, hipStream_t st) {
     if (p.nq == 0 || p.nrows == 0) return SCANN_HIP_OK;
     if (ix.fmt) return launch_quant_pass(ix, p, st);
     if (stream_eligible(ix, p)) {
-        const uint32_t dimp = (ix.dim + 3u) & ~3u;
-        const size_t lds = ((size_t)kStQT * dimp + 4u * 64u * kStLd) * sizeof(float);
+        const size_t lds = stream_lds_bytes(ix.dim);
         const uint32_t ny = ceil_div_u32(p.nq, kStQT);
         const uint32_t ngroups = ceil_div_u32(p.nrows, 64);
         const uint32_t nx = std::max(1u, std::min(ceil_div_u32(ngroups, 4), 4u * (uint32_t)num_cus()));
@@ -1722,8 +1753,7 @@ static int launch_pass(const BfIndexDev &ix, const BfPass &p, hipStream_t st) {
             });
         });
     }
-    const uint32_t dimp = (ix.dim + 3u) & ~3u;
-    const size_t lds = ((size_t)kBfGenQT * dimp + kBfGenQT) * sizeof(float);
+    const size_t lds = generic_lds_bytes(ix.dim);
     dim3 grid(ceil_div_u32(p.nrows, 256), ceil_div_u32(p.nq, kBfGenQT));
     return with_measure(ix.measure, [&](auto m) {
         return launch(bf_generic_kernel<m()>, grid, dim3(256), lds, st, ix, p);
@@ -2300,10 +2330,8 @@ int bf_search_radius_host(const BfIndexDev &ix, BfWorkspace &w, const float *que
 int bf_assign_nearest_device(const BfIndexDev &ix, const float *d_centers, uint32_t k, uint32_t *d_out_idx,
                              float *d_out_dist, hipStream_t st) {
     if (ix.n == 0) return SCANN_HIP_OK;
-    const uint32_t dimp = (ix.dim + 3u) & ~3u;
-    const size_t lds = (size_t)kAsgTC * dimp * sizeof(float);
-    return launch(assign_nearest_kernel, dim3((uint32_t)ceil_div_u64(ix.n, 256)), dim3(256), lds, st, ix, d_centers, k,
-                  d_out_idx, d_out_dist);
+    return launch_assign_nearest(ix.dim, dim3((uint32_t)ceil_div_u64(ix.n, 256)), st, ix, d_centers, k, d_out_idx,
+                                 d_out_dist);
 }
 
 int bf_assign_nearest_host(const BfIndexDev &ix, const float *centers, uint32_t k, uint32_t *out_idx,
@@ -2610,8 +2638,7 @@ static int km_launch_assign(const BfIndexDev &v, const float *d_centers, uint32_
         const size_t lds = (size_t)kAvxTC * dimp * sizeof(float);
         SCANN_TRY(launch(assign_nearest_avx_kernel, grid, dim3(256), lds, st, v, d_centers, k, d_assign, d_dist));
     } else {
-        const size_t lds = (size_t)kAsgTC * dimp * sizeof(float);
-        SCANN_TRY(launch(assign_nearest_kernel, grid, dim3(256), lds, st, v, d_centers, k, d_assign, d_dist));
+        SCANN_TRY(launch_assign_nearest(v.dim, grid, st, v, d_centers, k, d_assign, d_dist));
     }
     return SCANN_HIP_OK;
 }

@@ -48,12 +48,16 @@ inline int static_lds_bytes(const void *kernel, size_t *out) {
     return SCANN_HIP_OK;
 }
 
+// LDS of one CU.  A launcher that has a choice (a smaller tile, another kernel) sizes it against this, so that the
+// dims an entry point refuses do not depend on the batch size (DESIGN.md "Dimensionality ceilings").
+constexpr size_t kMaxLdsBytes = 160 * 1024;
+
 // The dynamic-LDS attribute of a launch that asks for `bytes`.  Nothing is set at 64 KB or below.  Above, it is one
 // constant per kernel (the CU's 160 KB less the kernel's static arrays: the attribute bounds the DYNAMIC part, and
 // static + dynamic may not exceed the CU's LDS), never the launch's own size: threads searching different indexes
 // set this attribute concurrently, and a smaller value written by one of them must not undercut another's launch.
 inline int set_dyn_lds(const void *kernel, size_t bytes) {
-    constexpr size_t kMaxLds = 160 * 1024;
+    constexpr size_t kMaxLds = kMaxLdsBytes;
     if (bytes <= 64 * 1024) return SCANN_HIP_OK;
     size_t static_bytes = 0;
     if (bytes <= kMaxLds) SCANN_TRY(static_lds_bytes(kernel, &static_bytes));

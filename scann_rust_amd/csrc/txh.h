@@ -242,6 +242,10 @@ static inline bool txh_scan_is_mfma(TxhScan s) { return s == TxhScan::Mfma32 || 
 int txh_launch_search(const TxhIndexDev &ix, const TxhWork &w, bool local_only,
                       hipStream_t stream, hipEvent_t ev_scan_begin, hipEvent_t ev_scan_end);
 
+// false where the batched exact leaf scan (Partitioned mode) refuses this dim for want of LDS: the small-batch
+// pipeline is then not planned either, so that the dims a search refuses do not depend on the batch size
+bool txh_exact_scan_fits(const TxhIndexDev &ix);
+
 int txh_launch_partition_only(const TxhIndexDev &ix, const TxhWork &w, hipStream_t stream);
 
 int txh_launch_merge(uint32_t world, uint32_t nq, uint32_t m_local, uint32_t m, uint32_t k,

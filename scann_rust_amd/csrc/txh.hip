@@ -2995,6 +2995,20 @@ static int launch_sample_mfma_bound(const TxhIndexDev &ix, const TxhWork &w, hip
     });
 }
 
+static size_t exact_scan_lds_bytes(uint32_t dim) {
+    return (size_t)exact_quads_per_tile(dim) * 4 * ((dim + 3u) & ~3u) * sizeof(float);
+}
+
+// set_dyn_lds' own decision for launch_exact_scan: the dynamic request plus the kernel's static arrays, asked of the
+// code object (a failed query counts as "does not fit": the batched launch then reports it)
+bool txh_exact_scan_fits(const TxhIndexDev &ix) {
+    size_t static_bytes = 0;
+    const int s = with_measure(ix.measure, [&](auto m) {
+        return static_lds_bytes(reinterpret_cast<const void *>(leaf_exact_scan_kernel<m()>), &static_bytes);
+    });
+    return s == SCANN_HIP_OK && exact_scan_lds_bytes(ix.dim) + static_bytes <= kMaxLdsBytes;
+}
+
 // SearchMode::Partitioned: dense key lists (no threshold), one exact-distance tile kernel.
 static int launch_exact_scan(const TxhIndexDev &ix, const TxhWork &w, hipStream_t st, hipEvent_t ev0,
                              hipEvent_t ev1) {
@@ -3006,7 +3020,7 @@ static int launch_exact_scan(const TxhIndexDev &ix, const TxhWork &w, hipStream_
     a.pair_off = w.pair_off; a.tile_off = w.tile_off; a.pair_q = w.pair_q; a.pair_vbase = w.pair_vbase;
     a.counters = w.counters; a.queries = w.queries; a.q_stride = w.q_stride; a.cand = w.cand; a.cap = w.cap;
     a.qpt = exact_quads_per_tile(ix.dim);
-    const size_t lds = (size_t)a.qpt * 4 * ((ix.dim + 3u) & ~3u) * sizeof(float);
+    const size_t lds = exact_scan_lds_bytes(ix.dim);
     if (ev0) SCANN_HIP_CHECK(hipEventRecord(ev0, st));
     const dim3 grid((uint32_t)cus * 8u), block(256);
     SCANN_TRY(with_measure(ix.measure, [&](auto m) {

@@ -352,9 +352,11 @@ int launch_ah_tokens(const TxhIndexDev &ix, const TxhWork &w, hipStream_t st) {
 
 int launch_centroid_scores(const TxhIndexDev &ix, const TxhWork &w, hipStream_t st) {
     // queries per single-wave block: fewer when the grid would not fill the chip (one thread per
-    // centroid, so a block's work is 64 centroids x QT queries)
+    // centroid, so a block's work is 64 centroids x QT queries), and 4 where 16 queries exceed the LDS (dim > 2560):
+    // the per-pair arithmetic is the same, so a dim that one batch size accepts every batch size accepts
     const uint64_t waves16 = (uint64_t)ceil_div_u32(ix.L, 64) * ceil_div_u32(w.nq, 16);
-    return with_value<16, 4>(waves16 >= 8192 ? 16 : 4, [&](auto qt) {
+    const bool fits16 = (size_t)16 * ix.dim * sizeof(float) <= kMaxLdsBytes;
+    return with_value<16, 4>(waves16 >= 8192 && fits16 ? 16 : 4, [&](auto qt) {
         const size_t lds1 = (size_t)qt() * ix.dim * sizeof(float);
         return launch(centroid_scores_kernel<qt()>, dim3(ceil_div_u32(ix.L, 64), ceil_div_u32(w.nq, qt())), dim3(64), lds1,
                       st, ix.centers, ix.L, ix.dim, w.queries, w.nq, w.q_stride, w.cdist);

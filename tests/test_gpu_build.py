@@ -437,10 +437,11 @@ def test_build_chain_matches_oracle_step_by_step():
 
 # ---- the LDS limit --------------------------------------------------------------------------------------------------
 def test_assign_nearest_lds_limit():
-    """16 centres x ceil(dim / 4) x 16 B of LDS: 160 KB at dim 2560; above it ResourceExhausted, no launch error"""
+    """16 centres x ceil(dim / 4) x 16 B of LDS: 160 KB at dim 2560; above it 8 centres per tile, 160 KB at dim 5120;
+    above that ResourceExhausted, no launch error"""
     n, k = 64, 3
     rng = np.random.default_rng(550)
-    for dim, ok in ((2560, True), (2564, False)):
+    for dim, ok in ((2560, True), (2564, True), (5120, True), (5124, False)):
         rows = rng.uniform(-1, 1, (n, dim)).astype(np.float32)
         centers = rng.uniform(-1, 1, (k, dim)).astype(np.float32)
         index, _, _ = bf_index(rows)
@@ -455,7 +456,7 @@ def test_assign_nearest_lds_limit():
 
 
 def test_kmeans_lds_limit():
-    """the AVX2-order kernel stages 8 centres: 160 KB at sub_dim 5120 (the sequential one at 2560)"""
+    """the AVX2-order kernel stages 8 centres: 160 KB at sub_dim 5120; the sequential one 16 up to 2560 and 8 above"""
     n, k = 64, 3
     rng = np.random.default_rng(551)
     rows = rng.uniform(-1, 1, (n, 5128)).astype(np.float32)
@@ -463,7 +464,11 @@ def test_kmeans_lds_limit():
     check_lloyd(index, data, n, st, seeds_of(rows[:, :5120], k, 13), thr=AVX, max_iterations=2, what="avx 5120")
     check_lloyd(index, data, n, st, seeds_of(rows[:, 8:2568], k, 13), col=8, thr=SEQ, max_iterations=2,
                 what="seq 2560")
-    for sub, thr in ((5128, AVX), (2564, SEQ)):
+    check_lloyd(index, data, n, st, seeds_of(rows[:, 4:2568], k, 13), col=4, thr=SEQ, max_iterations=2,
+                what="seq 2564")
+    check_lloyd(index, data, n, st, seeds_of(rows[:, 8:5128], k, 13), col=8, thr=SEQ, max_iterations=2,
+                what="seq 5120")
+    for sub, thr in ((5128, AVX), (5124, SEQ)):
         with pytest.raises(hip.ScannError) as e:
             hip.kmeans_lloyd(index, seeds_of(rows[:, :sub], k, 13), max_iterations=2, simd_threshold=thr)
         assert e.value.code == hip.RESOURCE_EXHAUSTED, e.value
