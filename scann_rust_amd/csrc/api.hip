@@ -1393,6 +1393,7 @@ static int plan_txh_search(const scann_hip_index *ix, uint32_t k, const scann_hi
     p.sample_mfma = kn.sample_mfma && p.thr_tail && p.thr_ties && txh_scan_is_mfma(p.scan) && t.ah_mode && t.L == 1 &&
                     P == 1 && t.code_bits == 4;
     p.select_direct = kn.select_direct;
+    p.select_regs = kn.select_regs;
     // int8 re-rank filter: lists of a few hundred candidates and more
     p.use_i8 = t.rows8 && exact_reorder && m >= kn.rerank_i8_min && m > 4 * k;
     p.i8_expand = kn.rerank_expand;

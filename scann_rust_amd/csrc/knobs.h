@@ -35,6 +35,8 @@
 //                                   (default: integer-MFMA sample, exact re-score of its low tail)
 // SCANN_HIP_FUSED                   0: small batches always as three launches                      every call
 // SCANN_HIP_SELECT_DIRECT           0: stage long candidate lists in LDS for the unsorted select   every call
+// SCANN_HIP_SELECT_REGS             0: that select sweeps its list four times from global memory   every call
+//                                   (default: one read, the list ranked in registers)
 // SCANN_HIP_LOCAL_PRUNE             0: multi-GPU local stage re-ranks every candidate exactly      every call
 // SCANN_HIP_COMM_FILL               multi-GPU: room in a destination block, multiple of the even   every call
 //                                   share (2.5; 0 = worst case)
@@ -82,6 +84,7 @@ struct Knobs {
     bool sample_mfma = true;
     bool fused = true;
     bool select_direct = true;
+    bool select_regs = true;
     bool local_prune = true;
     double comm_fill = 2.5;
     double bf_shortlist_tail = 1e-6;
@@ -133,6 +136,7 @@ inline Knobs read_knobs() {
         else if (is("SCANN_HIP_SAMPLE_MFMA")) k.sample_mfma = atoi(v) != 0;
         else if (is("SCANN_HIP_FUSED")) k.fused = atoi(v) != 0;
         else if (is("SCANN_HIP_SELECT_DIRECT")) k.select_direct = atoi(v) != 0;
+        else if (is("SCANN_HIP_SELECT_REGS")) k.select_regs = atoi(v) != 0;
         else if (is("SCANN_HIP_LOCAL_PRUNE")) k.local_prune = atoi(v) != 0;
         else if (is("SCANN_HIP_COMM_FILL")) {
             const double f = atof(v);

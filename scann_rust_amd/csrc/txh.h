@@ -171,6 +171,7 @@ struct TxhPlan {
     uint32_t small_max_leaf;   // longest local leaf (grid of the three-launch small scan)
     uint32_t wide_cap2;        // wide pipeline: entries per query of the compact candidate arrays
     bool select_direct;        // the unsorted select of a long list may read it straight from global memory
+    bool select_regs;          // ... and ranks it in registers after one read (select_regs_kernel)
     bool use_i8;               // int8 row filter in front of the exact re-rank (needs ix.rows8)
     bool i8_expand;            // its brackets by the expanded square, one epilogue per wave (else per dimension, per round)
     bool local_prune;          // local stage of a sharded search: the filter's prefix form (+inf for hopeless candidates)

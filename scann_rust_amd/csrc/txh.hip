@@ -29,12 +29,13 @@ namespace scann {
 // centroid_scores_kernel's arithmetic (sequential scalar sum of (q_j - c_j)^2, no FMA), instead of reading
 // a matrix another launch produced.
 // Bin of 1-based rank `rank` in a complete histogram of `bins` bins (1024 or 4096) in LDS (counts synchronised by the caller; the
-// histogram holds >= rank entries); s_w[49] = the rank inside that bin.  Every thread of a kSelectThreads block calls; two
+// histogram holds >= rank entries); s_w[49] = the rank inside that bin.  Every thread of an NT-thread block calls; two
 // barriers; s_w: LDS u32[>= 50].
+template <uint32_t NT = kSelectThreads>
 __device__ __forceinline__ uint32_t block_hist_rank_bin(const uint32_t *s_hist, uint32_t *s_w, uint32_t rank,
                                                         uint32_t bins = kSelBinsMax) {
     const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
-    const uint32_t per = bins / kSelectThreads;   // bins per thread (1 or 4)
+    const uint32_t per = bins / NT;   // bins per thread (1 or 4; 8 with 512 threads)
     uint32_t mine = 0;
     for (uint32_t j = 0; j < per; ++j) mine += s_hist[tid * per + j];
     uint32_t incl = mine;
@@ -1827,6 +1828,193 @@ __global__ __launch_bounds__(kSelectThreads) void select_rerank_kernel(TxhIndexD
 }
 
 // =====================================================================================
+// K7r: the unsorted select of a long list (SelectArgs::direct) with the list in registers.  select_rerank_kernel
+// sweeps the query's list four times from global memory (min / max, histogram, the rank's bin, keep and decode),
+// 16-25 dependent trips per thread each; here every thread loads its VPT keys once, all loads in flight, and
+// block_select's scheme runs on that copy as in wide_final_kernel: histogram over [min, max], the bin of rank m,
+// its members ranked exactly by counting; a crowded bin becomes the new range and the round repeats on the
+// registers.  The keys are unique, so T (the m-th smallest) is the value block_select returns and exactly m keys
+// are <= T.  Same checks, same status codes, same outputs as the unsorted branch above, except cand_dist: only a
+// caller that asks for stage outputs reads it, and that forces the sorted path (need_sorted_cands).
+// Launched when cap <= VPT * kSelRegThreads (launch_select).
+// =====================================================================================
+// 512 threads: 16 / 26 / 36 keys each, 86 / 103 / 124 VGPRs, two workgroups per CU (1024 threads x 8 / 13 / 18 keys
+// measured slower: 80 VGPRs at 13 keys leave room for one 16-wave workgroup per CU)
+constexpr uint32_t kSelRegThreads = 512;
+constexpr uint32_t kSelRegCaps[3] = {8192, 13312, 18432};   // list capacities of the three instantiations
+
+template <int VPT>
+__global__ __launch_bounds__(kSelRegThreads) void select_regs_kernel(TxhIndexDev ix, SelectArgs a) {
+    __shared__ uint32_t s_hist[kSelBinsMax];
+    __shared__ uint64_t s_slist[kSelListMax], s_mm[2 * (kSelRegThreads / 64)], s_T;
+    __shared__ uint32_t s_dvb[kDecodeStage], s_drow[kDecodeStage], s_w[50], s_cn, s_pre[VPT * (kSelRegThreads / 64)];
+    constexpr uint32_t nt = kSelRegThreads;
+    const uint32_t q = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
+    const uint32_t m = a.m;
+
+    const uint32_t cnt = a.cand_cnt[q];
+    if (cnt > a.cap) {  // candidate buffer overflow: report, never return a wrong row
+        select_fail(a, q, (uint32_t)SCANN_HIP_RESOURCE_EXHAUSTED);
+        return;
+    }
+    if (a.thr[q] != SCANN_KEY_MAX && cnt < m) {   // a statistical bound that was too tight (see select_rerank_kernel)
+        select_fail(a, q, (uint32_t)SCANN_HIP_ABORTED);
+        return;
+    }
+    // key e * nt + tid of the list lives in this lane's registers (cnt <= cap <= VPT * nt); padding sorts last
+    const uint64_t *list = a.cand + (size_t)q * a.cap;
+    uint64_t kk[VPT];
+#pragma unroll
+    for (int e = 0; e < VPT; ++e) {
+        const uint32_t i = (uint32_t)e * nt + tid;
+        kk[e] = i < cnt ? list[i] : SCANN_KEY_MAX;
+    }
+    const uint32_t *vb = a.vbase + (size_t)q * (a.P + 1);
+    const bool staged = a.P <= kDecodeStage;
+    if (staged) {
+        for (uint32_t r = tid; r < a.P; r += nt) {
+            s_dvb[r] = vb[r];
+            s_drow[r] = ix.leaf_off[a.tokens[(size_t)q * a.P + r]];
+        }
+    }
+    auto clear = [&]() {
+        for (uint32_t i = tid; i < kSelBinsMax; i += nt) s_hist[i] = 0;
+        if (tid == 0) s_cn = 0;
+    };
+    clear();
+
+    uint64_t T = SCANN_KEY_MAX;   // cnt <= m: everything stays
+    if (cnt > m) {                // block-uniform
+        uint64_t vmin = SCANN_KEY_MAX, vmax = 0;
+#pragma unroll
+        for (int e = 0; e < VPT; ++e)
+            if (kk[e] != SCANN_KEY_MAX) {
+                vmin = kk[e] < vmin ? kk[e] : vmin;
+                vmax = kk[e] > vmax ? kk[e] : vmax;
+            }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const uint64_t x = shfl_xor_t<uint64_t>(vmin, o), y = shfl_xor_t<uint64_t>(vmax, o);
+            vmin = x < vmin ? x : vmin;
+            vmax = y > vmax ? y : vmax;
+        }
+        if (lane == 0) {
+            s_mm[wave] = vmin;
+            s_mm[nt / 64 + wave] = vmax;
+        }
+        __syncthreads();
+        for (uint32_t w2 = 0; w2 < nt / 64; ++w2) {
+            vmin = s_mm[w2] < vmin ? s_mm[w2] : vmin;
+            vmax = s_mm[nt / 64 + w2] > vmax ? s_mm[nt / 64 + w2] : vmax;
+        }
+        uint32_t rank = m;
+        for (;;) {
+            uint32_t sh = 0;
+            while (((vmax - vmin) >> sh) >= (uint64_t)kSelBinsMax) ++sh;
+#pragma unroll
+            for (int e = 0; e < VPT; ++e)
+                if (kk[e] >= vmin && kk[e] <= vmax) atomicAdd(&s_hist[(uint32_t)((kk[e] - vmin) >> sh)], 1u);
+            __syncthreads();
+            const uint32_t bin = block_hist_rank_bin<nt>(s_hist, s_w, rank);
+            const uint32_t rk = s_w[49], pop = s_hist[bin];
+            const uint64_t lo = vmin + ((uint64_t)bin << sh);
+            uint64_t hi = lo + (((uint64_t)1 << sh) - 1);
+            if (hi > vmax || hi < lo) hi = vmax;
+            if (sh == 0) {
+                T = lo;
+                break;
+            }
+            if (pop <= kSelListMax) {
+#pragma unroll
+                for (int e = 0; e < VPT; ++e)
+                    if (kk[e] >= lo && kk[e] <= hi) s_slist[atomicAdd(&s_cn, 1u)] = kk[e];
+                __syncthreads();
+                for (uint32_t i = tid; i < pop; i += nt) {
+                    const uint64_t v = s_slist[i];
+                    uint32_t r = 0;
+                    for (uint32_t j2 = 0; j2 < pop; ++j2) r += s_slist[j2] < v ? 1u : 0u;   // (keys are unique)
+                    if (r + 1 == rk) s_T = v;
+                }
+                __syncthreads();
+                T = s_T;
+                break;
+            }
+            // a crowded bin (tie-heavy distances) is the new range
+            vmin = lo;
+            vmax = hi;
+            rank = rk;
+            __syncthreads();   // everyone has read the bin's count and rank
+            clear();
+            __syncthreads();
+        }
+    }
+
+    auto decode = [&](uint64_t key, uint32_t i) {   // select_rerank_kernel's, without cand_dist
+        const uint32_t vpos = (uint32_t)key;
+        uint32_t lo = 0, hi = a.P;
+        uint32_t csr;
+        if (staged) {
+            while (hi - lo > 1) {
+                uint32_t mid = (lo + hi) >> 1;
+                if (s_dvb[mid] <= vpos) lo = mid; else hi = mid;
+            }
+            csr = s_drow[lo] + (vpos - s_dvb[lo]);
+        } else {
+            while (hi - lo > 1) {
+                uint32_t mid = (lo + hi) >> 1;
+                if (vb[mid] <= vpos) lo = mid; else hi = mid;
+            }
+            csr = ix.leaf_off[a.tokens[(size_t)q * a.P + lo]] + (vpos - vb[lo]);
+        }
+        const uint32_t idx = ix.leaf_ids ? ix.leaf_ids[csr] : csr;
+        a.cand_row[(size_t)q * m + i] = ix.rows_csr ? csr : idx;
+        a.cand_key[(size_t)q * m + i] = key;
+        a.cand_idx[(size_t)q * m + i] = idx;
+    };
+    // keep key <= T, in LIST order: the survivors' order follows the scan's, and the int8 bracket pass behind this
+    // kernel gathers its rows in candidate order -- it takes 1.7 % longer behind slots handed out wave by wave.  The
+    // kept keys of every 64-key run (e, wave) are counted by ballot, one wave scans the counts, no atomics
+    constexpr uint32_t runs = (uint32_t)VPT * (nt / 64), per = (runs + 63u) / 64u;
+    {
+#pragma unroll
+        for (int e = 0; e < VPT; ++e) {
+            const unsigned long long kept = __ballot((uint32_t)e * nt + tid < cnt && kk[e] <= T);
+            if (lane == 0) s_pre[(uint32_t)e * (nt / 64) + wave] = (uint32_t)__popcll(kept);
+        }
+        __syncthreads();
+        if (wave == 0) {   // exclusive prefix over the runs, `per` consecutive runs a lane
+            uint32_t c[per], mine = 0;
+#pragma unroll
+            for (uint32_t j = 0; j < per; ++j) {
+                c[j] = lane * per + j < runs ? s_pre[lane * per + j] : 0u;
+                mine += c[j];
+            }
+            uint32_t incl = mine;
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const uint32_t up = (uint32_t)__shfl_up((int)incl, o);
+                if ((int)lane >= o) incl += up;
+            }
+            uint32_t excl = incl - mine;
+#pragma unroll
+            for (uint32_t j = 0; j < per; ++j) {
+                if (lane * per + j < runs) s_pre[lane * per + j] = excl;
+                excl += c[j];
+            }
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int e = 0; e < VPT; ++e) {
+        const bool keep = (uint32_t)e * nt + tid < cnt && kk[e] <= T;
+        uint32_t etot;
+        const uint32_t slot = s_pre[(uint32_t)e * (nt / 64) + wave] + wave_prefix_count(keep, &etot);
+        if (keep && slot < m) decode(kk[e], slot);   // (exactly min(m, cnt) are kept: the row has m slots)
+    }
+    if (tid == 0) a.cand_count[q] = min(m, cnt);
+}
+
+// =====================================================================================
 // K8: exact re-rank.  tree_x_hybrid/mod.rs:350-358 -> squared_l2_avx2
 // (simd/x86.rs:139-165): 8 lanes per candidate are the 8 AVX2 FMA lane chains (chunk
 // order), combined by the fixed hsum tree (x86.rs:31-44) with DPP shuffles, plus the
@@ -3058,6 +3246,20 @@ static int launch_select(const TxhIndexDev &ix, const TxhWork &w, bool local_onl
     const bool direct = unsorted && w.select_direct && lds_keys > 4096u;
     s.direct = direct ? 1u : 0u;
     s.sel_n = w.cap;
+    if (direct && w.select_regs) {
+        // the list in registers (K7r): the instantiations cover plan_txh_search's capacities, (J + 8 sqrt(J) + 16) st
+        // + 256 -- 12 770 at 1M points and m = 5000, ~17 500 at m = 8192; a longer list takes the kernel below
+        void (*regs)(TxhIndexDev, SelectArgs) =
+            w.cap <= kSelRegCaps[0]   ? select_regs_kernel<kSelRegCaps[0] / kSelRegThreads>
+            : w.cap <= kSelRegCaps[1] ? select_regs_kernel<kSelRegCaps[1] / kSelRegThreads>
+            : w.cap <= kSelRegCaps[2] ? select_regs_kernel<kSelRegCaps[2] / kSelRegThreads>
+                                      : nullptr;
+        if (regs) {
+            s.lds_keys = 0;
+            SCANN_TRY(launch(regs, dim3(w.nq), dim3(kSelRegThreads), 0, st, ix, s));
+            return SCANN_HIP_OK;
+        }
+    }
     if (direct) lds_keys = 64;
     s.lds_keys = lds_keys;
     const SelCfg scfg = sel_cfg(direct ? w.cap : lds_keys);
