@@ -78,15 +78,18 @@ def recall_at_k(retrieved, gt, k):
     return tot / len(retrieved)
 
 
-def check_txh_query(oix, query, k, got_idx, got_dist, got_tok, got_tokd, got_ci, got_cd, what=""):
+def check_txh_query(oix, query, k, got_idx, got_dist, got_tok, got_tokd, got_ci, got_cd, what="", oracle=None):
     """Stage-aware parity check of one Tree-X-Hybrid query against the oracle.
 
     tokens / centre distances: bit-exact.  Candidates: the sorted approximate distances
     must be bitwise identical; memberships may differ only inside ties of the approximate
     distance (FastTopNeighbors' slot-order tie behaviour is not reproduced: SURVEY 8c "up
     to distance ties").  Final rows: equal to the oracle's if the candidate sets agree,
-    otherwise equal to the oracle's exact re-rank OF THE GPU's candidate list."""
-    oi, od, otok, otokd, oci, ocd = orc.txh_search(oix, query, k, stages=True)
+    otherwise equal to the oracle's exact re-rank OF THE GPU's candidate list.  `oracle`: the staged oracle outputs of
+    this query (orc.txh_search(oix, query, k, stages=True)), where the caller keeps them.  They are trusted: the caller
+    must have computed them for this very query, k, oix.allow and oix.pre_reorder_multiplier -- a stale tuple is
+    compared against without any error."""
+    oi, od, otok, otokd, oci, ocd = oracle if oracle is not None else orc.txh_search(oix, query, k, stages=True)
     P = otok.size
     assert np.array_equal(got_tok[:P], otok), "%s tokens" % what
     assert np.array_equal(np.asarray(got_tokd[:P], np.float32).view(np.uint32), otokd.view(np.uint32))
@@ -373,17 +376,22 @@ def txh_from_codes(rows, codebook, codes, L, P, mult, seed, use_residuals=True, 
     return oix, kw
 
 
-def check_ah_query(codebook, codes, data, stride, dim, query, k, m, got_idx, got_dist, got_ci, got_cd, what=""):
+def check_ah_query(codebook, codes, data, stride, dim, query, k, m, got_idx, got_dist, got_ci, got_cd, what="",
+                   oracle=None):
     """Stage-aware parity check of one AsymmetricHasher::search_with_reordering query (as check_txh_query): the sorted
     approximate candidate distances bitwise equal to the oracle's, memberships equal up to their ties; final rows
-    equal to the oracle's if the candidate sets agree, else to the oracle's re-rank of the GPU's candidate list."""
-    oci, ocd = orc.ah_search(codebook, codes, query, m)
+    equal to the oracle's if the candidate sets agree, else to the oracle's re-rank of the GPU's candidate list.
+    `oracle`: (candidate idx, candidate dist, final idx, final dist) of this query from orc.ah_search and
+    orc.ah_search_with_reordering, where the caller keeps them.  They are trusted: the caller must have computed them
+    for this very codebook, codes, data, query, k and m -- a stale tuple is compared against without any error."""
+    oci, ocd = oracle[:2] if oracle is not None else orc.ah_search(codebook, codes, query, m)
     assert got_ci.size == oci.size, "%s candidate count %d vs %d" % (what, got_ci.size, oci.size)
     assert np.array_equal(np.asarray(got_cd, np.float32).view(np.uint32), ocd.view(np.uint32)), \
         "%s approximate distances differ" % what
     assert_topk_equal_up_to_ties(got_ci, got_cd, oci, ocd, what=what + " cand")
     if sorted(got_ci.tolist()) == sorted(oci.tolist()):
-        oi, od = orc.ah_search_with_reordering(codebook, codes, data, stride, query, k, m)
+        oi, od = oracle[2:] if oracle is not None else \
+            orc.ah_search_with_reordering(codebook, codes, data, stride, query, k, m)
     else:
         oi, od = orc.reorder(data, stride, dim, query, got_ci, k)
     assert got_idx.size == oi.size, "%s final count %d vs %d" % (what, got_idx.size, oi.size)
