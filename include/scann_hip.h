@@ -311,6 +311,78 @@ int scann_hip_txh_create(scann_hip_ctx *ctx, const scann_hip_txh_desc *desc,
 int scann_hip_txh_create_quantized(scann_hip_ctx *ctx, const scann_hip_txh_desc *desc, const void *rows,
                                    int row_format, float inv_multiplier, scann_hip_index **out_index);
 
+/* ---- projections (src/projection/: PcaProjection, RandomOrthogonalProjection, GaussianRandomProjection,
+ * OpqProjection, TruncateProjection) ------------------------------------------------------------------------------
+ * Every dense projection of the reference is one loop (pca.rs:156-180, random.rs:82-92, 157-167, opq.rs:179-194):
+ *     out[j] = 0.0f;  for i in 0..in_dim (ascending):  out[j] += (in[i] - mean[i]) * M[(i, j)]
+ * an f32 sum, a multiply and then an add per step (no FMA), the subtraction PCA's alone.  The device computes exactly
+ * that chain for every output: a projected row equals the reference's bit for bit, subnormals kept,
+ * NaN and infinities propagated as the chain propagates them.  TRUNCATE (and an untrained PcaProjection) copies the
+ * window in[start .. start + out_dim).
+ * `matrix` is [out_dim][in_dim]: column j of the reference's column-major DMatrix is row j here.  `mean` is [in_dim].
+ * The object copies its arrays at create and is immutable afterwards; project calls on one object may run
+ * concurrently.  The trained matrix is an input (the reference's eigen-solver and RNG are not reproducible here:
+ * SURVEY F2, F4, F10), as centres and codebooks are. */
+typedef struct scann_hip_projection scann_hip_projection;
+#define SCANN_HIP_PROJ_MATRIX   1   /* random orthogonal / gaussian / OPQ rotation: no mean */
+#define SCANN_HIP_PROJ_PCA      2   /* matrix + mean */
+#define SCANN_HIP_PROJ_TRUNCATE 3   /* out = in[start .. start + out_dim) */
+/* Errors (InvalidArgument): unknown kind; in_dim == 0 or out_dim == 0; matrix == NULL (MATRIX, PCA); mean == NULL
+ * (PCA); TRUNCATE with start + out_dim > in_dim.  `start` is read for TRUNCATE only, matrix / mean are not. */
+int scann_hip_projection_create(scann_hip_ctx *ctx, int kind, uint32_t in_dim, uint32_t out_dim, const float *matrix,
+                                const float *mean, uint32_t start, scann_hip_projection **out_projection);
+void scann_hip_projection_destroy(scann_hip_projection *projection);
+/* out4 = kind, in_dim, out_dim, start */
+int scann_hip_projection_info(const scann_hip_projection *projection, uint32_t *out4);
+/* n rows of row_dim floats, row_stride apart -> n rows of out_dim floats, out_stride apart; host pointers.  Elements of
+ * `out` between out_dim and out_stride are not written.  Errors (InvalidArgument): row_dim != in_dim, row_stride <
+ * row_dim, out_stride < out_dim, NULL rows / out with n > 0. */
+int scann_hip_project(const scann_hip_projection *projection, const float *rows, uint64_t n, uint32_t row_stride,
+                      uint32_t row_dim, float *out, uint32_t out_stride);
+/* The same on device pointers: one kernel enqueued on hip_stream, no synchronisation, no allocation.  The rows are
+ * in_dim wide.  Errors: as above. */
+int scann_hip_project_device(const scann_hip_projection *projection, const float *d_rows, uint64_t n, uint32_t row_stride,
+                             float *d_out, uint32_t out_stride, void *hip_stream);
+
+/* A Tree-X-Hybrid / AsymmetricHasher index that partitions, hashes and scans in a PROJECTED space and re-ranks against
+ * the original rows.  desc->data must be NULL.  `desc` describes the index in the projected space: desc->dim ==
+ * projection.out_dim, centres [L][out_dim], codebook S * dsub == out_dim, codes as always (desc->stride is not read).
+ * `rows` holds n_rows (desc->n_rows is not read) original f32 rows of row_dim == projection.in_dim floats, row_stride
+ * apart, indexed by datapoint (AsymmetricHasher mode: datapoint = CSR order) and validated against leaf_ids as desc->data
+ * is; NULL = no exact re-ordering (build_no_store).  The handle
+ * copies the projection to the device: the caller may destroy `projection` afterwards.
+ * A search takes queries of row_dim floats (the q_dim check compares against row_dim, and
+ * scann_hip_index_dimensionality reports it):
+ *   1. qp = project(q) on the device, at the head of the call's stream, into a workspace buffer [nq][out_dim] (reserved
+ *      with the others by scann_hip_index_reserve; one per stream on the _device entry points);
+ *   2. every stage up to the merged candidate list is that of a scann_hip_txh_create handle of dim out_dim given qp,
+ *      bit for bit;
+ *   3. the re-rank scores the original q against the original rows with desc->distance_measure: exact distance, stable
+ *      sort in merged order, truncate to k -- today's rule;
+ *   4. exact_reorder = 0 returns the approximate distances of step 2 and reads no rows.
+ * Every batch size takes the batched pipeline (the few-query pipelines re-rank inside kernels that read one query
+ * space); the handle builds no 8-bit shadow store, so the re-rank row filter is off (it changes no result).
+ * Works unchanged: scann_hip_search_batched(_params), scann_hip_index_reserve, scann_hip_search_batched_device,
+ * scann_hip_index_last_device_status, allow-bitmaps per call and per query, token-map searches, the crowded searches,
+ * the stage outputs, timing, scann_hip_index_write_file / scann_hip_index_load_file (the header's dim / stride keep
+ * describing the index space; new sections "proj_meta" = u32 {kind, in_dim, out_dim, start, row_stride}, "proj_matrix" =
+ * f32 [out_dim][in_dim], "proj_mean" = f32 [in_dim] (PCA only); "data" holds the original rows at row_stride; a
+ * proj_meta that disagrees with the header or the section sizes -> DataLoss).  Timing: scann_hip_index_last_kernel_ms
+ * brackets the dominant kernel, the scan, as on every handle; the query projection is outside that bracket, like the
+ * partition, table, select and re-rank kernels.  The stage functions scann_hip_txh_partition, scann_hip_lut_from_query and
+ * scann_hip_adc_distances stay in INDEX space on such a handle: they take queries of out_dim floats.
+ * Unimplemented, each message naming projection: scann_hip_search_mmr*, scann_hip_mutable_create / _rebase / fold onto
+ * it, scann_hip_txh_search_local_device / _sharded_device, scann_hip_index_quantize_rows and
+ * scann_hip_index_quantization_stats from it, scann_hip_index_debug_rerank_brackets; at create: leaf_sizes_global, data_is_csr_order with partitions, SearchMode::Partitioned (no codes).
+ * InvalidArgument: a NULL projection, desc->data != NULL, desc->dim != out_dim, row_dim != in_dim, row_stride <
+ * row_dim; and all of scann_hip_txh_create's errors. */
+int scann_hip_txh_create_projected(scann_hip_ctx *ctx, const scann_hip_txh_desc *desc,
+                                   const scann_hip_projection *projection, const float *rows, uint64_t n_rows,
+                                   uint32_t row_dim, uint32_t row_stride, scann_hip_index **out_index);
+/* out4 = kind, in_dim, out_dim, start of the projection a handle searches through; kind 0 (and zeros) on every other
+ * handle. */
+int scann_hip_index_projection_info(const scann_hip_index *index, uint32_t *out4);
+
 typedef struct {
     /* 0 = the index default.  SearchParameters.num_leaves_to_search is ignored by
      * the reference searcher; this knob exists for sweeps. */

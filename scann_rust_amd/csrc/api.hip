@@ -24,6 +24,7 @@
 #include "mutable.h"
 #include "knobs.h"
 #include "launch.h"
+#include "project.h"
 #include "scalarq.h"
 #include "txh.h"
 
@@ -68,7 +69,8 @@ struct TxhWorkspace {
         counters, pair_q, pair_leaf, pair_vbase, pair_thr, slot_of, lutq, thr, cand_cnt, cand, cand_key,
         cand_idx, cand_dist, cand_exact, cand_row, cand_count, out_idx, out_dist, out_count, allow,
         sbase, pair_sbase, stile_off, samp, lut8, lut8_meta, cand32, cand32_codes, cand32_cnt, mfma_thr1, rr_lb, rr_ub, small_tickets,
-          wide_min, wide_ckey, wide_ceb, wide_cidx, wide_cnt;
+          wide_min, wide_ckey, wide_ceb, wide_cidx, wide_cnt,
+        proj_q;   // projected handles: [nq][dim] projected queries (last: the buffers before it keep their places)
     void *arena = nullptr;
     size_t arena_bytes = 0;
     bool dirty = false;
@@ -84,7 +86,7 @@ struct TxhWorkspace {
                         &cand_key, &cand_idx, &cand_dist, &cand_exact, &cand_row, &cand_count, &out_idx, &out_dist,
                         &out_count, &allow, &sbase, &pair_sbase, &stile_off, &samp, &lut8, &lut8_meta, &cand32,
                         &cand32_codes, &cand32_cnt, &mfma_thr1, &rr_lb, &rr_ub, &small_tickets,
-                        &wide_min, &wide_ckey, &wide_ceb, &wide_cidx, &wide_cnt};
+                        &wide_min, &wide_ckey, &wide_ceb, &wide_cidx, &wide_cnt, &proj_q};
         for (WsBuf *b : all) f(*b);
     }
     void want(WsBuf &b, size_t bytes) {
@@ -239,6 +241,10 @@ struct scann_hip_index {
     DevBuf d_qrows;           // scann_hip_txh_create_quantized: the re-rank rows as given (d_rows, d_rows8 stay empty)
     int q_fmt = 0;            // ... their SCANN_HIP_ROWS_* format (0: f32 rows or none) and the int8 inv_multiplier
     float q_inv = 1.0f;
+    // scann_hip_txh_create_projected: the handle's own copy of the projection (kind 0: none).  tx.dim is then the
+    // projection's out_dim, tx.row_dim / row_stride describe d_rows, and launch_txh projects every call's queries.
+    ProjDev proj;
+    DevBuf d_proj_matrix, d_proj_mean;
     std::vector<uint32_t> local_sizes_desc;  // local leaf sizes, descending, prefix-summed
     uint32_t default_P = 0;
     float multiplier = 3.0f;
@@ -291,6 +297,7 @@ int scann::index_base_view(const scann_hip_index *ix, BaseView *v) {
     } else {
         v->rows = ix->tx.rows;
         v->quantized = ix->tx.qfmt != 0;
+        v->projected = ix->proj.kind != 0;
         v->n = ix->tx.n_local;
         v->dim = ix->tx.dim;
         v->stride = ix->tx.stride;
@@ -433,7 +440,14 @@ int scann::index_download(const scann_hip_index *ix, IndexHostArrays *o, bool wi
     const TxhIndexDev &t = ix->tx;
     o->brute_force = false;
     txh_desc_of(ix, &d);
-    if (t.rows && with_rows) {
+    if (ix->proj.kind) {   // the projection, and the rows in their own space (d.data stays null: d is the index space)
+        const ProjDev &pd = ix->proj;
+        const uint32_t meta[5] = {(uint32_t)pd.kind, pd.in_dim, pd.out_dim, pd.start, t.row_stride};
+        std::memcpy(o->proj_meta, meta, sizeof(meta));
+        if (pd.matrix) SCANN_TRY(down(o->proj_matrix, pd.matrix, (size_t)pd.out_dim * pd.in_dim));
+        if (pd.mean) SCANN_TRY(down(o->proj_mean, pd.mean, (size_t)pd.in_dim));
+        if (t.rows && with_rows) SCANN_TRY(down(o->data, t.rows, (size_t)ix->n_rows * t.row_stride));
+    } else if (t.rows && with_rows) {
         SCANN_TRY(down(o->data, t.rows, (size_t)ix->n_rows * t.stride));
         d.data = o->data.data();
     }
@@ -549,7 +563,7 @@ uint64_t scann_hip_index_size(const scann_hip_index *ix) {
 }
 uint32_t scann_hip_index_dimensionality(const scann_hip_index *ix) {
     if (!ix) return 0;
-    return ix->kind == KIND_BF ? ix->bf.dim : ix->tx.dim;
+    return ix->kind == KIND_BF ? ix->bf.dim : ix->tx.row_dim;   // (projected handles: the rows' space)
 }
 
 void scann_hip_index_enable_timing(scann_hip_index *ix, int enable) {
@@ -893,6 +907,8 @@ static int txh_finish(scann_hip_index *ix, const scann_hip_txh_desc *d, const st
     TxhIndexDev &t = ix->tx;
     t.dim = d->dim;
     t.stride = d->stride;
+    t.row_dim = d->dim;       // (scann_hip_txh_create_projected overwrites the two)
+    t.row_stride = d->stride;
     t.L = L;
     t.S = S;
     t.K = K;
@@ -1063,6 +1079,92 @@ int scann_hip_txh_create_quantized(scann_hip_ctx *ctx, const scann_hip_txh_desc 
 
 }  // extern "C"
 
+// ---- projected handles (project.h) ------------------------------------------------------------------
+extern "C" {
+
+int scann_hip_txh_create_projected(scann_hip_ctx *ctx, const scann_hip_txh_desc *d, const scann_hip_projection *proj,
+                                   const float *rows, uint64_t n_rows, uint32_t row_dim, uint32_t row_stride,
+                                   scann_hip_index **out) {
+    return scann::txh_create_projected_checked(ctx, d, proj, rows, n_rows, row_dim, row_stride, out, SCANN_HIP_INVALID_ARGUMENT);
+}
+
+}  // extern "C"
+
+int scann::txh_create_projected_checked(scann_hip_ctx *ctx, const scann_hip_txh_desc *d, const scann_hip_projection *proj,
+                                        const float *rows, uint64_t n_rows, uint32_t row_dim, uint32_t row_stride,
+                                        scann_hip_index **out, int content_status) {
+    if (!ctx || !d || !out) return fail(SCANN_HIP_INVALID_ARGUMENT, "null ctx/desc/out_index");
+    if (!proj) return fail(SCANN_HIP_INVALID_ARGUMENT, "projected index: projection is null");
+    const ProjDev &pd = proj->dev;
+    if (d->data)
+        return fail(SCANN_HIP_INVALID_ARGUMENT, "projected index: desc.data must be NULL (the rows are the `rows` argument)");
+    if (d->dim != pd.out_dim)
+        return fail(SCANN_HIP_INVALID_ARGUMENT, "projected index: desc.dim " + std::to_string(d->dim) +
+                                                    " is not the projection's out_dim " + std::to_string(pd.out_dim));
+    if (row_dim != pd.in_dim)
+        return fail(SCANN_HIP_INVALID_ARGUMENT, "projected index: row_dim " + std::to_string(row_dim) +
+                                                    " is not the projection's in_dim " + std::to_string(pd.in_dim));
+    if (row_stride < row_dim) return fail(SCANN_HIP_INVALID_ARGUMENT, "projected index: row_stride < row_dim");
+    if (d->leaf_sizes_global || (d->data_is_csr_order && d->num_partitions))
+        return fail(SCANN_HIP_UNIMPLEMENTED, "a projection in a leaf-sharded index is not built");
+    if (!d->codebook && !d->codes && d->num_subspaces == 0)
+        return fail(SCANN_HIP_UNIMPLEMENTED, "a projection in SearchMode::Partitioned (no codes) is not built");
+    // the rows are validated as desc.data is (txh_create_checked skips these without desc.data)
+    if (rows) {
+        if (d->num_partitions == 0) {
+            if (n_rows < d->n_local)
+                return fail(content_status, "data has fewer rows than the index has points");
+        } else if (d->leaf_ids) {
+            for (uint64_t i = 0; i < d->n_local; ++i)
+                if (d->leaf_ids[i] >= n_rows)
+                    return fail(content_status, "leaf_ids entry " + std::to_string(i) + " >= n_rows");
+        }
+        if (n_rows > SIZE_MAX / 4 / row_stride) return fail(SCANN_HIP_OUT_OF_RANGE, "projected index: n_rows * row_stride overflows");
+    }
+    scann_hip_txh_desc dd = *d;
+    dd.n_rows = rows ? n_rows : 0;
+    dd.stride = d->dim;   // (index space; no row is read at it)
+    scann_hip_index *ix = nullptr;
+    SCANN_TRY(scann::txh_create_checked(ctx, &dd, &ix, content_status));
+    auto bail = [&](int s) {
+        scann_hip_index_destroy(ix);
+        return s;
+    };
+    int s = SCANN_HIP_OK;
+    ix->proj = pd;
+    ix->proj.matrix = ix->proj.mean = nullptr;
+    if (pd.kind != SCANN_HIP_PROJ_TRUNCATE) {
+        if ((s = upload(ix->d_proj_matrix, proj->matrix.data(), proj->matrix.size() * 4)) != SCANN_HIP_OK) return bail(s);
+        ix->proj.matrix = ix->d_proj_matrix.as<float>();
+    }
+    if (pd.kind == SCANN_HIP_PROJ_PCA) {
+        if ((s = upload(ix->d_proj_mean, proj->mean.data(), proj->mean.size() * 4)) != SCANN_HIP_OK) return bail(s);
+        ix->proj.mean = ix->d_proj_mean.as<float>();
+    }
+    if (rows) {
+        if ((s = upload(ix->d_rows, rows, (size_t)n_rows * row_stride * 4)) != SCANN_HIP_OK) return bail(s);
+        ix->tx.rows = ix->d_rows.as<float>();
+        ix->n_rows = n_rows;
+    }
+    ix->tx.row_dim = row_dim;
+    ix->tx.row_stride = row_stride;
+    *out = ix;
+    return SCANN_HIP_OK;
+}
+
+extern "C" {
+
+int scann_hip_index_projection_info(const scann_hip_index *ix, uint32_t *out4) {
+    if (!ix || !out4) return fail(SCANN_HIP_INVALID_ARGUMENT, "null index/output");
+    out4[0] = (uint32_t)ix->proj.kind;
+    out4[1] = ix->proj.in_dim;
+    out4[2] = ix->proj.out_dim;
+    out4[3] = ix->proj.start;
+    return SCANN_HIP_OK;
+}
+
+}  // extern "C"
+
 // ---- scalar quantizer over a handle's f32 rows (scalarq.h) ------------------------------------------
 // The f32 rows scann_hip_index_quantization_stats and scann_hip_index_quantize_rows read, or why there are none.
 struct SqSource {
@@ -1083,6 +1185,7 @@ static int sq_source(const scann_hip_index *ix, SqSource *o) {
         return SCANN_HIP_OK;
     }
     const TxhIndexDev &t = ix->tx;
+    if (ix->proj.kind) return fail(SCANN_HIP_UNIMPLEMENTED, "quantized rows behind a projection are not built");
     if (t.qfmt) return fail(SCANN_HIP_INVALID_ARGUMENT, "the index already holds quantized rows");
     if (t.measure == SCANN_HIP_L1 || t.measure == SCANN_HIP_COSINE)
         return fail(SCANN_HIP_UNIMPLEMENTED, "quantized rows: SquaredL2, L2 and DotProduct only");
@@ -1181,7 +1284,7 @@ uint64_t scann_hip_index_device_bytes(const scann_hip_index *ix) {
     for (const DevBuf *b : {&ix->bf_rows, &ix->bf_rows_b, &ix->bf_rows_bl, &ix->bf_norm2, &ix->bf_leaf, &ix->d_centers,
                             &ix->d_centers_t, &ix->d_leaf_off, &ix->d_leaf_gsize, &ix->d_leaf_ids, &ix->d_codes,
                             &ix->d_codes_sp, &ix->d_rows, &ix->d_codebook, &ix->d_rows8, &ix->d_rows8_meta, &ix->d_qrows,
-                            &ix->crowd_attrs, &ix->crowd_md_attrs})
+                            &ix->crowd_attrs, &ix->crowd_md_attrs, &ix->d_proj_matrix, &ix->d_proj_mean})
         if (b->p) sum += b->bytes;
     return sum;
 }
@@ -1232,6 +1335,8 @@ static int plan_txh_search(const scann_hip_index *ix, uint32_t k, const scann_hi
     // rows stored quantized: the small and wide pipelines re-rank inside their finish kernels from f32 rows, so every
     // batch size takes the staged pipeline, whose re-rank is a kernel of its own
     if (t.qfmt) widest = TxhPipeline::Staged;
+    // projected handles: the few-query pipelines re-rank inside kernels that read one query space
+    if (ix->proj.kind) widest = TxhPipeline::Staged;
     uint32_t P = o->partitions_to_search ? o->partitions_to_search : ix->default_P;
     P = std::min(P, t.L);  // tree_partitioner.rs:214
     if (t.ah_mode) P = 1;
@@ -1422,6 +1527,7 @@ static const char *txh_kernel_name(const TxhIndexDev &t, const TxhPlan &p, bool 
 int scann::txh_resolve_m(scann_hip_index *ix, uint32_t k, const scann_hip_search_opts *opts, uint32_t *out_m) {
     if (!ix || ix->kind != KIND_TXH) return fail(SCANN_HIP_INVALID_ARGUMENT, "not a tree index");
     if (ix->tx.qfmt) return fail(SCANN_HIP_UNIMPLEMENTED, "the leaf-sharded search over quantized rows is not built");
+    if (ix->proj.kind) return fail(SCANN_HIP_UNIMPLEMENTED, "the leaf-sharded search through a projection is not built");
     scann_hip_search_opts o;
     if (opts) o = *opts; else scann_hip_search_opts_default(&o);
     o.exact_reorder = 1;
@@ -1496,6 +1602,7 @@ static int ensure_txh_workspace(scann_hip_index *ix, TxhWorkspace &s, const TxhP
         s.want(s.cand32_cnt, (size_t)nq * 4);
     }
     if (small) s.want(s.small_tickets, 64 * 4);
+    if (ix->proj.kind) s.want(s.proj_q, (size_t)nq * t.dim * 4);
     if (wide) {
         s.want(s.wide_min, (size_t)nq * p.cap * 4);
         s.want(s.wide_ckey, (size_t)nq * p.wide_cap2 * 8);
@@ -1525,6 +1632,7 @@ static int ensure_txh_workspace(scann_hip_index *ix, TxhWorkspace &s, const TxhP
         w->cand32_cnt = s.cand32_cnt.as<uint32_t>();
     }
     if (small) w->small_tickets = s.small_tickets.as<uint32_t>();
+    if (ix->proj.kind) w->proj_q = s.proj_q.as<float>();
     if (wide) {
         w->wide_min = s.wide_min.as<uint32_t>();
         w->wide_ckey = s.wide_ckey.as<uint64_t>();
@@ -1562,6 +1670,20 @@ static int ensure_txh_workspace(scann_hip_index *ix, TxhWorkspace &s, const TxhP
     w->out_dist = s.out_dist.as<float>();
     w->out_count = s.out_count.as<uint32_t>();
     return SCANN_HIP_OK;
+}
+
+// txh_launch_search on a handle that may be projected.  A projected handle first writes qp = project(q) into the
+// workspace's proj_q at the head of the stream; the pipeline then runs on qp at dim = out_dim, and the re-rank alone
+// reads the caller's queries (w.rr_queries).  Any other handle: txh_launch_search as it was.
+static int launch_txh(const scann_hip_index *ix, TxhWork &w, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1) {
+    if (ix->proj.kind && w.nq) {
+        SCANN_TRY(launch_project(ix->proj, w.queries, w.nq, w.q_stride, w.proj_q, ix->tx.dim, st));
+        w.rr_queries = w.queries;
+        w.rr_q_stride = w.q_stride;
+        w.queries = w.proj_q;
+        w.q_stride = ix->tx.dim;
+    }
+    return txh_launch_search(ix->tx, w, false, st, ev0, ev1);
 }
 
 static void fill_empty(uint32_t nq, uint32_t k, uint32_t *out_idx, float *out_dist,
@@ -1802,8 +1924,7 @@ static int txh_search_host(scann_hip_index *ix, const float *queries, uint32_t n
         SCANN_HIP_CHECK(hipMemcpyAsync(ws.queries.p, queries, (size_t)nq * q_stride * 4,
                                        hipMemcpyHostToDevice, stream));
         if (sl.primary) ix->next_events();   // kernel timing follows the primary slot only
-        SCANN_TRY(txh_launch_search(ix->tx, w, false, stream, sl.primary ? ix->ev0 : nullptr,
-                                    sl.primary ? ix->ev1 : nullptr));
+        SCANN_TRY(launch_txh(ix, w, stream, sl.primary ? ix->ev0 : nullptr, sl.primary ? ix->ev1 : nullptr));
         if (sl.primary) ix->timing_valid = ix->timing;
         if (sl.primary) ix->timed_kernel = txh_kernel_name(ix->tx, p, /*pinned=*/false);
         uint32_t counters[CNT_N];
@@ -1957,7 +2078,7 @@ int scann_hip_search_batched(scann_hip_index *ix, const float *queries, uint32_t
         }
         return s;
     }
-    if (q_dim != ix->tx.dim)  // tree_x_hybrid/mod.rs:251-253, hashes/hasher.rs:167-171
+    if (q_dim != ix->tx.row_dim)  // tree_x_hybrid/mod.rs:251-253, hashes/hasher.rs:167-171 (projected handles: the rows' space)
         return fail(SCANN_HIP_INVALID_ARGUMENT, "Query dimensionality mismatch");
     if (q_stride < q_dim) return fail(SCANN_HIP_INVALID_ARGUMENT, "q_stride < q_dim");
     if (k == 0) {
@@ -2108,11 +2229,10 @@ static int search_device_ws(scann_hip_index *ix, scann_hip_index::DeviceSlot *ds
         w.allow_bits = opts->allow_bitmap_bits;
         w.allow_stride = opts->allow_bitmap_stride;
     }
-    if (!dsl) return txh_launch_search(ix->tx, w, false, st, nullptr, nullptr);
+    if (!dsl) return launch_txh(ix, w, st, nullptr, nullptr);
     ix->last_work = w;
     ix->next_events();
-    SCANN_TRY(txh_launch_search(ix->tx, w, false, st, ix->ev0,
-                                ix->ev1));
+    SCANN_TRY(launch_txh(ix, w, st, ix->ev0, ix->ev1));
     SCANN_TRY(device_slot_done(dsl, st));
     ix->timing_valid = ix->timing;
     ix->timed_kernel = txh_kernel_name(ix->tx, p, /*pinned=*/false);
@@ -2168,6 +2288,8 @@ int scann_hip_index_debug_rerank_brackets(scann_hip_index *ix, void *hip_stream,
     if (!ix || ix->kind != KIND_TXH) return fail(SCANN_HIP_INVALID_ARGUMENT, "not a tree / hasher index");
     if (ix->tx.qfmt)
         return fail(SCANN_HIP_UNIMPLEMENTED, "a handle over quantized rows has no re-rank row filter: no brackets to read");
+    if (ix->proj.kind)
+        return fail(SCANN_HIP_UNIMPLEMENTED, "a handle that searches through a projection has no re-rank row filter: no brackets to read");
     if (nq && m && (!out_lb || !out_ub || !out_rows || !out_counts))
         return fail(SCANN_HIP_INVALID_ARGUMENT, "an output is null");
     SCANN_TRY(set_device(ix->ctx));
@@ -2251,6 +2373,7 @@ static int mmr_rows(const scann_hip_index *ix, const float **rows, uint64_t *n, 
     }
     if (ix->sharded) return fail(SCANN_HIP_UNIMPLEMENTED, "MMR on a shard (leaf_sizes_global) is not built");
     if (ix->tx.qfmt) return fail(SCANN_HIP_UNIMPLEMENTED, "MMR over quantized rows is not built");
+    if (ix->proj.kind) return fail(SCANN_HIP_UNIMPLEMENTED, "MMR on a handle that searches through a projection is not built");
     if (!ix->tx.rows) return fail(SCANN_HIP_FAILED_PRECONDITION, "MMR needs the handle's f32 rows (desc.data)");
     if (ix->tx.rows_csr && !ix->tx.ah_mode)
         return fail(SCANN_HIP_UNIMPLEMENTED, "MMR over rows held in CSR order is not built");
@@ -2321,7 +2444,7 @@ static bool stage_on_device(const scann_hip_index *ix, const Stage &sg, uint32_t
     if (depth > sg.max_depth() || q_stride < q_dim) return false;
     if (o && (o->tokens || o->token_dists || o->cand_idx || o->cand_dist || o->cand_count)) return false;
     if (ix->kind == KIND_BF) return ix->bf.n > 0 && q_dim == ix->bf.dim && depth <= ix->bf.n;
-    return q_dim == ix->tx.dim;
+    return q_dim == ix->tx.row_dim;
 }
 
 // OK: the caller's arrays hold the answer.  Any other status: nothing was written that the second route does not
@@ -2593,6 +2716,7 @@ int scann_hip_txh_search_local_device(scann_hip_index *ix, const float *d_querie
                                       void *hip_stream) {
     if (!ix || ix->kind != KIND_TXH) return fail(SCANN_HIP_INVALID_ARGUMENT, "not a tree index");
     if (ix->tx.qfmt) return fail(SCANN_HIP_UNIMPLEMENTED, "the local stage of a sharded search over quantized rows is not built");
+    if (ix->proj.kind) return fail(SCANN_HIP_UNIMPLEMENTED, "the local stage of a sharded search through a projection is not built");
     SCANN_TRY(refuse_allow_stride(opts, "the leaf-sharded search"));
     if (nq == 0) return SCANN_HIP_OK;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);

@@ -22,6 +22,10 @@ struct DevBuf;
 int txh_create_checked(scann_hip_ctx *ctx, const scann_hip_txh_desc *d, scann_hip_index **out,
                        int content_status, const void *qrows = nullptr, int qfmt = 0, float qinv = 1.0f,
                        DevBuf *qrows_dev = nullptr);
+// scann_hip_txh_create_projected with the status reported for inconsistent array contents (api.hip)
+int txh_create_projected_checked(scann_hip_ctx *ctx, const scann_hip_txh_desc *d, const scann_hip_projection *proj,
+                                 const float *rows, uint64_t n_rows, uint32_t row_dim, uint32_t row_stride,
+                                 scann_hip_index **out, int content_status);
 // the argument checks scann_hip_txh_create_quantized makes before those of scann_hip_txh_create (api.hip)
 int txh_quantized_args(const scann_hip_txh_desc *d, const void *rows, int row_format, float inv_multiplier);
 

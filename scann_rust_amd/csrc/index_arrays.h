@@ -15,6 +15,10 @@ struct IndexHostArrays {
     std::vector<uint8_t> rows_q;                           // quantized re-rank rows as stored (d.data is then null) ...
     int rows_q_fmt = 0;                                    // ... their SCANN_HIP_ROWS_* format, 0 = none ...
     float rows_q_inv = 1.0f;                               // ... and the int8 inv_multiplier
+    // a projected handle (scann_hip_txh_create_projected): d describes the index space and d.data stays null; `data`
+    // holds the original rows, proj_meta[4] floats apart
+    uint32_t proj_meta[5] = {0, 0, 0, 0, 0};               // kind (0 = none), in_dim, out_dim, start, row_stride
+    std::vector<float> proj_matrix, proj_mean;
 };
 // with_rows = false: everything but the f32 / quantized rows (d.data stays null; d.n_rows is still the handle's)
 int index_download(const scann_hip_index *ix, IndexHostArrays *out, bool with_rows = true);

@@ -182,10 +182,18 @@ int section(const Mapping &m, const char *path, const char *name, uint64_t want,
     return SCANN_HIP_OK;
 }
 
+// The projection of a projected handle and its rows, as write_txh stores them: `proj_meta` (u32: kind, in_dim, out_dim,
+// start, row_stride), `proj_matrix` (f32 [out_dim][in_dim]; MATRIX, PCA), `proj_mean` (f32 [in_dim]; PCA), and `data` =
+// the original rows, row_stride floats apart (the header's dim / stride keep describing the index space).
+struct ProjSections {
+    const uint32_t *meta = nullptr;   // [5]
+    const float *matrix = nullptr, *mean = nullptr, *rows = nullptr;
+};
+
 // scann_hip_txh_write_file, and with rows_q != nullptr the file of a handle over quantized rows: no `data` section,
-// the rows' bytes in `rows_q`, {format, inv_multiplier bits} in `rows_q_meta`
+// the rows' bytes in `rows_q`, {format, inv_multiplier bits} in `rows_q_meta`; with pj != nullptr a projected handle's
 int write_txh(const char *path, const scann_hip_txh_desc *d, const void *rows_q, uint64_t rows_q_bytes, int rows_q_fmt,
-              float rows_q_inv) {
+              float rows_q_inv, const ProjSections *pj = nullptr) {
     if (!path || !d) return fail(SCANN_HIP_INVALID_ARGUMENT, "path/desc is null");
     const bool ah = d->num_partitions == 0;
     const bool exact = !d->codebook && !d->codes && d->num_subspaces == 0;
@@ -210,6 +218,13 @@ int write_txh(const char *path, const scann_hip_txh_desc *d, const void *rows_q,
     h.pre_reorder_multiplier = d->pre_reorder_multiplier;
     std::vector<PendingSection> secs;
     if (d->data) secs.push_back({"data", DT_F32, d->data, (uint64_t)d->n_rows * d->stride * 4});
+    if (pj) {
+        const uint64_t in_dim = pj->meta[1], out_dim = pj->meta[2];
+        if (pj->rows) secs.push_back({"data", DT_F32, pj->rows, (uint64_t)d->n_rows * pj->meta[4] * 4});
+        secs.push_back({"proj_meta", DT_U32, pj->meta, 5 * 4});
+        if (pj->matrix) secs.push_back({"proj_matrix", DT_F32, pj->matrix, out_dim * in_dim * 4});
+        if (pj->mean) secs.push_back({"proj_mean", DT_F32, pj->mean, in_dim * 4});
+    }
     uint32_t q_meta[2] = {(uint32_t)rows_q_fmt, 0u};
     std::memcpy(&q_meta[1], &rows_q_inv, 4);
     if (rows_q) {
@@ -262,6 +277,14 @@ int scann_hip_index_write_file(const scann_hip_index *index, const char *path) {
     if (a.brute_force)
         return scann_hip_bf_write_file(path, a.d.data, a.d.n_rows, a.d.dim, a.d.stride, a.d.distance_measure);
     if (a.rows_q_fmt) return write_txh(path, &a.d, a.rows_q.data(), a.rows_q.size(), a.rows_q_fmt, a.rows_q_inv);
+    if (a.proj_meta[0]) {
+        ProjSections pj;
+        pj.meta = a.proj_meta;
+        pj.matrix = a.proj_matrix.empty() ? nullptr : a.proj_matrix.data();
+        pj.mean = a.proj_mean.empty() ? nullptr : a.proj_mean.data();
+        pj.rows = a.data.empty() ? nullptr : a.data.data();
+        return write_txh(path, &a.d, nullptr, 0, 0, 1.0f, &pj);
+    }
     return scann_hip_txh_write_file(path, &a.d);
 }
 
@@ -325,8 +348,22 @@ int scann_hip_index_load_file(scann_hip_ctx *ctx, const char *path, scann_hip_in
     d.use_residuals = h.use_residuals;
     d.partitions_to_search = h.partitions_to_search;
     d.pre_reorder_multiplier = h.pre_reorder_multiplier;
-    SCANN_TRY(section(m, path, "data", bytes3(h.n_rows, h.stride, 4), false, &p));
-    d.data = static_cast<const float *>(p);
+    // a projected handle: `data` holds the original rows at proj_meta's row_stride, not at the header's stride
+    uint32_t pmeta[5] = {0, 0, 0, 0, 0};
+    const bool projected = m.find("proj_meta") != nullptr;
+    if (projected) {
+        SCANN_TRY(section(m, path, "proj_meta", sizeof(pmeta), true, &p));
+        std::memcpy(pmeta, p, sizeof(pmeta));
+        const uint32_t kind = pmeta[0], in_dim = pmeta[1], out_dim = pmeta[2], start = pmeta[3], row_stride = pmeta[4];
+        const bool known = kind == SCANN_HIP_PROJ_MATRIX || kind == SCANN_HIP_PROJ_PCA || kind == SCANN_HIP_PROJ_TRUNCATE;
+        if (!known || in_dim == 0 || out_dim != h.dim || row_stride < in_dim ||
+            (kind == SCANN_HIP_PROJ_TRUNCATE ? (uint64_t)start + out_dim > in_dim : start != 0))
+            return fail(SCANN_HIP_DATA_LOSS, std::string(path) + ": proj_meta disagrees with the header or with itself");
+        if (m.find("rows_q")) return fail(SCANN_HIP_DATA_LOSS, std::string(path) + ": both 'proj_meta' and 'rows_q' sections");
+    }
+    SCANN_TRY(section(m, path, "data", bytes3(h.n_rows, projected ? pmeta[4] : h.stride, 4), false, &p));
+    const float *data = static_cast<const float *>(p);
+    if (!projected) d.data = data;
     if (h.num_partitions) {
         SCANN_TRY(section(m, path, "centers", bytes3(h.num_partitions, h.dim, 4), true, &p));
         d.centers = static_cast<const float *>(p);
@@ -360,6 +397,24 @@ int scann_hip_index_load_file(scann_hip_ctx *ctx, const char *path, scann_hip_in
         SCANN_TRY(section(m, path, "rows_q", bytes3(h.n_rows, h.stride, fmt == SCANN_HIP_ROWS_BF16 ? 2 : 1), true, &p));
         SCANN_TRY(scann::txh_quantized_args(&d, p, fmt, inv));
         return scann::txh_create_checked(ctx, &d, out, SCANN_HIP_DATA_LOSS, p, fmt, inv);
+    }
+    if (projected) {
+        const uint32_t kind = pmeta[0], in_dim = pmeta[1], out_dim = pmeta[2];
+        const void *pm = nullptr, *pmean = nullptr;
+        const bool dense = kind != SCANN_HIP_PROJ_TRUNCATE;
+        SCANN_TRY(section(m, path, "proj_matrix", bytes3(out_dim, in_dim, 4), dense, &pm));
+        SCANN_TRY(section(m, path, "proj_mean", (uint64_t)in_dim * 4, kind == SCANN_HIP_PROJ_PCA, &pmean));
+        if (!dense && (pm || pmean))
+            return fail(SCANN_HIP_DATA_LOSS, std::string(path) + ": a TRUNCATE projection with a matrix or a mean");
+        if (kind == SCANN_HIP_PROJ_MATRIX && pmean)
+            return fail(SCANN_HIP_DATA_LOSS, std::string(path) + ": a MATRIX projection with a mean");
+        scann_hip_projection *proj = nullptr;
+        SCANN_TRY(scann_hip_projection_create(ctx, (int)kind, in_dim, out_dim, static_cast<const float *>(pm),
+                                              static_cast<const float *>(pmean), pmeta[3], &proj));
+        const int s = scann::txh_create_projected_checked(ctx, &d, proj, data, h.n_rows, in_dim, pmeta[4], out,
+                                                          SCANN_HIP_DATA_LOSS);
+        scann_hip_projection_destroy(proj);
+        return s;
     }
     return scann::txh_create_checked(ctx, &d, out, SCANN_HIP_DATA_LOSS);
 }

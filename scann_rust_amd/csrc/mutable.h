@@ -14,6 +14,7 @@ struct BaseView {
     uint32_t dim = 0, stride = 0;
     int measure = 0;               // measure of the handle's final distances (brute force: its own; tree / AH: the re-rank's)
     bool quantized = false, rows_csr = false, partitioned = false, sharded = false;
+    bool projected = false;        // scann_hip_txh_create_projected: the rows are not in the index's space
 };
 int index_base_view(const scann_hip_index *ix, BaseView *v);
 

@@ -323,6 +323,7 @@ int check_base(const scann_hip_index *base, BaseView *bv) {
     if (bv->partitioned) return fail(SCANN_HIP_UNIMPLEMENTED, "mutable index over SearchMode::Partitioned is not built");
     if (bv->sharded) return fail(SCANN_HIP_UNIMPLEMENTED, "mutable index over a shard (leaf_sizes_global) is not built");
     if (bv->quantized) return fail(SCANN_HIP_UNIMPLEMENTED, "mutable index over quantized rows is not built");
+    if (bv->projected) return fail(SCANN_HIP_UNIMPLEMENTED, "mutable index over a base that searches through a projection is not built");
     if (!bv->rows) return fail(SCANN_HIP_UNIMPLEMENTED, "mutable index needs a base that stores its rows");
     if (bv->rows_csr) return fail(SCANN_HIP_UNIMPLEMENTED, "mutable index needs rows stored by datapoint index");
     return SCANN_HIP_OK;

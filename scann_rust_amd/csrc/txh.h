@@ -122,6 +122,10 @@ struct TxhIndexDev {
     const void *qrows;
     int qfmt;                     // SCANN_HIP_ROWS_BF16 / _FP8_E4M3 / _INT8; 0 = f32 rows or none
     float inv_mult;               // int8 rows: value = (float)i8 * inv_mult
+    // the space of the re-rank rows: `rows` are row_dim wide and row_stride apart.  Equal to dim / stride on every
+    // handle but a projected one (scann_hip_txh_create_projected), whose centres, codebook and tables live at `dim` =
+    // the projection's out_dim while the rows keep the original dimensionality.  Read by the exact re-rank alone.
+    uint32_t row_dim, row_stride;
 };
 
 // points of one scan tile chunk for this index's code layout (Codec<S, bits>::TP in txh_dev.h)
@@ -185,6 +189,11 @@ struct TxhWork : TxhPlan {
     uint64_t allow_bits;       // bitmap capacity in bits; indices >= capacity are not allowed
     uint64_t allow_stride;     // 64-bit words from query i's bitmap to query i + 1's; 0 = one bitmap for the batch
     const float *queries;      // device
+    // projected handles: the queries the re-rank reads (the caller's, row_dim wide; `queries` are then their
+    // projections, written to proj_q at the head of the call).  nullptr: the re-rank reads `queries` / q_stride.
+    const float *rr_queries;
+    uint32_t rr_q_stride;
+    float *proj_q;             // [nq][dim] projected queries of a projected handle
     float *cdist;              // [nq][L]
     uint32_t *tokens;          // [nq][P]
     float *token_dists;        // [nq][P]

@@ -3274,14 +3274,24 @@ static int launch_rerank(const TxhIndexDev &ix, const TxhWork &w, bool local_onl
     // rows stored quantized: every candidate scored from its stored row (txh_rows.hip K8q); the final kernels finish
     if (ix.qfmt) return launch_rerank_quant(ix, w, st);
     const bool unsorted = select_unsorted(w, local_only);
-    const size_t lds_rr = (size_t)ix.dim * 4;
+    // The re-rank's own view of the index: the rows' dimensionality and stride, and the queries of that space.  The same
+    // as ix / w.queries on every handle but a projected one (txh.h: row_dim, rr_queries), which has no 8-bit store.
+    TxhIndexDev rx = ix;
+    if (ix.row_dim) {
+        rx.dim = ix.row_dim;
+        rx.stride = ix.row_stride;
+    }
+    const float *rr_q = w.rr_queries ? w.rr_queries : w.queries;
+    const uint32_t rr_qs = w.rr_queries ? w.rr_q_stride : w.q_stride;
+    const size_t lds_rr = (size_t)rx.dim * 4;
     // int8 row filter in front of the exact re-rank (K8b): single-GPU final stage, squared L2, lists long
     // enough for the two extra kernels to pay
     // (the local stage of a leaf-sharded search takes the same two kernels in their prefix form: ShortArgs::local_head;
     // without local_prune: every local candidate re-ranked exactly, as before)
     const bool i8_local = local_only && w.local_prune && w.exact_reorder && !w.need_sorted_cands && w.k <= kTopkMaxK &&
                           w.m > 2 * kLocalHead;
-    const bool i8 = (unsorted || i8_local) && w.use_i8 && ix.rows8 && ix.measure == SCANN_HIP_SQUARED_L2 && (ix.dim & 15u) == 0;
+    const bool i8 = (unsorted || i8_local) && w.use_i8 && ix.rows8 && ix.measure == SCANN_HIP_SQUARED_L2 && (ix.dim & 15u) == 0 &&
+                    !w.rr_queries;
     if (i8) {
         SCANN_TRY(launch_rerank_i8(ix, w, st));
         ShortArgs sa;
@@ -3292,8 +3302,8 @@ static int launch_rerank(const TxhIndexDev &ix, const TxhWork &w, bool local_onl
         const size_t lds_sh = (size_t)ix.dim * 4;
         SCANN_TRY(launch(rerank_short_kernel, dim3(w.nq), dim3(256), lds_sh, st, ix, sa));
     } else {
-        SCANN_TRY(launch(rerank_kernel, dim3(ceil_div_u32(w.m, 32), w.nq), dim3(256), lds_rr, st, ix,
-                         w.queries, w.q_stride, w.m, w.cand_row, w.cand_count, w.cand_exact));
+        SCANN_TRY(launch(rerank_kernel, dim3(ceil_div_u32(w.m, 32), w.nq), dim3(256), lds_rr, st, rx,
+                         rr_q, rr_qs, w.m, w.cand_row, w.cand_count, w.cand_exact));
     }
     return SCANN_HIP_OK;
 }

@@ -69,6 +69,8 @@ EXPORTS = [
     "scann_hip_allow_bitmaps_combine", "scann_hip_allow_bitmaps_combine_device",
     "scann_hip_index_quantization_stats", "scann_hip_scalar_quantizer_calibrate", "scann_hip_scalar_quantize",
     "scann_hip_scalar_dequantize", "scann_hip_scalar_quantize_device", "scann_hip_index_quantize_rows",
+    "scann_hip_projection_create", "scann_hip_projection_destroy", "scann_hip_projection_info", "scann_hip_project",
+    "scann_hip_project_device", "scann_hip_txh_create_projected", "scann_hip_index_projection_info",
 ]
 
 
@@ -299,6 +301,15 @@ def load():
                                                    vp, C.c_uint32, vp]
     L.scann_hip_index_quantize_rows.argtypes = [vp, C.c_int, C.c_uint32, C.c_int, C.c_float, C.c_float, C.POINTER(vp),
                                                 f32p, i32p]
+    L.scann_hip_projection_create.argtypes = [vp, C.c_int, C.c_uint32, C.c_uint32, f32p, f32p, C.c_uint32, C.POINTER(vp)]
+    L.scann_hip_projection_destroy.argtypes = [vp]
+    L.scann_hip_projection_destroy.restype = None
+    L.scann_hip_projection_info.argtypes = [vp, u32p]
+    L.scann_hip_project.argtypes = [vp, f32p, C.c_uint64, C.c_uint32, C.c_uint32, f32p, C.c_uint32]
+    L.scann_hip_project_device.argtypes = [vp, vp, C.c_uint64, C.c_uint32, vp, C.c_uint32, vp]
+    L.scann_hip_txh_create_projected.argtypes = [vp, C.POINTER(TxhDesc), vp, f32p, C.c_uint64, C.c_uint32, C.c_uint32,
+                                                 C.POINTER(vp)]
+    L.scann_hip_index_projection_info.argtypes = [vp, u32p]
     _lib = L
     return L
 
@@ -361,6 +372,13 @@ class Index:
 
     def dimensionality(self):
         return int(load().scann_hip_index_dimensionality(self.h))
+
+    def projection_info(self):
+        """(kind, in_dim, out_dim, start) of the projection the handle searches through; kind 0 on any other handle
+        (scann_hip_index_projection_info)."""
+        out = np.zeros(4, np.uint32)
+        check(load().scann_hip_index_projection_info(self.h, ptr(out, u32p)))
+        return tuple(int(v) for v in out)
 
     def device_bytes(self):
         """Bytes of the handle's persistent device allocations, search workspaces excluded
@@ -1122,6 +1140,93 @@ def txh_create_quantized(*, rows, fmt, inv_multiplier=1.0, device=0, **desc):
     h = vp()
     check(load().scann_hip_txh_create_quantized(context(device), C.byref(d), r.ctypes.data if r is not None else None,
                                                 fmt, float(np.float32(inv_multiplier)), C.byref(h)))
+    return Index(h)
+
+
+PROJ_MATRIX, PROJ_PCA, PROJ_TRUNCATE = 1, 2, 3   # SCANN_HIP_PROJ_*
+
+
+class Projection:
+    """Owns one scann_hip_projection: the reference's dense projections (out[j] = sum over ascending i of
+    (in[i] - mean[i]) * matrix[j, i], f32, a multiply then an add per step; the mean PCA's alone) and TruncateProjection
+    (out = in[start : start + out_dim]).  `matrix` is [out_dim, in_dim]; immutable after create."""
+
+    def __init__(self, kind, matrix=None, mean=None, in_dim=None, out_dim=None, start=0, device=0):
+        m = None if matrix is None else f32(matrix)
+        mu = None if mean is None else f32(mean).ravel()
+        if m is not None and m.ndim == 2:
+            out_dim = m.shape[0] if out_dim is None else out_dim
+            in_dim = m.shape[1] if in_dim is None else in_dim
+            if m.shape != (out_dim, in_dim):
+                raise ValueError("matrix is %s, not [out_dim, in_dim] = [%d, %d]" % (m.shape, out_dim, in_dim))
+        if mu is not None and in_dim is not None and mu.size != in_dim:
+            raise ValueError("mean holds %d values, in_dim = %d" % (mu.size, in_dim))
+        h = vp()
+        check(load().scann_hip_projection_create(context(device), int(kind), int(in_dim or 0), int(out_dim or 0),
+                                                 ptr(m, f32p), ptr(mu, f32p), int(start), C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if self.h:
+            load().scann_hip_projection_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def info(self):
+        """(kind, in_dim, out_dim, start)"""
+        out = np.zeros(4, np.uint32)
+        check(load().scann_hip_projection_info(self.h, ptr(out, u32p)))
+        return tuple(int(v) for v in out)
+
+    def project(self, rows, row_dim=None, out=None):
+        """rows [n, row_stride] (row_dim leading columns are the row; default all) -> [n, out_dim], or into `out`
+        [n, out_stride], whose columns past out_dim are left as they are (scann_hip_project)."""
+        r = f32(rows)
+        if r.ndim == 1:
+            r = r[None]
+        n, rs = r.shape
+        od = self.info()[2]
+        o = np.empty((n, od), np.float32) if out is None else out
+        if o.dtype != np.float32 or not o.flags.c_contiguous or o.ndim != 2 or o.shape[0] != n:
+            raise ValueError("out must be a C-contiguous float32 [n, out_stride] array")
+        check(load().scann_hip_project(self.h, ptr(r, f32p) if n else None, n, rs, rs if row_dim is None else row_dim,
+                                       ptr(o, f32p) if n else None, o.shape[1]))
+        return o
+
+    def project_device(self, d_rows, n, row_stride, d_out, out_stride, stream=0):
+        """scann_hip_project_device: device addresses (integers) and a HIP stream handle; one kernel is enqueued, nothing is
+        synchronised or allocated."""
+        check(load().scann_hip_project_device(self.h, vp(d_rows), int(n), int(row_stride), vp(d_out), int(out_stride),
+                                              vp(stream or None)))
+
+
+def txh_create_projected(*, projection, rows, row_dim, row_stride=None, n_rows=None, device=0, **desc):
+    """A tree / hasher index that partitions, hashes and scans in the projected space and re-ranks against the original
+    `rows` [n_rows, row_stride] (None: no exact re-ordering): scann_hip_txh_create_projected.  `desc`: txh_create's
+    keyword arguments for the index in the projected space, without data / n_rows / stride (dim = the projection's
+    out_dim).  Searches take queries of row_dim floats."""
+    if desc.get("data") is not None:
+        raise ValueError("txh_create_projected takes rows=, not data=")
+    r = None if rows is None else f32(rows)
+    if r is not None and r.ndim == 2:
+        row_stride = r.shape[1] if row_stride is None else row_stride
+        n_rows = r.shape[0] if n_rows is None else n_rows
+    row_stride = row_dim if row_stride is None else row_stride
+    n_rows = 0 if n_rows is None else n_rows
+    if r is not None and r.size < n_rows * row_stride:
+        raise ValueError("rows holds %d elements, n_rows * row_stride = %d" % (r.size, n_rows * row_stride))
+    desc["data"] = None
+    desc.setdefault("stride", desc.get("dim"))
+    desc["n_rows"] = n_rows
+    d, keep = _txh_desc(**desc)
+    h = vp()
+    check(load().scann_hip_txh_create_projected(context(device), C.byref(d), projection.h if projection is not None else None,
+                                                ptr(r, f32p), int(n_rows), int(row_dim), int(row_stride), C.byref(h)))
     return Index(h)
 
 

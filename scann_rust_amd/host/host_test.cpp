@@ -150,6 +150,40 @@ static void tree_x_hybrid_tests() {
         EXPECT(loaded.search(q, 10) == qr);
         std::remove(path.c_str());
     }
+    {   // behind a projection (with_projection): an identity matrix over the searcher's own rows answers exactly like it
+        std::vector<float> eye(32 * 32, 0.0f);
+        for (int i = 0; i < 32; ++i) eye[i * 32 + i] = 1.0f;
+        auto ps = s.with_projection(Projection::matrix(32, 32, eye), sin_dataset(500, 32));
+        EXPECT(ps.dimensionality() == 32 && ps.search(q, 10) == r);
+        EXPECT(ps.search_with_filter(q, 10, &allow) == fr);
+    }
+    {   // 40-d rows indexed in the window [4, 36): queries of 40 floats, exact distances to the 40-d rows, file round trip
+        const DenseDataset ds40 = sin_dataset(500, 40);
+        const Projection window = Projection::truncate(40, 32, 4);
+        TreeXHybridSearcher sp(cfg);
+        sp.build(window.project_dataset(ds40));
+        auto ps = sp.with_projection(window, ds40);
+        EXPECT(ps.dimensionality() == 40 && ps.num_datapoints() == 500);
+        std::vector<float> q40(40);
+        for (int i = 0; i < 40; ++i) q40[i] = std::sin((float)i / 10.0f);
+        auto pr = ps.search(q40, 10);
+        EXPECT(pr.size() == 10);
+        sorted(pr);
+        for (auto &p : pr) {   // the re-rank read the ORIGINAL rows and the original query
+            double d = 0.0;
+            for (int j = 0; j < 40; ++j) d += ((double)q40[j] - ds40.get(p.first)[j]) * ((double)q40[j] - ds40.get(p.first)[j]);
+            EXPECT(p.first < 500 && std::fabs((double)p.second - d) <= 1e-4 * (1.0 + d));
+        }
+        bool wrong_dim = false;   // queries of the index space are refused
+        try { ps.search(q, 10); } catch (const ScannError &e) { wrong_dim = e.code == ErrorCode::InvalidArgument; }
+        EXPECT(wrong_dim);
+        const std::string path = "/tmp/scann_host_test_p_" + std::to_string((long)getpid()) + ".scannidx";
+        ps.save(path);
+        auto loaded = TreeXHybridSearcher::load(path);
+        EXPECT(loaded.dimensionality() == 40 && loaded.num_datapoints() == 500);
+        EXPECT(loaded.search(q40, 10) == pr);
+        std::remove(path.c_str());
+    }
     // TreeXHybridConfig::default(): 100 partitions, search 10, 256 codes x 8 subspaces (mod.rs:37-48)
     TreeXHybridSearcher dflt{TreeXHybridConfig()};
     dflt.build(sin_dataset(3000, 32));

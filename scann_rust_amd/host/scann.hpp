@@ -1175,6 +1175,111 @@ private:
     scann_hip_mutable *h_ = nullptr;
 };
 
+// ---- projections (projection/: pca.rs, random.rs, opq.rs, truncate.rs) ---------------------------------------------------
+// The arrays of a trained projection (training stays with the caller: the reference's eigen-solver and RNG are not
+// reproducible here).  matrix is [out_dim][in_dim]: column j of the reference's column-major DMatrix
+// is row j.  project() is the reference's loop verbatim; to_device() makes the scann_hip_projection whose kernel gives
+// the same bits (scann_hip.h "projections").
+enum class ProjectionKind : int { Matrix = SCANN_HIP_PROJ_MATRIX, Pca = SCANN_HIP_PROJ_PCA, Truncate = SCANN_HIP_PROJ_TRUNCATE };
+
+class DeviceProjection {
+public:
+    DeviceProjection() = default;
+    explicit DeviceProjection(scann_hip_projection *h) : h_(h) {}
+    DeviceProjection(const DeviceProjection &) = delete;
+    DeviceProjection &operator=(const DeviceProjection &) = delete;
+    DeviceProjection(DeviceProjection &&o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+    ~DeviceProjection() { if (h_) scann_hip_projection_destroy(h_); }
+    scann_hip_projection *handle() const { return h_; }
+    // n rows of in_dim floats (row_stride apart) -> n rows of out_dim floats, on the device
+    std::vector<float> project(const float *rows, size_t n, uint32_t row_stride, uint32_t row_dim) const {
+        uint32_t info[4];
+        check(scann_hip_projection_info(h_, info));
+        std::vector<float> out(n * info[2]);
+        check(scann_hip_project(h_, rows, n, row_stride, row_dim, out.data(), info[2]));
+        return out;
+    }
+private:
+    scann_hip_projection *h_ = nullptr;
+};
+
+class Projection {
+public:
+    // RandomOrthogonalProjection / GaussianRandomProjection / OpqProjection: no mean
+    static Projection matrix(size_t in_dim, size_t out_dim, std::vector<float> m) {
+        return Projection(ProjectionKind::Matrix, in_dim, out_dim, 0, std::move(m), {});
+    }
+    // a trained PcaProjection: components and mean
+    static Projection pca(size_t in_dim, size_t out_dim, std::vector<float> components, std::vector<float> mean) {
+        return Projection(ProjectionKind::Pca, in_dim, out_dim, 0, std::move(components), std::move(mean));
+    }
+    // TruncateProjection, and a PcaProjection before train(): out = in[start .. start + out_dim)
+    static Projection truncate(size_t in_dim, size_t out_dim, size_t start = 0) {
+        return Projection(ProjectionKind::Truncate, in_dim, out_dim, start, {}, {});
+    }
+    ProjectionKind kind() const { return kind_; }
+    size_t input_dim() const { return in_dim_; }
+    size_t output_dim() const { return out_dim_; }
+    size_t start() const { return start_; }
+    const std::vector<float> &matrix_rows() const { return matrix_; }
+    const std::vector<float> &mean() const { return mean_; }
+
+    // pca.rs:156-180, random.rs:82-92, opq.rs:179-194: out[j] = 0; for i ascending: out[j] += (in[i] - mean[i]) * M[(i, j)].
+    // The product and the sum are separate f32 operations (volatile: no compiler may contract them).
+    void project(const float *in, float *out) const {
+        if (kind_ == ProjectionKind::Truncate) {
+            for (size_t j = 0; j < out_dim_; ++j) out[j] = in[start_ + j];
+            return;
+        }
+        for (size_t j = 0; j < out_dim_; ++j) {
+            const float *m = matrix_.data() + j * in_dim_;
+            float acc = 0.0f;
+            for (size_t i = 0; i < in_dim_; ++i) {
+                const float x = kind_ == ProjectionKind::Pca ? in[i] - mean_[i] : in[i];
+                volatile float p = x * m[i];
+                acc = acc + p;
+            }
+            out[j] = acc;
+        }
+    }
+    std::vector<float> project(const std::vector<float> &in) const {
+        if (in.size() != in_dim_)
+            throw ScannError::invalid_argument("Input dimension " + std::to_string(in.size()) + " does not match " +
+                                               std::to_string(in_dim_));
+        std::vector<float> out(out_dim_);
+        project(in.data(), out.data());
+        return out;
+    }
+    DenseDataset project_dataset(const DenseDataset &ds) const {
+        if (ds.dimensionality() != in_dim_) throw ScannError::invalid_argument("Dataset dimensionality does not match the projection");
+        std::vector<float> flat(ds.size() * out_dim_);
+        for (size_t i = 0; i < ds.size(); ++i) project(ds.get((DatapointIndex)i), flat.data() + i * out_dim_);
+        return DenseDataset::from_flat(flat, out_dim_);
+    }
+    DeviceProjection to_device(int device = 0) const {
+        scann_hip_projection *h = nullptr;
+        check(scann_hip_projection_create(context(device), (int)kind_, (uint32_t)in_dim_, (uint32_t)out_dim_,
+                                          matrix_.empty() ? nullptr : matrix_.data(), mean_.empty() ? nullptr : mean_.data(),
+                                          (uint32_t)start_, &h));
+        return DeviceProjection(h);
+    }
+
+private:
+    Projection(ProjectionKind kind, size_t in_dim, size_t out_dim, size_t start, std::vector<float> m, std::vector<float> mean)
+        : kind_(kind), in_dim_(in_dim), out_dim_(out_dim), start_(start), matrix_(std::move(m)), mean_(std::move(mean)) {
+        if (in_dim == 0 || out_dim == 0) throw ScannError::invalid_argument("projection: in_dim and out_dim must be > 0");
+        if (kind == ProjectionKind::Truncate) {
+            if (start + out_dim > in_dim) throw ScannError::invalid_argument("projection: start + out_dim exceeds in_dim");
+        } else {
+            if (matrix_.size() != in_dim * out_dim) throw ScannError::invalid_argument("projection: matrix must hold out_dim * in_dim values");
+            if (kind == ProjectionKind::Pca && mean_.size() != in_dim) throw ScannError::invalid_argument("projection: mean must hold in_dim values");
+        }
+    }
+    ProjectionKind kind_;
+    size_t in_dim_, out_dim_, start_;
+    std::vector<float> matrix_, mean_;
+};
+
 // ---- AsymmetricHasher (hashes/hasher.rs) ---------------------------------------------------
 struct AsymmetricHasherConfig {      // hasher.rs:19-69 (default 256 x 8: byte codes; K <= 16 takes the LUT16 path)
     size_t num_codes = 256, num_subspaces = 8;
@@ -1433,7 +1538,7 @@ public:
     // without a second host copy.
     void save(const std::string &path) const {
         if (!ix_.h || !dataset_) throw ScannError::failed_precondition("Partitioner not built");
-        if (quantized_) {   // the rows live on the device only, as stored: sections rows_q / rows_q_meta
+        if (quantized_ || projected_) {   // the rows live on the device only, as stored: sections rows_q / rows_q_meta, or proj_*
             check(scann_hip_index_write_file(ix_.h, path.c_str()));
             return;
         }
@@ -1457,6 +1562,24 @@ public:
         check(scann_hip_txh_create_quantized(context(device_), &d, rows, row_format, inv_multiplier, &s.ix_.h));
         return s;
     }
+    // This searcher was built over PROJECTED rows (Projection::project_dataset): the new searcher takes queries of the
+    // original dimensionality, projects them on the device, runs this searcher's trained index (centres, codebook,
+    // codes) in the projected space and re-ranks the survivors against `original` (scann_hip_txh_create_projected).
+    TreeXHybridSearcher with_projection(const Projection &projection, const DenseDataset &original) const {
+        if (!ix_.h || !dataset_) throw ScannError::failed_precondition("Partitioner not built");
+        if (original.size() != n_) throw ScannError::invalid_argument("the original dataset must hold the indexed rows");
+        TreeXHybridSearcher s(config_, device_);
+        s.dataset_ = dataset_;
+        s.centers_ = centers_; s.codebook_ = codebook_; s.leaf_off_ = leaf_off_; s.leaf_ids_ = leaf_ids_; s.codes_ = codes_;
+        s.n_ = n_; s.dim_ = original.dimensionality();
+        s.projected_ = true;
+        scann_hip_txh_desc d = s.desc();
+        d.data = nullptr;
+        const DeviceProjection dp = projection.to_device(device_);
+        check(scann_hip_txh_create_projected(context(device_), &d, dp.handle(), original.raw_data(), original.size(),
+                                             (uint32_t)original.dimensionality(), original.stride(), &s.ix_.h));
+        return s;
+    }
     static TreeXHybridSearcher load(const std::string &path, int device = 0) {
         scann_hip_file_info info;
         check(scann_hip_index_file_info(path.c_str(), &info));
@@ -1469,7 +1592,7 @@ public:
         TreeXHybridSearcher s(c, device);
         check(scann_hip_index_load_file(context(device), path.c_str(), &s.ix_.h));
         s.n_ = info.n_rows;
-        s.dim_ = info.dim;
+        s.dim_ = scann_hip_index_dimensionality(s.ix_.h);   // (a projected file: the rows' space, not info.dim)
         s.L_ = info.num_partitions;
         return s;
     }
@@ -1505,6 +1628,7 @@ private:
     std::vector<uint32_t> leaf_off_, leaf_ids_;
     std::vector<uint8_t> codes_;
     size_t n_ = 0, dim_ = 0, L_ = 0;
+    bool projected_ = false;   // with_projection: the handle searches through a projection, dataset_ holds the projected rows
     bool quantized_ = false;   // with_quantized_rows: the handle's rows are quantized, dataset_ only names the model's rows
     detail::IndexHandle ix_;
     detail::CrowdAttach crowd_;

@@ -55,7 +55,17 @@ def arrays(path):
     the CPU checker's index view (kind 1) or (data, n, dim, stride, measure) pieces (kind 0)."""
     h, s = read(path)
     out = dict(h)
-    if "data" in s:
+    if "proj_meta" in s:   # a projected handle (hip.txh_create_projected): "data" holds the original rows at row_stride
+        kind, in_dim, out_dim, start, row_stride = (int(v) for v in s["proj_meta"][:5])
+        out["proj_meta"] = s["proj_meta"]
+        out["projection"] = dict(kind=kind, in_dim=in_dim, out_dim=out_dim, start=start, row_stride=row_stride)
+        if "proj_matrix" in s:
+            out["proj_matrix"] = s["proj_matrix"].reshape(out_dim, in_dim)
+        if "proj_mean" in s:
+            out["proj_mean"] = s["proj_mean"]
+        if "data" in s:
+            out["data"] = s["data"].reshape(h["n_rows"], row_stride)
+    elif "data" in s:
         out["data"] = s["data"].reshape(h["n_rows"], h["stride"])
     if "rows_q" in s:   # a handle over quantized rows (hip.txh_create_quantized): no "data"
         fmt = int(s["rows_q_meta"][0])

@@ -137,6 +137,73 @@ def build_txh_index(data, L, S, K=16, use_residuals=True, kmeans_iters=10,
                 codes=codes, use_residuals=bool(use_residuals))
 
 
+def pca_projection(X, out_dim, max_samples=None, seed=42):
+    """PcaProjection::train (projection/pca.rs): mean, covariance and its eigenvectors, in f64 (numpy.linalg.eigh),
+    components by descending eigenvalue, cast to f32.  Returns (matrix f32 [out_dim, in_dim], mean f32 [in_dim]), the
+    arrays of hip.Projection(PROJ_PCA, ...).  The reference's eigen-solver is not reproducible here: the
+    trained matrix is an input to the parity contract, as centres and codebooks are."""
+    X = np.ascontiguousarray(X, np.float32)
+    n, d = X.shape
+    if not 0 < out_dim <= d:
+        raise ValueError("InvalidArgument: out_dim %d must be in 1..%d" % (out_dim, d))
+    if max_samples is not None and n > max_samples:
+        sel = (synth.splitmix64(seed ^ 0x9CA, 0, max_samples) % np.uint64(n)).astype(np.int64)
+        X = X[sel]
+    X64 = X.astype(np.float64)
+    mean = X64.mean(0)
+    Xc = X64 - mean
+    cov = (Xc.T @ Xc) / max(1, X.shape[0] - 1)
+    w, V = np.linalg.eigh(cov)                  # ascending eigenvalues, orthonormal columns
+    order = np.argsort(-w, kind="stable")[:out_dim]
+    return np.ascontiguousarray(V[:, order].T, np.float32), mean.astype(np.float32)
+
+
+def random_orthogonal(in_dim, out_dim, seed):
+    """RandomOrthogonalProjection (projection/random.rs): the Q factor of a Gaussian matrix; out_dim orthonormal rows of
+    in_dim.  Returns matrix f32 [out_dim, in_dim].  (The reference's RNG stream is not reproducible: SURVEY F10.)"""
+    if not 0 < out_dim <= in_dim:
+        raise ValueError("InvalidArgument: out_dim %d must be in 1..%d" % (out_dim, in_dim))
+    G = np.random.default_rng(seed).standard_normal((in_dim, out_dim))
+    Q, R = np.linalg.qr(G)                       # in_dim x out_dim, orthonormal columns
+    Q = Q * np.sign(np.where(np.diag(R) == 0.0, 1.0, np.diag(R)))   # a unique factor: R's diagonal positive
+    return np.ascontiguousarray(Q.T, np.float32)
+
+
+def project_rows(X, kind, matrix=None, mean=None, start=0, out_dim=None):
+    """The reference's projection loop on the host (pca.rs:156-180, random.rs:82-92, opq.rs:179-194): for i ascending,
+    out[j] += (x[i] - mean[i]) * matrix[j, i], every step an f32 multiply and then an f32 add; the mean only with
+    kind == "pca"; kind == "truncate" is the window x[start : start + out_dim].  What hip.Projection computes on the
+    device, bit for bit."""
+    X = np.ascontiguousarray(X, np.float32)
+    if kind == "truncate":
+        return np.ascontiguousarray(X[:, start:start + out_dim])
+    M = np.ascontiguousarray(matrix, np.float32)
+    acc = np.zeros((X.shape[0], M.shape[0]), np.float32)
+    with np.errstate(over="ignore", invalid="ignore", under="ignore"):
+        for i in range(M.shape[1]):
+            x = X[:, i:i + 1]
+            if kind == "pca":
+                x = x - np.float32(mean[i])
+            acc = acc + x * M[:, i]
+    return acc
+
+
+def build_projected_txh_index(data, projection_arrays, L, S, project=None, **kw):
+    """The arrays of hip.txh_create_projected: `data` [n, in_dim] is projected, then build_txh_index (L > 0) or
+    build_ah_index (L == 0) runs on the projected rows.  projection_arrays: dict(kind="matrix" | "pca" | "truncate",
+    matrix=, mean=, start=, out_dim=).  project: a callable rows -> projected rows (hip.Projection(...).project) in place
+    of the host loop.  Returns build_txh_index's dict plus projected=[n, out_dim] and out_dim."""
+    data = np.ascontiguousarray(data, np.float32)
+    pa = dict(projection_arrays)
+    kind = pa.pop("kind")
+    Xp = np.ascontiguousarray(project(data) if project is not None else project_rows(data, kind, **pa), np.float32)
+    ix = build_txh_index(Xp, L, S, **kw) if L else build_ah_index(Xp, S, **{k: v for k, v in kw.items()
+                                                                           if k in ("K", "pq_iters", "seed")})
+    ix["projected"] = Xp
+    ix["out_dim"] = Xp.shape[1]
+    return ix
+
+
 def build_ah_index(data, S, K=16, pq_iters=10, seed=42):
     """AsymmetricHasher::build (hashes/hasher.rs:109-134): global codebook on the
     raw vectors, codes in datapoint order."""
