@@ -3064,10 +3064,20 @@ static int launch_partition_stage(const TxhIndexDev &ix, const TxhWork &w, hipSt
     SCANN_TRY(launch_centroid_scores(ix, w, st));
     const uint32_t n2 = next_pow2_u32(ix.L);
     // select path when P is small against L: rank-select the P-th key, sort P keys instead of L
-    const uint32_t p2 = (w.P * 4u <= n2) ? next_pow2_u32(std::max(1u, w.P)) : 0u;
+    uint32_t p2 = (w.P * 4u <= n2) ? next_pow2_u32(std::max(1u, w.P)) : 0u;
     const SelCfg lcfg = sel_cfg(ix.L);
-    const size_t lds2 = (size_t)(n2 + p2) * sizeof(uint64_t) + (size_t)lcfg.bins * 4 + (size_t)lcfg.list * 8 +
-                        48 * 8 + 64 * 4;
+    const auto lds_of = [&](uint32_t p_pow2) {
+        return (size_t)(n2 + p_pow2) * sizeof(uint64_t) + (size_t)lcfg.bins * 4 + (size_t)lcfg.list * 8 + 48 * 8 + 64 * 4;
+    };
+    // ... and while its P extra keys fit: above 8192 leaves the 16384 keys and the large tables take 156 288 bytes, and
+    // the survivors of more than 512 partitions would pass the CU's 160 KB -- those sort all the keys in place
+    // (at 64 KB or below launch() checks nothing either)
+    if (p2 && lds_of(p2) > 64 * 1024) {
+        size_t static_bytes = 0;
+        SCANN_TRY(static_lds_bytes(reinterpret_cast<const void *>(select_leaves_kernel), &static_bytes));
+        if (lds_of(p2) + static_bytes > kMaxLdsBytes) p2 = 0;
+    }
+    const size_t lds2 = lds_of(p2);
     SCANN_TRY(launch(select_leaves_kernel, dim3(w.nq), dim3(p2 && ix.L <= 4096 ? 256u : kSelectThreads), lds2, st,
                      w.cdist, ix.L, n2, w.P, p2, ix.leaf_gsize, ix.leaf_off, w.st, w.tokens, w.token_dists,
                      w.vbase, w.sbase, (const float *)nullptr, (const float *)nullptr, 0u, 0u, 0u));

@@ -225,6 +225,23 @@ def test_partition_tie_is_stable():
     assert list(tok) == [4, 0, 1, 2, 3]
 
 
+def test_partition_orders_nan_last_and_keeps_ties_by_id():
+    """sort_by_key(|d| OrderedFloat(d)) (:212): OrderedFloat's total order puts NaN above +inf and makes all NaNs equal,
+    and the sort is stable -- equal keys, NaNs and infinities among them, keep ascending partition id."""
+    centers = np.array([[np.nan], [1.0], [3e19], [0.0], [np.nan], [-3e19], [1.0]], np.float32)
+    tok, d = orc.partition(centers, [0.0], 7)      # distances: NaN, 1, +inf, +0, NaN, +inf, 1
+    assert list(tok) == [3, 1, 6, 2, 5, 0, 4]
+    assert list(d[:3]) == [0.0, 1.0, 1.0] and np.isposinf(d[3:5]).all() and np.isnan(d[5:]).all()
+    tok, d = orc.partition(centers, [0.0], 6)      # the cut falls inside the NaN tie: the lower id stays
+    assert list(tok) == [3, 1, 6, 2, 5, 0]
+    # a NaN in the query makes every distance NaN: every key ties, the tokens are 0 .. P-1
+    centers = np.random.default_rng(5).random((300, 3), dtype=np.float32)
+    tok, d = orc.partition(centers, [0.5, np.nan, 0.5], 200)
+    assert np.array_equal(tok, np.arange(200)) and np.isnan(d).all()
+    tok, d = orc.partition(centers, [0.5, 3e19, 0.5], 200)     # ... and an overflowing component makes every one +inf
+    assert np.array_equal(tok, np.arange(200)) and np.isposinf(d).all()
+
+
 # ---- LUT16 -------------------------------------------------------------------------------
 def test_lut16_batch_portable():  # src/simd/tests.rs:237-264
     lut = np.zeros((2, 16), np.uint8)
