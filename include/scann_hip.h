@@ -91,8 +91,10 @@ const char *scann_hip_last_error(void);
 const char *scann_hip_version(void);
 /* ABI guard for bindings written by hand (Rust #[repr(C)], ctypes): fills out[0..n) with
  * { sizeof(scann_hip_txh_desc), offsetof(.., distance_measure), sizeof(scann_hip_search_opts),
- *   offsetof(.., bf_exact), sizeof(scann_hip_file_info), offsetof(.., has_data) } and returns the
- * number of values defined (6).  A binding asserts these against its own layout once at start-up. */
+ *   offsetof(.., bf_exact), sizeof(scann_hip_file_info), offsetof(.., has_data),
+ *   sizeof(scann_hip_build_config), offsetof(.., distance_measure), sizeof(scann_hip_build_report),
+ *   offsetof(.., stage_ms) } and returns the number of values defined (10; the first 6 are those of earlier
+ * versions, in place).  A binding asserts these against its own layout once at start-up. */
 uint32_t scann_hip_abi_layout(uint32_t *out, uint32_t n);
 /* data_format/dataset.rs:90-96 (DenseDataset::compute_stride for f32) */
 uint32_t scann_hip_compute_stride(uint32_t dim);
@@ -1221,6 +1223,70 @@ int scann_hip_mutable_last_stage_ms(scann_hip_mutable *m, float *out_ms3);
 int scann_hip_fold_mutable(scann_hip_mutable *m, scann_hip_index **out_new_base, uint32_t *out_base_ids,
                            uint64_t capacity_rows, uint64_t *out_n);
 int scann_hip_fold_mutable_stage_ms(scann_hip_mutable *m, float *out_ms5);
+
+/* ---- device build ----------------------------------------------------------------
+ * scann_hip_txh_build: TreeXHybridSearcher::build (tree_x_hybrid/mod.rs:131-237) or, with num_partitions == 0,
+ * AsymmetricHasher::build / build_no_store (hashes/hasher.rs:109-159) in one call, from the resident rows of an f32
+ * brute-force handle.  No row, code, id list or assignment crosses to the host: the host reads back convergence
+ * words, the leaf offsets (the planner's, as in the fold) and nothing else.  `rows` is left untouched and stays the
+ * caller's; the new handle owns all its arrays (the rows are copied device to device when store_rows is set; without
+ * them exact reordering returns FailedPrecondition, as after scann_hip_txh_create with data == NULL).
+ *
+ * THE RULE, as a function of the seeds -- every array of the new handle (centres, leaf offsets, leaf ids, codebook,
+ * packed codes, rows) is bit-identical to these steps run through the public primitives:
+ *   1 partitioner   k = min(num_partitions, n); scann_hip_kmeans_init_pp(k, kmeans_seed), then scann_hip_kmeans_lloyd
+ *                   (kmeans_iterations, kmeans_convergence): centres and the assignment `leaf`.  The CSR lists hold
+ *                   ascending datapoint index inside each leaf.  The new handle has k leaves.
+ *   2 training rows in DATAPOINT order: x - centres[token(x)], token = scann_hip_bf_assign_nearest (partition(x, 1):
+ *                   sequential scalar order, lowest index on ties -- not the k-means assignment, which takes the AVX2
+ *                   order from simd_threshold dims on); the rows themselves when use_residuals == 0 or flat.
+ *                   (scann.hpp's host build() trains on the residuals in CSR order against the k-means assignment,
+ *                   another training order: its codebooks differ.)
+ *   3 codebook      per subspace s: kc = min(num_codes, n) centres from scann_hip_kmeans_init_pp(seed + s) over the
+ *                   column window, then scann_hip_kmeans_lloyd(training_iterations, convergence_threshold); codes
+ *                   kc .. num_codes - 1 repeat centre kc - 1.
+ *   4 codes         scann_hip_encode of x - centres[leaf(x)] (x itself when use_residuals == 0 or flat), stored in
+ *                   CSR row order, packed 4-bit for num_codes <= 16, bytes above.
+ *   5 finish        the second half of scann_hip_txh_create on the device arrays.
+ * batched_codebook: 1 trains all subspaces in lockstep (one pass over the training rows per seeding round and per
+ *   Lloyd iteration; a subspace that converged or reached training_iterations is frozen and skipped); 0 runs one
+ *   seeding and one Lloyd loop per subspace, as the primitives do.  Both give the same bits.  The batched kernels
+ *   take the sequential scalar order only: with dims_per_subspace >= simd_threshold (the AVX2 order), or
+ *   n * num_subspaces >= 2^31, the per-subspace route is taken whatever the flag says.
+ * REFUSED before any training launch: `rows` not an f32 brute-force handle (quantized rows: InvalidArgument), n == 0
+ *   or dim % num_subspaces != 0 (InvalidArgument), the (num_subspaces, num_codes) shapes, the leaf ceiling and the
+ *   measures scann_hip_txh_create refuses (same status), dimensions past the k-means LDS limit (dim > 5120 for a tree,
+ *   dims_per_subspace > 5120 flat: ResourceExhausted), n >= 2^31 (OutOfRange).
+ * out_report (may be NULL): the partitioner's and every subspace's iteration count and converged flag as
+ *   scann_hip_kmeans_lloyd reports them, and stage_ms, host-clock milliseconds of: partition seeding, partition Lloyd,
+ *   CSR + residuals, codebook seeding, codebook Lloyd, encode + pack, finish half. */
+typedef struct scann_hip_build_config {
+    uint32_t num_partitions;          /* 0 = AsymmetricHasher::build (flat), else TreeXHybridSearcher::build */
+    uint32_t kmeans_iterations;       /* 100  (tree_partitioner.rs:72) */
+    double   kmeans_convergence;      /* 1e-5 */
+    uint64_t kmeans_seed;             /* 42 */
+    uint32_t num_subspaces, num_codes;
+    uint32_t training_iterations;     /* 25   (CodebookConfig.max_iterations) */
+    double   convergence_threshold;   /* 1e-5 */
+    uint64_t seed;                    /* 42; subspace s trains with seed + s (codebook.rs:177-199) */
+    uint32_t simd_threshold;          /* 128  (KMeansConfig.simd_threshold) */
+    int32_t  use_residuals;           /* 1 */
+    int32_t  store_rows;              /* 1; 0 = build_no_store (hasher.rs:137-159) */
+    int32_t  batched_codebook;        /* 1; 0 = one Lloyd loop per subspace, as the primitives run it */
+    uint32_t partitions_to_search; float pre_reorder_multiplier; int32_t distance_measure;
+} scann_hip_build_config;
+
+typedef struct scann_hip_build_report {
+    uint32_t partition_iterations; int32_t partition_converged; double partition_inertia;
+    uint32_t subspace_iterations[64]; int32_t subspace_converged[64];
+    float stage_ms[7];
+} scann_hip_build_report;
+
+/* the defaults noted above, partitions_to_search 10, pre_reorder_multiplier 3 (TreeXHybridConfig), SquaredL2;
+ * num_partitions, num_subspaces and num_codes are left 0: the caller sets them */
+void scann_hip_build_config_default(scann_hip_build_config *cfg);
+int scann_hip_txh_build(scann_hip_index *rows, const scann_hip_build_config *cfg, scann_hip_index **out_index,
+                        scann_hip_build_report *out_report);
 
 /* ---- introspection ------------------------------------------------------------- */
 uint64_t scann_hip_index_size(const scann_hip_index *index);          /* Searcher::dataset_size */

@@ -16,6 +16,7 @@
 
 #include "allow.h"
 #include "bf.h"
+#include "build.h"
 #include "comm.h"
 #include "common.h"
 #include "crowd.h"
@@ -415,6 +416,64 @@ int scann::index_fold_txh(const scann_hip_index *old, DevBuf &rows, DevBuf &code
     return SCANN_HIP_OK;
 }
 
+// The handle of scann_hip_txh_build (build.h): the arrays build_txh_device wrote, a device copy of the source's rows
+// when they are stored, then the second half of every tree / hasher create.
+int scann::index_build_txh(const scann_hip_index *src, const scann_hip_build_config &cfg, BuildParts &parts,
+                           scann_hip_index **out, scann_hip_build_report *rep) {
+    if (!src || !out || src->kind != KIND_BF) return fail(SCANN_HIP_INVALID_ARGUMENT, "not a brute-force index");
+    const auto t0 = std::chrono::steady_clock::now();
+    const bool tree = cfg.num_partitions != 0;
+    const uint64_t n = src->bf.n;
+    const uint32_t L = parts.L;
+    if (parts.off.size() != (size_t)L + 1) return fail(SCANN_HIP_INTERNAL, "build: leaf offsets of the wrong length");
+    SCANN_TRY(set_device(src->ctx));
+    auto *ix = new scann_hip_index();
+    ix->ctx = src->ctx;
+    ix->kind = KIND_TXH;
+    auto bail = [&](int s) {
+        scann_hip_index_destroy(ix);
+        return s;
+    };
+    int s = index_common_init(ix);
+    if (s != SCANN_HIP_OK) return bail(s);
+    if (cfg.store_rows) {
+        const size_t bytes = (size_t)n * src->bf.stride * 4;
+        if ((s = ix->d_rows.ensure(bytes)) != SCANN_HIP_OK) return bail(s);
+        if (hipMemcpy(ix->d_rows.p, src->bf.rows, bytes, hipMemcpyDeviceToDevice) != hipSuccess)
+            return bail(fail(SCANN_HIP_INTERNAL, "build: row copy failed"));
+    }
+    ix->d_codes.take(parts.codes);
+    ix->d_leaf_off.take(parts.leaf_off);
+    ix->d_codebook.take(parts.codebook);
+    if (tree) {
+        ix->d_leaf_ids.take(parts.leaf_ids);
+        ix->d_centers.take(parts.centers);
+    }
+    scann_hip_txh_desc d;
+    std::memset(&d, 0, sizeof(d));
+    d.n_rows = d.n_local = n;
+    d.dim = src->bf.dim;
+    d.stride = src->bf.stride;
+    d.num_partitions = tree ? L : 0u;
+    d.num_subspaces = cfg.num_subspaces;
+    d.num_codes = cfg.num_codes;
+    d.dims_per_subspace = src->bf.dim / cfg.num_subspaces;
+    d.distance_measure = cfg.distance_measure;
+    d.codes_packed4 = cfg.num_codes <= 16 ? 1 : 0;
+    d.use_residuals = (tree && cfg.use_residuals) ? 1 : 0;
+    d.partitions_to_search = tree ? cfg.partitions_to_search : 0u;
+    d.pre_reorder_multiplier = cfg.pre_reorder_multiplier;
+    d.data = cfg.store_rows ? ix->d_rows.as<float>() : nullptr;   // (txh_finish asks only whether rows are stored)
+    ix->n_rows = cfg.store_rows ? n : 0;
+    std::vector<uint32_t> gsz(L);
+    for (uint32_t l = 0; l < L; ++l) gsz[l] = parts.off[l + 1] - parts.off[l];
+    if ((s = upload(ix->d_leaf_gsize, gsz.data(), (size_t)L * 4)) != SCANN_HIP_OK) return bail(s);
+    if ((s = txh_finish(ix, &d, parts.off)) != SCANN_HIP_OK) return bail(s);
+    if (rep) rep->stage_ms[6] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    *out = ix;
+    return SCANN_HIP_OK;
+}
+
 int scann::index_download(const scann_hip_index *ix, IndexHostArrays *o, bool with_rows) {
     if (!ix || !o) return fail(SCANN_HIP_INVALID_ARGUMENT, "index is null");
     SCANN_TRY(set_device(ix->ctx));
@@ -485,11 +544,13 @@ const char *scann_hip_last_error(void) { return g_last_error.c_str(); }
 const char *scann_hip_version(void) { return "scann_hip 0.1.0 (gfx950)"; }
 
 uint32_t scann_hip_abi_layout(uint32_t *out, uint32_t n) {
-    const uint32_t v[6] = {(uint32_t)sizeof(scann_hip_txh_desc), (uint32_t)offsetof(scann_hip_txh_desc, distance_measure),
-                           (uint32_t)sizeof(scann_hip_search_opts), (uint32_t)offsetof(scann_hip_search_opts, bf_exact),
-                           (uint32_t)sizeof(scann_hip_file_info), (uint32_t)offsetof(scann_hip_file_info, has_data)};
-    for (uint32_t i = 0; i < 6 && i < n && out; ++i) out[i] = v[i];
-    return 6;
+    const uint32_t v[10] = {(uint32_t)sizeof(scann_hip_txh_desc), (uint32_t)offsetof(scann_hip_txh_desc, distance_measure),
+                            (uint32_t)sizeof(scann_hip_search_opts), (uint32_t)offsetof(scann_hip_search_opts, bf_exact),
+                            (uint32_t)sizeof(scann_hip_file_info), (uint32_t)offsetof(scann_hip_file_info, has_data),
+                            (uint32_t)sizeof(scann_hip_build_config), (uint32_t)offsetof(scann_hip_build_config, distance_measure),
+                            (uint32_t)sizeof(scann_hip_build_report), (uint32_t)offsetof(scann_hip_build_report, stage_ms)};
+    for (uint32_t i = 0; i < 10 && i < n && out; ++i) out[i] = v[i];
+    return 10;
 }
 
 uint32_t scann_hip_compute_stride(uint32_t dim) {
@@ -3051,6 +3112,38 @@ int scann_hip_kmeans_init_pp(scann_hip_index *ix, uint32_t col_offset, uint32_t 
     std::lock_guard<std::mutex> lock(ix->mu);
     SCANN_TRY(set_device(ix->ctx));
     return bf_kmeans_init_pp_host(ix->bf, col_offset, sub_dim, k, seed, simd_threshold, centers_out, ix->stream);
+}
+
+void scann_hip_build_config_default(scann_hip_build_config *c) {
+    if (!c) return;
+    std::memset(c, 0, sizeof(*c));
+    c->kmeans_iterations = 100;         // tree_partitioner.rs:72
+    c->kmeans_convergence = 1e-5;
+    c->kmeans_seed = 42;
+    c->training_iterations = 25;        // CodebookConfig.max_iterations
+    c->convergence_threshold = 1e-5;
+    c->seed = 42;
+    c->simd_threshold = 128;            // KMeansConfig.simd_threshold
+    c->use_residuals = 1;
+    c->store_rows = 1;
+    c->batched_codebook = 1;
+    c->partitions_to_search = 10;
+    c->pre_reorder_multiplier = 3.0f;
+    c->distance_measure = SCANN_HIP_SQUARED_L2;
+}
+
+int scann_hip_txh_build(scann_hip_index *rows, const scann_hip_build_config *cfg, scann_hip_index **out_index,
+                        scann_hip_build_report *out_report) {
+    if (!rows || !cfg || !out_index) return fail(SCANN_HIP_INVALID_ARGUMENT, "null rows/config/out_index");
+    *out_index = nullptr;
+    if (out_report) std::memset(out_report, 0, sizeof(*out_report));
+    if (rows->kind != KIND_BF) return fail(SCANN_HIP_INVALID_ARGUMENT, "not a brute-force index");
+    std::lock_guard<std::mutex> lock(rows->mu);
+    SCANN_TRY(set_device(rows->ctx));
+    SCANN_TRY(build_check(rows->bf, *cfg));   // every refusal, before the first training launch
+    BuildParts parts;
+    SCANN_TRY(build_txh_device(rows->bf, *cfg, rows->stream, &parts, out_report));
+    return index_build_txh(rows, *cfg, parts, out_index, out_report);
 }
 
 int scann_hip_kmeans_lloyd(scann_hip_index *ix, uint32_t col_offset, uint32_t sub_dim, float *centers,

@@ -107,4 +107,45 @@ int bf_kmeans_lloyd_host(const BfIndexDev &ix, uint32_t col_offset, uint32_t sub
                          double *out_inertia, uint32_t *out_iterations, int *out_converged,
                          hipStream_t stream);
 
+// ---- the same two with centres and assignment resident on the device (the host forms above wrap them; build.hip) ----
+// Grow-only scratch of the cores: one object serves any number of calls, so a loop over subspaces allocates once.
+struct KmScratch {
+    DevBuf dmin, dpart, dtotal, dpicks, ddist, dkeys, dsorted, dtmp, doff, dgrows;
+};
+// d_centers_out [k][sub_dim]; complete on return
+int bf_kmeans_init_pp_device(const BfIndexDev &ix, uint32_t col_offset, uint32_t sub_dim, uint32_t k, uint64_t seed,
+                             uint32_t simd_threshold, float *d_centers_out, KmScratch &sc, hipStream_t stream);
+// d_centers [k][sub_dim] and d_assign [n] updated in place.  final_assign false: no assignment of the final centres
+// (kmeans.rs:248-255) -- d_assign is then the one the last update was made from and *out_inertia the last one computed.
+int bf_kmeans_lloyd_device(const BfIndexDev &ix, uint32_t col_offset, uint32_t sub_dim, float *d_centers, uint32_t k,
+                           uint32_t max_iterations, double convergence_threshold, uint32_t simd_threshold,
+                           uint32_t *d_assign, bool final_assign, KmScratch &sc, double *out_inertia,
+                           uint32_t *out_iterations, int *out_converged, hipStream_t stream);
+// sc.dsorted [n]: the keys (cluster << 32 | index) of an assignment in ascending order, i.e. every cluster's members in
+// ascending datapoint index; sc.doff [k + 1]: where each cluster starts.  Enqueue only.
+int bf_kmeans_csr_device(const uint32_t *d_assign, uint64_t n, uint32_t k, KmScratch &sc, hipStream_t stream);
+
+// ---- the reductions and the centre update of the cores, launched once for a batch of lists / column windows ----
+// (the kernels are the primitives' own, so a batched codebook takes the same sums in the same trees)
+uint64_t km_seed_stream_next(uint64_t &state);   // splitmix64, the seeding's random stream
+bool km_tree_sum_is_exact(double total, uint32_t min_pos_bits);
+// list y of `lists`: d_vals + y * n -> d_partials + y * ceil(n / 256), smallest positive term into
+// d_min_pos[y * min_pos_stride] (atomicMin; null: none); skipped where d_skip[y * skip_stride] != 0
+int km_sums_batched(const float *d_vals, uint64_t n, uint32_t lists, double *d_partials, uint32_t *d_min_pos,
+                    uint32_t min_pos_stride, const uint32_t *d_skip, uint32_t skip_stride, hipStream_t stream);
+// list y: partials -> d_totals[y * total_stride]; with d_picks, the k-means++ pick over d_min_d + y * n with the draw
+// (d_u_tab[y], d_fallback_tab[y]) into d_picks[y * pick_stride]
+int km_totals_batched(const double *d_partials, uint64_t n, uint32_t lists, const float *d_min_d, const double *d_u_tab,
+                      const uint32_t *d_fallback_tab, double *d_totals, uint32_t total_stride, uint32_t *d_picks,
+                      uint32_t pick_stride, hipStream_t stream);
+// list y where d_need[y * need_stride] != 0: the sum in datapoint order into d_totals[y * total_stride]
+int km_sequential_sums_batched(const float *d_vals, uint64_t n, uint32_t lists, double *d_totals, uint32_t total_stride,
+                               const uint32_t *d_need, uint32_t need_stride, hipStream_t stream);
+// window y of `windows` (columns y * window0.dim .. of window0's rows): cluster c's members are the positions
+// d_offsets[y * k_stride + c] .. [+ 1] of d_grows ([position][window0.dim], member order); centres into
+// d_centers[(y * k_stride + c) * dim]; skipped where d_skip[y * skip_stride] != 0
+int km_update_batched(const BfIndexDev &window0, const float *d_grows, const uint32_t *d_offsets, float *d_centers,
+                      uint32_t k, uint32_t k_stride, uint32_t windows, const uint32_t *d_skip, uint32_t skip_stride,
+                      hipStream_t stream);
+
 }  // namespace scann

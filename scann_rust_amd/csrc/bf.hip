@@ -2361,10 +2361,18 @@ int bf_assign_nearest_host(const BfIndexDev &ix, const float *centers, uint32_t 
 //   update_centers :382-414    f64 sums in ascending datapoint order per (cluster, dim), mean
 //                              cast to f32; empty cluster c takes row c % n
 // =====================================================================================
+// blockIdx.y = the list (one per subspace in the batched codebook training, build.hip; the primitives launch one):
+// list y reads v + y * n, writes partials + y * gridDim.x and min_pos_bits + y * min_pos_stride, and is skipped when
+// skip[y * skip_stride] is set.
 __global__ __launch_bounds__(256) void km_sum_f64_kernel(const float *__restrict__ v, uint64_t n,
                                                          double *__restrict__ partials,
-                                                         uint32_t *__restrict__ min_pos_bits) {
+                                                         uint32_t *__restrict__ min_pos_bits, uint32_t min_pos_stride,
+                                                         const uint32_t *__restrict__ skip, uint32_t skip_stride) {
     __shared__ double s[256];
+    if (skip && skip[blockIdx.y * skip_stride]) return;   // (block-uniform)
+    v += (uint64_t)blockIdx.y * n;
+    partials += (size_t)blockIdx.y * gridDim.x;
+    if (min_pos_bits) min_pos_bits += (size_t)blockIdx.y * min_pos_stride;
     const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     const float x = i < n ? v[i] : 0.0f;
     s[threadIdx.x] = (double)x;
@@ -2386,11 +2394,18 @@ __global__ __launch_bounds__(256) void km_sum_f64_kernel(const float *__restrict
 // inertia as the reference computes it (kmeans.rs:376): f64 += (f64)min_dist in datapoint order, one
 // dependent chain.  Only used when the tree sum above is not provably exact.  One block: waves 1-3
 // stage the next 4096 values in LDS while lane 0 adds the current ones.
+// blockIdx.x = the list: reads v + x * n, writes total_out[x * out_stride]; runs only where need[x * need_stride] is set
+// (need null: always).
 __global__ __launch_bounds__(256) void km_sum_f64_sequential_kernel(const float *__restrict__ v, uint64_t n,
-                                                                    double *__restrict__ total_out) {
+                                                                    double *__restrict__ total_out, uint32_t out_stride,
+                                                                    const uint32_t *__restrict__ need,
+                                                                    uint32_t need_stride) {
     constexpr uint32_t T = 4096;
     __shared__ float s_x[2][T];
     const uint32_t tid = threadIdx.x;
+    if (need && !need[blockIdx.x * need_stride]) return;   // (block-uniform)
+    v += (uint64_t)blockIdx.x * n;
+    total_out += (size_t)blockIdx.x * out_stride;
     auto stage = [&](uint64_t i0, uint32_t buf, uint32_t t0, uint32_t nt) {
         const uint32_t cnt = (uint32_t)min((uint64_t)T, n - i0);
         for (uint32_t f = t0; f < cnt; f += nt) s_x[buf][f] = v[i0 + f];
@@ -2413,17 +2428,29 @@ __global__ __launch_bounds__(256) void km_sum_f64_sequential_kernel(const float 
 
 // partials -> total (fixed order: per-thread chunks, then the 256 chunk sums in order); optional
 // k-means++ pick: first i with cumulative min_d >= u * total (kmeans.rs:318-331), or `fallback`
-// if total == 0.  One block of 256 threads.
+// if total == 0.  One block of 256 threads per list (blockIdx.x; the primitives launch one): list x reads
+// partials + x * nb and min_d + x * n, draws (u_tab[x], fallback_tab[x]) when the tables are given, and writes
+// total_out[x * total_stride] and pick_out[x * pick_stride].
 __global__ __launch_bounds__(256) void km_total_pick_kernel(const double *__restrict__ partials, uint32_t nb,
                                                             const float *__restrict__ min_d, uint64_t n,
                                                             double u, uint32_t fallback,
-                                                            double *__restrict__ total_out,
-                                                            uint32_t *__restrict__ pick_out) {
+                                                            const double *__restrict__ u_tab,
+                                                            const uint32_t *__restrict__ fallback_tab,
+                                                            double *__restrict__ total_out, uint32_t total_stride,
+                                                            uint32_t *__restrict__ pick_out, uint32_t pick_stride) {
     __shared__ double s_chunk[256];
     __shared__ float s_vals[256];
     __shared__ uint32_t s_blk;
     __shared__ double s_cum;
     const uint32_t t = threadIdx.x;
+    partials += (size_t)blockIdx.x * nb;
+    if (min_d) min_d += (uint64_t)blockIdx.x * n;
+    total_out += (size_t)blockIdx.x * total_stride;
+    if (pick_out) pick_out += (size_t)blockIdx.x * pick_stride;
+    if (u_tab) {
+        u = u_tab[blockIdx.x];
+        fallback = fallback_tab[blockIdx.x];
+    }
     const uint32_t per = (nb + 255u) / 256u;
     const uint32_t b0 = min(nb, t * per), b1 = min(nb, b0 + per);
     double mine = 0.0;
@@ -2560,8 +2587,16 @@ __global__ void km_gather_sorted_kernel(BfIndexDev ix, const uint64_t *__restric
 constexpr uint32_t kKmTileFloats = 8192;   // 32 KB of staged row values
 __global__ __launch_bounds__(256) void km_update_kernel(BfIndexDev ix, const float *__restrict__ grows,
                                                         const uint32_t *__restrict__ offsets,
-                                                        float *__restrict__ centers) {
+                                                        float *__restrict__ centers, uint32_t k_stride,
+                                                        const uint32_t *__restrict__ skip, uint32_t skip_stride) {
+    // blockIdx.y = the column window (one per subspace in the batched codebook training; the primitives launch one):
+    // window y reads the columns from y * dim on, offsets + y * k_stride (positions into `grows` as a whole) and writes
+    // centers + y * k_stride * dim; it is skipped when skip[y * skip_stride] is set.
     __shared__ float s_x[kKmTileFloats];
+    if (skip && skip[blockIdx.y * skip_stride]) return;   // (block-uniform)
+    ix.rows += (size_t)blockIdx.y * ix.dim;
+    offsets += (size_t)blockIdx.y * k_stride;
+    centers += (size_t)blockIdx.y * k_stride * ix.dim;
     const uint32_t c = blockIdx.x, tid = threadIdx.x, dim = ix.dim;
     const uint32_t b = offsets[c], e = offsets[c + 1];
     if (e == b) {   // empty cluster: data[c % n]  (kmeans.rs:405-408)
@@ -2643,97 +2678,154 @@ static int km_launch_assign(const BfIndexDev &v, const float *d_centers, uint32_
     return SCANN_HIP_OK;
 }
 
-int bf_kmeans_init_pp_host(const BfIndexDev &ix, uint32_t col_offset, uint32_t sub_dim, uint32_t k,
-                           uint64_t seed, uint32_t simd_threshold, float *centers_out, hipStream_t st) {
+uint64_t km_seed_stream_next(uint64_t &s) { return km_splitmix(s); }
+
+// ---- batched launches of the kernels above (build.hip: every subspace of a codebook in one launch) ----
+int km_sums_batched(const float *d_vals, uint64_t n, uint32_t lists, double *d_partials, uint32_t *d_min_pos,
+                    uint32_t min_pos_stride, const uint32_t *d_skip, uint32_t skip_stride, hipStream_t st) {
+    const uint32_t nb = (uint32_t)ceil_div_u64(n, 256);
+    return launch(km_sum_f64_kernel, dim3(nb, lists), dim3(256), 0, st, d_vals, n, d_partials, d_min_pos, min_pos_stride,
+                  d_skip, skip_stride);
+}
+
+int km_totals_batched(const double *d_partials, uint64_t n, uint32_t lists, const float *d_min_d, const double *d_u_tab,
+                      const uint32_t *d_fallback_tab, double *d_totals, uint32_t total_stride, uint32_t *d_picks,
+                      uint32_t pick_stride, hipStream_t st) {
+    const uint32_t nb = (uint32_t)ceil_div_u64(n, 256);
+    return launch(km_total_pick_kernel, dim3(lists), dim3(256), 0, st, d_partials, nb, d_min_d, n, 0.0, 0u, d_u_tab,
+                  d_fallback_tab, d_totals, total_stride, d_picks, pick_stride);
+}
+
+int km_sequential_sums_batched(const float *d_vals, uint64_t n, uint32_t lists, double *d_totals, uint32_t total_stride,
+                               const uint32_t *d_need, uint32_t need_stride, hipStream_t st) {
+    return launch(km_sum_f64_sequential_kernel, dim3(lists), dim3(256), 0, st, d_vals, n, d_totals, total_stride, d_need,
+                  need_stride);
+}
+
+int km_update_batched(const BfIndexDev &window0, const float *d_grows, const uint32_t *d_offsets, float *d_centers,
+                      uint32_t k, uint32_t k_stride, uint32_t windows, const uint32_t *d_skip, uint32_t skip_stride,
+                      hipStream_t st) {
+    return launch(km_update_kernel, dim3(k, windows), dim3(256), 0, st, window0, d_grows, d_offsets, d_centers, k_stride,
+                  d_skip, skip_stride);
+}
+
+// The test of bf_kmeans_lloyd_device's inertia (below), for one list: every term is a non-negative multiple of
+// g = ulp(smallest positive term); if total <= 2^53 * g every partial sum of every order is exactly representable, so
+// the tree sum IS the sum in datapoint order.
+bool km_tree_sum_is_exact(double total, uint32_t min_pos_bits) {
+    if (min_pos_bits == 0xFFFFFFFFu) return true;   // all terms are zero
+    if (!(total == total && total < INFINITY)) return false;
+    float mp;
+    std::memcpy(&mp, &min_pos_bits, 4);
+    int e = 0;
+    (void)std::frexp(mp, &e);                    // mp = f * 2^e, f in [0.5, 1)
+    const int ge = std::max(e - 24, -149);       // ulp exponent (denormals: 2^-149)
+    return total <= std::ldexp(1.0, ge + 53);
+}
+
+// The seeding with everything on the device: d_centers_out [k][sub_dim], complete on return.
+int bf_kmeans_init_pp_device(const BfIndexDev &ix, uint32_t col_offset, uint32_t sub_dim, uint32_t k, uint64_t seed,
+                             uint32_t simd_threshold, float *d_centers_out, KmScratch &sc, hipStream_t st) {
     const int avx = sub_dim >= simd_threshold ? 1 : 0;   // kmeans.rs:419-431
     const BfIndexDev v = km_view(ix, col_offset, sub_dim);
     const uint64_t n = v.n;
     if (n == 0 || k == 0) return fail(SCANN_HIP_INVALID_ARGUMENT, "empty dataset / no clusters");
     const uint32_t nb = (uint32_t)ceil_div_u64(n, 256);
-    DevBuf dmin, dpart, dtotal, dpicks, dcent;
-    SCANN_TRY(dmin.ensure(n * 4));
-    SCANN_TRY(dpart.ensure((size_t)nb * 8));
-    SCANN_TRY(dtotal.ensure(8));
-    SCANN_TRY(dpicks.ensure((size_t)k * 4));
-    SCANN_TRY(dcent.ensure((size_t)k * sub_dim * 4));
+    SCANN_TRY(sc.dmin.ensure(n * 4));
+    SCANN_TRY(sc.dpart.ensure((size_t)nb * 8));
+    SCANN_TRY(sc.dtotal.ensure(16));
+    SCANN_TRY(sc.dpicks.ensure((size_t)k * 4));
     uint64_t s = seed;
     const uint32_t first = (uint32_t)(km_splitmix(s) % n);   // kmeans.rs:305-306
-    SCANN_HIP_CHECK(hipMemcpyAsync(dpicks.p, &first, 4, hipMemcpyHostToDevice, st));
+    SCANN_HIP_CHECK(hipMemcpyAsync(sc.dpicks.p, &first, 4, hipMemcpyHostToDevice, st));
     for (uint32_t c = 1; c <= k; ++c) {
-        uint32_t *sel = dpicks.as<uint32_t>() + (c - 1);
+        uint32_t *sel = sc.dpicks.as<uint32_t>() + (c - 1);
         SCANN_TRY(launch(km_mind_update_kernel, dim3(nb), dim3(256), 0, st, v, sel, c == 1 ? 1 : 0, avx,
-                         dmin.as<float>()));
+                         sc.dmin.as<float>()));
         if (c == k) break;
-        SCANN_TRY(launch(km_sum_f64_kernel, dim3(nb), dim3(256), 0, st, dmin.as<float>(), n,
-                         dpart.as<double>(), (uint32_t *)nullptr));
+        SCANN_TRY(launch(km_sum_f64_kernel, dim3(nb), dim3(256), 0, st, sc.dmin.as<float>(), n,
+                         sc.dpart.as<double>(), (uint32_t *)nullptr, 0u, (const uint32_t *)nullptr, 0u));
         const double u = (double)(km_splitmix(s) >> 11) * (1.0 / 9007199254740992.0);
         const uint32_t fallback = (uint32_t)(km_splitmix(s) % n);
-        SCANN_TRY(launch(km_total_pick_kernel, dim3(1), dim3(256), 0, st, dpart.as<double>(), nb,
-                         dmin.as<float>(), n, u, fallback, dtotal.as<double>(), dpicks.as<uint32_t>() + c));
+        SCANN_TRY(launch(km_total_pick_kernel, dim3(1), dim3(256), 0, st, sc.dpart.as<double>(), nb,
+                         sc.dmin.as<float>(), n, u, fallback, (const double *)nullptr, (const uint32_t *)nullptr,
+                         sc.dtotal.as<double>(), 0u, sc.dpicks.as<uint32_t>() + c, 0u));
     }
     SCANN_TRY(launch(km_gather_rows_kernel, dim3(ceil_div_u32(k * sub_dim, 256)), dim3(256), 0, st, v,
-                     dpicks.as<uint32_t>(), k, dcent.as<float>()));
+                     sc.dpicks.as<uint32_t>(), k, d_centers_out));
+    SCANN_HIP_CHECK(hipStreamSynchronize(st));   // (the first pick was uploaded from this frame)
+    return SCANN_HIP_OK;
+}
+
+int bf_kmeans_init_pp_host(const BfIndexDev &ix, uint32_t col_offset, uint32_t sub_dim, uint32_t k,
+                           uint64_t seed, uint32_t simd_threshold, float *centers_out, hipStream_t st) {
+    if (ix.n == 0 || k == 0) return fail(SCANN_HIP_INVALID_ARGUMENT, "empty dataset / no clusters");
+    KmScratch sc;
+    DevBuf dcent;
+    SCANN_TRY(dcent.ensure((size_t)k * sub_dim * 4));
+    SCANN_TRY(bf_kmeans_init_pp_device(ix, col_offset, sub_dim, k, seed, simd_threshold, dcent.as<float>(), sc, st));
     SCANN_HIP_CHECK(hipMemcpyAsync(centers_out, dcent.p, (size_t)k * sub_dim * 4, hipMemcpyDeviceToHost, st));
     SCANN_HIP_CHECK(hipStreamSynchronize(st));
     return SCANN_HIP_OK;
 }
 
-int bf_kmeans_lloyd_host(const BfIndexDev &ix, uint32_t col_offset, uint32_t sub_dim, float *centers,
-                         uint32_t k, uint32_t max_iterations, double convergence_threshold,
-                         uint32_t simd_threshold, uint32_t *out_assign, uint32_t *out_sizes, double *out_inertia,
-                         uint32_t *out_iterations, int *out_converged, hipStream_t st) {
+// keys (cluster << 32 | index) of an assignment, radix-sorted into sc.dsorted: every cluster's members in ascending
+// datapoint index; sc.doff [k + 1] = where each cluster starts.  Enqueue only.
+int bf_kmeans_csr_device(const uint32_t *d_assign, uint64_t n, uint32_t k, KmScratch &sc, hipStream_t st) {
+    const uint32_t nb = (uint32_t)ceil_div_u64(n, 256);
+    SCANN_TRY(sc.dkeys.ensure(n * 8));
+    SCANN_TRY(sc.dsorted.ensure(n * 8));
+    SCANN_TRY(sc.doff.ensure((size_t)(k + 1) * 4));
+    size_t tmp_bytes = 0;
+    SCANN_HIP_CHECK(hipcub::DeviceRadixSort::SortKeys(nullptr, tmp_bytes, sc.dkeys.as<uint64_t>(),
+                                                      sc.dsorted.as<uint64_t>(), (int)n, 0, 64, st));
+    SCANN_TRY(sc.dtmp.ensure(tmp_bytes));
+    tmp_bytes = sc.dtmp.bytes;
+    int key_bits = 33;   // 32 index bits + the bits of the cluster id
+    while (key_bits < 64 && (1ull << (key_bits - 32)) < k) ++key_bits;
+    SCANN_TRY(launch(km_make_keys_kernel, dim3(nb), dim3(256), 0, st, d_assign, n, sc.dkeys.as<uint64_t>()));
+    SCANN_HIP_CHECK(hipcub::DeviceRadixSort::SortKeys(sc.dtmp.p, tmp_bytes, sc.dkeys.as<uint64_t>(),
+                                                      sc.dsorted.as<uint64_t>(), (int)n, 0, key_bits, st));
+    SCANN_TRY(launch(km_offsets_kernel, dim3(ceil_div_u32(k + 1, 256)), dim3(256), 0, st, sc.dsorted.as<uint64_t>(), n, k,
+                     sc.doff.as<uint32_t>()));
+    return SCANN_HIP_OK;
+}
+
+// The Lloyd loop with centres [k][sub_dim] and the assignment [n] on the device, both updated in place.
+// final_assign: the assignment (and inertia) of the final centres (kmeans.rs:248-255); without it d_assign holds the
+// assignment the last update was made from, which is all a codebook needs (only the centres are kept).
+int bf_kmeans_lloyd_device(const BfIndexDev &ix, uint32_t col_offset, uint32_t sub_dim, float *d_centers, uint32_t k,
+                           uint32_t max_iterations, double convergence_threshold, uint32_t simd_threshold,
+                           uint32_t *d_assign, bool final_assign, KmScratch &sc, double *out_inertia,
+                           uint32_t *out_iterations, int *out_converged, hipStream_t st) {
     const BfIndexDev v = km_view(ix, col_offset, sub_dim);
     const bool avx = sub_dim >= simd_threshold;   // kmeans.rs:419-431
     const uint64_t n = v.n;
     if (n == 0 || k == 0) return fail(SCANN_HIP_INVALID_ARGUMENT, "Cannot cluster empty dataset");
     const uint32_t nb = (uint32_t)ceil_div_u64(n, 256);
-    DevBuf dcent, dassign, ddist, dpart, dtotal, dkeys, dsorted, dtmp, doff, dgrows;
-    SCANN_TRY(upload(dcent, centers, (size_t)k * sub_dim * 4));
-    SCANN_TRY(dassign.ensure(n * 4));
-    SCANN_TRY(ddist.ensure(n * 4));
-    SCANN_TRY(dpart.ensure((size_t)nb * 8));
-    SCANN_TRY(dtotal.ensure(16));
-    SCANN_TRY(dkeys.ensure(n * 8));
-    SCANN_TRY(dsorted.ensure(n * 8));
-    SCANN_TRY(doff.ensure((size_t)(k + 1) * 4));
-    SCANN_TRY(dgrows.ensure(n * sub_dim * 4));
-    size_t tmp_bytes = 0;
-    SCANN_HIP_CHECK(hipcub::DeviceRadixSort::SortKeys(nullptr, tmp_bytes, dkeys.as<uint64_t>(),
-                                                      dsorted.as<uint64_t>(), (int)n, 0, 64, st));
-    SCANN_TRY(dtmp.ensure(tmp_bytes));
-    int key_bits = 33;   // 32 index bits + the bits of the cluster id
-    while (key_bits < 64 && (1ull << (key_bits - 32)) < k) ++key_bits;
+    SCANN_TRY(sc.ddist.ensure(n * 4));
+    SCANN_TRY(sc.dpart.ensure((size_t)nb * 8));
+    SCANN_TRY(sc.dtotal.ensure(16));
+    SCANN_TRY(sc.dgrows.ensure(n * sub_dim * 4));
 
     // dtotal: [0] f64 total, [1] (as u32) bit pattern of the smallest positive term
     auto assign_and_inertia = [&](double *inertia) -> int {
-        SCANN_TRY(km_launch_assign(v, dcent.as<float>(), k, dassign.as<uint32_t>(), ddist.as<float>(), avx, st));
-        uint32_t *d_minpos = reinterpret_cast<uint32_t *>(dtotal.as<double>() + 1);
+        SCANN_TRY(km_launch_assign(v, d_centers, k, d_assign, sc.ddist.as<float>(), avx, st));
+        uint32_t *d_minpos = reinterpret_cast<uint32_t *>(sc.dtotal.as<double>() + 1);
         SCANN_HIP_CHECK(hipMemsetAsync(d_minpos, 0xFF, 4, st));
-        SCANN_TRY(launch(km_sum_f64_kernel, dim3(nb), dim3(256), 0, st, ddist.as<float>(), n,
-                         dpart.as<double>(), d_minpos));
-        SCANN_TRY(launch(km_total_pick_kernel, dim3(1), dim3(256), 0, st, dpart.as<double>(), nb,
-                         (const float *)nullptr, n, 0.0, 0u, dtotal.as<double>(), (uint32_t *)nullptr));
+        SCANN_TRY(launch(km_sum_f64_kernel, dim3(nb), dim3(256), 0, st, sc.ddist.as<float>(), n,
+                         sc.dpart.as<double>(), d_minpos, 0u, (const uint32_t *)nullptr, 0u));
+        SCANN_TRY(launch(km_total_pick_kernel, dim3(1), dim3(256), 0, st, sc.dpart.as<double>(), nb,
+                         (const float *)nullptr, n, 0.0, 0u, (const double *)nullptr, (const uint32_t *)nullptr,
+                         sc.dtotal.as<double>(), 0u, (uint32_t *)nullptr, 0u));
         struct { double total; uint32_t minpos; uint32_t pad; } h;
-        SCANN_HIP_CHECK(hipMemcpyAsync(&h, dtotal.p, 16, hipMemcpyDeviceToHost, st));
+        SCANN_HIP_CHECK(hipMemcpyAsync(&h, sc.dtotal.p, 16, hipMemcpyDeviceToHost, st));
         SCANN_HIP_CHECK(hipStreamSynchronize(st));
-        // The reference adds the terms in datapoint order (kmeans.rs:376).  Every term is a
-        // non-negative multiple of g = ulp(smallest positive term); if total <= 2^53 * g every
-        // partial sum of every order is exactly representable, so the tree sum IS that sum.
-        bool exact = false;
-        if (h.minpos == 0xFFFFFFFFu) {
-            exact = true;   // all terms are zero
-        } else if (h.total == h.total && h.total < INFINITY) {
-            float mp;
-            std::memcpy(&mp, &h.minpos, 4);
-            int e = 0;
-            (void)std::frexp(mp, &e);                    // mp = f * 2^e, f in [0.5, 1)
-            const int ge = std::max(e - 24, -149);       // ulp exponent (denormals: 2^-149)
-            exact = h.total <= std::ldexp(1.0, ge + 53);
-        }
-        if (!exact) {
-            SCANN_TRY(launch(km_sum_f64_sequential_kernel, dim3(1), dim3(256), 0, st, ddist.as<float>(), n,
-                             dtotal.as<double>()));
-            SCANN_HIP_CHECK(hipMemcpyAsync(&h.total, dtotal.p, 8, hipMemcpyDeviceToHost, st));
+        // The reference adds the terms in datapoint order (kmeans.rs:376); the tree sum stands when it is that sum.
+        if (!km_tree_sum_is_exact(h.total, h.minpos)) {
+            SCANN_TRY(launch(km_sum_f64_sequential_kernel, dim3(1), dim3(256), 0, st, sc.ddist.as<float>(), n,
+                             sc.dtotal.as<double>(), 0u, (const uint32_t *)nullptr, 0u));
+            SCANN_HIP_CHECK(hipMemcpyAsync(&h.total, sc.dtotal.p, 8, hipMemcpyDeviceToHost, st));
             SCANN_HIP_CHECK(hipStreamSynchronize(st));
         }
         *inertia = h.total;
@@ -2753,19 +2845,33 @@ int bf_kmeans_lloyd_host(const BfIndexDev &ix, uint32_t col_offset, uint32_t sub
         }
         prev = inertia;
         // update_centers: members of every cluster in ascending datapoint order
-        SCANN_TRY(launch(km_make_keys_kernel, dim3(nb), dim3(256), 0, st, dassign.as<uint32_t>(), n,
-                         dkeys.as<uint64_t>()));
-        SCANN_HIP_CHECK(hipcub::DeviceRadixSort::SortKeys(dtmp.p, tmp_bytes, dkeys.as<uint64_t>(),
-                                                          dsorted.as<uint64_t>(), (int)n, 0, key_bits, st));
-        SCANN_TRY(launch(km_offsets_kernel, dim3(ceil_div_u32(k + 1, 256)), dim3(256), 0, st,
-                         dsorted.as<uint64_t>(), n, k, doff.as<uint32_t>()));
+        SCANN_TRY(bf_kmeans_csr_device(d_assign, n, k, sc, st));
         SCANN_TRY(launch(km_gather_sorted_kernel, dim3((uint32_t)ceil_div_u64(n * sub_dim, 256)), dim3(256), 0,
-                         st, v, dsorted.as<uint64_t>(), n, dgrows.as<float>()));
-        SCANN_TRY(launch(km_update_kernel, dim3(k), dim3(256), 0, st, v, dgrows.as<float>(),
-                         doff.as<uint32_t>(), dcent.as<float>()));
+                         st, v, sc.dsorted.as<uint64_t>(), n, sc.dgrows.as<float>()));
+        SCANN_TRY(launch(km_update_kernel, dim3(k), dim3(256), 0, st, v, sc.dgrows.as<float>(),
+                         sc.doff.as<uint32_t>(), d_centers, 0u, (const uint32_t *)nullptr, 0u));
     }
     // final assignment for accurate sizes / inertia (kmeans.rs:248-255)
-    SCANN_TRY(assign_and_inertia(&inertia));
+    if (final_assign) SCANN_TRY(assign_and_inertia(&inertia));
+    if (out_inertia) *out_inertia = inertia;
+    if (out_iterations) *out_iterations = iters;
+    if (out_converged) *out_converged = converged;
+    return SCANN_HIP_OK;
+}
+
+int bf_kmeans_lloyd_host(const BfIndexDev &ix, uint32_t col_offset, uint32_t sub_dim, float *centers,
+                         uint32_t k, uint32_t max_iterations, double convergence_threshold,
+                         uint32_t simd_threshold, uint32_t *out_assign, uint32_t *out_sizes, double *out_inertia,
+                         uint32_t *out_iterations, int *out_converged, hipStream_t st) {
+    const uint64_t n = ix.n;
+    if (n == 0 || k == 0) return fail(SCANN_HIP_INVALID_ARGUMENT, "Cannot cluster empty dataset");
+    KmScratch sc;
+    DevBuf dcent, dassign;
+    SCANN_TRY(upload(dcent, centers, (size_t)k * sub_dim * 4));
+    SCANN_TRY(dassign.ensure(n * 4));
+    SCANN_TRY(bf_kmeans_lloyd_device(ix, col_offset, sub_dim, dcent.as<float>(), k, max_iterations, convergence_threshold,
+                                     simd_threshold, dassign.as<uint32_t>(), true, sc, out_inertia, out_iterations,
+                                     out_converged, st));
     SCANN_HIP_CHECK(hipMemcpyAsync(centers, dcent.p, (size_t)k * sub_dim * 4, hipMemcpyDeviceToHost, st));
     if (out_assign || out_sizes) {
         std::vector<uint32_t> tmp;
@@ -2782,9 +2888,6 @@ int bf_kmeans_lloyd_host(const BfIndexDev &ix, uint32_t col_offset, uint32_t sub
         }
     }
     SCANN_HIP_CHECK(hipStreamSynchronize(st));
-    if (out_inertia) *out_inertia = inertia;
-    if (out_iterations) *out_iterations = iters;
-    if (out_converged) *out_converged = converged;
     return SCANN_HIP_OK;
 }
 

@@ -1,0 +1,33 @@
+// build.h -- scann_hip_txh_build (scann_hip.h "device build"): a tree or flat-hasher index trained, encoded and laid
+// out on the device from the resident rows of an f32 brute-force handle (build.hip).  The handle itself is put
+// together in api.hip (index_build_txh), which owns scann_hip_index.
+#pragma once
+#include <vector>
+
+#include "bf.h"
+#include "common.h"
+
+namespace scann {
+
+// What build_txh_device leaves on the device for the new handle.
+struct BuildParts {
+    DevBuf codes;       // [n][nw] packed code words, CSR row order
+    DevBuf leaf_off;    // [L + 1]
+    DevBuf leaf_ids;    // [n] (tree only)
+    DevBuf centers;     // [L][dim] (tree only)
+    DevBuf codebook;    // [S][K][dsub]
+    std::vector<uint32_t> off;   // host copy of leaf_off (the planner's, as in the fold)
+    uint32_t L = 0;     // leaves: min(num_partitions, n); 1 for a flat hasher
+};
+
+// Every refusal of scann_hip_txh_build that depends on the rows' shape and the configuration; launches nothing.
+int build_check(const BfIndexDev &src, const scann_hip_build_config &cfg);
+// Runs stages 0..5 of scann_hip_build_report.stage_ms on `stream` (complete on return); `rep` may be null.
+int build_txh_device(const BfIndexDev &src, const scann_hip_build_config &cfg, hipStream_t stream, BuildParts *out,
+                     scann_hip_build_report *rep);
+
+// api.hip: the new handle around `parts` (taken) and a device copy of src's rows when cfg.store_rows; stage_ms[6]
+int index_build_txh(const scann_hip_index *src, const scann_hip_build_config &cfg, BuildParts &parts,
+                    scann_hip_index **out, scann_hip_build_report *rep);
+
+}  // namespace scann

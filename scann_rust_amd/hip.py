@@ -71,6 +71,7 @@ EXPORTS = [
     "scann_hip_scalar_dequantize", "scann_hip_scalar_quantize_device", "scann_hip_index_quantize_rows",
     "scann_hip_projection_create", "scann_hip_projection_destroy", "scann_hip_projection_info", "scann_hip_project",
     "scann_hip_project_device", "scann_hip_txh_create_projected", "scann_hip_index_projection_info",
+    "scann_hip_build_config_default", "scann_hip_txh_build",
 ]
 
 
@@ -129,6 +130,29 @@ class SearchOpts(C.Structure):
         ("allow_bitmap", u64p), ("allow_bitmap_bits", C.c_uint64),
         ("bf_exact", C.c_int32),
         ("allow_bitmap_stride", C.c_uint64),
+    ]
+
+
+class BuildConfig(C.Structure):
+    """scann_hip_build_config"""
+    _fields_ = [
+        ("num_partitions", C.c_uint32), ("kmeans_iterations", C.c_uint32), ("kmeans_convergence", C.c_double),
+        ("kmeans_seed", C.c_uint64),
+        ("num_subspaces", C.c_uint32), ("num_codes", C.c_uint32),
+        ("training_iterations", C.c_uint32), ("convergence_threshold", C.c_double),
+        ("seed", C.c_uint64),
+        ("simd_threshold", C.c_uint32), ("use_residuals", C.c_int32), ("store_rows", C.c_int32),
+        ("batched_codebook", C.c_int32),
+        ("partitions_to_search", C.c_uint32), ("pre_reorder_multiplier", C.c_float), ("distance_measure", C.c_int32),
+    ]
+
+
+class BuildReport(C.Structure):
+    """scann_hip_build_report"""
+    _fields_ = [
+        ("partition_iterations", C.c_uint32), ("partition_converged", C.c_int32), ("partition_inertia", C.c_double),
+        ("subspace_iterations", C.c_uint32 * 64), ("subspace_converged", C.c_int32 * 64),
+        ("stage_ms", C.c_float * 7),
     ]
 
 
@@ -220,6 +244,9 @@ def load():
     L.scann_hip_kmeans_lloyd.argtypes = [vp, C.c_uint32, C.c_uint32, f32p, C.c_uint32, C.c_uint32,
                                          C.c_double, C.c_uint32, u32p, u32p, C.POINTER(C.c_double), u32p,
                                          C.POINTER(C.c_int)]
+    L.scann_hip_build_config_default.argtypes = [C.POINTER(BuildConfig)]
+    L.scann_hip_build_config_default.restype = None
+    L.scann_hip_txh_build.argtypes = [vp, C.POINTER(BuildConfig), C.POINTER(vp), C.POINTER(BuildReport)]
     L.scann_hip_abi_layout.restype = C.c_uint32
     L.scann_hip_abi_layout.argtypes = [u32p, C.c_uint32]
     L.scann_hip_lut16_quantize.argtypes = [vp, f32p, C.c_uint32, u8p, f32p, f32p]
@@ -1384,9 +1411,11 @@ def fp8_distances(query, database, stride, n, measure, device=0):
     return out
 
 
-def abi_layout():
-    out = np.zeros(6, np.uint32)
-    n = load().scann_hip_abi_layout(ptr(out, u32p), 6)
+def abi_layout(words=6):
+    """The first `words` layout words of scann_hip_abi_layout: 6 = the descriptor, search options and file info;
+    10 adds sizeof / last-field offset of scann_hip_build_config and scann_hip_build_report."""
+    out = np.zeros(words, np.uint32)
+    n = load().scann_hip_abi_layout(ptr(out, u32p), words)
     return [int(v) for v in out[:n]]
 
 
@@ -1495,6 +1524,40 @@ def kmeans_lloyd(index, centers, max_iterations=100, convergence_threshold=1e-5,
                                         ptr(sizes, u32p), C.byref(inertia),
                                         C.cast(C.byref(iters), u32p), C.byref(conv)))
     return c, assign, sizes, inertia.value, iters.value, bool(conv.value)
+
+
+BUILD_STAGES = ("partition_seeding", "partition_lloyd", "csr_residuals", "codebook_seeding", "codebook_lloyd",
+                "encode", "finish")
+
+
+def build_config(**cfg):
+    """scann_hip_build_config_default with the keyword arguments set on top (field names of BuildConfig)."""
+    c = BuildConfig()
+    load().scann_hip_build_config_default(C.byref(c))
+    names = {f for f, _ in BuildConfig._fields_}
+    for key, value in cfg.items():
+        if key not in names:
+            raise TypeError("scann_hip_build_config has no field %r" % key)
+        setattr(c, key, value)
+    return c
+
+
+def txh_build(bf_index, **cfg):
+    """scann_hip_txh_build: a tree (num_partitions > 0) or flat-hasher (0) index trained, encoded and laid out on the
+    device from the resident rows of an f32 brute-force index.  Returns (Index, report): report is a dict with
+    partition_iterations / _converged / _inertia, subspace_iterations and subspace_converged ([S] lists) and stage_ms
+    ({stage name: milliseconds}, BUILD_STAGES)."""
+    c = build_config(**cfg)
+    rep = BuildReport()
+    h = vp()
+    check(load().scann_hip_txh_build(bf_index.h, C.byref(c), C.byref(h), C.byref(rep)))
+    S = c.num_subspaces
+    report = dict(partition_iterations=int(rep.partition_iterations), partition_converged=bool(rep.partition_converged),
+                  partition_inertia=float(rep.partition_inertia),
+                  subspace_iterations=[int(v) for v in rep.subspace_iterations[:S]],
+                  subspace_converged=[bool(v) for v in rep.subspace_converged[:S]],
+                  stage_ms=dict(zip(BUILD_STAGES, (float(v) for v in rep.stage_ms))))
+    return Index(h), report
 
 
 def bf_assign_nearest(index, centers, want_dist=True):

@@ -1301,6 +1301,33 @@ public:
         dataset_ = std::make_shared<DenseDataset>(std::move(dataset));
     }
     void build_no_store(const DenseDataset &dataset) { build_impl(dataset, false); }   // :137-159
+    // build / build_no_store from rows that are already on the device, in one call (scann_hip_txh_build with
+    // num_partitions 0): `source` keeps its rows and stays the caller's, the new handle takes its own copy when `store`.
+    // The codebook is the one build() trains (same training rows, same seeds); it and the codes stay on the device, so
+    // codebook() and encoded_database() are empty afterwards.
+    void build_on_device(const BruteForceSearcher &source, bool store = true, scann_hip_build_report *report = nullptr) {
+        scann_hip_build_config c;
+        scann_hip_build_config_default(&c);
+        c.num_partitions = 0;
+        c.num_subspaces = (uint32_t)config_.num_subspaces;
+        c.num_codes = (uint32_t)config_.num_codes;
+        c.training_iterations = (uint32_t)config_.training_iterations;
+        c.convergence_threshold = config_.convergence_threshold;
+        c.seed = config_.seed;
+        c.store_rows = store ? 1 : 0;
+        c.partitions_to_search = 1;
+        c.pre_reorder_multiplier = 1.0f;
+        scann_hip_index *h = nullptr;
+        check(scann_hip_txh_build(source.handle(), &c, &h, report));
+        if (ix_.h) scann_hip_index_destroy(ix_.h);
+        ix_.h = h;
+        n_ = source.dataset_size();
+        dim_ = source.dimensionality();
+        stored_ = store;
+        dataset_.reset();
+        codebook_.clear();
+        codes_.clear();
+    }
 
     NNResultsVector search(const std::vector<float> &query, size_t k) const {          // :162-185
         if (!ix_.h) return {};
@@ -1463,6 +1490,37 @@ public:
         const scann_hip_txh_desc d = desc();
         if (ix_.h) { scann_hip_index_destroy(ix_.h); ix_.h = nullptr; }
         check(scann_hip_txh_create(context(device_), &d, &ix_.h));
+    }
+
+    // build() from rows that are already on the device, in one call (scann_hip_txh_build): partitioner, residuals,
+    // codebook, codes and CSR layout never leave it; `source` keeps its rows and stays the caller's.  NOT the arrays of
+    // build() above: that trains the codebook on the residuals in CSR order against the k-means assignment, this one --
+    // as the reference does (mod.rs:151-158, 211-237) -- in datapoint order against partition(x, 1), another training
+    // order and therefore another codebook.  The index lives on the device only: save() needs a searcher made by
+    // build() or load().
+    void build_on_device(const BruteForceSearcher &source, scann_hip_build_report *report = nullptr) {
+        scann_hip_build_config c;
+        scann_hip_build_config_default(&c);
+        c.num_partitions = (uint32_t)config_.num_partitions;
+        c.kmeans_iterations = (uint32_t)config_.kmeans_iterations;
+        c.num_subspaces = (uint32_t)config_.hash_config.num_subspaces;
+        c.num_codes = (uint32_t)config_.hash_config.num_codes;
+        c.training_iterations = (uint32_t)config_.hash_config.training_iterations;
+        c.convergence_threshold = config_.hash_config.convergence_threshold;
+        c.seed = config_.hash_config.seed;
+        c.use_residuals = config_.use_residuals ? 1 : 0;
+        c.partitions_to_search = (uint32_t)config_.partitions_to_search;
+        c.pre_reorder_multiplier = config_.pre_reorder_multiplier;
+        if (c.num_partitions == 0) throw ScannError::invalid_argument("num_partitions is 0");
+        scann_hip_index *h = nullptr;
+        check(scann_hip_txh_build(source.handle(), &c, &h, report));
+        if (ix_.h) scann_hip_index_destroy(ix_.h);
+        ix_.h = h;
+        n_ = source.dataset_size();
+        dim_ = source.dimensionality();
+        L_ = std::min<size_t>(config_.num_partitions, n_);
+        dataset_.reset();
+        centers_.clear(); codebook_.clear(); leaf_off_.clear(); leaf_ids_.clear(); codes_.clear();
     }
 
     NNResultsVector search(const std::vector<float> &query, size_t k) const {   // mod.rs:240-294
