@@ -324,7 +324,8 @@ int scann_hip_txh_create_quantized(scann_hip_ctx *ctx, const scann_hip_txh_desc 
  * `matrix` is [out_dim][in_dim]: column j of the reference's column-major DMatrix is row j here.  `mean` is [in_dim].
  * The object copies its arrays at create and is immutable afterwards; project calls on one object may run
  * concurrently.  The trained matrix is an input (the reference's eigen-solver and RNG are not reproducible here:
- * SURVEY F2, F4, F10), as centres and codebooks are. */
+ * SURVEY F2, F4, F10), as centres and codebooks are; scann_hip_pca_train ("PCA training on the device", below) trains
+ * one by the project's own rule. */
 typedef struct scann_hip_projection scann_hip_projection;
 #define SCANN_HIP_PROJ_MATRIX   1   /* random orthogonal / gaussian / OPQ rotation: no mean */
 #define SCANN_HIP_PROJ_PCA      2   /* matrix + mean */
@@ -1287,6 +1288,63 @@ typedef struct scann_hip_build_report {
 void scann_hip_build_config_default(scann_hip_build_config *cfg);
 int scann_hip_txh_build(scann_hip_index *rows, const scann_hip_build_config *cfg, scann_hip_index **out_index,
                         scann_hip_build_report *out_report);
+
+/* ---- PCA training on the device (PcaProjection::train, projection/pca.rs:71-129, utils/linear_algebra.rs:89-120) ----
+ * Trains a SCANN_HIP_PROJ_PCA projection from the resident rows of an f32 brute-force handle (in_dim = its dim); no row
+ * crosses to the host.  The object is indistinguishable from one scann_hip_projection_create makes from the same
+ * arrays.  THE RULE is the project's own (the reference's shuffle and nalgebra SVD are not reproducible: SURVEY F2, F4,
+ * F10), the one trainer.pca_projection states:
+ *   1 sample      max_samples == 0 or >= n: every row, in order.  Otherwise ns = max_samples rows, row t =
+ *                 splitmix64(seed ^ 0x9CA, 0, ns)[t] % n: with replacement, counter based, computed on the device.
+ *   2 mean        per column in f64, in a fixed order that depends on ns alone (at most 1024 runs of consecutive sample
+ *                 positions, each summed ascending, the runs added ascending); no floating-point atomics.  The
+ *                 projection's mean is its rounding to f32.
+ *   3 covariance  C = sum (x - mean64)(x - mean64)^T / max(1, ns - 1): rows widened to f64 and centred with the
+ *                 UNROUNDED f64 mean before the product; two passes, never E[xx^T] - mu mu^T.  Elements between dim and
+ *                 stride are never read.  Computed on v_mfma_f64_16x16x4_f64, upper-triangle tiles only and mirrored,
+ *                 split over row runs into a workspace of at most 128 MiB and reduced in ascending run order.
+ *   4 eigen-solve cyclic Jacobi on C, in f64, on the device: a fixed round-robin pairing (d - 1 rounds of floor(d / 2)
+ *                 disjoint rotations, a bye for odd d), one kernel per round, so the result is a function of C alone.
+ *                 Converged when the Frobenius norm of the strict off-diagonal, summed from the off-diagonal entries
+ *                 themselves, is <= 2^-46 ||C||_F.  At most 30 sweeps; out_sweeps and out_converged report the count
+ *                 and the outcome; an unconverged solve still returns its result, with *out_converged = 0.
+ *   5 components  eigenvalues descending (ties: lower original column first); each component's sign makes its
+ *                 largest-magnitude entry positive (ties: lowest index); cast to f32; matrix [out_dim][in_dim].
+ * Only the matrix, the mean and the optional outputs are read back: out_eigenvalues [in_dim] (all of them, sorted),
+ * out_covariance [in_dim][in_dim] (before the solve), each may be NULL, as may out_sweeps and out_converged.
+ * Device memory while training, released on return (d = in_dim, m = d rounded up to even): ns * 4 bytes of sample
+ * indices when sampling, 1024 * d * 8 of mean runs, at most 128 MiB of covariance runs, 3 * m * m * 8 for the solve.
+ * REFUSED before any launch (`rows` keeps searching): not an f32 brute-force handle (a quantized, tree or hasher
+ * handle), n == 0, out_dim == 0 or > in_dim -> InvalidArgument; in_dim > 2048 -> ResourceExhausted, the message naming
+ * the limit (the solve is O(d^3) per sweep). */
+int scann_hip_pca_train(scann_hip_index *rows, uint32_t out_dim, uint64_t max_samples, uint64_t seed,
+                        scann_hip_projection **out_projection, double *out_eigenvalues, double *out_covariance,
+                        uint32_t *out_sweeps, int *out_converged);
+/* The arrays of a projection object, any kind: out_matrix [out_dim][in_dim] (not written for TRUNCATE), out_mean
+ * [in_dim] (written for PCA only); each may be NULL. */
+int scann_hip_projection_arrays(const scann_hip_projection *projection, float *out_matrix, float *out_mean);
+/* Host-clock milliseconds of the calling thread's last scann_hip_pca_train: sample + mean, covariance, eigen-solve,
+ * components + read-back. */
+void scann_hip_pca_last_stage_ms(float *out_ms4);
+
+/* ---- projected device build ---------------------------------------------------------
+ * scann_hip_txh_build for a PROJECTED index, in one call: `rows` is an f32 brute-force handle of projection.in_dim
+ * floats per row, `projection` any kind (PCA from scann_hip_pca_train, a caller's MATRIX or TRUNCATE).  THE RULE: every
+ * array of the new handle is bit-identical to, and its searches are those of, this chain through the public entry points:
+ *   1 scann_hip_project_device of the rows into [n][out_dim];
+ *   2 scann_hip_bf_create of those rows at stride out_dim;
+ *   3 scann_hip_txh_build(cfg with store_rows = 0);
+ *   4 scann_hip_txh_create_projected from the built arrays, with the original rows, or none when cfg->store_rows == 0.
+ * No code, id list, assignment or row visits the host; the projection is copied into the handle (the caller may destroy
+ * it) and the original rows are copied device to device.  Extra device memory during the call, beyond
+ * scann_hip_txh_build's: n * out_dim * 4 bytes for the projected rows, released before the handle is assembled.
+ * out_report: as scann_hip_txh_build's, all seven stage_ms slots; the projection pass is added to stage_ms[0].
+ * The handle writes and reloads through the proj_* file sections like any projected handle.
+ * REFUSED before any launch: everything scann_hip_txh_build refuses, judged on out_dim (dim % num_subspaces, the k-means
+ * LDS limit, ...); a NULL projection and rows whose dim is not projection.in_dim -> InvalidArgument. */
+int scann_hip_txh_build_projected(scann_hip_index *rows, const scann_hip_projection *projection,
+                                  const scann_hip_build_config *cfg, scann_hip_index **out_index,
+                                  scann_hip_build_report *out_report);
 
 /* ---- introspection ------------------------------------------------------------- */
 uint64_t scann_hip_index_size(const scann_hip_index *index);          /* Searcher::dataset_size */

@@ -14,8 +14,8 @@ OBJ = os.path.join(HERE, "_obj")
 LIB = os.path.join(HERE, "libscann_hip.so")
 # the units of the tree / flat-hasher search
 TXH_SOURCES = ["txh.hip", "txh_partition.hip", "txh_prefilter.hip", "txh_rows.hip", "txh_blocks.hip"]
-SOURCES = ["api.hip"] + TXH_SOURCES + ["bf.hip", "index_file.hip", "comm.hip", "crowd.hip", "mmr.hip", "mutable.hip", "fold.hip", "allow.hip", "tokens.hip", "scalarq.hip", "project.hip", "build.hip"]
-HEADERS = ["common.h", "knobs.h", "txh.h", "txh_dev.h", "txh_stages.h", "allow.h", "tokens.h", "bf.h", "comm.h", "crowd.h", "mmr.h", "mutable.h", "fold.h", "index_arrays.h", "pair.h", "launch.h", "quant.h", "scalarq.h", "project.h", "build.h", os.path.join("..", "..", "include", "scann_hip.h")]
+SOURCES = ["api.hip"] + TXH_SOURCES + ["bf.hip", "index_file.hip", "comm.hip", "crowd.hip", "mmr.hip", "mutable.hip", "fold.hip", "allow.hip", "tokens.hip", "scalarq.hip", "project.hip", "build.hip", "pca.hip"]
+HEADERS = ["common.h", "knobs.h", "txh.h", "txh_dev.h", "txh_stages.h", "allow.h", "tokens.h", "bf.h", "comm.h", "crowd.h", "mmr.h", "mutable.h", "fold.h", "index_arrays.h", "pair.h", "launch.h", "quant.h", "scalarq.h", "project.h", "build.h", "pca.h", os.path.join("..", "..", "include", "scann_hip.h")]
 # -ffp-contract=off: the reference never contracts a*b+c (Rust); FMA is used only via
 # explicit fmaf()/MFMA where the reference uses _mm256_fmadd_ps.
 CFLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "-fPIC", "-Wall",
@@ -121,7 +121,8 @@ HOST_PROGRAMS = ["host_test", "ann_benchmark", "bf_filter_test",   # C++ mirror 
                  "mutable_test", "fold_test",                    # crowding and MMR, mutable indexes and their fold through the mirror,
                  "scalar_quantizer_test",                        # the scalar quantizer and its brute-force searcher,
                  "projection_test",                              # the CPU projection loop (uses no GPU),
-                 "device_build_test"]                            # build_on_device of the hasher and the tree searcher
+                 "device_build_test",                            # build_on_device of the hasher and the tree searcher,
+                 "pca_build_test"]                               # PCA training and projected builds on the device
 
 
 def build_host(verbose=False):

@@ -23,6 +23,7 @@
 #include "index_arrays.h"
 #include "mmr.h"
 #include "mutable.h"
+#include "pca.h"
 #include "knobs.h"
 #include "launch.h"
 #include "project.h"
@@ -418,12 +419,16 @@ int scann::index_fold_txh(const scann_hip_index *old, DevBuf &rows, DevBuf &code
 
 // The handle of scann_hip_txh_build (build.h): the arrays build_txh_device wrote, a device copy of the source's rows
 // when they are stored, then the second half of every tree / hasher create.
+// With `proj` (scann_hip_txh_build_projected) the arrays were built from the projected rows: the handle's index space is
+// out_dim wide at stride out_dim, the source's rows are the re-rank rows in their own space and the projection is copied
+// in, as scann_hip_txh_create_projected lays a handle out.
 int scann::index_build_txh(const scann_hip_index *src, const scann_hip_build_config &cfg, BuildParts &parts,
-                           scann_hip_index **out, scann_hip_build_report *rep) {
+                           scann_hip_index **out, scann_hip_build_report *rep, const scann_hip_projection *proj) {
     if (!src || !out || src->kind != KIND_BF) return fail(SCANN_HIP_INVALID_ARGUMENT, "not a brute-force index");
     const auto t0 = std::chrono::steady_clock::now();
     const bool tree = cfg.num_partitions != 0;
     const uint64_t n = src->bf.n;
+    const uint32_t dim = proj ? proj->dev.out_dim : src->bf.dim, stride = proj ? proj->dev.out_dim : src->bf.stride;
     const uint32_t L = parts.L;
     if (parts.off.size() != (size_t)L + 1) return fail(SCANN_HIP_INTERNAL, "build: leaf offsets of the wrong length");
     SCANN_TRY(set_device(src->ctx));
@@ -452,23 +457,43 @@ int scann::index_build_txh(const scann_hip_index *src, const scann_hip_build_con
     scann_hip_txh_desc d;
     std::memset(&d, 0, sizeof(d));
     d.n_rows = d.n_local = n;
-    d.dim = src->bf.dim;
-    d.stride = src->bf.stride;
+    d.dim = dim;
+    d.stride = stride;
     d.num_partitions = tree ? L : 0u;
     d.num_subspaces = cfg.num_subspaces;
     d.num_codes = cfg.num_codes;
-    d.dims_per_subspace = src->bf.dim / cfg.num_subspaces;
+    d.dims_per_subspace = dim / cfg.num_subspaces;
     d.distance_measure = cfg.distance_measure;
     d.codes_packed4 = cfg.num_codes <= 16 ? 1 : 0;
     d.use_residuals = (tree && cfg.use_residuals) ? 1 : 0;
     d.partitions_to_search = tree ? cfg.partitions_to_search : 0u;
     d.pre_reorder_multiplier = cfg.pre_reorder_multiplier;
-    d.data = cfg.store_rows ? ix->d_rows.as<float>() : nullptr;   // (txh_finish asks only whether rows are stored)
-    ix->n_rows = cfg.store_rows ? n : 0;
+    // (txh_finish asks only whether rows are stored; a projected handle's rows are not in the index space)
+    d.data = (cfg.store_rows && !proj) ? ix->d_rows.as<float>() : nullptr;
+    ix->n_rows = (cfg.store_rows && !proj) ? n : 0;
     std::vector<uint32_t> gsz(L);
     for (uint32_t l = 0; l < L; ++l) gsz[l] = parts.off[l + 1] - parts.off[l];
     if ((s = upload(ix->d_leaf_gsize, gsz.data(), (size_t)L * 4)) != SCANN_HIP_OK) return bail(s);
     if ((s = txh_finish(ix, &d, parts.off)) != SCANN_HIP_OK) return bail(s);
+    if (proj) {
+        const ProjDev &pd = proj->dev;
+        ix->proj = pd;
+        ix->proj.matrix = ix->proj.mean = nullptr;
+        if (pd.kind != SCANN_HIP_PROJ_TRUNCATE) {
+            if ((s = upload(ix->d_proj_matrix, proj->matrix.data(), proj->matrix.size() * 4)) != SCANN_HIP_OK) return bail(s);
+            ix->proj.matrix = ix->d_proj_matrix.as<float>();
+        }
+        if (pd.kind == SCANN_HIP_PROJ_PCA) {
+            if ((s = upload(ix->d_proj_mean, proj->mean.data(), proj->mean.size() * 4)) != SCANN_HIP_OK) return bail(s);
+            ix->proj.mean = ix->d_proj_mean.as<float>();
+        }
+        if (cfg.store_rows) {
+            ix->tx.rows = ix->d_rows.as<float>();
+            ix->n_rows = n;
+        }
+        ix->tx.row_dim = src->bf.dim;
+        ix->tx.row_stride = src->bf.stride;
+    }
     if (rep) rep->stage_ms[6] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     *out = ix;
     return SCANN_HIP_OK;
@@ -3144,6 +3169,56 @@ int scann_hip_txh_build(scann_hip_index *rows, const scann_hip_build_config *cfg
     BuildParts parts;
     SCANN_TRY(build_txh_device(rows->bf, *cfg, rows->stream, &parts, out_report));
     return index_build_txh(rows, *cfg, parts, out_index, out_report);
+}
+
+int scann_hip_txh_build_projected(scann_hip_index *rows, const scann_hip_projection *projection,
+                                  const scann_hip_build_config *cfg, scann_hip_index **out_index,
+                                  scann_hip_build_report *out_report) {
+    if (!rows || !cfg || !out_index) return fail(SCANN_HIP_INVALID_ARGUMENT, "null rows/config/out_index");
+    *out_index = nullptr;
+    if (out_report) std::memset(out_report, 0, sizeof(*out_report));
+    if (!projection) return fail(SCANN_HIP_INVALID_ARGUMENT, "projected build: projection is null");
+    if (rows->kind != KIND_BF) return fail(SCANN_HIP_INVALID_ARGUMENT, "not a brute-force index");
+    std::lock_guard<std::mutex> lock(rows->mu);
+    SCANN_TRY(set_device(rows->ctx));
+    const ProjDev &pd = projection->dev;
+    // the rows' view in the index space: [n][out_dim] at stride out_dim (the temporary buffer below)
+    BfIndexDev view = rows->bf;
+    view.dim = view.stride = pd.out_dim;
+    view.rows_b = view.rows_bl = nullptr;
+    view.norm2 = nullptr;
+    view.max_norm = 0.0f;
+    SCANN_TRY(build_check(view, *cfg));   // every refusal of scann_hip_txh_build, judged on out_dim, before any launch
+    if (rows->bf.dim != pd.in_dim)
+        return fail(SCANN_HIP_INVALID_ARGUMENT, "projected build: the rows' dim " + std::to_string(rows->bf.dim) +
+                                                    " is not the projection's in_dim " + std::to_string(pd.in_dim));
+    const uint64_t n = rows->bf.n;
+    if (n > SIZE_MAX / 4 / pd.out_dim) return fail(SCANN_HIP_OUT_OF_RANGE, "projected build: n * out_dim overflows");
+    const auto t0 = std::chrono::steady_clock::now();
+    DevBuf projected;
+    SCANN_TRY(projected.ensure((size_t)n * pd.out_dim * 4));
+    SCANN_TRY(launch_project(pd, rows->bf.rows, n, rows->bf.stride, projected.as<float>(), pd.out_dim, rows->stream));
+    SCANN_HIP_CHECK(hipStreamSynchronize(rows->stream));
+    const float project_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    view.rows = projected.as<float>();
+    BuildParts parts;
+    SCANN_TRY(build_txh_device(view, *cfg, rows->stream, &parts, out_report));
+    projected.release();
+    if (out_report) out_report->stage_ms[0] += project_ms;
+    return index_build_txh(rows, *cfg, parts, out_index, out_report, projection);
+}
+
+int scann_hip_pca_train(scann_hip_index *rows, uint32_t out_dim, uint64_t max_samples, uint64_t seed,
+                        scann_hip_projection **out_projection, double *out_eigenvalues, double *out_covariance,
+                        uint32_t *out_sweeps, int *out_converged) {
+    if (!rows || !out_projection) return fail(SCANN_HIP_INVALID_ARGUMENT, "null rows/out_projection");
+    *out_projection = nullptr;
+    if (rows->kind != KIND_BF) return fail(SCANN_HIP_INVALID_ARGUMENT, "pca_train: not a brute-force index");
+    std::lock_guard<std::mutex> lock(rows->mu);
+    SCANN_TRY(set_device(rows->ctx));
+    SCANN_TRY(pca_check(rows->bf, out_dim));   // every refusal, before the first launch
+    return pca_train_device(rows->ctx, rows->bf, out_dim, max_samples, seed, rows->stream, out_projection, out_eigenvalues,
+                            out_covariance, out_sweeps, out_converged);
 }
 
 int scann_hip_kmeans_lloyd(scann_hip_index *ix, uint32_t col_offset, uint32_t sub_dim, float *centers,

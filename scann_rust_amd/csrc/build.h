@@ -26,8 +26,10 @@ int build_check(const BfIndexDev &src, const scann_hip_build_config &cfg);
 int build_txh_device(const BfIndexDev &src, const scann_hip_build_config &cfg, hipStream_t stream, BuildParts *out,
                      scann_hip_build_report *rep);
 
-// api.hip: the new handle around `parts` (taken) and a device copy of src's rows when cfg.store_rows; stage_ms[6]
+// api.hip: the new handle around `parts` (taken) and a device copy of src's rows when cfg.store_rows; stage_ms[6].
+// proj != nullptr (scann_hip_txh_build_projected): `parts` index the projected rows, [n][out_dim]; the handle copies
+// the projection and keeps src's rows as re-rank rows in their own space.
 int index_build_txh(const scann_hip_index *src, const scann_hip_build_config &cfg, BuildParts &parts,
-                    scann_hip_index **out, scann_hip_build_report *rep);
+                    scann_hip_index **out, scann_hip_build_report *rep, const scann_hip_projection *proj = nullptr);
 
 }  // namespace scann

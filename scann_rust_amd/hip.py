@@ -72,6 +72,7 @@ EXPORTS = [
     "scann_hip_projection_create", "scann_hip_projection_destroy", "scann_hip_projection_info", "scann_hip_project",
     "scann_hip_project_device", "scann_hip_txh_create_projected", "scann_hip_index_projection_info",
     "scann_hip_build_config_default", "scann_hip_txh_build",
+    "scann_hip_pca_train", "scann_hip_projection_arrays", "scann_hip_pca_last_stage_ms", "scann_hip_txh_build_projected",
 ]
 
 
@@ -337,6 +338,12 @@ def load():
     L.scann_hip_txh_create_projected.argtypes = [vp, C.POINTER(TxhDesc), vp, f32p, C.c_uint64, C.c_uint32, C.c_uint32,
                                                  C.POINTER(vp)]
     L.scann_hip_index_projection_info.argtypes = [vp, u32p]
+    L.scann_hip_pca_train.argtypes = [vp, C.c_uint32, C.c_uint64, C.c_uint64, C.POINTER(vp), C.POINTER(C.c_double),
+                                      C.POINTER(C.c_double), u32p, C.POINTER(C.c_int)]
+    L.scann_hip_projection_arrays.argtypes = [vp, f32p, f32p]
+    L.scann_hip_pca_last_stage_ms.argtypes = [f32p]
+    L.scann_hip_pca_last_stage_ms.restype = None
+    L.scann_hip_txh_build_projected.argtypes = [vp, vp, C.POINTER(BuildConfig), C.POINTER(vp), C.POINTER(BuildReport)]
     _lib = L
     return L
 
@@ -1193,8 +1200,23 @@ class Projection:
                                                  ptr(m, f32p), ptr(mu, f32p), int(start), C.byref(h)))
         self.h = h
 
+    @classmethod
+    def from_handle(cls, h):
+        """Owns a scann_hip_projection the library made (pca_train)."""
+        p = cls.__new__(cls)
+        p.h = h
+        return p
+
+    def arrays(self):
+        """(matrix [out_dim, in_dim] or None for TRUNCATE, mean [in_dim] or None unless PCA): scann_hip_projection_arrays"""
+        kind, in_dim, out_dim, _ = self.info()
+        m = np.zeros((out_dim, in_dim), np.float32) if kind != PROJ_TRUNCATE else None
+        mu = np.zeros(in_dim, np.float32) if kind == PROJ_PCA else None
+        check(load().scann_hip_projection_arrays(self.h, ptr(m, f32p), ptr(mu, f32p)))
+        return m, mu
+
     def close(self):
-        if self.h:
+        if getattr(self, "h", None):
             load().scann_hip_projection_destroy(self.h)
             self.h = None
 
@@ -1551,13 +1573,57 @@ def txh_build(bf_index, **cfg):
     rep = BuildReport()
     h = vp()
     check(load().scann_hip_txh_build(bf_index.h, C.byref(c), C.byref(h), C.byref(rep)))
-    S = c.num_subspaces
-    report = dict(partition_iterations=int(rep.partition_iterations), partition_converged=bool(rep.partition_converged),
-                  partition_inertia=float(rep.partition_inertia),
-                  subspace_iterations=[int(v) for v in rep.subspace_iterations[:S]],
-                  subspace_converged=[bool(v) for v in rep.subspace_converged[:S]],
-                  stage_ms=dict(zip(BUILD_STAGES, (float(v) for v in rep.stage_ms))))
-    return Index(h), report
+    return Index(h), _build_report(rep, c.num_subspaces)
+
+
+def _build_report(rep, S):
+    return dict(partition_iterations=int(rep.partition_iterations), partition_converged=bool(rep.partition_converged),
+                partition_inertia=float(rep.partition_inertia),
+                subspace_iterations=[int(v) for v in rep.subspace_iterations[:S]],
+                subspace_converged=[bool(v) for v in rep.subspace_converged[:S]],
+                stage_ms=dict(zip(BUILD_STAGES, (float(v) for v in rep.stage_ms))))
+
+
+def txh_build_projected(bf_index, projection, **cfg):
+    """scann_hip_txh_build_projected: txh_build of a PROJECTED index in one call -- the rows of the f32 brute-force index
+    (projection.in_dim floats each) are projected on the device, the tree / flat hasher is trained, encoded and laid out
+    in the projected space, and the handle re-ranks against the original rows (store_rows=1) or holds none.  Returns
+    (Index, report) as txh_build does; stage_ms["partition_seeding"] includes the projection pass."""
+    c = build_config(**cfg)
+    rep = BuildReport()
+    h = vp()
+    check(load().scann_hip_txh_build_projected(bf_index.h, projection.h if projection is not None else None, C.byref(c),
+                                               C.byref(h), C.byref(rep)))
+    return Index(h), _build_report(rep, c.num_subspaces)
+
+
+PCA_STAGES = ("sample_mean", "covariance", "eigen_solve", "components")
+
+
+def pca_train(bf_index, out_dim, max_samples=0, seed=42, want_eigenvalues=False, want_covariance=False):
+    """scann_hip_pca_train: a PROJ_PCA Projection trained on the device from the rows of an f32 brute-force index (the rule
+    of trainer.pca_projection; max_samples 0 = every row).  Returns (projection, info): info holds sweeps, converged,
+    and, when asked for, eigenvalues (f64 [in_dim], descending) and covariance (f64 [in_dim, in_dim])."""
+    d = bf_index.dimensionality()
+    eig = np.zeros(d, np.float64) if want_eigenvalues else None
+    cov = np.zeros((d, d), np.float64) if want_covariance else None
+    sweeps, conv, h = C.c_uint32(0), C.c_int(0), vp()
+    f64p = C.POINTER(C.c_double)
+    check(load().scann_hip_pca_train(bf_index.h, int(out_dim), int(max_samples), int(seed) & 0xFFFFFFFFFFFFFFFF, C.byref(h),
+                                     ptr(eig, f64p), ptr(cov, f64p), C.cast(C.byref(sweeps), u32p), C.byref(conv)))
+    info = dict(sweeps=int(sweeps.value), converged=bool(conv.value))
+    if want_eigenvalues:
+        info["eigenvalues"] = eig
+    if want_covariance:
+        info["covariance"] = cov
+    return Projection.from_handle(h), info
+
+
+def pca_last_stage_ms():
+    """{stage: host-clock milliseconds} of this thread's last pca_train (PCA_STAGES)"""
+    out = np.zeros(4, np.float32)
+    load().scann_hip_pca_last_stage_ms(ptr(out, f32p))
+    return dict(zip(PCA_STAGES, (float(v) for v in out)))
 
 
 def bf_assign_nearest(index, centers, want_dist=True):

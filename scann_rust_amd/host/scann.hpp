@@ -1176,8 +1176,8 @@ private:
 };
 
 // ---- projections (projection/: pca.rs, random.rs, opq.rs, truncate.rs) ---------------------------------------------------
-// The arrays of a trained projection (training stays with the caller: the reference's eigen-solver and RNG are not
-// reproducible here).  matrix is [out_dim][in_dim]: column j of the reference's column-major DMatrix
+// The arrays of a trained projection (the reference's eigen-solver and RNG are not reproducible here, SURVEY F2, F4,
+// F10: the arrays are the caller's, or PCA's from Projection::train_pca_on_device by the library's own rule).  matrix is [out_dim][in_dim]: column j of the reference's column-major DMatrix
 // is row j.  project() is the reference's loop verbatim; to_device() makes the scann_hip_projection whose kernel gives
 // the same bits (scann_hip.h "projections").
 enum class ProjectionKind : int { Matrix = SCANN_HIP_PROJ_MATRIX, Pca = SCANN_HIP_PROJ_PCA, Truncate = SCANN_HIP_PROJ_TRUNCATE };
@@ -1256,6 +1256,31 @@ public:
         for (size_t i = 0; i < ds.size(); ++i) project(ds.get((DatapointIndex)i), flat.data() + i * out_dim_);
         return DenseDataset::from_flat(flat, out_dim_);
     }
+    // PcaProjection::train on the device (scann_hip_pca_train: the rule is in scann_hip.h) from the resident rows of a
+    // brute-force searcher; max_samples 0 = every row (the reference's default is 100 000).  Returns the device object;
+    // from_device() reads its arrays back into a Projection.
+    static DeviceProjection train_pca_on_device(const BruteForceSearcher &source, size_t out_dim, uint64_t max_samples = 0,
+                                                uint64_t seed = 42, uint32_t *sweeps = nullptr, bool *converged = nullptr,
+                                                std::vector<double> *eigenvalues = nullptr) {
+        scann_hip_projection *h = nullptr;
+        int conv = 0;
+        uint32_t sw = 0;
+        if (eigenvalues) eigenvalues->assign(source.dimensionality(), 0.0);
+        check(scann_hip_pca_train(source.handle(), (uint32_t)out_dim, max_samples, seed, &h,
+                                  eigenvalues ? eigenvalues->data() : nullptr, nullptr, &sw, &conv));
+        if (sweeps) *sweeps = sw;
+        if (converged) *converged = conv != 0;
+        return DeviceProjection(h);
+    }
+    static Projection from_device(const DeviceProjection &p) {
+        uint32_t info[4];
+        check(scann_hip_projection_info(p.handle(), info));
+        const ProjectionKind kind = (ProjectionKind)info[0];
+        std::vector<float> m(kind == ProjectionKind::Truncate ? 0 : (size_t)info[1] * info[2]);
+        std::vector<float> mean(kind == ProjectionKind::Pca ? info[1] : 0);
+        check(scann_hip_projection_arrays(p.handle(), m.empty() ? nullptr : m.data(), mean.empty() ? nullptr : mean.data()));
+        return Projection(kind, info[1], info[2], info[3], std::move(m), std::move(mean));
+    }
     DeviceProjection to_device(int device = 0) const {
         scann_hip_projection *h = nullptr;
         check(scann_hip_projection_create(context(device), (int)kind_, (uint32_t)in_dim_, (uint32_t)out_dim_,
@@ -1306,6 +1331,19 @@ public:
     // The codebook is the one build() trains (same training rows, same seeds); it and the codes stay on the device, so
     // codebook() and encoded_database() are empty afterwards.
     void build_on_device(const BruteForceSearcher &source, bool store = true, scann_hip_build_report *report = nullptr) {
+        build_device_impl(source, nullptr, store, report);
+    }
+    // The same for a PROJECTED hasher (scann_hip_txh_build_projected): the rows of `source` (projection.in_dim floats
+    // each) are projected on the device, the codebook is trained and the rows are encoded in the projected space, and
+    // searches take queries in the rows' own space; with `store` the re-ranking scores the original rows.
+    void build_projected_on_device(const BruteForceSearcher &source, const DeviceProjection &projection, bool store = true,
+                                   scann_hip_build_report *report = nullptr) {
+        build_device_impl(source, &projection, store, report);
+    }
+
+private:
+    void build_device_impl(const BruteForceSearcher &source, const DeviceProjection *projection, bool store,
+                           scann_hip_build_report *report) {
         scann_hip_build_config c;
         scann_hip_build_config_default(&c);
         c.num_partitions = 0;
@@ -1318,7 +1356,8 @@ public:
         c.partitions_to_search = 1;
         c.pre_reorder_multiplier = 1.0f;
         scann_hip_index *h = nullptr;
-        check(scann_hip_txh_build(source.handle(), &c, &h, report));
+        if (projection) check(scann_hip_txh_build_projected(source.handle(), projection->handle(), &c, &h, report));
+        else check(scann_hip_txh_build(source.handle(), &c, &h, report));
         if (ix_.h) scann_hip_index_destroy(ix_.h);
         ix_.h = h;
         n_ = source.dataset_size();
@@ -1328,6 +1367,8 @@ public:
         codebook_.clear();
         codes_.clear();
     }
+
+public:
 
     NNResultsVector search(const std::vector<float> &query, size_t k) const {          // :162-185
         if (!ix_.h) return {};
@@ -1499,6 +1540,19 @@ public:
     // order and therefore another codebook.  The index lives on the device only: save() needs a searcher made by
     // build() or load().
     void build_on_device(const BruteForceSearcher &source, scann_hip_build_report *report = nullptr) {
+        build_device_impl(source, nullptr, report);
+    }
+    // The same for a PROJECTED index (scann_hip_txh_build_projected): the rows of `source` (projection.in_dim floats each)
+    // are projected on the device, the index is built in the projected space, searches take queries in the rows' own
+    // space and re-rank against the original rows.
+    void build_projected_on_device(const BruteForceSearcher &source, const DeviceProjection &projection,
+                                   scann_hip_build_report *report = nullptr) {
+        build_device_impl(source, &projection, report);
+    }
+
+private:
+    void build_device_impl(const BruteForceSearcher &source, const DeviceProjection *projection,
+                           scann_hip_build_report *report) {
         scann_hip_build_config c;
         scann_hip_build_config_default(&c);
         c.num_partitions = (uint32_t)config_.num_partitions;
@@ -1513,7 +1567,8 @@ public:
         c.pre_reorder_multiplier = config_.pre_reorder_multiplier;
         if (c.num_partitions == 0) throw ScannError::invalid_argument("num_partitions is 0");
         scann_hip_index *h = nullptr;
-        check(scann_hip_txh_build(source.handle(), &c, &h, report));
+        if (projection) check(scann_hip_txh_build_projected(source.handle(), projection->handle(), &c, &h, report));
+        else check(scann_hip_txh_build(source.handle(), &c, &h, report));
         if (ix_.h) scann_hip_index_destroy(ix_.h);
         ix_.h = h;
         n_ = source.dataset_size();
@@ -1522,6 +1577,8 @@ public:
         dataset_.reset();
         centers_.clear(); codebook_.clear(); leaf_off_.clear(); leaf_ids_.clear(); codes_.clear();
     }
+
+public:
 
     NNResultsVector search(const std::vector<float> &query, size_t k) const {   // mod.rs:240-294
         if (!ix_.h) throw ScannError::failed_precondition("Partitioner not built");
