@@ -523,6 +523,11 @@ int scann_hip_index_last_device_status(scann_hip_index *index, void *hip_stream)
  * candidate, UINT64_MAX = no bound.  The CALLER synchronises hip_stream first; the copy itself is synchronous.
  * OutOfRange when the workspace has never held nq bounds. */
 int scann_hip_index_debug_filter_bounds(scann_hip_index *index, void *hip_stream, uint32_t nq, uint64_t *out_bounds);
+/* Debugging aid of the sparse prefilter's plan: the bytes of survivor bitmaps that the searches enqueued on hip_stream
+ * (its workspace, else the primary one) have asked for so far -- 0 while every one of them flushed its survivors into
+ * lists inside the scan, else the size of the largest [queries rounded up to 64][ranges of 1024 points][32] u32 array a
+ * call of the bitmap form (SCANN_HIP_SP_BITMAP) wanted.  No device work. */
+int scann_hip_index_debug_survivor_bitmap_bytes(scann_hip_index *index, void *hip_stream, uint64_t *out_bytes);
 /* Debugging aid of the 8-bit row filter in front of the exact re-rank: copies what the last batched search enqueued on
  * hip_stream (its workspace, else the primary one) left there for nq queries of pre_reorder_k = m: the ordered lower
  * and upper bounds of every candidate's exact distance (out_lb, out_ub: [nq][m] u32, the order-preserving image of

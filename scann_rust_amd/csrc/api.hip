@@ -72,7 +72,8 @@ struct TxhWorkspace {
         cand_idx, cand_dist, cand_exact, cand_row, cand_count, out_idx, out_dist, out_count, allow,
         sbase, pair_sbase, stile_off, samp, lut8, lut8_meta, cand32, cand32_codes, cand32_cnt, mfma_thr1, rr_lb, rr_ub, small_tickets,
           wide_min, wide_ckey, wide_ceb, wide_cidx, wide_cnt,
-        proj_q;   // projected handles: [nq][dim] projected queries (last: the buffers before it keep their places)
+        proj_q,   // projected handles: [nq][dim] projected queries (behind the rest: the buffers before it keep their places)
+        surv;     // sparse prefilter's survivor bitmaps (likewise)
     void *arena = nullptr;
     size_t arena_bytes = 0;
     bool dirty = false;
@@ -88,7 +89,7 @@ struct TxhWorkspace {
                         &cand_key, &cand_idx, &cand_dist, &cand_exact, &cand_row, &cand_count, &out_idx, &out_dist,
                         &out_count, &allow, &sbase, &pair_sbase, &stile_off, &samp, &lut8, &lut8_meta, &cand32,
                         &cand32_codes, &cand32_cnt, &mfma_thr1, &rr_lb, &rr_ub, &small_tickets,
-                        &wide_min, &wide_ckey, &wide_ceb, &wide_cidx, &wide_cnt, &proj_q};
+                        &wide_min, &wide_ckey, &wide_ceb, &wide_cidx, &wide_cnt, &proj_q, &surv};
         for (WsBuf *b : all) f(*b);
     }
     void want(WsBuf &b, size_t bytes) {
@@ -1571,6 +1572,20 @@ static int plan_txh_search(const scann_hip_index *ix, uint32_t k, const scann_hi
         const bool flat = t.ah_mode && L == 1 && P == 1;
         p.sp_pairs64 = compiled && (kn.sp_pairs ? kn.sp_pairs == 64 : flat && (tiles32 % 2 == 0 || nq > 224));
     }
+    // ... which, on a flat hasher, end by storing the item's survivor bitmap as it stands in LDS (128 bytes per query and
+    // 1024 points) and leave the walk over its bits to the refine (adc_smfmac_bits_kernel64, adc_refine_bits_kernel): no
+    // lists, no atomics and no gathers in the kernel that runs at two waves per SIMD.  The bitmap is rewritten whole by
+    // every call, so its size is bounded: kSurvBytesMax covers a batch of 4096 queries over 1M points (489 MiB).
+    // SCANN_HIP_SP_BITMAP = 0 keeps the flush inside the scan.  (A forced 64-pair form on a tree index keeps it too.)
+    // Every batch size that runs 64-pair items takes the form: it won the sweep at 64, 256 and 1024 queries.
+    {
+        constexpr uint64_t kSurvBytesMax = 512ull << 20;
+        const uint64_t nranges = ((uint64_t)t.n_local + kSpRange64 - 1) / kSpRange64;
+        const uint64_t rows = ((uint64_t)nq + 63) / 64 * 64;
+        const bool flat = t.ah_mode && L == 1 && P == 1;
+        p.surv_stride = (uint32_t)(nranges * 32);
+        p.sp_bitmap = p.sp_pairs64 && flat && kn.sp_bitmap && rows * nranges * 128 <= kSurvBytesMax;
+    }
     // The survivors' codes travel with their positions for flat hashers: their ~12 k survivors per query
     // are spread over the whole code array (random 16-byte gathers from 16 MB: refine 145 -> 65 us at
     // C3).  In a tree index the survivors sit densely in the query's nearest leaves, the gathers hit
@@ -1681,11 +1696,15 @@ static int ensure_txh_workspace(scann_hip_index *ix, TxhWorkspace &s, const TxhP
         s.want(s.lut8, (size_t)max_slots * t.S * 16 + 64);
         s.want(s.lut8_meta, (size_t)(max_slots + 4) * 16);
         s.want(s.mfma_thr1, (size_t)(max_slots + 4) * 4);
-        s.want(s.cand32, (size_t)nq * p.cap32 * 4);
-        // flat hashers: the survivors' packed codes (dense prefilter) or plane rows (sparse prefilter) travel with them
-        if (t.ah_mode)
-            s.want(s.cand32_codes, (size_t)nq * p.cap32 * std::max(t.S / 8, p.scan == TxhScan::Smfmac ? sp_words(t.S) : 0u) * 4);
-        s.want(s.cand32_cnt, (size_t)nq * 4);
+        if (p.sp_bitmap) {   // survivor bitmaps instead of lists
+            s.want(s.surv, ((size_t)nq + 63) / 64 * 64 * p.surv_stride * 4);
+        } else {
+            s.want(s.cand32, (size_t)nq * p.cap32 * 4);
+            // flat hashers: the survivors' packed codes (dense prefilter) or plane rows (sparse prefilter) travel with them
+            if (t.ah_mode)
+                s.want(s.cand32_codes, (size_t)nq * p.cap32 * std::max(t.S / 8, p.scan == TxhScan::Smfmac ? sp_words(t.S) : 0u) * 4);
+            s.want(s.cand32_cnt, (size_t)nq * 4);
+        }
     }
     if (small) s.want(s.small_tickets, 64 * 4);
     if (ix->proj.kind) s.want(s.proj_q, (size_t)nq * t.dim * 4);
@@ -1713,9 +1732,13 @@ static int ensure_txh_workspace(scann_hip_index *ix, TxhWorkspace &s, const TxhP
         w->lut8 = s.lut8.as<int8_t>();
         w->lut8_meta = s.lut8_meta.p;
         w->mfma_thr1 = s.mfma_thr1.as<int>();
-        w->cand32 = s.cand32.as<uint32_t>();
-        w->cand32_codes = t.ah_mode ? s.cand32_codes.as<uint32_t>() : nullptr;
-        w->cand32_cnt = s.cand32_cnt.as<uint32_t>();
+        if (p.sp_bitmap) {
+            w->surv = s.surv.as<uint32_t>();
+        } else {
+            w->cand32 = s.cand32.as<uint32_t>();
+            w->cand32_codes = t.ah_mode ? s.cand32_codes.as<uint32_t>() : nullptr;
+            w->cand32_cnt = s.cand32_cnt.as<uint32_t>();
+        }
     }
     if (small) w->small_tickets = s.small_tickets.as<uint32_t>();
     if (ix->proj.kind) w->proj_q = s.proj_q.as<float>();
@@ -2366,6 +2389,18 @@ int scann_hip_index_debug_filter_bounds(scann_hip_index *ix, void *hip_stream, u
     if (!ws->thr.p || ws->thr.bytes < (size_t)nq * 8)
         return fail(SCANN_HIP_OUT_OF_RANGE, "no batched search of that many queries has run in this workspace");
     SCANN_HIP_CHECK(hipMemcpy(out_bounds, ws->thr.p, (size_t)nq * 8, hipMemcpyDeviceToHost));
+    return SCANN_HIP_OK;
+}
+
+int scann_hip_index_debug_survivor_bitmap_bytes(scann_hip_index *ix, void *hip_stream, uint64_t *out_bytes) {
+    if (!ix || ix->kind != KIND_TXH) return fail(SCANN_HIP_INVALID_ARGUMENT, "not a tree / hasher index");
+    if (!out_bytes) return fail(SCANN_HIP_INVALID_ARGUMENT, "out_bytes is null");
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    std::lock_guard<std::mutex> lock(ix->mu);
+    const TxhWorkspace *ws = &ix->ws;
+    for (auto &d : ix->dslots)
+        if (d.used && d.key == st && d.ws) ws = d.ws;
+    *out_bytes = ws->surv.need;
     return SCANN_HIP_OK;
 }
 

@@ -29,6 +29,9 @@
 // SCANN_HIP_SP_PAIRS                32 / 64: pairs per item of the sparse prefilter, where the     every call
 //                                   64-pair form is compiled (S <= 32, lane-walk flush); default:
 //                                   by the batch, flat hashers only
+// SCANN_HIP_SP_BITMAP               0: 64-pair items of a flat hasher flush their survivors into   every call
+//                                   lists inside the scan (default: the scan stores the survivor
+//                                   bitmap and the refine walks it)
 // SCANN_HIP_THR_TIES                0: filter bound on the distance alone (diagnostics)            every call
 // SCANN_HIP_THR_TAIL                0: filter bound by the full histogram select                   every call
 // SCANN_HIP_SAMPLE_MFMA             0: flat hashers score the bound's sample with the f32 gather   every call
@@ -79,6 +82,7 @@ struct Knobs {
     bool rerank_expand = true;
     int sp_words = -1;                    // -1 = by index kind
     int sp_pairs = 0;                     // 0 = by the batch (api.hip plan_txh_search)
+    bool sp_bitmap = true;
     bool thr_ties = true;
     bool thr_tail = true;
     bool sample_mfma = true;
@@ -131,7 +135,8 @@ inline Knobs read_knobs() {
         else if (is("SCANN_HIP_SP_PAIRS")) {
             const int n = atoi(v);
             if (n == 32 || n == 64) k.sp_pairs = n;
-        } else if (is("SCANN_HIP_THR_TIES")) k.thr_ties = atoi(v) != 0;
+        } else if (is("SCANN_HIP_SP_BITMAP")) k.sp_bitmap = atoi(v) != 0;
+        else if (is("SCANN_HIP_THR_TIES")) k.thr_ties = atoi(v) != 0;
         else if (is("SCANN_HIP_THR_TAIL")) k.thr_tail = atoi(v) != 0;
         else if (is("SCANN_HIP_SAMPLE_MFMA")) k.sample_mfma = atoi(v) != 0;
         else if (is("SCANN_HIP_FUSED")) k.fused = atoi(v) != 0;

@@ -47,6 +47,11 @@ constexpr uint32_t kWideMinStream = 16384;                // ... and the stream 
 constexpr int kWideRep = 4;                               // ... ADC stream positions per thread of its scan
 constexpr uint32_t kFusedChunk = kSelectThreads;          // one-launch small pipeline: stream positions per workgroup
 constexpr uint32_t kFusedMaxWgs = 512;                    // ... nq x workgroups per query above which three launches are used
+// points per work item of the sparse prefilter's 64-pair form (adc_smfmac_body, CT = 2: two column tiles per point tile)
+#ifndef SCANN_SP_RANGE64
+#define SCANN_SP_RANGE64 1024
+#endif
+constexpr uint32_t kSpRange64 = SCANN_SP_RANGE64;
 constexpr uint32_t kDecodeStage = 512;                    // selected leaves whose decode tables are staged in LDS
 constexpr uint32_t kThrTailMaxRank = 384;                 // J above this takes threshold_select_kernel
 
@@ -166,6 +171,8 @@ struct TxhPlan {
     uint32_t cap32;            // survivors per query of the MFMA prefilter
     bool sp_words;             // sparse prefilter's survivor flush: word-parallel (else lanes walk their own words)
     bool sp_pairs64;           // sparse prefilter's items: 64 pairs x 1024 points (else 32 x 2048); S <= 32, lane-walk flush
+    bool sp_bitmap;            // ... 64-pair items that end by storing their survivor bitmap (surv); the refine walks it
+    uint32_t surv_stride;      // words per query of surv: ranges of kSpRange64 points x 32
     bool codes_in_list;        // prefilter survivors carry their packed codes / plane rows
     bool thr_ties;             // filter bound on (distance, stream position); false: on the distance alone
     bool thr_tail;             // filter bound by threshold_tail_kernel (else threshold_select_kernel)
@@ -205,6 +212,7 @@ struct TxhWork : TxhPlan {
     uint32_t *cand32_cnt;      // [nq]
     uint32_t *cand32;          // [nq][cap32] stream positions of the prefilter's survivors
     uint32_t *cand32_codes;    // [nq][cap32][S/8] their packed codes (written next to the positions)
+    uint32_t *surv;            // [nq rounded up to 64][surv_stride] survivor bitmaps (sp_bitmap; then no cand32*)
     uint32_t *small_done;      // small-batch host calls: [nq] pinned completion flags (or nullptr) ...
     uint32_t small_seq;        // ... and the value the finish kernel stores there after the result rows
     uint32_t *small_tickets;   // [kSmallBatch] ticket counters of the one-launch pipeline (zero between launches)

@@ -191,11 +191,7 @@ __device__ __forceinline__ uint32_t grab_tile(uint32_t *queues, uint32_t total_t
 #define SCANN_MFMA_RANGE 2048
 #endif
 constexpr uint32_t kMfmaRange = SCANN_MFMA_RANGE;     // points per item
-// ... of the sparse prefilter's 64-pair form (adc_smfmac_body, CT = 2: two column tiles per point tile)
-#ifndef SCANN_SP_RANGE64
-#define SCANN_SP_RANGE64 1024
-#endif
-constexpr uint32_t kSpRange64 = SCANN_SP_RANGE64;
+// ... of the sparse prefilter's 64-pair form: kSpRange64 (txh.h; the plan sizes the survivor bitmaps by it)
 
 // per pair slot, next to its quantised tables (lut8_build_kernel, txh_prefilter.hip; read again by K5e in txh.hip)
 struct Lut8Meta {

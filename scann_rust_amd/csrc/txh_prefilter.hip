@@ -1,5 +1,15 @@
 // txh_prefilter.hip -- the integer-MFMA scans of the tree / flat-hasher search (see txh.hip for the pipeline): K6d / K6e,
 // the dense and 2:4-sparse prefilters with their table and operand-plane builds, and the exact refine.
+//
+// Launch order of launch_prefilter_refine (one stream; the timing events enclose the scan alone):
+//   lut8_build_kernel                          quantised tables (sparse prefilter: the pass bound folded in)
+//   adc_mfma16 / adc_mfma / adc_smfmac[_wide][_pq]_kernel / adc_smfmac[_pq]_kernel64
+//                                              survivors -> per-query lists (cand32, cand32_codes, cand32_cnt)
+//   adc_refine_kernel                          lists -> exact keys, key <= T -> cand / cand_cnt
+// and under TxhPlan::sp_bitmap (flat hashers, 64-pair items; SCANN_HIP_SP_BITMAP=0 keeps the order above):
+//   lut8_build_kernel
+//   adc_smfmac_bits_kernel64                   each item's survivor bitmap -> surv[query][range * 32 ..], no lists
+//   adc_refine_bits_kernel                     walks the query's row of surv, allow test, exact keys -> cand / cand_cnt
 #include "launch.h"
 #include "txh_dev.h"
 #include "txh_stages.h"
@@ -194,6 +204,8 @@ struct MfmaArgs {
     uint32_t cap32;
     const uint64_t *allow;    // the search's allow-bitmap (or nullptr): disallowed survivors never enter the lists,
     uint64_t allow_bits;      // so that the filter bounds them as it bounds the gather scan's (cap32 assumes it)
+    uint32_t *surv;           // [nq rounded up to 64][surv_stride] survivor bitmaps (adc_smfmac_bits_kernel64), else unused
+    uint32_t surv_stride;     // words per query: ranges of kSpRange64 points x 32
 };
 
 // The survivor mask `m` of a prefilter tile without its disallowed points: bit b of m stands for the point at leaf
@@ -836,17 +848,74 @@ __device__ SCANN_SP_FLUSH_INLINE void sp_flush_item_words(const uint32_t *__rest
     }
 }
 
+#ifndef SCANN_SP_BITS_RUN_MAX
+#define SCANN_SP_BITS_RUN_MAX 8
+#endif
+constexpr uint32_t kSpBitsRunMax = SCANN_SP_BITS_RUN_MAX;   // queue entries a wave of the BITMAP form takes at once, at most
+// grab_tile (txh_dev.h) for `run` entries of one queue at once: the tiles first, first + 8, ... (*cnt of them; the run
+// is cut at the queue's end).  kInvalid = no tiles left.
+__device__ __forceinline__ uint32_t grab_run(uint32_t *queues, uint32_t total_tiles, uint32_t run, uint32_t *cnt) {
+    const uint32_t xcd = blockIdx.x & 7u;
+    for (uint32_t a2 = 0; a2 < 8u; ++a2) {
+        const uint32_t x = (xcd + a2) & 7u;
+        const uint32_t nx = (total_tiles + 7u - x) >> 3;   // tiles = x (mod 8)
+        uint32_t *ctr = queues + x * CNT_XQ_STRIDE;
+        if (a2 && __hip_atomic_load(ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= nx) continue;
+        const uint32_t l = atomicAdd(ctr, run);
+        if (l < nx) {
+            *cnt = min(run, nx - l);
+            return l * 8u + x;
+        }
+    }
+    *cnt = 0;
+    return kInvalid;
+}
+
+// The item's end in the BITMAP form of the 64-pair items (flat hashers): the wave copies the item's survivor bitmap
+// from LDS to the queries' rows of `surv` as it stands -- query q's 32 words of this range, [tt][h] (128 contiguous
+// bytes), at surv[q][range * 32 ..]: bit bpos of word [tt][h] is point
+//     jrel = (2 tt + (bpos >> 4)) * 32 + 4 h + (r & 3) + ((r >> 2) << 3),  r = 15 - (bpos & 15)
+// of the range.  Words past the item's last tile pair are written as zero (s_bits holds an earlier item's words there),
+// padding pairs write nothing.  Every (query, range) belongs to exactly one item of a call, so the rows need no
+// clearing and nothing of an earlier call is ever read.  Nothing here waits on memory: eight 16-byte stores per lane,
+// eight neighbouring lanes to a query's line.  adc_refine_bits_kernel walks the rows.
+__device__ __forceinline__ void sp_store_item_bits(uint32_t *__restrict__ surv, uint32_t stride, const uint32_t *bits_w,
+                                                   uint32_t ntile, uint32_t range, const uint32_t (&pq)[2]) {
+    constexpr uint32_t TTM = SpItem<2>::TTM;
+    static_assert(TTM == 16, "a query's words of an item: 16 tile pairs x 2 halves = 128 bytes");
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t ntt = (ntile + 1u) >> 1;
+    const uint32_t k = lane & 7u;           // the 16-byte part of a pair's 128 bytes: words [2k][0], [2k][1], [2k+1][0], [2k+1][1]
+    __builtin_amdgcn_wave_barrier();        // (the words of the other lanes)
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const uint32_t p = (uint32_t)i * 8u + (lane >> 3);   // pair of the item: column tile i >> 2, column p & 31
+        const uint32_t q = (uint32_t)__shfl((int)pq[i >> 2], (int)(p & 31u));
+        const uint32_t *src = bits_w + ((uint32_t)(i >> 2) * TTM + 2u * k) * 64u + (p & 31u);
+        // (the eight lanes of a pair read the same bank, 128 words apart: 8-way, ~500 LDS cycles an item against the
+        // ~40 k cycles of its MFMAs; the stores stay whole lines)
+        uint4 v;
+        v.x = src[0]; v.y = src[32]; v.z = src[64]; v.w = src[96];
+        if (2u * k >= ntt) v.x = v.y = 0u;
+        if (2u * k + 1u >= ntt) v.z = v.w = 0u;
+        if (q != kInvalid) *reinterpret_cast<uint4 *>(surv + (size_t)q * stride + range * 32u + 4u * k) = v;
+    }
+    __builtin_amdgcn_wave_barrier();        // (before the next item's tile loop writes the words again)
+}
+
 // WORDS: the word-parallel flush (tree indexes); else lanes walk their own words (flat).  CT: column tiles of 32 pairs
 // scored against each point tile.  With CT = 2 the point side of a tile step -- the plane words, their unpacking, the
 // byte extractions and every LDS operand read -- is paid once for two MFMA chains (18 MFMAs at S = 32), the wave holds
 // both tiles' tables (128 registers at S = 32) and two accumulator pairs, and runs at two waves per SIMD.
-template <int S_, bool WORDS, int CT>
+// BITMAP (CT = 2 only): the item ends with sp_store_item_bits instead of a flush -- no lists, no allow-list, no stage.
+template <int S_, bool WORDS, int CT, bool BITMAP = false>
 __device__ __forceinline__ void adc_smfmac_body(const TxhIndexDev &ix, const MfmaArgs &a, const uint64_t allow_stride) {
     typedef int v4i __attribute__((ext_vector_type(4)));
     typedef int v8i __attribute__((ext_vector_type(8)));
     typedef int v16i __attribute__((ext_vector_type(16)));
     typedef SpLayout<S_> SP;
     static_assert(CT == 1 || (CT == 2 && !WORDS && S_ <= 32), "64-pair items: lane-walk flush, S <= 32");
+    static_assert(!BITMAP || CT == 2, "the bitmap form is a form of the 64-pair items");
     constexpr int S = S_, NS = SP::NS, KT = NS + 2, NWP = SP::NWP, SPW = SP::SPW;
     // operands in flight ahead of the MFMA that consumes them (CT = 2: every operand feeds two MFMAs, so about the same
     // cover in MFMA slots from fewer registers)
@@ -861,8 +930,12 @@ __device__ __forceinline__ void adc_smfmac_body(const TxhIndexDev &ix, const Mfm
     // of lane (col, h) in column tile ct.  Written once per two tiles with one conflict-free ds_write_b32; no atomics, no
     // branches and no waits in the tile loop -- the item's flush turns it into list entries.
     __shared__ uint32_t s_bits[kMfmaWaves][CT * kTT][64];
-    __shared__ uint2 s_stage[kMfmaWaves][SpItem<CT>::STAGE];                         // flush: staged list entries
-    __shared__ uint32_t s_fq[kMfmaWaves][32 * CT], s_fvb[kMfmaWaves][32 * CT], s_fgb[kMfmaWaves][32 * CT];   // flush: per pair
+    // (BITMAP: no flush.  Its one-element arrays are never referenced and take no LDS -- the kernel's 33 344 bytes are the
+    // bitmap and the three operand tables; declaring them through a conditional type changed the instruction streams of
+    // the list-form kernels, which this form leaves as they were.)
+    constexpr uint32_t kStage = BITMAP ? 1u : SpItem<CT>::STAGE, kRows = BITMAP ? 1u : 32u * CT;
+    __shared__ uint2 s_stage[kMfmaWaves][kStage];                                    // flush: staged list entries
+    __shared__ uint32_t s_fq[kMfmaWaves][kRows], s_fvb[kMfmaWaves][kRows], s_fgb[kMfmaWaves][kRows];   // flush: per pair
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const uint32_t col = lane & 31u, h = lane >> 5;
     if (tid < 64) {
@@ -888,12 +961,33 @@ __device__ __forceinline__ void adc_smfmac_body(const TxhIndexDev &ix, const Mfm
         int iv[D];
     };
 
+    // BITMAP: a wave takes `run` entries of a queue at once -- tiles 8 apart, which on a flat hasher are ranges 8 apart
+    // of the same pair tile -- and keeps its table fragments (32 KB of loads an item at S = 32) while the pair tile
+    // stays the same.  run = the items a wave gets anyway (at most 8), so the queues still hand every wave its share.
+    uint32_t run = 1, left = 0;   // left: tiles of the current run behind `tile`
+    if constexpr (BITMAP) run = min(kSpBitsRunMax, max(1u, (total_tiles + gridDim.x * kMfmaWaves - 1u) / (gridDim.x * kMfmaWaves)));
+    uint32_t have_slot0 = kInvalid, have_pt = kInvalid;   // BITMAP: the pair tile whose tables the wave holds
     uint32_t tile = 0;
-    if (lane == 0) tile = grab_tile(a.counters + CNT_XQ, total_tiles);
+    if constexpr (BITMAP) {
+        uint32_t cnt = 0;
+        if (lane == 0) tile = grab_run(a.counters + CNT_XQ, total_tiles, run, &cnt);
+        left = (uint32_t)__builtin_amdgcn_readfirstlane(cnt);
+        left = left ? left - 1u : 0u;
+    } else {
+        if (lane == 0) tile = grab_tile(a.counters + CNT_XQ, total_tiles);
+    }
     tile = __builtin_amdgcn_readfirstlane(tile);
+    // this lane's pair (column) of each column tile: tables (the pass bound is folded into them), key base
+    uint32_t pq[CT], vb[CT];
+    v4i bd[CT][2];
+    v8i bs[CT][NS];
     while (tile != kInvalid) {
-        uint32_t next_tile = 0;
-        if (lane == 0) next_tile = grab_tile(a.counters + CNT_XQ, total_tiles);
+        uint32_t next_tile = 0, next_cnt = 0;
+        if constexpr (BITMAP) {
+            if (left == 0 && lane == 0) next_tile = grab_run(a.counters + CNT_XQ, total_tiles, run, &next_cnt);
+        } else {
+            if (lane == 0) next_tile = grab_tile(a.counters + CNT_XQ, total_tiles);
+        }
         const WorkItem item = decode_item(ix, a.tile_off, a.pair_off, tile);
         const uint32_t lb = item.lb, size = item.size, local = item.local, slot0 = item.slot0, slot_end = item.slot_end;
         const uint32_t nranges = (size + kRange - 1) / kRange;
@@ -901,10 +995,10 @@ __device__ __forceinline__ void adc_smfmac_body(const TxhIndexDev &ix, const Mfm
         const uint32_t c0 = range * kRange;
         const uint32_t npts = min(kRange, size - c0);
 
-        // this lane's pair (column) of each column tile: tables (the pass bound is folded into them), key base
-        uint32_t pq[CT], vb[CT];
-        v4i bd[CT][2];
-        v8i bs[CT][NS];
+        const bool reload = !BITMAP || slot0 != have_slot0 || pt != have_pt;   // (wave-uniform)
+        have_slot0 = slot0;
+        have_pt = pt;
+        if (reload) {
 #pragma unroll
         for (int ct = 0; ct < CT; ++ct) {
             const uint32_t slot = slot0 + pt * (32u * CT) + (uint32_t)ct * 32u + col;
@@ -927,6 +1021,7 @@ __device__ __forceinline__ void adc_smfmac_body(const TxhIndexDev &ix, const Mfm
 #pragma unroll
                 for (int kt = 0; kt < NS; ++kt) bs[ct][kt] = v8i{k7, k7, k7, k7, k7, k7, k7, k7};
             }
+        }
         }
 
         const uint32_t ntile = (npts + 31u) >> 5;
@@ -1065,13 +1160,26 @@ __device__ __forceinline__ void adc_smfmac_body(const TxhIndexDev &ix, const Mfm
         }
         // ---- flush: the item's bitmap -> the queries' lists (sp_flush_item: its own function, so that its registers
         // are allocated apart from the tile loop's -- inlined, the loop spilled its table fragments)
-        if constexpr (WORDS)
+        if constexpr (BITMAP)
+            sp_store_item_bits(a.surv, a.surv_stride, &s_bits[wave][0][0], ntile, range, pq);
+        else if constexpr (WORDS)
             sp_flush_item_words<S>(ix.codes_sp, ix, a.allow, a.allow_bits, allow_stride, a.cand32_cnt, a.cand32, a.cand32_codes, a.cap32, &s_bits[wave][0][0],
                                    s_stage[wave], s_fq[wave], s_fvb[wave], s_fgb[wave], ntile, c0, lb, pq[0], vb[0]);
         else
             sp_flush_item_lanes<S, CT>(ix.codes_sp, ix, a.allow, a.allow_bits, allow_stride, a.cand32_cnt, a.cand32, a.cand32_codes, a.cap32, bits, s_stage[wave],
                                        s_fq[wave], s_fvb[wave], s_fgb[wave], ntile, c0, lb, pq, vb);
-        tile = __builtin_amdgcn_readfirstlane(next_tile);
+        if constexpr (BITMAP) {
+            if (left) {
+                tile += 8u;
+                --left;
+            } else {
+                tile = __builtin_amdgcn_readfirstlane(next_tile);
+                left = (uint32_t)__builtin_amdgcn_readfirstlane(next_cnt);
+                left = left ? left - 1u : 0u;
+            }
+        } else {
+            tile = __builtin_amdgcn_readfirstlane(next_tile);
+        }
     }
 }
 
@@ -1108,6 +1216,13 @@ __global__ __launch_bounds__(kMfmaWaves * 64, 2) void adc_smfmac_kernel64(TxhInd
 template <int S_>
 __global__ __launch_bounds__(kMfmaWaves * 64, 2) void adc_smfmac_pq_kernel64(TxhIndexDev ix, MfmaArgs a, uint64_t allow_stride) {
     adc_smfmac_body<S_, false, 2>(ix, a, allow_stride);
+}
+
+// ... and its BITMAP form: the item's survivor bitmap goes to MfmaArgs::surv as it is (no lists, no allow-list: the
+// refine tests it).  Its LDS is the bitmap alone (32 KB a workgroup); registers still hold it at two waves per SIMD.
+template <int S_>
+__global__ __launch_bounds__(kMfmaWaves * 64, 2) void adc_smfmac_bits_kernel64(TxhIndexDev ix, MfmaArgs a) {
+    adc_smfmac_body<S_, false, 2, true>(ix, a, 0);
 }
 
 // The prefilter with 16-pair tiles on v_mfma_i32_16x16x64_i8, for leaves scanned by 8-24 queries of the batch
@@ -1323,6 +1438,8 @@ struct RefineArgs {
     const uint64_t *allow;
     uint64_t allow_bits, allow_stride;
     int planes;   // cand32_codes holds codes_sp plane rows (adc_smfmac_kernel), not packed codes
+    const uint32_t *surv;   // adc_refine_bits_kernel: [nq..][surv_stride] survivor bitmaps (adc_smfmac_bits_kernel64)
+    uint32_t surv_stride;   // words per query (a multiple of 32)
 };
 
 // code of subspace s from a point's plane row (SpLayout: [ha][plane V, N][word]); ca / cb = the code nibbles of the
@@ -1509,6 +1626,139 @@ __global__ __launch_bounds__(kRefineThreads) void adc_refine_kernel(TxhIndexDev 
     if (tid == 0) a.cand_cnt[q] = s_out;   // > cap: select_rerank reports the overflow
 }
 
+// The refine behind adc_smfmac_bits_kernel64 (flat hashers: one leaf, P = 1): block per query, the query's table staged
+// in LDS as above; the survivors come from the query's row of the bitmap (sp_store_item_bits gives the bit -> point
+// map) and their plane rows from ix.codes_sp.  The row is ~1 % dense, so a thread that scored the bits of its own words
+// would leave three lanes in four idle: every wave takes the row 256 words at a time (one 16-byte load per lane, the
+// next one in flight), its lanes push the points of their words' set bits onto the wave's LDS queue (a DPP prefix gives
+// each lane its place), and whenever the queue holds kRefineBitsU full waves of points they are popped off its end
+// and scored side by side -- allow bit first, then the plane-row gather, SpRow decode, the sequential f32 sum, the key
+// and key <= T, as adc_refine_kernel does them.  A chunk that holds more points than the queue has room for (dense
+// rows: a bound every point meets) is pushed in rounds.  All blocks walk their rows upwards from word 0, so the batch
+// sweeps the plane array roughly together and its lines repeat in the L2s.
+#ifndef SCANN_REFINE_BITS_THREADS
+#define SCANN_REFINE_BITS_THREADS 256
+#endif
+constexpr uint32_t kRefineBitsThreads = SCANN_REFINE_BITS_THREADS;   // (512: refine 135 us against 119 us at the flagship)
+constexpr uint32_t kRefineBitsU = 4;            // points per lane scored side by side
+constexpr uint32_t kRefineBitsQueue = 1024;     // points a wave's queue holds
+static_assert(kRefineBitsQueue > 2 * 64 * kRefineBitsU, "room for a push on top of what a pop leaves");
+
+template <typename C>
+__global__ __launch_bounds__(kRefineBitsThreads, kRefineBitsThreads >= 512 ? 8 : 4) void adc_refine_bits_kernel(TxhIndexDev ix, RefineArgs a) {
+    constexpr int S = C::S;
+    constexpr int SPW = SpLayout<S>::SPW;
+    constexpr uint32_t U = kRefineBitsU, POP = 64u * U, NWAVES = kRefineBitsThreads / 64u;
+    static_assert(C::BITS == 4 && kSpRange64 == 1024, "plane rows; 32 bitmap words per (query, range)");
+    extern __shared__ __attribute__((aligned(16))) float s_tab[];       // [S][16]
+    __shared__ uint32_t s_queue[NWAVES][kRefineBitsQueue];
+    __shared__ uint32_t s_out;
+    const uint32_t q = blockIdx.x, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint64_t T = a.thr[q];
+    const uint32_t vb = a.vbase[(size_t)q * 2];                         // (P = 1: [nq][2])
+    const uint32_t lb = ix.leaf_off[a.tokens[q]];
+    const uint32_t slot = a.slot_of[q];
+    if (tid == 0) s_out = 0;
+    for (uint32_t e = tid; e < (uint32_t)S * 16u; e += kRefineBitsThreads)   // this query's table, de-interleaved: [s][16]
+        s_tab[e] = slot == kInvalid ? 0.0f : a.lutq[((size_t)(slot >> 2) * S * 16 + e) * 4 + (slot & 3u)];
+    __syncthreads();
+    uint64_t *out = a.cand + (size_t)q * a.cap;
+    const uint4 *row4 = reinterpret_cast<const uint4 *>(a.surv + (size_t)q * a.surv_stride);
+    const uint32_t n4 = a.surv_stride / 4u;
+    uint32_t *queue = s_queue[wave];
+
+    // scores the n <= POP points queue[0 .. n) (n wave-uniform)
+    auto score = [&](const uint32_t *pts, uint32_t n) {
+        uint32_t j[U];
+        bool ok[U];
+        uint4 rw[U][SPW / 4];
+#pragma unroll
+        for (uint32_t u = 0; u < U; ++u) {
+            const uint32_t e = lane + 64u * u;
+            ok[u] = e < n;
+            j[u] = ok[u] ? pts[e] : 0u;
+        }
+        if (a.allow) {   // (block-uniform)
+#pragma unroll
+            for (uint32_t u = 0; u < U; ++u)
+                ok[u] = ok[u] && row_allowed(ix, a.allow, a.allow_stride, q, a.allow_bits, lb + j[u]);
+        }
+#pragma unroll
+        for (uint32_t u = 0; u < U; ++u)
+#pragma unroll
+            for (int x = 0; x < SPW / 4; ++x)
+                rw[u][x] = reinterpret_cast<const uint4 *>(ix.codes_sp + (size_t)(lb + (ok[u] ? j[u] : 0u)) * SPW)[x];
+#pragma unroll
+        for (uint32_t u = 0; u < U; ++u) {
+            uint32_t w[SPW];
+#pragma unroll
+            for (int x = 0; x < SPW / 4; ++x) {
+                w[4 * x] = rw[u][x].x; w[4 * x + 1] = rw[u][x].y; w[4 * x + 2] = rw[u][x].z; w[4 * x + 3] = rw[u][x].w;
+            }
+            SpRow<S> r;
+            r.decode(w);
+            float acc = 0.0f;
+#pragma unroll
+            for (int s2 = 0; s2 < S; ++s2) {
+                const float tv = s_tab[s2 * 16 + r.code(s2)];
+                acc = s2 == 0 ? tv : acc + tv;
+            }
+            const uint64_t key = make_key(acc, vb + j[u]);
+            const bool keep = ok[u] && key <= T;
+            uint32_t wtot;
+            const uint32_t wpre = wave_prefix_count(keep, &wtot);
+            uint32_t base = 0;
+            if (lane == 0 && wtot) base = atomicAdd(&s_out, wtot);
+            base = (uint32_t)__shfl((int)base, 0);
+            if (keep && base + wpre < a.cap) out[base + wpre] = key;
+        }
+    };
+
+    uint32_t qn = 0;   // points in the wave's queue (wave-uniform)
+    uint4 nxt = wave * 64u + lane < n4 ? row4[wave * 64u + lane] : make_uint4(0u, 0u, 0u, 0u);
+    for (uint32_t c = wave; c * 64u < n4; c += NWAVES) {
+        uint32_t w[4] = {nxt.x, nxt.y, nxt.z, nxt.w};
+        {
+            const uint32_t i4 = (c + NWAVES) * 64u + lane;
+            nxt = i4 < n4 ? row4[i4] : make_uint4(0u, 0u, 0u, 0u);
+        }
+        const uint32_t cnt = (uint32_t)(__popc(w[0]) + __popc(w[1]) + __popc(w[2]) + __popc(w[3]));
+        const uint32_t incl = wave_incl_scan(cnt);
+        const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+        if (total == 0) continue;
+        const uint32_t gw = (c * 64u + lane) * 4u;   // the lane's first word: range gw >> 5, words gw & 31 .. + 3
+        const uint32_t p0 = (gw >> 5) * kSpRange64;
+        uint32_t sq = incl - cnt;                    // the lane's next point in the chunk's order
+        for (uint32_t base = 0; base < total;) {
+            const uint32_t take = min(total - base, kRefineBitsQueue - qn);
+            const uint32_t lim = base + take;
+#pragma unroll
+            for (uint32_t x = 0; x < 4; ++x) {
+                const uint32_t wl = (gw & 31u) + x, tt = wl >> 1, h = wl & 1u;
+                while (w[x] && sq < lim) {
+                    const uint32_t bpos = (uint32_t)__ffs((int)w[x]) - 1u;
+                    w[x] &= w[x] - 1u;
+                    const uint32_t r = 15u - (bpos & 15u);
+                    const uint32_t jrel = (2u * tt + (bpos >> 4)) * 32u + 4u * h + (r & 3u) + ((r >> 2) << 3);
+                    queue[qn + sq - base] = p0 + jrel;
+                    ++sq;
+                }
+            }
+            qn += take;
+            base = lim;
+            __builtin_amdgcn_wave_barrier();
+            while (qn >= POP) {
+                qn -= POP;
+                score(queue + qn, POP);
+            }
+            __builtin_amdgcn_wave_barrier();
+        }
+    }
+    if (qn) score(queue, qn);   // (fewer than POP are left)
+    __syncthreads();
+    if (tid == 0) a.cand_cnt[q] = s_out;   // > cap: select_rerank reports the overflow
+}
+
 // =====================================================================================
 // launchers
 // =====================================================================================
@@ -1533,6 +1783,7 @@ int launch_prefilter_refine(const TxhIndexDev &ix, const TxhWork &w, hipStream_t
             ma.counters = w.counters; ma.lut8 = w.lut8; ma.meta = reinterpret_cast<const Lut8Meta *>(w.lut8_meta);
             ma.pair_thr = w.pair_thr; ma.cand32_cnt = w.cand32_cnt; ma.cand32 = w.cand32; ma.cand32_codes = codes_in_list ? w.cand32_codes : nullptr; ma.cap32 = w.cap32;
             ma.allow = w.allow; ma.allow_bits = w.allow_bits;
+            ma.surv = w.sp_bitmap ? w.surv : nullptr; ma.surv_stride = w.surv_stride;
             if (ev0) SCANN_HIP_CHECK(hipEventRecord(ev0, st));
             const bool words = w.sp_words;
             const dim3 mgrid((uint32_t)cus * 4u), mblock(kMfmaWaves * 64);   // 4 workgroups per CU (4 waves each)
@@ -1540,7 +1791,8 @@ int launch_prefilter_refine(const TxhIndexDev &ix, const TxhWork &w, hipStream_t
                 if constexpr (C::S <= 32) {
                     if (words) return fail(SCANN_HIP_INTERNAL, "64-pair items take the lane-walk flush");
                     const dim3 grid64((uint32_t)cus * 2u);
-                    if (w.allow && w.allow_stride) SCANN_TRY(launch(adc_smfmac_pq_kernel64<C::S>, grid64, mblock, 0, st, ix, ma, w.allow_stride));
+                    if (w.sp_bitmap) SCANN_TRY(launch(adc_smfmac_bits_kernel64<C::S>, grid64, mblock, 0, st, ix, ma));
+                    else if (w.allow && w.allow_stride) SCANN_TRY(launch(adc_smfmac_pq_kernel64<C::S>, grid64, mblock, 0, st, ix, ma, w.allow_stride));
                     else SCANN_TRY(launch(adc_smfmac_kernel64<C::S>, grid64, mblock, 0, st, ix, ma));
                 } else {
                     return fail(SCANN_HIP_INTERNAL, "64-pair items are compiled for S <= 32");
@@ -1567,6 +1819,17 @@ int launch_prefilter_refine(const TxhIndexDev &ix, const TxhWork &w, hipStream_t
             ra.cand32 = w.cand32; ra.cand32_codes = codes_in_list ? w.cand32_codes : nullptr; ra.cand_cnt = w.cand_cnt; ra.cand = w.cand; ra.counters = w.counters;
             ra.allow = w.allow; ra.allow_bits = w.allow_bits; ra.allow_stride = w.allow_stride;
             ra.planes = (w.scan == TxhScan::Smfmac && ra.cand32_codes) ? 1 : 0;
+            ra.surv = ma.surv; ra.surv_stride = ma.surv_stride;
+            if (w.sp_bitmap) {   // the scan left bitmaps, not lists
+                if (w.scan != TxhScan::Smfmac || !w.sp_pairs64 || w.P != 1 || !ra.surv)
+                    return fail(SCANN_HIP_INTERNAL, "survivor bitmaps are the 64-pair sparse prefilter's, P = 1");
+                if constexpr (C::S <= 32) {   // (as the 64-pair items themselves)
+                    SCANN_TRY(launch(adc_refine_bits_kernel<C>, dim3(w.nq), dim3(kRefineBitsThreads), (size_t)C::S * 16 * sizeof(float), st, ix, ra));
+                    return SCANN_HIP_OK;
+                } else {
+                    return fail(SCANN_HIP_INTERNAL, "64-pair items are compiled for S <= 32");
+                }
+            }
             const size_t lds_rf = w.P <= kRefineTablesMax ? (size_t)w.P * C::S * 16 * sizeof(float) : 16;
             SCANN_TRY(launch(adc_refine_kernel<C>, dim3(w.nq), dim3(kRefineThreads), lds_rf, st, ix, ra));
             return SCANN_HIP_OK;

@@ -38,7 +38,7 @@ EXPORTS = [
     "scann_hip_txh_create", "scann_hip_txh_create_quantized", "scann_hip_index_device_bytes",
     "scann_hip_search_opts_default", "scann_hip_search_batched", "scann_hip_search_batched_params", "scann_hip_index_reserve",
     "scann_hip_search_batched_device", "scann_hip_index_last_device_status", "scann_hip_index_debug_filter_bounds",
-    "scann_hip_index_debug_rerank_brackets",
+    "scann_hip_index_debug_rerank_brackets", "scann_hip_index_debug_survivor_bitmap_bytes",
     "scann_hip_crowd_table_slots", "scann_hip_index_set_crowding_attributes", "scann_hip_search_crowded",
     "scann_hip_index_reserve_crowded", "scann_hip_search_crowded_device",
     "scann_hip_index_set_crowding_attributes_md", "scann_hip_search_crowded_md", "scann_hip_search_crowded_md_device",
@@ -200,6 +200,7 @@ def load():
                                                   C.POINTER(SearchOpts), vp, vp, vp, vp]
     L.scann_hip_index_last_device_status.argtypes = [vp, vp]
     L.scann_hip_index_debug_filter_bounds.argtypes = [vp, vp, C.c_uint32, u64p]
+    L.scann_hip_index_debug_survivor_bitmap_bytes.argtypes = [vp, vp, u64p]
     L.scann_hip_index_debug_rerank_brackets.argtypes = [vp, vp, C.c_uint32, C.c_uint32, u32p, u32p, u32p, u32p]
     L.scann_hip_crowd_table_slots.restype = C.c_uint32
     L.scann_hip_crowd_table_slots.argtypes = [C.c_uint32]
@@ -639,6 +640,13 @@ class Index:
         out = np.zeros(nq, np.uint64)
         check(load().scann_hip_index_debug_filter_bounds(self.h, vp(stream), nq, ptr(out, u64p)))
         return out
+
+    def debug_survivor_bitmap_bytes(self, stream=0):
+        """bytes of survivor bitmaps the searches enqueued on `stream` have asked for (0: none of them took the sparse
+        prefilter's bitmap form).  scann_hip_index_debug_survivor_bitmap_bytes."""
+        out = C.c_uint64(0)
+        check(load().scann_hip_index_debug_survivor_bitmap_bytes(self.h, vp(stream), C.byref(out)))
+        return int(out.value)
 
     def debug_rerank_brackets(self, nq, m, stream=0):
         """(lb, ub, rows, counts) of the 8-bit row filter after the last batched search of nq queries with
