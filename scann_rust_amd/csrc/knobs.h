@@ -97,6 +97,19 @@ struct Knobs {
     double bf_filter_compact_max = 1.0;   // (every fraction: the crossover is not measured yet)
 };
 
+// The knobs' names, in the order of the bits of read_knobs' first-occurrence mask.
+constexpr const char *kKnobNames[] = {
+    "SCANN_HIP_DEVICE_SLOTS", "SCANN_HIP_SEARCH_SLOTS", "SCANN_HIP_RCCL_LIB", "SCANN_HIP_SMFMAC", "SCANN_HIP_RERANK_I8",
+    "SCANN_HIP_RERANK_STORE", "SCANN_HIP_RERANK_UNIFORM", "SCANN_HIP_BF_SHORTLIST_MIN_ROWS", "SCANN_HIP_LOAD_PIN",
+    "SCANN_HIP_SMALL", "SCANN_HIP_WIDE", "SCANN_HIP_RESIDENT", "SCANN_HIP_RES_CL", "SCANN_HIP_MFMA",
+    "SCANN_HIP_RERANK_I8_MIN", "SCANN_HIP_RERANK_EXPAND", "SCANN_HIP_SP_WORDS", "SCANN_HIP_SP_PAIRS",
+    "SCANN_HIP_SP_BITMAP", "SCANN_HIP_THR_TIES", "SCANN_HIP_THR_TAIL", "SCANN_HIP_SAMPLE_MFMA", "SCANN_HIP_FUSED",
+    "SCANN_HIP_SELECT_DIRECT", "SCANN_HIP_SELECT_REGS", "SCANN_HIP_LOCAL_PRUNE", "SCANN_HIP_COMM_FILL",
+    "SCANN_HIP_BF_SHORTLIST_TAIL", "SCANN_HIP_BF_SHORTLIST_MIN_QUERIES", "SCANN_HIP_BF_FILTER",
+    "SCANN_HIP_BF_FILTER_COMPACT_MAX"};
+constexpr int kKnobCount = (int)(sizeof(kKnobNames) / sizeof(kKnobNames[0]));
+static_assert(kKnobCount <= 32, "read_knobs tracks first occurrences in a 32-bit mask: one bit per name, widen `seen` first");
+
 // The first occurrence of a name wins, as with getenv.
 inline Knobs read_knobs() {
     Knobs k;
@@ -108,13 +121,12 @@ inline Knobs read_knobs() {
         if (!eq) continue;
         const size_t n = (size_t)(eq - e);
         const char *v = eq + 1;
-        int bit = 0;
-        auto is = [&](const char *s) {
-            const int b = bit++;
-            if (strlen(s) != n || memcmp(s, e, n) != 0 || ((seen >> b) & 1u)) return false;
-            seen |= 1u << b;
-            return true;
-        };
+        int id = -1;
+        for (int i = 0; i < kKnobCount && id < 0; ++i)
+            if (strlen(kKnobNames[i]) == n && memcmp(kKnobNames[i], e, n) == 0) id = i;
+        if (id < 0 || ((seen >> id) & 1u)) continue;
+        seen |= 1u << id;
+        auto is = [&](const char *s) { return strcmp(kKnobNames[id], s) == 0; };
         if (is("SCANN_HIP_DEVICE_SLOTS")) k.device_slots = atoi(v);
         else if (is("SCANN_HIP_SEARCH_SLOTS")) k.search_slots = (uint32_t)std::max(1, std::min(64, atoi(v)));
         else if (is("SCANN_HIP_RCCL_LIB")) k.rccl_lib = v;

@@ -24,6 +24,7 @@ FACTORS = (
     ("SCANN_HIP_RES_CL", (None, "1", "3")),
     ("SCANN_HIP_SP_WORDS", (None, "0", "1")),
     ("SCANN_HIP_SP_PAIRS", (None, "32", "64")),
+    ("SCANN_HIP_SP_BITMAP", (None, "0")),
     ("SCANN_HIP_THR_TIES", (None, "0")),
     ("SCANN_HIP_THR_TAIL", (None, "0")),
     ("SCANN_HIP_SAMPLE_MFMA", (None, "0")),
@@ -42,6 +43,7 @@ SMALL_BATCH, SMALL_MAX_CANDIDATES, SMALL_MAX_STREAM = 16, 1024, 262144
 WIDE_BATCH, WIDE_MAX_CANDIDATES, WIDE_MAX_STREAM, WIDE_MIN_STREAM = 4, 8192, 4 << 20, 16384
 SCAN_PPT, RES_THREADS, RES_QUADS = 2, 512, 4
 FUSED_CHUNK, FUSED_MAX_WGS, DECODE_STAGE, THR_TAIL_MAX_RANK = 1024, 512, 512, 384
+SP_RANGE64, SURV_BYTES_MAX = 1024, 512 << 20   # points per 64-pair item; api.hip plan_txh_search kSurvBytesMax
 S, TREE_P = 16, 3   # subspaces and partitions_to_search of the matrix's indexes (tests/test_gpu_knob_matrix.py)
 
 
@@ -211,6 +213,9 @@ def expected_plan(row, kind, stream, leaves, P=None):
     sp_pairs = _int(row, "SCANN_HIP_SP_PAIRS", 0)
     flat = ah and L == 1 and P == 1
     sp_pairs64 = compiled and (sp_pairs == 64 if sp_pairs else flat and (tiles32 % 2 == 0 or nq > 224))
+    # the bitmap form of the 64-pair items: flat hashers, unless the knob says 0 or the bitmaps pass the byte cap
+    sp_bitmap_bytes = -(-nq // 64) * 64 * -(-n // SP_RANGE64) * 128
+    sp_bitmap = sp_pairs64 and flat and row["SCANN_HIP_SP_BITMAP"] is None and sp_bitmap_bytes <= SURV_BYTES_MAX
     thr_ties = row["SCANN_HIP_THR_TIES"] is None
     thr_tail = row["SCANN_HIP_THR_TAIL"] is None and not no_threshold and J <= THR_TAIL_MAX_RANK and scap > 4096
     sample_mfma = (row["SCANN_HIP_SAMPLE_MFMA"] is None and thr_tail and thr_ties and is_mfma and ah and L == 1 and
@@ -221,6 +226,7 @@ def expected_plan(row, kind, stream, leaves, P=None):
     pinned = row["entry"] == "host" and pipeline != "staged"
     return dict(pipeline=pipeline, scan=scan, pinned=pinned, no_threshold=no_threshold, cap=cap, st=st, scap=scap, J=J,
                 fused=fused, thr_tail=thr_tail, sample_mfma=sample_mfma, sp_words=sp_words, sp_pairs64=sp_pairs64,
+                sp_bitmap=sp_bitmap, sp_bitmap_bytes=sp_bitmap_bytes if sp_bitmap else 0,
                 select_direct=row["SCANN_HIP_SELECT_DIRECT"] is None, select_regs=row["SCANN_HIP_SELECT_REGS"] is None,
                 use_i8=use_i8, i8_expand=row["SCANN_HIP_RERANK_EXPAND"] is None)
 

@@ -2,13 +2,16 @@
 
 csrc/knobs.h says of the SCANN_HIP_* switches read on every call: "None of them changes a result."  The rows of
 tests/knob_matrix.py hold every pair of levels of the batch size, pre_reorder_k, the entry point / filter and the
-sixteen knobs plan_txh_search reads.  Per index variant (flat hasher and tree, int8 and FP8 re-rank stores) every row
+seventeen knobs plan_txh_search reads.  Per index variant (flat hasher and tree, int8 and FP8 re-rank stores) every row
 runs on one long-lived handle, in an order that starts at the smallest shapes (the workspace arena is rebuilt mid-
 sequence, error and empty calls woven in), then on a second handle in a shuffled order that starts with the largest.
 
 Every row: the kernel scann_hip_index_last_kernel_ms names is the one the mirror (knob_matrix.expected_kernel) derives;
 counts and distance bits equal those of a default-knob call on a fresh handle, indices up to ties; the oracle's rows
 for eight fixed queries; unused slots empty; the device entry Ok; pass 2 bit-identical to pass 1.  No tolerance.
+On the flat hasher the form of the sparse prefilter's 64-pair items is read from the handle's workspace after every
+row: it holds survivor bitmaps sized by the largest bitmap-form row so far (the mirror's sp_bitmap), and none on a
+fresh handle that runs the same rows under SCANN_HIP_SP_BITMAP=0.
 
 Indexes from explicit random 4-bit codes (no training), S = 16, dim 32, 131 072 rows: the smallest at which the sample
 has more than 4096 points (the tail bound), the candidate list is longer than 4096 keys at m = 2000 (the select reads
@@ -242,8 +245,24 @@ def _disturb(index, kd, d):
         assert np.all(cnt == d["count"]), "%s: counts %s" % (d["name"], cnt)
 
 
-def _run_row(index, kd, row, ref, monkeypatch):
-    """the row's call on `index` under its knobs, with every check that needs no other pass; returns its outputs"""
+def _stream():
+    import torch
+    return torch.cuda.current_stream(torch.device("cuda:0")).cuda_stream
+
+
+def _bitmap_bytes(index):
+    """bytes of survivor bitmaps in the workspace the rows run on.  The device entry's calls are enqueued on torch's
+    current stream, whose workspace is the primary one the host entry uses (the first device slot): the two reads are
+    of one workspace, and both are made so that a second one would show."""
+    host, dev = index.debug_survivor_bitmap_bytes(), index.debug_survivor_bitmap_bytes(_stream())
+    assert host == dev, "the host and the device entry ran on two workspaces: %d / %d bytes" % (host, dev)
+    return host
+
+
+def _run_row(index, kd, row, ref, monkeypatch, seen=None):
+    """the row's call on `index` under its knobs, with every check that needs no other pass; returns its outputs.
+    seen: {"bytes": the largest survivor bitmaps a bitmap-form row of this handle has asked for so far} -- updated by
+    the mirror's plan and compared with the handle's"""
     what = KM.row_id(row)
     for name in KM.KNOBS:
         monkeypatch.delenv(name, raising=False)
@@ -256,6 +275,12 @@ def _run_row(index, kd, row, ref, monkeypatch):
     want = KM.expected_kernel(row, kd.kind, kd.stream, kd.leaves)
     assert kernel == want, "%s: ran %s, the plan mirror says %s" % (what, kernel, want)
     assert status == hip.OK, "%s: status %d" % (what, status)
+    if seen is not None:
+        plan = KM.expected_plan(row, kd.kind, kd.stream, kd.leaves)
+        assert plan["sp_bitmap"] == (kd.kind == "ah" and plan["sp_pairs64"] and row["SCANN_HIP_SP_BITMAP"] is None), what
+        seen["bytes"] = max(seen["bytes"], plan["sp_bitmap_bytes"])
+        assert _bitmap_bytes(index) == seen["bytes"], "%s: %d bytes of survivor bitmaps, the plan mirror says %d" % (
+            what, _bitmap_bytes(index), seen["bytes"])
     nq, m, filt = row["nq"], row["m"], ENTRY_FILTER[row["entry"]]
     _same_rows((idx, dist, cnt), tuple(x[:nq] for x in ref[m, filt]), what)
     for i in ORACLE_QUERIES:
@@ -292,11 +317,14 @@ def test_knob_matrix(kinds, variant, monkeypatch):
     index = _create(kd, creation, monkeypatch)
     held = index.device_bytes()
     first = {}
+    seen = {"bytes": 0}
+    assert _bitmap_bytes(index) == 0
     for n_done, r in enumerate(order, 1):
-        first[r] = _run_row(index, kd, rows[r], ref, monkeypatch)
+        first[r] = _run_row(index, kd, rows[r], ref, monkeypatch, seen)
         if n_done % 8 == 0:
             _disturb(index, kd, KM.DISTURBANCES[(n_done // 8 - 1) % len(KM.DISTURBANCES)])
     assert len(first) == len(rows)
+    assert (seen["bytes"] > 0) == (kind == "ah"), "the bitmap form ran on the flat hasher, and only there"
     assert index.device_bytes() == held, "the handle's persistent allocations changed during the searches"
     index.close()
 
@@ -304,9 +332,22 @@ def test_knob_matrix(kinds, variant, monkeypatch):
     order = KM.pass2_order(rows)
     assert KM.growth_steps(rows, order) == 0
     index = _create(kd, creation, monkeypatch)
+    seen = {"bytes": 0}
     for r in order:
-        again = _run_row(index, kd, rows[r], ref, monkeypatch)
+        again = _run_row(index, kd, rows[r], ref, monkeypatch, seen)
         for a, b in zip(again, first[r]):
             assert a.dtype == b.dtype and np.array_equal(a.view(np.uint8), b.view(np.uint8)), \
                 "%s: pass 2 differs from pass 1" % KM.row_id(rows[r])
     index.close()
+
+    # the list form on a fresh handle: every row that runs 64-pair items, under SCANN_HIP_SP_BITMAP=0 -- the same kernel
+    # name, the rows of the default-knob handle and of the oracle, and no survivor bitmaps in the workspace
+    if kind == "ah":
+        index = _create(kd, creation, monkeypatch)
+        seen = {"bytes": 0}
+        pairs64 = [r for r in range(len(rows)) if KM.expected_plan(rows[r], kind, kd.stream, kd.leaves)["sp_pairs64"]]
+        assert len(pairs64) >= 2
+        for r in pairs64:
+            _run_row(index, kd, dict(rows[r], SCANN_HIP_SP_BITMAP="0"), ref, monkeypatch, seen)
+        assert seen["bytes"] == 0 and _bitmap_bytes(index) == 0
+        index.close()

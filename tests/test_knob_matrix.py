@@ -56,15 +56,36 @@ def test_every_plan_field_takes_both_values(shapes, kind):
     plans = [KM.expected_plan(r, kind, stream, leaves, P) for r in KM.matrix_rows()]
     fields = ["no_threshold", "thr_tail", "sp_words", "select_direct", "select_regs", "use_i8", "i8_expand"]
     if kind == "ah":
-        fields += ["sample_mfma", "sp_pairs64", "fused"]
+        fields += ["sample_mfma", "sp_pairs64", "sp_bitmap", "fused"]
     for f in fields:
         assert {p[f] for p in plans} == {False, True}, (kind, f)
     assert {p["pipeline"] for p in plans} == {"small", "wide", "staged"}
     if kind == "ah":
-        for f in ("sample_mfma", "sp_pairs64", "fused"):
+        for f in ("sample_mfma", "sp_pairs64", "sp_bitmap", "fused"):
             assert sum(p[f] for p in plans) >= 2, (f, sum(p[f] for p in plans))
+        assert any(p["sp_pairs64"] and not p["sp_bitmap"] for p in plans), "no row runs 64-pair items in the list form"
     else:   # flat hashers only (plan_txh_search), the one-launch small pipeline P = 1 only
-        assert not any(p["sample_mfma"] or p["fused"] for p in plans)
+        assert not any(p["sample_mfma"] or p["fused"] or p["sp_bitmap"] for p in plans)
+
+
+def test_the_bitmap_form_follows_the_knob_alone(shapes):
+    """sp_bitmap = 64-pair items, a flat hasher and the knob unset: the byte cap of plan_txh_search cannot bind at these
+    shapes (the largest batch over every 1024-point range of the index stays far below it), and the sizes the GPU test
+    compares with the handle's are those of the rows' batches"""
+    stream, leaves, P = shapes["ah"]
+    ranges = -(-G.N // KM.SP_RANGE64)
+    assert -(-KM.NQ_MAX // 64) * 64 * ranges * 128 == 4 << 20 < KM.SURV_BYTES_MAX
+    sizes = set()
+    for r in KM.matrix_rows():
+        for kind in ("ah", "txh"):
+            st, lv, p = shapes[kind]
+            plan = KM.expected_plan(r, kind, st, lv, p)
+            assert plan["sp_bitmap"] == (kind == "ah" and plan["sp_pairs64"] and r["SCANN_HIP_SP_BITMAP"] is None)
+            assert plan["sp_bitmap_bytes"] == (-(-r["nq"] // 64) * 64 * ranges * 128 if plan["sp_bitmap"] else 0)
+            sizes.add(plan["sp_bitmap_bytes"])
+            if r["SCANN_HIP_SP_BITMAP"] == "0":
+                assert not plan["sp_bitmap"]
+    assert len(sizes) >= 3, "the running maximum of the GPU test grows at least once"
 
 
 @pytest.mark.parametrize("kind", ["ah", "txh"])
