@@ -1,6 +1,6 @@
 // build.h -- scann_hip_txh_build (scann_hip.h "device build"): a tree or flat-hasher index trained, encoded and laid
 // out on the device from the resident rows of an f32 brute-force handle (build.hip).  The handle itself is put
-// together in api.hip (index_build_txh), which owns scann_hip_index.
+// together in api_create.hip (index_build_txh), which owns scann_hip_index.
 #pragma once
 #include <vector>
 
@@ -26,7 +26,7 @@ int build_check(const BfIndexDev &src, const scann_hip_build_config &cfg);
 int build_txh_device(const BfIndexDev &src, const scann_hip_build_config &cfg, hipStream_t stream, BuildParts *out,
                      scann_hip_build_report *rep);
 
-// api.hip: the new handle around `parts` (taken) and a device copy of src's rows when cfg.store_rows; stage_ms[6].
+// api_create.hip: the new handle around `parts` (taken) and a device copy of src's rows when cfg.store_rows; stage_ms[6].
 // proj != nullptr (scann_hip_txh_build_projected): `parts` index the projected rows, [n][out_dim]; the handle copies
 // the projection and keeps src's rows as re-rank rows in their own space.
 int index_build_txh(const scann_hip_index *src, const scann_hip_build_config &cfg, BuildParts &parts,

@@ -1,4 +1,4 @@
-// comm.h -- internals shared by comm.hip (the RCCL exchange) and api.hip.
+// comm.h -- internals shared by comm.hip (the RCCL exchange) and the api*.hip units.
 #pragma once
 #include <stdint.h>
 
@@ -20,7 +20,7 @@ CommLayout comm_layout(uint32_t nq, uint32_t world, uint32_t m_local, uint32_t k
 
 // api.hip
 int ctx_device(const scann_hip_ctx *ctx);
-// pre-reorder candidate count m a search with (k, opts) on this index keeps (tree_x_hybrid/mod.rs:263)
+// api_search.hip: pre-reorder candidate count m a search with (k, opts) on this index keeps (tree_x_hybrid/mod.rs:263)
 int txh_resolve_m(scann_hip_index *index, uint32_t k, const scann_hip_search_opts *opts, uint32_t *out_m);
 
 }  // namespace scann

@@ -14,7 +14,7 @@ namespace scann {
 // ---- error plumbing ---------------------------------------------------------------
 void set_last_error(const std::string &msg);
 int fail(int status, const std::string &msg);
-// scann_hip_txh_create with the status reported for inconsistent array CONTENTS (api.hip)
+// scann_hip_txh_create with the status reported for inconsistent array CONTENTS (api_create.hip)
 // qrows != nullptr: scann_hip_txh_create_quantized -- d->data is NULL and the re-rank rows are qrows, n_rows rows of
 // d->stride elements of qfmt (SCANN_HIP_ROWS_*), int8 values scaled by qinv.  qrows_dev (with qrows == nullptr): the same
 // rows already on the device, in an allocation the new handle takes over (scann_hip_index_quantize_rows)
@@ -22,11 +22,11 @@ struct DevBuf;
 int txh_create_checked(scann_hip_ctx *ctx, const scann_hip_txh_desc *d, scann_hip_index **out,
                        int content_status, const void *qrows = nullptr, int qfmt = 0, float qinv = 1.0f,
                        DevBuf *qrows_dev = nullptr);
-// scann_hip_txh_create_projected with the status reported for inconsistent array contents (api.hip)
+// scann_hip_txh_create_projected with the status reported for inconsistent array contents (api_create.hip)
 int txh_create_projected_checked(scann_hip_ctx *ctx, const scann_hip_txh_desc *d, const scann_hip_projection *proj,
                                  const float *rows, uint64_t n_rows, uint32_t row_dim, uint32_t row_stride,
                                  scann_hip_index **out, int content_status);
-// the argument checks scann_hip_txh_create_quantized makes before those of scann_hip_txh_create (api.hip)
+// the argument checks scann_hip_txh_create_quantized makes before those of scann_hip_txh_create (api_create.hip)
 int txh_quantized_args(const scann_hip_txh_desc *d, const void *rows, int row_format, float inv_multiplier);
 
 #define SCANN_HIP_CHECK(expr)                                                         \

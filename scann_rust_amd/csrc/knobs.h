@@ -81,7 +81,7 @@ struct Knobs {
     uint32_t rerank_i8_min = 512;
     bool rerank_expand = true;
     int sp_words = -1;                    // -1 = by index kind
-    int sp_pairs = 0;                     // 0 = by the batch (api.hip plan_txh_search)
+    int sp_pairs = 0;                     // 0 = by the batch (api_search.hip plan_txh_search)
     bool sp_bitmap = true;
     bool thr_ties = true;
     bool thr_tail = true;

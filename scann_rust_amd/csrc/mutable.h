@@ -1,4 +1,4 @@
-// mutable.h -- what the mutable-index layer (mutable.hip) asks of a base handle (api.hip).
+// mutable.h -- what the mutable-index layer (mutable.hip) asks of a base handle (handle.h; the views are in api.hip).
 #pragma once
 #include <vector>
 
@@ -30,7 +30,7 @@ struct FoldView {
 int index_fold_view(const scann_hip_index *ix, FoldView *v);
 // New handles over arrays the fold wrote on the device.  The buffers are TAKEN (left empty) on success and on failure
 // alike; model (centres, codebook, measure, search defaults) is copied from `old` device to device; everything derived is
-// built by the finish half of scann_hip_bf_create / scann_hip_txh_create (api.hip).  off: host copy of leaf_off.
+// built by the finish half of scann_hip_bf_create / scann_hip_txh_create (api_create.hip).  off: host copy of leaf_off.
 int index_fold_bf(const scann_hip_index *old, DevBuf &rows, uint64_t n, uint32_t stride, scann_hip_index **out);
 int index_fold_txh(const scann_hip_index *old, DevBuf &rows, DevBuf &codes, DevBuf &leaf_off, DevBuf &leaf_ids,
                    const std::vector<uint32_t> &off, uint64_t n, uint32_t stride, scann_hip_index **out);

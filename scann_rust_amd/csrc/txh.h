@@ -157,7 +157,7 @@ enum class TxhPipeline : uint8_t { Staged, Small, Wide };
 // exact leaf scan (SearchMode::Partitioned).
 enum class TxhScan : uint8_t { Gather, Resident, Mfma32, Mfma16, Smfmac, Exact };
 
-// Every path decision of one search call and the sizes they were derived from (api.hip plan_txh_search).
+// Every path decision of one search call and the sizes they were derived from (api_search.hip plan_txh_search).
 struct TxhPlan {
     uint32_t nq, P, m, k;
     uint32_t cap;              // candidate slots per query

@@ -1,5 +1,5 @@
 // txh_stages.h -- the stage launchers that the units of the tree / flat-hasher search define for txh.hip's
-// orchestration.  Internal: txh.h stays the interface api.hip and the other sources see.
+// orchestration.  Internal: txh.h stays the interface the api*.hip units and the other sources see.
 #pragma once
 #include "txh.h"
 

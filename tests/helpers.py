@@ -571,7 +571,7 @@ def nonfinite_zero_row(n):
 
 # ---- allow-list filters (tests/test_gpu_filters.py) -----------------------------------------------------------------
 # Python mirror of the sample plan of csrc/txh.h (sample_stride / sample_plan / sample_rank) and of the candidate
-# capacities plan_txh_search derives from it (api.hip), so that a test can name the points the threshold sample reads
+# capacities plan_txh_search derives from it (api_search.hip), so that a test can name the points the threshold sample reads
 # and the sizes at which a bound is statistical.
 SAMPLE_TARGET, SAMPLE_MIN = 32768, 4096
 WIDE_GROUPS = 16384

@@ -1,4 +1,4 @@
-"""An all-pairs matrix over the per-call decisions of a tree / flat-hasher search (api.hip plan_txh_search), and a mirror
+"""An all-pairs matrix over the per-call decisions of a tree / flat-hasher search (api_search.hip plan_txh_search), and a mirror
 of the two decisions scann_hip_index_last_kernel_ms reports: the pipeline and the batched scan.
 
 Pure Python: no GPU and no library.  tests/test_knob_matrix.py checks the generator and the mirror's coverage,
@@ -43,7 +43,7 @@ SMALL_BATCH, SMALL_MAX_CANDIDATES, SMALL_MAX_STREAM = 16, 1024, 262144
 WIDE_BATCH, WIDE_MAX_CANDIDATES, WIDE_MAX_STREAM, WIDE_MIN_STREAM = 4, 8192, 4 << 20, 16384
 SCAN_PPT, RES_THREADS, RES_QUADS = 2, 512, 4
 FUSED_CHUNK, FUSED_MAX_WGS, DECODE_STAGE, THR_TAIL_MAX_RANK = 1024, 512, 512, 384
-SP_RANGE64, SURV_BYTES_MAX = 1024, 512 << 20   # points per 64-pair item; api.hip plan_txh_search kSurvBytesMax
+SP_RANGE64, SURV_BYTES_MAX = 1024, 512 << 20   # points per 64-pair item; api_search.hip plan_txh_search kSurvBytesMax
 S, TREE_P = 16, 3   # subspaces and partitions_to_search of the matrix's indexes (tests/test_gpu_knob_matrix.py)
 
 
@@ -232,7 +232,7 @@ def expected_plan(row, kind, stream, leaves, P=None):
 
 
 def expected_kernel(row, kind, stream, leaves, P=None):
-    """api.hip txh_kernel_name of the row's first attempt: the pinned host call of a non-staged pipeline is named by
+    """api_search.hip txh_kernel_name of the row's first attempt: the pinned host call of a non-staged pipeline is named by
     the pipeline's scan, every other call by the batched scan of its plan (also where a small pipeline runs it)"""
     p = expected_plan(row, kind, stream, leaves, P)
     if p["pinned"]:
@@ -262,7 +262,7 @@ DISTURBANCES = (
 
 def pass1_order(rows):
     """indices of `rows` from the smallest shapes up (nq, then m): every new largest nq asks for longer per-query
-    buffers (api.hip ensure_txh_workspace: samp, cand, queries, ... are nq x something), so the arena is rebuilt
+    buffers (api_search.hip ensure_txh_workspace: samp, cand, queries, ... are nq x something), so the arena is rebuilt
     several times mid-sequence"""
     return sorted(range(len(rows)), key=lambda i: (rows[i]["nq"], rows[i]["m"], i))
 

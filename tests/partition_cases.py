@@ -19,7 +19,7 @@ WIDE_BATCH, WIDE_MAX_CANDIDATES, WIDE_MAX_STREAM = 4, 8192, 4 << 20
 FUSED_CHUNK, FUSED_MAX_WGS = 1024, 512
 SEL_REG_CAP = 18432
 SELECT_STATIC = 0           # select_leaves_kernel has no __shared__ array of its own (hipFuncGetAttributes: 0 bytes)
-INLINE_MAX_LEAVES = 4096    # api.hip: the transposed centroid copy (centers_t) and the Small / Wide pipelines
+INLINE_MAX_LEAVES = 4096    # api_create.hip / api_search.hip: the transposed centroid copy (centers_t) and the Small / Wide pipelines
 NQ = 33                     # queries of a partition case: no multiple of centroid_scores_kernel's 4- or 16-query tile
 K = 10
 
@@ -68,7 +68,7 @@ def staged_select(L, P):
 
 
 def pipeline(L, P, nq, m, ms, wide=False, exact_scan=False, sharded=False, k=K):
-    """csrc/api.hip plan_txh_search: Staged, Small (at most 16 queries) or Wide (at most 4, where SCANN_HIP_WIDE=2
+    """csrc/api_search.hip plan_txh_search: Staged, Small (at most 16 queries) or Wide (at most 4, where SCANN_HIP_WIDE=2
     forces it).  ms: the longest stream, the sum of the P largest leaves."""
     pipe = "Staged"
     if nq <= SMALL_BATCH and not sharded and m <= SMALL_MAX_CANDIDATES and k <= 64 and ms <= SMALL_MAX_STREAM and \
@@ -81,7 +81,7 @@ def pipeline(L, P, nq, m, ms, wide=False, exact_scan=False, sharded=False, k=K):
 
 
 def small_fused(P, nq, ms, exact_scan):
-    """csrc/api.hip plan_small_launch: the Small pipeline as one launch (small_fused_kernel) or three"""
+    """csrc/api_search.hip plan_small_launch: the Small pipeline as one launch (small_fused_kernel) or three"""
     chunk = FUSED_CHUNK
     if exact_scan:
         chunk = min(FUSED_CHUNK, max(128, (-(-ms // 256) + 127) & ~127))
@@ -90,7 +90,7 @@ def small_fused(P, nq, ms, exact_scan):
 
 
 def plan_cap(ms, P, m):
-    """csrc/api.hip plan_txh_search: the candidate list of the staged pipeline's first attempt (tests/helpers.py
+    """csrc/api_search.hip plan_txh_search: the candidate list of the staged pipeline's first attempt (tests/helpers.py
     plan_caps has the same arithmetic; repeated here so that this module imports no library)"""
     ns = min(max(ms // 16, 4096), 32768)
     st = max(1, -(-ms // ns))

@@ -15,7 +15,7 @@ F32 = np.float32
 INF = F32(np.inf)
 SHORT_MAX_FAST = 1024   # txh.hip kShortMaxFast: longer shortlists fall back to final_topk_kernel
 LOCAL_HEAD = 256        # txh.hip kLocalHead: entries of a sharded rank's list that are always re-ranked exactly
-UNIFORM_SPREAD = 1.02   # api.hip: one scale when the largest per-row scale is within 2 % of the mean
+UNIFORM_SPREAD = 1.02   # api_create.hip: one scale when the largest per-row scale is within 2 % of the mean
 # the bracket's three parts (rerank_i8_kernel); a mutation test drops one of them
 TERMS = ("error", "f32sum", "floor")
 
@@ -68,7 +68,7 @@ def i8_store(rows, uni_scale=None):
 
 
 def uniform_choice(store, mode=1):
-    """api.hip: the one-scale rebuild is taken when every row is finite and the largest scale is within 2 % of the mean
+    """api_create.hip: the one-scale rebuild is taken when every row is finite and the largest scale is within 2 % of the mean
     scale (SCANN_HIP_RERANK_UNIFORM: 0 never, 2 whenever the rows are finite).  Returns the one scale or None."""
     if mode == 0 or store.deq.size == 0:
         return None

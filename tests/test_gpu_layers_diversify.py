@@ -14,7 +14,7 @@ Every case is checked two ways, as tests/test_gpu_crowding.py test_hashed_crowde
       the seeds, in tests/test_layer_checkers.py on the CPU).
 
 Which scan ran.  The HOST entries of the stages run the base search on the primary workspace without touching the
-handle's kernel timing (api.hip search_device_ws with no device slot), so scann_hip_index_last_kernel_ms does not
+handle's kernel timing (api_search.hip search_device_ws with no device slot), so scann_hip_index_last_kernel_ms does not
 report them: the plan is asserted through the plain search with the same nq, depth and opts on the same handle, and --
 the workspace IS reported -- through debug_survivor_bitmap_bytes right after the stage's call on a fresh handle (bitmaps
 of the call's size under the bitmap form, none under the lists).  The DEVICE entries are named by the handle."""

@@ -798,7 +798,7 @@ def test_pack_blocks_matches_reference():
 # ---- resident-table scan kernel (long leaves scanned by >= 128 queries) ----------------------------
 @pytest.fixture
 def force_resident(monkeypatch):
-    """adc_scan_res_kernel is selected by a size heuristic (api.hip); SCANN_HIP_RESIDENT=2 selects it
+    """adc_scan_res_kernel is selected by a size heuristic (api_search.hip); SCANN_HIP_RESIDENT=2 selects it
     for every 4-bit S <= 32 index so that small test cases run it too."""
     monkeypatch.setenv("SCANN_HIP_RESIDENT", "2")
     monkeypatch.setenv("SCANN_HIP_RES_CL", "3")
@@ -1979,6 +1979,50 @@ def test_device_calls_on_two_streams_match_oracle(kind):
             wi, wd = oracle(qs[s][i])[:2]
             H.assert_topk_equal_up_to_ties(outs[s][0][i].cpu().numpy().view(np.uint32)[:wi.size],
                                            outs[s][1][i].cpu().numpy()[:wi.size], wi, wd, what="%s s%d q%d" % (kind, s, i))
+
+
+@pytest.mark.parametrize("kind", ["txh", "bf"])
+def test_host_call_claims_primary_workspace_behind_device_call(kind):
+    """A device call on a caller stream binds device slot 0, which is the primary scratch.  A host call that takes the
+    primary slot right behind it -- no synchronisation in between -- runs on the handle's own stream in the same
+    scratch: it must first order its stream behind the slot's completion event.  The host batch is smaller than the
+    device batch, so the arena is not rebuilt (a rebuild's hipFree would wait for the device by itself) and the event
+    alone orders the two.  The device call is then made again on its stream.  All three answers equal the host answers
+    computed beforehand, bit for bit."""
+    import ctypes
+
+    import torch
+    dev = torch.device("cuda:0")
+    n, dim, k = 5000, 64, 10
+    if kind == "txh":
+        rows, data, stride, ix, oix, kw = H.make_txh_case(n, dim, 12, 16, seed=91, P=4, mult=3.0, kmeans_iters=3, pq_iters=3)
+        index = hip.txh_create(**kw)
+    else:
+        rows = synth.uniform_f32(n, dim, 92)
+        data, stride = orc.to_strided(rows)
+        index = hip.bf_create(data, n, dim, stride, hip.SQUARED_L2)
+    L = hip.load()
+    p = lambda t: ctypes.c_void_p(t.data_ptr())
+    q_dev, q_host = synth.uniform_f32(200, dim, 910), synth.uniform_f32(24, dim, 911)
+    want_dev, want_host = index.search_batched(q_dev, k), index.search_batched(q_host, k)
+    stream = torch.cuda.Stream(device=dev)
+    sp = ctypes.c_void_p(stream.cuda_stream)
+    qd = torch.from_numpy(q_dev).to(dev)
+    outs = [(torch.full((200, k), -1, dtype=torch.int32, device=dev), torch.zeros((200, k), dtype=torch.float32, device=dev),
+             torch.zeros((200,), dtype=torch.int32, device=dev)) for _ in range(2)]
+    torch.cuda.synchronize()
+    device_call = lambda o: hip.check(L.scann_hip_search_batched_device(index.h, p(qd), 200, dim, k, None, p(o[0]), p(o[1]),
+                                                                       p(o[2]), sp))
+    device_call(outs[0])
+    got_host = index.search_batched(q_host, k)
+    device_call(outs[1])
+    hip.check(L.scann_hip_index_last_device_status(index.h, sp))
+    torch.cuda.synchronize()
+    for what, (gi, gd, gc), (wi, wd, wc) in [("host", got_host, want_host)] + \
+            [("device %d" % j, tuple(t.cpu().numpy() for t in o), want_dev) for j, o in enumerate(outs)]:
+        assert np.array_equal(np.asarray(gc).view(np.uint32), wc), (kind, what)
+        assert np.array_equal(bits(gd), bits(wd)), (kind, what)
+        assert np.array_equal(np.asarray(gi).view(np.uint32), wi), (kind, what)
 
 
 # ---- Searcher::search_batched_with_params: one num_neighbors per query ------------------------------------------
