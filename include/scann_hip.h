@@ -1039,7 +1039,8 @@ int scann_hip_search_batched_tokens(scann_hip_index *index, scann_hip_token_map 
  * exactly a or b (same pointer, same stride).  SCANN_HIP_ALLOW_NOT does not read b (NULL is fine).  Unknown op, a
  * non-zero operand stride or an output stride below ceil(bits / 64) -> InvalidArgument.  Device form: device
  * pointers, one streaming kernel enqueued on hip_stream (16 bytes a lane where every row is 16-byte aligned), no
- * synchronisation.  Host form: host pointers, no context, no GPU; the model.  RangeFilter is not built. */
+ * synchronisation.  Host form: host pointers, no context, no GPU; the model.  RangeFilter is the attribute table's
+ * row-index column, below: a range ANDs into a block in place, with no second block and no combine pass. */
 #define SCANN_HIP_ALLOW_AND 1
 #define SCANN_HIP_ALLOW_OR 2
 #define SCANN_HIP_ALLOW_ANDNOT 3 /* a & ~b */
@@ -1049,6 +1050,79 @@ int scann_hip_allow_bitmaps_combine(int op, const uint64_t *a, uint64_t stride_a
 int scann_hip_allow_bitmaps_combine_device(scann_hip_ctx *ctx, int op, const uint64_t *d_a, uint64_t stride_a,
                                            const uint64_t *d_b, uint64_t stride_b, uint32_t nq, uint64_t bits,
                                            uint64_t *d_out, uint64_t stride_out, void *hip_stream);
+/* ---- range filters: typed attribute columns resident on the device that write per-query bitmaps ------------------
+ * RangeFilter (restricts/mod.rs:73-95) allows start <= index < end on the datapoint index.  The handle holds n_columns
+ * typed columns of num_datapoints values each -- SCANN_HIP_ATTR_I64 (int64_t: timestamps, counters, ids) or
+ * SCANN_HIP_ATTR_F32 (float: prices, scores) -- uploaded once and shared by every query of every batch.  The
+ * pseudo-column SCANN_HIP_ATTR_ROW_INDEX needs no storage: its value at row j is j as an i64, which is the reference's
+ * RangeFilter: RangeFilter::new(start, end) is lo = start, hi = (int64_t)end - 1 (end = 0 and start > end give an
+ * empty bitmap; the reference's num_allowed underflows there and is not mirrored).
+ *   create   n_columns = 0 is valid (only the row index), num_datapoints = 0 too (nothing but gap words is written).
+ *            num_datapoints >= 2^32 - 1 -> OutOfRange; an unknown type or a null column pointer with num_datapoints >
+ *            0 -> InvalidArgument.  A created table does not change (to change a value: build a new table).
+ *   column_type   SCANN_HIP_ATTR_I64 / _F32, 0 for an unknown column.
+ * Bitmaps of a batch: the call names n_cols <= SCANN_HIP_ATTR_MAX_CLAUSES clauses, cols[c] (a small HOST array, the
+ * same for every query; a column index or SCANN_HIP_ATTR_ROW_INDEX; a column may repeat: two clauses on one column
+ * intersect), and gives one inclusive range per (query, clause): bounds[(q * n_cols + c) * 2 + {0, 1}] = lo, hi (8
+ * bytes each, an f32 in the low four).  Bit j of query q's bitmap -- words [q * stride_words, q * stride_words +
+ * ceil(num_datapoints / 64)) -- is the AND over the clauses of lo <= value(cols[c], j) && value(cols[c], j) <= hi.
+ * i64 columns compare as signed 64-bit integers, with no detour through a float type.  f32 columns compare by IEEE on
+ * the stored value: -0.0 matches [0, 0], denormals are compared as stored (no flush), a NaN value matches no range (a
+ * NaN attribute is "missing"), a NaN bound matches nothing, [-inf, +inf] matches every non-NaN row.  So a query that
+ * does not care about a column STILL EXCLUDES that column's NaN rows if the column is among the call's clauses: leave
+ * the column out of cols, or give such batches a call of their own.  lo > hi gives an empty bitmap; n_cols = 0 is the
+ * empty conjunction (every bit below num_datapoints).  No bit at or past num_datapoints is ever set, under any op.
+ *   op 0                     write: all nq * stride_words words are written, gap words as zero (the contract of
+ *                            scann_hip_allow_bitmaps_from_ids)
+ *   SCANN_HIP_ALLOW_AND      out = out & range: only words [0, ceil(bits / 64)) of each row are read and written, gap
+ *   SCANN_HIP_ALLOW_OR       out = out | range     words are untouched (as scann_hip_allow_bitmaps_combine leaves
+ *   SCANN_HIP_ALLOW_ANDNOT   out = out & ~range    them): a token block AND a range is one read-modify-write
+ *   anything else (SCANN_HIP_ALLOW_NOT included) -> InvalidArgument.
+ * Refusals come before anything is enqueued, and a refused call writes nothing: n_cols > SCANN_HIP_ATTR_MAX_CLAUSES ->
+ * Unimplemented; a clause column that is neither < n_columns nor the row index, null cols / bounds / output where
+ * they would be read, stride_words < ceil(bits / 64) or >= 2^32 -> InvalidArgument.
+ *   _device           device pointers for bounds and output, cols on the host (read at the call); ONE kernel enqueued
+ *                     on hip_stream: no clear, no global atomic, no synchronisation, nothing visits the host.
+ *                     Workgroup (t, y) holds tile t (SCANN_HIP_RANGE_TILE_BITS rows) of every clause's column in
+ *                     registers and writes that tile of the bitmaps of queries y, y + gridDim.y, ...
+ *   (no suffix)       host pointers, synchronous: bounds up (for op != 0 the block too), the same kernel, the block
+ *                     back.  One call at a time per table (serialised inside).
+ *   scann_hip_allow_bitmaps_from_ranges   stateless, on the host, no context, no GPU: the model and the form for
+ *                     machines without a device.  The two handle forms give its output bitwise. */
+typedef struct scann_hip_attr_table scann_hip_attr_table;
+typedef union { int64_t i64; float f32; uint64_t bits; } scann_hip_range_bound; /* 8 bytes; f32 in the low 4 */
+#define SCANN_HIP_ATTR_I64 1
+#define SCANN_HIP_ATTR_F32 2
+#define SCANN_HIP_ATTR_ROW_INDEX 0xFFFFFFFFu
+#define SCANN_HIP_ATTR_MAX_CLAUSES 8
+#define SCANN_HIP_RANGE_TILE_BITS 1024
+int scann_hip_attr_table_create(scann_hip_ctx *ctx, uint64_t num_datapoints, uint32_t n_columns, const int32_t *types,
+                                const void *const *columns, scann_hip_attr_table **out);
+void scann_hip_attr_table_destroy(scann_hip_attr_table *t);
+uint64_t scann_hip_attr_table_num_datapoints(const scann_hip_attr_table *t);
+uint32_t scann_hip_attr_table_num_columns(const scann_hip_attr_table *t);
+int scann_hip_attr_table_column_type(const scann_hip_attr_table *t, uint32_t column);
+int scann_hip_attr_table_allow_bitmaps_device(const scann_hip_attr_table *t, const uint32_t *cols, uint32_t n_cols,
+                                              const scann_hip_range_bound *d_bounds, uint32_t nq, int op,
+                                              uint64_t stride_words, uint64_t *d_out_words, void *hip_stream);
+int scann_hip_attr_table_allow_bitmaps(scann_hip_attr_table *t, const uint32_t *cols, uint32_t n_cols,
+                                       const scann_hip_range_bound *bounds, uint32_t nq, int op, uint64_t stride_words,
+                                       uint64_t *out_words);
+int scann_hip_allow_bitmaps_from_ranges(uint64_t num_datapoints, uint32_t n_columns, const int32_t *types,
+                                        const void *const *columns, const uint32_t *cols, uint32_t n_cols,
+                                        const scann_hip_range_bound *bounds, uint32_t nq, int op, uint64_t stride_words,
+                                        uint64_t *out_words);
+/* The twin of scann_hip_search_batched_tokens: host pointers, synchronous: queries and bounds go up, the block is built
+ * on the device by the table's kernel (op 0) and scann_hip_search_batched_device reads it on the same stream with
+ * nothing between the two enqueues; the rows come back.  opts as for scann_hip_search_batched, with allow_bitmap NULL
+ * (set -> InvalidArgument: the ranges are the filter); index and table live on the same device, and the table's
+ * num_datapoints equals the index's row count (else InvalidArgument).  Where the enqueue-only search reports Aborted
+ * or ResourceExhausted, the batch is answered by scann_hip_search_batched under the same block.  Brute-force handles
+ * refuse per-query bitmaps as before (Unimplemented).  k = 0 -> InvalidArgument. */
+int scann_hip_search_batched_ranges(scann_hip_index *index, scann_hip_attr_table *t, const float *queries, uint32_t nq,
+                                    uint32_t q_stride, uint32_t q_dim, uint32_t k, const scann_hip_search_opts *opts,
+                                    const uint32_t *cols, uint32_t n_cols, const scann_hip_range_bound *bounds,
+                                    uint32_t *out_idx, float *out_dist, uint32_t *out_count);
 int scann_hip_bf_search_radius(scann_hip_index *index, const float *query, uint32_t q_dim, float radius,
                                uint32_t *out_idx, float *out_dist, uint64_t capacity,
                                uint64_t *out_count);

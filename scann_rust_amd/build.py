@@ -16,8 +16,8 @@ LIB = os.path.join(HERE, "libscann_hip.so")
 TXH_SOURCES = ["txh.hip", "txh_partition.hip", "txh_prefilter.hip", "txh_rows.hip", "txh_blocks.hip"]
 # the C ABI over the handle of handle.h: lifetime and building blocks, creation, searches, crowding / MMR stages
 API_SOURCES = ["api.hip", "api_create.hip", "api_search.hip", "api_stages.hip"]
-SOURCES = API_SOURCES + TXH_SOURCES + ["bf.hip", "index_file.hip", "comm.hip", "crowd.hip", "mmr.hip", "mutable.hip", "fold.hip", "allow.hip", "tokens.hip", "scalarq.hip", "project.hip", "build.hip", "pca.hip"]
-HEADERS = ["common.h", "knobs.h", "handle.h", "txh_arena.h", "txh.h", "txh_dev.h", "txh_stages.h", "allow.h", "tokens.h", "bf.h", "comm.h", "crowd.h", "mmr.h", "mutable.h", "fold.h", "index_arrays.h", "pair.h", "launch.h", "quant.h", "scalarq.h", "project.h", "build.h", "pca.h", os.path.join("..", "..", "include", "scann_hip.h")]
+SOURCES = API_SOURCES + TXH_SOURCES + ["bf.hip", "index_file.hip", "comm.hip", "crowd.hip", "mmr.hip", "mutable.hip", "fold.hip", "allow.hip", "tokens.hip", "ranges.hip", "scalarq.hip", "project.hip", "build.hip", "pca.hip"]
+HEADERS = ["common.h", "knobs.h", "handle.h", "txh_arena.h", "txh.h", "txh_dev.h", "txh_stages.h", "allow.h", "tokens.h", "ranges.h", "bf.h", "comm.h", "crowd.h", "mmr.h", "mutable.h", "fold.h", "index_arrays.h", "pair.h", "launch.h", "quant.h", "scalarq.h", "project.h", "build.h", "pca.h", os.path.join("..", "..", "include", "scann_hip.h")]
 # -ffp-contract=off: the reference never contracts a*b+c (Rust); FMA is used only via
 # explicit fmaf()/MFMA where the reference uses _mm256_fmadd_ps.
 CFLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "-fPIC", "-Wall",

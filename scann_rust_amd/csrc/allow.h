@@ -33,6 +33,28 @@ static inline int refuse_allow_stride(const scann_hip_search_opts *o, const char
     return SCANN_HIP_OK;
 }
 
+// the checks every builder of a bitmap block shares: stride_words >= ceil(bits / 64) and < 2^32, else InvalidArgument
+int check_block_args(uint64_t bits, uint64_t stride_words);
+
+// ---- a filtered batch in one host call: the block is built on the device, the enqueue-only search reads it on the
+// same stream (scann_hip_search_batched_tokens, scann_hip_search_batched_ranges) -----------------------------------
+// grow-only staging of such a call, owned by the filter's handle (one call at a time per handle)
+struct FilterSearchBufs {
+    DevBuf block, queries, idx, dist, count;
+};
+// the argument checks the two entries share; `filter_is` names the filter in the allow_bitmap refusal
+int filter_search_check(const scann_hip_index *index, const float *queries, uint32_t q_stride, uint32_t q_dim, uint32_t k,
+                        const scann_hip_search_opts *opts, const uint32_t *out_idx, const float *out_dist,
+                        const uint32_t *out_count, const char *filter_is);
+// sizes the staging and enqueues the queries' upload on st
+int filter_search_begin(FilterSearchBufs &b, hipStream_t st, const float *queries, uint32_t nq, uint32_t q_stride, uint32_t k);
+// after the block's kernel was enqueued on st into b.block (`stride` words a query, capacity `bits`): the enqueue-only
+// search right behind it, the rows back; where that search reports Aborted or ResourceExhausted the batch is answered
+// by scann_hip_search_batched under the same block.  Synchronous.
+int filter_search_finish(scann_hip_index *index, FilterSearchBufs &b, hipStream_t st, const float *queries, uint32_t nq,
+                         uint32_t q_stride, uint32_t q_dim, uint32_t k, scann_hip_search_opts o, uint64_t bits,
+                         uint64_t stride, uint32_t *out_idx, float *out_dist, uint32_t *out_count);
+
 // d_out[i * stride .. (i + 1) * stride): bit id set for every id < bits of d_ids[d_offsets[i] .. d_offsets[i + 1]),
 // every other word zero.  stride >= allow_words(bits) (the caller checks).  Enqueue only: a clear and one kernel.
 int allow_from_ids_launch(const uint32_t *d_ids, const uint64_t *d_offsets, uint32_t nq, uint64_t bits, uint64_t stride,

@@ -10,6 +10,8 @@
 // word with a 64-bit atomic (agent scope, no return value): duplicates and any order give the same words.  The
 // total number of ids stays on the device (offsets[nq] is never read by the host): no synchronisation.
 #include <algorithm>
+#include <string>
+#include <vector>
 
 #include "allow.h"
 #include "comm.h"   // ctx_device
@@ -49,6 +51,61 @@ int allow_from_ids_launch(const uint32_t *d_ids, const uint64_t *d_offsets, uint
     const uint32_t gx = std::max<uint32_t>(1u, std::min<uint32_t>(64u, (uint32_t)num_cus() * 8u / gy));
     return launch(allow_scatter_kernel, dim3(gx, gy), dim3(kAllowThreads), 0, st, d_ids, d_offsets, nq, bits, stride,
                   reinterpret_cast<unsigned long long *>(d_out));
+}
+
+int check_block_args(uint64_t bits, uint64_t stride_words) {
+    if (stride_words < allow_words(bits))
+        return fail(SCANN_HIP_INVALID_ARGUMENT, "allow-bitmap stride is smaller than one bitmap (ceil(bits / 64) words)");
+    if (stride_words > 0xFFFFFFFFull)   // (check_allow_stride's limit: the search kernels carry the stride in 32 bits)
+        return fail(SCANN_HIP_INVALID_ARGUMENT, "allow-bitmap stride must be below 2^32 words");
+    return SCANN_HIP_OK;
+}
+
+int filter_search_check(const scann_hip_index *index, const float *queries, uint32_t q_stride, uint32_t q_dim, uint32_t k,
+                        const scann_hip_search_opts *opts, const uint32_t *out_idx, const float *out_dist,
+                        const uint32_t *out_count, const char *filter_is) {
+    if (!queries || !out_idx || !out_dist || !out_count) return fail(SCANN_HIP_INVALID_ARGUMENT, "null query/output pointer");
+    if (k == 0) return fail(SCANN_HIP_INVALID_ARGUMENT, "k must be > 0");
+    if (opts && opts->allow_bitmap)
+        return fail(SCANN_HIP_INVALID_ARGUMENT, std::string(filter_is) + " are the filter: allow_bitmap must be null");
+    if (q_dim != scann_hip_index_dimensionality(index)) return fail(SCANN_HIP_INVALID_ARGUMENT, "Query dimensionality mismatch");
+    if (q_stride < q_dim) return fail(SCANN_HIP_INVALID_ARGUMENT, "q_stride < q_dim");
+    return SCANN_HIP_OK;
+}
+
+int filter_search_begin(FilterSearchBufs &b, hipStream_t st, const float *queries, uint32_t nq, uint32_t q_stride, uint32_t k) {
+    const size_t qb = (size_t)nq * q_stride * 4, ob = (size_t)nq * k * 4;
+    SCANN_TRY(b.queries.ensure(qb));
+    SCANN_TRY(b.idx.ensure(ob));
+    SCANN_TRY(b.dist.ensure(ob));
+    SCANN_TRY(b.count.ensure((size_t)nq * 4));
+    SCANN_HIP_CHECK(hipMemcpyAsync(b.queries.p, queries, qb, hipMemcpyHostToDevice, st));
+    return SCANN_HIP_OK;
+}
+
+int filter_search_finish(scann_hip_index *index, FilterSearchBufs &b, hipStream_t st, const float *queries, uint32_t nq,
+                         uint32_t q_stride, uint32_t q_dim, uint32_t k, scann_hip_search_opts o, uint64_t bits,
+                         uint64_t stride, uint32_t *out_idx, float *out_dist, uint32_t *out_count) {
+    const size_t ob = (size_t)nq * k * 4;
+    o.allow_bitmap = b.block.as<uint64_t>();
+    o.allow_bitmap_bits = bits;
+    o.allow_bitmap_stride = stride;
+    SCANN_TRY(scann_hip_search_batched_device(index, b.queries.as<float>(), nq, q_stride, k, &o, b.idx.as<uint32_t>(),
+                                              b.dist.as<float>(), b.count.as<uint32_t>(), st));
+    const int status = scann_hip_index_last_device_status(index, st);   // (synchronises the stream)
+    if (status == SCANN_HIP_ABORTED || status == SCANN_HIP_RESOURCE_EXHAUSTED) {
+        // the enqueue-only search's documented misses: the host entry point repeats such a batch, under the same block
+        std::vector<uint64_t> block((size_t)nq * stride);
+        SCANN_HIP_CHECK(hipMemcpy(block.data(), b.block.p, block.size() * 8, hipMemcpyDeviceToHost));
+        o.allow_bitmap = block.data();
+        return scann_hip_search_batched(index, queries, nq, q_stride, q_dim, k, &o, out_idx, out_dist, out_count);
+    }
+    SCANN_TRY(status);
+    SCANN_HIP_CHECK(hipMemcpyAsync(out_idx, b.idx.p, ob, hipMemcpyDeviceToHost, st));
+    SCANN_HIP_CHECK(hipMemcpyAsync(out_dist, b.dist.p, ob, hipMemcpyDeviceToHost, st));
+    SCANN_HIP_CHECK(hipMemcpyAsync(out_count, b.count.p, (size_t)nq * 4, hipMemcpyDeviceToHost, st));
+    SCANN_HIP_CHECK(hipStreamSynchronize(st));
+    return SCANN_HIP_OK;
 }
 
 }  // namespace scann

@@ -21,6 +21,35 @@ __host__ __device__ static inline uint64_t allow_combine_word(int op, uint64_t a
     }
 }
 
+// threads of a workgroup of the kernels that write bitmap blocks (token_bitmap_kernel, allow_combine_kernel,
+// range_bitmap_kernel)
+constexpr uint32_t kBitmapThreads = 256;
+
+#ifdef __HIPCC__
+// nw words to dst (8-byte aligned), from src (LDS) or zeros (src null): 16-byte stores wherever dst allows them, an
+// 8-byte store for a misaligned first word and for an odd last one.  Every thread of a block of kBitmapThreads calls.
+__device__ __forceinline__ void store_words(uint64_t *__restrict__ dst, const uint64_t *src, uint64_t nw) {
+    if (nw == 0) return;
+    const uint64_t head = ((uint64_t)dst >> 3) & 1ull;
+    const uint64_t pairs = (nw - head) >> 1, tail = (nw - head) & 1ull;
+    if (threadIdx.x == 0) {
+        if (head) dst[0] = src ? src[0] : 0ull;
+        if (tail) dst[nw - 1] = src ? src[nw - 1] : 0ull;
+    }
+    typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
+    for (uint64_t p = threadIdx.x; p < pairs; p += kBitmapThreads) {
+        const uint64_t w = head + 2 * p;
+        u64x2 v = {0ull, 0ull};
+        if (src) v = u64x2{src[w], src[w + 1]};
+#ifdef SCANN_TOKEN_NT_STORES   // (tools/time_token_filters.py's variant build: DESIGN 3.3c-t has the comparison)
+        __builtin_nontemporal_store(v, reinterpret_cast<u64x2 *>(dst + w));
+#else
+        *reinterpret_cast<u64x2 *>(dst + w) = v;
+#endif
+    }
+}
+#endif
+
 // d_out[i * stride .. (i + 1) * stride): bit j set iff j is in the posting of one of query i's tokens
 // d_q_tokens[d_q_offsets[i] .. d_q_offsets[i + 1]); every other word zero.  The map is three device arrays: ntok
 // ascending distinct tokens, ntok + 1 posting offsets, the ascending in-range (< bits) postings.  stride >=

@@ -30,7 +30,7 @@ namespace scann {
 
 namespace {
 
-constexpr uint32_t kTokThreads = 256;
+constexpr uint32_t kTokThreads = kBitmapThreads;
 
 // ---- host form of the map: the model of the device arrays, and what get_indices reads ---------------------------
 struct TokenCsr {
@@ -79,14 +79,6 @@ void csr_bitmaps_host(const TokenCsr &m, const uint64_t *q_tokens, const uint64_
     }
 }
 
-// the checks every form of the bitmap builder shares (host-readable arguments only)
-int check_block_args(uint64_t bits, uint64_t stride_words) {
-    if (stride_words < allow_words(bits))
-        return fail(SCANN_HIP_INVALID_ARGUMENT, "allow-bitmap stride is smaller than one bitmap (ceil(bits / 64) words)");
-    if (stride_words > 0xFFFFFFFFull)   // (check_allow_stride's limit: the search kernels carry the stride in 32 bits)
-        return fail(SCANN_HIP_INVALID_ARGUMENT, "allow-bitmap stride must be below 2^32 words");
-    return SCANN_HIP_OK;
-}
 int check_host_lists(const uint64_t *q_tokens, const uint64_t *q_offsets, uint32_t nq) {
     if (!q_offsets) return fail(SCANN_HIP_INVALID_ARGUMENT, "null offsets pointer");
     for (uint32_t q = 0; q < nq; ++q)
@@ -124,29 +116,6 @@ __device__ __forceinline__ uint64_t group_lower_bound(const T *__restrict__ a, u
         lo = nlo;
     }
     return lo;
-}
-
-// nw words to dst (8-byte aligned), from src (LDS) or zeros (src null): 16-byte stores wherever dst allows them, an
-// 8-byte store for a misaligned first word and for an odd last one.  Every thread of the block calls.
-__device__ __forceinline__ void store_words(uint64_t *__restrict__ dst, const uint64_t *src, uint64_t nw) {
-    if (nw == 0) return;
-    const uint64_t head = ((uint64_t)dst >> 3) & 1ull;
-    const uint64_t pairs = (nw - head) >> 1, tail = (nw - head) & 1ull;
-    if (threadIdx.x == 0) {
-        if (head) dst[0] = src ? src[0] : 0ull;
-        if (tail) dst[nw - 1] = src ? src[nw - 1] : 0ull;
-    }
-    typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
-    for (uint64_t p = threadIdx.x; p < pairs; p += kTokThreads) {
-        const uint64_t w = head + 2 * p;
-        u64x2 v = {0ull, 0ull};
-        if (src) v = u64x2{src[w], src[w + 1]};
-#ifdef SCANN_TOKEN_NT_STORES   // (tools/time_token_filters.py's variant build: DESIGN 3.3c-t has the comparison)
-        __builtin_nontemporal_store(v, reinterpret_cast<u64x2 *>(dst + w));
-#else
-        *reinterpret_cast<u64x2 *>(dst + w) = v;
-#endif
-    }
 }
 
 __global__ __launch_bounds__(kTokThreads) void token_bitmap_kernel(
@@ -340,7 +309,8 @@ struct scann_hip_token_map {
     // the host-pointer forms: one stream and grow-only staging buffers, one call at a time
     std::mutex mu;
     hipStream_t stream = nullptr;
-    DevBuf s_tokens, s_offsets, s_block, s_queries, s_idx, s_dist, s_count;
+    DevBuf s_tokens, s_offsets;
+    FilterSearchBufs fs;   // fs.block: the block of the host-pointer forms
     ~scann_hip_token_map() {
         if (stream) (void)hipStreamDestroy(stream);
     }
@@ -348,12 +318,12 @@ struct scann_hip_token_map {
 
 namespace {
 
-// the host-pointer form under m->mu: lists up, one kernel, the block left in m->s_block (no copy back, no synchronise)
+// the host-pointer form under m->mu: lists up, one kernel, the block left in m->fs.block (no copy back, no synchronise)
 int stage_block(scann_hip_token_map *m, const uint64_t *q_tokens, const uint64_t *q_offsets, uint32_t nq, uint64_t stride) {
     const uint64_t nt = q_offsets[nq] - q_offsets[0];
     SCANN_TRY(m->s_tokens.ensure(nt * 8));
     SCANN_TRY(m->s_offsets.ensure(((size_t)nq + 1) * 8));
-    SCANN_TRY(m->s_block.ensure((size_t)nq * stride * 8));
+    SCANN_TRY(m->fs.block.ensure((size_t)nq * stride * 8));
     if (nt) SCANN_HIP_CHECK(hipMemcpyAsync(m->s_tokens.p, q_tokens + q_offsets[0], nt * 8, hipMemcpyHostToDevice, m->stream));
     std::vector<uint64_t> rel((size_t)nq + 1);   // offsets relative to the first token sent
     for (uint32_t q = 0; q <= nq; ++q) rel[q] = q_offsets[q] - q_offsets[0];
@@ -361,7 +331,7 @@ int stage_block(scann_hip_token_map *m, const uint64_t *q_tokens, const uint64_t
     SCANN_HIP_CHECK(hipStreamSynchronize(m->stream));   // rel leaves scope; pageable copies may still be in flight
     return token_bitmaps_launch(m->d_tokens.as<uint64_t>(), m->host.tokens.size(), m->d_offsets.as<uint64_t>(),
                                 m->d_postings.as<uint32_t>(), m->s_tokens.as<uint64_t>(), m->s_offsets.as<uint64_t>(), nq,
-                                m->n, stride, m->s_block.as<uint64_t>(), m->stream);
+                                m->n, stride, m->fs.block.as<uint64_t>(), m->stream);
 }
 
 }  // namespace
@@ -435,7 +405,7 @@ int scann_hip_token_map_allow_bitmaps(scann_hip_token_map *m, const uint64_t *to
     std::lock_guard<std::mutex> lock(m->mu);
     SCANN_HIP_CHECK(hipSetDevice(m->device));
     SCANN_TRY(stage_block(m, tokens, offsets, nq, stride_words));
-    SCANN_HIP_CHECK(hipMemcpyAsync(out_words, m->s_block.p, (size_t)nq * stride_words * 8, hipMemcpyDeviceToHost, m->stream));
+    SCANN_HIP_CHECK(hipMemcpyAsync(out_words, m->fs.block.p, (size_t)nq * stride_words * 8, hipMemcpyDeviceToHost, m->stream));
     SCANN_HIP_CHECK(hipStreamSynchronize(m->stream));
     return SCANN_HIP_OK;
 }
@@ -462,11 +432,7 @@ int scann_hip_search_batched_tokens(scann_hip_index *index, scann_hip_token_map 
                                     uint32_t *out_count) {
     if (!index || !m) return fail(SCANN_HIP_INVALID_ARGUMENT, "null index/token map");
     if (nq == 0) return SCANN_HIP_OK;
-    if (!queries || !out_idx || !out_dist || !out_count) return fail(SCANN_HIP_INVALID_ARGUMENT, "null query/output pointer");
-    if (k == 0) return fail(SCANN_HIP_INVALID_ARGUMENT, "k must be > 0");
-    if (opts && opts->allow_bitmap) return fail(SCANN_HIP_INVALID_ARGUMENT, "the token lists are the filter: allow_bitmap must be null");
-    if (q_dim != scann_hip_index_dimensionality(index)) return fail(SCANN_HIP_INVALID_ARGUMENT, "Query dimensionality mismatch");
-    if (q_stride < q_dim) return fail(SCANN_HIP_INVALID_ARGUMENT, "q_stride < q_dim");
+    SCANN_TRY(filter_search_check(index, queries, q_stride, q_dim, k, opts, out_idx, out_dist, out_count, "the token lists"));
     SCANN_TRY(check_host_lists(q_tokens, q_offsets, nq));
     const uint64_t stride = std::max<uint64_t>(allow_words(m->n), 1);   // (a stride of 0 would mean one shared bitmap)
     scann_hip_search_opts o;
@@ -474,33 +440,11 @@ int scann_hip_search_batched_tokens(scann_hip_index *index, scann_hip_token_map 
     else scann_hip_search_opts_default(&o);
     std::lock_guard<std::mutex> lock(m->mu);
     SCANN_HIP_CHECK(hipSetDevice(m->device));
-    const size_t qb = (size_t)nq * q_stride * 4, ob = (size_t)nq * k * 4;
-    SCANN_TRY(m->s_queries.ensure(qb));
-    SCANN_TRY(m->s_idx.ensure(ob));
-    SCANN_TRY(m->s_dist.ensure(ob));
-    SCANN_TRY(m->s_count.ensure((size_t)nq * 4));
-    SCANN_HIP_CHECK(hipMemcpyAsync(m->s_queries.p, queries, qb, hipMemcpyHostToDevice, m->stream));
+    SCANN_TRY(filter_search_begin(m->fs, m->stream, queries, nq, q_stride, k));
     // the block is built and read on one stream, with nothing between the two enqueues
     SCANN_TRY(stage_block(m, q_tokens, q_offsets, nq, stride));
-    o.allow_bitmap = m->s_block.as<uint64_t>();
-    o.allow_bitmap_bits = m->n;
-    o.allow_bitmap_stride = stride;
-    SCANN_TRY(scann_hip_search_batched_device(index, m->s_queries.as<float>(), nq, q_stride, k, &o, m->s_idx.as<uint32_t>(),
-                                              m->s_dist.as<float>(), m->s_count.as<uint32_t>(), m->stream));
-    const int status = scann_hip_index_last_device_status(index, m->stream);   // (synchronises the stream)
-    if (status == SCANN_HIP_ABORTED || status == SCANN_HIP_RESOURCE_EXHAUSTED) {
-        // the enqueue-only search's documented misses: the host entry point repeats such a batch, under the same block
-        std::vector<uint64_t> block((size_t)nq * stride);
-        SCANN_HIP_CHECK(hipMemcpy(block.data(), m->s_block.p, block.size() * 8, hipMemcpyDeviceToHost));
-        o.allow_bitmap = block.data();
-        return scann_hip_search_batched(index, queries, nq, q_stride, q_dim, k, &o, out_idx, out_dist, out_count);
-    }
-    SCANN_TRY(status);
-    SCANN_HIP_CHECK(hipMemcpyAsync(out_idx, m->s_idx.p, ob, hipMemcpyDeviceToHost, m->stream));
-    SCANN_HIP_CHECK(hipMemcpyAsync(out_dist, m->s_dist.p, ob, hipMemcpyDeviceToHost, m->stream));
-    SCANN_HIP_CHECK(hipMemcpyAsync(out_count, m->s_count.p, (size_t)nq * 4, hipMemcpyDeviceToHost, m->stream));
-    SCANN_HIP_CHECK(hipStreamSynchronize(m->stream));
-    return SCANN_HIP_OK;
+    return filter_search_finish(index, m->fs, m->stream, queries, nq, q_stride, q_dim, k, o, m->n, stride, out_idx, out_dist,
+                                out_count);
 }
 
 int scann_hip_allow_bitmaps_combine(int op, const uint64_t *a, uint64_t stride_a, const uint64_t *b, uint64_t stride_b,

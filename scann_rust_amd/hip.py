@@ -24,6 +24,10 @@ MUTABLE_DELTA_TILE = 1024      # SCANN_HIP_MUTABLE_DELTA_TILE: delta rows sorted
 FOLD_CHUNK = 1024              # SCANN_HIP_FOLD_CHUNK: CSR positions per workgroup of the fold's count and scatter passes
 TOKEN_TILE_BITS = 65536        # SCANN_HIP_TOKEN_TILE_BITS: bits of one query's bitmap a workgroup of the token-map kernel assembles in LDS
 ALLOW_AND, ALLOW_OR, ALLOW_ANDNOT, ALLOW_NOT = 1, 2, 3, 4   # SCANN_HIP_ALLOW_*: ops of allow_bitmaps_combine
+ATTR_I64, ATTR_F32 = 1, 2      # SCANN_HIP_ATTR_*: column types of an AttrTable
+ATTR_ROW_INDEX = 0xFFFFFFFF    # SCANN_HIP_ATTR_ROW_INDEX: the pseudo-column whose value at row j is j (RangeFilter)
+ATTR_MAX_CLAUSES = 8           # SCANN_HIP_ATTR_MAX_CLAUSES: clauses of one range call
+RANGE_TILE_BITS = 1024         # SCANN_HIP_RANGE_TILE_BITS: rows whose values a workgroup of the range kernel holds in registers
 
 _CODE_NAMES = {
     0: "Ok", 1: "Cancelled", 2: "Unknown", 3: "InvalidArgument", 4: "DeadlineExceeded",
@@ -67,6 +71,9 @@ EXPORTS = [
     "scann_hip_token_map_num_datapoints", "scann_hip_token_map_get_indices", "scann_hip_token_map_allow_bitmaps_device",
     "scann_hip_token_map_allow_bitmaps", "scann_hip_allow_bitmaps_from_tokens", "scann_hip_search_batched_tokens",
     "scann_hip_allow_bitmaps_combine", "scann_hip_allow_bitmaps_combine_device",
+    "scann_hip_attr_table_create", "scann_hip_attr_table_destroy", "scann_hip_attr_table_num_datapoints",
+    "scann_hip_attr_table_num_columns", "scann_hip_attr_table_column_type", "scann_hip_attr_table_allow_bitmaps_device",
+    "scann_hip_attr_table_allow_bitmaps", "scann_hip_allow_bitmaps_from_ranges", "scann_hip_search_batched_ranges",
     "scann_hip_index_quantization_stats", "scann_hip_scalar_quantizer_calibrate", "scann_hip_scalar_quantize",
     "scann_hip_scalar_dequantize", "scann_hip_scalar_quantize_device", "scann_hip_index_quantize_rows",
     "scann_hip_projection_create", "scann_hip_projection_destroy", "scann_hip_projection_info", "scann_hip_project",
@@ -322,6 +329,20 @@ def load():
                                                   u64p, C.c_uint64]
     L.scann_hip_allow_bitmaps_combine_device.argtypes = [vp, C.c_int, vp, C.c_uint64, vp, C.c_uint64, C.c_uint32,
                                                          C.c_uint64, vp, C.c_uint64, vp]
+    L.scann_hip_attr_table_create.argtypes = [vp, C.c_uint64, C.c_uint32, i32p, C.POINTER(vp), C.POINTER(vp)]
+    L.scann_hip_attr_table_destroy.argtypes = [vp]
+    L.scann_hip_attr_table_destroy.restype = None
+    L.scann_hip_attr_table_num_datapoints.restype = C.c_uint64
+    L.scann_hip_attr_table_num_datapoints.argtypes = [vp]
+    L.scann_hip_attr_table_num_columns.restype = C.c_uint32
+    L.scann_hip_attr_table_num_columns.argtypes = [vp]
+    L.scann_hip_attr_table_column_type.argtypes = [vp, C.c_uint32]
+    L.scann_hip_attr_table_allow_bitmaps_device.argtypes = [vp, u32p, C.c_uint32, vp, C.c_uint32, C.c_int, C.c_uint64, vp, vp]
+    L.scann_hip_attr_table_allow_bitmaps.argtypes = [vp, u32p, C.c_uint32, u64p, C.c_uint32, C.c_int, C.c_uint64, u64p]
+    L.scann_hip_allow_bitmaps_from_ranges.argtypes = [C.c_uint64, C.c_uint32, i32p, C.POINTER(vp), u32p, C.c_uint32, u64p,
+                                                      C.c_uint32, C.c_int, C.c_uint64, u64p]
+    L.scann_hip_search_batched_ranges.argtypes = [vp, vp, f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                  C.POINTER(SearchOpts), u32p, C.c_uint32, u64p, u32p, f32p, u32p]
     L.scann_hip_index_quantization_stats.argtypes = [vp, f32p]
     L.scann_hip_scalar_quantizer_calibrate.argtypes = [f32p, C.c_uint32, C.c_int, C.c_float, C.c_float, f32p, i32p]
     L.scann_hip_scalar_quantize.argtypes = [f32p, C.c_uint64, C.c_uint32, C.c_int, f32p, i8p]
@@ -982,6 +1003,157 @@ def allow_bitmaps_from_tokens(indices, tokens, num_datapoints, token_lists, stri
     check(load().scann_hip_allow_bitmaps_from_tokens(ptr(idx, u32p) if idx.size else None, ptr(tok, u64p) if tok.size else None,
                                                      idx.size, int(num_datapoints), ptr(qt, u64p) if qt.size else None,
                                                      ptr(off, u64p), nq, stride, ptr(out, u64p) if out.size else None))
+    return out
+
+
+def _attr_columns(n, columns):
+    """(types int32[n_columns], the columns as contiguous arrays, a void*[n_columns] of their addresses): int64 arrays are
+    ATTR_I64 columns, float32 arrays ATTR_F32 ones; anything else is refused rather than converted"""
+    cols = []
+    for i, c in enumerate(columns):
+        c = np.asarray(c)
+        if c.dtype not in (np.dtype(np.int64), np.dtype(np.float32)):
+            raise ValueError("column %d: dtype %s is neither int64 nor float32" % (i, c.dtype))
+        c = np.ascontiguousarray(c).ravel()
+        if c.size != int(n):
+            raise ValueError("column %d holds %d values, num_datapoints is %d" % (i, c.size, int(n)))
+        cols.append(c)
+    types = np.array([ATTR_I64 if c.dtype == np.int64 else ATTR_F32 for c in cols], np.int32)
+    ptrs = (vp * max(len(cols), 1))(*[c.ctypes.data if c.size else None for c in cols])
+    return types, cols, ptrs
+
+
+def _range_bounds(cols_types, lo, hi):
+    """[nq, n_cols, 2] uint64 bound words of a range call: cols_types[c] is clause c's type (ATTR_I64, ATTR_F32, or 0 /
+    ATTR_ROW_INDEX for the row index, whose bounds are int64), lo[c] / hi[c] its per-query inclusive bounds (nq values,
+    or a scalar for every query).  An f32 bound sits in the low four bytes of its word."""
+    n_cols = len(cols_types)
+    if len(lo) != n_cols or len(hi) != n_cols:
+        raise ValueError("one lo and one hi array per clause")
+    nq = max([np.size(x) for x in list(lo) + list(hi)] + [1])
+    out = np.zeros((nq, n_cols, 2), np.uint64)
+    for c, t in enumerate(cols_types):
+        for side, x in enumerate((lo[c], hi[c])):
+            if t == ATTR_F32:
+                w = np.broadcast_to(np.asarray(x, np.float32), (nq,)).copy().view(np.uint32).astype(np.uint64)
+            else:
+                w = np.broadcast_to(np.asarray(x, np.int64), (nq,)).copy().view(np.uint64)
+            out[:, c, side] = w
+    return out
+
+
+def _range_call(n, cols, bounds, stride, op, out):
+    """(cols uint32, bounds uint64 [nq, n_cols, 2], nq, stride, the output block) of a range call's arguments"""
+    cols = np.ascontiguousarray(cols, np.uint32).ravel()
+    b = np.ascontiguousarray(bounds, np.uint64)
+    if b.ndim != 3 or b.shape[1] != cols.size or b.shape[2] != 2:
+        raise ValueError("bounds must be [nq, n_cols, 2] bound words (hip._range_bounds)")
+    nq = b.shape[0]
+    stride = (int(n) + 63) // 64 if stride is None else int(stride)
+    if out is None:
+        if op != 0:
+            raise ValueError("an in-place op needs the block it combines into (out=)")
+        out = np.empty((nq, stride), np.uint64)
+    if out.dtype != np.uint64 or out.ndim != 2 or out.shape != (nq, stride) or not out.flags.c_contiguous:
+        raise ValueError("out must be a C-contiguous [nq, stride] uint64 block")
+    return cols, b, nq, stride, out
+
+
+class AttrTable:
+    """Owns one scann_hip_attr_table: typed attribute columns resident on the device.  `columns` is a list of numpy
+    arrays of num_datapoints values each; int64 / float32 decide the type.  ATTR_ROW_INDEX names the row index as a
+    clause column (the reference's RangeFilter).  The table does not change after it is created."""
+
+    def __init__(self, num_datapoints, columns=(), device=0):
+        types, cols, ptrs = _attr_columns(num_datapoints, columns)
+        self.h = vp()
+        self.device = device
+        check(load().scann_hip_attr_table_create(context(device), int(num_datapoints), len(cols),
+                                                 ptr(types, i32p) if len(cols) else None, ptrs, C.byref(self.h)))
+
+    def close(self):
+        if self.h:
+            load().scann_hip_attr_table_destroy(self.h)
+            self.h = None
+
+    destroy = close
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def num_datapoints(self):
+        return int(load().scann_hip_attr_table_num_datapoints(self.h))
+
+    def num_columns(self):
+        return int(load().scann_hip_attr_table_num_columns(self.h))
+
+    def column_type(self, column):
+        """ATTR_I64 / ATTR_F32; 0 for an unknown column"""
+        return int(load().scann_hip_attr_table_column_type(self.h, int(column)))
+
+    def clause_types(self, cols):
+        """the types _range_bounds wants for the clause columns `cols` (0 for the row index)"""
+        return [0 if int(c) == ATTR_ROW_INDEX else self.column_type(c) for c in cols]
+
+    def allow_bitmaps(self, cols, bounds, stride=None, op=0, out=None):
+        """[nq, stride] uint64 block: bit j of row q is the AND over the clauses of lo <= value(cols[c], j) <= hi,
+        bounds = _range_bounds(...) ([nq, n_cols, 2] words), built by the device kernel.  op 0 writes a new block (or
+        all of `out`); ALLOW_AND / ALLOW_OR / ALLOW_ANDNOT combine the range into `out` in place.  stride defaults to
+        ceil(num_datapoints / 64).  Pass the block as `allow=` (2-D) with allow_bits=num_datapoints()."""
+        cols, b, nq, stride, out = _range_call(self.num_datapoints(), cols, bounds, stride, op, out)
+        check(load().scann_hip_attr_table_allow_bitmaps(self.h, ptr(cols, u32p) if cols.size else None, cols.size,
+                                                        ptr(b, u64p) if b.size else None, nq, int(op), stride,
+                                                        ptr(out, u64p) if out.size else None))
+        return out
+
+    def allow_bitmaps_device(self, cols, d_bounds, nq, stride_words, d_out_words, op=0, stream=0):
+        """scann_hip_attr_table_allow_bitmaps_device: cols on the host, device addresses (integers) for the bound words
+        and the block, a HIP stream handle; one kernel is enqueued, nothing is synchronised.  d_out_words holds nq *
+        stride_words uint64."""
+        cols = np.ascontiguousarray(cols, np.uint32).ravel()
+        check(load().scann_hip_attr_table_allow_bitmaps_device(self.h, ptr(cols, u32p) if cols.size else None, cols.size,
+                                                               vp(d_bounds or None), int(nq), int(op), int(stride_words),
+                                                               vp(d_out_words), vp(stream)))
+
+    def search_batched(self, index, queries, k, cols, bounds, opts=None, q_dim=None):
+        """scann_hip_search_batched_ranges: query i of a tree / flat-hasher Index under the ranges bounds[i]; the block
+        is built on the device and searched on the same stream.  Returns (idx, dist, count)."""
+        q = f32(queries)
+        if q.ndim == 1:
+            q = q[None]
+        nq, qs = q.shape
+        cols = np.ascontiguousarray(cols, np.uint32).ravel()
+        b = np.ascontiguousarray(bounds, np.uint64)
+        if b.shape != (nq, cols.size, 2):
+            raise ValueError("one range per query and clause: bounds %s, %d queries, %d clauses" % (b.shape, nq, cols.size))
+        out_idx = np.full((nq, max(k, 1)), 0xFFFFFFFF, np.uint32)
+        out_dist = np.full((nq, max(k, 1)), np.inf, np.float32)
+        out_cnt = np.zeros(nq, np.uint32)
+        check(load().scann_hip_search_batched_ranges(index.h, self.h, ptr(q, f32p), nq, qs, qs if q_dim is None else q_dim,
+                                                     k, C.byref(opts) if opts is not None else None,
+                                                     ptr(cols, u32p) if cols.size else None, cols.size,
+                                                     ptr(b, u64p) if b.size else None, ptr(out_idx, u32p),
+                                                     ptr(out_dist, f32p), ptr(out_cnt, u32p)))
+        return out_idx, out_dist, out_cnt
+
+
+def search_batched_ranges(index, table, queries, k, cols, bounds, opts=None, q_dim=None):
+    """scann_hip_search_batched_ranges (AttrTable.search_batched)"""
+    return table.search_batched(index, queries, k, cols, bounds, opts, q_dim)
+
+
+def allow_bitmaps_from_ranges(num_datapoints, columns, cols, bounds, stride=None, op=0, out=None):
+    """The stateless host form of AttrTable(num_datapoints, columns).allow_bitmaps(cols, bounds, ...): no context, no
+    GPU; the model the device forms equal bitwise."""
+    types, arrs, ptrs = _attr_columns(num_datapoints, columns)
+    cols, b, nq, stride, out = _range_call(num_datapoints, cols, bounds, stride, op, out)
+    check(load().scann_hip_allow_bitmaps_from_ranges(int(num_datapoints), len(arrs), ptr(types, i32p) if len(arrs) else None,
+                                                     ptrs, ptr(cols, u32p) if cols.size else None, cols.size,
+                                                     ptr(b, u64p) if b.size else None, nq, int(op), stride,
+                                                     ptr(out, u64p) if out.size else None))
     return out
 
 

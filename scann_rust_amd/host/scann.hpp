@@ -217,6 +217,68 @@ private:
     RestrictAllowlist deny_;
 };
 
+// Range-based filter (restricts/mod.rs:73-95): allows indices in [start, end).  num_allowed is end - start where the
+// range is well formed and 0 where it is not (start > end: the reference's subtraction underflows there).
+class RangeFilter : public RestrictFilter {
+public:
+    RangeFilter(DatapointIndex start, DatapointIndex end) : start_(start), end_(end) {}
+    bool is_allowed(DatapointIndex index) const override { return index >= start_ && index < end_; }
+    size_t num_allowed() const { return end_ > start_ ? (size_t)(end_ - start_) : 0; }
+    DatapointIndex start() const { return start_; }
+    DatapointIndex end() const { return end_; }
+    // the same filter as a clause on an AttributeTable's row-index column: lo = start, hi = end - 1 as i64
+    scann_hip_range_bound lo_bound() const { scann_hip_range_bound b; b.i64 = (int64_t)start_; return b; }
+    scann_hip_range_bound hi_bound() const { scann_hip_range_bound b; b.i64 = (int64_t)end_ - 1; return b; }
+
+private:
+    DatapointIndex start_, end_;
+};
+
+// Typed attribute columns resident on the device (scann_hip_attr_table): int64 and float columns of one value per
+// datapoint, uploaded once; a batch names clause columns and gives one inclusive range per (query, clause).  The
+// table is a snapshot: build a new one to change a value.
+class AttributeTable {
+public:
+    static constexpr uint32_t kRowIndex = SCANN_HIP_ATTR_ROW_INDEX;   // the clause column of RangeFilter
+    AttributeTable() = default;
+    explicit AttributeTable(scann_hip_attr_table *h) : h_(h) {}
+    // columns of num_datapoints values each; types[c] is SCANN_HIP_ATTR_I64 (int64_t) or SCANN_HIP_ATTR_F32 (float)
+    AttributeTable(scann_hip_ctx *ctx, size_t num_datapoints, const std::vector<int32_t> &types,
+                   const std::vector<const void *> &columns) {
+        if (types.size() != columns.size()) throw ScannError::invalid_argument("one type per column");
+        check(scann_hip_attr_table_create(ctx, num_datapoints, (uint32_t)types.size(), types.data(), columns.data(), &h_));
+    }
+    AttributeTable(const AttributeTable &) = delete;
+    AttributeTable &operator=(const AttributeTable &) = delete;
+    AttributeTable(AttributeTable &&o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+    AttributeTable &operator=(AttributeTable &&o) noexcept {
+        if (this != &o) { reset(); h_ = o.h_; o.h_ = nullptr; }
+        return *this;
+    }
+    ~AttributeTable() { reset(); }
+    void reset() { if (h_) scann_hip_attr_table_destroy(h_); h_ = nullptr; }
+    scann_hip_attr_table *handle() const { return h_; }
+    size_t num_datapoints() const { return h_ ? (size_t)scann_hip_attr_table_num_datapoints(h_) : 0; }
+    size_t num_columns() const { return h_ ? (size_t)scann_hip_attr_table_num_columns(h_) : 0; }
+    int column_type(uint32_t column) const { return h_ ? scann_hip_attr_table_column_type(h_, column) : 0; }
+    static scann_hip_range_bound i64_bound(int64_t v) { scann_hip_range_bound b; b.i64 = v; return b; }
+    static scann_hip_range_bound f32_bound(float v) { scann_hip_range_bound b; b.bits = 0; b.f32 = v; return b; }
+    // one bitmap per query ([nq][ceil(n / 64)] words): bounds[q * cols.size() * 2 + c * 2 + {0, 1}] = lo, hi
+    std::vector<uint64_t> allow_bitmaps(const std::vector<uint32_t> &cols, const std::vector<scann_hip_range_bound> &bounds,
+                                        size_t nq) const {
+        if (!h_) throw ScannError::failed_precondition("the attribute table is not on the device");
+        if (bounds.size() != nq * cols.size() * 2) throw ScannError::invalid_argument("two bounds per query and clause");
+        const size_t words = (num_datapoints() + 63) / 64;
+        std::vector<uint64_t> out(nq * words);
+        check(scann_hip_attr_table_allow_bitmaps(h_, cols.data(), (uint32_t)cols.size(), bounds.data(), (uint32_t)nq, 0, words,
+                                                 out.data()));
+        return out;
+    }
+
+private:
+    scann_hip_attr_table *h_ = nullptr;
+};
+
 // A RestrictTokenMap resident on the device (scann_hip_token_map): what RestrictTokenMap::to_device returns.  The
 // map is a snapshot: tokens added to the host map afterwards are not in it (build a new one).
 class DeviceTokenMap {
@@ -626,6 +688,29 @@ inline std::vector<NNResultsVector> run_search_tokens(scann_hip_index *h, const 
     std::vector<float> dist((size_t)nq * std::max(1u, kk));
     check(scann_hip_search_batched_tokens(h, map.handle(), flat.data(), nq, d, d, kk, &o, tok.data(), off.data(), idx.data(),
                                           dist.data(), cnt.data()));
+    std::vector<NNResultsVector> out(nq);
+    for (uint32_t i = 0; i < nq; ++i)
+        for (uint32_t j = 0; j < cnt[i]; ++j) out[i].emplace_back(idx[(size_t)i * kk + j], dist[(size_t)i * kk + j]);
+    return out;
+}
+
+// query i under the conjunction of ranges bounds[i * cols.size() * 2 + c * 2 + {0, 1}] over the table's clause columns
+// `cols`: the block is built on the device from the resident columns and searched on the same stream
+// (scann_hip_search_batched_ranges)
+inline std::vector<NNResultsVector> run_search_ranges(scann_hip_index *h, const std::vector<std::vector<float>> &queries,
+                                                      size_t k, const std::vector<uint32_t> &cols,
+                                                      const std::vector<scann_hip_range_bound> &bounds,
+                                                      const AttributeTable &table, const scann_hip_search_opts &o) {
+    if (bounds.size() != queries.size() * cols.size() * 2) throw ScannError::invalid_argument("two bounds per query and clause");
+    if (!table.handle()) throw ScannError::failed_precondition("the attribute table is not on the device");
+    if (queries.empty()) return {};
+    uint32_t d;
+    const auto flat = flatten(queries, &d);
+    const uint32_t nq = (uint32_t)queries.size(), kk = (uint32_t)k;
+    std::vector<uint32_t> idx((size_t)nq * std::max(1u, kk)), cnt(nq);
+    std::vector<float> dist((size_t)nq * std::max(1u, kk));
+    check(scann_hip_search_batched_ranges(h, table.handle(), flat.data(), nq, d, d, kk, &o, cols.data(), (uint32_t)cols.size(),
+                                          bounds.data(), idx.data(), dist.data(), cnt.data()));
     std::vector<NNResultsVector> out(nq);
     for (uint32_t i = 0; i < nq; ++i)
         for (uint32_t j = 0; j < cnt[i]; ++j) out[i].emplace_back(idx[(size_t)i * kk + j], dist[(size_t)i * kk + j]);
@@ -1425,6 +1510,18 @@ public:
         o.exact_reorder = 0;
         return detail::run_search_tokens(ix_.h, queries, k, token_lists, device_map, o);
     }
+    // query i under the ranges bounds[(i * cols.size() + c) * 2 + {0, 1}] over `table`'s clause columns `cols`: the
+    // bitmap block is built on the device from the resident columns and searched on the same stream
+    std::vector<NNResultsVector> search_batched_with_ranges(const std::vector<std::vector<float>> &queries, size_t k,
+                                                            const std::vector<uint32_t> &cols,
+                                                            const std::vector<scann_hip_range_bound> &bounds,
+                                                            const AttributeTable &table) const {
+        if (!ix_.h) return std::vector<NNResultsVector>(queries.size());
+        scann_hip_search_opts o;
+        scann_hip_search_opts_default(&o);
+        o.exact_reorder = 0;
+        return detail::run_search_ranges(ix_.h, queries, k, cols, bounds, table, o);
+    }
     size_t num_datapoints() const { return n_; }
     size_t dimensionality() const { return dim_; }
     const std::vector<float> &codebook() const { return codebook_; }
@@ -1631,6 +1728,17 @@ public:
         scann_hip_search_opts o;
         scann_hip_search_opts_default(&o);
         return detail::run_search_tokens(ix_.h, queries, k, token_lists, device_map, o);
+    }
+    // query i under the ranges bounds[(i * cols.size() + c) * 2 + {0, 1}] over `table`'s clause columns `cols`: the
+    // bitmap block is built on the device from the resident columns and searched on the same stream
+    std::vector<NNResultsVector> search_batched_with_ranges(const std::vector<std::vector<float>> &queries, size_t k,
+                                                            const std::vector<uint32_t> &cols,
+                                                            const std::vector<scann_hip_range_bound> &bounds,
+                                                            const AttributeTable &table) const {
+        if (!ix_.h) throw ScannError::failed_precondition("Partitioner not built");
+        scann_hip_search_opts o;
+        scann_hip_search_opts_default(&o);
+        return detail::run_search_ranges(ix_.h, queries, k, cols, bounds, table, o);
     }
     // Searcher::search_batched_with_params (tree_x_hybrid/mod.rs:399-409): params[i].num_neighbors per query
     std::vector<NNResultsVector> search_batched_with_params(const std::vector<std::vector<float>> &queries,
