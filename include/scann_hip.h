@@ -1368,6 +1368,75 @@ void scann_hip_build_config_default(scann_hip_build_config *cfg);
 int scann_hip_txh_build(scann_hip_index *rows, const scann_hip_build_config *cfg, scann_hip_index **out_index,
                         scann_hip_build_report *out_report);
 
+/* ---- hierarchical device build ------------------------------------------------------
+ * scann_hip_txh_build_hierarchical: scann_hip_txh_build with the partitioner of TreePartitioner::build_hierarchical
+ * (partitioning/tree_partitioner.rs:101-140) -- a KMeansTree (trees/kmeans_tree.rs:183-284) built on the device and
+ * flattened to its leaves.  The result is an ordinary tree handle whose partitions are the tree's leaves and whose
+ * centres are the leaves' means: search, filters, fold and index files treat it like any other; the tree itself is not
+ * kept.  A tree of depth 2 with c children per node scores every row against 2 c centres per iteration for up to c^2
+ * leaves, where the flat partitioner scores it against all c^2.
+ * COMPOSITION: the reference has build_hierarchical but no searcher of it calls it; feeding the flattened
+ * leaves to steps 2-5 of scann_hip_txh_build is this project's own composition.
+ * Of `cfg`, num_partitions, kmeans_iterations, kmeans_convergence and kmeans_seed are IGNORED: `tree` replaces them.
+ * Every other field means what it means to scann_hip_txh_build (simd_threshold also governs the tree's k-means).
+ *
+ * THE RULE, as a function of the seeds -- every array of the new handle is bit-identical to these steps run through
+ * the public primitives:
+ *   1 tree          build_node (kmeans_tree.rs:212-267) over nodes whose members are ascending datapoint indices; the
+ *                   root holds every row at depth 0.  A node at depth d with n_node members is a LEAF when
+ *                   d >= max_depth, n_node <= min_leaf_size or n_node <= num_children.  Any other node trains
+ *                   k = min(num_children, n_node) = num_children centres exactly as the two primitives run, in this
+ *                   order, on a brute-force handle that holds the node's rows alone (member t = row t):
+ *                   scann_hip_kmeans_init_pp(k, seed + d, cfg->simd_threshold), then scann_hip_kmeans_lloyd
+ *                   (kmeans_iterations, kmeans_convergence, cfg->simd_threshold) -- so an empty cluster c takes the
+ *                   node's member c % n_node, and every node of a level draws from the same stream.  Its children are
+ *                   the NON-EMPTY clusters of the final assignment, in cluster order, each with its members ascending;
+ *                   a node with exactly one non-empty cluster is a leaf.  Leaves are numbered depth first, children in
+ *                   order (collect_leaves).  The centre of a leaf is compute_center (:270-284): per dimension the f64
+ *                   sum of its members in ascending order, divided by the count, cast to f32 -- the arithmetic of the
+ *                   Lloyd loop's centre update applied to the FINAL assignment, not the loop's last centres.  The CSR
+ *                   lists hold ascending datapoint index inside each leaf.
+ *   2-5             steps 2-5 of scann_hip_txh_build on those centres and that leaf assignment: training rows in
+ *                   datapoint order against scann_hip_bf_assign_nearest of the flattened centres, codebook, codes in
+ *                   CSR order, finish.
+ * All nodes of one level train in lockstep: the number of kernel launches per seeding round and per Lloyd iteration does
+ * not depend on the number of nodes.  A node that converged is frozen and skipped.  Rows are gathered through the
+ * level's permutation, never copied into level order.  The host keeps the level's node table: it reads the per-node
+ * stop records once per iteration and the cluster offsets once per level; no row, distance or assignment visits it.
+ * Extra device memory during the tree stage, released before step 2: n * dim * 4 bytes (member-ordered rows of the
+ * centre update, as scann_hip_kmeans_lloyd holds) and 9 arrays of n * 4 bytes, plus num_children * dim * 4 bytes per
+ * training node of a level.
+ * REFUSED before any training launch (`rows` keeps searching): everything scann_hip_txh_build refuses, with the same
+ *   status (the leaf ceiling aside); num_children == 0 -> InvalidArgument; max_depth > 4 -> Unimplemented.
+ *   max_depth == 0, or n <= num_children or n <= min_leaf_size at the root: a single leaf holding every row.
+ *   More than 16384 leaves (the search's num_partitions ceiling) is known only during the tree stage: Unimplemented
+ *   with the node count in the message, as soon as a level has more than 16384 nodes; no handle is returned.
+ * out_report (may be NULL): as scann_hip_txh_build's; the partition_* slots hold the ROOT's k-means (zeros when the root
+ *   is a leaf), stage_ms[0] and [1] the seeding and the Lloyd time of the whole tree stage.
+ * out_tree_report (may be NULL): per level d = 0..4, level_nodes = the nodes that ran k-means at depth d,
+ *   level_iterations = the sum of their iteration counts, level_converged = how many converged, level_leaves = the leaves
+ *   of depth d; stage_ms[2 d] and [2 d + 1] = host-clock milliseconds of level d's seeding and of its Lloyd loop with
+ *   the children's layout. */
+typedef struct scann_hip_tree_config {   /* KMeansTreeConfig, kmeans_tree.rs:20-55 */
+    uint32_t num_children;        /* 100 */
+    uint32_t max_depth;           /* 1 = flat */
+    uint32_t min_leaf_size;       /* 1 */
+    uint32_t kmeans_iterations;   /* 100 */
+    double   kmeans_convergence;  /* 1e-5 */
+    uint64_t seed;                /* 42; a node at depth d trains with seed + d (kmeans_tree.rs:235) */
+} scann_hip_tree_config;
+
+typedef struct scann_hip_tree_report {
+    uint32_t num_leaves, depth_reached;
+    uint32_t level_nodes[5], level_iterations[5], level_converged[5], level_leaves[5];
+    float stage_ms[10];
+} scann_hip_tree_report;
+
+void scann_hip_tree_config_default(scann_hip_tree_config *tree);
+int scann_hip_txh_build_hierarchical(scann_hip_index *rows, const scann_hip_tree_config *tree,
+                                     const scann_hip_build_config *cfg, scann_hip_index **out_index,
+                                     scann_hip_build_report *out_report, scann_hip_tree_report *out_tree_report);
+
 /* ---- PCA training on the device (PcaProjection::train, projection/pca.rs:71-129, utils/linear_algebra.rs:89-120) ----
  * Trains a SCANN_HIP_PROJ_PCA projection from the resident rows of an f32 brute-force handle (in_dim = its dim); no row
  * crosses to the host.  The object is indistinguishable from one scann_hip_projection_create makes from the same

@@ -16,8 +16,8 @@ LIB = os.path.join(HERE, "libscann_hip.so")
 TXH_SOURCES = ["txh.hip", "txh_partition.hip", "txh_prefilter.hip", "txh_rows.hip", "txh_blocks.hip"]
 # the C ABI over the handle of handle.h: lifetime and building blocks, creation, searches, crowding / MMR stages
 API_SOURCES = ["api.hip", "api_create.hip", "api_search.hip", "api_stages.hip"]
-SOURCES = API_SOURCES + TXH_SOURCES + ["bf.hip", "index_file.hip", "comm.hip", "crowd.hip", "mmr.hip", "mutable.hip", "fold.hip", "allow.hip", "tokens.hip", "ranges.hip", "scalarq.hip", "project.hip", "build.hip", "pca.hip"]
-HEADERS = ["common.h", "knobs.h", "handle.h", "txh_arena.h", "txh.h", "txh_dev.h", "txh_stages.h", "allow.h", "tokens.h", "ranges.h", "bf.h", "comm.h", "crowd.h", "mmr.h", "mutable.h", "fold.h", "index_arrays.h", "pair.h", "launch.h", "quant.h", "scalarq.h", "project.h", "build.h", "pca.h", os.path.join("..", "..", "include", "scann_hip.h")]
+SOURCES = API_SOURCES + TXH_SOURCES + ["bf.hip", "index_file.hip", "comm.hip", "crowd.hip", "mmr.hip", "mutable.hip", "fold.hip", "allow.hip", "tokens.hip", "ranges.hip", "scalarq.hip", "project.hip", "build.hip", "pca.hip", "ktree.hip"]
+HEADERS = ["common.h", "knobs.h", "handle.h", "txh_arena.h", "txh.h", "txh_dev.h", "txh_stages.h", "allow.h", "tokens.h", "ranges.h", "bf.h", "comm.h", "crowd.h", "mmr.h", "mutable.h", "fold.h", "index_arrays.h", "pair.h", "launch.h", "quant.h", "scalarq.h", "project.h", "build.h", "pca.h", "ktree.h", os.path.join("..", "..", "include", "scann_hip.h")]
 # -ffp-contract=off: the reference never contracts a*b+c (Rust); FMA is used only via
 # explicit fmaf()/MFMA where the reference uses _mm256_fmadd_ps.
 CFLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "-fPIC", "-Wall",
@@ -124,7 +124,8 @@ HOST_PROGRAMS = ["host_test", "ann_benchmark", "bf_filter_test",   # C++ mirror 
                  "scalar_quantizer_test",                        # the scalar quantizer and its brute-force searcher,
                  "projection_test",                              # the CPU projection loop (uses no GPU),
                  "device_build_test",                            # build_on_device of the hasher and the tree searcher,
-                 "pca_build_test"]                               # PCA training and projected builds on the device
+                 "pca_build_test",                               # PCA training and projected builds on the device,
+                 "hier_build_test"]                              # the hierarchical k-means tree build through the mirror
 
 
 def build_host(verbose=False):

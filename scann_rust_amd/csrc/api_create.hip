@@ -11,6 +11,7 @@
 #include "build.h"
 #include "handle.h"
 #include "index_arrays.h"
+#include "ktree.h"
 #include "launch.h"
 #include "mutable.h"
 #include "pca.h"
@@ -868,6 +869,40 @@ int scann_hip_txh_build(scann_hip_index *rows, const scann_hip_build_config *cfg
     BuildParts parts;
     SCANN_TRY(build_txh_device(rows->bf, *cfg, rows->stream, &parts, out_report));
     return index_build_txh(rows, *cfg, parts, out_index, out_report);
+}
+
+void scann_hip_tree_config_default(scann_hip_tree_config *c) {
+    if (!c) return;
+    std::memset(c, 0, sizeof(*c));
+    c->num_children = 100;            // KMeansTreeConfig::default (kmeans_tree.rs:42-55)
+    c->max_depth = 1;
+    c->min_leaf_size = 1;
+    c->kmeans_iterations = 100;
+    c->kmeans_convergence = 1e-5;
+    c->seed = 42;
+}
+
+int scann_hip_txh_build_hierarchical(scann_hip_index *rows, const scann_hip_tree_config *tree,
+                                     const scann_hip_build_config *cfg, scann_hip_index **out_index,
+                                     scann_hip_build_report *out_report, scann_hip_tree_report *out_tree_report) {
+    if (!rows || !tree || !cfg || !out_index) return fail(SCANN_HIP_INVALID_ARGUMENT, "null rows/tree/config/out_index");
+    *out_index = nullptr;
+    if (out_report) std::memset(out_report, 0, sizeof(*out_report));
+    if (out_tree_report) std::memset(out_tree_report, 0, sizeof(*out_tree_report));
+    if (rows->kind != KIND_BF) return fail(SCANN_HIP_INVALID_ARGUMENT, "not a brute-force index");
+    std::lock_guard<std::mutex> lock(rows->mu);
+    SCANN_TRY(set_device(rows->ctx));
+    scann_hip_build_config c = *cfg;   // the tree configuration replaces the flat partitioner's four fields
+    c.num_partitions = 1;              // "a tree"; the number of leaves is known after the tree stage
+    c.kmeans_iterations = tree->kmeans_iterations;
+    c.kmeans_convergence = tree->kmeans_convergence;
+    c.kmeans_seed = tree->seed;
+    SCANN_TRY(build_check(rows->bf, c));   // every refusal of scann_hip_txh_build, before the first training launch
+    SCANN_TRY(ktree_check(*tree));
+    BuildParts parts;
+    SCANN_TRY(build_txh_hierarchical_device(rows->bf, *tree, c, rows->stream, &parts, out_report, out_tree_report));
+    c.num_partitions = parts.L;
+    return index_build_txh(rows, c, parts, out_index, out_report);
 }
 
 int scann_hip_txh_build_projected(scann_hip_index *rows, const scann_hip_projection *projection,

@@ -28,6 +28,7 @@
 #include <cmath>
 #include <cstring>
 
+#include "ktree.h"
 #include "launch.h"
 #include "txh.h"
 
@@ -541,18 +542,73 @@ int build_check(const BfIndexDev &src, const scann_hip_build_config &cfg) {
     return SCANN_HIP_OK;
 }
 
+// Steps 2-5 on the partitioner's outputs, whichever partitioner made them: out->centers / leaf_off / leaf_ids / off / L
+// and d_leaf (the leaf of every datapoint) for a tree, nothing for a flat hasher.  ms[2] also holds what the caller
+// spent since `t` (the flat partitioner's CSR); stages 2..5 of stage_ms.
+static int build_after_partition(const BfIndexDev &src, const scann_hip_build_config &cfg, bool tree, hipStream_t st,
+                                 BuildParts *out, const DevBuf &d_leaf, KmScratch &sc, float *ms,
+                                 std::chrono::steady_clock::time_point t, scann_hip_build_report *rep) {
+    const uint64_t n = src.n;
+    const uint32_t dim = src.dim, stride = src.stride, S = cfg.num_subspaces, K = cfg.num_codes, dsub = dim / S;
+    const bool residual = tree && cfg.use_residuals;
+    const uint32_t L = out->L;
+    const uint32_t bits = K <= 16 ? 4u : 8u, nw = bits == 4 ? S / 8 : S / 4;
+    DevBuf d_token, d_train, d_code8;
+    if (tree) {
+        // ---- 2 training rows: residuals against partition(x, 1), datapoint order ----
+        if (residual) {
+            SCANN_TRY(d_token.ensure(n * 4));
+            SCANN_TRY(d_train.ensure(n * stride * 4));
+            SCANN_TRY(bf_assign_nearest_device(src, out->centers.as<float>(), L, d_token.as<uint32_t>(), nullptr, st));
+            const int vec = ((stride & 3u) == 0 && (reinterpret_cast<uintptr_t>(src.rows) & 15u) == 0) ? 1 : 0;
+            const uint64_t threads = vec ? n * (stride >> 2) : n * stride;
+            SCANN_TRY(launch(build_residual_kernel, dim3((uint32_t)ceil_div_u64(threads, 256)), dim3(256), 0, st, src.rows, n,
+                             dim, stride, (const float *)out->centers.as<float>(), (const uint32_t *)d_token.as<uint32_t>(),
+                             d_train.as<float>(), vec));
+        }
+        SCANN_HIP_CHECK(hipStreamSynchronize(st));
+        ms[2] = ms_since(t);
+    }
+
+    // ---- 3 codebook ----
+    BfIndexDev tv = src;
+    if (residual) tv.rows = d_train.as<float>();
+    const uint32_t kc = (uint32_t)std::min<uint64_t>(K, n);
+    SCANN_TRY(out->codebook.ensure((size_t)S * K * dsub * 4));
+    const uint32_t G = cb_group_size(S, kc, dsub);
+    const bool batched = cfg.batched_codebook && dsub < cfg.simd_threshold && G >= 1 && n * S <= 0x7FFFFFFFull;
+    t = std::chrono::steady_clock::now();
+    if (batched)
+        SCANN_TRY(train_codebook_batched(tv, cfg, dsub, kc, G, out->codebook.as<float>(), st, rep, &ms[3], &ms[4]));
+    else
+        SCANN_TRY(train_codebook_per_subspace(tv, cfg, dsub, kc, out->codebook.as<float>(), sc, st, rep, &ms[3], &ms[4]));
+
+    // ---- 4 codes: Codebook::encode of x - centres[leaf], through the CSR permutation into packed words ----
+    t = std::chrono::steady_clock::now();
+    SCANN_TRY(d_code8.ensure(n * S));
+    SCANN_TRY(out->codes.ensure(n * nw * 4));
+    SCANN_TRY(launch_encode(out->codebook.as<float>(), S, K, dsub, src.rows, n, stride,
+                            residual ? out->centers.as<float>() : nullptr, residual ? d_leaf.as<uint32_t>() : nullptr,
+                            d_code8.as<uint8_t>(), st));
+    SCANN_TRY(launch(build_pack_codes_kernel, dim3((uint32_t)ceil_div_u64(n * nw, 256)), dim3(256), 0, st,
+                     (const uint8_t *)d_code8.as<uint8_t>(), (const uint32_t *)(tree ? out->leaf_ids.as<uint32_t>() : nullptr), n,
+                     S, nw, bits, out->codes.as<uint32_t>()));
+    SCANN_HIP_CHECK(hipStreamSynchronize(st));
+    ms[5] = ms_since(t);
+    if (rep) std::memcpy(rep->stage_ms, ms, 6 * sizeof(float));
+    return SCANN_HIP_OK;
+}
+
 int build_txh_device(const BfIndexDev &src, const scann_hip_build_config &cfg, hipStream_t st, BuildParts *out,
                      scann_hip_build_report *rep) {
     SCANN_TRY(build_check(src, cfg));
     const uint64_t n = src.n;
-    const uint32_t dim = src.dim, stride = src.stride, S = cfg.num_subspaces, K = cfg.num_codes, dsub = dim / S;
+    const uint32_t dim = src.dim;
     const bool tree = cfg.num_partitions != 0;
-    const bool residual = tree && cfg.use_residuals;
     const uint32_t L = tree ? (uint32_t)std::min<uint64_t>(cfg.num_partitions, n) : 1u;   // kmeans.rs:171-175
-    const uint32_t bits = K <= 16 ? 4u : 8u, nw = bits == 4 ? S / 8 : S / 4;
     float ms[6] = {};
     KmScratch sc;
-    DevBuf d_leaf, d_token, d_train, d_code8;
+    DevBuf d_leaf;
     auto t = std::chrono::steady_clock::now();
     out->L = L;
     out->off.assign((size_t)L + 1, 0u);
@@ -583,52 +639,32 @@ int build_txh_device(const BfIndexDev &src, const scann_hip_build_config &cfg, h
                          out->leaf_ids.as<uint32_t>()));
         SCANN_HIP_CHECK(hipMemcpyAsync(out->leaf_off.p, sc.doff.p, ((size_t)L + 1) * 4, hipMemcpyDeviceToDevice, st));
         SCANN_HIP_CHECK(hipMemcpyAsync(out->off.data(), sc.doff.p, ((size_t)L + 1) * 4, hipMemcpyDeviceToHost, st));
-        // ---- 2 training rows: residuals against partition(x, 1), datapoint order ----
-        if (residual) {
-            SCANN_TRY(d_token.ensure(n * 4));
-            SCANN_TRY(d_train.ensure(n * stride * 4));
-            SCANN_TRY(bf_assign_nearest_device(src, out->centers.as<float>(), L, d_token.as<uint32_t>(), nullptr, st));
-            const int vec = ((stride & 3u) == 0 && (reinterpret_cast<uintptr_t>(src.rows) & 15u) == 0) ? 1 : 0;
-            const uint64_t threads = vec ? n * (stride >> 2) : n * stride;
-            SCANN_TRY(launch(build_residual_kernel, dim3((uint32_t)ceil_div_u64(threads, 256)), dim3(256), 0, st, src.rows, n,
-                             dim, stride, (const float *)out->centers.as<float>(), (const uint32_t *)d_token.as<uint32_t>(),
-                             d_train.as<float>(), vec));
-        }
-        SCANN_HIP_CHECK(hipStreamSynchronize(st));
-        ms[2] = ms_since(t);
     } else {
         out->off[1] = (uint32_t)n;
         SCANN_HIP_CHECK(hipMemcpyAsync(out->leaf_off.p, out->off.data(), 8, hipMemcpyHostToDevice, st));
         SCANN_HIP_CHECK(hipStreamSynchronize(st));
     }
+    return build_after_partition(src, cfg, tree, st, out, d_leaf, sc, ms, t, rep);
+}
 
-    // ---- 3 codebook ----
-    BfIndexDev tv = src;
-    if (residual) tv.rows = d_train.as<float>();
-    const uint32_t kc = (uint32_t)std::min<uint64_t>(K, n);
-    SCANN_TRY(out->codebook.ensure((size_t)S * K * dsub * 4));
-    const uint32_t G = cb_group_size(S, kc, dsub);
-    const bool batched = cfg.batched_codebook && dsub < cfg.simd_threshold && G >= 1 && n * S <= 0x7FFFFFFFull;
-    t = std::chrono::steady_clock::now();
-    if (batched)
-        SCANN_TRY(train_codebook_batched(tv, cfg, dsub, kc, G, out->codebook.as<float>(), st, rep, &ms[3], &ms[4]));
-    else
-        SCANN_TRY(train_codebook_per_subspace(tv, cfg, dsub, kc, out->codebook.as<float>(), sc, st, rep, &ms[3], &ms[4]));
-
-    // ---- 4 codes: Codebook::encode of x - centres[leaf], through the CSR permutation into packed words ----
-    t = std::chrono::steady_clock::now();
-    SCANN_TRY(d_code8.ensure(n * S));
-    SCANN_TRY(out->codes.ensure(n * nw * 4));
-    SCANN_TRY(launch_encode(out->codebook.as<float>(), S, K, dsub, src.rows, n, stride,
-                            residual ? out->centers.as<float>() : nullptr, residual ? d_leaf.as<uint32_t>() : nullptr,
-                            d_code8.as<uint8_t>(), st));
-    SCANN_TRY(launch(build_pack_codes_kernel, dim3((uint32_t)ceil_div_u64(n * nw, 256)), dim3(256), 0, st,
-                     (const uint8_t *)d_code8.as<uint8_t>(), (const uint32_t *)(tree ? out->leaf_ids.as<uint32_t>() : nullptr), n,
-                     S, nw, bits, out->codes.as<uint32_t>()));
-    SCANN_HIP_CHECK(hipStreamSynchronize(st));
-    ms[5] = ms_since(t);
-    if (rep) std::memcpy(rep->stage_ms, ms, sizeof(ms));
-    return SCANN_HIP_OK;
+int build_txh_hierarchical_device(const BfIndexDev &src, const scann_hip_tree_config &tree,
+                                  const scann_hip_build_config &cfg, hipStream_t st, BuildParts *out,
+                                  scann_hip_build_report *rep, scann_hip_tree_report *trep) {
+    SCANN_TRY(build_check(src, cfg));
+    float ms[6] = {};
+    KmScratch sc;
+    DevBuf d_leaf;
+    scann_hip_build_report tree_rep;
+    std::memset(&tree_rep, 0, sizeof(tree_rep));
+    SCANN_TRY(ktree_build_device(src, tree, cfg.simd_threshold, st, out, &d_leaf, &tree_rep, trep));
+    if (rep) {
+        rep->partition_iterations = tree_rep.partition_iterations;
+        rep->partition_converged = tree_rep.partition_converged;
+        rep->partition_inertia = tree_rep.partition_inertia;
+    }
+    ms[0] = tree_rep.stage_ms[0];
+    ms[1] = tree_rep.stage_ms[1];
+    return build_after_partition(src, cfg, true, st, out, d_leaf, sc, ms, std::chrono::steady_clock::now(), rep);
 }
 
 }  // namespace scann

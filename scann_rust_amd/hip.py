@@ -80,6 +80,7 @@ EXPORTS = [
     "scann_hip_project_device", "scann_hip_txh_create_projected", "scann_hip_index_projection_info",
     "scann_hip_build_config_default", "scann_hip_txh_build",
     "scann_hip_pca_train", "scann_hip_projection_arrays", "scann_hip_pca_last_stage_ms", "scann_hip_txh_build_projected",
+    "scann_hip_tree_config_default", "scann_hip_txh_build_hierarchical",
 ]
 
 
@@ -161,6 +162,24 @@ class BuildReport(C.Structure):
         ("partition_iterations", C.c_uint32), ("partition_converged", C.c_int32), ("partition_inertia", C.c_double),
         ("subspace_iterations", C.c_uint32 * 64), ("subspace_converged", C.c_int32 * 64),
         ("stage_ms", C.c_float * 7),
+    ]
+
+
+class TreeConfig(C.Structure):
+    """scann_hip_tree_config"""
+    _fields_ = [
+        ("num_children", C.c_uint32), ("max_depth", C.c_uint32), ("min_leaf_size", C.c_uint32),
+        ("kmeans_iterations", C.c_uint32), ("kmeans_convergence", C.c_double), ("seed", C.c_uint64),
+    ]
+
+
+class TreeReport(C.Structure):
+    """scann_hip_tree_report"""
+    _fields_ = [
+        ("num_leaves", C.c_uint32), ("depth_reached", C.c_uint32),
+        ("level_nodes", C.c_uint32 * 5), ("level_iterations", C.c_uint32 * 5), ("level_converged", C.c_uint32 * 5),
+        ("level_leaves", C.c_uint32 * 5),
+        ("stage_ms", C.c_float * 10),
     ]
 
 
@@ -256,6 +275,10 @@ def load():
     L.scann_hip_build_config_default.argtypes = [C.POINTER(BuildConfig)]
     L.scann_hip_build_config_default.restype = None
     L.scann_hip_txh_build.argtypes = [vp, C.POINTER(BuildConfig), C.POINTER(vp), C.POINTER(BuildReport)]
+    L.scann_hip_tree_config_default.argtypes = [C.POINTER(TreeConfig)]
+    L.scann_hip_tree_config_default.restype = None
+    L.scann_hip_txh_build_hierarchical.argtypes = [vp, C.POINTER(TreeConfig), C.POINTER(BuildConfig), C.POINTER(vp),
+                                                   C.POINTER(BuildReport), C.POINTER(TreeReport)]
     L.scann_hip_abi_layout.restype = C.c_uint32
     L.scann_hip_abi_layout.argtypes = [u32p, C.c_uint32]
     L.scann_hip_lut16_quantize.argtypes = [vp, f32p, C.c_uint32, u8p, f32p, f32p]
@@ -1762,6 +1785,40 @@ def _build_report(rep, S):
                 subspace_iterations=[int(v) for v in rep.subspace_iterations[:S]],
                 subspace_converged=[bool(v) for v in rep.subspace_converged[:S]],
                 stage_ms=dict(zip(BUILD_STAGES, (float(v) for v in rep.stage_ms))))
+
+
+def tree_config(**kw):
+    """scann_hip_tree_config_default with the keyword arguments set on top (field names of TreeConfig)."""
+    c = TreeConfig()
+    load().scann_hip_tree_config_default(C.byref(c))
+    names = {f for f, _ in TreeConfig._fields_}
+    for key, value in kw.items():
+        if key not in names:
+            raise TypeError("scann_hip_tree_config has no field %r" % key)
+        setattr(c, key, value)
+    return c
+
+
+def txh_build_hierarchical(bf_index, tree=None, **cfg):
+    """scann_hip_txh_build_hierarchical: txh_build with the partitioner of TreePartitioner::build_hierarchical -- a k-means
+    tree trained level by level on the device and flattened to its leaves.  `tree`: a TreeConfig, a dict of its fields, or
+    None for the defaults; of **cfg, num_partitions and the kmeans_* fields are ignored.  Returns (Index, report,
+    tree_report): report as txh_build's (the partition_* slots hold the root's k-means), tree_report a dict with
+    num_leaves, depth_reached, the per-level lists level_nodes / level_iterations / level_converged / level_leaves
+    (depths 0..4) and stage_ms ([(seeding, lloyd)] per level, milliseconds)."""
+    t = tree if isinstance(tree, TreeConfig) else tree_config(**(tree or {}))
+    c = build_config(**cfg)
+    rep, trep = BuildReport(), TreeReport()
+    h = vp()
+    check(load().scann_hip_txh_build_hierarchical(bf_index.h, C.byref(t), C.byref(c), C.byref(h), C.byref(rep),
+                                                  C.byref(trep)))
+    tree_report = dict(num_leaves=int(trep.num_leaves), depth_reached=int(trep.depth_reached),
+                       level_nodes=[int(v) for v in trep.level_nodes],
+                       level_iterations=[int(v) for v in trep.level_iterations],
+                       level_converged=[int(v) for v in trep.level_converged],
+                       level_leaves=[int(v) for v in trep.level_leaves],
+                       stage_ms=[(float(trep.stage_ms[2 * d]), float(trep.stage_ms[2 * d + 1])) for d in range(5)])
+    return Index(h), _build_report(rep, c.num_subspaces), tree_report
 
 
 def txh_build_projected(bf_index, projection, **cfg):

@@ -1646,10 +1646,19 @@ public:
                                    scann_hip_build_report *report = nullptr) {
         build_device_impl(source, &projection, report);
     }
+    // build_on_device with the partitioner of TreePartitioner::build_hierarchical (scann_hip_txh_build_hierarchical): a
+    // k-means tree trained level by level on the device and flattened to its leaves, which become the partitions.
+    // `tree` replaces config().num_partitions and kmeans_iterations; everything else is read from config() as above.
+    void build_hierarchical_on_device(const BruteForceSearcher &source, const scann_hip_tree_config &tree,
+                                      scann_hip_build_report *report = nullptr,
+                                      scann_hip_tree_report *tree_report = nullptr) {
+        build_device_impl(source, nullptr, report, &tree, tree_report);
+    }
 
 private:
     void build_device_impl(const BruteForceSearcher &source, const DeviceProjection *projection,
-                           scann_hip_build_report *report) {
+                           scann_hip_build_report *report, const scann_hip_tree_config *tree = nullptr,
+                           scann_hip_tree_report *tree_report = nullptr) {
         scann_hip_build_config c;
         scann_hip_build_config_default(&c);
         c.num_partitions = (uint32_t)config_.num_partitions;
@@ -1662,15 +1671,18 @@ private:
         c.use_residuals = config_.use_residuals ? 1 : 0;
         c.partitions_to_search = (uint32_t)config_.partitions_to_search;
         c.pre_reorder_multiplier = config_.pre_reorder_multiplier;
-        if (c.num_partitions == 0) throw ScannError::invalid_argument("num_partitions is 0");
+        if (!tree && c.num_partitions == 0) throw ScannError::invalid_argument("num_partitions is 0");
         scann_hip_index *h = nullptr;
-        if (projection) check(scann_hip_txh_build_projected(source.handle(), projection->handle(), &c, &h, report));
+        scann_hip_tree_report trep;
+        if (tree) check(scann_hip_txh_build_hierarchical(source.handle(), tree, &c, &h, report, &trep));
+        else if (projection) check(scann_hip_txh_build_projected(source.handle(), projection->handle(), &c, &h, report));
         else check(scann_hip_txh_build(source.handle(), &c, &h, report));
+        if (tree && tree_report) *tree_report = trep;
         if (ix_.h) scann_hip_index_destroy(ix_.h);
         ix_.h = h;
         n_ = source.dataset_size();
         dim_ = source.dimensionality();
-        L_ = std::min<size_t>(config_.num_partitions, n_);
+        L_ = tree ? (size_t)trep.num_leaves : std::min<size_t>(config_.num_partitions, n_);
         dataset_.reset();
         centers_.clear(); codebook_.clear(); leaf_off_.clear(); leaf_ids_.clear(); codes_.clear();
     }
