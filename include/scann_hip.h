@@ -265,8 +265,9 @@ typedef struct {
     uint64_t n_local;
     const float *codebook;
     uint32_t num_subspaces;      /* S */
-    uint32_t num_codes;          /* K <= 16: LUT16 (4-bit codes, S in {8,16,24,32,48,64});
-                                  * 16 < K <= 256: byte codes (S in {4,8,16}) */
+    uint32_t num_codes;          /* K <= 16: LUT16 (4-bit codes, S in {8,16,24,32,48,64}, or a multiple of 32 from 96
+                                  * to 512: the slab-walking scan, no MFMA prefilter or resident form);
+                                  * 16 < K <= 256: byte codes (S in {4,8,16}).  Other shapes: Unimplemented */
     uint32_t dims_per_subspace;  /* dsub; S * dsub must equal dim (codebook.rs:154-159) */
     const uint8_t *codes;
     int32_t codes_packed4;
@@ -1358,7 +1359,7 @@ typedef struct scann_hip_build_config {
 
 typedef struct scann_hip_build_report {
     uint32_t partition_iterations; int32_t partition_converged; double partition_inertia;
-    uint32_t subspace_iterations[64]; int32_t subspace_converged[64];
+    uint32_t subspace_iterations[64]; int32_t subspace_converged[64];   /* the first 64 subspaces when S > 64 */
     float stage_ms[7];
 } scann_hip_build_report;
 

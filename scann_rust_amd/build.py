@@ -13,7 +13,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "_obj")
 LIB = os.path.join(HERE, "libscann_hip.so")
 # the units of the tree / flat-hasher search
-TXH_SOURCES = ["txh.hip", "txh_partition.hip", "txh_prefilter.hip", "txh_rows.hip", "txh_blocks.hip"]
+TXH_SOURCES = ["txh.hip", "txh_partition.hip", "txh_prefilter.hip", "txh_rows.hip", "txh_blocks.hip", "txh_slab.hip"]
 # the C ABI over the handle of handle.h: lifetime and building blocks, creation, searches, crowding / MMR stages
 API_SOURCES = ["api.hip", "api_create.hip", "api_search.hip", "api_stages.hip"]
 SOURCES = API_SOURCES + TXH_SOURCES + ["bf.hip", "index_file.hip", "comm.hip", "crowd.hip", "mmr.hip", "mutable.hip", "fold.hip", "allow.hip", "tokens.hip", "ranges.hip", "scalarq.hip", "project.hip", "build.hip", "pca.hip", "ktree.hip"]
@@ -23,6 +23,9 @@ HEADERS = ["common.h", "knobs.h", "handle.h", "txh_arena.h", "txh.h", "txh_dev.h
 CFLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "-fPIC", "-Wall",
           "-Wno-unused-function"]
 LDFLAGS = ["-shared", "-fPIC", "--offload-arch=gfx950", "-ldl"]
+# flags of single units.  txh_slab.hip adds float4 table entries lane by lane: packed f32 VALU forms are kept out of it,
+# so that every add is the scalar v_add_f32 the older scans were measured and verified with.
+UNIT_FLAGS = {"txh_slab.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def src_sha256():
@@ -36,7 +39,7 @@ def src_sha256():
         h.update(os.path.basename(p).encode() + b"\0")
         with open(p, "rb") as fh:
             h.update(fh.read())
-    h.update(" ".join(CFLAGS + LDFLAGS).encode())
+    h.update(" ".join(CFLAGS + LDFLAGS + [f for k in sorted(UNIT_FLAGS) for f in [k] + UNIT_FLAGS[k]]).encode())
     return h.hexdigest()
 
 
@@ -85,7 +88,7 @@ def build_variant(name, extra_flags, only=tuple(TXH_SOURCES)):
     for s in _sources():
         if s in only:
             o = os.path.join(OBJ, os.path.splitext(s)[0] + "_" + name + ".o")
-            subprocess.check_call([hipcc] + CFLAGS + list(extra_flags) + ["-c", "-o", o, os.path.join(CSRC, s)], cwd=CSRC)
+            subprocess.check_call([hipcc] + CFLAGS + UNIT_FLAGS.get(s, []) + list(extra_flags) + ["-c", "-o", o, os.path.join(CSRC, s)], cwd=CSRC)
             objs.append(o)
         else:
             objs.append(_obj(s))
@@ -103,7 +106,7 @@ def build(force=False, verbose=False, extra_flags=()):
         return LIB
 
     def compile_one(s):
-        cmd = [hipcc] + CFLAGS + list(extra_flags) + ["-c", "-o", _obj(s), os.path.join(CSRC, s)]
+        cmd = [hipcc] + CFLAGS + UNIT_FLAGS.get(s, []) + list(extra_flags) + ["-c", "-o", _obj(s), os.path.join(CSRC, s)]
         if verbose:
             print(" ".join(cmd), flush=True)
         subprocess.check_call(cmd, cwd=CSRC)

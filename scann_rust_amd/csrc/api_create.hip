@@ -272,8 +272,10 @@ int scann::txh_create_checked(scann_hip_ctx *ctx, const scann_hip_txh_desc *d, s
         return fail(SCANN_HIP_UNIMPLEMENTED, "num_codes must be 1..256");
     // K <= 16: 4-bit packed codes + 16-slot tables (LUT16); else bytes + 256-slot tables
     const uint32_t bits = K <= 16 ? 4u : 8u;
-    if (!exact && bits == 4 && (S % 8 != 0 || S > 64 || S == 40 || S == 56))
-        return fail(SCANN_HIP_UNIMPLEMENTED, "num_subspaces must be 8,16,24,32,48 or 64 for num_codes <= 16");
+    // (S > 64: the slab-walking scan, txh_slab.hip -- whole slabs of kSlabSub subspaces, up to kSlabMaxS)
+    if (!exact && bits == 4 && (S % 8 != 0 || S == 40 || S == 56 || (S > 64 && (S % kSlabSub != 0 || S > kSlabMaxS))))
+        return fail(SCANN_HIP_UNIMPLEMENTED,
+                    "num_subspaces must be 8,16,24,32,48,64 or a multiple of 32 from 96 to 512 for num_codes <= 16");
     if (bits == 8 && S != 4 && S != 8 && S != 16)
         return fail(SCANN_HIP_UNIMPLEMENTED, "num_subspaces must be 4, 8 or 16 for 16 < num_codes <= 256");
     if (bits == 8 && d->codes_packed4)
@@ -449,9 +451,10 @@ static int txh_finish(scann_hip_index *ix, const scann_hip_txh_desc *d, const st
     t.codes_sp = nullptr;
     const Knobs kn = read_knobs();
     // operand planes of the sparse-MFMA prefilter (txh_prefilter.hip K6e): a second copy of the 4-bit codes, S/2 .. 2 S bytes
-    // per point.  SCANN_HIP_SMFMAC=0: not built, the dense integer-MFMA prefilter is used instead.
+    // per point.  SCANN_HIP_SMFMAC=0: not built, the dense integer-MFMA prefilter is used instead.  Not built above
+    // S = 64 either: those indexes are scanned by the slab-walking gather scan alone.
     {
-        if (!exact && bits == 4 && kn.smfmac) {
+        if (!exact && bits == 4 && S <= 64 && kn.smfmac) {
             if ((s = ix->d_codes_sp.ensure((size_t)n * sp_words(S) * 4)) != SCANN_HIP_OK) return s;
             if ((s = launch_codes_sp_build(ix->d_codes.as<uint32_t>(), n, S, ix->d_codes_sp.as<uint32_t>(), ix->stream)) != SCANN_HIP_OK)
                 return s;

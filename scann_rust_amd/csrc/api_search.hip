@@ -194,6 +194,14 @@ int scann::plan_txh_search(const scann_hip_index *ix, uint32_t k, const scann_hi
         mfma = TxhScan::Smfmac;
     if (mfma == TxhScan::Mfma32 && t.codes_sp && kn.smfmac) mfma = TxhScan::Smfmac;   // (forced 32-pair form, fewer pairs per leaf)
     p.scan = t.exact_scan ? TxhScan::Exact : mfma != TxhScan::Gather ? mfma : resident ? TxhScan::Resident : TxhScan::Gather;
+    // 4-bit codes with more than 64 subspaces: the slab-walking gather scan and its sample pass (txh_slab.hip), whatever
+    // a knob that names an MFMA, sparse or resident scan says -- none of those is compiled above S = 64.  Its work
+    // items are 512 points x kSlabQuads quads, for the sample pass too (the tables of a quad are S x 256 bytes in
+    // lutq, up to 32 KB per pair at S = 512; an item holds two slabs of 8 KB of each quad in LDS).
+    if (txh_slab_layout(t)) {
+        p.scan = TxhScan::Slab;
+        p.qpt = p.sqpt = kSlabQuads;
+    }
     if (txh_scan_is_mfma(p.scan)) {
         // survivors of the integer bound: the f32 filter's (<= cap) plus the quantisation margin
         // (the margin's share is independent of m -- the points within 17 table steps above the bound -- and in
@@ -258,6 +266,7 @@ static const char *txh_kernel_name(const TxhIndexDev &t, const TxhPlan &p, bool 
         case TxhScan::Smfmac: return t.S > 32 ? "adc_smfmac_wide_kernel" : "adc_smfmac_kernel";
         case TxhScan::Mfma32: return "adc_mfma_kernel";
         case TxhScan::Resident: return "adc_scan_res_kernel";
+        case TxhScan::Slab: return "adc_slab_scan_kernel";
         default: return "adc_scan_kernel";
     }
 }

@@ -386,7 +386,7 @@ int train_codebook_batched(const BfIndexDev &tv, const scann_hip_build_config &c
     SCANN_TRY(d_tot.ensure((size_t)S * sizeof(CbTotal)));
     SCANN_TRY(d_state.ensure((size_t)S * sizeof(CbState)));
     SCANN_TRY(d_picks.ensure((size_t)S * k * 4));
-    SCANN_TRY(launch(cb_init_state_kernel, dim3(1), dim3(64), 0, st, d_state.as<CbState>(), d_tot.as<CbTotal>(), S));
+    SCANN_TRY(launch(cb_init_state_kernel, dim3(ceil_div_u32(S, 64)), dim3(64), 0, st, d_state.as<CbState>(), d_tot.as<CbTotal>(), S));
     const uint32_t *state_words = d_state.as<uint32_t>();
 
     // ---- seeding: the S random streams of kmeans_plusplus_init, round by round ----
@@ -442,15 +442,15 @@ int train_codebook_batched(const BfIndexDev &tv, const scann_hip_build_config &c
         for (uint32_t it = 0; it < cfg.training_iterations; ++it) {
             SCANN_TRY(launch_assign_all(dsub, dim3(gx, groups), lds, st, a, (const float *)d_codebook, state_words,
                                         d_code.as<uint8_t>(), d_vals.as<float>()));
-            SCANN_TRY(launch(cb_reset_min_pos_kernel, dim3(1), dim3(64), 0, st, d_tot.as<CbTotal>(), S));
+            SCANN_TRY(launch(cb_reset_min_pos_kernel, dim3(ceil_div_u32(S, 64)), dim3(64), 0, st, d_tot.as<CbTotal>(), S));
             SCANN_TRY(km_sums_batched(d_vals.as<float>(), n, S, d_part.as<double>(), &d_tot.as<CbTotal>()->min_pos, 4,
                                       state_words + 6, kCbStateWords, st));
             SCANN_TRY(km_totals_batched(d_part.as<double>(), n, S, nullptr, nullptr, nullptr, &d_tot.as<CbTotal>()->total,
                                         2, nullptr, 0, st));
-            SCANN_TRY(launch(cb_exact_kernel, dim3(1), dim3(64), 0, st, d_tot.as<CbTotal>(), d_state.as<CbState>(), S));
+            SCANN_TRY(launch(cb_exact_kernel, dim3(ceil_div_u32(S, 64)), dim3(64), 0, st, d_tot.as<CbTotal>(), d_state.as<CbState>(), S));
             SCANN_TRY(km_sequential_sums_batched(d_vals.as<float>(), n, S, &d_tot.as<CbTotal>()->total, 2, state_words + 7,
                                                  kCbStateWords, st));
-            SCANN_TRY(launch(cb_step_kernel, dim3(1), dim3(64), 0, st, d_tot.as<CbTotal>(), d_state.as<CbState>(), S, it,
+            SCANN_TRY(launch(cb_step_kernel, dim3(ceil_div_u32(S, 64)), dim3(64), 0, st, d_tot.as<CbTotal>(), d_state.as<CbState>(), S, it,
                              cfg.convergence_threshold));
             SCANN_HIP_CHECK(hipMemcpyAsync(hs.data(), d_state.p, (size_t)S * sizeof(CbState), hipMemcpyDeviceToHost, st));
             SCANN_HIP_CHECK(hipStreamSynchronize(st));
@@ -475,8 +475,8 @@ int train_codebook_batched(const BfIndexDev &tv, const scann_hip_build_config &c
         SCANN_TRY(launch(cb_pad_kernel, dim3(ceil_div_u32(S * (K - k) * dsub, 256)), dim3(256), 0, st, d_codebook, S, K, k,
                          dsub));
     SCANN_HIP_CHECK(hipStreamSynchronize(st));
-    if (rep)
-        for (uint32_t s = 0; s < S; ++s) {
+    if (rep)   // (the report's arrays hold the first 64 subspaces)
+        for (uint32_t s = 0; s < S && s < 64u; ++s) {
             rep->subspace_iterations[s] = hs[s].iters;
             rep->subspace_converged[s] = (int32_t)hs[s].converged;
         }
@@ -504,7 +504,7 @@ int train_codebook_per_subspace(const BfIndexDev &tv, const scann_hip_build_conf
         SCANN_TRY(launch(cb_store_subspace_kernel, dim3(ceil_div_u32(K * dsub, 256)), dim3(256), 0, st, d_sub.as<float>(),
                          d_codebook + (size_t)s * K * dsub, K, k, dsub));
         SCANN_HIP_CHECK(hipStreamSynchronize(st));
-        if (rep) {
+        if (rep && s < 64u) {
             rep->subspace_iterations[s] = iters;
             rep->subspace_converged[s] = conv;
         }
@@ -528,8 +528,9 @@ int build_check(const BfIndexDev &src, const scann_hip_build_config &cfg) {
                                                     " must be divisible by num_subspaces " + std::to_string(S));
     if (K == 0 || K > 256) return fail(SCANN_HIP_UNIMPLEMENTED, "num_codes must be 1..256");
     const uint32_t bits = K <= 16 ? 4u : 8u;
-    if (bits == 4 && (S % 8 != 0 || S > 64 || S == 40 || S == 56))
-        return fail(SCANN_HIP_UNIMPLEMENTED, "num_subspaces must be 8,16,24,32,48 or 64 for num_codes <= 16");
+    if (bits == 4 && (S % 8 != 0 || S == 40 || S == 56 || (S > 64 && (S % kSlabSub != 0 || S > kSlabMaxS))))
+        return fail(SCANN_HIP_UNIMPLEMENTED,
+                    "num_subspaces must be 8,16,24,32,48,64 or a multiple of 32 from 96 to 512 for num_codes <= 16");
     if (bits == 8 && S != 4 && S != 8 && S != 16)
         return fail(SCANN_HIP_UNIMPLEMENTED, "num_subspaces must be 4, 8 or 16 for 16 < num_codes <= 256");
     if (std::min<uint64_t>(cfg.num_partitions, src.n) > kMaxLeavesSelect)

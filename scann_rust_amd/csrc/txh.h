@@ -22,6 +22,11 @@ constexpr uint32_t kScanDepth = SCANN_SCAN_DEPTH;         // gather software-pip
 constexpr uint32_t kScanWaves = SCANN_SCAN_WAVES;         // workgroups per CU = waves per SIMD (S <= 32)
 constexpr uint32_t kResThreads = 512;                     // resident-table scan: threads per workgroup
 constexpr uint32_t kResQuads = 4;                         // ... quads whose tables stay in LDS
+// the slab-walking scan of 4-bit indexes with more than 64 subspaces (txh_slab.hip K6s)
+constexpr uint32_t kSlabSub = 32;                         // subspaces per slab: one uint4 of codes, 8 KB of table per quad
+constexpr uint32_t kSlabQuads = 4;                        // ... query quads per work item (its qpt and sqpt)
+constexpr uint32_t kSlabStage = 64;                       // ... LDS-staged survivors per (quad, query)
+constexpr uint32_t kSlabMaxS = 512;                       // ... largest S it takes
 constexpr uint32_t kSortCap = 16384;                      // u64 keys sorted in LDS (select)
 #ifndef SCANN_SAMPLE_TARGET
 #define SCANN_SAMPLE_TARGET 32768
@@ -138,6 +143,9 @@ static inline uint32_t scan_tile_points(const TxhIndexDev &ix) {
     return kScanThreads * (ix.code_bits == 4 ? kScanPPT : 8u);
 }
 
+// 4-bit codes whose S only the slab scan takes: a multiple of kSlabSub with 64 < S <= kSlabMaxS (txh_slab.hip)
+bool txh_slab_layout(const TxhIndexDev &ix);
+
 // counters[] slots
 enum {
     CNT_TOTAL_QUADS = 0, CNT_TOTAL_TILES = 1, CNT_QUEUE_HEAD = 2, CNT_STATUS = 3,
@@ -154,8 +162,8 @@ enum {
 enum class TxhPipeline : uint8_t { Staged, Small, Wide };
 // Scan kernel of the batched pipeline: the f32 LDS-gather scan, its resident-table form (long leaves), the
 // integer-MFMA prefilter + exact refine on 32- or 16-pair dense tiles or 32-pair tiles of the 2:4-sparse MFMA, or the
-// exact leaf scan (SearchMode::Partitioned).
-enum class TxhScan : uint8_t { Gather, Resident, Mfma32, Mfma16, Smfmac, Exact };
+// exact leaf scan (SearchMode::Partitioned), or the slab-walking gather scan of 4-bit codes with 64 < S <= 512 (txh_slab.hip).
+enum class TxhScan : uint8_t { Gather, Resident, Mfma32, Mfma16, Smfmac, Exact, Slab };
 
 // Every path decision of one search call and the sizes they were derived from (api_search.hip plan_txh_search).
 struct TxhPlan {

@@ -3095,7 +3095,9 @@ static size_t threshold_select_lds(uint32_t scap) {
 
 // K5a + K5b / K5c: the f32 sample of every query's stream and the filter bound from it
 static int launch_gather_bound(const TxhIndexDev &ix, const TxhWork &w, hipStream_t st) {
-    if (!w.no_threshold) {
+    if (!w.no_threshold && w.scan == TxhScan::Slab) {   // 4-bit codes, S > 64: the slab-walking sample pass (txh_slab.hip)
+        SCANN_TRY(launch_slab_sample(ix, w, st));
+    } else if (!w.no_threshold) {
         SCANN_TRY(with_codec(ix, [&](auto codec) -> int {
             using C = decltype(codec);
             SampleArgs sa;
@@ -3132,6 +3134,12 @@ static int launch_open_bound(const TxhWork &w, hipStream_t st) {
 
 // K6 / K6b: the f32 gather scan or its resident-table form
 static int launch_gather_scan(const TxhIndexDev &ix, const TxhWork &w, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1) {
+    if (w.scan == TxhScan::Slab) {   // 4-bit codes, S > 64: the slab-walking scan (txh_slab.hip)
+        if (ev0) SCANN_HIP_CHECK(hipEventRecord(ev0, st));
+        SCANN_TRY(launch_slab_scan(ix, w, st));
+        if (ev1) SCANN_HIP_CHECK(hipEventRecord(ev1, st));
+        return SCANN_HIP_OK;
+    }
     return with_codec(ix, [&](auto codec) -> int {
         using C = decltype(codec);
         const int cus = num_cus();
@@ -4247,7 +4255,8 @@ int txh_launch_search(const TxhIndexDev &ix, const TxhWork &w, bool local_only, 
     } else {
         // tables, bound, scan
         SCANN_TRY(launch_lut_build(ix, w, st));
-        SCANN_TRY(with_codec(ix, [](auto) { return (int)SCANN_HIP_OK; }));   // an unsupported code layout ends the call here
+        // an unsupported code layout ends the call here
+        if (w.scan != TxhScan::Slab || !txh_slab_layout(ix)) SCANN_TRY(with_codec(ix, [](auto) { return (int)SCANN_HIP_OK; }));
         if (w.sample_mfma) SCANN_TRY(launch_sample_mfma_bound(ix, w, st));
         else SCANN_TRY(launch_gather_bound(ix, w, st));
         if (ix.code_bits == 4 && txh_scan_is_mfma(w.scan)) SCANN_TRY(launch_prefilter_refine(ix, w, st, ev0, ev1));

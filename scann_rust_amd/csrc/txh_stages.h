@@ -24,6 +24,10 @@ int launch_lut_build(const TxhIndexDev &ix, const TxhWork &w, hipStream_t st);
 int launch_lut8_build(const TxhWork &w, uint32_t S, int fold, hipStream_t st);
 int launch_prefilter_refine(const TxhIndexDev &ix, const TxhWork &w, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
 
+// ---- txh_slab.hip: K5s / K6s, the sample pass and the scan of 4-bit indexes with 96 .. 512 subspaces ----
+int launch_slab_sample(const TxhIndexDev &ix, const TxhWork &w, hipStream_t st);
+int launch_slab_scan(const TxhIndexDev &ix, const TxhWork &w, hipStream_t st);
+
 // ---- txh_rows.hip: the 8-bit row stores of the re-rank filter (K8b) ----
 int launch_rerank_i8(const TxhIndexDev &ix, const TxhWork &w, hipStream_t st);
 // ... and the re-rank of a handle whose rows are stored quantized (ix.qrows): cand_exact of every candidate

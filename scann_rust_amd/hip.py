@@ -1770,7 +1770,8 @@ def build_config(**cfg):
 def txh_build(bf_index, **cfg):
     """scann_hip_txh_build: a tree (num_partitions > 0) or flat-hasher (0) index trained, encoded and laid out on the
     device from the resident rows of an f32 brute-force index.  Returns (Index, report): report is a dict with
-    partition_iterations / _converged / _inertia, subspace_iterations and subspace_converged ([S] lists) and stage_ms
+    partition_iterations / _converged / _inertia, subspace_iterations and subspace_converged ([S] lists; the first 64
+    subspaces when num_subspaces is 96 .. 512, the LUT16 shapes of the slab-walking scan) and stage_ms
     ({stage name: milliseconds}, BUILD_STAGES)."""
     c = build_config(**cfg)
     rep = BuildReport()

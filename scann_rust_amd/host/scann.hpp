@@ -1391,7 +1391,8 @@ private:
 };
 
 // ---- AsymmetricHasher (hashes/hasher.rs) ---------------------------------------------------
-struct AsymmetricHasherConfig {      // hasher.rs:19-69 (default 256 x 8: byte codes; K <= 16 takes the LUT16 path)
+struct AsymmetricHasherConfig {      // hasher.rs:19-69 (default 256 x 8: byte codes; K <= 16 takes the LUT16 path:
+                                     // num_subspaces 8,16,24,32,48,64 or a multiple of 32 from 96 to 512)
     size_t num_codes = 256, num_subspaces = 8;
     uint64_t seed = 42;
     bool has_seed = false;
