@@ -267,7 +267,10 @@ typedef struct {
     uint32_t num_subspaces;      /* S */
     uint32_t num_codes;          /* K <= 16: LUT16 (4-bit codes, S in {8,16,24,32,48,64}, or a multiple of 32 from 96
                                   * to 512: the slab-walking scan, no MFMA prefilter or resident form);
-                                  * 16 < K <= 256: byte codes (S in {4,8,16}).  Other shapes: Unimplemented */
+                                  * 16 < K <= 256: byte codes (S in {4,8,16}, or, for K >= 32, a multiple of 8 from 24
+                                  * to 128: the byte-code slab scan; its search workspace holds S KB of query tables
+                                  * per (query, leaf) pair, 64 KB at S = 64: 0.67 GB at batch 1024 x 10 partitions).
+                                  * Other shapes: Unimplemented */
     uint32_t dims_per_subspace;  /* dsub; S * dsub must equal dim (codebook.rs:154-159) */
     const uint8_t *codes;
     int32_t codes_packed4;

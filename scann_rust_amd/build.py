@@ -13,7 +13,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "_obj")
 LIB = os.path.join(HERE, "libscann_hip.so")
 # the units of the tree / flat-hasher search
-TXH_SOURCES = ["txh.hip", "txh_partition.hip", "txh_prefilter.hip", "txh_rows.hip", "txh_blocks.hip", "txh_slab.hip"]
+TXH_SOURCES = ["txh.hip", "txh_partition.hip", "txh_prefilter.hip", "txh_rows.hip", "txh_blocks.hip", "txh_slab.hip", "txh_slab8.hip"]
 # the C ABI over the handle of handle.h: lifetime and building blocks, creation, searches, crowding / MMR stages
 API_SOURCES = ["api.hip", "api_create.hip", "api_search.hip", "api_stages.hip"]
 SOURCES = API_SOURCES + TXH_SOURCES + ["bf.hip", "index_file.hip", "comm.hip", "crowd.hip", "mmr.hip", "mutable.hip", "fold.hip", "allow.hip", "tokens.hip", "ranges.hip", "scalarq.hip", "project.hip", "build.hip", "pca.hip", "ktree.hip"]
@@ -23,9 +23,10 @@ HEADERS = ["common.h", "knobs.h", "handle.h", "txh_arena.h", "txh.h", "txh_dev.h
 CFLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "-fPIC", "-Wall",
           "-Wno-unused-function"]
 LDFLAGS = ["-shared", "-fPIC", "--offload-arch=gfx950", "-ldl"]
-# flags of single units.  txh_slab.hip adds float4 table entries lane by lane: packed f32 VALU forms are kept out of it,
-# so that every add is the scalar v_add_f32 the older scans were measured and verified with.
-UNIT_FLAGS = {"txh_slab.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+# flags of single units.  txh_slab.hip and txh_slab8.hip add float4 table entries lane by lane: packed f32 VALU forms are
+# kept out of them, so that every add is the scalar v_add_f32 the older scans were measured and verified with.
+_NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+UNIT_FLAGS = {"txh_slab.hip": _NO_PK_F32, "txh_slab8.hip": _NO_PK_F32}
 
 
 def src_sha256():

@@ -276,8 +276,10 @@ int scann::txh_create_checked(scann_hip_ctx *ctx, const scann_hip_txh_desc *d, s
     if (!exact && bits == 4 && (S % 8 != 0 || S == 40 || S == 56 || (S > 64 && (S % kSlabSub != 0 || S > kSlabMaxS))))
         return fail(SCANN_HIP_UNIMPLEMENTED,
                     "num_subspaces must be 8,16,24,32,48,64 or a multiple of 32 from 96 to 512 for num_codes <= 16");
-    if (bits == 8 && S != 4 && S != 8 && S != 16)
-        return fail(SCANN_HIP_UNIMPLEMENTED, "num_subspaces must be 4, 8 or 16 for 16 < num_codes <= 256");
+    // (S >= 24: the byte-code slab scan, txh_slab8.hip)
+    if (bits == 8 && S != 4 && S != 8 && S != 16 && !txh_slab8_shape(S, K))
+        return fail(SCANN_HIP_UNIMPLEMENTED, "num_subspaces must be 4, 8 or 16 for 16 < num_codes <= 256, or a multiple "
+                                             "of 8 from 24 to 128 for 32 <= num_codes <= 256");
     if (bits == 8 && d->codes_packed4)
         return fail(SCANN_HIP_INVALID_ARGUMENT, "codes_packed4 needs num_codes <= 16");
     if (!ah) {

@@ -45,6 +45,8 @@ static void plan_small_launch(const TxhIndexDev &t, const Knobs &kn, TxhPlan *p)
     p->grid = std::max(1u, ceil_div_u32(p->cap, p->chunk));
     p->fused = kn.fused && p->P <= kDecodeStage && (uint64_t)p->nq * p->grid <= kFusedMaxWgs &&
                (t.exact_scan || p->P == 1);
+    // (byte codes with S > 16: the one-launch form keeps ~78 KB of static arrays beside the tables)
+    if (p->fused && txh_slab8_layout(t)) p->fused = txh_few_query_fits(t, TxhPipeline::Small, true);
 }
 
 // Every path decision of a tree / AH search of nq queries.  retry: the host entry's second attempt after a
@@ -100,8 +102,13 @@ int scann::plan_txh_search(const scann_hip_index *ix, uint32_t k, const scann_hi
     // A handful of queries over a short stream: three launches with dense candidate lists instead of
     // the batched pipeline (SCANN_HIP_SMALL=0 disables).  Unsharded indexes only: stream positions are
     // list slots, and a shard's local leaves leave holes in them.
+    // (byte codes with S > 16: a few-query pipeline holds a whole table, S KB, in LDS; a shape that does not fit one
+    // takes the next: 134 KB at S = 128, dim 768 fits both)
+    const bool slab8 = txh_slab8_layout(t);
+    const bool small_fits = !slab8 || txh_few_query_fits(t, TxhPipeline::Small, false);
+    const bool wide_fits = !slab8 || txh_few_query_fits(t, TxhPipeline::Wide, false);
     p.pipeline = TxhPipeline::Staged;
-    if (widest != TxhPipeline::Staged && kn.small && nq <= kSmallBatch && !ix->sharded && m <= kSmallMaxCandidates &&
+    if (widest != TxhPipeline::Staged && small_fits && kn.small && nq <= kSmallBatch && !ix->sharded && m <= kSmallMaxCandidates &&
         k <= 64 && ms <= kSmallMaxStream && t.L <= 4096 && (!t.exact_scan || txh_exact_scan_fits(t)))
         p.pipeline = TxhPipeline::Small;
     // Fewer queries still, over a long stream: the wide pipeline (three launches, every stage spread over the chip).
@@ -110,7 +117,7 @@ int scann::plan_txh_search(const scann_hip_index *ix, uint32_t k, const scann_hi
     // pipeline, 0.147 through this one).  Streams of >= 8 m points: below that most of the stream is candidates anyway.
     // SCANN_HIP_WIDE: 0 = never, 2 = whenever the limits allow (tests), else from kWideMinStream points.
     {
-        const bool limits = widest == TxhPipeline::Wide && kn.small && kn.wide != 0 && nq <= kWideBatch &&
+        const bool limits = widest == TxhPipeline::Wide && wide_fits && kn.small && kn.wide != 0 && nq <= kWideBatch &&
                             !ix->sharded && m >= 1 && m <= kWideMaxCandidates && k <= 64 && ms <= kWideMaxStream &&
                             t.L <= 4096 && P <= 512 && !t.exact_scan;
         const bool long_leaves = P == 1 || t.n_local / std::max(1u, t.L) >= 512;
@@ -202,6 +209,14 @@ int scann::plan_txh_search(const scann_hip_index *ix, uint32_t k, const scann_hi
         p.scan = TxhScan::Slab;
         p.qpt = p.sqpt = kSlabQuads;
     }
+    // Byte codes with more than 16 subspaces: the byte-code slab scan and its sample pass (txh_slab8.hip), whatever the
+    // knobs say -- byte codes have no prefilter, resident form or operand planes.  Its work items are 2048 points x
+    // kSlab8Quads quads, for the sample pass too (a quad's tables are S x 4 KB in lutq, S KB or 64 KB per pair at S = 64; an
+    // item holds two slabs of 16 KB of each quad in LDS).
+    if (slab8) {
+        p.scan = TxhScan::Slab8;
+        p.qpt = p.sqpt = kSlab8Quads;
+    }
     if (txh_scan_is_mfma(p.scan)) {
         // survivors of the integer bound: the f32 filter's (<= cap) plus the quantisation margin
         // (the margin's share is independent of m -- the points within 17 table steps above the bound -- and in
@@ -267,6 +282,7 @@ static const char *txh_kernel_name(const TxhIndexDev &t, const TxhPlan &p, bool 
         case TxhScan::Mfma32: return "adc_mfma_kernel";
         case TxhScan::Resident: return "adc_scan_res_kernel";
         case TxhScan::Slab: return "adc_slab_scan_kernel";
+        case TxhScan::Slab8: return "adc_slab8_scan_kernel";
         default: return "adc_scan_kernel";
     }
 }

@@ -27,6 +27,15 @@ constexpr uint32_t kSlabSub = 32;                         // subspaces per slab:
 constexpr uint32_t kSlabQuads = 4;                        // ... query quads per work item (its qpt and sqpt)
 constexpr uint32_t kSlabStage = 64;                       // ... LDS-staged survivors per (quad, query)
 constexpr uint32_t kSlabMaxS = 512;                       // ... largest S it takes
+// the slab-walking scan of byte-code indexes with more than 16 subspaces (txh_slab8.hip K6t)
+constexpr uint32_t kSlab8Sub = 4;                         // subspaces per slab: one u32 of codes, 16 KB of table per quad
+constexpr uint32_t kSlab8Quads = 2;                       // ... query quads per work item (its qpt and sqpt)
+constexpr uint32_t kSlab8Stage = 192;                     // ... LDS-staged survivors per (quad, query)
+constexpr uint32_t kSlab8MinS = 24;                       // ... smallest and largest S it takes, in steps of
+constexpr uint32_t kSlab8MaxS = 128;                      //     kSlab8Step (below kSlab8MinS: adc_scan_kernel at 4, 8, 16)
+constexpr uint32_t kSlab8Step = 8;
+constexpr uint32_t kSlab8MinCodes = 32;                   // ... fewest codes it takes there: 17 .. 31 codes (5 bits) in bytes and
+                                                          //     256-slot tables stay refused above 16 subspaces, as before
 constexpr uint32_t kSortCap = 16384;                      // u64 keys sorted in LDS (select)
 #ifndef SCANN_SAMPLE_TARGET
 #define SCANN_SAMPLE_TARGET 32768
@@ -145,6 +154,12 @@ static inline uint32_t scan_tile_points(const TxhIndexDev &ix) {
 
 // 4-bit codes whose S only the slab scan takes: a multiple of kSlabSub with 64 < S <= kSlabMaxS (txh_slab.hip)
 bool txh_slab_layout(const TxhIndexDev &ix);
+// byte codes whose S only the byte-code slab scan takes: a multiple of kSlab8Step from kSlab8MinS to kSlab8MaxS
+// with kSlab8MinCodes <= K <= 256 (txh_slab8.hip); the first form is the shape test of create and build
+static inline bool txh_slab8_shape(uint32_t S, uint32_t K) {
+    return S >= kSlab8MinS && S <= kSlab8MaxS && S % kSlab8Step == 0 && K >= kSlab8MinCodes && K <= 256;
+}
+bool txh_slab8_layout(const TxhIndexDev &ix);
 
 // counters[] slots
 enum {
@@ -162,8 +177,9 @@ enum {
 enum class TxhPipeline : uint8_t { Staged, Small, Wide };
 // Scan kernel of the batched pipeline: the f32 LDS-gather scan, its resident-table form (long leaves), the
 // integer-MFMA prefilter + exact refine on 32- or 16-pair dense tiles or 32-pair tiles of the 2:4-sparse MFMA, or the
-// exact leaf scan (SearchMode::Partitioned), or the slab-walking gather scan of 4-bit codes with 64 < S <= 512 (txh_slab.hip).
-enum class TxhScan : uint8_t { Gather, Resident, Mfma32, Mfma16, Smfmac, Exact, Slab };
+// exact leaf scan (SearchMode::Partitioned), or the slab-walking gather scan of 4-bit codes with 64 < S <= 512 (txh_slab.hip)
+// or of byte codes with 24 <= S <= 128 (txh_slab8.hip).
+enum class TxhScan : uint8_t { Gather, Resident, Mfma32, Mfma16, Smfmac, Exact, Slab, Slab8 };
 
 // Every path decision of one search call and the sizes they were derived from (api_search.hip plan_txh_search).
 struct TxhPlan {
@@ -271,6 +287,10 @@ int txh_launch_search(const TxhIndexDev &ix, const TxhWork &w, bool local_only,
 // false where the batched exact leaf scan (Partitioned mode) refuses this dim for want of LDS: the small-batch
 // pipeline is then not planned either, so that the dims a search refuses do not depend on the batch size
 bool txh_exact_scan_fits(const TxhIndexDev &ix);
+// whether the few-query pipeline `p` (its one-launch form if `fused`) has the LDS for this index's tables: 4 (S kp + dim)
+// bytes beside the kernel's static arrays -- 134 KB at S = 128, dim 768 (the leaf selection's LDS is not counted).
+// The plan asks it for txh_slab8_layout indexes and routes a shape that does not fit to the staged pipeline.
+bool txh_few_query_fits(const TxhIndexDev &ix, TxhPipeline p, bool fused);
 
 int txh_launch_partition_only(const TxhIndexDev &ix, const TxhWork &w, hipStream_t stream);
 

@@ -3097,6 +3097,8 @@ static size_t threshold_select_lds(uint32_t scap) {
 static int launch_gather_bound(const TxhIndexDev &ix, const TxhWork &w, hipStream_t st) {
     if (!w.no_threshold && w.scan == TxhScan::Slab) {   // 4-bit codes, S > 64: the slab-walking sample pass (txh_slab.hip)
         SCANN_TRY(launch_slab_sample(ix, w, st));
+    } else if (!w.no_threshold && w.scan == TxhScan::Slab8) {   // byte codes, S > 16: theirs (txh_slab8.hip)
+        SCANN_TRY(launch_slab8_sample(ix, w, st));
     } else if (!w.no_threshold) {
         SCANN_TRY(with_codec(ix, [&](auto codec) -> int {
             using C = decltype(codec);
@@ -3134,9 +3136,9 @@ static int launch_open_bound(const TxhWork &w, hipStream_t st) {
 
 // K6 / K6b: the f32 gather scan or its resident-table form
 static int launch_gather_scan(const TxhIndexDev &ix, const TxhWork &w, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1) {
-    if (w.scan == TxhScan::Slab) {   // 4-bit codes, S > 64: the slab-walking scan (txh_slab.hip)
-        if (ev0) SCANN_HIP_CHECK(hipEventRecord(ev0, st));
-        SCANN_TRY(launch_slab_scan(ix, w, st));
+    if (w.scan == TxhScan::Slab || w.scan == TxhScan::Slab8) {   // the slab-walking scans: 4-bit codes with S > 64
+        if (ev0) SCANN_HIP_CHECK(hipEventRecord(ev0, st));       // (txh_slab.hip), byte codes with S > 16 (txh_slab8.hip)
+        SCANN_TRY(w.scan == TxhScan::Slab ? launch_slab_scan(ix, w, st) : launch_slab8_scan(ix, w, st));
         if (ev1) SCANN_HIP_CHECK(hipEventRecord(ev1, st));
         return SCANN_HIP_OK;
     }
@@ -4225,6 +4227,18 @@ static int launch_search_small(const TxhIndexDev &ix, const TxhWork &w, hipStrea
     return SCANN_HIP_OK;
 }
 
+// Whether the scan kernel of launch_search_small has the LDS for this index's tables: its table request beside the
+// kernel's static arrays (a failed query counts as "does not fit").  The leaf selection's request, which the one-launch
+// and wide forms take the maximum with, is not counted: it does not depend on the code layout.
+bool txh_few_query_fits(const TxhIndexDev &ix, TxhPipeline p, bool fused) {
+    const void *kernel = p == TxhPipeline::Wide ? reinterpret_cast<const void *>(wide_scan_kernel)
+                         : fused                ? reinterpret_cast<const void *>(small_fused_kernel)
+                                                : reinterpret_cast<const void *>(small_scan_kernel);
+    size_t static_bytes = 0;
+    if (static_lds_bytes(kernel, &static_bytes) != SCANN_HIP_OK) return false;
+    return ((size_t)ix.S * ix.kp + ix.dim) * sizeof(float) + static_bytes <= kMaxLdsBytes;
+}
+
 // The work lists follow the scan kernel's items.
 static WorkTiling work_tiling(const TxhIndexDev &ix, const TxhWork &w) {
     switch (w.scan) {
@@ -4256,7 +4270,8 @@ int txh_launch_search(const TxhIndexDev &ix, const TxhWork &w, bool local_only, 
         // tables, bound, scan
         SCANN_TRY(launch_lut_build(ix, w, st));
         // an unsupported code layout ends the call here
-        if (w.scan != TxhScan::Slab || !txh_slab_layout(ix)) SCANN_TRY(with_codec(ix, [](auto) { return (int)SCANN_HIP_OK; }));
+        if (!(w.scan == TxhScan::Slab && txh_slab_layout(ix)) && !(w.scan == TxhScan::Slab8 && txh_slab8_layout(ix)))
+            SCANN_TRY(with_codec(ix, [](auto) { return (int)SCANN_HIP_OK; }));
         if (w.sample_mfma) SCANN_TRY(launch_sample_mfma_bound(ix, w, st));
         else SCANN_TRY(launch_gather_bound(ix, w, st));
         if (ix.code_bits == 4 && txh_scan_is_mfma(w.scan)) SCANN_TRY(launch_prefilter_refine(ix, w, st, ev0, ev1));

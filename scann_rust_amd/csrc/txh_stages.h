@@ -28,6 +28,10 @@ int launch_prefilter_refine(const TxhIndexDev &ix, const TxhWork &w, hipStream_t
 int launch_slab_sample(const TxhIndexDev &ix, const TxhWork &w, hipStream_t st);
 int launch_slab_scan(const TxhIndexDev &ix, const TxhWork &w, hipStream_t st);
 
+// ---- txh_slab8.hip: K5t / K6t, the sample pass and the scan of byte-code indexes with 24 .. 128 subspaces ----
+int launch_slab8_sample(const TxhIndexDev &ix, const TxhWork &w, hipStream_t st);
+int launch_slab8_scan(const TxhIndexDev &ix, const TxhWork &w, hipStream_t st);
+
 // ---- txh_rows.hip: the 8-bit row stores of the re-rank filter (K8b) ----
 int launch_rerank_i8(const TxhIndexDev &ix, const TxhWork &w, hipStream_t st);
 // ... and the re-rank of a handle whose rows are stored quantized (ix.qrows): cand_exact of every candidate

@@ -1771,7 +1771,8 @@ def txh_build(bf_index, **cfg):
     """scann_hip_txh_build: a tree (num_partitions > 0) or flat-hasher (0) index trained, encoded and laid out on the
     device from the resident rows of an f32 brute-force index.  Returns (Index, report): report is a dict with
     partition_iterations / _converged / _inertia, subspace_iterations and subspace_converged ([S] lists; the first 64
-    subspaces when num_subspaces is 96 .. 512, the LUT16 shapes of the slab-walking scan) and stage_ms
+    subspaces when num_subspaces is above 64: the LUT16 shapes 96 .. 512 of the slab-walking scan, the byte-code
+    shapes 72 .. 128 of its byte-code form) and stage_ms
     ({stage name: milliseconds}, BUILD_STAGES)."""
     c = build_config(**cfg)
     rep = BuildReport()

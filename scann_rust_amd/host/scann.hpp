@@ -1391,8 +1391,9 @@ private:
 };
 
 // ---- AsymmetricHasher (hashes/hasher.rs) ---------------------------------------------------
-struct AsymmetricHasherConfig {      // hasher.rs:19-69 (default 256 x 8: byte codes; K <= 16 takes the LUT16 path:
-                                     // num_subspaces 8,16,24,32,48,64 or a multiple of 32 from 96 to 512)
+struct AsymmetricHasherConfig {      // hasher.rs:19-69 (default 256 x 8: byte codes, num_subspaces 4,8,16 or, from 32 codes, a
+                                     // multiple of 8 from 24 to 128; K <= 16 takes the LUT16 path: num_subspaces 8,16,24,32,48,64
+                                     // or a multiple of 32 from 96 to 512)
     size_t num_codes = 256, num_subspaces = 8;
     uint64_t seed = 42;
     bool has_seed = false;

@@ -12,7 +12,14 @@ slab scan).  One process, a warm-up, then interleaved rounds: every round times 
     point x query x subspace, median with min / max, and the ratio to S = 64.
 (b) recall10@10 against the exact brute force of the same rows and the QPS of whole search calls, at equal
     pre_reorder_k = 100 and 1000.
-One JSON line per measurement, appended to profiles/slab_scan_768_time.jsonl."""
+One JSON line per measurement, appended to profiles/slab_scan_768_time.jsonl.
+
+    python tools/time_slab_scan.py --num-codes 256 --subspaces 16 32 64 96 128 192x16 \
+        --json profiles/slab8_scan_768_time.jsonl
+
+--num-codes 256: byte codes, S = 16 on adc_scan_kernel<Codec<16, 8>> as the yardstick and the others on
+adc_slab8_scan_kernel.  An entry SxK builds that handle with K codes: 192x16 beside 96 is the
+equal-code-bytes pair of part (b)."""
 import argparse
 import json
 import os
@@ -34,7 +41,9 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--num-points", dest="n", type=int, default=1_000_000)
     ap.add_argument("--dim", type=int, default=768)
-    ap.add_argument("--subspaces", type=int, nargs="+", default=[64, 96, 192, 384])
+    ap.add_argument("--subspaces", nargs="+", default=["64", "96", "192", "384"], help="S, or SxK for a handle of K codes")
+    ap.add_argument("--num-codes", type=int, default=16)
+    ap.add_argument("--training-iterations", type=int, default=6)
     ap.add_argument("--batch", type=int, default=1024)
     ap.add_argument("--k", type=int, default=10)
     ap.add_argument("--scan-m", type=int, default=5000)
@@ -53,11 +62,16 @@ def main():
     ne = min(256, Q)
     truth = bf.search_batched(q[:ne], k)[0]
     handles = {}
-    for S in a.subspaces:
+    codes = {}   # handle key (S, or the string SxK) -> (S, K)
+    for spec in a.subspaces:
+        S, _, K = spec.partition("x")
+        codes[spec if K else int(S)] = (int(S), int(K) if K else a.num_codes)
+    for key, (S, K) in codes.items():
         t0 = time.time()
-        handles[S], _ = hip.txh_build(bf, num_partitions=0, num_subspaces=S, num_codes=16, training_iterations=6)
-        handles[S].enable_timing(True)
-        print("built S=%d in %.1fs" % (S, time.time() - t0), file=sys.stderr, flush=True)
+        handles[key], _ = hip.txh_build(bf, num_partitions=0, num_subspaces=S, num_codes=K,
+                                        training_iterations=a.training_iterations)
+        handles[key].enable_timing(True)
+        print("built S=%d K=%d in %.1fs" % (S, K, time.time() - t0), file=sys.stderr, flush=True)
     lines = []
 
     def emit(d):
@@ -82,13 +96,15 @@ def main():
             ix.search_batched(q, k, o)
             ms, names[S] = ix.last_kernel_ms()
             scan[S].append(ms)
-    ps = lambda S, ms: ms * 1e9 / (float(n) * Q * S)
-    base = ps(64, med(scan[64])[0]) if 64 in scan else None
-    for S in handles:
-        m_, lo, hi = med(scan[S])
-        emit({"what": "scan", "kernel": names[S], "n": n, "dim": dim, "S": S, "nq": Q, "m": a.scan_m, "ms": round(m_, 4),
-              "ms_min": round(lo, 4), "ms_max": round(hi, 4), "ps_per_point_query_subspace": round(ps(S, m_), 4),
-              "ratio_to_S64": round(ps(S, m_) / base, 3) if base else None, "rounds": a.rounds})
+    ps = lambda key, ms: ms * 1e9 / (float(n) * Q * codes[key][0])
+    yard = 64 if a.num_codes <= 16 else 16   # the largest S of the gather scan for these codes
+    base = ps(yard, med(scan[yard])[0]) if yard in scan else None
+    for key in handles:
+        m_, lo, hi = med(scan[key])
+        emit({"what": "scan", "kernel": names[key], "n": n, "dim": dim, "S": codes[key][0], "num_codes": codes[key][1],
+              "nq": Q, "m": a.scan_m, "ms": round(m_, 4), "ms_min": round(lo, 4), "ms_max": round(hi, 4),
+              "ps_per_point_query_subspace": round(ps(key, m_), 4),
+              "ratio_to_S%d" % yard: round(ps(key, m_) / base, 3) if base else None, "rounds": a.rounds})
     # ---- (b) recall and QPS at equal pre_reorder_k ------------------------------------------------------------------
     for m in a.recall_m:
         o = opts(m)
@@ -105,7 +121,8 @@ def main():
             gi = ix.search_batched(q[:ne], k, o)[0]
             rec = sum(len(set(gi[i].tolist()) & set(truth[i].tolist())) for i in range(ne)) / (ne * float(k))
             m_, lo, hi = med(step[S])
-            emit({"what": "search", "n": n, "dim": dim, "S": S, "nq": Q, "k": k, "m": m, "step_ms": round(m_, 4),
+            emit({"what": "search", "n": n, "dim": dim, "S": codes[S][0], "num_codes": codes[S][1], "nq": Q, "k": k, "m": m,
+                  "step_ms": round(m_, 4),
                   "step_ms_min": round(lo, 4), "step_ms_max": round(hi, 4), "qps": round(Q / (m_ * 1e-3), 1),
                   "recall10at10": round(rec, 4)})
     with open(a.json, "a") as f:
