@@ -1636,23 +1636,82 @@ __global__ __launch_bounds__(kRefineThreads) void adc_refine_kernel(TxhIndexDev 
 // and key <= T, as adc_refine_kernel does them.  A chunk that holds more points than the queue has room for (dense
 // rows: a bound every point meets) is pushed in rounds.  All blocks walk their rows upwards from word 0, so the batch
 // sweeps the plane array roughly together and its lines repeat in the L2s.
+// Two stages are written for few vector instructions: a lane pops its four words in ONE loop (as many
+// trips as the fullest lane has bits, not the sum over the word slots of the fullest slot) and queues the bit's number
+// in the row, which sp_bit_point turns into the point when 64 lanes pop at once; and the table's byte offsets come one
+// v_bfe each from pre-masked code words (SpRowOffsets) and meet the table at LDS address 0, so that the subspace's
+// offset is the ds_read's immediate.
 #ifndef SCANN_REFINE_BITS_THREADS
 #define SCANN_REFINE_BITS_THREADS 256
 #endif
 constexpr uint32_t kRefineBitsThreads = SCANN_REFINE_BITS_THREADS;   // (512: refine 135 us against 119 us at the flagship)
-constexpr uint32_t kRefineBitsU = 4;            // points per lane scored side by side
+constexpr uint32_t kRefineBitsU = 4;            // points per lane scored side by side (2 and 6: within 1 us of 4 at the flagship)
 constexpr uint32_t kRefineBitsQueue = 1024;     // points a wave's queue holds
 static_assert(kRefineBitsQueue > 2 * 64 * kRefineBitsU, "room for a push on top of what a pop leaves");
 
+// bit b of a query's row of surv -> the point it stands for (sp_store_item_bits; tests/sp_bitmap_model.py): word
+// b >> 5 = range * 32 + 2 tt + h, bpos = b & 31, point range * 1024 + (2 tt + (bpos >> 4)) * 32 + 4 h + (r & 3) +
+// ((r >> 2) << 3) with r = 15 - (bpos & 15).  In bits: r = ~b[0..3]; b[0,1] -> p[0,1] and b[2,3] -> p[3,4] inverted,
+// b[4] -> p[5], b[5] -> p[2], b[6..] stay.
+__device__ __forceinline__ uint32_t sp_bit_point(uint32_t b) {
+    const uint32_t t = b ^ 15u;
+    return (t & ~0x3Cu) | ((t & 0x1Cu) << 1) | ((t >> 3) & 4u);
+}
+
+// SpRow's codes as byte offsets into a [s][16] f32 table (code * 4).  A code word (ca / cb: eight codes, a nibble each)
+// is kept twice, with the upper two bits of its odd / of its even nibbles cleared: the six bits from bit 4 k - 2 of the
+// copy whose nibble k - 1 is cleared are code k * 4, one v_bfe_u32 (k = 0: mask and shift).
+template <int S>
+struct SpRowOffsets {
+    static constexpr int NWP = SpLayout<S>::NWP, NS = SpLayout<S>::NS;
+    uint32_t ev[2][2][NWP], od[2][2][NWP];   // [ca, cb][ha][word]: the copy the even / the odd nibbles are read from
+    uint32_t dv[2], dn[2];
+    __device__ __forceinline__ void decode(const uint32_t *row) {
+#pragma unroll
+        for (int ha = 0; ha < 2; ++ha) {
+#pragma unroll
+            for (int wi = 0; wi < NWP; ++wi) {
+                const uint32_t v = row[(ha * 2 + 0) * NWP + wi], n = row[(ha * 2 + 1) * NWP + wi];
+                const uint32_t ca = ((v & 0x33333333u) << 2) | (n & 0x33333333u);
+                const uint32_t cb = (v & 0xCCCCCCCCu) | ((n >> 2) & 0x33333333u);
+                ev[0][ha][wi] = ca & 0x3F3F3F3Fu; od[0][ha][wi] = ca & 0xF3F3F3F3u;
+                ev[1][ha][wi] = cb & 0x3F3F3F3Fu; od[1][ha][wi] = cb & 0xF3F3F3F3u;
+            }
+            dv[ha] = ((row[(ha * 2 + 0) * NWP + (NS >> 3)] >> (4 * (NS & 7))) & 15u) << 2;
+            dn[ha] = ((row[(ha * 2 + 1) * NWP + (NS >> 3)] >> (4 * (NS & 7))) & 15u) << 2;
+        }
+    }
+    __device__ __forceinline__ uint32_t offset(int s) const {   // s: compile-time after unrolling
+        if (s < 4) return (s >> 1) ? dn[s & 1] : dv[s & 1];
+        const int kt = (s - 4) >> 2, q = (s - 4) & 3, ha = q & 1, k = kt & 7;
+        if (k == 0) return (ev[q >> 1][ha][kt >> 3] & 15u) << 2;
+        const uint32_t src = (k & 1) ? od[q >> 1][ha][kt >> 3] : ev[q >> 1][ha][kt >> 3];
+        uint32_t off;   // (written as shift and mask, the compiler merges the masks and is back at two instructions a code)
+        asm("v_bfe_u32 %0, %1, %2, 6" : "=v"(off) : "v"(src), "s"(4 * k - 2));
+        return off;
+    }
+};
+
+template <int S, uint32_t NWAVES>
+struct RefineBitsLds {   // the kernel's only LDS object: the table sits at address 0
+    float tab[S * 16];
+    uint32_t queue[NWAVES][kRefineBitsQueue];
+    uint32_t out;
+};
+
+// At most 64 VGPRs (eight waves per SIMD by registers), though the grid brings four: with two caller streams the other
+// stream's select and re-rank kernels run beside this one, and at 70 registers (what the compiler takes under a bound
+// of four waves) the two-stream step loses everything the kernel gained.
 template <typename C>
-__global__ __launch_bounds__(kRefineBitsThreads, kRefineBitsThreads >= 512 ? 8 : 4) void adc_refine_bits_kernel(TxhIndexDev ix, RefineArgs a) {
+__global__ __launch_bounds__(kRefineBitsThreads, 8) void adc_refine_bits_kernel(TxhIndexDev ix, RefineArgs a) {
     constexpr int S = C::S;
     constexpr int SPW = SpLayout<S>::SPW;
     constexpr uint32_t U = kRefineBitsU, POP = 64u * U, NWAVES = kRefineBitsThreads / 64u;
     static_assert(C::BITS == 4 && kSpRange64 == 1024, "plane rows; 32 bitmap words per (query, range)");
-    extern __shared__ __attribute__((aligned(16))) float s_tab[];       // [S][16]
-    __shared__ uint32_t s_queue[NWAVES][kRefineBitsQueue];
-    __shared__ uint32_t s_out;
+    __shared__ __attribute__((aligned(16))) RefineBitsLds<S, NWAVES> lds;
+    float *const s_tab = lds.tab;                                        // [S][16]
+    uint32_t &s_out = lds.out;
+    uint32_t *queue = lds.queue[threadIdx.x >> 6];
     const uint32_t q = blockIdx.x, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const uint64_t T = a.thr[q];
     const uint32_t vb = a.vbase[(size_t)q * 2];                         // (P = 1: [nq][2])
@@ -1665,9 +1724,8 @@ __global__ __launch_bounds__(kRefineBitsThreads, kRefineBitsThreads >= 512 ? 8 :
     uint64_t *out = a.cand + (size_t)q * a.cap;
     const uint4 *row4 = reinterpret_cast<const uint4 *>(a.surv + (size_t)q * a.surv_stride);
     const uint32_t n4 = a.surv_stride / 4u;
-    uint32_t *queue = s_queue[wave];
 
-    // scores the n <= POP points queue[0 .. n) (n wave-uniform)
+    // scores the n <= POP entries queue[0 .. n) (n wave-uniform)
     auto score = [&](const uint32_t *pts, uint32_t n) {
         uint32_t j[U];
         bool ok[U];
@@ -1676,7 +1734,7 @@ __global__ __launch_bounds__(kRefineBitsThreads, kRefineBitsThreads >= 512 ? 8 :
         for (uint32_t u = 0; u < U; ++u) {
             const uint32_t e = lane + 64u * u;
             ok[u] = e < n;
-            j[u] = ok[u] ? pts[e] : 0u;
+            j[u] = ok[u] ? sp_bit_point(pts[e]) : 0u;
         }
         if (a.allow) {   // (block-uniform)
 #pragma unroll
@@ -1695,12 +1753,12 @@ __global__ __launch_bounds__(kRefineBitsThreads, kRefineBitsThreads >= 512 ? 8 :
             for (int x = 0; x < SPW / 4; ++x) {
                 w[4 * x] = rw[u][x].x; w[4 * x + 1] = rw[u][x].y; w[4 * x + 2] = rw[u][x].z; w[4 * x + 3] = rw[u][x].w;
             }
-            SpRow<S> r;
+            SpRowOffsets<S> r;
             r.decode(w);
             float acc = 0.0f;
 #pragma unroll
             for (int s2 = 0; s2 < S; ++s2) {
-                const float tv = s_tab[s2 * 16 + r.code(s2)];
+                const float tv = *reinterpret_cast<const float *>(reinterpret_cast<const char *>(s_tab) + (s2 * 64 + r.offset(s2)));
                 acc = s2 == 0 ? tv : acc + tv;
             }
             const uint64_t key = make_key(acc, vb + j[u]);
@@ -1717,32 +1775,30 @@ __global__ __launch_bounds__(kRefineBitsThreads, kRefineBitsThreads >= 512 ? 8 :
     uint32_t qn = 0;   // points in the wave's queue (wave-uniform)
     uint4 nxt = wave * 64u + lane < n4 ? row4[wave * 64u + lane] : make_uint4(0u, 0u, 0u, 0u);
     for (uint32_t c = wave; c * 64u < n4; c += NWAVES) {
-        uint32_t w[4] = {nxt.x, nxt.y, nxt.z, nxt.w};
+        uint32_t cur = nxt.x, w1 = nxt.y, w2 = nxt.z, w3 = nxt.w;   // the word being popped and the words behind it
         {
             const uint32_t i4 = (c + NWAVES) * 64u + lane;
             nxt = i4 < n4 ? row4[i4] : make_uint4(0u, 0u, 0u, 0u);
         }
-        const uint32_t cnt = (uint32_t)(__popc(w[0]) + __popc(w[1]) + __popc(w[2]) + __popc(w[3]));
+        const uint32_t cnt = (uint32_t)(__popc(cur) + __popc(w1) + __popc(w2) + __popc(w3));
         const uint32_t incl = wave_incl_scan(cnt);
         const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
         if (total == 0) continue;
-        const uint32_t gw = (c * 64u + lane) * 4u;   // the lane's first word: range gw >> 5, words gw & 31 .. + 3
-        const uint32_t p0 = (gw >> 5) * kSpRange64;
-        uint32_t sq = incl - cnt;                    // the lane's next point in the chunk's order
+        uint32_t sq = incl - cnt;                    // the lane's next point in the chunk's order; its last is incl - 1
+        uint32_t bit32 = (c * 64u + lane) * 4u;      // cur's word in the row: its bit 0 is the row's bit 32 * bit32
         for (uint32_t base = 0; base < total;) {
             const uint32_t take = min(total - base, kRefineBitsQueue - qn);
             const uint32_t lim = base + take;
-#pragma unroll
-            for (uint32_t x = 0; x < 4; ++x) {
-                const uint32_t wl = (gw & 31u) + x, tt = wl >> 1, h = wl & 1u;
-                while (w[x] && sq < lim) {
-                    const uint32_t bpos = (uint32_t)__ffs((int)w[x]) - 1u;
-                    w[x] &= w[x] - 1u;
-                    const uint32_t r = 15u - (bpos & 15u);
-                    const uint32_t jrel = (2u * tt + (bpos >> 4)) * 32u + 4u * h + (r & 3u) + ((r >> 2) << 3);
-                    queue[qn + sq - base] = p0 + jrel;
-                    ++sq;
-                }
+            const uint32_t end = min(incl, lim), at = qn - base;   // this round takes the lane's points sq .. end - 1
+            while (sq < end) {   // one pop a trip, no branch inside; an emptied word makes room for the next in the same trip
+                // (an empty cur -- empty words before the lane's last bit -- writes a number that the lane's next pop,
+                // which the loop's condition promises, overwrites: sq stays)
+                queue[at + sq] = (bit32 << 5) + (uint32_t)__ffs((int)cur) - 1u;
+                sq += cur != 0u;
+                cur &= cur - 1u;
+                const bool empty = cur == 0u;
+                cur = empty ? w1 : cur; w1 = empty ? w2 : w1; w2 = empty ? w3 : w2;   // (w3 stays: the lane's count ends
+                bit32 += empty;                                                    // the loop before a copy is popped)
             }
             qn += take;
             base = lim;
@@ -1824,7 +1880,7 @@ int launch_prefilter_refine(const TxhIndexDev &ix, const TxhWork &w, hipStream_t
                 if (w.scan != TxhScan::Smfmac || !w.sp_pairs64 || w.P != 1 || !ra.surv)
                     return fail(SCANN_HIP_INTERNAL, "survivor bitmaps are the 64-pair sparse prefilter's, P = 1");
                 if constexpr (C::S <= 32) {   // (as the 64-pair items themselves)
-                    SCANN_TRY(launch(adc_refine_bits_kernel<C>, dim3(w.nq), dim3(kRefineBitsThreads), (size_t)C::S * 16 * sizeof(float), st, ix, ra));
+                    SCANN_TRY(launch(adc_refine_bits_kernel<C>, dim3(w.nq), dim3(kRefineBitsThreads), 0, st, ix, ra));
                     return SCANN_HIP_OK;
                 } else {
                     return fail(SCANN_HIP_INTERNAL, "64-pair items are compiled for S <= 32");
