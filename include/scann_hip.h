@@ -1479,6 +1479,93 @@ int scann_hip_projection_arrays(const scann_hip_projection *projection, float *o
  * components + read-back. */
 void scann_hip_pca_last_stage_ms(float *out_ms4);
 
+/* ---- OPQ training on the device (OpqProjection::train_on_vecs, projection/opq.rs:91-157) -----------------
+ * Learns the rotation a product quantiser wants -- one that balances variance across subspaces -- from the resident
+ * rows of an f32 brute-force handle; no row crosses to the host.  The result is a SCANN_HIP_PROJ_MATRIX projection with
+ * in_dim = out_dim = d = the rows' dim, indistinguishable from one scann_hip_projection_create makes from the same
+ * array; the stored matrix is [out][in] = R^T, and scann_hip_txh_build_projected takes it unchanged.  The reference's
+ * routine calls itself "a simplified version - full OPQ would use k-means"; this is the full non-parametric
+ * alternation of Ge et al. (PAMI 2014) that comment points to.  THE RULE is the project's own (the reference's nalgebra
+ * calls are not reproducible: SURVEY F2, F4, F10), the one trainer.opq_rotation states.  X is the [ns][d] training
+ * rows, R_0 is `init`'s matrix taken as given (NULL: the identity):
+ *   1 sample      scann_hip_pca_train's step 1 with salt seed ^ 0x0B9; the sampled rows are gathered once into a
+ *                 device buffer.  max_samples == 0 or >= n: the handle's rows, in place.
+ *   2 for t = 0 .. opq_iterations - 1:
+ *     a project   Y = X R_t by scann_hip_project_device's kernel (f32, sequential, no FMA): the rows a later projected
+ *                 build sees.
+ *     b codebook  t == 0: step 3 of scann_hip_txh_build on Y (flat; seed + s per subspace; training_iterations Lloyd
+ *                 steps).  t >= 1: no seeding -- inner_iterations Lloyd steps per subspace from the previous codebook,
+ *                 with the same centre-update arithmetic and empty-cluster rule.
+ *     c encode    scann_hip_encode's rule on Y.  distortion[t] = ||Y - decode(codes)||_F^2 / ns, in f64: per row the
+ *                 columns lane, lane + 64, .. ascending per lane and a halving tree over 64 lanes; the rows by 256
+ *                 strided ascending sums and a halving tree.
+ *     d cross     M = X^T Yhat in f64, Yhat[r][j] = codebook[s][code[r][s]][j - s dsub], X widened, no centring.  On
+ *                 v_mfma_f64_16x16x4_f64, every 64 x 64 panel pair (M is not symmetric), Yhat decoded from the codes
+ *                 while the rows are staged (it never exists in memory), split over row runs into a workspace of at
+ *                 most 128 MiB and reduced in ascending run order; no floating-point atomics.
+ *     e polar     M = U S V^T by one-sided (Hestenes) Jacobi in f64 -- never an eigen-solve of M^T M, which squares a
+ *                 condition number that reaches 10^6 here: scann_hip_pca_train's round-robin pairing (d - 1 rounds of
+ *                 floor(d / 2) disjoint column pairs, a bye for odd d), one kernel per round, one workgroup per pair;
+ *                 alpha = ||m_p||^2, beta = ||m_q||^2, gamma = m_p . m_q reduced in a fixed lane order; zeta = (beta -
+ *                 alpha) / (2 gamma), t = sign(zeta) / (|zeta| + sqrt(1 + zeta^2)); gamma == 0 or a zero column: no
+ *                 rotation.  Converged when the largest |gamma| / sqrt(alpha beta) of a whole sweep is <= d 2^-52; at
+ *                 most 30 sweeps; an unconverged solve still returns its result, with converged = 0.  Then sigma_j =
+ *                 ||m'_j|| and R_{t+1} = sum over j of (m'_j / sigma_j) v_j^T in f64, cast to f32 (the polar factor of
+ *                 a non-singular M is unique: no sign or ordering rule).  sigma_min <= 2^-40 sigma_max: M is treated as
+ *                 singular -- training stops, R_t is returned and stopped_singular = 1.  (The threshold is a choice:
+ *                 the solve converges to about 2^-46 relative, this leaves six bits.)
+ *   3 R after the last completed iteration.
+ * cfg: num_subspaces and num_codes are the caller's (the (S, K) shapes scann_hip_txh_build accepts); the rest default to
+ *   opq_iterations 20 (OpqConfig::new; at most 64), training_iterations 25, inner_iterations 1, convergence_threshold
+ *   1e-5, seed 42, simd_threshold 128, max_samples 0 (every row).
+ * out_report (may be NULL): iterations_run = completed iterations; per iteration distortion, the solve's sweeps and
+ *   converged flag and sigma_min / sigma_max; stopped_singular; stage_ms = host-clock milliseconds of sample, project,
+ *   codebook + encode, cross-covariance, polar, summed over the iterations.
+ * Device memory while training, released on return: ns * d * 4 for the gathered sample (only when sampling), ns * d * 4
+ *   for Y, ns * S code bytes, ns * 8 row errors, scann_hip_txh_build's codebook buffers, at most 128 MiB of
+ *   cross-covariance runs, 2 * d * d * 8 for the solve, 2 * d * d * 4 for R_t and R_{t+1}.
+ * REFUSED before any launch (`rows` keeps searching): everything scann_hip_pca_train refuses, with the same status (d >
+ *   2048 -> ResourceExhausted, the message naming the limit); d % num_subspaces != 0 or an (S, K) shape the build
+ *   refuses -> the build's status; opq_iterations == 0 or > 64 -> InvalidArgument; `init` not a MATRIX projection or not
+ *   d x d -> InvalidArgument.
+ * NOT BUILT: training on the residuals of a tree; warm-starting from a PCA handle with a mean; a stream-ordered
+ *   *_device form; the segmented-sum form of M (sum over codes of (sum of the X rows with that code) x centroid, dsub
+ *   times fewer flops -- the k-means step dominates the iteration); d > 2048. */
+typedef struct scann_hip_opq_config {
+    uint32_t num_subspaces, num_codes;
+    uint32_t opq_iterations;          /* 20 */
+    uint32_t training_iterations;     /* 25 */
+    uint32_t inner_iterations;        /* 1 */
+    double   convergence_threshold;   /* 1e-5 */
+    uint64_t seed;                    /* 42 */
+    uint32_t simd_threshold;          /* 128 */
+    uint64_t max_samples;             /* 0 = every row */
+} scann_hip_opq_config;
+
+typedef struct scann_hip_opq_report {
+    uint32_t iterations_run; int32_t stopped_singular;
+    double distortion[64];
+    uint32_t sweeps[64]; int32_t converged[64];
+    double sigma_min_over_max[64];
+    float stage_ms[5];
+} scann_hip_opq_report;
+
+void scann_hip_opq_config_default(scann_hip_opq_config *cfg);
+int scann_hip_opq_train(scann_hip_index *rows, const scann_hip_opq_config *cfg, const scann_hip_projection *init,
+                        scann_hip_projection **out_projection, scann_hip_opq_report *out_report);
+/* Steps d and e as primitives, as scann_hip_kmeans_lloyd and scann_hip_encode are.
+ * scann_hip_opq_cross_covariance: out_M [d][d] (M[i][j] at i * d + j) = X^T Yhat of step d for the rows of an f32
+ * brute-force handle (d = its dim = S * dsub), a host codebook [S][K][dsub] and host codes [n][S] bytes, or, with
+ * codes_packed4 (K <= 16), [n][ceil(S / 2)] bytes holding subspace s in bits 4 (s & 1) .. of byte s >> 1.  A code >=
+ * K -> InvalidArgument.
+ * scann_hip_opq_polar: out_R [d][d] f32 (R[i][j] at i * d + j) = U V^T of the host matrix M [d][d] by step e, d <= 2048.
+ * out_singular [d] (may be NULL): the singular values, descending.  A singular M (a zero column, M = 0) is not an
+ * error: its zero singular values are returned and the columns they belong to contribute nothing to out_R. */
+int scann_hip_opq_cross_covariance(scann_hip_index *rows, const float *codebook, uint32_t S, uint32_t K, uint32_t dsub,
+                                   const uint8_t *codes, int codes_packed4, double *out_M);
+int scann_hip_opq_polar(scann_hip_ctx *ctx, const double *M, uint32_t d, float *out_R, double *out_singular,
+                        uint32_t *out_sweeps, int *out_converged);
+
 /* ---- projected device build ---------------------------------------------------------
  * scann_hip_txh_build for a PROJECTED index, in one call: `rows` is an f32 brute-force handle of projection.in_dim
  * floats per row, `projection` any kind (PCA from scann_hip_pca_train, a caller's MATRIX or TRUNCATE).  THE RULE: every

@@ -14,6 +14,7 @@
 #include "ktree.h"
 #include "launch.h"
 #include "mutable.h"
+#include "opq.h"
 #include "pca.h"
 #include "scalarq.h"
 
@@ -958,6 +959,47 @@ int scann_hip_pca_train(scann_hip_index *rows, uint32_t out_dim, uint64_t max_sa
     SCANN_TRY(pca_check(rows->bf, out_dim));   // every refusal, before the first launch
     return pca_train_device(rows->ctx, rows->bf, out_dim, max_samples, seed, rows->stream, out_projection, out_eigenvalues,
                             out_covariance, out_sweeps, out_converged);
+}
+
+int scann_hip_opq_train(scann_hip_index *rows, const scann_hip_opq_config *cfg, const scann_hip_projection *init,
+                        scann_hip_projection **out_projection, scann_hip_opq_report *out_report) {
+    if (!rows || !cfg || !out_projection) return fail(SCANN_HIP_INVALID_ARGUMENT, "null rows/config/out_projection");
+    *out_projection = nullptr;
+    if (out_report) std::memset(out_report, 0, sizeof(*out_report));
+    if (rows->kind != KIND_BF) return fail(SCANN_HIP_INVALID_ARGUMENT, "opq_train: not a brute-force index");
+    std::lock_guard<std::mutex> lock(rows->mu);
+    SCANN_TRY(set_device(rows->ctx));
+    SCANN_TRY(opq_check(rows->bf, *cfg, init));   // every refusal, before the first launch
+    return opq_train_device(rows->ctx, rows->bf, *cfg, init, rows->stream, out_projection, out_report);
+}
+
+int scann_hip_opq_cross_covariance(scann_hip_index *rows, const float *codebook, uint32_t S, uint32_t K, uint32_t dsub,
+                                   const uint8_t *codes, int codes_packed4, double *out_M) {
+    if (!rows || rows->kind != KIND_BF) return fail(SCANN_HIP_INVALID_ARGUMENT, "opq_cross_covariance: not a brute-force index");
+    const BfIndexDev &bf = rows->bf;
+    if (bf.fmt || !bf.rows) return fail(SCANN_HIP_INVALID_ARGUMENT, "opq_cross_covariance: the index holds quantized rows, not f32 rows");
+    if (!codebook || !codes || !out_M || S == 0 || K == 0 || K > 256 || dsub == 0 || bf.n == 0)
+        return fail(SCANN_HIP_INVALID_ARGUMENT, "opq_cross_covariance: null/empty argument or num_codes not in 1..256");
+    if ((uint64_t)S * dsub != bf.dim)
+        return fail(SCANN_HIP_INVALID_ARGUMENT, "opq_cross_covariance: S * dsub is not the rows' dim " + std::to_string(bf.dim));
+    if (codes_packed4 && K > 16) return fail(SCANN_HIP_INVALID_ARGUMENT, "opq_cross_covariance: packed 4-bit codes need num_codes <= 16");
+    const uint32_t pitch = codes_packed4 ? (S + 1) / 2 : S;
+    for (uint64_t i = 0; i < bf.n; ++i)   // a code indexes the codebook slice in LDS: checked here, not in the kernel
+        for (uint32_t s = 0; s < S; ++s) {
+            const uint32_t c = codes_packed4 ? (codes[i * pitch + (s >> 1)] >> (4 * (s & 1))) & 15u : codes[i * pitch + s];
+            if (c >= K) return fail(SCANN_HIP_INVALID_ARGUMENT, "opq_cross_covariance: a code is >= num_codes");
+        }
+    std::lock_guard<std::mutex> lock(rows->mu);
+    SCANN_TRY(set_device(rows->ctx));
+    DevBuf d_cb, d_codes, d_m, d_partial;
+    SCANN_TRY(upload(d_cb, codebook, (size_t)S * K * dsub * 4));
+    SCANN_TRY(upload(d_codes, codes, (size_t)bf.n * pitch));
+    SCANN_TRY(d_m.ensure((size_t)bf.dim * bf.dim * 8));
+    SCANN_TRY(opq_cross_device(bf.rows, bf.n, bf.dim, bf.stride, d_cb.as<float>(), S, K, dsub, d_codes.as<uint8_t>(),
+                               codes_packed4, d_m.as<double>(), false, d_partial, rows->stream));
+    SCANN_HIP_CHECK(hipStreamSynchronize(rows->stream));
+    SCANN_HIP_CHECK(hipMemcpy(out_M, d_m.p, (size_t)bf.dim * bf.dim * 8, hipMemcpyDeviceToHost));
+    return SCANN_HIP_OK;
 }
 
 }  // extern "C"

@@ -26,6 +26,14 @@ int build_check(const BfIndexDev &src, const scann_hip_build_config &cfg);
 int build_txh_device(const BfIndexDev &src, const scann_hip_build_config &cfg, hipStream_t stream, BuildParts *out,
                      scann_hip_build_report *rep);
 
+// Step 3 of scann_hip_txh_build on the rows of `tv` (tv.dim = num_subspaces * dims_per_subspace): d_codebook
+// [S][K][dsub] on the device, complete on return.  The batched route when cfg and the shape allow it, else one loop per
+// subspace; both give the same bits.  warm (OPQ's alternation, opq.hip): no seeding -- the Lloyd loop runs
+// cfg.training_iterations steps from the centres d_codebook already holds, with the same centre-update arithmetic and
+// empty-cluster rule.  `rep` may be null; the two times are added to.
+int train_codebook_device(const BfIndexDev &tv, const scann_hip_build_config &cfg, bool warm, float *d_codebook, KmScratch &sc,
+                          hipStream_t stream, scann_hip_build_report *rep, float *seed_ms, float *lloyd_ms);
+
 // scann_hip_txh_build_hierarchical: step 1 by the level-order k-means tree of ktree.hip (flattened to its leaves), then the
 // same stages 2..5 on its centres and leaf assignment.  cfg.num_partitions only says "a tree" (non-zero); out->L is the
 // number of leaves found.  More than 16384 leaves: Unimplemented.  `trep` may be null.

@@ -361,9 +361,10 @@ int launch_assign_all(uint32_t dsub, dim3 grid, size_t lds, hipStream_t st, Args
     });
 }
 
-// Codebook::train with all subspaces in lockstep; codebook [S][K][dsub] on the device, complete on return
+// Codebook::train with all subspaces in lockstep; codebook [S][K][dsub] on the device, complete on return.  warm: no
+// seeding, the Lloyd loop starts from the centres d_codebook holds.
 int train_codebook_batched(const BfIndexDev &tv, const scann_hip_build_config &cfg, uint32_t dsub, uint32_t k, uint32_t G,
-                           float *d_codebook, hipStream_t st, scann_hip_build_report *rep, float *seed_ms,
+                           float *d_codebook, bool warm, hipStream_t st, scann_hip_build_report *rep, float *seed_ms,
                            float *lloyd_ms) {
     const uint32_t S = cfg.num_subspaces, K = cfg.num_codes;
     const uint64_t n = tv.n, total = n * S;
@@ -390,7 +391,7 @@ int train_codebook_batched(const BfIndexDev &tv, const scann_hip_build_config &c
     const uint32_t *state_words = d_state.as<uint32_t>();
 
     // ---- seeding: the S random streams of kmeans_plusplus_init, round by round ----
-    {
+    if (!warm) {
         std::vector<uint32_t> first(S), fb((size_t)k * S, 0u);
         std::vector<double> us((size_t)k * S, 0.0);
         for (uint32_t s = 0; s < S; ++s) {
@@ -484,9 +485,10 @@ int train_codebook_batched(const BfIndexDev &tv, const scann_hip_build_config &c
     return SCANN_HIP_OK;
 }
 
-// Codebook::train as scann.hpp's detail::train_codebook runs it: one seeding and one Lloyd loop per subspace
+// Codebook::train as scann.hpp's detail::train_codebook runs it: one seeding and one Lloyd loop per subspace.  warm: no
+// seeding, subspace s starts from the first k centres of d_codebook[s].
 int train_codebook_per_subspace(const BfIndexDev &tv, const scann_hip_build_config &cfg, uint32_t dsub, uint32_t k,
-                                float *d_codebook, KmScratch &sc, hipStream_t st, scann_hip_build_report *rep,
+                                float *d_codebook, bool warm, KmScratch &sc, hipStream_t st, scann_hip_build_report *rep,
                                 float *seed_ms, float *lloyd_ms) {
     const uint32_t S = cfg.num_subspaces, K = cfg.num_codes;
     DevBuf d_sub, d_assign;
@@ -494,7 +496,11 @@ int train_codebook_per_subspace(const BfIndexDev &tv, const scann_hip_build_conf
     SCANN_TRY(d_assign.ensure(tv.n * 4));
     auto t = std::chrono::steady_clock::now();
     for (uint32_t s = 0; s < S; ++s) {
-        SCANN_TRY(bf_kmeans_init_pp_device(tv, s * dsub, dsub, k, cfg.seed + s, cfg.simd_threshold, d_sub.as<float>(), sc, st));
+        if (warm)
+            SCANN_HIP_CHECK(hipMemcpyAsync(d_sub.p, d_codebook + (size_t)s * K * dsub, (size_t)k * dsub * 4,
+                                           hipMemcpyDeviceToDevice, st));
+        else
+            SCANN_TRY(bf_kmeans_init_pp_device(tv, s * dsub, dsub, k, cfg.seed + s, cfg.simd_threshold, d_sub.as<float>(), sc, st));
         *seed_ms += ms_since(t);
         uint32_t iters = 0;
         int conv = 0;
@@ -514,6 +520,16 @@ int train_codebook_per_subspace(const BfIndexDev &tv, const scann_hip_build_conf
 }
 
 }  // namespace
+
+int train_codebook_device(const BfIndexDev &tv, const scann_hip_build_config &cfg, bool warm, float *d_codebook, KmScratch &sc,
+                          hipStream_t st, scann_hip_build_report *rep, float *seed_ms, float *lloyd_ms) {
+    const uint32_t S = cfg.num_subspaces, dsub = tv.dim / S;
+    const uint32_t kc = (uint32_t)std::min<uint64_t>(cfg.num_codes, tv.n);
+    const uint32_t G = cb_group_size(S, kc, dsub);
+    const bool batched = cfg.batched_codebook && dsub < cfg.simd_threshold && G >= 1 && tv.n * S <= 0x7FFFFFFFull;
+    if (batched) return train_codebook_batched(tv, cfg, dsub, kc, G, d_codebook, warm, st, rep, seed_ms, lloyd_ms);
+    return train_codebook_per_subspace(tv, cfg, dsub, kc, d_codebook, warm, sc, st, rep, seed_ms, lloyd_ms);
+}
 
 int build_check(const BfIndexDev &src, const scann_hip_build_config &cfg) {
     if (src.fmt || !src.rows) return fail(SCANN_HIP_INVALID_ARGUMENT, "the index holds quantized rows, not f32 rows");
@@ -576,15 +592,9 @@ static int build_after_partition(const BfIndexDev &src, const scann_hip_build_co
     // ---- 3 codebook ----
     BfIndexDev tv = src;
     if (residual) tv.rows = d_train.as<float>();
-    const uint32_t kc = (uint32_t)std::min<uint64_t>(K, n);
     SCANN_TRY(out->codebook.ensure((size_t)S * K * dsub * 4));
-    const uint32_t G = cb_group_size(S, kc, dsub);
-    const bool batched = cfg.batched_codebook && dsub < cfg.simd_threshold && G >= 1 && n * S <= 0x7FFFFFFFull;
     t = std::chrono::steady_clock::now();
-    if (batched)
-        SCANN_TRY(train_codebook_batched(tv, cfg, dsub, kc, G, out->codebook.as<float>(), st, rep, &ms[3], &ms[4]));
-    else
-        SCANN_TRY(train_codebook_per_subspace(tv, cfg, dsub, kc, out->codebook.as<float>(), sc, st, rep, &ms[3], &ms[4]));
+    SCANN_TRY(train_codebook_device(tv, cfg, false, out->codebook.as<float>(), sc, st, rep, &ms[3], &ms[4]));
 
     // ---- 4 codes: Codebook::encode of x - centres[leaf], through the CSR permutation into packed words ----
     t = std::chrono::steady_clock::now();

@@ -5,6 +5,7 @@ library is missing or no gfx950 device is present every call raises.
 """
 import ctypes as C
 import os
+import threading
 
 import numpy as np
 
@@ -81,6 +82,7 @@ EXPORTS = [
     "scann_hip_build_config_default", "scann_hip_txh_build",
     "scann_hip_pca_train", "scann_hip_projection_arrays", "scann_hip_pca_last_stage_ms", "scann_hip_txh_build_projected",
     "scann_hip_tree_config_default", "scann_hip_txh_build_hierarchical",
+    "scann_hip_opq_config_default", "scann_hip_opq_train", "scann_hip_opq_cross_covariance", "scann_hip_opq_polar",
 ]
 
 
@@ -162,6 +164,24 @@ class BuildReport(C.Structure):
         ("partition_iterations", C.c_uint32), ("partition_converged", C.c_int32), ("partition_inertia", C.c_double),
         ("subspace_iterations", C.c_uint32 * 64), ("subspace_converged", C.c_int32 * 64),
         ("stage_ms", C.c_float * 7),
+    ]
+
+
+class OpqConfig(C.Structure):
+    """scann_hip_opq_config"""
+    _fields_ = [
+        ("num_subspaces", C.c_uint32), ("num_codes", C.c_uint32), ("opq_iterations", C.c_uint32),
+        ("training_iterations", C.c_uint32), ("inner_iterations", C.c_uint32), ("convergence_threshold", C.c_double),
+        ("seed", C.c_uint64), ("simd_threshold", C.c_uint32), ("max_samples", C.c_uint64),
+    ]
+
+
+class OpqReport(C.Structure):
+    """scann_hip_opq_report"""
+    _fields_ = [
+        ("iterations_run", C.c_uint32), ("stopped_singular", C.c_int32), ("distortion", C.c_double * 64),
+        ("sweeps", C.c_uint32 * 64), ("converged", C.c_int32 * 64), ("sigma_min_over_max", C.c_double * 64),
+        ("stage_ms", C.c_float * 5),
     ]
 
 
@@ -389,6 +409,13 @@ def load():
     L.scann_hip_pca_last_stage_ms.argtypes = [f32p]
     L.scann_hip_pca_last_stage_ms.restype = None
     L.scann_hip_txh_build_projected.argtypes = [vp, vp, C.POINTER(BuildConfig), C.POINTER(vp), C.POINTER(BuildReport)]
+    L.scann_hip_opq_config_default.argtypes = [C.POINTER(OpqConfig)]
+    L.scann_hip_opq_config_default.restype = None
+    L.scann_hip_opq_train.argtypes = [vp, C.POINTER(OpqConfig), vp, C.POINTER(vp), C.POINTER(OpqReport)]
+    L.scann_hip_opq_cross_covariance.argtypes = [vp, f32p, C.c_uint32, C.c_uint32, C.c_uint32, u8p, C.c_int,
+                                                 C.POINTER(C.c_double)]
+    L.scann_hip_opq_polar.argtypes = [vp, C.POINTER(C.c_double), C.c_uint32, f32p, C.POINTER(C.c_double), u32p,
+                                      C.POINTER(C.c_int)]
     _lib = L
     return L
 
@@ -1863,6 +1890,78 @@ def pca_last_stage_ms():
     out = np.zeros(4, np.float32)
     load().scann_hip_pca_last_stage_ms(ptr(out, f32p))
     return dict(zip(PCA_STAGES, (float(v) for v in out)))
+
+
+OPQ_STAGES = ("sample", "project", "codebook_encode", "cross_covariance", "polar")
+_opq_local = threading.local()
+
+
+def opq_config(**cfg):
+    """scann_hip_opq_config_default with the keyword arguments set on top (field names of OpqConfig)."""
+    c = OpqConfig()
+    load().scann_hip_opq_config_default(C.byref(c))
+    names = {f for f, _ in OpqConfig._fields_}
+    for key, value in cfg.items():
+        if key not in names:
+            raise TypeError("scann_hip_opq_config has no field %r" % key)
+        setattr(c, key, value)
+    return c
+
+
+def opq_train(bf_index, init=None, **cfg):
+    """scann_hip_opq_train: a PROJ_MATRIX Projection (d x d, the stored matrix is R^T) learned on the device from the rows
+    of an f32 brute-force index by the alternation trainer.opq_rotation states; `init`: a d x d PROJ_MATRIX Projection
+    (None: the identity); **cfg: fields of OpqConfig (num_subspaces and num_codes are required).  Returns (projection,
+    report): report holds iterations_run, stopped_singular, and per completed-or-stopped iteration distortion, sweeps,
+    converged and sigma_min_over_max, and stage_ms ({stage: milliseconds}, OPQ_STAGES)."""
+    c = opq_config(**cfg)
+    rep, h = OpqReport(), vp()
+    check(load().scann_hip_opq_train(bf_index.h, C.byref(c), init.h if init is not None else None, C.byref(h),
+                                     C.byref(rep)))
+    nt = min(int(rep.iterations_run) + int(rep.stopped_singular), 64)
+    stage_ms = dict(zip(OPQ_STAGES, (float(v) for v in rep.stage_ms)))
+    _opq_local.stage_ms = stage_ms
+    return Projection.from_handle(h), dict(
+        iterations_run=int(rep.iterations_run), stopped_singular=bool(rep.stopped_singular),
+        distortion=[float(v) for v in rep.distortion[:nt]], sweeps=[int(v) for v in rep.sweeps[:nt]],
+        converged=[bool(v) for v in rep.converged[:nt]],
+        sigma_min_over_max=[float(v) for v in rep.sigma_min_over_max[:nt]], stage_ms=stage_ms)
+
+
+def opq_last_stage_ms():
+    """{stage: host-clock milliseconds} of this thread's last opq_train (OPQ_STAGES)"""
+    return dict(getattr(_opq_local, "stage_ms", dict.fromkeys(OPQ_STAGES, 0.0)))
+
+
+def opq_cross_covariance(bf_index, codebook, codes, packed4=False):
+    """scann_hip_opq_cross_covariance: M = X^T Yhat, f64 [d, d], of the rows X of an f32 brute-force index and the rows
+    Yhat decoded from `codes` ([n, S] bytes, or [n, ceil(S / 2)] packed nibbles, low nibble = even subspace) through
+    `codebook` [S, K, dsub]."""
+    cb = f32(codebook)
+    S, K, dsub = cb.shape
+    n, d = bf_index.size(), bf_index.dimensionality()
+    cd = np.ascontiguousarray(codes, np.uint8)
+    if cd.shape != (n, (S + 1) // 2 if packed4 else S):
+        raise ValueError("codes is %s for n = %d, S = %d, packed4 = %s" % (cd.shape, n, S, bool(packed4)))
+    out = np.zeros((d, d), np.float64)
+    check(load().scann_hip_opq_cross_covariance(bf_index.h, ptr(cb, f32p), S, K, dsub, ptr(cd, u8p), int(bool(packed4)),
+                                                ptr(out, C.POINTER(C.c_double))))
+    return out
+
+
+def opq_polar(M, device=0):
+    """scann_hip_opq_polar: (R f32 [d, d] = U V^T, info) of M = U S V^T by the one-sided Jacobi solve on the device; info
+    holds singular (f64 [d], descending), sweeps and converged."""
+    m = np.ascontiguousarray(M, np.float64)
+    d = m.shape[0]
+    if m.shape != (d, d):
+        raise ValueError("M is %s, not square" % (m.shape,))
+    R, sv = np.zeros((d, d), np.float32), np.zeros(d, np.float64)
+    sweeps, conv = C.c_uint32(0), C.c_int(0)
+    f64p = C.POINTER(C.c_double)
+    check(load().scann_hip_opq_polar(context(device), ptr(m, f64p), d, ptr(R, f32p), ptr(sv, f64p),
+                                     C.cast(C.byref(sweeps), u32p), C.byref(conv)))
+    return R, dict(singular=sv, sweeps=int(sweeps.value), converged=bool(conv.value))
 
 
 def bf_assign_nearest(index, centers, want_dist=True):

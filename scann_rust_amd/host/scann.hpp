@@ -1288,6 +1288,18 @@ private:
     scann_hip_projection *h_ = nullptr;
 };
 
+struct OpqConfig {                       // OpqConfig::new (projection/opq.rs) and the codebook step's fields
+    size_t num_subspaces = 8, num_codes = 256;
+    size_t opq_iterations = 20;          // at most 64
+    size_t training_iterations = 25;     // Lloyd steps of the first codebook
+    size_t inner_iterations = 1;         // Lloyd steps per later iteration, from the previous codebook
+    double convergence_threshold = 1e-5;
+    uint64_t seed = 42;
+    uint64_t max_samples = 0;            // 0 = every row
+    OpqConfig() = default;
+    OpqConfig(size_t subspaces, size_t codes) : num_subspaces(subspaces), num_codes(codes) {}
+};
+
 class Projection {
 public:
     // RandomOrthogonalProjection / GaussianRandomProjection / OpqProjection: no mean
@@ -1355,6 +1367,27 @@ public:
                                   eigenvalues ? eigenvalues->data() : nullptr, nullptr, &sw, &conv));
         if (sweeps) *sweeps = sw;
         if (converged) *converged = conv != 0;
+        return DeviceProjection(h);
+    }
+    // OpqProjection::train_on_vecs as the full alternation, on the device (scann_hip_opq_train: the rule is in
+    // scann_hip.h) from the resident rows of a brute-force searcher: a Matrix projection of in_dim x in_dim.  `init`: a
+    // Matrix projection of the same shape to start from (default: the identity); `report`: distortion per iteration,
+    // the solves' sweeps, the stop flag.
+    static DeviceProjection train_opq_on_device(const BruteForceSearcher &source, const OpqConfig &config,
+                                                const DeviceProjection *init = nullptr,
+                                                scann_hip_opq_report *report = nullptr) {
+        scann_hip_opq_config c;
+        scann_hip_opq_config_default(&c);
+        c.num_subspaces = (uint32_t)config.num_subspaces;
+        c.num_codes = (uint32_t)config.num_codes;
+        c.opq_iterations = (uint32_t)config.opq_iterations;
+        c.training_iterations = (uint32_t)config.training_iterations;
+        c.inner_iterations = (uint32_t)config.inner_iterations;
+        c.convergence_threshold = config.convergence_threshold;
+        c.seed = config.seed;
+        c.max_samples = config.max_samples;
+        scann_hip_projection *h = nullptr;
+        check(scann_hip_opq_train(source.handle(), &c, init ? init->handle() : nullptr, &h, report));
         return DeviceProjection(h);
     }
     static Projection from_device(const DeviceProjection &p) {

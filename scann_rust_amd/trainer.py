@@ -158,6 +158,48 @@ def pca_projection(X, out_dim, max_samples=None, seed=42):
     return np.ascontiguousarray(V[:, order].T, np.float32), mean.astype(np.float32)
 
 
+def opq_rotation(X, S, K, iterations=20, training_iterations=25, inner_iterations=1, seed=42, max_samples=None,
+                 init=None):
+    """The rule of hip.opq_train (scann_hip.h "OPQ training on the device") on the host, in f64: the non-parametric OPQ
+    alternation of Ge et al. -- project Y = X R, train (first iteration) or refine (later ones: inner_iterations Lloyd
+    steps from the previous centres, no seeding) a codebook of S subspaces x K codes on Y, encode, M = X^T Yhat, R = U V^T
+    of M's SVD (numpy.linalg.svd here, one-sided Jacobi on the device); sigma_min <= 2^-40 sigma_max stops the training
+    with the previous R.  The k-means seeding is this module's (`kmeans`), not the device's, so a device run is compared
+    by its distortion trace, not element-wise.  Returns (matrix f32 [d, d] = R^T, the [out][in] array of
+    hip.Projection(PROJ_MATRIX, ...), distortion list)."""
+    X = np.ascontiguousarray(X, np.float32)
+    n, d = X.shape
+    if d % S != 0:
+        raise ValueError("InvalidArgument: dimensionality %d must be divisible by num_subspaces %d" % (d, S))
+    if max_samples is not None and n > max_samples:
+        X = X[(synth.splitmix64(seed ^ 0x0B9, 0, max_samples) % np.uint64(n)).astype(np.int64)]
+    dsub, X64 = d // S, X.astype(np.float64)
+    R = np.eye(d) if init is None else np.asarray(init, np.float64).T
+    cb, distortion = None, []
+    for t in range(iterations):
+        Y = X64 @ R
+        Yhat = np.empty_like(Y)
+        if cb is None:
+            cb = [kmeans(Y[:, s * dsub:(s + 1) * dsub], K, iters=training_iterations, seed=seed + s)[0].astype(np.float64)
+                  for s in range(S)]
+        for s in range(S):
+            ys = Y[:, s * dsub:(s + 1) * dsub]
+            for step in range(inner_iterations + 1 if t else 1):   # the last pass is the encode
+                a = ((ys[:, None, :] - cb[s][None]) ** 2).sum(2).argmin(1)
+                if t and step < inner_iterations:
+                    cnt = np.bincount(a, minlength=cb[s].shape[0])
+                    sums = np.zeros_like(cb[s])
+                    np.add.at(sums, a, ys)
+                    cb[s][cnt > 0] = sums[cnt > 0] / cnt[cnt > 0, None]
+            Yhat[:, s * dsub:(s + 1) * dsub] = cb[s][a]
+        distortion.append(float(((Y - Yhat) ** 2).sum() / X64.shape[0]))
+        U, sv, Vt = np.linalg.svd(X64.T @ Yhat)
+        if sv[-1] <= np.ldexp(sv[0], -40):
+            break
+        R = U @ Vt
+    return np.ascontiguousarray(R.T, np.float32), distortion
+
+
 def random_orthogonal(in_dim, out_dim, seed):
     """RandomOrthogonalProjection (projection/random.rs): the Q factor of a Gaussian matrix; out_dim orthonormal rows of
     in_dim.  Returns matrix f32 [out_dim, in_dim].  (The reference's RNG stream is not reproducible: SURVEY F10.)"""
