@@ -1585,6 +1585,60 @@ int scann_hip_txh_build_projected(scann_hip_index *rows, const scann_hip_project
                                   const scann_hip_build_config *cfg, scann_hip_index **out_index,
                                   scann_hip_build_report *out_report);
 
+/* ---- sparse brute force -----------------------------------------------------------------
+ * SparseDataset + BruteForceSearcher (data_format/dataset.rs, brute_force/mod.rs) for rows and queries given as index /
+ * value lists: rows live on the device in CSR (row_offsets u64[n + 1], dims u32[nnz], vals f32[nnz], one f32 squared
+ * norm and one u32 length per row) and a batch of sparse queries is scored against all of them.
+ * q is the query, x the row, I the dimensions stored in both, visited in ascending order:
+ *   SCANN_HIP_DOT_PRODUCT              s = 0.0f; s += q[d] * x[d] over I (unfused); distance = -s
+ *   SCANN_HIP_COSINE                   nq = sqrtf(|q|^2), nx = sqrtf(|x|^2) (sequential f32 sums in stored order); either 0 ->
+ *                                      1.0f - 0.0f, else 1.0f - s / (nq * nx)        (one_to_one.rs:473-490)
+ *   SCANN_HIP_SPARSE_JACCARD           both lists empty -> 0.0f, else 1.0f - (float)|I| / (float)(|q| + |x| - |I|); stored
+ *                                      zeros count, the measure reads indices only   (sparse.rs:17-32)
+ *   SCANN_HIP_SPARSE_DICE              both lists empty -> 0.0f, else 1.0f - (2.0f * (float)|I|) / (float)(|q| + |x|)
+ *   SCANN_HIP_SPARSE_NONZERO_INTERSECT c = |{d in I : q[d] != 0 && x[d] != 0}|; distance = (float)(-c), +0.0 at c = 0
+ * The three SCANN_HIP_SPARSE_* constants are accepted by scann_hip_sparse_create only.  SquaredL2 / L2 / L1 ->
+ * Unimplemented: their reference form sums over the UNION of the two index lists, an order the intersection-only scan
+ * cannot reproduce.
+ * scann_hip_sparse_create: host arrays; row_offsets[0] == 0, nnz = row_offsets[n]; dimensionality <= 2^32 - 1.  Checked ON
+ * THE DEVICE, InvalidArgument if one fails: offsets monotone, dims strictly ascending inside a row and below
+ * dimensionality, every value finite.  n == 0 is legal; n >= 2^32 - 1 -> OutOfRange.
+ * Results of a search: the k smallest rows by (f32_to_ordered(distance), row) -- the total order of every other path's
+ * keys: ties go to the lower row -- ascending, out_count[q] = min(k, rows allowed).  Slots past out_count hold index
+ * 0xFFFFFFFF and distance +NaN.  1 <= k <= SCANN_HIP_SPARSE_MAX_K (above: Unimplemented); k > n is legal.
+ * Queries: q_offsets u64[nq + 1] ascending (entries are relative to q_offsets[0]), dims strictly ascending inside a query
+ * and below dimensionality, values finite: checked on the host, InvalidArgument.  A query of more than
+ * SCANN_HIP_SPARSE_TILE_SLOTS entries -> Unimplemented.
+ * allow_bitmap (NULL: no filter): one bitmap for the call, bit j of word j / 64 allows row j, rows at or past
+ * allow_bitmap_bits are not allowed; the answer is that of an unfiltered search over the allowed rows, indices unchanged.
+ * scann_hip_sparse_distances: the scan and the measure's epilogue alone, out [nq][n] f32 (as scann_hip_bf_distances).
+ * scann_hip_sparse_last_kernel_ms: out_ms[0] the scan, out_ms[1] the merge of the handle's last search (device events; 0
+ * before any).  scann_hip_sparse_last_plan: out[0] query tiles, out[1] row chunks of the last scan; out[2] CSR elements
+ * probed, out[3] hash-map probes made and out[4] elements found in the map by it, all three 0 unless
+ * scann_hip_sparse_enable_stats(index, 1) came first.  out holds 5 values.
+ * One call at a time per handle (serialised inside).  Every search entry synchronises. */
+typedef struct scann_hip_sparse_index scann_hip_sparse_index;
+#define SCANN_HIP_SPARSE_JACCARD 100
+#define SCANN_HIP_SPARSE_DICE 101
+#define SCANN_HIP_SPARSE_NONZERO_INTERSECT 102
+#define SCANN_HIP_SPARSE_TILE_QUERIES 16 /* queries whose values one workgroup's LDS panel holds */
+#define SCANN_HIP_SPARSE_TILE_SLOTS 1024 /* panel slots: the sum of a tile's query lengths may not exceed it */
+#define SCANN_HIP_SPARSE_MAP_SIZE 2048   /* entries of the LDS dimension -> slot map; home of d is d % MAP_SIZE */
+#define SCANN_HIP_SPARSE_MAX_K 256
+int scann_hip_sparse_create(scann_hip_ctx *ctx, const uint64_t *row_offsets, const uint32_t *dims, const float *vals,
+                            uint64_t n, uint32_t dimensionality, int measure, scann_hip_sparse_index **out);
+void scann_hip_sparse_destroy(scann_hip_sparse_index *index);
+uint64_t scann_hip_sparse_size(const scann_hip_sparse_index *index);
+uint64_t scann_hip_sparse_device_bytes(const scann_hip_sparse_index *index);
+int scann_hip_sparse_search_batched(scann_hip_sparse_index *index, const uint64_t *q_offsets, const uint32_t *q_dims,
+                                    const float *q_vals, uint32_t nq, uint32_t k, const uint64_t *allow_bitmap,
+                                    uint64_t allow_bitmap_bits, uint32_t *out_idx, float *out_dist, uint32_t *out_count);
+int scann_hip_sparse_distances(scann_hip_sparse_index *index, const uint64_t *q_offsets, const uint32_t *q_dims,
+                               const float *q_vals, uint32_t nq, float *out);
+void scann_hip_sparse_last_kernel_ms(scann_hip_sparse_index *index, float *out_ms);
+void scann_hip_sparse_enable_stats(scann_hip_sparse_index *index, int enable);
+void scann_hip_sparse_last_plan(scann_hip_sparse_index *index, uint64_t *out);
+
 /* ---- introspection ------------------------------------------------------------- */
 uint64_t scann_hip_index_size(const scann_hip_index *index);          /* Searcher::dataset_size */
 uint32_t scann_hip_index_dimensionality(const scann_hip_index *index);/* Searcher::dimensionality */

@@ -29,6 +29,11 @@ ATTR_I64, ATTR_F32 = 1, 2      # SCANN_HIP_ATTR_*: column types of an AttrTable
 ATTR_ROW_INDEX = 0xFFFFFFFF    # SCANN_HIP_ATTR_ROW_INDEX: the pseudo-column whose value at row j is j (RangeFilter)
 ATTR_MAX_CLAUSES = 8           # SCANN_HIP_ATTR_MAX_CLAUSES: clauses of one range call
 RANGE_TILE_BITS = 1024         # SCANN_HIP_RANGE_TILE_BITS: rows whose values a workgroup of the range kernel holds in registers
+SPARSE_JACCARD, SPARSE_DICE, SPARSE_NONZERO_INTERSECT = 100, 101, 102   # SCANN_HIP_SPARSE_*: measures of a SparseIndex only
+SPARSE_TILE_QUERIES = 16       # SCANN_HIP_SPARSE_TILE_QUERIES: queries whose values one workgroup's LDS panel holds
+SPARSE_TILE_SLOTS = 1024       # SCANN_HIP_SPARSE_TILE_SLOTS: the sum of a tile's query lengths, and the longest query served
+SPARSE_MAP_SIZE = 2048         # SCANN_HIP_SPARSE_MAP_SIZE: entries of the LDS dimension -> slot map; home of d is d % SPARSE_MAP_SIZE
+SPARSE_MAX_K = 256             # SCANN_HIP_SPARSE_MAX_K
 
 _CODE_NAMES = {
     0: "Ok", 1: "Cancelled", 2: "Unknown", 3: "InvalidArgument", 4: "DeadlineExceeded",
@@ -83,6 +88,9 @@ EXPORTS = [
     "scann_hip_pca_train", "scann_hip_projection_arrays", "scann_hip_pca_last_stage_ms", "scann_hip_txh_build_projected",
     "scann_hip_tree_config_default", "scann_hip_txh_build_hierarchical",
     "scann_hip_opq_config_default", "scann_hip_opq_train", "scann_hip_opq_cross_covariance", "scann_hip_opq_polar",
+    "scann_hip_sparse_create", "scann_hip_sparse_destroy", "scann_hip_sparse_size", "scann_hip_sparse_device_bytes",
+    "scann_hip_sparse_search_batched", "scann_hip_sparse_distances", "scann_hip_sparse_last_kernel_ms",
+    "scann_hip_sparse_enable_stats", "scann_hip_sparse_last_plan",
 ]
 
 
@@ -416,6 +424,21 @@ def load():
                                                  C.POINTER(C.c_double)]
     L.scann_hip_opq_polar.argtypes = [vp, C.POINTER(C.c_double), C.c_uint32, f32p, C.POINTER(C.c_double), u32p,
                                       C.POINTER(C.c_int)]
+    L.scann_hip_sparse_create.argtypes = [vp, u64p, u32p, f32p, C.c_uint64, C.c_uint32, C.c_int, C.POINTER(vp)]
+    L.scann_hip_sparse_destroy.argtypes = [vp]
+    L.scann_hip_sparse_destroy.restype = None
+    L.scann_hip_sparse_size.argtypes = [vp]
+    L.scann_hip_sparse_size.restype = C.c_uint64
+    L.scann_hip_sparse_device_bytes.argtypes = [vp]
+    L.scann_hip_sparse_device_bytes.restype = C.c_uint64
+    L.scann_hip_sparse_search_batched.argtypes = [vp, u64p, u32p, f32p, C.c_uint32, C.c_uint32, u64p, C.c_uint64, u32p, f32p, u32p]
+    L.scann_hip_sparse_distances.argtypes = [vp, u64p, u32p, f32p, C.c_uint32, f32p]
+    L.scann_hip_sparse_last_kernel_ms.argtypes = [vp, f32p]
+    L.scann_hip_sparse_last_kernel_ms.restype = None
+    L.scann_hip_sparse_enable_stats.argtypes = [vp, C.c_int]
+    L.scann_hip_sparse_enable_stats.restype = None
+    L.scann_hip_sparse_last_plan.argtypes = [vp, u64p]
+    L.scann_hip_sparse_last_plan.restype = None
     _lib = L
     return L
 
@@ -1054,6 +1077,108 @@ def allow_bitmaps_from_tokens(indices, tokens, num_datapoints, token_lists, stri
                                                      idx.size, int(num_datapoints), ptr(qt, u64p) if qt.size else None,
                                                      ptr(off, u64p), nq, stride, ptr(out, u64p) if out.size else None))
     return out
+
+
+def sparse_csr(lists_or_offsets, dims=None, vals=None):
+    """(offsets uint64[n + 1], dims uint32[nnz], vals float32[nnz]) of CSR arrays (offsets, dims, vals), or of a list
+    of per-row (dims, vals) pairs"""
+    if dims is None:
+        pairs = [(np.ascontiguousarray(d, np.uint32).ravel(), f32(v).ravel()) for d, v in lists_or_offsets]
+        for d, v in pairs:
+            if d.size != v.size:
+                raise ValueError("one value per dimension: %d dims, %d values" % (d.size, v.size))
+        off = np.concatenate([[0], np.cumsum([d.size for d, _ in pairs])]).astype(np.uint64)
+        return (off, np.concatenate([d for d, _ in pairs] + [np.zeros(0, np.uint32)]),
+                np.concatenate([v for _, v in pairs] + [np.zeros(0, np.float32)]))
+    off = np.ascontiguousarray(lists_or_offsets, np.uint64).ravel()
+    d, v = np.ascontiguousarray(dims, np.uint32).ravel(), f32(vals).ravel()
+    if off.size == 0 or d.size != v.size or int(off[-1]) - int(off[0]) != d.size:
+        raise ValueError("CSR arrays disagree: %d offsets ending at %s, %d dims, %d values"
+                         % (off.size, off[-1] if off.size else None, d.size, v.size))
+    return off, d, v
+
+
+class SparseIndex:
+    """Owns one scann_hip_sparse_index: sparse rows in CSR on the device, searched exhaustively by sparse queries
+    (DESIGN.md 3.3j).  SparseIndex(offsets, dims, vals, dimensionality=D, measure=...) takes CSR arrays;
+    SparseIndex.from_rows(rows, ...) a list of per-row (dims, vals) pairs.  Queries are given the same two ways."""
+
+    def __init__(self, offsets, dims, vals, dimensionality, measure=DOT_PRODUCT, device=0):
+        off, d, v = sparse_csr(offsets, dims, vals)
+        self.h = vp()
+        self.n, self.dimensionality, self.measure = off.size - 1, int(dimensionality), measure
+        check(load().scann_hip_sparse_create(context(device), ptr(off, u64p), ptr(d, u32p) if d.size else None,
+                                             ptr(v, f32p) if v.size else None, self.n, self.dimensionality, measure,
+                                             C.byref(self.h)))
+
+    @classmethod
+    def from_rows(cls, rows, dimensionality, measure=DOT_PRODUCT, device=0):
+        return cls(*sparse_csr(rows), dimensionality=dimensionality, measure=measure, device=device)
+
+    def close(self):
+        if self.h:
+            load().scann_hip_sparse_destroy(self.h)
+            self.h = None
+
+    destroy = close
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def size(self):
+        return int(load().scann_hip_sparse_size(self.h))
+
+    def device_bytes(self):
+        return int(load().scann_hip_sparse_device_bytes(self.h))
+
+    @staticmethod
+    def _queries(queries):
+        off, d, v = sparse_csr(*queries) if isinstance(queries, tuple) else sparse_csr(queries)
+        return off, d, v, (ptr(off, u64p), ptr(d, u32p) if d.size else None, ptr(v, f32p) if v.size else None, off.size - 1)
+
+    def search_batched(self, queries, k, allow=None, allow_bits=None):
+        """queries: (offsets, dims, vals) or a list of (dims, vals) pairs.  allow: one uint64 bitmap for the batch (bit j
+        allows row j; rows at or past allow_bits, default all the words given, are not allowed).  (idx [nq, k] uint32,
+        dist [nq, k] float32, count [nq] uint32); slots past count hold 0xFFFFFFFF / NaN."""
+        off, d, v, args = self._queries(queries)
+        nq = args[3]
+        idx, dist = np.empty((nq, k), np.uint32), np.empty((nq, k), np.float32)
+        cnt = np.zeros(nq, np.uint32)
+        words = None if allow is None else np.ascontiguousarray(allow, np.uint64).ravel()
+        bits = 0 if words is None else (words.size * 64 if allow_bits is None else int(allow_bits))
+        if words is not None and bits > words.size * 64:
+            raise ValueError("allow_bits %d exceeds the %d bits given" % (bits, words.size * 64))
+        if words is not None and words.size == 0:
+            words = np.zeros(1, np.uint64)
+        check(load().scann_hip_sparse_search_batched(self.h, *args, int(k), ptr(words, u64p), bits, ptr(idx, u32p),
+                                                     ptr(dist, f32p), ptr(cnt, u32p)))
+        return idx, dist, cnt
+
+    def distances(self, queries):
+        """[nq, n] float32: the scan and the measure's epilogue alone"""
+        off, d, v, args = self._queries(queries)
+        out = np.empty((args[3], self.n), np.float32)
+        if out.size or args[3]:
+            check(load().scann_hip_sparse_distances(self.h, *args, ptr(out if out.size else np.empty(1, np.float32), f32p)))
+        return out
+
+    def last_kernel_ms(self):
+        """(scan ms, merge ms) of the last search"""
+        ms = np.zeros(2, np.float32)
+        load().scann_hip_sparse_last_kernel_ms(self.h, ptr(ms, f32p))
+        return float(ms[0]), float(ms[1])
+
+    def enable_stats(self, enable=True):
+        load().scann_hip_sparse_enable_stats(self.h, int(bool(enable)))
+
+    def last_plan(self):
+        """{'tiles', 'chunks', 'elements', 'probes', 'hits'} of the last scan (the last three only after enable_stats)"""
+        p = np.zeros(5, np.uint64)
+        load().scann_hip_sparse_last_plan(self.h, ptr(p, u64p))
+        return dict(zip(("tiles", "chunks", "elements", "probes", "hits"), (int(x) for x in p)))
 
 
 def _attr_columns(n, columns):
