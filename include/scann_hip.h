@@ -1616,6 +1616,17 @@ int scann_hip_txh_build_projected(scann_hip_index *rows, const scann_hip_project
  * before any).  scann_hip_sparse_last_plan: out[0] query tiles, out[1] row chunks of the last scan; out[2] CSR elements
  * probed, out[3] hash-map probes made and out[4] elements found in the map by it, all three 0 unless
  * scann_hip_sparse_enable_stats(index, 1) came first.  out holds 5 values.
+ * scann_hip_sparse_build_postings: a second layout on the handle, built on the device from its CSR arrays (which stay):
+ * rows are cut into blocks of SCANN_HIP_SPARSE_BLOCK_ROWS; a block holds a directory of the ascending dimensions its rows
+ * store, and per dimension a posting list (u16 row inside the block, f32 value), ascending by row.  Idempotent; n == 0
+ * gives zero blocks; more than 2^32 - 2 stored entries -> Unimplemented.  From then on scann_hip_sparse_search_batched
+ * and scann_hip_sparse_distances on the handle walk only the lists of the query's dimensions.  One wave owns each row's
+ * accumulator and takes the query's terms in ascending dimension, so every sum is the same sequence of f32 operations:
+ * the results are those of a handle without postings, bit for bit, and every check above holds unchanged.
+ * scann_hip_sparse_last_plan describes exhaustive scans and is all 0 after a posting-list one.
+ * scann_hip_sparse_postings_info: out[0] blocks (0: no postings, or n == 0), out[1] rows per block, out[2] bytes of the
+ * postings and directories, out[3] block chunks of the last posting-list search, out[4] postings visited by it (0 unless
+ * scann_hip_sparse_enable_stats(index, 1) came first).  out holds 5 values.
  * One call at a time per handle (serialised inside).  Every search entry synchronises. */
 typedef struct scann_hip_sparse_index scann_hip_sparse_index;
 #define SCANN_HIP_SPARSE_JACCARD 100
@@ -1625,6 +1636,9 @@ typedef struct scann_hip_sparse_index scann_hip_sparse_index;
 #define SCANN_HIP_SPARSE_TILE_SLOTS 1024 /* panel slots: the sum of a tile's query lengths may not exceed it */
 #define SCANN_HIP_SPARSE_MAP_SIZE 2048   /* entries of the LDS dimension -> slot map; home of d is d % MAP_SIZE */
 #define SCANN_HIP_SPARSE_MAX_K 256
+#ifndef SCANN_HIP_SPARSE_BLOCK_ROWS       /* (a tuning build of the library may set another) */
+#define SCANN_HIP_SPARSE_BLOCK_ROWS 16384 /* rows of a posting-list block: a power of two <= 65536, 4 B of LDS each */
+#endif
 int scann_hip_sparse_create(scann_hip_ctx *ctx, const uint64_t *row_offsets, const uint32_t *dims, const float *vals,
                             uint64_t n, uint32_t dimensionality, int measure, scann_hip_sparse_index **out);
 void scann_hip_sparse_destroy(scann_hip_sparse_index *index);
@@ -1638,6 +1652,8 @@ int scann_hip_sparse_distances(scann_hip_sparse_index *index, const uint64_t *q_
 void scann_hip_sparse_last_kernel_ms(scann_hip_sparse_index *index, float *out_ms);
 void scann_hip_sparse_enable_stats(scann_hip_sparse_index *index, int enable);
 void scann_hip_sparse_last_plan(scann_hip_sparse_index *index, uint64_t *out);
+int scann_hip_sparse_build_postings(scann_hip_sparse_index *index);
+void scann_hip_sparse_postings_info(scann_hip_sparse_index *index, uint64_t *out);
 
 /* ---- introspection ------------------------------------------------------------- */
 uint64_t scann_hip_index_size(const scann_hip_index *index);          /* Searcher::dataset_size */

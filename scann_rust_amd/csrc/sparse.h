@@ -1,5 +1,6 @@
 // sparse.h -- the host side of the sparse brute-force scan (sparse.hip): constants of the LDS panel,
-// the checks made on a batch of sparse queries, the greedy packing of queries into tiles and the row-chunk rule.
+// the checks made on a batch of sparse queries, the greedy packing of queries into tiles and the row-chunk rule, and
+// the constants, LDS size and block-chunk rule of the posting-list scan (sparse_inv.hip).
 // Plain C++ with no device code and no HIP types, so that it can be compiled into a stand-alone host program.
 #pragma once
 #include <math.h>
@@ -52,6 +53,38 @@ static inline void sparse_chunks(uint64_t n, uint32_t max_chunks, uint32_t *chun
     rows = (rows + kSparseRoundRows - 1) / kSparseRoundRows * kSparseRoundRows;
     *chunk_rows = (uint32_t)rows;
     *chunks = n ? (uint32_t)((n + rows - 1) / rows) : 0u;
+}
+
+// ---- the posting-list scan (sparse_inv.hip) --------------------------------------------------------------------------
+constexpr uint32_t kSparseBlockRows = SCANN_HIP_SPARSE_BLOCK_ROWS;        // rows of a block: one LDS accumulator each
+constexpr uint32_t kSparseWaveRows = kSparseBlockRows / kSparseWaves;     // the rows of a block one wave owns
+static_assert((kSparseBlockRows & (kSparseBlockRows - 1)) == 0 && kSparseBlockRows <= 65536, "a row inside its block is a u16");
+static_assert(kSparseWaveRows >= 64 && kSparseWaveRows % 64 == 0, "a wave's epilogue takes its rows 64 at a time");
+
+// Append-buffer entries of the posting-list scan's one query: the k kept keys and the keys of one epilogue round (one
+// row per thread), a power of two.
+static inline uint32_t sparse_inv_select_cap(uint32_t k) {
+    uint32_t c = 1;
+    while (c < k + kSparseThreads) c <<= 1;
+    return c;
+}
+
+// Dynamic LDS of the posting-list scan: the block's accumulators; per query term its posting range in the block and
+// the query's value; with a selection the append buffer.
+static inline size_t sparse_inv_lds(uint32_t k, bool select) {
+    size_t b = (size_t)kSparseBlockRows * 4 + (size_t)kSparseSlots * 12;
+    if (select) b += (size_t)sparse_inv_select_cap(k) * 8;
+    return b;
+}
+
+// Blocks per chunk and chunks of a posting-list scan over `blocks` blocks: chunks are whole blocks, and a search keeps
+// chunks * k within the merge kernel's LDS sort exactly as sparse_chunks does.
+static inline void sparse_inv_chunks(uint32_t blocks, uint32_t max_chunks, uint32_t *chunk_blocks, uint32_t *chunks) {
+    if (max_chunks < 1) max_chunks = 1;
+    uint32_t per = (blocks + max_chunks - 1) / max_chunks;
+    if (per < 1) per = 1;
+    *chunk_blocks = per;
+    *chunks = (blocks + per - 1) / per;
 }
 
 // The checks of a batch of sparse queries (ascending offsets; per query strictly ascending dims below dimensionality and

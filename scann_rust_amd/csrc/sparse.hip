@@ -18,13 +18,14 @@
 //                 running threshold, sorted and cut to k whenever a further round could overflow it; the k best keys of
 //                 the chunk go to partial[query][chunk][k].
 //   sparse_merge_kernel     one workgroup per query: sorts the chunk partials in LDS, writes the final rows.
+// A handle that has postings (scann_hip_sparse_build_postings) keeps this driver and the merge and swaps the scan for
+// sparse_inv.hip's; what the two scans share (the handle, the epilogue, the LDS selection) is in sparse_dev.h.
 #include <memory>
-#include <mutex>
 #include <vector>
 
 #include "comm.h"   // ctx_device
 #include "launch.h"
-#include "sparse.h"
+#include "sparse_dev.h"
 
 namespace scann {
 namespace {
@@ -90,27 +91,6 @@ __global__ __launch_bounds__(kPrepThreads) void sparse_prepare_kernel(const uint
 // non-zero (NonZeroIntersect) -- products of these, summed in f32, are the sum or the exact count (<= 1024 < 2^24)
 __device__ __forceinline__ float sparse_term(int mode, float v) { return mode == 0 ? v : mode == 1 ? 1.0f : (v != 0.0f ? 1.0f : 0.0f); }
 
-__device__ __forceinline__ float sparse_distance(int measure, float acc, uint32_t xlen, float xn2, uint32_t qlen, float qn2) {
-    switch (measure) {
-        case SCANN_HIP_COSINE: {
-            const float nq = sqrtf(qn2), nx = sqrtf(xn2);
-            const float sim = (nq == 0.0f || nx == 0.0f) ? 0.0f : acc / (nq * nx);
-            return 1.0f - sim;
-        }
-        case SCANN_HIP_SPARSE_JACCARD: {
-            if (qlen == 0 && xlen == 0) return 0.0f;
-            const uint32_t c = (uint32_t)acc;
-            return 1.0f - (float)c / (float)((uint64_t)qlen + xlen - c);
-        }
-        case SCANN_HIP_SPARSE_DICE: {
-            if (qlen == 0 && xlen == 0) return 0.0f;
-            return 1.0f - (2.0f * (float)(uint32_t)acc) / (float)((uint64_t)qlen + xlen);
-        }
-        case SCANN_HIP_SPARSE_NONZERO_INTERSECT: return (float)(-(int32_t)acc);
-        default: return -acc;
-    }
-}
-
 // slot of dimension d (one is always free: the map is at most half full); false on a miss.  *probes counts key reads.
 __device__ __forceinline__ bool sparse_probe(const uint32_t *keys, uint32_t d, uint32_t *pos, uint32_t *probes) {
     uint32_t h = d & kMapMask;
@@ -129,41 +109,6 @@ __device__ __forceinline__ bool sparse_probe(const uint32_t *keys, uint32_t d, u
 __device__ __forceinline__ uint64_t low_mask(uint32_t bits) { return bits >= 64 ? ~0ull : (1ull << bits) - 1ull; }
 // lanes of a fetch that starts at element `base` which lie before element `o`
 __device__ __forceinline__ uint32_t lanes_before(uint64_t o, uint64_t base) { return o <= base ? 0u : (o - base >= 64 ? 64u : (uint32_t)(o - base)); }
-
-// kSparseQT buffers of 2^cap_log keys each, sorted ascending side by side: one barrier per pass for all of them
-__device__ void sparse_sort_buffers(uint64_t *buf, uint32_t cap_log) {
-    const uint32_t half_log = cap_log - 1, pairs = kSparseQT << half_log;
-    for (uint32_t lk = 1; lk <= cap_log; ++lk) {
-        for (int lj = (int)lk - 1; lj >= 0; --lj) {
-            for (uint32_t i = threadIdx.x; i < pairs; i += kSparseThreads) {
-                const uint32_t b = i >> half_log, ii = i & ((1u << half_log) - 1);
-                const uint32_t lo = ((ii >> lj) << (lj + 1)) | (ii & ((1u << lj) - 1)), hi = lo + (1u << lj);
-                uint64_t *p = buf + ((size_t)b << cap_log);
-                const uint64_t x = p[lo], y = p[hi];
-                const bool up = ((lo >> lk) & 1u) == 0;
-                if ((x > y) == up) {
-                    p[lo] = y;
-                    p[hi] = x;
-                }
-            }
-            __syncthreads();
-        }
-    }
-}
-
-// pads every buffer past its count, sorts, cuts to k and moves the thresholds.  Every thread of the workgroup calls.
-__device__ void sparse_compact(uint64_t *buf, uint32_t cap_log, uint32_t k, uint32_t *cnt, uint64_t *thr) {
-    for (uint32_t i = threadIdx.x; i < (kSparseQT << cap_log); i += kSparseThreads)
-        if ((i & ((1u << cap_log) - 1)) >= cnt[i >> cap_log]) buf[i] = SCANN_KEY_MAX;
-    __syncthreads();
-    sparse_sort_buffers(buf, cap_log);
-    if (threadIdx.x < kSparseQT) {
-        const uint32_t c = min(cnt[threadIdx.x], k);
-        cnt[threadIdx.x] = c;
-        if (c == k) thr[threadIdx.x] = buf[((size_t)threadIdx.x << cap_log) + k - 1];
-    }
-    __syncthreads();
-}
 
 template <bool SELECT, bool STATS>
 __global__ __launch_bounds__(kSparseThreads) void sparse_scan_kernel(const SparseScanArgs a) {
@@ -300,12 +245,12 @@ __global__ __launch_bounds__(kSparseThreads) void sparse_scan_kernel(const Spars
             // one decision for the workgroup: the counts are read before the second barrier, the next round's appends
             // come after it, so no thread can see a count another has already moved
             const int full = __syncthreads_or(tid < kSparseQT && s_cnt[tid] > (1u << cap_log) - kSparseRoundRows);
-            if (full) sparse_compact(buf, cap_log, a.k, s_cnt, s_thr);
+            if (full) sparse_compact<kSparseQT>(buf, cap_log, a.k, s_cnt, s_thr);
         }
     }
     if (SELECT) {
         __syncthreads();
-        sparse_compact(buf, cap_log, a.k, s_cnt, s_thr);
+        sparse_compact<kSparseQT>(buf, cap_log, a.k, s_cnt, s_thr);
         for (uint32_t i = tid; i < tnq * a.k; i += kSparseThreads) {
             const uint32_t jq = i / a.k, ii = i % a.k;
             a.partial[((size_t)(q0 + jq) * a.chunks + chunk) * a.k + ii] = buf[((size_t)jq << cap_log) + ii];
@@ -351,26 +296,6 @@ __global__ __launch_bounds__(kMergeThreads) void sparse_merge_kernel(const uint6
 
 using namespace scann;
 
-struct scann_hip_sparse_index {
-    int device = 0;
-    uint64_t n = 0, nnz = 0;
-    uint32_t dimensionality = 0;
-    int measure = SCANN_HIP_DOT_PRODUCT;
-    DevBuf d_off, d_dims, d_vals, d_norm, d_len;
-    // searches: one stream and grow-only buffers, one call at a time
-    std::mutex mu;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    bool timed = false, stats = false;
-    uint64_t plan[5] = {0, 0, 0, 0, 0};
-    DevBuf q_off, q_dims, q_vals, q_norm, tiles, allow, partial, out_idx, out_dist, out_count, dist, d_stats;
-    ~scann_hip_sparse_index() {
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
-};
-
 namespace {
 
 // queries checked, planned and uploaded; the scan launched (with k: the selection and the merge); results copied back
@@ -391,6 +316,7 @@ int sparse_run(scann_hip_sparse_index *ix, const uint64_t *q_offsets, const uint
     std::lock_guard<std::mutex> lock(ix->mu);
     ix->timed = false;
     for (uint64_t &p : ix->plan) p = 0;
+    ix->inv_chunks = ix->inv_visited = 0;
     if (select) {   // what a search that launches nothing leaves: no rows, the halves of the all-ones key
         for (uint32_t i = 0; i < nq; ++i) out_count[i] = 0;
         for (size_t i = 0; i < (size_t)nq * k; ++i) {
@@ -400,8 +326,10 @@ int sparse_run(scann_hip_sparse_index *ix, const uint64_t *q_offsets, const uint
     }
     if (ix->n == 0 || nq == 0) return SCANN_HIP_OK;
     const uint32_t n = (uint32_t)ix->n, ntiles = (uint32_t)starts.size() - 1;
+    const bool inv = ix->inv;   // the posting-list route (sparse_inv.hip): chunks are whole blocks of rows
     uint32_t chunk_rows = 0, chunks = 0;
-    sparse_chunks(n, select ? kSparseMergeKeys / k : 65535u, &chunk_rows, &chunks);
+    if (inv) sparse_inv_chunks(ix->inv_blocks, select ? kSparseMergeKeys / k : 65535u, &chunk_rows, &chunks);
+    else sparse_chunks(n, select ? kSparseMergeKeys / k : 65535u, &chunk_rows, &chunks);
     if (allow_bits > n) allow_bits = n;
     std::vector<uint64_t> rel((size_t)nq + 1);
     for (uint32_t i = 0; i <= nq; ++i) rel[i] = q_offsets[i] - q_offsets[0];
@@ -465,7 +393,23 @@ int sparse_run(scann_hip_sparse_index *ix, const uint64_t *q_offsets, const uint
     const dim3 grid(ntiles, chunks), block(kSparseThreads);
     const size_t lds = sparse_scan_lds(k, select);
     SCANN_HIP_CHECK(hipEventRecord(ix->ev[0], st));
-    if (select) {
+    if (inv) {
+        SparseInvArgs v{};
+        v.q_off = a.q_off;
+        v.q_dims = a.q_dims;
+        v.q_vals = a.q_vals;
+        v.q_norm = a.q_norm;
+        v.nq = nq;
+        v.allow = a.allow;
+        v.allow_bits = a.allow_bits;
+        v.k = k;
+        v.chunk_blocks = chunk_rows;
+        v.chunks = chunks;
+        v.partial = a.partial;
+        v.out = select ? nullptr : a.out;
+        v.stats = ix->stats ? a.stats : nullptr;
+        SCANN_TRY(sparse_inv_scan(ix, v));
+    } else if (select) {
         if (ix->stats) SCANN_TRY(launch(sparse_scan_kernel<true, true>, grid, block, lds, st, a));
         else SCANN_TRY(launch(sparse_scan_kernel<true, false>, grid, block, lds, st, a));
     } else {
@@ -490,6 +434,11 @@ int sparse_run(scann_hip_sparse_index *ix, const uint64_t *q_offsets, const uint
     if (ix->stats) SCANN_HIP_CHECK(hipMemcpyAsync(stats, ix->d_stats.p, 24, hipMemcpyDeviceToHost, st));
     SCANN_HIP_CHECK(hipStreamSynchronize(st));
     ix->timed = true;
+    if (inv) {   // (the plan stays all zero: it describes exhaustive scans)
+        ix->inv_chunks = chunks;
+        ix->inv_visited = stats[0];
+        return SCANN_HIP_OK;
+    }
     ix->plan[0] = ntiles;
     ix->plan[1] = chunks;
     ix->plan[2] = stats[0];
@@ -566,7 +515,7 @@ uint64_t scann_hip_sparse_size(const scann_hip_sparse_index *index) { return ind
 
 uint64_t scann_hip_sparse_device_bytes(const scann_hip_sparse_index *index) {
     if (!index || !index->n) return 0;
-    return index->d_off.bytes + index->d_dims.bytes + index->d_vals.bytes + index->d_norm.bytes + index->d_len.bytes;
+    return index->d_off.bytes + index->d_dims.bytes + index->d_vals.bytes + index->d_norm.bytes + index->d_len.bytes + index->inv_bytes;
 }
 
 int scann_hip_sparse_search_batched(scann_hip_sparse_index *index, const uint64_t *q_offsets, const uint32_t *q_dims, const float *q_vals,

@@ -34,6 +34,7 @@ SPARSE_TILE_QUERIES = 16       # SCANN_HIP_SPARSE_TILE_QUERIES: queries whose va
 SPARSE_TILE_SLOTS = 1024       # SCANN_HIP_SPARSE_TILE_SLOTS: the sum of a tile's query lengths, and the longest query served
 SPARSE_MAP_SIZE = 2048         # SCANN_HIP_SPARSE_MAP_SIZE: entries of the LDS dimension -> slot map; home of d is d % SPARSE_MAP_SIZE
 SPARSE_MAX_K = 256             # SCANN_HIP_SPARSE_MAX_K
+SPARSE_BLOCK_ROWS = 16384      # SCANN_HIP_SPARSE_BLOCK_ROWS: rows of a posting-list block (SparseIndex.build_postings)
 
 _CODE_NAMES = {
     0: "Ok", 1: "Cancelled", 2: "Unknown", 3: "InvalidArgument", 4: "DeadlineExceeded",
@@ -90,7 +91,8 @@ EXPORTS = [
     "scann_hip_opq_config_default", "scann_hip_opq_train", "scann_hip_opq_cross_covariance", "scann_hip_opq_polar",
     "scann_hip_sparse_create", "scann_hip_sparse_destroy", "scann_hip_sparse_size", "scann_hip_sparse_device_bytes",
     "scann_hip_sparse_search_batched", "scann_hip_sparse_distances", "scann_hip_sparse_last_kernel_ms",
-    "scann_hip_sparse_enable_stats", "scann_hip_sparse_last_plan",
+    "scann_hip_sparse_enable_stats", "scann_hip_sparse_last_plan", "scann_hip_sparse_build_postings",
+    "scann_hip_sparse_postings_info",
 ]
 
 
@@ -439,6 +441,9 @@ def load():
     L.scann_hip_sparse_enable_stats.restype = None
     L.scann_hip_sparse_last_plan.argtypes = [vp, u64p]
     L.scann_hip_sparse_last_plan.restype = None
+    L.scann_hip_sparse_build_postings.argtypes = [vp]
+    L.scann_hip_sparse_postings_info.argtypes = [vp, u64p]
+    L.scann_hip_sparse_postings_info.restype = None
     _lib = L
     return L
 
@@ -1101,19 +1106,34 @@ def sparse_csr(lists_or_offsets, dims=None, vals=None):
 class SparseIndex:
     """Owns one scann_hip_sparse_index: sparse rows in CSR on the device, searched exhaustively by sparse queries
     (DESIGN.md 3.3j).  SparseIndex(offsets, dims, vals, dimensionality=D, measure=...) takes CSR arrays;
-    SparseIndex.from_rows(rows, ...) a list of per-row (dims, vals) pairs.  Queries are given the same two ways."""
+    SparseIndex.from_rows(rows, ...) a list of per-row (dims, vals) pairs.  Queries are given the same two ways.
+    inverted=True (or build_postings() later) adds row-blocked posting lists: searches then read only the entries of
+    the query's dimensions, with the same results bit for bit."""
 
-    def __init__(self, offsets, dims, vals, dimensionality, measure=DOT_PRODUCT, device=0):
+    def __init__(self, offsets, dims, vals, dimensionality, measure=DOT_PRODUCT, device=0, inverted=False):
         off, d, v = sparse_csr(offsets, dims, vals)
         self.h = vp()
         self.n, self.dimensionality, self.measure = off.size - 1, int(dimensionality), measure
         check(load().scann_hip_sparse_create(context(device), ptr(off, u64p), ptr(d, u32p) if d.size else None,
                                              ptr(v, f32p) if v.size else None, self.n, self.dimensionality, measure,
                                              C.byref(self.h)))
+        if inverted:
+            self.build_postings()
 
     @classmethod
-    def from_rows(cls, rows, dimensionality, measure=DOT_PRODUCT, device=0):
-        return cls(*sparse_csr(rows), dimensionality=dimensionality, measure=measure, device=device)
+    def from_rows(cls, rows, dimensionality, measure=DOT_PRODUCT, device=0, inverted=False):
+        return cls(*sparse_csr(rows), dimensionality=dimensionality, measure=measure, device=device, inverted=inverted)
+
+    def build_postings(self):
+        """builds the posting lists on the device from the CSR arrays (idempotent); later searches walk them"""
+        check(load().scann_hip_sparse_build_postings(self.h))
+
+    def postings_info(self):
+        """{'blocks', 'block_rows', 'bytes', 'chunks', 'visited'}: the posting layout, and of the last posting-list search
+        its chunks of blocks and (only after enable_stats) the postings it visited"""
+        p = np.zeros(5, np.uint64)
+        load().scann_hip_sparse_postings_info(self.h, ptr(p, u64p))
+        return dict(zip(("blocks", "block_rows", "bytes", "chunks", "visited"), (int(x) for x in p)))
 
     def close(self):
         if self.h:

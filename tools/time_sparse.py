@@ -22,7 +22,11 @@ The baseline is the only other route to the same answer: the same rows densified
 dim = 30 522 (n = 100 000: 12.2 GB), the same queries densified.  The two routes are timed alternately in one run; the
 dense route sums in another order, so the top-10 lists are compared by overlap.
 
-    python tools/time_sparse.py [--n 1000000] [--n-small 100000] [--batch 1024] [--reps 5] [--no-dense] [--variants]
+--inverted times the posting-list route (SparseIndex.build_postings) against the exhaustive one instead: two handles over
+the same arrays, 3 warm-ups, at least 10 batches each, alternating; one JSON line per size with both routes' QPS and
+kernel times, the postings visited per query, the bytes of the two layouts and the posting build time.
+
+    python tools/time_sparse.py [--n 1000000] [--n-small 100000] [--batch 1024] [--reps 5] [--no-dense] [--variants] [--inverted]
 """
 import argparse
 import json
@@ -70,8 +74,46 @@ def spread(v):
     return {"median": round(float(np.median(v)), 4), "min": round(float(min(v)), 4), "max": round(float(max(v)), 4)}
 
 
+def time_inverted(a, csr, n, queries):
+    """The exhaustive and the posting-list route over the same rows in one process: two handles made from the same
+    arrays (a handle with postings always takes them), 3 warm-ups, then the two alternate.  One JSON line."""
+    nnz = int(csr[1].size)
+    ex = hip.SparseIndex(*csr, dimensionality=D)
+    inv = hip.SparseIndex(*csr, dimensionality=D)
+    t0 = time.perf_counter()
+    inv.build_postings()
+    build_s = time.perf_counter() - t0
+    for _ in range(3):
+        want = ex.search_batched(queries, K)
+        got = inv.search_batched(queries, K)
+    same = all(np.array_equal(x.view(np.uint32), y.view(np.uint32)) for x, y in zip(want, got))
+    t = {"ex": ([], [], []), "inv": ([], [], [])}
+    for _ in range(max(a.reps, 10)):
+        for name, ix in (("ex", ex), ("inv", inv)):
+            t0 = time.perf_counter()
+            ix.search_batched(queries, K)
+            t[name][0].append(time.perf_counter() - t0)
+            ms = ix.last_kernel_ms()
+            t[name][1].append(ms[0])
+            t[name][2].append(ms[1])
+    inv.enable_stats(True)
+    inv.search_batched(queries, K)
+    info = inv.postings_info()
+    out = {"route": "postings_vs_exhaustive", "build": a.label, "n": n, "nnz": nnz, "batch": a.batch, "k": K, "same_bits": same,
+           "block_rows": info["block_rows"], "blocks": info["blocks"], "chunks": info["chunks"], "build_postings_s": round(build_s, 3),
+           "postings_bytes": info["bytes"], "csr_bytes": ex.device_bytes(),
+           "visited_per_query": round(info["visited"] / a.batch, 1), "visited_share_of_entries": round(info["visited"] / a.batch / nnz, 5)}
+    for name, label in (("ex", "exhaustive"), ("inv", "postings")):
+        out[label] = {"qps": round(a.batch / float(np.median(t[name][0])), 1), "call_ms": spread([w * 1e3 for w in t[name][0]]),
+                      "scan_ms": spread(t[name][1]), "merge_ms": spread(t[name][2])}
+    print(json.dumps(out), flush=True)
+    ex.close()
+    inv.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--inverted", action="store_true", help="time the posting-list route against the exhaustive one, nothing else")
     ap.add_argument("--n", type=int, default=1_000_000)
     ap.add_argument("--n-small", type=int, default=100_000)
     ap.add_argument("--batch", type=int, default=1024)
@@ -85,6 +127,11 @@ def main():
     rows = zipf_lists(rng, a.n, 175)
     queries = zipf_lists(rng, a.batch, 40)
     small = (rows[0][:a.n_small + 1], rows[1][:int(rows[0][a.n_small])], rows[2][:int(rows[0][a.n_small])])
+
+    if a.inverted:
+        for csr, n in ((small, a.n_small),) if a.only_small else ((small, a.n_small), (rows, a.n)):
+            time_inverted(a, csr, n, queries)
+        return
 
     dense = dense_q = None
     if not a.no_dense:
