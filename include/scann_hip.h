@@ -146,6 +146,16 @@ int scann_hip_bf_create(scann_hip_ctx *ctx, const float *data, uint64_t n, uint3
 #define SCANN_HIP_ROWS_BF16 1
 #define SCANN_HIP_ROWS_FP8_E4M3 2
 #define SCANN_HIP_ROWS_INT8 3
+/* SCANN_HIP_ROWS_INT4 (brute-force handles only): Int4PackedData (quantization/scalar.rs:354-389).  A row is `stride`
+ * elements in stride / 2 BYTES; element j is the low (even j) or high (odd j) nibble of byte j / 2, code = nibble - 8
+ * in -8 .. 7, value = (float)code * inv_multiplier.  Distances are the INT8 format's, bit for bit, on the unpacked
+ * codes: an INT4 handle and an INT8 handle over the unpacked rows return the same bits and ids.  Elements dim ..
+ * stride - 1 are never read (odd dim: the last nibble's neighbour is padding).  An odd stride -> InvalidArgument.
+ * Everything said above of quantized handles holds; the device holds stride / 2 bytes per row plus the squared norm
+ * when the index qualifies for the shortlist, which for this format (stride % 32 == 0) is scored by the integer
+ * MFMA (bf_i8mfma_kernel: the codes as int8 against int8 digit planes of the query, exact i32 sums).
+ * scann_hip_txh_create_quantized refuses the value. */
+#define SCANN_HIP_ROWS_INT4 5
 int scann_hip_bf_create_quantized(scann_hip_ctx *ctx, const void *rows, uint64_t n, uint32_t dim,
                                   uint32_t stride, int row_format, float inv_multiplier, int measure,
                                   scann_hip_index **out_index);
@@ -207,7 +217,14 @@ int scann_hip_scalar_quantize_device(scann_hip_ctx *ctx, const float *d_rows, ui
  * resident in src: no row visits the host.  src is left untouched and stays usable; destroy it to reclaim its memory.
  * INT8: stats, calibrate(bits, mode, a, b), quantize; the handle's inv_multiplier is the calibrated scale.  BF16 /
  * FP8_E4M3: the arithmetic of scann_hip_bf16_quantize / scann_hip_fp8_quantize(scale 1); bits, mode, a, b are
- * ignored and out_params4 / out_zero_point are written as {0, 0, 1, 1} / 0.  Output rows keep src's stride in
+ * ignored and out_params4 / out_zero_point are written as {0, 0, 1, 1} / 0.
+ * INT4 (brute-force src only; a tree / hasher src -> Unimplemented): bits must be 4 and src's stride even, else
+ * InvalidArgument.  The three reference modes take the 4-bit level c in 0 .. 15 of the arithmetic above and store the
+ * nibble (c + 8) & 15 -- Int4PackedData::from_int8 applied to the quantizer's byte, its offset-binary wrap included, so
+ * the handle reads c - 8 for c >= 8 and c + 8 - 16 below, times the calibrated scale (the reference's reading, as for
+ * INT8).  SCANN_HIP_SQ_SIGNED (allowed at 4 bits with this format only): m = max|x|, s = (float)((double)m / 7.0) (1 when
+ * m == 0), code = clip(rintf(x / s), -7, 7), nibble code + 8, params4 = {-m, m, s, 1 / s}.  One kernel quantizes and
+ * packs into rows of stride / 2 bytes; pad elements are nibble 8 (code 0).  Output rows keep src's stride in
  * ELEMENTS, pad columns 0.  out_params4 / out_zero_point may be NULL.
  * A brute-force src gives what scann_hip_bf_create_quantized builds from the same bytes, measure and inv_multiplier;
  * a Tree-X-Hybrid / AsymmetricHasher src with f32 rows gives what scann_hip_txh_create_quantized builds from the same

@@ -233,7 +233,7 @@ static int bf_finish_quantized(scann_hip_index *ix, uint64_t n, uint32_t dim, ui
     ix->bf.measure = measure;
     ix->bf.fmt = row_format;
     ix->bf.qrows = ix->bf_rows.p;
-    ix->bf.inv_mult = row_format == SCANN_HIP_ROWS_INT8 ? inv_multiplier : 1.0f;
+    ix->bf.inv_mult = row_format == SCANN_HIP_ROWS_INT8 || row_format == SCANN_HIP_ROWS_INT4 ? inv_multiplier : 1.0f;
     SCANN_TRY(bf_build_shortlist_data(ix->bf, ix->bf_rows_b, ix->bf_rows_bl, ix->bf_norm2, &ix->bf.max_norm, ix->stream));
     if (ix->bf_norm2.p) ix->bf.norm2 = ix->bf_norm2.as<float>();
     return SCANN_HIP_OK;
@@ -709,11 +709,13 @@ int scann_hip_bf_create(scann_hip_ctx *ctx, const float *data, uint64_t n, uint3
 int scann_hip_bf_create_quantized(scann_hip_ctx *ctx, const void *rows, uint64_t n, uint32_t dim, uint32_t stride,
                                   int row_format, float inv_multiplier, int measure, scann_hip_index **out) {
     if (!ctx || !out) return fail(SCANN_HIP_INVALID_ARGUMENT, "null ctx/out_index");
-    if (row_format != SCANN_HIP_ROWS_BF16 && row_format != SCANN_HIP_ROWS_FP8_E4M3 && row_format != SCANN_HIP_ROWS_INT8)
+    const bool int4 = row_format == SCANN_HIP_ROWS_INT4;
+    if (row_format != SCANN_HIP_ROWS_BF16 && row_format != SCANN_HIP_ROWS_FP8_E4M3 && row_format != SCANN_HIP_ROWS_INT8 && !int4)
         return fail(SCANN_HIP_INVALID_ARGUMENT, "unknown row format " + std::to_string(row_format));
     if (n > 0 && !rows) return fail(SCANN_HIP_INVALID_ARGUMENT, "rows is null");
     if (n > 0 && (dim == 0 || stride < dim)) return fail(SCANN_HIP_INVALID_ARGUMENT, "bad dim/stride");
-    if (row_format == SCANN_HIP_ROWS_INT8 && !std::isfinite(inv_multiplier))
+    if (int4 && (stride & 1u)) return fail(SCANN_HIP_INVALID_ARGUMENT, "packed int4 rows: the stride must be even");
+    if ((row_format == SCANN_HIP_ROWS_INT8 || int4) && !std::isfinite(inv_multiplier))
         return fail(SCANN_HIP_INVALID_ARGUMENT, "inv_multiplier is not finite");
     if (measure == SCANN_HIP_L1 || measure == SCANN_HIP_COSINE)
         return fail(SCANN_HIP_UNIMPLEMENTED, "quantized rows: SquaredL2, L2 and DotProduct only");
@@ -724,7 +726,7 @@ int scann_hip_bf_create_quantized(scann_hip_ctx *ctx, const void *rows, uint64_t
     auto *ix = new scann_hip_index();
     ix->ctx = ctx;
     ix->kind = KIND_BF;
-    const size_t bytes = (size_t)n * stride * (row_format == SCANN_HIP_ROWS_BF16 ? 2 : 1);
+    const size_t bytes = int4 ? (size_t)n * (stride / 2) : (size_t)n * stride * (row_format == SCANN_HIP_ROWS_BF16 ? 2 : 1);
     int s = index_common_init(ix);
     if (s == SCANN_HIP_OK) s = upload(ix->bf_rows, rows, bytes);
     if (s != SCANN_HIP_OK) {
@@ -783,40 +785,46 @@ int scann_hip_index_quantization_stats(scann_hip_index *ix, float *out_stats4) {
 int scann_hip_index_quantize_rows(scann_hip_index *src_ix, int row_format, uint32_t bits, int mode, float a, float b,
                                   scann_hip_index **out, float *out_params4, int32_t *out_zero_point) {
     if (!src_ix || !out) return fail(SCANN_HIP_INVALID_ARGUMENT, "null index/out_index");
-    if (row_format != SCANN_HIP_ROWS_BF16 && row_format != SCANN_HIP_ROWS_FP8_E4M3 && row_format != SCANN_HIP_ROWS_INT8)
+    const bool int4 = row_format == SCANN_HIP_ROWS_INT4, ints = int4 || row_format == SCANN_HIP_ROWS_INT8;
+    if (row_format != SCANN_HIP_ROWS_BF16 && row_format != SCANN_HIP_ROWS_FP8_E4M3 && !ints)
         return fail(SCANN_HIP_INVALID_ARGUMENT, "unknown row format " + std::to_string(row_format));
     SqSource src;
     SCANN_TRY(sq_source(src_ix, &src));
+    if (int4) {   // packed rows: 4-bit levels only, brute-force sources only
+        if (bits != 4) return fail(SCANN_HIP_INVALID_ARGUMENT, "packed int4 rows: bits must be 4");
+        if (src_ix->kind != KIND_BF) return fail(SCANN_HIP_UNIMPLEMENTED, "packed int4 rows: brute-force sources only");
+        if (src.stride & 1u) return fail(SCANN_HIP_INVALID_ARGUMENT, "packed int4 rows: the stride must be even");
+    }
     SCANN_TRY(set_device(src_ix->ctx));
     SqParams p{0.0f, 0.0f, 1.0f, 1.0f, 255};
     int32_t zp = 0;
-    const size_t qbytes = (size_t)src.n * src.stride * (row_format == SCANN_HIP_ROWS_BF16 ? 2 : 1);
+    const size_t qbytes = int4 ? (size_t)src.n * (src.stride / 2) : (size_t)src.n * src.stride * (row_format == SCANN_HIP_ROWS_BF16 ? 2 : 1);
     DevBuf qrows;
     {
         std::lock_guard<std::mutex> lock(src_ix->mu);   // the source's primary stream runs both passes
-        if (row_format == SCANN_HIP_ROWS_INT8) {
+        if (ints) {
             // a bad mode / bits / range is refused before any device work
             const float probe[4] = {0.0f, 0.0f, 0.0f, 0.0f};
             SqParams tmp{};
             int32_t tz = 0;
-            SCANN_TRY(sq_calibrate(probe, bits, mode, a, b, &tmp, &tz));
+            SCANN_TRY(sq_calibrate(probe, bits, mode, a, b, &tmp, &tz, int4));
             SqPartial sums;
             SCANN_TRY(sq_stats_device(src.rows, src.n, src.dim, src.stride, src_ix->stream, &sums));
             if (mode == SCANN_HIP_SQ_SIGNED && sums.nonfinite)
                 return fail(SCANN_HIP_INVALID_ARGUMENT, "scalar quantizer: the signed mode needs finite values");
             float stats4[4];
             sq_stats_finish(sums, src.n * src.dim, stats4);
-            SCANN_TRY(sq_calibrate(stats4, bits, mode, a, b, &p, &zp));
+            SCANN_TRY(sq_calibrate(stats4, bits, mode, a, b, &p, &zp, int4));
         }
         SCANN_TRY(qrows.ensure(qbytes));
         SCANN_TRY(launch_sq_quantize(src.rows, src.n, src.dim, src.stride, row_format, mode, p, qrows.p, src.stride,
                                      src_ix->stream));
         SCANN_HIP_CHECK(hipStreamSynchronize(src_ix->stream));
     }
-    const float inv = row_format == SCANN_HIP_ROWS_INT8 ? p.scale : 1.0f;
+    const float inv = ints ? p.scale : 1.0f;
     scann_hip_index *ix = nullptr;
     if (src_ix->kind == KIND_BF) {
-        if (row_format == SCANN_HIP_ROWS_INT8 && !std::isfinite(inv))
+        if (ints && !std::isfinite(inv))
             return fail(SCANN_HIP_INVALID_ARGUMENT, "inv_multiplier is not finite");
         ix = new scann_hip_index();
         ix->ctx = src_ix->ctx;

@@ -753,7 +753,7 @@ int scann::search_device_ws(scann_hip_index *ix, DeviceSlot *dsl, SlotScratch &s
         int s = bf_search_device(ix->bf, sc.bfw, d_queries, nq, q_stride, k, shortlist, kn.bf_shortlist_tail, flt,
                                  d_out_idx, d_out_dist, d_out_count, st, tv.ev0, tv.ev1);
         if (dsl && s == SCANN_HIP_OK) s = device_slot_done(dsl, st);
-        ix->timing_end(tv, s == SCANN_HIP_OK, shortlist ? "bf_bf16_kernel" : bf_pass_kernel_name(ix->bf, nq));
+        ix->timing_end(tv, s == SCANN_HIP_OK, shortlist ? bf_shortlist_kernel_name(ix->bf) : bf_pass_kernel_name(ix->bf, nq));
         return s;
     }
     TxhPlan p;
@@ -816,7 +816,7 @@ int scann_hip_search_batched(scann_hip_index *ix, const float *queries, uint32_t
         const bool shortlist = !flt.bitmap && !(opts && opts->bf_exact) && bf_shortlist_eligible(ix->bf, nq, k, kn);
         int s = bf_search_host(ix->bf, sl.sc->bfw, queries, nq, q_stride, k, shortlist, kn.bf_shortlist_tail, flt, out_idx,
                                out_dist, out_count, sl.stream, tv.ev0, tv.ev1);
-        ix->timing_end(tv, s == SCANN_HIP_OK, shortlist ? "bf_bf16_kernel" : bf_pass_kernel_name(ix->bf, nq));
+        ix->timing_end(tv, s == SCANN_HIP_OK, shortlist ? bf_shortlist_kernel_name(ix->bf) : bf_pass_kernel_name(ix->bf, nq));
         return s;
     }
     if (q_dim != ix->tx.row_dim)  // tree_x_hybrid/mod.rs:251-253, hashes/hasher.rs:167-171 (projected handles: the rows' space)

@@ -10,11 +10,11 @@ struct BfIndexDev {
     uint64_t n;
     uint32_t dim, stride;
     int measure;         // scann_hip_measure
-    // quantized rows (scann_hip_bf_create_quantized): fmt = SCANN_HIP_ROWS_BF16 / _FP8_E4M3 / _INT8, qrows =
-    // [n][stride] elements of that format; every pass takes bf_quant_kernel.  fmt 0 = f32 rows above.
+    // quantized rows (scann_hip_bf_create_quantized): fmt = SCANN_HIP_ROWS_BF16 / _FP8_E4M3 / _INT8 / _INT4, qrows =
+    // [n][stride] elements of that format (INT4: stride / 2 bytes a row); every pass takes bf_quant_kernel.  fmt 0 = f32 rows above.
     int fmt;
     const void *qrows;
-    float inv_mult;      // INT8: value = (float)i8 * inv_mult
+    float inv_mult;      // INT8 / INT4: value = (float)code * inv_mult
     // bf16 shortlist (bf_shortlist_*): a bf16 copy of the rows [n][dim], f32 squared norms and the
     // largest row norm; nullptr when the index does not qualify (dim % 16, size)
     const uint16_t *rows_b, *rows_bl;   // hi and lo halves of the split bf16 copy
@@ -25,8 +25,34 @@ struct BfIndexDev {
 struct BfWorkspace {
     DevBuf queries, sample, thr, cand_cnt, cand, counters, out_idx, out_dist, out_count;
     DevBuf q_b, q_bl, q_n2, sl_idx, sl_approx, sl_cnt, sl_exact, sl_fail;   // bf16 shortlist path
+    DevBuf q_err;   // integer shortlist pass (bf_int.hip; q_b / q_bl hold its digit planes / weights)
     DevBuf allow, ids, allow_sums;   // filtered search: bitmap copy, compacted id list, per-block popcounts
 };
+
+// One pass of a scoring kernel over (a sample of) the rows: what bf.hip's kernels and bf_int.hip's read.
+struct BfPass {
+    const float *queries;   // device [nq][q_stride]
+    uint32_t nq, q_stride;
+    uint32_t nrows;         // virtual rows of this pass
+    uint32_t row_mult;      // real row = virtual row * row_mult
+    int filter;             // 0: store all to out[nq][ld]; 1: threshold filter -> candidates
+    float *out;
+    uint32_t ld;
+    const uint64_t *thr;    // [nq]
+    uint32_t *cand_cnt;     // [nq]
+    uint64_t *cand;         // [nq][cap]
+    uint32_t cap;
+    // allow-list filter (scann_hip_search_opts.allow_bitmap); both null on an unfiltered search.
+    const uint32_t *ids;    // compacted form: real row = ids[virtual row * row_mult], ascending allowed datapoints
+    const uint64_t *allow;  // bit-test form: a row is a candidate only if its bit is set (tested at the emit)
+    uint32_t allow_bits;    // capacity of the bitmap clipped to the row count
+};
+
+// the distance half of a threshold key as a float; the no-bound key is +inf
+__device__ __forceinline__ float bf_thr_float(uint64_t T) {
+    const uint32_t hi = (uint32_t)(T >> 32);
+    return hi == 0xFFFFFFFFu ? __builtin_inff() : ordered_to_f32(hi);
+}
 
 // Allow-list of one search (scann_hip_search_opts.allow_bitmap / allow_bitmap_bits); bitmap == nullptr: none.
 // A filtered search answers as an unfiltered search over the allowed rows alone, indices mapped back.
@@ -52,6 +78,7 @@ constexpr uint32_t kBfSampleRows = 8192;   // rows of the threshold sample (== L
 int bf_reserve(const BfIndexDev &ix, BfWorkspace &w, uint32_t max_nq, uint32_t max_k, bool filtered);
 
 const char *bf_pass_kernel_name(const BfIndexDev &ix, uint32_t nq);
+const char *bf_shortlist_kernel_name(const BfIndexDev &ix);
 // true if the pass kernels accept this index's dim at EVERY batch size (the last resort's queries fit the LDS): a
 // caller with a path of its own for some batch sizes must not take it past this ceiling, or the dims it refuses
 // would depend on the batch size

@@ -15,6 +15,7 @@
 //  * top-k: a strided row sample gives a valid upper bound of the k-th best key; the full
 //    pass keeps only (distance, index) keys <= bound; a per-query LDS sort finishes.
 #include "bf.h"
+#include "bf_int.h"
 #include "launch.h"
 #include "quant.h"
 
@@ -35,24 +36,6 @@ constexpr uint32_t kBfSelectThreads = 1024;
 constexpr uint32_t kBfInvalid = 0xFFFFFFFFu;
 
 enum { BF_CNT_STATUS = 0, BF_CNT_N = 4 };
-
-struct BfPass {
-    const float *queries;   // device [nq][q_stride]
-    uint32_t nq, q_stride;
-    uint32_t nrows;         // virtual rows of this pass
-    uint32_t row_mult;      // real row = virtual row * row_mult
-    int filter;             // 0: store all to out[nq][ld]; 1: threshold filter -> candidates
-    float *out;
-    uint32_t ld;
-    const uint64_t *thr;    // [nq]
-    uint32_t *cand_cnt;     // [nq]
-    uint64_t *cand;         // [nq][cap]
-    uint32_t cap;
-    // allow-list filter (scann_hip_search_opts.allow_bitmap); both null on an unfiltered search.
-    const uint32_t *ids;    // compacted form: real row = ids[virtual row * row_mult], ascending allowed datapoints
-    const uint64_t *allow;  // bit-test form: a row is a candidate only if its bit is set (tested at the emit)
-    uint32_t allow_bits;    // capacity of the bitmap clipped to the row count
-};
 
 // datapoint index of a virtual row (the row that is read, and the index half of its key)
 __device__ __forceinline__ uint32_t bf_real_row(const BfPass &p, uint32_t vrow) {
@@ -79,11 +62,6 @@ __device__ __forceinline__ void bf_emit(const BfPass &p, uint32_t q, uint32_t vr
             if (pos < p.cap) p.cand[(size_t)q * p.cap + pos] = key;
         }
     }
-}
-
-__device__ __forceinline__ float bf_thr_float(uint64_t T) {
-    const uint32_t hi = (uint32_t)(T >> 32);
-    return hi == 0xFFFFFFFFu ? __builtin_inff() : ordered_to_f32(hi);
 }
 
 // =====================================================================================
@@ -1207,10 +1185,10 @@ __global__ __launch_bounds__(256) void bf_quant_rerank_kernel(BfIndexDev ix, con
     __syncthreads();
     const uint32_t c = blockIdx.x * 256u + tid;
     if (c >= nsel) return;
-    constexpr bool FUSED = FMT == SCANN_HIP_ROWS_INT8;
+    constexpr bool FUSED = quant_is_int<FMT>();
     const float inv = ix.inv_mult;
     const uint8_t *row = static_cast<const uint8_t *>(ix.qrows) +
-                         (size_t)sl_idx[(size_t)q * kp + c] * ix.stride * quant_bytes<FMT>();
+                         (size_t)sl_idx[(size_t)q * kp + c] * quant_row_bytes<FMT>(ix.stride);
     f32x2q acc[8];
 #pragma unroll
     for (int t = 0; t < 8; ++t) acc[t] = f32x2q{0.0f, 0.0f};
@@ -1238,7 +1216,7 @@ template <int FMT>
 __global__ void bf_quant_norms_kernel(BfIndexDev ix, float *__restrict__ norm2) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= ix.n) return;
-    const uint8_t *row = static_cast<const uint8_t *>(ix.qrows) + i * ix.stride * quant_bytes<FMT>();
+    const uint8_t *row = static_cast<const uint8_t *>(ix.qrows) + i * quant_row_bytes<FMT>(ix.stride);
     float s2 = 0.0f;
     for (uint32_t j = 0; j < ix.dim; ++j) {
         const float v = quant_load1<FMT>(row, j, ix.inv_mult);
@@ -1251,7 +1229,7 @@ __global__ void bf_quant_norms_kernel(BfIndexDev ix, float *__restrict__ norm2) 
 template <int MEASURE>
 __global__ __launch_bounds__(64) void bf_shortlist_final_kernel(
     uint32_t n, uint32_t k, uint32_t kp, float max_norm, float dot_err, const float *__restrict__ qn2,
-    const uint64_t *__restrict__ thr, const uint32_t *__restrict__ sl_idx, const float *__restrict__ sl_approx,
+    const float *__restrict__ q_err, const uint64_t *__restrict__ thr, const uint32_t *__restrict__ sl_idx, const float *__restrict__ sl_approx,
     const uint32_t *__restrict__ sl_cnt, const float *__restrict__ sl_exact,
     uint32_t *__restrict__ counters, uint32_t *__restrict__ fail_flag, uint32_t *__restrict__ out_idx,
     float *__restrict__ out_dist, uint32_t *__restrict__ out_count) {
@@ -1290,9 +1268,11 @@ __global__ __launch_bounds__(64) void bf_shortlist_final_kernel(
             const float floor_b = nsel == kp ? sl_approx[(size_t)q * kp + kp - 1] : bf_thr_float(thr[q]);
             const float dk = ordered_to_f32((uint32_t)(skeys[k - 1] >> 32));   // k-th exact (the root for L2)
             const float qn = sqrtf(qn2[q]);
+            // q_err (the integer pass): |e_q|_2 of the query residual its digits drop, |e_q.x| <= q_err |x|
+            const float Ed = dot_err * qn * max_norm + (q_err ? q_err[q] * max_norm * 1.000001f : 0.0f);
             float E;
-            if (MEASURE == SCANN_HIP_DOT_PRODUCT) E = dot_err * qn * max_norm;
-            else E = 2.0f * dot_err * qn * max_norm + kF32SqErr * (qn * qn + max_norm * max_norm);
+            if (MEASURE == SCANN_HIP_DOT_PRODUCT) E = Ed;
+            else E = 2.0f * Ed + kF32SqErr * (qn * qn + max_norm * max_norm);
             // L2: every row outside scores >= floor_b - E squared, so its root is >= the root of that (sqrtf is
             // monotone); strictly above dk, no root ties it
             const float lb = floor_b - E * 1.0001f;
@@ -1523,14 +1503,15 @@ __global__ __launch_bounds__(kBfSelectThreads) void bf_select_kernel(
 // pairs on the packed-f32 pipe (v_pk_*: two IEEE operations, the results of the scalar ones).  A lane reads
 // its row 64 elements at a time (8 x 16-byte loads in flight for bf16, 4 for the byte formats, so a cache line
 // of the row is consumed in one or two consecutive visits) and decodes in registers.  (128 byte-format elements
-// at a time spill: the compiler decodes them all before the first use.)
+// at a time spill: the compiler decodes them all before the first use.)  Packed int4 rows keep the 64-element
+// visit, now 2 x 16 bytes; a nibble costs one v_bfe_i32 after one v_xor per word (quant_decode).
 // =====================================================================================
 template <int FMT, int MEASURE, int QT>
 __global__ __launch_bounds__(256) void bf_quant_kernel(BfIndexDev ix, BfPass p) {
     static_assert(QT % 2 == 0, "queries travel in pairs");
-    constexpr int NCH = FMT == SCANN_HIP_ROWS_INT8 ? 8 : 1;   // accumulator chains per query
-    constexpr bool FUSED = FMT == SCANN_HIP_ROWS_INT8;
-    constexpr uint32_t B = quant_bytes<FMT>(), EPW = 4 / B, EPV = 16 / B;   // elements per word / per 16 B
+    constexpr int NCH = quant_is_int<FMT>() ? 8 : 1;   // accumulator chains per query
+    constexpr bool FUSED = quant_is_int<FMT>();
+    constexpr uint32_t EPW = (uint32_t)(8 / quant_row_bytes<FMT>(2)), EPV = 4 * EPW;   // elements per word / per 16 B
     constexpr int NV = 64 / EPV;                                             // 16-byte loads per 64 elements
     extern __shared__ __attribute__((aligned(16))) float qs[];   // [dim][QT]
     const uint32_t dim = ix.dim;
@@ -1543,8 +1524,8 @@ __global__ __launch_bounds__(256) void bf_quant_kernel(BfIndexDev ix, BfPass p) 
     const uint32_t vrow = blockIdx.x * blockDim.x + threadIdx.x;
     if (vrow >= p.nrows) return;
     const float inv = ix.inv_mult;
-    const uint8_t *row = static_cast<const uint8_t *>(ix.qrows) + (size_t)bf_real_row(p, vrow) * ix.stride * B;
-    const bool vec = (((size_t)ix.stride * B) & 15u) == 0 && (reinterpret_cast<uintptr_t>(ix.qrows) & 15u) == 0;
+    const uint8_t *row = static_cast<const uint8_t *>(ix.qrows) + (size_t)bf_real_row(p, vrow) * quant_row_bytes<FMT>(ix.stride);
+    const bool vec = (quant_row_bytes<FMT>(ix.stride) & 15u) == 0 && (reinterpret_cast<uintptr_t>(ix.qrows) & 15u) == 0;
     f32x2q acc[QT / 2][NCH];
 #pragma unroll
     for (int h = 0; h < QT / 2; ++h)
@@ -1563,7 +1544,7 @@ __global__ __launch_bounds__(256) void bf_quant_kernel(BfIndexDev ix, BfPass p) 
         for (; e + 64 <= dim; e += 64) {
             uint4 r[NV];
 #pragma unroll
-            for (int i = 0; i < NV; ++i) r[i] = *reinterpret_cast<const uint4 *>(row + (size_t)e * B + 16 * i);
+            for (int i = 0; i < NV; ++i) r[i] = *reinterpret_cast<const uint4 *>(row + quant_row_bytes<FMT>(e) + 16 * i);
 #pragma unroll
             for (int i = 0; i < NV; ++i) {
                 const uint32_t w[4] = {r[i].x, r[i].y, r[i].z, r[i].w};
@@ -1575,7 +1556,7 @@ __global__ __launch_bounds__(256) void bf_quant_kernel(BfIndexDev ix, BfPass p) 
             }
         }
         for (; e + EPV <= dim; e += EPV) {
-            const uint4 r = *reinterpret_cast<const uint4 *>(row + (size_t)e * B);
+            const uint4 r = *reinterpret_cast<const uint4 *>(row + quant_row_bytes<FMT>(e));
             const uint32_t w[4] = {r.x, r.y, r.z, r.w};
 #pragma unroll
             for (int wi = 0; wi < 4; ++wi)
@@ -1701,12 +1682,16 @@ static int launch_quant(const BfIndexDev &ix, const BfPass &p, hipStream_t st) {
 static int launch_quant_pass(const BfIndexDev &ix, const BfPass &p, hipStream_t st) {
     // (one pair too where four pairs of queries exceed the LDS, dim > 5120: the same arithmetic per pair of values)
     const bool few = p.nq <= 2 || (size_t)ix.dim * 8 * sizeof(float) > kMaxLdsBytes;
-    if (ix.fmt != SCANN_HIP_ROWS_BF16 && ix.fmt != SCANN_HIP_ROWS_FP8_E4M3 && ix.fmt != SCANN_HIP_ROWS_INT8)
+    if (ix.fmt != SCANN_HIP_ROWS_BF16 && ix.fmt != SCANN_HIP_ROWS_FP8_E4M3 && ix.fmt != SCANN_HIP_ROWS_INT8 &&
+        ix.fmt != SCANN_HIP_ROWS_INT4)
         return fail(SCANN_HIP_INVALID_ARGUMENT, "unknown row format");
-    return with_value<SCANN_HIP_ROWS_BF16, SCANN_HIP_ROWS_FP8_E4M3, SCANN_HIP_ROWS_INT8>(ix.fmt, [&](auto fmt) {
+    return with_value<SCANN_HIP_ROWS_BF16, SCANN_HIP_ROWS_FP8_E4M3, SCANN_HIP_ROWS_INT8, SCANN_HIP_ROWS_INT4>(ix.fmt, [&](auto fmt) {
         return few ? launch_quant<fmt(), 2>(ix, p, st) : launch_quant<fmt(), 8>(ix, p, st);
     });
 }
+
+// name of the kernel that scores the rows on the shortlist path (timing reports)
+const char *bf_shortlist_kernel_name(const BfIndexDev &ix) { return bf_int_eligible(ix) ? "bf_i8mfma_kernel" : "bf_bf16_kernel"; }
 
 // name of the kernel launch_pass picks for a batch of nq queries (timing reports)
 const char *bf_pass_kernel_name(const BfIndexDev &ix, uint32_t nq) {
@@ -1903,6 +1888,13 @@ static int enqueue_search(const BfIndexDev &ix, BfWorkspace &w, const BfPlan &pl
 }
 
 // ---- bf16 shortlist path --------------------------------------------------------------------
+// every row format of a brute-force handle (default: 0, f32 rows)
+template <typename F>
+static int with_bf_row_format(int fmt, F &&f) {
+    return with_value<SCANN_HIP_ROWS_BF16, SCANN_HIP_ROWS_FP8_E4M3, SCANN_HIP_ROWS_INT8, SCANN_HIP_ROWS_INT4, 0>(
+        fmt, std::forward<F>(f));
+}
+
 static bool shortlist_dims_ok(uint32_t dim) {
     switch (dim) {
         case 32: case 64: case 96: case 128: case 192: case 256: return true;
@@ -1919,6 +1911,7 @@ int bf_build_shortlist_data(const BfIndexDev &ix, DevBuf &rows_b, DevBuf &rows_b
     if (ix.measure > SCANN_HIP_DOT_PRODUCT) return SCANN_HIP_OK;   // L1 / Cosine: no bf16 bound is derived for them
     // quantized rows: the pass reads 8 elements per load (stride % 8) and needs only the norms, no row copy
     if (ix.fmt && ((ix.stride & 7u) || (reinterpret_cast<uintptr_t>(ix.qrows) & 15u))) return SCANN_HIP_OK;
+    if (ix.fmt == SCANN_HIP_ROWS_INT4 && !bf_int_eligible(ix)) return SCANN_HIP_OK;   // the integer pass: stride % 32
     if (!ix.fmt) {
         SCANN_TRY(rows_b.ensure((size_t)ix.n * ix.dim * 2));
         SCANN_TRY(rows_bl.ensure((size_t)ix.n * ix.dim * 2));
@@ -1928,7 +1921,7 @@ int bf_build_shortlist_data(const BfIndexDev &ix, DevBuf &rows_b, DevBuf &rows_b
     SCANN_TRY(mx.ensure(4));
     SCANN_HIP_CHECK(hipMemsetAsync(mx.p, 0, 4, st));
     const dim3 grid_n((uint32_t)ceil_div_u64(ix.n, 256));
-    SCANN_TRY(with_row_format(ix.fmt, [&](auto fmt) {
+    SCANN_TRY(with_bf_row_format(ix.fmt, [&](auto fmt) {
         if constexpr (fmt() != 0)
             return launch(bf_quant_norms_kernel<fmt()>, grid_n, dim3(256), 0, st, ix, norm2.as<float>());
         else
@@ -1984,7 +1977,7 @@ static int launch_bf16_pass(const BfIndexDev &ix, const BfPass &p, const uint16_
 template <int MEASURE>
 static int launch_rerank(const BfIndexDev &ix, const float *d_queries, uint32_t q_stride, uint32_t kp, BfWorkspace &w,
                          uint32_t nq, hipStream_t st) {
-    return with_row_format(ix.fmt, [&](auto fmt) {
+    return with_bf_row_format(ix.fmt, [&](auto fmt) {
         if constexpr (fmt() != 0)
             return launch((bf_quant_rerank_kernel<fmt(), MEASURE>), dim3(ceil_div_u32(kp, 256), nq), dim3(256),
                           (size_t)ix.dim * 4, st, ix, d_queries, q_stride, kp, w.sl_idx.as<uint32_t>(),
@@ -2003,8 +1996,16 @@ static int enqueue_shortlist_search(const BfIndexDev &ix, BfWorkspace &w, uint32
     const uint32_t n = (uint32_t)ix.n, kp = shortlist_size(k);
     const uint32_t ns = std::min(n, kBfSampleRows), rs = n / ns;
     const uint32_t cap = (uint32_t)std::min<uint64_t>(n, 2ull * kp * rs + 16ull * rs + 256ull);
-    SCANN_TRY(w.q_b.ensure((size_t)nq * ix.dim * 2));
-    SCANN_TRY(w.q_bl.ensure((size_t)nq * ix.dim * 2));
+    // integer-coded rows the integer pass reads (bf_int.hip): digit planes and weights instead of the split bf16 query
+    const bool ints = bf_int_eligible(ix);
+    if (ints) {
+        SCANN_TRY(w.q_b.ensure(bf_int_digit_bytes(nq, ix.dim)));
+        SCANN_TRY(w.q_bl.ensure(bf_int_weight_bytes(nq)));
+        SCANN_TRY(w.q_err.ensure((size_t)nq * 4));
+    } else {
+        SCANN_TRY(w.q_b.ensure((size_t)nq * ix.dim * 2));
+        SCANN_TRY(w.q_bl.ensure((size_t)nq * ix.dim * 2));
+    }
     SCANN_TRY(w.sl_fail.ensure((size_t)nq * 4));
     SCANN_TRY(w.q_n2.ensure((size_t)nq * 4));
     SCANN_TRY(w.sample.ensure((size_t)nq * ns * 4));
@@ -2018,8 +2019,16 @@ static int enqueue_shortlist_search(const BfIndexDev &ix, BfWorkspace &w, uint32
     SCANN_TRY(w.sl_cnt.ensure((size_t)nq * 4));
     SCANN_HIP_CHECK(hipMemsetAsync(w.counters.p, 0, BF_CNT_N * 4, st));
     SCANN_HIP_CHECK(hipMemsetAsync(w.cand_cnt.p, 0, (size_t)nq * 4, st));
-    SCANN_TRY(launch(bf_q_prep_kernel, dim3(ceil_div_u32(nq, 4)), dim3(256), 0, st, d_queries, nq, ix.dim,
-                     q_stride, w.q_b.as<uint16_t>(), w.q_bl.as<uint16_t>(), w.q_n2.as<float>()));
+    if (ints)
+        SCANN_TRY(bf_int_q_prep(ix, d_queries, nq, q_stride, w.q_b.as<int8_t>(), w.q_bl.as<float>(), w.q_n2.as<float>(),
+                                w.q_err.as<float>(), st));
+    else
+        SCANN_TRY(launch(bf_q_prep_kernel, dim3(ceil_div_u32(nq, 4)), dim3(256), 0, st, d_queries, nq, ix.dim,
+                         q_stride, w.q_b.as<uint16_t>(), w.q_bl.as<uint16_t>(), w.q_n2.as<float>()));
+    auto score_pass = [&](const BfPass &p) {
+        if (!ints) return launch_bf16_pass(ix, p, w.q_b.as<uint16_t>(), w.q_bl.as<uint16_t>(), w.q_n2.as<float>(), st);
+        return bf_int_pass(ix, p, w.q_b.as<int8_t>(), w.q_bl.as<float>(), w.q_n2.as<float>(), st);
+    };
     // 1. bf16 scores of an evenly spaced sample -> bound of the kp-th best bf16 score
     BfPass a{};
     a.queries = d_queries;
@@ -2030,7 +2039,7 @@ static int enqueue_shortlist_search(const BfIndexDev &ix, BfWorkspace &w, uint32
     a.filter = 0;
     a.out = w.sample.as<float>();
     a.ld = ns;
-    SCANN_TRY(launch_bf16_pass(ix, a, w.q_b.as<uint16_t>(), w.q_bl.as<uint16_t>(), w.q_n2.as<float>(), st));
+    SCANN_TRY(score_pass(a));
     const SelCfg tcfg = sel_cfg(ns);
     const size_t lds_thr = (size_t)next_pow2_u32(ns) * 8 + (size_t)tcfg.bins * 4 + (size_t)tcfg.list * 8 + 48 * 8;
     // Sample rank of the filter bound.  The kp-th smallest sample score is a certain bound of the
@@ -2063,7 +2072,7 @@ static int enqueue_shortlist_search(const BfIndexDev &ix, BfWorkspace &w, uint32
     b.cand = w.cand.as<uint64_t>();
     b.cap = cap;
     if (ev0) SCANN_HIP_CHECK(hipEventRecord(ev0, st));
-    SCANN_TRY(launch_bf16_pass(ix, b, w.q_b.as<uint16_t>(), w.q_bl.as<uint16_t>(), w.q_n2.as<float>(), st));
+    SCANN_TRY(score_pass(b));
     if (ev1) SCANN_HIP_CHECK(hipEventRecord(ev1, st));
     // 3. the kp best bf16 scores (sorted): the shortlist
     const SelCfg scfg = sel_cfg(kBfSortCap);
@@ -2073,12 +2082,14 @@ static int enqueue_shortlist_search(const BfIndexDev &ix, BfWorkspace &w, uint32
                      w.cand_cnt.as<uint32_t>(), w.cand.as<uint64_t>(), w.counters.as<uint32_t>(),
                      w.sl_idx.as<uint32_t>(), w.sl_approx.as<float>(), w.sl_cnt.as<uint32_t>()));
     // 4. exact f32 score of the shortlist, 5. first k + verification
-    const float err = ix.fmt ? shortlist_quant_err(ix.dim, ix.fmt) : shortlist_dot_err(ix.dim);
+    const float err = ints ? shortlist_int_err(ix.dim, 0)   // (the dropped query residual: per query, q_err)
+                           : (ix.fmt ? shortlist_quant_err(ix.dim, ix.fmt) : shortlist_dot_err(ix.dim));
+    const float *q_err = ints ? w.q_err.as<float>() : nullptr;
     return with_value<SCANN_HIP_DOT_PRODUCT, SCANN_HIP_L2, SCANN_HIP_SQUARED_L2>(ix.measure, [&](auto m) {
         constexpr int kRerank = m() == SCANN_HIP_DOT_PRODUCT ? SCANN_HIP_DOT_PRODUCT : SCANN_HIP_SQUARED_L2;
         SCANN_TRY(launch_rerank<kRerank>(ix, d_queries, q_stride, kp, w, nq, st));
         return launch(bf_shortlist_final_kernel<m()>, dim3(nq), dim3(64), 0, st, n, k, kp, ix.max_norm, err,
-                      w.q_n2.as<float>(), w.thr.as<uint64_t>(), w.sl_idx.as<uint32_t>(), w.sl_approx.as<float>(),
+                      w.q_n2.as<float>(), q_err, w.thr.as<uint64_t>(), w.sl_idx.as<uint32_t>(), w.sl_approx.as<float>(),
                       w.sl_cnt.as<uint32_t>(), w.sl_exact.as<float>(), w.counters.as<uint32_t>(),
                       w.sl_fail.as<uint32_t>(), d_out_idx, d_out_dist, d_out_count);
     });

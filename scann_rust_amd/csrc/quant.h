@@ -1,5 +1,5 @@
 // quant.h -- element decoders and the accumulation step of quantized rows (bf16 bits, the reference's FP8 E4M3 codes,
-// int8 with one inv_multiplier): shared by the brute-force kernels (bf.hip: bf_quant_kernel, the quantized shortlist
+// int8 with one inv_multiplier, packed int4 = two offset-binary nibbles per byte with one inv_multiplier): shared by the brute-force kernels (bf.hip: bf_quant_kernel, the quantized shortlist
 // pass) and the tree / hasher re-rank over quantized rows (txh_rows.hip: rerank_quant_kernel).  Device code only.
 #pragma once
 #include "common.h"
@@ -10,6 +10,15 @@ typedef float f32x2q __attribute__((ext_vector_type(2)));
 
 template <int FMT>
 __host__ __device__ constexpr uint32_t quant_bytes() { return FMT == SCANN_HIP_ROWS_BF16 ? 2u : 1u; }
+// bytes of `elems` row elements (a row stride, or the offset of an element that starts a byte).  INT4
+// (Int4PackedData, quantization/scalar.rs:354-389): element j is the low (even j) or high (odd j) nibble of byte j / 2.
+template <int FMT>
+__host__ __device__ constexpr size_t quant_row_bytes(size_t elems) {
+    return FMT == SCANN_HIP_ROWS_INT4 ? elems / 2 : elems * quant_bytes<FMT>();
+}
+// INT4 and INT8 share one arithmetic: x = (float)code * inv_multiplier, 8 fused chains (one_to_many_int8_float_*)
+template <int FMT>
+__host__ __device__ constexpr bool quant_is_int() { return FMT == SCANN_HIP_ROWS_INT8 || FMT == SCANN_HIP_ROWS_INT4; }
 
 // fp8_to_f32(b, 0) of txh_rows.hip without branches: exponent field e and mantissa m as one 7-bit field em shifted
 // into place, biased by 120 = 127 - 7, one binade lower when e == 0 (2^-8 * (1 + m/8)), zero when em == 0.
@@ -53,6 +62,9 @@ __device__ __forceinline__ uint32_t fp8_from_f32(float value, int format) {
 template <int FMT>
 __device__ __forceinline__ float quant_decode(uint32_t w, int sub, float inv) {
     if (FMT == SCANN_HIP_ROWS_BF16) return __uint_as_float(sub ? (w & 0xFFFF0000u) : (w << 16));
+    // INT4: nibble - 8 = the nibble with its top bit flipped, read as a signed 4-bit field: one v_xor per word (the
+    // compiler shares it among the eight elements), one v_bfe_i32 and one v_cvt per element
+    if (FMT == SCANN_HIP_ROWS_INT4) return (float)((int)((w ^ 0x88888888u) << (28 - 4 * sub)) >> 28) * inv;
     const uint32_t b = (w >> (8 * sub)) & 0xFFu;
     if (FMT == SCANN_HIP_ROWS_FP8_E4M3) return fp8_e4m3_to_f32(b);
     return (float)(int)(int8_t)b * inv;
@@ -63,6 +75,7 @@ __device__ __forceinline__ float quant_load1(const uint8_t *row, uint32_t e, flo
     if (FMT == SCANN_HIP_ROWS_BF16)
         return __uint_as_float((uint32_t)reinterpret_cast<const uint16_t *>(row)[e] << 16);
     if (FMT == SCANN_HIP_ROWS_FP8_E4M3) return fp8_e4m3_to_f32(row[e]);
+    if (FMT == SCANN_HIP_ROWS_INT4) return (float)((int)((row[e >> 1] >> (4u * (e & 1u))) & 15u) - 8) * inv;
     return (float)(int)(int8_t)row[e] * inv;
 }
 

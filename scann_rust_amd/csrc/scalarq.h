@@ -52,26 +52,29 @@ __host__ __device__ inline int8_t sq_ref_code(float v, const SqParams &p) {
     return (int8_t)(uint8_t)q;
 }
 
-// hip.symmetric_int8: clip(rint(x / s), -127, 127), a correctly rounded division; NaN -> 0
-__host__ __device__ inline int8_t sq_signed_code(float v, float s) {
+// hip.symmetric_int8: clip(rint(x / s), -127, 127), a correctly rounded division; NaN -> 0 (lim = 7: 4-bit codes)
+__host__ __device__ inline int8_t sq_signed_code(float v, float s, float lim = 127.0f) {
     float t = rintf(v / s);
     if (!(t == t)) return 0;   // (fmaxf / fminf would drop the NaN and keep the bound)
-    t = fminf(fmaxf(t, -127.0f), 127.0f);
+    t = fminf(fmaxf(t, -lim), lim);
     return (int8_t)(int)t;
 }
 
 // ---- host arithmetic (scalarq.hip) ---------------------------------------------------------------------------------
 // mean / std_dev of quantization/mod.rs:96-102 from the reduced sums; out4 = min, max, mean, std_dev
 void sq_stats_finish(const SqPartial &r, uint64_t count, float *out4);
-// scann_hip_scalar_quantizer_calibrate without the output-pointer checks; writes nothing on failure
-int sq_calibrate(const float *stats4, uint32_t bits, int mode, float a, float b, SqParams *out, int32_t *zero_point);
+// scann_hip_scalar_quantizer_calibrate without the output-pointer checks; writes nothing on failure.  signed4: the
+// signed mode at 4 bits (levels 7, s = m / 7), which only packed int4 rows take (scann_hip_index_quantize_rows)
+int sq_calibrate(const float *stats4, uint32_t bits, int mode, float a, float b, SqParams *out, int32_t *zero_point,
+                 bool signed4 = false);
 // mode / bits / params of a quantize call -> SqParams (InvalidArgument on a bad one)
 int sq_params_checked(uint32_t bits, int mode, const float *params4, SqParams *out);
 
 // ---- launches -------------------------------------------------------------------------------------------------------
 // sq_stats_kernel + sq_stats_final_kernel over n rows of dim values at `stride`; synchronises `st` and returns the sums
 int sq_stats_device(const float *d_rows, uint64_t n, uint32_t dim, uint32_t stride, hipStream_t st, SqPartial *out);
-// f32 rows -> rows of out_stride elements of `fmt` (SCANN_HIP_ROWS_*; INT8: `mode` and `p`), pad columns 0; enqueue only
+// f32 rows -> rows of out_stride elements of `fmt` (SCANN_HIP_ROWS_*; INT8 / INT4: `mode` and `p`), pad columns 0
+// (INT4: nibble 8, out_stride even, out_stride / 2 bytes a row); enqueue only
 int launch_sq_quantize(const float *d_rows, uint64_t n, uint32_t dim, uint32_t stride, int fmt, int mode,
                        const SqParams &p, void *d_out, uint32_t out_stride, hipStream_t st);
 

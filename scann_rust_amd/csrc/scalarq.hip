@@ -177,24 +177,25 @@ void sq_stats_finish(const SqPartial &r, uint64_t count, float *out4) {
 // =====================================================================================
 // calibrate (scalar.rs:103-130) and the project's signed mode
 // =====================================================================================
-static int sq_levels(uint32_t bits, int mode, int32_t *levels) {
+static int sq_levels(uint32_t bits, int mode, int32_t *levels, bool signed4 = false) {
     if (mode < SCANN_HIP_SQ_STDDEV || mode > SCANN_HIP_SQ_SIGNED)
         return fail(SCANN_HIP_INVALID_ARGUMENT, "scalar quantizer: unknown mode " + std::to_string(mode));
-    if (mode == SCANN_HIP_SQ_SIGNED ? bits != 8 : (bits != 4 && bits != 8))
+    if (mode == SCANN_HIP_SQ_SIGNED ? bits != (signed4 ? 4u : 8u) : (bits != 4 && bits != 8))
         return fail(SCANN_HIP_INVALID_ARGUMENT, "scalar quantizer: bits must be 4 or 8 (8 in the signed mode)");
-    *levels = mode == SCANN_HIP_SQ_SIGNED ? 127 : (1 << bits) - 1;
+    *levels = mode == SCANN_HIP_SQ_SIGNED ? (signed4 ? 7 : 127) : (1 << bits) - 1;
     return SCANN_HIP_OK;
 }
 
-int sq_calibrate(const float *stats4, uint32_t bits, int mode, float a, float b, SqParams *out, int32_t *zero_point) {
+int sq_calibrate(const float *stats4, uint32_t bits, int mode, float a, float b, SqParams *out, int32_t *zero_point,
+                 bool signed4) {
     SqParams p{};
-    SCANN_TRY(sq_levels(bits, mode, &p.levels));
+    SCANN_TRY(sq_levels(bits, mode, &p.levels, signed4));
     const float smin = stats4[0], smax = stats4[1], mean = stats4[2], std_dev = stats4[3];
     if (mode == SCANN_HIP_SQ_SIGNED) {
         if (!std::isfinite(smin) || !std::isfinite(smax) || !std::isfinite(mean))
             return fail(SCANN_HIP_INVALID_ARGUMENT, "scalar quantizer: the signed mode needs finite values");
         const float m = fmaxf(fabsf(smin), fabsf(smax));
-        const float s = m > 0.0f ? (float)((double)m / 127.0) : 1.0f;
+        const float s = m > 0.0f ? (float)((double)m / (double)p.levels) : 1.0f;   // levels: 127, or 7 for int4 rows
         p.mn = -m;
         p.mx = m;
         p.scale = s;
@@ -325,6 +326,56 @@ __global__ __launch_bounds__(256) void sq_quantize_kernel(const float *__restric
     }
 }
 
+// Packed int4 rows (Int4PackedData::from_int8, scalar.rs:354-389): one pass quantizes and packs.  A thread owns one
+// 16-byte word of one output row (32 elements) and writes it with one store where the row is whole words on an aligned
+// base (wide), byte by byte otherwise; a row's last word may be partial.  Reference modes: level c in 0 .. 15, nibble
+// (c + 8) & 15 (the offset-binary wrap of the quantizer's byte); signed: code in -7 .. 7, nibble code + 8.  Pad
+// elements are nibble 8 (code 0).
+template <bool SIGNED>
+__global__ __launch_bounds__(256) void sq_quantize_int4_kernel(const float *__restrict__ rows, uint64_t n, uint32_t dim,
+                                                               uint32_t stride, SqParams p, uint8_t *__restrict__ out,
+                                                               uint32_t row_bytes, int wide) {
+    const uint32_t wpr = (row_bytes + 15u) / 16u;   // words per row
+    const uint64_t units = n * wpr;
+    for (uint64_t u = (uint64_t)blockIdx.x * 256 + threadIdx.x; u < units; u += (uint64_t)gridDim.x * 256) {
+        const uint64_t row = u / wpr;
+        const uint32_t b0 = (uint32_t)(u % wpr) * 16u, live = min(16u, row_bytes - b0);
+        const float *src = rows + row * stride;
+        uint32_t w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+        for (uint32_t e = 0; e < 32; ++e) {
+            const uint32_t col = 2u * b0 + e;
+            uint32_t nib = 8u;
+            if (col < dim) {
+                const float v = src[col];
+                nib = SIGNED ? (uint32_t)((int)sq_signed_code(v, p.scale, 7.0f) + 8)
+                             : (((uint32_t)(uint8_t)sq_ref_code(v, p) + 8u) & 15u);
+            }
+            w[e / 8] |= nib << (4 * (e % 8));
+        }
+        uint8_t *o = out + row * row_bytes + b0;
+        if (wide) {
+            *reinterpret_cast<uint4 *>(o) = make_uint4(w[0], w[1], w[2], w[3]);
+        } else {
+            for (uint32_t b = 0; b < live; ++b) o[b] = (uint8_t)(w[b / 4] >> (8 * (b % 4)));
+        }
+    }
+}
+
+static int launch_sq_int4(const float *d_rows, uint64_t n, uint32_t dim, uint32_t stride, int mode, const SqParams &p,
+                          void *d_out, uint32_t out_stride, hipStream_t st) {
+    if (out_stride & 1u) return fail(SCANN_HIP_INVALID_ARGUMENT, "packed int4 rows: the stride must be even");
+    const uint32_t row_bytes = out_stride / 2;
+    const int wide = (row_bytes & 15u) == 0 && (reinterpret_cast<uintptr_t>(d_out) & 15u) == 0 ? 1 : 0;
+    const uint64_t units = n * ceil_div_u32(row_bytes, 16);
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(ceil_div_u64(units, 256), (uint64_t)num_cus() * 8);
+    if (mode == SCANN_HIP_SQ_SIGNED)
+        return launch(sq_quantize_int4_kernel<true>, dim3(grid), dim3(256), 0, st, d_rows, n, dim, stride, p,
+                      static_cast<uint8_t *>(d_out), row_bytes, wide);
+    return launch(sq_quantize_int4_kernel<false>, dim3(grid), dim3(256), 0, st, d_rows, n, dim, stride, p,
+                  static_cast<uint8_t *>(d_out), row_bytes, wide);
+}
+
 template <int KIND>
 static int launch_sq_kind(const float *d_rows, uint64_t n, uint32_t dim, uint32_t stride, const SqParams &p, void *d_out,
                           uint32_t out_stride, hipStream_t st) {
@@ -349,6 +400,7 @@ int launch_sq_quantize(const float *d_rows, uint64_t n, uint32_t dim, uint32_t s
         return fail(SCANN_HIP_INVALID_ARGUMENT, "quantize rows: null rows/output or a stride below dim");
     if (fmt == SCANN_HIP_ROWS_BF16) return launch_sq_kind<kSqKindBf16>(d_rows, n, dim, stride, p, d_out, out_stride, st);
     if (fmt == SCANN_HIP_ROWS_FP8_E4M3) return launch_sq_kind<kSqKindFp8>(d_rows, n, dim, stride, p, d_out, out_stride, st);
+    if (fmt == SCANN_HIP_ROWS_INT4) return launch_sq_int4(d_rows, n, dim, stride, mode, p, d_out, out_stride, st);
     if (fmt != SCANN_HIP_ROWS_INT8) return fail(SCANN_HIP_INVALID_ARGUMENT, "unknown row format " + std::to_string(fmt));
     if (mode == SCANN_HIP_SQ_SIGNED) return launch_sq_kind<kSqKindSigned>(d_rows, n, dim, stride, p, d_out, out_stride, st);
     return launch_sq_kind<kSqKindRef>(d_rows, n, dim, stride, p, d_out, out_stride, st);

@@ -760,7 +760,8 @@ class Index:
 
 
     def quantize_rows(self, fmt, mode=None, bits=8, num_std_devs=3.0, value_range=None):
-        """A NEW Index over this handle's f32 rows stored as `fmt` (ROWS_BF16, ROWS_FP8_E4M3, ROWS_INT8), made on the
+        """A NEW Index over this handle's f32 rows stored as `fmt` (ROWS_BF16, ROWS_FP8_E4M3, ROWS_INT8, or ROWS_INT4
+        with bits=4 on a brute-force handle), made on the
         device (scann_hip_index_quantize_rows); this handle stays as it is.  INT8: `mode` (default SQ_SIGNED, the mode
         whose codes mean what the searcher reads; SQ_STDDEV / SQ_SYMMETRIC / SQ_RANGE reproduce the reference,
         offset-binary bytes read as signed included), `bits`, `num_std_devs` (SQ_STDDEV), `value_range` = (min, max)
@@ -1409,17 +1410,36 @@ def bf_create(data, n, dim, stride, measure, device=0):
 
 
 ROWS_BF16, ROWS_FP8_E4M3, ROWS_INT8 = 1, 2, 3
-_ROWS_DTYPE = {ROWS_BF16: np.uint16, ROWS_FP8_E4M3: np.uint8, ROWS_INT8: np.int8}
+ROWS_INT4 = 5   # Int4PackedData: two offset-binary nibbles per byte, stride / 2 bytes a row
+_ROWS_DTYPE = {ROWS_BF16: np.uint16, ROWS_FP8_E4M3: np.uint8, ROWS_INT8: np.int8, ROWS_INT4: np.uint8}
+
+
+def pack_int4(codes_i8):
+    """Int4PackedData::from_int8 (quantization/scalar.rs:354-389) over the last axis: codes in -8 .. 7 -> bytes, element
+    j in the low (even j) or high (odd j) nibble of byte j // 2 as code + 8."""
+    nib = ((np.asarray(codes_i8, np.int8).astype(np.int16) + 8) & 15).astype(np.uint8)
+    if nib.shape[-1] % 2:   # the last byte's high nibble stays 0, as in the reference; it is never read
+        nib = np.concatenate([nib, np.zeros(nib.shape[:-1] + (1,), np.uint8)], axis=-1)
+    return nib[..., 0::2] | (nib[..., 1::2] << np.uint8(4))
+
+
+def unpack_int4(packed, n_elems):
+    """The first n_elems int8 codes (nibble - 8) of each row of packed bytes (last axis)."""
+    b = np.asarray(packed, np.uint8)
+    nib = np.stack([b & np.uint8(15), b >> np.uint8(4)], axis=-1).reshape(b.shape[:-1] + (-1,))
+    return (nib[..., :n_elems].astype(np.int16) - 8).astype(np.int8)
 
 
 def bf_create_quantized(rows, n, dim, stride, fmt, measure, inv_multiplier=1.0, device=0):
-    """Brute force over rows stored as bf16 bits (uint16), the reference's E4M3 codes (uint8) or int8
-    (value = i8 * inv_multiplier): scann_hip_bf_create_quantized.  The returned Index's search methods,
+    """Brute force over rows stored as bf16 bits (uint16), the reference's E4M3 codes (uint8), int8
+    (value = i8 * inv_multiplier) or packed int4 (ROWS_INT4: pack_int4 bytes, stride in ELEMENTS, stride / 2 bytes a
+    row): scann_hip_bf_create_quantized.  The returned Index's search methods,
     bf_distances and bf_search_radius work as for bf_create."""
     dt = _ROWS_DTYPE.get(fmt, np.uint8)
     r = np.ascontiguousarray(rows).view(dt) if n else None
-    if r is not None and r.size < n * stride:
-        raise ValueError("rows holds %d elements, n * stride = %d" % (r.size, n * stride))
+    if r is not None and r.size < (n * (stride // 2) if fmt == ROWS_INT4 else n * stride):
+        raise ValueError("rows holds %d elements of its dtype, the handle needs %d" %
+                         (r.size, n * (stride // 2) if fmt == ROWS_INT4 else n * stride))
     h = vp()
     check(load().scann_hip_bf_create_quantized(context(device), r.ctypes.data if n else None, n, dim, stride, fmt,
                                                float(np.float32(inv_multiplier)), measure, C.byref(h)))

@@ -1,10 +1,14 @@
 #!/usr/bin/env python3
-"""Times brute force over 1M x 128 U[0,1) rows stored as f32, bf16, FP8 E4M3 and int8 (k = 10, SquaredL2 and
+"""Times brute force over 1M x 128 U[0,1) rows stored as f32, bf16, FP8 E4M3, int8 and packed int4 (the f32 handle's
+rows through quantize_rows(ROWS_INT4, SQ_SIGNED)) (k = 10, SquaredL2 and
 DotProduct, batches 1, 32, 1024) through the device entry point.  Prints one JSON line per case: QPS, the main
 pass kernel's HIP-event time and name, the bytes-per-row floor of one read of the rows at 6.3 TB/s and the
 fraction of it the kernel reached, and the fraction of queries the first (unforced) pass verified (status Ok).
 
-    python tools/time_bf_quantized.py [n] [steps]
+    python tools/time_bf_quantized.py [n] [steps] [formats, comma separated] [variant tag copied into every line]
+
+A variant library (build.build_variant, e.g. -DSCANN_BF_INT_DIGITS=2 on bf_int.hip and bf.hip) is selected with
+SCANN_HIP_LIB; `verified` false means at least one query of the batch was Aborted.
 """
 import ctypes
 import json
@@ -31,8 +35,13 @@ dev = torch.device("cuda", 0)
 sptr = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 p = lambda t: ctypes.c_void_p(t.data_ptr())
 
-formats = [("f32", 0, 4), ("bf16", hip.ROWS_BF16, 2), ("fp8_e4m3", hip.ROWS_FP8_E4M3, 1), ("int8", hip.ROWS_INT8, 1)]
+formats = [("f32", 0, 4), ("bf16", hip.ROWS_BF16, 2), ("fp8_e4m3", hip.ROWS_FP8_E4M3, 1), ("int8", hip.ROWS_INT8, 1),
+           ("int4", hip.ROWS_INT4, 0.5)]
+only = sys.argv[3].split(",") if len(sys.argv) > 3 else [f[0] for f in formats]
+variant = sys.argv[4] if len(sys.argv) > 4 else None
 for fname, fmt, bpe in formats:
+    if fname not in only:
+        continue
     if fmt == hip.ROWS_BF16:
         rows, inv = qc.bf16_from_f32(x), 1.0
     elif fmt == hip.ROWS_FP8_E4M3:
@@ -41,8 +50,13 @@ for fname, fmt, bpe in formats:
     elif fmt == hip.ROWS_INT8:
         rows, inv = hip.symmetric_int8(x)
     for mname, meas in (("sql2", hip.SQUARED_L2), ("dot", hip.DOT_PRODUCT)):
-        ix = hip.bf_create(x, n, dim, dim, meas) if fmt == 0 else hip.bf_create_quantized(rows, n, dim, dim, fmt,
-                                                                                           meas, inv)
+        if fmt == hip.ROWS_INT4:
+            src = hip.bf_create(x, n, dim, dim, meas)
+            ix = src.quantize_rows(hip.ROWS_INT4, mode=hip.SQ_SIGNED, bits=4)[0]
+            src.close()
+        else:
+            ix = hip.bf_create(x, n, dim, dim, meas) if fmt == 0 else hip.bf_create_quantized(rows, n, dim, dim, fmt,
+                                                                                               meas, inv)
         for nq in (1, 32, 1024):
             q = synth.uniform_f32(nq, dim, 123)
             qd = torch.from_numpy(q).to(dev)
@@ -65,9 +79,9 @@ for fname, fmt, bpe in formats:
             kms, kname = ix.last_kernel_ms()
             ix.enable_timing(False)
             floor_ms = n * dim * bpe / HBM * 1e3
-            print(json.dumps({"rows": fname, "measure": mname, "n": n, "dim": dim, "nq": nq, "k": k,
+            print(json.dumps({**({"variant": variant} if variant else {}), "rows": fname, "measure": mname, "n": n, "dim": dim, "nq": nq, "k": k,
                               "qps": round(nq / el, 1), "step_ms": round(el * 1e3, 4), "kernel": kname,
-                              "kernel_ms": round(kms, 4), "bytes_per_row": dim * bpe,
+                              "kernel_ms": round(kms, 4), "bytes_per_row": int(dim * bpe),
                               "floor_ms": round(floor_ms, 4),
                               "floor_fraction": round(floor_ms / kms, 3) if kms > 0 else None,
                               "verified": bool(verified)}), flush=True)
