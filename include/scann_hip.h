@@ -76,9 +76,13 @@ typedef enum {
      * brute-force handles and as the distance_measure of Scann-facade indexes (SearchMode::Partitioned,
      * exact reordering); TreeXHybridSearcher / AsymmetricHasher re-rank by squared L2 regardless. */
     SCANN_HIP_L1 = 3,          /* l1_distance_avx2, simd/x86.rs:103-132 */
-    SCANN_HIP_COSINE = 4       /* 1 - cosine similarity, one_to_one.rs:559-612; its horizontal sums are the
+    SCANN_HIP_COSINE = 4,      /* 1 - cosine similarity, one_to_one.rs:559-612; its horizontal sums are the
                                 * third-party wide::f32x8::reduce_add (wide 0.7, non-AVX build): restated,
                                 * parity unpinned by the reference */
+    SCANN_HIP_HAMMING = 5      /* DistanceMeasure::Hamming "for binary vectors" (distance_measures/mod.rs:49-50,
+                                * one_to_one.rs:618-632): the count of positions whose values differ.  Only with
+                                * SCANN_HIP_ROWS_BIN1 rows in scann_hip_bf_create_quantized; every other create,
+                                * build or fold call answers Unimplemented */
 } scann_hip_measure;
 
 typedef struct scann_hip_ctx scann_hip_ctx;     /* one device + stream/workspace pool */
@@ -156,6 +160,27 @@ int scann_hip_bf_create(scann_hip_ctx *ctx, const float *data, uint64_t n, uint3
  * MFMA (bf_i8mfma_kernel: the codes as int8 against int8 digit planes of the query, exact i32 sums).
  * scann_hip_txh_create_quantized refuses the value. */
 #define SCANN_HIP_ROWS_INT4 5
+/* SCANN_HIP_ROWS_BIN1 (brute-force handles only, measure SCANN_HIP_HAMMING only): binary embeddings, one bit per
+ * element.  `stride` and `dim` count ELEMENTS, i.e. bits: a row is stride / 8 BYTES and element j is bit j & 7 of byte
+ * j >> 3 (numpy.packbits(..., bitorder="little")).  stride % 32 != 0 -> InvalidArgument.  Bits dim .. stride - 1 are
+ * never read (the kernels mask them); inv_multiplier is ignored.
+ * Queries keep the const float * form of every entry point: query bit j is q[j] != 0.0f (so -0.0 is 0 and a NaN is 1).
+ * Distance = (float) popcount(x XOR q) over the first dim bits, exact in f32 (dim >= 2^24 -> OutOfRange); for 0/1
+ * queries it is the reference's hamming_distance over the unpacked 0/1 values.
+ * Selection is the brute-force contract above: k = min(k, n), TopK by (distance, index), drained sorted; n == 0 gives
+ * empty rows; radius search returns every d <= radius.  The handle works with scann_hip_search_batched(_params),
+ * scann_hip_index_reserve, scann_hip_search_batched_device / scann_hip_index_last_device_status,
+ * scann_hip_bf_distances, scann_hip_bf_search_radius(_opts), the timing calls, concurrent search slots and
+ * opts.allow_bitmap (one bitmap per call, as on every brute-force handle; both SCANN_HIP_BF_FILTER forms).
+ * opts.bf_exact is accepted and has no effect: every distance is exact and the handle builds no shortlist data.
+ * The device holds the rows as given, n * stride / 8 bytes, and nothing else.  Batches of 64 queries and more (128 on
+ * rows wider than 1024 bits) on rows with stride % 128 == 0 are scored on the integer matrix cores
+ * (bf_hamming_mfma_kernel), the others by XOR and popcount (bf_hamming_kernel); the results are the same integers.
+ * Refusals: BIN1 with any measure but HAMMING, HAMMING with any other row format -> Unimplemented;
+ * scann_hip_txh_create_quantized and scann_hip_index_quantize_rows refuse the value with InvalidArgument (rows are
+ * not binarised on the device); entry points that read rows as f32 refuse the handle as they refuse every
+ * quantized handle. */
+#define SCANN_HIP_ROWS_BIN1 6
 int scann_hip_bf_create_quantized(scann_hip_ctx *ctx, const void *rows, uint64_t n, uint32_t dim,
                                   uint32_t stride, int row_format, float inv_multiplier, int measure,
                                   scann_hip_index **out_index);

@@ -16,6 +16,7 @@
 #include "mutable.h"
 #include "opq.h"
 #include "pca.h"
+#include "quant.h"
 #include "scalarq.h"
 
 using namespace scann;
@@ -709,24 +710,28 @@ int scann_hip_bf_create(scann_hip_ctx *ctx, const float *data, uint64_t n, uint3
 int scann_hip_bf_create_quantized(scann_hip_ctx *ctx, const void *rows, uint64_t n, uint32_t dim, uint32_t stride,
                                   int row_format, float inv_multiplier, int measure, scann_hip_index **out) {
     if (!ctx || !out) return fail(SCANN_HIP_INVALID_ARGUMENT, "null ctx/out_index");
-    const bool int4 = row_format == SCANN_HIP_ROWS_INT4;
-    if (row_format != SCANN_HIP_ROWS_BF16 && row_format != SCANN_HIP_ROWS_FP8_E4M3 && row_format != SCANN_HIP_ROWS_INT8 && !int4)
+    const bool int4 = row_format == SCANN_HIP_ROWS_INT4, bin1 = row_format == SCANN_HIP_ROWS_BIN1;
+    if (row_format != SCANN_HIP_ROWS_BF16 && row_format != SCANN_HIP_ROWS_FP8_E4M3 && row_format != SCANN_HIP_ROWS_INT8 && !int4 && !bin1)
         return fail(SCANN_HIP_INVALID_ARGUMENT, "unknown row format " + std::to_string(row_format));
     if (n > 0 && !rows) return fail(SCANN_HIP_INVALID_ARGUMENT, "rows is null");
     if (n > 0 && (dim == 0 || stride < dim)) return fail(SCANN_HIP_INVALID_ARGUMENT, "bad dim/stride");
     if (int4 && (stride & 1u)) return fail(SCANN_HIP_INVALID_ARGUMENT, "packed int4 rows: the stride must be even");
+    if (bin1 != (measure == SCANN_HIP_HAMMING))   // the two values come together or not at all
+        return fail(SCANN_HIP_UNIMPLEMENTED, "Hamming distance is built for SCANN_HIP_ROWS_BIN1 rows, and those rows for it alone");
+    if (bin1 && (stride & 31u)) return fail(SCANN_HIP_INVALID_ARGUMENT, "bit rows: the stride must be a multiple of 32 bits");
+    if (bin1 && dim >= (1u << 24)) return fail(SCANN_HIP_OUT_OF_RANGE, "bit rows: a count of 2^24 bits or more is not exact in f32");
     if ((row_format == SCANN_HIP_ROWS_INT8 || int4) && !std::isfinite(inv_multiplier))
         return fail(SCANN_HIP_INVALID_ARGUMENT, "inv_multiplier is not finite");
     if (measure == SCANN_HIP_L1 || measure == SCANN_HIP_COSINE)
         return fail(SCANN_HIP_UNIMPLEMENTED, "quantized rows: SquaredL2, L2 and DotProduct only");
-    if (measure < SCANN_HIP_SQUARED_L2 || measure > SCANN_HIP_DOT_PRODUCT)
+    if (!bin1 && (measure < SCANN_HIP_SQUARED_L2 || measure > SCANN_HIP_DOT_PRODUCT))
         return fail(SCANN_HIP_UNIMPLEMENTED, "unknown distance measure");
     if (n >= 0xFFFFFFFFull) return fail(SCANN_HIP_OUT_OF_RANGE, "DatapointIndex is u32");
     SCANN_TRY(set_device(ctx));
     auto *ix = new scann_hip_index();
     ix->ctx = ctx;
     ix->kind = KIND_BF;
-    const size_t bytes = int4 ? (size_t)n * (stride / 2) : (size_t)n * stride * (row_format == SCANN_HIP_ROWS_BF16 ? 2 : 1);
+    const size_t bytes = (size_t)n * quant_row_bytes(row_format, stride);
     int s = index_common_init(ix);
     if (s == SCANN_HIP_OK) s = upload(ix->bf_rows, rows, bytes);
     if (s != SCANN_HIP_OK) {

@@ -12,6 +12,7 @@ struct BfIndexDev {
     int measure;         // scann_hip_measure
     // quantized rows (scann_hip_bf_create_quantized): fmt = SCANN_HIP_ROWS_BF16 / _FP8_E4M3 / _INT8 / _INT4, qrows =
     // [n][stride] elements of that format (INT4: stride / 2 bytes a row); every pass takes bf_quant_kernel.  fmt 0 = f32 rows above.
+    // SCANN_HIP_ROWS_BIN1 (measure SCANN_HIP_HAMMING only): stride / 8 bytes a row, every pass takes bf_bin.hip's kernels.
     int fmt;
     const void *qrows;
     float inv_mult;      // INT8 / INT4: value = (float)code * inv_mult
@@ -26,6 +27,7 @@ struct BfWorkspace {
     DevBuf queries, sample, thr, cand_cnt, cand, counters, out_idx, out_dist, out_count;
     DevBuf q_b, q_bl, q_n2, sl_idx, sl_approx, sl_cnt, sl_exact, sl_fail;   // bf16 shortlist path
     DevBuf q_err;   // integer shortlist pass (bf_int.hip; q_b / q_bl hold its digit planes / weights)
+    DevBuf q_bits;  // bit rows (bf_bin.hip): the batch's queries as packed words, bf_bin_query_bytes
     DevBuf allow, ids, allow_sums;   // filtered search: bitmap copy, compacted id list, per-block popcounts
 };
 
@@ -46,7 +48,37 @@ struct BfPass {
     const uint32_t *ids;    // compacted form: real row = ids[virtual row * row_mult], ascending allowed datapoints
     const uint64_t *allow;  // bit-test form: a row is a candidate only if its bit is set (tested at the emit)
     uint32_t allow_bits;    // capacity of the bitmap clipped to the row count
+    const uint32_t *qbits;  // bit rows only: the queries packed by bf_bin_pack_queries, [nq][stride / 32] words
 };
+
+// datapoint index of a virtual row (the row that is read, and the index half of its key)
+__device__ __forceinline__ uint32_t bf_real_row(const BfPass &p, uint32_t vrow) {
+    const uint32_t r = vrow * p.row_mult;
+    return p.ids ? p.ids[r] : r;
+}
+
+// RestrictFilter::is_allowed (restricts/mod.rs:17-30) on the bitmap form: indices at or past the capacity are
+// not allowed (allowlist.rs:97-100).
+__device__ __forceinline__ bool bf_row_allowed(const uint64_t *allow, uint32_t allow_bits, uint32_t row) {
+    return row < allow_bits && ((allow[row >> 6] >> (row & 63u)) & 1ull);
+}
+
+// what every scoring kernel does with a distance: the dense store of a sample / matrix pass, or the threshold test
+// and the append to the query's candidate list (Tf = the distance half of the bound T)
+__device__ __forceinline__ void bf_emit(const BfPass &p, uint32_t q, uint32_t vrow, float dist,
+                                        float Tf, uint64_t T) {
+    if (!p.filter) {
+        p.out[(size_t)q * p.ld + vrow] = dist;
+    } else if (dist <= Tf) {
+        const uint32_t row = bf_real_row(p, vrow);
+        if (p.allow && !bf_row_allowed(p.allow, p.allow_bits, row)) return;   // skipped before scoring: mod.rs:327-332
+        const uint64_t key = make_key(dist, row);
+        if (key <= T) {
+            const uint32_t pos = atomicAdd(&p.cand_cnt[q], 1u);
+            if (pos < p.cap) p.cand[(size_t)q * p.cap + pos] = key;
+        }
+    }
+}
 
 // the distance half of a threshold key as a float; the no-bound key is +inf
 __device__ __forceinline__ float bf_thr_float(uint64_t T) {
@@ -101,6 +133,16 @@ int bf_search_device(const BfIndexDev &ix, BfWorkspace &w, const float *d_querie
                      hipEvent_t ev1);
 // OK, or the status the last enqueued search left in the workspace counters (synchronises).
 int bf_last_status(const BfWorkspace &w, hipStream_t stream);
+
+// ---- bit rows (SCANN_HIP_ROWS_BIN1, Hamming distance): bf_bin.hip, DESIGN.md 3.3b-ii ----
+// bytes of the packed form of nq queries: stride / 32 words each
+size_t bf_bin_query_bytes(const BfIndexDev &ix, uint32_t nq);
+// f32 queries -> words (bit j = q[j] != 0, bits dim .. stride - 1 clear).  Enqueue only.
+int bf_bin_pack_queries(const BfIndexDev &ix, const float *d_queries, uint32_t nq, uint32_t q_stride, uint32_t *d_qbits,
+                        hipStream_t stream);
+// any pass of launch_pass over bit rows (p.qbits set); the name of the kernel it takes for a batch of nq queries
+int bf_bin_pass(const BfIndexDev &ix, const BfPass &p, hipStream_t stream);
+const char *bf_bin_kernel_name(const BfIndexDev &ix, uint32_t nq);
 
 // half::bf16::from_f32 over n values (scann_hip_bf16_quantize), host in / host out.
 int bf16_quantize_host(const float *values, uint64_t n, uint16_t *out_bits, hipStream_t stream);

@@ -37,33 +37,6 @@ constexpr uint32_t kBfInvalid = 0xFFFFFFFFu;
 
 enum { BF_CNT_STATUS = 0, BF_CNT_N = 4 };
 
-// datapoint index of a virtual row (the row that is read, and the index half of its key)
-__device__ __forceinline__ uint32_t bf_real_row(const BfPass &p, uint32_t vrow) {
-    const uint32_t r = vrow * p.row_mult;
-    return p.ids ? p.ids[r] : r;
-}
-
-// RestrictFilter::is_allowed (restricts/mod.rs:17-30) on the bitmap form: indices at or past the capacity are
-// not allowed (allowlist.rs:97-100).
-__device__ __forceinline__ bool bf_row_allowed(const uint64_t *allow, uint32_t allow_bits, uint32_t row) {
-    return row < allow_bits && ((allow[row >> 6] >> (row & 63u)) & 1ull);
-}
-
-__device__ __forceinline__ void bf_emit(const BfPass &p, uint32_t q, uint32_t vrow, float dist,
-                                        float Tf, uint64_t T) {
-    if (!p.filter) {
-        p.out[(size_t)q * p.ld + vrow] = dist;
-    } else if (dist <= Tf) {
-        const uint32_t row = bf_real_row(p, vrow);
-        if (p.allow && !bf_row_allowed(p.allow, p.allow_bits, row)) return;   // skipped before scoring: mod.rs:327-332
-        const uint64_t key = make_key(dist, row);
-        if (key <= T) {
-            const uint32_t pos = atomicAdd(&p.cand_cnt[q], 1u);
-            if (pos < p.cap) p.cand[(size_t)q * p.cap + pos] = key;
-        }
-    }
-}
-
 // =====================================================================================
 // Generic VALU kernel: any dim, all three measures; one row per thread, QT queries from
 // LDS.  Arithmetic = simd/x86.rs:139-165 / :72-96 lane for lane.
@@ -1691,10 +1664,15 @@ static int launch_quant_pass(const BfIndexDev &ix, const BfPass &p, hipStream_t 
 }
 
 // name of the kernel that scores the rows on the shortlist path (timing reports)
-const char *bf_shortlist_kernel_name(const BfIndexDev &ix) { return bf_int_eligible(ix) ? "bf_i8mfma_kernel" : "bf_bf16_kernel"; }
+// (bit rows have no shortlist: the name is that of their one pass)
+const char *bf_shortlist_kernel_name(const BfIndexDev &ix) {
+    if (ix.fmt == SCANN_HIP_ROWS_BIN1) return bf_bin_kernel_name(ix, 0);
+    return bf_int_eligible(ix) ? "bf_i8mfma_kernel" : "bf_bf16_kernel";
+}
 
 // name of the kernel launch_pass picks for a batch of nq queries (timing reports)
 const char *bf_pass_kernel_name(const BfIndexDev &ix, uint32_t nq) {
+    if (ix.fmt == SCANN_HIP_ROWS_BIN1) return bf_bin_kernel_name(ix, nq);
     if (ix.fmt) return "bf_quant_kernel";
     BfPass p{};
     p.nq = nq;
@@ -1711,11 +1689,13 @@ static size_t generic_lds_bytes(uint32_t dim) {
 }
 
 bool bf_pass_fits(const BfIndexDev &ix) {
+    if (ix.fmt == SCANN_HIP_ROWS_BIN1) return true;   // a fixed chunk of the packed queries in LDS, whatever the dim
     return ix.fmt ? (size_t)ix.dim * 2 * sizeof(float) <= kMaxLdsBytes : generic_lds_bytes(ix.dim) <= kMaxLdsBytes;
 }
 
 static int launch_pass(const BfIndexDev &ix, const BfPass &p, hipStream_t st) {
     if (p.nq == 0 || p.nrows == 0) return SCANN_HIP_OK;
+    if (ix.fmt == SCANN_HIP_ROWS_BIN1) return bf_bin_pass(ix, p, st);
     if (ix.fmt) return launch_quant_pass(ix, p, st);
     if (stream_eligible(ix, p)) {
         const size_t lds = stream_lds_bytes(ix.dim);
@@ -1767,7 +1747,7 @@ static int make_plan(uint32_t n, uint32_t k, bool full_cap, BfPlan *pl) {
 
 static int ensure_ws(const BfIndexDev &ix, BfWorkspace &w, uint32_t nq, const BfPlan &pl,
                      bool own_q, uint32_t q_stride, bool own_out) {
-    (void)ix;
+    if (ix.fmt == SCANN_HIP_ROWS_BIN1) SCANN_TRY(w.q_bits.ensure(std::max<size_t>(bf_bin_query_bytes(ix, nq), 4)));
     if (own_q) SCANN_TRY(w.queries.ensure((size_t)nq * q_stride * 4));
     SCANN_TRY(w.sample.ensure((size_t)nq * pl.ns * 4));
     SCANN_TRY(w.thr.ensure((size_t)nq * 8));
@@ -1854,6 +1834,10 @@ static int enqueue_search(const BfIndexDev &ix, BfWorkspace &w, const BfPlan &pl
     a.ids = fd.ids;
     a.allow = fd.allow;
     a.allow_bits = fd.allow_bits;
+    if (ix.fmt == SCANN_HIP_ROWS_BIN1) {   // bit rows: the batch's queries as words, once for both passes
+        SCANN_TRY(bf_bin_pack_queries(ix, d_queries, nq, q_stride, w.q_bits.as<uint32_t>(), st));
+        a.qbits = w.q_bits.as<uint32_t>();
+    }
     if (pl.direct && ev0) SCANN_HIP_CHECK(hipEventRecord(ev0, st));
     SCANN_TRY(launch_pass(ix, a, st));
     if (pl.direct && ev1) SCANN_HIP_CHECK(hipEventRecord(ev1, st));
@@ -1905,6 +1889,7 @@ static bool shortlist_dims_ok(uint32_t dim) {
 int bf_build_shortlist_data(const BfIndexDev &ix, DevBuf &rows_b, DevBuf &rows_bl, DevBuf &norm2,
                             float *max_norm, hipStream_t st) {
     *max_norm = 0.0f;
+    if (ix.fmt == SCANN_HIP_ROWS_BIN1) return SCANN_HIP_OK;   // bit rows: every distance is exact, nothing to shortlist
     if (ix.n == 0 || !shortlist_dims_ok(ix.dim)) return SCANN_HIP_OK;
     // SCANN_HIP_BF_SHORTLIST_MIN_ROWS: below this the exact kernels are fast enough (tests set 1)
     if (ix.n < read_knobs().bf_shortlist_min_rows) return SCANN_HIP_OK;
@@ -2236,13 +2221,23 @@ int bf16_quantize_host(const float *values, uint64_t n, uint16_t *out_bits, hipS
     return SCANN_HIP_OK;
 }
 
+// bit rows: a pass made outside enqueue_search packs its queries here (no-op for every other format)
+static int bin_pass_queries(const BfIndexDev &ix, BfWorkspace &w, const float *d_queries, uint32_t nq, uint32_t q_stride,
+                            BfPass *p, hipStream_t st) {
+    if (ix.fmt != SCANN_HIP_ROWS_BIN1) return SCANN_HIP_OK;
+    SCANN_TRY(w.q_bits.ensure(std::max<size_t>(bf_bin_query_bytes(ix, nq), 4)));
+    SCANN_TRY(bf_bin_pack_queries(ix, d_queries, nq, q_stride, w.q_bits.as<uint32_t>(), st));
+    p->qbits = w.q_bits.as<uint32_t>();
+    return SCANN_HIP_OK;
+}
+
 int bf_distances_host(const BfIndexDev &ix, BfWorkspace &w, const float *queries, uint32_t nq,
                       uint32_t q_stride, float *out, hipStream_t st) {
     DevBuf dq, dout;
-    (void)w;
     SCANN_TRY(upload(dq, queries, (size_t)nq * q_stride * 4));
     SCANN_TRY(dout.ensure((size_t)nq * ix.n * 4));
     BfPass a{};
+    SCANN_TRY(bin_pass_queries(ix, w, dq.as<float>(), nq, q_stride, &a, st));
     a.queries = dq.as<float>();
     a.nq = nq;
     a.q_stride = q_stride;
@@ -2299,6 +2294,7 @@ int bf_search_radius_host(const BfIndexDev &ix, BfWorkspace &w, const float *que
     SCANN_TRY(dcand.ensure((size_t)allowed * 8));
     SCANN_HIP_CHECK(hipMemsetAsync(dcnt.p, 0, 4, st));
     BfPass b{};
+    SCANN_TRY(bin_pass_queries(ix, w, dq.as<float>(), 1, q_stride, &b, st));
     b.queries = dq.as<float>();
     b.nq = 1;
     b.q_stride = q_stride;

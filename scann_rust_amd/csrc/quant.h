@@ -14,7 +14,11 @@ __host__ __device__ constexpr uint32_t quant_bytes() { return FMT == SCANN_HIP_R
 // (Int4PackedData, quantization/scalar.rs:354-389): element j is the low (even j) or high (odd j) nibble of byte j / 2.
 template <int FMT>
 __host__ __device__ constexpr size_t quant_row_bytes(size_t elems) {
-    return FMT == SCANN_HIP_ROWS_INT4 ? elems / 2 : elems * quant_bytes<FMT>();
+    return FMT == SCANN_HIP_ROWS_BIN1 ? elems / 8 : FMT == SCANN_HIP_ROWS_INT4 ? elems / 2 : elems * quant_bytes<FMT>();
+}
+// the same for a format known at run time (uploads, footprints).  BIN1: element j is bit j & 7 of byte j >> 3
+__host__ __device__ constexpr size_t quant_row_bytes(int fmt, size_t elems) {
+    return fmt == SCANN_HIP_ROWS_BIN1 ? elems / 8 : fmt == SCANN_HIP_ROWS_INT4 ? elems / 2 : elems * (fmt == SCANN_HIP_ROWS_BF16 ? 2u : 1u);
 }
 // INT4 and INT8 share one arithmetic: x = (float)code * inv_multiplier, 8 fused chains (one_to_many_int8_float_*)
 template <int FMT>

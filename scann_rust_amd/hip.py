@@ -17,6 +17,7 @@ OK, INVALID_ARGUMENT, RESOURCE_EXHAUSTED, FAILED_PRECONDITION = 0, 3, 8, 9
 NOT_FOUND, ABORTED = 5, 10
 OUT_OF_RANGE, UNIMPLEMENTED, INTERNAL, UNAVAILABLE = 11, 12, 13, 14
 SQUARED_L2, L2, DOT_PRODUCT, L1, COSINE = 0, 1, 2, 3, 4
+HAMMING = 5   # bit rows (ROWS_BIN1) in bf_create_quantized only
 MMR_MAX_DEPTH = 2048    # SCANN_HIP_MMR_MAX_DEPTH
 CROWD_MAX_DIMS = 8      # SCANN_HIP_CROWD_MAX_DIMS
 MUTABLE_MAX_CAPACITY = 65536   # SCANN_HIP_MUTABLE_MAX_CAPACITY
@@ -1411,7 +1412,13 @@ def bf_create(data, n, dim, stride, measure, device=0):
 
 ROWS_BF16, ROWS_FP8_E4M3, ROWS_INT8 = 1, 2, 3
 ROWS_INT4 = 5   # Int4PackedData: two offset-binary nibbles per byte, stride / 2 bytes a row
-_ROWS_DTYPE = {ROWS_BF16: np.uint16, ROWS_FP8_E4M3: np.uint8, ROWS_INT8: np.int8, ROWS_INT4: np.uint8}
+ROWS_BIN1 = 6   # one bit per element, stride / 8 bytes a row, element j = bit j & 7 of byte j >> 3; measure HAMMING
+_ROWS_DTYPE = {ROWS_BF16: np.uint16, ROWS_FP8_E4M3: np.uint8, ROWS_INT8: np.int8, ROWS_INT4: np.uint8, ROWS_BIN1: np.uint8}
+
+
+def _row_items(fmt, n, stride):
+    """Items of the format's dtype in n rows of `stride` elements."""
+    return n * (stride // 8 if fmt == ROWS_BIN1 else stride // 2 if fmt == ROWS_INT4 else stride)
 
 
 def pack_int4(codes_i8):
@@ -1423,6 +1430,17 @@ def pack_int4(codes_i8):
     return nib[..., 0::2] | (nib[..., 1::2] << np.uint8(4))
 
 
+def pack_bits(bits01):
+    """ROWS_BIN1 bytes of 0/1 (or boolean) values over the last axis: element j is bit j & 7 of byte j >> 3
+    (numpy.packbits, bitorder="little"); a last axis that is no multiple of 8 is padded with 0 bits."""
+    return np.packbits(np.asarray(bits01) != 0, axis=-1, bitorder="little")
+
+
+def unpack_bits(packed, n_elems):
+    """The first n_elems bits (uint8 0/1) of each row of packed bytes (last axis)."""
+    return np.unpackbits(np.asarray(packed, np.uint8), axis=-1, count=n_elems, bitorder="little")
+
+
 def unpack_int4(packed, n_elems):
     """The first n_elems int8 codes (nibble - 8) of each row of packed bytes (last axis)."""
     b = np.asarray(packed, np.uint8)
@@ -1432,14 +1450,14 @@ def unpack_int4(packed, n_elems):
 
 def bf_create_quantized(rows, n, dim, stride, fmt, measure, inv_multiplier=1.0, device=0):
     """Brute force over rows stored as bf16 bits (uint16), the reference's E4M3 codes (uint8), int8
-    (value = i8 * inv_multiplier) or packed int4 (ROWS_INT4: pack_int4 bytes, stride in ELEMENTS, stride / 2 bytes a
-    row): scann_hip_bf_create_quantized.  The returned Index's search methods,
+    (value = i8 * inv_multiplier), packed int4 (ROWS_INT4: pack_int4 bytes, stride in ELEMENTS, stride / 2 bytes a
+    row) or bits (ROWS_BIN1 with measure HAMMING: pack_bits bytes, dim and stride in BITS, stride % 32 == 0, stride / 8
+    bytes a row; queries stay float32, bit j = q[j] != 0): scann_hip_bf_create_quantized.  The returned Index's search methods,
     bf_distances and bf_search_radius work as for bf_create."""
     dt = _ROWS_DTYPE.get(fmt, np.uint8)
     r = np.ascontiguousarray(rows).view(dt) if n else None
-    if r is not None and r.size < (n * (stride // 2) if fmt == ROWS_INT4 else n * stride):
-        raise ValueError("rows holds %d elements of its dtype, the handle needs %d" %
-                         (r.size, n * (stride // 2) if fmt == ROWS_INT4 else n * stride))
+    if r is not None and r.size < _row_items(fmt, n, stride):
+        raise ValueError("rows holds %d elements of its dtype, the handle needs %d" % (r.size, _row_items(fmt, n, stride)))
     h = vp()
     check(load().scann_hip_bf_create_quantized(context(device), r.ctypes.data if n else None, n, dim, stride, fmt,
                                                float(np.float32(inv_multiplier)), measure, C.byref(h)))
