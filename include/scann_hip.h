@@ -1697,6 +1697,56 @@ void scann_hip_sparse_last_plan(scann_hip_sparse_index *index, uint64_t *out);
 int scann_hip_sparse_build_postings(scann_hip_sparse_index *index);
 void scann_hip_sparse_postings_info(scann_hip_sparse_index *index, uint64_t *out);
 
+/* ---- stacked / additive quantizers --------------------------------------------------------
+ * StackedQuantizer and AdditiveQuantizer (hashes/stacked.rs) as one handle kind: num_levels codebooks,
+ * level l with S_l = subspaces[l] subspaces of K_l = num_codes[l] codes over dim / S_l dimensions each (the additive form
+ * is S_l = 1).  codebooks: level after level, each [S_l][K_l][dim / S_l] f32.  A row is T = S_0 + ... + S_{L-1} code
+ * bytes, level-major.  Every f32 operation below is unfused and every sum sequential from 0.0f in ascending order.
+ * Encode (stacked.rs:131-154): r = row; for l ascending, for every subspace s the code c with the smallest
+ *   d_c = sum_j (r[s * dsub_l + j] - cb_l[s][c][j])^2 (strict < from +inf: the lowest index wins a tie, all-NaN gives 0);
+ *   then r[j] = r[j] - centroid[j].  out_residual_sq[i] (may be NULL) = sum_j r_j^2 of the last residual.
+ * Decode (stacked.rs:157-172): x^ = 0.0f; for l ascending x^[j] += centroid_l[j].
+ * Distance of query q to stored row i: lut[l][s][c] = sum_j q[s * dsub_l + j] * cb_l[s][c][j]; acc = 0.0f; for l, s
+ *   ascending acc += lut[l][s][code];  SCANN_HIP_DOT_PRODUCT: d = -acc;  SCANN_HIP_SQUARED_L2: d = (qq + xx_i) - 2.0f * acc
+ *   with qq, xx_i the sums of squares of q and of the decoded row (xx_i is computed on the device when rows or codes are
+ *   set).  L2 / L1 / Cosine -> Unimplemented.
+ * scann_hip_stacked_set_rows encodes host rows on the device, all levels in one launch per batch, and keeps codes and
+ * norms there; scann_hip_stacked_set_codes takes codes [n][T] encoded earlier.  Either replaces the handle's rows; n == 0
+ * is legal.  A search or scann_hip_stacked_distances before one of them -> FailedPrecondition.
+ * Results of a search: the k smallest rows by (f32_to_ordered(d), row), ascending; out_count[q] = min(k, rows allowed);
+ * slots past it hold 0xFFFFFFFF and +NaN.  1 <= k <= SCANN_HIP_STACKED_MAX_K; k > n is legal.  allow_bitmap: exactly as
+ * scann_hip_sparse_search_batched's.  scann_hip_stacked_distances: out [nq][n] f32, the scan and the measure alone.
+ * REFUSED, InvalidArgument unless said: dim % S_l != 0; K_l outside 2..256; num_levels outside
+ * 1..SCANN_HIP_STACKED_MAX_LEVELS; T > SCANN_HIP_STACKED_MAX_CODES; dim > SCANN_HIP_STACKED_MAX_DIM -> Unimplemented (the
+ * encode keeps a tile of at least 4 rows' residuals in 64 KB of LDS); stride or q_stride < dim; a code >= K_l in
+ * scann_hip_stacked_set_codes or _decode (checked on the device; the handle keeps the rows it had); k outside its range;
+ * n >= 2^32 - 1 -> OutOfRange.
+ * scann_hip_stacked_info: out holds 9 values: [0] levels, [1] T, [2] bytes of the handle's persistent device arrays,
+ * [3] rows of an encode tile; of the last scan [4] table slabs, [5] rows per chunk, [6] chunks, [7] query quads per
+ * workgroup, [8] query groups.  scann_hip_stacked_last_kernel_ms: out_ms[0] the encode kernels of the last
+ * scann_hip_stacked_encode / _set_rows, [1] table build, [2] scan, [3] merge of the last search (device events).
+ * One call at a time per handle (serialised inside).  Every entry synchronises. */
+typedef struct scann_hip_stacked scann_hip_stacked;
+#define SCANN_HIP_STACKED_MAX_LEVELS 8
+#define SCANN_HIP_STACKED_MAX_CODES 256 /* T: code bytes of a row */
+#define SCANN_HIP_STACKED_MAX_DIM 4095
+#define SCANN_HIP_STACKED_MAX_K 256
+int scann_hip_stacked_create(scann_hip_ctx *ctx, uint32_t dim, uint32_t num_levels, const uint32_t *subspaces,
+                             const uint32_t *num_codes, const float *codebooks, int measure, scann_hip_stacked **out);
+void scann_hip_stacked_destroy(scann_hip_stacked *sq);
+int scann_hip_stacked_encode(scann_hip_stacked *sq, const float *rows, uint64_t n, uint32_t stride, uint8_t *out_codes,
+                             float *out_residual_sq);
+int scann_hip_stacked_decode(scann_hip_stacked *sq, const uint8_t *codes, uint64_t n, float *out_rows);
+int scann_hip_stacked_set_rows(scann_hip_stacked *sq, const float *rows, uint64_t n, uint32_t stride);
+int scann_hip_stacked_set_codes(scann_hip_stacked *sq, const uint8_t *codes, uint64_t n);
+int scann_hip_stacked_distances(scann_hip_stacked *sq, const float *queries, uint32_t nq, uint32_t q_stride, float *out);
+int scann_hip_stacked_search_batched(scann_hip_stacked *sq, const float *queries, uint32_t nq, uint32_t q_stride, uint32_t k,
+                                     const uint64_t *allow_bitmap, uint64_t allow_bitmap_bits, uint32_t *out_idx,
+                                     float *out_dist, uint32_t *out_count);
+uint64_t scann_hip_stacked_size(const scann_hip_stacked *sq);
+void scann_hip_stacked_info(const scann_hip_stacked *sq, uint64_t *out);
+void scann_hip_stacked_last_kernel_ms(scann_hip_stacked *sq, float *out_ms);
+
 /* ---- introspection ------------------------------------------------------------- */
 uint64_t scann_hip_index_size(const scann_hip_index *index);          /* Searcher::dataset_size */
 uint32_t scann_hip_index_dimensionality(const scann_hip_index *index);/* Searcher::dimensionality */

@@ -292,6 +292,14 @@ __global__ __launch_bounds__(kMergeThreads) void sparse_merge_kernel(const uint6
 }
 
 }  // namespace
+
+int sparse_merge(const uint64_t *partial, uint32_t nq, uint32_t chunks, uint32_t k, uint32_t *out_idx, float *out_dist,
+                 uint32_t *out_count, hipStream_t stream) {
+    const uint32_t total = chunks * k, npad = next_pow2_u32(total);
+    return launch(sparse_merge_kernel, dim3(nq), dim3(kMergeThreads), (size_t)npad * 8, stream, partial, total, npad, k, out_idx, out_dist,
+                  out_count);
+}
+
 }  // namespace scann
 
 using namespace scann;
@@ -418,9 +426,8 @@ int sparse_run(scann_hip_sparse_index *ix, const uint64_t *q_offsets, const uint
     }
     SCANN_HIP_CHECK(hipEventRecord(ix->ev[1], st));
     if (select) {
-        const uint32_t total = chunks * k, npad = next_pow2_u32(total);
-        SCANN_TRY(launch(sparse_merge_kernel, dim3(nq), dim3(kMergeThreads), (size_t)npad * 8, st, ix->partial.as<uint64_t>(), total, npad, k,
-                         ix->out_idx.as<uint32_t>(), ix->out_dist.as<float>(), ix->out_count.as<uint32_t>()));
+        SCANN_TRY(sparse_merge(ix->partial.as<uint64_t>(), nq, chunks, k, ix->out_idx.as<uint32_t>(), ix->out_dist.as<float>(),
+                               ix->out_count.as<uint32_t>(), st));
     }
     SCANN_HIP_CHECK(hipEventRecord(ix->ev[2], st));
     if (select) {

@@ -75,13 +75,19 @@ __device__ __forceinline__ float sparse_distance(int measure, float acc, uint32_
     }
 }
 
-// NBUF buffers of 2^cap_log keys each, sorted ascending side by side: one barrier per pass for all of them
-template <uint32_t NBUF>
+// sparse.hip: the merge of a search's chunk partials ([nq][chunks][k] keys, chunks * k <= kSparseMergeKeys) into the final
+// rows, enqueued on `stream`; the stacked-quantizer scan (stacked.hip) ends in it too
+int sparse_merge(const uint64_t *partial, uint32_t nq, uint32_t chunks, uint32_t k, uint32_t *out_idx, float *out_dist,
+                 uint32_t *out_count, hipStream_t stream);
+
+// NBUF buffers of 2^cap_log keys each, sorted ascending side by side: one barrier per pass for all of them.  THREADS: the
+// workgroup's size.
+template <uint32_t NBUF, uint32_t THREADS = kSparseThreads>
 __device__ void sparse_sort_buffers(uint64_t *buf, uint32_t cap_log) {
     const uint32_t half_log = cap_log - 1, pairs = NBUF << half_log;
     for (uint32_t lk = 1; lk <= cap_log; ++lk) {
         for (int lj = (int)lk - 1; lj >= 0; --lj) {
-            for (uint32_t i = threadIdx.x; i < pairs; i += kSparseThreads) {
+            for (uint32_t i = threadIdx.x; i < pairs; i += THREADS) {
                 const uint32_t b = i >> half_log, ii = i & ((1u << half_log) - 1);
                 const uint32_t lo = ((ii >> lj) << (lj + 1)) | (ii & ((1u << lj) - 1)), hi = lo + (1u << lj);
                 uint64_t *p = buf + ((size_t)b << cap_log);
@@ -98,12 +104,12 @@ __device__ void sparse_sort_buffers(uint64_t *buf, uint32_t cap_log) {
 }
 
 // pads every buffer past its count, sorts, cuts to k and moves the thresholds.  Every thread of the workgroup calls.
-template <uint32_t NBUF>
+template <uint32_t NBUF, uint32_t THREADS = kSparseThreads>
 __device__ void sparse_compact(uint64_t *buf, uint32_t cap_log, uint32_t k, uint32_t *cnt, uint64_t *thr) {
-    for (uint32_t i = threadIdx.x; i < (NBUF << cap_log); i += kSparseThreads)
+    for (uint32_t i = threadIdx.x; i < (NBUF << cap_log); i += THREADS)
         if ((i & ((1u << cap_log) - 1)) >= cnt[i >> cap_log]) buf[i] = SCANN_KEY_MAX;
     __syncthreads();
-    sparse_sort_buffers<NBUF>(buf, cap_log);
+    sparse_sort_buffers<NBUF, THREADS>(buf, cap_log);
     if (threadIdx.x < NBUF) {
         const uint32_t c = min(cnt[threadIdx.x], k);
         cnt[threadIdx.x] = c;

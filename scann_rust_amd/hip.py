@@ -36,6 +36,7 @@ SPARSE_TILE_SLOTS = 1024       # SCANN_HIP_SPARSE_TILE_SLOTS: the sum of a tile'
 SPARSE_MAP_SIZE = 2048         # SCANN_HIP_SPARSE_MAP_SIZE: entries of the LDS dimension -> slot map; home of d is d % SPARSE_MAP_SIZE
 SPARSE_MAX_K = 256             # SCANN_HIP_SPARSE_MAX_K
 SPARSE_BLOCK_ROWS = 16384      # SCANN_HIP_SPARSE_BLOCK_ROWS: rows of a posting-list block (SparseIndex.build_postings)
+STACKED_MAX_LEVELS, STACKED_MAX_CODES, STACKED_MAX_DIM, STACKED_MAX_K = 8, 256, 4095, 256   # SCANN_HIP_STACKED_*: limits of a StackedIndex
 
 _CODE_NAMES = {
     0: "Ok", 1: "Cancelled", 2: "Unknown", 3: "InvalidArgument", 4: "DeadlineExceeded",
@@ -94,6 +95,9 @@ EXPORTS = [
     "scann_hip_sparse_search_batched", "scann_hip_sparse_distances", "scann_hip_sparse_last_kernel_ms",
     "scann_hip_sparse_enable_stats", "scann_hip_sparse_last_plan", "scann_hip_sparse_build_postings",
     "scann_hip_sparse_postings_info",
+    "scann_hip_stacked_create", "scann_hip_stacked_destroy", "scann_hip_stacked_encode", "scann_hip_stacked_decode",
+    "scann_hip_stacked_set_rows", "scann_hip_stacked_set_codes", "scann_hip_stacked_distances",
+    "scann_hip_stacked_search_batched", "scann_hip_stacked_size", "scann_hip_stacked_info", "scann_hip_stacked_last_kernel_ms",
 ]
 
 
@@ -445,6 +449,21 @@ def load():
     L.scann_hip_sparse_build_postings.argtypes = [vp]
     L.scann_hip_sparse_postings_info.argtypes = [vp, u64p]
     L.scann_hip_sparse_postings_info.restype = None
+    L.scann_hip_stacked_create.argtypes = [vp, C.c_uint32, C.c_uint32, u32p, u32p, f32p, C.c_int, C.POINTER(vp)]
+    L.scann_hip_stacked_destroy.argtypes = [vp]
+    L.scann_hip_stacked_destroy.restype = None
+    L.scann_hip_stacked_encode.argtypes = [vp, f32p, C.c_uint64, C.c_uint32, u8p, f32p]
+    L.scann_hip_stacked_decode.argtypes = [vp, u8p, C.c_uint64, f32p]
+    L.scann_hip_stacked_set_rows.argtypes = [vp, f32p, C.c_uint64, C.c_uint32]
+    L.scann_hip_stacked_set_codes.argtypes = [vp, u8p, C.c_uint64]
+    L.scann_hip_stacked_distances.argtypes = [vp, f32p, C.c_uint32, C.c_uint32, f32p]
+    L.scann_hip_stacked_search_batched.argtypes = [vp, f32p, C.c_uint32, C.c_uint32, C.c_uint32, u64p, C.c_uint64, u32p, f32p, u32p]
+    L.scann_hip_stacked_size.argtypes = [vp]
+    L.scann_hip_stacked_size.restype = C.c_uint64
+    L.scann_hip_stacked_info.argtypes = [vp, u64p]
+    L.scann_hip_stacked_info.restype = None
+    L.scann_hip_stacked_last_kernel_ms.argtypes = [vp, f32p]
+    L.scann_hip_stacked_last_kernel_ms.restype = None
     _lib = L
     return L
 
@@ -1201,6 +1220,112 @@ class SparseIndex:
         p = np.zeros(5, np.uint64)
         load().scann_hip_sparse_last_plan(self.h, ptr(p, u64p))
         return dict(zip(("tiles", "chunks", "elements", "probes", "hits"), (int(x) for x in p)))
+
+
+def _rows2d(a, dim, what):
+    """(contiguous float32 [n, stride] array, n, stride) of rows whose first `dim` columns count"""
+    a = np.asarray(a, np.float32)
+    if a.ndim != 2 or a.shape[1] < dim:
+        raise ValueError("%s must be [n, >= %d], got %s" % (what, dim, a.shape))
+    a = np.ascontiguousarray(a)
+    return a, a.shape[0], a.shape[1]
+
+
+class StackedIndex:
+    """Owns one scann_hip_stacked: a stacked / additive quantizer (hashes/stacked.rs) with its codes
+    resident on the device.  codebooks: one float32 [S_l, K_l, dim / S_l] array per level (trainer.train_stacked makes
+    them; S_l = 1 throughout is the additive form).  encode / decode work on host arrays; set_rows (encode on the device)
+    or set_codes make the rows that distances and search_batched scan.  Rows and queries may be wider than dim: the
+    array's second axis is the stride."""
+
+    def __init__(self, codebooks, measure=DOT_PRODUCT, device=0):
+        cbs = [f32(c) for c in codebooks]
+        if not cbs or any(c.ndim != 3 for c in cbs):
+            raise ValueError("codebooks: one [S, K, dsub] array per level")
+        self.dim = cbs[0].shape[0] * cbs[0].shape[2]
+        self.subspaces = np.array([c.shape[0] for c in cbs], np.uint32)
+        self.num_codes = np.array([c.shape[1] for c in cbs], np.uint32)
+        self.T, self.measure = int(self.subspaces.sum()), measure
+        flat = np.concatenate([c.ravel() for c in cbs])
+        if any(c.shape[0] * c.shape[2] != self.dim for c in cbs):
+            raise ValueError("every level's S * dsub must be the same dim")
+        self.h = vp()
+        check(load().scann_hip_stacked_create(context(device), self.dim, len(cbs), ptr(self.subspaces, u32p),
+                                              ptr(self.num_codes, u32p), ptr(flat, f32p), measure, C.byref(self.h)))
+
+    def close(self):
+        if self.h:
+            load().scann_hip_stacked_destroy(self.h)
+            self.h = None
+
+    destroy = close
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def encode(self, rows, residual_sq=False):
+        """codes uint8 [n, T] (level-major); with residual_sq=True also the float32 [n] squared norms of the last residuals"""
+        a, n, stride = _rows2d(rows, self.dim, "rows")
+        codes = np.empty((n, self.T), np.uint8)
+        res = np.empty(n, np.float32) if residual_sq else None
+        check(load().scann_hip_stacked_encode(self.h, ptr(a, f32p), n, stride, ptr(codes, u8p), ptr(res, f32p)))
+        return (codes, res) if residual_sq else codes
+
+    def decode(self, codes):
+        c = np.ascontiguousarray(codes, np.uint8).reshape(-1, self.T)
+        out = np.empty((c.shape[0], self.dim), np.float32)
+        check(load().scann_hip_stacked_decode(self.h, ptr(c, u8p), c.shape[0], ptr(out, f32p)))
+        return out
+
+    def set_rows(self, rows):
+        a, n, stride = _rows2d(rows, self.dim, "rows")
+        check(load().scann_hip_stacked_set_rows(self.h, ptr(a, f32p), n, stride))
+
+    def set_codes(self, codes):
+        c = np.ascontiguousarray(codes, np.uint8).reshape(-1, self.T)
+        check(load().scann_hip_stacked_set_codes(self.h, ptr(c, u8p), c.shape[0]))
+
+    def size(self):
+        return int(load().scann_hip_stacked_size(self.h))
+
+    def distances(self, queries):
+        """[nq, n] float32: the scan and the measure alone"""
+        q, nq, stride = _rows2d(queries, self.dim, "queries")
+        out = np.empty((nq, self.size()), np.float32)
+        check(load().scann_hip_stacked_distances(self.h, ptr(q, f32p), nq, stride, ptr(out if out.size else np.empty(1, np.float32), f32p)))
+        return out
+
+    def search_batched(self, queries, k, allow=None, allow_bits=None):
+        """allow: one uint64 bitmap for the batch, as SparseIndex.search_batched's.  (idx [nq, k] uint32, dist [nq, k]
+        float32, count [nq] uint32); slots past count hold 0xFFFFFFFF / NaN."""
+        q, nq, stride = _rows2d(queries, self.dim, "queries")
+        idx, dist = np.empty((nq, k), np.uint32), np.empty((nq, k), np.float32)
+        cnt = np.zeros(nq, np.uint32)
+        words = None if allow is None else np.ascontiguousarray(allow, np.uint64).ravel()
+        bits = 0 if words is None else (words.size * 64 if allow_bits is None else int(allow_bits))
+        if words is not None and bits > words.size * 64:
+            raise ValueError("allow_bits %d exceeds the %d bits given" % (bits, words.size * 64))
+        if words is not None and words.size == 0:
+            words = np.zeros(1, np.uint64)
+        check(load().scann_hip_stacked_search_batched(self.h, ptr(q, f32p), nq, stride, int(k), ptr(words, u64p), bits,
+                                                      ptr(idx, u32p), ptr(dist, f32p), ptr(cnt, u32p)))
+        return idx, dist, cnt
+
+    def info(self):
+        """{'levels', 'T', 'device_bytes', 'tile_rows'} and of the last scan {'slabs', 'chunk_rows', 'chunks', 'quads', 'groups'}"""
+        p = np.zeros(9, np.uint64)
+        load().scann_hip_stacked_info(self.h, ptr(p, u64p))
+        return dict(zip(("levels", "T", "device_bytes", "tile_rows", "slabs", "chunk_rows", "chunks", "quads", "groups"),
+                        (int(x) for x in p)))
+
+    def last_kernel_ms(self):
+        """(encode, table build, scan, merge) ms of the last encode / set_rows and of the last search"""
+        ms = np.zeros(4, np.float32)
+        load().scann_hip_stacked_last_kernel_ms(self.h, ptr(ms, f32p))
+        return tuple(float(x) for x in ms)
 
 
 def _attr_columns(n, columns):

@@ -98,6 +98,28 @@ def encode(codebook, R, chunk=65536):
     return codes
 
 
+def decode(codebook, codes):
+    """Codebook::decode (hashes/codebook.rs): the chosen centroids side by side, [n, S * dsub]."""
+    codebook = np.ascontiguousarray(codebook, np.float32)
+    return codebook[np.arange(codebook.shape[0])[None, :], codes].reshape(codes.shape[0], -1)
+
+
+def train_stacked(X, subspaces, codes, iters=10, seed=42, sample=65536):
+    """StackedQuantizer::train (hashes/stacked.rs:81-128; AdditiveQuantizer::train is subspaces = (1, ..., 1)): per
+    level a codebook trained on the current residuals (seed + level), then residual = residual - decode(encode(residual)),
+    one f32 subtraction per element.  Returns (codebooks: one f32 [S_l, K_l, dim / S_l] per level, the arrays of
+    hip.StackedIndex; the final residuals [n, dim])."""
+    R = np.ascontiguousarray(X, np.float32)
+    if len(subspaces) != len(codes) or not len(codes):
+        raise ValueError("InvalidArgument: one subspace count and one code count per level")
+    books = []
+    for level, (S, K) in enumerate(zip(subspaces, codes)):
+        cb = train_codebook(R, S, K, iters=iters, seed=seed + level, sample=sample)
+        R = R - decode(cb, encode(cb, R))
+        books.append(cb)
+    return books, R
+
+
 def pack4(codes):
     """PackedCodes4Bit::from_codes (hashes/lut16.rs:43-61): byte j =
     code[2j] | code[2j+1] << 4; odd S pads the last high nibble with 0."""
